@@ -15,9 +15,17 @@ the 8 run counters at the end of every step (RCCL over xGMI).
 
 Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel
 (k_emit_philox in the default counter mode): algorithmic bytes per launch / its
-HIP-event duration measured on the engine's stream.  `cpu_baseline` is the CPU oracle (a port of the
-reference algorithm; the Rust reference cannot be built here) timed on this
-host on a bounded sample of the same workload.
+HIP-event duration measured on the engine's stream.
+
+A plain run sets up, warms up, times the --steps steps and prints the line.  `--full` adds
+what takes runs of its own: the untimed side measurements (the other rng mode, layout and
+plan, the plan overlap, the FASTQ text), `reference_toolchain`, and `cpu_baseline`, the CPU
+oracle (a port of the reference algorithm; the Rust reference cannot be built here) timed
+on this host on a bounded sample of the same workload.
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float32 /
+float64; a fixed, seeded sample of a large shard, see dump_outputs), so that two builds can
+be compared output for output.
 """
 import argparse
 import json
@@ -94,7 +102,15 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo only for rehearsing N>1 on a single GPU (all ranks then share --rehearse-device)")
     ap.add_argument("--rehearse-device", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements (--no-other-mode turns them off), reference_toolchain and cpu_baseline "
+                         "(--no-cpu-baseline turns it off); a plain run times the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                         "at most ~45 MB: a fixed, seeded sample of a larger shard)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: nothing but the headline figure
+        args.no_other_mode = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # started plainly with --gpus N: this process has touched no device yet and never will
@@ -278,6 +294,12 @@ def main():
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
+    if args.dump_outputs:  # (before the side measurements, which emit into the same buffers)
+        prefix = f"rank{rank}_" if world > 1 else ""
+        if args.through_fastq:
+            dump_outputs(args.dump_outputs, prefix, counters_dev, text=fq["text"][:fq["bytes"]])
+        else:
+            dump_outputs(args.dump_outputs, prefix, counters_dev, reads=out)
 
     # untimed side measurement of the other rng mode on the same shard (N = 1 only)
     other = None
@@ -533,7 +555,8 @@ def main():
         dist.destroy_process_group()
     if rank == 0:
         # the CPU leg runs on rank 0 after the ranks have parted (nobody waits in a collective while it runs)
-        result["reference_toolchain"] = reference_toolchain()
+        if args.full:
+            result["reference_toolchain"] = reference_toolchain()
         if not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline_long(args, prof) if long_mode else cpu_baseline(args, prof)
         print(json.dumps(result), flush=True)
@@ -545,6 +568,69 @@ def text_kernel_label(args):
     if os.environ.get("SIMMR_TEXT_FORM") == "2" and args.profile in ("minimal-short", "perfect-short"):
         return "k_emit_text_lines<COPY_ONLY>" if args.profile == "perfect-short" else "k_emit_text_lines"
     return "k_emit_philox<COPY_ONLY, TEXT>" if args.profile == "perfect-short" else "k_emit_philox<TEXT>"
+
+
+DUMP_READS = 1 << 17  # per-read columns of at most this many reads ...
+DUMP_BYTES = 1 << 21  # ... and bases / qualities / FASTQ text at most this many positions: ~45 MB in all
+
+
+def _sample(n, k, seed):
+    """sorted indices of a fixed sample of k of range(n) (all of them when n <= k): a function of (n, k, seed) alone"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, prefix, counters_dev, reads=None, text=None):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as <path>/<prefix><name>.npy.
+    Integers that a float32 holds exactly (bases, qualities, text bytes) are float32, everything else float64.
+
+    counters    the run counters (include/simmr_hip.h, SIMMR_CNT_*)
+    columns (reads): the layout Reads.to_host() hands out, compact whichever layout the kernel wrote —
+    read_index  the sampled reads (all of them up to DUMP_READS; above, a fixed seeded sample)
+    read_{start,end,contig,genome,id,flags,length,seq_off}   their columns, seq_off = first base in the compact streams
+    base_index  the sampled positions of the compact seq / qual streams (likewise, DUMP_BYTES)
+    seq, qual   the bytes there
+    FASTQ text (text): text_bytes, text_index (sampled byte positions), text (the bytes there)"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+
+    def save(name, a, dtype):
+        a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        np.save(os.path.join(path, prefix + name + ".npy"), a.astype(dtype))
+
+    save("counters", counters_dev, np.float64)
+    if text is not None:
+        idx = torch.from_numpy(_sample(text.numel(), DUMP_BYTES, 2)).to(text.device)
+        save("text_bytes", [text.numel()], np.float64)
+        save("text_index", idx, np.float64)
+        save("text", text[idx], np.float32)
+        return
+    n = reads.n_reads
+    if reads.slot_bytes == 16:  # a read's length is |end - start|; seq starts at seq_off, qual at seq_off & ~15
+        lens = (reads.end[:n] - reads.start[:n]).abs()
+        off = torch.zeros(n + 1, dtype=torch.int64, device=lens.device)
+        torch.cumsum(lens, 0, out=off[1:])
+        first_seq = reads.seq_off[:n]
+        first_qual = first_seq & ~15
+    else:  # compact: seq_off is the CSR offset of both streams
+        off = reads.seq_off[:n + 1]
+        lens = off[1:] - off[:-1]
+        first_seq = first_qual = off[:n]
+    ri =torch.from_numpy(_sample(n, DUMP_READS, 0)).to(lens.device)
+    save("read_index", ri, np.float64)
+    for name, col in (("start", reads.start), ("end", reads.end), ("contig", reads.contig), ("genome", reads.genome),
+                      ("id", reads.read_id), ("flags", reads.flags), ("length", lens), ("seq_off", off)):
+        save("read_" + name, col[ri], np.float64)
+    total = int(off[n] - off[0])
+    p = torch.from_numpy(_sample(total, DUMP_BYTES, 1)).to(lens.device) + off[0]
+    r = torch.searchsorted(off[1:].contiguous(), p, right=True)  # the read each position lies in
+    within = p - off[r]
+    save("base_index", p, np.float64)
+    save("seq", reads.seq[first_seq[r] + within], np.float32)
+    save("qual", reads.qual[first_qual[r] + within], np.float32)
 
 
 PMC_RECORD = ROOT / "profiles" / "r5" / "pmc_traffic.json"

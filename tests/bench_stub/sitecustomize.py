@@ -79,6 +79,9 @@ def _install():
             out.seq_off[:n + 1] = torch.from_numpy(h["seq_off"].astype(np.int64))
             out.start[:n] = torch.from_numpy(h["start"].astype(np.int64))
             out.end[:n] = torch.from_numpy(h["end"].astype(np.int64))
+            for col in ("contig", "genome", "read_id"):
+                getattr(out, col)[:n] = torch.from_numpy(h[col].astype(np.int32))
+            out.flags[:n] = torch.from_numpy(h["flags"].astype(np.uint8))
             acgt = int(np.isin(h["seq"], np.frombuffer(b"ACGT", np.uint8)).sum())
             self.cnt[_abi.CNT_READS] += n
             self.cnt[_abi.CNT_BASES] += tb

@@ -5,7 +5,7 @@ tag="${1:-r5}"; out="gpurun_out/prof_$tag"; mkdir -p "$out"
 export TMPDIR=/tmp
 stats() {  # name, bench args...
   name="$1"; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/$name" -o t -- python3 bench.py --no-cpu-baseline --no-overlap-side "$@" > "$out/${name}_bench.log" 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/$name" -o t -- python3 bench.py --full --no-cpu-baseline --no-overlap-side "$@" > "$out/${name}_bench.log" 2>&1
   f=$(find "$out/$name" -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp "$f" "$out/kernel_stats_$name.csv"
   grep '^{"metric"' "$out/${name}_bench.log" | tail -1 > "$out/bench_${name}_under_rocprof.json"  # (rocprofv3 logs after it)
@@ -21,7 +21,7 @@ SIMMR_TEXT_FORM=2 stats bench_through_fastq_whole_lines --through-fastq --no-oth
 S="FETCH_SIZE;WRITE_SIZE;SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES;SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU;SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD;GRBM_GUI_ACTIVE SQ_BUSY_CYCLES"
 tools/pmc_cmd.sh "prof_$tag/pmc_default" "k_emit_philox<false, false, true, false" "$S" -- python3 bench.py --no-cpu-baseline --no-other-mode --steps 1 --warmup 0 > "$out/pmc_default.txt"
 tools/pmc_cmd.sh "prof_$tag/pmc_compact" "k_emit_philox<false, false, true, false" "FETCH_SIZE;WRITE_SIZE;SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES;SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES SQ_WAIT_ANY" -- python3 bench.py --no-cpu-baseline --no-other-mode --layout compact --steps 1 --warmup 0 > "$out/pmc_compact.txt"
-tools/pmc_cmd.sh "prof_$tag/pmc_perfect" k_emit_perfect_pe "FETCH_SIZE;WRITE_SIZE;SQ_INSTS_VALU SQ_WAVES" -- python3 bench.py --no-cpu-baseline --profile perfect-short --steps 1 --warmup 0 > "$out/pmc_perfect.txt"
+tools/pmc_cmd.sh "prof_$tag/pmc_perfect" k_emit_perfect_pe "FETCH_SIZE;WRITE_SIZE;SQ_INSTS_VALU SQ_WAVES" -- python3 bench.py --full --no-cpu-baseline --profile perfect-short --steps 1 --warmup 0 > "$out/pmc_perfect.txt"
 tools/pmc_cmd.sh "prof_$tag/pmc_custom_long" k_custom_long_splice "FETCH_SIZE;WRITE_SIZE;SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES;SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS" -- python3 bench.py --no-cpu-baseline --no-other-mode --profile custom-long --reads 1000000 --steps 1 --warmup 0 > "$out/pmc_custom_long.txt"
 tools/pmc_cmd.sh "prof_$tag/pmc_custom_long_reference" k_custom_long_splice "FETCH_SIZE;WRITE_SIZE;SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES;SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS" -- python3 bench.py --no-cpu-baseline --no-other-mode --profile custom-long --rng reference --reads 1000000 --steps 1 --warmup 0 > "$out/pmc_custom_long_reference.txt"
 # (the TEXT form only: <HAS_EXC, COPY_ONLY, CACHED, TEXT, ...> = <false, false, true, true, ...>; the command's one column launch is left out)
