@@ -88,16 +88,28 @@ SIMMR_DEV uint32_t wg_exclusive_scan_u32(uint32_t v, uint32_t* lds4, uint32_t* t
 SIMMR_DEV uint32_t wg_exclusive_scan_u32(uint32_t v, uint32_t* lds4, uint32_t* total) {
   return wg_exclusive_scan_u32(v, lds4, total, threadIdx.x);
 }
+// inclusive scan of one u32 over a whole wave (every lane active): four DPP row shifts and the two GFX9 row broadcasts,
+// one v_add with a DPP source each — where __shfl_up costs a ds_bpermute, its address and a select per step
+SIMMR_DEV uint32_t wave_inclusive_scan_u32(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);   // row_shr:1
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);   // row_shr:2
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);   // row_shr:4
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);   // row_shr:8
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 into rows 1 and 3
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 into rows 2 and 3
+  return v;
+}
+// base[i] for a base the whole wave shares and a 32-bit index: the address is the scalar base plus a zero-extended 32-bit
+// byte offset, the global_load / global_store form with an SGPR base (saddr) — no 64-bit address arithmetic per lane.
+// (i * sizeof(T) must stay below 2^32: block-relative indices)
+template <class T>
+SIMMR_DEV T& lane_at(T* base, uint32_t i) { return *(T*)((const char*)base + i * (uint32_t)sizeof(T)); }
 // two 32-bit values scanned together (one barrier): v = lo | hi << 32, no carry from lo into hi as long as the
-// workgroup's sum of lo stays below 2^32; lds4: four u64
+// workgroup's sum of lo stays below 2^32; lds4: four u64.  Called by all 256 threads (the wave scans are DPP).
 SIMMR_DEV uint64_t wg_exclusive_scan_2x32(uint64_t v, uint64_t* lds4, uint64_t* total, uint32_t tid) {
-  const uint32_t lane = tid & 63u, wave = tid >> 6;
-  uint64_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t o = __shfl_up(inc, d, 64);
-    if (lane >= (uint32_t)d) inc += o;
-  }
+  const uint32_t lane = tid & 63u, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // (the wave's number is uniform)
+  // the halves scanned apart: the same sums as one 64-bit scan while lo does not carry (see above)
+  const uint64_t inc = (uint64_t)wave_inclusive_scan_u32((uint32_t)v) | ((uint64_t)wave_inclusive_scan_u32((uint32_t)(v >> 32)) << 32);
   if (lane == 63) lds4[wave] = inc;
   lds_barrier();
   const uint64_t t0 = lds4[0], t1 = lds4[1], t2 = lds4[2], t3 = lds4[3];
@@ -2082,19 +2094,31 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
     uint32_t h_L = 0, h_genome = 0, h_contig = 0, h_flags = 0;
     if (tix < nr) {
       const uint32_t t = tix;
-      const uint64_t u = u0 + (paired ? (t >> 1) : t);
+      // Every column is read and written as block base + lane offset (lane_at): u = u0 + ui, rd = rpu * u0 + t
+      const uint32_t ui = paired ? (t >> 1) : t;  // the unit's index in the block
+      const uint64_t u = u0 + ui;
       const uint32_t rev = paired ? (t & 1u) : 0u;
-      const uint32_t L = PL(pl.len[u]);
+      const uint32_t L = PL(lane_at(pl.len + u0, ui));
       g = (L + 15u) >> 4;
-      const uint32_t contig = PL(u_contig[u]);
-      const uint32_t genome = (!CACHED && u_genome) ? u_genome[u] : genome_const;
-      const uint64_t rd = paired ? 2 * u + rev : u;
+      const uint32_t contig = PL(lane_at(u_contig + u0, ui));
+      const uint32_t genome = (!CACHED && u_genome) ? lane_at(u_genome + u0, ui) : genome_const;
+      const uint64_t rd0 = rpu * u0;  // the block's first read
+      const uint64_t rd = rd0 + t;
       const uint32_t Lp = SLOT ? ((L + 15u) & ~15u) : L;  // the read's place in the streams
       const uint64_t my_rec = TEXT ? out0 + rec_place : 0u;
-      const uint64_t dst = TEXT ? my_rec + hlen[rd] + 1u : (coarse ? out0 : u_off[u] + (rev ? Lp : 0u));  // (coarse: after the scan below)
+      const uint64_t dst = TEXT ? my_rec + lane_at(hlen + rd0, t) + 1u : (coarse ? out0 : lane_at(u_off + u0, ui) + (rev ? Lp : 0u));  // (coarse: after the scan below)
       my_Lp = Lp; my_pad = (SLOT && rev) ? Lp - L : 0u; my_rd = rd; my_dst = dst;
-      const uint64_t pos = rev ? PL(pl.b[u]) : PL(pl.a[u]);  // first source base of this read on the contig
-      const uint64_t key = COPY_ONLY ? 0ull : (rev ? PL(pl.qs2[u]) : PL(u_seed[u]));  // (no draws, no key; qs2 may not exist)
+      // (both mates load both columns and keep their own: a per-lane choice of base would be per-lane address arithmetic;
+      // unpaired, the second base is the first again — every column read here exists)
+      const uint64_t* const b_col = paired ? pl.b : pl.a;
+      const uint64_t pos_a = PL(lane_at(pl.a + u0, ui)), pos_b = PL(lane_at(b_col + u0, ui));
+      const uint64_t pos = rev ? pos_b : pos_a;  // first source base of this read on the contig
+      uint64_t key = 0;  // (COPY_ONLY: no draws, no key; qs2 may not exist)
+      if (!COPY_ONLY) {
+        const uint64_t* const k_col = paired ? pl.qs2 : u_seed;
+        const uint64_t key_a = PL(lane_at(u_seed + u0, ui)), key_b = PL(lane_at(k_col + u0, ui));
+        key = rev ? key_b : key_a;
+      }
       uint64_t cb;
       const uint32_t* packed;
       const uint32_t* mk = nullptr;
@@ -2123,28 +2147,29 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       if (FULL) {
 #endif
         // metadata columns of this read (the other emit kernels leave them to k_write_meta)
-        const uint32_t fl = PL(pl.flags[u]);
+        const uint32_t fl = PL(lane_at(pl.flags + u0, ui));
         if (TEXT) { h_pos = pos; h_L = L; h_genome = genome; h_contig = contig; h_flags = (paired && !rev) ? 0u : fl; h_rec = my_rec; }
         if (!TEXT) {
           if (paired) {
-            if (o.start) COL_STORE(&o.start[rd], (uint64_t)(rev ? pos + L : pos));  // simulate.rs:289,295
-            if (o.end) COL_STORE(&o.end[rd], (uint64_t)(rev ? pos : pos + L));      // simulate.rs:290,296
+            if (o.start) COL_STORE(&lane_at(o.start + rd0, t), (uint64_t)(rev ? pos + L : pos));  // simulate.rs:289,295
+            if (o.end) COL_STORE(&lane_at(o.end + rd0, t), (uint64_t)(rev ? pos : pos + L));      // simulate.rs:290,296
           } else {
-            if (o.start) COL_STORE(&o.start[rd], (uint64_t)pos);                  // simulate.rs:515
-            if (o.end) COL_STORE(&o.end[rd], (uint64_t)pl.b[u]);                  // simulate.rs:516
+            if (o.start) COL_STORE(&lane_at(o.start + rd0, t), (uint64_t)pos);                  // simulate.rs:515
+            if (o.end) COL_STORE(&lane_at(o.end + rd0, t), (uint64_t)lane_at(pl.b + u0, ui));  // simulate.rs:516
           }
-          if (o.contig) COL_STORE(&o.contig[rd], contig);
-          if (o.genome) COL_STORE(&o.genome[rd], genome);
-          if (o.read_id) COL_STORE(&o.read_id[rd], read_id_base + (uint32_t)(first_unit + u));  // simulate.rs:85-89,274
-          if (o.flags) COL_STORE(&o.flags[rd], (paired && !rev) ? (uint8_t)0 : (uint8_t)fl);
+          if (o.contig) COL_STORE(&lane_at(o.contig + rd0, t), contig);
+          if (o.genome) COL_STORE(&lane_at(o.genome + rd0, t), genome);
+          if (o.read_id) COL_STORE(&lane_at(o.read_id + rd0, t), read_id_base + (uint32_t)(first_unit + u));  // simulate.rs:85-89,274
+          if (o.flags) COL_STORE(&lane_at(o.flags + rd0, t), (paired && !rev) ? (uint8_t)0 : (uint8_t)fl);
         }
         if (!rev) {
           p_bases32 += paired ? 2u * L : L;  // (a pair's reads are u16 lengths; a long read can be longer: the sum moves to LDS at 2^31 either way)
           if (p_bases32 >= 0x80000000u) { atomicAdd(&spill_bases, (unsigned long long)p_bases32); p_bases32 = 0u; }
         }
-        s_redrawn += (uint32_t)__builtin_popcountll(__ballot(!rev && (fl & SIMMR_FLAG_REDRAWN)));
-        s_seedsubst += (uint32_t)__builtin_popcountll(__ballot(!rev && (fl & SIMMR_FLAG_QSEED_SUBST))) +
-                       (uint32_t)__builtin_popcountll(__ballot(!rev && (fl & SIMMR_FLAG_MSEED_SUBST)));
+        const uint32_t fl1 = rev ? 0u : fl;  // (each pair's flags counted once)
+        s_redrawn += (uint32_t)__builtin_popcountll(__ballot((fl1 & SIMMR_FLAG_REDRAWN) != 0u));
+        s_seedsubst += (uint32_t)__builtin_popcountll(__ballot((fl1 & SIMMR_FLAG_QSEED_SUBST) != 0u)) +
+                       (uint32_t)__builtin_popcountll(__ballot((fl1 & SIMMR_FLAG_MSEED_SUBST) != 0u));
       }
     }
     if (TEXT) {
@@ -2213,7 +2238,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
     }
 #if !defined(SIMMR_ABLATE_META)
     if (!TEXT && !COPY_ONLY && tix < nr) {
-      COL_STORE(&o.seq_off[my_rd], (uint64_t)(my_dst + my_pad));  // first base (SLOT: a reverse mate's bases are right-aligned)
+      COL_STORE(&lane_at(o.seq_off + rpu * u0, tix), (uint64_t)(my_dst + my_pad));  // first base (SLOT: a reverse mate's bases are right-aligned)
       if (my_rd + 1 == n_reads) o.seq_off[n_reads] = coarse ? off64[(n_units + 63u) >> 6] : u_off[n_units];  // closing CSR offset
     }
 #endif
