@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 
 from simmr_amd import MinimalLongErrorProfile, MinimalShortErrorProfile, PerfectShortErrorProfile, SimmrError, _abi
-from tests import _synth
+from tests import _fastq, _synth
 from tests.test_gpu_cli import FMT
 
 pytestmark = pytest.mark.gpu
@@ -29,24 +29,7 @@ def genome_multi(engine):
 
 def _check(engine, reads, names, fmt, paired):
     got = engine.fastq(reads, fmt, names, paired).cpu().numpy().tobytes()
-    d = reads.to_host()
-    by_slot = {slot: (gid, sids) for slot, gid, sids in names}
-    want = bytearray()
-    for r in range(reads.n_reads):
-        gid, sids = by_slot[int(d["genome"][r])]
-        h = fmt  # fastq.rs:34-56: the replace calls in the reference's order
-        for k, v in (("{:genome_id:}", gid), ("{:read_id:}", str(int(d["read_id"][r]))),
-                     ("{:sequence_id:}", sids[int(d["contig"][r])]), ("{:start_position:}", str(int(d["start"][r]))),
-                     ("{:end_position:}", str(int(d["end"][r]))), ("{:reverse_complement:}", "t" if d["flags"][r] & 1 else "f"),
-                     ("{:pair:}", "2" if (paired and r & 1) else "1")):
-            h = h.replace(k, v)
-        a, b = int(d["seq_off"][r]), int(d["seq_off"][r + 1])
-        want += h.encode() + b"\n" + d["seq"][a:b].tobytes() + b"\n+\n" + d["qual"][a:b].tobytes() + b"\n"
-    assert len(got) == len(want)
-    if got != bytes(want):
-        g, w = np.frombuffer(got, np.uint8), np.frombuffer(bytes(want), np.uint8)
-        i = int(np.flatnonzero(g != w)[0])
-        raise AssertionError(f"first difference at byte {i}: {got[max(0, i - 60):i + 20]!r} vs {bytes(want)[max(0, i - 60):i + 20]!r}")
+    _fastq.assert_same_text(got, _fastq.expected_text(reads.to_host(), names, fmt, paired, 0, reads.n_reads))
 
 
 @pytest.mark.parametrize("fmt", [

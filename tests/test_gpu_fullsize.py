@@ -366,3 +366,138 @@ def test_whole_line_text_is_the_item_form_text_at_full_size(big):
     # structure: 4 lines per record; one '@' line start and one "\n+\n" per record at least (quality bytes may also be '@' or '+')
     n_nl = sum(int((b[lo:lo + step] == 10).sum()) for lo in range(0, b.numel(), step))
     assert n_nl == 4 * N_READS and int(b[0]) == ord("@") and int(b[-1]) == 10
+
+
+# ---- windows of the full-size run against the CPU oracle, bit for bit ----------------------------------------------------------
+# The oracle takes first / count, so any 512 pairs of the 100 M-read run can be had on the host: under SIMMR_RNG_PHILOX_FULL
+# the pair's index alone decides the pair, under SIMMR_RNG_PHILOX the oracle walks the outer stream to `first` (seconds).
+# The properties above pass an error that the whole run and its shards make alike; these windows do not, and they lie where
+# the offsets pass multiples of 2^32 and where a workgroup is in its twelfth block.
+WINDOW = 512
+NAMES_5 = [(5, "0b5e3c9e-7d1c-4c1a-9c55-2f7d3a1b6e42", ["synthetic_100Mbp"])]
+
+
+@pytest.fixture(scope="module")
+def host_genome(big):
+    """the 100 Mbp synthetic genome on the host (chunked: no 8-byte intermediate per base), checked against the staged one"""
+    from tests import _oracle, _synth
+    contig = _synth.synthetic_contigs_chunked([GENOME], 2)[0]
+    for a, n in ((0, 4096), (33_554_400, 5000), (GENOME // 2 - 17, 70_001), (GENOME - 3000, 3000)):
+        assert np.array_equal(big.unstage(5, 0, a, n), contig[a:a + n]), a
+    return _oracle.HostGenome([contig])
+
+
+def place_windows(pair_at, n_pairs, total):
+    """[(what, first pair, pairs)]: pair 0; around every multiple of 2^32 of the stream (`pair_at`: device column, first byte
+    of each pair, the stream's end last); a block boundary in the twelfth trip of the default grid; the last 300 pairs"""
+    import torch
+    wins = [("pair 0", 0, WINDOW)]
+    k = 1
+    while (k << 32) < total:
+        at = torch.tensor([k << 32], dtype=pair_at.dtype, device=pair_at.device)
+        p = int(torch.searchsorted(pair_at, at)[0])  # the first pair that starts at or after k * 2^32
+        w = p - 200
+        assert int(pair_at[w]) < (k << 32) < int(pair_at[w + WINDOW]), f"the window does not straddle {k} * 2^32"
+        wins.append((f"{k} * 2^32", w, WINDOW))
+        k += 1
+    assert k > 1, "no offset of this run passes 2^32"
+    # engine.hip: grid = min(blocks, n_cu * 128) workgroups of the item kernel; block b is trip b // grid of its workgroup
+    n_cu = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    grid = min(-(-n_pairs // 128), n_cu * 128)
+    w = 128 * (32768 * 11) - 200
+    assert (w + 200) % 128 == 0 and w % 128 != 0 and (w + 200) // 128 >= 11 * grid and w + WINDOW <= n_pairs, \
+        "not a block boundary of a twelfth trip: resize for this device"
+    wins.append(("twelfth trip", w, WINDOW))
+    wins.append(("last 300 pairs", n_pairs - 300, 300))
+    return wins
+
+
+def assert_window_metadata(run, ora, w, cnt, what):
+    lo, hi = 2 * w, 2 * (w + cnt)
+    for col in ("start", "end", "contig", "read_id", "flags"):
+        got = getattr(run, col)[lo:hi].cpu().numpy().astype(ora[col].dtype)
+        assert np.array_equal(got, ora[col]), f"{what}: {col}, first at read {lo + int(np.flatnonzero(got != ora[col])[0])}"
+
+
+@pytest.mark.parametrize("rng_mode", [_abi.RNG_PHILOX_FULL, _abi.RNG_PHILOX], ids=["philox-full", "philox"])
+def test_c2_full_size_windows_match_the_oracle(big, oracle, host_genome, rng_mode):
+    """The whole run on the default engine (the default grid: twelve blocks per workgroup), compact layout; windows of 512
+    pairs copied out and compared with the oracle's same pairs: bases, qualities, offsets, every metadata column."""
+    from tests import _oracle
+    prof = MinimalShortErrorProfile(rng_mode=rng_mode).pod()
+    whole = big.simulate_pe_reads_from_genome(5, prof, N_READS, 42, qual_offset=33)
+    n, tb = whole.n_reads, whole.total_bases
+    assert n == N_READS and whole.slot_bytes == 0
+    off = whole.seq_off[: n + 1]
+    for what, w, cnt in place_windows(off[0::2].contiguous(), n // 2, tb):
+        ora = _oracle.simulate_pe(oracle, host_genome, prof, N_READS, 42, first=w, count=cnt, qual_offset=33).trimmed()
+        lo, hi = 2 * w, 2 * (w + cnt)
+        a, b = int(off[lo]), int(off[hi])
+        assert np.array_equal((off[lo:hi + 1] - a).cpu().numpy().astype(np.uint64), ora["seq_off"]), what
+        assert_window_metadata(whole, ora, w, cnt, what)
+        for col in ("seq", "qual"):
+            got = getattr(whole, col)[a:b].cpu().numpy()
+            assert got.shape == ora[col].shape, what
+            assert np.array_equal(got, ora[col]), f"{what}: {col}, first at byte {a + int(np.flatnonzero(got != ora[col])[0])}"
+    assert int(off[n]) == tb > 3 << 32
+
+
+def test_c2_full_size_slot16_windows_match_the_oracle(big, oracle, host_genome):
+    """The same windows of the 16-byte slot layout (the benchmark's): a read's slot is ceil(L / 16) * 16 bytes, forward bases
+    and all qualities left-aligned, a reverse mate's bases right-aligned, padding 0 (include/simmr_hip.h) — the expected slot
+    bytes are rebuilt from the oracle's reads and the whole slot range is compared, padding included."""
+    from tests import _oracle
+    prof = MinimalShortErrorProfile(rng_mode=_abi.RNG_PHILOX_FULL).pod()
+    big.set_read_slots(16)
+    try:
+        run = big.simulate_pe_reads_from_genome(5, prof, N_READS, 42, qual_offset=33)
+    finally:
+        big.set_read_slots(0)
+    n, tb = run.n_reads, run.total_bases
+    assert n == N_READS and run.slot_bytes == 16
+    first = run.seq_off[: n + 1]
+    for what, w, cnt in place_windows((first[0::2] & ~15).contiguous(), n // 2, tb):
+        ora = _oracle.simulate_pe(oracle, host_genome, prof, N_READS, 42, first=w, count=cnt, qual_offset=33).trimmed()
+        lo, hi = 2 * w, 2 * (w + cnt)
+        o_off = ora["seq_off"].astype(np.int64)
+        L = np.diff(o_off)
+        Lp = (L + 15) // 16 * 16
+        place = np.zeros(hi - lo + 1, dtype=np.int64)
+        np.cumsum(Lp, out=place[1:])
+        rev = (ora["flags"] & _abi.FLAG_REVCOMP) != 0
+        base_at = place[:-1] + np.where(rev, Lp - L, 0)
+        a = int(first[lo]) & ~15
+        b = a + int(place[-1])
+        assert b == ((int(first[hi]) & ~15) if hi < n else tb), what
+        assert np.array_equal((first[lo:hi] - a).cpu().numpy().astype(np.int64), base_at), what  # seq_off: a read's first base
+        assert_window_metadata(run, ora, w, cnt, what)
+        within = np.arange(int(o_off[-1]), dtype=np.int64) - np.repeat(o_off[:-1], L)
+        want_s = np.zeros(int(place[-1]), dtype=np.uint8)
+        want_q = np.zeros(int(place[-1]), dtype=np.uint8)
+        want_s[np.repeat(base_at, L) + within] = ora["seq"]
+        want_q[np.repeat(place[:-1], L) + within] = ora["qual"]
+        for col, want in (("seq", want_s), ("qual", want_q)):
+            got = getattr(run, col)[a:b].cpu().numpy()
+            assert np.array_equal(got, want), f"{what}: {col}, first at byte {a + int(np.flatnonzero(got != want)[0])}"
+
+
+def test_c2_full_size_text_head_and_tail_match_the_oracle(big, oracle, host_genome):
+    """The FASTQ text of the same run straight from the plan (44.7 GB): the first 512 pairs' records, and the last 300 pairs'
+    up to the last byte of the text — beyond every multiple of 2^32 the text has, in the last trip of the block loop —
+    against text built on the host from the ORACLE's columns."""
+    from tests import _fastq, _oracle
+    from tests.test_gpu_cli import FMT
+    prof = MinimalShortErrorProfile(rng_mode=_abi.RNG_PHILOX_FULL).pod()
+    assert big.pe_plan(5, prof, N_READS, 42).n_reads == N_READS
+    text = big.fastq_direct(FMT, NAMES_5, 0)
+    n_pairs = N_READS // 2
+    for what, w, cnt in (("head", 0, WINDOW), ("tail", n_pairs - 300, 300)):
+        ora = _oracle.simulate_pe(oracle, host_genome, prof, N_READS, 42, first=w, count=cnt, qual_offset=33).trimmed()
+        ora["genome"][:] = 5
+        want = _fastq.expected_text(ora, NAMES_5, FMT, True)
+        if what == "head":
+            got = text[: len(want)]
+        else:
+            assert text.numel() - len(want) > (text.numel() >> 32) << 32 > 0, "the tail does not lie beyond the last multiple of 2^32"
+            got = text[text.numel() - len(want):]
+        _fastq.assert_same_text(got.cpu().numpy().tobytes(), want, what + ": ")

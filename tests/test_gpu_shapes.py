@@ -335,7 +335,24 @@ def test_results_do_not_depend_on_the_grid(engine, monkeypatch, knobs):
     """The emit kernels are grid-stride loops whose launch size is a tuning knob ("the grid"), and the
     run counters are summed from per-workgroup rows: reads, metadata and counters must be the same for one workgroup per
     CU, for an odd number, and for one block per workgroup — both generators, both layouts of the counter mode,
-    perfect-short, long reads, and the FASTQ text straight from the plan."""
+    perfect-short, long reads, and the FASTQ text straight from the plan.
+    The runs are sized from the item kernel's grid, min(blocks of 128 units, n_cu * SIMMR_PHILOX_WGS_PER_CU) (engine.hip;
+    tests/test_host.py pins the line): with 1 and 7 workgroups per CU the engine under test launches at most a third of the
+    blocks as workgroups — every workgroup loops three times or more — while the default engine (128 per CU) launches one
+    workgroup per block.  4096 per CU against the default 128 cannot differ below 4.2 M pairs: that parameter set keeps its
+    small size and pins the other end, one block per workgroup on both engines."""
+    import torch
+    n_cu = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    wgs = int(knobs["SIMMR_PHILOX_WGS_PER_CU"])
+    count = 29_000 if wgs == 4096 else 128 * 3 * wgs * n_cu + 77
+    blocks = -(-count // 128)
+    grids = (min(blocks, n_cu * 128), min(blocks, n_cu * wgs))  # the default engine's, the other's
+    if wgs == 4096:
+        assert grids[0] == grids[1] == blocks
+    else:
+        assert grids[0] != grids[1] and 3 * min(grids) <= blocks, (grids, blocks)
+    total = 2 * (count + 7) + 2001
+    n_long = 900 if wgs == 4096 else count  # (a long-read plan's unit is the read)
     from simmr_amd import MinimalLongErrorProfile, PerfectShortErrorProfile
     from simmr_amd.engine import Engine
     for k, v in knobs.items():
@@ -355,9 +372,9 @@ def test_results_do_not_depend_on_the_grid(engine, monkeypatch, knobs):
                 eng.set_read_slots(slot)
                 try:
                     eng.counters_reset()
-                    r = eng.simulate_pe_reads_from_genome(21, prof, 60_001, 5, first=7, count=29_000, read_id_base=3, qual_offset=33)
+                    r = eng.simulate_pe_reads_from_genome(21, prof, total, 5, first=7, count=count, read_id_base=3, qual_offset=33)
                     c = eng.counters()
-                    eng.pe_plan(21, prof, 60_001, 5, 7, 29_000)
+                    eng.pe_plan(21, prof, total, 5, 7, count)
                     text = eng.fastq_direct("@{:read_id:}/{:pair:} {:sequence_id:} {:start_position:}", names, 3).cpu().numpy().tobytes() if slot == 0 else b""
                 finally:
                     eng.set_read_slots(0)
@@ -371,11 +388,13 @@ def test_results_do_not_depend_on_the_grid(engine, monkeypatch, knobs):
             else:
                 from tests.test_gpu_parity import assert_same
                 assert_same(a, b)
-        lp = MinimalLongErrorProfile(gamma_mean=3000.0, gamma_std=2500.0, length_mode=_abi.LEN_PER_READ, rng_mode=_abi.RNG_PHILOX).pod()
+        # (the larger runs draw shorter reads: the same two forms of the item search, a tenth of the bytes)
+        mean, std = (3000.0, 2500.0) if wgs == 4096 else (600.0, 400.0)
+        lp = MinimalLongErrorProfile(gamma_mean=mean, gamma_std=std, length_mode=_abi.LEN_PER_READ, rng_mode=_abi.RNG_PHILOX).pod()
         got = []
         for eng in (engine, other):
             eng.counters_reset()
-            r = eng.simulate_long_reads([21], [900], lp, 9, qual_offset=33)
+            r = eng.simulate_long_reads([21], [n_long], lp, 9, qual_offset=33)
             got.append((r.to_host(), eng.counters()))
         from tests.test_gpu_parity import assert_same
         assert_same(got[0][0], got[1][0])

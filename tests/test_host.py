@@ -198,3 +198,39 @@ def test_header_states_the_shipped_philox_specification():
         assert "2^24 - 2^e" in (ROOT / f).read_text(), f
     assert "(uint32_t)(i >> 2), 2u, 0x73696D6Du, 0x72000003u" in (ROOT / "oracle" / "custom.c").read_text()
     assert "philox4x32_10(i >> 2, 2u," in (ROOT / "simmr_amd" / "csrc" / "kernels.hip").read_text()
+
+
+def test_block_loop_tests_are_sized_from_the_kernels_constants():
+    """tests/test_gpu_blockloop.py and test_results_do_not_depend_on_the_grid compute "this workgroup takes a second and a
+    third block" from these constants: the units of a block, the grid of the item kernel at its three launches (columns,
+    the copy-only form, the text), and the grids of the perfect-short and lane-per-read kernels.  If one of them changes,
+    those tests have to be resized — they assert their premise, and this test says where it comes from."""
+    kernels = (ROOT / "simmr_amd" / "csrc" / "kernels.hip").read_text()
+    engine = (ROOT / "simmr_amd" / "csrc" / "engine.hip").read_text()
+    for needle in ("#define PHILOX_UNITS 128u", "#define PHILOX_CBASE 64u", "#define PERFECT_GROUP 256u", "#define LANES_WG 512",
+                   "#define PHILOX_MAP_ITEMS 4096u", "for (uint64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {"):
+        assert needle in kernels, needle
+    grid = "std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);"
+    assert engine.count("const uint32_t grid = (uint32_t)" + grid) == 2, "the column launch and the TEXT launch"
+    assert engine.count("const uint32_t cgrid = (uint32_t)std::min<uint64_t>(cblocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);") == 1, "COPY_ONLY"
+    assert engine.count("blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;") == 3
+    for needle in ("uint32_t philox_wgs_per_cu = 128;",
+                   "std::min<uint64_t>(groups, (uint64_t)e->n_cu * 8 * e->perfect_mult);",
+                   "std::min<uint64_t>(wgs, (uint64_t)e->n_cu * (uint64_t)per_cu * e->lanes_mult);",
+                   "bool escq = (out->qual_offset & 0xffu) + e->prof.philox_qmax1 <= 127u;",
+                   "bool escq = 33u + e->prof.philox_qmax1 <= 127u;"):
+        assert needle in engine, needle
+
+
+@pytest.mark.parametrize("lens", [[1], [64, 65], [1000, 31, 4097, 0, 333], [70_001], [32, 33, 95, 96, 97]])
+def test_chunked_synthetic_contigs_are_the_plain_ones(lens):
+    """tests/_synth.synthetic_contigs_chunked (the 100 Mbp host genome of tests/test_gpu_fullsize.py) against the plain
+    form, with chunks smaller than a contig, of odd sizes, and larger than everything."""
+    from tests import _synth
+    for seed in (2, 9):
+        want = _synth.synthetic_contigs(lens, seed)
+        for chunk_words in (1, 3, 7, 64, 1 << 20):
+            got = _synth.synthetic_contigs_chunked(lens, seed, chunk_words)
+            assert len(got) == len(want)
+            for a, b in zip(got, want):
+                assert a.dtype == np.uint8 and np.array_equal(a, b), (lens, seed, chunk_words)
