@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <map>
 #include <random>
 #include <string>
 #include <mutex>
@@ -94,8 +95,6 @@ struct simmr_engine {
   bool plan_short_ok = false;  // the current paired plan has no read longer than LONGREAD_MAXL (text_lines.hip takes it)
   bool plan_coarse = false; // pairs for the counter-mode kernel: u_off64 (first byte of every 64th pair) instead of u_off
   DevBuf w_bytes, u_off64, fq_off64;
-  uint32_t splice_lds_set[2] = {0, 0};  // dynamic-LDS limit already set on this device for k_custom_long_splice<exc, fast>
-  uint32_t splice_ctr_lds_set[2] = {0, 0};  // the same for the counter mode's instantiations <exc, fast, CTR>
   bool fq_coarse = false;  // the direct FASTQ plan in force has fq_off64 (first byte of every 64th record) instead of fq_off
   bool plan_paired = false;
   bool plan_multi = false;    // paired-end plan over several genomes (u_genome per pair)
@@ -116,7 +115,6 @@ struct simmr_engine {
   DevBuf s_w_bytes, s_u_off64, s_m_genomes, s_u_contig, s_u_genome, s_u_seed, s_u_len, s_u_a, s_u_b, s_u_qs2, s_u_ms2, s_u_flags,
       s_u_off, s_u_order, s_d_err, s_d_runs, s_d_usable, s_ph_table;
   // measurement knobs, read ONCE when the engine is made (a stray variable cannot change a running engine's launches)
-  bool tl_debug = false;                // SIMMR_TL_DEBUG: print the occupancy of k_emit_text_lines launches
   bool inject_null_ctr_tables = false;  // SIMMR_FAULT_INJECT=null_ctr_tables: test switch, see custom_long_tables_missing
   int text_form = TEXT_FORM_DEFAULT;  // SIMMR_TEXT_FORM: 1 = the item form (k_emit_philox<TEXT>) always, 2 = the whole-line kernel (text_lines.hip) wherever it applies: same-box A/B
   uint32_t philox_wgs_per_cu = 128;  // SIMMR_PHILOX_WGS_PER_CU (item kernel), clamped to 1..4096.  More workgroups than the 4 per CU that
@@ -147,7 +145,6 @@ struct simmr_engine {
   bool fq_paired = false, fq_ready = false;
   bool fq_direct = false;          // planned by simmr_fastq_plan_direct (sizes from the plan, for simmr_emit_fastq)
   uint32_t fq_read_id_base = 0, fq_maxhdr = 0;
-  uint32_t text_lines_lds_set[16] = {0};  // dynamic LDS granted to each instantiation of k_emit_text_lines so far
   DevBuf fq_hlen;                  // header bytes per read (direct form)
   DevBuf fq_tpl_dev;               // the compiled header template, read by the kernels through a pointer
   DevBuf fd_seq, fd_qual, fd_seq_off, fd_start, fd_end, fd_contig, fd_genome, fd_read_id, fd_flags;  // columns of the unfused fallback
@@ -879,6 +876,44 @@ OutCols out_cols(const simmr_reads_out* out) {
   return o;
 }
 
+// Raises a kernel's limit of dynamic LDS to `bytes` where it is lower.  The limit belongs to a (device, function), not
+// to an engine — two engines on one device share it (simmr-hip --devices 0,0) — so the largest size granted so far is
+// kept process-wide, and a second engine never lowers what the launches of the first still need.
+template <class Kernel>
+static hipError_t grant_dynamic_lds(const simmr_engine* e, Kernel fn, uint32_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, uint32_t> granted;
+  std::lock_guard<std::mutex> lock(mu);
+  uint32_t& have = granted[{e->device, reinterpret_cast<const void*>(fn)}];
+  if (bytes <= have) return hipSuccess;
+  const hipError_t s = hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (s == hipSuccess) have = bytes;
+  return s;
+}
+
+// Traits of a launch of the item kernels (k_emit_philox, k_emit_text_lines) over the engine's current plan.  `exc` alone
+// also serves the custom long-read and lane-per-read kernels.
+struct ItemLaunch {
+  bool exc;       // some genome the plan may read has an exception plane
+  bool cached;    // pairs of one genome with few contigs: the contig bases live in LDS (no dependent load per record)
+  uint32_t grid;
+};
+static ItemLaunch item_launch(const simmr_engine* e) {
+  ItemLaunch t;
+  t.exc = false;
+  if (e->plan_paired) t.exc = e->plan_any_exc;
+  else for (const auto& g : e->genomes) t.exc = t.exc || (g.staged && g.has_exc);
+  t.cached = e->plan_paired && !e->plan_multi && e->plan_genome < e->genomes.size() &&
+             e->genomes[e->plan_genome].contigs.size() <= PHILOX_CBASE;
+  const uint64_t n_units = e->plan_units;
+  const uint64_t blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;
+  t.grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);
+  return t;
+}
+// an escaped base is noticed through its quality byte when no real one has bit 7 set (kernels.hip: esc_q); `offset` is
+// the quality offset of the launch
+static bool philox_escq(const simmr_engine* e, uint32_t offset) { return offset + e->prof.philox_qmax1 <= 127u; }
+
 // the instantiation of the counter-mode item kernel for (exception plane, contig bases in LDS, escapes noticed through
 // the quality byte, 16-byte read slots, block offsets from the coarse scan)
 // Paired plans are coarse (the block places its reads) and may keep their contig bases in LDS; long-read plans have
@@ -903,6 +938,27 @@ static PhiloxKernel philox_text_kernel(bool exc, bool cached, bool escq, bool co
   if (!escq) return k_emit_philox<true, false, false, true, false, false, true>;
   return cached ? (exc ? k_emit_philox<true, false, true, true, true, false, true> : k_emit_philox<false, false, true, true, true, false, true>)
                 : (exc ? k_emit_philox<true, false, false, true, true, false, true> : k_emit_philox<false, false, false, true, true, false, true>);
+}
+
+// What differs between the three forms of a k_emit_philox launch: the columns, the copy-only half of custom-short, the
+// FASTQ text (seq = qual = the text, no columns, the header arguments set).
+struct PhiloxForm {
+  const uint32_t* u_genome;
+  uint8_t* seq;
+  uint8_t* qual;
+  uint32_t qual_offset, read_id_base;
+  OutCols cols;
+  const uint8_t* hlen = nullptr;
+  const FqTemplate* fq_tp = nullptr;
+  FqTables fq_tb = FqTables{};
+  uint32_t fq_lit_bytes = 0, fq_hpitch = 0, fq_wshift = 0;
+  const uint64_t* off64 = nullptr;  // coarse plans and the text: first byte of every 64th pair / record
+};
+static void launch_philox(simmr_engine* e, PhiloxKernel kern, uint32_t grid, uint32_t lds, const PlanArrays& pl, const PhiloxForm& f) {
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, e->stream, e->prof, e->plan_paired ? 1u : 0u, e->d_genomes.as<GenomeDev>(),
+                     e->plan_genome, e->plan_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), f.u_genome,
+                     e->u_seed.as<uint64_t>(), f.seq, f.qual, f.qual_offset, e->plan_first, f.read_id_base, f.cols,
+                     e->d_counters.as<unsigned long long>(), f.hlen, f.fq_tp, f.fq_tb, f.fq_lit_bytes, f.fq_hpitch, f.fq_wshift, f.off64);
 }
 
 // Every device table the custom long-read kernels dereference for this mode and form must exist BEFORE they are launched:
@@ -989,7 +1045,6 @@ int simmr_engine_create(int device_ordinal, simmr_engine** out) {
         (uint32_t)std::min<unsigned long long>(512, std::max<unsigned long long>(1, strtoull(v, nullptr, 10)));
   if (const char* v = getenv("SIMMR_FASTQ_GRID_MULT")) e->fastq_mult = (uint32_t)std::min<unsigned long long>(512, std::max<unsigned long long>(1, strtoull(v, nullptr, 10)));
   if (const char* v = getenv("SIMMR_TEXT_FORM")) e->text_form = atoi(v);
-  e->tl_debug = getenv("SIMMR_TL_DEBUG") != nullptr;
   if (const char* v = getenv("SIMMR_FAULT_INJECT")) e->inject_null_ctr_tables = strcmp(v, "null_ctr_tables") == 0;
   if (const char* v = getenv("SIMMR_PHILOX_WGS_PER_CU")) e->philox_wgs_per_cu = (uint32_t)std::min<unsigned long long>(4096, std::max<unsigned long long>(1, strtoull(v, nullptr, 10)));
   if (const char* v = getenv("SIMMR_SPLICE_VARIANT")) e->splice_variant = atoi(v);
@@ -1641,6 +1696,7 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
                        paired ? 1u : 0u, n_units, e->plan_first, read_id_base, e->plan_genome, pl,
                        e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), u_genome, out_cols(out));
   unsigned long long* counters = e->d_counters.as<unsigned long long>();
+  const ItemLaunch il = item_launch(e);
   HIP_TRY(e, next_emit_events(e));
   HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
   if (n_units > 0) {
@@ -1653,29 +1709,11 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
                          e->u_contig.as<uint32_t>(), out->seq,
                          out->qual, 60u + out->qual_offset, e->plan_first, read_id_base, out_cols(out), counters);
     } else if (e->prof.rng_mode != SIMMR_RNG_REFERENCE && e->prof.kind != SIMMR_K_CUSTOM) {  // (a custom model's counter mode: below)
-      bool exc = false;
-      if (paired) exc = e->plan_any_exc;
-      else for (const auto& g : e->genomes) exc = exc || (g.staged && g.has_exc);
-      // pairs of one genome with few contigs: the contig bases live in LDS (no dependent load per record)
-      const bool cached = paired && !e->plan_multi && e->plan_genome < e->genomes.size() &&
-                          e->genomes[e->plan_genome].contigs.size() <= PHILOX_CBASE;
-      {
-        const uint64_t blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);
-        // an escaped base is noticed through its quality byte when no real one has bit 7 set (kernels.hip: esc_q)
-        bool escq = (out->qual_offset & 0xffu) + e->prof.philox_qmax1 <= 127u;
-#if defined(SIMMR_NO_ESCQ)
-        escq = false;  // test build: the flag-bit form on every input
-#endif
-        const bool coarse = paired && e->plan_coarse;
-        auto kern = philox_kernel(exc, cached, escq, e->plan_slot != 0, coarse);
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, e->prof, paired ? 1u : 0u,
-                           e->d_genomes.as<GenomeDev>(), e->plan_genome, n_units, pl, e->u_off.as<uint64_t>(),
-                           e->u_contig.as<uint32_t>(), u_genome, e->u_seed.as<uint64_t>(), out->seq, out->qual,
-                           out->qual_offset, e->plan_first, read_id_base, out_cols(out), counters,
-                           (const uint8_t*)nullptr, (const FqTemplate*)nullptr, FqTables{}, 0u, 0u, 0u,
-                           coarse ? (const uint64_t*)e->u_off64.as<uint64_t>() : (const uint64_t*)nullptr);
-      }
+      const bool escq = philox_escq(e, out->qual_offset & 0xffu);
+      const bool coarse = paired && e->plan_coarse;
+      PhiloxForm f{u_genome, out->seq, out->qual, out->qual_offset, read_id_base, out_cols(out)};
+      if (coarse) f.off64 = e->u_off64.as<uint64_t>();
+      launch_philox(e, philox_kernel(il.exc, il.cached, escq, e->plan_slot != 0, coarse), il.grid, 0, pl, f);
     } else if (e->prof.kind == SIMMR_K_CUSTOM && !paired) {
       {
         const bool fast0 = e->prof.custom.kmer_stride != 0 && e->splice_variant != 1;
@@ -1684,8 +1722,7 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
                                        "(nothing was launched)", missing, e->prof.rng_mode);
       }
       HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
-      bool exc = false;
-      for (const auto& g : e->genomes) exc = exc || (g.staged && g.has_exc);
+      const bool exc = il.exc;
       const uint64_t blocks = (n_reads + 255) / 256;
       const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
       const uint32_t* order = e->plan_sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr;
@@ -1703,10 +1740,7 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
         const uint32_t tab = fast ? splice_ctr_lds_bytes(e->prof.custom.kmer_size) : 0u;
         const uint32_t lanes = tab > 16384u ? SPLICE_CTR_LANES_MAX : 256u;
         const uint32_t lds = fast ? tab + 16u * lanes : 0u;  // the k-mer table + 16 bytes per lane (an even group waiting for its odd neighbour's store)
-        if (lds > 32768u && lds > e->splice_ctr_lds_set[exc ? 1 : 0]) {  // (64 KB of table + the kernel's static LDS: over the default limit)
-          HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          e->splice_ctr_lds_set[exc ? 1 : 0] = lds;
-        }
+        if (lds > 32768u) HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (64 KB of table + the kernel's static LDS: over the default limit)
         // (many more workgroups than are resident: reads come longest first, and the tail of the launch is short ones)
         const uint32_t cgrid = (uint32_t)std::min<uint64_t>((n_reads + lanes - 1) / lanes, (uint64_t)e->n_cu * 64 * e->custom_long_mult);
         hipLaunchKernelGGL(kern, dim3(cgrid), dim3(lanes), lds, e->stream, e->prof, e->d_genomes.as<GenomeDev>(), n_units, order,
@@ -1716,12 +1750,7 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
         // one workgroup of 1024 lanes per CU around the LDS count table (kernels.hip section 9c)
         auto kern = exc ? k_custom_long_splice<true, true> : k_custom_long_splice<false, true>;
         const uint32_t lds = splice_fast_lds_bytes(e->prof.custom.kmer_size);
-        // not once per emit: the limit is per device and grows with the model's k (132 KB + 4^k), so each engine keeps
-        // the largest size it has set per kernel variant and sets it again only when a model needs more
-        if (lds > e->splice_lds_set[exc ? 1 : 0]) {
-          HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          e->splice_lds_set[exc ? 1 : 0] = lds;
-        }
+        HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (grows with the model's k: 132 KB + 4^k)
         const uint32_t fgrid = (uint32_t)std::min<uint64_t>((n_reads + SPLICE_FAST_LANES - 1) / SPLICE_FAST_LANES, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
         hipLaunchKernelGGL(kern, dim3(fgrid), dim3(SPLICE_FAST_LANES), lds, e->stream, e->prof, e->d_genomes.as<GenomeDev>(),
                            n_units, order, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
@@ -1741,19 +1770,12 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
                          e->plan_genome, n_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(),
                          e->u_seed.as<uint64_t>(), out->seq, out->qual, out->qual_offset, counters,
                          e->d_err.as<uint32_t>());
-      const uint64_t cblocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;
-      const uint32_t cgrid = (uint32_t)std::min<uint64_t>(cblocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);
-      auto copy = e->plan_any_exc ? k_emit_philox<true, true, false> : k_emit_philox<false, true, false>;
-      hipLaunchKernelGGL(copy, dim3(cgrid), dim3(256), 0, e->stream, e->prof, 1u, e->d_genomes.as<GenomeDev>(),
-                         e->plan_genome, n_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(),
-                         (const uint32_t*)nullptr, e->u_seed.as<uint64_t>(), out->seq, out->qual, out->qual_offset,
-                         e->plan_first, read_id_base, out_cols(out), counters, (const uint8_t*)nullptr,
-                         (const FqTemplate*)nullptr, FqTables{}, 0u, 0u, 0u, (const uint64_t*)nullptr);
+      // (its plain form whatever the plan: per-pair offsets, no contig cache, no genome column)
+      launch_philox(e, il.exc ? k_emit_philox<true, true, false> : k_emit_philox<false, true, false>, il.grid, 0, pl,
+                    PhiloxForm{nullptr, out->seq, out->qual, out->qual_offset, read_id_base, out_cols(out)});
     } else {
       // lane-per-read kernel: template on (exception plane present, paired, perfect-long Phred)
-      bool exc = false;
-      if (paired) exc = e->plan_any_exc;
-      else for (const auto& g : e->genomes) exc = exc || (g.staged && g.has_exc);
+      const bool exc = il.exc;
       const bool pl_kind = e->prof.kind == SIMMR_K_PERFECT_LONG;
       using KernT = void (*)(ProfileDev, const GenomeDev*, uint32_t, uint64_t, const uint32_t*, PlanArrays,
                              const uint64_t*, const uint32_t*, const uint32_t*, const uint64_t*, uint8_t*, uint8_t*,
@@ -2164,8 +2186,7 @@ int simmr_fastq_emit(simmr_engine* e, const simmr_reads_out* reads, uint8_t* dst
   const uint64_t n_batches = (e->fq_reads + FQ_BATCH - 1) / FQ_BATCH;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n_batches + 3) / 4, (uint64_t)e->n_cu * 8 * e->fastq_mult);
   const uint32_t hdr_lds = 4 * FQ_BATCH * e->fq_hpitch;  // up to 68 KB with 255-byte headers: above the default limit
-  if (hdr_lds > 48 * 1024)
-    HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_fastq_write), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hdr_lds));
+  if (hdr_lds > 48 * 1024) HIP_TRY(e, grant_dynamic_lds(e, k_fastq_write, hdr_lds));
   HIP_TRY(e, next_emit_events(e));
   HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
   hipLaunchKernelGGL(k_fastq_write, dim3(grid), dim3(256), hdr_lds, e->stream, e->fq_tpl_dev.as<FqTemplate>(), tb, rd,
@@ -2284,8 +2305,7 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
     const uint64_t n_batches = (n_reads + FQ_BATCH - 1) / FQ_BATCH;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n_batches + 3) / 4, (uint64_t)e->n_cu * 8 * e->fastq_mult);
     const uint32_t hdr_lds = 4 * FQ_BATCH * e->fq_hpitch;
-    if (hdr_lds > 48 * 1024)
-      HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(k_fastq_write), hipFuncAttributeMaxDynamicSharedMemorySize, (int)hdr_lds));
+    if (hdr_lds > 48 * 1024) HIP_TRY(e, grant_dynamic_lds(e, k_fastq_write, hdr_lds));
     hipLaunchKernelGGL(k_fastq_write, dim3(grid), dim3(256), hdr_lds, e->stream, e->fq_tpl_dev.as<FqTemplate>(), tb, rd, n_reads, paired ? 1u : 0u,
                        e->fq_lit_bytes, e->fq_hpitch, e->fq_off.as<uint64_t>(), dst);
     hipError_t s = hipGetLastError();
@@ -2299,17 +2319,9 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
   HIP_TRY(e, next_emit_events(e));
   HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
   {
-    const uint64_t blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);
-    bool exc = false;
-    if (paired) exc = e->plan_any_exc;
-    else for (const auto& g : e->genomes) exc = exc || (g.staged && g.has_exc);
-    const bool cached = paired && !e->plan_multi && e->plan_genome < e->genomes.size() &&
-                        e->genomes[e->plan_genome].contigs.size() <= PHILOX_CBASE;
-    bool escq = 33u + e->prof.philox_qmax1 <= 127u;
-#if defined(SIMMR_NO_ESCQ)
-    escq = false;
-#endif
+    const ItemLaunch il = item_launch(e);
+    const bool exc = il.exc, cached = il.cached, escq = philox_escq(e, 33u);
+    const uint32_t grid = il.grid;
     const bool copy_only = e->prof.kind == SIMMR_K_PERFECT_SHORT;  // (perfect-short: bases of the plan, every quality 60)
     // The whole-line form: paired plans whose reads fit its segments, into a buffer its 16-byte chunks are aligned in,
     // with header slots that leave room for two workgroups per CU; everything else takes the item form.
@@ -2317,49 +2329,24 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
     const uint32_t tl_lds = TL_GROUP * tl_pitch;
     if (e->text_form == 2 && paired && e->plan_short_ok && ((uintptr_t)dst & 15u) == 0 && tl_lds <= 40u * 1024u) {
       auto tk = text_lines_kernel(exc, cached, escq, copy_only);
-      const int slot = (exc ? 1 : 0) | (cached ? 2 : 0) | (escq ? 4 : 0) | (copy_only ? 8 : 0);
-      if (tl_lds > e->text_lines_lds_set[slot]) {  // (static + dynamic LDS may pass the default limit with long headers)
-        HIP_TRY(e, hipFuncSetAttribute(reinterpret_cast<const void*>(tk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl_lds));
-        e->text_lines_lds_set[slot] = tl_lds;
-      }
-      if (e->tl_debug) {  // (SIMMR_TL_DEBUG, measurement aid: how many workgroups of this launch share a CU)
-        int per_cu = -1;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, tk, 256, tl_lds);
-        fprintf(stderr, "k_emit_text_lines: dynamic LDS %u bytes (slot pitch %u), %d workgroups per CU, grid %u\n", tl_lds, tl_pitch, per_cu, grid);
-      }
+      HIP_TRY(e, grant_dynamic_lds(e, tk, tl_lds));  // (static + dynamic LDS may pass the default limit with long headers)
       const uint32_t t8 = tl_pitch / 8u, t9 = (t8 + 1u) / 2u;
       hipLaunchKernelGGL(tk, dim3(grid), dim3(256), tl_lds, e->stream, e->prof, e->d_genomes.as<GenomeDev>(), e->plan_genome, n_units, pl,
                          e->u_contig.as<uint32_t>(), u_genome, e->u_seed.as<uint64_t>(), dst, 33u, e->plan_first, e->fq_read_id_base,
                          counters, e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(), tb, e->fq_lit_bytes, tl_pitch, t9,
                          65536u / t9 + 1u, (const uint64_t*)e->fq_off64.as<uint64_t>());
       HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
-#if defined(TL_DIAG)
-      {  // measurement build: time per section, mean per wave, in microseconds (s_memtime: 100 MHz)
-        unsigned long long d[16];
-        (void)hipStreamSynchronize(e->stream);
-        (void)hipMemcpyFromSymbol(d, HIP_SYMBOL(tl_diag), sizeof d);
-        const char* nm[10] = {"prologue", "wait_slots", "format", "wait_format", "segment", "items", "tasks", "extent_fetch", "flush", "tail"};
-        fprintf(stderr, "tl_diag (us per wave, %llu waves):", d[10]);
-        for (int k = 0; k < 10; k++) fprintf(stderr, " %s=%.1f", nm[k], 0.01 * (double)d[k] / (double)std::max(1ull, d[10]));
-        fprintf(stderr, "\n");
-        unsigned long long z[16] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(tl_diag), z, sizeof z);
-      }
-#endif
       hipError_t s2 = hipGetLastError();
       if (s2 != hipSuccess) return e->fail(SIMMR_ENODEV, "fastq launch failed: %s", hipGetErrorString(s2));
       return SIMMR_OK;
     }
-    auto kern = philox_text_kernel(exc, cached, escq, copy_only);
     // windows per run: the power of two that covers the longest run ('\n' + header + '\n'), at most 32 (512 bytes)
     uint32_t wshift = 0;
     while ((16u << wshift) < e->fq_maxhdr + 2u) wshift++;
     const uint32_t slots_lds = std::max<uint32_t>(PHILOX_MAP_ITEMS, FQ_GROUP * e->fq_hpitch);  // header slots; the item map lives there too
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), slots_lds, e->stream, e->prof, paired ? 1u : 0u, e->d_genomes.as<GenomeDev>(),
-                       e->plan_genome, n_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), u_genome,
-                       e->u_seed.as<uint64_t>(), dst, dst, 33u, e->plan_first, e->fq_read_id_base, OutCols{}, counters,
-                       e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(), tb, e->fq_lit_bytes, e->fq_hpitch, wshift,
-                       (const uint64_t*)e->fq_off64.as<uint64_t>());
+    launch_philox(e, philox_text_kernel(exc, cached, escq, copy_only), grid, slots_lds, pl,
+                  PhiloxForm{u_genome, dst, dst, 33u, e->fq_read_id_base, OutCols{}, e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(),
+                             tb, e->fq_lit_bytes, e->fq_hpitch, wshift, e->fq_off64.as<uint64_t>()});
   }
   HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
   hipError_t s = hipGetLastError();

@@ -217,9 +217,6 @@ SIMMR_DEV uint32_t fq_format_header(uint8_t* slot, uint32_t lead, const FqSeg* s
   const uint32_t g = f.genome;
   const uint32_t row = tb.g_cbase[g] + f.contig;
   const uint32_t gid_off = tb.g_id_off[g], gid_len = tb.g_id_len[g], sid_off = tb.c_off[row], sid_len = tb.c_len[row];
-#if defined(SIMMR_ABLATE_HALF_SEGS)  /* timing only: what formatting costs if a lane wrote half of a header (wrong text, same places) */
-  n_segs = (n_segs + 1u) / 2u;
-#endif
   for (uint32_t s = 0; s < n_segs; s++) {
     const FqSeg sg = segs[s];
     // (one copy of each routine: the two ids share one, the three numbers one, the two letters one — inlined per field

@@ -60,11 +60,7 @@ k_pack_ascii(const uint8_t* __restrict__ ascii, uint64_t n, uint64_t dst_base,
 // makes every wave wait for its outstanding GLOBAL stores (s_waitcnt vmcnt(0)) although no other wave will read
 // them; a kernel that streams its output and synchronises per block then pays the store latency at every barrier.
 SIMMR_DEV void lds_barrier() {
-#if defined(SIMMR_ABLATE_FULL_BARRIER)
-  __syncthreads();
-#else
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#endif
 }
 
 // exclusive scan of one u32 per thread over a 256-thread workgroup (tid = threadIdx.x; a caller inside a long loop
@@ -983,13 +979,9 @@ typedef v4u32 __attribute__((aligned(1))) v4u32_unaligned;
 // writes WHOLE lines the stores are nontemporal (`nt`): the lines are not kept in L2 / MALL behind the write.  Same-box
 // A/B (profiles/r3/ab_nt_stores_*): k_emit_perfect_pe 6.3 against 7.4 ms per 100 M reads, k_emit_philox in the slot
 // layout 11.4 against 11.9 — and in the compact layout, whose 16-byte stores straddle lines and whose read ends are
-// written bytewise, 15.3 against 12.7: there the stores stay plain.  -DSIMMR_PLAIN_STORES: the A side.
+// written bytewise, 15.3 against 12.7: there the stores stay plain.
 // (a macro, not a function template: the pointee types carry `aligned(1)`, which template deduction would drop)
-#if defined(SIMMR_PLAIN_STORES)
-#define stream_store(p, v) (*(p) = (v))
-#else
 #define stream_store(p, v) __builtin_nontemporal_store((v), (p))
-#endif
 typedef const __attribute__((address_space(1))) u64_unaligned* global_u64_unaligned_ptr;
 SIMMR_DEV uint64_t load_plane_u64(const uint32_t* __restrict__ plane, int64_t word) {
   return *(global_u64_unaligned_ptr)(plane + word);  // words `word` and `word + 1`, 4-byte aligned
@@ -1777,17 +1769,6 @@ k_emit_lanes(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32_t ge
 // packed 2-bit codes; blocks of short reads keep an item -> read map in LDS (one
 // byte load), otherwise a branch-free binary search over the item prefix finds the
 // read.
-// Named -D switches compile pieces out for differential timing (Makefile, `make ablate`):
-// SIMMR_ABLATE_PHILOX (words from one multiply instead of the ten rounds), SIMMR_ABLATE_LOOKUP
-// (no table lookups), SIMMR_ABLATE_STORES (no global stores of bases / qualities), SIMMR_ABLATE_CODES
-// (no load from the reference plane), SIMMR_ABLATE_META (no metadata columns), SIMMR_ABLATE_ITEMS (one
-// round of items per block), SIMMR_ABLATE_ALL16 / SIMMR_ABLATE_ALIGN16 (partial groups stored as
-// 16 bytes, except the shard's last ones / every store aligned down to 16 bytes: wrong bytes, inside the buffers), SIMMR_ABLATE_NOP
-// (without the wait states between the compare and the select), SIMMR_ABLATE_HOTSTORE (the same store
-// instructions, all landing in the first 64 KB of the two streams: store issue without the DRAM write
-// path), SIMMR_ABLATE_LINES (every store instruction of a wave writes sixteen whole 64-byte lines, clamped to the
-// streams' total_bases).  None of them changes an index, a pointer into a table or a loop bound; the two that
-// move stores are bounded by the planned size (tests/test_gpu_shapes.py runs them between canaries when built).
 // ===========================================================================
 #include "fastq_format.hpp"  // (inside namespace simmr) header formatting, for the TEXT form of k_emit_philox
 
@@ -1869,21 +1850,13 @@ struct alignas(16) PhRec {
 // v_cndmask_b32_sdwa picks the half in place.  A VALU write of VCC needs two wait states before a VALU reads it as
 // a mask on gfx950 (the compiler pads its own code; inside an asm statement that is this statement's job).
 SIMMR_DEV uint32_t philox_pick(uint32_t R, const uint2* __restrict__ jtab) {
-#if defined(SIMMR_ABLATE_LOOKUP)
-  return ((R >> 8) & 3u) | ((R >> 10) & 0x3f00u) | 0x2100u;
-#else
   const uint2 e = jtab[R >> 22];
   uint32_t x;
-#if defined(SIMMR_ABLATE_NOP)
-  asm("v_cmp_lt_u32_e32 vcc, %1, %2\n\t"
-#else
   asm("v_cmp_lt_u32_e32 vcc, %1, %2\n\t"
       "s_nop 1\n\t"
-#endif
       "v_cndmask_b32_sdwa %0, %3, %3, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:WORD_0"
       : "=v"(x) : "v"(R), "v"(e.x), "v"(e.y) : "vcc");
   return x;
-#endif
 }
 
 // An item in which a base escaped (one item in 9 000): its 16 draws again, four bases at a time, the escaped ones
@@ -1956,9 +1929,9 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
               const uint64_t* __restrict__ u_seed, uint8_t* __restrict__ seq, uint8_t* __restrict__ qual,
               uint32_t qual_offset, uint64_t first_unit, uint32_t read_id_base, OutCols o,
               unsigned long long* __restrict__ counters,
-              const uint8_t* __restrict__ hlen = nullptr, const FqTemplate* __restrict__ fq_tp = nullptr, FqTables fq_tb = FqTables{},
-              uint32_t fq_lit_bytes = 0, uint32_t fq_hpitch = 0, uint32_t fq_wshift = 0,
-              const uint64_t* __restrict__ off64 = nullptr) {
+              const uint8_t* __restrict__ hlen, const FqTemplate* __restrict__ fq_tp, FqTables fq_tb,
+              uint32_t fq_lit_bytes, uint32_t fq_hpitch, uint32_t fq_wshift,
+              const uint64_t* __restrict__ off64) {
   // off64 != null ("coarse" plans, engine.hip): u_off does not exist; off64[w] = first output byte of pair 64 w (the scan
   // of the plan kernel's per-wave byte sums), and a block places its reads with a scan of their (padded) lengths
   constexpr bool coarse = COARSE && !TEXT;
@@ -1969,7 +1942,6 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
   // bases, a constant quality line, headers and counters as in the drawing form
   constexpr bool FULL = !COPY_ONLY || TEXT;  // this launch writes qualities, headers / metadata and all run counters
   const uint32_t const_q4 = (((60u + (qual_offset & 0xffu)) & 0xffu) * 0x01010101u);
-#define PL(x) (x)
 #define COL_STORE(p, v) do { if (SLOT) stream_store((p), (v)); else *(p) = (v); } while (0)  /* the metadata columns, as the streams */
   // TEXT: header slots of FQ_GROUP reads at a time (dynamic LDS, FQ_GROUP * fq_hpitch bytes), the template and its literals
   extern __shared__ __attribute__((aligned(16))) uint8_t fq_slots[];
@@ -2079,7 +2051,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       const bool on = tix < nr;
       if (on) {
         const uint64_t u = u0 + (paired ? (tix >> 1) : tix);
-        L0 = PL(pl.len[u]);
+        L0 = pl.len[u];
         h0 = hlen[paired ? 2 * u + (tix & 1u) : u];
       }
       uint64_t tot2;
@@ -2098,9 +2070,9 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       const uint32_t ui = paired ? (t >> 1) : t;  // the unit's index in the block
       const uint64_t u = u0 + ui;
       const uint32_t rev = paired ? (t & 1u) : 0u;
-      const uint32_t L = PL(lane_at(pl.len + u0, ui));
+      const uint32_t L = lane_at(pl.len + u0, ui);
       g = (L + 15u) >> 4;
-      const uint32_t contig = PL(lane_at(u_contig + u0, ui));
+      const uint32_t contig = lane_at(u_contig + u0, ui);
       const uint32_t genome = (!CACHED && u_genome) ? lane_at(u_genome + u0, ui) : genome_const;
       const uint64_t rd0 = rpu * u0;  // the block's first read
       const uint64_t rd = rd0 + t;
@@ -2111,12 +2083,12 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       // (both mates load both columns and keep their own: a per-lane choice of base would be per-lane address arithmetic;
       // unpaired, the second base is the first again — every column read here exists)
       const uint64_t* const b_col = paired ? pl.b : pl.a;
-      const uint64_t pos_a = PL(lane_at(pl.a + u0, ui)), pos_b = PL(lane_at(b_col + u0, ui));
+      const uint64_t pos_a = lane_at(pl.a + u0, ui), pos_b = lane_at(b_col + u0, ui);
       const uint64_t pos = rev ? pos_b : pos_a;  // first source base of this read on the contig
       uint64_t key = 0;  // (COPY_ONLY: no draws, no key; qs2 may not exist)
       if (!COPY_ONLY) {
         const uint64_t* const k_col = paired ? pl.qs2 : u_seed;
-        const uint64_t key_a = PL(lane_at(u_seed + u0, ui)), key_b = PL(lane_at(k_col + u0, ui));
+        const uint64_t key_a = lane_at(u_seed + u0, ui), key_b = lane_at(k_col + u0, ui);
         key = rev ? key_b : key_a;
       }
       uint64_t cb;
@@ -2141,13 +2113,9 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       rc.gs = 0; rc.pad = 0;
       recs[t] = rc;
       if (HAS_EXC) { x_src[t] = src; x_mask[t] = mk; }
-#if defined(SIMMR_ABLATE_META)
-      if (false) {
-#else
       if (FULL) {
-#endif
         // metadata columns of this read (the other emit kernels leave them to k_write_meta)
-        const uint32_t fl = PL(lane_at(pl.flags + u0, ui));
+        const uint32_t fl = lane_at(pl.flags + u0, ui);
         if (TEXT) { h_pos = pos; h_L = L; h_genome = genome; h_contig = contig; h_flags = (paired && !rev) ? 0u : fl; h_rec = my_rec; }
         if (!TEXT) {
           if (paired) {
@@ -2207,17 +2175,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
           if (n >= 16u) {  // the last window ends where the run ends (it overlaps its neighbour with the same bytes)
             if (piece * 16u < n) {
               const uint32_t w0 = (piece + 1u) * 16u <= n ? piece * 16u : n - 16u;
-#if defined(SIMMR_ABLATE_LINES)  /* timing only: the window stores of a wave as sixteen whole lines inside the text */
-              {
-                const uint64_t tot = off64[(n_reads + 63u) >> 6];
-                const uint64_t last = tot >= 1024u ? ((tot - 1024u) & ~1023ull) : 0u;
-                uint64_t a = (uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(fq_run_at[i] >> 10)) << 10;
-                a = a < last ? a : last;
-                if (tot >= 1024u) *reinterpret_cast<v4u32*>(seq + a + 16u * (tix & 63u)) = fq_read16(sl, w0);
-              }
-#else
               *reinterpret_cast<v4u32_unaligned*>(d + w0) = (v4u32_unaligned)fq_read16(sl, w0);
-#endif
             }
           } else if (piece == 0u) {
             for (uint32_t j = 0; j < n; j++) d[j] = sl[j];
@@ -2236,12 +2194,10 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
     } else {
       ex = wg_exclusive_scan_u32<true>(g, lds4, &n_items, tix);
     }
-#if !defined(SIMMR_ABLATE_META)
     if (!TEXT && !COPY_ONLY && tix < nr) {
       COL_STORE(&lane_at(o.seq_off + rpu * u0, tix), (uint64_t)(my_dst + my_pad));  // first base (SLOT: a reverse mate's bases are right-aligned)
       if (my_rd + 1 == n_reads) o.seq_off[n_reads] = coarse ? off64[(n_units + 63u) >> 6] : u_off[n_units];  // closing CSR offset
     }
-#endif
     if (tix < nr) recs[tix].gs = ex;
     r_gs[tix] = tix < nr ? ex : 0xffffffffu;
     if (tix == 0) r_gs[PHILOX_READS] = 0xffffffffu;
@@ -2259,11 +2215,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       }
     }
     lds_barrier();
-#if defined(SIMMR_ABLATE_ITEMS)
-    const uint32_t i_end = n_items < 256u ? n_items : 256u;  // one round instead of all
-#else
     const uint32_t i_end = n_items;
-#endif
     // long reads (64 items and more each on average): a lane's items ascend 256 apart, so its read moves on by one
     // now and then — one look at the next read's first item instead of the eight dependent ones of the search
     const bool walk = !use_map && n_items >= nr * 64u;
@@ -2287,11 +2239,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
     auto plane_word = [&](const uint32_t it, const uint32_t r) -> uint64_t {
       const uint4 rb = rec4[2 * r + 1];
       const uint64_t wa = ((uint64_t)rb.x | ((uint64_t)rb.y << 32)) + 4ull * (it - rb.z);
-#if defined(SIMMR_ABLATE_CODES)
-      return wa * 0x9E3779B97F4A7C15ull;  // timing only: no load from the plane
-#else
       return *reinterpret_cast<global_u64_unaligned_ptr>(wa);
-#endif
     };
     // One item ahead: the NEXT item's read and plane word are fetched before this item's stores are issued, so the wait for
     // that load does not stand behind them in the in-order counter.  Only in the copy-only forms, which have nothing but
@@ -2404,65 +2352,21 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       const uint64_t q_lo = (uint64_t)qr[0] | ((uint64_t)qr[1] << 32), q_hi = (uint64_t)qr[2] | ((uint64_t)qr[3] << 32);
       const uint64_t s_lo = (uint64_t)s0 | ((uint64_t)s1 << 32), s_hi = (uint64_t)s2 | ((uint64_t)s3 << 32);
       if (prefetch && item + 256u < i_end) { r_next = locate(item + 256u); raw_next = plane_word(item + 256u, r_next); }
-#if defined(SIMMR_ABLATE_STORES)
-      asm volatile("" :: "v"(q_lo), "v"(q_hi), "v"(s_lo), "v"(s_hi), "v"(o_q), "v"(o_s));  // alive, not stored
-#else
-#if defined(SIMMR_ABLATE_LINES)
-      // timing only: every 16-byte store instruction of a wave writes sixteen WHOLE 64-byte lines (the wave's first
-      // lane's place rounded down to 1 KB, then lane by lane); wrong places, and clamped so that the 1 KB stays
-      // inside the total_bases bytes of the streams (a shard of less than 1 KB writes nothing at all)
-      const uint64_t abl_total = TEXT ? off64[(n_reads + 63u) >> 6] : (coarse ? off64[(n_units + 63u) >> 6] : u_off[n_units]);
-      const uint64_t abl_last = abl_total >= 1024u ? ((abl_total - 1024u) & ~1023ull) : 0u;
-      uint64_t abl_q = ((uint64_t)__builtin_amdgcn_readfirstlane(o_q) + out0) & ~1023ull;
-      uint64_t abl_s = ((uint64_t)__builtin_amdgcn_readfirstlane(o_s) + out0) & ~1023ull;
-      abl_q = abl_q < abl_last ? abl_q : abl_last;
-      abl_s = abl_s < abl_last ? abl_s : abl_last;
-      if (abl_total < 1024u) continue;
-      uint8_t* qd = qual + abl_q + 16u * (threadIdx.x & 63u);
-      uint8_t* sd = seq + abl_s + 16u * (threadIdx.x & 63u);
-#elif defined(SIMMR_ABLATE_HOTSTORE)
-      // timing only: every store lands in the first 64 KB of the buffers (same instructions, no DRAM write traffic)
-      uint8_t* qd = qual + ((o_q + (uint32_t)out0) & 0xffffu);
-      uint8_t* sd = seq + ((o_s + (uint32_t)out0) & 0xffffu);
-#elif defined(SIMMR_ABLATE_ALIGN16)
-      // timing only: every store lands on the aligned 16 bytes below its place (still inside the buffers)
-      uint8_t* qd = (uint8_t*)((uintptr_t)(qual_blk + o_q) & ~(uintptr_t)15);
-      uint8_t* sd = (uint8_t*)((uintptr_t)(seq_blk + o_s) & ~(uintptr_t)15);
-#else
       uint8_t* qd = qual_blk + o_q;
       uint8_t* sd = seq_blk + o_s;
-#endif
-#if !defined(SIMMR_ABLATE_LINES)
       if (TEXT && ci == 0u)  // "\n+\n" and, once more, the first quality
-#else
-      if (false)
-#endif
         *reinterpret_cast<uint32_t __attribute__((aligned(1)))*>(qd - 3) = 0x000a2b0au | ((uint32_t)q_lo << 24);
-#if defined(SIMMR_ABLATE_ALL16) && defined(SIMMR_ABLATE_LINES)
-      if (true) {  // timing only (the clamped whole-line places above hold 16 bytes for every lane)
-#elif defined(SIMMR_ABLATE_ALL16)
-      // timing only: partial groups store 16 bytes too (they overwrite the head of the next read) — except where those
-      // 16 bytes would leave the streams: the last groups of the shard keep their exact stores
-      if (n == 16u || (uint64_t)(o_q > o_s ? o_q : o_s) + out0 + 16u <= (coarse ? off64[(n_units + 63u) >> 6] : u_off[n_units])) {
-#else
-      if (SLOT || n == 16u) {
-#endif
-#if !defined(SIMMR_ABLATE_LINES) && !defined(SIMMR_ABLATE_HOTSTORE) && !defined(SIMMR_ABLATE_ALIGN16)
-        if (SLOT) {  // (whole aligned lines per wave in the slot layout: nontemporal)
-          if (FULL) slot_store16(qual_blk, o_q, q_lo, q_hi);
-          slot_store16(seq_blk, o_s, s_lo, s_hi);
-        } else
-#endif
-        {
-          if (FULL) store16<SLOT>(qd, q_lo, q_hi);
-          store16<SLOT>(sd, s_lo, s_hi);
-        }
+      if (SLOT) {  // (whole aligned lines per wave in the slot layout: nontemporal)
+        if (FULL) slot_store16(qual_blk, o_q, q_lo, q_hi);
+        slot_store16(seq_blk, o_s, s_lo, s_hi);
+      } else if (n == 16u) {  // (plain stores: the compact layout's 16 bytes straddle lines, see stream_store)
+        if (FULL) store16<false>(qd, q_lo, q_hi);
+        store16<false>(sd, s_lo, s_hi);
       } else if (FULL) {
         store_tail2(qd, q_lo, q_hi, sd, s_lo, s_hi, n);
       } else {
         store_tail(sd, s_lo, s_hi, n);
       }
-#endif
     }
   }
   // sum of the raw Phred values (per lane modulo 2^64: a lane that wrote records but drew few bases goes "negative";
@@ -3137,9 +3041,6 @@ k_custom_long_splice(ProfileDev prof, const GenomeDev* __restrict__ genomes, uin
             }
             }
             n_acgt += 16u;
-#if defined(SIMMR_TEST_SPLICE_REDO)
-            rare = rare || ((i0 >> 4) & 1u) != 0u;  // test build: every other group is taken back and walked again
-#endif
             todo = rare;
             if (rare) {
               // the words of this group are generated again where they are needed (have = the block wpos lies in)
@@ -3257,7 +3158,6 @@ k_custom_long_splice(ProfileDev prof, const GenomeDev* __restrict__ genomes, uin
         }
         if (i0 < n) {
           const uint64_t lo = (uint64_t)out[0] | ((uint64_t)out[1] << 32), hi = (uint64_t)out[2] | ((uint64_t)out[3] << 32);
-#if !defined(SIMMR_SPLICE_NO_PAIRS)
           if (FAST && (CTR || !HAS_EXC)) {  // (the reference mode's form for genomes with N runs has no register left: 126 of 128)
             // Two groups per store (round 5): a lane's 16-byte store at any byte address dirties 1.5 32-byte sectors on
             // average, and they went to memory before the lane's next store reached them — 2.96 bytes written per base
@@ -3277,16 +3177,9 @@ k_custom_long_splice(ProfileDev prof, const GenomeDev* __restrict__ genomes, uin
               }
               if (full) store16(sd + i0, lo, hi); else store_tail(sd + i0, lo, hi, n - i0);
             }
-          } else
-#endif
-          if (i0 + 16u <= n) {
-#if defined(SIMMR_SPLICE_NT)
-            __builtin_nontemporal_store(lo, reinterpret_cast<u64_unaligned*>(sd + i0));
-            __builtin_nontemporal_store(hi, reinterpret_cast<u64_unaligned*>(sd + i0 + 8u));
-#else
+          } else if (i0 + 16u <= n) {
             *reinterpret_cast<u64_unaligned*>(sd + i0) = lo;
             *reinterpret_cast<u64_unaligned*>(sd + i0 + 8u) = hi;
-#endif
           } else {
             store_tail(sd + i0, lo, hi, n - i0);
           }

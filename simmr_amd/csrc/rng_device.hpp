@@ -110,10 +110,6 @@ SIMMR_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_a
 SIMMR_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t out[4]) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
   uint32_t c2 = 0x73696D6Du, c3 = 0x72000003u;
-#if defined(SIMMR_ABLATE_PHILOX)
-  out[0] = c0 * M0 + k0; out[1] = (c0 ^ c1) * M1 + k1; out[2] = out[0] ^ c2 ^ (k1 + W0); out[3] = out[1] ^ c3 ^ (k0 + W1);
-  return;
-#endif
 #pragma unroll
   for (int r = 0; r < 10; r++) {
     const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;  // one v_mad_u64_u32 each

@@ -49,35 +49,17 @@ namespace simmr {
 #define TL_MAP (TL_SEG_READS * 16u)
 static_assert(TL_MAXL == LONGREAD_MAXL, "the plan kernel's note bit is this kernel's precondition");
 
-// -DTL_DIAG (measurement build): time per section of the kernel, summed over waves, in s_memtime ticks (10 ns on gfx9):
-// TL_T(k) adds the time since the previous stamp to section k; engine.hip prints the table after the launch.
-#if defined(TL_DIAG)
-__device__ unsigned long long tl_diag[16];
-#define TL_T(k) do { const uint64_t t_now = __builtin_readcyclecounter(); tl_acc[k] += (uint32_t)(t_now - tl_t0); tl_t0 = t_now; } while (0)
-#else
-#define TL_T(k) do { } while (0)
-#endif
-
 struct alignas(16) TlRec {
   uint32_t k0, k1;  // Philox key = the read's Phred seed
   uint32_t dst;     // first base of the read in block coordinates x (x = byte in the text - the block's 64-byte-aligned origin)
   uint32_t lw;      // L | (2 * (source position & 15)) << 16 | rev << 31
 };
 
-// (-DSIMMR_ABLATE_TL_OR, timing only: plain LDS writes in their place — wrong bytes, the same addresses)
 SIMMR_DEV void tl_or32(uint32_t* p, uint32_t v) {
-#if defined(SIMMR_ABLATE_TL_OR)
-  *(volatile uint32_t*)p = v;
-#else
   (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);  // ds_or_b32, nothing returned
-#endif
 }
 SIMMR_DEV void tl_or64(uint64_t* p, uint64_t v) {
-#if defined(SIMMR_ABLATE_TL_OR)
-  *(volatile uint64_t*)p = v;
-#else
   (void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);  // ds_or_b64
-#endif
 }
 // sixteen bytes (w0 = the first four) ORed into the ring at text position p (any byte): five aligned words
 SIMMR_DEV void tl_or16(uint32_t* __restrict__ ringw, uint32_t p, uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
@@ -184,10 +166,6 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
     const uint32_t nc = G0->n_contigs < PHILOX_CBASE ? G0->n_contigs : PHILOX_CBASE;
     if (threadIdx.x < nc) cbase[threadIdx.x] = ((global_contig_ptr)G0->contigs)[threadIdx.x].base;
   }
-#if defined(TL_DIAG)
-  uint32_t tl_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t tl_t0 = __builtin_readcyclecounter();
-#endif
   uint64_t qsum = 0;
   uint32_t n_subst = 0, n_acgt = 0;
   uint32_t p_bases32 = 0;
@@ -273,9 +251,7 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
     uint8_t* const ringb = reinterpret_cast<uint8_t*>(ringw);
     uint8_t* const owner = &owner_all[wave][0];
     for (uint32_t phase = 0; phase * TL_GROUP < nr; phase++) {
-      TL_T(0);
       lds_barrier();  // the slots are free; (the first time) records, template and literals are staged
-      TL_T(1);
       if (on && (tix / TL_GROUP) == phase) {
         // header + '\n' into this read's slot, at the byte offset its place in the text has modulo 8 (the slot is zero elsewhere)
         uint8_t* h = tl_slots + (tix & (TL_GROUP - 1u)) * pitch8;
@@ -292,9 +268,7 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
         hf.read_id = read_id_base + (uint32_t)(first_unit + u0 + (tix >> 1));  // simulate.rs:85-89,274
         (void)fq_format_header_fetched(h, fq_segs, fq_n_segs, fq_tb, fq_lit, hf, h_rev ? '2' : '1', x_rec & 7u, h_ids, gidb, sidb);
       }
-      TL_T(2);
       lds_barrier();
-      TL_T(3);
       // ---- this wave's segment: reads R0 .. R0 + nsr of the block, one contiguous piece of text ----
       const uint32_t R0 = phase * TL_GROUP + wave * TL_SEG_READS;
       if (R0 >= nr) continue;
@@ -356,14 +330,10 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
           f.r = R0 + owner[item];
           f.ra = *reinterpret_cast<const uint4*>(&recA[f.r]);
           f.ci = item - ((uint32_t)r_gs[f.r] - it0);
-#if defined(SIMMR_ABLATE_CODES)
-          f.raw = ((uint64_t)recW[f.r] + f.ci) * 0x9E3779B97F4A7C15ull;
-#else
           // (`text` is deliberately not __restrict__: the compiler must then keep this load in front of the flush's stores
           // instead of sinking it to its use in the next round)
           const uint64_t wa = CACHED ? (uint64_t)(uintptr_t)packed0 + 4ull * ((uint64_t)recW[f.r] + f.ci) : (uint64_t)recW[f.r] + 4ull * f.ci;
           f.raw = *reinterpret_cast<global_u64_unaligned_ptr>(wa);
-#endif
         }
         return f;
       };
@@ -371,7 +341,6 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
       Fetch cur = fetch(s, e);
       for (;;) {
         if (e == s && j_e == j_s) break;  // (cannot happen: engine.hip sizes the ring so that a read always fits)
-        TL_T(4);
         // ---- how far the text will be complete after this round (every whole line below that point can go) ----
         const bool last = (e == n_it) && (j_e == nsr);
         uint32_t C;
@@ -398,7 +367,6 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
           extent(e, j_e, F2, e2, j_e2);
           nxt = fetch(e, e2);
         }
-        TL_T(7);
         // ---- items ----
         if (s + lane < e) {
           const uint32_t r = cur.r;
@@ -476,15 +444,10 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
           } else {
             s0 = asc[codes & 0xffu]; s1 = asc[(codes >> 8) & 0xffu]; s2 = asc[(codes >> 16) & 0xffu]; s3 = asc[codes >> 24];
           }
-#if !defined(SIMMR_ABLATE_STORES)
           // only the item's n live bytes may reach the image (what lies behind them is another piece's)
           tl_or16(ringw, p_q, qr[0] & bm.x, qr[1] & bm.y, qr[2] & bm.z, qr[3] & bm.w);
           tl_or16(ringw, p_s, s0 & bm.x, s1 & bm.y, s2 & bm.z, s3 & bm.w);
-#else
-          asm volatile("" :: "v"(qr[0]), "v"(qr[1]), "v"(qr[2]), "v"(qr[3]), "v"(s0), "v"(s1), "v"(s2), "v"(s3), "v"(p_q), "v"(p_s));
-#endif
         }
-        TL_T(5);
         // ---- the reads that start in this round: header + '\n' from the slot, "\n+\n", the closing '\n' ----
         {
           const uint32_t n_task = (j_e - j_s) * t9;
@@ -510,7 +473,6 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
             }
           }
         }
-        TL_T(6);
         // ---- the next round's item records and plane words take the place of this round's, in front of this round's stores
         // (a register move that waits for the load — it was asked for at the round's top, and the stores of the round before
         // are older still)
@@ -543,9 +505,6 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
             if (cx < limit) {
               const uint32_t lo = cx < x_begin ? x_begin - cx : 0u;
               const uint32_t hi = limit - cx < 16u ? limit - cx : 16u;
-#if defined(SIMMR_ABLATE_STORES)
-              asm volatile("" :: "v"(v[k].x), "v"(v[k].y), "v"(v[k].z), "v"(v[k].w), "v"(lo), "v"(hi));
-#else
               if (lo == 0u && hi == 16u) {
                 stream_store(reinterpret_cast<v4u32*>(gbase + cx), v[k]);
               } else if (lo < hi) {
@@ -556,19 +515,15 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
                 *reinterpret_cast<v4u32*>(&edge_v[wave][kk]) = v[k];
                 edge_m[wave][kk] = cx | (lo << 24) | ((hi & 15u) << 28);
               }
-#endif
             }
           }
         }
-        if (last) { TL_T(8); }
         if (last) break;
         F = F2; s = e; j_s = j_e; e = e2; j_e = j_e2;
-        TL_T(8);
         tl_wave_sync();  // (the zeroes are in place before the next round's pieces)
       }
       // the segment's shared chunks, bytewise (lane 0: the first chunk, lane 1: the last)
       tl_wave_sync();
-      TL_T(8);
       if (lane < 2u) {
         const uint32_t m = edge_m[wave][lane];
         if (m != 0xffffffffu) {
@@ -579,13 +534,6 @@ k_emit_text_lines(ProfileDev prof, const GenomeDev* __restrict__ genomes, uint32
       }
     }
   }
-#if defined(TL_DIAG)
-  TL_T(9);
-  if ((threadIdx.x & 63u) == 0) {
-    for (int k = 0; k < 10; k++) atomicAdd(&tl_diag[k], (unsigned long long)tl_acc[k]);
-    atomicAdd(&tl_diag[10], 1ull);
-  }
-#endif
   // ---- run counters (as k_emit_philox) ----
   __syncthreads();
   uint64_t p_bases = (uint64_t)p_bases32 + (threadIdx.x == 0 ? (uint64_t)spill_bases : 0ull);

@@ -1,11 +1,11 @@
-"""The whole-line form of the FASTQ text kernel (simmr_amd/csrc/text_lines.hip, the default of simmr_emit_fastq for paired
-plans of short reads) against the item form it replaces (k_emit_philox<TEXT>, SIMMR_TEXT_FORM=1): the same bytes and the
+"""The whole-line form of the FASTQ text kernel (simmr_amd/csrc/text_lines.hip, opt-in: SIMMR_TEXT_FORM=2 selects it for
+paired plans of short reads) against the item form that is the default (k_emit_philox<TEXT>, TEXT_FORM_DEFAULT 1): the same bytes and the
 same run counters for every read length a segment can hold, every header shape, shards that start anywhere in a run,
 genomes with N / '-' runs, several genomes in one plan and perfect-short; exact-capacity destinations between canaries;
 destinations the whole-line form does not take (not 16-byte aligned) fall back to the item form.
 
 The item form itself is pinned to the oracle through the column path (tests/test_gpu_fastq.py: text == framing of the
-emitted columns; tests/test_gpu_parity.py: columns == oracle), and those tests now run the whole-line form."""
+emitted columns; tests/test_gpu_parity.py: columns == oracle)."""
 import os
 
 import numpy as np

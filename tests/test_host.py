@@ -202,7 +202,7 @@ def test_header_states_the_shipped_philox_specification():
 
 def test_block_loop_tests_are_sized_from_the_kernels_constants():
     """tests/test_gpu_blockloop.py and test_results_do_not_depend_on_the_grid compute "this workgroup takes a second and a
-    third block" from these constants: the units of a block, the grid of the item kernel at its three launches (columns,
+    third block" from these constants: the units of a block, the grid of the item kernel, defined once for its three forms (columns,
     the copy-only form, the text), and the grids of the perfect-short and lane-per-read kernels.  If one of them changes,
     those tests have to be resized — they assert their premise, and this test says where it comes from."""
     kernels = (ROOT / "simmr_amd" / "csrc" / "kernels.hip").read_text()
@@ -210,15 +210,15 @@ def test_block_loop_tests_are_sized_from_the_kernels_constants():
     for needle in ("#define PHILOX_UNITS 128u", "#define PHILOX_CBASE 64u", "#define PERFECT_GROUP 256u", "#define LANES_WG 512",
                    "#define PHILOX_MAP_ITEMS 4096u", "for (uint64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {"):
         assert needle in kernels, needle
-    grid = "std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);"
-    assert engine.count("const uint32_t grid = (uint32_t)" + grid) == 2, "the column launch and the TEXT launch"
-    assert engine.count("const uint32_t cgrid = (uint32_t)std::min<uint64_t>(cblocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);") == 1, "COPY_ONLY"
-    assert engine.count("blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;") == 3
+    # one definition each (item_launch, philox_escq), which every launch of the item kernel goes through
+    assert engine.count("std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu)") == 1
+    assert engine.count("blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS") == 1
     for needle in ("uint32_t philox_wgs_per_cu = 128;",
                    "std::min<uint64_t>(groups, (uint64_t)e->n_cu * 8 * e->perfect_mult);",
                    "std::min<uint64_t>(wgs, (uint64_t)e->n_cu * (uint64_t)per_cu * e->lanes_mult);",
-                   "bool escq = (out->qual_offset & 0xffu) + e->prof.philox_qmax1 <= 127u;",
-                   "bool escq = 33u + e->prof.philox_qmax1 <= 127u;"):
+                   "static bool philox_escq(const simmr_engine* e, uint32_t offset) { return offset + e->prof.philox_qmax1 <= 127u; }",
+                   "philox_escq(e, out->qual_offset & 0xffu)",
+                   "philox_escq(e, 33u)"):
         assert needle in engine, needle
 
 

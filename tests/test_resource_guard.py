@@ -46,7 +46,8 @@ def test_counter_mode_item_kernel_every_instantiation(kernels):
 
 
 def test_whole_line_text_kernel(kernels):
-    """k_emit_text_lines (text_lines.hip, what simmr_emit_fastq runs for paired short reads): nine instantiations, three
+    """k_emit_text_lines (text_lines.hip, what simmr_emit_fastq runs for paired short reads under SIMMR_TEXT_FORM=2; the item form
+    is the default, TEXT_FORM_DEFAULT 1): nine instantiations, three
     waves per SIMD without scratch, and — the binding number — static LDS that leaves room for the header slots of the
     reference's default header format beside THREE workgroups per CU (160 KB): 128 slots x 136 bytes = 17 408 bytes."""
     ks = _named(kernels, r"k_emit_text_lines<")

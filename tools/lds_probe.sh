@@ -1,7 +1,7 @@
 #!/bin/bash
 # Which LDS access of k_emit_philox owns its bank-conflict cycles: the LDS counters of the product
-# library and of the differential builds that compile one piece out (`make ablate`: lookup = no jtab gathers, draws = no
-# Philox / lookups / plane load, items = one round of items per block), per launch of the default bench command, and of
+# library and of any measurement builds given beside it (`make variant`; profiles/r4/lds_conflicts_k_emit_philox.md was
+# made with builds that compiled one piece out each, whose switches have left the sources), per launch of the default bench command, and of
 # the TEXT form.  usage: tools/lds_probe.sh <out-dir-under-gpurun_out> name=lib [name=lib ...]
 out="$1"; shift
 S="SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_UNALIGNED_STALL SQ_LDS_ADDR_CONFLICT;SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES"
