@@ -465,6 +465,55 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity);
 /* HIP-event time (ms) of the last simmr_fastq_plan_direct's device work (size pass + scan). */
 int simmr_last_fastq_plan_ms(simmr_engine* e, float* ms);
 
+/* ---- ground truth per read: which bases of a read are not the reference's -------------------------------------
+ * Replaces nothing in the reference (it records where a read came from, never what it changed); it is what a caller
+ * who scores an aligner, an error corrector or a variant caller needs next to the reads.
+ *
+ * What counts as an edit.  For read r, L = |end[r] - start[r]| and lo = min(start[r], end[r]); the coordinates index
+ * Seq.seq of contig contig[r] of genome slot genome[r], as simmr_unstage_contig sees them.  The EXPECTED byte at offset
+ * j (0 <= j < L) of the read as written is
+ *   the staged base at lo + j                            for a forward read,
+ *   complement(staged base at lo + L - 1 - j)            for a read with SIMMR_FLAG_REVCOMP (util.rs:15-37);
+ * a staged 'N' or '-' is expected as itself (the exception plane) and is its own complement.  An EDIT is an offset whose
+ * byte in seq[] differs from the expected byte.  The edits of a read come in ascending edit_pos, reads in order, so
+ * nm[r] = edit_off[r + 1] - edit_off[r].  No profile of a successful run changes a read's length (a deleting splice
+ * already answers SIMMR_ERANGE), so every edit is a substitution: insertions and deletions are out of scope.
+ *
+ * The pass is a diff of seq[] as the caller hands it over against the staged planes, not a replay of the draws: it
+ * serves every profile, every rng mode, both layouts (reads->slot_bytes 0 and SIMMR_SLOT16, with the right-aligned
+ * reverse mates), paired and long reads, columns of any plan call — and bytes changed after the emit.  The result is a
+ * function of the inputs alone: edits are counted, the counts scanned, then written at their ranks (no atomics hand out
+ * slots), so launch geometry never changes a byte.
+ *
+ * `reads` must carry seq, qual, seq_off, start, end, contig, genome and flags (read_id may be NULL), with seq_capacity
+ * >= seq_off[n_reads] as for the emit that filled them. */
+typedef struct simmr_truth_out {       /* DEVICE pointers, caller-owned */
+  uint32_t* nm;         /* n_reads: altered bases of read r                                  */
+  uint64_t* edit_off;   /* n_reads + 1: CSR offsets into the edit columns                    */
+  uint32_t* edit_pos;   /* 0-based offset in the read AS WRITTEN (read orientation)          */
+  uint8_t*  edit_ref;   /* ASCII base the unaltered read would carry there                   */
+  uint8_t*  edit_alt;   /* ASCII base the read carries                                       */
+  uint8_t*  edit_qual;  /* the byte of qual[] at that position, as stored (qual_offset kept) */
+  uint64_t  reads_capacity, edits_capacity;
+} simmr_truth_out;
+/* Counts the edits of every read and scans the counts into buffers the engine holds; *n_edits = their total.
+ * SIMMR_EINVAL: a missing required column, or a read whose genome / contig entry is not staged or whose coordinates
+ * leave its contig or seq[] (found by a bounds check on the device and reported through an error word: such a read is
+ * never loaded from). */
+int simmr_truth_plan(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint64_t* n_edits);
+/* Writes the columns for the SAME reads.  nm and any edit_* may be NULL to skip that column; edit_off is required when
+ * an edit_* column is given.  SIMMR_ESTATE: no simmr_truth_plan for these columns (same seq, seq_off and layout).
+ * SIMMR_ERANGE, nothing written: reads_capacity < n_reads (with nm or edit_off given) or edits_capacity < n_edits (with
+ * an edit_* column given).
+ * Between the plan and the emit seq[], the columns and the staged genomes must stay as they were: the emit finds the
+ * edits again and places them by the plan's offsets.  Staging a genome discards the plan (SIMMR_ESTATE); bytes of seq[]
+ * changed in between are not detected — no store leaves a read's own range of the edit columns, but entries of that
+ * range may then be left unwritten or hold the changed bytes' edits. */
+int simmr_truth_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_truth_out* out);
+/* HIP-event time (ms) of the last simmr_truth_plan's device work (count + scan) plus that of the simmr_truth_emit after
+ * it, if any.  Synchronises the stream. */
+int simmr_last_truth_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

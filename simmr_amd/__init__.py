@@ -10,14 +10,14 @@ from .profiles import (AbundanceProfile, CustomAbundanceProfile, CustomShortErro
                        MinimalLongErrorProfile, MinimalShortErrorProfile, PerfectLongErrorProfile,
                        PerfectShortErrorProfile, UniformAbundanceProfile)
 
-__all__ = ["_abi", "SimmrError", "Engine", "Reads", "ErrorProfile", "AbundanceProfile",
+__all__ = ["_abi", "SimmrError", "Engine", "Reads", "Truth", "ErrorProfile", "AbundanceProfile",
            "PerfectShortErrorProfile", "MinimalShortErrorProfile", "PerfectLongErrorProfile",
            "MinimalLongErrorProfile", "CustomShortErrorProfile", "UniformAbundanceProfile", "ExactAbundanceProfile",
            "CustomAbundanceProfile"]
 
 
 def __getattr__(name):
-    if name in ("Engine", "Reads"):
+    if name in ("Engine", "Reads", "Truth"):
         from . import engine
         return getattr(engine, name)
     raise AttributeError(name)

@@ -109,6 +109,20 @@ class FastqNames(C.Structure):
     ]
 
 
+class TruthOut(C.Structure):
+    """struct simmr_truth_out (device pointers as raw addresses)"""
+    _fields_ = [
+        ("nm", C.c_void_p),
+        ("edit_off", C.c_void_p),
+        ("edit_pos", C.c_void_p),
+        ("edit_ref", C.c_void_p),
+        ("edit_alt", C.c_void_p),
+        ("edit_qual", C.c_void_p),
+        ("reads_capacity", C.c_uint64),
+        ("edits_capacity", C.c_uint64),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -154,6 +168,9 @@ SYMBOLS = {
     "simmr_fastq_plan_direct": (C.c_int, [C.c_void_p, C.c_char_p, _P(FastqNames), C.c_uint32, _P(C.c_uint64)]),
     "simmr_emit_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_last_fastq_plan_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_truth_plan": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64, _P(C.c_uint64)]),
+    "simmr_truth_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut)]),
+    "simmr_last_truth_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

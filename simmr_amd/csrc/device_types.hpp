@@ -39,6 +39,7 @@ struct GenomeDev {
 #define SIMMR_ERRBIT_KMER 16u /* simulate_errors chose an alternate the reference cannot splice (deletion / bad code / bad weights) */
 #define SIMMR_ERRBIT_PDF 4u /* custom PDF picked a bin without a range (a reference panic) or ran out of words */
 #define SIMMR_NOTEBIT_LONGREAD 32u /* not an error: a planned pair has reads longer than LONGREAD_MAXL (selects the TEXT form of the emit kernel) */
+#define SIMMR_ERRBIT_TRUTH 64u /* simmr_truth_plan: a read names a genome / contig that is not staged, or its window leaves the contig or seq[] (bit 32 is SIMMR_NOTEBIT_LONGREAD) */
 #define LONGREAD_MAXL 256u /* longest read the whole-line TEXT kernel takes (text_lines.hip: TL_MAXL) */
 
 // One CustomPDF entry (custom_short.rs:28-35): WeightedAliasIndex<f64> + per-bin Uniform<u32>,

@@ -23,6 +23,7 @@
 #include "kernels.hip"
 #include "text_lines.hip"
 #include "fastq_kernels.hip"
+#include "truth_kernels.hip"
 #include "custom_model.hpp"
 
 using namespace simmr;
@@ -148,6 +149,15 @@ struct simmr_engine {
   DevBuf fq_hlen;                  // header bytes per read (direct form)
   DevBuf fq_tpl_dev;               // the compiled header template, read by the kernels through a pointer
   DevBuf fd_seq, fd_qual, fd_seq_off, fd_start, fd_end, fd_contig, fd_genome, fd_read_id, fd_flags;  // columns of the unfused fallback
+
+  // ground truth per read (simmr_truth_plan / simmr_truth_emit): counts, their scan, an error word of its own (a plan
+  // of the next shard may own d_err), and the columns the plan was made for
+  DevBuf tr_nm, tr_off, tr_err;
+  hipEvent_t tr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // plan begin / end, emit begin / end
+  bool tr_ready = false, tr_emitted = false;
+  uint64_t tr_reads = 0, tr_edits = 0;
+  const void *tr_seq = nullptr, *tr_seq_off = nullptr;
+  uint32_t tr_slot = 0;
 
   int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -1185,6 +1195,8 @@ void simmr_engine_destroy(simmr_engine* e) {
                     &e->fq_blob, &e->fq_gid_off, &e->fq_gid_len, &e->fq_cbase, &e->fq_ncontig, &e->fq_coff, &e->fq_clen,
                     &e->fq_len, &e->fq_off, &e->m_genomes, &e->m_contig, &e->m_seed, &e->w_bytes, &e->u_off64, &e->fq_off64};
   for (DevBuf* b : bufs) b->release();
+  for (DevBuf* b : {&e->tr_nm, &e->tr_off, &e->tr_err}) b->release();
+  for (hipEvent_t ev : e->tr_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->ev_a) (void)hipEventDestroy(e->ev_a);
   if (e->ev_b) (void)hipEventDestroy(e->ev_b);
   if (e->n_emits == 0) { e->ring_c[0] = e->ev_c; e->ring_d[0] = e->ev_d; }
@@ -1227,6 +1239,7 @@ int simmr_stage_genome(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
                        const uint8_t* const* contig_ascii, const uint64_t* contig_len,
                        const uint64_t* contig_size) {
   if (!e) return SIMMR_EINVAL;
+  e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
   if (!contig_ascii || !contig_len || n_contigs == 0) return e->fail(SIMMR_EINVAL, "empty genome");
   HIP_TRY(e, hipSetDevice(e->device));
   if (genome_idx >= e->genomes.size()) e->genomes.resize(genome_idx + 1);
@@ -1267,6 +1280,7 @@ int simmr_stage_fasta(simmr_engine* e, uint32_t genome_idx, uint32_t n_records, 
                       const uint64_t* body_len, int contiguous, uint64_t min_size, uint64_t* base_count,
                       uint32_t* n_staged) {
   if (!e) return SIMMR_EINVAL;
+  e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
   if (!body || !body_len || !base_count || n_records == 0) return e->fail(SIMMR_EINVAL, "empty FASTA");
   HIP_TRY(e, hipSetDevice(e->device));
   if (genome_idx >= e->genomes.size()) e->genomes.resize(genome_idx + 1);
@@ -1347,6 +1361,7 @@ int simmr_stage_fasta(simmr_engine* e, uint32_t genome_idx, uint32_t n_records, 
 int simmr_stage_synthetic(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
                           const uint64_t* contig_len, uint64_t splitmix_seed) {
   if (!e) return SIMMR_EINVAL;
+  e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
   if (!contig_len || n_contigs == 0) return e->fail(SIMMR_EINVAL, "empty genome");
   HIP_TRY(e, hipSetDevice(e->device));
   if (genome_idx >= e->genomes.size()) e->genomes.resize(genome_idx + 1);
@@ -2351,6 +2366,102 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
   HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
   hipError_t s = hipGetLastError();
   if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "fastq launch failed: %s", hipGetErrorString(s));
+  return SIMMR_OK;
+}
+
+// ---- ground truth per read (include/simmr_hip.h) ------------------------------------------------------------------
+static TruthReads truth_reads(const simmr_reads_out* reads) {
+  return TruthReads{reads->seq, reads->qual, reads->seq_off, reads->start, reads->end, reads->contig, reads->genome,
+                    reads->flags, reads->seq_capacity, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
+}
+static uint32_t truth_grid(const simmr_engine* e, uint64_t n_reads) {
+  const uint64_t n_batches = (n_reads + TRUTH_WG_READS - 1) / TRUTH_WG_READS;
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_batches, (uint64_t)e->n_cu * TRUTH_WGS_PER_CU));
+}
+
+int simmr_truth_plan(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint64_t* n_edits) {
+  if (!e) return SIMMR_EINVAL;
+  e->tr_ready = false;
+  e->tr_emitted = false;
+  if (!reads || !n_edits) return e->fail(SIMMR_EINVAL, "simmr_truth_plan: NULL argument");
+  if (!reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags ||
+      (n_reads > 0 && (!reads->seq || !reads->qual)))
+    return e->fail(SIMMR_EINVAL, "simmr_truth_plan needs seq, qual, seq_off, start, end, contig, genome and flags");
+  if (reads->slot_bytes > 1u && reads->slot_bytes != SIMMR_SLOT16) return e->fail(SIMMR_EINVAL, "reads->slot_bytes is 0 (compact) or 16");
+  HIP_TRY(e, hipSetDevice(e->device));
+  for (hipEvent_t& ev : e->tr_ev)
+    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
+  if (!e->tr_nm.ensure(std::max<uint64_t>(n_reads, 1) * 4) || !e->tr_err.ensure(64))
+    return e->fail(SIMMR_ENOMEM, "truth count allocation failed");
+  HIP_TRY(e, hipMemsetAsync(e->tr_err.p, 0, 64, e->stream));
+  HIP_TRY(e, hipEventRecord(e->tr_ev[0], e->stream));
+  if (n_reads > 0)
+    hipLaunchKernelGGL(k_truth<false>, dim3(truth_grid(e, n_reads)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
+                       (uint32_t)e->genomes.size(), truth_reads(reads), n_reads, e->tr_nm.as<uint32_t>(),
+                       (const uint64_t*)nullptr, TruthCols{nullptr, nullptr, nullptr, nullptr}, e->tr_err.as<uint32_t>());
+  uint64_t total = 0;
+  int rc;
+  if ((rc = scan_scaled<uint32_t>(e, e->tr_nm, n_reads, 1u, e->tr_off, &total))) return rc;
+  HIP_TRY(e, hipEventRecord(e->tr_ev[1], e->stream));
+  uint32_t errw = 0;
+  HIP_TRY(e, hipMemcpyAsync(&errw, e->tr_err.p, 4, hipMemcpyDeviceToHost, e->stream));
+  if ((rc = sync_check(e, "truth count readback"))) return rc;
+  if (errw & SIMMR_ERRBIT_TRUTH)
+    return e->fail(SIMMR_EINVAL, "a read names a genome or contig that is not staged, or its coordinates leave the contig or seq[]");
+  e->tr_reads = n_reads;
+  e->tr_edits = total;
+  e->tr_seq = reads->seq;
+  e->tr_seq_off = reads->seq_off;
+  e->tr_slot = reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u;
+  e->tr_ready = true;
+  *n_edits = total;
+  return SIMMR_OK;
+}
+
+int simmr_truth_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_truth_out* out) {
+  if (!e) return SIMMR_EINVAL;
+  e->tr_emitted = false;  // (simmr_last_truth_ms: an emit that fails adds nothing to the plan's time)
+  if (!reads || !out) return e->fail(SIMMR_EINVAL, "simmr_truth_emit: NULL argument");
+  if (!e->tr_ready || reads->seq != e->tr_seq || reads->seq_off != e->tr_seq_off ||
+      (reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u) != e->tr_slot)
+    return e->fail(SIMMR_ESTATE, "simmr_truth_emit called without a simmr_truth_plan for these columns");
+  if (!reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags || (e->tr_reads > 0 && !reads->qual))
+    return e->fail(SIMMR_EINVAL, "simmr_truth_emit needs seq, qual, seq_off, start, end, contig, genome and flags");
+  const bool any_edit = out->edit_pos || out->edit_ref || out->edit_alt || out->edit_qual;
+  if (any_edit && !out->edit_off) return e->fail(SIMMR_EINVAL, "edit columns without edit_off");
+  if ((out->nm || out->edit_off) && out->reads_capacity < e->tr_reads)
+    return e->fail(SIMMR_ERANGE, "reads_capacity %llu < %llu reads planned", (unsigned long long)out->reads_capacity,
+                   (unsigned long long)e->tr_reads);
+  if (any_edit && out->edits_capacity < e->tr_edits)
+    return e->fail(SIMMR_ERANGE, "edits_capacity %llu < %llu edits planned", (unsigned long long)out->edits_capacity,
+                   (unsigned long long)e->tr_edits);
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipEventRecord(e->tr_ev[2], e->stream));
+  if (out->nm && e->tr_reads > 0)
+    HIP_TRY(e, hipMemcpyAsync(out->nm, e->tr_nm.p, e->tr_reads * 4, hipMemcpyDeviceToDevice, e->stream));
+  if (out->edit_off)
+    HIP_TRY(e, hipMemcpyAsync(out->edit_off, e->tr_off.p, (e->tr_reads + 1) * 8, hipMemcpyDeviceToDevice, e->stream));
+  if (any_edit && e->tr_edits > 0)
+    hipLaunchKernelGGL(k_truth<true>, dim3(truth_grid(e, e->tr_reads)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
+                       (uint32_t)e->genomes.size(), truth_reads(reads), e->tr_reads, (uint32_t*)nullptr,
+                       (const uint64_t*)e->tr_off.as<uint64_t>(), TruthCols{out->edit_pos, out->edit_ref, out->edit_alt, out->edit_qual},
+                       e->tr_err.as<uint32_t>());
+  HIP_TRY(e, hipEventRecord(e->tr_ev[3], e->stream));
+  hipError_t s = hipGetLastError();
+  if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "truth launch failed: %s", hipGetErrorString(s));
+  e->tr_emitted = true;
+  return SIMMR_OK;
+}
+
+int simmr_last_truth_ms(simmr_engine* e, float* ms) {
+  if (!e || !ms) return SIMMR_EINVAL;
+  if (!e->tr_ready) return e->fail(SIMMR_ESTATE, "no truth plan yet");
+  int rc = sync_check(e, "truth");
+  if (rc) return rc;
+  float a = 0.f, b = 0.f;
+  HIP_TRY(e, hipEventElapsedTime(&a, e->tr_ev[0], e->tr_ev[1]));
+  if (e->tr_emitted) HIP_TRY(e, hipEventElapsedTime(&b, e->tr_ev[2], e->tr_ev[3]));
+  *ms = a + b;
   return SIMMR_OK;
 }
 

@@ -111,6 +111,32 @@ class Reads:
         }
 
 
+@dataclass
+class Truth:
+    """Ground truth per read (simmr_truth_plan / simmr_truth_emit) in HBM: nm[r] altered bases of read r, and their CSR
+    edit lists — offset in the read as written, the base the unaltered read would carry, the base it carries, and the
+    byte of qual[] there."""
+    nm: "object"
+    edit_off: "object"
+    edit_pos: "object"
+    edit_ref: "object"
+    edit_alt: "object"
+    edit_qual: "object"
+    n_reads: int
+    n_edits: int
+
+    def to_host(self) -> dict:
+        n, m = self.n_reads, self.n_edits
+        return {
+            "nm": self.nm[:n].cpu().numpy().astype(np.uint32),
+            "edit_off": self.edit_off[: n + 1].cpu().numpy().astype(np.uint64),
+            "edit_pos": self.edit_pos[:m].cpu().numpy().astype(np.uint32),
+            "edit_ref": self.edit_ref[:m].cpu().numpy(),
+            "edit_alt": self.edit_alt[:m].cpu().numpy(),
+            "edit_qual": self.edit_qual[:m].cpu().numpy(),
+        }
+
+
 class Engine:
     """One engine == one GPU == one host thread (include/simmr_hip.h)."""
 
@@ -339,6 +365,37 @@ class Engine:
     def last_fastq_plan_ms(self) -> float:
         ms = C.c_float()
         self._check(self.lib.simmr_last_fastq_plan_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    # -- ground truth per read ------------------------------------------------------
+    def truth_plan(self, reads: Reads) -> int:
+        """Counts the edits of `reads` against the staged genomes (simmr_truth_plan); returns their total."""
+        pod = reads.pod()
+        total = C.c_uint64(0)
+        self._check(self.lib.simmr_truth_plan(self._h, C.byref(pod), reads.n_reads, C.byref(total)))
+        return int(total.value)
+
+    def truth(self, reads: Reads) -> Truth:
+        """Mismatch counts and edit lists of `reads` as CUDA tensors (simmr_truth_plan + simmr_truth_emit)."""
+        torch = _torch()
+        m = self.truth_plan(reads)
+        n = reads.n_reads
+        t = Truth(nm=torch.empty(max(n, 1), dtype=torch.int32, device=self.device),
+                  edit_off=torch.empty(n + 1, dtype=torch.int64, device=self.device),
+                  edit_pos=torch.empty(max(m, 1), dtype=torch.int32, device=self.device),
+                  edit_ref=torch.empty(max(m, 1), dtype=torch.uint8, device=self.device),
+                  edit_alt=torch.empty(max(m, 1), dtype=torch.uint8, device=self.device),
+                  edit_qual=torch.empty(max(m, 1), dtype=torch.uint8, device=self.device),
+                  n_reads=n, n_edits=m)
+        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
+                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), n, m)
+        pod = reads.pod()
+        self._check(self.lib.simmr_truth_emit(self._h, C.byref(pod), C.byref(out)))
+        return t
+
+    def last_truth_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_truth_ms(self._h, C.byref(ms)))
         return ms.value
 
     # -- counters / timing --------------------------------------------------------

@@ -274,6 +274,54 @@ bool write_to_fastq(const std::string& genome_uuid, const Genome& genome, const 
   return true;
 }
 
+// --------------------------------------------------------------- ground truth per read
+static const char* const TRUTH_TSV_HEADER = "read_id\tpair\tgenome_id\tsequence_id\tstart\tend\tstrand\tlength\tNM\tedits\n";
+
+// the line of read r; gid / sid: its genome's and sequence's id
+static void truth_line(std::string* out, uint64_t r, bool paired, uint32_t read_id, const char* gid, const char* sid, uint64_t start,
+                       uint64_t end, uint8_t flags, uint32_t nm, const uint64_t* edit_off, const uint32_t* edit_pos,
+                       const uint8_t* edit_ref, const uint8_t* edit_alt, const uint8_t* edit_qual, uint32_t qual_offset) {
+  char buf[160];
+  const uint64_t len = end > start ? end - start : start - end;
+  snprintf(buf, sizeof buf, "%u\t%d\t", read_id, paired ? (int)(r & 1) + 1 : 0);
+  *out += buf; *out += gid; *out += '\t'; *out += sid;
+  snprintf(buf, sizeof buf, "\t%llu\t%llu\t%c\t%llu\t%u\t", (unsigned long long)start, (unsigned long long)end,
+           (flags & SIMMR_FLAG_REVCOMP) ? '-' : '+', (unsigned long long)len, nm);
+  *out += buf;
+  if (edit_off[r] == edit_off[r + 1]) *out += '*';
+  for (uint64_t i = edit_off[r]; i < edit_off[r + 1]; i++) {
+    snprintf(buf, sizeof buf, "%s%u:%c>%c:%d", i > edit_off[r] ? "," : "", edit_pos[i], (char)edit_ref[i], (char)edit_alt[i],
+             (int)edit_qual[i] - (int)qual_offset);
+    *out += buf;
+  }
+  *out += '\n';
+}
+
+bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads, const HostTruth& t, uint32_t qual_offset,
+                     const std::string& output, bool with_header, std::string* err) {
+  FILE* f = fopen(output.c_str(), "ab");
+  if (!f) { *err = std::string("cannot open ") + output; return false; }
+  std::string text;
+  if (with_header) text += TRUTH_TSV_HEADER;
+  bool ok = true;
+  for (uint64_t r = 0; r < reads.n_reads && ok; r++) {
+    if (reads.genome[r] >= genomes.size() || reads.contig[r] >= genomes[reads.genome[r]].sequence.size()) {
+      *err = "read " + std::to_string(r) + " names a genome or sequence the run does not have";
+      ok = false;
+      break;
+    }
+    const Genome& g = genomes[reads.genome[r]];
+    truth_line(&text, r, reads.paired, reads.read_id[r], g.uuid.c_str(), g.sequence[reads.contig[r]].id.c_str(), reads.start[r],
+               reads.end[r], reads.flags[r], t.nm[r], t.edit_off.data(), t.edit_pos.data(), t.edit_ref.data(), t.edit_alt.data(),
+               t.edit_qual.data(), qual_offset);
+    if (text.size() >= (1u << 20)) { ok = fwrite(text.data(), 1, text.size(), f) == text.size(); text.clear(); }
+  }
+  if (ok && !text.empty()) ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  if (fclose(f) != 0) ok = false;
+  if (!ok && err->empty()) *err = "short write to " + output;
+  return ok;
+}
+
 // --------------------------------------------------------------- error profiles
 
 static simmr_error_profile zero_pod() {
@@ -387,7 +435,10 @@ std::string usage() {
          "  --seed <N>                    Random seed\n"
          "  --size-adjusted               Adjust by genome size\n"
          "  --contiguous                  Treat separate sequences in a genome as one contiguous sequence\n"
-         "extensions: --device <N>  --devices <a,b,...>  --gamma <mean,std>  --per-read-lengths  --uniform-start  --host-fastq  --host-normalize  --device-chunk-reads <N>  --rng <reference|philox|philox-full>\n";
+         "extensions: --device <N>  --devices <a,b,...>  --gamma <mean,std>  --per-read-lengths  --uniform-start  --host-fastq  --host-normalize  --device-chunk-reads <N>  --rng <reference|philox|philox-full>\n"
+         "            --truth <FILE>  per-read ground truth as a TSV: read_id pair genome_id sequence_id start end strand length NM edits\n"
+         "                            (edits: * or pos:REF>ALT:Q, ...; found on the device by comparing every read with the staged genome;\n"
+         "                             not with --devices)\n";
 }
 
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
@@ -447,6 +498,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--contiguous") a->contiguous = true;
     else if (arg == "--host-fastq") a->host_fastq = true;
     else if (arg == "--host-normalize") a->host_normalize = true;
+    else if (arg == "--truth") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--truth'"; return false; } a->truth = v; }
     else if (arg == "--device-chunk-reads") { if (!need(&v) || !parse_u64(v, UINT64_MAX, &u) || u == 0) { *err = "invalid value for --device-chunk-reads"; return false; } a->device_chunk_reads = u; }
     else if (arg == "--devices") {
       if (!need(&v)) return false;
@@ -585,6 +637,32 @@ char* simmr_host_load_fasta(const char* path, int contiguous) {
   for (const Seq& s : g.sequence)
     out += s.id + "\t" + std::to_string(s.size) + "\t" + std::to_string(s.seq.size()) + "\t" + s.seq + "\n";
   return dup_str(out);
+}
+// The truth TSV of write_truth_tsv for columns given as plain arrays: genome_id[g] / n_contigs[g] per genome slot,
+// sequence_id flattened genome by genome (the shape of simmr_fastq_names).  Returns the text, or "ERR\t..." .
+char* simmr_host_truth_tsv(uint64_t n_reads, int paired, const uint32_t* read_id, const uint32_t* genome, const uint32_t* contig,
+                           const uint64_t* start, const uint64_t* end, const uint8_t* flags, const uint32_t* nm,
+                           const uint64_t* edit_off, const uint32_t* edit_pos, const uint8_t* edit_ref, const uint8_t* edit_alt,
+                           const uint8_t* edit_qual, uint32_t qual_offset, uint32_t n_genomes, const char* const* genome_id,
+                           const uint32_t* n_contigs, const char* const* sequence_id, int with_header, const char* path) {
+  std::vector<Genome> genomes(n_genomes);
+  size_t at = 0;
+  for (uint32_t g = 0; g < n_genomes; g++) {
+    genomes[g].uuid = genome_id[g];
+    for (uint32_t c = 0; c < n_contigs[g]; c++) { Seq s; s.id = sequence_id[at++]; genomes[g].sequence.push_back(std::move(s)); }
+  }
+  HostReads h;
+  h.n_reads = n_reads; h.paired = paired != 0;
+  h.read_id.assign(read_id, read_id + n_reads); h.genome.assign(genome, genome + n_reads); h.contig.assign(contig, contig + n_reads);
+  h.start.assign(start, start + n_reads); h.end.assign(end, end + n_reads); h.flags.assign(flags, flags + n_reads);
+  HostTruth t;
+  const uint64_t m = n_reads ? edit_off[n_reads] : 0;
+  t.nm.assign(nm, nm + n_reads); t.edit_off.assign(edit_off, edit_off + n_reads + 1);
+  t.edit_pos.assign(edit_pos, edit_pos + m); t.edit_ref.assign(edit_ref, edit_ref + m);
+  t.edit_alt.assign(edit_alt, edit_alt + m); t.edit_qual.assign(edit_qual, edit_qual + m);
+  std::string err;
+  if (!write_truth_tsv(genomes, h, t, qual_offset, path, with_header != 0, &err)) return dup_str("ERR\t" + err);
+  return dup_str("OK");
 }
 char* simmr_host_parse_genome_file(const char* path) {
   std::vector<GenomeRecord> recs;

@@ -76,6 +76,26 @@ struct DeviceOut {
   }
 };
 
+// The truth columns of one range's reads (simmr_truth_plan / simmr_truth_emit on the columns `d`), copied to the host.
+static bool device_truth(simmr_engine* eng, const simmr_reads_out* reads, uint64_t n_reads, HostTruth* t, std::string* err) {
+  uint64_t m = 0;
+  if (simmr_truth_plan(eng, reads, n_reads, &m) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  DeviceOut mem;  // (its allocation list only)
+  simmr_truth_out o{};
+  o.reads_capacity = n_reads; o.edits_capacity = m;
+  if (!(mem.alloc(&o.nm, n_reads) && mem.alloc(&o.edit_off, n_reads + 1) && mem.alloc(&o.edit_pos, m) && mem.alloc(&o.edit_ref, m) &&
+        mem.alloc(&o.edit_alt, m) && mem.alloc(&o.edit_qual, m))) { *err = "device allocation failed"; return false; }
+  if (simmr_truth_emit(eng, reads, &o) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  t->nm.resize(n_reads); t->edit_off.resize(n_reads + 1); t->edit_pos.resize(m); t->edit_ref.resize(m); t->edit_alt.resize(m); t->edit_qual.resize(m);
+  auto cp = [](void* d, const void* s, size_t n) { return n == 0 || hipMemcpy(d, s, n, hipMemcpyDeviceToHost) == hipSuccess; };
+  if (!(cp(t->nm.data(), o.nm, n_reads * 4) && cp(t->edit_off.data(), o.edit_off, (n_reads + 1) * 8) && cp(t->edit_pos.data(), o.edit_pos, m * 4) &&
+        cp(t->edit_ref.data(), o.edit_ref, m) && cp(t->edit_alt.data(), o.edit_alt, m) && cp(t->edit_qual.data(), o.edit_qual, m))) {
+    *err = "copy back failed";
+    return false;
+  }
+  return true;
+}
+
 // ---- output of one planned range ------------------------------------------------------------------------------------
 // A run is generated range by range of its units (pairs / long reads): the reference holds every read of a run in RAM
 // before it writes (main.rs:180-206, readme.md:219-220); here a range is what fits the device next to the reference
@@ -187,7 +207,8 @@ static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<G
   if (chunk_units == 0 || chunk_units > total_units) chunk_units = std::max<uint64_t>(total_units, 1);
   NameTables nt(genomes, sc.g0, sc.g1);
   std::string err;
-  bool use_device_text = !args.host_fastq;
+  // --truth reads the columns: the run takes the column route (the same bytes, include/simmr_hip.h)
+  bool use_device_text = !args.host_fastq && args.truth.empty();
   uint64_t text_bytes = 0, n_ranges = 0;
   TextDrain drain;
   if (use_device_text && !drain.open(args.output, &err)) return die(err);
@@ -224,8 +245,11 @@ static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<G
       DeviceOut d;
       if (!d.init(pi.n_reads, pi.total_bases, pi.slot_bytes)) return die("device allocation failed");
       if (sc.emit(eng, sc.id_base, &d.o) != SIMMR_OK) return die(simmr_last_error(eng));
+      HostTruth truth;
+      if (!args.truth.empty() && !device_truth(eng, &d.o, pi.n_reads, &truth, &err)) return die("--truth: " + err);
       HostReads h;
       if (!d.to_host(pi.n_reads, pi.total_bases, sc.paired, &h)) return die("copy back failed");
+      if (!args.truth.empty() && !write_truth_tsv(genomes, h, truth, d.o.qual_offset, args.truth, false, &err)) return die("--truth: " + err);
       uint64_t g_first = 0;  // first unit of genome gi in the scope
       for (size_t gi = sc.g0; gi < sc.g1; gi++) {
         const uint64_t g_units = sc.genome_units[gi - sc.g0];
@@ -413,6 +437,7 @@ static int run_main(int argc, char** argv) {
   if (!parse_cli_args(argc, argv, &args, &err, &help)) { fprintf(stderr, "error: %s\n\n%s", err.c_str(), usage().c_str()); return 2; }
   if (help) { fputs(usage().c_str(), stdout); return 0; }
 
+  if (!args.truth.empty() && !args.devices.empty()) return die("--truth does not combine with --devices: use --device");
   std::unique_ptr<ErrorProfile> eprofile = determine_error_profile(args, &err);  // main.rs:27
   if (!eprofile) return die(err);
   // main.rs:30-33
@@ -537,6 +562,10 @@ static int run_main(int argc, char** argv) {
   if (is_regular_file(args.output)) remove(args.output.c_str());  // (a pipe or a device given as the output is written to, not replaced)
   const std::string meta_path = args.output + ".tsv";
   if (exists(meta_path)) remove(meta_path.c_str());
+  if (!args.truth.empty()) {  // the header line; every range appends its reads
+    if (is_regular_file(args.truth)) remove(args.truth.c_str());
+    if (!write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, args.truth, true, &err)) return die("--truth: " + err);
+  }
 
   simmr_error_profile pod = eprofile->pod();
   if (args.rng_philox) {  // (extension) the counter mode, for the profiles that draw per base from a parametric law

@@ -91,6 +91,22 @@ bool write_to_fastq(const std::string& genome_uuid, const Genome& genome, const 
                     uint64_t first, uint64_t count, const std::string& output,
                     const std::string& header_format, bool append, std::string* err);
 
+// ---------------------------------------------------------------- ground truth per read (no reference counterpart)
+// Host copy of simmr_truth_out for the reads of one HostReads.
+struct HostTruth {
+  std::vector<uint32_t> nm;
+  std::vector<uint64_t> edit_off;
+  std::vector<uint32_t> edit_pos;
+  std::vector<uint8_t> edit_ref, edit_alt, edit_qual;  // edit_qual as stored (Phred + qual_offset)
+};
+// `simmr-hip --truth FILE`: one tab-separated line per read, in read order:
+//   read_id  pair  genome_id  sequence_id  start  end  strand  length  NM  edits
+// pair 1 / 2 (0 for long reads), strand '-' iff reverse-complemented, edits `*` or a comma-joined list of
+// pos:REF>ALT:Q (Q the decimal Phred).  reads.genome[r] indexes `genomes`.  with_header: the line of column names
+// first (simmr-hip writes it with no reads when the run starts; every range then appends its reads).  Appends to `output`.
+bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads, const HostTruth& truth, uint32_t qual_offset,
+                     const std::string& output, bool with_header, std::string* err);
+
 // ------------------------------------------------------- error_profiles/*.rs
 class ErrorProfile {  // error_profiles/base.rs:6-32 (the per-read methods run on the device)
  public:
@@ -194,6 +210,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::vector<int> devices;  // --devices a,b,...: one engine per entry (an ordinal may repeat), the run's ranges dealt to them in turn
   bool host_normalize = false;  // --host-normalize: normalise FASTA on the host instead of the device
   bool host_fastq = false;  // --host-fastq: frame the FASTQ on the host instead of the device
+  std::string truth;  // --truth FILE: per-read mismatch counts and edit lists (simmr_truth_plan / simmr_truth_emit) as a TSV
   uint64_t device_chunk_reads = 0;  // --device-chunk-reads: reads generated per device pass (0: what fits the free device memory)
   std::optional<std::pair<float, float>> gamma;  // --gamma mean,std
   bool uniform_start = false;                    // --uniform-start (SIMMR_START_UNIFORM)
