@@ -514,6 +514,57 @@ int simmr_truth_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_
  * it, if any.  Synchronises the stream. */
 int simmr_last_truth_ms(simmr_engine* e, float* ms);
 
+/* ---- run statistics: quality, base and mismatch tables of the reads of a run ------------------------------------
+ * Replaces nothing in the reference.  The eight run counters are sums; these tables are the distributions a user of a
+ * read simulator looks at — quality per cycle, base composition, which substitutions occurred, how often a base of
+ * Phred q was altered — counted on the device from the columns in HBM, without draining the reads.
+ *
+ * Definitions.  EXPECTED byte, EDIT, lo and L = |end[r] - start[r]| are exactly simmr_truth_out's (above): coordinates
+ * into Seq.seq, reverse mates complemented, a staged 'N' or '-' expected as itself.  The WRITTEN byte at offset j is
+ * seq[seq_off[r] + j]; the quality at offset j is qual[qbase + j] with qbase = seq_off[r] (compact) or seq_off[r] & ~15
+ * (SIMMR_SLOT16), and q = (that byte - reads->qual_offset) & 255.  A byte's CLASS is 0 1 2 3 for 'A' 'C' 'G' 'T' and 4
+ * ("other") for every other byte, 'N' and '-' among them.  Read r belongs to SET r % n_sets: n_sets = 2 for a paired
+ * shard (mate 1 / mate 2), 1 for long reads (everything in set 0).
+ * Offsets at or above SIMMR_STATS_CYCLES enter every table except the four cycle_* ones (they are not clamped into a
+ * last bin).
+ *
+ * Every table is an integer sum over reads, so the result is a function of the inputs alone — launch geometry never
+ * changes a number — and the tables of several adds, ranges, engines or ranks add up entry by entry (the caller sums
+ * them; the library offers no all-reduce for them). */
+#define SIMMR_STATS_CYCLES  512u   /* per-cycle tables cover offsets 0..511 of a read as written */
+#define SIMMR_STATS_NM_BINS 64u
+
+typedef struct simmr_run_stats {            /* HOST memory, every entry a uint64_t */
+  uint64_t reads[2];                        /* reads of set m, L = 0 included */
+  uint64_t bases[2];                        /* sum of L */
+  uint64_t qual_n[256];                     /* bases by q = (qual byte - qual_offset) & 255 */
+  uint64_t qual_mismatch[256];              /* of those, edits (simmr_truth_out's definition of an edit) */
+  uint64_t pair[5][5];                      /* [expected class][written class], classes A C G T other; every base counted once */
+  uint64_t nm_hist[SIMMR_STATS_NM_BINS];    /* reads (L = 0 included) by number of edits, clamped to the last bin */
+  uint64_t gc_hist[101];                    /* reads with L > 0 by floor(100 * (#'G' + #'C' written) / L) */
+  uint64_t cycle_n[2][SIMMR_STATS_CYCLES];  /* reads of set m with L > j */
+  uint64_t cycle_qsum[2][SIMMR_STATS_CYCLES];      /* sum of q at offset j */
+  uint64_t cycle_mismatch[2][SIMMR_STATS_CYCLES];  /* edits at offset j */
+  uint64_t cycle_base[2][SIMMR_STATS_CYCLES][5];   /* written class at offset j */
+} simmr_run_stats;
+
+/* Allocates the engine's tables on first use and zeroes them and the sticky error (on the engine's stream). */
+int simmr_stats_reset(simmr_engine* e);
+/* Adds the reads of `reads` to the tables.  Only enqueues on the engine's stream — no synchronisation — so it can sit in
+ * a step loop beside the emit; staging a genome afterwards does not discard the tables (they are sums over reads already
+ * seen), but the genomes the columns name must be staged when the add runs.
+ * `reads` must carry seq, qual, seq_off, start, end, contig, genome and flags (read_id may be NULL).
+ * SIMMR_EINVAL, at once: n_sets other than 1 or 2, or a missing required column.  SIMMR_ESTATE: no simmr_stats_reset yet.
+ * A read whose genome or contig entry is not staged, whose window leaves its contig or seq[] (simmr_truth_plan's bounds
+ * check), or which is longer than 65 535 bases (the longest read the library writes; the bound keeps the kernel's 32-bit
+ * partial counts from wrapping) is never loaded from: it sets a sticky error word, simmr_stats_read then answers
+ * SIMMR_EINVAL and copies nothing, and the tables are unspecified until the next simmr_stats_reset. */
+int simmr_stats_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint32_t n_sets);
+/* Synchronises the stream and copies the tables to *dst_host.  SIMMR_ESTATE before any simmr_stats_reset. */
+int simmr_stats_read(simmr_engine* e, simmr_run_stats* dst_host);
+/* HIP-event time (ms) of the last simmr_stats_add's device work.  Synchronises the stream. */
+int simmr_last_stats_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -123,6 +123,26 @@ class TruthOut(C.Structure):
     ]
 
 
+STATS_CYCLES, STATS_NM_BINS = 512, 64
+
+
+class RunStats(C.Structure):
+    """struct simmr_run_stats (host memory)"""
+    _fields_ = [
+        ("reads", C.c_uint64 * 2),
+        ("bases", C.c_uint64 * 2),
+        ("qual_n", C.c_uint64 * 256),
+        ("qual_mismatch", C.c_uint64 * 256),
+        ("pair", C.c_uint64 * 5 * 5),
+        ("nm_hist", C.c_uint64 * STATS_NM_BINS),
+        ("gc_hist", C.c_uint64 * 101),
+        ("cycle_n", C.c_uint64 * STATS_CYCLES * 2),
+        ("cycle_qsum", C.c_uint64 * STATS_CYCLES * 2),
+        ("cycle_mismatch", C.c_uint64 * STATS_CYCLES * 2),
+        ("cycle_base", C.c_uint64 * 5 * STATS_CYCLES * 2),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -171,6 +191,10 @@ SYMBOLS = {
     "simmr_truth_plan": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64, _P(C.c_uint64)]),
     "simmr_truth_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut)]),
     "simmr_last_truth_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_stats_reset": (C.c_int, [C.c_void_p]),
+    "simmr_stats_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64, C.c_uint32]),
+    "simmr_stats_read": (C.c_int, [C.c_void_p, _P(RunStats)]),
+    "simmr_last_stats_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

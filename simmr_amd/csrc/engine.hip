@@ -24,6 +24,7 @@
 #include "text_lines.hip"
 #include "fastq_kernels.hip"
 #include "truth_kernels.hip"
+#include "stats_kernels.hip"
 #include "custom_model.hpp"
 
 using namespace simmr;
@@ -158,6 +159,12 @@ struct simmr_engine {
   uint64_t tr_reads = 0, tr_edits = 0;
   const void *tr_seq = nullptr, *tr_seq_off = nullptr;
   uint32_t tr_slot = 0;
+
+  // run statistics (simmr_stats_reset / simmr_stats_add / simmr_stats_read): the simmr_run_stats the kernel adds to,
+  // followed by its sticky error word
+  DevBuf st_tab;
+  hipEvent_t st_ev[2] = {nullptr, nullptr};  // the last add's begin / end
+  bool st_ready = false, st_timed = false;
 
   int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -1197,6 +1204,8 @@ void simmr_engine_destroy(simmr_engine* e) {
   for (DevBuf* b : bufs) b->release();
   for (DevBuf* b : {&e->tr_nm, &e->tr_off, &e->tr_err}) b->release();
   for (hipEvent_t ev : e->tr_ev) if (ev) (void)hipEventDestroy(ev);
+  e->st_tab.release();
+  for (hipEvent_t ev : e->st_ev) if (ev) (void)hipEventDestroy(ev);
   if (e->ev_a) (void)hipEventDestroy(e->ev_a);
   if (e->ev_b) (void)hipEventDestroy(e->ev_b);
   if (e->n_emits == 0) { e->ring_c[0] = e->ev_c; e->ring_d[0] = e->ev_d; }
@@ -2462,6 +2471,70 @@ int simmr_last_truth_ms(simmr_engine* e, float* ms) {
   HIP_TRY(e, hipEventElapsedTime(&a, e->tr_ev[0], e->tr_ev[1]));
   if (e->tr_emitted) HIP_TRY(e, hipEventElapsedTime(&b, e->tr_ev[2], e->tr_ev[3]));
   *ms = a + b;
+  return SIMMR_OK;
+}
+
+// ---- run statistics (include/simmr_hip.h) -----------------------------------------------------------------------
+static const size_t STATS_BYTES = sizeof(simmr_run_stats) + 8;  // the tables and the error word behind them
+
+int simmr_stats_reset(simmr_engine* e) {
+  if (!e) return SIMMR_EINVAL;
+  HIP_TRY(e, hipSetDevice(e->device));
+  for (hipEvent_t& ev : e->st_ev)
+    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
+  if (!e->st_tab.ensure(STATS_BYTES)) return e->fail(SIMMR_ENOMEM, "statistics allocation failed");
+  HIP_TRY(e, hipMemsetAsync(e->st_tab.p, 0, STATS_BYTES, e->stream));
+  e->st_ready = true;
+  e->st_timed = false;
+  return SIMMR_OK;
+}
+
+int simmr_stats_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint32_t n_sets) {
+  if (!e) return SIMMR_EINVAL;
+  if (!reads) return e->fail(SIMMR_EINVAL, "simmr_stats_add: NULL argument");
+  if (n_sets != 1u && n_sets != 2u) return e->fail(SIMMR_EINVAL, "simmr_stats_add: n_sets is 1 or 2");
+  if (!reads->seq || !reads->qual || !reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags)
+    return e->fail(SIMMR_EINVAL, "simmr_stats_add needs seq, qual, seq_off, start, end, contig, genome and flags");
+  if (reads->slot_bytes > 1u && reads->slot_bytes != SIMMR_SLOT16) return e->fail(SIMMR_EINVAL, "reads->slot_bytes is 0 (compact) or 16");
+  if (!e->st_ready) return e->fail(SIMMR_ESTATE, "simmr_stats_add called before simmr_stats_reset");
+  HIP_TRY(e, hipSetDevice(e->device));
+  HIP_TRY(e, hipEventRecord(e->st_ev[0], e->stream));
+  if (n_reads > 0) {
+    const uint64_t n_batches = (n_reads + STATS_WG_READS - 1) / STATS_WG_READS;
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_batches, (uint64_t)e->n_cu * STATS_WGS_PER_CU));
+    unsigned long long* tab = e->st_tab.as<unsigned long long>();
+    hipLaunchKernelGGL(k_read_stats, dim3(grid), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(), (uint32_t)e->genomes.size(),
+                       truth_reads(reads), n_reads, n_sets, reads->qual_offset, tab, (uint32_t*)(tab + STATS_TABLE_WORDS));
+  }
+  HIP_TRY(e, hipEventRecord(e->st_ev[1], e->stream));
+  hipError_t s = hipGetLastError();
+  if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "statistics launch failed: %s", hipGetErrorString(s));
+  e->st_timed = true;
+  return SIMMR_OK;
+}
+
+int simmr_stats_read(simmr_engine* e, simmr_run_stats* dst_host) {
+  if (!e) return SIMMR_EINVAL;
+  if (!dst_host) return e->fail(SIMMR_EINVAL, "simmr_stats_read: NULL argument");
+  if (!e->st_ready) return e->fail(SIMMR_ESTATE, "simmr_stats_read called before simmr_stats_reset");
+  HIP_TRY(e, hipSetDevice(e->device));
+  std::vector<uint64_t> host(STATS_BYTES / 8);
+  HIP_TRY(e, hipMemcpyAsync(host.data(), e->st_tab.p, STATS_BYTES, hipMemcpyDeviceToHost, e->stream));
+  int rc = sync_check(e, "statistics readback");
+  if (rc) return rc;
+  if (host[STATS_TABLE_WORDS] != 0)
+    return e->fail(SIMMR_EINVAL, "a read added since the last simmr_stats_reset names a genome or contig that is not staged, "
+                                 "its coordinates leave the contig or seq[], or it is longer than 65535 bases");
+  memcpy(dst_host, host.data(), sizeof(simmr_run_stats));
+  return SIMMR_OK;
+}
+
+int simmr_last_stats_ms(simmr_engine* e, float* ms) {
+  if (!e || !ms) return SIMMR_EINVAL;
+  if (!e->st_timed) return e->fail(SIMMR_ESTATE, "no simmr_stats_add yet");
+  int rc = sync_check(e, "statistics");
+  if (rc) return rc;
+  HIP_TRY(e, hipEventElapsedTime(ms, e->st_ev[0], e->st_ev[1]));
   return SIMMR_OK;
 }
 

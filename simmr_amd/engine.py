@@ -398,6 +398,27 @@ class Engine:
         self._check(self.lib.simmr_last_truth_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- run statistics -------------------------------------------------------------
+    def stats_reset(self):
+        """Zeroes the engine's run-statistics tables and their sticky error (simmr_stats_reset)."""
+        self._check(self.lib.simmr_stats_reset(self._h))
+
+    def stats_add(self, reads: Reads, n_sets: int):
+        """Adds `reads` to the tables (simmr_stats_add): enqueues only.  n_sets 2: mates 1 / 2 of a paired shard; 1: long reads."""
+        pod = reads.pod()
+        self._check(self.lib.simmr_stats_add(self._h, C.byref(pod), reads.n_reads, int(n_sets)))
+
+    def stats(self) -> dict:
+        """The tables as numpy uint64 arrays with the names and shapes of struct simmr_run_stats (simmr_stats_read)."""
+        st = _abi.RunStats()
+        self._check(self.lib.simmr_stats_read(self._h, C.byref(st)))
+        return {name: np.ctypeslib.as_array(getattr(st, name)).astype(np.uint64) for name, _ in _abi.RunStats._fields_}
+
+    def last_stats_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_stats_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- counters / timing --------------------------------------------------------
     def counters(self) -> np.ndarray:
         host = (C.c_uint64 * _abi.N_COUNTERS)()

@@ -322,6 +322,36 @@ bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads,
   return ok;
 }
 
+// --------------------------------------------------------------- run statistics
+bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::string* err) {
+  std::string text = "table\tset\ti\tj\tcount\n";
+  char buf[96];
+  auto row = [&](const char* table, int set, int i, int j, uint64_t count) {
+    if (!count) return;
+    auto idx = [&](int v) { if (v < 0) text += "\t-"; else { snprintf(buf, sizeof buf, "\t%d", v); text += buf; } };
+    text += table; idx(set); idx(i); idx(j);
+    snprintf(buf, sizeof buf, "\t%llu\n", (unsigned long long)count);
+    text += buf;
+  };
+  for (int m = 0; m < 2; m++) row("reads", m, -1, -1, st.reads[m]);
+  for (int m = 0; m < 2; m++) row("bases", m, -1, -1, st.bases[m]);
+  for (int q = 0; q < 256; q++) row("qual_n", -1, q, -1, st.qual_n[q]);
+  for (int q = 0; q < 256; q++) row("qual_mismatch", -1, q, -1, st.qual_mismatch[q]);
+  for (int a = 0; a < 5; a++) for (int b = 0; b < 5; b++) row("pair", -1, a, b, st.pair[a][b]);
+  for (int i = 0; i < (int)SIMMR_STATS_NM_BINS; i++) row("nm_hist", -1, i, -1, st.nm_hist[i]);
+  for (int i = 0; i < 101; i++) row("gc_hist", -1, i, -1, st.gc_hist[i]);
+  for (int m = 0; m < 2; m++) for (int j = 0; j < (int)SIMMR_STATS_CYCLES; j++) row("cycle_n", m, j, -1, st.cycle_n[m][j]);
+  for (int m = 0; m < 2; m++) for (int j = 0; j < (int)SIMMR_STATS_CYCLES; j++) row("cycle_qsum", m, j, -1, st.cycle_qsum[m][j]);
+  for (int m = 0; m < 2; m++) for (int j = 0; j < (int)SIMMR_STATS_CYCLES; j++) row("cycle_mismatch", m, j, -1, st.cycle_mismatch[m][j]);
+  for (int m = 0; m < 2; m++) for (int j = 0; j < (int)SIMMR_STATS_CYCLES; j++) for (int c = 0; c < 5; c++) row("cycle_base", m, j, c, st.cycle_base[m][j][c]);
+  FILE* f = fopen(output.c_str(), "wb");
+  if (!f) { *err = std::string("cannot open ") + output; return false; }
+  bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  if (fclose(f) != 0) ok = false;
+  if (!ok) *err = "short write to " + output;
+  return ok;
+}
+
 // --------------------------------------------------------------- error profiles
 
 static simmr_error_profile zero_pod() {
@@ -438,7 +468,11 @@ std::string usage() {
          "extensions: --device <N>  --devices <a,b,...>  --gamma <mean,std>  --per-read-lengths  --uniform-start  --host-fastq  --host-normalize  --device-chunk-reads <N>  --rng <reference|philox|philox-full>\n"
          "            --truth <FILE>  per-read ground truth as a TSV: read_id pair genome_id sequence_id start end strand length NM edits\n"
          "                            (edits: * or pos:REF>ALT:Q, ...; found on the device by comparing every read with the staged genome;\n"
-         "                             not with --devices)\n";
+         "                             not with --devices)\n"
+         "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
+         "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
+         "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
+         "                            not with --devices\n";
 }
 
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
@@ -499,6 +533,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--host-fastq") a->host_fastq = true;
     else if (arg == "--host-normalize") a->host_normalize = true;
     else if (arg == "--truth") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--truth'"; return false; } a->truth = v; }
+    else if (arg == "--stats") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--stats'"; return false; } a->stats = v; }
     else if (arg == "--device-chunk-reads") { if (!need(&v) || !parse_u64(v, UINT64_MAX, &u) || u == 0) { *err = "invalid value for --device-chunk-reads"; return false; } a->device_chunk_reads = u; }
     else if (arg == "--devices") {
       if (!need(&v)) return false;
@@ -662,6 +697,13 @@ char* simmr_host_truth_tsv(uint64_t n_reads, int paired, const uint32_t* read_id
   t.edit_alt.assign(edit_alt, edit_alt + m); t.edit_qual.assign(edit_qual, edit_qual + m);
   std::string err;
   if (!write_truth_tsv(genomes, h, t, qual_offset, path, with_header != 0, &err)) return dup_str("ERR\t" + err);
+  return dup_str("OK");
+}
+// The statistics TSV of write_stats_tsv for a simmr_run_stats in host memory.  Returns "OK", or "ERR\t..." .
+char* simmr_host_stats_tsv(const simmr_run_stats* st, const char* path) {
+  std::string err;
+  if (!st || !path) return dup_str("ERR\tNULL argument");
+  if (!write_stats_tsv(*st, path, &err)) return dup_str("ERR\t" + err);
   return dup_str("OK");
 }
 char* simmr_host_parse_genome_file(const char* path) {

@@ -208,7 +208,8 @@ static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<G
   NameTables nt(genomes, sc.g0, sc.g1);
   std::string err;
   // --truth reads the columns: the run takes the column route (the same bytes, include/simmr_hip.h)
-  bool use_device_text = !args.host_fastq && args.truth.empty();
+  // (--stats likewise)
+  bool use_device_text = !args.host_fastq && args.truth.empty() && args.stats.empty();
   uint64_t text_bytes = 0, n_ranges = 0;
   TextDrain drain;
   if (use_device_text && !drain.open(args.output, &err)) return die(err);
@@ -245,6 +246,8 @@ static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<G
       DeviceOut d;
       if (!d.init(pi.n_reads, pi.total_bases, pi.slot_bytes)) return die("device allocation failed");
       if (sc.emit(eng, sc.id_base, &d.o) != SIMMR_OK) return die(simmr_last_error(eng));
+      // every range adds to the run's tables (enqueued behind the emit; the copies below wait for the device)
+      if (!args.stats.empty() && simmr_stats_add(eng, &d.o, pi.n_reads, sc.paired ? 2u : 1u) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
       HostTruth truth;
       if (!args.truth.empty() && !device_truth(eng, &d.o, pi.n_reads, &truth, &err)) return die("--truth: " + err);
       HostReads h;
@@ -438,6 +441,7 @@ static int run_main(int argc, char** argv) {
   if (help) { fputs(usage().c_str(), stdout); return 0; }
 
   if (!args.truth.empty() && !args.devices.empty()) return die("--truth does not combine with --devices: use --device");
+  if (!args.stats.empty() && !args.devices.empty()) return die("--stats does not combine with --devices: use --device");
   std::unique_ptr<ErrorProfile> eprofile = determine_error_profile(args, &err);  // main.rs:27
   if (!eprofile) return die(err);
   // main.rs:30-33
@@ -567,6 +571,11 @@ static int run_main(int argc, char** argv) {
     if (!write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, args.truth, true, &err)) return die("--truth: " + err);
   }
 
+  if (!args.stats.empty()) {
+    if (is_regular_file(args.stats)) remove(args.stats.c_str());
+    if (simmr_stats_reset(eng) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
+  }
+
   simmr_error_profile pod = eprofile->pod();
   if (args.rng_philox) {  // (extension) the counter mode, for the profiles that draw per base from a parametric law
     // (a custom model draws base by base only in the k-mer splice of its long-read path: include/simmr_hip.h)
@@ -652,6 +661,11 @@ static int run_main(int argc, char** argv) {
     if (int rc = run(sc, chunk_units)) return rc;
   }
   info(("Writing simulated reads to " + args.output).c_str());
+  if (!args.stats.empty()) {
+    auto st = std::make_unique<simmr_run_stats>();
+    if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
+    if (!write_stats_tsv(*st, args.stats, &err)) return die("--stats: " + err);
+  }
 
   // main.rs:213-258
   std::vector<MetadataRow> rows;

@@ -107,6 +107,14 @@ struct HostTruth {
 bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads, const HostTruth& truth, uint32_t qual_offset,
                      const std::string& output, bool with_header, std::string* err);
 
+// ---------------------------------------------------------------- run statistics (no reference counterpart)
+// `simmr-hip --stats FILE`: the tables of a simmr_run_stats (include/simmr_hip.h) in long form, tab-separated:
+//   table  set  i  j  count
+// one line per NON-ZERO entry, tables and entries in the struct's order; `set`, `i`, `j` are `-` where a table has no such
+// index (reads, bases, cycle_n, cycle_qsum, cycle_mismatch: set and i; cycle_base: set, i = offset, j = class; pair: i =
+// expected class, j = written class; the histograms and quality tables: i).  Replaces `output`.
+bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::string* err);
+
 // ------------------------------------------------------- error_profiles/*.rs
 class ErrorProfile {  // error_profiles/base.rs:6-32 (the per-read methods run on the device)
  public:
@@ -211,6 +219,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   bool host_normalize = false;  // --host-normalize: normalise FASTA on the host instead of the device
   bool host_fastq = false;  // --host-fastq: frame the FASTQ on the host instead of the device
   std::string truth;  // --truth FILE: per-read mismatch counts and edit lists (simmr_truth_plan / simmr_truth_emit) as a TSV
+  std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   uint64_t device_chunk_reads = 0;  // --device-chunk-reads: reads generated per device pass (0: what fits the free device memory)
   std::optional<std::pair<float, float>> gamma;  // --gamma mean,std
   bool uniform_start = false;                    // --uniform-start (SIMMR_START_UNIFORM)
