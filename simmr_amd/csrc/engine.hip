@@ -64,6 +64,22 @@ constexpr size_t BACK_PAD_WORDS = 24;  // the custom-long splice reads 17 words 
 
 enum PlanKind { PLAN_NONE = 0, PLAN_PE = 1, PLAN_LONG = 2 };
 
+// The plan in force.  A plan call starts with PlanState{} (no plan) and commits a fully built value in plan_finish, so a
+// field that call did not set is the default below, never what the plan before it left.
+struct PlanState {
+  int kind = PLAN_NONE;
+  ProfileDev prof{};
+  uint32_t genome = 0;
+  uint64_t first = 0, units = 0, total_bases = 0;
+  uint32_t slot = 0;      // the layout of this plan (simmr_engine::read_slots: of the plans to come)
+  bool short_ok = false;  // a paired plan without a read longer than LONGREAD_MAXL (text_lines.hip takes it)
+  bool coarse = false;    // pairs for the counter-mode kernel: u_off64 (first byte of every 64th pair) instead of u_off
+  bool paired = false;
+  bool multi = false;     // paired-end plan over several genomes (u_genome per pair)
+  bool any_exc = false;   // some genome of a paired plan has an exception plane
+  bool sorted = false;    // u_order holds a processing order (sort_by_length)
+};
+
 }  // namespace
 
 // which form simmr_emit_fastq runs when SIMMR_TEXT_FORM does not say: the one that measures faster (LAB.md, round 5)
@@ -87,24 +103,13 @@ struct simmr_engine {
   uint64_t n_emits = 0;
   float last_emit_ms = 0.f, last_plan_ms = 0.f, last_fastq_plan_ms = 0.f;
 
-  // current plan
-  int plan_kind = PLAN_NONE;
-  ProfileDev prof{};
-  uint32_t plan_genome = 0;
-  uint64_t plan_first = 0, plan_units = 0, plan_total_bases = 0;
+  PlanState plan;           // current plan
   uint32_t read_slots = 0;  // simmr_engine_set_read_slots: the layout of the plans to come (0 compact, 16 SIMMR_SLOT16)
-  uint32_t plan_slot = 0;   // ... and of the plan in force
-  bool plan_short_ok = false;  // the current paired plan has no read longer than LONGREAD_MAXL (text_lines.hip takes it)
-  bool plan_coarse = false; // pairs for the counter-mode kernel: u_off64 (first byte of every 64th pair) instead of u_off
   DevBuf w_bytes, u_off64, fq_off64;
   bool fq_coarse = false;  // the direct FASTQ plan in force has fq_off64 (first byte of every 64th record) instead of fq_off
-  bool plan_paired = false;
-  bool plan_multi = false;    // paired-end plan over several genomes (u_genome per pair)
-  bool plan_any_exc = false;  // some genome of the plan has an exception plane
   DevBuf m_genomes, m_contig, m_seed;
   DevBuf u_contig, u_genome, u_seed, u_len, u_a, u_b, u_qs2, u_ms2, u_flags, u_off;
   DevBuf scan_tmp, u_order, len_hist;
-  bool plan_sorted = false;
   // simmr_engine_set_plan_overlap: the plan calls run on a stream of their own and write a SECOND set of the buffers an
   // emit reads (plan columns, offsets, order, error word, counter-mode tables), so that the plan of the next shard runs
   // while the emit of this one is still on the device — one is bound by latency, the other by VALU issue.  plan_sets_swap
@@ -717,8 +722,8 @@ int run_outer(simmr_engine* e, uint64_t seed, uint64_t range, uint64_t start_slo
 }
 
 // processing order by unit length (granularity 2^shift), so the lanes of a wave finish together
-int sort_by_length(simmr_engine* e, uint64_t count, uint32_t shift) {
-  e->plan_sorted = false;
+int sort_by_length(simmr_engine* e, uint64_t count, uint32_t shift, bool* sorted) {
+  *sorted = false;
   if (count == 0) return SIMMR_OK;
   if (count > 0xffffffffULL) return e->fail(SIMMR_ERANGE, "more than 2^32 units in one shard");
   if (!e->u_order.ensure(count * 4) || !e->len_hist.ensure(LBINS * 4))
@@ -731,7 +736,7 @@ int sort_by_length(simmr_engine* e, uint64_t count, uint32_t shift) {
   const uint32_t g2 = (uint32_t)std::min<uint64_t>(grid_for(count, 4096), (uint64_t)e->n_cu * 8);
   hipLaunchKernelGGL(k_len_scatter, dim3(g2), dim3(256), 0, e->stream, e->u_len.as<uint32_t>(), count, shift,
                      e->len_hist.as<uint32_t>(), e->u_order.as<uint32_t>());
-  e->plan_sorted = true;
+  *sorted = true;
   return SIMMR_OK;
 }
 
@@ -880,9 +885,9 @@ int check_out(simmr_engine* e, const simmr_reads_out* out, uint64_t n_reads, uin
     return e->fail(SIMMR_ERANGE, "reads_capacity %llu < %llu reads planned",
                    (unsigned long long)out->reads_capacity, (unsigned long long)n_reads);
   if (out->qual_offset > 255u) return e->fail(SIMMR_EINVAL, "qual_offset too large");
-  if ((out->slot_bytes <= 1u ? 0u : out->slot_bytes) != e->plan_slot)
+  if ((out->slot_bytes <= 1u ? 0u : out->slot_bytes) != e->plan.slot)
     return e->fail(SIMMR_EINVAL, "out->slot_bytes = %u, but the plan was made for %s (simmr_engine_set_read_slots, simmr_plan_info.slot_bytes)",
-                   out->slot_bytes, e->plan_slot ? "16-byte read slots" : "the compact layout");
+                   out->slot_bytes, e->plan.slot ? "16-byte read slots" : "the compact layout");
   return SIMMR_OK;
 }
 
@@ -918,18 +923,18 @@ struct ItemLaunch {
 static ItemLaunch item_launch(const simmr_engine* e) {
   ItemLaunch t;
   t.exc = false;
-  if (e->plan_paired) t.exc = e->plan_any_exc;
+  if (e->plan.paired) t.exc = e->plan.any_exc;
   else for (const auto& g : e->genomes) t.exc = t.exc || (g.staged && g.has_exc);
-  t.cached = e->plan_paired && !e->plan_multi && e->plan_genome < e->genomes.size() &&
-             e->genomes[e->plan_genome].contigs.size() <= PHILOX_CBASE;
-  const uint64_t n_units = e->plan_units;
+  t.cached = e->plan.paired && !e->plan.multi && e->plan.genome < e->genomes.size() &&
+             e->genomes[e->plan.genome].contigs.size() <= PHILOX_CBASE;
+  const uint64_t n_units = e->plan.units;
   const uint64_t blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;
   t.grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);
   return t;
 }
 // an escaped base is noticed through its quality byte when no real one has bit 7 set (kernels.hip: esc_q); `offset` is
 // the quality offset of the launch
-static bool philox_escq(const simmr_engine* e, uint32_t offset) { return offset + e->prof.philox_qmax1 <= 127u; }
+static bool philox_escq(const simmr_engine* e, uint32_t offset) { return offset + e->plan.prof.philox_qmax1 <= 127u; }
 
 // the instantiation of the counter-mode item kernel for (exception plane, contig bases in LDS, escapes noticed through
 // the quality byte, 16-byte read slots, block offsets from the coarse scan)
@@ -972,9 +977,9 @@ struct PhiloxForm {
   const uint64_t* off64 = nullptr;  // coarse plans and the text: first byte of every 64th pair / record
 };
 static void launch_philox(simmr_engine* e, PhiloxKernel kern, uint32_t grid, uint32_t lds, const PlanArrays& pl, const PhiloxForm& f) {
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, e->stream, e->prof, e->plan_paired ? 1u : 0u, e->d_genomes.as<GenomeDev>(),
-                     e->plan_genome, e->plan_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), f.u_genome,
-                     e->u_seed.as<uint64_t>(), f.seq, f.qual, f.qual_offset, e->plan_first, f.read_id_base, f.cols,
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, e->stream, e->plan.prof, e->plan.paired ? 1u : 0u, e->d_genomes.as<GenomeDev>(),
+                     e->plan.genome, e->plan.units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), f.u_genome,
+                     e->u_seed.as<uint64_t>(), f.seq, f.qual, f.qual_offset, e->plan.first, f.read_id_base, f.cols,
                      e->d_counters.as<unsigned long long>(), f.hlen, f.fq_tp, f.fq_tb, f.fq_lit_bytes, f.fq_hpitch, f.fq_wshift, f.off64);
 }
 
@@ -1471,52 +1476,44 @@ int simmr_pe_plan_at(simmr_engine* e, uint32_t genome_idx, const simmr_error_pro
   return pe_plan_impl(e, genome_idx, profile, genome_reads, 1, seed, shard, start_slot, start_unit, info);
 }
 
-static int pe_plan_impl(simmr_engine* e, uint32_t genome_idx, const simmr_error_profile* profile, uint64_t genome_reads,
-                        int has_seed, uint64_t seed, simmr_range shard, uint64_t start_slot, uint64_t start_unit,
-                        simmr_plan_info* info) {
-  if (!e) return SIMMR_EINVAL;
-  e->plan_kind = PLAN_NONE;
+// ---- what the plan calls share ----
+// A plan call opens with plan_reset, makes its PlanScope (which must live to the end of the CALL, so the call owns it),
+// and asks plan_begin for the device form of the profile and the layout.
+static int plan_reset(simmr_engine* e) {
+  e->plan = PlanState{};
   e->fq_direct = false;  // (a direct FASTQ plan belongs to the plan it was made for)
   HIP_TRY(e, hipSetDevice(e->device));
-  PlanScope plan_scope(e);  // (simmr_engine_set_plan_overlap: the other buffer set, the plan stream)
-  int rc = check_genome(e, genome_idx);
-  if (rc) return rc;
-  ProfileDev prof;
-  if ((rc = make_profile(e, profile, false, &prof))) return rc;
-  uint32_t slot_round = 0;
-  if ((rc = plan_slot_round(e, prof, &slot_round))) return rc;
-  GenomeHost& g = e->genomes[genome_idx];
-  // simulate.rs:220-225: a sequence not larger than minimum_genome_size() is an
-  // Err that the caller unwrap()s (simulate.rs:186) — any such sequence can be drawn.
+  return SIMMR_OK;
+}
+static int plan_begin(simmr_engine* e, const simmr_error_profile* profile, bool want_long, PlanState* p, uint32_t* slot_round) {
+  int rc;
+  if ((rc = make_profile(e, profile, want_long, &p->prof))) return rc;
+  if ((rc = plan_slot_round(e, p->prof, slot_round))) return rc;
+  p->slot = *slot_round ? SIMMR_SLOT16 : 0u;
+  return SIMMR_OK;
+}
+
+// simulate.rs:220-225: a sequence not larger than minimum_genome_size() is an
+// Err that the caller unwrap()s (simulate.rs:186) — any such sequence can be drawn.
+static int check_contig_sizes(simmr_engine* e, const GenomeHost& g, uint32_t required) {
   for (size_t c = 0; c < g.contigs.size(); c++)
-    if (g.contigs[c].size <= prof.required)
+    if (g.contigs[c].size <= required)
       return e->fail(SIMMR_EGENOME, "Genome size (%llunt) is smaller than the required length (%u)",
-                     (unsigned long long)g.contigs[c].size, prof.required);
-  const uint64_t n_pairs = genome_reads / 2;  // simulate.rs:179
-  uint64_t first = std::min(shard.first, n_pairs);
-  uint64_t count = std::min(shard.count, n_pairs - first);
-  if (start_unit > first)
-    return e->fail(SIMMR_EINVAL, "start_unit %llu is past the first pair of the shard (%llu)", (unsigned long long)start_unit,
-                   (unsigned long long)first);
-  if (!has_seed) seed = os_entropy_u64();  // simulate.rs:174 from_entropy()
-  const bool seeds2 = prof.kind != SIMMR_K_PERFECT_SHORT;
-  if ((rc = ensure_plan_arrays(e, count, seeds2, false))) return rc;
-  HIP_TRY(e, hipEventRecord(e->ev_a, e->stream));
-  HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
-  uint64_t end_slot = 0, total = 0;
+                     (unsigned long long)g.contigs[c].size, required);
+  return SIMMR_OK;
+}
+
+// The two paired-end plans from the plan kernel to the offset scan: p->units pairs whose outer draws are in u_contig /
+// u_seed (or are made by the plan kernel: `oc`).  Sets p->coarse, p->sorted and p->total_bases.
+static int plan_pe_pairs(simmr_engine* e, PlanState* p, uint32_t slot_round, uint32_t genome, const uint32_t* u_genome,
+                         const OuterCtrArgs& oc) {
+  const ProfileDev& prof = p->prof;
+  const uint64_t count = p->units;
+  int rc;
   bool presummed = false;
-  const bool coarse = plan_is_coarse(e, prof);
+  const bool coarse = p->coarse = plan_is_coarse(e, prof);
   if (count > 0) {
-    // the stream is entered at pair start_unit (slot start_slot): units are counted from there
-    if (prof.rng_mode == SIMMR_RNG_PHILOX_FULL) {
-      // one Philox block per pair, made by the plan kernel: nothing to walk, nothing to seek in (start_slot / start_unit have no meaning)
-      rc = SIMMR_OK;
-    } else {
-      rc = run_outer(e, seed, g.contigs.size(), start_slot, first - start_unit + count, first - start_unit, count,
-                     e->u_contig.as<uint32_t>(), e->u_seed.as<uint64_t>(), &end_slot);
-    }
-    if (rc) return rc;
-    PlanArrays pw = plan_arrays(e, seeds2);
+    PlanArrays pw = plan_arrays(e, prof.kind != SIMMR_K_PERFECT_SHORT);
     // the mutation seed of mate 2 is only read by the kernels that walk the reference's mutation stream
     if (prof.kind == SIMMR_K_CUSTOM || prof.rng_mode != SIMMR_RNG_REFERENCE) pw.ms2 = nullptr;
     // the plan kernel adds each pair's bytes to its tile of the offset scan (sort_by_length uses the same scratch first)
@@ -1525,53 +1522,94 @@ static int pe_plan_impl(simmr_engine* e, uint32_t genome_idx, const simmr_error_
     unsigned long long* tiles = presummed ? tile_sums_begin(e, count) : nullptr;
     if (presummed && !tiles) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
     if (coarse && !e->w_bytes.ensure(((count + 63) / 64) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
-    const OuterCtrArgs oc{nullptr, 0u, (uint32_t)g.contigs.size(), seed, first, nullptr, e->u_contig.as<uint32_t>(), e->u_seed.as<uint64_t>()};
-    if ((rc = launch_plan_pe(e, prof, genome_idx, count, (const uint32_t*)nullptr, pw, tiles, slot_round,
+    if ((rc = launch_plan_pe(e, prof, genome, count, u_genome, pw, tiles, slot_round,
                              coarse ? e->w_bytes.as<unsigned long long>() : (unsigned long long*)nullptr, oc)))
       return rc;
   }
-  e->plan_sorted = false;
   if (prof.kind == SIMMR_K_MINIMAL_SHORT && prof.rng_mode == SIMMR_RNG_REFERENCE &&
-      (rc = sort_by_length(e, count, 0)))
+      (rc = sort_by_length(e, count, 0, &p->sorted)))
     return rc;
   if (prof.kind == SIMMR_K_PERFECT_SHORT && count > 0) {
-    total = count * 2ull * prof.read_length;  // constant lengths (perfect_short.rs:22-40): read r starts at r * L
+    p->total_bases = count * 2ull * prof.read_length;  // constant lengths (perfect_short.rs:22-40): read r starts at r * L
   } else if (coarse) {  // the first output byte of every 64th pair is all the counter-mode emit kernel asks for
-    if ((rc = scan_u64(e, e->w_bytes, (count + 63) / 64, e->u_off64, &total))) return rc;
-  } else if ((rc = presummed ? scan_presummed<uint32_t>(e, e->u_len, count, 2u, e->u_off, &total, slot_round) : scan_offsets(e, count, 2u, &total, slot_round))) {
+    if ((rc = scan_u64(e, e->w_bytes, (count + 63) / 64, e->u_off64, &p->total_bases))) return rc;
+  } else if ((rc = presummed ? scan_presummed<uint32_t>(e, e->u_len, count, 2u, e->u_off, &p->total_bases, slot_round)
+                             : scan_offsets(e, count, 2u, &p->total_bases, slot_round))) {
     return rc;
   }
+  return SIMMR_OK;
+}
+
+// The end of a plan call: closes the timed span, turns the kernels' error word into the call's answer, and on success
+// makes `p` the plan in force and fills *info.  genome_msg: what SIMMR_ERRBIT_GENOME means to this plan.
+static int plan_finish(simmr_engine* e, PlanState p, const char* genome_msg, uint64_t seed, uint64_t end_slot,
+                       uint32_t const_read_length, simmr_plan_info* info) {
   HIP_TRY(e, hipEventRecord(e->ev_b, e->stream));
   uint32_t errw = 0;
+  int rc;
   if ((rc = read_err_word(e, &errw))) return rc;
-  if (errw & SIMMR_ERRBIT_GENOME) return e->fail(SIMMR_EGENOME, "a sequence is smaller than the required length");
+  if (errw & SIMMR_ERRBIT_GENOME) return e->fail(SIMMR_EGENOME, "%s", genome_msg);
   if (errw & SIMMR_ERRBIT_SLICE)
     return e->fail(SIMMR_ERANGE, "a read would extend past its sequence (the reference panics on this slice)");
   if (errw & SIMMR_ERRBIT_PDF)
     return e->fail(SIMMR_ERANGE, "a custom PDF selected a density without a bin range (the reference panics: index out of bounds)");
   (void)hipEventElapsedTime(&e->last_plan_ms, e->ev_a, e->ev_b);
-  e->plan_kind = PLAN_PE;
-  e->prof = prof;
-  e->plan_genome = genome_idx;
-  e->plan_slot = slot_round ? SIMMR_SLOT16 : 0u;
-  e->plan_coarse = coarse;
-  e->plan_short_ok = !(errw & SIMMR_NOTEBIT_LONGREAD);
-  e->plan_first = first;
-  e->plan_units = count;
-  e->plan_total_bases = total;
-  e->plan_paired = true;
-  e->plan_multi = false;
-  e->plan_any_exc = g.has_exc;
+  p.short_ok = p.paired && !(errw & SIMMR_NOTEBIT_LONGREAD);
+  e->plan = p;
   if (info) {
     memset(info, 0, sizeof *info);
-    info->n_units = count;
-    info->n_reads = 2 * count;
-    info->total_bases = total;
+    info->n_units = p.units;
+    info->n_reads = p.paired ? 2 * p.units : p.units;
+    info->total_bases = p.total_bases;
     info->seed_used = seed;
     info->outer_slots = end_slot;
-    info->slot_bytes = e->plan_slot;
+    info->const_read_length = const_read_length;
+    info->slot_bytes = p.slot;
   }
   return SIMMR_OK;
+}
+
+static int pe_plan_impl(simmr_engine* e, uint32_t genome_idx, const simmr_error_profile* profile, uint64_t genome_reads,
+                        int has_seed, uint64_t seed, simmr_range shard, uint64_t start_slot, uint64_t start_unit,
+                        simmr_plan_info* info) {
+  if (!e) return SIMMR_EINVAL;
+  int rc = plan_reset(e);
+  if (rc) return rc;
+  PlanScope plan_scope(e);  // (simmr_engine_set_plan_overlap: the other buffer set, the plan stream)
+  if ((rc = check_genome(e, genome_idx))) return rc;
+  PlanState p;
+  p.kind = PLAN_PE;
+  p.paired = true;
+  uint32_t slot_round = 0;
+  if ((rc = plan_begin(e, profile, false, &p, &slot_round))) return rc;
+  const ProfileDev& prof = p.prof;
+  GenomeHost& g = e->genomes[genome_idx];
+  if ((rc = check_contig_sizes(e, g, prof.required))) return rc;
+  const uint64_t n_pairs = genome_reads / 2;  // simulate.rs:179
+  uint64_t first = std::min(shard.first, n_pairs);
+  uint64_t count = std::min(shard.count, n_pairs - first);
+  if (start_unit > first)
+    return e->fail(SIMMR_EINVAL, "start_unit %llu is past the first pair of the shard (%llu)", (unsigned long long)start_unit,
+                   (unsigned long long)first);
+  if (!has_seed) seed = os_entropy_u64();  // simulate.rs:174 from_entropy()
+  if ((rc = ensure_plan_arrays(e, count, prof.kind != SIMMR_K_PERFECT_SHORT, false))) return rc;
+  HIP_TRY(e, hipEventRecord(e->ev_a, e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
+  uint64_t end_slot = 0;
+  // the stream is entered at pair start_unit (slot start_slot): units are counted from there.  (SIMMR_RNG_PHILOX_FULL:
+  // one Philox block per pair, made by the plan kernel: nothing to walk, nothing to seek in, start_slot / start_unit
+  // have no meaning)
+  if (count > 0 && prof.rng_mode != SIMMR_RNG_PHILOX_FULL &&
+      (rc = run_outer(e, seed, g.contigs.size(), start_slot, first - start_unit + count, first - start_unit, count,
+                      e->u_contig.as<uint32_t>(), e->u_seed.as<uint64_t>(), &end_slot)))
+    return rc;
+  p.genome = genome_idx;
+  p.first = first;
+  p.units = count;
+  p.any_exc = g.has_exc;
+  const OuterCtrArgs oc{nullptr, 0u, (uint32_t)g.contigs.size(), seed, first, nullptr, e->u_contig.as<uint32_t>(), e->u_seed.as<uint64_t>()};
+  if ((rc = plan_pe_pairs(e, &p, slot_round, genome_idx, (const uint32_t*)nullptr, oc))) return rc;
+  return plan_finish(e, p, "a sequence is smaller than the required length", seed, end_slot, 0u, info);
 }
 
 // simulate_pe_reads (simulate.rs:110-150) for several genomes in one plan: the shard is a range of the
@@ -1580,16 +1618,16 @@ int simmr_pe_plan_multi(simmr_engine* e, uint32_t n_genomes, const uint32_t* gen
                         const simmr_error_profile* profile, int has_seed, uint64_t seed, simmr_range shard,
                         simmr_plan_info* info) {
   if (!e) return SIMMR_EINVAL;
-  e->plan_kind = PLAN_NONE;
-  e->fq_direct = false;  // (a direct FASTQ plan belongs to the plan it was made for)
-  if (n_genomes == 0 || !genome_idx || !genome_reads) return e->fail(SIMMR_EINVAL, "simmr_pe_plan_multi: no genomes");
-  HIP_TRY(e, hipSetDevice(e->device));
+  int rc = plan_reset(e);
+  if (rc) return rc;
   PlanScope plan_scope(e);  // (simmr_engine_set_plan_overlap: the other buffer set, the plan stream)
-  int rc;
-  ProfileDev prof;
-  if ((rc = make_profile(e, profile, false, &prof))) return rc;
+  if (n_genomes == 0 || !genome_idx || !genome_reads) return e->fail(SIMMR_EINVAL, "simmr_pe_plan_multi: no genomes");
+  PlanState p;
+  p.kind = PLAN_PE;
+  p.paired = p.multi = true;
   uint32_t slot_round = 0;
-  if ((rc = plan_slot_round(e, prof, &slot_round))) return rc;
+  if ((rc = plan_begin(e, profile, false, &p, &slot_round))) return rc;
+  const ProfileDev& prof = p.prof;
   if (prof.kind == SIMMR_K_CUSTOM)
     return e->fail(SIMMR_ENOTSUP, "a custom profile is planned one genome at a time (simmr_pe_plan)");
   // global pair ranges of the genomes (simulate.rs:179: num_reads / 2 pairs each)
@@ -1606,18 +1644,13 @@ int simmr_pe_plan_multi(simmr_engine* e, uint32_t n_genomes, const uint32_t* gen
   struct Cls { uint64_t range, need, off; };
   std::vector<Cls> classes;
   std::vector<MultiGenome> mg(n_genomes);
-  bool any_exc = false;
   for (uint32_t g = 0; g < n_genomes; g++) {
     const GenomeHost& G = e->genomes[genome_idx[g]];
     mg[g] = MultiGenome{base[g], 0, genome_idx[g], 0};
     const uint64_t lo = std::max(first, base[g]), hi = std::min(first + count, base[g + 1]);
     if (hi <= lo) continue;
-    // simulate.rs:220-225: any sequence not larger than minimum_genome_size() can be drawn and is an error
-    for (size_t c = 0; c < G.contigs.size(); c++)
-      if (G.contigs[c].size <= prof.required)
-        return e->fail(SIMMR_EGENOME, "Genome size (%llunt) is smaller than the required length (%u)",
-                       (unsigned long long)G.contigs[c].size, prof.required);
-    any_exc = any_exc || G.has_exc;
+    if ((rc = check_contig_sizes(e, G, prof.required))) return rc;
+    p.any_exc = p.any_exc || G.has_exc;
     const uint64_t range = G.contigs.size(), need = hi - base[g];  // local pairs [0, need)
     size_t ci = 0;
     while (ci < classes.size() && classes[ci].range != range) ci++;
@@ -1628,16 +1661,13 @@ int simmr_pe_plan_multi(simmr_engine* e, uint32_t n_genomes, const uint32_t* gen
   uint64_t list_total = 0;
   for (Cls& c : classes) { c.off = list_total; list_total += c.need; }
   for (uint32_t g = 0; g < n_genomes; g++) mg[g].cls_off = classes.empty() ? 0 : classes[mg[g].pad].off;
-  const bool seeds2 = prof.kind != SIMMR_K_PERFECT_SHORT;
-  if ((rc = ensure_plan_arrays(e, count, seeds2, true))) return rc;
+  if ((rc = ensure_plan_arrays(e, count, prof.kind != SIMMR_K_PERFECT_SHORT, true))) return rc;
   if (!e->m_contig.ensure(std::max<uint64_t>(list_total, 1) * 4) || !e->m_seed.ensure(std::max<uint64_t>(list_total, 1) * 8))
     return e->fail(SIMMR_ENOMEM, "outer list allocation failed");
   if ((rc = upload_vec(e, e->m_genomes, mg))) return rc;
   HIP_TRY(e, hipEventRecord(e->ev_a, e->stream));
   HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
-  uint64_t end_slot = 0, total = 0;
-  bool presummed = false;
-  const bool coarse = plan_is_coarse(e, prof);
+  uint64_t end_slot = 0;
   const bool full = prof.rng_mode == SIMMR_RNG_PHILOX_FULL;
   for (const Cls& c : classes) {  // run_outer synchronises, so `mg` has been uploaded when it returns
     if (full) break;  // (no outer lists: every pair's block is made where the pair is planned)
@@ -1645,153 +1675,109 @@ int simmr_pe_plan_multi(simmr_engine* e, uint32_t n_genomes, const uint32_t* gen
                         e->m_seed.as<uint64_t>() + c.off, &end_slot)))
       return rc;
   }
-  if (count > 0) {
-    if (!full)  // (the full counter mode: the plan kernel finds each pair's genome and makes its outer draws)
+  if (count > 0 && !full)  // (the full counter mode: the plan kernel finds each pair's genome and makes its outer draws)
     hipLaunchKernelGGL(k_multi_units, dim3(grid_for(count, 256)), dim3(256), 0, e->stream, e->m_genomes.as<MultiGenome>(),
                        n_genomes, first, count, e->m_contig.as<uint32_t>(), e->m_seed.as<uint64_t>(),
                        e->u_genome.as<uint32_t>(), e->u_contig.as<uint32_t>(), e->u_seed.as<uint64_t>());
-    PlanArrays pw = plan_arrays(e, seeds2);
-    if (prof.kind == SIMMR_K_CUSTOM || prof.rng_mode != SIMMR_RNG_REFERENCE) pw.ms2 = nullptr;
-    presummed = prof.kind != SIMMR_K_PERFECT_SHORT && !coarse && !(prof.kind == SIMMR_K_MINIMAL_SHORT && prof.rng_mode == SIMMR_RNG_REFERENCE);
-    unsigned long long* tiles = presummed ? tile_sums_begin(e, count) : nullptr;
-    if (presummed && !tiles) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
-    if (coarse && !e->w_bytes.ensure(((count + 63) / 64) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
-    const OuterCtrArgs oc{e->m_genomes.as<MultiGenome>(), n_genomes, 0u, seed, first, e->u_genome.as<uint32_t>(),
-                          e->u_contig.as<uint32_t>(), e->u_seed.as<uint64_t>()};
-    if ((rc = launch_plan_pe(e, prof, 0u, count, (const uint32_t*)e->u_genome.as<uint32_t>(), pw, tiles, slot_round,
-                             coarse ? e->w_bytes.as<unsigned long long>() : (unsigned long long*)nullptr, oc)))
-      return rc;
-  }
-  e->plan_sorted = false;
-  if (prof.kind == SIMMR_K_MINIMAL_SHORT && prof.rng_mode == SIMMR_RNG_REFERENCE && (rc = sort_by_length(e, count, 0)))
-    return rc;
-  if (prof.kind == SIMMR_K_PERFECT_SHORT && count > 0) {
-    total = count * 2ull * prof.read_length;
-  } else if (coarse) {
-    if ((rc = scan_u64(e, e->w_bytes, (count + 63) / 64, e->u_off64, &total))) return rc;
-  } else if ((rc = presummed ? scan_presummed<uint32_t>(e, e->u_len, count, 2u, e->u_off, &total, slot_round) : scan_offsets(e, count, 2u, &total, slot_round))) {
-    return rc;
-  }
-  HIP_TRY(e, hipEventRecord(e->ev_b, e->stream));
-  uint32_t errw = 0;
-  if ((rc = read_err_word(e, &errw))) return rc;  // also: the host vector `mg` may go out of scope now
-  if (errw & SIMMR_ERRBIT_GENOME) return e->fail(SIMMR_EGENOME, "a sequence is smaller than the required length");
-  if (errw & SIMMR_ERRBIT_SLICE)
-    return e->fail(SIMMR_ERANGE, "a read would extend past its sequence (the reference panics on this slice)");
-  (void)hipEventElapsedTime(&e->last_plan_ms, e->ev_a, e->ev_b);
-  e->plan_kind = PLAN_PE;
-  e->prof = prof;
-  e->plan_genome = genome_idx[0];
-  e->plan_slot = slot_round ? SIMMR_SLOT16 : 0u;
-  e->plan_coarse = coarse;
-  e->plan_short_ok = !(errw & SIMMR_NOTEBIT_LONGREAD);
-  e->plan_first = first;
-  e->plan_units = count;
-  e->plan_total_bases = total;
-  e->plan_paired = true;
-  e->plan_multi = true;
-  e->plan_any_exc = any_exc;
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->n_units = count;
-    info->n_reads = 2 * count;
-    info->total_bases = total;
-    info->seed_used = seed;
-    info->outer_slots = end_slot;
-    info->slot_bytes = e->plan_slot;
-  }
-  return SIMMR_OK;
+  p.genome = genome_idx[0];
+  p.first = first;
+  p.units = count;
+  const OuterCtrArgs oc{e->m_genomes.as<MultiGenome>(), n_genomes, 0u, seed, first, e->u_genome.as<uint32_t>(),
+                        e->u_contig.as<uint32_t>(), e->u_seed.as<uint64_t>()};
+  if ((rc = plan_pe_pairs(e, &p, slot_round, 0u, (const uint32_t*)e->u_genome.as<uint32_t>(), oc))) return rc;
+  // (plan_finish reads the error word back: after it the host vector `mg` may go out of scope)
+  return plan_finish(e, p, "a sequence is smaller than the required length", seed, end_slot, 0u, info);
 }
 
 static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads_out* out) {
-  const uint64_t n_units = e->plan_units;
-  const bool paired = e->plan_paired;
+  const uint64_t n_units = e->plan.units;
+  const bool paired = e->plan.paired;
   const uint64_t n_reads = paired ? 2 * n_units : n_units;
-  int rc = check_out(e, out, n_reads, e->plan_total_bases);
+  int rc = check_out(e, out, n_reads, e->plan.total_bases);
   if (rc) return rc;
-  const bool seeds2 = paired && e->prof.kind != SIMMR_K_PERFECT_SHORT;
+  const bool seeds2 = paired && e->plan.prof.kind != SIMMR_K_PERFECT_SHORT;
   PlanArrays pl = plan_arrays(e, seeds2);
-  const uint32_t* u_genome = (paired && !e->plan_multi) ? nullptr : e->u_genome.as<uint32_t>();
+  const uint32_t* u_genome = (paired && !e->plan.multi) ? nullptr : e->u_genome.as<uint32_t>();
   // the Philox and perfect-short emit kernels write the metadata columns and the plan counters themselves
-  const bool fused = n_units > 0 && (e->prof.kind == SIMMR_K_PERFECT_SHORT ||
-                                     (e->prof.kind != SIMMR_K_CUSTOM && e->prof.rng_mode != SIMMR_RNG_REFERENCE));
+  const bool fused = n_units > 0 && (e->plan.prof.kind == SIMMR_K_PERFECT_SHORT ||
+                                     (e->plan.prof.kind != SIMMR_K_CUSTOM && e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE));
   if (!fused)
     hipLaunchKernelGGL(k_write_meta, dim3(grid_for(n_units + 1, 256)), dim3(256), 0, e->stream,
-                       paired ? 1u : 0u, n_units, e->plan_first, read_id_base, e->plan_genome, pl,
+                       paired ? 1u : 0u, n_units, e->plan.first, read_id_base, e->plan.genome, pl,
                        e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), u_genome, out_cols(out));
   unsigned long long* counters = e->d_counters.as<unsigned long long>();
   const ItemLaunch il = item_launch(e);
   HIP_TRY(e, next_emit_events(e));
   HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
   if (n_units > 0) {
-    if (e->prof.kind == SIMMR_K_PERFECT_SHORT) {
+    if (e->plan.prof.kind == SIMMR_K_PERFECT_SHORT) {
       const uint64_t groups = (n_reads + PERFECT_GROUP - 1) / PERFECT_GROUP;
       const uint32_t grid = (uint32_t)std::min<uint64_t>(groups, (uint64_t)e->n_cu * 8 * e->perfect_mult);
-      auto kern = e->plan_multi ? k_emit_perfect_pe<true> : k_emit_perfect_pe<false>;
+      auto kern = e->plan.multi ? k_emit_perfect_pe<true> : k_emit_perfect_pe<false>;
       hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
-                         e->plan_genome, u_genome, e->plan_any_exc ? 1u : 0u, n_units, e->prof.read_length, pl,
+                         e->plan.genome, u_genome, e->plan.any_exc ? 1u : 0u, n_units, e->plan.prof.read_length, pl,
                          e->u_contig.as<uint32_t>(), out->seq,
-                         out->qual, 60u + out->qual_offset, e->plan_first, read_id_base, out_cols(out), counters);
-    } else if (e->prof.rng_mode != SIMMR_RNG_REFERENCE && e->prof.kind != SIMMR_K_CUSTOM) {  // (a custom model's counter mode: below)
+                         out->qual, 60u + out->qual_offset, e->plan.first, read_id_base, out_cols(out), counters);
+    } else if (e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE && e->plan.prof.kind != SIMMR_K_CUSTOM) {  // (a custom model's counter mode: below)
       const bool escq = philox_escq(e, out->qual_offset & 0xffu);
-      const bool coarse = paired && e->plan_coarse;
+      const bool coarse = paired && e->plan.coarse;
       PhiloxForm f{u_genome, out->seq, out->qual, out->qual_offset, read_id_base, out_cols(out)};
       if (coarse) f.off64 = e->u_off64.as<uint64_t>();
-      launch_philox(e, philox_kernel(il.exc, il.cached, escq, e->plan_slot != 0, coarse), il.grid, 0, pl, f);
-    } else if (e->prof.kind == SIMMR_K_CUSTOM && !paired) {
+      launch_philox(e, philox_kernel(il.exc, il.cached, escq, e->plan.slot != 0, coarse), il.grid, 0, pl, f);
+    } else if (e->plan.prof.kind == SIMMR_K_CUSTOM && !paired) {
       {
-        const bool fast0 = e->prof.custom.kmer_stride != 0 && e->splice_variant != 1;
-        if (const char* missing = custom_long_tables_missing(e->prof, fast0, e->prof.rng_mode != SIMMR_RNG_REFERENCE))
+        const bool fast0 = e->plan.prof.custom.kmer_stride != 0 && e->splice_variant != 1;
+        if (const char* missing = custom_long_tables_missing(e->plan.prof, fast0, e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE))
           return e->fail(SIMMR_EINVAL, "custom long-read emit refused: device table `%s` of the model is not set for rng_mode %u "
-                                       "(nothing was launched)", missing, e->prof.rng_mode);
+                                       "(nothing was launched)", missing, e->plan.prof.rng_mode);
       }
       HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
       const bool exc = il.exc;
       const uint64_t blocks = (n_reads + 255) / 256;
       const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
-      const uint32_t* order = e->plan_sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr;
-      hipLaunchKernelGGL(k_custom_long_qual, dim3(grid), dim3(256), 0, e->stream, e->prof, n_units, order, pl,
+      const uint32_t* order = e->plan.sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr;
+      hipLaunchKernelGGL(k_custom_long_qual, dim3(grid), dim3(256), 0, e->stream, e->plan.prof, n_units, order, pl,
                          e->u_off.as<uint64_t>(), e->u_seed.as<uint64_t>(), out->qual, out->qual_offset, counters,
                          e->d_err.as<uint32_t>());
-      bool fast = e->prof.custom.kmer_stride != 0;
+      bool fast = e->plan.prof.custom.kmer_stride != 0;
       if (e->splice_variant == 1) fast = false;  // the two-load kernel (A/B timing)
-      if (e->prof.rng_mode != SIMMR_RNG_REFERENCE) {
+      if (e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE) {
         // the counter mode of the splice (kernels.hip section 9c, CTR): the LDS holds one word per k-mer (4^k words);
         // with k = 7 (64 KB) two workgroups of 768 lanes share a CU — six waves per SIMD, what the kernel's registers allow —
         // with smaller tables 256-lane workgroups do
         auto kern = fast ? (exc ? k_custom_long_splice<true, true, true> : k_custom_long_splice<false, true, true>)
                          : (exc ? k_custom_long_splice<true, false, true> : k_custom_long_splice<false, false, true>);
-        const uint32_t tab = fast ? splice_ctr_lds_bytes(e->prof.custom.kmer_size) : 0u;
+        const uint32_t tab = fast ? splice_ctr_lds_bytes(e->plan.prof.custom.kmer_size) : 0u;
         const uint32_t lanes = tab > 16384u ? SPLICE_CTR_LANES_MAX : 256u;
         const uint32_t lds = fast ? tab + 16u * lanes : 0u;  // the k-mer table + 16 bytes per lane (an even group waiting for its odd neighbour's store)
         if (lds > 32768u) HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (64 KB of table + the kernel's static LDS: over the default limit)
         // (many more workgroups than are resident: reads come longest first, and the tail of the launch is short ones)
         const uint32_t cgrid = (uint32_t)std::min<uint64_t>((n_reads + lanes - 1) / lanes, (uint64_t)e->n_cu * 64 * e->custom_long_mult);
-        hipLaunchKernelGGL(kern, dim3(cgrid), dim3(lanes), lds, e->stream, e->prof, e->d_genomes.as<GenomeDev>(), n_units, order,
+        hipLaunchKernelGGL(kern, dim3(cgrid), dim3(lanes), lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), n_units, order,
                            pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
                            e->u_seed.as<uint64_t>(), out->seq, counters, e->d_err.as<uint32_t>());
       } else if (fast) {
         // one workgroup of 1024 lanes per CU around the LDS count table (kernels.hip section 9c)
         auto kern = exc ? k_custom_long_splice<true, true> : k_custom_long_splice<false, true>;
-        const uint32_t lds = splice_fast_lds_bytes(e->prof.custom.kmer_size);
+        const uint32_t lds = splice_fast_lds_bytes(e->plan.prof.custom.kmer_size);
         HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (grows with the model's k: 132 KB + 4^k)
         const uint32_t fgrid = (uint32_t)std::min<uint64_t>((n_reads + SPLICE_FAST_LANES - 1) / SPLICE_FAST_LANES, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
-        hipLaunchKernelGGL(kern, dim3(fgrid), dim3(SPLICE_FAST_LANES), lds, e->stream, e->prof, e->d_genomes.as<GenomeDev>(),
+        hipLaunchKernelGGL(kern, dim3(fgrid), dim3(SPLICE_FAST_LANES), lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
                            n_units, order, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
                            e->u_seed.as<uint64_t>(), out->seq, counters, e->d_err.as<uint32_t>());
       } else {
         auto kern = exc ? k_custom_long_splice<true, false> : k_custom_long_splice<false, false>;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, e->prof, e->d_genomes.as<GenomeDev>(), n_units, order,
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), n_units, order,
                            pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
                            e->u_seed.as<uint64_t>(), out->seq, counters, e->d_err.as<uint32_t>());
       }
-    } else if (e->prof.kind == SIMMR_K_CUSTOM) {
+    } else if (e->plan.prof.kind == SIMMR_K_CUSTOM) {
       HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
       const uint64_t blocks = (n_units + 255) / 256;  // one lane per pair
       const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * 8 * e->custom_pe_mult);
       // qualities: one lane per pair (k_emit_custom_pe); bases: the item kernel without draws (coalesced stores)
-      hipLaunchKernelGGL(k_emit_custom_pe, dim3(grid), dim3(256), 0, e->stream, e->prof, e->d_genomes.as<GenomeDev>(),
-                         e->plan_genome, n_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(),
+      hipLaunchKernelGGL(k_emit_custom_pe, dim3(grid), dim3(256), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
+                         e->plan.genome, n_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(),
                          e->u_seed.as<uint64_t>(), out->seq, out->qual, out->qual_offset, counters,
                          e->d_err.as<uint32_t>());
       // (its plain form whatever the plan: per-pair offsets, no contig cache, no genome column)
@@ -1800,7 +1786,7 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
     } else {
       // lane-per-read kernel: template on (exception plane present, paired, perfect-long Phred)
       const bool exc = il.exc;
-      const bool pl_kind = e->prof.kind == SIMMR_K_PERFECT_LONG;
+      const bool pl_kind = e->plan.prof.kind == SIMMR_K_PERFECT_LONG;
       using KernT = void (*)(ProfileDev, const GenomeDev*, uint32_t, uint64_t, const uint32_t*, PlanArrays,
                              const uint64_t*, const uint32_t*, const uint32_t*, const uint64_t*, uint8_t*, uint8_t*,
                              uint32_t, const Tables*, unsigned long long*);
@@ -1813,22 +1799,22 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
       const uint64_t n_tasks = paired ? 2 * n_units : n_units;
       const uint64_t wgs = (n_tasks + LANES_WG - 1) / LANES_WG;
       const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)e->n_cu * (uint64_t)per_cu * e->lanes_mult);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(LANES_WG), 0, e->stream, e->prof, e->d_genomes.as<GenomeDev>(),
-                         e->plan_genome, n_units, e->plan_sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr,
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(LANES_WG), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
+                         e->plan.genome, n_units, e->plan.sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr,
                          pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), u_genome, e->u_seed.as<uint64_t>(),
                          out->seq, out->qual, out->qual_offset, e->d_tables.as<Tables>(), counters);
     }
   }
   HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
   if (n_units > 0 && !fused) {
-    const bool perfect = e->prof.kind == SIMMR_K_PERFECT_SHORT;
-    const bool acgt_all = perfect && !e->plan_any_exc;
+    const bool perfect = e->plan.prof.kind == SIMMR_K_PERFECT_SHORT;
+    const bool acgt_all = perfect && !e->plan.any_exc;
     hipLaunchKernelGGL(k_count_plan, dim3(std::min<uint32_t>(grid_for(n_units, 256), (uint32_t)e->n_cu * 4)), dim3(256), 0, e->stream, paired ? 1u : 0u,
                        n_units, pl, perfect ? 60u : 0u, acgt_all ? 1u : 0u, counters);
   }
   hipError_t s = hipGetLastError();
   if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "emit launch failed: %s", hipGetErrorString(s));
-  if (n_units > 0 && e->prof.kind == SIMMR_K_CUSTOM) {
+  if (n_units > 0 && e->plan.prof.kind == SIMMR_K_CUSTOM) {
     uint32_t errw = 0;
     if ((rc = read_err_word(e, &errw))) return rc;
     if (errw & SIMMR_ERRBIT_PDF)
@@ -1842,7 +1828,7 @@ static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads
 
 int simmr_pe_emit(simmr_engine* e, uint32_t read_id_base, const simmr_reads_out* out) {
   if (!e) return SIMMR_EINVAL;
-  if (e->plan_kind != PLAN_PE) return e->fail(SIMMR_ESTATE, "simmr_pe_emit called without a paired-end plan");
+  if (e->plan.kind != PLAN_PE) return e->fail(SIMMR_ESTATE, "simmr_pe_emit called without a paired-end plan");
   HIP_TRY(e, hipSetDevice(e->device));
   return emit_common(e, read_id_base, out);
 }
@@ -1852,16 +1838,15 @@ int simmr_long_plan(simmr_engine* e, uint32_t n_genomes, const uint32_t* genome_
                     const uint64_t* genome_reads, const simmr_error_profile* profile, int has_seed,
                     uint64_t seed, simmr_range shard, simmr_plan_info* info) {
   if (!e) return SIMMR_EINVAL;
-  e->plan_kind = PLAN_NONE;
-  e->fq_direct = false;  // (a direct FASTQ plan belongs to the plan it was made for)
-  HIP_TRY(e, hipSetDevice(e->device));
+  int rc = plan_reset(e);
+  if (rc) return rc;
   PlanScope plan_scope(e);  // (simmr_engine_set_plan_overlap: the other buffer set, the plan stream)
   if (!genome_idx || !genome_reads || n_genomes == 0) return e->fail(SIMMR_EINVAL, "no genomes");
-  int rc;
-  ProfileDev prof;
-  if ((rc = make_profile(e, profile, true, &prof))) return rc;
+  PlanState p;
+  p.kind = PLAN_LONG;
   uint32_t slot_round = 0;
-  if ((rc = plan_slot_round(e, prof, &slot_round))) return rc;
+  if ((rc = plan_begin(e, profile, true, &p, &slot_round))) return rc;
+  const ProfileDev& prof = p.prof;
   uint64_t total_reads = 0;
   for (uint32_t g = 0; g < n_genomes; g++) {
     if ((rc = check_genome(e, genome_idx[g]))) return rc;
@@ -1960,43 +1945,18 @@ int simmr_long_plan(simmr_engine* e, uint32_t n_genomes, const uint32_t* genome_
                          e->d_tables.as<Tables>(), e->d_err.as<uint32_t>());
     }
   }
-  e->plan_sorted = false;
   // (the lane-per-read kernels: the reference's streams, and a custom model in either mode)
-  if ((prof.rng_mode == SIMMR_RNG_REFERENCE || prof.kind == SIMMR_K_CUSTOM) && (rc = sort_by_length(e, count, 6))) return rc;
+  if ((prof.rng_mode == SIMMR_RNG_REFERENCE || prof.kind == SIMMR_K_CUSTOM) && (rc = sort_by_length(e, count, 6, &p.sorted))) return rc;
   if ((rc = scan_offsets(e, count, 1u, &total, slot_round))) return rc;
-  HIP_TRY(e, hipEventRecord(e->ev_b, e->stream));
-  uint32_t errw = 0;
-  if ((rc = read_err_word(e, &errw))) return rc;
-  if (errw & SIMMR_ERRBIT_GENOME) return e->fail(SIMMR_EGENOME, "no usable sequence for a drawn read length");
-  if (errw & SIMMR_ERRBIT_SLICE)
-    return e->fail(SIMMR_ERANGE, "a read would extend past its sequence (the reference panics on this slice)");
-  (void)hipEventElapsedTime(&e->last_plan_ms, e->ev_a, e->ev_b);
-  e->plan_kind = PLAN_LONG;
-  e->prof = prof;
-  e->plan_genome = 0;
-  e->plan_slot = slot_round ? SIMMR_SLOT16 : 0u;
-  e->plan_coarse = false;
-  e->plan_short_ok = false;
-  e->plan_first = first;
-  e->plan_units = count;
-  e->plan_total_bases = total;
-  e->plan_paired = false;
-  if (info) {
-    memset(info, 0, sizeof *info);
-    info->n_units = count;
-    info->n_reads = count;
-    info->total_bases = total;
-    info->seed_used = seed;
-    info->outer_slots = end_slot;
-    info->const_read_length = per_read ? 0 : L0;
-    info->slot_bytes = e->plan_slot;
-  }
-  return SIMMR_OK;
+  p.first = first;
+  p.units = count;
+  p.total_bases = total;
+  return plan_finish(e, p, "no usable sequence for a drawn read length", seed, end_slot, per_read ? 0 : L0, info);
 }
 
 int simmr_long_emit(simmr_engine* e, uint32_t read_id_base, const simmr_reads_out* out) {
   if (!e) return SIMMR_EINVAL;
-  if (e->plan_kind != PLAN_LONG) return e->fail(SIMMR_ESTATE, "simmr_long_emit called without a long-read plan");
+  if (e->plan.kind != PLAN_LONG) return e->fail(SIMMR_ESTATE, "simmr_long_emit called without a long-read plan");
   HIP_TRY(e, hipSetDevice(e->device));
   return emit_common(e, read_id_base, out);
 }
@@ -2223,15 +2183,15 @@ int simmr_fastq_emit(simmr_engine* e, const simmr_reads_out* reads, uint8_t* dst
 
 // ---- FASTQ text straight from the plan (include/simmr_hip.h) --------------------------------------------------
 static FqPlan fq_plan_view(simmr_engine* e) {
-  const bool paired = e->plan_paired;
-  const bool seeds2 = paired && e->prof.kind != SIMMR_K_PERFECT_SHORT;
+  const bool paired = e->plan.paired;
+  const bool seeds2 = paired && e->plan.prof.kind != SIMMR_K_PERFECT_SHORT;
   FqPlan pn;
   pn.pl = plan_arrays(e, seeds2);
   pn.u_contig = e->u_contig.as<uint32_t>();
-  pn.u_genome = (paired && !e->plan_multi) ? nullptr : e->u_genome.as<uint32_t>();
-  pn.first_unit = e->plan_first;
+  pn.u_genome = (paired && !e->plan.multi) ? nullptr : e->u_genome.as<uint32_t>();
+  pn.first_unit = e->plan.first;
   pn.read_id_base = e->fq_read_id_base;
-  pn.genome_const = e->plan_genome;
+  pn.genome_const = e->plan.genome;
   pn.paired = paired ? 1u : 0u;
   return pn;
 }
@@ -2239,8 +2199,8 @@ static FqPlan fq_plan_view(simmr_engine* e) {
 // does the current plan's emit kernel write into FASTQ text?  The counter-mode item kernel does, and so does its copy-only
 // form for perfect-short (no draws at all: the planned bases, a constant quality line; perfect_short.rs:24-44)
 static bool fq_direct_kernel(const simmr_engine* e) {
-  if (e->prof.kind == SIMMR_K_PERFECT_SHORT) return true;
-  return e->prof.kind != SIMMR_K_CUSTOM && e->prof.rng_mode != SIMMR_RNG_REFERENCE;
+  if (e->plan.prof.kind == SIMMR_K_PERFECT_SHORT) return true;
+  return e->plan.prof.kind != SIMMR_K_CUSTOM && e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE;
 }
 
 int simmr_fastq_plan_direct(simmr_engine* e, const char* header_format, const simmr_fastq_names* names,
@@ -2249,12 +2209,12 @@ int simmr_fastq_plan_direct(simmr_engine* e, const char* header_format, const si
   e->fq_ready = false;
   e->fq_direct = false;
   if (!header_format || !names || !total_bytes) return e->fail(SIMMR_EINVAL, "simmr_fastq_plan_direct: NULL argument");
-  if (e->plan_kind == PLAN_NONE) return e->fail(SIMMR_ESTATE, "simmr_fastq_plan_direct called without a plan");
+  if (e->plan.kind == PLAN_NONE) return e->fail(SIMMR_ESTATE, "simmr_fastq_plan_direct called without a plan");
   HIP_TRY(e, hipSetDevice(e->device));
   uint32_t lit_bytes = 0, n_slots = 0;
   int rc;
   if ((rc = fq_prepare(e, header_format, names, &lit_bytes, &n_slots))) return rc;
-  const uint64_t n_reads = e->plan_paired ? 2 * e->plan_units : e->plan_units;
+  const uint64_t n_reads = e->plan.paired ? 2 * e->plan.units : e->plan.units;
   if (!e->fq_len.ensure(std::max<uint64_t>(n_reads, 1) * 8) || !e->fq_hlen.ensure(std::max<uint64_t>(n_reads, 1)))
     return e->fail(SIMMR_ENOMEM, "record length allocation failed");
   HIP_TRY(e, hipEventRecord(e->ev_a, e->stream));
@@ -2289,7 +2249,7 @@ int simmr_fastq_plan_direct(simmr_engine* e, const char* header_format, const si
   e->fq_total = total;
   e->fq_slots = n_slots;
   e->fq_lit_bytes = lit_bytes;
-  e->fq_paired = e->plan_paired;
+  e->fq_paired = e->plan.paired;
   e->fq_ready = true;
   e->fq_direct = true;
   *total_bytes = total;
@@ -2298,22 +2258,22 @@ int simmr_fastq_plan_direct(simmr_engine* e, const char* header_format, const si
 
 int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
   if (!e) return SIMMR_EINVAL;
-  if (!e->fq_ready || !e->fq_direct || e->plan_kind == PLAN_NONE)
+  if (!e->fq_ready || !e->fq_direct || e->plan.kind == PLAN_NONE)
     return e->fail(SIMMR_ESTATE, "simmr_emit_fastq called without simmr_fastq_plan_direct on the current plan");
   if (dst_capacity < e->fq_total)
     return e->fail(SIMMR_ERANGE, "dst_capacity %llu < %llu bytes planned", (unsigned long long)dst_capacity,
                    (unsigned long long)e->fq_total);
-  const uint64_t n_units = e->plan_units, n_reads = e->fq_reads;
+  const uint64_t n_units = e->plan.units, n_reads = e->fq_reads;
   if (n_reads == 0) return SIMMR_OK;
   if (!dst) return e->fail(SIMMR_EINVAL, "dst is NULL");
   HIP_TRY(e, hipSetDevice(e->device));
-  const bool paired = e->plan_paired;
+  const bool paired = e->plan.paired;
   const bool direct_kernel = fq_direct_kernel(e);
   const FqTables tb = fq_tables(e, e->fq_slots);
   if (!direct_kernel) {
     // No emit kernel of this profile writes into text: the columns are built in buffers of the engine and framed from
     // there (the same kernels as simmr_*_emit + simmr_fastq_emit; qualities with the FASTQ offset, util.rs:46-57).
-    const uint64_t tb_bytes = std::max<uint64_t>(e->plan_total_bases, 1), nr = std::max<uint64_t>(n_reads, 1);
+    const uint64_t tb_bytes = std::max<uint64_t>(e->plan.total_bases, 1), nr = std::max<uint64_t>(n_reads, 1);
     if (!e->fd_seq.ensure(tb_bytes) || !e->fd_qual.ensure(tb_bytes) || !e->fd_seq_off.ensure((nr + 1) * 8) || !e->fd_start.ensure(nr * 8) ||
         !e->fd_end.ensure(nr * 8) || !e->fd_contig.ensure(nr * 4) || !e->fd_genome.ensure(nr * 4) || !e->fd_read_id.ensure(nr * 4) ||
         !e->fd_flags.ensure(nr))
@@ -2336,9 +2296,9 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
     if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "fastq launch failed: %s", hipGetErrorString(s));
     return SIMMR_OK;
   }
-  const bool seeds2 = paired && e->prof.kind != SIMMR_K_PERFECT_SHORT;
+  const bool seeds2 = paired && e->plan.prof.kind != SIMMR_K_PERFECT_SHORT;
   PlanArrays pl = plan_arrays(e, seeds2);
-  const uint32_t* u_genome = (paired && !e->plan_multi) ? nullptr : e->u_genome.as<uint32_t>();
+  const uint32_t* u_genome = (paired && !e->plan.multi) ? nullptr : e->u_genome.as<uint32_t>();
   unsigned long long* counters = e->d_counters.as<unsigned long long>();
   HIP_TRY(e, next_emit_events(e));
   HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
@@ -2346,17 +2306,17 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
     const ItemLaunch il = item_launch(e);
     const bool exc = il.exc, cached = il.cached, escq = philox_escq(e, 33u);
     const uint32_t grid = il.grid;
-    const bool copy_only = e->prof.kind == SIMMR_K_PERFECT_SHORT;  // (perfect-short: bases of the plan, every quality 60)
+    const bool copy_only = e->plan.prof.kind == SIMMR_K_PERFECT_SHORT;  // (perfect-short: bases of the plan, every quality 60)
     // The whole-line form: paired plans whose reads fit its segments, into a buffer its 16-byte chunks are aligned in,
     // with header slots that leave room for two workgroups per CU; everything else takes the item form.
     const uint32_t tl_pitch = tl_slot_pitch(e->fq_maxhdr);
     const uint32_t tl_lds = TL_GROUP * tl_pitch;
-    if (e->text_form == 2 && paired && e->plan_short_ok && ((uintptr_t)dst & 15u) == 0 && tl_lds <= 40u * 1024u) {
+    if (e->text_form == 2 && paired && e->plan.short_ok && ((uintptr_t)dst & 15u) == 0 && tl_lds <= 40u * 1024u) {
       auto tk = text_lines_kernel(exc, cached, escq, copy_only);
       HIP_TRY(e, grant_dynamic_lds(e, tk, tl_lds));  // (static + dynamic LDS may pass the default limit with long headers)
       const uint32_t t8 = tl_pitch / 8u, t9 = (t8 + 1u) / 2u;
-      hipLaunchKernelGGL(tk, dim3(grid), dim3(256), tl_lds, e->stream, e->prof, e->d_genomes.as<GenomeDev>(), e->plan_genome, n_units, pl,
-                         e->u_contig.as<uint32_t>(), u_genome, e->u_seed.as<uint64_t>(), dst, 33u, e->plan_first, e->fq_read_id_base,
+      hipLaunchKernelGGL(tk, dim3(grid), dim3(256), tl_lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), e->plan.genome, n_units, pl,
+                         e->u_contig.as<uint32_t>(), u_genome, e->u_seed.as<uint64_t>(), dst, 33u, e->plan.first, e->fq_read_id_base,
                          counters, e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(), tb, e->fq_lit_bytes, tl_pitch, t9,
                          65536u / t9 + 1u, (const uint64_t*)e->fq_off64.as<uint64_t>());
       HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
@@ -2383,9 +2343,20 @@ static TruthReads truth_reads(const simmr_reads_out* reads) {
   return TruthReads{reads->seq, reads->qual, reads->seq_off, reads->start, reads->end, reads->contig, reads->genome,
                     reads->flags, reads->seq_capacity, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
 }
-static uint32_t truth_grid(const simmr_engine* e, uint64_t n_reads) {
+// the grid of the kernels that walk the reads, a row of 16 lanes per read and 16 reads per workgroup and batch
+static_assert(TRUTH_WG_READS == STATS_WG_READS, "k_truth and k_read_stats batch their reads alike");
+static uint32_t row_grid(const simmr_engine* e, uint64_t n_reads, uint32_t wgs_per_cu) {
   const uint64_t n_batches = (n_reads + TRUTH_WG_READS - 1) / TRUTH_WG_READS;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_batches, (uint64_t)e->n_cu * TRUTH_WGS_PER_CU));
+  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_batches, (uint64_t)e->n_cu * wgs_per_cu));
+}
+// the columns those kernels read: all of them, seq and qual once there is a read (n_reads > 0), and, where the call
+// takes the layout from `reads` (check_slot), a slot_bytes it knows
+static int check_read_columns(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, const char* who, bool check_slot = true) {
+  if (!reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags ||
+      (n_reads > 0 && (!reads->seq || !reads->qual)))
+    return e->fail(SIMMR_EINVAL, "%s needs seq, qual, seq_off, start, end, contig, genome and flags", who);
+  if (check_slot && reads->slot_bytes > 1u && reads->slot_bytes != SIMMR_SLOT16) return e->fail(SIMMR_EINVAL, "reads->slot_bytes is 0 (compact) or 16");
+  return SIMMR_OK;
 }
 
 int simmr_truth_plan(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint64_t* n_edits) {
@@ -2393,10 +2364,8 @@ int simmr_truth_plan(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
   e->tr_ready = false;
   e->tr_emitted = false;
   if (!reads || !n_edits) return e->fail(SIMMR_EINVAL, "simmr_truth_plan: NULL argument");
-  if (!reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags ||
-      (n_reads > 0 && (!reads->seq || !reads->qual)))
-    return e->fail(SIMMR_EINVAL, "simmr_truth_plan needs seq, qual, seq_off, start, end, contig, genome and flags");
-  if (reads->slot_bytes > 1u && reads->slot_bytes != SIMMR_SLOT16) return e->fail(SIMMR_EINVAL, "reads->slot_bytes is 0 (compact) or 16");
+  int rc;
+  if ((rc = check_read_columns(e, reads, n_reads, "simmr_truth_plan"))) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
   for (hipEvent_t& ev : e->tr_ev)
     if (!ev) HIP_TRY(e, hipEventCreate(&ev));
@@ -2405,11 +2374,10 @@ int simmr_truth_plan(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
   HIP_TRY(e, hipMemsetAsync(e->tr_err.p, 0, 64, e->stream));
   HIP_TRY(e, hipEventRecord(e->tr_ev[0], e->stream));
   if (n_reads > 0)
-    hipLaunchKernelGGL(k_truth<false>, dim3(truth_grid(e, n_reads)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
+    hipLaunchKernelGGL(k_truth<false>, dim3(row_grid(e, n_reads, TRUTH_WGS_PER_CU)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
                        (uint32_t)e->genomes.size(), truth_reads(reads), n_reads, e->tr_nm.as<uint32_t>(),
                        (const uint64_t*)nullptr, TruthCols{nullptr, nullptr, nullptr, nullptr}, e->tr_err.as<uint32_t>());
   uint64_t total = 0;
-  int rc;
   if ((rc = scan_scaled<uint32_t>(e, e->tr_nm, n_reads, 1u, e->tr_off, &total))) return rc;
   HIP_TRY(e, hipEventRecord(e->tr_ev[1], e->stream));
   uint32_t errw = 0;
@@ -2434,8 +2402,8 @@ int simmr_truth_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_
   if (!e->tr_ready || reads->seq != e->tr_seq || reads->seq_off != e->tr_seq_off ||
       (reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u) != e->tr_slot)
     return e->fail(SIMMR_ESTATE, "simmr_truth_emit called without a simmr_truth_plan for these columns");
-  if (!reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags || (e->tr_reads > 0 && !reads->qual))
-    return e->fail(SIMMR_EINVAL, "simmr_truth_emit needs seq, qual, seq_off, start, end, contig, genome and flags");
+  // (seq and seq_off are the plan's, which checked them; so is the layout)
+  if (int rc = check_read_columns(e, reads, e->tr_reads, "simmr_truth_emit", false)) return rc;
   const bool any_edit = out->edit_pos || out->edit_ref || out->edit_alt || out->edit_qual;
   if (any_edit && !out->edit_off) return e->fail(SIMMR_EINVAL, "edit columns without edit_off");
   if ((out->nm || out->edit_off) && out->reads_capacity < e->tr_reads)
@@ -2451,7 +2419,7 @@ int simmr_truth_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_
   if (out->edit_off)
     HIP_TRY(e, hipMemcpyAsync(out->edit_off, e->tr_off.p, (e->tr_reads + 1) * 8, hipMemcpyDeviceToDevice, e->stream));
   if (any_edit && e->tr_edits > 0)
-    hipLaunchKernelGGL(k_truth<true>, dim3(truth_grid(e, e->tr_reads)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
+    hipLaunchKernelGGL(k_truth<true>, dim3(row_grid(e, e->tr_reads, TRUTH_WGS_PER_CU)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
                        (uint32_t)e->genomes.size(), truth_reads(reads), e->tr_reads, (uint32_t*)nullptr,
                        (const uint64_t*)e->tr_off.as<uint64_t>(), TruthCols{out->edit_pos, out->edit_ref, out->edit_alt, out->edit_qual},
                        e->tr_err.as<uint32_t>());
@@ -2493,17 +2461,14 @@ int simmr_stats_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_re
   if (!e) return SIMMR_EINVAL;
   if (!reads) return e->fail(SIMMR_EINVAL, "simmr_stats_add: NULL argument");
   if (n_sets != 1u && n_sets != 2u) return e->fail(SIMMR_EINVAL, "simmr_stats_add: n_sets is 1 or 2");
-  if (!reads->seq || !reads->qual || !reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags)
-    return e->fail(SIMMR_EINVAL, "simmr_stats_add needs seq, qual, seq_off, start, end, contig, genome and flags");
-  if (reads->slot_bytes > 1u && reads->slot_bytes != SIMMR_SLOT16) return e->fail(SIMMR_EINVAL, "reads->slot_bytes is 0 (compact) or 16");
+  // (seq and qual are asked for even of no reads)
+  if (int rc = check_read_columns(e, reads, std::max<uint64_t>(n_reads, 1), "simmr_stats_add")) return rc;
   if (!e->st_ready) return e->fail(SIMMR_ESTATE, "simmr_stats_add called before simmr_stats_reset");
   HIP_TRY(e, hipSetDevice(e->device));
   HIP_TRY(e, hipEventRecord(e->st_ev[0], e->stream));
   if (n_reads > 0) {
-    const uint64_t n_batches = (n_reads + STATS_WG_READS - 1) / STATS_WG_READS;
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_batches, (uint64_t)e->n_cu * STATS_WGS_PER_CU));
     unsigned long long* tab = e->st_tab.as<unsigned long long>();
-    hipLaunchKernelGGL(k_read_stats, dim3(grid), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(), (uint32_t)e->genomes.size(),
+    hipLaunchKernelGGL(k_read_stats, dim3(row_grid(e, n_reads, STATS_WGS_PER_CU)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(), (uint32_t)e->genomes.size(),
                        truth_reads(reads), n_reads, n_sets, reads->qual_offset, tab, (uint32_t*)(tab + STATS_TABLE_WORDS));
   }
   HIP_TRY(e, hipEventRecord(e->st_ev[1], e->stream));

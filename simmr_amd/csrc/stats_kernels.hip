@@ -2,11 +2,11 @@
 // as integer sums in a simmr_run_stats (include/simmr_hip.h states every table).  Included by engine.hip after
 // truth_kernels.hip; entry points simmr_stats_reset / simmr_stats_add / simmr_stats_read.
 //
-// One kernel, k_read_stats, one pass over the columns.  It walks the reads as k_truth does — STATS_LANES = 16 lanes (one
-// DPP row) share a read, a lane takes 16 bases per round, the expected bytes come from gather_piece / expand4, a read's
-// last 16-byte window of seq[] AND of qual[] ends at the read's end with the overlapped bits masked, reads under 16
-// bases are loaded bytewise, the same bounds check keeps every load inside the read — and turns each base into adds on
-// 32-bit tables in LDS.  The workgroup adds its LDS tables to the engine's 64-bit tables in HBM (the struct itself, word
+// One kernel, k_read_stats, one pass over the columns.  It walks the reads with the walker of truth_kernels.hip
+// (walk_open / walk_window, shared with k_truth) — STATS_LANES = 16 lanes (one DPP row) share a read, a lane takes 16
+// bases per round, the expected bytes come from gather_piece / expand4, a read's last 16-byte window of seq[] AND of
+// qual[] ends at the read's end with the overlapped bits masked, reads under 16 bases are loaded bytewise, one bounds
+// check keeps every load inside the read — and turns each base into adds on 32-bit tables in LDS.  The workgroup adds its LDS tables to the engine's 64-bit tables in HBM (the struct itself, word
 // for word) and zeroes them; there is no second kernel.
 //
 // LDS, 36 616 bytes per workgroup (four workgroups of 256 per CU: 4 waves per SIMD):
@@ -65,15 +65,6 @@ SIMMR_DEV uint32_t stats_class(uint32_t x) {
 // byte B (a constant) of four words
 #define STATS_BYTE(v, B) (((v)[(B) >> 2] >> (((B) & 3u) * 8u)) & 0xffu)
 
-// sum over the row of 16 lanes (DPP row shifts), kept by the row's last lane
-SIMMR_DEV uint32_t stats_row_sum(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);  // row_shr:1
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);  // row_shr:2
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);  // row_shr:4
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);  // row_shr:8
-  return v;
-}
-
 // tab: the engine's simmr_run_stats in HBM (STATS_TABLE_WORDS words); err: its sticky error word
 __global__ void __launch_bounds__(256)
 k_read_stats(const GenomeDev* __restrict__ genomes, uint32_t n_genomes, TruthReads rd, uint64_t n_reads, uint32_t n_sets,
@@ -130,70 +121,19 @@ k_read_stats(const GenomeDev* __restrict__ genomes, uint32_t n_genomes, TruthRea
     since_flush++;
 
     const uint64_t r = batch * STATS_WG_READS + row;
-    // every lane of a row reads the same columns; all-or-nothing per row, so the DPP rows stay whole (k_truth)
-    uint32_t L = 0, rev = 0;
-    uint64_t so = 0;
-    int64_t pos0 = 0;
-    bool good = false;
-    GenomeDev G{};
-    if (r < n_reads) {
-      const uint64_t a = rd.start[r], b = rd.end[r];
-      const uint64_t lo = a < b ? a : b, len = a < b ? b - a : a - b;
-      const uint32_t g = rd.genome[r], c = rd.contig[r];
-      so = rd.seq_off[r];
-      const uint64_t so1 = rd.seq_off[r + 1];
-      rev = rd.flags[r] & SIMMR_FLAG_REVCOMP;
-      bool ok = g < n_genomes && len <= STATS_MAX_L && so <= so1 && so1 <= rd.seq_capacity && len <= so1 - so;
-      if (ok) {
-        G = genomes[g];
-        ok = G.packed != nullptr && c < G.n_contigs;
-      }
-      if (ok) {
-        const ContigDev C = G.contigs[c];
-        ok = lo <= C.len && len <= C.len - lo;
-        L = (uint32_t)len;
-        pos0 = (int64_t)(C.base + lo) + (rev ? (int64_t)len - 1 : 0);  // gather_piece: byte k from pos0 + k, or pos0 - k complemented
-      }
-      good = ok;
-      if (!ok) {
-        L = 0;
-        if (sub == 0) atomicOr(err, 1u);
-      }
-    }
-    const PieceSrc src{pos0, rev};
-    const uint8_t* seq = rd.seq + so;
-    const uint8_t* qual = rd.qual + (rd.slot16 ? (so & ~15ull) : so);
+    const ReadWalk w = walk_open<STATS_MAX_L>(genomes, n_genomes, rd, r, n_reads, err, 1u, sub == 0);
+    const uint32_t L = w.L;
+    const bool good = w.good;
+    const uint8_t* seq = rd.seq + w.so;
+    const uint8_t* qual = rd.qual + (rd.slot16 ? (w.so & ~15ull) : w.so);
     const uint32_t n_groups = (L + 15u) >> 4;
     uint32_t nm = 0, gc = 0, same01 = 0, same23 = 0;  // edits; 'G' + 'C' written; unedited A | C << 16 and G | T << 16
     for (uint32_t g0 = 0; g0 < n_groups; g0 += STATS_LANES) {  // (uniform over the row)
       const uint32_t grp = g0 + sub;
       if (grp >= n_groups) continue;
-      const uint32_t k16 = grp * 16u;
-      uint32_t k = 0, keep;
-      v4u32 have, qv;
-      if (L >= 16u) {
-        k = k16 + 16u <= L ? k16 : L - 16u;       // the last window ends at the read's end
-        keep = (0xffffu << (k16 - k)) & 0xffffu;  // ... and owns only the bases no earlier window had
-        have = __builtin_nontemporal_load((global_v4u32_unaligned_ptr)(seq + k));
-        qv = __builtin_nontemporal_load((global_v4u32_unaligned_ptr)(qual + k));
-      } else {
-        uint32_t w[4] = {0u, 0u, 0u, 0u}, x[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; j++)
-          if (j < L) {
-            w[j >> 2] |= (uint32_t)seq[j] << ((j & 3u) * 8u);
-            x[j >> 2] |= (uint32_t)qual[j] << ((j & 3u) * 8u);
-          }
-        have = v4u32{w[0], w[1], w[2], w[3]};
-        qv = v4u32{x[0], x[1], x[2], x[3]};
-        keep = (1u << L) - 1u;
-      }
-      uint32_t codes, exc;
-      gather_piece(G, src, k, codes, exc);
-      const v4u32 want = v4u32{expand4(codes & 0xffu, exc & 0xfu), expand4((codes >> 8) & 0xffu, (exc >> 4) & 0xfu),
-                               expand4((codes >> 16) & 0xffu, (exc >> 8) & 0xfu), expand4(codes >> 24, (exc >> 12) & 0xfu)};
-      const uint32_t diff = (truth_nonzero_bytes(have.x ^ want.x) | truth_nonzero_bytes(have.y ^ want.y) << 4 |
-                             truth_nonzero_bytes(have.z ^ want.z) << 8 | truth_nonzero_bytes(have.w ^ want.w) << 12) & keep;
+      const ReadWindow x = walk_window<true>(w, grp, seq, qual);
+      const uint32_t k = x.k, keep = x.keep, diff = x.diff;
+      const v4u32 have = x.have, qv = x.qv, want = x.want;
       nm += __builtin_popcount(diff);
 #pragma unroll
       for (uint32_t b = 0; b < 16u; b++) {
@@ -218,10 +158,10 @@ k_read_stats(const GenomeDev* __restrict__ genomes, uint32_t n_genomes, TruthRea
         }
       }
     }
-    nm = stats_row_sum(nm);
-    gc = stats_row_sum(gc);
-    same01 = stats_row_sum(same01);
-    same23 = stats_row_sum(same23);
+    nm = row_inclusive_scan_u32(nm);
+    gc = row_inclusive_scan_u32(gc);
+    same01 = row_inclusive_scan_u32(same01);
+    same23 = row_inclusive_scan_u32(same23);
     if (sub == STATS_LANES - 1u && good) {
       atomicAdd(&lds[STATS_WORD(reads) + set], 1u);
       atomicAdd(&lds[STATS_WORD(nm_hist) + (nm < SIMMR_STATS_NM_BINS ? nm : SIMMR_STATS_NM_BINS - 1u)], 1u);

@@ -18,6 +18,8 @@
 // right-aligned in their slots.  Reads shorter than 16 bases are loaded bytewise.
 // The expected bytes come from gather_piece (the emit kernels' funnel-shift addressing and code-domain reverse
 // complement) and expand4; the comparison is bytewise, so 'N' and '-' need no special case.
+// The bounds check and the window loads are the read walker below (walk_open / walk_window), which k_read_stats
+// (stats_kernels.hip, included after this file) uses too.
 #pragma once
 
 namespace simmr {
@@ -59,6 +61,96 @@ SIMMR_DEV uint32_t truth_byte(const v4u32 v, uint32_t b) {
   return (((b & 8u) ? hi : lo) >> ((b & 3u) * 8u)) & 0xffu;
 }
 
+// ---- the read walker: shared by k_truth and k_read_stats (stats_kernels.hip) ----------------------------------------
+// Sixteen lanes (one DPP row) share a read.  walk_open checks a row's read once, walk_window loads one lane's 16 bases
+// of it; between them they hold every rule that keeps a load inside the read, so both kernels answer to one copy.
+
+// A row's read, opened: L bases of seq[] from byte `so`; output byte k is the reference's pos0 + k (forward) or pos0 - k,
+// complemented (reverse): gather_piece.  A refused read, and a row past n_reads, has L = 0 and good = false.
+struct ReadWalk {
+  uint32_t L, rev;
+  uint64_t so;
+  int64_t pos0;
+  GenomeDev G;
+  bool good;
+};
+// The bounds check: genome staged, contig in range, so <= so1 <= seq_capacity, len <= so1 - so and MAX_L, coordinates
+// inside the contig.  Every lane of a row reads the same columns (one address per row) and so takes the same branch:
+// all-or-nothing per row, which keeps the DPP rows whole.  A refused read raises the caller's `errbit` in the caller's
+// error word `err`, through the one lane of its row that has `raise` set.  (The atomic sits where the read is refused:
+// raised by the caller after the checks have joined again, both kernels measured slower.)
+template <uint64_t MAX_L>
+SIMMR_DEV ReadWalk walk_open(const GenomeDev* __restrict__ genomes, uint32_t n_genomes, const TruthReads& rd, uint64_t r,
+                             uint64_t n_reads, uint32_t* __restrict__ err, uint32_t errbit, bool raise) {
+  uint32_t L = 0, rev = 0;
+  uint64_t so = 0;
+  int64_t pos0 = 0;
+  bool good = false;
+  GenomeDev G{};
+  if (r < n_reads) {
+    const uint64_t a = rd.start[r], b = rd.end[r];
+    const uint64_t lo = a < b ? a : b, len = a < b ? b - a : a - b;
+    const uint32_t g = rd.genome[r], c = rd.contig[r];
+    so = rd.seq_off[r];
+    const uint64_t so1 = rd.seq_off[r + 1];
+    rev = rd.flags[r] & SIMMR_FLAG_REVCOMP;
+    bool ok = g < n_genomes && len <= MAX_L && so <= so1 && so1 <= rd.seq_capacity && len <= so1 - so;
+    if (ok) {
+      G = genomes[g];
+      ok = G.packed != nullptr && c < G.n_contigs;
+    }
+    if (ok) {
+      const ContigDev C = G.contigs[c];
+      ok = lo <= C.len && len <= C.len - lo;
+      L = (uint32_t)len;
+      pos0 = (int64_t)(C.base + lo) + (rev ? (int64_t)len - 1 : 0);
+    }
+    good = ok;
+    if (!ok) {
+      L = 0;
+      if (raise) atomicOr(err, errbit);
+    }
+  }
+  return ReadWalk{L, rev, so, pos0, G, good};
+}
+
+// Group `grp` (< ceil(L / 16)) of an opened read: bit b of keep = byte b of the window is base k + b and belongs to this
+// group; have / qv = the 16 bytes of seq[] / qual[] (qv only with QUAL), want = what the reference holds there, diff =
+// the kept bytes where they differ.
+struct ReadWindow {
+  uint32_t k, keep, diff;
+  v4u32 have, qv, want;
+};
+template <bool QUAL>
+SIMMR_DEV ReadWindow walk_window(const ReadWalk& w, uint32_t grp, const uint8_t* seq, const uint8_t* qual) {
+  ReadWindow o{};
+  const uint32_t k16 = grp * 16u, L = w.L;
+  if (L >= 16u) {
+    o.k = k16 + 16u <= L ? k16 : L - 16u;         // the last window ends at the read's end
+    o.keep = (0xffffu << (k16 - o.k)) & 0xffffu;  // ... and owns only the bases no earlier window had
+    o.have = __builtin_nontemporal_load((global_v4u32_unaligned_ptr)(seq + o.k));
+    if (QUAL) o.qv = __builtin_nontemporal_load((global_v4u32_unaligned_ptr)(qual + o.k));
+  } else {
+    uint32_t h[4] = {0u, 0u, 0u, 0u}, q[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; j++)
+      if (j < L) {
+        h[j >> 2] |= (uint32_t)seq[j] << ((j & 3u) * 8u);
+        if (QUAL) q[j >> 2] |= (uint32_t)qual[j] << ((j & 3u) * 8u);
+      }
+    o.have = v4u32{h[0], h[1], h[2], h[3]};
+    o.qv = v4u32{q[0], q[1], q[2], q[3]};
+    o.keep = (1u << L) - 1u;
+  }
+  uint32_t codes, exc;
+  gather_piece(w.G, PieceSrc{w.pos0, w.rev}, o.k, codes, exc);
+  o.want = v4u32{expand4(codes & 0xffu, exc & 0xfu), expand4((codes >> 8) & 0xffu, (exc >> 4) & 0xfu),
+                 expand4((codes >> 16) & 0xffu, (exc >> 8) & 0xfu), expand4(codes >> 24, (exc >> 12) & 0xfu)};
+  o.diff = (truth_nonzero_bytes(o.have.x ^ o.want.x) | truth_nonzero_bytes(o.have.y ^ o.want.y) << 4 |
+            truth_nonzero_bytes(o.have.z ^ o.want.z) << 8 | truth_nonzero_bytes(o.have.w ^ o.want.w) << 12) & o.keep;
+  return o;
+}
+
 template <bool WRITE>
 __global__ void __launch_bounds__(256)
 k_truth(const GenomeDev* __restrict__ genomes, uint32_t n_genomes, TruthReads rd, uint64_t n_reads,
@@ -67,36 +159,9 @@ k_truth(const GenomeDev* __restrict__ genomes, uint32_t n_genomes, TruthReads rd
   const uint64_t n_batches = (n_reads + TRUTH_WG_READS - 1u) / TRUTH_WG_READS;
   for (uint64_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
     const uint64_t r = batch * TRUTH_WG_READS + row;
-    // every lane of a row reads the same columns (one address per row); all-or-nothing per row, so the DPP rows stay whole
-    uint32_t L = 0, rev = 0;
-    uint64_t so = 0;
-    int64_t pos0 = 0;
-    GenomeDev G{};
-    if (r < n_reads) {
-      const uint64_t a = rd.start[r], b = rd.end[r];
-      const uint64_t lo = a < b ? a : b, len = a < b ? b - a : a - b;
-      const uint32_t g = rd.genome[r], c = rd.contig[r];
-      so = rd.seq_off[r];
-      const uint64_t so1 = rd.seq_off[r + 1];
-      rev = rd.flags[r] & SIMMR_FLAG_REVCOMP;
-      bool ok = g < n_genomes && len <= 0xffffffffull && so <= so1 && so1 <= rd.seq_capacity && len <= so1 - so;
-      if (ok) {
-        G = genomes[g];
-        ok = G.packed != nullptr && c < G.n_contigs;
-      }
-      if (ok) {
-        const ContigDev C = G.contigs[c];
-        ok = lo <= C.len && len <= C.len - lo;
-        L = (uint32_t)len;
-        // output byte k comes from pos0 + k (forward) or pos0 - k, complemented (reverse): gather_piece
-        pos0 = (int64_t)(C.base + lo) + (rev ? (int64_t)len - 1 : 0);
-      }
-      if (!ok) {
-        L = 0;
-        if (sub == 0) atomicOr(err, SIMMR_ERRBIT_TRUTH);
-      }
-    }
-    const PieceSrc src{pos0, rev};
+    const ReadWalk w = walk_open<0xffffffffull>(genomes, n_genomes, rd, r, n_reads, err, SIMMR_ERRBIT_TRUTH, sub == 0);
+    const uint32_t L = w.L;
+    const uint64_t so = w.so;
     const uint8_t* seq = rd.seq + so;
     const uint32_t n_groups = (L + 15u) >> 4;
     uint64_t cursor = 0;  // WRITE: where the next edit of this round's first lane goes
@@ -108,59 +173,29 @@ k_truth(const GenomeDev* __restrict__ genomes, uint32_t n_genomes, TruthReads rd
     uint32_t count = 0;
     for (uint32_t g0 = 0; g0 < n_groups; g0 += TRUTH_LANES) {  // (uniform over the row)
       const uint32_t grp = g0 + sub;
-      uint32_t diff = 0, k = 0;
-      v4u32 have{}, want{};
-      if (grp < n_groups) {
-        const uint32_t k16 = grp * 16u;
-        uint32_t keep = 0xffffu;
-        if (L >= 16u) {
-          k = k16 + 16u <= L ? k16 : L - 16u;       // the last window ends at the read's end
-          keep = (0xffffu << (k16 - k)) & 0xffffu;  // ... and owns only the bases no earlier window had
-          have = __builtin_nontemporal_load((global_v4u32_unaligned_ptr)(seq + k));
-        } else {
-          uint32_t w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-          for (uint32_t j = 0; j < 16u; j++)
-            if (j < L) w[j >> 2] |= (uint32_t)seq[j] << ((j & 3u) * 8u);
-          have = v4u32{w[0], w[1], w[2], w[3]};
-          keep = (1u << L) - 1u;
-        }
-        uint32_t codes, exc;
-        gather_piece(G, src, k, codes, exc);
-        want = v4u32{expand4(codes & 0xffu, exc & 0xfu), expand4((codes >> 8) & 0xffu, (exc >> 4) & 0xfu),
-                     expand4((codes >> 16) & 0xffu, (exc >> 8) & 0xfu), expand4(codes >> 24, (exc >> 12) & 0xfu)};
-        diff = (truth_nonzero_bytes(have.x ^ want.x) | truth_nonzero_bytes(have.y ^ want.y) << 4 |
-                truth_nonzero_bytes(have.z ^ want.z) << 8 | truth_nonzero_bytes(have.w ^ want.w) << 12) & keep;
-      }
-      const uint32_t n = __builtin_popcount(diff);
+      ReadWindow x{};
+      if (grp < n_groups) x = walk_window<false>(w, grp, seq, nullptr);
+      const uint32_t n = __builtin_popcount(x.diff);
       if (!WRITE) {
         count += n;
       } else {
-        // inclusive scan over the row of 16 lanes (DPP row shifts; lanes without a group add 0)
-        uint32_t inc = n;
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x111, 0xf, 0xf, true);  // row_shr:1
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x112, 0xf, 0xf, true);  // row_shr:2
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x114, 0xf, 0xf, true);  // row_shr:4
-        inc += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)inc, 0x118, 0xf, 0xf, true);  // row_shr:8
+        // inclusive scan over the row of 16 lanes (lanes without a group add 0)
+        const uint32_t inc = row_inclusive_scan_u32(n);
         const uint32_t round_total = (uint32_t)__shfl((int)inc, (int)TRUTH_LANES - 1, (int)TRUTH_LANES);  // the row's last lane
         uint64_t o = cursor + (inc - n);
         // (o < limit: seq[] changed between the plan and this call must not carry a store past the read's own slots)
-        for (uint32_t m = diff; m && o < limit; m &= m - 1u, o++) {
+        for (uint32_t m = x.diff; m && o < limit; m &= m - 1u, o++) {
           const uint32_t bit = (uint32_t)__builtin_ctz(m);
-          if (out.pos) out.pos[o] = k + bit;
-          if (out.ref) out.ref[o] = (uint8_t)truth_byte(want, bit);
-          if (out.alt) out.alt[o] = (uint8_t)truth_byte(have, bit);
-          if (out.qual) out.qual[o] = rd.qual[qbase + k + bit];
+          if (out.pos) out.pos[o] = x.k + bit;
+          if (out.ref) out.ref[o] = (uint8_t)truth_byte(x.want, bit);
+          if (out.alt) out.alt[o] = (uint8_t)truth_byte(x.have, bit);
+          if (out.qual) out.qual[o] = rd.qual[qbase + x.k + bit];
         }
         cursor += round_total;
       }
     }
     if (!WRITE) {
-      // sum over the row (DPP), kept by its last lane
-      count += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)count, 0x111, 0xf, 0xf, true);
-      count += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)count, 0x112, 0xf, 0xf, true);
-      count += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)count, 0x114, 0xf, 0xf, true);
-      count += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)count, 0x118, 0xf, 0xf, true);
+      count = row_inclusive_scan_u32(count);  // the row's sum, kept by its last lane
       if (sub == TRUTH_LANES - 1u && r < n_reads) nm[r] = count;
     }
   }

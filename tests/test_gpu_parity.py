@@ -847,6 +847,54 @@ def test_pe_plan_multi_edges(engine, genome_multi, genome_1m):
     assert ei.value.code == _abi.ENOTSUP
 
 
+def test_plans_in_sequence_on_one_engine(engine, oracle, genome_multi):
+    """A multi-genome paired plan (one genome with an exception plane), a long-read plan and a single-genome
+    perfect-short plan, one after the other on one engine, each emit compared with the oracle: a plan leaves nothing of
+    itself to the next.  A plan call that fails leaves no plan: the emit after it answers SIMMR_ESTATE."""
+    from simmr_amd import SimmrError
+    from simmr_amd.engine import Reads
+    rng = np.random.default_rng(9)
+    exc = _synth.synthetic_contigs([20_000], 41)[0].copy()
+    exc[rng.integers(0, 20_000, 2500)] = ord("N")
+    engine.stage_genome(6, [exc])
+    hosts = {1: genome_multi, 6: _oracle.HostGenome([exc])}
+    # 1: 64 pairs of 20 bp over two genomes, counter mode
+    prof = MinimalShortErrorProfile(read_length=20, insert_size=20, rng_mode=_abi.RNG_PHILOX).pod()
+    order, reads, seed = [6, 1], [60, 68], 11
+    parts, base = [], 0
+    for gi, n in zip(order, reads):
+        o = _oracle.simulate_pe(oracle, hosts[gi], prof, n, seed, read_id_base=base, qual_offset=33).trimmed()
+        o["genome"] = np.full(o["read_id"].size, gi, np.uint32)
+        parts.append(o)
+        base += n // 2
+    lens = np.concatenate([np.diff(p["seq_off"].astype(np.int64)) for p in parts])
+    whole = {c: np.concatenate([p[c] for p in parts]) for c in ("seq", "qual", "start", "end", "contig", "genome", "read_id", "flags")}
+    whole["seq_off"] = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    d = engine.simulate_pe_reads_multi(order, reads, prof, seed, qual_offset=33).to_host()
+    assert d["read_id"].size == 128 and (d["seq"] == ord("N")).any()
+    assert_same(d, whole, cols=COLS + ("genome",), what="multi: ")
+    # 2: 40 long reads of the plain genome, a length per read
+    lp = MinimalLongErrorProfile(gamma_mean=3000.0, gamma_std=2500.0, length_mode=_abi.LEN_PER_READ, rng_mode=_abi.RNG_PHILOX).pod()
+    d = engine.simulate_long_reads([1], [40], lp, 3, qual_offset=33).to_host()
+    o = _oracle.simulate_long(oracle, [genome_multi], [40], lp, 3, qual_offset=33).trimmed()
+    o["genome"][:] = 1
+    assert_same(d, o, cols=COLS + ("genome",), what="long: ")
+    # 3: 64 perfect-short pairs of one genome
+    ps = PerfectShortErrorProfile().pod()
+    d = engine.simulate_pe_reads_from_genome(6, ps, 128, 5, qual_offset=33).to_host()
+    assert_same(d, _oracle.simulate_pe(oracle, hosts[6], ps, 128, 5, qual_offset=33).trimmed(), what="perfect-short: ")
+    assert (d["genome"] == 6).all() and (d["seq"] == ord("N")).any()
+    # 4: a plan call that fails takes the plan before it along
+    info = engine.pe_plan(6, ps, 128, 5)
+    out = Reads.allocate(info.n_reads, info.total_bases, engine.device, 33, info.slot_bytes)
+    with pytest.raises(SimmrError) as ei:
+        engine.pe_plan(63, ps, 128, 5)  # a slot no test stages
+    assert ei.value.code == _abi.EINVAL
+    with pytest.raises(SimmrError) as ei:
+        engine.pe_emit(0, out)
+    assert ei.value.code == _abi.ESTATE
+
+
 def test_long_reads_uniform_start(engine, oracle, genome_multi, genome_1m):
     """SIMMR_START_UNIFORM: the start is drawn over the whole sequence instead of the
     reference's [0, read_length); same streams otherwise, bit-exact against the oracle in both length modes."""

@@ -9,6 +9,7 @@ import pytest
 from simmr_amd import (CustomShortErrorProfile, MinimalLongErrorProfile, MinimalShortErrorProfile, PerfectLongErrorProfile,
                        PerfectShortErrorProfile, _abi)
 from tests import _model, _oracle, _synth, _truth
+from tests._hand_built import hand_built
 from tests.test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
@@ -128,6 +129,21 @@ def test_long_reads_of_65535_bases(engine, oracle, genomes, layout):
     h = dev.to_host()
     assert (np.abs(h["end"].astype(np.int64) - h["start"].astype(np.int64)) == 65535).all()
     check(engine, oracle, genomes, dev, ora, "65 535-base reads", subs)
+
+
+def test_hand_built_columns(engine, oracle, genomes, layout):
+    """The columns of tests/test_gpu_stats.py::test_hand_built_columns through the truth pass: lengths 0, 1, 15, 16, 17, 511,
+    512, 513 on both strands, reverse mates right-aligned in their slots, a read that ends at its contig's end, a window
+    inside an N run.  k_truth and k_read_stats walk a read with the same code, so both answer for these shapes, and
+    they count the same edits."""
+    dev, host = hand_built(oracle, genomes, layout, engine.device, np.random.default_rng(5))
+    want = _truth.model(oracle, host, genomes)
+    got = device_truth(engine, dev)
+    _truth.assert_truth(got, want, "hand-built")
+    assert np.array_equal(got["nm"], np.diff(got["edit_off"].astype(np.int64)).astype(np.uint32)) and got["nm"].max() == 75
+    engine.stats_reset()
+    engine.stats_add(dev, 1)
+    assert int(got["nm"].sum()) == int(engine.stats()["qual_mismatch"].sum())
 
 
 @pytest.mark.parametrize("rng_mode", [_abi.RNG_REFERENCE, _abi.RNG_PHILOX], ids=["reference", "philox"])

@@ -216,7 +216,7 @@ def test_block_loop_tests_are_sized_from_the_kernels_constants():
     for needle in ("uint32_t philox_wgs_per_cu = 128;",
                    "std::min<uint64_t>(groups, (uint64_t)e->n_cu * 8 * e->perfect_mult);",
                    "std::min<uint64_t>(wgs, (uint64_t)e->n_cu * (uint64_t)per_cu * e->lanes_mult);",
-                   "static bool philox_escq(const simmr_engine* e, uint32_t offset) { return offset + e->prof.philox_qmax1 <= 127u; }",
+                   "static bool philox_escq(const simmr_engine* e, uint32_t offset) { return offset + e->plan.prof.philox_qmax1 <= 127u; }",
                    "philox_escq(e, out->qual_offset & 0xffu)",
                    "philox_escq(e, 33u)"):
         assert needle in engine, needle
