@@ -926,7 +926,9 @@ static ItemLaunch item_launch(const simmr_engine* e) {
   if (e->plan.paired) t.exc = e->plan.any_exc;
   else for (const auto& g : e->genomes) t.exc = t.exc || (g.staged && g.has_exc);
   t.cached = e->plan.paired && !e->plan.multi && e->plan.genome < e->genomes.size() &&
-             e->genomes[e->plan.genome].contigs.size() <= PHILOX_CBASE;
+             e->genomes[e->plan.genome].contigs.size() <= PHILOX_CBASE &&
+             // (the slot form of the cached kernels addresses the plane with 32-bit byte offsets: PhRec)
+             e->genomes[e->plan.genome].plane_bases / 4u + 4u * (FRONT_PAD_WORDS + BACK_PAD_WORDS) < (1ull << 32);
   const uint64_t n_units = e->plan.units;
   const uint64_t blocks = (n_units + PHILOX_UNITS - 1) / PHILOX_UNITS;
   t.grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * e->philox_wgs_per_cu);

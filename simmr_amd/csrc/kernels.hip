@@ -1838,15 +1838,26 @@ SIMMR_DEV void store_tail2(uint8_t* __restrict__ d0, uint64_t lo0, uint64_t hi0,
   if (n & 1u) { d0[p] = (uint8_t)v0; d1[p] = (uint8_t)v1; }
 }
 
-// Per-read record of a block: 32 bytes, read with two ds_read_b128.
+// Per-read record of a block: 32 bytes, read with two ds_read_b128.  Whatever is a pure function of the read is worked
+// out once here, by the prologue lane that writes the record, and not once per item.
+// Two shapes of the second half.  The general one: (w0, w1) = the 64-bit address of the 2-bit plane word that holds the
+// read's first source base, `sd` unused.  The slot layout over one cached genome (SLOT && CACHED, the default step): the
+// plane's base is the same for every read (a scalar), so
+//   w0 = byte offset of that plane word from the plane's base (32 bits: engine.hip keeps longer planes off this form)
+//   w1 = where item 0's sixteen bases go, relative to the block's first output byte: dst for a forward read, the last
+//        16 bytes of the slot for a reverse mate (right-aligned: its items run backwards through the slot)
+//   sd = +16 forward, -16 reverse: item ci's bases go to w1 + ci * sd (one v_mad_i32_i24); bit 10 of it (clear in +16,
+//        set in -16) also picks the row of reverse byte masks, 1024 bytes behind the forward one
 struct alignas(16) PhRec {
   uint32_t k0, k1;  // Philox key = the read's Phred seed
   uint32_t dst;     // first output byte of the read, relative to the block's first output byte
-  uint32_t lw;      // L | (2 * (source position & 15)) << 16 | rev << 31   (L <= 65535: u16 lengths)
-  uint64_t wa;      // address of the 2-bit plane word that holds the read's first source base
+  uint32_t lw;      // 2 * (source position & 15) | L << 5 | rev << 31   (L <= 65535: u16 lengths).  The funnel shift
+                    // takes the low five bits as they are (v_alignbit_b32 ignores the rest), lw & PHREC_L32 = 32 L
+  uint32_t w0, w1;
   uint32_t gs;      // first item of the read among the block's items
-  uint32_t pad;
+  uint32_t sd;
 };
+#define PHREC_L32 0x1fffe0u
 
 // One base: R holds the 24-bit draw F in its upper 24 bits (the low byte is whatever the bit string has there).
 // Level-1 LDS entry of column c = F >> 14 (T 16384ths answer A, the rest B; results r = enc(q) << 8 | esc << 2 | s):
@@ -1869,8 +1880,9 @@ SIMMR_DEV uint32_t philox_pick(uint32_t R, const uint2* __restrict__ jtab) {
 // from the residual law (counter (b >> 2, 1), word b & 3).  A loop, not unrolled: it must not cost the item loop
 // registers.  t1 = the level-1 table as uploaded (T | A << 16, then B), t2 = the level-2 table.
 SIMMR_DEV void philox_repair(const uint32_t k0, const uint32_t k1, const uint32_t ci, const uint32_t* __restrict__ t1,
-                             const uint32_t* __restrict__ t2, const uint32_t qoff, uint32_t& ss, uint32_t qr[4]) {
-  ss = 0u;
+                             const uint32_t* __restrict__ t2, const uint32_t qoff, uint32_t& ss_out, uint32_t qr_out[4]) {
+  // (results of its own, handed over at the end: the item's first answers then do not live through this loop)
+  uint32_t ss = 0u, qr[4] = {0u, 0u, 0u, 0u};
 #pragma nounroll
   for (uint32_t g4 = 0; g4 < 4u; g4++) {
     // words 3 g4 .. 3 g4 + 2 of the group's twelve: calls (3 g4) >> 2 and (3 g4 + 2) >> 2
@@ -1903,6 +1915,8 @@ SIMMR_DEV void philox_repair(const uint32_t k0, const uint32_t k1, const uint32_
     if (g4 == 2u) qr[2] = q4;
     if (g4 == 3u) qr[3] = q4;
   }
+  ss_out = ss;
+  qr_out[0] = qr[0]; qr_out[1] = qr[1]; qr_out[2] = qr[2]; qr_out[3] = qr[3];
 }
 
 // COPY_ONLY: the same item machinery without the draws: bases of the planned reads (mate 2 reverse-complemented)
@@ -1973,8 +1987,11 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
   uint8_t* const owner = TEXT ? fq_slots : owner_static;
   __shared__ uint64_t cbase[CACHED ? PHILOX_CBASE : 1];
   // byte masks (0xff) of the first n bytes of 16; SLOT: a second row at +32 with the LAST n bytes (a reverse mate's live bytes)
-  __shared__ uint4 nmask[SLOT ? 64 : 17];
-  __shared__ uint32_t nmask2[17]; // the low 2n bits
+  // FAST (the slot layout over one cached genome): one table of 32-byte rows, row n = the byte masks of n and, in its
+  // fifth word, the low 2n bits (both from one address, 32 n); the LAST-n-bytes masks 1024 bytes further (PhRec::sd)
+  constexpr bool FAST = SLOT && CACHED;
+  __shared__ uint4 nmask[FAST ? 98 : (SLOT ? 64 : 17)];
+  __shared__ uint32_t nmask2[FAST ? 1 : 17]; // the low 2n bits
   __shared__ uint32_t lds4[4];
   __shared__ uint64_t lds4w[COARSE ? 4 : 1];  // (TEXT too)
   const uint32_t qoff = qual_offset & 0xffu;
@@ -2000,12 +2017,19 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       auto bytes = [](int k) { return k >= 4 ? 0xffffffffu : (k <= 0 ? 0u : ((1u << (8 * k)) - 1u)); };
       // (v_dot4_u32_u8 against them sums the live quality bytes 255-fold in one instruction per word: qsum is divided once,
       // at the end; and the same masks zero the padding of the slot layout with a plain `and`, no multiply)
-      nmask[t] = make_uint4(bytes((int)t), bytes((int)t - 4), bytes((int)t - 8), bytes((int)t - 12));
-      if (SLOT) {
-        const int d = 16 - (int)t;  // the low d bytes are padding
-        nmask[32u + t] = make_uint4(~bytes(d), ~bytes(d - 4), ~bytes(d - 8), ~bytes(d - 12));
+      const uint4 first_n = make_uint4(bytes((int)t), bytes((int)t - 4), bytes((int)t - 8), bytes((int)t - 12));
+      const int d = 16 - (int)t;  // SLOT, reverse mate: the low d bytes are padding
+      const uint4 last_n = make_uint4(~bytes(d), ~bytes(d - 4), ~bytes(d - 8), ~bytes(d - 12));
+      const uint32_t low_2n = t >= 16u ? 0xffffffffu : ((1u << (2u * t)) - 1u);
+      if (FAST) {
+        nmask[2u * t] = first_n;
+        nmask[2u * t + 1u] = make_uint4(low_2n, 0u, 0u, 0u);
+        nmask[64u + 2u * t] = last_n;
+      } else {
+        nmask[t] = first_n;
+        if (SLOT) nmask[32u + t] = last_n;
+        nmask2[t] = low_2n;
       }
-      nmask2[t] = t >= 16u ? 0xffffffffu : ((1u << (2u * t)) - 1u);
     }
     const uint32_t acgt = 0x54474341u;  // "ACGT"
     asc[t] = ((acgt >> (8 * (t & 3u))) & 0xffu) | (((acgt >> (8 * ((t >> 2) & 3u))) & 0xffu) << 8) |
@@ -2023,6 +2047,9 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
   }
   const uint4* rec4 = reinterpret_cast<const uint4*>(recs);
   uint64_t qsum = 0;  // adds encoded qualities; the offset is taken off at the end (every base is drawn exactly once: p_bases)
+  // ... gathered block by block in 32 bits: an item adds at most 16 * 255 * 255 = 1 040 400, and a lane sees at most
+  // 4096 items of a block (256 reads of at most 65 535 bases are 4096 items each, dealt to 256 lanes): 4 261 478 400 < 2^32
+  uint32_t qsum_blk = 0;
   uint32_t n_subst = 0, n_acgt = 0;
   // Plan-derived counters, gathered while the read records are written — kept out of the vector registers the item loop
   // needs: the flag counts are ballots (wave-uniform: scalar registers), the bases of this thread's reads a 32-bit sum
@@ -2114,9 +2141,17 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       PhRec rc;
       rc.k0 = (uint32_t)key; rc.k1 = (uint32_t)(key >> 32);
       rc.dst = (uint32_t)(dst - out0);
-      rc.lw = (L & 0xffffu) | ((2u * (uint32_t)(src & 15u)) << 16) | (rev << 31);
-      rc.wa = (uint64_t)(uintptr_t)(packed + (src >> 4));
-      rc.gs = 0; rc.pad = 0;
+      rc.lw = (2u * (uint32_t)(src & 15u)) | ((L & 0xffffu) << 5) | (rev << 31);
+      if (FAST) {
+        rc.w0 = 4u * (uint32_t)(src >> 4);
+        rc.w1 = 0;  // (after the scan below)
+        rc.sd = rev ? (uint32_t)-16 : 16u;
+      } else {
+        const uint64_t wa = (uint64_t)(uintptr_t)(packed + (src >> 4));
+        rc.w0 = (uint32_t)wa; rc.w1 = (uint32_t)(wa >> 32);
+        rc.sd = 0;
+      }
+      rc.gs = 0;
       recs[t] = rc;
       if (HAS_EXC) { x_src[t] = src; x_mask[t] = mk; }
       if (FULL) {
@@ -2205,6 +2240,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       if (my_rd + 1 == n_reads) o.seq_off[n_reads] = coarse ? off64[(n_units + 63u) >> 6] : u_off[n_units];  // closing CSR offset
     }
     if (tix < nr) recs[tix].gs = ex;
+    if (FAST && tix < nr) recs[tix].w1 = (uint32_t)(my_dst - out0) + ((paired && (tix & 1u)) ? my_Lp - 16u : 0u);  // (a read without bases has no item)
     r_gs[tix] = tix < nr ? ex : 0xffffffffu;
     if (tix == 0) r_gs[PHILOX_READS] = 0xffffffffu;
     // short reads: every read writes its index over its items, so an item finds its read with one LDS load
@@ -2242,8 +2278,10 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       return r;
     };
     // the plane word of an item: two 32-bit words at the read's word address + 4 * (item's group)
+    // (FAST: the plane's scalar base + a 32-bit lane offset, as the stores are addressed)
     auto plane_word = [&](const uint32_t it, const uint32_t r) -> uint64_t {
       const uint4 rb = rec4[2 * r + 1];
+      if (FAST) return *(global_u64_unaligned_ptr)((const __attribute__((address_space(1))) char*)packed0 + (rb.x + 4u * (it - rb.z)));
       const uint64_t wa = ((uint64_t)rb.x | ((uint64_t)rb.y << 32)) + 4ull * (it - rb.z);
       return *reinterpret_cast<global_u64_unaligned_ptr>(wa);
     };
@@ -2254,17 +2292,25 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
     uint32_t r_next = 0;
     uint64_t raw_next = 0;
     if (prefetch && threadIdx.x < i_end) { r_next = locate(threadIdx.x); raw_next = plane_word(threadIdx.x, r_next); }
+    // (-512 as a value the compiler cannot see through: ci * -512 + 32 L then stays one v_mad_i32_i24, not shift and subtract)
+    int m512 = -512;
+    asm("" : "+s"(m512));
     for (uint32_t item = threadIdx.x; item < i_end; item += 256u) {
       const uint32_t r = prefetch ? r_next : locate(item);
       const uint64_t raw = prefetch ? raw_next : plane_word(item, r);
       const uint4 ra = rec4[2 * r], rb = rec4[2 * r + 1];
       const uint32_t k0 = ra.x, k1 = ra.y, lw = ra.w;
-      const uint32_t L = lw & 0xffffu, rev = lw >> 31;
-      const uint32_t ci = item - rb.z;
+      const uint32_t L = (lw >> 5) & 0xffffu, rev = lw >> 31;
+      uint32_t ci = item - rb.z;
+      // (the item's number in its read as a value of its own: what the rare paths below need of it — the repair's
+      // counters, the wrap count's bounds — is then made there, not kept up item by item as functions of `item`)
+      asm("" : "+v"(ci));
       const uint32_t b0 = ci << 4;
-      const uint32_t n = (L - b0) < 16u ? (L - b0) : 16u;
+      // FAST: 32 n straight from the record (lw & PHREC_L32 = 32 L, ci < 2^12): it is the address of the item's masks
+      const uint32_t n32 = FAST ? min((uint32_t)__mul24((int)ci, m512) + (lw & PHREC_L32), 512u) : 0u;
+      const uint32_t n = FAST ? (n32 >> 5) : ((L - b0) < 16u ? (L - b0) : 16u);
       // the 16 source bases: 32 bits at bit offset 2 * (source position & 15) of two plane words
-      uint32_t codes = (uint32_t)(raw >> ((lw >> 16) & 31u));
+      uint32_t codes = __builtin_amdgcn_alignbit((uint32_t)(raw >> 32), (uint32_t)raw, lw);  // (the low five bits of lw)
       uint32_t exc = 0u;
       if (HAS_EXC) { const uint32_t* mk = x_mask[r]; if (mk) exc = fetch_mask16(mk, (int64_t)(x_src[r] + b0)); }
       // per base: 24 bits -> (Phred, substitution shift s); qualities packed as bytes, s as 2-bit fields
@@ -2300,8 +2346,8 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       }
       // only live ACGT bases mutate (minimal_short.rs:120-128)
       // masks of the n live bases of the item: byte masks for the four quality words, 2-bit-field mask
-      const uint4 bm = nmask[n];
-      const uint32_t live2 = nmask2[n];
+      const uint4 bm = FAST ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(nmask) + n32) : nmask[n];
+      const uint32_t live2 = FAST ? *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(nmask) + n32 + 16u) : nmask2[n];
       if (HAS_EXC) ss &= ~spread16(exc);
       ss &= live2;
       n_subst += __builtin_popcount((ss | (ss >> 1)) & 0x55555555u);
@@ -2309,11 +2355,11 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       if (HAS_EXC) n_acgt += __builtin_popcount(~spread16(exc) & live2 & 0x55555555u);
       else if (COPY_ONLY && !TEXT) n_acgt += n;
       if (!COPY_ONLY) {
-        uint32_t qs = __builtin_amdgcn_udot4(qr[0], bm.x, 0u, false);
-        qs = __builtin_amdgcn_udot4(qr[1], bm.y, qs, false);
-        qs = __builtin_amdgcn_udot4(qr[2], bm.z, qs, false);
-        qs = __builtin_amdgcn_udot4(qr[3], bm.w, qs, false);
-        qsum += qs;  // 255 x the sum of the live bytes (<= 16 * 255 * 255 per item)
+        // 255 x the sum of the live bytes (<= 16 * 255 * 255 per item), on top of the block's sum so far
+        qsum_blk = __builtin_amdgcn_udot4(qr[0], bm.x, qsum_blk, false);
+        qsum_blk = __builtin_amdgcn_udot4(qr[1], bm.y, qsum_blk, false);
+        qsum_blk = __builtin_amdgcn_udot4(qr[2], bm.z, qsum_blk, false);
+        qsum_blk = __builtin_amdgcn_udot4(qr[3], bm.w, qsum_blk, false);
       }
       if (!COPY_ONLY && !q_nowrap) {
         uint32_t nw = 0;
@@ -2324,15 +2370,18 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
       // (two-bit addition without the field masks: the low bits add as xor, their carry = and goes into the high bit;
       // v_bitop3_b32 takes three inputs, so this is and-and, shift, xor-xor: three instructions for nine)
       codes = xor3(codes, ss, __builtin_amdgcn_bitop3_b32(codes, ss, 0x55555555u, 0x80) << 1);
-      uint32_t o_s = ra.z + b0;
-      const uint32_t o_q = TEXT ? o_s + L + 3u : o_s;  // (TEXT: the qualities' line follows the bases' line and "+\n")
+      // FAST: both places from the record (PhRec), whichever way the read runs
+      uint32_t o_s = FAST ? rb.y + (uint32_t)__mul24((int)ci, (int)rb.w) : ra.z + b0;
+      const uint32_t o_q = TEXT ? o_s + L + 3u : ra.z + b0;  // (TEXT: the qualities' line follows the bases' line and "+\n")
       if (rev) {
         // mate 2 is reverse-complemented after mutation (simulate.rs:283), still in the code domain:
         // base b0+j -> byte L-1-(b0+j); the 16-n dead groups fall off the low end
         codes = reverse_complement_groups16(codes);
         if (HAS_EXC) { exc = __builtin_bitreverse32(exc) >> 16; codes ^= spread16(exc); }
         const uint32_t dead = 16u - n;
-        if (SLOT) {
+        if (FAST) {
+          // (right-aligned by the record)
+        } else if (SLOT) {
           // right-aligned: the group's 16 bytes end at slot byte Lp - b0, the dead groups stay at the low end (zeroed below)
           o_s = ra.z + (((L + 15u) & ~15u) - b0 - 16u);
         } else {
@@ -2351,7 +2400,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
         // padding bytes are 0: the qualities' and a forward read's bases' high 16 - n bytes, a reverse mate's low ones
         // (every item, without a branch: the masks of n = 16 are all ones)
         qr[0] &= bm.x; qr[1] &= bm.y; qr[2] &= bm.z; qr[3] &= bm.w;
-        const uint4 sm = nmask[(rev << 5) + n];
+        const uint4 sm = FAST ? *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(nmask) + ((rb.w & 1024u) | n32)) : nmask[(rev << 5) + n];
         s0 &= sm.x; s1 &= sm.y; s2 &= sm.z; s3 &= sm.w;
       }
       // qualities are already offset-encoded, forward order
@@ -2374,6 +2423,7 @@ k_emit_philox(ProfileDev prof, uint32_t paired, const GenomeDev* __restrict__ ge
         store_tail(sd, s_lo, s_hi, n);
       }
     }
+    qsum += qsum_blk; qsum_blk = 0u;
   }
   // sum of the raw Phred values (per lane modulo 2^64: a lane that wrote records but drew few bases goes "negative";
   // the sum over the lanes is exact)
