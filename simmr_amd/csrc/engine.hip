@@ -17,6 +17,7 @@
 #include <map>
 #include <random>
 #include <string>
+#include <type_traits>
 #include <mutex>
 #include <vector>
 
@@ -80,6 +81,21 @@ struct PlanState {
   bool sorted = false;    // u_order holds a processing order (sort_by_length)
 };
 
+enum FqKind { FQPLAN_NONE = 0, FQPLAN_COLUMNS = 1, FQPLAN_DIRECT = 2 };
+
+// The FASTQ plan in force, kept like the plan: a FASTQ plan call starts with FqState{} (none) and commits a fully built
+// value in fq_finish.  FQPLAN_COLUMNS (simmr_fastq_plan) describes the caller's columns and outlives the engine's plan;
+// FQPLAN_DIRECT (simmr_fastq_plan_direct) was sized from the engine's plan and goes with it (plan_reset).
+struct FqState {
+  int kind = FQPLAN_NONE;
+  uint64_t reads = 0, total = 0;
+  uint32_t slots = 0, lit_bytes = 0, hpitch = 272;
+  uint32_t maxhdr = 0, read_id_base = 0;
+  bool paired = false;
+  bool coarse = false;  // a direct plan with fq_off64 (first byte of every 64th record) instead of fq_off
+  FqTemplate tpl{};     // host copy of the compiled header template (fq_tpl_dev holds the kernels' copy)
+};
+
 }  // namespace
 
 // which form simmr_emit_fastq runs when SIMMR_TEXT_FORM does not say: the one that measures faster (LAB.md, round 5)
@@ -106,7 +122,6 @@ struct simmr_engine {
   PlanState plan;           // current plan
   uint32_t read_slots = 0;  // simmr_engine_set_read_slots: the layout of the plans to come (0 compact, 16 SIMMR_SLOT16)
   DevBuf w_bytes, u_off64, fq_off64;
-  bool fq_coarse = false;  // the direct FASTQ plan in force has fq_off64 (first byte of every 64th record) instead of fq_off
   DevBuf m_genomes, m_contig, m_seed;
   DevBuf u_contig, u_genome, u_seed, u_len, u_a, u_b, u_qs2, u_ms2, u_flags, u_off;
   DevBuf scan_tmp, u_order, len_hist;
@@ -146,12 +161,7 @@ struct simmr_engine {
   ProfileDev custom_prof{};
   // FASTQ framing
   DevBuf fq_blob, fq_gid_off, fq_gid_len, fq_cbase, fq_ncontig, fq_coff, fq_clen, fq_len, fq_off;
-  FqTemplate fq_tpl{};
-  uint64_t fq_reads = 0, fq_total = 0;
-  uint32_t fq_slots = 0, fq_lit_bytes = 0, fq_hpitch = 272;
-  bool fq_paired = false, fq_ready = false;
-  bool fq_direct = false;          // planned by simmr_fastq_plan_direct (sizes from the plan, for simmr_emit_fastq)
-  uint32_t fq_read_id_base = 0, fq_maxhdr = 0;
+  FqState fq;                      // current FASTQ plan
   DevBuf fq_hlen;                  // header bytes per read (direct form)
   DevBuf fq_tpl_dev;               // the compiled header template, read by the kernels through a pointer
   DevBuf fd_seq, fd_qual, fd_seq_off, fd_start, fd_end, fd_contig, fd_genome, fd_read_id, fd_flags;  // columns of the unfused fallback
@@ -913,6 +923,16 @@ static hipError_t grant_dynamic_lds(const simmr_engine* e, Kernel fn, uint32_t b
   return s;
 }
 
+// Run-time bools as template arguments: with_bools(f, a, b) is f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a
+// selector names its kernel once, `k<x, true, c>`, and instantiates exactly the combinations of the bools it passes.
+template <class F>
+static auto with_bools(F f) { return f(); }
+template <class F, class... Bools>
+static auto with_bools(F f, bool b, Bools... rest) {
+  return b ? with_bools([f](auto... cs) { return f(std::true_type{}, cs...); }, rest...)
+           : with_bools([f](auto... cs) { return f(std::false_type{}, cs...); }, rest...);
+}
+
 // Traits of a launch of the item kernels (k_emit_philox, k_emit_text_lines) over the engine's current plan.  `exc` alone
 // also serves the custom long-read and lane-per-read kernels.
 struct ItemLaunch {
@@ -945,23 +965,16 @@ static bool philox_escq(const simmr_engine* e, uint32_t offset) { return offset 
 // mean Phred far above what the profiles of the reference use) exists in its most general shape only — with the
 // exception plane, without the contig cache — which serves every plan.  16 instantiations (tests/test_resource_guard.py).
 using PhiloxKernel = decltype(&k_emit_philox<false, false, false, false, false, false, false>);
-template <bool EXC, bool CACHED, bool ESCQ, bool COARSE>
-static PhiloxKernel philox_kernel2(bool slot) {
-  return slot ? k_emit_philox<EXC, false, CACHED, false, ESCQ, true, COARSE> : k_emit_philox<EXC, false, CACHED, false, ESCQ, false, COARSE>;
-}
 static PhiloxKernel philox_kernel(bool exc, bool cached, bool escq, bool slot, bool coarse) {
-  if (!escq) return coarse ? philox_kernel2<true, false, false, true>(slot) : philox_kernel2<true, false, false, false>(slot);
-  if (!coarse) return exc ? philox_kernel2<true, false, true, false>(slot) : philox_kernel2<false, false, true, false>(slot);
-  if (exc) return cached ? philox_kernel2<true, true, true, true>(slot) : philox_kernel2<true, false, true, true>(slot);
-  return cached ? philox_kernel2<false, true, true, true>(slot) : philox_kernel2<false, false, true, true>(slot);
+  if (!escq) return with_bools([](auto s, auto co) -> PhiloxKernel { return k_emit_philox<true, false, false, false, false, s, co>; }, slot, coarse);
+  if (!coarse) return with_bools([](auto x, auto s) -> PhiloxKernel { return k_emit_philox<x, false, false, false, true, s, false>; }, exc, slot);
+  return with_bools([](auto x, auto c, auto s) -> PhiloxKernel { return k_emit_philox<x, false, c, false, true, s, true>; }, exc, cached, slot);
 }
 // the same for the TEXT form (simmr_emit_fastq): always coarse; `copy_only` = perfect-short (no draws)
 static PhiloxKernel philox_text_kernel(bool exc, bool cached, bool escq, bool copy_only) {
-  if (copy_only) return cached ? (exc ? k_emit_philox<true, true, true, true, false, false, true> : k_emit_philox<false, true, true, true, false, false, true>)
-                               : (exc ? k_emit_philox<true, true, false, true, false, false, true> : k_emit_philox<false, true, false, true, false, false, true>);
+  if (copy_only) return with_bools([](auto x, auto c) -> PhiloxKernel { return k_emit_philox<x, true, c, true, false, false, true>; }, exc, cached);
   if (!escq) return k_emit_philox<true, false, false, true, false, false, true>;
-  return cached ? (exc ? k_emit_philox<true, false, true, true, true, false, true> : k_emit_philox<false, false, true, true, true, false, true>)
-                : (exc ? k_emit_philox<true, false, false, true, true, false, true> : k_emit_philox<false, false, false, true, true, false, true>);
+  return with_bools([](auto x, auto c) -> PhiloxKernel { return k_emit_philox<x, false, c, true, true, false, true>; }, exc, cached);
 }
 
 // What differs between the three forms of a k_emit_philox launch: the columns, the copy-only half of custom-short, the
@@ -1007,17 +1020,22 @@ static const char* custom_long_tables_missing(const ProfileDev& prof, bool fast,
 // the whole-line form (text_lines.hip)
 using TextLinesKernel = decltype(&k_emit_text_lines<false, false, false, false>);
 static TextLinesKernel text_lines_kernel(bool exc, bool cached, bool escq, bool copy_only) {
-  if (copy_only) return cached ? (exc ? k_emit_text_lines<true, true, true, false> : k_emit_text_lines<false, true, true, false>)
-                               : (exc ? k_emit_text_lines<true, true, false, false> : k_emit_text_lines<false, true, false, false>);
+  if (copy_only) return with_bools([](auto x, auto c) -> TextLinesKernel { return k_emit_text_lines<x, true, c, false>; }, exc, cached);
   if (!escq) return k_emit_text_lines<true, false, false, false>;
-  return cached ? (exc ? k_emit_text_lines<true, false, true, true> : k_emit_text_lines<false, false, true, true>)
-                : (exc ? k_emit_text_lines<true, false, false, true> : k_emit_text_lines<false, false, false, true>);
+  return with_bools([](auto x, auto c) -> TextLinesKernel { return k_emit_text_lines<x, false, c, true>; }, exc, cached);
 }
 // bytes of a header slot of that kernel: the header at any offset below 8, its '\n', what FqW may write past its bytes; a multiple of 8 and an odd number of 8-byte words (the lanes of a wave then start on different banks)
 static uint32_t tl_slot_pitch(uint32_t max_header) {
   uint32_t w = (7u + max_header + 1u + 12u + 7u) / 8u;  // (a piece of fq_put8 writes three whole words: up to ten bytes past the header's end)
   if (!(w & 1u)) w++;
   return 8u * w;
+}
+
+// a measurement knob of simmr_engine_create: the environment variable `name`, where set, clamped to 1..max
+static bool env_clamped(const char* name, unsigned long long max, uint32_t* knob) {
+  const char* v = getenv(name);
+  if (v) *knob = (uint32_t)std::min(max, std::max(1ull, strtoull(v, nullptr, 10)));
+  return v != nullptr;
 }
 
 }  // namespace
@@ -1064,13 +1082,11 @@ int simmr_engine_create(int device_ordinal, simmr_engine** out) {
   e->n_cu = prop.multiProcessorCount;
   // Four measurement knobs (grid multiples, workgroups per CU, the splice variant) + SIMMR_TEXT_FORM (which kernel writes the
   // FASTQ text: same-box A/B) + SIMMR_FAULT_INJECT (test switch), read once here; the defaults are what the sweeps of LAB.md found.
-  if (const char* v = getenv("SIMMR_GRID_MULT"))
-    e->lanes_mult = e->perfect_mult = e->custom_pe_mult = e->custom_long_mult = e->fastq_mult =
-        (uint32_t)std::min<unsigned long long>(512, std::max<unsigned long long>(1, strtoull(v, nullptr, 10)));
-  if (const char* v = getenv("SIMMR_FASTQ_GRID_MULT")) e->fastq_mult = (uint32_t)std::min<unsigned long long>(512, std::max<unsigned long long>(1, strtoull(v, nullptr, 10)));
+  if (env_clamped("SIMMR_GRID_MULT", 512, &e->fastq_mult)) e->lanes_mult = e->perfect_mult = e->custom_pe_mult = e->custom_long_mult = e->fastq_mult;
+  env_clamped("SIMMR_FASTQ_GRID_MULT", 512, &e->fastq_mult);
+  env_clamped("SIMMR_PHILOX_WGS_PER_CU", 4096, &e->philox_wgs_per_cu);
   if (const char* v = getenv("SIMMR_TEXT_FORM")) e->text_form = atoi(v);
   if (const char* v = getenv("SIMMR_FAULT_INJECT")) e->inject_null_ctr_tables = strcmp(v, "null_ctr_tables") == 0;
-  if (const char* v = getenv("SIMMR_PHILOX_WGS_PER_CU")) e->philox_wgs_per_cu = (uint32_t)std::min<unsigned long long>(4096, std::max<unsigned long long>(1, strtoull(v, nullptr, 10)));
   if (const char* v = getenv("SIMMR_SPLICE_VARIANT")) e->splice_variant = atoi(v);
   bool ok = e->d_tables.ensure(sizeof(Tables)) && e->d_counters.ensure(8 * SIMMR_N_COUNTERS * (1 + SIMMR_CNT_SHARDS)) &&
             e->d_err.ensure(64) && e->d_scalars.ensure(256);
@@ -1483,7 +1499,7 @@ int simmr_pe_plan_at(simmr_engine* e, uint32_t genome_idx, const simmr_error_pro
 // and asks plan_begin for the device form of the profile and the layout.
 static int plan_reset(simmr_engine* e) {
   e->plan = PlanState{};
-  e->fq_direct = false;  // (a direct FASTQ plan belongs to the plan it was made for)
+  if (e->fq.kind == FQPLAN_DIRECT) e->fq = FqState{};  // (a direct FASTQ plan belongs to the plan it was made for)
   HIP_TRY(e, hipSetDevice(e->device));
   return SIMMR_OK;
 }
@@ -1691,132 +1707,146 @@ int simmr_pe_plan_multi(simmr_engine* e, uint32_t n_genomes, const uint32_t* gen
   return plan_finish(e, p, "a sequence is smaller than the required length", seed, end_slot, 0u, info);
 }
 
-static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads_out* out) {
-  const uint64_t n_units = e->plan.units;
+// ---- the emit calls ----
+// What an emit over the plan in force starts from; built once per call (emit_common, simmr_emit_fastq, fq_plan_view).
+struct EmitCtx {
+  bool paired;
+  uint64_t n_units, n_reads;
+  PlanArrays pl;             // (the seeds of mate 2 only where the plan made them: pairs other than perfect-short)
+  const uint32_t* u_genome;  // the genome of every unit; null for pairs of one genome (plan.genome)
+  unsigned long long* counters;
+  ItemLaunch il;
+};
+static EmitCtx emit_ctx(simmr_engine* e) {
   const bool paired = e->plan.paired;
-  const uint64_t n_reads = paired ? 2 * n_units : n_units;
-  int rc = check_out(e, out, n_reads, e->plan.total_bases);
+  const uint64_t n_units = e->plan.units;
+  return EmitCtx{paired, n_units, paired ? 2 * n_units : n_units, plan_arrays(e, paired && e->plan.prof.kind != SIMMR_K_PERFECT_SHORT),
+                 (paired && !e->plan.multi) ? nullptr : e->u_genome.as<uint32_t>(), e->d_counters.as<unsigned long long>(), item_launch(e)};
+}
+
+// One launcher per kernel family: what emit_common puts on the stream between its two events.
+static void launch_perfect_short(simmr_engine* e, const EmitCtx& c, const simmr_reads_out* out, uint32_t read_id_base) {
+  const uint64_t groups = (c.n_reads + PERFECT_GROUP - 1) / PERFECT_GROUP;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(groups, (uint64_t)e->n_cu * 8 * e->perfect_mult);
+  auto kern = e->plan.multi ? k_emit_perfect_pe<true> : k_emit_perfect_pe<false>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(), e->plan.genome, c.u_genome,
+                     e->plan.any_exc ? 1u : 0u, c.n_units, e->plan.prof.read_length, c.pl, e->u_contig.as<uint32_t>(), out->seq,
+                     out->qual, 60u + out->qual_offset, e->plan.first, read_id_base, out_cols(out), c.counters);
+}
+
+// the item kernel, column form (counter mode of the built-in profiles)
+static void launch_item_columns(simmr_engine* e, const EmitCtx& c, const simmr_reads_out* out, uint32_t read_id_base) {
+  const bool escq = philox_escq(e, out->qual_offset & 0xffu);
+  const bool coarse = c.paired && e->plan.coarse;
+  PhiloxForm f{c.u_genome, out->seq, out->qual, out->qual_offset, read_id_base, out_cols(out)};
+  if (coarse) f.off64 = e->u_off64.as<uint64_t>();
+  launch_philox(e, philox_kernel(c.il.exc, c.il.cached, escq, e->plan.slot != 0, coarse), c.il.grid, 0, c.pl, f);
+}
+
+using SpliceKernel = decltype(&k_custom_long_splice<false, false, false>);
+static void launch_splice(simmr_engine* e, const EmitCtx& c, const simmr_reads_out* out, const uint32_t* order, SpliceKernel kern,
+                          uint32_t grid, uint32_t lanes, uint32_t lds) {
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(lanes), lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), c.n_units, order,
+                     c.pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
+                     e->u_seed.as<uint64_t>(), out->seq, c.counters, e->d_err.as<uint32_t>());
+}
+// a custom model's long reads: qualities (k_custom_long_qual), then bases (one of the three shapes of k_custom_long_splice)
+static int launch_custom_long(simmr_engine* e, const EmitCtx& c, const simmr_reads_out* out, uint32_t /*read_id_base*/) {
+  const ProfileDev& prof = e->plan.prof;
+  const bool ctr = prof.rng_mode != SIMMR_RNG_REFERENCE;
+  const bool fast = prof.custom.kmer_stride != 0 && e->splice_variant != 1;  // (1: the two-load kernel, A/B timing)
+  if (const char* missing = custom_long_tables_missing(prof, fast, ctr))
+    return e->fail(SIMMR_EINVAL, "custom long-read emit refused: device table `%s` of the model is not set for rng_mode %u "
+                                 "(nothing was launched)", missing, prof.rng_mode);
+  HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
+  const uint64_t blocks = (c.n_reads + 255) / 256;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
+  const uint32_t* order = e->plan.sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr;
+  hipLaunchKernelGGL(k_custom_long_qual, dim3(grid), dim3(256), 0, e->stream, prof, c.n_units, order, c.pl,
+                     e->u_off.as<uint64_t>(), e->u_seed.as<uint64_t>(), out->qual, out->qual_offset, c.counters,
+                     e->d_err.as<uint32_t>());
+  const SpliceKernel kern = with_bools([](auto x, auto f, auto t) -> SpliceKernel { return k_custom_long_splice<x, f, t>; }, c.il.exc, fast, ctr);
+  if (ctr) {
+    // the counter mode of the splice (kernels.hip section 9c, CTR): the LDS holds one word per k-mer (4^k words);
+    // with k = 7 (64 KB) two workgroups of 768 lanes share a CU — six waves per SIMD, what the kernel's registers allow —
+    // with smaller tables 256-lane workgroups do
+    const uint32_t tab = fast ? splice_ctr_lds_bytes(prof.custom.kmer_size) : 0u;
+    const uint32_t lanes = tab > 16384u ? SPLICE_CTR_LANES_MAX : 256u;
+    const uint32_t lds = fast ? tab + 16u * lanes : 0u;  // the k-mer table + 16 bytes per lane (an even group waiting for its odd neighbour's store)
+    if (lds > 32768u) HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (64 KB of table + the kernel's static LDS: over the default limit)
+    // (many more workgroups than are resident: reads come longest first, and the tail of the launch is short ones)
+    const uint32_t cgrid = (uint32_t)std::min<uint64_t>((c.n_reads + lanes - 1) / lanes, (uint64_t)e->n_cu * 64 * e->custom_long_mult);
+    launch_splice(e, c, out, order, kern, cgrid, lanes, lds);
+  } else if (fast) {
+    // one workgroup of 1024 lanes per CU around the LDS count table (kernels.hip section 9c)
+    const uint32_t lds = splice_fast_lds_bytes(prof.custom.kmer_size);
+    HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (grows with the model's k: 132 KB + 4^k)
+    const uint32_t fgrid = (uint32_t)std::min<uint64_t>((c.n_reads + SPLICE_FAST_LANES - 1) / SPLICE_FAST_LANES, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
+    launch_splice(e, c, out, order, kern, fgrid, SPLICE_FAST_LANES, lds);
+  } else {
+    launch_splice(e, c, out, order, kern, grid, 256u, 0u);
+  }
+  return SIMMR_OK;
+}
+
+// a custom model's pairs.  Qualities: one lane per pair (k_emit_custom_pe); bases: the item kernel without draws (coalesced stores)
+static int launch_custom_pe(simmr_engine* e, const EmitCtx& c, const simmr_reads_out* out, uint32_t read_id_base) {
+  HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
+  const uint64_t blocks = (c.n_units + 255) / 256;  // one lane per pair
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * 8 * e->custom_pe_mult);
+  hipLaunchKernelGGL(k_emit_custom_pe, dim3(grid), dim3(256), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
+                     e->plan.genome, c.n_units, c.pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(),
+                     e->u_seed.as<uint64_t>(), out->seq, out->qual, out->qual_offset, c.counters, e->d_err.as<uint32_t>());
+  // (its plain form whatever the plan: per-pair offsets, no contig cache, no genome column)
+  launch_philox(e, c.il.exc ? k_emit_philox<true, true, false> : k_emit_philox<false, true, false>, c.il.grid, 0, c.pl,
+                PhiloxForm{nullptr, out->seq, out->qual, out->qual_offset, read_id_base, out_cols(out)});
+  return SIMMR_OK;
+}
+
+// lane-per-read kernel: template on (exception plane present, paired, perfect-long Phred)
+static void launch_lanes(simmr_engine* e, const EmitCtx& c, const simmr_reads_out* out, uint32_t /*read_id_base*/) {
+  using LanesKernel = decltype(&k_emit_lanes<false, false, false>);
+  const bool pl_kind = e->plan.prof.kind == SIMMR_K_PERFECT_LONG;
+  const LanesKernel kern = c.paired ? with_bools([](auto x) -> LanesKernel { return k_emit_lanes<x, true, false>; }, c.il.exc)
+                                    : with_bools([](auto x, auto p) -> LanesKernel { return k_emit_lanes<x, false, p>; }, c.il.exc, pl_kind);
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, LANES_WG, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+  const uint64_t wgs = (c.n_reads + LANES_WG - 1) / LANES_WG;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)e->n_cu * (uint64_t)per_cu * e->lanes_mult);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(LANES_WG), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
+                     e->plan.genome, c.n_units, e->plan.sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr,
+                     c.pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), c.u_genome, e->u_seed.as<uint64_t>(),
+                     out->seq, out->qual, out->qual_offset, e->d_tables.as<Tables>(), c.counters);
+}
+
+static int emit_common(simmr_engine* e, uint32_t read_id_base, const simmr_reads_out* out) {
+  const EmitCtx c = emit_ctx(e);
+  const ProfileDev& prof = e->plan.prof;
+  int rc = check_out(e, out, c.n_reads, e->plan.total_bases);
   if (rc) return rc;
-  const bool seeds2 = paired && e->plan.prof.kind != SIMMR_K_PERFECT_SHORT;
-  PlanArrays pl = plan_arrays(e, seeds2);
-  const uint32_t* u_genome = (paired && !e->plan.multi) ? nullptr : e->u_genome.as<uint32_t>();
+  const bool custom = prof.kind == SIMMR_K_CUSTOM, perfect = prof.kind == SIMMR_K_PERFECT_SHORT;
   // the Philox and perfect-short emit kernels write the metadata columns and the plan counters themselves
-  const bool fused = n_units > 0 && (e->plan.prof.kind == SIMMR_K_PERFECT_SHORT ||
-                                     (e->plan.prof.kind != SIMMR_K_CUSTOM && e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE));
+  const bool fused = c.n_units > 0 && (perfect || (!custom && prof.rng_mode != SIMMR_RNG_REFERENCE));
   if (!fused)
-    hipLaunchKernelGGL(k_write_meta, dim3(grid_for(n_units + 1, 256)), dim3(256), 0, e->stream,
-                       paired ? 1u : 0u, n_units, e->plan.first, read_id_base, e->plan.genome, pl,
-                       e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), u_genome, out_cols(out));
-  unsigned long long* counters = e->d_counters.as<unsigned long long>();
-  const ItemLaunch il = item_launch(e);
+    hipLaunchKernelGGL(k_write_meta, dim3(grid_for(c.n_units + 1, 256)), dim3(256), 0, e->stream,
+                       c.paired ? 1u : 0u, c.n_units, e->plan.first, read_id_base, e->plan.genome, c.pl,
+                       e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), c.u_genome, out_cols(out));
   HIP_TRY(e, next_emit_events(e));
   HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
-  if (n_units > 0) {
-    if (e->plan.prof.kind == SIMMR_K_PERFECT_SHORT) {
-      const uint64_t groups = (n_reads + PERFECT_GROUP - 1) / PERFECT_GROUP;
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(groups, (uint64_t)e->n_cu * 8 * e->perfect_mult);
-      auto kern = e->plan.multi ? k_emit_perfect_pe<true> : k_emit_perfect_pe<false>;
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
-                         e->plan.genome, u_genome, e->plan.any_exc ? 1u : 0u, n_units, e->plan.prof.read_length, pl,
-                         e->u_contig.as<uint32_t>(), out->seq,
-                         out->qual, 60u + out->qual_offset, e->plan.first, read_id_base, out_cols(out), counters);
-    } else if (e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE && e->plan.prof.kind != SIMMR_K_CUSTOM) {  // (a custom model's counter mode: below)
-      const bool escq = philox_escq(e, out->qual_offset & 0xffu);
-      const bool coarse = paired && e->plan.coarse;
-      PhiloxForm f{u_genome, out->seq, out->qual, out->qual_offset, read_id_base, out_cols(out)};
-      if (coarse) f.off64 = e->u_off64.as<uint64_t>();
-      launch_philox(e, philox_kernel(il.exc, il.cached, escq, e->plan.slot != 0, coarse), il.grid, 0, pl, f);
-    } else if (e->plan.prof.kind == SIMMR_K_CUSTOM && !paired) {
-      {
-        const bool fast0 = e->plan.prof.custom.kmer_stride != 0 && e->splice_variant != 1;
-        if (const char* missing = custom_long_tables_missing(e->plan.prof, fast0, e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE))
-          return e->fail(SIMMR_EINVAL, "custom long-read emit refused: device table `%s` of the model is not set for rng_mode %u "
-                                       "(nothing was launched)", missing, e->plan.prof.rng_mode);
-      }
-      HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
-      const bool exc = il.exc;
-      const uint64_t blocks = (n_reads + 255) / 256;
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
-      const uint32_t* order = e->plan.sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr;
-      hipLaunchKernelGGL(k_custom_long_qual, dim3(grid), dim3(256), 0, e->stream, e->plan.prof, n_units, order, pl,
-                         e->u_off.as<uint64_t>(), e->u_seed.as<uint64_t>(), out->qual, out->qual_offset, counters,
-                         e->d_err.as<uint32_t>());
-      bool fast = e->plan.prof.custom.kmer_stride != 0;
-      if (e->splice_variant == 1) fast = false;  // the two-load kernel (A/B timing)
-      if (e->plan.prof.rng_mode != SIMMR_RNG_REFERENCE) {
-        // the counter mode of the splice (kernels.hip section 9c, CTR): the LDS holds one word per k-mer (4^k words);
-        // with k = 7 (64 KB) two workgroups of 768 lanes share a CU — six waves per SIMD, what the kernel's registers allow —
-        // with smaller tables 256-lane workgroups do
-        auto kern = fast ? (exc ? k_custom_long_splice<true, true, true> : k_custom_long_splice<false, true, true>)
-                         : (exc ? k_custom_long_splice<true, false, true> : k_custom_long_splice<false, false, true>);
-        const uint32_t tab = fast ? splice_ctr_lds_bytes(e->plan.prof.custom.kmer_size) : 0u;
-        const uint32_t lanes = tab > 16384u ? SPLICE_CTR_LANES_MAX : 256u;
-        const uint32_t lds = fast ? tab + 16u * lanes : 0u;  // the k-mer table + 16 bytes per lane (an even group waiting for its odd neighbour's store)
-        if (lds > 32768u) HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (64 KB of table + the kernel's static LDS: over the default limit)
-        // (many more workgroups than are resident: reads come longest first, and the tail of the launch is short ones)
-        const uint32_t cgrid = (uint32_t)std::min<uint64_t>((n_reads + lanes - 1) / lanes, (uint64_t)e->n_cu * 64 * e->custom_long_mult);
-        hipLaunchKernelGGL(kern, dim3(cgrid), dim3(lanes), lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), n_units, order,
-                           pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
-                           e->u_seed.as<uint64_t>(), out->seq, counters, e->d_err.as<uint32_t>());
-      } else if (fast) {
-        // one workgroup of 1024 lanes per CU around the LDS count table (kernels.hip section 9c)
-        auto kern = exc ? k_custom_long_splice<true, true> : k_custom_long_splice<false, true>;
-        const uint32_t lds = splice_fast_lds_bytes(e->plan.prof.custom.kmer_size);
-        HIP_TRY(e, grant_dynamic_lds(e, kern, lds));  // (grows with the model's k: 132 KB + 4^k)
-        const uint32_t fgrid = (uint32_t)std::min<uint64_t>((n_reads + SPLICE_FAST_LANES - 1) / SPLICE_FAST_LANES, (uint64_t)e->n_cu * 8 * e->custom_long_mult);
-        hipLaunchKernelGGL(kern, dim3(fgrid), dim3(SPLICE_FAST_LANES), lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
-                           n_units, order, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
-                           e->u_seed.as<uint64_t>(), out->seq, counters, e->d_err.as<uint32_t>());
-      } else {
-        auto kern = exc ? k_custom_long_splice<true, false> : k_custom_long_splice<false, false>;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), n_units, order,
-                           pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), e->u_genome.as<uint32_t>(),
-                           e->u_seed.as<uint64_t>(), out->seq, counters, e->d_err.as<uint32_t>());
-      }
-    } else if (e->plan.prof.kind == SIMMR_K_CUSTOM) {
-      HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
-      const uint64_t blocks = (n_units + 255) / 256;  // one lane per pair
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, (uint64_t)e->n_cu * 8 * e->custom_pe_mult);
-      // qualities: one lane per pair (k_emit_custom_pe); bases: the item kernel without draws (coalesced stores)
-      hipLaunchKernelGGL(k_emit_custom_pe, dim3(grid), dim3(256), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
-                         e->plan.genome, n_units, pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(),
-                         e->u_seed.as<uint64_t>(), out->seq, out->qual, out->qual_offset, counters,
-                         e->d_err.as<uint32_t>());
-      // (its plain form whatever the plan: per-pair offsets, no contig cache, no genome column)
-      launch_philox(e, il.exc ? k_emit_philox<true, true, false> : k_emit_philox<false, true, false>, il.grid, 0, pl,
-                    PhiloxForm{nullptr, out->seq, out->qual, out->qual_offset, read_id_base, out_cols(out)});
-    } else {
-      // lane-per-read kernel: template on (exception plane present, paired, perfect-long Phred)
-      const bool exc = il.exc;
-      const bool pl_kind = e->plan.prof.kind == SIMMR_K_PERFECT_LONG;
-      using KernT = void (*)(ProfileDev, const GenomeDev*, uint32_t, uint64_t, const uint32_t*, PlanArrays,
-                             const uint64_t*, const uint32_t*, const uint32_t*, const uint64_t*, uint8_t*, uint8_t*,
-                             uint32_t, const Tables*, unsigned long long*);
-      KernT kern;
-      if (paired) kern = exc ? k_emit_lanes<true, true, false> : k_emit_lanes<false, true, false>;
-      else if (pl_kind) kern = exc ? k_emit_lanes<true, false, true> : k_emit_lanes<false, false, true>;
-      else kern = exc ? k_emit_lanes<true, false, false> : k_emit_lanes<false, false, false>;
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, LANES_WG, 0) != hipSuccess || per_cu < 1) per_cu = 1;
-      const uint64_t n_tasks = paired ? 2 * n_units : n_units;
-      const uint64_t wgs = (n_tasks + LANES_WG - 1) / LANES_WG;
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)e->n_cu * (uint64_t)per_cu * e->lanes_mult);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(LANES_WG), 0, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(),
-                         e->plan.genome, n_units, e->plan.sorted ? e->u_order.as<uint32_t>() : (const uint32_t*)nullptr,
-                         pl, e->u_off.as<uint64_t>(), e->u_contig.as<uint32_t>(), u_genome, e->u_seed.as<uint64_t>(),
-                         out->seq, out->qual, out->qual_offset, e->d_tables.as<Tables>(), counters);
-    }
+  if (c.n_units > 0) {
+    if (perfect) launch_perfect_short(e, c, out, read_id_base);
+    else if (custom) rc = c.paired ? launch_custom_pe(e, c, out, read_id_base) : launch_custom_long(e, c, out, read_id_base);
+    else if (prof.rng_mode != SIMMR_RNG_REFERENCE) launch_item_columns(e, c, out, read_id_base);
+    else launch_lanes(e, c, out, read_id_base);
+    if (rc) return rc;  // (the custom families: a table the model lacks, a stream call that failed)
   }
   HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
-  if (n_units > 0 && !fused) {
-    const bool perfect = e->plan.prof.kind == SIMMR_K_PERFECT_SHORT;
-    const bool acgt_all = perfect && !e->plan.any_exc;
-    hipLaunchKernelGGL(k_count_plan, dim3(std::min<uint32_t>(grid_for(n_units, 256), (uint32_t)e->n_cu * 4)), dim3(256), 0, e->stream, paired ? 1u : 0u,
-                       n_units, pl, perfect ? 60u : 0u, acgt_all ? 1u : 0u, counters);
-  }
+  if (c.n_units > 0 && !fused)
+    hipLaunchKernelGGL(k_count_plan, dim3(std::min<uint32_t>(grid_for(c.n_units, 256), (uint32_t)e->n_cu * 4)), dim3(256), 0, e->stream,
+                       c.paired ? 1u : 0u, c.n_units, c.pl, perfect ? 60u : 0u, (perfect && !e->plan.any_exc) ? 1u : 0u, c.counters);
   hipError_t s = hipGetLastError();
   if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "emit launch failed: %s", hipGetErrorString(s));
-  if (n_units > 0 && e->plan.prof.kind == SIMMR_K_CUSTOM) {
+  if (c.n_units > 0 && custom) {
     uint32_t errw = 0;
     if ((rc = read_err_word(e, &errw))) return rc;
     if (errw & SIMMR_ERRBIT_PDF)
@@ -2028,12 +2058,12 @@ bool compile_header_format(const char* fmt, std::vector<uint8_t>* blob, FqTempla
 bool has_brace(const char* s) { return strchr(s, '{') || strchr(s, '}'); }
 }  // namespace
 
-// the header template and the id tables of simmr_fastq_plan / simmr_fastq_plan_direct, compiled and uploaded
-static int fq_prepare(simmr_engine* e, const char* header_format, const simmr_fastq_names* names, uint32_t* lit_bytes_out,
-                      uint32_t* n_slots_out) {
+// the header template and the id tables of simmr_fastq_plan / simmr_fastq_plan_direct, compiled and uploaded; fills
+// f->tpl, f->lit_bytes and f->slots
+static int fq_prepare(simmr_engine* e, const char* header_format, const simmr_fastq_names* names, FqState* f) {
   std::vector<uint8_t> blob;
   bool risky = false;
-  if (!compile_header_format(header_format, &blob, &e->fq_tpl, &risky))
+  if (!compile_header_format(header_format, &blob, &f->tpl, &risky))
     return e->fail(SIMMR_ENOTSUP, "header format has more than %d pieces", FQ_MAX_SEGS);
   if (risky)
     return e->fail(SIMMR_ENOTSUP, "the header format has braces around a genome / sequence id: the reference's chain of "
@@ -2078,10 +2108,10 @@ static int fq_prepare(simmr_engine* e, const char* header_format, const simmr_fa
       (rc = upload_vec(e, e->fq_clen, clen)))
     return rc;
   if (!e->fq_tpl_dev.ensure(sizeof(FqTemplate))) return e->fail(SIMMR_ENOMEM, "template allocation failed");
-  HIP_TRY(e, hipMemcpyAsync(e->fq_tpl_dev.p, &e->fq_tpl, sizeof(FqTemplate), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(e->fq_tpl_dev.p, &f->tpl, sizeof(FqTemplate), hipMemcpyHostToDevice, e->stream));
   if ((rc = sync_check(e, "fastq table upload"))) return rc;  // the host vectors go out of scope
-  *lit_bytes_out = lit_bytes;
-  *n_slots_out = n_slots;
+  f->lit_bytes = lit_bytes;
+  f->slots = n_slots;
   return SIMMR_OK;
 }
 
@@ -2117,85 +2147,85 @@ static FqTables fq_tables(const simmr_engine* e, uint32_t n_slots) {
                   e->fq_clen.as<uint32_t>(), n_slots};
 }
 
+static FqReads fq_reads_view(const simmr_reads_out* reads) {
+  return FqReads{reads->seq, reads->qual, reads->seq_off, reads->start, reads->end, reads->contig, reads->genome,
+                 reads->read_id, reads->flags, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
+}
+
+// The end of a FASTQ plan call: turns the size kernel's error word into the call's answer, and on success sizes the
+// header slots from the longest header and makes `f` the FASTQ plan in force.  slot_extra: the bytes of a slot besides
+// the header and the slack of the 8-byte id copies and 16-byte window reads.
+static int fq_finish(simmr_engine* e, FqState f, uint32_t slot_extra, uint64_t* total_bytes) {
+  uint32_t errw2[2] = {0, 0};  // error bits, longest header
+  HIP_TRY(e, hipMemcpyAsync(errw2, e->d_err.p, 8, hipMemcpyDeviceToHost, e->stream));
+  if (int rc = sync_check(e, "fastq size readback")) return rc;
+  if (errw2[0] & SIMMR_ERRBIT_FASTQ)
+    return e->fail(SIMMR_ENOTSUP, "a FASTQ header is longer than %u bytes, or a read names a genome / contig without an id", FQ_HMAX - 1);
+  f.maxhdr = errw2[1];
+  f.hpitch = fq_slot_pitch(f.maxhdr + slot_extra + 8u + 16u);
+  e->fq = f;
+  *total_bytes = f.total;
+  return SIMMR_OK;
+}
+
 int simmr_fastq_plan(simmr_engine* e, const char* header_format, const simmr_fastq_names* names,
                      const simmr_reads_out* reads, uint64_t n_reads, int paired, uint64_t* total_bytes) {
   if (!e) return SIMMR_EINVAL;
-  e->fq_ready = false;
-  e->fq_direct = false;
+  e->fq = FqState{};
   if (!header_format || !names || !reads || !total_bytes) return e->fail(SIMMR_EINVAL, "simmr_fastq_plan: NULL argument");
   if (!reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->read_id ||
       !reads->flags || (n_reads > 0 && (!reads->seq || !reads->qual)))
     return e->fail(SIMMR_EINVAL, "simmr_fastq_plan needs every column of simmr_reads_out");
   HIP_TRY(e, hipSetDevice(e->device));
-  uint32_t lit_bytes = 0, n_slots = 0;
+  FqState f;
+  f.kind = FQPLAN_COLUMNS;
+  f.reads = n_reads;
+  f.paired = paired != 0;
   int rc;
-  if ((rc = fq_prepare(e, header_format, names, &lit_bytes, &n_slots))) return rc;
+  if ((rc = fq_prepare(e, header_format, names, &f))) return rc;
   if (!e->fq_len.ensure(std::max<uint64_t>(n_reads, 1) * 8)) return e->fail(SIMMR_ENOMEM, "record length allocation failed");
   HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
-  const FqTables tb = fq_tables(e, n_slots);
-  const FqReads rd{reads->seq, reads->qual, reads->seq_off, reads->start, reads->end, reads->contig, reads->genome,
-                   reads->read_id, reads->flags, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
   if (n_reads > 0)
-    hipLaunchKernelGGL(k_fastq_size, dim3(grid_for(n_reads, 256)), dim3(256), 0, e->stream, fq_len_coef(e->fq_tpl), tb, rd, n_reads,
-                       e->fq_len.as<uint64_t>(), e->d_err.as<uint32_t>());
-  uint64_t total = 0;
-  if ((rc = scan_u64(e, e->fq_len, n_reads, e->fq_off, &total))) return rc;  // also waits for the uploads
-  uint32_t errw2[2] = {0, 0};  // error bits, longest header
-  HIP_TRY(e, hipMemcpyAsync(errw2, e->d_err.p, 8, hipMemcpyDeviceToHost, e->stream));
-  if ((rc = sync_check(e, "fastq size readback"))) return rc;
-  if (errw2[0] & SIMMR_ERRBIT_FASTQ)
-    return e->fail(SIMMR_ENOTSUP, "a FASTQ header is longer than %u bytes, or a read names a genome / contig without an id", FQ_HMAX - 1);
-  e->fq_hpitch = fq_slot_pitch(errw2[1] + 1u + 8u + 16u);  // header, '\n', slack of the 8-byte id copies and 16-byte window reads
-  e->fq_reads = n_reads;
-  e->fq_total = total;
-  e->fq_slots = n_slots;
-  e->fq_lit_bytes = lit_bytes;
-  e->fq_paired = paired != 0;
-  e->fq_ready = true;
-  *total_bytes = total;
-  return SIMMR_OK;
+    hipLaunchKernelGGL(k_fastq_size, dim3(grid_for(n_reads, 256)), dim3(256), 0, e->stream, fq_len_coef(f.tpl), fq_tables(e, f.slots),
+                       fq_reads_view(reads), n_reads, e->fq_len.as<uint64_t>(), e->d_err.as<uint32_t>());
+  if ((rc = scan_u64(e, e->fq_len, n_reads, e->fq_off, &f.total))) return rc;  // also waits for the uploads
+  return fq_finish(e, f, 1u, total_bytes);  // header, '\n'
 }
 
-int simmr_fastq_emit(simmr_engine* e, const simmr_reads_out* reads, uint8_t* dst, uint64_t dst_capacity) {
-  if (!e) return SIMMR_EINVAL;
-  if (!e->fq_ready || e->fq_direct) return e->fail(SIMMR_ESTATE, "simmr_fastq_emit called without simmr_fastq_plan");
-  if (!reads) return e->fail(SIMMR_EINVAL, "reads is NULL");
-  if (dst_capacity < e->fq_total)
-    return e->fail(SIMMR_ERANGE, "dst_capacity %llu < %llu bytes planned", (unsigned long long)dst_capacity,
-                   (unsigned long long)e->fq_total);
-  if (e->fq_reads == 0) return SIMMR_OK;
-  if (!dst) return e->fail(SIMMR_EINVAL, "dst is NULL");
-  HIP_TRY(e, hipSetDevice(e->device));
-  const FqTables tb = fq_tables(e, e->fq_slots);
-  const FqReads rd{reads->seq, reads->qual, reads->seq_off, reads->start, reads->end, reads->contig, reads->genome,
-                   reads->read_id, reads->flags, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
-  const uint64_t n_batches = (e->fq_reads + FQ_BATCH - 1) / FQ_BATCH;
+// k_fastq_write over the columns `rd` with the offsets of the FASTQ plan in force (fq_off).  timed: as an emit of its
+// own, between a pair of the emit events.
+static int launch_fastq_write(simmr_engine* e, const FqReads& rd, uint8_t* dst, bool timed) {
+  const FqState& f = e->fq;
+  const uint64_t n_batches = (f.reads + FQ_BATCH - 1) / FQ_BATCH;
   const uint32_t grid = (uint32_t)std::min<uint64_t>((n_batches + 3) / 4, (uint64_t)e->n_cu * 8 * e->fastq_mult);
-  const uint32_t hdr_lds = 4 * FQ_BATCH * e->fq_hpitch;  // up to 68 KB with 255-byte headers: above the default limit
+  const uint32_t hdr_lds = 4 * FQ_BATCH * f.hpitch;  // up to 68 KB with 255-byte headers: above the default limit
   if (hdr_lds > 48 * 1024) HIP_TRY(e, grant_dynamic_lds(e, k_fastq_write, hdr_lds));
-  HIP_TRY(e, next_emit_events(e));
-  HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
-  hipLaunchKernelGGL(k_fastq_write, dim3(grid), dim3(256), hdr_lds, e->stream, e->fq_tpl_dev.as<FqTemplate>(), tb, rd,
-                     e->fq_reads, e->fq_paired ? 1u : 0u, e->fq_lit_bytes, e->fq_hpitch, e->fq_off.as<uint64_t>(), dst);
-  HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
+  if (timed) HIP_TRY(e, next_emit_events(e));
+  if (timed) HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
+  hipLaunchKernelGGL(k_fastq_write, dim3(grid), dim3(256), hdr_lds, e->stream, e->fq_tpl_dev.as<FqTemplate>(), fq_tables(e, f.slots), rd,
+                     f.reads, f.paired ? 1u : 0u, f.lit_bytes, f.hpitch, e->fq_off.as<uint64_t>(), dst);
+  if (timed) HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
   hipError_t s = hipGetLastError();
   if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "fastq launch failed: %s", hipGetErrorString(s));
   return SIMMR_OK;
 }
 
+int simmr_fastq_emit(simmr_engine* e, const simmr_reads_out* reads, uint8_t* dst, uint64_t dst_capacity) {
+  if (!e) return SIMMR_EINVAL;
+  if (e->fq.kind != FQPLAN_COLUMNS) return e->fail(SIMMR_ESTATE, "simmr_fastq_emit called without simmr_fastq_plan");
+  if (!reads) return e->fail(SIMMR_EINVAL, "reads is NULL");
+  if (dst_capacity < e->fq.total)
+    return e->fail(SIMMR_ERANGE, "dst_capacity %llu < %llu bytes planned", (unsigned long long)dst_capacity,
+                   (unsigned long long)e->fq.total);
+  if (e->fq.reads == 0) return SIMMR_OK;
+  if (!dst) return e->fail(SIMMR_EINVAL, "dst is NULL");
+  HIP_TRY(e, hipSetDevice(e->device));
+  return launch_fastq_write(e, fq_reads_view(reads), dst, true);
+}
+
 // ---- FASTQ text straight from the plan (include/simmr_hip.h) --------------------------------------------------
-static FqPlan fq_plan_view(simmr_engine* e) {
-  const bool paired = e->plan.paired;
-  const bool seeds2 = paired && e->plan.prof.kind != SIMMR_K_PERFECT_SHORT;
-  FqPlan pn;
-  pn.pl = plan_arrays(e, seeds2);
-  pn.u_contig = e->u_contig.as<uint32_t>();
-  pn.u_genome = (paired && !e->plan.multi) ? nullptr : e->u_genome.as<uint32_t>();
-  pn.first_unit = e->plan.first;
-  pn.read_id_base = e->fq_read_id_base;
-  pn.genome_const = e->plan.genome;
-  pn.paired = paired ? 1u : 0u;
-  return pn;
+static FqPlan fq_plan_view(simmr_engine* e, const EmitCtx& c, uint32_t read_id_base) {
+  return FqPlan{c.pl, e->u_contig.as<uint32_t>(), c.u_genome, e->plan.first, read_id_base, e->plan.genome, c.paired ? 1u : 0u};
 }
 
 // does the current plan's emit kernel write into FASTQ text?  The counter-mode item kernel does, and so does its copy-only
@@ -2208,74 +2238,58 @@ static bool fq_direct_kernel(const simmr_engine* e) {
 int simmr_fastq_plan_direct(simmr_engine* e, const char* header_format, const simmr_fastq_names* names,
                             uint32_t read_id_base, uint64_t* total_bytes) {
   if (!e) return SIMMR_EINVAL;
-  e->fq_ready = false;
-  e->fq_direct = false;
+  e->fq = FqState{};
   if (!header_format || !names || !total_bytes) return e->fail(SIMMR_EINVAL, "simmr_fastq_plan_direct: NULL argument");
   if (e->plan.kind == PLAN_NONE) return e->fail(SIMMR_ESTATE, "simmr_fastq_plan_direct called without a plan");
   HIP_TRY(e, hipSetDevice(e->device));
-  uint32_t lit_bytes = 0, n_slots = 0;
+  const EmitCtx c = emit_ctx(e);
+  FqState f;
+  f.kind = FQPLAN_DIRECT;
+  f.reads = c.n_reads;
+  f.paired = c.paired;
+  f.read_id_base = read_id_base;
   int rc;
-  if ((rc = fq_prepare(e, header_format, names, &lit_bytes, &n_slots))) return rc;
-  const uint64_t n_reads = e->plan.paired ? 2 * e->plan.units : e->plan.units;
+  if ((rc = fq_prepare(e, header_format, names, &f))) return rc;
+  const uint64_t n_reads = c.n_reads;
   if (!e->fq_len.ensure(std::max<uint64_t>(n_reads, 1) * 8) || !e->fq_hlen.ensure(std::max<uint64_t>(n_reads, 1)))
     return e->fail(SIMMR_ENOMEM, "record length allocation failed");
   HIP_TRY(e, hipEventRecord(e->ev_a, e->stream));
   HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
-  e->fq_read_id_base = read_id_base;
-  const FqTables tb = fq_tables(e, n_slots);
   // When the emit kernel writes into the text and formats the headers itself it also places its own records: it asks for
   // the first byte of every 64th record only (fq_off64, the scan of the size kernel's per-wave sums), not for fq_off.
-  const bool coarse = fq_direct_kernel(e);
+  const bool coarse = f.coarse = fq_direct_kernel(e);
   const uint64_t n_w = (n_reads + 63) / 64;
   unsigned long long* tiles = coarse ? nullptr : tile_sums_begin(e, n_reads);
   if (!coarse && !tiles) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
   if (coarse && !e->w_bytes.ensure(std::max<uint64_t>(n_w, 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
   if (n_reads > 0)
-    hipLaunchKernelGGL(k_fastq_size_plan, dim3(grid_for(n_reads, 256)), dim3(256), 0, e->stream, fq_len_coef(e->fq_tpl), tb, fq_plan_view(e),
-                       n_reads, coarse ? (uint64_t*)nullptr : e->fq_len.as<uint64_t>(), e->fq_hlen.as<uint8_t>(), e->d_err.as<uint32_t>(), tiles,
-                       coarse ? e->w_bytes.as<unsigned long long>() : (unsigned long long*)nullptr);
-  uint64_t total = 0;
-  if (coarse) { if ((rc = scan_u64(e, e->w_bytes, n_w, e->fq_off64, &total))) return rc; }
-  else if ((rc = scan_presummed<uint64_t>(e, e->fq_len, n_reads, 1u, e->fq_off, &total))) return rc;
-  e->fq_coarse = coarse;
+    hipLaunchKernelGGL(k_fastq_size_plan, dim3(grid_for(n_reads, 256)), dim3(256), 0, e->stream, fq_len_coef(f.tpl), fq_tables(e, f.slots),
+                       fq_plan_view(e, c, read_id_base), n_reads, coarse ? (uint64_t*)nullptr : e->fq_len.as<uint64_t>(), e->fq_hlen.as<uint8_t>(),
+                       e->d_err.as<uint32_t>(), tiles, coarse ? e->w_bytes.as<unsigned long long>() : (unsigned long long*)nullptr);
+  if (coarse) { if ((rc = scan_u64(e, e->w_bytes, n_w, e->fq_off64, &f.total))) return rc; }
+  else if ((rc = scan_presummed<uint64_t>(e, e->fq_len, n_reads, 1u, e->fq_off, &f.total))) return rc;
   HIP_TRY(e, hipEventRecord(e->ev_b, e->stream));
-  uint32_t errw2[2] = {0, 0};  // error bits, longest header
-  HIP_TRY(e, hipMemcpyAsync(errw2, e->d_err.p, 8, hipMemcpyDeviceToHost, e->stream));
-  if ((rc = sync_check(e, "fastq size readback"))) return rc;
-  if (errw2[0] & SIMMR_ERRBIT_FASTQ)
-    return e->fail(SIMMR_ENOTSUP, "a FASTQ header is longer than %u bytes, or a read names a genome / contig without an id", FQ_HMAX - 1);
+  if ((rc = fq_finish(e, f, 2u, total_bytes))) return rc;  // the previous record's '\n', header, '\n'
   (void)hipEventElapsedTime(&e->last_fastq_plan_ms, e->ev_a, e->ev_b);
-  e->fq_hpitch = fq_slot_pitch(errw2[1] + 2u + 8u + 16u);  // the previous record's '\n', header, '\n', slack of the 8-byte id copies
-  e->fq_maxhdr = errw2[1];
-  e->fq_reads = n_reads;
-  e->fq_total = total;
-  e->fq_slots = n_slots;
-  e->fq_lit_bytes = lit_bytes;
-  e->fq_paired = e->plan.paired;
-  e->fq_ready = true;
-  e->fq_direct = true;
-  *total_bytes = total;
   return SIMMR_OK;
 }
 
 int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
   if (!e) return SIMMR_EINVAL;
-  if (!e->fq_ready || !e->fq_direct || e->plan.kind == PLAN_NONE)
+  const FqState& f = e->fq;
+  if (f.kind != FQPLAN_DIRECT || e->plan.kind == PLAN_NONE)
     return e->fail(SIMMR_ESTATE, "simmr_emit_fastq called without simmr_fastq_plan_direct on the current plan");
-  if (dst_capacity < e->fq_total)
+  if (dst_capacity < f.total)
     return e->fail(SIMMR_ERANGE, "dst_capacity %llu < %llu bytes planned", (unsigned long long)dst_capacity,
-                   (unsigned long long)e->fq_total);
-  const uint64_t n_units = e->plan.units, n_reads = e->fq_reads;
-  if (n_reads == 0) return SIMMR_OK;
+                   (unsigned long long)f.total);
+  if (f.reads == 0) return SIMMR_OK;
   if (!dst) return e->fail(SIMMR_EINVAL, "dst is NULL");
   HIP_TRY(e, hipSetDevice(e->device));
-  const bool paired = e->plan.paired;
-  const bool direct_kernel = fq_direct_kernel(e);
-  const FqTables tb = fq_tables(e, e->fq_slots);
-  if (!direct_kernel) {
-    // No emit kernel of this profile writes into text: the columns are built in buffers of the engine and framed from
-    // there (the same kernels as simmr_*_emit + simmr_fastq_emit; qualities with the FASTQ offset, util.rs:46-57).
-    const uint64_t tb_bytes = std::max<uint64_t>(e->plan.total_bases, 1), nr = std::max<uint64_t>(n_reads, 1);
+  if (!f.coarse) {
+    // No emit kernel of this profile writes into text (fq_direct_kernel; the plan call made fq_off): the columns are built
+    // in buffers of the engine and framed from there (the same kernels as simmr_*_emit + simmr_fastq_emit; qualities
+    // with the FASTQ offset, util.rs:46-57).
+    const uint64_t tb_bytes = std::max<uint64_t>(e->plan.total_bases, 1), nr = std::max<uint64_t>(f.reads, 1);
     if (!e->fd_seq.ensure(tb_bytes) || !e->fd_qual.ensure(tb_bytes) || !e->fd_seq_off.ensure((nr + 1) * 8) || !e->fd_start.ensure(nr * 8) ||
         !e->fd_end.ensure(nr * 8) || !e->fd_contig.ensure(nr * 4) || !e->fd_genome.ensure(nr * 4) || !e->fd_read_id.ensure(nr * 4) ||
         !e->fd_flags.ensure(nr))
@@ -2285,54 +2299,35 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
     cols.start = e->fd_start.as<uint64_t>(); cols.end = e->fd_end.as<uint64_t>(); cols.contig = e->fd_contig.as<uint32_t>();
     cols.genome = e->fd_genome.as<uint32_t>(); cols.read_id = e->fd_read_id.as<uint32_t>(); cols.flags = e->fd_flags.as<uint8_t>();
     cols.seq_capacity = tb_bytes; cols.reads_capacity = nr; cols.qual_offset = 33;
-    int rc = emit_common(e, e->fq_read_id_base, &cols);
-    if (rc) return rc;
-    const FqReads rd{cols.seq, cols.qual, cols.seq_off, cols.start, cols.end, cols.contig, cols.genome, cols.read_id, cols.flags, 0u};
-    const uint64_t n_batches = (n_reads + FQ_BATCH - 1) / FQ_BATCH;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_batches + 3) / 4, (uint64_t)e->n_cu * 8 * e->fastq_mult);
-    const uint32_t hdr_lds = 4 * FQ_BATCH * e->fq_hpitch;
-    if (hdr_lds > 48 * 1024) HIP_TRY(e, grant_dynamic_lds(e, k_fastq_write, hdr_lds));
-    hipLaunchKernelGGL(k_fastq_write, dim3(grid), dim3(256), hdr_lds, e->stream, e->fq_tpl_dev.as<FqTemplate>(), tb, rd, n_reads, paired ? 1u : 0u,
-                       e->fq_lit_bytes, e->fq_hpitch, e->fq_off.as<uint64_t>(), dst);
-    hipError_t s = hipGetLastError();
-    if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "fastq launch failed: %s", hipGetErrorString(s));
-    return SIMMR_OK;
+    if (int rc = emit_common(e, f.read_id_base, &cols)) return rc;
+    return launch_fastq_write(e, fq_reads_view(&cols), dst, false);  // (the event pair of this emit is the one around emit_common's kernels)
   }
-  const bool seeds2 = paired && e->plan.prof.kind != SIMMR_K_PERFECT_SHORT;
-  PlanArrays pl = plan_arrays(e, seeds2);
-  const uint32_t* u_genome = (paired && !e->plan.multi) ? nullptr : e->u_genome.as<uint32_t>();
-  unsigned long long* counters = e->d_counters.as<unsigned long long>();
+  const EmitCtx c = emit_ctx(e);
+  const FqTables tb = fq_tables(e, f.slots);
   HIP_TRY(e, next_emit_events(e));
   HIP_TRY(e, hipEventRecord(e->ev_c, e->stream));
-  {
-    const ItemLaunch il = item_launch(e);
-    const bool exc = il.exc, cached = il.cached, escq = philox_escq(e, 33u);
-    const uint32_t grid = il.grid;
-    const bool copy_only = e->plan.prof.kind == SIMMR_K_PERFECT_SHORT;  // (perfect-short: bases of the plan, every quality 60)
-    // The whole-line form: paired plans whose reads fit its segments, into a buffer its 16-byte chunks are aligned in,
-    // with header slots that leave room for two workgroups per CU; everything else takes the item form.
-    const uint32_t tl_pitch = tl_slot_pitch(e->fq_maxhdr);
-    const uint32_t tl_lds = TL_GROUP * tl_pitch;
-    if (e->text_form == 2 && paired && e->plan.short_ok && ((uintptr_t)dst & 15u) == 0 && tl_lds <= 40u * 1024u) {
-      auto tk = text_lines_kernel(exc, cached, escq, copy_only);
-      HIP_TRY(e, grant_dynamic_lds(e, tk, tl_lds));  // (static + dynamic LDS may pass the default limit with long headers)
-      const uint32_t t8 = tl_pitch / 8u, t9 = (t8 + 1u) / 2u;
-      hipLaunchKernelGGL(tk, dim3(grid), dim3(256), tl_lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), e->plan.genome, n_units, pl,
-                         e->u_contig.as<uint32_t>(), u_genome, e->u_seed.as<uint64_t>(), dst, 33u, e->plan.first, e->fq_read_id_base,
-                         counters, e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(), tb, e->fq_lit_bytes, tl_pitch, t9,
-                         65536u / t9 + 1u, (const uint64_t*)e->fq_off64.as<uint64_t>());
-      HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
-      hipError_t s2 = hipGetLastError();
-      if (s2 != hipSuccess) return e->fail(SIMMR_ENODEV, "fastq launch failed: %s", hipGetErrorString(s2));
-      return SIMMR_OK;
-    }
+  const bool exc = c.il.exc, cached = c.il.cached, escq = philox_escq(e, 33u);
+  const bool copy_only = e->plan.prof.kind == SIMMR_K_PERFECT_SHORT;  // (perfect-short: bases of the plan, every quality 60)
+  // The whole-line form: paired plans whose reads fit its segments, into a buffer its 16-byte chunks are aligned in,
+  // with header slots that leave room for two workgroups per CU; everything else takes the item form.
+  const uint32_t tl_pitch = tl_slot_pitch(f.maxhdr);
+  const uint32_t tl_lds = TL_GROUP * tl_pitch;
+  if (e->text_form == 2 && c.paired && e->plan.short_ok && ((uintptr_t)dst & 15u) == 0 && tl_lds <= 40u * 1024u) {
+    auto tk = text_lines_kernel(exc, cached, escq, copy_only);
+    HIP_TRY(e, grant_dynamic_lds(e, tk, tl_lds));  // (static + dynamic LDS may pass the default limit with long headers)
+    const uint32_t t8 = tl_pitch / 8u, t9 = (t8 + 1u) / 2u;
+    hipLaunchKernelGGL(tk, dim3(c.il.grid), dim3(256), tl_lds, e->stream, e->plan.prof, e->d_genomes.as<GenomeDev>(), e->plan.genome, c.n_units, c.pl,
+                       e->u_contig.as<uint32_t>(), c.u_genome, e->u_seed.as<uint64_t>(), dst, 33u, e->plan.first, f.read_id_base,
+                       c.counters, e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(), tb, f.lit_bytes, tl_pitch, t9,
+                       65536u / t9 + 1u, (const uint64_t*)e->fq_off64.as<uint64_t>());
+  } else {
     // windows per run: the power of two that covers the longest run ('\n' + header + '\n'), at most 32 (512 bytes)
     uint32_t wshift = 0;
-    while ((16u << wshift) < e->fq_maxhdr + 2u) wshift++;
-    const uint32_t slots_lds = std::max<uint32_t>(PHILOX_MAP_ITEMS, FQ_GROUP * e->fq_hpitch);  // header slots; the item map lives there too
-    launch_philox(e, philox_text_kernel(exc, cached, escq, copy_only), grid, slots_lds, pl,
-                  PhiloxForm{u_genome, dst, dst, 33u, e->fq_read_id_base, OutCols{}, e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(),
-                             tb, e->fq_lit_bytes, e->fq_hpitch, wshift, e->fq_off64.as<uint64_t>()});
+    while ((16u << wshift) < f.maxhdr + 2u) wshift++;
+    const uint32_t slots_lds = std::max<uint32_t>(PHILOX_MAP_ITEMS, FQ_GROUP * f.hpitch);  // header slots; the item map lives there too
+    launch_philox(e, philox_text_kernel(exc, cached, escq, copy_only), c.il.grid, slots_lds, c.pl,
+                  PhiloxForm{c.u_genome, dst, dst, 33u, f.read_id_base, OutCols{}, e->fq_hlen.as<uint8_t>(), e->fq_tpl_dev.as<FqTemplate>(),
+                             tb, f.lit_bytes, f.hpitch, wshift, e->fq_off64.as<uint64_t>()});
   }
   HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
   hipError_t s = hipGetLastError();

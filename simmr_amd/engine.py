@@ -316,13 +316,7 @@ class Engine:
         [sequence id per contig]), ...]; qualities must have been emitted with qual_offset=33.
         Raises SimmrError(ENOTSUP) for the cases the library leaves to the host writer."""
         torch = _torch()
-        n = len(names)
-        gi = (C.c_uint32 * max(n, 1))(*[int(x[0]) for x in names])
-        gid = (C.c_char_p * max(n, 1))(*[str(x[1]).encode() for x in names])
-        nc = (C.c_uint32 * max(n, 1))(*[len(x[2]) for x in names])
-        flat = [str(sid).encode() for x in names for sid in x[2]]
-        sids = (C.c_char_p * max(len(flat), 1))(*flat)
-        fn = _abi.FastqNames(n, gi, gid, nc, sids)
+        fn = self._fastq_names(names)
         pod = reads.pod()
         total = C.c_uint64(0)
         self._check(self.lib.simmr_fastq_plan(self._h, header_format.encode(), C.byref(fn), C.byref(pod),

@@ -217,3 +217,89 @@ def test_fastq_direct_exception_bases(engine):
     want = _two_step(engine, reads, names, FMT, False)
     engine.long_plan([12], [60], lp, 8)
     _same_text(engine.fastq_direct(FMT, names, 0).cpu().numpy().tobytes(), want, "long ")
+
+
+# ---- which FASTQ plan is in force: one state, committed whole (engine.hip: FqState) ----------------------------------
+MARK = 0xA5
+
+
+def _fastq_emit_rc(engine, reads, buf):
+    """simmr_fastq_emit itself (Engine.fastq plans before it emits): its status, the text going to `buf`."""
+    import ctypes as C
+    pod = reads.pod()
+    return engine.lib.simmr_fastq_emit(engine._h, C.byref(pod), C.c_void_p(buf.data_ptr()), buf.numel())
+
+
+def _marked(engine, n):
+    import torch
+    return torch.full((max(n, 1),), MARK, dtype=torch.uint8, device=engine.device)
+
+
+def _emit_fastq_code(engine, buf):
+    with pytest.raises(SimmrError) as ei:
+        engine.emit_fastq(buf)
+    return ei.value.code
+
+
+@pytest.fixture(scope="module")
+def state_case(engine, genome_multi):
+    """800 reads of 37 bp on the reference generator, their names and their text through the columns."""
+    prof = MinimalShortErrorProfile(read_length=37, insert_size=80).pod()
+    names = PE_NAMES(genome_multi)
+    reads = engine.simulate_pe_reads_from_genome(1, prof, 800, 11, qual_offset=33)
+    want = engine.fastq(reads, FMT, names, True).cpu().numpy().tobytes()
+    assert reads.n_reads == 800 and len(want) > 800 * (2 * 37 + 6)
+    return prof, names, reads, want
+
+
+def test_direct_fastq_plan_does_not_outlive_its_plan_for_fastq_emit(engine, state_case):
+    """simmr_fastq_plan_direct, a new plan call, simmr_fastq_emit: SIMMR_ESTATE and nothing written (the header's
+    "simmr_fastq_emit called without simmr_fastq_plan"), not a framing of the caller's columns with the offsets the direct
+    plan left.  The direct plan of this profile is the per-record one, made for exactly these reads, and the buffer has
+    the full size: a build that lets the emit through still writes inside it."""
+    prof, names, reads, want = state_case
+    engine.pe_plan(1, prof, 800, 11)
+    assert engine.fastq_plan_direct(FMT, names) == len(want)
+    engine.pe_plan(1, prof, 800, 11)
+    buf = _marked(engine, len(want))
+    assert _fastq_emit_rc(engine, reads, buf) == _abi.ESTATE
+    assert bool((buf == MARK).all())
+    assert engine.fastq(reads, FMT, names, True).cpu().numpy().tobytes() == want
+
+
+def test_failed_fastq_plan_leaves_none(engine, state_case, genome_multi):
+    prof, names, reads, want = state_case
+    bad = [(1, "id{with}braces", ["c"] * len(genome_multi.contigs))]
+    buf = _marked(engine, len(want))
+    # a columns plan in force, then a direct plan that fails
+    assert engine.fastq(reads, FMT, names, True).numel() == len(want)
+    engine.pe_plan(1, prof, 800, 11)
+    with pytest.raises(SimmrError) as ei:
+        engine.fastq_plan_direct(FMT, bad)
+    assert ei.value.code == _abi.ENOTSUP
+    assert _fastq_emit_rc(engine, reads, buf) == _abi.ESTATE
+    assert _emit_fastq_code(engine, buf) == _abi.ESTATE
+    # a direct plan in force, then a columns plan that fails
+    assert engine.fastq_plan_direct(FMT, names) == len(want)
+    with pytest.raises(SimmrError) as ei:
+        engine.fastq(reads, FMT, bad, True)
+    assert ei.value.code == _abi.ENOTSUP
+    assert _fastq_emit_rc(engine, reads, buf) == _abi.ESTATE
+    assert _emit_fastq_code(engine, buf) == _abi.ESTATE
+    assert bool((buf == MARK).all())
+
+
+def test_columns_fastq_plan_survives_a_new_plan_call(engine, state_case):
+    """simmr_fastq_plan describes the caller's columns, not the engine's plan: a plan of another shard in between
+    changes nothing."""
+    import ctypes as C
+    prof, names, reads, want = state_case
+    fn = engine._fastq_names(names)
+    pod = reads.pod()
+    total = C.c_uint64(0)
+    assert engine.lib.simmr_fastq_plan(engine._h, FMT.encode(), C.byref(fn), C.byref(pod), reads.n_reads, 1, C.byref(total)) == _abi.OK
+    assert total.value == len(want)
+    engine.pe_plan(1, PerfectShortErrorProfile().pod(), 3000, 5, 100, 700)
+    buf = _marked(engine, len(want))
+    assert _fastq_emit_rc(engine, reads, buf) == _abi.OK
+    assert buf.cpu().numpy().tobytes() == want
