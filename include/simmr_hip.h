@@ -565,6 +565,75 @@ int simmr_stats_read(simmr_engine* e, simmr_run_stats* dst_host);
 /* HIP-event time (ms) of the last simmr_stats_add's device work.  Synchronises the stream. */
 int simmr_last_stats_ms(simmr_engine* e, float* ms);
 
+/* ---- coverage depth: where the reads of a run landed, per position, window and contig ----------------------------
+ * Replaces nothing in the reference, which reports the nominal num_reads and abundance of a genome (files.rs:100-134) and
+ * never what a run put on each contig.  Counted on the device from four columns in HBM, without draining the reads.
+ *
+ * Definition.  For read r, L = |end[r] - start[r]| and lo = min(start[r], end[r]): coordinates into Seq.seq, exactly
+ * simmr_truth_out's (above).  The read COVERS positions lo .. lo + L - 1 of contig contig[r] of genome slot genome[r]; a
+ * read with L = 0 covers nothing.  depth[x] = the number of added reads that cover x.  Mates count separately (an
+ * overlapping pair contributes 2 where it overlaps): read depth, not fragment depth.
+ * depth[] is ONE dense uint32_t array over every genome staged when simmr_depth_reset was called: genomes in ascending slot
+ * order, the contigs of a genome in order, each contig Seq.seq.len() entries, no padding; n_positions is the total, and
+ * simmr_depth_contig_first says where a contig starts.
+ *
+ * Every result is an integer sum over reads, so it is a function of the inputs alone — launch geometry and the order of
+ * the adds never change a number — and the arrays of several adds, ranges, engines or ranks add up entry by entry (the
+ * caller sums them; the library offers no all-reduce for them). */
+#define SIMMR_DEPTH_HIST_BINS 256u
+
+typedef struct simmr_depth_contig {   /* HOST memory: one row per tracked contig, in the order of depth[] */
+  uint32_t genome, contig;            /* genome slot, contig index */
+  uint64_t first, len;                /* the contig is depth[first .. first + len) */
+  uint64_t covered;                   /* positions with depth >= 1 */
+  uint64_t depth_sum;                 /* sum of depth over the contig = bases of the reads that landed on it */
+  uint32_t depth_max, reserved0;
+  uint64_t first_window;              /* index of the contig's first window in the window columns (window > 0), else 0 */
+} simmr_depth_contig;
+
+typedef struct simmr_depth_windows {  /* DEVICE pointers, caller-owned: one entry per window */
+  uint64_t* sum;                      /* sum of depth over the window */
+  uint32_t* covered;                  /* positions of the window with depth >= 1 */
+  uint32_t* max;
+  uint64_t capacity;                  /* entries available in each column */
+  uint64_t n_windows;                 /* OUT: windows of the run, written whenever the layout is known (also with
+                                         SIMMR_ERANGE, so that a caller can size the columns and call again) */
+} simmr_depth_windows;
+
+/* Allocates on first use and zeroes (on the engine's stream) the engine's difference array — n_positions + 1 int32_t —
+ * and its sticky error word, and records which genomes are tracked: those staged now.  *n_positions receives the length
+ * of depth[], *n_contigs the number of tracked contigs (the rows of simmr_depth_summarize); either may be NULL.
+ * SIMMR_ENOMEM if the array cannot be had. */
+int simmr_depth_reset(simmr_engine* e, uint64_t* n_positions, uint64_t* n_contigs);
+/* Adds the reads of `reads`.  Only enqueues on the engine's stream — no synchronisation.  Needs start, end, contig and
+ * genome; seq, qual and seq_off are not read and may be NULL here.
+ * SIMMR_ESTATE: no simmr_depth_reset yet, or a genome was staged since (the layout of depth[] is the reset's).
+ * SIMMR_ERANGE: the reads added since the reset would reach 2^31 (the bound keeps every int32_t partial from wrapping).
+ * A read whose genome slot is not tracked, whose contig does not exist or whose window leaves its contig adds nothing and
+ * sets the sticky error word (the check comes before any address is formed from the read). */
+int simmr_depth_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads);
+/* Scans the difference array into depth_device (DEVICE memory, 16-byte aligned, `capacity` uint32_t entries) and
+ * synchronises.  The difference array is left as it is: adds may go on and a later emit sees all of them.
+ * SIMMR_ESTATE: no simmr_depth_reset yet.  SIMMR_ERANGE, nothing written: capacity < n_positions.  SIMMR_EINVAL: the sticky
+ * error word is set (depth_device is then unspecified, and stays so until the next simmr_depth_reset). */
+int simmr_depth_emit(simmr_engine* e, uint32_t* depth_device, uint64_t capacity);
+/* Host arithmetic: *first = where contig `contig` of genome slot `genome_idx` starts in depth[].  SIMMR_ESTATE before a
+ * reset, SIMMR_EINVAL for a slot or contig the reset did not track. */
+int simmr_depth_contig_first(simmr_engine* e, uint32_t genome_idx, uint32_t contig, uint64_t* first);
+/* Summarises a depth[] array of the layout of the last reset (depth_device: n_positions entries in DEVICE memory — what
+ * simmr_depth_emit wrote, or a sum of such arrays) and synchronises.
+ *   rows_host[k], k < the number of tracked contigs (rows_capacity must hold them, else SIMMR_ERANGE): see the struct;
+ *   hist_host[SIMMR_DEPTH_HIST_BINS]: positions by depth, clamped to the last bin; its sum is n_positions;
+ *   window > 0 with win != NULL: the three columns per window.  Contig k has ceil(len / window) windows, the last one
+ *     partial, at first_window(k) onwards; windows never span contigs.  SIMMR_ERANGE (nothing written) if win->capacity is
+ *     smaller than their number, which win->n_windows receives either way.  window must be below 2^30 (SIMMR_EINVAL).
+ * rows_host and hist_host may be NULL to skip them.  window == 0 or win == NULL: no window columns. */
+int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_t window, simmr_depth_contig* rows_host,
+                          uint64_t rows_capacity, uint64_t* hist_host, simmr_depth_windows* win);
+/* HIP-event time (ms) of the last simmr_depth_add's device work plus that of the simmr_depth_emit and the
+ * simmr_depth_summarize after it, if any.  Synchronises the stream. */
+int simmr_last_depth_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

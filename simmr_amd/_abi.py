@@ -143,6 +143,35 @@ class RunStats(C.Structure):
     ]
 
 
+DEPTH_HIST_BINS = 256
+
+
+class DepthContig(C.Structure):
+    """struct simmr_depth_contig (host memory)"""
+    _fields_ = [
+        ("genome", C.c_uint32),
+        ("contig", C.c_uint32),
+        ("first", C.c_uint64),
+        ("len", C.c_uint64),
+        ("covered", C.c_uint64),
+        ("depth_sum", C.c_uint64),
+        ("depth_max", C.c_uint32),
+        ("reserved0", C.c_uint32),
+        ("first_window", C.c_uint64),
+    ]
+
+
+class DepthWindows(C.Structure):
+    """struct simmr_depth_windows (device pointers as raw addresses)"""
+    _fields_ = [
+        ("sum", C.c_void_p),
+        ("covered", C.c_void_p),
+        ("max", C.c_void_p),
+        ("capacity", C.c_uint64),
+        ("n_windows", C.c_uint64),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -195,6 +224,13 @@ SYMBOLS = {
     "simmr_stats_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64, C.c_uint32]),
     "simmr_stats_read": (C.c_int, [C.c_void_p, _P(RunStats)]),
     "simmr_last_stats_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_depth_reset": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_depth_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64]),
+    "simmr_depth_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_depth_contig_first": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, _P(C.c_uint64)]),
+    "simmr_depth_summarize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, _P(DepthContig), C.c_uint64, _P(C.c_uint64),
+                                        _P(DepthWindows)]),
+    "simmr_last_depth_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

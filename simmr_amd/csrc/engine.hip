@@ -27,6 +27,7 @@
 #include "truth_kernels.hip"
 #include "stats_kernels.hip"
 #include "custom_model.hpp"
+#include "engine_internal.hpp"
 
 using namespace simmr;
 
@@ -180,6 +181,12 @@ struct simmr_engine {
   DevBuf st_tab;
   hipEvent_t st_ev[2] = {nullptr, nullptr};  // the last add's begin / end
   bool st_ready = false, st_timed = false;
+
+  // engine_internal.hpp: the simmr_stage_* calls so far, and the state of the library's other translation unit
+  // (depth.hip: coverage depth) with the function that frees it
+  uint64_t staging_epoch = 0;
+  void* ext_slot = nullptr;
+  void (*ext_destroy)(void*) = nullptr;
 
   int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -1043,6 +1050,32 @@ static bool env_clamped(const char* name, unsigned long long max, uint32_t* knob
 // =============================================================================
 // C ABI
 // =============================================================================
+// ---- engine_internal.hpp ------------------------------------------------------------------------------------------
+namespace simmr {
+int eng_device(const simmr_engine* e) { return e->device; }
+hipStream_t eng_stream(const simmr_engine* e) { return e->stream; }
+int eng_cu_count(const simmr_engine* e) { return e->n_cu; }
+uint32_t eng_genome_slots(const simmr_engine* e) { return (uint32_t)e->genomes.size(); }
+uint32_t eng_contig_count(const simmr_engine* e, uint32_t slot) {
+  return slot < e->genomes.size() && e->genomes[slot].staged ? (uint32_t)e->genomes[slot].contigs.size() : 0u;
+}
+uint64_t eng_contig_len(const simmr_engine* e, uint32_t slot, uint32_t contig) { return e->genomes[slot].contigs[contig].len; }
+uint64_t eng_staging_epoch(const simmr_engine* e) { return e->staging_epoch; }
+int eng_fail(simmr_engine* e, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  e->err = buf;
+  return code;
+}
+void** eng_ext_slot(simmr_engine* e, void (*destroy)(void*)) {
+  e->ext_destroy = destroy;
+  return &e->ext_slot;
+}
+}  // namespace simmr
+
 extern "C" {
 
 int simmr_abi_version(void) { return SIMMR_ABI_VERSION; }
@@ -1210,6 +1243,7 @@ void simmr_engine_destroy(simmr_engine* e) {
   (void)hipStreamSynchronize(e->stream);
   comm_release(e);
   (void)hipDeviceSynchronize();
+  if (e->ext_slot && e->ext_destroy) e->ext_destroy(e->ext_slot);
   if (e->plan_stream) (void)hipStreamDestroy(e->plan_stream);
   if (e->ev_plan_done) (void)hipEventDestroy(e->ev_plan_done);
   for (int i = 0; i < 2; i++) if (e->ev_mark[i]) (void)hipEventDestroy(e->ev_mark[i]);
@@ -1272,6 +1306,7 @@ int simmr_stage_genome(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
                        const uint64_t* contig_size) {
   if (!e) return SIMMR_EINVAL;
   e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
+  e->staging_epoch++;
   if (!contig_ascii || !contig_len || n_contigs == 0) return e->fail(SIMMR_EINVAL, "empty genome");
   HIP_TRY(e, hipSetDevice(e->device));
   if (genome_idx >= e->genomes.size()) e->genomes.resize(genome_idx + 1);
@@ -1313,6 +1348,7 @@ int simmr_stage_fasta(simmr_engine* e, uint32_t genome_idx, uint32_t n_records, 
                       uint32_t* n_staged) {
   if (!e) return SIMMR_EINVAL;
   e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
+  e->staging_epoch++;
   if (!body || !body_len || !base_count || n_records == 0) return e->fail(SIMMR_EINVAL, "empty FASTA");
   HIP_TRY(e, hipSetDevice(e->device));
   if (genome_idx >= e->genomes.size()) e->genomes.resize(genome_idx + 1);
@@ -1394,6 +1430,7 @@ int simmr_stage_synthetic(simmr_engine* e, uint32_t genome_idx, uint32_t n_conti
                           const uint64_t* contig_len, uint64_t splitmix_seed) {
   if (!e) return SIMMR_EINVAL;
   e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
+  e->staging_epoch++;
   if (!contig_len || n_contigs == 0) return e->fail(SIMMR_EINVAL, "empty genome");
   HIP_TRY(e, hipSetDevice(e->device));
   if (genome_idx >= e->genomes.size()) e->genomes.resize(genome_idx + 1);

@@ -413,6 +413,71 @@ class Engine:
         self._check(self.lib.simmr_last_stats_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- coverage depth ---------------------------------------------------------------
+    def depth_reset(self) -> int:
+        """Zeroes the engine's difference array over every genome staged now (simmr_depth_reset); returns n_positions."""
+        n, rows = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.simmr_depth_reset(self._h, C.byref(n), C.byref(rows)))
+        self._depth_positions, self._depth_rows = int(n.value), int(rows.value)
+        return self._depth_positions
+
+    def depth_add(self, reads: Reads):
+        """Adds the windows of `reads` (simmr_depth_add): enqueues only; reads start, end, contig and genome."""
+        pod = reads.pod()
+        self._check(self.lib.simmr_depth_add(self._h, C.byref(pod), reads.n_reads))
+
+    def depth(self):
+        """depth[] of the reads added since the reset as a CUDA uint32 tensor of n_positions entries (simmr_depth_emit)."""
+        torch = _torch()
+        n = self._depth_positions
+        out = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        self._check(self.lib.simmr_depth_emit(self._h, C.c_void_p(out.data_ptr()), n))
+        return out[:n].view(torch.uint32)
+
+    def depth_contig_first(self, genome_idx: int, contig: int) -> int:
+        first = C.c_uint64(0)
+        self._check(self.lib.simmr_depth_contig_first(self._h, int(genome_idx), int(contig), C.byref(first)))
+        return int(first.value)
+
+    def depth_summary(self, window: int = 0, depth=None) -> dict:
+        """Contig rows, depth histogram and (window > 0) the window columns of `depth` (default: self.depth()) as numpy
+        arrays (simmr_depth_summarize): genome, contig, first, len, covered, depth_sum, depth_max, first_window per
+        tracked contig; hist[256]; win_sum, win_covered, win_max per window."""
+        torch = _torch()
+        if depth is None:
+            depth = self.depth()
+        n_rows = self._depth_rows
+        rows = (_abi.DepthContig * max(n_rows, 1))()
+        hist = (C.c_uint64 * _abi.DEPTH_HIST_BINS)()
+        win = _abi.DepthWindows(None, None, None, 0, 0)
+        cols = None
+        for _ in range(2):  # win.capacity too small: size the columns from what the call reports and call again
+            rc = self.lib.simmr_depth_summarize(self._h, C.c_void_p(depth.data_ptr()), int(window), rows, len(rows), hist,
+                                                C.byref(win) if window else None)
+            if not (rc == _abi.ERANGE and window and win.capacity < win.n_windows):
+                break
+            n = int(win.n_windows)
+            cols = (torch.empty(n, dtype=torch.int64, device=self.device), torch.empty(n, dtype=torch.int32, device=self.device),
+                    torch.empty(n, dtype=torch.int32, device=self.device))
+            win = _abi.DepthWindows(cols[0].data_ptr(), cols[1].data_ptr(), cols[2].data_ptr(), n, 0)
+        self._check(rc)
+        n = n_rows
+        out = {name: np.array([getattr(rows[k], name) for k in range(n)], dtype=np.uint32 if name in ("genome", "contig", "depth_max") else np.uint64)
+               for name in ("genome", "contig", "first", "len", "covered", "depth_sum", "depth_max", "first_window")}
+        out["hist"] = np.array(list(hist), dtype=np.uint64)
+        if window:
+            m = int(win.n_windows)
+            empty = m == 0 or cols is None
+            out["win_sum"] = np.zeros(0, np.uint64) if empty else cols[0][:m].cpu().numpy().astype(np.uint64)
+            out["win_covered"] = np.zeros(0, np.uint32) if empty else cols[1][:m].cpu().numpy().astype(np.uint32)
+            out["win_max"] = np.zeros(0, np.uint32) if empty else cols[2][:m].cpu().numpy().astype(np.uint32)
+        return out
+
+    def last_depth_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_depth_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- counters / timing --------------------------------------------------------
     def counters(self) -> np.ndarray:
         host = (C.c_uint64 * _abi.N_COUNTERS)()

@@ -352,6 +352,67 @@ bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::
   return ok;
 }
 
+// --------------------------------------------------------------- coverage depth
+static bool replace_file(const std::string& text, const std::string& output, std::string* err) {
+  FILE* f = fopen(output.c_str(), "wb");
+  if (!f) { *err = std::string("cannot open ") + output; return false; }
+  bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  if (fclose(f) != 0) ok = false;
+  if (!ok) *err = "short write to " + output;
+  return ok;
+}
+// genome id and sequence id of a row, or nullptr with *err set
+static const Seq* depth_row_names(const std::vector<Genome>& genomes, const simmr_depth_contig& r, std::string* err) {
+  if (r.genome >= genomes.size() || r.contig >= genomes[r.genome].sequence.size()) {
+    *err = "a depth row names a genome or sequence the run does not have";
+    return nullptr;
+  }
+  return &genomes[r.genome].sequence[r.contig];
+}
+
+bool write_depth_tsv(const std::vector<Genome>& genomes, const simmr_depth_contig* rows, uint64_t n_rows, const std::string& output,
+                     std::string* err) {
+  std::string text = "genome_id\tsequence_id\tlength\tcovered\tdepth_sum\tdepth_max\n";
+  char buf[128];
+  for (uint64_t k = 0; k < n_rows; k++) {
+    const Seq* s = depth_row_names(genomes, rows[k], err);
+    if (!s) return false;
+    text += genomes[rows[k].genome].uuid; text += '\t'; text += s->id;
+    snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\t%u\n", (unsigned long long)rows[k].len, (unsigned long long)rows[k].covered,
+             (unsigned long long)rows[k].depth_sum, rows[k].depth_max);
+    text += buf;
+  }
+  return replace_file(text, output, err);
+}
+
+bool write_depth_track_tsv(const std::vector<Genome>& genomes, const simmr_depth_contig* rows, uint64_t n_rows, uint32_t window,
+                           const uint64_t* win_sum, const uint32_t* win_covered, const uint32_t* win_max, const std::string& output,
+                           std::string* err) {
+  if (window == 0) { *err = "a depth track needs a window of at least one position"; return false; }
+  FILE* f = fopen(output.c_str(), "wb");
+  if (!f) { *err = std::string("cannot open ") + output; return false; }
+  std::string text = "genome_id\tsequence_id\tstart\tend\tdepth_sum\tcovered\tdepth_max\n";
+  char buf[160];
+  bool ok = true;
+  for (uint64_t k = 0; k < n_rows && ok; k++) {
+    const Seq* s = depth_row_names(genomes, rows[k], err);
+    if (!s) { ok = false; break; }
+    const std::string head = genomes[rows[k].genome].uuid + "\t" + s->id;
+    uint64_t w = rows[k].first_window;
+    for (uint64_t x = 0; x < rows[k].len && ok; x += window, w++) {
+      text += head;
+      snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\t%u\t%u\n", (unsigned long long)x, (unsigned long long)std::min<uint64_t>(x + window, rows[k].len),
+               (unsigned long long)win_sum[w], win_covered[w], win_max[w]);
+      text += buf;
+      if (text.size() >= (1u << 20)) { ok = fwrite(text.data(), 1, text.size(), f) == text.size(); text.clear(); }
+    }
+  }
+  if (ok && !text.empty()) ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  if (fclose(f) != 0) ok = false;
+  if (!ok && err->empty()) *err = "short write to " + output;
+  return ok;
+}
+
 // --------------------------------------------------------------- error profiles
 
 static simmr_error_profile zero_pod() {
@@ -472,7 +533,12 @@ std::string usage() {
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
-         "                            not with --devices\n";
+         "                            not with --devices\n"
+         "            --depth <FILE>  coverage the run put on every sequence, as a TSV: genome_id sequence_id length covered depth_sum depth_max\n"
+         "                            (read depth, mates counted separately; counted on the device from every range of the run;\n"
+         "                             combines with --truth and --stats; not with --devices)\n"
+         "            --depth-track <FILE>  the same per window: genome_id sequence_id start end depth_sum covered depth_max\n"
+         "            --depth-window <W>    positions per window of --depth-track [default: 1000]\n";
 }
 
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
@@ -534,6 +600,9 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--host-normalize") a->host_normalize = true;
     else if (arg == "--truth") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--truth'"; return false; } a->truth = v; }
     else if (arg == "--stats") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--stats'"; return false; } a->stats = v; }
+    else if (arg == "--depth") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--depth'"; return false; } a->depth = v; }
+    else if (arg == "--depth-track") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--depth-track'"; return false; } a->depth_track = v; }
+    else if (arg == "--depth-window") { if (!need(&v) || !parse_u64(v, (1u << 30) - 1, &u) || u == 0) { *err = "invalid value for --depth-window (1 .. 2^30 - 1)"; return false; } a->depth_window = (uint32_t)u; }
     else if (arg == "--device-chunk-reads") { if (!need(&v) || !parse_u64(v, UINT64_MAX, &u) || u == 0) { *err = "invalid value for --device-chunk-reads"; return false; } a->device_chunk_reads = u; }
     else if (arg == "--devices") {
       if (!need(&v)) return false;
@@ -704,6 +773,22 @@ char* simmr_host_stats_tsv(const simmr_run_stats* st, const char* path) {
   std::string err;
   if (!st || !path) return dup_str("ERR\tNULL argument");
   if (!write_stats_tsv(*st, path, &err)) return dup_str("ERR\t" + err);
+  return dup_str("OK");
+}
+// The two depth TSVs of write_depth_tsv / write_depth_track_tsv for rows and window columns in host memory; names in the
+// shape of simmr_host_truth_tsv.  track_path may be NULL (then window and win_* are not read).  Returns "OK", or "ERR\t..." .
+char* simmr_host_depth_tsv(const simmr_depth_contig* rows, uint64_t n_rows, uint32_t n_genomes, const char* const* genome_id,
+                           const uint32_t* n_contigs, const char* const* sequence_id, const char* path, uint32_t window,
+                           const uint64_t* win_sum, const uint32_t* win_covered, const uint32_t* win_max, const char* track_path) {
+  std::vector<Genome> genomes(n_genomes);
+  size_t at = 0;
+  for (uint32_t g = 0; g < n_genomes; g++) {
+    genomes[g].uuid = genome_id[g];
+    for (uint32_t c = 0; c < n_contigs[g]; c++) { Seq s; s.id = sequence_id[at++]; genomes[g].sequence.push_back(std::move(s)); }
+  }
+  std::string err;
+  if (path && !write_depth_tsv(genomes, rows, n_rows, path, &err)) return dup_str("ERR\t" + err);
+  if (track_path && !write_depth_track_tsv(genomes, rows, n_rows, window, win_sum, win_covered, win_max, track_path, &err)) return dup_str("ERR\t" + err);
   return dup_str("OK");
 }
 char* simmr_host_parse_genome_file(const char* path) {

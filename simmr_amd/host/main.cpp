@@ -96,6 +96,40 @@ static bool device_truth(simmr_engine* eng, const simmr_reads_out* reads, uint64
   return true;
 }
 
+// `--depth` / `--depth-track`: depth[] of every range added so far (simmr_depth_emit), its contig rows and windows
+// (simmr_depth_summarize), and the two files.
+static bool write_depth_files(simmr_engine* eng, const CliArgs& args, const std::vector<Genome>& genomes, uint64_t n_positions,
+                              uint64_t n_contigs, std::string* err) {
+  DeviceOut mem;  // (its allocation list only)
+  uint32_t* depth = nullptr;
+  if (!mem.alloc(&depth, std::max<uint64_t>(n_positions, 1))) { *err = "device allocation failed"; return false; }
+  if (simmr_depth_emit(eng, depth, n_positions) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  std::vector<simmr_depth_contig> rows(std::max<uint64_t>(n_contigs, 1));
+  const bool track = !args.depth_track.empty();
+  simmr_depth_windows win{};
+  if (track) {  // a call without room answers SIMMR_ERANGE and says how many windows the staged lengths make
+    const int rc = simmr_depth_summarize(eng, depth, args.depth_window, nullptr, 0, nullptr, &win);
+    if (rc != SIMMR_OK && rc != SIMMR_ERANGE) { *err = simmr_last_error(eng); return false; }
+    win.capacity = win.n_windows;
+    const uint64_t n = std::max<uint64_t>(win.capacity, 1);
+    if (!(mem.alloc(&win.sum, n) && mem.alloc(&win.covered, n) && mem.alloc(&win.max, n))) { *err = "device allocation failed"; return false; }
+  }
+  if (simmr_depth_summarize(eng, depth, track ? args.depth_window : 0u, rows.data(), rows.size(), nullptr, track ? &win : nullptr) != SIMMR_OK) {
+    *err = simmr_last_error(eng);
+    return false;
+  }
+  if (!args.depth.empty() && !write_depth_tsv(genomes, rows.data(), n_contigs, args.depth, err)) return false;
+  if (!track) return true;
+  std::vector<uint64_t> ws(win.n_windows);
+  std::vector<uint32_t> wc(win.n_windows), wm(win.n_windows);
+  auto cp = [](void* d, const void* s, size_t n) { return n == 0 || hipMemcpy(d, s, n, hipMemcpyDeviceToHost) == hipSuccess; };
+  if (!(cp(ws.data(), win.sum, ws.size() * 8) && cp(wc.data(), win.covered, wc.size() * 4) && cp(wm.data(), win.max, wm.size() * 4))) {
+    *err = "copy back failed";
+    return false;
+  }
+  return write_depth_track_tsv(genomes, rows.data(), n_contigs, args.depth_window, ws.data(), wc.data(), wm.data(), args.depth_track, err);
+}
+
 // ---- output of one planned range ------------------------------------------------------------------------------------
 // A run is generated range by range of its units (pairs / long reads): the reference holds every read of a run in RAM
 // before it writes (main.rs:180-206, readme.md:219-220); here a range is what fits the device next to the reference
@@ -208,8 +242,9 @@ static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<G
   NameTables nt(genomes, sc.g0, sc.g1);
   std::string err;
   // --truth reads the columns: the run takes the column route (the same bytes, include/simmr_hip.h)
-  // (--stats likewise)
-  bool use_device_text = !args.host_fastq && args.truth.empty() && args.stats.empty();
+  // (--stats, --depth and --depth-track likewise)
+  const bool want_depth = !args.depth.empty() || !args.depth_track.empty();
+  bool use_device_text = !args.host_fastq && args.truth.empty() && args.stats.empty() && !want_depth;
   uint64_t text_bytes = 0, n_ranges = 0;
   TextDrain drain;
   if (use_device_text && !drain.open(args.output, &err)) return die(err);
@@ -248,6 +283,7 @@ static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<G
       if (sc.emit(eng, sc.id_base, &d.o) != SIMMR_OK) return die(simmr_last_error(eng));
       // every range adds to the run's tables (enqueued behind the emit; the copies below wait for the device)
       if (!args.stats.empty() && simmr_stats_add(eng, &d.o, pi.n_reads, sc.paired ? 2u : 1u) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
+      if (want_depth && simmr_depth_add(eng, &d.o, pi.n_reads) != SIMMR_OK) return die(std::string("--depth: ") + simmr_last_error(eng));
       HostTruth truth;
       if (!args.truth.empty() && !device_truth(eng, &d.o, pi.n_reads, &truth, &err)) return die("--truth: " + err);
       HostReads h;
@@ -442,6 +478,7 @@ static int run_main(int argc, char** argv) {
 
   if (!args.truth.empty() && !args.devices.empty()) return die("--truth does not combine with --devices: use --device");
   if (!args.stats.empty() && !args.devices.empty()) return die("--stats does not combine with --devices: use --device");
+  if ((!args.depth.empty() || !args.depth_track.empty()) && !args.devices.empty()) return die("--depth does not combine with --devices: use --device");
   std::unique_ptr<ErrorProfile> eprofile = determine_error_profile(args, &err);  // main.rs:27
   if (!eprofile) return die(err);
   // main.rs:30-33
@@ -576,6 +613,13 @@ static int run_main(int argc, char** argv) {
     if (simmr_stats_reset(eng) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
   }
 
+  const bool want_depth = !args.depth.empty() || !args.depth_track.empty();
+  uint64_t depth_positions = 0, depth_contigs = 0;
+  if (want_depth) {  // the genomes are staged: depth[] covers all of them
+    for (const std::string& f : {args.depth, args.depth_track}) if (!f.empty() && is_regular_file(f)) remove(f.c_str());
+    if (simmr_depth_reset(eng, &depth_positions, &depth_contigs) != SIMMR_OK) return die(std::string("--depth: ") + simmr_last_error(eng));
+  }
+
   simmr_error_profile pod = eprofile->pod();
   if (args.rng_philox) {  // (extension) the counter mode, for the profiles that draw per base from a parametric law
     // (a custom model draws base by base only in the k-mer splice of its long-read path: include/simmr_hip.h)
@@ -666,6 +710,7 @@ static int run_main(int argc, char** argv) {
     if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
     if (!write_stats_tsv(*st, args.stats, &err)) return die("--stats: " + err);
   }
+  if (want_depth && !write_depth_files(eng, args, genomes, depth_positions, depth_contigs, &err)) return die("--depth: " + err);
 
   // main.rs:213-258
   std::vector<MetadataRow> rows;

@@ -115,6 +115,20 @@ bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads,
 // expected class, j = written class; the histograms and quality tables: i).  Replaces `output`.
 bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::string* err);
 
+// ---------------------------------------------------------------- coverage depth (no reference counterpart)
+// `simmr-hip --depth FILE`: a line of column names, then one tab-separated line per contig, in the order of depth[]:
+//   genome_id  sequence_id  length  covered  depth_sum  depth_max
+// from the rows of simmr_depth_summarize; rows[k].genome indexes `genomes`.  Every column is an integer.  Replaces `output`.
+bool write_depth_tsv(const std::vector<Genome>& genomes, const simmr_depth_contig* rows, uint64_t n_rows, const std::string& output,
+                     std::string* err);
+// `simmr-hip --depth-track FILE`: a line of column names, then one line per window of `window` positions:
+//   genome_id  sequence_id  start  end  depth_sum  covered  depth_max
+// start / end 0-based and half-open inside the sequence (a sequence's last window is partial); win_* are HOST copies of the
+// columns of simmr_depth_windows, rows[k].first_window the index of contig k's first window.  Replaces `output`.
+bool write_depth_track_tsv(const std::vector<Genome>& genomes, const simmr_depth_contig* rows, uint64_t n_rows, uint32_t window,
+                           const uint64_t* win_sum, const uint32_t* win_covered, const uint32_t* win_max, const std::string& output,
+                           std::string* err);
+
 // ------------------------------------------------------- error_profiles/*.rs
 class ErrorProfile {  // error_profiles/base.rs:6-32 (the per-read methods run on the device)
  public:
@@ -220,6 +234,9 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   bool host_fastq = false;  // --host-fastq: frame the FASTQ on the host instead of the device
   std::string truth;  // --truth FILE: per-read mismatch counts and edit lists (simmr_truth_plan / simmr_truth_emit) as a TSV
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
+  std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
+  std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions
+  uint32_t depth_window = 1000;  // --depth-window W
   uint64_t device_chunk_reads = 0;  // --device-chunk-reads: reads generated per device pass (0: what fits the free device memory)
   std::optional<std::pair<float, float>> gamma;  // --gamma mean,std
   bool uniform_start = false;                    // --uniform-start (SIMMR_START_UNIFORM)

@@ -19,10 +19,11 @@ FIELDS = {"VGPRs": "vgpr", "AGPRs": "agpr", "TotalSGPRs": "sgpr", "ScratchSize [
           "SGPRs Spill": "sgpr_spill"}
 
 
-def collect(extra_flags=()):
-    """[{name (demangled), vgpr, scratch, occupancy, lds, ...}] for engine.hip compiled with the Makefile's flags."""
+def collect(extra_flags=(), source="engine.hip"):
+    """[{name (demangled), vgpr, scratch, occupancy, lds, ...}] for one translation unit of the library (engine.hip, or
+    depth.hip: the coverage-depth kernels have a budget of their own) compiled with the Makefile's flags."""
     flags = subprocess.run(["make", "-s", "-C", str(CSRC), "print-flags"], capture_output=True, text=True, check=True).stdout.split()
-    cmd = flags + list(extra_flags) + ["-c", "engine.hip", "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
+    cmd = flags + list(extra_flags) + ["-c", source, "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"]
     p = subprocess.run(cmd, cwd=str(CSRC), capture_output=True, text=True)
     if p.returncode != 0:
         raise RuntimeError("compile failed:\n" + p.stderr[-4000:])
