@@ -211,14 +211,11 @@ std::string format_f64_display(double v) {
 bool write_metadata(const std::vector<MetadataRow>& rows, const std::string& output, std::string* err) {
   // files.rs:100-134
   remove(output.c_str());
-  FILE* f = fopen(output.c_str(), "wb");
-  if (!f) { *err = std::string("cannot open ") + output; return false; }
-  fputs("genome_id\tfilepath\tnum_reads\tabundance\n", f);
+  OutFile out(output, false);
+  out.append("genome_id\tfilepath\tnum_reads\tabundance\n");
   for (const MetadataRow& r : rows)
-    fprintf(f, "%s\t%s\t%llu\t%s\n", r.genome_id.c_str(), r.filepath.c_str(), (unsigned long long)r.num_reads,
-            format_f64_display(r.abundance).c_str());
-  fclose(f);
-  return true;
+    out.append(r.genome_id + "\t" + r.filepath + "\t" + std::to_string(r.num_reads) + "\t" + format_f64_display(r.abundance) + "\n");
+  return out.close(err);
 }
 
 // ------------------------------------------------------------------- fastq.rs
@@ -250,10 +247,7 @@ std::string format_header(const std::string& header_format, const std::string& g
 bool write_to_fastq(const std::string& genome_uuid, const Genome& genome, const HostReads& reads,
                     uint64_t first, uint64_t count, const std::string& output,
                     const std::string& header_format, bool append, std::string* err) {
-  FILE* f = fopen(output.c_str(), append ? "ab" : "wb");
-  if (!f) { *err = std::string("cannot open ") + output; return false; }
-  std::vector<char> buf(1 << 20);
-  setvbuf(f, buf.data(), _IOFBF, buf.size());
+  OutFile out(output, append);
   for (uint64_t r = first; r < first + count; r++) {
     const uint64_t o = reads.seq_off[r];
     const bool rc = (reads.flags[r] & SIMMR_FLAG_REVCOMP) != 0;
@@ -263,15 +257,14 @@ bool write_to_fastq(const std::string& genome_uuid, const Genome& genome, const 
     const std::string& sid = genome.sequence[reads.contig[r]].id;
     std::string h = format_header(header_format, genome_uuid, reads.read_id[r], sid, reads.start[r],
                                   reads.end[r], rc, pair);
-    fwrite(h.data(), 1, h.size(), f);
-    fputc('\n', f);
-    fwrite(reads.seq.data() + o, 1, len, f);
-    fputs("\n+\n", f);
-    fwrite(reads.qual.data() + o, 1, len, f);  // util::encode_quality_scores: +33, applied on the device
-    fputc('\n', f);
+    h += '\n';
+    out.append(h);
+    out.append(reads.seq.data() + o, len);
+    out.append("\n+\n", 3);
+    out.append(reads.qual.data() + o, len);  // util::encode_quality_scores: +33, applied on the device
+    out.append("\n", 1);
   }
-  fclose(f);
-  return true;
+  return out.close(err);
 }
 
 // --------------------------------------------------------------- ground truth per read
@@ -299,27 +292,22 @@ static void truth_line(std::string* out, uint64_t r, bool paired, uint32_t read_
 
 bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads, const HostTruth& t, uint32_t qual_offset,
                      const std::string& output, bool with_header, std::string* err) {
-  FILE* f = fopen(output.c_str(), "ab");
-  if (!f) { *err = std::string("cannot open ") + output; return false; }
-  std::string text;
-  if (with_header) text += TRUTH_TSV_HEADER;
-  bool ok = true;
-  for (uint64_t r = 0; r < reads.n_reads && ok; r++) {
+  OutFile out(output, true);
+  if (with_header) out.append(TRUTH_TSV_HEADER);
+  std::string line;
+  for (uint64_t r = 0; r < reads.n_reads && out.ok(); r++) {
     if (reads.genome[r] >= genomes.size() || reads.contig[r] >= genomes[reads.genome[r]].sequence.size()) {
       *err = "read " + std::to_string(r) + " names a genome or sequence the run does not have";
-      ok = false;
-      break;
+      return false;
     }
     const Genome& g = genomes[reads.genome[r]];
-    truth_line(&text, r, reads.paired, reads.read_id[r], g.uuid.c_str(), g.sequence[reads.contig[r]].id.c_str(), reads.start[r],
+    line.clear();
+    truth_line(&line, r, reads.paired, reads.read_id[r], g.uuid.c_str(), g.sequence[reads.contig[r]].id.c_str(), reads.start[r],
                reads.end[r], reads.flags[r], t.nm[r], t.edit_off.data(), t.edit_pos.data(), t.edit_ref.data(), t.edit_alt.data(),
                t.edit_qual.data(), qual_offset);
-    if (text.size() >= (1u << 20)) { ok = fwrite(text.data(), 1, text.size(), f) == text.size(); text.clear(); }
+    out.append(line);
   }
-  if (ok && !text.empty()) ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-  if (fclose(f) != 0) ok = false;
-  if (!ok && err->empty()) *err = "short write to " + output;
-  return ok;
+  return out.close(err);
 }
 
 // --------------------------------------------------------------- run statistics
@@ -344,23 +332,12 @@ bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::
   for (int m = 0; m < 2; m++) for (int j = 0; j < (int)SIMMR_STATS_CYCLES; j++) row("cycle_qsum", m, j, -1, st.cycle_qsum[m][j]);
   for (int m = 0; m < 2; m++) for (int j = 0; j < (int)SIMMR_STATS_CYCLES; j++) row("cycle_mismatch", m, j, -1, st.cycle_mismatch[m][j]);
   for (int m = 0; m < 2; m++) for (int j = 0; j < (int)SIMMR_STATS_CYCLES; j++) for (int c = 0; c < 5; c++) row("cycle_base", m, j, c, st.cycle_base[m][j][c]);
-  FILE* f = fopen(output.c_str(), "wb");
-  if (!f) { *err = std::string("cannot open ") + output; return false; }
-  bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-  if (fclose(f) != 0) ok = false;
-  if (!ok) *err = "short write to " + output;
-  return ok;
+  OutFile out(output, false);
+  out.append(text);
+  return out.close(err);
 }
 
 // --------------------------------------------------------------- coverage depth
-static bool replace_file(const std::string& text, const std::string& output, std::string* err) {
-  FILE* f = fopen(output.c_str(), "wb");
-  if (!f) { *err = std::string("cannot open ") + output; return false; }
-  bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-  if (fclose(f) != 0) ok = false;
-  if (!ok) *err = "short write to " + output;
-  return ok;
-}
 // genome id and sequence id of a row, or nullptr with *err set
 static const Seq* depth_row_names(const std::vector<Genome>& genomes, const simmr_depth_contig& r, std::string* err) {
   if (r.genome >= genomes.size() || r.contig >= genomes[r.genome].sequence.size()) {
@@ -382,35 +359,31 @@ bool write_depth_tsv(const std::vector<Genome>& genomes, const simmr_depth_conti
              (unsigned long long)rows[k].depth_sum, rows[k].depth_max);
     text += buf;
   }
-  return replace_file(text, output, err);
+  OutFile out(output, false);  // (opened once every row is known to be good: a refused row leaves the old file)
+  out.append(text);
+  return out.close(err);
 }
 
 bool write_depth_track_tsv(const std::vector<Genome>& genomes, const simmr_depth_contig* rows, uint64_t n_rows, uint32_t window,
                            const uint64_t* win_sum, const uint32_t* win_covered, const uint32_t* win_max, const std::string& output,
                            std::string* err) {
   if (window == 0) { *err = "a depth track needs a window of at least one position"; return false; }
-  FILE* f = fopen(output.c_str(), "wb");
-  if (!f) { *err = std::string("cannot open ") + output; return false; }
-  std::string text = "genome_id\tsequence_id\tstart\tend\tdepth_sum\tcovered\tdepth_max\n";
+  OutFile out(output, false);
+  out.append("genome_id\tsequence_id\tstart\tend\tdepth_sum\tcovered\tdepth_max\n");
   char buf[160];
-  bool ok = true;
-  for (uint64_t k = 0; k < n_rows && ok; k++) {
+  for (uint64_t k = 0; k < n_rows; k++) {
     const Seq* s = depth_row_names(genomes, rows[k], err);
-    if (!s) { ok = false; break; }
+    if (!s) return false;
     const std::string head = genomes[rows[k].genome].uuid + "\t" + s->id;
     uint64_t w = rows[k].first_window;
-    for (uint64_t x = 0; x < rows[k].len && ok; x += window, w++) {
-      text += head;
+    for (uint64_t x = 0; x < rows[k].len && out.ok(); x += window, w++) {
+      out.append(head);
       snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\t%u\t%u\n", (unsigned long long)x, (unsigned long long)std::min<uint64_t>(x + window, rows[k].len),
                (unsigned long long)win_sum[w], win_covered[w], win_max[w]);
-      text += buf;
-      if (text.size() >= (1u << 20)) { ok = fwrite(text.data(), 1, text.size(), f) == text.size(); text.clear(); }
+      out.append(buf, strlen(buf));
     }
   }
-  if (ok && !text.empty()) ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-  if (fclose(f) != 0) ok = false;
-  if (!ok && err->empty()) *err = "short write to " + output;
-  return ok;
+  return out.close(err);
 }
 
 // --------------------------------------------------------------- error profiles
@@ -463,7 +436,7 @@ simmr_error_profile CustomShortErrorProfile::pod() const {
   p.kind = SIMMR_CUSTOM;
   p.custom_model = model.data();
   p.custom_model_bytes = model.size();
-  p.length_mode = length_mode;          // long-read models only (extensions --per-read-lengths / --uniform-start)
+  p.length_mode = length_mode;          // (set for long-read models only: determine_error_profile)
   p.long_start_mode = long_start_mode;
   return p;
 }
@@ -565,15 +538,25 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     };
     std::string v;
     uint64_t u;
+    // a value in [lo, max] into u; whatever is wrong with it, a missing value included, is the one message
+    auto uint = [&](uint64_t lo, uint64_t max, const char* hint = "") -> bool {
+      if (need(&v) && parse_u64(v, max, &u) && u >= lo) return true;
+      *err = "invalid value for " + arg + hint;
+      return false;
+    };
+    auto file = [&](std::string* dst) -> bool {  // a file name that is not empty
+      if (need(dst) && dst->empty()) *err = "a file name is required for '" + arg + "'";
+      return err->empty();
+    };
     if (arg == "--help" || arg == "-h") { *help = true; return true; }
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
     else if (arg == "--genome-file") { if (!need(&v)) return false; a->genome_file = v; }
     else if (arg == "--output") { if (!need(&v)) return false; a->output = v; }
-    else if (arg == "--num-reads") { if (!need(&v) || !parse_u64(v, UINT64_MAX, &u)) { *err = "invalid value for --num-reads"; return false; } a->num_reads = u; }
-    else if (arg == "--read-length") { if (!need(&v) || !parse_u64(v, 65535, &u)) { *err = "invalid value for --read-length"; return false; } a->read_length = (uint16_t)u; }
+    else if (arg == "--num-reads") { if (!uint(0, UINT64_MAX)) return false; a->num_reads = u; }
+    else if (arg == "--read-length") { if (!uint(0, 65535)) return false; a->read_length = (uint16_t)u; }
     else if (arg == "--read-length-std") { if (!need(&v)) return false; a->read_length_std = atof(v.c_str()); }
-    else if (arg == "--insert-size") { if (!need(&v) || !parse_u64(v, 65535, &u)) { *err = "invalid value for --insert-size"; return false; } a->insert_size = (uint16_t)u; }
-    else if (arg == "--mean-phred-score") { if (!need(&v) || !parse_u64(v, 255, &u)) { *err = "invalid value for --mean-phred-score"; return false; } a->mean_phred_score = (uint8_t)u; }
+    else if (arg == "--insert-size") { if (!uint(0, 65535)) return false; a->insert_size = (uint16_t)u; }
+    else if (arg == "--mean-phred-score") { if (!uint(0, 255)) return false; a->mean_phred_score = (uint8_t)u; }
     else if (arg == "--error-profile") {
       if (!need(&v)) return false;
       if (v == "minimal-short") a->error_profile = ErrorProfileKind::MinimalShort;
@@ -591,19 +574,19 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
       else { *err = "invalid value '" + v + "' for '--abundance-profile'"; return false; }
     }
     else if (arg == "--custom-profile") { if (!need(&v)) return false; a->custom_profile = v; }
-    else if (arg == "--with-ani") { if (!need(&v) || !parse_u64(v, 255, &u)) { *err = "invalid value for --with-ani"; return false; } a->with_ani = (uint8_t)u; }
+    else if (arg == "--with-ani") { if (!uint(0, 255)) return false; a->with_ani = (uint8_t)u; }
     else if (arg == "--read-header-format") { if (!need(&v)) return false; a->read_header_format = v; }
-    else if (arg == "--seed") { if (!need(&v) || !parse_u64(v, UINT64_MAX, &u)) { *err = "invalid value for --seed"; return false; } a->seed = u; }
+    else if (arg == "--seed") { if (!uint(0, UINT64_MAX)) return false; a->seed = u; }
     else if (arg == "--size-adjusted") a->size_adjusted = true;
     else if (arg == "--contiguous") a->contiguous = true;
     else if (arg == "--host-fastq") a->host_fastq = true;
     else if (arg == "--host-normalize") a->host_normalize = true;
-    else if (arg == "--truth") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--truth'"; return false; } a->truth = v; }
-    else if (arg == "--stats") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--stats'"; return false; } a->stats = v; }
-    else if (arg == "--depth") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--depth'"; return false; } a->depth = v; }
-    else if (arg == "--depth-track") { if (!need(&v) || v.empty()) { if (err->empty()) *err = "a file name is required for '--depth-track'"; return false; } a->depth_track = v; }
-    else if (arg == "--depth-window") { if (!need(&v) || !parse_u64(v, (1u << 30) - 1, &u) || u == 0) { *err = "invalid value for --depth-window (1 .. 2^30 - 1)"; return false; } a->depth_window = (uint32_t)u; }
-    else if (arg == "--device-chunk-reads") { if (!need(&v) || !parse_u64(v, UINT64_MAX, &u) || u == 0) { *err = "invalid value for --device-chunk-reads"; return false; } a->device_chunk_reads = u; }
+    else if (arg == "--truth") { if (!file(&a->truth)) return false; }
+    else if (arg == "--stats") { if (!file(&a->stats)) return false; }
+    else if (arg == "--depth") { if (!file(&a->depth)) return false; }
+    else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
+    else if (arg == "--depth-window") { if (!uint(1, (1u << 30) - 1, " (1 .. 2^30 - 1)")) return false; a->depth_window = (uint32_t)u; }
+    else if (arg == "--device-chunk-reads") { if (!uint(1, UINT64_MAX)) return false; a->device_chunk_reads = u; }
     else if (arg == "--devices") {
       if (!need(&v)) return false;
       a->devices.clear();
@@ -616,7 +599,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
       }
       if (a->devices.empty() || a->devices.size() > 64) { *err = "invalid value for --devices"; return false; }
     }
-    else if (arg == "--device") { if (!need(&v) || !parse_u64(v, 1023, &u)) { *err = "invalid value for --device"; return false; } a->device = (int)u; }
+    else if (arg == "--device") { if (!uint(0, 1023)) return false; a->device = (int)u; }
     else if (arg == "--gamma") {
       if (!need(&v)) return false;
       float m = 0, s = 0;
@@ -642,6 +625,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
 }
 
 std::unique_ptr<ErrorProfile> determine_error_profile(const CliArgs& args, std::string* err) {
+  std::unique_ptr<ErrorProfile> out;
   switch (args.error_profile) {
     case ErrorProfileKind::PerfectShort: {  // cli.rs:231-234
       auto p = std::make_unique<PerfectShortErrorProfile>();
@@ -654,22 +638,16 @@ std::unique_ptr<ErrorProfile> determine_error_profile(const CliArgs& args, std::
       p->mean_phred_score = args.mean_phred_score; p->insert_size_std = 75.0; p->read_length_std = 15.0;
       return p;
     }
-    case ErrorProfileKind::PerfectLong: {  // cli.rs:283
-      auto p = std::make_unique<PerfectLongErrorProfile>();
-      if (args.gamma) { p->gamma_mean = args.gamma->first; p->gamma_std = args.gamma->second; }
-      if (args.per_read_lengths) p->length_mode = SIMMR_LEN_PER_READ;
-      if (args.uniform_start) p->long_start_mode = SIMMR_START_UNIFORM;
-      return p;
-    }
+    case ErrorProfileKind::PerfectLong:    // cli.rs:283
     case ErrorProfileKind::MinimalLong: {  // cli.rs:284-297
-      auto p = std::make_unique<MinimalLongErrorProfile>();
-      p->mean_phred_score = args.mean_phred_score;
-      p->read_length = args.read_length < 400 ? 20000 : args.read_length;
-      p->read_length_std = args.read_length < 400 ? args.read_length_std : 5000.0;
+      const bool perfect = args.error_profile == ErrorProfileKind::PerfectLong;
+      std::unique_ptr<MinimalLongErrorProfile> p = perfect ? std::make_unique<PerfectLongErrorProfile>() : std::make_unique<MinimalLongErrorProfile>();
+      if (!perfect) p->mean_phred_score = args.mean_phred_score;
+      if (!perfect) p->read_length = args.read_length < 400 ? 20000 : args.read_length;
+      if (!perfect) p->read_length_std = args.read_length < 400 ? args.read_length_std : 5000.0;
       if (args.gamma) { p->gamma_mean = args.gamma->first; p->gamma_std = args.gamma->second; }
-      if (args.per_read_lengths) p->length_mode = SIMMR_LEN_PER_READ;
-      if (args.uniform_start) p->long_start_mode = SIMMR_START_UNIFORM;
-      return p;
+      out = std::move(p);
+      break;
     }
     case ErrorProfileKind::CustomLong:    // extension: the same object, driven through simulate_long_reads
     case ErrorProfileKind::CustomShort: {  // cli.rs:255-272
@@ -677,15 +655,16 @@ std::unique_ptr<ErrorProfile> determine_error_profile(const CliArgs& args, std::
       std::string e2;
       auto p = CustomShortErrorProfile::from_path(*args.custom_profile, &e2);
       if (!p) { *err = "Error parsing custom error profile: " + e2; return nullptr; }
-      if (args.error_profile == ErrorProfileKind::CustomLong) {
-        if (args.per_read_lengths) p->length_mode = SIMMR_LEN_PER_READ;
-        if (args.uniform_start) p->long_start_mode = SIMMR_START_UNIFORM;
-      }
-      return p;
+      if (args.error_profile == ErrorProfileKind::CustomShort) return p;
+      out = std::move(p);
+      break;
     }
   }
-  *err = "unknown error profile";
-  return nullptr;
+  if (!out) { *err = "unknown error profile"; return nullptr; }
+  // the long-read kinds: the extensions --per-read-lengths / --uniform-start
+  if (args.per_read_lengths) out->length_mode = SIMMR_LEN_PER_READ;
+  if (args.uniform_start) out->long_start_mode = SIMMR_START_UNIFORM;
+  return out;
 }
 
 std::unique_ptr<AbundanceProfile> determine_abundance_profile(const CliArgs& args,
@@ -720,6 +699,18 @@ static char* dup_str(const std::string& s) {
   return p;
 }
 void simmr_host_free(void* p) { free(p); }
+// genomes that carry names only: genome_id[g] / n_contigs[g] per genome slot, sequence_id flattened genome by genome (the
+// shape of simmr_fastq_names)
+static std::vector<Genome> genomes_from_names(uint32_t n_genomes, const char* const* genome_id, const uint32_t* n_contigs,
+                                              const char* const* sequence_id) {
+  std::vector<Genome> genomes(n_genomes);
+  size_t at = 0;
+  for (uint32_t g = 0; g < n_genomes; g++) {
+    genomes[g].uuid = genome_id[g];
+    for (uint32_t c = 0; c < n_contigs[g]; c++) { Seq s; s.id = sequence_id[at++]; genomes[g].sequence.push_back(std::move(s)); }
+  }
+  return genomes;
+}
 // the PRODUCT's builder of the counter mode's splice tables (csrc/custom_model.hpp: what engine.hip uploads), for the CPU
 // test that enumerates the law the tables encode (the test tree's custom-profile specification tests)
 uint32_t simmr_host_ctr_splice_tables(const uint32_t* alt, const float* w, uint32_t n, uint32_t self_code, int has_self,
@@ -742,19 +733,13 @@ char* simmr_host_load_fasta(const char* path, int contiguous) {
     out += s.id + "\t" + std::to_string(s.size) + "\t" + std::to_string(s.seq.size()) + "\t" + s.seq + "\n";
   return dup_str(out);
 }
-// The truth TSV of write_truth_tsv for columns given as plain arrays: genome_id[g] / n_contigs[g] per genome slot,
-// sequence_id flattened genome by genome (the shape of simmr_fastq_names).  Returns the text, or "ERR\t..." .
+// The truth TSV of write_truth_tsv for columns given as plain arrays, names as for genomes_from_names.  Returns "OK", or "ERR\t..." .
 char* simmr_host_truth_tsv(uint64_t n_reads, int paired, const uint32_t* read_id, const uint32_t* genome, const uint32_t* contig,
                            const uint64_t* start, const uint64_t* end, const uint8_t* flags, const uint32_t* nm,
                            const uint64_t* edit_off, const uint32_t* edit_pos, const uint8_t* edit_ref, const uint8_t* edit_alt,
                            const uint8_t* edit_qual, uint32_t qual_offset, uint32_t n_genomes, const char* const* genome_id,
                            const uint32_t* n_contigs, const char* const* sequence_id, int with_header, const char* path) {
-  std::vector<Genome> genomes(n_genomes);
-  size_t at = 0;
-  for (uint32_t g = 0; g < n_genomes; g++) {
-    genomes[g].uuid = genome_id[g];
-    for (uint32_t c = 0; c < n_contigs[g]; c++) { Seq s; s.id = sequence_id[at++]; genomes[g].sequence.push_back(std::move(s)); }
-  }
+  const std::vector<Genome> genomes = genomes_from_names(n_genomes, genome_id, n_contigs, sequence_id);
   HostReads h;
   h.n_reads = n_reads; h.paired = paired != 0;
   h.read_id.assign(read_id, read_id + n_reads); h.genome.assign(genome, genome + n_reads); h.contig.assign(contig, contig + n_reads);
@@ -780,12 +765,7 @@ char* simmr_host_stats_tsv(const simmr_run_stats* st, const char* path) {
 char* simmr_host_depth_tsv(const simmr_depth_contig* rows, uint64_t n_rows, uint32_t n_genomes, const char* const* genome_id,
                            const uint32_t* n_contigs, const char* const* sequence_id, const char* path, uint32_t window,
                            const uint64_t* win_sum, const uint32_t* win_covered, const uint32_t* win_max, const char* track_path) {
-  std::vector<Genome> genomes(n_genomes);
-  size_t at = 0;
-  for (uint32_t g = 0; g < n_genomes; g++) {
-    genomes[g].uuid = genome_id[g];
-    for (uint32_t c = 0; c < n_contigs[g]; c++) { Seq s; s.id = sequence_id[at++]; genomes[g].sequence.push_back(std::move(s)); }
-  }
+  const std::vector<Genome> genomes = genomes_from_names(n_genomes, genome_id, n_contigs, sequence_id);
   std::string err;
   if (path && !write_depth_tsv(genomes, rows, n_rows, path, &err)) return dup_str("ERR\t" + err);
   if (track_path && !write_depth_track_tsv(genomes, rows, n_rows, window, win_sum, win_covered, win_max, track_path, &err)) return dup_str("ERR\t" + err);

@@ -9,7 +9,6 @@
 
 #include <algorithm>
 #include <condition_variable>
-#include <functional>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -19,16 +18,17 @@
 
 using namespace simmr_host;
 
-static void info(const char* msg) { fprintf(stderr, " INFO simmr-hip: %s\n", msg); }
+static void info(const std::string& msg) { fprintf(stderr, " INFO simmr-hip: %s\n", msg.c_str()); }
 static void warn(const std::string& msg) { fprintf(stderr, " WARN simmr-hip: %s\n", msg.c_str()); }
 static int die(const std::string& msg) { fprintf(stderr, "ERROR simmr-hip: %s\n", msg.c_str()); return 1; }
+static void reads_not_written(const std::string& err) { fprintf(stderr, "ERROR simmr-hip: Failed to write reads to the output file: %s\n", err.c_str()); }
 static bool exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0; }
 static bool is_regular_file(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
 
-struct DeviceOut {
-  simmr_reads_out o{};
+// Device allocations that are freed together, and the copy of a device array into a host vector.
+struct DeviceMem {
   std::vector<void*> allocs;
-  ~DeviceOut() { for (void* p : allocs) (void)hipFree(p); }
+  ~DeviceMem() { for (void* p : allocs) (void)hipFree(p); }
   template <class T> bool alloc(T** dst, size_t n) {
     void* p = nullptr;
     if (hipMalloc(&p, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
@@ -36,26 +36,29 @@ struct DeviceOut {
     *dst = (T*)p;
     return true;
   }
+  template <class T> static bool fetch(std::vector<T>* h, const T* dev, size_t n) {
+    h->resize(n);
+    return n == 0 || hipMemcpy(h->data(), dev, n * sizeof(T), hipMemcpyDeviceToHost) == hipSuccess;
+  }
+};
+
+struct DeviceOut {
+  simmr_reads_out o{};
+  DeviceMem mem;
   bool init(uint64_t n_reads, uint64_t total_bases, uint32_t slot_bytes) {
     o.slot_bytes = slot_bytes;  // simmr_plan_info.slot_bytes: the layout the plan in force emits
     o.seq_capacity = total_bases + 32;
     o.reads_capacity = n_reads;
     o.qual_offset = 33;  // util::encode_quality_scores (util.rs:46-57)
-    return alloc(&o.seq, o.seq_capacity) && alloc(&o.qual, o.seq_capacity) && alloc(&o.seq_off, n_reads + 1) &&
-           alloc(&o.start, n_reads) && alloc(&o.end, n_reads) && alloc(&o.contig, n_reads) &&
-           alloc(&o.genome, n_reads) && alloc(&o.read_id, n_reads) && alloc(&o.flags, n_reads);
+    return mem.alloc(&o.seq, o.seq_capacity) && mem.alloc(&o.qual, o.seq_capacity) && mem.alloc(&o.seq_off, n_reads + 1) &&
+           mem.alloc(&o.start, n_reads) && mem.alloc(&o.end, n_reads) && mem.alloc(&o.contig, n_reads) &&
+           mem.alloc(&o.genome, n_reads) && mem.alloc(&o.read_id, n_reads) && mem.alloc(&o.flags, n_reads);
   }
   bool to_host(uint64_t n_reads, uint64_t total_bases, bool paired, HostReads* h) {
     h->n_reads = n_reads; h->paired = paired;
-    h->seq.resize(total_bases); h->qual.resize(total_bases);
-    h->seq_off.resize(n_reads + 1); h->start.resize(n_reads); h->end.resize(n_reads);
-    h->contig.resize(n_reads); h->genome.resize(n_reads); h->read_id.resize(n_reads); h->flags.resize(n_reads);
-    auto cp = [](void* d, const void* s, size_t n) { return n == 0 || hipMemcpy(d, s, n, hipMemcpyDeviceToHost) == hipSuccess; };
-    if (!(cp(h->seq.data(), o.seq, total_bases) && cp(h->qual.data(), o.qual, total_bases) &&
-          cp(h->seq_off.data(), o.seq_off, (n_reads + 1) * 8) && cp(h->start.data(), o.start, n_reads * 8) &&
-          cp(h->end.data(), o.end, n_reads * 8) && cp(h->contig.data(), o.contig, n_reads * 4) &&
-          cp(h->genome.data(), o.genome, n_reads * 4) && cp(h->read_id.data(), o.read_id, n_reads * 4) &&
-          cp(h->flags.data(), o.flags, n_reads)))
+    if (!(mem.fetch(&h->seq, o.seq, total_bases) && mem.fetch(&h->qual, o.qual, total_bases) && mem.fetch(&h->seq_off, o.seq_off, n_reads + 1) &&
+          mem.fetch(&h->start, o.start, n_reads) && mem.fetch(&h->end, o.end, n_reads) && mem.fetch(&h->contig, o.contig, n_reads) &&
+          mem.fetch(&h->genome, o.genome, n_reads) && mem.fetch(&h->read_id, o.read_id, n_reads) && mem.fetch(&h->flags, o.flags, n_reads)))
       return false;
     if (o.slot_bytes == SIMMR_SLOT16) {
       // the consumer's side of the slot layout (include/simmr_hip.h): L = |end - start|, bases from seq_off[r], qualities
@@ -80,19 +83,14 @@ struct DeviceOut {
 static bool device_truth(simmr_engine* eng, const simmr_reads_out* reads, uint64_t n_reads, HostTruth* t, std::string* err) {
   uint64_t m = 0;
   if (simmr_truth_plan(eng, reads, n_reads, &m) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
-  DeviceOut mem;  // (its allocation list only)
+  DeviceMem mem;
   simmr_truth_out o{};
   o.reads_capacity = n_reads; o.edits_capacity = m;
   if (!(mem.alloc(&o.nm, n_reads) && mem.alloc(&o.edit_off, n_reads + 1) && mem.alloc(&o.edit_pos, m) && mem.alloc(&o.edit_ref, m) &&
         mem.alloc(&o.edit_alt, m) && mem.alloc(&o.edit_qual, m))) { *err = "device allocation failed"; return false; }
   if (simmr_truth_emit(eng, reads, &o) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
-  t->nm.resize(n_reads); t->edit_off.resize(n_reads + 1); t->edit_pos.resize(m); t->edit_ref.resize(m); t->edit_alt.resize(m); t->edit_qual.resize(m);
-  auto cp = [](void* d, const void* s, size_t n) { return n == 0 || hipMemcpy(d, s, n, hipMemcpyDeviceToHost) == hipSuccess; };
-  if (!(cp(t->nm.data(), o.nm, n_reads * 4) && cp(t->edit_off.data(), o.edit_off, (n_reads + 1) * 8) && cp(t->edit_pos.data(), o.edit_pos, m * 4) &&
-        cp(t->edit_ref.data(), o.edit_ref, m) && cp(t->edit_alt.data(), o.edit_alt, m) && cp(t->edit_qual.data(), o.edit_qual, m))) {
-    *err = "copy back failed";
-    return false;
-  }
+  if (!(mem.fetch(&t->nm, o.nm, n_reads) && mem.fetch(&t->edit_off, o.edit_off, n_reads + 1) && mem.fetch(&t->edit_pos, o.edit_pos, m) &&
+        mem.fetch(&t->edit_ref, o.edit_ref, m) && mem.fetch(&t->edit_alt, o.edit_alt, m) && mem.fetch(&t->edit_qual, o.edit_qual, m))) { *err = "copy back failed"; return false; }
   return true;
 }
 
@@ -100,9 +98,9 @@ static bool device_truth(simmr_engine* eng, const simmr_reads_out* reads, uint64
 // (simmr_depth_summarize), and the two files.
 static bool write_depth_files(simmr_engine* eng, const CliArgs& args, const std::vector<Genome>& genomes, uint64_t n_positions,
                               uint64_t n_contigs, std::string* err) {
-  DeviceOut mem;  // (its allocation list only)
+  DeviceMem mem;
   uint32_t* depth = nullptr;
-  if (!mem.alloc(&depth, std::max<uint64_t>(n_positions, 1))) { *err = "device allocation failed"; return false; }
+  if (!mem.alloc(&depth, n_positions)) { *err = "device allocation failed"; return false; }
   if (simmr_depth_emit(eng, depth, n_positions) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
   std::vector<simmr_depth_contig> rows(std::max<uint64_t>(n_contigs, 1));
   const bool track = !args.depth_track.empty();
@@ -111,24 +109,89 @@ static bool write_depth_files(simmr_engine* eng, const CliArgs& args, const std:
     const int rc = simmr_depth_summarize(eng, depth, args.depth_window, nullptr, 0, nullptr, &win);
     if (rc != SIMMR_OK && rc != SIMMR_ERANGE) { *err = simmr_last_error(eng); return false; }
     win.capacity = win.n_windows;
-    const uint64_t n = std::max<uint64_t>(win.capacity, 1);
-    if (!(mem.alloc(&win.sum, n) && mem.alloc(&win.covered, n) && mem.alloc(&win.max, n))) { *err = "device allocation failed"; return false; }
+    if (!(mem.alloc(&win.sum, win.capacity) && mem.alloc(&win.covered, win.capacity) && mem.alloc(&win.max, win.capacity))) { *err = "device allocation failed"; return false; }
   }
-  if (simmr_depth_summarize(eng, depth, track ? args.depth_window : 0u, rows.data(), rows.size(), nullptr, track ? &win : nullptr) != SIMMR_OK) {
-    *err = simmr_last_error(eng);
-    return false;
-  }
+  if (simmr_depth_summarize(eng, depth, track ? args.depth_window : 0u, rows.data(), rows.size(), nullptr, track ? &win : nullptr) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
   if (!args.depth.empty() && !write_depth_tsv(genomes, rows.data(), n_contigs, args.depth, err)) return false;
   if (!track) return true;
-  std::vector<uint64_t> ws(win.n_windows);
-  std::vector<uint32_t> wc(win.n_windows), wm(win.n_windows);
-  auto cp = [](void* d, const void* s, size_t n) { return n == 0 || hipMemcpy(d, s, n, hipMemcpyDeviceToHost) == hipSuccess; };
-  if (!(cp(ws.data(), win.sum, ws.size() * 8) && cp(wc.data(), win.covered, wc.size() * 4) && cp(wm.data(), win.max, wm.size() * 4))) {
-    *err = "copy back failed";
-    return false;
-  }
+  std::vector<uint64_t> ws;
+  std::vector<uint32_t> wc, wm;
+  if (!(mem.fetch(&ws, win.sum, win.n_windows) && mem.fetch(&wc, win.covered, win.n_windows) && mem.fetch(&wm, win.max, win.n_windows))) { *err = "copy back failed"; return false; }
   return write_depth_track_tsv(genomes, rows.data(), n_contigs, args.depth_window, ws.data(), wc.data(), wm.data(), args.depth_track, err);
 }
+
+// The side outputs of a run: --truth, --stats, --depth and --depth-track.  They read the columns, so a run that wants one
+// takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
+struct SideOutputs {
+  explicit SideOutputs(const CliArgs& args) : a(args) {}
+  const CliArgs& a;
+  std::string err;
+  HostTruth truth;           // of the range last added, until write_range has written it
+  uint32_t qual_offset = 33;
+  uint64_t depth_positions = 0, depth_contigs = 0;
+  bool depth() const { return !a.depth.empty() || !a.depth_track.empty(); }
+  bool wanted() const { return !a.truth.empty() || !a.stats.empty() || depth(); }
+  bool fail(const char* flag, const std::string& what) { err = std::string(flag) + ": " + what; return false; }
+  // true, with the message, if one of them is asked for together with --devices
+  bool refuse_devices() {
+    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth() ? "--depth" : nullptr;
+    if (flag && !a.devices.empty()) err = std::string(flag) + " does not combine with --devices: use --device";
+    return flag && !a.devices.empty();
+  }
+  // the old files go, the truth file gets its header line (every range appends its reads), the tables start at zero
+  // (the genomes are staged: depth[] covers all of them)
+  bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
+    for (const std::string* f : {&a.truth, &a.stats, &a.depth, &a.depth_track})
+      if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
+    std::string e;
+    if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
+    if (!a.stats.empty() && simmr_stats_reset(eng) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
+    if (depth() && simmr_depth_reset(eng, &depth_positions, &depth_contigs) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
+    return true;
+  }
+  // every range adds to the run's tables (enqueued behind the emit; the copies that follow wait for the device)
+  bool add_range(simmr_engine* eng, const simmr_reads_out& reads, uint64_t n_reads, bool paired) {
+    if (!a.stats.empty() && simmr_stats_add(eng, &reads, n_reads, paired ? 2u : 1u) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
+    if (depth() && simmr_depth_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
+    std::string e;
+    qual_offset = reads.qual_offset;
+    if (!a.truth.empty() && !device_truth(eng, &reads, n_reads, &truth, &e)) return fail("--truth", e);
+    return true;
+  }
+  bool write_range(const std::vector<Genome>& genomes, const HostReads& h) {
+    std::string e;
+    return a.truth.empty() || write_truth_tsv(genomes, h, truth, qual_offset, a.truth, false, &e) || fail("--truth", e);
+  }
+  bool finish(simmr_engine* eng, const std::vector<Genome>& genomes) {
+    std::string e;
+    if (!a.stats.empty()) {
+      auto st = std::make_unique<simmr_run_stats>();
+      if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
+      if (!write_stats_tsv(*st, a.stats, &e)) return fail("--stats", e);
+    }
+    return !depth() || write_depth_files(eng, a, genomes, depth_positions, depth_contigs, &e) || fail("--depth", e);
+  }
+};
+
+// A buffer that grows to the largest size asked of it, with a sixteenth to spare so that sizes creeping up do not allocate
+// every time: device memory, or pinned host memory.
+struct GrowBuf {
+  bool pinned = false;
+  void* p = nullptr;
+  uint64_t cap = 0;
+  ~GrowBuf() { release(); }
+  void release() { if (p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+  // room for `bytes`, or nullptr if there is none; what the buffer held is gone when it grows
+  uint8_t* room(uint64_t bytes) {
+    if (cap < bytes) {
+      release();
+      const uint64_t want = bytes + bytes / 16 + 256;
+      if ((pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return nullptr; }
+      cap = want;
+    }
+    return (uint8_t*)p;
+  }
+};
 
 // ---- output of one planned range ------------------------------------------------------------------------------------
 // A run is generated range by range of its units (pairs / long reads): the reference holds every read of a run in RAM
@@ -138,37 +201,20 @@ static bool write_depth_files(simmr_engine* eng, const CliArgs& args, const std:
 // (simmr_fastq_plan_direct / simmr_emit_fastq: no SoA columns in between).
 struct TextDrain {
   // two device buffers for the text and two pinned buffers for the copy out; the file is appended to in order
-  void* dev[2] = {nullptr, nullptr};
-  uint64_t cap[2] = {0, 0}, len[2] = {0, 0};
+  GrowBuf dev[2];  // (a buffer is free again when it is asked for: its previous text was drained two ranges ago)
+  uint64_t len[2] = {0, 0};
   void* pin[2] = {nullptr, nullptr};
   hipStream_t cs = nullptr;
   hipEvent_t emitted = nullptr;
-  FILE* f = nullptr;
+  std::optional<OutFile> f;
   static constexpr size_t CHUNK = 256u << 20;
   int pending = -1;  // buffer whose text still has to go to the file
-  bool own_file = true;
-  // `shared`: the file several drains append to, each when it is its turn (run_scope_devices); the caller closes it
-  bool open(const std::string& output, std::string* err, FILE* shared = nullptr) {
-    if (shared) { f = shared; own_file = false; }
-    else f = fopen(output.c_str(), "ab");
-    if (!f) { *err = "cannot open " + output; return false; }
+  bool open(const std::string& output, std::string* err) {
+    f.emplace(output, true);
+    if (!f->ok()) { *err = f->error(); return false; }
     if (hipHostMalloc(&pin[0], CHUNK, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&pin[1], CHUNK, hipHostMallocDefault) != hipSuccess ||
-        hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&emitted, hipEventDisableTiming) != hipSuccess) {
-      *err = "pinned buffer / stream allocation failed";
-      return false;
-    }
+        hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&emitted, hipEventDisableTiming) != hipSuccess) { *err = "pinned buffer / stream allocation failed"; return false; }
     return true;
-  }
-  // a device buffer of at least `bytes` for the next range; the buffer is free again: its previous text was drained
-  // two ranges ago.  nullptr if the device has no room.
-  uint8_t* buffer(int b, uint64_t bytes) {
-    if (cap[b] < bytes) {
-      if (dev[b]) (void)hipFree(dev[b]);
-      dev[b] = nullptr; cap[b] = 0;
-      if (hipMalloc(&dev[b], bytes + bytes / 16 + 256) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-      cap[b] = bytes + bytes / 16 + 256;
-    }
-    return (uint8_t*)dev[b];
   }
   // the text in buffer b (written by work queued on the null stream up to now) goes to the file; returns at once after
   // queueing the first copy, the rest happens in flush()
@@ -176,7 +222,7 @@ struct TextDrain {
     if (!flush(err)) return false;
     len[b] = bytes;
     if (hipEventRecord(emitted, nullptr) != hipSuccess || hipStreamWaitEvent(cs, emitted, 0) != hipSuccess) { *err = "event failed"; return false; }
-    if (bytes > 0 && hipMemcpyAsync(pin[0], dev[b], std::min<uint64_t>(CHUNK, bytes), hipMemcpyDeviceToHost, cs) != hipSuccess) { *err = "copy back failed"; return false; }
+    if (bytes > 0 && hipMemcpyAsync(pin[0], dev[b].p, std::min<uint64_t>(CHUNK, bytes), hipMemcpyDeviceToHost, cs) != hipSuccess) { *err = "copy back failed"; return false; }
     pending = b;
     return true;
   }
@@ -189,121 +235,158 @@ struct TextDrain {
     auto len_of = [&](uint64_t i) { return (size_t)std::min<uint64_t>(CHUNK, total - i * CHUNK); };
     for (uint64_t i = 0; i < n_chunks; i++) {
       if (hipStreamSynchronize(cs) != hipSuccess) { *err = "copy back failed"; return false; }  // chunk i is in pin[i & 1]
-      if (i + 1 < n_chunks && hipMemcpyAsync(pin[(i + 1) & 1], (const char*)dev[b] + (i + 1) * CHUNK, len_of(i + 1), hipMemcpyDeviceToHost, cs) != hipSuccess) {
-        *err = "copy back failed";
-        return false;
-      }
-      if (fwrite(pin[i & 1], 1, len_of(i), f) != len_of(i)) { *err = "short write"; return false; }
+      if (i + 1 < n_chunks && hipMemcpyAsync(pin[(i + 1) & 1], (const char*)dev[b].p + (i + 1) * CHUNK, len_of(i + 1), hipMemcpyDeviceToHost, cs) != hipSuccess) { *err = "copy back failed"; return false; }
+      f->append(pin[i & 1], len_of(i));
+      if (!f->ok()) { *err = f->error(); return false; }
     }
     return true;
   }
+  // the pending text, then the file's one status
+  bool close(std::string* err) { return flush(err) && f->close(err); }
   ~TextDrain() {
-    if (f && own_file) fclose(f);
     if (cs) (void)hipStreamDestroy(cs);
     if (emitted) (void)hipEventDestroy(emitted);
     for (void* q : pin) if (q) (void)hipHostFree(q);
-    for (void* q : dev) if (q) (void)hipFree(q);
-  }
-};
-
-struct NameTables {  // simmr_fastq_names of genomes [g0, g1)
-  std::vector<uint32_t> idx, ncontigs;
-  std::vector<const char*> gids, sids;
-  simmr_fastq_names names{};
-  NameTables(const std::vector<Genome>& genomes, size_t g0, size_t g1) {
-    for (size_t gi = g0; gi < g1; gi++) {
-      idx.push_back((uint32_t)gi);
-      gids.push_back(genomes[gi].uuid.c_str());
-      ncontigs.push_back((uint32_t)genomes[gi].sequence.size());
-      for (const Seq& s : genomes[gi].sequence) sids.push_back(s.id.c_str());
-    }
-    names = simmr_fastq_names{(uint32_t)idx.size(), idx.data(), gids.data(), ncontigs.data(), sids.data()};
   }
 };
 
 // One scope of the run = one plan function over a range of units: all genomes' pairs in one plan, one genome's pairs
-// (custom profiles), or all long reads.  `genome_units[g - g0]` = units of genome g, in generation order.
+// (custom profiles), or all long reads.
 struct Scope {
-  bool paired;
-  size_t g0, g1;
-  std::vector<uint64_t> genome_units;
+  enum Kind { PE_ALL, PE_GENOME, LONG } kind;
+  std::vector<uint32_t> idx;    // the scope's genomes, ascending
+  std::vector<uint64_t> reads;  // reads asked of each, in generation order
+  simmr_error_profile pod;
+  int has_seed;
+  uint64_t seed;  // (of --seed, or the one probe_scope drew)
   uint32_t id_base;
+  uint64_t text_bytes_per_unit;  // what sizes the ranges; an upper estimate of a unit's FASTQ text
+  bool paired() const { return kind != LONG; }
+  uint32_t reads_per_unit() const { return paired() ? 2u : 1u; }
+  uint64_t units(size_t k) const { return reads[k] / reads_per_unit(); }  // simulate.rs:179: a genome's odd read makes no pair
   // plans units [first, first + count) of the scope; SIMMR_* code
-  std::function<int(simmr_engine*, simmr_range, simmr_plan_info*)> plan;
-  std::function<int(simmr_engine*, uint32_t, const simmr_reads_out*)> emit;  // columns (host writer only)
+  int plan(simmr_engine* en, simmr_range rg, simmr_plan_info* pi) const {
+    switch (kind) {
+      case PE_ALL: return simmr_pe_plan_multi(en, (uint32_t)idx.size(), idx.data(), reads.data(), &pod, has_seed, seed, rg, pi);
+      case PE_GENOME: return simmr_pe_plan(en, idx[0], &pod, reads[0], has_seed, seed, rg, pi);
+      case LONG: return simmr_long_plan(en, (uint32_t)idx.size(), idx.data(), reads.data(), &pod, has_seed, seed, rg, pi);
+    }
+    return SIMMR_EINVAL;
+  }
+  // columns (host writer only)
+  int emit(simmr_engine* en, const simmr_reads_out* o) const { return paired() ? simmr_pe_emit(en, id_base, o) : simmr_long_emit(en, id_base, o); }
 };
 
+// Plans an empty range of the scope.  The answer says whether the library takes this plan at all (SIMMR_ENOTSUP: a custom
+// profile in the one plan over all genomes).  Without --seed the call draws a seed, and it becomes the scope's: every
+// plan call would draw its own otherwise (simulate.rs:174), and the ranges have to continue one stream.
+static int probe_scope(simmr_engine* eng, Scope* sc) {
+  simmr_plan_info p0{};
+  const int rc = sc->plan(eng, simmr_range{0, 0}, &p0);
+  if (rc == SIMMR_OK && !sc->has_seed) {
+    sc->has_seed = 1; sc->seed = p0.seed_used;
+    // (without --seed the library selects per-read lengths by itself; the ranges, which now name a seed, say so)
+    if (!sc->paired()) sc->pod.length_mode = SIMMR_LEN_PER_READ;
+  }
+  return rc;
+}
+
+struct NameTables {  // simmr_fastq_names of the scope's genomes
+  std::vector<uint32_t> ncontigs;
+  std::vector<const char*> gids, sids;
+  simmr_fastq_names names{};
+  NameTables(const std::vector<Genome>& genomes, const Scope& sc) {
+    for (uint32_t gi : sc.idx) {
+      gids.push_back(genomes[gi].uuid.c_str());
+      ncontigs.push_back((uint32_t)genomes[gi].sequence.size());
+      for (const Seq& s : genomes[gi].sequence) sids.push_back(s.id.c_str());
+    }
+    names = simmr_fastq_names{(uint32_t)sc.idx.size(), sc.idx.data(), gids.data(), ncontigs.data(), sids.data()};
+  }
+};
+
+// The ranges of a scope, the same whoever walks them: `chunk_units` each (0: all in one).  Several engines get at least a
+// range each, of at most MAX_TEXT bytes of text (a range waits in pinned host memory for its turn; allocating that costs
+// ~0.25 s per GB, once).  A scope without a unit has one empty range.
+struct Ranges {
+  static constexpr uint64_t MAX_TEXT = 1ull << 30;
+  uint64_t total = 0, chunk, n;
+  Ranges(const Scope& sc, uint64_t chunk_units, size_t n_engines) : chunk(chunk_units) {
+    for (size_t k = 0; k < sc.reads.size(); k++) total += sc.units(k);
+    if (chunk == 0 || chunk > total) chunk = total;
+    if (n_engines > 1) chunk = std::min({chunk, (total + n_engines - 1) / n_engines, MAX_TEXT / std::max<uint64_t>(sc.text_bytes_per_unit, 1)});
+    chunk = std::max<uint64_t>(chunk, 1);
+    n = std::max<uint64_t>((total + chunk - 1) / chunk, 1);
+  }
+  simmr_range at(uint64_t k) const { return simmr_range{k * chunk, std::min(chunk, total - k * chunk)}; }
+};
+
+// Plans range rg of the scope on `eng` and, given the names, sizes its FASTQ text.  SIMMR_OK with *bytes; SIMMR_ENOTSUP if
+// the headers need the host writer (an id with a brace, a header over 255 bytes: the range stays planned; the plan itself
+// answers this code only to probe_scope); or the code of the call that failed, with simmr_last_error.
+static int plan_range(simmr_engine* eng, const Scope& sc, simmr_range rg, const NameTables* nt, const std::string& header_format,
+                      simmr_plan_info* pi, uint64_t* bytes) {
+  const int rc = sc.plan(eng, rg, pi);  // the reference unwrap()s this Err (simulate.rs:137)
+  if (rc != SIMMR_OK || !nt) return rc;
+  return simmr_fastq_plan_direct(eng, header_format.c_str(), &nt->names, sc.id_base, bytes);
+}
+
 // Generates the scope range by range and appends its FASTQ to args.output.  0, or 1 after die().
-static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<Genome>& genomes, const Scope& sc, uint64_t chunk_units) {
-  uint64_t total_units = 0;
-  for (uint64_t u : sc.genome_units) total_units += u;
-  const uint32_t rpu = sc.paired ? 2u : 1u;
-  if (chunk_units == 0 || chunk_units > total_units) chunk_units = std::max<uint64_t>(total_units, 1);
-  NameTables nt(genomes, sc.g0, sc.g1);
+static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<Genome>& genomes, const Scope& sc, uint64_t chunk_units,
+                     SideOutputs* side) {
+  const Ranges ranges(sc, chunk_units, 1);
+  const uint32_t rpu = sc.reads_per_unit();
+  NameTables nt(genomes, sc);
   std::string err;
-  // --truth reads the columns: the run takes the column route (the same bytes, include/simmr_hip.h)
-  // (--stats, --depth and --depth-track likewise)
-  const bool want_depth = !args.depth.empty() || !args.depth_track.empty();
-  bool use_device_text = !args.host_fastq && args.truth.empty() && args.stats.empty() && !want_depth;
-  uint64_t text_bytes = 0, n_ranges = 0;
+  bool use_device_text = !args.host_fastq && !side->wanted();
+  uint64_t text_bytes = 0, n_passes = 0;
   TextDrain drain;
   if (use_device_text && !drain.open(args.output, &err)) return die(err);
   int buf = 0;
-  for (uint64_t first = 0; first < total_units || (first == 0 && total_units == 0); first += chunk_units) {
-    const simmr_range rg{first, std::min<uint64_t>(chunk_units, total_units - first)};
+  for (uint64_t k = 0; k < ranges.n; k++) {
+    const simmr_range rg = ranges.at(k);
     simmr_plan_info pi{};
-    if (sc.plan(eng, rg, &pi) != SIMMR_OK) return die(simmr_last_error(eng));  // the reference unwrap()s this Err (simulate.rs:137)
-    bool written = false;
+    uint64_t bytes = 0;
+    const int rc = plan_range(eng, sc, rg, use_device_text ? &nt : nullptr, args.read_header_format, &pi, &bytes);
+    if (rc == SIMMR_ENOTSUP) {
+      use_device_text = false;  // the host writer frames this run from here
+      if (!drain.close(&err)) return die(err);
+    } else if (rc != SIMMR_OK) {
+      return die(simmr_last_error(eng));
+    }
     if (use_device_text) {
-      uint64_t bytes = 0;
-      const int rc = simmr_fastq_plan_direct(eng, args.read_header_format.c_str(), &nt.names, sc.id_base, &bytes);
-      if (rc == SIMMR_ENOTSUP) {
-        use_device_text = false;  // an id with a brace, a header over 255 bytes: the host writer frames this run
-        if (!drain.flush(&err)) return die(err);
-        fclose(drain.f); drain.f = nullptr;
-      } else if (rc != SIMMR_OK) {
-        return die(simmr_last_error(eng));
-      } else if (bytes == 0) {
-        written = true;  // a scope without a unit (--num-reads < 2, a genome whose share is below one pair): the reference
-                         // writes nothing for it and goes on (simulate.rs:179, main.rs:188-206)
-      } else {
-        uint8_t* dst = drain.buffer(buf, bytes);
-        if (!dst) return die("no device memory for " + std::to_string(bytes) + " bytes of FASTQ text: use a smaller --device-chunk-reads");
-        if (simmr_emit_fastq(eng, dst, bytes) != SIMMR_OK) return die(simmr_last_error(eng));
-        if (!drain.submit(buf, bytes, &err)) { fprintf(stderr, "ERROR simmr-hip: Failed to write reads to the output file: %s\n", err.c_str()); }
-        buf ^= 1;
-        written = true;
-        text_bytes += bytes;
-        n_ranges++;
-      }
+      // (no text: a scope without a unit — --num-reads < 2, a genome whose share is below one pair: the reference writes
+      // nothing for it and goes on, simulate.rs:179, main.rs:188-206)
+      if (bytes == 0) continue;
+      uint8_t* dst = drain.dev[buf].room(bytes);
+      if (!dst) return die("no device memory for " + std::to_string(bytes) + " bytes of FASTQ text: use a smaller --device-chunk-reads");
+      if (simmr_emit_fastq(eng, dst, bytes) != SIMMR_OK) return die(simmr_last_error(eng));
+      if (!drain.submit(buf, bytes, &err)) reads_not_written(err);
+      buf ^= 1;
+      text_bytes += bytes;
+      n_passes++;
+      continue;
     }
-    if (!written) {  // columns to the host, framed by the restatement of fastq.rs in host.cpp, genome by genome
-      DeviceOut d;
-      if (!d.init(pi.n_reads, pi.total_bases, pi.slot_bytes)) return die("device allocation failed");
-      if (sc.emit(eng, sc.id_base, &d.o) != SIMMR_OK) return die(simmr_last_error(eng));
-      // every range adds to the run's tables (enqueued behind the emit; the copies below wait for the device)
-      if (!args.stats.empty() && simmr_stats_add(eng, &d.o, pi.n_reads, sc.paired ? 2u : 1u) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
-      if (want_depth && simmr_depth_add(eng, &d.o, pi.n_reads) != SIMMR_OK) return die(std::string("--depth: ") + simmr_last_error(eng));
-      HostTruth truth;
-      if (!args.truth.empty() && !device_truth(eng, &d.o, pi.n_reads, &truth, &err)) return die("--truth: " + err);
-      HostReads h;
-      if (!d.to_host(pi.n_reads, pi.total_bases, sc.paired, &h)) return die("copy back failed");
-      if (!args.truth.empty() && !write_truth_tsv(genomes, h, truth, d.o.qual_offset, args.truth, false, &err)) return die("--truth: " + err);
-      uint64_t g_first = 0;  // first unit of genome gi in the scope
-      for (size_t gi = sc.g0; gi < sc.g1; gi++) {
-        const uint64_t g_units = sc.genome_units[gi - sc.g0];
-        const uint64_t lo = std::max(first, g_first), hi = std::min(first + rg.count, g_first + g_units);
-        if (hi > lo &&
-            !write_to_fastq(genomes[gi].uuid, genomes[gi], h, (lo - first) * rpu, (hi - lo) * rpu, args.output, args.read_header_format, true, &err))
-          fprintf(stderr, "ERROR simmr-hip: Failed to write reads to the output file: %s\n", err.c_str());
-        g_first += g_units;
-      }
+    // columns to the host, framed by the restatement of fastq.rs in host.cpp, genome by genome
+    DeviceOut d;
+    if (!d.init(pi.n_reads, pi.total_bases, pi.slot_bytes)) return die("device allocation failed");
+    if (sc.emit(eng, &d.o) != SIMMR_OK) return die(simmr_last_error(eng));
+    if (!side->add_range(eng, d.o, pi.n_reads, sc.paired())) return die(side->err);
+    HostReads h;
+    if (!d.to_host(pi.n_reads, pi.total_bases, sc.paired(), &h)) return die("copy back failed");
+    if (!side->write_range(genomes, h)) return die(side->err);
+    uint64_t g_first = 0;  // first unit of genome idx[j] in the scope
+    for (size_t j = 0; j < sc.idx.size(); j++) {
+      const Genome& g = genomes[sc.idx[j]];
+      const uint64_t lo = std::max(rg.first, g_first), hi = std::min(rg.first + rg.count, g_first + sc.units(j));
+      if (hi > lo && !write_to_fastq(g.uuid, g, h, (lo - rg.first) * rpu, (hi - lo) * rpu, args.output, args.read_header_format, true, &err))
+        reads_not_written(err);
+      g_first += sc.units(j);
     }
-    if (total_units == 0) break;
   }
-  if (use_device_text && !drain.flush(&err)) fprintf(stderr, "ERROR simmr-hip: Failed to write reads to the output file: %s\n", err.c_str());
-  if (n_ranges > 1)
-    info((std::to_string(total_units * rpu) + " reads in " + std::to_string(n_ranges) + " device passes, " + std::to_string(text_bytes) + " bytes of FASTQ").c_str());
+  if (use_device_text && !drain.close(&err)) reads_not_written(err);
+  if (n_passes > 1)
+    info(std::to_string(ranges.total * rpu) + " reads in " + std::to_string(n_passes) + " device passes, " + std::to_string(text_bytes) + " bytes of FASTQ");
   return 0;
 }
 
@@ -313,25 +396,16 @@ static int run_scope(simmr_engine* eng, const CliArgs& args, const std::vector<G
 // turn: engine d plans and emits ranges d, d + N, d + 2N, ... on a host thread of its own (one engine per device, or
 // several on one: an ordinal may repeat), copies each range's text to pinned host memory over ITS device's link as soon as
 // it is emitted — the devices' copies run side by side; a drain that waited for its turn would put the whole node behind one
-// PCIe link — and appends it to the file when the range before it is on disk.  Ranges are at most MAX_RANGE_TEXT bytes of
-// text (a range waits in host memory for its turn).  Ids are
+// PCIe link — and appends it to the file when the range before it is on disk.  Ids are
 // those of the single-engine run (the library's ids come from the global unit index, simulate.rs:85-89); nothing is
 // exchanged between devices, the run counters are not needed for the files.  0, or 1 after die().
 static int run_scope_devices(const std::vector<simmr_engine*>& engs, const std::vector<int>& ordinals, const CliArgs& args,
-                             const std::vector<Genome>& genomes, const Scope& sc, uint64_t chunk_units, uint64_t text_bytes_per_unit) {
-  constexpr uint64_t MAX_RANGE_TEXT = 1ull << 30;  // (pinned host memory per engine; allocating it costs ~0.25 s per GB, once)
-  uint64_t total_units = 0;
-  for (uint64_t u : sc.genome_units) total_units += u;
-  if (total_units == 0) return 0;  // (the reference writes nothing for a scope without a unit)
-  const uint32_t rpu = sc.paired ? 2u : 1u;
+                             const std::vector<Genome>& genomes, const Scope& sc, uint64_t chunk_units) {
   const size_t N = engs.size();
-  // ranges no larger than a device pass, and at least one per engine
-  if (chunk_units == 0 || chunk_units > total_units) chunk_units = total_units;
-  chunk_units = std::max<uint64_t>(std::min<uint64_t>(chunk_units, (total_units + N - 1) / N), 1);
-  chunk_units = std::max<uint64_t>(std::min<uint64_t>(chunk_units, MAX_RANGE_TEXT / std::max<uint64_t>(text_bytes_per_unit, 1)), 1);
-  const uint64_t n_ranges = (total_units + chunk_units - 1) / chunk_units;
-  FILE* f = fopen(args.output.c_str(), "ab");
-  if (!f) return die("cannot open " + args.output);
+  const Ranges ranges(sc, chunk_units, N);
+  if (ranges.total == 0) return 0;  // (the reference writes nothing for a scope without a unit)
+  OutFile f(args.output, true);
+  if (!f.ok()) return die(f.error());
   std::mutex m;
   std::condition_variable cv;
   uint64_t turn = 0;        // the range whose text goes to the file next
@@ -346,41 +420,30 @@ static int run_scope_devices(const std::vector<simmr_engine*>& engs, const std::
   auto worker = [&](size_t d) {
     simmr_engine* eng = engs[d];
     if (hipSetDevice(ordinals[d]) != hipSuccess) return fail("hipSetDevice failed");
-    NameTables nt(genomes, sc.g0, sc.g1);
+    NameTables nt(genomes, sc);
     // this engine's text buffers: one on the device, one pinned on the host (both grow to the largest range), a copy stream
     struct Bufs {
-      void* dev = nullptr; void* host = nullptr; uint64_t dev_cap = 0, host_cap = 0; hipStream_t cs = nullptr;
-      ~Bufs() { if (dev) (void)hipFree(dev); if (host) (void)hipHostFree(host); if (cs) (void)hipStreamDestroy(cs); }
+      GrowBuf dev, host{true};
+      hipStream_t cs = nullptr;
+      ~Bufs() { if (cs) (void)hipStreamDestroy(cs); }
     } b;
     if (hipStreamCreateWithFlags(&b.cs, hipStreamNonBlocking) != hipSuccess) return fail("stream allocation failed");
-    for (uint64_t k = d; k < n_ranges; k += N) {
+    for (uint64_t k = d; k < ranges.n; k += N) {
       { std::lock_guard<std::mutex> lk(m); if (failed) return; }
-      const simmr_range rg{k * chunk_units, std::min<uint64_t>(chunk_units, total_units - k * chunk_units)};
       simmr_plan_info pi{};
-      if (sc.plan(eng, rg, &pi) != SIMMR_OK) return fail(simmr_last_error(eng));
       uint64_t bytes = 0;
-      const int rc = simmr_fastq_plan_direct(eng, args.read_header_format.c_str(), &nt.names, sc.id_base, &bytes);
+      const int rc = plan_range(eng, sc, ranges.at(k), &nt, args.read_header_format, &pi, &bytes);
       if (rc == SIMMR_ENOTSUP) return fail(std::string("--devices writes the text on the devices, and this run's headers need the host writer (") + simmr_last_error(eng) + "): use --device with --host-fastq");
       if (rc != SIMMR_OK) return fail(simmr_last_error(eng));
-      if (bytes > b.dev_cap) {
-        if (b.dev) (void)hipFree(b.dev);
-        b.dev = nullptr; b.dev_cap = 0;
-        if (hipMalloc(&b.dev, bytes + bytes / 16 + 256) != hipSuccess) { (void)hipGetLastError(); return fail("no device memory for " + std::to_string(bytes) + " bytes of FASTQ text: use a smaller --device-chunk-reads"); }
-        b.dev_cap = bytes + bytes / 16 + 256;
-      }
-      if (bytes > b.host_cap) {
-        if (b.host) (void)hipHostFree(b.host);
-        b.host = nullptr; b.host_cap = 0;
-        if (hipHostMalloc(&b.host, bytes + bytes / 16 + 256, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail("no pinned host memory for " + std::to_string(bytes) + " bytes of FASTQ text"); }
-        b.host_cap = bytes + bytes / 16 + 256;
-      }
       if (bytes) {
-        if (simmr_emit_fastq(eng, (uint8_t*)b.dev, bytes) != SIMMR_OK) return fail(simmr_last_error(eng));
+        if (!b.dev.room(bytes)) return fail("no device memory for " + std::to_string(bytes) + " bytes of FASTQ text: use a smaller --device-chunk-reads");
+        if (!b.host.room(bytes)) return fail("no pinned host memory for " + std::to_string(bytes) + " bytes of FASTQ text");
+        if (simmr_emit_fastq(eng, (uint8_t*)b.dev.p, bytes) != SIMMR_OK) return fail(simmr_last_error(eng));
         // over this device's own link, now: the emit ran on the null stream of the device, the copy stream waits for it
         hipEvent_t done = nullptr;
         if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess || hipEventRecord(done, nullptr) != hipSuccess ||
             hipStreamWaitEvent(b.cs, done, 0) != hipSuccess ||
-            hipMemcpyAsync(b.host, b.dev, bytes, hipMemcpyDeviceToHost, b.cs) != hipSuccess || hipStreamSynchronize(b.cs) != hipSuccess) {
+            hipMemcpyAsync(b.host.p, b.dev.p, bytes, hipMemcpyDeviceToHost, b.cs) != hipSuccess || hipStreamSynchronize(b.cs) != hipSuccess) {
           if (done) (void)hipEventDestroy(done);
           return fail("copy back failed");
         }
@@ -391,10 +454,11 @@ static int run_scope_devices(const std::vector<simmr_engine*>& engs, const std::
         cv.wait(lk, [&] { return failed || turn == k; });
         if (failed) return;
       }
-      const bool ok = bytes == 0 || fwrite(b.host, 1, bytes, f) == bytes;  // this thread owns the file until it passes the turn on
+      f.append(b.host.p, bytes);  // this thread owns the file until it passes the turn on
+      const bool ok = f.ok();
       {
         std::lock_guard<std::mutex> lk(m);
-        if (!ok && !failed) { failed = true; first_error = "Failed to write reads to the output file: short write"; }
+        if (!ok && !failed) { failed = true; first_error = "Failed to write reads to the output file: " + f.error(); }
         text_bytes += bytes;
         turn = k + 1;
       }
@@ -405,10 +469,11 @@ static int run_scope_devices(const std::vector<simmr_engine*>& engs, const std::
   std::vector<std::thread> threads;
   for (size_t d = 0; d < N; d++) threads.emplace_back(worker, d);
   for (auto& t : threads) t.join();
-  fclose(f);
+  std::string err;
+  if (!f.close(&err) && !failed) { failed = true; first_error = "Failed to write reads to the output file: " + err; }
   if (failed) return die(first_error);
-  info((std::to_string(total_units * rpu) + " reads in " + std::to_string(n_ranges) + " device passes on " + std::to_string(N) +
-        " engines, " + std::to_string(text_bytes) + " bytes of FASTQ").c_str());
+  info(std::to_string(ranges.total * sc.reads_per_unit()) + " reads in " + std::to_string(ranges.n) + " device passes on " + std::to_string(N) +
+       " engines, " + std::to_string(text_bytes) + " bytes of FASTQ");
   return 0;
 }
 
@@ -469,6 +534,11 @@ static int load_genome_device(simmr_engine* eng, uint32_t slot, const std::strin
   return 0;
 }
 
+struct Engines {  // released on every way out of run_main
+  std::vector<simmr_engine*> v;
+  ~Engines() { for (simmr_engine* en : v) simmr_engine_destroy(en); }
+};
+
 static int run_main(int argc, char** argv) {
   CliArgs args;
   std::string err;
@@ -476,9 +546,8 @@ static int run_main(int argc, char** argv) {
   if (!parse_cli_args(argc, argv, &args, &err, &help)) { fprintf(stderr, "error: %s\n\n%s", err.c_str(), usage().c_str()); return 2; }
   if (help) { fputs(usage().c_str(), stdout); return 0; }
 
-  if (!args.truth.empty() && !args.devices.empty()) return die("--truth does not combine with --devices: use --device");
-  if (!args.stats.empty() && !args.devices.empty()) return die("--stats does not combine with --devices: use --device");
-  if ((!args.depth.empty() || !args.depth_track.empty()) && !args.devices.empty()) return die("--depth does not combine with --devices: use --device");
+  SideOutputs side(args);
+  if (side.refuse_devices()) return die(side.err);
   std::unique_ptr<ErrorProfile> eprofile = determine_error_profile(args, &err);  // main.rs:27
   if (!eprofile) return die(err);
   // main.rs:30-33
@@ -490,73 +559,56 @@ static int run_main(int argc, char** argv) {
   // one engine per entry of --devices (an ordinal may repeat: two engines on one device), or the one of --device
   const std::vector<int> ordinals = args.devices.empty() ? std::vector<int>{args.device} : args.devices;
   if (ordinals.size() > 1 && args.host_fastq) return die("--devices writes the text on the devices: it does not combine with --host-fastq");
-  std::vector<simmr_engine*> engs;
+  Engines engines;
+  const std::vector<simmr_engine*>& engs = engines.v;
   for (int ord : ordinals) {
     simmr_engine* en = nullptr;
     if (simmr_engine_create(ord, &en) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+    engines.v.push_back(en);
     // 16-byte read slots wherever the emit kernel of a plan writes them (include/simmr_hip.h: simmr_reads_out); the columns
     // only exist on the --host-fastq path (the text path writes no columns), and DeviceOut::to_host reads either layout
     if (simmr_engine_set_read_slots(en, SIMMR_SLOT16) != SIMMR_OK) return die(simmr_last_error(en));
-    engs.push_back(en);
   }
   simmr_engine* const eng = engs[0];
 
   info("Loading genomes");
-  std::vector<Genome> genomes;
-  const uint64_t device_min_size = eprofile->minimum_genome_size();
-  if (!args.host_normalize) {
-    // main.rs:38-162 with the sequences normalised, filtered and packed on the device
-    std::vector<GenomeRecord> records;
-    if (args.genome_file) {
-      if (!parse_genome_file(*args.genome_file, &records, &err)) return die("Failed to read genome file: " + err);
-      for (const auto& rec : records)
-        if (!exists(rec.filepath)) return die("Genome (" + rec.filepath + ") does not exist");
-    } else {
-      for (const auto& path : args.genome) { GenomeRecord r; r.filepath = path; records.push_back(r); }
-    }
-    for (const auto& rec : records) {
-      Genome g;
-      const int rc = load_genome_device(eng, (uint32_t)genomes.size(), rec.filepath, args.contiguous, device_min_size, &g, &err);
-      if (rc < 0) return die("Failed to parse " + rec.filepath + ": " + err);
-      if (rec.uuid) g.uuid = *rec.uuid;
-      if (args.genome_file && args.abundance_profile == AbundanceProfileKind::Custom && !rec.abundance)
-        return die("You used a custom abundance profile but didn't provide abundances for genome " + g.filepath);
-      g.abundance = rec.abundance;
-      // every further engine stages its own copy of the reference (replicated, as across ranks: DESIGN.md section 5)
-      for (size_t k = 1; rc == 0 && k < engs.size(); k++) {
-        Genome again;
-        if (load_genome_device(engs[k], (uint32_t)genomes.size(), rec.filepath, args.contiguous, device_min_size, &again, &err) != 0)
-          return die("Failed to stage " + rec.filepath + " on device " + std::to_string(ordinals[k]) + ": " + err);
-      }
-      if (rc == 0) genomes.push_back(std::move(g));
-    }
-  } else if (args.genome_file) {  // main.rs:38-100
-    std::vector<GenomeRecord> records;
+  // main.rs:38-117: the records of --genome-file, or one per --genome
+  std::vector<GenomeRecord> records;
+  if (args.genome_file) {
     if (!parse_genome_file(*args.genome_file, &records, &err)) return die("Failed to read genome file: " + err);
     for (const auto& rec : records)
       if (!exists(rec.filepath)) return die("Genome (" + rec.filepath + ") does not exist");
-    for (const auto& rec : records) {
-      Genome g;
-      if (!Genome::from_fasta(rec.filepath, args.contiguous, &g, &err)) return die("Failed to parse " + rec.filepath + ": " + err);
-      if (rec.uuid) g.uuid = *rec.uuid;
-      if (args.abundance_profile == AbundanceProfileKind::Custom && !rec.abundance)
-        return die("You used a custom abundance profile but didn't provide abundances for genome " + g.filepath);
-      g.abundance = rec.abundance;
-      genomes.push_back(std::move(g));
+  } else {
+    for (const auto& path : args.genome) { GenomeRecord r; r.filepath = path; records.push_back(r); }
+  }
+  std::vector<Genome> genomes;
+  const uint64_t min_size = eprofile->minimum_genome_size();
+  for (const auto& rec : records) {
+    Genome g;
+    int rc = 0;  // 1: no usable sequence, the genome is left out
+    if (args.host_normalize) {
+      if (!Genome::from_fasta(rec.filepath, args.contiguous, &g, &err)) rc = -1;
+    } else {  // the sequences normalised, filtered (main.rs:117-162) and packed on the device
+      rc = load_genome_device(eng, (uint32_t)genomes.size(), rec.filepath, args.contiguous, min_size, &g, &err);
     }
-  } else {  // main.rs:101-117
-    for (const auto& path : args.genome) {
-      Genome g;
-      if (!Genome::from_fasta(path, args.contiguous, &g, &err)) return die("Failed to parse " + path + ": " + err);
-      genomes.push_back(std::move(g));
+    if (rc < 0) return die("Failed to parse " + rec.filepath + ": " + err);
+    if (rec.uuid) g.uuid = *rec.uuid;
+    if (args.genome_file && args.abundance_profile == AbundanceProfileKind::Custom && !rec.abundance)
+      return die("You used a custom abundance profile but didn't provide abundances for genome " + g.filepath);
+    g.abundance = rec.abundance;
+    // every further engine stages its own copy of the reference (replicated, as across ranks: DESIGN.md section 5)
+    for (size_t k = 1; !args.host_normalize && rc == 0 && k < engs.size(); k++) {
+      Genome again;
+      if (load_genome_device(engs[k], (uint32_t)genomes.size(), rec.filepath, args.contiguous, min_size, &again, &err) != 0)
+        return die("Failed to stage " + rec.filepath + " on device " + std::to_string(ordinals[k]) + ": " + err);
     }
+    if (rc == 0) genomes.push_back(std::move(g));
   }
   if (args.abundance_profile == AbundanceProfileKind::Custom && !args.genome_file)
     return die("a custom abundance profile needs a --genome-file with abundances");
 
   info("Ensuring genomes meet minimum sequence length requirements for simulation");
   if (!args.contiguous && args.host_normalize) {  // main.rs:117-162
-    const uint64_t min_size = eprofile->minimum_genome_size();
     std::vector<Genome> kept;
     for (Genome& g : genomes) {
       std::vector<Seq> seqs;
@@ -603,22 +655,7 @@ static int run_main(int argc, char** argv) {
   if (is_regular_file(args.output)) remove(args.output.c_str());  // (a pipe or a device given as the output is written to, not replaced)
   const std::string meta_path = args.output + ".tsv";
   if (exists(meta_path)) remove(meta_path.c_str());
-  if (!args.truth.empty()) {  // the header line; every range appends its reads
-    if (is_regular_file(args.truth)) remove(args.truth.c_str());
-    if (!write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, args.truth, true, &err)) return die("--truth: " + err);
-  }
-
-  if (!args.stats.empty()) {
-    if (is_regular_file(args.stats)) remove(args.stats.c_str());
-    if (simmr_stats_reset(eng) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
-  }
-
-  const bool want_depth = !args.depth.empty() || !args.depth_track.empty();
-  uint64_t depth_positions = 0, depth_contigs = 0;
-  if (want_depth) {  // the genomes are staged: depth[] covers all of them
-    for (const std::string& f : {args.depth, args.depth_track}) if (!f.empty() && is_regular_file(f)) remove(f.c_str());
-    if (simmr_depth_reset(eng, &depth_positions, &depth_contigs) != SIMMR_OK) return die(std::string("--depth: ") + simmr_last_error(eng));
-  }
+  if (!side.begin(eng, genomes)) return die(side.err);
 
   simmr_error_profile pod = eprofile->pod();
   if (args.rng_philox) {  // (extension) the counter mode, for the profiles that draw per base from a parametric law
@@ -632,92 +669,51 @@ static int run_main(int argc, char** argv) {
       pod.rng_mode = SIMMR_RNG_PHILOX_FULL;
     }
   }
-  const int has_seed = args.seed ? 1 : 0;
-  const uint64_t seed = args.seed.value_or(0);
 
-  const uint64_t chunk_reads = args.device_chunk_reads;
-  auto run = [&](const Scope& sc, uint64_t chunk_units) {
-    const uint64_t text_per_unit = sc.paired ? 2 * (2 * (uint64_t)args.read_length + 4 + 160) : 2 * 24000 + 260;  // (as the range sizes below)
-    return engs.size() > 1 ? run_scope_devices(engs, ordinals, args, genomes, sc, chunk_units, text_per_unit) : run_scope(eng, args, genomes, sc, chunk_units);
+  // a unit's FASTQ text, generously: a pair's two records with their headers; a long read is up to 65 535 bases (u16
+  // lengths) and the gamma profiles average 20 000 (minimal_long.rs:64-65)
+  const uint64_t text_per_unit = is_long ? 2 * 24000 + 260 : 2 * (2 * (uint64_t)args.read_length + 4 + 160);
+  const uint64_t chunk_units = args.device_chunk_reads ? std::max<uint64_t>(args.device_chunk_reads / (is_long ? 1 : 2), 1) : auto_chunk_units(text_per_unit);
+  // the scope of genomes [g0, g1), with the seed of --seed if there is one
+  auto scope = [&](Scope::Kind kind, size_t g0, size_t g1, uint32_t id_base) {
+    Scope sc{kind, {}, {}, pod, args.seed ? 1 : 0, args.seed.value_or(0), id_base, text_per_unit};
+    for (size_t gi = g0; gi < g1; gi++) { sc.idx.push_back((uint32_t)gi); sc.reads.push_back(ab[gi].first); }
+    return sc;
+  };
+  auto run = [&](const Scope& sc) {
+    return engs.size() > 1 ? run_scope_devices(engs, ordinals, args, genomes, sc, chunk_units) : run_scope(eng, args, genomes, sc, chunk_units, &side);
   };
   if (!is_long) {
     info("Simulating short reads");
-    const uint64_t text_per_pair = 2 * (2 * (uint64_t)args.read_length + 4 + 160);
-    const uint64_t chunk_units = chunk_reads ? std::max<uint64_t>(chunk_reads / 2, 1) : auto_chunk_units(text_per_pair);
     // all genomes in one device plan (simulate_pe_reads, simulate.rs:110-150); the library leaves
     // custom profiles to the genome-by-genome loop below
-    std::vector<uint32_t> all_idx(genomes.size());
-    std::vector<uint64_t> all_reads(genomes.size());
-    for (size_t gi = 0; gi < genomes.size(); gi++) { all_idx[gi] = (uint32_t)gi; all_reads[gi] = ab[gi].first; }
-    simmr_plan_info probe{};
-    const int mrc = simmr_pe_plan_multi(eng, (uint32_t)genomes.size(), all_idx.data(), all_reads.data(), &pod, has_seed, seed,
-                                        simmr_range{0, 0}, &probe);  // (an empty range: does the library take this profile in one plan?)
+    Scope all = scope(Scope::PE_ALL, 0, genomes.size(), 0);
+    const int mrc = probe_scope(eng, &all);
     if (mrc != SIMMR_OK && mrc != SIMMR_ENOTSUP) return die(simmr_last_error(eng));
-    // without --seed every plan call would draw its own seed (simulate.rs:174): draw the run's here, so that the ranges
-    // of one genome continue one stream
-    const uint64_t run_seed = has_seed ? seed : probe.seed_used;
-    if (mrc == SIMMR_OK) {
-      Scope sc{true, 0, genomes.size(), {}, 0, nullptr, nullptr};
-      for (size_t gi = 0; gi < genomes.size(); gi++) sc.genome_units.push_back(ab[gi].first / 2);  // simulate.rs:179
-      sc.plan = [&](simmr_engine* en, simmr_range rg, simmr_plan_info* pi) {
-        return simmr_pe_plan_multi(en, (uint32_t)genomes.size(), all_idx.data(), all_reads.data(), &pod, 1, run_seed, rg, pi);
-      };
-      sc.emit = [&](simmr_engine* en, uint32_t idb, const simmr_reads_out* o) { return simmr_pe_emit(en, idb, o); };
-      if (int rc = run(sc, chunk_units)) return rc;
-    }
+    if (mrc == SIMMR_OK)
+      if (int rc = run(all)) return rc;
     uint32_t id_base = 0;  // the global AtomicU32 of simulate.rs:85-89
     for (size_t gi = 0; mrc == SIMMR_ENOTSUP && gi < genomes.size(); gi++) {
       // the reference draws a fresh entropy seed per genome when there is no --seed (simulate.rs:174)
-      uint64_t g_seed = seed;
-      if (!has_seed) {
-        simmr_plan_info p0{};
-        if (simmr_pe_plan(eng, (uint32_t)gi, &pod, ab[gi].first, 0, 0, simmr_range{0, 0}, &p0) != SIMMR_OK) return die(simmr_last_error(eng));
-        g_seed = p0.seed_used;
-      }
-      Scope sc{true, gi, gi + 1, {ab[gi].first / 2}, id_base, nullptr, nullptr};
-      sc.plan = [&, gi, g_seed](simmr_engine* en, simmr_range rg, simmr_plan_info* pi) { return simmr_pe_plan(en, (uint32_t)gi, &pod, ab[gi].first, 1, g_seed, rg, pi); };
-      sc.emit = [&](simmr_engine* en, uint32_t idb, const simmr_reads_out* o) { return simmr_pe_emit(en, idb, o); };
-      if (int rc = run(sc, chunk_units)) return rc;
-      id_base += (uint32_t)(ab[gi].first / 2);
+      Scope sc = scope(Scope::PE_GENOME, gi, gi + 1, id_base);
+      if (!sc.has_seed && probe_scope(eng, &sc) != SIMMR_OK) return die(simmr_last_error(eng));
+      if (int rc = run(sc)) return rc;
+      id_base += (uint32_t)sc.units(0);
     }
   } else {
     info("Simulating long reads");
-    std::vector<uint32_t> idx(genomes.size());
-    std::vector<uint64_t> reads(genomes.size());
-    for (size_t gi = 0; gi < genomes.size(); gi++) { idx[gi] = (uint32_t)gi; reads[gi] = ab[gi].first; }
-    uint64_t run_seed = seed;
-    if (!has_seed) {
-      simmr_plan_info p0{};
-      if (simmr_long_plan(eng, (uint32_t)genomes.size(), idx.data(), reads.data(), &pod, 0, 0, simmr_range{0, 0}, &p0) != SIMMR_OK)
-        return die(simmr_last_error(eng));
-      run_seed = p0.seed_used;
-    }
-    // a long read is up to 65 535 bases (u16 lengths); the gamma profiles average 20 000 (minimal_long.rs:64-65)
-    const uint64_t chunk_units = chunk_reads ? chunk_reads : auto_chunk_units(2 * 24000 + 260);
-    Scope sc{false, 0, genomes.size(), reads, 0, nullptr, nullptr};
-    sc.plan = [&](simmr_engine* en, simmr_range rg, simmr_plan_info* pi) {
-      // (without --seed the library selects per-read lengths by itself; the ranges then share the seed drawn above)
-      simmr_error_profile p = pod;
-      if (!has_seed) p.length_mode = SIMMR_LEN_PER_READ;
-      return simmr_long_plan(en, (uint32_t)genomes.size(), idx.data(), reads.data(), &p, 1, run_seed, rg, pi);
-    };
-    sc.emit = [&](simmr_engine* en, uint32_t idb, const simmr_reads_out* o) { return simmr_long_emit(en, idb, o); };
-    if (int rc = run(sc, chunk_units)) return rc;
+    Scope sc = scope(Scope::LONG, 0, genomes.size(), 0);
+    if (!sc.has_seed && probe_scope(eng, &sc) != SIMMR_OK) return die(simmr_last_error(eng));
+    if (int rc = run(sc)) return rc;
   }
-  info(("Writing simulated reads to " + args.output).c_str());
-  if (!args.stats.empty()) {
-    auto st = std::make_unique<simmr_run_stats>();
-    if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return die(std::string("--stats: ") + simmr_last_error(eng));
-    if (!write_stats_tsv(*st, args.stats, &err)) return die("--stats: " + err);
-  }
-  if (want_depth && !write_depth_files(eng, args, genomes, depth_positions, depth_contigs, &err)) return die("--depth: " + err);
+  info("Writing simulated reads to " + args.output);
+  if (!side.finish(eng, genomes)) return die(side.err);
 
   // main.rs:213-258
   std::vector<MetadataRow> rows;
   for (size_t gi = 0; gi < genomes.size(); gi++) rows.push_back({genomes[gi].uuid, genomes[gi].filepath, ab[gi].first, ab[gi].second});
-  info(("Writing simulation metadata to " + meta_path).c_str());
+  info("Writing simulation metadata to " + meta_path);
   if (!write_metadata(rows, meta_path, &err)) fprintf(stderr, "ERROR simmr-hip: Failed to write metadata file: %s\n", err.c_str());
-  for (simmr_engine* en : engs) simmr_engine_destroy(en);
   return 0;
 }
 

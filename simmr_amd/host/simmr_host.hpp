@@ -9,6 +9,7 @@
 // No simulation arithmetic lives here: reads come from libsimmr_hip.so.
 #pragma once
 #include <cstdint>
+#include <cstdio>
 #include <memory>
 #include <optional>
 #include <string>
@@ -67,6 +68,38 @@ struct MetadataRow {
   std::string genome_id, filepath;
   uint64_t num_reads;
   double abundance;
+};
+// One output file, as every writer here uses it: opened once ("wb" replaces, "ab" appends), text appended through a 1 MiB
+// buffer, closed once.  The open, every fwrite and the fclose end in one status, and the two messages are made here only:
+// "cannot open <path>" and "short write to <path>".
+class OutFile {
+ public:
+  OutFile(const std::string& path, bool append) : path_(path), f_(fopen(path.c_str(), append ? "ab" : "wb")) {
+    if (!f_) error_ = "cannot open " + path_;
+  }
+  OutFile(const OutFile&) = delete;
+  ~OutFile() { if (f_) fclose(f_); }  // (without a word, and the text still buffered is dropped: the way out of a writer that fails)
+  bool ok() const { return error_.empty(); }
+  const std::string& error() const { return error_; }
+  void append(const void* p, size_t n) {
+    if (n == 0) return;
+    if (buf_.size() + n >= BUFFER) { write(buf_.data(), buf_.size()); buf_.clear(); }
+    if (n >= BUFFER) write(p, n);  // (a block this large goes to the file as it is)
+    else buf_.append((const char*)p, n);
+  }
+  void append(const std::string& s) { append(s.data(), s.size()); }
+  bool close(std::string* err) {  // false with *err = error() if anything failed since the open
+    write(buf_.data(), buf_.size()); buf_.clear();
+    if (f_ && fclose(f_) != 0 && ok()) error_ = "short write to " + path_;
+    f_ = nullptr;
+    if (!ok()) *err = error_;
+    return ok();
+  }
+ private:
+  static constexpr size_t BUFFER = 1u << 20;
+  void write(const void* p, size_t n) { if (f_ && ok() && n && fwrite(p, 1, n, f_) != n) error_ = "short write to " + path_; }
+  std::string path_, error_, buf_;
+  FILE* f_;
 };
 bool write_metadata(const std::vector<MetadataRow>& rows, const std::string& output, std::string* err);
 // Rust `{}` for f64: shortest digits that round-trip, never scientific notation
@@ -133,6 +166,9 @@ bool write_depth_track_tsv(const std::vector<Genome>& genomes, const simmr_depth
 class ErrorProfile {  // error_profiles/base.rs:6-32 (the per-read methods run on the device)
  public:
   virtual ~ErrorProfile() = default;
+  // extensions of the long-read kinds (--per-read-lengths / --uniform-start), read by their pod()
+  uint32_t length_mode = SIMMR_LEN_REFERENCE;
+  uint8_t long_start_mode = SIMMR_START_REFERENCE;
   virtual simmr_error_profile pod() const = 0;
   virtual uint16_t minimum_genome_size() const = 0;
   virtual bool is_long_read() const = 0;
@@ -156,8 +192,6 @@ struct MinimalLongErrorProfile : ErrorProfile {  // minimal_long.rs
   uint16_t read_length = 20000;  // unused by the reference (minimal_long.rs:64-65 hard-codes the gamma)
   double read_length_std = 5000.0;
   float gamma_mean = 20000.0f, gamma_std = 15000.0f;
-  uint32_t length_mode = SIMMR_LEN_REFERENCE;
-  uint8_t long_start_mode = SIMMR_START_REFERENCE;
   simmr_error_profile pod() const override;
   uint16_t minimum_genome_size() const override { return 20000; }
   bool is_long_read() const override { return true; }
@@ -170,8 +204,6 @@ struct CustomShortErrorProfile : ErrorProfile {  // custom_short.rs (model read 
   std::vector<uint8_t> model;  // bincode ErrorModelParams, handed to the library as is
   double read_length_mean = 0, insert_size_mean = 0;
   bool is_long = false;
-  uint32_t length_mode = SIMMR_LEN_REFERENCE;       // custom-long only
-  uint8_t long_start_mode = SIMMR_START_REFERENCE;  // custom-long only
   // shared/src/encoding.rs:268-281 deserialize_model_from_path
   static std::unique_ptr<CustomShortErrorProfile> from_path(const std::string& path, std::string* err);
   simmr_error_profile pod() const override;

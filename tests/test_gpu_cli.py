@@ -348,3 +348,24 @@ def test_cli_rng_philox(workdir, oracle, profile, cls, mode):
     assert outs[0] == exp
     r = subprocess.run([str(EXE), "--genome", str(d / "g1.fna"), "--output", str(d / "x.fq"), "--rng", "xorshift"], capture_output=True)
     assert r.returncode != 0
+
+
+def test_cli_an_id_with_a_brace_goes_to_the_host_writer(workdir, oracle):
+    """A sequence id with a brace: simmr_fastq_plan_direct answers SIMMR_ENOTSUP on the first range and the host writer frames
+    the run from there, range by range.  The file is the oracle's bytes and the file --host-fastq writes; with --truth, which
+    takes the column route from the start, the same, and the truth file has a line per read."""
+    d, _ = workdir
+    contigs = _synth.synthetic_contigs([20_000], 31)
+    _synth.write_fasta(d / "brace.fna", contigs, ["chr{1}"])
+    (d / "brace.tsv").write_text(f"path\tid\n{d}/brace.fna\tgb\n")
+    outs = []
+    for tag, extra in (("dev", []), ("host", ["--host-fastq"]), ("truth", ["--truth", str(d / "brace_truth.tsv")])):
+        subprocess.check_call([str(EXE), "--genome-file", str(d / "brace.tsv"), "--output", str(d / f"brace_{tag}.fq"), "--num-reads", "600",
+                               "--seed", "5", "--error-profile", "minimal-short", "--device-chunk-reads", "100"] + extra)
+        outs.append((d / f"brace_{tag}.fq").read_bytes())
+    o = _oracle.simulate_pe(oracle, _oracle.HostGenome(contigs), MinimalShortErrorProfile().pod(), 600, 5, qual_offset=33)
+    assert o.n_reads == 600
+    exp = fastq_of(o.trimmed(), o.n_reads, ["chr{1}"], "gb", True)
+    assert b"sid=chr{1}|" in exp and outs[0] == exp and outs[1] == exp and outs[2] == exp
+    truth = (d / "brace_truth.tsv").read_text().split("\n")
+    assert truth[0].startswith("read_id\tpair\t") and len(truth) == 1 + 600 + 1 and truth[-1] == ""
