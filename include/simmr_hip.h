@@ -112,7 +112,10 @@ enum simmr_profile_kind {
  *   Minimal-short, and minimal-long / perfect-long with SIMMR_LEN_PER_READ (the one constant length of a seeded reference
  *   run, simulate.rs:358, is a property of its stream); not the custom profiles.  Restated in oracle/ (rand08.c: the
  *   generator's second word source; simulate.c: orc_pe_outer_ctr), compared bit for bit; law tests in
- *   tests/test_gpu_parity.py::test_philox_full_*. */
+ *   tests/test_gpu_parity.py::test_philox_full_*.
+ * The second counter word names the domain of a draw: 0 and 1 the two levels of the per-base draws, 2 the k-mer splice,
+ * 3 the word streams of the plan, 4 the outer stream — and 5 the strain sites, which belong to a staged genome and to no
+ * rng mode: "strain sites, version 1" is stated with simmr_strain_plan below. */
 enum simmr_rng_mode { SIMMR_RNG_REFERENCE = 0, SIMMR_RNG_PHILOX = 1, SIMMR_RNG_PHILOX_FULL = 2 };
 
 /* Long-read length policy (Appendix A Q5 of SURVEY.md).
@@ -633,6 +636,51 @@ int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_
 /* HIP-event time (ms) of the last simmr_depth_add's device work plus that of the simmr_depth_emit and the
  * simmr_depth_summarize after it, if any.  Synchronises the stream. */
 int simmr_last_depth_ms(simmr_engine* e, float* ms);
+
+/* ---- strain divergence: a genome that is N % identical to the one that was staged --------------------------------
+ * Replaces nothing in the reference, whose --with-ani flag ("Generate reads with an average identity of N (compared to
+ * their reference)", cli.rs:185-191) is declared and never read.  Average nucleotide identity is a property of a strain:
+ * the same differences in every read that covers a site, which no per-read error rate gives.  The pass substitutes bases
+ * of a staged genome IN PLACE in its 2-bit plane (no second copy of the genome) and lists the sites.  Substitutions keep
+ * every coordinate, so plans, headers, depth and statistics work unchanged on the diverged genome; simmr_truth_* diffs
+ * reads against the genome they were drawn from — the diverged one — and so keeps reporting the sequencing errors, while
+ * the site list reports the strain's differences: together the full truth against the original assembly.
+ *
+ * Strain sites, version 1 (restated in DESIGN.md section 4 and, independently, in tests/_strain.py, which the kernels are
+ * compared with byte for byte).  Inputs: a staged genome, identity (a double, 0.25 <= identity <= 1), a 64-bit seed.
+ *   T32 = floor((1 - identity) * 2^32 + 0.5) (at most 3 * 2^30); A = ceil(T32 / 3), B = ceil(2 T32 / 3), in integers.
+ *   The base at position pos (0-based, in Seq.seq coordinates as simmr_unstage_contig sees them) of contig c owns ONE
+ *   32-bit word X: word pos & 3 of the Philox4x32-10 block with key = (seed low word, seed high word) and counter
+ *   (pos >> 2, 5, c, 0x72000003) — domain 5, the next free one after 0-4 (enum simmr_rng_mode).  A contig of 2^34 bases
+ *   or more is refused with SIMMR_ENOTSUP, so pos >> 2 fits the first counter word.
+ *   The base is a SITE iff X < T32 and it is not under the exception plane: an 'N' or '-' stays what it is, its word is
+ *   not used.  At a site s = 1 + (X >= A) + (X >= B) and the new code is (code + s) & 3 over A0 C1 G2 T3 — the alternate
+ *   rule of specification 3 of the per-base draws.
+ *   identity == 1 gives T32 == 0: no sites, planes unchanged bit for bit.  Padding bases between contigs, the pad words in
+ *   front of and behind the plane and the exception plane are never written.
+ * The result is a function of (planes, identity, seed) alone: sites are counted per tile, the counts scanned, the sites
+ * written at their ranks (no atomics hand out slots), so launch geometry never changes a byte. */
+typedef struct simmr_strain_out {   /* DEVICE pointers, caller-owned; any column may be NULL */
+  uint32_t* contig;                 /* index of the site's Seq inside the genome                       */
+  uint64_t* pos;                    /* 0-based position in Seq.seq                                     */
+  uint8_t* ref;                     /* ASCII base before the apply                                     */
+  uint8_t* alt;                     /* ASCII base after it                                             */
+  uint64_t capacity;                /* entries available in each column                                */
+} simmr_strain_out;
+/* Counts the sites per tile and scans the counts into buffers the engine holds; *n_sites = their total.  Changes nothing
+ * else.  SIMMR_EINVAL: the slot is not staged, identity is outside [0.25, 1] or NaN.  SIMMR_ENOTSUP: see above. */
+int simmr_strain_plan(simmr_engine* e, uint32_t genome_idx, double identity, uint64_t seed, uint64_t* n_sites);
+/* Draws again, writes the sites at their ranks — ordered by contig, then by pos ascending — and rewrites the 2-bit plane
+ * in place; synchronises.  out may be NULL (or every column NULL): the genome is diverged all the same.
+ * Counts as a staging call: the truth plan is dropped and the staging epoch counts on exactly as in simmr_stage_genome,
+ * and the plan in force is dropped too (plan again before the next emit).  The strain plan is consumed: a second apply
+ * answers SIMMR_ESTATE, so a genome is not diverged twice by accident.
+ * SIMMR_ESTATE: no simmr_strain_plan for that genome, or a staging call since.  SIMMR_ERANGE, nothing written, the planes
+ * included, and the plan kept: a column is given and capacity < n_sites. */
+int simmr_strain_apply(simmr_engine* e, uint32_t genome_idx, const simmr_strain_out* out);
+/* HIP-event time (ms) of the last simmr_strain_plan's device work (count + scan) plus that of the simmr_strain_apply after
+ * it, if any.  Synchronises the stream. */
+int simmr_last_strain_ms(simmr_engine* e, float* ms);
 
 #ifdef __cplusplus
 }

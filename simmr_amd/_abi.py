@@ -172,6 +172,17 @@ class DepthWindows(C.Structure):
     ]
 
 
+class StrainOut(C.Structure):
+    """struct simmr_strain_out (device pointers as raw addresses)"""
+    _fields_ = [
+        ("contig", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("ref", C.c_void_p),
+        ("alt", C.c_void_p),
+        ("capacity", C.c_uint64),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -231,6 +242,9 @@ SYMBOLS = {
     "simmr_depth_summarize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, _P(DepthContig), C.c_uint64, _P(C.c_uint64),
                                         _P(DepthWindows)]),
     "simmr_last_depth_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_strain_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint64, _P(C.c_uint64)]),
+    "simmr_strain_apply": (C.c_int, [C.c_void_p, C.c_uint32, _P(StrainOut)]),
+    "simmr_last_strain_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

@@ -50,7 +50,7 @@ void depth_destroy(void* q) {
 }
 
 DepthState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, depth_destroy);
+  void** slot = eng_ext_slot(e, ENG_EXT_DEPTH, depth_destroy);
   if (!*slot && create) *slot = new DepthState();
   return (DepthState*)*slot;
 }

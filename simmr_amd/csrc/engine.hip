@@ -182,11 +182,11 @@ struct simmr_engine {
   hipEvent_t st_ev[2] = {nullptr, nullptr};  // the last add's begin / end
   bool st_ready = false, st_timed = false;
 
-  // engine_internal.hpp: the simmr_stage_* calls so far, and the state of the library's other translation unit
-  // (depth.hip: coverage depth) with the function that frees it
+  // engine_internal.hpp: the simmr_stage_* calls so far, and the states of the library's other translation units
+  // (depth.hip: coverage depth, strain.hip: strain divergence) with the functions that free them
   uint64_t staging_epoch = 0;
-  void* ext_slot = nullptr;
-  void (*ext_destroy)(void*) = nullptr;
+  void* ext_slot[ENG_EXT_COUNT] = {};
+  void (*ext_destroy[ENG_EXT_COUNT])(void*) = {};
 
   int fail(int code, const char* fmt, ...) {
     char buf[512];
@@ -1070,9 +1070,23 @@ int eng_fail(simmr_engine* e, int code, const char* fmt, ...) {
   e->err = buf;
   return code;
 }
-void** eng_ext_slot(simmr_engine* e, void (*destroy)(void*)) {
-  e->ext_destroy = destroy;
-  return &e->ext_slot;
+void eng_genome_planes(const simmr_engine* e, uint32_t slot, uint32_t** packed, const uint32_t** mask,
+                       const ContigDev** contigs_device, uint64_t* plane_bases) {
+  const GenomeHost& g = e->genomes[slot];
+  *packed = g.packed.as<uint32_t>() + FRONT_PAD_WORDS;
+  *mask = g.has_exc ? g.mask.as<uint32_t>() + FRONT_PAD_WORDS : nullptr;
+  *contigs_device = g.d_contigs.as<ContigDev>();
+  *plane_bases = g.plane_bases;
+}
+void eng_planes_rewritten(simmr_engine* e) {
+  e->tr_ready = false;
+  e->staging_epoch++;
+  e->plan = PlanState{};
+  if (e->fq.kind == FQPLAN_DIRECT) e->fq = FqState{};
+}
+void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*)) {
+  e->ext_destroy[which] = destroy;
+  return &e->ext_slot[which];
 }
 }  // namespace simmr
 
@@ -1243,7 +1257,8 @@ void simmr_engine_destroy(simmr_engine* e) {
   (void)hipStreamSynchronize(e->stream);
   comm_release(e);
   (void)hipDeviceSynchronize();
-  if (e->ext_slot && e->ext_destroy) e->ext_destroy(e->ext_slot);
+  for (int i = 0; i < ENG_EXT_COUNT; i++)
+    if (e->ext_slot[i] && e->ext_destroy[i]) e->ext_destroy[i](e->ext_slot[i]);
   if (e->plan_stream) (void)hipStreamDestroy(e->plan_stream);
   if (e->ev_plan_done) (void)hipEventDestroy(e->ev_plan_done);
   for (int i = 0; i < 2; i++) if (e->ev_mark[i]) (void)hipEventDestroy(e->ev_mark[i]);

@@ -1,10 +1,11 @@
-// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip) may ask of an engine.  simmr_engine is
+// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip) may ask of an engine.  simmr_engine is
 // defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/simmr_hip.h"
+#include "device_types.hpp"
 
 namespace simmr {
 
@@ -21,8 +22,16 @@ SIMMR_HIDDEN uint64_t eng_contig_len(const simmr_engine* e, uint32_t slot, uint3
 SIMMR_HIDDEN uint64_t eng_staging_epoch(const simmr_engine* e);
 // simmr_engine::fail: stores the message for simmr_last_error and returns `code`
 SIMMR_HIDDEN int eng_fail(simmr_engine* e, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-// One opaque slot per engine for that translation unit's state; simmr_engine_destroy calls `destroy` on a non-null slot
-// (on the engine's device, after the device has been synchronised).
-SIMMR_HIDDEN void** eng_ext_slot(simmr_engine* e, void (*destroy)(void*));
+// The planes of a staged slot (the caller has seen eng_contig_count(e, slot) > 0): the 2-bit plane and the exception plane
+// from their word 0 (*mask = nullptr for a genome of pure ACGT), the device copy of the contig table, the plane's bases.
+SIMMR_HIDDEN void eng_genome_planes(const simmr_engine* e, uint32_t slot, uint32_t** packed, const uint32_t** mask,
+                                    const ContigDev** contigs_device, uint64_t* plane_bases);
+// What a call that rewrites staged bases owes the engine: what every simmr_stage_* call does (the truth plan is dropped,
+// the staging epoch counts on), and the plan in force is dropped with the direct FASTQ plan made from it.
+SIMMR_HIDDEN void eng_planes_rewritten(simmr_engine* e);
+// One opaque slot per engine and translation unit for that unit's state; simmr_engine_destroy calls `destroy` on a non-null
+// slot (on the engine's device, after the device has been synchronised).
+enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_COUNT = 2 };
+SIMMR_HIDDEN void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*));
 
 }  // namespace simmr

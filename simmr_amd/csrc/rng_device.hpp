@@ -104,12 +104,11 @@ struct Tables {
 
 #define SIMMR_ZIG_R 3.654152885361008796
 
-// Philox4x32-10 (Random123 constants; rocRAND's rocrand_philox4x32_10 with subsequence 'simm' | 'r\0\0\3' << 32): the
-// block with key (k0, k1) and counter (c0, c1, 'simm', 'r\0\0\3').  Two v_mad_u64_u32 and two v_bitop3_b32 per round.
 SIMMR_DEV uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96); }
-SIMMR_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+// Philox4x32-10 (Random123 constants): the block with key (k0, k1) and counter (c0, c1, c2, c3).  Two v_mad_u64_u32 and two
+// v_bitop3_b32 per round.
+SIMMR_DEV void philox4x32_10_ctr(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t out[4]) {
   const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-  uint32_t c2 = 0x73696D6Du, c3 = 0x72000003u;
 #pragma unroll
   for (int r = 0; r < 10; r++) {
     const uint64_t p0 = (uint64_t)M0 * c0, p1 = (uint64_t)M1 * c2;  // one v_mad_u64_u32 each
@@ -118,6 +117,11 @@ SIMMR_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1,
     k0 += W0; k1 += W1;
   }
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+// The per-read draws (rocRAND's rocrand_philox4x32_10 with subsequence 'simm' | 'r\0\0\3' << 32): counter
+// (c0, c1, 'simm', 'r\0\0\3').
+SIMMR_DEV void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t k0, uint32_t k1, uint32_t out[4]) {
+  philox4x32_10_ctr(c0, c1, 0x73696D6Du, 0x72000003u, k0, k1, out);
 }
 
 // ---------------------------------------------------------------------------

@@ -392,6 +392,36 @@ class Engine:
         self._check(self.lib.simmr_last_truth_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- strain divergence ------------------------------------------------------------
+    def strain_plan(self, genome_idx: int, identity: float, seed: int) -> int:
+        """Counts the sites that `identity` and `seed` give genome slot `genome_idx` (simmr_strain_plan); returns their total."""
+        total = C.c_uint64(0)
+        self._check(self.lib.simmr_strain_plan(self._h, genome_idx, float(identity), C.c_uint64(seed & (2**64 - 1)), C.byref(total)))
+        return int(total.value)
+
+    def strain(self, genome_idx: int, identity: float, seed: int, sites: bool = True):
+        """Diverges the staged genome in place to `identity` (0.25 .. 1) of what it was (simmr_strain_plan +
+        simmr_strain_apply).  sites=True: the site list as numpy arrays {contig: uint32, pos: uint64, ref: uint8, alt: uint8}
+        (ASCII), ordered by contig, then by position; sites=False: their number alone."""
+        n = self.strain_plan(genome_idx, identity, seed)
+        if not sites:
+            self._check(self.lib.simmr_strain_apply(self._h, genome_idx, None))
+            return n
+        torch = _torch()
+        cols = {"contig": torch.empty(max(n, 1), dtype=torch.int32, device=self.device),
+                "pos": torch.empty(max(n, 1), dtype=torch.int64, device=self.device),
+                "ref": torch.empty(max(n, 1), dtype=torch.uint8, device=self.device),
+                "alt": torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)}
+        out = _abi.StrainOut(cols["contig"].data_ptr(), cols["pos"].data_ptr(), cols["ref"].data_ptr(), cols["alt"].data_ptr(), n)
+        self._check(self.lib.simmr_strain_apply(self._h, genome_idx, C.byref(out)))
+        host = {k: v[:n].cpu().numpy() for k, v in cols.items()}
+        return {"contig": host["contig"].view(np.uint32), "pos": host["pos"].view(np.uint64), "ref": host["ref"], "alt": host["alt"]}
+
+    def last_strain_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_strain_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- run statistics -------------------------------------------------------------
     def stats_reset(self):
         """Zeroes the engine's run-statistics tables and their sticky error (simmr_stats_reset)."""

@@ -310,6 +310,23 @@ bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads,
   return out.close(err);
 }
 
+// --------------------------------------------------------------- strain sites
+bool write_strain_sites_tsv(const Genome& genome, const HostStrainSites& s, const std::string& output, bool with_header,
+                            std::string* err) {
+  OutFile out(output, true);
+  if (with_header) out.append("genome_id\tsequence_id\tposition\tref\talt\n");
+  char buf[64];
+  std::string line;
+  for (size_t i = 0; i < s.pos.size() && out.ok(); i++) {
+    if (s.contig[i] >= genome.sequence.size()) { *err = "site " + std::to_string(i) + " names a sequence the genome does not have"; return false; }
+    line = genome.uuid; line += '\t'; line += genome.sequence[s.contig[i]].id;
+    snprintf(buf, sizeof buf, "\t%llu\t%c\t%c\n", (unsigned long long)s.pos[i], (char)s.ref[i], (char)s.alt[i]);
+    line += buf;
+    out.append(line);
+  }
+  return out.close(err);
+}
+
 // --------------------------------------------------------------- run statistics
 bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::string* err) {
   std::string text = "table\tset\ti\tj\tcount\n";
@@ -494,7 +511,9 @@ std::string usage() {
          "                                 which the reference's own enum cannot select, cli.rs:62-70)\n"
          "  --abundance-profile <P>       exact | uniform | custom [default: uniform]\n"
          "  --custom-profile <FILE>       Filepath to a custom error profile (simmrd model) for custom-short\n"
-         "  --with-ani <N>                [not implemented, as in the reference]\n"
+         "  --with-ani <N>                Generate reads with an average identity of N percent (25 .. 100, decimals accepted)\n"
+         "                                compared to their reference: every genome becomes a strain, with the same substitutions\n"
+         "                                in every read that covers a site (declared and never read in the reference, cli.rs:185-191)\n"
          "  --read-header-format <FMT>    header template ({:genome_id:} {:read_id:} {:pair:} {:sequence_id:} ...)\n"
          "  --seed <N>                    Random seed\n"
          "  --size-adjusted               Adjust by genome size\n"
@@ -511,7 +530,10 @@ std::string usage() {
          "                            (read depth, mates counted separately; counted on the device from every range of the run;\n"
          "                             combines with --truth and --stats; not with --devices)\n"
          "            --depth-track <FILE>  the same per window: genome_id sequence_id start end depth_sum covered depth_max\n"
-         "            --depth-window <W>    positions per window of --depth-track [default: 1000]\n";
+         "            --depth-window <W>    positions per window of --depth-track [default: 1000]\n"
+         "            --strain-sites <FILE>  the sites --with-ani changed, as a TSV: genome_id sequence_id position ref alt (position 0-based;\n"
+         "                            drawn and listed on the device; with --truth, which reports the sequencing errors against the strain,\n"
+         "                            the full truth against the original assembly; needs --with-ani; with --devices written from the first)\n";
 }
 
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
@@ -574,7 +596,13 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
       else { *err = "invalid value '" + v + "' for '--abundance-profile'"; return false; }
     }
     else if (arg == "--custom-profile") { if (!need(&v)) return false; a->custom_profile = v; }
-    else if (arg == "--with-ani") { if (!uint(0, 255)) return false; a->with_ani = (uint8_t)u; }
+    else if (arg == "--with-ani") {  // a percentage in plain decimal notation: digits, at most one point
+      const bool plain = need(&v) && v.find_first_not_of("0123456789.") == std::string::npos && v.find_first_of("0123456789") != std::string::npos &&
+                         std::count(v.begin(), v.end(), '.') <= 1;
+      const double pct = plain ? strtod(v.c_str(), nullptr) : 0.0;
+      if (!(pct >= 25.0 && pct <= 100.0)) { *err = "invalid value for --with-ani"; return false; }
+      a->with_ani = pct;
+    }
     else if (arg == "--read-header-format") { if (!need(&v)) return false; a->read_header_format = v; }
     else if (arg == "--seed") { if (!uint(0, UINT64_MAX)) return false; a->seed = u; }
     else if (arg == "--size-adjusted") a->size_adjusted = true;
@@ -585,6 +613,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
+    else if (arg == "--strain-sites") { if (!file(&a->strain_sites)) return false; }
     else if (arg == "--depth-window") { if (!uint(1, (1u << 30) - 1, " (1 .. 2^30 - 1)")) return false; a->depth_window = (uint32_t)u; }
     else if (arg == "--device-chunk-reads") { if (!uint(1, UINT64_MAX)) return false; a->device_chunk_reads = u; }
     else if (arg == "--devices") {
@@ -617,6 +646,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--uniform-start") a->uniform_start = true;
     else { *err = "Found argument '" + arg + "' which wasn't expected"; return false; }
   }
+  if (!a->strain_sites.empty() && !a->with_ani) { *err = "--strain-sites needs --with-ani"; return false; }
   // cli.rs:88-92: ArgGroup "genomes" is required, and --output has no default
   if (a->genome.empty() && !a->genome_file) { *err = "one of --genome / --genome-file is required"; return false; }
   if (!a->genome.empty() && a->genome_file) { *err = "--genome and --genome-file cannot be used together"; return false; }
@@ -751,6 +781,18 @@ char* simmr_host_truth_tsv(uint64_t n_reads, int paired, const uint32_t* read_id
   t.edit_alt.assign(edit_alt, edit_alt + m); t.edit_qual.assign(edit_qual, edit_qual + m);
   std::string err;
   if (!write_truth_tsv(genomes, h, t, qual_offset, path, with_header != 0, &err)) return dup_str("ERR\t" + err);
+  return dup_str("OK");
+}
+// The strain-site TSV of write_strain_sites_tsv for columns given as plain arrays; the genome's names: its id and its
+// n_contigs sequence ids.  Returns "OK", or "ERR\t..." .
+char* simmr_host_strain_tsv(uint64_t n_sites, const uint32_t* contig, const uint64_t* pos, const uint8_t* ref, const uint8_t* alt,
+                            const char* genome_id, uint32_t n_contigs, const char* const* sequence_id, int with_header, const char* path) {
+  const std::vector<Genome> genomes = genomes_from_names(1, &genome_id, &n_contigs, sequence_id);
+  HostStrainSites s;
+  s.contig.assign(contig, contig + n_sites); s.pos.assign(pos, pos + n_sites);
+  s.ref.assign(ref, ref + n_sites); s.alt.assign(alt, alt + n_sites);
+  std::string err;
+  if (!write_strain_sites_tsv(genomes[0], s, path, with_header != 0, &err)) return dup_str("ERR\t" + err);
   return dup_str("OK");
 }
 // The statistics TSV of write_stats_tsv for a simmr_run_stats in host memory.  Returns "OK", or "ERR\t..." .

@@ -120,6 +120,35 @@ static bool write_depth_files(simmr_engine* eng, const CliArgs& args, const std:
   return write_depth_track_tsv(genomes, rows.data(), n_contigs, args.depth_window, ws.data(), wc.data(), wm.data(), args.depth_track, err);
 }
 
+// `--with-ani` / `--strain-sites`: genome i of the run becomes a strain on every engine (simmr_strain_plan /
+// simmr_strain_apply with the seed run seed + 0x9E3779B97F4A7C15 (i + 1)); the outcome is a function of the inputs, so the
+// engines' copies agree, and the sites are listed from the first engine.
+static bool diverge_genomes(const std::vector<simmr_engine*>& engs, const CliArgs& args, const std::vector<Genome>& genomes,
+                            uint64_t run_seed, std::string* err) {
+  const bool list = !args.strain_sites.empty();
+  if (list && is_regular_file(args.strain_sites)) remove(args.strain_sites.c_str());
+  for (size_t gi = 0; gi < genomes.size(); gi++) {
+    const uint64_t seed = run_seed + 0x9E3779B97F4A7C15ull * (uint64_t)(gi + 1);
+    for (size_t k = 0; k < engs.size(); k++) {
+      uint64_t n = 0;
+      if (simmr_strain_plan(engs[k], (uint32_t)gi, *args.with_ani / 100.0, seed, &n) != SIMMR_OK) { *err = simmr_last_error(engs[k]); return false; }
+      if (k > 0 || !list) {
+        if (simmr_strain_apply(engs[k], (uint32_t)gi, nullptr) != SIMMR_OK) { *err = simmr_last_error(engs[k]); return false; }
+        continue;
+      }
+      DeviceMem mem;  // (on the first engine's device: the plan call selected it)
+      simmr_strain_out o{};
+      o.capacity = n;
+      if (!(mem.alloc(&o.contig, n) && mem.alloc(&o.pos, n) && mem.alloc(&o.ref, n) && mem.alloc(&o.alt, n))) { *err = "device allocation failed"; return false; }
+      if (simmr_strain_apply(engs[k], (uint32_t)gi, &o) != SIMMR_OK) { *err = simmr_last_error(engs[k]); return false; }
+      HostStrainSites h;
+      if (!(mem.fetch(&h.contig, o.contig, n) && mem.fetch(&h.pos, o.pos, n) && mem.fetch(&h.ref, o.ref, n) && mem.fetch(&h.alt, o.alt, n))) { *err = "copy back failed"; return false; }
+      if (!write_strain_sites_tsv(genomes[gi], h, args.strain_sites, gi == 0, err)) return false;
+    }
+  }
+  return true;
+}
+
 // The side outputs of a run: --truth, --stats, --depth and --depth-track.  They read the columns, so a run that wants one
 // takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
 struct SideOutputs {
@@ -655,7 +684,16 @@ static int run_main(int argc, char** argv) {
   if (is_regular_file(args.output)) remove(args.output.c_str());  // (a pipe or a device given as the output is written to, not replaced)
   const std::string meta_path = args.output + ".tsv";
   if (exists(meta_path)) remove(meta_path.c_str());
-  if (!side.begin(eng, genomes)) return die(side.err);
+  // Once, before the run's first range: --with-ani diverges the staged genomes with the run's seed — that of --seed, or the
+  // one the run's first probe_scope drew — and then the side outputs begin (depth[] is laid out for the genomes as they
+  // are from now on).
+  bool begun = false;
+  auto begin_run = [&](const Scope& sc) {
+    if (begun) return 0;
+    begun = true;
+    if (args.with_ani && !diverge_genomes(engs, args, genomes, sc.seed, &err)) return die("--with-ani: " + err);
+    return side.begin(eng, genomes) ? 0 : die(side.err);
+  };
 
   simmr_error_profile pod = eprofile->pod();
   if (args.rng_philox) {  // (extension) the counter mode, for the profiles that draw per base from a parametric law
@@ -690,13 +728,16 @@ static int run_main(int argc, char** argv) {
     Scope all = scope(Scope::PE_ALL, 0, genomes.size(), 0);
     const int mrc = probe_scope(eng, &all);
     if (mrc != SIMMR_OK && mrc != SIMMR_ENOTSUP) return die(simmr_last_error(eng));
-    if (mrc == SIMMR_OK)
+    if (mrc == SIMMR_OK) {
+      if (int rc = begin_run(all)) return rc;
       if (int rc = run(all)) return rc;
+    }
     uint32_t id_base = 0;  // the global AtomicU32 of simulate.rs:85-89
     for (size_t gi = 0; mrc == SIMMR_ENOTSUP && gi < genomes.size(); gi++) {
       // the reference draws a fresh entropy seed per genome when there is no --seed (simulate.rs:174)
       Scope sc = scope(Scope::PE_GENOME, gi, gi + 1, id_base);
       if (!sc.has_seed && probe_scope(eng, &sc) != SIMMR_OK) return die(simmr_last_error(eng));
+      if (int rc = begin_run(sc)) return rc;
       if (int rc = run(sc)) return rc;
       id_base += (uint32_t)sc.units(0);
     }
@@ -704,6 +745,7 @@ static int run_main(int argc, char** argv) {
     info("Simulating long reads");
     Scope sc = scope(Scope::LONG, 0, genomes.size(), 0);
     if (!sc.has_seed && probe_scope(eng, &sc) != SIMMR_OK) return die(simmr_last_error(eng));
+    if (int rc = begin_run(sc)) return rc;
     if (int rc = run(sc)) return rc;
   }
   info("Writing simulated reads to " + args.output);

@@ -140,6 +140,21 @@ struct HostTruth {
 bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads, const HostTruth& truth, uint32_t qual_offset,
                      const std::string& output, bool with_header, std::string* err);
 
+// ---------------------------------------------------------------- strain sites (no reference counterpart)
+// Host copy of simmr_strain_out for one genome.
+struct HostStrainSites {
+  std::vector<uint32_t> contig;
+  std::vector<uint64_t> pos;
+  std::vector<uint8_t> ref, alt;
+};
+// `simmr-hip --strain-sites FILE`: a line of column names, then one tab-separated line per site of `genome`, in the order
+// of the columns (sequence, then position):
+//   genome_id  sequence_id  position  ref  alt
+// position 0-based inside the sequence; the ids are the ones the FASTQ headers use.  with_header: the line of column names
+// first (simmr-hip writes it with the run's first genome; every further genome appends its sites).  Appends to `output`.
+bool write_strain_sites_tsv(const Genome& genome, const HostStrainSites& sites, const std::string& output, bool with_header,
+                            std::string* err);
+
 // ---------------------------------------------------------------- run statistics (no reference counterpart)
 // `simmr-hip --stats FILE`: the tables of a simmr_run_stats (include/simmr_hip.h) in long form, tab-separated:
 //   table  set  i  j  count
@@ -253,7 +268,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   ErrorProfileKind error_profile = ErrorProfileKind::PerfectShort;
   AbundanceProfileKind abundance_profile = AbundanceProfileKind::Uniform;
   std::optional<std::string> custom_profile;
-  std::optional<uint8_t> with_ani;
+  std::optional<double> with_ani;  // a percentage, 25 .. 100 (decimals accepted): every genome of the run becomes a strain of that identity
   std::string read_header_format =
       "@{:read_id:}|{:genome_id:}/{:pair:} metadata:sid={:sequence_id:}|sp={:start_position:}|ep={:end_position:}|rc={:reverse_complement:}";
   std::optional<uint64_t> seed;
@@ -269,6 +284,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions
   uint32_t depth_window = 1000;  // --depth-window W
+  std::string strain_sites;      // --strain-sites FILE: the sites --with-ani changed (simmr_strain_apply's columns) as a TSV
   uint64_t device_chunk_reads = 0;  // --device-chunk-reads: reads generated per device pass (0: what fits the free device memory)
   std::optional<std::pair<float, float>> gamma;  // --gamma mean,std
   bool uniform_start = false;                    // --uniform-start (SIMMR_START_UNIFORM)

@@ -43,6 +43,26 @@ def _prefer_layout(backend, read_slots: int) -> None:
         backend.set_read_slots(read_slots)
 
 
+STRAIN_SEED_STEP = 0x9E3779B97F4A7C15
+
+
+def strain_seed(seed: int, i: int) -> int:
+    """The seed that diverges genome i (0-based, in run order) of a run with seed `seed`: simmr-hip --with-ani's rule."""
+    return (seed + STRAIN_SEED_STEP * (i + 1)) & U64_MAX
+
+
+def diverge_genomes(backend, genomes: Sequence[GenomeRef], with_ani: float, seed: int, sites: bool = True):
+    """--with-ani: every staged genome of the run becomes a strain that is `with_ani` percent (25 .. 100) identical to what
+    was staged (Engine.strain: in place, once — call it once per staging).  Returns one Engine.strain result per genome: the
+    site columns, or the site count with sites=False.  Every rank of a run diverges its own copy; the outcome is a function
+    of (genome, with_ani, seed), so the copies agree."""
+    if not 25.0 <= with_ani <= 100.0:  # (False for NaN)
+        raise ValueError("with_ani is a percentage between 25 and 100")
+    if seed is None:
+        raise ValueError("with_ani needs a seed: the strain is a function of it")
+    return [backend.strain(g.index, with_ani / 100.0, strain_seed(seed, i), sites=sites) for i, g in enumerate(genomes)]
+
+
 def split_range(total: int, rank: int, world: int) -> Tuple[int, int]:
     """Contiguous [first, first+count) share of `total` units for `rank`."""
     lo = total * rank // world
@@ -149,10 +169,12 @@ def compose_outer_summaries(pieces, summaries, want):
 
 def simulate_pe_reads(backend, num_reads: int, genomes: Sequence[GenomeRef], error_profile: ErrorProfile,
                       abundance_profile: AbundanceProfile, seed: Optional[int], rank: int = 0, world: int = 1,
-                      qual_offset: int = 0, read_slots: int = 16):
+                      qual_offset: int = 0, read_slots: int = 16, with_ani: Optional[float] = None):
     """Returns one tuple per genome, like simulate.rs:119:
     (filepath, uuid, genome_reads, abundance, reads-of-this-rank or None)."""
     _prefer_layout(backend, read_slots)
+    if with_ani is not None:  # (the genomes as staged become strains, once: stage again before the next such call)
+        diverge_genomes(backend, genomes, with_ani, seed, sites=False)
     ab = determine_reads(num_reads, genomes, error_profile, abundance_profile, True)
     reads_per_genome = [r for r, _ in ab]
     shards = pe_shards(reads_per_genome, rank, world)
@@ -190,13 +212,15 @@ def simulate_pe_reads(backend, num_reads: int, genomes: Sequence[GenomeRef], err
 
 def simulate_pe_reads_batched(backend, num_reads: int, genomes: Sequence[GenomeRef], error_profile: ErrorProfile,
                               abundance_profile: AbundanceProfile, seed: Optional[int], rank: int = 0,
-                              world: int = 1, qual_offset: int = 0, read_slots: int = 16):
+                              world: int = 1, qual_offset: int = 0, read_slots: int = 16, with_ani: Optional[float] = None):
     """simulate_pe_reads (simulate.rs:110-150) with all genomes in ONE device plan
     (`simmr_pe_plan_multi`): same reads, ids and order as the per-genome loop, returned like
     simulate_long_reads as (per-genome metadata, reads of this rank's range of the global pair
     index).  For runs over many genomes (BASELINE config 4) this removes the per-genome launch
     and synchronisation cost."""
     _prefer_layout(backend, read_slots)
+    if with_ani is not None:  # (the genomes as staged become strains, once: stage again before the next such call)
+        diverge_genomes(backend, genomes, with_ani, seed, sites=False)
     ab = determine_reads(num_reads, genomes, error_profile, abundance_profile, True)
     reads_per_genome = [r for r, _ in ab]
     first, count = split_range(sum(r // 2 for r in reads_per_genome), rank, world)
@@ -208,10 +232,12 @@ def simulate_pe_reads_batched(backend, num_reads: int, genomes: Sequence[GenomeR
 
 def simulate_long_reads(backend, num_reads: int, genomes: Sequence[GenomeRef], error_profile: ErrorProfile,
                         abundance_profile: AbundanceProfile, seed: Optional[int], rank: int = 0, world: int = 1,
-                        qual_offset: int = 0, read_slots: int = 16):
+                        qual_offset: int = 0, read_slots: int = 16, with_ani: Optional[float] = None):
     """One StdRng stream spans all genomes (simulate.rs:348): the shard is a
     range of global read indices.  Returns (per-genome metadata, reads)."""
     _prefer_layout(backend, read_slots)
+    if with_ani is not None:  # (the genomes as staged become strains, once: stage again before the next such call)
+        diverge_genomes(backend, genomes, with_ani, seed, sites=False)
     ab = determine_reads(num_reads, genomes, error_profile, abundance_profile, False)
     total = sum(r for r, _ in ab)
     first, count = split_range(total, rank, world)
