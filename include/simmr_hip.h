@@ -682,6 +682,53 @@ int simmr_strain_apply(simmr_engine* e, uint32_t genome_idx, const simmr_strain_
  * it, if any.  Synchronises the stream. */
 int simmr_last_strain_ms(simmr_engine* e, float* ms);
 
+/* ---- gold-standard assembly: the covered regions of every genome and their bases ------------------------------------
+ * Replaces nothing in the reference.  The stretches of every genome that a run covered well enough to be assembled, as
+ * coordinates and as sequence: what assemblers and binners are scored against.  depth[], the 2-bit planes and the contig
+ * tables already sit in HBM; this pass turns them into a region list and a base stream without copying either to the host
+ * — and after simmr_strain_apply the planes are the only place where the strain's sequence exists.
+ *
+ * Inputs.  depth_device: a uint32_t array of n_positions entries in the layout of the last simmr_depth_reset — what
+ * simmr_depth_emit wrote, or an entry-wise sum of such arrays; min_depth >= 1; min_len >= 1.
+ * Run.  A maximal set of consecutive positions of one contig with depth[x] >= min_depth.  Runs never span contigs:
+ * depth[] has no padding between contigs, so a run that reaches a contig's last position ends there even if the next
+ * contig's first position qualifies.
+ * Region.  A run of at least min_len positions.
+ * Order.  Regions are ordered as depth[] is: genome slot, contig, start ascending.
+ * Per region k: genome[k], contig[k]; start[k], 0-based, in Seq.seq coordinates as simmr_unstage_contig sees them; len[k];
+ * depth_sum[k], the sum of depth[x] over the region, 64-bit; seq_off[k], the exclusive prefix sum of len;
+ * seq_off[n_regions] = n_bases.
+ * Base stream.  seq[seq_off[k] .. seq_off[k] + len[k]) holds the ASCII bases of the region as staged now: byte for byte
+ * what simmr_unstage_contig(genome, contig, start, len) returns — 'N' and '-' as themselves, the strain's bases after
+ * simmr_strain_apply.  There are no separators.
+ * Determinism.  Every output is a function of (depth[], planes, min_depth, min_len) alone: ranks come from counts and
+ * scans, never from an atomic that hands out slots (depth_sum is summed with integer atomic adds, whose order changes
+ * nothing). */
+typedef struct simmr_regions_out {   /* DEVICE pointers, caller-owned; any column may be NULL */
+  uint32_t* genome; uint32_t* contig; uint64_t* start; uint64_t* len; uint64_t* depth_sum;
+  uint64_t* seq_off;                 /* n_regions + 1 entries */
+  uint64_t capacity;                 /* regions each column holds (seq_off: capacity + 1) */
+  uint8_t* seq; uint64_t seq_capacity; /* the base stream, 16-byte aligned, and the bytes it holds; NULL skips the bases */
+} simmr_regions_out;
+/* Counts the runs per tile, scans, pairs run starts with run ends, flags the regions among the runs and ranks them — all
+ * into buffers the engine holds (sized from the counted runs and regions, not from n_positions); writes nothing to the
+ * caller's buffers but *n_regions and *n_bases.  Runs on the engine's stream and synchronises.  depth_device is 16-byte
+ * aligned.
+ * SIMMR_ESTATE: no simmr_depth_reset yet, or a staging call since (the epoch check of simmr_depth_add).  SIMMR_EINVAL:
+ * min_depth == 0 or min_len == 0.  SIMMR_ENOMEM: the run buffers cannot be had. */
+int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t min_depth, uint64_t min_len, uint64_t* n_regions,
+                       uint64_t* n_bases);
+/* Writes the columns that are given and, if out->seq is given, the base stream; synchronises.  The call is made with the
+ * SAME depth_device contents as the plan: the regions are the plan's, and depth[] is read again only for depth_sum (over
+ * the plan's regions; it may be NULL when depth_sum is).  The plan stays valid for repeated emits until the next
+ * simmr_regions_plan, simmr_depth_reset or staging call.
+ * SIMMR_ESTATE: no plan for this epoch.  SIMMR_ERANGE, nothing written, the plan kept: a column is given and capacity <
+ * n_regions, or seq is given and seq_capacity < n_bases. */
+int simmr_regions_emit(simmr_engine* e, const uint32_t* depth_device, const simmr_regions_out* out);
+/* HIP-event time (ms) of the last simmr_regions_plan (first launch to last, the two read-backs of counts in between
+ * included) plus that of the simmr_regions_emit after it, if any.  Synchronises the stream. */
+int simmr_last_regions_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

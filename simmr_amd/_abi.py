@@ -183,6 +183,21 @@ class StrainOut(C.Structure):
     ]
 
 
+class RegionsOut(C.Structure):
+    """struct simmr_regions_out (device pointers as raw addresses)"""
+    _fields_ = [
+        ("genome", C.c_void_p),
+        ("contig", C.c_void_p),
+        ("start", C.c_void_p),
+        ("len", C.c_void_p),
+        ("depth_sum", C.c_void_p),
+        ("seq_off", C.c_void_p),
+        ("capacity", C.c_uint64),
+        ("seq", C.c_void_p),
+        ("seq_capacity", C.c_uint64),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -245,6 +260,9 @@ SYMBOLS = {
     "simmr_strain_plan": (C.c_int, [C.c_void_p, C.c_uint32, C.c_double, C.c_uint64, _P(C.c_uint64)]),
     "simmr_strain_apply": (C.c_int, [C.c_void_p, C.c_uint32, _P(StrainOut)]),
     "simmr_last_strain_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_regions_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_regions_emit": (C.c_int, [C.c_void_p, C.c_void_p, _P(RegionsOut)]),
+    "simmr_last_regions_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

@@ -20,7 +20,7 @@ struct DepthState {
   std::vector<uint64_t> cfirst;           // n_contigs + 1
   std::vector<uint32_t> c_genome, c_contig;
   std::vector<uint64_t> fwin;             // n_contigs + 1, of the last summarize
-  uint64_t n_positions = 0, n_tiles = 0, epoch = 0, added = 0;
+  uint64_t n_positions = 0, n_tiles = 0, epoch = 0, added = 0, resets = 0;
   bool ready = false, timed = false, emitted = false, summarized = false;
   void *diff = nullptr, *tile_sum = nullptr, *d_slots = nullptr, *d_cfirst = nullptr, *d_fwin = nullptr, *d_out = nullptr;
   size_t diff_cap = 0, tile_cap = 0, slots_cap = 0, cfirst_cap = 0, fwin_cap = 0, out_cap = 0;  // bytes
@@ -70,6 +70,17 @@ int sync_check(simmr_engine* e, const char* what) {
 
 }  // namespace
 
+// engine_internal.hpp: what regions.hip reads of the layout
+namespace simmr {
+bool depth_layout(simmr_engine* e, DepthLayout* out) {
+  DepthState* s = state_of(e, false);
+  if (!s || !s->ready) return false;
+  *out = DepthLayout{s->cfirst.data(), (const uint64_t*)s->d_cfirst, s->c_genome.data(), s->c_contig.data(), s->c_genome.size(),
+                     s->n_positions, s->epoch, s->resets};
+  return true;
+}
+}  // namespace simmr
+
 extern "C" {
 
 int simmr_depth_reset(simmr_engine* e, uint64_t* n_positions, uint64_t* n_contigs) {
@@ -111,6 +122,7 @@ int simmr_depth_reset(simmr_engine* e, uint64_t* n_positions, uint64_t* n_contig
   s->timed = s->emitted = s->summarized = false;
   if (int rc = sync_check(e, "depth reset")) return rc;  // (the tables were copied from vectors the next reset rewrites)
   s->ready = true;
+  s->resets++;
   if (n_positions) *n_positions = s->n_positions;
   if (n_contigs) *n_contigs = s->c_genome.size();
   return SIMMR_OK;

@@ -508,6 +508,45 @@ class Engine:
         self._check(self.lib.simmr_last_depth_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- gold-standard assembly ---------------------------------------------------------
+    REGION_COLUMNS = (("genome", np.uint32), ("contig", np.uint32), ("start", np.uint64), ("len", np.uint64),
+                      ("depth_sum", np.uint64), ("seq_off", np.uint64))
+
+    def regions_plan(self, depth, min_depth: int = 1, min_len: int = 1):
+        """Counts the regions of `depth` (a CUDA uint32 tensor in the layout of the last depth_reset) and their bases
+        (simmr_regions_plan); returns (n_regions, n_bases)."""
+        nr, nb = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.simmr_regions_plan(self._h, C.c_void_p(depth.data_ptr()), int(min_depth), int(min_len), C.byref(nr), C.byref(nb)))
+        return int(nr.value), int(nb.value)
+
+    def regions_emit(self, depth, out: "_abi.RegionsOut"):
+        """Writes the columns and the base stream that `out` gives of the plan in force (simmr_regions_emit)."""
+        self._check(self.lib.simmr_regions_emit(self._h, C.c_void_p(depth.data_ptr()) if depth is not None else None, C.byref(out)))
+
+    def regions(self, min_depth: int = 1, min_len: int = 1, depth=None, seq: bool = True) -> dict:
+        """The gold-standard assembly of `depth` (default: self.depth()): every run of at least `min_len` consecutive positions
+        of one contig with depth >= `min_depth` (simmr_regions_plan + simmr_regions_emit).  numpy columns genome, contig
+        (uint32), start, len, depth_sum (uint64) per region and seq_off (uint64, one more entry), ordered as depth[] is; "seq":
+        the regions' bases as staged now, back to back, as a CUDA uint8 tensor of seq_off[-1] bytes (None with seq=False)."""
+        torch = _torch()
+        if depth is None:
+            depth = self.depth()
+        n, nb = self.regions_plan(depth, min_depth, min_len)
+        dt = {np.uint32: torch.int32, np.uint64: torch.int64}
+        cols = {name: torch.empty(n + 1, dtype=dt[t], device=self.device) for name, t in self.REGION_COLUMNS}
+        bases = torch.empty((nb + 15) // 16 * 16 + 16, dtype=torch.uint8, device=self.device) if seq else None
+        out = _abi.RegionsOut(*[cols[name].data_ptr() for name, _ in self.REGION_COLUMNS], n,
+                              bases.data_ptr() if seq else None, bases.numel() if seq else 0)
+        self.regions_emit(depth, out)
+        res = {name: cols[name][: n + (name == "seq_off")].cpu().numpy().view(t) for name, t in self.REGION_COLUMNS}
+        res["seq"] = bases[:nb] if seq else None
+        return res
+
+    def last_regions_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_regions_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- counters / timing --------------------------------------------------------
     def counters(self) -> np.ndarray:
         host = (C.c_uint64 * _abi.N_COUNTERS)()

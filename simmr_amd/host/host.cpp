@@ -403,6 +403,63 @@ bool write_depth_track_tsv(const std::vector<Genome>& genomes, const simmr_depth
   return out.close(err);
 }
 
+// --------------------------------------------------------------- gold-standard assembly
+// the sequence a region lies on, or nullptr with *err set; the columns must agree in length and seq_off must ascend inside seq
+static const Seq* region_names(const std::vector<Genome>& genomes, const HostRegions& r, size_t k, bool with_seq, std::string* err) {
+  if (r.genome[k] >= genomes.size() || r.contig[k] >= genomes[r.genome[k]].sequence.size()) {
+    *err = "region " + std::to_string(k) + " names a genome or sequence the run does not have";
+    return nullptr;
+  }
+  if (with_seq && (r.seq_off[k] > r.seq.size() || r.len[k] > r.seq.size() - r.seq_off[k])) {
+    *err = "region " + std::to_string(k) + " leaves the base stream";
+    return nullptr;
+  }
+  return &genomes[r.genome[k]].sequence[r.contig[k]];
+}
+static bool region_columns_agree(const HostRegions& r, std::string* err) {
+  const size_t n = r.genome.size();
+  if (r.contig.size() == n && r.start.size() == n && r.len.size() == n && r.depth_sum.size() == n && r.seq_off.size() == n + 1) return true;
+  *err = "the region columns differ in length";
+  return false;
+}
+
+bool write_gold_fasta(const std::vector<Genome>& genomes, const HostRegions& r, const std::string& output, std::string* err) {
+  if (!region_columns_agree(r, err)) return false;
+  for (size_t k = 0; k < r.genome.size(); k++)
+    if (!region_names(genomes, r, k, true, err)) return false;
+  OutFile out(output, false);  // (opened once every region is known to be good: a refused one leaves the old file)
+  char buf[96];
+  for (size_t k = 0; k < r.genome.size() && out.ok(); k++) {
+    const Seq* s = region_names(genomes, r, k, true, err);
+    out.append(">" + genomes[r.genome[k]].uuid + "|" + s->id);
+    snprintf(buf, sizeof buf, ":%llu-%llu depth_sum=%llu\n", (unsigned long long)(r.start[k] + 1), (unsigned long long)(r.start[k] + r.len[k]),
+             (unsigned long long)r.depth_sum[k]);
+    out.append(buf, strlen(buf));
+    const uint8_t* b = r.seq.data() + r.seq_off[k];
+    for (uint64_t at = 0; at < r.len[k]; at += 80) {
+      out.append(b + at, (size_t)std::min<uint64_t>(80, r.len[k] - at));
+      out.append("\n", 1);
+    }
+  }
+  return out.close(err);
+}
+
+bool write_gold_regions_tsv(const std::vector<Genome>& genomes, const HostRegions& r, const std::string& output, std::string* err) {
+  if (!region_columns_agree(r, err)) return false;
+  for (size_t k = 0; k < r.genome.size(); k++)
+    if (!region_names(genomes, r, k, false, err)) return false;
+  OutFile out(output, false);
+  out.append("genome_id\tsequence_id\tstart\tlength\tdepth_sum\tseq_off\n");
+  char buf[128];
+  for (size_t k = 0; k < r.genome.size() && out.ok(); k++) {
+    out.append(genomes[r.genome[k]].uuid + "\t" + genomes[r.genome[k]].sequence[r.contig[k]].id);
+    snprintf(buf, sizeof buf, "\t%llu\t%llu\t%llu\t%llu\n", (unsigned long long)r.start[k], (unsigned long long)r.len[k],
+             (unsigned long long)r.depth_sum[k], (unsigned long long)r.seq_off[k]);
+    out.append(buf, strlen(buf));
+  }
+  return out.close(err);
+}
+
 // --------------------------------------------------------------- error profiles
 
 static simmr_error_profile zero_pod() {
@@ -531,6 +588,13 @@ std::string usage() {
          "                             combines with --truth and --stats; not with --devices)\n"
          "            --depth-track <FILE>  the same per window: genome_id sequence_id start end depth_sum covered depth_max\n"
          "            --depth-window <W>    positions per window of --depth-track [default: 1000]\n"
+         "            --gold-assembly <FILE>  the gold-standard assembly as FASTA: every stretch of a sequence the run covered, one record\n"
+         "                            >genome_id|sequence_id:first-last depth_sum=N per stretch (1-based, closed), bases in lines of 80; found and\n"
+         "                            read out on the device from the run's depth (turns the depth pass on); with --with-ani the bases\n"
+         "                            are the strain's; not with --devices\n"
+         "            --gold-regions <FILE>   the same stretches as a TSV: genome_id sequence_id start length depth_sum seq_off (start 0-based)\n"
+         "            --gold-min-depth <D>    a position belongs to a stretch from this read depth on [default: 1]\n"
+         "            --gold-min-length <M>   shorter stretches are left out [default: 1]\n"
          "            --strain-sites <FILE>  the sites --with-ani changed, as a TSV: genome_id sequence_id position ref alt (position 0-based;\n"
          "                            drawn and listed on the device; with --truth, which reports the sequencing errors against the strain,\n"
          "                            the full truth against the original assembly; needs --with-ani; with --devices written from the first)\n";
@@ -614,6 +678,10 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
     else if (arg == "--strain-sites") { if (!file(&a->strain_sites)) return false; }
+    else if (arg == "--gold-assembly") { if (!file(&a->gold_assembly)) return false; }
+    else if (arg == "--gold-regions") { if (!file(&a->gold_regions)) return false; }
+    else if (arg == "--gold-min-depth") { if (!uint(1, UINT32_MAX, " (at least 1)")) return false; a->gold_min_depth = (uint32_t)u; }
+    else if (arg == "--gold-min-length") { if (!uint(1, UINT64_MAX, " (at least 1)")) return false; a->gold_min_length = u; }
     else if (arg == "--depth-window") { if (!uint(1, (1u << 30) - 1, " (1 .. 2^30 - 1)")) return false; a->depth_window = (uint32_t)u; }
     else if (arg == "--device-chunk-reads") { if (!uint(1, UINT64_MAX)) return false; a->device_chunk_reads = u; }
     else if (arg == "--devices") {
@@ -811,6 +879,23 @@ char* simmr_host_depth_tsv(const simmr_depth_contig* rows, uint64_t n_rows, uint
   std::string err;
   if (path && !write_depth_tsv(genomes, rows, n_rows, path, &err)) return dup_str("ERR\t" + err);
   if (track_path && !write_depth_track_tsv(genomes, rows, n_rows, window, win_sum, win_covered, win_max, track_path, &err)) return dup_str("ERR\t" + err);
+  return dup_str("OK");
+}
+// The gold-assembly FASTA and TSV of write_gold_fasta / write_gold_regions_tsv for columns in host memory (seq_off: n_regions + 1
+// entries; seq: seq_off[n_regions] bytes); names in the shape of simmr_host_truth_tsv.  Either path may be NULL.  Returns
+// "OK", or "ERR\t..." .
+char* simmr_host_gold_files(uint64_t n_regions, const uint32_t* genome, const uint32_t* contig, const uint64_t* start, const uint64_t* len,
+                            const uint64_t* depth_sum, const uint64_t* seq_off, const uint8_t* seq, uint32_t n_genomes,
+                            const char* const* genome_id, const uint32_t* n_contigs, const char* const* sequence_id, const char* fasta_path,
+                            const char* tsv_path) {
+  const std::vector<Genome> genomes = genomes_from_names(n_genomes, genome_id, n_contigs, sequence_id);
+  HostRegions r;
+  r.genome.assign(genome, genome + n_regions); r.contig.assign(contig, contig + n_regions); r.start.assign(start, start + n_regions);
+  r.len.assign(len, len + n_regions); r.depth_sum.assign(depth_sum, depth_sum + n_regions); r.seq_off.assign(seq_off, seq_off + n_regions + 1);
+  if (seq) r.seq.assign(seq, seq + seq_off[n_regions]);
+  std::string err;
+  if (fasta_path && !write_gold_fasta(genomes, r, fasta_path, &err)) return dup_str("ERR\t" + err);
+  if (tsv_path && !write_gold_regions_tsv(genomes, r, tsv_path, &err)) return dup_str("ERR\t" + err);
   return dup_str("OK");
 }
 char* simmr_host_parse_genome_file(const char* path) {

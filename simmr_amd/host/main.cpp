@@ -120,6 +120,29 @@ static bool write_depth_files(simmr_engine* eng, const CliArgs& args, const std:
   return write_depth_track_tsv(genomes, rows.data(), n_contigs, args.depth_window, ws.data(), wc.data(), wm.data(), args.depth_track, err);
 }
 
+// `--gold-assembly` / `--gold-regions`: the regions of the run's depth[] (simmr_regions_plan / simmr_regions_emit over what
+// simmr_depth_emit gives of every range added so far), copied to the host and written as FASTA and as a TSV.
+static bool write_gold_files(simmr_engine* eng, const CliArgs& args, const std::vector<Genome>& genomes, uint64_t n_positions, std::string* err) {
+  DeviceMem mem;
+  uint32_t* depth = nullptr;
+  if (!mem.alloc(&depth, n_positions)) { *err = "device allocation failed"; return false; }
+  if (simmr_depth_emit(eng, depth, n_positions) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  uint64_t n = 0, nb = 0;
+  if (simmr_regions_plan(eng, depth, args.gold_min_depth, args.gold_min_length, &n, &nb) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  const bool fasta = !args.gold_assembly.empty();
+  simmr_regions_out o{};
+  o.capacity = n;
+  o.seq_capacity = fasta ? nb + 16 : 0;
+  if (!(mem.alloc(&o.genome, n) && mem.alloc(&o.contig, n) && mem.alloc(&o.start, n) && mem.alloc(&o.len, n) && mem.alloc(&o.depth_sum, n) &&
+        mem.alloc(&o.seq_off, n + 1) && (!fasta || mem.alloc(&o.seq, o.seq_capacity)))) { *err = "device allocation failed"; return false; }
+  if (simmr_regions_emit(eng, depth, &o) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  HostRegions h;
+  if (!(mem.fetch(&h.genome, o.genome, n) && mem.fetch(&h.contig, o.contig, n) && mem.fetch(&h.start, o.start, n) && mem.fetch(&h.len, o.len, n) &&
+        mem.fetch(&h.depth_sum, o.depth_sum, n) && mem.fetch(&h.seq_off, o.seq_off, n + 1) && (!fasta || mem.fetch(&h.seq, o.seq, nb)))) { *err = "copy back failed"; return false; }
+  if (fasta && !write_gold_fasta(genomes, h, args.gold_assembly, err)) return false;
+  return args.gold_regions.empty() || write_gold_regions_tsv(genomes, h, args.gold_regions, err);
+}
+
 // `--with-ani` / `--strain-sites`: genome i of the run becomes a strain on every engine (simmr_strain_plan /
 // simmr_strain_apply with the seed run seed + 0x9E3779B97F4A7C15 (i + 1)); the outcome is a function of the inputs, so the
 // engines' copies agree, and the sites are listed from the first engine.
@@ -149,7 +172,7 @@ static bool diverge_genomes(const std::vector<simmr_engine*>& engs, const CliArg
   return true;
 }
 
-// The side outputs of a run: --truth, --stats, --depth and --depth-track.  They read the columns, so a run that wants one
+// The side outputs of a run: --truth, --stats, --depth, --depth-track, --gold-assembly and --gold-regions.  They read the columns, so a run that wants one
 // takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
 struct SideOutputs {
   explicit SideOutputs(const CliArgs& args) : a(args) {}
@@ -158,19 +181,21 @@ struct SideOutputs {
   HostTruth truth;           // of the range last added, until write_range has written it
   uint32_t qual_offset = 33;
   uint64_t depth_positions = 0, depth_contigs = 0;
-  bool depth() const { return !a.depth.empty() || !a.depth_track.empty(); }
+  bool depth_files() const { return !a.depth.empty() || !a.depth_track.empty(); }
+  bool gold() const { return !a.gold_assembly.empty() || !a.gold_regions.empty(); }
+  bool depth() const { return depth_files() || gold(); }  // (the gold-standard assembly is read off the run's depth[])
   bool wanted() const { return !a.truth.empty() || !a.stats.empty() || depth(); }
   bool fail(const char* flag, const std::string& what) { err = std::string(flag) + ": " + what; return false; }
   // true, with the message, if one of them is asked for together with --devices
   bool refuse_devices() {
-    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth() ? "--depth" : nullptr;
+    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : nullptr;
     if (flag && !a.devices.empty()) err = std::string(flag) + " does not combine with --devices: use --device";
     return flag && !a.devices.empty();
   }
   // the old files go, the truth file gets its header line (every range appends its reads), the tables start at zero
   // (the genomes are staged: depth[] covers all of them)
   bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
-    for (const std::string* f : {&a.truth, &a.stats, &a.depth, &a.depth_track})
+    for (const std::string* f : {&a.truth, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions})
       if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
     std::string e;
     if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
@@ -198,7 +223,8 @@ struct SideOutputs {
       if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
       if (!write_stats_tsv(*st, a.stats, &e)) return fail("--stats", e);
     }
-    return !depth() || write_depth_files(eng, a, genomes, depth_positions, depth_contigs, &e) || fail("--depth", e);
+    if (depth_files() && !write_depth_files(eng, a, genomes, depth_positions, depth_contigs, &e)) return fail("--depth", e);
+    return !gold() || write_gold_files(eng, a, genomes, depth_positions, &e) || fail("--gold-assembly", e);
   }
 };
 

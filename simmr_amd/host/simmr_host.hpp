@@ -177,6 +177,23 @@ bool write_depth_track_tsv(const std::vector<Genome>& genomes, const simmr_depth
                            const uint64_t* win_sum, const uint32_t* win_covered, const uint32_t* win_max, const std::string& output,
                            std::string* err);
 
+// ---------------------------------------------------------------- gold-standard assembly (no reference counterpart)
+// Host copy of simmr_regions_out: one entry per region (seq_off one more), seq the regions' bases back to back.
+struct HostRegions {
+  std::vector<uint32_t> genome, contig;
+  std::vector<uint64_t> start, len, depth_sum, seq_off;
+  std::vector<uint8_t> seq;
+};
+// `simmr-hip --gold-assembly FILE`: one FASTA record per region, in the order of the columns:
+//   >{genome_id}|{sequence_id}:{start+1}-{start+len} depth_sum={depth_sum}
+// (1-based, closed coordinates inside the sequence) and the region's bases in lines of 80.  regions.genome[k] indexes
+// `genomes`.  Replaces `output`.
+bool write_gold_fasta(const std::vector<Genome>& genomes, const HostRegions& regions, const std::string& output, std::string* err);
+// `simmr-hip --gold-regions FILE`: a line of column names, then one tab-separated line per region:
+//   genome_id  sequence_id  start  length  depth_sum  seq_off
+// start 0-based inside the sequence, seq_off the region's first base in the base stream.  regions.seq is not read.  Replaces `output`.
+bool write_gold_regions_tsv(const std::vector<Genome>& genomes, const HostRegions& regions, const std::string& output, std::string* err);
+
 // ------------------------------------------------------- error_profiles/*.rs
 class ErrorProfile {  // error_profiles/base.rs:6-32 (the per-read methods run on the device)
  public:
@@ -284,6 +301,10 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions
   uint32_t depth_window = 1000;  // --depth-window W
+  std::string gold_assembly;     // --gold-assembly FILE: the regions the run covered (simmr_regions_plan / simmr_regions_emit over the run's depth[]) as FASTA
+  std::string gold_regions;      // --gold-regions FILE: the same regions' columns as a TSV
+  uint32_t gold_min_depth = 1;   // --gold-min-depth D: a position belongs to a region from this depth on
+  uint64_t gold_min_length = 1;  // --gold-min-length M: shorter runs are no regions
   std::string strain_sites;      // --strain-sites FILE: the sites --with-ani changed (simmr_strain_apply's columns) as a TSV
   uint64_t device_chunk_reads = 0;  // --device-chunk-reads: reads generated per device pass (0: what fits the free device memory)
   std::optional<std::pair<float, float>> gamma;  // --gamma mean,std
