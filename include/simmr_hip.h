@@ -729,6 +729,55 @@ int simmr_regions_emit(simmr_engine* e, const uint32_t* depth_device, const simm
  * included) plus that of the simmr_regions_emit after it, if any.  Synchronises the stream. */
 int simmr_last_regions_ms(simmr_engine* e, float* ms);
 
+/* ---- allele counts at listed sites: what the reads of a run show at every site of a list ---------------------------------
+ * Replaces nothing in the reference.  What a variant truth set carries per site next to REF and ALT — depth and allele
+ * depth, per strand (DP, AD, ADF, ADR) — counted on the device from the columns in HBM, without draining the reads: a site
+ * nobody covered cannot be called, and a site covered three times is not the truth a site covered sixty times is.
+ *
+ * Site list.  n triples (genome slot, contig, pos) in device memory, strictly ascending by (slot, contig, pos): the order of
+ * depth[], and the order in which simmr_strain_apply writes one genome's sites, so the lists of several genomes concatenate
+ * in slot order.  pos is 0-based in Seq.seq coordinates as simmr_unstage_contig sees them.
+ * Covering.  For read r, L = |end[r] - start[r]| and lo = min(start[r], end[r]), exactly simmr_truth_out's.  The read
+ * COVERS a site iff genome[r] and contig[r] are the site's and lo <= pos < lo + L (a read with L = 0 covers nothing).
+ * Written byte.  j = pos - lo for a forward read, j = L - 1 - (pos - lo) for a read with SIMMR_FLAG_REVCOMP; the byte is
+ * seq[seq_off[r] + j] in both layouts (seq_off[r] is the read's first base in SIMMR_SLOT16 too).  Its CLASS is the
+ * statistics pass's: 0 1 2 3 for 'A' 'C' 'G' 'T' and 4 for every other byte.
+ * Observed class, in genome orientation: the class itself for a forward read; for a reverse read its complement, 0 <-> 3
+ * and 1 <-> 2, while 4 stays 4.
+ * counts[s][strand][class] += 1 for every read that covers site s, strand = 1 for a reverse read: the table is
+ * uint32_t counts[n][2][5].  Mates count separately, as in read depth — INVARIANT: the ten counts of site s sum to
+ * depth[x] of its position for the same reads.
+ *
+ * Every entry is an integer sum over reads, so the result is a function of the inputs alone — launch geometry and the order
+ * of the adds never change a number — and the tables of several adds, ranges or engines add up entry by entry. */
+typedef struct simmr_pileup_sites {     /* DEVICE pointers, caller-owned */
+  const uint32_t* genome; const uint32_t* contig; const uint64_t* pos; uint64_t n;
+} simmr_pileup_sites;
+/* Records the dense layout of the genomes staged now (depth[]'s: genomes in ascending slot order, contigs in order, no
+ * padding; no simmr_depth_reset is needed), turns every site into a 64-bit key first(slot, contig) + pos in a buffer the
+ * engine holds, allocates and zeroes counts and the sticky error word, and synchronises: the caller's columns are not needed
+ * after the call.  n == 0 is valid (adds then do nothing).
+ * SIMMR_EINVAL, found on the device before a key is used as an address anywhere: a site whose slot is not staged, whose
+ * contig does not exist, whose pos is not below the contig's length, or that does not come after the site before it (out of
+ * order, or repeated); simmr_last_error names the index of the first such site.  No table is then in force.
+ * SIMMR_ENOMEM if the buffers cannot be had. */
+int simmr_pileup_reset(simmr_engine* e, const simmr_pileup_sites* sites);
+/* Adds the reads of `reads`.  Only enqueues on the engine's stream — no synchronisation.  Needs seq, seq_off, start, end,
+ * contig, genome and flags; qual is not read.
+ * SIMMR_ESTATE: no simmr_pileup_reset yet, or a genome was staged since (simmr_strain_apply counts as staging: reset after
+ * it).  SIMMR_ERANGE: the reads added since the reset would reach 2^31 (the bound keeps a uint32_t count from wrapping).
+ * A read whose genome slot is not tracked, whose contig does not exist, whose window leaves its contig or whose bytes would
+ * leave seq[0 .. seq_capacity) is never loaded from: it adds nothing and sets the sticky error word (simmr_truth_plan's
+ * bounds check, made before any address is formed from the read). */
+int simmr_pileup_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads);
+/* Synchronises, then copies the table — n * 10 uint32_t — to counts_device (DEVICE memory holding capacity_sites * 10
+ * entries).  The engine's table is left as it is: adds may go on and a later read sees all of them.
+ * SIMMR_ESTATE: no simmr_pileup_reset yet.  SIMMR_ERANGE, nothing written: capacity_sites < n.  SIMMR_EINVAL, nothing
+ * written: the sticky error word is set (it stays so until the next simmr_pileup_reset). */
+int simmr_pileup_read(simmr_engine* e, uint32_t* counts_device, uint64_t capacity_sites);
+/* HIP-event time (ms) of the last simmr_pileup_add's device work.  Synchronises the stream. */
+int simmr_last_pileup_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,16 @@ class RegionsOut(C.Structure):
     ]
 
 
+class PileupSites(C.Structure):
+    """struct simmr_pileup_sites (device pointers as raw addresses)"""
+    _fields_ = [
+        ("genome", C.c_void_p),
+        ("contig", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("n", C.c_uint64),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -263,6 +273,10 @@ SYMBOLS = {
     "simmr_regions_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64)]),
     "simmr_regions_emit": (C.c_int, [C.c_void_p, C.c_void_p, _P(RegionsOut)]),
     "simmr_last_regions_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_pileup_reset": (C.c_int, [C.c_void_p, _P(PileupSites)]),
+    "simmr_pileup_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64]),
+    "simmr_pileup_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_last_pileup_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

@@ -547,6 +547,46 @@ class Engine:
         self._check(self.lib.simmr_last_regions_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- allele counts at listed sites ----------------------------------------------------
+    def pileup_reset(self, genome, contig, pos) -> int:
+        """Takes the site list (genome slot, contig, pos), strictly ascending in that order — torch tensors on this device or
+        numpy arrays — and zeroes the engine's counts[n][2][5] (simmr_pileup_reset); returns n.  The columns are not kept."""
+        torch = _torch()
+
+        def col(a, unsigned, signed, dt):  # (torch holds the unsigned columns in the signed type of their width)
+            if isinstance(a, torch.Tensor):
+                return a.to(device=self.device, dtype=dt).contiguous()
+            return torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(unsigned)).view(signed)).to(self.device)
+        g, c, p = (col(genome, np.uint32, np.int32, torch.int32), col(contig, np.uint32, np.int32, torch.int32),
+                   col(pos, np.uint64, np.int64, torch.int64))
+        n = int(p.numel())
+        if g.numel() != n or c.numel() != n:
+            raise ValueError("pileup_reset: genome, contig and pos differ in length")
+        sites = _abi.PileupSites(g.data_ptr() if n else None, c.data_ptr() if n else None, p.data_ptr() if n else None, n)
+        self._pileup_sites = None
+        self._check(self.lib.simmr_pileup_reset(self._h, C.byref(sites)))
+        self._pileup_sites = n
+        return n
+
+    def pileup_add(self, reads: Reads):
+        """Adds what `reads` show at the sites (simmr_pileup_add): enqueues only; reads every column but qual and read_id."""
+        pod = reads.pod()
+        self._check(self.lib.simmr_pileup_add(self._h, C.byref(pod), reads.n_reads))
+
+    def pileup(self) -> np.ndarray:
+        """counts[site][strand][class] of the reads added since the reset as a numpy uint32[n, 2, 5] (simmr_pileup_read):
+        strand 1 = reverse reads; classes A C G T other, observed in genome orientation."""
+        torch = _torch()
+        n = getattr(self, "_pileup_sites", None) or 0
+        out = torch.empty(max(n, 1) * 10, dtype=torch.int32, device=self.device)
+        self._check(self.lib.simmr_pileup_read(self._h, C.c_void_p(out.data_ptr()), n))
+        return out[: n * 10].cpu().numpy().view(np.uint32).reshape(n, 2, 5)
+
+    def last_pileup_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_pileup_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- counters / timing --------------------------------------------------------
     def counters(self) -> np.ndarray:
         host = (C.c_uint64 * _abi.N_COUNTERS)()

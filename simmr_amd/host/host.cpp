@@ -327,6 +327,47 @@ bool write_strain_sites_tsv(const Genome& genome, const HostStrainSites& s, cons
   return out.close(err);
 }
 
+// the class of the statistics and pileup passes: A C G T are 0 1 2 3, every other byte 4
+static int base_class(uint8_t b) { return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : 4; }
+
+bool write_strain_vcf(const std::vector<Genome>& genomes, const std::vector<std::vector<uint64_t>>& contig_len, const HostStrainSites& s,
+                      const std::vector<uint32_t>& site_genome, const std::vector<uint32_t>& counts, const std::string& output,
+                      std::string* err) {
+  const size_t n = s.pos.size();
+  if (site_genome.size() != n || s.contig.size() != n || s.ref.size() != n || s.alt.size() != n || counts.size() != n * 10) { *err = "the site columns and the count table differ in length"; return false; }
+  OutFile out(output, false);
+  out.append("##fileformat=VCFv4.2\n##source=simmr-hip\n");
+  for (size_t g = 0; g < genomes.size(); g++)
+    for (size_t c = 0; c < genomes[g].sequence.size(); c++) {
+      if (g >= contig_len.size() || c >= contig_len[g].size()) { *err = "no length for sequence " + std::to_string(c) + " of genome " + std::to_string(g); return false; }
+      out.append("##contig=<ID=" + genomes[g].uuid + "|" + genomes[g].sequence[c].id + ",length=" + std::to_string(contig_len[g][c]) + ">\n");
+    }
+  out.append("##INFO=<ID=DP,Number=1,Type=Integer,Description=\"Reads of the run that cover the site (mates count separately)\">\n"
+             "##INFO=<ID=AD,Number=R,Type=Integer,Description=\"Reads that show the reference and the alternate base\">\n"
+             "##INFO=<ID=ADF,Number=R,Type=Integer,Description=\"The same among forward reads\">\n"
+             "##INFO=<ID=ADR,Number=R,Type=Integer,Description=\"The same among reverse reads\">\n"
+             "##INFO=<ID=OTH,Number=1,Type=Integer,Description=\"Reads that show neither: a third base or N\">\n"
+             "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n");
+  char buf[256];
+  std::string line;
+  for (size_t i = 0; i < n && out.ok(); i++) {
+    if (site_genome[i] >= genomes.size() || s.contig[i] >= genomes[site_genome[i]].sequence.size()) { *err = "site " + std::to_string(i) + " names a sequence the run does not have"; return false; }
+    const Genome& g = genomes[site_genome[i]];
+    const uint32_t* k = counts.data() + i * 10;  // [strand][class]
+    const int r = base_class(s.ref[i]), a = base_class(s.alt[i]);
+    uint64_t dp = 0;
+    for (int j = 0; j < 10; j++) dp += k[j];
+    const uint64_t ad_r = (uint64_t)k[r] + k[5 + r], ad_a = (uint64_t)k[a] + k[5 + a];
+    line = g.uuid; line += '|'; line += g.sequence[s.contig[i]].id;
+    snprintf(buf, sizeof buf, "\t%llu\t.\t%c\t%c\t.\t.\tDP=%llu;AD=%llu,%llu;ADF=%u,%u;ADR=%u,%u;OTH=%llu\n", (unsigned long long)s.pos[i] + 1,
+             (char)s.ref[i], (char)s.alt[i], (unsigned long long)dp, (unsigned long long)ad_r, (unsigned long long)ad_a, k[r], k[a], k[5 + r], k[5 + a],
+             (unsigned long long)(dp - ad_r - ad_a));
+    line += buf;
+    out.append(line);
+  }
+  return out.close(err);
+}
+
 // --------------------------------------------------------------- run statistics
 bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::string* err) {
   std::string text = "table\tset\ti\tj\tcount\n";
@@ -597,7 +638,11 @@ std::string usage() {
          "            --gold-min-length <M>   shorter stretches are left out [default: 1]\n"
          "            --strain-sites <FILE>  the sites --with-ani changed, as a TSV: genome_id sequence_id position ref alt (position 0-based;\n"
          "                            drawn and listed on the device; with --truth, which reports the sequencing errors against the strain,\n"
-         "                            the full truth against the original assembly; needs --with-ani; with --devices written from the first)\n";
+         "                            the full truth against the original assembly; needs --with-ani; with --devices written from the first)\n"
+         "            --strain-vcf <FILE>  the same sites as VCF 4.2 with what the reads of this run show at each: DP, AD, ADF, ADR (reference and\n"
+         "                            alternate base, all / forward / reverse reads) and OTH (a third base or N), mates counted separately;\n"
+         "                            counted on the device from every range of the run; CHROM is genome_id|sequence_id, POS 1-based;\n"
+         "                            needs --with-ani; combines with --strain-sites; not with --devices\n";
 }
 
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
@@ -678,6 +723,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
     else if (arg == "--strain-sites") { if (!file(&a->strain_sites)) return false; }
+    else if (arg == "--strain-vcf") { if (!file(&a->strain_vcf)) return false; }
     else if (arg == "--gold-assembly") { if (!file(&a->gold_assembly)) return false; }
     else if (arg == "--gold-regions") { if (!file(&a->gold_regions)) return false; }
     else if (arg == "--gold-min-depth") { if (!uint(1, UINT32_MAX, " (at least 1)")) return false; a->gold_min_depth = (uint32_t)u; }
@@ -715,6 +761,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else { *err = "Found argument '" + arg + "' which wasn't expected"; return false; }
   }
   if (!a->strain_sites.empty() && !a->with_ani) { *err = "--strain-sites needs --with-ani"; return false; }
+  if (!a->strain_vcf.empty() && !a->with_ani) { *err = "--strain-vcf needs --with-ani"; return false; }
   // cli.rs:88-92: ArgGroup "genomes" is required, and --output has no default
   if (a->genome.empty() && !a->genome_file) { *err = "one of --genome / --genome-file is required"; return false; }
   if (!a->genome.empty() && a->genome_file) { *err = "--genome and --genome-file cannot be used together"; return false; }
@@ -861,6 +908,22 @@ char* simmr_host_strain_tsv(uint64_t n_sites, const uint32_t* contig, const uint
   s.ref.assign(ref, ref + n_sites); s.alt.assign(alt, alt + n_sites);
   std::string err;
   if (!write_strain_sites_tsv(genomes[0], s, path, with_header != 0, &err)) return dup_str("ERR\t" + err);
+  return dup_str("OK");
+}
+// The VCF of write_strain_vcf for site columns and a count table given as plain arrays (counts: n_sites * 10 entries); names in
+// the shape of simmr_host_truth_tsv, contig_len flattened like sequence_id.  Returns "OK", or "ERR\t..." .
+char* simmr_host_strain_vcf(uint64_t n_sites, const uint32_t* genome, const uint32_t* contig, const uint64_t* pos, const uint8_t* ref,
+                            const uint8_t* alt, const uint32_t* counts, uint32_t n_genomes, const char* const* genome_id,
+                            const uint32_t* n_contigs, const char* const* sequence_id, const uint64_t* contig_len, const char* path) {
+  const std::vector<Genome> genomes = genomes_from_names(n_genomes, genome_id, n_contigs, sequence_id);
+  std::vector<std::vector<uint64_t>> lens(n_genomes);
+  for (uint32_t g = 0, at = 0; g < n_genomes; at += n_contigs[g], g++) lens[g].assign(contig_len + at, contig_len + at + n_contigs[g]);
+  HostStrainSites s;
+  s.contig.assign(contig, contig + n_sites); s.pos.assign(pos, pos + n_sites);
+  s.ref.assign(ref, ref + n_sites); s.alt.assign(alt, alt + n_sites);
+  std::string err;
+  if (!write_strain_vcf(genomes, lens, s, std::vector<uint32_t>(genome, genome + n_sites), std::vector<uint32_t>(counts, counts + n_sites * 10), path, &err))
+    return dup_str("ERR\t" + err);
   return dup_str("OK");
 }
 // The statistics TSV of write_stats_tsv for a simmr_run_stats in host memory.  Returns "OK", or "ERR\t..." .

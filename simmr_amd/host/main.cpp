@@ -145,17 +145,18 @@ static bool write_gold_files(simmr_engine* eng, const CliArgs& args, const std::
 
 // `--with-ani` / `--strain-sites`: genome i of the run becomes a strain on every engine (simmr_strain_plan /
 // simmr_strain_apply with the seed run seed + 0x9E3779B97F4A7C15 (i + 1)); the outcome is a function of the inputs, so the
-// engines' copies agree, and the sites are listed from the first engine.
+// engines' copies agree, and the sites are listed from the first engine.  `--strain-vcf`: the sites of every genome are kept
+// in `keep`, back to back in genome order, with the genome's index in `keep_genome`.
 static bool diverge_genomes(const std::vector<simmr_engine*>& engs, const CliArgs& args, const std::vector<Genome>& genomes,
-                            uint64_t run_seed, std::string* err) {
-  const bool list = !args.strain_sites.empty();
+                            uint64_t run_seed, HostStrainSites* keep, std::vector<uint32_t>* keep_genome, std::string* err) {
+  const bool list = !args.strain_sites.empty(), kept = !args.strain_vcf.empty();
   if (list && is_regular_file(args.strain_sites)) remove(args.strain_sites.c_str());
   for (size_t gi = 0; gi < genomes.size(); gi++) {
     const uint64_t seed = run_seed + 0x9E3779B97F4A7C15ull * (uint64_t)(gi + 1);
     for (size_t k = 0; k < engs.size(); k++) {
       uint64_t n = 0;
       if (simmr_strain_plan(engs[k], (uint32_t)gi, *args.with_ani / 100.0, seed, &n) != SIMMR_OK) { *err = simmr_last_error(engs[k]); return false; }
-      if (k > 0 || !list) {
+      if (k > 0 || !(list || kept)) {
         if (simmr_strain_apply(engs[k], (uint32_t)gi, nullptr) != SIMMR_OK) { *err = simmr_last_error(engs[k]); return false; }
         continue;
       }
@@ -166,13 +167,45 @@ static bool diverge_genomes(const std::vector<simmr_engine*>& engs, const CliArg
       if (simmr_strain_apply(engs[k], (uint32_t)gi, &o) != SIMMR_OK) { *err = simmr_last_error(engs[k]); return false; }
       HostStrainSites h;
       if (!(mem.fetch(&h.contig, o.contig, n) && mem.fetch(&h.pos, o.pos, n) && mem.fetch(&h.ref, o.ref, n) && mem.fetch(&h.alt, o.alt, n))) { *err = "copy back failed"; return false; }
-      if (!write_strain_sites_tsv(genomes[gi], h, args.strain_sites, gi == 0, err)) return false;
+      if (list && !write_strain_sites_tsv(genomes[gi], h, args.strain_sites, gi == 0, err)) return false;
+      if (kept) {
+        keep->contig.insert(keep->contig.end(), h.contig.begin(), h.contig.end());
+        keep->pos.insert(keep->pos.end(), h.pos.begin(), h.pos.end());
+        keep->ref.insert(keep->ref.end(), h.ref.begin(), h.ref.end());
+        keep->alt.insert(keep->alt.end(), h.alt.begin(), h.alt.end());
+        keep_genome->insert(keep_genome->end(), h.pos.size(), (uint32_t)gi);
+      }
     }
   }
   return true;
 }
 
-// The side outputs of a run: --truth, --stats, --depth, --depth-track, --gold-assembly and --gold-regions.  They read the columns, so a run that wants one
+// `--strain-vcf`: the table of every range added so far (simmr_pileup_read), the sequences' lengths from the layout of depth[]
+// (the engine's own contig table: exact under --contiguous too), and the file.
+static bool write_vcf_file(simmr_engine* eng, const CliArgs& args, const std::vector<Genome>& genomes, const HostStrainSites& sites,
+                           const std::vector<uint32_t>& site_genome, uint64_t n_positions, std::string* err) {
+  std::vector<std::vector<uint64_t>> lens(genomes.size());
+  std::vector<uint64_t> firsts;
+  for (size_t g = 0; g < genomes.size(); g++)
+    for (size_t c = 0; c < genomes[g].sequence.size(); c++) {
+      uint64_t first = 0;
+      if (simmr_depth_contig_first(eng, (uint32_t)g, (uint32_t)c, &first) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+      firsts.push_back(first);
+    }
+  firsts.push_back(n_positions);
+  for (size_t g = 0, k = 0; g < genomes.size(); g++)
+    for (size_t c = 0; c < genomes[g].sequence.size(); c++, k++) lens[g].push_back(firsts[k + 1] - firsts[k]);
+  const uint64_t n = sites.pos.size();
+  DeviceMem mem;
+  uint32_t* table = nullptr;
+  std::vector<uint32_t> counts;
+  if (!mem.alloc(&table, n * 10)) { *err = "device allocation failed"; return false; }
+  if (simmr_pileup_read(eng, table, n) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  if (!mem.fetch(&counts, table, n * 10)) { *err = "copy back failed"; return false; }
+  return write_strain_vcf(genomes, lens, sites, site_genome, counts, args.strain_vcf, err);
+}
+
+// The side outputs of a run: --truth, --stats, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
 // takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
 struct SideOutputs {
   explicit SideOutputs(const CliArgs& args) : a(args) {}
@@ -181,32 +214,50 @@ struct SideOutputs {
   HostTruth truth;           // of the range last added, until write_range has written it
   uint32_t qual_offset = 33;
   uint64_t depth_positions = 0, depth_contigs = 0;
+  HostStrainSites sites;             // --strain-vcf: what diverge_genomes kept, and each site's genome
+  std::vector<uint32_t> site_genome;
+  bool vcf() const { return !a.strain_vcf.empty(); }
   bool depth_files() const { return !a.depth.empty() || !a.depth_track.empty(); }
   bool gold() const { return !a.gold_assembly.empty() || !a.gold_regions.empty(); }
   bool depth() const { return depth_files() || gold(); }  // (the gold-standard assembly is read off the run's depth[])
-  bool wanted() const { return !a.truth.empty() || !a.stats.empty() || depth(); }
+  bool wanted() const { return !a.truth.empty() || !a.stats.empty() || depth() || vcf(); }
   bool fail(const char* flag, const std::string& what) { err = std::string(flag) + ": " + what; return false; }
   // true, with the message, if one of them is asked for together with --devices
   bool refuse_devices() {
-    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : nullptr;
+    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : nullptr;
     if (flag && !a.devices.empty()) err = std::string(flag) + " does not combine with --devices: use --device";
     return flag && !a.devices.empty();
   }
   // the old files go, the truth file gets its header line (every range appends its reads), the tables start at zero
   // (the genomes are staged: depth[] covers all of them)
   bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
-    for (const std::string* f : {&a.truth, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions})
+    for (const std::string* f : {&a.truth, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
       if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
     std::string e;
     if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
     if (!a.stats.empty() && simmr_stats_reset(eng) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
-    if (depth() && simmr_depth_reset(eng, &depth_positions, &depth_contigs) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
-    return true;
+    // (--strain-vcf takes the sequences' lengths from the layout the depth reset records)
+    if ((depth() || vcf()) && simmr_depth_reset(eng, &depth_positions, &depth_contigs) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
+    return !vcf() || begin_pileup(eng);
+  }
+  // the kept sites go up as one list — genome index, contig, pos: ascending, genome by genome — and the table starts at zero
+  bool begin_pileup(simmr_engine* eng) {
+    DeviceMem mem;
+    simmr_pileup_sites s{};
+    s.n = sites.pos.size();
+    uint32_t *g = nullptr, *c = nullptr;
+    uint64_t* p = nullptr;
+    if (!(mem.alloc(&g, s.n) && mem.alloc(&c, s.n) && mem.alloc(&p, s.n))) return fail("--strain-vcf", "device allocation failed");
+    if (s.n > 0 && (hipMemcpy(g, site_genome.data(), s.n * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(c, sites.contig.data(), s.n * 4, hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(p, sites.pos.data(), s.n * 8, hipMemcpyHostToDevice) != hipSuccess)) return fail("--strain-vcf", "copy to the device failed");
+    s.genome = g; s.contig = c; s.pos = p;
+    return simmr_pileup_reset(eng, &s) == SIMMR_OK || fail("--strain-vcf", simmr_last_error(eng));
   }
   // every range adds to the run's tables (enqueued behind the emit; the copies that follow wait for the device)
   bool add_range(simmr_engine* eng, const simmr_reads_out& reads, uint64_t n_reads, bool paired) {
     if (!a.stats.empty() && simmr_stats_add(eng, &reads, n_reads, paired ? 2u : 1u) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
     if (depth() && simmr_depth_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
+    if (vcf() && simmr_pileup_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--strain-vcf", simmr_last_error(eng));
     std::string e;
     qual_offset = reads.qual_offset;
     if (!a.truth.empty() && !device_truth(eng, &reads, n_reads, &truth, &e)) return fail("--truth", e);
@@ -224,7 +275,8 @@ struct SideOutputs {
       if (!write_stats_tsv(*st, a.stats, &e)) return fail("--stats", e);
     }
     if (depth_files() && !write_depth_files(eng, a, genomes, depth_positions, depth_contigs, &e)) return fail("--depth", e);
-    return !gold() || write_gold_files(eng, a, genomes, depth_positions, &e) || fail("--gold-assembly", e);
+    if (gold() && !write_gold_files(eng, a, genomes, depth_positions, &e)) return fail("--gold-assembly", e);
+    return !vcf() || write_vcf_file(eng, a, genomes, sites, site_genome, depth_positions, &e) || fail("--strain-vcf", e);
   }
 };
 
@@ -717,7 +769,7 @@ static int run_main(int argc, char** argv) {
   auto begin_run = [&](const Scope& sc) {
     if (begun) return 0;
     begun = true;
-    if (args.with_ani && !diverge_genomes(engs, args, genomes, sc.seed, &err)) return die("--with-ani: " + err);
+    if (args.with_ani && !diverge_genomes(engs, args, genomes, sc.seed, &side.sites, &side.site_genome, &err)) return die("--with-ani: " + err);
     return side.begin(eng, genomes) ? 0 : die(side.err);
   };
 

@@ -155,6 +155,17 @@ struct HostStrainSites {
 bool write_strain_sites_tsv(const Genome& genome, const HostStrainSites& sites, const std::string& output, bool with_header,
                             std::string* err);
 
+// `simmr-hip --strain-vcf FILE`: VCF 4.2 — ##fileformat, ##source=simmr-hip, one ##contig=<ID={genome_id}|{sequence_id},length=N>
+// per sequence of the run (the naming of --gold-assembly; contig_len[g][c] its length in Seq.seq coordinates), the ##INFO lines
+// of DP, AD, ADF, ADR (Number=R) and OTH, the eight-column #CHROM line, then one record per site in list order:
+//   CHROM  pos+1  .  REF  ALT  .  .  DP=..;AD=r,a;ADF=r,a;ADR=r,a;OTH=..
+// `sites` holds the sites of every genome back to back, site_genome[i] indexing `genomes`; counts is simmr_pileup_read's table,
+// ten entries per site ([strand][class]).  r and a are the counts of REF's and ALT's classes, DP all ten, OTH = DP - AD's two
+// numbers.  No sample columns.  Replaces `output`.
+bool write_strain_vcf(const std::vector<Genome>& genomes, const std::vector<std::vector<uint64_t>>& contig_len, const HostStrainSites& sites,
+                      const std::vector<uint32_t>& site_genome, const std::vector<uint32_t>& counts, const std::string& output,
+                      std::string* err);
+
 // ---------------------------------------------------------------- run statistics (no reference counterpart)
 // `simmr-hip --stats FILE`: the tables of a simmr_run_stats (include/simmr_hip.h) in long form, tab-separated:
 //   table  set  i  j  count
@@ -306,6 +317,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   uint32_t gold_min_depth = 1;   // --gold-min-depth D: a position belongs to a region from this depth on
   uint64_t gold_min_length = 1;  // --gold-min-length M: shorter runs are no regions
   std::string strain_sites;      // --strain-sites FILE: the sites --with-ani changed (simmr_strain_apply's columns) as a TSV
+  std::string strain_vcf;        // --strain-vcf FILE: the same sites with the allele counts of the run's reads (simmr_pileup_add over every range) as VCF 4.2
   uint64_t device_chunk_reads = 0;  // --device-chunk-reads: reads generated per device pass (0: what fits the free device memory)
   std::optional<std::pair<float, float>> gamma;  // --gamma mean,std
   bool uniform_start = false;                    // --uniform-start (SIMMR_START_UNIFORM)
