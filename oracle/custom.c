@@ -407,6 +407,20 @@ orc_custom* orc_custom_new(const uint8_t* bytes, uint64_t n) {
   return c;
 }
 const orc_model* orc_custom_model(const orc_custom* c) { return &c->model; }
+static void bins_free(orc_bins* b) { free(b->density); free(b->range_lo); free(b->range_hi); }
+static void pdf_free(orc_pdf* p) { orc_alias_free(&p->alias); free(p->bins); }
+/* everything orc_custom_new and orc_model_parse allocated */
+void orc_custom_free(orc_custom* c) {
+  if (!c) return;
+  orc_model* m = &c->model;
+  for (uint64_t i = 0; i < m->n_quality; i++) { pdf_free(&c->quality[i]); bins_free(&m->quality[i]); }
+  pdf_free(&c->read_length); pdf_free(&c->insert_size);
+  bins_free(&m->read_length_bins); bins_free(&m->insert_bins);
+  for (uint64_t i = 0; i < m->n_prob; i++) { free(m->prob_alt[i]); free(m->prob_w[i]); }
+  free(m->prob_kmer); free(m->prob_n); free(m->prob_alt); free(m->prob_w);
+  free(c->quality); free(m->quality);
+  free(c);
+}
 /* get_read_length (custom_short.rs:237-244): PDF sample `as u16` */
 int orc_custom_get_read_length(const orc_custom* c, uint64_t seed, uint16_t* out) {
   uint32_t v;

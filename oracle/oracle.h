@@ -201,6 +201,7 @@ int orc_pdf_new(const orc_bins* b, orc_pdf* p);
 int orc_pdf_sample(const orc_pdf* p, uint64_t seed, uint32_t* out);
 typedef struct orc_custom orc_custom;
 orc_custom* orc_custom_new(const uint8_t* bytes, uint64_t n);
+void orc_custom_free(orc_custom* c);
 const orc_model* orc_custom_model(const orc_custom* c);
 int orc_custom_get_read_length(const orc_custom* c, uint64_t seed, uint16_t* out);
 int orc_custom_get_insert_size(const orc_custom* c, uint64_t seed, uint16_t* out);

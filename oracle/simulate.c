@@ -109,20 +109,35 @@ uint64_t orc_per_read_seed(uint64_t seed, uint64_t read_index) {
 
 /* CustomShortErrorProfile objects are built once per model buffer (cli.rs:255-272) */
 static orc_custom* custom_of(const simmr_error_profile* p) {
-  /* keyed by the model CONTENT (FNV-1a), not by the caller's buffer address */
+  /* keyed by the model CONTENT, not by the caller's buffer address: FNV-1a steps over 8-byte words with the high half folded
+   * down after every step (every profile method of every pair comes through here, and a model of some hundred wide
+   * positions is megabytes: byte by byte this hash was most of the oracle's time on such models), bytes at the tail */
   static uint64_t key_hash[8], key_n[8];
   static orc_custom* val[8];
   static int used = 0;
   orc_custom* r = NULL;
-  uint64_t h = 1469598103934665603ULL;
   const uint8_t* b = (const uint8_t*)p->custom_model;
-  for (uint64_t i = 0; i < p->custom_model_bytes; i++) { h ^= b[i]; h *= 1099511628211ULL; }
+  const uint64_t n = p->custom_model_bytes, prime = 1099511628211ULL;
+  uint64_t lane[4] = {1469598103934665603ULL, 1469598103934665604ULL, 1469598103934665605ULL, 1469598103934665606ULL};
+  uint64_t at = 0;
+  for (; at + 32 <= n; at += 32)  /* four independent chains over 32-byte rows */
+    for (int l = 0; l < 4; l++) { uint64_t w; memcpy(&w, b + at + 8 * l, 8); lane[l] = (lane[l] ^ w) * prime; lane[l] ^= lane[l] >> 32; }
+  uint64_t h = lane[0];
+  for (int l = 1; l < 4; l++) { h = (h ^ lane[l]) * prime; h ^= h >> 32; }
+  for (; at + 8 <= n; at += 8) { uint64_t w; memcpy(&w, b + at, 8); h = (h ^ w) * prime; h ^= h >> 32; }
+  for (; at < n; at++) h = (h ^ b[at]) * prime;
 #pragma omp critical(orc_custom_cache)
   {
     for (int i = 0; i < used; i++) if (key_hash[i] == h && key_n[i] == p->custom_model_bytes) r = val[i];
     if (!r) {
       r = orc_custom_new(b, p->custom_model_bytes);
-      if (r) { int slot = used < 8 ? used++ : 7; key_hash[slot] = h; key_n[slot] = p->custom_model_bytes; val[slot] = r; }
+      if (r) {
+        int slot = used < 8 ? used++ : 7;
+        /* the ninth model and every later one take the last slot: its tenant is freed (a sweep of some hundred models would
+         * otherwise keep them all).  A model is in use only inside a simulate call, and one call uses one model. */
+        if (val[slot]) orc_custom_free(val[slot]);
+        key_hash[slot] = h; key_n[slot] = p->custom_model_bytes; val[slot] = r;
+      }
     }
   }
   return r;
