@@ -778,6 +778,65 @@ int simmr_pileup_read(simmr_engine* e, uint32_t* counts_device, uint64_t capacit
 /* HIP-event time (ms) of the last simmr_pileup_add's device work.  Synchronises the stream. */
 int simmr_last_pileup_ms(simmr_engine* e, float* ms);
 
+/* ---- the true alignments as SAM text: one alignment line per read, formatted on the device ---------------------------------
+ * Replaces nothing in the reference.  The form of ground truth that samtools, variant callers and aligner-scoring scripts take
+ * directly, made from the read columns (simmr_reads_out) and the caller-owned truth columns (simmr_truth_out) that
+ * simmr_truth_plan / simmr_truth_emit filled — without draining the reads, and without touching the genome planes: NM and MD
+ * need edit_off, edit_pos and edit_ref only.  The lines carry no header: @HD, @SQ and @PG are a few lines for the host.
+ *
+ * Record of read r.  lo = min(start, end), hi = max(start, end), L = hi - lo, rev = flags & SIMMR_FLAG_REVCOMP.  Eleven
+ * tab-separated fields, two tags, '\n':
+ *   QNAME  read_id[r] in decimal (mates share it)
+ *   FLAG   paired: 0x1 | 0x2 | (rev ? 0x10 : 0) | (rev of read r^1 ? 0x20 : 0) | ((r & 1) ? 0x80 : 0x40); else rev ? 16 : 0
+ *   RNAME  the name given for (genome[r], contig[r])
+ *   POS    lo + 1
+ *   MAPQ   255
+ *   CIGAR  <L>M (no profile changes a read's length); for L == 0: *, with SEQ and QUAL * and MD 0
+ *   RNEXT PNEXT TLEN   paired: =, lo of read r^1 plus 1, and the signed span; else *, 0, 0.  The span of a pair is max(hi) -
+ *          min(lo) over the two mates: positive for the mate with the smaller lo (on a tie mate 1), negative for the other.
+ *          Mates of a re-drawn window (SIMMR_FLAG_REDRAWN) follow the same rule.
+ *   SEQ    the read on the forward strand: the bytes of seq[] as written, or for a rev read their reverse complement (ACGTN,
+ *          other bytes kept); then every byte that is not one of A C G T N is written as N (SAM has no '-')
+ *   QUAL   the bytes of qual[] for the read, back to front for a rev read (reads->qual_offset must be 33)
+ *   NM:i:  edit_off[r + 1] - edit_off[r]
+ *   MD:Z:  forward-strand order: the number of matching bases, a reference base, the next number, and so on; it begins and
+ *          ends with a number, so two adjacent edits have 0 between them.  For a rev read the edits are taken from last to
+ *          first, at forward offset L - 1 - edit_pos, with edit_ref complemented.  A reference byte outside ACGT is written N.
+ * Both layouts are read (for SIMMR_SLOT16 the qualities start at seq_off & ~15 and reverse mates are right-aligned).  `reads`
+ * must carry every column, read_id included; `truth` edit_off, edit_pos and edit_ref; with `paired`, n_reads is even.
+ *
+ * The text is a function of the inputs alone: sizes are counted and scanned, records written at their offsets; no atomic hands
+ * out space and launch geometry changes no byte.  No store of record r leaves its own bytes of dst even when the columns were
+ * changed between the plan and the emit, and no load leaves a read's own bytes of seq[] / qual[] in either layout. */
+typedef struct simmr_sam_names {      /* HOST memory */
+  uint32_t n_genomes;
+  const uint32_t* genome_idx;         /* engine genome slot of each entry */
+  const uint32_t* n_contigs;          /* contigs of each entry, as staged */
+  const char* const* rname;           /* RNAME per contig, flattened entry by entry, NUL-terminated */
+} simmr_sam_names;
+/* Sizes every record on the device, scans the sizes into offsets the engine holds, and returns the total.  Fewer than 2^31
+ * reads a call (SIMMR_ERANGE).
+ * SIMMR_EINVAL: a required column is missing, qual_offset != 33, `paired` with an odd n_reads, a names entry that is not a staged
+ * slot (or not with that many contigs); and, found on the device and reported through an error word, with nothing loaded or
+ * stored for that read: a read whose genome / contig has no name, whose seq_off leaves seq_capacity, whose length is above
+ * 65 535, whose edit_off decreases or leaves edits_capacity; an edit_pos >= L, or edits that do not ascend within a read.
+ * SIMMR_ENOTSUP: an RNAME that is empty, longer than 254 bytes, or outside SAM's
+ * [0-9A-Za-z!#$%&+./:;?@^_|~-][0-9A-Za-z!#$%&*+./:;=?@^_|~-]*. */
+int simmr_sam_plan(simmr_engine* e, const simmr_sam_names* names, const simmr_reads_out* reads,
+                   const simmr_truth_out* truth, uint64_t n_reads, int paired, uint64_t* total_bytes);
+/* Writes the n_reads alignment lines back to back into dst (DEVICE memory of at least total_bytes bytes) and synchronises.
+ * SIMMR_ESTATE: no simmr_sam_plan for the same columns — every pointer of `reads`, its seq_capacity and layout, and edit_off,
+ * edit_pos, edit_ref and edits_capacity of `truth` are the plan's — or a staging call since.  SIMMR_ERANGE, nothing written:
+ * dst_capacity < total_bytes.  SIMMR_EINVAL: the CONTENTS of the columns were changed since the plan so that a read fails a check
+ * again.  A read refused by the bounds check (names, seq_off, length, edit_off) has its record left unwritten; a read whose
+ * edit_pos entries no longer ascend below L is found while its MD is written, and its record is then unspecified — partly
+ * written, its MD short — but inside its own bytes.  In both cases no store leaves any record's own bytes. */
+int simmr_sam_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_truth_out* truth,
+                   uint8_t* dst, uint64_t dst_capacity);
+/* HIP-event time (ms) of the last simmr_sam_plan's device work (size pass + scan) plus that of the simmr_sam_emit after it,
+ * if any.  Synchronises the stream. */
+int simmr_last_sam_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,16 @@ class PileupSites(C.Structure):
     ]
 
 
+class SamNames(C.Structure):
+    """struct simmr_sam_names (host memory)"""
+    _fields_ = [
+        ("n_genomes", C.c_uint32),
+        ("genome_idx", C.POINTER(C.c_uint32)),
+        ("n_contigs", C.POINTER(C.c_uint32)),
+        ("rname", C.POINTER(C.c_char_p)),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -277,6 +287,9 @@ SYMBOLS = {
     "simmr_pileup_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64]),
     "simmr_pileup_read": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_last_pileup_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_sam_plan": (C.c_int, [C.c_void_p, _P(SamNames), _P(ReadsOut), _P(TruthOut), C.c_uint64, C.c_int, _P(C.c_uint64)]),
+    "simmr_sam_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut), C.c_void_p, C.c_uint64]),
+    "simmr_last_sam_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

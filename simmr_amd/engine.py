@@ -392,6 +392,39 @@ class Engine:
         self._check(self.lib.simmr_last_truth_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- the true alignments as SAM text ---------------------------------------------
+    def _sam_names(self, rnames):
+        n = len(rnames)
+        gi = (C.c_uint32 * max(n, 1))(*[int(x[0]) for x in rnames])
+        nc = (C.c_uint32 * max(n, 1))(*[len(x[1]) for x in rnames])
+        flat = [str(name).encode() for x in rnames for name in x[1]]
+        names = (C.c_char_p * max(len(flat), 1))(*flat)
+        sn = _abi.SamNames(n, gi, nc, names)
+        sn._keep = (gi, nc, names)
+        return sn
+
+    def sam(self, reads: Reads, rnames, paired: bool, truth: Optional[Truth] = None):
+        """The alignment lines of `reads` (simmr_sam_plan + simmr_sam_emit) as a CUDA uint8 tensor, without a header
+        (simmr_amd.sam.sam_header writes one).  `rnames` = [(engine genome slot, [RNAME per contig]), ...]; the reads
+        must have been emitted with qual_offset=33.  `truth`: what Engine.truth(reads) returned; made here if None."""
+        torch = _torch()
+        t = truth if truth is not None else self.truth(reads)
+        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
+                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        sn = self._sam_names(rnames)
+        pod = reads.pod()
+        total = C.c_uint64(0)
+        self._check(self.lib.simmr_sam_plan(self._h, C.byref(sn), C.byref(pod), C.byref(out), reads.n_reads,
+                                            1 if paired else 0, C.byref(total)))
+        text = torch.empty(max(total.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.simmr_sam_emit(self._h, C.byref(pod), C.byref(out), C.c_void_p(text.data_ptr()), total.value))
+        return text[: total.value]
+
+    def last_sam_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_sam_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- strain divergence ------------------------------------------------------------
     def strain_plan(self, genome_idx: int, identity: float, seed: int) -> int:
         """Counts the sites that `identity` and `seed` give genome slot `genome_idx` (simmr_strain_plan); returns their total."""

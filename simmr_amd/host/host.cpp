@@ -9,8 +9,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <ctype.h>
+
 #include <algorithm>
 #include <fstream>
+#include <set>
 #include <random>
 #include <sstream>
 
@@ -265,6 +268,36 @@ bool write_to_fastq(const std::string& genome_uuid, const Genome& genome, const 
     out.append("\n", 1);
   }
   return out.close(err);
+}
+
+// --------------------------------------------------------------- SAM
+std::string sam_rname(const std::string& id) {
+  const char* ws = " \t\n\v\f\r";
+  const size_t a = id.find_first_not_of(ws);
+  if (a == std::string::npos) return "";
+  const size_t b = id.find_first_of(ws, a);
+  return id.substr(a, b == std::string::npos ? std::string::npos : b - a);
+}
+bool sam_rname_legal(const std::string& n) {
+  if (n.empty() || n.size() > 254) return false;
+  for (size_t i = 0; i < n.size(); i++) {
+    const unsigned char c = (unsigned char)n[i];
+    if (isalnum(c) || (c != 0 && strchr("!#$%&+./:;?@^_|~-", c))) continue;
+    if (i > 0 && (c == '*' || c == '=')) continue;
+    return false;
+  }
+  return true;
+}
+bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<uint64_t>& lengths, std::string* out, std::string* err) {
+  std::set<std::string> seen;
+  *out = "@HD\tVN:1.6\tSO:unsorted\n";
+  for (size_t k = 0; k < rnames.size(); k++) {
+    if (!sam_rname_legal(rnames[k])) { *err = "'" + rnames[k] + "' is not a SAM reference name"; return false; }
+    if (!seen.insert(rnames[k]).second) { *err = "two sequences share the RNAME '" + rnames[k] + "'"; return false; }
+    *out += "@SQ\tSN:" + rnames[k] + "\tLN:" + std::to_string(lengths[k]) + "\n";
+  }
+  *out += "@PG\tID:simmr-hip\tPN:simmr-hip\n";
+  return true;
 }
 
 // --------------------------------------------------------------- ground truth per read
@@ -620,6 +653,12 @@ std::string usage() {
          "            --truth <FILE>  per-read ground truth as a TSV: read_id pair genome_id sequence_id start end strand length NM edits\n"
          "                            (edits: * or pos:REF>ALT:Q, ...; found on the device by comparing every read with the staged genome;\n"
          "                             not with --devices)\n"
+         "            --sam <FILE>    the true alignments as SAM: @HD / @SQ / @PG, then one line per read in read order with FLAG, the mate\n"
+         "                            fields, SEQ and QUAL on the forward strand, NM:i: and MD:Z: (CIGAR <L>M, MAPQ 255, unsorted, no @RG);\n"
+         "                            formatted on the device from the reads and their ground truth (turns the truth pass on); RNAME is the\n"
+         "                            first word of the sequence id and must be unique in the run; QNAME is the read id, so\n"
+         "                            --read-header-format '@{:read_id:}/{:pair:}' makes the FASTQ names match; combines with --truth;\n"
+         "                            not with --devices\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -719,6 +758,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--host-fastq") a->host_fastq = true;
     else if (arg == "--host-normalize") a->host_normalize = true;
     else if (arg == "--truth") { if (!file(&a->truth)) return false; }
+    else if (arg == "--sam") { if (!file(&a->sam)) return false; }
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
@@ -862,6 +902,14 @@ uint32_t simmr_host_ctr_splice_tables(const uint32_t* alt, const float* w, uint3
                                       uint32_t* thr, uint32_t* alias) {
   return simmr::ctr_splice_tables(alt, w, n, self_code, has_self != 0, thr, alias);
 }
+// The SAM header of sam_header_text for n names and lengths.  Returns the text, or "ERR\t..." .
+char* simmr_host_sam_header(uint32_t n, const char* const* rname, const uint64_t* length) {
+  std::string out, err;
+  if (!sam_header_text(std::vector<std::string>(rname, rname + n), std::vector<uint64_t>(length, length + n), &out, &err)) return dup_str("ERR\t" + err);
+  return dup_str(out);
+}
+// RNAME of a sequence id (sam_rname)
+char* simmr_host_sam_rname(const char* sequence_id) { return dup_str(sam_rname(sequence_id)); }
 char* simmr_host_normalize(const char* raw, uint64_t n) { return dup_str(normalize(std::string(raw, n))); }
 char* simmr_host_format_f64(double v) { return dup_str(format_f64_display(v)); }
 char* simmr_host_format_header(const char* fmt, const char* genome_id, uint32_t read_id, const char* seq_id,

@@ -79,18 +79,47 @@ struct DeviceOut {
   }
 };
 
-// The truth columns of one range's reads (simmr_truth_plan / simmr_truth_emit on the columns `d`), copied to the host.
-static bool device_truth(simmr_engine* eng, const simmr_reads_out* reads, uint64_t n_reads, HostTruth* t, std::string* err) {
+// The truth columns of one range's reads (simmr_truth_plan / simmr_truth_emit on the columns `d`): on the device in `o`, owned
+// by `mem`, and copied to the host if `t` is given.
+static bool device_truth(simmr_engine* eng, const simmr_reads_out* reads, uint64_t n_reads, DeviceMem* mem, simmr_truth_out* o, HostTruth* t,
+                         std::string* err) {
   uint64_t m = 0;
   if (simmr_truth_plan(eng, reads, n_reads, &m) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
-  DeviceMem mem;
-  simmr_truth_out o{};
-  o.reads_capacity = n_reads; o.edits_capacity = m;
-  if (!(mem.alloc(&o.nm, n_reads) && mem.alloc(&o.edit_off, n_reads + 1) && mem.alloc(&o.edit_pos, m) && mem.alloc(&o.edit_ref, m) &&
-        mem.alloc(&o.edit_alt, m) && mem.alloc(&o.edit_qual, m))) { *err = "device allocation failed"; return false; }
-  if (simmr_truth_emit(eng, reads, &o) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
-  if (!(mem.fetch(&t->nm, o.nm, n_reads) && mem.fetch(&t->edit_off, o.edit_off, n_reads + 1) && mem.fetch(&t->edit_pos, o.edit_pos, m) &&
-        mem.fetch(&t->edit_ref, o.edit_ref, m) && mem.fetch(&t->edit_alt, o.edit_alt, m) && mem.fetch(&t->edit_qual, o.edit_qual, m))) { *err = "copy back failed"; return false; }
+  *o = simmr_truth_out{};
+  o->reads_capacity = n_reads; o->edits_capacity = m;
+  if (!(mem->alloc(&o->nm, n_reads) && mem->alloc(&o->edit_off, n_reads + 1) && mem->alloc(&o->edit_pos, m) && mem->alloc(&o->edit_ref, m) &&
+        mem->alloc(&o->edit_alt, m) && mem->alloc(&o->edit_qual, m))) { *err = "device allocation failed"; return false; }
+  if (simmr_truth_emit(eng, reads, o) != SIMMR_OK) { *err = simmr_last_error(eng); return false; }
+  if (t && !(mem->fetch(&t->nm, o->nm, n_reads) && mem->fetch(&t->edit_off, o->edit_off, n_reads + 1) && mem->fetch(&t->edit_pos, o->edit_pos, m) &&
+             mem->fetch(&t->edit_ref, o->edit_ref, m) && mem->fetch(&t->edit_alt, o->edit_alt, m) && mem->fetch(&t->edit_qual, o->edit_qual, m))) { *err = "copy back failed"; return false; }
+  return true;
+}
+
+// `--sam`, before any device work: every sequence of the run's FASTA files gets its RNAME (the first word of its id; under
+// --contiguous a genome is the one sequence "whole genome"), which has to be a SAM reference name that no other sequence of the
+// run has.  false with the one message that names the sequence.  A file that cannot be read is left to the loading code.
+static bool sam_check_names(const CliArgs& args, std::string* err) {
+  std::vector<std::string> paths = args.genome;
+  if (args.genome_file) {
+    std::vector<GenomeRecord> records;
+    std::string e;
+    if (!parse_genome_file(*args.genome_file, &records, &e)) return true;
+    for (const GenomeRecord& r : records) paths.push_back(r.filepath);
+  }
+  std::vector<std::pair<std::string, std::string>> seen;  // RNAME, "sequence 'id' of path"
+  for (const std::string& path : paths) {
+    FastaRecords recs;
+    std::string e;
+    if (!scan_fasta(path, &recs, &e)) continue;
+    std::vector<std::string> ids = args.contiguous ? std::vector<std::string>{"whole genome"} : recs.ids;
+    for (const std::string& id : ids) {
+      const std::string rname = sam_rname(id), who = "sequence '" + id + "' of " + path;
+      if (!sam_rname_legal(rname)) { *err = "--sam: " + who + " gets the RNAME '" + rname + "', which is not a SAM reference name"; return false; }
+      for (const auto& s : seen)
+        if (s.first == rname) { *err = "--sam: " + who + " gets the RNAME '" + rname + "', which " + s.second + " has already"; return false; }
+      seen.emplace_back(rname, who);
+    }
+  }
   return true;
 }
 
@@ -205,7 +234,7 @@ static bool write_vcf_file(simmr_engine* eng, const CliArgs& args, const std::ve
   return write_strain_vcf(genomes, lens, sites, site_genome, counts, args.strain_vcf, err);
 }
 
-// The side outputs of a run: --truth, --stats, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
+// The side outputs of a run: --truth, --sam, --stats, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
 // takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
 struct SideOutputs {
   explicit SideOutputs(const CliArgs& args) : a(args) {}
@@ -216,29 +245,65 @@ struct SideOutputs {
   uint64_t depth_positions = 0, depth_contigs = 0;
   HostStrainSites sites;             // --strain-vcf: what diverge_genomes kept, and each site's genome
   std::vector<uint32_t> site_genome;
+  std::vector<std::string> sam_names;  // --sam: RNAME per sequence, genome by genome (simmr_sam_names), and where each genome's begin
+  std::vector<uint32_t> sam_genome, sam_contigs;
   bool vcf() const { return !a.strain_vcf.empty(); }
+  bool sam() const { return !a.sam.empty(); }
   bool depth_files() const { return !a.depth.empty() || !a.depth_track.empty(); }
   bool gold() const { return !a.gold_assembly.empty() || !a.gold_regions.empty(); }
   bool depth() const { return depth_files() || gold(); }  // (the gold-standard assembly is read off the run's depth[])
-  bool wanted() const { return !a.truth.empty() || !a.stats.empty() || depth() || vcf(); }
+  bool wanted() const { return !a.truth.empty() || sam() || !a.stats.empty() || depth() || vcf(); }
   bool fail(const char* flag, const std::string& what) { err = std::string(flag) + ": " + what; return false; }
   // true, with the message, if one of them is asked for together with --devices
   bool refuse_devices() {
-    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : nullptr;
+    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : sam() ? "--sam" : nullptr;
     if (flag && !a.devices.empty()) err = std::string(flag) + " does not combine with --devices: use --device";
     return flag && !a.devices.empty();
   }
   // the old files go, the truth file gets its header line (every range appends its reads), the tables start at zero
   // (the genomes are staged: depth[] covers all of them)
   bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
-    for (const std::string* f : {&a.truth, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
+    for (const std::string* f : {&a.truth, &a.sam, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
       if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
     std::string e;
     if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
+    if (sam() && !begin_sam(genomes)) return false;
     if (!a.stats.empty() && simmr_stats_reset(eng) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
     // (--strain-vcf takes the sequences' lengths from the layout the depth reset records)
     if ((depth() || vcf()) && simmr_depth_reset(eng, &depth_positions, &depth_contigs) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
     return !vcf() || begin_pileup(eng);
+  }
+  // the names of the run's sequences as the device wants them, and the header: once, before the first range
+  bool begin_sam(const std::vector<Genome>& genomes) {
+    std::vector<uint64_t> lengths;
+    for (size_t g = 0; g < genomes.size(); g++) {
+      sam_genome.push_back((uint32_t)g);
+      sam_contigs.push_back((uint32_t)genomes[g].sequence.size());
+      for (const Seq& q : genomes[g].sequence) { sam_names.push_back(sam_rname(q.id)); lengths.push_back(q.size); }
+    }
+    std::string text, e;
+    if (!sam_header_text(sam_names, lengths, &text, &e)) return fail("--sam", e);
+    OutFile f(a.sam, false);
+    f.append(text);
+    return f.close(&e) || fail("--sam", e);
+  }
+  // the alignment lines of one range, formatted on the device from its columns and truth columns, appended to the file
+  bool sam_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
+    std::vector<const char*> names;
+    for (const std::string& n : sam_names) names.push_back(n.c_str());
+    simmr_sam_names sn{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), names.data()};
+    uint64_t total = 0;
+    if (simmr_sam_plan(eng, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--sam", simmr_last_error(eng));
+    DeviceMem mem;
+    uint8_t* text = nullptr;
+    std::vector<uint8_t> h;
+    if (!mem.alloc(&text, total)) return fail("--sam", "device allocation failed");
+    if (simmr_sam_emit(eng, &reads, &t, text, total) != SIMMR_OK) return fail("--sam", simmr_last_error(eng));
+    if (!mem.fetch(&h, text, total)) return fail("--sam", "copy back failed");
+    std::string e;
+    OutFile f(a.sam, true);
+    f.append(h.data(), h.size());
+    return f.close(&e) || fail("--sam", e);
   }
   // the kept sites go up as one list — genome index, contig, pos: ascending, genome by genome — and the table starts at zero
   bool begin_pileup(simmr_engine* eng) {
@@ -260,8 +325,11 @@ struct SideOutputs {
     if (vcf() && simmr_pileup_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--strain-vcf", simmr_last_error(eng));
     std::string e;
     qual_offset = reads.qual_offset;
-    if (!a.truth.empty() && !device_truth(eng, &reads, n_reads, &truth, &e)) return fail("--truth", e);
-    return true;
+    if (a.truth.empty() && !sam()) return true;
+    DeviceMem mem;  // the truth columns on the device: --truth copies them out, --sam formats from them
+    simmr_truth_out t{};
+    if (!device_truth(eng, &reads, n_reads, &mem, &t, a.truth.empty() ? nullptr : &truth, &e)) return fail(a.truth.empty() ? "--sam" : "--truth", e);
+    return !sam() || sam_range(eng, reads, t, n_reads, paired);
   }
   bool write_range(const std::vector<Genome>& genomes, const HostReads& h) {
     std::string e;
@@ -655,6 +723,7 @@ static int run_main(int argc, char** argv) {
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);
+  if (side.sam() && !sam_check_names(args, &err)) return die(err);
   std::unique_ptr<ErrorProfile> eprofile = determine_error_profile(args, &err);  // main.rs:27
   if (!eprofile) return die(err);
   // main.rs:30-33

@@ -140,6 +140,16 @@ struct HostTruth {
 bool write_truth_tsv(const std::vector<Genome>& genomes, const HostReads& reads, const HostTruth& truth, uint32_t qual_offset,
                      const std::string& output, bool with_header, std::string* err);
 
+// ---------------------------------------------------------------- SAM (no reference counterpart)
+// `simmr-hip --sam FILE`: the alignment lines come from the device (simmr_sam_plan / simmr_sam_emit); the host gives the names
+// and writes the header.  RNAME of a sequence: the first whitespace-delimited token of its id.
+std::string sam_rname(const std::string& sequence_id);
+// SAM's [0-9A-Za-z!#$%&+./:;?@^_|~-][0-9A-Za-z!#$%&*+./:;=?@^_|~-]*, at most 254 bytes
+bool sam_rname_legal(const std::string& rname);
+// "@HD\tVN:1.6\tSO:unsorted", one "@SQ\tSN:..\tLN:.." per name in order, "@PG\tID:simmr-hip\tPN:simmr-hip".  false with *err naming
+// the first name that is not legal or that an earlier one has already.
+bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<uint64_t>& lengths, std::string* out, std::string* err);
+
 // ---------------------------------------------------------------- strain sites (no reference counterpart)
 // Host copy of simmr_strain_out for one genome.
 struct HostStrainSites {
@@ -308,6 +318,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   bool host_normalize = false;  // --host-normalize: normalise FASTA on the host instead of the device
   bool host_fastq = false;  // --host-fastq: frame the FASTQ on the host instead of the device
   std::string truth;  // --truth FILE: per-read mismatch counts and edit lists (simmr_truth_plan / simmr_truth_emit) as a TSV
+  std::string sam;    // --sam FILE: the true alignments as SAM (simmr_sam_plan / simmr_sam_emit on every range's columns, the header from the host)
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions
