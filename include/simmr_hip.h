@@ -837,6 +837,42 @@ int simmr_sam_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_tr
  * if any.  Synchronises the stream. */
 int simmr_last_sam_ms(simmr_engine* e, float* ms);
 
+/* ---- the same lines in coordinate order: a stable radix sort of the reads on the device ---------------------------------------
+ * What samtools index, IGV, pileup-based callers and gold-standard BAMs want.  Sorting is a permutation of where the records are
+ * written, not a second pass over text: (key, read) pairs are sorted, the record sizes scanned in sorted order, and the record
+ * writer of simmr_sam_emit puts each line at its sorted offset.
+ *
+ * Key of read r.  row = the index of (genome[r], contig[r]) among the contigs of `names`, flattened entry by entry: the order in
+ * which a caller writes the @SQ lines.  lo = min(start, end).  key = (row << 40) | lo.
+ * Order.  Records ascend by key; equal keys ascend by read index r (the sort is stable).  Every read is mapped, so there is no
+ * "unmapped last" class; a read with L == 0 sorts by its lo like any other.  Each line's bytes are exactly those simmr_sam_emit
+ * writes for that read: the mate fields stay as they are, mates merely stop being adjacent.  The text is a function of the inputs
+ * alone: no atomic decides a position and launch geometry changes no byte.
+ * Limits.  More than 2^24 named contigs, or a named contig of 2^40 bases or more: SIMMR_ERANGE on the host.  A read whose
+ * max(start, end) exceeds the staged length of its contig: refused on the device through the error word (SIMMR_EINVAL), with
+ * nothing loaded or stored for it — a check the unsorted calls do not make; it is what bounds the key's width.
+ * The sort runs over the significant bits only — bits(longest named contig) + bits(rows - 1) — in 8-bit digits. */
+
+/* The widths of the internal sort key for a names set of n_rows contigs, the longest of longest_contig bases; either pointer may
+ * be NULL.  SIMMR_ERANGE: the limits above.  Needs no engine. */
+int simmr_sam_sort_key_bits(uint64_t n_rows, uint64_t longest_contig, uint32_t* pos_bits, uint32_t* row_bits);
+/* simmr_sam_plan's arguments, checks and status codes, with the limits above on top; *total_bytes is what simmr_sam_plan returns
+ * for the same input.  Sizes the records, sorts the reads and scans the sizes in sorted order; the engine holds the result in a
+ * state of its own: a sorted plan and an unsorted plan on one engine do not disturb each other. */
+int simmr_sam_sort_plan(simmr_engine* e, const simmr_sam_names* names, const simmr_reads_out* reads,
+                        const simmr_truth_out* truth, uint64_t n_reads, int paired, uint64_t* total_bytes);
+/* simmr_sam_emit's arguments, checks and status codes (the plan meant is the last simmr_sam_sort_plan): the n_reads lines in
+ * coordinate order, back to back in dst.  Every store of the i-th line is bounded by that line's planned length, so columns
+ * changed since the plan cannot carry a store out of a record.
+ * key_out (DEVICE, n_reads entries, may be NULL): the key of the i-th line written.  line_off_out (DEVICE, n_reads + 1 entries,
+ * may be NULL): the offset of the i-th line in dst, and total_bytes behind the last.  With them a caller merges several sorted
+ * ranges without parsing text. */
+int simmr_sam_sort_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_truth_out* truth,
+                        uint8_t* dst, uint64_t dst_capacity, uint64_t* key_out, uint64_t* line_off_out);
+/* HIP-event time (ms) of the last simmr_sam_sort_plan's device work (sizes and keys, the sort passes, the scan) plus that of the
+ * simmr_sam_sort_emit after it, if any.  Synchronises the stream. */
+int simmr_last_sam_sort_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -290,6 +290,10 @@ SYMBOLS = {
     "simmr_sam_plan": (C.c_int, [C.c_void_p, _P(SamNames), _P(ReadsOut), _P(TruthOut), C.c_uint64, C.c_int, _P(C.c_uint64)]),
     "simmr_sam_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut), C.c_void_p, C.c_uint64]),
     "simmr_last_sam_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_sam_sort_key_bits": (C.c_int, [C.c_uint64, C.c_uint64, _P(C.c_uint32), _P(C.c_uint32)]),
+    "simmr_sam_sort_plan": (C.c_int, [C.c_void_p, _P(SamNames), _P(ReadsOut), _P(TruthOut), C.c_uint64, C.c_int, _P(C.c_uint64)]),
+    "simmr_sam_sort_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "simmr_last_sam_sort_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

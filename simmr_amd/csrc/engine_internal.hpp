@@ -1,4 +1,4 @@
-// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip) may ask of an engine.  simmr_engine is
+// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip) may ask of an engine.  simmr_engine is
 // defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,7 +31,7 @@ SIMMR_HIDDEN void eng_genome_planes(const simmr_engine* e, uint32_t slot, uint32
 SIMMR_HIDDEN void eng_planes_rewritten(simmr_engine* e);
 // One opaque slot per engine and translation unit for that unit's state; simmr_engine_destroy calls `destroy` on a non-null
 // slot (on the engine's device, after the device has been synchronised).
-enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_COUNT = 5 };
+enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_COUNT = 6 };
 SIMMR_HIDDEN void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*));
 // The layout of depth[] that the last simmr_depth_reset recorded (defined in depth.hip): tracked contig k is entries
 // cfirst[k] .. cfirst[k + 1] - 1 (n_contigs + 1 entries, on the host and on the device) and contig c_contig[k] of genome slot

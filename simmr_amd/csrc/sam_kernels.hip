@@ -30,6 +30,10 @@
 // sets the error word and loads and stores nothing.  Every store of record r is bounded by off[r + 1] - off[r] (`room`),
 // as k_truth<true> bounds its stores by `limit`: columns changed between the plan and the emit cannot carry a store out
 // of the record.
+// sam_sort_kernels.hip (the coordinate-sorted form, a unit of its own) includes this file with SAM_ROUTINES_ONLY defined: the
+// constants, the record routine and the scans' bodies without the four kernels, which stay in sam.hip's budget alone.  For
+// that form the place of a record is a parameter of sam_record (`at`: the entry of off[] the record starts at) beside the
+// read it shows: here the two are the same number.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -257,10 +261,11 @@ SIMMR_DEV uint32_t sam_format_head(uint8_t* slot, const SamRead& R, uint32_t pai
 }
 
 // ---- a record: its length (WRITE == false) or its bytes (WRITE == true) ------------------------------------------------
-// Called by all 16 lanes of a row for read r; returns the record's bytes (0 for a refused read) in every lane.
+// Called by all 16 lanes of a row for read r; returns the record's bytes (0 for a refused read) in every lane.  The record
+// is bytes off[at] .. off[at + 1] of dst.
 template <bool WRITE>
-SIMMR_DEV uint32_t sam_record(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t n_reads, uint32_t paired,
-                              uint32_t sub, uint8_t* slot, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst,
+SIMMR_DEV uint32_t sam_record(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t at, uint64_t n_reads,
+                              uint32_t paired, uint32_t sub, uint8_t* slot, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst,
                               uint32_t* __restrict__ err) {
   const SamRead R = sam_open(rd, ed, nm, r, n_reads, paired, err, sub == 0u);
   if (!R.good) return 0u;
@@ -268,7 +273,7 @@ SIMMR_DEV uint32_t sam_record(const SamReads& rd, const SamEdits& ed, const SamN
   uint32_t H, T, room = 0;
   uint8_t* rec = nullptr;
   if (WRITE) {
-    const uint64_t o0 = off[r], o1 = off[r + 1];
+    const uint64_t o0 = off[at], o1 = off[at + 1];
     room = (o1 >= o0 && o1 - o0 <= 0xffffffffull) ? (uint32_t)(o1 - o0) : 0u;
     rec = dst + o0;
     uint32_t h = 0, t = 0;
@@ -354,33 +359,6 @@ SIMMR_DEV uint32_t sam_record(const SamReads& rd, const SamEdits& ed, const SamN
   return md0 + cursor;
 }
 
-// ---- sizes ----------------------------------------------------------------------------------------------------------
-// A workgroup takes chunks of SAM_CHUNK consecutive reads, 16 at a time, and leaves every chunk's sum: the scan's first level.
-extern "C" __global__ void __launch_bounds__(256)
-k_sam_size(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, uint32_t* __restrict__ len,
-           uint64_t* __restrict__ chunk_sum, uint32_t* __restrict__ err) {
-  __shared__ uint32_t part[SAM_WG_READS];
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1u) / SAM_CHUNK;
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-    uint32_t acc = 0;  // (a record is below 2^20 bytes: 64 of them fit)
-    for (uint32_t it = 0; it < SAM_CHUNK / SAM_WG_READS; it++) {
-      const uint64_t r = chunk * SAM_CHUNK + it * SAM_WG_READS + row;
-      const uint32_t bytes = sam_record<false>(rd, ed, nm, r, n_reads, paired, sub, nullptr, nullptr, nullptr, err);
-      if (sub == 0u && r < n_reads) len[r] = bytes;
-      acc += bytes;
-    }
-    if (sub == 0u) part[row] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t s = 0;
-      for (uint32_t i = 0; i < SAM_WG_READS; i++) s += part[i];
-      chunk_sum[chunk] = s;
-    }
-    __syncthreads();
-  }
-}
-
 // exclusive scan of one value per thread over the 256-thread workgroup through LDS; *total = the sum
 template <class T>
 SIMMR_DEV T sam_wg_scan(T v, T* lds, T* total) {
@@ -400,9 +378,7 @@ SIMMR_DEV T sam_wg_scan(T v, T* lds, T* total) {
 }
 
 // ONE workgroup: prefix[c] = the bytes before chunk c, prefix[n] = the total
-extern "C" __global__ void __launch_bounds__(256)
-k_sam_scan(const uint64_t* __restrict__ sum, uint64_t* __restrict__ prefix, uint64_t n) {
-  __shared__ uint64_t lds[256];
+SIMMR_DEV void sam_scan_chunks(const uint64_t* __restrict__ sum, uint64_t* __restrict__ prefix, uint64_t n, uint64_t* lds) {
   uint64_t carry = 0;
   for (uint64_t base = 0; base < n; base += 256u) {  // (uniform over the workgroup)
     const uint64_t i = base + threadIdx.x;
@@ -415,9 +391,8 @@ k_sam_scan(const uint64_t* __restrict__ sum, uint64_t* __restrict__ prefix, uint
 }
 
 // a workgroup per chunk, four consecutive reads per thread: off[r] for r < n_reads, and off[n_reads] = the total
-extern "C" __global__ void __launch_bounds__(256)
-k_sam_offsets(const uint32_t* __restrict__ len, const uint64_t* __restrict__ prefix, uint64_t n_reads, uint64_t* __restrict__ off) {
-  __shared__ uint32_t lds[256];
+SIMMR_DEV void sam_chunk_offsets(const uint32_t* __restrict__ len, const uint64_t* __restrict__ prefix, uint64_t n_reads,
+                                 uint64_t* __restrict__ off, uint32_t* lds) {
   const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1u) / SAM_CHUNK;
   if (blockIdx.x == 0 && threadIdx.x == 0) off[n_reads] = prefix[n_chunks];
   for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {  // (uniform over the workgroup)
@@ -436,6 +411,54 @@ k_sam_offsets(const uint32_t* __restrict__ len, const uint64_t* __restrict__ pre
   }
 }
 
+// ---- the writer's body: one row of 16 lanes writes the record of read r at entry `at` of off[] --------------------------
+// k_sam_write calls it with at == r (read order); the ordered writer of sam_sort_kernels.hip with r = perm[at].
+SIMMR_DEV void sam_write_row(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t at, uint64_t n_reads,
+                             uint32_t paired, uint32_t sub, uint8_t* slot, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst,
+                             uint32_t* __restrict__ err) {
+  (void)sam_record<true>(rd, ed, nm, r, at, n_reads, paired, sub, slot, off, dst, err);
+}
+
+#ifndef SAM_ROUTINES_ONLY
+// ---- sizes ----------------------------------------------------------------------------------------------------------
+// A workgroup takes chunks of SAM_CHUNK consecutive reads, 16 at a time, and leaves every chunk's sum: the scan's first level.
+extern "C" __global__ void __launch_bounds__(256)
+k_sam_size(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, uint32_t* __restrict__ len,
+           uint64_t* __restrict__ chunk_sum, uint32_t* __restrict__ err) {
+  __shared__ uint32_t part[SAM_WG_READS];
+  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
+  const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1u) / SAM_CHUNK;
+  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
+    uint32_t acc = 0;  // (a record is below 2^20 bytes: 64 of them fit)
+    for (uint32_t it = 0; it < SAM_CHUNK / SAM_WG_READS; it++) {
+      const uint64_t r = chunk * SAM_CHUNK + it * SAM_WG_READS + row;
+      const uint32_t bytes = sam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, nullptr, err);
+      if (sub == 0u && r < n_reads) len[r] = bytes;
+      acc += bytes;
+    }
+    if (sub == 0u) part[row] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint64_t s = 0;
+      for (uint32_t i = 0; i < SAM_WG_READS; i++) s += part[i];
+      chunk_sum[chunk] = s;
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_sam_scan(const uint64_t* __restrict__ sum, uint64_t* __restrict__ prefix, uint64_t n) {
+  __shared__ uint64_t lds[256];
+  sam_scan_chunks(sum, prefix, n, lds);
+}
+
+extern "C" __global__ void __launch_bounds__(256)
+k_sam_offsets(const uint32_t* __restrict__ len, const uint64_t* __restrict__ prefix, uint64_t n_reads, uint64_t* __restrict__ off) {
+  __shared__ uint32_t lds[256];
+  sam_chunk_offsets(len, prefix, n_reads, off, lds);
+}
+
 // ---- the records ------------------------------------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(256)
 k_sam_write(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, const uint64_t* __restrict__ off,
@@ -444,7 +467,8 @@ k_sam_write(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_
   const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
   const uint64_t n_batches = (n_reads + SAM_WG_READS - 1u) / SAM_WG_READS;
   for (uint64_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x)
-    (void)sam_record<true>(rd, ed, nm, batch * SAM_WG_READS + row, n_reads, paired, sub, slots[row], off, dst, err);
+    sam_write_row(rd, ed, nm, batch * SAM_WG_READS + row, batch * SAM_WG_READS + row, n_reads, paired, sub, slots[row], off, dst, err);
 }
+#endif  // SAM_ROUTINES_ONLY
 
 }  // namespace simmr

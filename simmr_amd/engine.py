@@ -425,6 +425,35 @@ class Engine:
         self._check(self.lib.simmr_last_sam_ms(self._h, C.byref(ms)))
         return ms.value
 
+    def sam_sorted(self, reads: Reads, rnames, paired: bool, truth: Optional[Truth] = None, with_keys: bool = False):
+        """The alignment lines of Engine.sam() in coordinate order (simmr_sam_sort_plan + simmr_sam_sort_emit): ascending by
+        (index of the contig in `rnames`, leftmost position), ties in read order.  Returns the text tensor; with `with_keys`
+        (text, key, line_off): CUDA int64 tensors holding the key (row << 40 | lo) of every line written and the lines'
+        offsets (n_reads + 1)."""
+        torch = _torch()
+        t = truth if truth is not None else self.truth(reads)
+        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
+                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        sn = self._sam_names(rnames)
+        pod = reads.pod()
+        total = C.c_uint64(0)
+        self._check(self.lib.simmr_sam_sort_plan(self._h, C.byref(sn), C.byref(pod), C.byref(out), reads.n_reads,
+                                                 1 if paired else 0, C.byref(total)))
+        text = torch.empty(max(total.value, 1), dtype=torch.uint8, device=self.device)
+        key = torch.empty(max(reads.n_reads, 1), dtype=torch.int64, device=self.device) if with_keys else None
+        line_off = torch.empty(reads.n_reads + 1, dtype=torch.int64, device=self.device) if with_keys else None
+        self._check(self.lib.simmr_sam_sort_emit(self._h, C.byref(pod), C.byref(out), C.c_void_p(text.data_ptr()), total.value,
+                                                 C.c_void_p(key.data_ptr()) if with_keys else None,
+                                                 C.c_void_p(line_off.data_ptr()) if with_keys else None))
+        if with_keys:
+            return text[: total.value], key[: reads.n_reads], line_off
+        return text[: total.value]
+
+    def last_sam_sort_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_sam_sort_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- strain divergence ------------------------------------------------------------
     def strain_plan(self, genome_idx: int, identity: float, seed: int) -> int:
         """Counts the sites that `identity` and `seed` give genome slot `genome_idx` (simmr_strain_plan); returns their total."""

@@ -13,6 +13,7 @@
 
 #include <algorithm>
 #include <fstream>
+#include <queue>
 #include <set>
 #include <random>
 #include <sstream>
@@ -288,9 +289,10 @@ bool sam_rname_legal(const std::string& n) {
   }
   return true;
 }
-bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<uint64_t>& lengths, std::string* out, std::string* err) {
+bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<uint64_t>& lengths, std::string* out, std::string* err,
+                     bool coordinate) {
   std::set<std::string> seen;
-  *out = "@HD\tVN:1.6\tSO:unsorted\n";
+  *out = coordinate ? "@HD\tVN:1.6\tSO:coordinate\n" : "@HD\tVN:1.6\tSO:unsorted\n";
   for (size_t k = 0; k < rnames.size(); k++) {
     if (!sam_rname_legal(rnames[k])) { *err = "'" + rnames[k] + "' is not a SAM reference name"; return false; }
     if (!seen.insert(rnames[k]).second) { *err = "two sequences share the RNAME '" + rnames[k] + "'"; return false; }
@@ -298,6 +300,50 @@ bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<u
   }
   *out += "@PG\tID:simmr-hip\tPN:simmr-hip\n";
   return true;
+}
+
+// A heap of the runs' next lines, smallest (key, run) on top; a run's lines are read through a window of its text so that
+// the source is asked for large pieces, whatever the number of runs.
+bool sam_merge_sorted_runs(const std::vector<SamSortedRun>& runs, const std::function<bool(uint64_t, size_t, char*)>& read,
+                           const std::function<bool(const char*, size_t)>& write) {
+  struct Cursor {
+    size_t next = 0;          // the run's next line
+    uint64_t at = 0;          // its place in the source
+    std::vector<char> win;    // bytes [win_at, win_at + win.size()) of the source
+    uint64_t win_at = 0;
+  };
+  constexpr size_t WINDOW = 1u << 20;
+  std::vector<Cursor> cur(runs.size());
+  typedef std::pair<uint64_t, size_t> Top;  // key, run number
+  std::priority_queue<Top, std::vector<Top>, std::greater<Top>> heap;
+  for (size_t k = 0; k < runs.size(); k++) {
+    if (runs[k].key.size() != runs[k].len.size()) return false;
+    cur[k].at = runs[k].offset;
+    if (!runs[k].key.empty()) heap.emplace(runs[k].key[0], k);
+  }
+  std::string out;
+  while (!heap.empty()) {
+    const size_t k = heap.top().second;
+    heap.pop();
+    const SamSortedRun& run = runs[k];
+    Cursor& c = cur[k];
+    const size_t n = (size_t)run.len[c.next];
+    if (c.at < c.win_at || c.at + n > c.win_at + c.win.size()) {  // the line is not in the window: refill from the line on
+      uint64_t ahead = 0;  // whole lines, up to the window's size (one line at least)
+      for (size_t i = c.next; i < run.len.size() && (i == c.next || ahead + run.len[i] <= WINDOW); i++) ahead += run.len[i];
+      c.win.resize((size_t)ahead);
+      c.win_at = c.at;
+      if (ahead && !read(c.at, (size_t)ahead, c.win.data())) return false;
+    }
+    out.append(c.win.data() + (c.at - c.win_at), n);
+    if (out.size() >= WINDOW) {
+      if (!write(out.data(), out.size())) return false;
+      out.clear();
+    }
+    c.at += n;
+    if (++c.next < run.key.size()) heap.emplace(run.key[c.next], k);
+  }
+  return out.empty() || write(out.data(), out.size());
 }
 
 // --------------------------------------------------------------- ground truth per read
@@ -659,6 +705,9 @@ std::string usage() {
          "                            first word of the sequence id and must be unique in the run; QNAME is the read id, so\n"
          "                            --read-header-format '@{:read_id:}/{:pair:}' makes the FASTQ names match; combines with --truth;\n"
          "                            not with --devices\n"
+         "            --sam-sorted    the file of --sam in coordinate order, under @HD SO:coordinate: the lines ascend by (@SQ index, POS),\n"
+         "                            ties in read order, across every range of the run (each range is sorted on the device; several\n"
+         "                            ranges are merged through a temporary file beside FILE); needs --sam; not with --devices\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -759,6 +808,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--host-normalize") a->host_normalize = true;
     else if (arg == "--truth") { if (!file(&a->truth)) return false; }
     else if (arg == "--sam") { if (!file(&a->sam)) return false; }
+    else if (arg == "--sam-sorted") a->sam_sorted = true;
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
@@ -800,6 +850,8 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--uniform-start") a->uniform_start = true;
     else { *err = "Found argument '" + arg + "' which wasn't expected"; return false; }
   }
+  if (a->sam_sorted && a->sam.empty()) { *err = "--sam-sorted needs --sam"; return false; }
+  if (a->sam_sorted && !a->devices.empty()) { *err = "--sam-sorted does not combine with --devices: use --device"; return false; }
   if (!a->strain_sites.empty() && !a->with_ani) { *err = "--strain-sites needs --with-ani"; return false; }
   if (!a->strain_vcf.empty() && !a->with_ani) { *err = "--strain-vcf needs --with-ani"; return false; }
   // cli.rs:88-92: ArgGroup "genomes" is required, and --output has no default
@@ -907,6 +959,32 @@ char* simmr_host_sam_header(uint32_t n, const char* const* rname, const uint64_t
   std::string out, err;
   if (!sam_header_text(std::vector<std::string>(rname, rname + n), std::vector<uint64_t>(length, length + n), &out, &err)) return dup_str("ERR\t" + err);
   return dup_str(out);
+}
+// The header for a coordinate-sorted file
+char* simmr_host_sam_header_sorted(uint32_t n, const char* const* rname, const uint64_t* length) {
+  std::string out, err;
+  if (!sam_header_text(std::vector<std::string>(rname, rname + n), std::vector<uint64_t>(length, length + n), &out, &err, true)) return dup_str("ERR\t" + err);
+  return dup_str(out);
+}
+// sam_merge_sorted_runs over runs given as plain arrays: run k has run_lines[k] lines, its keys and lengths follow those of
+// run k - 1 in key[] / len[], its text begins at run_offset[k] of src (src_bytes bytes).  The merged bytes go to dst
+// (dst_capacity bytes); returns their number, or -1 if a run leaves src, the output leaves dst, or the merge fails.
+int64_t simmr_host_sam_merge(uint32_t n_runs, const uint64_t* run_lines, const uint64_t* run_offset, const uint64_t* key, const uint64_t* len,
+                             const char* src, uint64_t src_bytes, char* dst, uint64_t dst_capacity) {
+  std::vector<SamSortedRun> runs(n_runs);
+  size_t at = 0;
+  for (uint32_t k = 0; k < n_runs; k++) {
+    runs[k].key.assign(key + at, key + at + run_lines[k]);
+    runs[k].len.assign(len + at, len + at + run_lines[k]);
+    runs[k].offset = run_offset[k];
+    at += run_lines[k];
+  }
+  uint64_t written = 0;
+  const bool ok = sam_merge_sorted_runs(
+      runs,
+      [&](uint64_t off, size_t n, char* p) { if (off > src_bytes || n > src_bytes - off) return false; memcpy(p, src + off, n); return true; },
+      [&](const char* p, size_t n) { if (n > dst_capacity - written) return false; memcpy(dst + written, p, n); written += n; return true; });
+  return ok ? (int64_t)written : -1;
 }
 // RNAME of a sequence id (sam_rname)
 char* simmr_host_sam_rname(const char* sequence_id) { return dup_str(sam_rname(sequence_id)); }

@@ -247,6 +247,14 @@ struct SideOutputs {
   std::vector<uint32_t> site_genome;
   std::vector<std::string> sam_names;  // --sam: RNAME per sequence, genome by genome (simmr_sam_names), and where each genome's begin
   std::vector<uint32_t> sam_genome, sam_contigs;
+  // --sam-sorted: every range's lines come sorted from the device.  The first range's text waits in memory; from the second
+  // range on the texts lie back to back in a temporary file beside the SAM file, and finish() merges them by the keys and line
+  // lengths kept here (16 bytes a read).  The temporary file goes on every way out.
+  std::vector<SamSortedRun> sam_runs;
+  std::vector<uint8_t> sam_first_text;
+  std::string sam_tmp;
+  uint64_t sam_tmp_bytes = 0;
+  ~SideOutputs() { if (!sam_tmp.empty()) remove(sam_tmp.c_str()); }
   bool vcf() const { return !a.strain_vcf.empty(); }
   bool sam() const { return !a.sam.empty(); }
   bool depth_files() const { return !a.depth.empty() || !a.depth_track.empty(); }
@@ -282,7 +290,7 @@ struct SideOutputs {
       for (const Seq& q : genomes[g].sequence) { sam_names.push_back(sam_rname(q.id)); lengths.push_back(q.size); }
     }
     std::string text, e;
-    if (!sam_header_text(sam_names, lengths, &text, &e)) return fail("--sam", e);
+    if (!sam_header_text(sam_names, lengths, &text, &e, a.sam_sorted)) return fail("--sam", e);
     OutFile f(a.sam, false);
     f.append(text);
     return f.close(&e) || fail("--sam", e);
@@ -293,6 +301,7 @@ struct SideOutputs {
     for (const std::string& n : sam_names) names.push_back(n.c_str());
     simmr_sam_names sn{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), names.data()};
     uint64_t total = 0;
+    if (a.sam_sorted) return sam_sorted_range(eng, sn, reads, t, n_reads, paired);
     if (simmr_sam_plan(eng, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--sam", simmr_last_error(eng));
     DeviceMem mem;
     uint8_t* text = nullptr;
@@ -304,6 +313,63 @@ struct SideOutputs {
     OutFile f(a.sam, true);
     f.append(h.data(), h.size());
     return f.close(&e) || fail("--sam", e);
+  }
+  // the same lines in coordinate order, with the key and the length of each: a sorted run for finish() to merge
+  bool sam_sorted_range(simmr_engine* eng, const simmr_sam_names& sn, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads,
+                        bool paired) {
+    uint64_t total = 0;
+    if (simmr_sam_sort_plan(eng, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--sam-sorted", simmr_last_error(eng));
+    DeviceMem mem;
+    uint8_t* text = nullptr;
+    uint64_t *key = nullptr, *line_off = nullptr;
+    std::vector<uint8_t> h;
+    std::vector<uint64_t> off;
+    SamSortedRun run;
+    if (!(mem.alloc(&text, total) && mem.alloc(&key, n_reads) && mem.alloc(&line_off, n_reads + 1))) return fail("--sam-sorted", "device allocation failed");
+    if (simmr_sam_sort_emit(eng, &reads, &t, text, total, key, line_off) != SIMMR_OK) return fail("--sam-sorted", simmr_last_error(eng));
+    if (!(mem.fetch(&h, text, total) && mem.fetch(&run.key, key, n_reads) && mem.fetch(&off, line_off, n_reads + 1))) return fail("--sam-sorted", "copy back failed");
+    run.len.resize(n_reads);
+    for (uint64_t i = 0; i < n_reads; i++) run.len[i] = off[i + 1] - off[i];
+    if (sam_runs.empty()) {  // a run of one range needs no file
+      sam_first_text = std::move(h);
+      sam_runs.push_back(std::move(run));
+      return true;
+    }
+    std::string e;
+    if (sam_tmp.empty()) {
+      sam_tmp = a.sam + ".sorting.tmp";
+      OutFile f(sam_tmp, false);
+      f.append(sam_first_text.data(), sam_first_text.size());
+      if (!f.close(&e)) return fail("--sam-sorted", e);
+      sam_tmp_bytes = sam_first_text.size();
+      std::vector<uint8_t>().swap(sam_first_text);
+    }
+    run.offset = sam_tmp_bytes;
+    OutFile f(sam_tmp, true);
+    f.append(h.data(), h.size());
+    if (!f.close(&e)) return fail("--sam-sorted", e);
+    sam_tmp_bytes += h.size();
+    sam_runs.push_back(std::move(run));
+    return true;
+  }
+  // the run's lines behind the header: one range's text as it is, several merged by (key, range, place in the range)
+  bool finish_sam_sorted() {
+    std::string e;
+    OutFile out(a.sam, true);
+    if (sam_tmp.empty()) {
+      out.append(sam_first_text.data(), sam_first_text.size());
+      return out.close(&e) || fail("--sam-sorted", e);
+    }
+    FILE* src = fopen(sam_tmp.c_str(), "rb");
+    if (!src) return fail("--sam-sorted", "cannot open " + sam_tmp);
+    const bool merged = sam_merge_sorted_runs(
+        sam_runs, [&](uint64_t at, size_t n, char* p) { return fseeko(src, (off_t)at, SEEK_SET) == 0 && fread(p, 1, n, src) == n; },
+        [&](const char* p, size_t n) { out.append(p, n); return out.ok(); });
+    fclose(src);
+    remove(sam_tmp.c_str());
+    sam_tmp.clear();
+    if (!out.close(&e)) return fail("--sam-sorted", e);
+    return merged || fail("--sam-sorted", "the merge of the sorted ranges failed");
   }
   // the kept sites go up as one list — genome index, contig, pos: ascending, genome by genome — and the table starts at zero
   bool begin_pileup(simmr_engine* eng) {
@@ -337,6 +403,7 @@ struct SideOutputs {
   }
   bool finish(simmr_engine* eng, const std::vector<Genome>& genomes) {
     std::string e;
+    if (sam() && a.sam_sorted && !finish_sam_sorted()) return false;
     if (!a.stats.empty()) {
       auto st = std::make_unique<simmr_run_stats>();
       if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <memory>
 #include <optional>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -148,7 +149,22 @@ std::string sam_rname(const std::string& sequence_id);
 bool sam_rname_legal(const std::string& rname);
 // "@HD\tVN:1.6\tSO:unsorted", one "@SQ\tSN:..\tLN:.." per name in order, "@PG\tID:simmr-hip\tPN:simmr-hip".  false with *err naming
 // the first name that is not legal or that an earlier one has already.
-bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<uint64_t>& lengths, std::string* out, std::string* err);
+// `coordinate`: SO:coordinate, for the file of --sam-sorted.
+bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<uint64_t>& lengths, std::string* out, std::string* err,
+                     bool coordinate = false);
+// `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
+// (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
+// ascend, and its text lies at `offset` of the byte source.
+struct SamSortedRun {
+  std::vector<uint64_t> key;  // of every line, ascending
+  std::vector<uint64_t> len;  // bytes of every line
+  uint64_t offset = 0;        // of the run's first byte in the source
+};
+// The k-way merge: the lines of every run in the order of (key, run number, position in the run) — which makes the output the
+// stable sort of the runs' lines laid end to end.  read(offset, n, dst) fetches n bytes of the source, write(p, n) takes the
+// merged bytes in order; either may answer false, and the merge then ends with false.
+bool sam_merge_sorted_runs(const std::vector<SamSortedRun>& runs, const std::function<bool(uint64_t, size_t, char*)>& read,
+                           const std::function<bool(const char*, size_t)>& write);
 
 // ---------------------------------------------------------------- strain sites (no reference counterpart)
 // Host copy of simmr_strain_out for one genome.
@@ -318,6 +334,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   bool host_normalize = false;  // --host-normalize: normalise FASTA on the host instead of the device
   bool host_fastq = false;  // --host-fastq: frame the FASTQ on the host instead of the device
   std::string truth;  // --truth FILE: per-read mismatch counts and edit lists (simmr_truth_plan / simmr_truth_emit) as a TSV
+  bool sam_sorted = false;  // --sam-sorted: the file of --sam in coordinate order (simmr_sam_sort_plan / simmr_sam_sort_emit, a merge of the ranges)
   std::string sam;    // --sam FILE: the true alignments as SAM (simmr_sam_plan / simmr_sam_emit on every range's columns, the header from the host)
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV

@@ -13,8 +13,11 @@ def rname_of(sequence_id: str) -> str:
     return parts[0] if parts else ""
 
 
-def sam_header(rnames: Sequence[str], lengths: Sequence[int]) -> str:
-    """@HD, one @SQ per contig in names order, @PG.  The records are in read order (unsorted) and carry no read group."""
+def sam_header(rnames: Sequence[str], lengths: Sequence[int], sort_order: str = "unsorted") -> str:
+    """@HD, one @SQ per contig in names order, @PG.  The records carry no read group.  `sort_order`: "unsorted" for the lines of
+    Engine.sam() (read order), "coordinate" for those of Engine.sam_sorted()."""
+    if sort_order not in ("unsorted", "coordinate"):
+        raise ValueError("sort_order is 'unsorted' or 'coordinate'")
     if len(rnames) != len(lengths):
         raise ValueError("one length per RNAME")
     seen = set()
@@ -24,7 +27,7 @@ def sam_header(rnames: Sequence[str], lengths: Sequence[int]) -> str:
         if name in seen:
             raise ValueError(f"two contigs share the RNAME '{name}'")
         seen.add(name)
-    lines = ["@HD\tVN:1.6\tSO:unsorted"]
+    lines = [f"@HD\tVN:1.6\tSO:{sort_order}"]
     lines += [f"@SQ\tSN:{name}\tLN:{int(n)}" for name, n in zip(rnames, lengths)]
     lines.append("@PG\tID:simmr-hip\tPN:simmr-hip")
     return "\n".join(lines) + "\n"
