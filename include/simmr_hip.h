@@ -873,6 +873,73 @@ int simmr_sam_sort_emit(simmr_engine* e, const simmr_reads_out* reads, const sim
  * simmr_sam_sort_emit after it, if any.  Synchronises the stream. */
 int simmr_last_sam_sort_ms(simmr_engine* e, float* ms);
 
+/* ---- the true read-to-read overlaps as PAF: which reads of a run share reference bases, found and formatted on the device ------
+ * Replaces nothing in the reference.  What overlappers (minimap2 -x ava-ont) and the overlap stage of long-read assemblers are
+ * scored against: every pair of reads whose reference intervals share at least min_overlap bases, known here without aligning
+ * anything.  The pass needs the metadata columns of simmr_reads_out only — no read byte is loaded — and follows the
+ * accumulate-then-read shape of simmr_depth_* and simmr_pileup_*: reads of different ranges of a run overlap too.
+ *
+ * Definitions.  The row of a read is the index of (genome slot, contig) among all contigs staged on the engine, slots ascending
+ * and contigs in staged order (the order simmr_depth_contig_first uses).  lo = min(start, end), hi = max(start, end), L = hi - lo,
+ * rev = flags & SIMMR_FLAG_REVCOMP.  The ordinal of a read is its index in the order the reads were added since the reset.  The key
+ * is (row << 40) | lo, with the limits of simmr_sam_sort_key_bits (the pass keeps one row value for itself: fewer than 2^24 contigs).
+ * Place order ascends by key, equal keys by ordinal — among the reads with L >= min_overlap; the reads with L < min_overlap take the
+ * places behind all of those, in ordinal order (they are in no record, so the order of the records is not touched by where they lie).
+ *
+ * The overlap.  Reads a and b overlap when they share a row and ov = min(hi_a, hi_b) - max(lo_a, lo_b) >= min_overlap >= 1.  Every
+ * unordered pair is reported once: the query is the read at the earlier place, the target the read at the later place, and records
+ * are ordered by (place of the query, place of the target).  Mates of one pair are reads like any others and may overlap each other.
+ * A read with L < min_overlap is in no record.
+ *
+ * The record: twelve tab-separated PAF columns and '\n':
+ *   query name, L_q, query start, query end, '+' if rev_q == rev_t else '-', target name, L_t, target start, target end, ov, ov, 255
+ * The name is read_id in decimal; when the reset said `paired` it is followed by /1 or /2 by the parity of the read's index within
+ * its add call.  Start and end are the shared reference interval [s, e) = [max(lo), min(hi)) in the read's own as-written
+ * coordinates: [s - lo, e - lo) for a forward read, [hi - e, hi - s) for a rev read.  Columns 10 and 11 both carry the length of
+ * the shared reference interval: the record is a fact about where the reads came from, not an alignment of their bases (which may
+ * differ by the profile's substitutions).  No profile changes a read's length, so there are no gaps.
+ *
+ * The output is a function of the inputs alone: partners are counted and scanned, record sizes counted and scanned, and every record
+ * written at its offset; no atomic hands out space and launch geometry changes no byte.  No store leaves dst[0, bytes) or a column's
+ * own entries. */
+typedef struct simmr_overlap_cols {   /* DEVICE pointers, caller-owned; any column may be NULL.  One entry per record */
+  uint32_t* a;          /* ordinal of the query  */
+  uint32_t* b;          /* ordinal of the target */
+  uint64_t* ref_start;  /* s: the shared reference interval inside the contig */
+  uint64_t* ref_end;    /* e */
+  uint32_t* row;        /* the row both reads lie on */
+  uint64_t capacity;    /* entries available in every column given */
+} simmr_overlap_cols;
+/* Drops what was accumulated (and any plan) and fixes the rows to what is staged now; `paired`: the reads of every add call are
+ * interleaved mates, named /1 and /2.  Synchronises.  SIMMR_ERANGE: 2^24 contigs or more, or a contig of 2^40 bases or more. */
+int simmr_overlap_reset(simmr_engine* e, int paired);
+/* Appends (key, L, read_id, rev, mate bit) of every read to engine-held columns that grow (20 bytes a read).  Needs start, end,
+ * contig, genome, read_id and flags; seq, qual and seq_off are never read.  Synchronises, and drops the plan in force.
+ * SIMMR_EINVAL: a missing column, an odd n_reads under `paired`; and, found on the device and reported through an error word with
+ * nothing appended for the call: a read whose genome slot or contig is not staged, or whose hi exceeds the contig's staged length.
+ * SIMMR_ERANGE: the reads added since the reset would reach 2^31.  SIMMR_ESTATE: no simmr_overlap_reset yet, or a staging call
+ * since the reset. */
+int simmr_overlap_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads);
+/* Sorts the reads added, counts the partners of every place, sizes every record, scans both, and keeps the result until the next
+ * add or reset.  *n_reads: the places (every read added has one); *n_pairs: the records; *total_bytes: their text.  Any of the
+ * three pointers may be NULL.  SIMMR_EINVAL: min_overlap == 0.  SIMMR_ESTATE: as simmr_overlap_add. */
+int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads, uint64_t* n_pairs, uint64_t* total_bytes);
+/* The longest run of places from first_place (<= n_reads) whose records fit max_bytes: its places, records and bytes.  A place
+ * without records fits anywhere.  SIMMR_ERANGE: the first place alone does not fit; *bytes then holds what it needs and *n_places
+ * is 0.  With this a caller drains an output larger than its buffer in pieces: emit the run, go on at first_place + n_places, until
+ * that is n_reads.  SIMMR_ESTATE: no simmr_overlap_plan for the reads added, or a staging call since the reset. */
+int simmr_overlap_window(simmr_engine* e, uint64_t first_place, uint64_t max_bytes, uint64_t* n_places, uint64_t* n_pairs,
+                         uint64_t* bytes);
+/* Writes the records whose query place is in [first_place, first_place + n_places): the text back to back into dst (DEVICE), the
+ * columns of the same records into `cols`.  Either of dst and cols may be NULL, and so may any column.  Synchronises.
+ * SIMMR_ERANGE, nothing written: dst_capacity is below the run's bytes, or cols->capacity below its records.  SIMMR_EINVAL: the run
+ * leaves the places.  SIMMR_ESTATE: as simmr_overlap_window. */
+int simmr_overlap_emit(simmr_engine* e, uint64_t first_place, uint64_t n_places, const simmr_overlap_cols* cols, uint8_t* dst,
+                       uint64_t dst_capacity);
+/* HIP-event time (ms) of the last simmr_overlap_plan's device work plus that of the simmr_overlap_emit calls since.  Synchronises
+ * the stream. */
+int simmr_last_overlap_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

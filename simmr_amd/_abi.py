@@ -218,6 +218,18 @@ class SamNames(C.Structure):
     ]
 
 
+class OverlapCols(C.Structure):
+    """struct simmr_overlap_cols (device pointers as raw addresses)"""
+    _fields_ = [
+        ("a", C.c_void_p),
+        ("b", C.c_void_p),
+        ("ref_start", C.c_void_p),
+        ("ref_end", C.c_void_p),
+        ("row", C.c_void_p),
+        ("capacity", C.c_uint64),
+    ]
+
+
 # every symbol include/simmr_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SYMBOLS = {
@@ -294,6 +306,12 @@ SYMBOLS = {
     "simmr_sam_sort_plan": (C.c_int, [C.c_void_p, _P(SamNames), _P(ReadsOut), _P(TruthOut), C.c_uint64, C.c_int, _P(C.c_uint64)]),
     "simmr_sam_sort_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "simmr_last_sam_sort_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_overlap_reset": (C.c_int, [C.c_void_p, C.c_int]),
+    "simmr_overlap_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64]),
+    "simmr_overlap_plan": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_overlap_window": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_overlap_emit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _P(OverlapCols), C.c_void_p, C.c_uint64]),
+    "simmr_last_overlap_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

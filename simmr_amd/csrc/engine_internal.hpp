@@ -1,4 +1,4 @@
-// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip) may ask of an engine.  simmr_engine is
+// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip, overlap.hip) may ask of an engine.  simmr_engine is
 // defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,9 +29,17 @@ SIMMR_HIDDEN void eng_genome_planes(const simmr_engine* e, uint32_t slot, uint32
 // What a call that rewrites staged bases owes the engine: what every simmr_stage_* call does (the truth plan is dropped,
 // the staging epoch counts on), and the plan in force is dropped with the direct FASTQ plan made from it.
 SIMMR_HIDDEN void eng_planes_rewritten(simmr_engine* e);
+// The stable radix sort of sam_sort_kernels.hip (defined in sam_sort.hip, whose kernels cannot be included into a second unit):
+// sorts the n pairs (key[0][i], i) over the low key_bits bits of the keys on `st`, in 8-bit digits, least significant first.
+// key[0] / key[1] and idx[0] / idx[1] are the ping and the pong (n entries each), hist holds SAMSORT_PAIRS_DIGITS words per tile of
+// SAMSORT_PAIRS_TILE pairs, digit_total SAMSORT_PAIRS_DIGITS words.  Returns the side that holds the sorted pairs; with key_bits == 0
+// nothing is launched, the answer is 0 and no index buffer is written (the order is the identity).  Only enqueues.
+constexpr uint64_t SAMSORT_PAIRS_TILE = 2048, SAMSORT_PAIRS_DIGITS = 256;
+SIMMR_HIDDEN int samsort_sort_pairs(hipStream_t st, uint64_t* const key[2], uint32_t* const idx[2], uint32_t* hist, uint32_t* digit_total,
+                                    uint64_t n, uint32_t key_bits);
 // One opaque slot per engine and translation unit for that unit's state; simmr_engine_destroy calls `destroy` on a non-null
 // slot (on the engine's device, after the device has been synchronised).
-enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_COUNT = 6 };
+enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_OVERLAP = 6, ENG_EXT_COUNT = 7 };
 SIMMR_HIDDEN void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*));
 // The layout of depth[] that the last simmr_depth_reset recorded (defined in depth.hip): tracked contig k is entries
 // cfirst[k] .. cfirst[k + 1] - 1 (n_contigs + 1 entries, on the host and on the device) and contig c_contig[k] of genome slot

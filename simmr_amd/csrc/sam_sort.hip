@@ -54,6 +54,28 @@ uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0
 
 }  // namespace
 
+// engine_internal.hpp: the sort itself, for this unit's plan and for overlap.hip's
+namespace simmr {
+static_assert(SAMSORT_PAIRS_TILE == SAMSORT_TILE && SAMSORT_PAIRS_DIGITS == SAMSORT_DIGITS, "engine_internal.hpp states the tile and the digits");
+int samsort_sort_pairs(hipStream_t st, uint64_t* const key[2], uint32_t* const idx[2], uint32_t* hist, uint32_t* digit_total, uint64_t n,
+                       uint32_t key_bits) {
+  const uint32_t n_passes = (key_bits + SAMSORT_DIGIT_BITS - 1u) / SAMSORT_DIGIT_BITS;
+  const uint32_t n_tiles = (uint32_t)((n + SAMSORT_TILE - 1) / SAMSORT_TILE);
+  int cur = 0;
+  if (n == 0) return cur;
+  // least significant digit first, over the bits the caller gives the key: a stable pass per digit
+  for (uint32_t p = 0; p < n_passes; p++) {
+    const uint32_t shift = p * SAMSORT_DIGIT_BITS;
+    hipLaunchKernelGGL(k_samsort_hist, dim3(n_tiles), dim3(256), 0, st, (const uint64_t*)key[cur], n, shift, hist, n_tiles);
+    hipLaunchKernelGGL(k_samsort_digit_scan, dim3(SAMSORT_DIGITS), dim3(256), 0, st, hist, n_tiles, digit_total);
+    hipLaunchKernelGGL(k_samsort_scatter, dim3(n_tiles), dim3(256), 0, st, (const uint64_t*)key[cur], p ? (const uint32_t*)idx[cur] : (const uint32_t*)nullptr,
+                       key[cur ^ 1], idx[cur ^ 1], n, shift, (const uint32_t*)hist, (const uint32_t*)digit_total, n_tiles);
+    cur ^= 1;
+  }
+  return cur;
+}
+}  // namespace simmr
+
 extern "C" {
 
 int simmr_sam_sort_key_bits(uint64_t n_rows, uint64_t longest_contig, uint32_t* pos_bits, uint32_t* row_bits) {
@@ -76,7 +98,7 @@ int simmr_sam_sort_plan(simmr_engine* e, const simmr_sam_names* names, const sim
   if (simmr_sam_sort_key_bits(s->nt.n_rows, s->nt.longest, &pos_bits, &row_bits) != SIMMR_OK)
     return eng_fail(e, SIMMR_ERANGE, "simmr_sam_sort_plan: %llu named contigs, the longest of %llu bases: the key takes at most 2^24 contigs of "
                                      "fewer than 2^40 bases", (unsigned long long)s->nt.n_rows, (unsigned long long)s->nt.longest);
-  const uint32_t key_bits = pos_bits + row_bits, n_passes = (key_bits + SAMSORT_DIGIT_BITS - 1u) / SAMSORT_DIGIT_BITS;
+  const uint32_t key_bits = pos_bits + row_bits;
   for (hipEvent_t& ev : s->ev)
     if (!ev) SAM_TRY(e, hipEventCreate(&ev));
   const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1) / SAM_CHUNK, n_tiles = (n_reads + SAMSORT_TILE - 1) / SAMSORT_TILE;
@@ -97,20 +119,10 @@ int simmr_sam_sort_plan(simmr_engine* e, const simmr_sam_names* names, const sim
   if (n_reads > 0) {
     hipLaunchKernelGGL(k_samsort_size, dim3(grid), dim3(256), 0, st, sam_reads(reads), sam_edits(truth), s->nt.names(),
                        s->nt.c_bases.as<const uint64_t>(), n_reads, paired ? 1u : 0u, pos_bits, s->len.as<uint32_t>(), s->key[0].as<uint64_t>(), s->err_p());
-    // least significant digit first, over the bits the names give the key: a stable pass per digit
-    for (uint32_t p = 0; p < n_passes; p++) {
-      const uint32_t shift = p * SAMSORT_DIGIT_BITS;
-      hipLaunchKernelGGL(k_samsort_hist, dim3((uint32_t)n_tiles), dim3(256), 0, st, s->key[cur].as<const uint64_t>(), n_reads, shift,
-                         s->hist.as<uint32_t>(), (uint32_t)n_tiles);
-      hipLaunchKernelGGL(k_samsort_digit_scan, dim3(SAMSORT_DIGITS), dim3(256), 0, st, s->hist.as<uint32_t>(), (uint32_t)n_tiles,
-                         s->digit_total.as<uint32_t>());
-      hipLaunchKernelGGL(k_samsort_scatter, dim3((uint32_t)n_tiles), dim3(256), 0, st, s->key[cur].as<const uint64_t>(),
-                         have_idx ? s->idx[cur].as<const uint32_t>() : (const uint32_t*)nullptr, s->key[cur ^ 1].as<uint64_t>(),
-                         s->idx[cur ^ 1].as<uint32_t>(), n_reads, shift, s->hist.as<const uint32_t>(), s->digit_total.as<const uint32_t>(),
-                         (uint32_t)n_tiles);
-      cur ^= 1;
-      have_idx = true;
-    }
+    uint64_t* const keys[2] = {s->key[0].as<uint64_t>(), s->key[1].as<uint64_t>()};
+    uint32_t* const idxs[2] = {s->idx[0].as<uint32_t>(), s->idx[1].as<uint32_t>()};
+    cur = samsort_sort_pairs(st, keys, idxs, s->hist.as<uint32_t>(), s->digit_total.as<uint32_t>(), n_reads, key_bits);
+    have_idx = key_bits > 0u;
     s->perm = have_idx ? s->idx[cur].as<const uint32_t>() : nullptr;
     s->ckey = s->key[cur ^ 1].as<const uint64_t>();
     uint32_t* slen = s->idx[cur ^ 1].as<uint32_t>();

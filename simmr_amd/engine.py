@@ -454,6 +454,68 @@ class Engine:
         self._check(self.lib.simmr_last_sam_sort_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- the true read-to-read overlaps as PAF ------------------------------------------
+    OVERLAP_COLUMNS = (("a", np.uint32), ("b", np.uint32), ("ref_start", np.uint64), ("ref_end", np.uint64), ("row", np.uint32))
+
+    def overlap_reset(self, paired: bool):
+        """Drops the reads accumulated for the overlap pass and fixes the rows to the genomes staged now (simmr_overlap_reset);
+        `paired`: every add carries interleaved mates, named <read_id>/1 and /2."""
+        self._check(self.lib.simmr_overlap_reset(self._h, 1 if paired else 0))
+
+    def overlap_add(self, reads: Reads):
+        """Appends the metadata of `reads` (simmr_overlap_add): start, end, contig, genome, read_id and flags; no base is read."""
+        pod = reads.pod()
+        self._check(self.lib.simmr_overlap_add(self._h, C.byref(pod), reads.n_reads))
+
+    def overlap_plan(self, min_overlap: int):
+        """(n_reads, n_pairs, total_bytes) of the reads added since the reset (simmr_overlap_plan)."""
+        n, pairs, total = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.simmr_overlap_plan(self._h, int(min_overlap), C.byref(n), C.byref(pairs), C.byref(total)))
+        return int(n.value), int(pairs.value), int(total.value)
+
+    def overlap_window(self, first_place: int, max_bytes: int):
+        """(n_places, n_pairs, bytes) of the longest run of places from `first_place` whose records fit `max_bytes`
+        (simmr_overlap_window); SimmrError with code ERANGE if the first place alone does not fit."""
+        n, pairs, b = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.simmr_overlap_window(self._h, int(first_place), int(max_bytes), C.byref(n), C.byref(pairs), C.byref(b)))
+        return int(n.value), int(pairs.value), int(b.value)
+
+    def overlaps(self, min_overlap: int, text: bool = True, columns: bool = False, max_bytes: Optional[int] = None):
+        """The true overlaps of the reads added since overlap_reset (simmr_overlap_plan + simmr_overlap_emit): every pair of reads
+        that share at least `min_overlap` reference bases, ordered by (place of the query, place of the target).  text: the PAF
+        records as a CUDA uint8 tensor; columns: a dict of CUDA tensors a, b (ordinals, int32), ref_start, ref_end (int64) and
+        row (int32), one entry per record.  Returns the text, the columns, or (text, columns).  With `max_bytes` the output is
+        drained by windows of at most that many bytes of text (simmr_overlap_window) and concatenated."""
+        torch = _torch()
+        n, pairs, total = self.overlap_plan(min_overlap)
+        dt = {np.uint32: torch.int32, np.uint64: torch.int64}
+        out = torch.empty(max(total, 1), dtype=torch.uint8, device=self.device) if text else None
+        cols = {name: torch.empty(max(pairs, 1), dtype=dt[t], device=self.device) for name, t in self.OVERLAP_COLUMNS} if columns else None
+        place, rec, at = 0, 0, 0
+        while True:
+            if max_bytes is None:
+                n_places, n_rec, n_bytes = n, pairs, total
+            else:
+                n_places, n_rec, n_bytes = self.overlap_window(place, max_bytes)
+            pod = None
+            if columns:
+                pod = _abi.OverlapCols(*[cols[name].data_ptr() + rec * np.dtype(t).itemsize for name, t in self.OVERLAP_COLUMNS], pairs - rec)
+            self._check(self.lib.simmr_overlap_emit(self._h, place, n_places, C.byref(pod) if columns else None,
+                                                    C.c_void_p(out.data_ptr() + at) if text else None, total - at))
+            place, rec, at = place + n_places, rec + n_rec, at + n_bytes
+            if place >= n:
+                break
+        if columns:
+            cols = {name: v[:pairs] for name, v in cols.items()}
+        if text and columns:
+            return out[:total], cols
+        return out[:total] if text else cols
+
+    def last_overlap_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_overlap_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- strain divergence ------------------------------------------------------------
     def strain_plan(self, genome_idx: int, identity: float, seed: int) -> int:
         """Counts the sites that `identity` and `seed` give genome slot `genome_idx` (simmr_strain_plan); returns their total."""

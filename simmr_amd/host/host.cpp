@@ -708,6 +708,11 @@ std::string usage() {
          "            --sam-sorted    the file of --sam in coordinate order, under @HD SO:coordinate: the lines ascend by (@SQ index, POS),\n"
          "                            ties in read order, across every range of the run (each range is sorted on the device; several\n"
          "                            ranges are merged through a temporary file beside FILE); needs --sam; not with --devices\n"
+         "            --overlaps <FILE>  the true read-to-read overlaps of the run as PAF: one record per pair of reads that share at least\n"
+         "                            --min-overlap reference bases of one sequence, across every range of the run, found and formatted on\n"
+         "                            the device; names as --sam's QNAME (the read id, /1 or /2 for pairs); columns 10 and 11 carry the\n"
+         "                            length of the shared reference interval; not with --devices\n"
+         "            --min-overlap <N>  shared reference bases from which two reads overlap [default: 1]\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -809,6 +814,8 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--truth") { if (!file(&a->truth)) return false; }
     else if (arg == "--sam") { if (!file(&a->sam)) return false; }
     else if (arg == "--sam-sorted") a->sam_sorted = true;
+    else if (arg == "--overlaps") { if (!file(&a->overlaps)) return false; }
+    else if (arg == "--min-overlap") { if (!uint(1, UINT64_MAX, " (at least 1)")) return false; a->min_overlap = u; }
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }

@@ -234,7 +234,30 @@ static bool write_vcf_file(simmr_engine* eng, const CliArgs& args, const std::ve
   return write_strain_vcf(genomes, lens, sites, site_genome, counts, args.strain_vcf, err);
 }
 
-// The side outputs of a run: --truth, --sam, --stats, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
+// A buffer that grows to the largest size asked of it, with a sixteenth to spare so that sizes creeping up do not allocate
+// every time: device memory, or pinned host memory.
+struct GrowBuf {
+  bool pinned = false;
+  void* p = nullptr;
+  uint64_t cap = 0;
+  ~GrowBuf() { release(); }
+  void release() { if (p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
+  // room for `bytes`, or nullptr if there is none; what the buffer held is gone when it grows
+  uint8_t* room(uint64_t bytes) {
+    if (cap < bytes) {
+      release();
+      const uint64_t want = bytes + bytes / 16 + 256;
+      if ((pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return nullptr; }
+      cap = want;
+    }
+    return (uint8_t*)p;
+  }
+};
+
+// the text buffer of the drains: what one copy to the host moves, and what a window of --overlaps holds
+static constexpr size_t TEXT_CHUNK = 256u << 20;
+
+// The side outputs of a run: --truth, --sam, --overlaps, --stats, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
 // takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
 struct SideOutputs {
   explicit SideOutputs(const CliArgs& args) : a(args) {}
@@ -254,26 +277,29 @@ struct SideOutputs {
   std::vector<uint8_t> sam_first_text;
   std::string sam_tmp;
   uint64_t sam_tmp_bytes = 0;
+  bool run_paired = false;  // --overlaps: the run's reads are interleaved mates (set before begin)
   ~SideOutputs() { if (!sam_tmp.empty()) remove(sam_tmp.c_str()); }
+  bool overlaps() const { return !a.overlaps.empty(); }
   bool vcf() const { return !a.strain_vcf.empty(); }
   bool sam() const { return !a.sam.empty(); }
   bool depth_files() const { return !a.depth.empty() || !a.depth_track.empty(); }
   bool gold() const { return !a.gold_assembly.empty() || !a.gold_regions.empty(); }
   bool depth() const { return depth_files() || gold(); }  // (the gold-standard assembly is read off the run's depth[])
-  bool wanted() const { return !a.truth.empty() || sam() || !a.stats.empty() || depth() || vcf(); }
+  bool wanted() const { return !a.truth.empty() || sam() || overlaps() || !a.stats.empty() || depth() || vcf(); }
   bool fail(const char* flag, const std::string& what) { err = std::string(flag) + ": " + what; return false; }
   // true, with the message, if one of them is asked for together with --devices
   bool refuse_devices() {
-    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : sam() ? "--sam" : nullptr;
+    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : sam() ? "--sam" : overlaps() ? "--overlaps" : nullptr;
     if (flag && !a.devices.empty()) err = std::string(flag) + " does not combine with --devices: use --device";
     return flag && !a.devices.empty();
   }
   // the old files go, the truth file gets its header line (every range appends its reads), the tables start at zero
   // (the genomes are staged: depth[] covers all of them)
   bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
-    for (const std::string* f : {&a.truth, &a.sam, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
+    for (const std::string* f : {&a.truth, &a.sam, &a.overlaps, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
       if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
     std::string e;
+    if (overlaps() && simmr_overlap_reset(eng, run_paired ? 1 : 0) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
     if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
     if (sam() && !begin_sam(genomes)) return false;
     if (!a.stats.empty() && simmr_stats_reset(eng) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
@@ -389,6 +415,7 @@ struct SideOutputs {
     if (!a.stats.empty() && simmr_stats_add(eng, &reads, n_reads, paired ? 2u : 1u) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
     if (depth() && simmr_depth_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
     if (vcf() && simmr_pileup_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--strain-vcf", simmr_last_error(eng));
+    if (overlaps() && simmr_overlap_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
     std::string e;
     qual_offset = reads.qual_offset;
     if (a.truth.empty() && !sam()) return true;
@@ -401,8 +428,34 @@ struct SideOutputs {
     std::string e;
     return a.truth.empty() || write_truth_tsv(genomes, h, truth, qual_offset, a.truth, false, &e) || fail("--truth", e);
   }
+  // the overlaps of every range added: one plan, then window by window through the file — a window is what the text buffer of
+  // the FASTQ drain holds (a place whose records alone are more than that gets a buffer of its own size)
+  bool finish_overlaps(simmr_engine* eng) {
+    uint64_t n = 0, pairs = 0, total = 0;
+    if (simmr_overlap_plan(eng, a.min_overlap, &n, &pairs, &total) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
+    std::string e;
+    OutFile f(a.overlaps, false);
+    GrowBuf text;
+    std::vector<uint8_t> h;
+    uint64_t room = std::min<uint64_t>(total, TEXT_CHUNK);
+    for (uint64_t place = 0; place < n;) {
+      uint64_t n_places = 0, n_rec = 0, bytes = 0;
+      const int rc = simmr_overlap_window(eng, place, room, &n_places, &n_rec, &bytes);
+      if (rc == SIMMR_ERANGE && bytes > room) { room = bytes; continue; }
+      if (rc != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
+      uint8_t* dst = text.room(std::max<uint64_t>(bytes, 1));
+      if (!dst) return fail("--overlaps", "device allocation failed");
+      if (simmr_overlap_emit(eng, place, n_places, nullptr, dst, bytes) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
+      if (!DeviceMem::fetch(&h, (const uint8_t*)dst, bytes)) return fail("--overlaps", "copy back failed");
+      f.append(h.data(), h.size());
+      if (!f.ok()) break;
+      place += n_places;
+    }
+    return f.close(&e) || fail("--overlaps", e);
+  }
   bool finish(simmr_engine* eng, const std::vector<Genome>& genomes) {
     std::string e;
+    if (overlaps() && !finish_overlaps(eng)) return false;
     if (sam() && a.sam_sorted && !finish_sam_sorted()) return false;
     if (!a.stats.empty()) {
       auto st = std::make_unique<simmr_run_stats>();
@@ -412,26 +465,6 @@ struct SideOutputs {
     if (depth_files() && !write_depth_files(eng, a, genomes, depth_positions, depth_contigs, &e)) return fail("--depth", e);
     if (gold() && !write_gold_files(eng, a, genomes, depth_positions, &e)) return fail("--gold-assembly", e);
     return !vcf() || write_vcf_file(eng, a, genomes, sites, site_genome, depth_positions, &e) || fail("--strain-vcf", e);
-  }
-};
-
-// A buffer that grows to the largest size asked of it, with a sixteenth to spare so that sizes creeping up do not allocate
-// every time: device memory, or pinned host memory.
-struct GrowBuf {
-  bool pinned = false;
-  void* p = nullptr;
-  uint64_t cap = 0;
-  ~GrowBuf() { release(); }
-  void release() { if (p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
-  // room for `bytes`, or nullptr if there is none; what the buffer held is gone when it grows
-  uint8_t* room(uint64_t bytes) {
-    if (cap < bytes) {
-      release();
-      const uint64_t want = bytes + bytes / 16 + 256;
-      if ((pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return nullptr; }
-      cap = want;
-    }
-    return (uint8_t*)p;
   }
 };
 
@@ -449,7 +482,7 @@ struct TextDrain {
   hipStream_t cs = nullptr;
   hipEvent_t emitted = nullptr;
   std::optional<OutFile> f;
-  static constexpr size_t CHUNK = 256u << 20;
+  static constexpr size_t CHUNK = TEXT_CHUNK;
   int pending = -1;  // buffer whose text still has to go to the file
   bool open(const std::string& output, std::string* err) {
     f.emplace(output, true);
@@ -891,6 +924,7 @@ static int run_main(int argc, char** argv) {
 
   // abundances (simulate.rs:121-132 / :334-343)
   const bool is_long = eprofile->is_long_read();
+  side.run_paired = !is_long;
   Abundances ab = aprofile->determine_abundances(args.num_reads, genomes.size());
   if (aprofile->is_size_aware()) ab = aprofile->adjust_for_size(genomes, ab, is_long ? 20000 : args.read_length, !is_long);
 
