@@ -940,6 +940,121 @@ int simmr_overlap_emit(simmr_engine* e, uint64_t first_place, uint64_t n_places,
  * the stream. */
 int simmr_last_overlap_ms(simmr_engine* e, float* ms);
 
+/* ---- fitting an error model from a run: what `simmrd` makes from alignments, counted on the device ----------------
+ * The reference's second program builds a shared::encoding::ErrorModelParams from SAM records: k-mer to alternate-k-mer
+ * probabilities, a quality density per read offset, read-length and insert-size densities.  Here the same products come
+ * from the columns of a run in HBM: the bases as written, the expected bases from the staged planes, the qualities.
+ *
+ * Definitions.  The EXPECTED byte, the WRITTEN byte, the quality q, L, the layouts (compact and SIMMR_SLOT16), the set
+ * r % n_sets and the bounds check are exactly simmr_stats_add's (above).  Everything is in the READ'S OWN orientation,
+ * reverse mates complemented: the orientation in which the custom profiles consume a model.  (The reference reverse-
+ * complements SEQ and then applies the forward CIGAR / MD to it, and skips a second record with a name already seen:
+ * accidents of its SAM route, not reproduced.)
+ *
+ * K-mer pairs (simmrd/src/alignment.rs, encoded_kmerize_alignment, for an alignment without gaps).  For every read and
+ * every ndx with ndx + k < L (strictly: the last window is left out, as in the reference) the reference k-mer is
+ * expected[ndx .. ndx + k).  A byte of it outside A C G T (a staged N or '-') skips the window.  The query k-mer is
+ * written[ndx .. ndx + k) with every N and '-' removed and N appended back to length k; nothing left skips the window,
+ * and so does a written byte outside A C G T N '-' (the reference's encoder refuses it).  Both are 3-bit coded, base i at
+ * bits 3 i, A C G T N = 0 1 2 3 4.  The window adds 1 to count[ref][ref] and 1 to count[ref][query]: an unchanged window
+ * adds 2 to count[ref][ref].  k is 3 .. 10, counts are 64-bit.  Per reference k-mer: total = the sum over its alternates,
+ * probability = (float)count / (float)total in f32 (the 64-bit values converted; the reference's u32 counts end at 2^32,
+ * which is documented, not emulated), alternates by count descending, ties by code ascending, cut to the first
+ * max_alt_kmers WITHOUT renormalising, as in the reference.  Reference k-mers ascend by code (the reference's order is its
+ * HashMap's).
+ *
+ * Qualities.  hist[pos][q] for every offset pos < L of every read, q = 0 .. SIMMR_FIT_MAX_Q (a larger q sets the sticky
+ * error); positions run to the longest read seen (no 512-cycle limit).  Per position, over its n observations: population
+ * mean and standard deviation (shared/src/util.rs), bandwidth 1.06 sd n^(-1/5), and density[s] for s = 0 .. 70 by
+ * probability.rs's `gaussian`: SIMMR_FIT_DENSITIES = 71 values beside num_bins = 70 and 70 bin_ranges (i, i), as the
+ * reference writes them.  All in f64, summed over histogram entries, not observations.
+ *
+ * Read lengths.  A histogram of L over all reads; mean, standard deviation, is_long = mean > 400; the bin width by
+ * freedman_diaconis_rule with the quartiles read from the cumulative histogram at indices floor(n * 0.25) and
+ * floor(n * 0.75), (2 iqr / n^(1/3)) as usize, 10 if that is <= 1; bins, clamped ends and mid-point densities as
+ * create_read_length_bins.
+ * Insert sizes (n_sets == 2 only).  For each mate |TLEN| as the SAM pass defines TLEN for the pair (the span of the two
+ * mates), pushed once per mate as the reference pushes it once per record; values above SIMMR_FIT_MAX_INSERT are left
+ * out.  Mean, standard deviation and bins as create_insert_size_bins (ends not clamped; the quartiles are those of the
+ * sorted values, where the reference indexes its unsorted list).  No insert bins when is_long or when nothing was kept
+ * (the mean and the deviation are then 0, where the reference writes NaN).
+ *
+ * One deliberate departure.  A bandwidth of 0 (every observation equal: one observation, perfect-short's constant Phred,
+ * a constant read length) makes the reference divide by zero and write NaN, which its own loader then rejects.  Here
+ * the density is the point mass: 1.0 at that value and 0.0 elsewhere, a quality above 70 going to entry 70; a length or
+ * insert column with min == max gets ONE bin (min, min) of density 1.0 (the reference gives zero bins).
+ *
+ * Every table is an integer sum over reads: identical for any launch geometry, layout or split into adds.  The finish
+ * runs on the device too (the pairs sorted, totalled, cut and divided; the densities evaluated); the host takes only the
+ * scalars and the bins of the length and insert histograms. */
+#define SIMMR_FIT_MAX_Q 93u          /* largest quality taken */
+#define SIMMR_FIT_QUALS 94u          /* entries of a position's quality histogram */
+#define SIMMR_FIT_DENSITIES 71u      /* entries of a position's binned_density */
+#define SIMMR_FIT_MAX_L 65535u       /* longest read taken; the length histogram has SIMMR_FIT_MAX_L + 1 entries */
+#define SIMMR_FIT_MAX_INSERT 5000u   /* largest insert kept; the insert histogram has SIMMR_FIT_MAX_INSERT + 1 entries */
+
+typedef struct simmr_fit_info {      /* HOST memory: the sizes and scalars of the model simmr_fit_plan made */
+  uint64_t n_ref_kmers;              /* reference k-mers */
+  uint64_t n_pairs;                  /* (reference, alternate) pairs kept after the cut */
+  uint64_t n_positions;              /* the longest read seen */
+  uint64_t n_length_bins;
+  uint64_t n_insert_bins;            /* 0: insert_size_bins is absent */
+  uint64_t n_reads;                  /* observations of the length histogram */
+  uint64_t n_inserts;                /* observations of the insert histogram */
+  uint64_t length_bin_width;
+  uint64_t insert_bin_width;
+  double read_length_mean, read_length_std;
+  double insert_size_mean, insert_size_std;
+  uint32_t is_long;
+  uint32_t k;
+  uint32_t max_alt_kmers;
+  uint32_t pad;
+} simmr_fit_info;
+
+typedef struct simmr_fit_out {       /* DEVICE pointers, caller-owned; any column may be NULL */
+  uint32_t* kmer_ref;                /* [n_ref_kmers] 3-bit codes, ascending */
+  uint64_t* kmer_first;              /* [n_ref_kmers + 1]: the pairs of reference k-mer i are kmer_first[i] .. kmer_first[i + 1] - 1 */
+  uint32_t* pair_alt;                /* [n_pairs] */
+  uint64_t* pair_count;              /* [n_pairs] */
+  float* pair_prob;                  /* [n_pairs] */
+  uint64_t* qual_hist;               /* [n_positions][SIMMR_FIT_QUALS] */
+  double* qual_density;              /* [n_positions][SIMMR_FIT_DENSITIES] */
+  uint64_t* length_hist;             /* [SIMMR_FIT_MAX_L + 1] */
+  uint64_t* insert_hist;             /* [SIMMR_FIT_MAX_INSERT + 1] */
+  double* length_density;            /* [n_length_bins] */
+  uint32_t* length_lo;               /* [n_length_bins] bin_ranges .0 */
+  uint32_t* length_hi;               /* [n_length_bins] bin_ranges .1 */
+  double* insert_density;            /* [n_insert_bins] */
+  uint32_t* insert_lo;
+  uint32_t* insert_hi;
+  uint64_t ref_capacity;             /* entries available in kmer_ref (kmer_first has one more) */
+  uint64_t pair_capacity;            /* ... in the three pair columns */
+  uint64_t position_capacity;        /* positions available in qual_hist and qual_density */
+  uint64_t length_bin_capacity;
+  uint64_t insert_bin_capacity;
+} simmr_fit_out;
+
+/* Allocates the tables on first use and zeroes them and the sticky error.  pair_capacity: how many distinct CHANGED
+ * (reference, alternate) pairs the run may show; the open-addressing table gets the next power of two at or above twice
+ * that.  SIMMR_EINVAL: k outside 3 .. 10, max_alt_kmers == 0, pair_capacity == 0 or above 2^26. */
+int simmr_fit_reset(simmr_engine* e, uint32_t k, uint32_t max_alt_kmers, uint64_t pair_capacity);
+/* Adds the reads of `reads`.  Only enqueues on the engine's stream; can be called once per range.  Needs seq, qual,
+ * seq_off, start, end, contig, genome and flags.  Staging a genome afterwards does not discard the tables (the rule of
+ * simmr_stats_add), but the genomes the columns name must be staged when the add runs.
+ * SIMMR_EINVAL, at once: n_sets other than 1 or 2, an odd n_reads with n_sets == 2, a missing column.  SIMMR_ESTATE: no
+ * simmr_fit_reset yet.  Sticky, reported by simmr_fit_plan: a read that fails simmr_stats_add's bounds check (unstaged
+ * genome or contig, a window out of bounds, L > SIMMR_FIT_MAX_L), q > SIMMR_FIT_MAX_Q, a full pair table. */
+int simmr_fit_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint32_t n_sets);
+/* Finishes the model from what was added since the reset, keeps it for simmr_fit_emit, synchronises and fills *info.
+ * Adds may follow; the next plan takes them in.  SIMMR_EINVAL (nothing made): the sticky error of a bad read or quality.
+ * SIMMR_ERANGE: the pair table was full.  SIMMR_ESTATE: no simmr_fit_reset yet. */
+int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info);
+/* Copies the planned model into the columns given.  Synchronises.  SIMMR_ERANGE (nothing written): a capacity below its
+ * size in simmr_fit_info.  SIMMR_ESTATE: no simmr_fit_plan since the last reset or add. */
+int simmr_fit_emit(simmr_engine* e, const simmr_fit_out* out);
+/* HIP-event time (ms) of the last simmr_fit_add's device work.  Synchronises the stream. */
+int simmr_last_fit_ms(simmr_engine* e, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

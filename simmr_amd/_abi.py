@@ -208,6 +208,26 @@ class PileupSites(C.Structure):
     ]
 
 
+class FitInfo(C.Structure):
+    """struct simmr_fit_info (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_ref_kmers", "n_pairs", "n_positions", "n_length_bins", "n_insert_bins", "n_reads",
+                                         "n_inserts", "length_bin_width", "insert_bin_width")] + \
+               [(n, C.c_double) for n in ("read_length_mean", "read_length_std", "insert_size_mean", "insert_size_std")] + \
+               [(n, C.c_uint32) for n in ("is_long", "k", "max_alt_kmers", "pad")]
+
+
+FIT_COLUMNS = ("kmer_ref", "kmer_first", "pair_alt", "pair_count", "pair_prob", "qual_hist", "qual_density", "length_hist",
+               "insert_hist", "length_density", "length_lo", "length_hi", "insert_density", "insert_lo", "insert_hi")
+FIT_QUALS, FIT_DENSITIES, FIT_MAX_L, FIT_MAX_INSERT = 94, 71, 65535, 5000
+
+
+class FitOut(C.Structure):
+    """struct simmr_fit_out (device pointers as raw addresses)"""
+    _fields_ = [(n, C.c_void_p) for n in FIT_COLUMNS] + \
+               [(n, C.c_uint64) for n in ("ref_capacity", "pair_capacity", "position_capacity", "length_bin_capacity",
+                                          "insert_bin_capacity")]
+
+
 class SamNames(C.Structure):
     """struct simmr_sam_names (host memory)"""
     _fields_ = [
@@ -312,6 +332,11 @@ SYMBOLS = {
     "simmr_overlap_window": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
     "simmr_overlap_emit": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, _P(OverlapCols), C.c_void_p, C.c_uint64]),
     "simmr_last_overlap_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_fit_reset": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64]),
+    "simmr_fit_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64, C.c_uint32]),
+    "simmr_fit_plan": (C.c_int, [C.c_void_p, _P(FitInfo)]),
+    "simmr_fit_emit": (C.c_int, [C.c_void_p, _P(FitOut)]),
+    "simmr_last_fit_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

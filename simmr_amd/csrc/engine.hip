@@ -1061,6 +1061,10 @@ uint32_t eng_contig_count(const simmr_engine* e, uint32_t slot) {
 }
 uint64_t eng_contig_len(const simmr_engine* e, uint32_t slot, uint32_t contig) { return e->genomes[slot].contigs[contig].len; }
 uint64_t eng_staging_epoch(const simmr_engine* e) { return e->staging_epoch; }
+const GenomeDev* eng_genome_table(const simmr_engine* e, uint32_t* n_slots) {
+  *n_slots = (uint32_t)e->genomes.size();
+  return e->d_genomes.as<GenomeDev>();
+}
 int eng_fail(simmr_engine* e, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;

@@ -1,4 +1,4 @@
-// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip, overlap.hip) may ask of an engine.  simmr_engine is
+// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip) may ask of an engine.  simmr_engine is
 // defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -26,6 +26,9 @@ SIMMR_HIDDEN int eng_fail(simmr_engine* e, int code, const char* fmt, ...) __att
 // from their word 0 (*mask = nullptr for a genome of pure ACGT), the device copy of the contig table, the plane's bases.
 SIMMR_HIDDEN void eng_genome_planes(const simmr_engine* e, uint32_t slot, uint32_t** packed, const uint32_t** mask,
                                     const ContigDev** contigs_device, uint64_t* plane_bases);
+// The device table of the genome slots (GenomeDev[*n_slots], what the read walker of read_walk.hpp takes); rewritten by every
+// simmr_stage_* call on the engine's stream, so a kernel enqueued there sees the table of its own moment.
+SIMMR_HIDDEN const GenomeDev* eng_genome_table(const simmr_engine* e, uint32_t* n_slots);
 // What a call that rewrites staged bases owes the engine: what every simmr_stage_* call does (the truth plan is dropped,
 // the staging epoch counts on), and the plan in force is dropped with the direct FASTQ plan made from it.
 SIMMR_HIDDEN void eng_planes_rewritten(simmr_engine* e);
@@ -39,7 +42,7 @@ SIMMR_HIDDEN int samsort_sort_pairs(hipStream_t st, uint64_t* const key[2], uint
                                     uint64_t n, uint32_t key_bits);
 // One opaque slot per engine and translation unit for that unit's state; simmr_engine_destroy calls `destroy` on a non-null
 // slot (on the engine's device, after the device has been synchronised).
-enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_OVERLAP = 6, ENG_EXT_COUNT = 7 };
+enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_OVERLAP = 6, ENG_EXT_FIT = 7, ENG_EXT_COUNT = 8 };
 SIMMR_HIDDEN void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*));
 // The layout of depth[] that the last simmr_depth_reset recorded (defined in depth.hip): tracked contig k is entries
 // cfirst[k] .. cfirst[k + 1] - 1 (n_contigs + 1 entries, on the host and on the device) and contig c_contig[k] of genome slot

@@ -11,6 +11,7 @@
 
 #include "device_types.hpp"
 #include "rng_device.hpp"
+#include "read_walk.hpp"
 
 namespace simmr {
 
@@ -974,13 +975,8 @@ k_write_meta(uint32_t paired, uint64_t n_units, uint64_t first_unit, uint32_t re
 // ASCII with v_perm_b32 — so all stores are global_store_dwordx4.
 // ===========================================================================
 
-// 16 bases (32 bits of codes) starting at absolute base position p (may be
-// slightly negative: the plane has front padding).
-// The planes live in device memory: say so (a pointer that came out of a struct or out of LDS is a
-// generic pointer, and a flat load is slower than a global one).
-typedef uint64_t __attribute__((aligned(1))) u64_unaligned;
-typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
-typedef v4u32 __attribute__((aligned(1))) v4u32_unaligned;
+// The plane routines (fetch_codes16 .. expand4, gather_piece) live in read_walk.hpp (included above), shared with the units that
+// walk reads.
 // A store into the output streams and columns.  They are written once and read by nobody on the device, so where a wave
 // writes WHOLE lines the stores are nontemporal (`nt`): the lines are not kept in L2 / MALL behind the write.  Same-box
 // A/B (profiles/r3/ab_nt_stores_*): k_emit_perfect_pe 6.3 against 7.4 ms per 100 M reads, k_emit_philox in the slot
@@ -988,79 +984,6 @@ typedef v4u32 __attribute__((aligned(1))) v4u32_unaligned;
 // written bytewise, 15.3 against 12.7: there the stores stay plain.
 // (a macro, not a function template: the pointee types carry `aligned(1)`, which template deduction would drop)
 #define stream_store(p, v) __builtin_nontemporal_store((v), (p))
-typedef const __attribute__((address_space(1))) u64_unaligned* global_u64_unaligned_ptr;
-SIMMR_DEV uint64_t load_plane_u64(const uint32_t* __restrict__ plane, int64_t word) {
-  return *(global_u64_unaligned_ptr)(plane + word);  // words `word` and `word + 1`, 4-byte aligned
-}
-SIMMR_DEV uint32_t fetch_codes16(const uint32_t* __restrict__ packed, int64_t p) {
-  return (uint32_t)(load_plane_u64(packed, p >> 4) >> ((uint32_t)(p & 15) * 2u));
-}
-SIMMR_DEV uint32_t fetch_mask16(const uint32_t* __restrict__ mask, int64_t p) {
-  return (uint32_t)(load_plane_u64(mask, p >> 5) >> (uint32_t)(p & 31)) & 0xffffu;
-}
-// reverse the order of the sixteen 2-bit groups
-SIMMR_DEV uint32_t reverse_groups16(uint32_t x) {
-  const uint32_t y = __builtin_bitreverse32(x);
-  // each bit pair swapped back: odd result bits from y << 1, even ones from y >> 1 — one three-input select (v_bitop3_b32,
-  // truth table of c ? a : b with a = y >> 1, b = y << 1, c = 0x55555555)
-  return __builtin_amdgcn_bitop3_b32(y >> 1, y << 1, 0x55555555u, 0xe4);
-}
-// ~reverse_groups16(x): the complement folded into the select's truth table
-SIMMR_DEV uint32_t reverse_complement_groups16(uint32_t x) {
-  const uint32_t y = __builtin_bitreverse32(x);
-  return __builtin_amdgcn_bitop3_b32(y >> 1, y << 1, 0x55555555u, 0x1b);
-}
-// low bit of each of the sixteen 2-bit codes -> 16 bits
-SIMMR_DEV uint32_t c16_odd(uint32_t c) {
-  c &= 0x55555555u;
-  c = (c | (c >> 1)) & 0x33333333u;
-  c = (c | (c >> 2)) & 0x0F0F0F0Fu;
-  c = (c | (c >> 4)) & 0x00FF00FFu;
-  c = (c | (c >> 8)) & 0x0000FFFFu;
-  return c;
-}
-// 16 mask bits -> 16 two-bit groups (each bit duplicated)
-SIMMR_DEV uint32_t spread16(uint32_t m) {
-  m = (m | (m << 8)) & 0x00FF00FFu;
-  m = (m | (m << 4)) & 0x0F0F0F0Fu;
-  m = (m | (m << 2)) & 0x33333333u;
-  m = (m | (m << 1)) & 0x55555555u;
-  return m * 3u;
-}
-// 4 codes (8 bits) + 4 exception bits -> 4 ASCII bytes
-SIMMR_DEV uint32_t expand4(uint32_t c8, uint32_t m4) {
-  uint32_t sel = (c8 | (c8 << 6) | (c8 << 12) | (c8 << 18)) & 0x03030303u;
-  uint32_t ms = (m4 | (m4 << 7) | (m4 << 14) | (m4 << 21)) & 0x01010101u;
-  sel |= ms << 2;
-  // selector 0-3 -> "ACGT" (src1), 4-7 -> "N-N-" (src0)
-  return __builtin_amdgcn_perm(0x2D4E2D4Eu, 0x54474341u, sel);
-}
-
-struct PieceSrc {
-  int64_t pos;   // absolute base position of output byte 0's source
-  uint32_t rev;  // mate 2: byte k comes from pos - k, complemented
-};
-
-SIMMR_DEV void gather_piece(const GenomeDev& G, const PieceSrc& s, uint32_t k, uint32_t& codes,
-                            uint32_t& exc) {
-  // codes for output bytes k .. k+15 of this read (garbage past the read end)
-  if (!s.rev) {
-    int64_t p = s.pos + (int64_t)k;
-    codes = fetch_codes16(G.packed, p);
-    exc = G.has_exc ? fetch_mask16(G.mask, p) : 0u;
-  } else {
-    int64_t p = s.pos - (int64_t)k - 15;
-    uint32_t c = fetch_codes16(G.packed, p);
-    codes = ~reverse_groups16(c);  // complement = 3 - code
-    if (G.has_exc) {
-      uint32_t m = fetch_mask16(G.mask, p);
-      exc = __builtin_bitreverse32(m) >> 16;
-      codes ^= spread16(exc);  // exceptions ('N', '-') are their own complement
-    } else {
-      exc = 0u;
-    }
-  }
-}
 
 #define PERFECT_GROUP 256u /* reads per workgroup iteration: 256*L is a multiple of 16 */
 #define PERFECT_UNROLL 2

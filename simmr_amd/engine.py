@@ -711,6 +711,51 @@ class Engine:
         self._check(self.lib.simmr_last_pileup_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- fitting an error model from a run ------------------------------------------------
+    def fit_reset(self, k: int = 7, max_alt_kmers: int = 20, pair_capacity: int = 1 << 20):
+        """Zeroes the engine's model-fitting tables (simmr_fit_reset): k-mer size 3..10, the cut per reference k-mer, and how
+        many distinct changed (reference, alternate) pairs the run may show."""
+        self._check(self.lib.simmr_fit_reset(self._h, int(k), int(max_alt_kmers), int(pair_capacity)))
+
+    def fit_add(self, reads: Reads, n_sets: int):
+        """Adds `reads` to the tables (simmr_fit_add): enqueues only.  n_sets 2: a paired shard (insert sizes are taken); 1: long reads."""
+        pod = reads.pod()
+        self._check(self.lib.simmr_fit_add(self._h, C.byref(pod), reads.n_reads, int(n_sets)))
+
+    def fit_model(self) -> dict:
+        """Finishes the model from what was added (simmr_fit_plan / simmr_fit_emit): the columns of struct simmr_fit_out as
+        numpy arrays, the scalars of struct simmr_fit_info, and `model_bytes`, the bincode image of the ErrorModelParams
+        (model_io.serialize_model), which the custom profiles load unchanged."""
+        from . import model_io
+        torch = _torch()
+        info = _abi.FitInfo()
+        self._check(self.lib.simmr_fit_plan(self._h, C.byref(info)))
+        nr, npair, npos, nl, ni = (int(info.n_ref_kmers), int(info.n_pairs), int(info.n_positions), int(info.n_length_bins),
+                                   int(info.n_insert_bins))
+        shapes = {"kmer_ref": (nr, torch.int32, np.uint32), "kmer_first": (nr + 1, torch.int64, np.uint64),
+                  "pair_alt": (npair, torch.int32, np.uint32), "pair_count": (npair, torch.int64, np.uint64),
+                  "pair_prob": (npair, torch.float32, np.float32),
+                  "qual_hist": (npos * _abi.FIT_QUALS, torch.int64, np.uint64), "qual_density": (npos * _abi.FIT_DENSITIES, torch.float64, np.float64),
+                  "length_hist": (_abi.FIT_MAX_L + 1, torch.int64, np.uint64), "insert_hist": (_abi.FIT_MAX_INSERT + 1, torch.int64, np.uint64),
+                  "length_density": (nl, torch.float64, np.float64), "length_lo": (nl, torch.int32, np.uint32), "length_hi": (nl, torch.int32, np.uint32),
+                  "insert_density": (ni, torch.float64, np.float64), "insert_lo": (ni, torch.int32, np.uint32), "insert_hi": (ni, torch.int32, np.uint32)}
+        cols = {n: torch.zeros(max(size, 1), dtype=dt, device=self.device) for n, (size, dt, _) in shapes.items()}
+        out = _abi.FitOut(*[cols[n].data_ptr() for n in _abi.FIT_COLUMNS], nr, npair, npos, nl, ni)
+        self._check(self.lib.simmr_fit_emit(self._h, C.byref(out)))
+        m = {n: cols[n][:shapes[n][0]].cpu().numpy().view(shapes[n][2]) for n in _abi.FIT_COLUMNS}
+        m["qual_hist"] = m["qual_hist"].reshape(npos, _abi.FIT_QUALS)
+        m["qual_density"] = m["qual_density"].reshape(npos, _abi.FIT_DENSITIES)
+        for name, _ in _abi.FitInfo._fields_:
+            if name != "pad":
+                m[name] = getattr(info, name)
+        m["model_bytes"] = model_io.serialize_fitted(m)
+        return m
+
+    def last_fit_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_fit_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # -- counters / timing --------------------------------------------------------
     def counters(self) -> np.ndarray:
         host = (C.c_uint64 * _abi.N_COUNTERS)()

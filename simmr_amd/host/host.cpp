@@ -3,6 +3,7 @@
 #include "simmr_host.hpp"
 
 #include "../csrc/custom_model.hpp"
+#include "../csrc/fit_host.hpp"
 
 #include <math.h>
 #include <stdio.h>
@@ -448,6 +449,48 @@ bool write_strain_vcf(const std::vector<Genome>& genomes, const std::vector<std:
 }
 
 // --------------------------------------------------------------- run statistics
+std::string fit_model_bytes(const simmr_fit_info& f, const simmr_fit_out& c) {
+  simmr::ModelHost m;
+  m.bin_size = 1;
+  m.quality.resize(f.n_positions);
+  for (uint64_t p = 0; p < f.n_positions; p++) {
+    simmr::BinsHost& b = m.quality[p];
+    b.num_bins = 70;
+    b.bin_width = 1;
+    b.density.assign(c.qual_density + p * SIMMR_FIT_DENSITIES, c.qual_density + (p + 1) * SIMMR_FIT_DENSITIES);
+    for (uint32_t i = 0; i < 70; i++) b.ranges.emplace_back(i, i);
+  }
+  m.bit_encoding = 3;
+  m.kmer_size = f.k;
+  m.probabilities.resize(f.n_ref_kmers);
+  for (uint64_t i = 0; i < f.n_ref_kmers; i++) {
+    m.probabilities[i].first = c.kmer_ref[i];
+    for (uint64_t j = c.kmer_first[i]; j < c.kmer_first[i + 1] && j < f.n_pairs; j++) m.probabilities[i].second.emplace_back(c.pair_alt[j], c.pair_prob[j]);
+  }
+  auto bins = [](uint64_t n, uint64_t width, const double* d, const uint32_t* lo, const uint32_t* hi) {
+    simmr::BinsHost b;
+    b.num_bins = n;
+    b.bin_width = width;
+    b.density.assign(d, d + n);
+    for (uint64_t i = 0; i < n; i++) b.ranges.emplace_back(lo[i], hi[i]);
+    return b;
+  };
+  m.insert_size_mean = f.insert_size_mean;
+  m.insert_size_std = f.insert_size_std;
+  m.has_insert_bins = f.n_insert_bins > 0;
+  if (m.has_insert_bins) m.insert_bins = bins(f.n_insert_bins, f.insert_bin_width, c.insert_density, c.insert_lo, c.insert_hi);
+  m.read_length_mean = f.read_length_mean;
+  m.read_length_std = f.read_length_std;
+  m.read_length_bins = bins(f.n_length_bins, f.length_bin_width, c.length_density, c.length_lo, c.length_hi);
+  m.is_long = f.is_long != 0;
+  return simmr::serialize_model(m);
+}
+bool write_fit_model(const simmr_fit_info& info, const simmr_fit_out& cols, const std::string& output, std::string* err) {
+  OutFile f(output, false);
+  f.append(fit_model_bytes(info, cols));
+  return f.close(err);
+}
+
 bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::string* err) {
   std::string text = "table\tset\ti\tj\tcount\n";
   char buf[96];
@@ -717,6 +760,12 @@ std::string usage() {
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
          "                            not with --devices\n"
+         "            --fit-model <FILE>  an error model fitted from the run, as `simmrd generate` writes it and --custom-profile reads it:\n"
+         "                            k-mer to alternate-k-mer probabilities, a quality density per read position, read-length and insert-size\n"
+         "                            densities, counted on the device over every range of the run; a quality above 93 is refused;\n"
+         "                            not with --devices\n"
+         "            --fit-k <K>  k-mer size of --fit-model, 3 .. 10 [default: 7]\n"
+         "            --fit-max-alt <N>  alternates kept per reference k-mer [default: 20]\n"
          "            --depth <FILE>  coverage the run put on every sequence, as a TSV: genome_id sequence_id length covered depth_sum depth_max\n"
          "                            (read depth, mates counted separately; counted on the device from every range of the run;\n"
          "                             combines with --truth and --stats; not with --devices)\n"
@@ -817,6 +866,9 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--overlaps") { if (!file(&a->overlaps)) return false; }
     else if (arg == "--min-overlap") { if (!uint(1, UINT64_MAX, " (at least 1)")) return false; a->min_overlap = u; }
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }
+    else if (arg == "--fit-model") { if (!file(&a->fit_model)) return false; }
+    else if (arg == "--fit-k") { if (!uint(3, 10, " (3 .. 10)")) return false; a->fit_k = (uint32_t)u; }
+    else if (arg == "--fit-max-alt") { if (!uint(1, UINT32_MAX, " (at least 1)")) return false; a->fit_max_alt = (uint32_t)u; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
     else if (arg == "--strain-sites") { if (!file(&a->strain_sites)) return false; }
@@ -1057,6 +1109,13 @@ char* simmr_host_strain_vcf(uint64_t n_sites, const uint32_t* genome, const uint
   std::string err;
   if (!write_strain_vcf(genomes, lens, s, std::vector<uint32_t>(genome, genome + n_sites), std::vector<uint32_t>(counts, counts + n_sites * 10), path, &err))
     return dup_str("ERR\t" + err);
+  return dup_str("OK");
+}
+// The model file of write_fit_model for an info and columns in host memory.  Returns "OK", or "ERR\t..." .
+char* simmr_host_fit_model(const simmr_fit_info* info, const simmr_fit_out* cols, const char* path) {
+  std::string err;
+  if (!info || !cols || !path) return dup_str("ERR\tNULL argument");
+  if (!write_fit_model(*info, *cols, path, &err)) return dup_str("ERR\t" + err);
   return dup_str("OK");
 }
 // The statistics TSV of write_stats_tsv for a simmr_run_stats in host memory.  Returns "OK", or "ERR\t..." .

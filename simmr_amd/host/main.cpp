@@ -257,7 +257,7 @@ struct GrowBuf {
 // the text buffer of the drains: what one copy to the host moves, and what a window of --overlaps holds
 static constexpr size_t TEXT_CHUNK = 256u << 20;
 
-// The side outputs of a run: --truth, --sam, --overlaps, --stats, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
+// The side outputs of a run: --truth, --sam, --overlaps, --stats, --fit-model, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
 // takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
 struct SideOutputs {
   explicit SideOutputs(const CliArgs& args) : a(args) {}
@@ -285,24 +285,26 @@ struct SideOutputs {
   bool depth_files() const { return !a.depth.empty() || !a.depth_track.empty(); }
   bool gold() const { return !a.gold_assembly.empty() || !a.gold_regions.empty(); }
   bool depth() const { return depth_files() || gold(); }  // (the gold-standard assembly is read off the run's depth[])
-  bool wanted() const { return !a.truth.empty() || sam() || overlaps() || !a.stats.empty() || depth() || vcf(); }
+  bool fit() const { return !a.fit_model.empty(); }
+  bool wanted() const { return !a.truth.empty() || sam() || overlaps() || !a.stats.empty() || fit() || depth() || vcf(); }
   bool fail(const char* flag, const std::string& what) { err = std::string(flag) + ": " + what; return false; }
   // true, with the message, if one of them is asked for together with --devices
   bool refuse_devices() {
-    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : sam() ? "--sam" : overlaps() ? "--overlaps" : nullptr;
+    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : fit() ? "--fit-model" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : sam() ? "--sam" : overlaps() ? "--overlaps" : nullptr;
     if (flag && !a.devices.empty()) err = std::string(flag) + " does not combine with --devices: use --device";
     return flag && !a.devices.empty();
   }
   // the old files go, the truth file gets its header line (every range appends its reads), the tables start at zero
   // (the genomes are staged: depth[] covers all of them)
   bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
-    for (const std::string* f : {&a.truth, &a.sam, &a.overlaps, &a.stats, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
+    for (const std::string* f : {&a.truth, &a.sam, &a.overlaps, &a.stats, &a.fit_model, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
       if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
     std::string e;
     if (overlaps() && simmr_overlap_reset(eng, run_paired ? 1 : 0) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
     if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
     if (sam() && !begin_sam(genomes)) return false;
     if (!a.stats.empty() && simmr_stats_reset(eng) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
+    if (fit() && simmr_fit_reset(eng, a.fit_k, a.fit_max_alt, FIT_PAIR_CAPACITY) != SIMMR_OK) return fail("--fit-model", simmr_last_error(eng));
     // (--strain-vcf takes the sequences' lengths from the layout the depth reset records)
     if ((depth() || vcf()) && simmr_depth_reset(eng, &depth_positions, &depth_contigs) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
     return !vcf() || begin_pileup(eng);
@@ -413,6 +415,7 @@ struct SideOutputs {
   // every range adds to the run's tables (enqueued behind the emit; the copies that follow wait for the device)
   bool add_range(simmr_engine* eng, const simmr_reads_out& reads, uint64_t n_reads, bool paired) {
     if (!a.stats.empty() && simmr_stats_add(eng, &reads, n_reads, paired ? 2u : 1u) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
+    if (fit() && simmr_fit_add(eng, &reads, n_reads, paired ? 2u : 1u) != SIMMR_OK) return fail("--fit-model", simmr_last_error(eng));
     if (depth() && simmr_depth_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--depth", simmr_last_error(eng));
     if (vcf() && simmr_pileup_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--strain-vcf", simmr_last_error(eng));
     if (overlaps() && simmr_overlap_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
@@ -453,8 +456,41 @@ struct SideOutputs {
     }
     return f.close(&e) || fail("--overlaps", e);
   }
+  // the model of every range added: one plan, the columns through device buffers of the planned sizes, the bincode image
+  static constexpr uint64_t FIT_PAIR_CAPACITY = 1ull << 24;  // distinct changed (reference, alternate) pairs a run may show
+  bool finish_fit(simmr_engine* eng) {
+    simmr_fit_info f{};
+    if (simmr_fit_plan(eng, &f) != SIMMR_OK) return fail("--fit-model", simmr_last_error(eng));
+    DeviceMem mem;
+    simmr_fit_out d{}, h{};
+    d.ref_capacity = f.n_ref_kmers; d.pair_capacity = f.n_pairs; d.position_capacity = f.n_positions;
+    d.length_bin_capacity = f.n_length_bins; d.insert_bin_capacity = f.n_insert_bins;
+    if (!(mem.alloc(&d.kmer_ref, f.n_ref_kmers) && mem.alloc(&d.kmer_first, f.n_ref_kmers + 1) && mem.alloc(&d.pair_alt, f.n_pairs) &&
+          mem.alloc(&d.pair_prob, f.n_pairs) && mem.alloc(&d.qual_density, f.n_positions * SIMMR_FIT_DENSITIES) &&
+          mem.alloc(&d.length_density, f.n_length_bins) && mem.alloc(&d.length_lo, f.n_length_bins) && mem.alloc(&d.length_hi, f.n_length_bins) &&
+          mem.alloc(&d.insert_density, f.n_insert_bins) && mem.alloc(&d.insert_lo, f.n_insert_bins) && mem.alloc(&d.insert_hi, f.n_insert_bins)))
+      return fail("--fit-model", "device allocation failed");
+    if (simmr_fit_emit(eng, &d) != SIMMR_OK) return fail("--fit-model", simmr_last_error(eng));
+    std::vector<uint32_t> kmer_ref, pair_alt, llo, lhi, ilo, ihi;
+    std::vector<uint64_t> kmer_first;
+    std::vector<float> pair_prob;
+    std::vector<double> qd, ld, id;
+    if (!(DeviceMem::fetch(&kmer_ref, (const uint32_t*)d.kmer_ref, f.n_ref_kmers) && DeviceMem::fetch(&kmer_first, (const uint64_t*)d.kmer_first, f.n_ref_kmers + 1) &&
+          DeviceMem::fetch(&pair_alt, (const uint32_t*)d.pair_alt, f.n_pairs) && DeviceMem::fetch(&pair_prob, (const float*)d.pair_prob, f.n_pairs) &&
+          DeviceMem::fetch(&qd, (const double*)d.qual_density, f.n_positions * SIMMR_FIT_DENSITIES) &&
+          DeviceMem::fetch(&ld, (const double*)d.length_density, f.n_length_bins) && DeviceMem::fetch(&llo, (const uint32_t*)d.length_lo, f.n_length_bins) &&
+          DeviceMem::fetch(&lhi, (const uint32_t*)d.length_hi, f.n_length_bins) && DeviceMem::fetch(&id, (const double*)d.insert_density, f.n_insert_bins) &&
+          DeviceMem::fetch(&ilo, (const uint32_t*)d.insert_lo, f.n_insert_bins) && DeviceMem::fetch(&ihi, (const uint32_t*)d.insert_hi, f.n_insert_bins)))
+      return fail("--fit-model", "copy back failed");
+    h.kmer_ref = kmer_ref.data(); h.kmer_first = kmer_first.data(); h.pair_alt = pair_alt.data(); h.pair_prob = pair_prob.data();
+    h.qual_density = qd.data(); h.length_density = ld.data(); h.length_lo = llo.data(); h.length_hi = lhi.data();
+    h.insert_density = id.data(); h.insert_lo = ilo.data(); h.insert_hi = ihi.data();
+    std::string e;
+    return write_fit_model(f, h, a.fit_model, &e) || fail("--fit-model", e);
+  }
   bool finish(simmr_engine* eng, const std::vector<Genome>& genomes) {
     std::string e;
+    if (fit() && !finish_fit(eng)) return false;
     if (overlaps() && !finish_overlaps(eng)) return false;
     if (sam() && a.sam_sorted && !finish_sam_sorted()) return false;
     if (!a.stats.empty()) {

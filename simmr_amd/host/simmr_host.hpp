@@ -199,6 +199,13 @@ bool write_strain_vcf(const std::vector<Genome>& genomes, const std::vector<std:
 // index (reads, bases, cycle_n, cycle_qsum, cycle_mismatch: set and i; cycle_base: set, i = offset, j = class; pair: i =
 // expected class, j = written class; the histograms and quality tables: i).  Replaces `output`.
 bool write_stats_tsv(const simmr_run_stats& st, const std::string& output, std::string* err);
+// `simmr-hip --fit-model FILE`: the model simmr_fit_plan made as the bincode image of a shared::encoding::ErrorModelParams, what
+// `simmrd generate` writes and --custom-profile reads.  `cols` holds the columns of simmr_fit_emit copied to HOST memory (every
+// one of kmer_ref, kmer_first, pair_alt, pair_prob, qual_density and the length / insert density, lo and hi columns that `info`
+// gives a size); per position 71 densities beside num_bins 70 and ranges (i, i), bin_size 1.  The bytes are those of
+// simmr_amd/model_io.py:serialize_fitted.  Replaces `output`.
+std::string fit_model_bytes(const simmr_fit_info& info, const simmr_fit_out& cols);
+bool write_fit_model(const simmr_fit_info& info, const simmr_fit_out& cols, const std::string& output, std::string* err);
 
 // ---------------------------------------------------------------- coverage depth (no reference counterpart)
 // `simmr-hip --depth FILE`: a line of column names, then one tab-separated line per contig, in the order of depth[]:
@@ -338,6 +345,9 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string sam;    // --sam FILE: the true alignments as SAM (simmr_sam_plan / simmr_sam_emit on every range's columns, the header from the host)
   std::string overlaps;       // --overlaps FILE: the true read-to-read overlaps of the run as PAF (simmr_overlap_add over every range, one plan, drained by windows)
   uint64_t min_overlap = 1;   // --min-overlap N: shared reference bases from which two reads overlap
+  std::string fit_model;      // --fit-model FILE: an error model fitted from the run (simmr_fit_add over every range, one plan) as simmrd writes it
+  uint32_t fit_k = 7;         // --fit-k K: its k-mer size, 3 .. 10
+  uint32_t fit_max_alt = 20;  // --fit-max-alt N: alternates kept per reference k-mer
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions

@@ -10,7 +10,8 @@ import numpy as np
 
 def _bins(density, ranges, num_bins=None, bin_width=1):
     out = struct.pack("<QQ", len(ranges) if num_bins is None else num_bins, bin_width)
-    out += struct.pack("<Q", len(density)) + b"".join(struct.pack("<d", float(x)) for x in density)
+    density = np.asarray(density, dtype="<f8")
+    out += struct.pack("<Q", density.size) + density.tobytes()
     out += struct.pack("<Q", len(ranges)) + b"".join(struct.pack("<II", int(a), int(b)) for a, b in ranges)
     return out
 
@@ -24,23 +25,41 @@ def three_bit_encode(kmer: str) -> int:
 
 def serialize_model(quality_bins, read_length_bins, insert_size_bins=None, probabilities=(), kmer_size=7,
                     bin_size=1, insert_size_mean=150.0, insert_size_std=75.0, read_length_mean=150.0,
-                    read_length_std=15.0, is_long=False) -> bytes:
-    """quality_bins: list of (density, ranges) per read position; *_bins: (density, ranges)."""
-    out = struct.pack("<Q", bin_size)
-    out += struct.pack("<Q", len(quality_bins)) + b"".join(_bins(d, r) for d, r in quality_bins)
-    out += struct.pack("<B", 3) + struct.pack("<Q", kmer_size)
-    out += struct.pack("<Q", len(probabilities))
+                    read_length_std=15.0, is_long=False, read_length_bin_width=1, insert_size_bin_width=1) -> bytes:
+    """quality_bins: list of (density, ranges) per read position; *_bins: (density, ranges).  The *_bin_width arguments are
+    the Bins.bin_width fields of the two histograms (simmrd writes its Freedman-Diaconis width there; no reader uses it)."""
+    out = [struct.pack("<Q", bin_size)]  # (parts, joined once: a fitted model has tens of thousands of k-mers behind megabytes of bins)
+    out.append(struct.pack("<Q", len(quality_bins)) + b"".join(_bins(d, r) for d, r in quality_bins))
+    out.append(struct.pack("<B", 3) + struct.pack("<Q", kmer_size))
+    out.append(struct.pack("<Q", len(probabilities)))
     for kmer, alts in probabilities:
-        out += struct.pack("<I", int(kmer) & 0xFFFFFFFF) + struct.pack("<Q", len(alts))
-        out += b"".join(struct.pack("<If", int(a) & 0xFFFFFFFF, float(w)) for a, w in alts)
-    out += struct.pack("<dd", insert_size_mean, insert_size_std)
+        out.append(struct.pack("<I", int(kmer) & 0xFFFFFFFF) + struct.pack("<Q", len(alts)))
+        out.append(b"".join(struct.pack("<If", int(a) & 0xFFFFFFFF, float(w)) for a, w in alts))
+    out.append(struct.pack("<dd", insert_size_mean, insert_size_std))
     if insert_size_bins is None:
-        out += b"\x00"
+        out.append(b"\x00")
     else:
-        out += b"\x01" + _bins(*insert_size_bins)
-    out += struct.pack("<dd", read_length_mean, read_length_std) + _bins(*read_length_bins)
-    out += struct.pack("<B", 1 if is_long else 0)
-    return out
+        out.append(b"\x01" + _bins(*insert_size_bins, bin_width=insert_size_bin_width))
+    out.append(struct.pack("<dd", read_length_mean, read_length_std) + _bins(*read_length_bins, bin_width=read_length_bin_width))
+    out.append(struct.pack("<B", 1 if is_long else 0))
+    return b"".join(out)
+
+
+def serialize_fitted(m) -> bytes:
+    """The bincode image of a model fitted on the device: `m` holds the columns of struct simmr_fit_out and the scalars of struct
+    simmr_fit_info (Engine.fit_model(), include/simmr_hip.h).  Shaped as simmrd writes it: per position 71 densities beside
+    num_bins = 70 and 70 ranges (i, i); bin_size 1."""
+    ranges70 = [(i, i) for i in range(70)]
+    quality = [(row, ranges70) for row in np.asarray(m["qual_density"], dtype=np.float64)]
+    first = np.asarray(m["kmer_first"], dtype=np.uint64)
+    probs = [(int(ref), list(zip(m["pair_alt"][int(first[i]):int(first[i + 1])].tolist(), m["pair_prob"][int(first[i]):int(first[i + 1])].tolist())))
+             for i, ref in enumerate(np.asarray(m["kmer_ref"]))]
+    bins = lambda name: (m[name + "_density"], list(zip(np.asarray(m[name + "_lo"]).tolist(), np.asarray(m[name + "_hi"]).tolist())))
+    return serialize_model(quality, bins("length"), bins("insert") if len(m["insert_lo"]) else None, probabilities=probs,
+                           kmer_size=int(m["k"]), bin_size=1, insert_size_mean=float(m["insert_size_mean"]),
+                           insert_size_std=float(m["insert_size_std"]), read_length_mean=float(m["read_length_mean"]),
+                           read_length_std=float(m["read_length_std"]), is_long=bool(m["is_long"]),
+                           read_length_bin_width=int(m["length_bin_width"]), insert_size_bin_width=int(m["insert_bin_width"]))
 
 
 def synthetic_short_model(n_positions=120, seed=3, mean_len=140, sd_len=12, mean_insert=200, sd_insert=40):
