@@ -1055,6 +1055,75 @@ int simmr_fit_emit(simmr_engine* e, const simmr_fit_out* out);
 /* HIP-event time (ms) of the last simmr_fit_add's device work.  Synchronises the stream. */
 int simmr_last_fit_ms(simmr_engine* e, float* ms);
 
+/* ---- the same fit from a user's SAM file: text in HBM, parsed on the device ------------------------------------------
+ * What `simmrd` itself starts from (simmrd/src/main.rs:110-260, simmrd/src/alignment.rs): SAM records with CIGAR and
+ * MD:Z.  simmr_fit_add_sam adds the records of `text` into the SAME tables as simmr_fit_add, so adds from columns and from
+ * SAM may be mixed between one simmr_fit_reset and one simmr_fit_plan; no genome need be staged.  The SAM text of a run
+ * (simmr_sam_emit, either order) gives the model of that run's columns, byte for byte.
+ *
+ * Text.  Whole lines of plain SAM (no BAM, no gzip): every line ends in '\n', except that the last line of a call may lack
+ * it; the caller cuts a large file at line ends, at most SIMMR_FIT_SAM_MAX_BYTES a call.  An empty line is skipped and not
+ * counted.  A line that starts with '@' is a header line: counted and skipped.  Every other line is a record of tab-separated
+ * fields: 11 mandatory ones and the optional ones, of which the first that starts with "MD:Z:" is taken.
+ *
+ * Malformed (sticky, simmr_fit_plan answers SIMMR_EINVAL and makes nothing): a record with fewer than 11 fields; a FLAG,
+ * MAPQ or TLEN that is not a decimal number (1 to 18 digits; TLEN may start with '-'); a CIGAR that is neither "*" nor
+ * (<digits><op>)+ with 1 to 9 digits a run, an op being any byte that is no digit; a QUAL that is neither "*" nor exactly as
+ * long as SEQ (a SEQ of "*" has no bases: its QUAL is "*"); a QUAL byte outside '!' .. '~'.  These are checked on every
+ * record, whatever the filters would say of it.
+ *
+ * Filters, in this order (main.rs:156-232); L = the length of SEQ, the quality of a byte is byte - 33:
+ *    1. SEQ is "*": skip_no_sequence.
+ *    2. FLAG has 0x100 or 0x800: skip_secondary.  (This stands in for the reference's "name already seen", which also drops
+ *       every mate 2 whose name equals mate 1's: the accident noted above, not reproduced.)
+ *    3. L > SIMMR_FIT_MAX_L: skip_too_long.
+ *    4. The record counts for the length histogram and, if QUAL is not "*", for the quality histogram (taken_quality).
+ *    5. FLAG 0x4: skip_unmapped.                        6. MAPQ == 0: skip_mapq0 (255 passes, as in the reference).
+ *    7. n_sets == 2, TLEN == 0 and FLAG 0x8: skip_mate_unmapped.           8. No MD:Z: field: skip_no_md.
+ *    9. n_sets == 2 and |TLEN| > SIMMR_FIT_MAX_INSERT: skip_insert.
+ *   10. n_sets == 2: |TLEN| goes into the insert histogram (n_sets == 1 takes no inserts: simmr_fit_add's rule).
+ *   11. The alignment is taken (taken_alignment), unless the next paragraph skips it; that does not undo steps 4 and 10.
+ *
+ * Alignment rows (alignment.rs, reconstruct_alignment), built in SAM's forward orientation.  M, = and X give one column
+ * each: the query byte from SEQ, the reference byte that same byte where MD says match and MD's letter where it says
+ * mismatch.  I: reference '-', the query byte.  D: the reference byte from MD's '^' run, query '-'.  H: nothing.  S consumes
+ * query bases and gives NO column — a departure: the reference walks MD through soft clips, which MD does not cover, and
+ * so shifts every later base.  N, P, any other op, or a CIGAR of "*": skip_cigar_op (the reference panics).  MD is numbers of
+ * 1 to 9 digits, letters 'A' .. 'Z' and '^'; a letter is a deleted base when the nearest byte before it that is no letter
+ * is '^', otherwise a mismatch.  skip_inconsistent, where the reference would silently truncate: the query bases of the
+ * CIGAR (M = X I S) differ from L; MD's matches plus mismatches differ from the CIGAR's M = X columns; MD's deleted bases
+ * differ from its D columns; MD holds another byte or a longer number.
+ *
+ * Orientation.  With FLAG 0x10 both rows are reversed and complemented (A <-> T, C <-> G; a gap and every other byte keep
+ * their byte), and quality offset i of the read is QUAL[L - 1 - i]: the read's own orientation, what simmr_fit_add counts in
+ * and what the custom profiles consume.  A departure beside the one above: the reference complements SEQ and keeps the forward
+ * CIGAR, and indexes qualities in file order.
+ *
+ * Windows.  The k-mer rule above over the two rows, with `columns` (M = X + I + D) in the place of L: every ndx with
+ * ndx + k < columns, over k COLUMNS.  A reference window that holds a '-' or a byte outside ACGT is skipped; the query
+ * window loses its '-' and N and is N-padded; an empty query window, or a query byte outside ACGTN-, is skipped.
+ *
+ * Every table stays an integer sum over records: the same for any launch geometry and any cut of the text into adds. */
+#define SIMMR_FIT_SAM_MAX_BYTES 0xf0000000ull   /* most bytes of text in one simmr_fit_add_sam */
+
+typedef struct simmr_fit_sam_counts {   /* HOST; every entry an integer sum over lines, cumulative since simmr_fit_reset */
+  uint64_t lines, header_lines, records;   /* lines = header_lines + records: empty lines are not counted */
+  uint64_t taken_quality;      /* records whose length (and qualities, if present) were counted */
+  uint64_t taken_alignment;    /* records whose k-mer windows were counted */
+  uint64_t skip_no_sequence, skip_secondary, skip_too_long, skip_unmapped, skip_mapq0,
+           skip_mate_unmapped, skip_no_md, skip_insert, skip_cigar_op, skip_inconsistent;
+} simmr_fit_sam_counts;
+
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add).  Only
+ * enqueues on the engine's stream; timed by simmr_last_fit_ms like simmr_fit_add.  Side buffers of about seven bytes per byte
+ * of text grow with the engine and are freed with it.
+ * SIMMR_EINVAL, at once: n_sets other than 1 or 2, a NULL text with n_bytes > 0.  SIMMR_ENOTSUP: n_bytes above
+ * SIMMR_FIT_SAM_MAX_BYTES.  SIMMR_ESTATE: no simmr_fit_reset yet.  Sticky, reported by simmr_fit_plan as SIMMR_EINVAL: a
+ * malformed record (above); SIMMR_ERANGE there: a full pair table. */
+int simmr_fit_add_sam(simmr_engine* e, const uint8_t* text, uint64_t n_bytes, uint32_t n_sets);
+/* The counts of the SAM adds since the last simmr_fit_reset.  Synchronises.  SIMMR_ESTATE: no simmr_fit_reset yet. */
+int simmr_fit_sam_counts_read(simmr_engine* e, simmr_fit_sam_counts* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -228,6 +228,16 @@ class FitOut(C.Structure):
                                           "insert_bin_capacity")]
 
 
+FIT_SAM_COUNTS = ("lines", "header_lines", "records", "taken_quality", "taken_alignment", "skip_no_sequence", "skip_secondary",
+                  "skip_too_long", "skip_unmapped", "skip_mapq0", "skip_mate_unmapped", "skip_no_md", "skip_insert", "skip_cigar_op",
+                  "skip_inconsistent")
+
+
+class FitSamCounts(C.Structure):
+    """struct simmr_fit_sam_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in FIT_SAM_COUNTS]
+
+
 class SamNames(C.Structure):
     """struct simmr_sam_names (host memory)"""
     _fields_ = [
@@ -337,6 +347,8 @@ SYMBOLS = {
     "simmr_fit_plan": (C.c_int, [C.c_void_p, _P(FitInfo)]),
     "simmr_fit_emit": (C.c_int, [C.c_void_p, _P(FitOut)]),
     "simmr_last_fit_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_fit_add_sam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "simmr_fit_sam_counts_read": (C.c_int, [C.c_void_p, _P(FitSamCounts)]),
 }
 
 _lib = None

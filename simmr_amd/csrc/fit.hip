@@ -47,7 +47,7 @@ struct FitState {
   // largest since the tables were last cleared whole); an add without a plan behind it leaves the whole table suspect
   uint64_t dirty_pos = 0, clean_dense = 0, clean_slots = 0;
   bool unplanned_add = true;
-  // tables: dense | hkey | hcnt | qhist | lhist | ihist | n_out (8 bytes) | err (8 bytes)
+  // tables: dense | hkey | hcnt | qhist | lhist | ihist | n_out (8 bytes) | err (8 bytes) | the SAM route's counts
   DevBuf tables, out_key, out_cnt, pts, qdens, ldens, idens;
   // the finish: sort buffers, the per-reference tables (start | n_alt | total | first | sizes[2]), the model's pair columns
   DevBuf skey[2], sidx[2], perm[2], hist, digit_total, refs, kmer_ref, kmer_first, pair_alt, pair_count, pair_prob;
@@ -57,7 +57,7 @@ struct FitState {
   FitBins len, ins;
 
   static constexpr uint64_t Q_WORDS = (uint64_t)FIT_MAX_L * SIMMR_FIT_QUALS, L_WORDS = FIT_MAX_L + 1ull, I_WORDS = SIMMR_FIT_MAX_INSERT + 1ull;
-  uint64_t words() const { return n_dense + 2 * n_slots + Q_WORDS + L_WORDS + I_WORDS + 2; }
+  uint64_t words() const { return n_dense + 2 * n_slots + Q_WORDS + L_WORDS + I_WORDS + 2 + FIT_SAM_COUNTS; }
   unsigned long long* w(uint64_t at) const { return tables.as<unsigned long long>() + at; }
   unsigned long long* dense() const { return w(0); }
   unsigned long long* hkey() const { return w(n_dense); }
@@ -67,6 +67,7 @@ struct FitState {
   unsigned long long* ihist() const { return lhist() + L_WORDS; }
   unsigned long long* n_out() const { return ihist() + I_WORDS; }
   uint32_t* err() const { return (uint32_t*)(n_out() + 1); }
+  unsigned long long* sam_counts() const { return n_out() + 2; }
   FitTables dev() const { return FitTables{dense(), hkey(), hcnt(), qhist(), lhist(), ihist(), err(), (uint32_t)(n_slots - 1), k}; }
 };
 
@@ -101,6 +102,25 @@ int sync_check(simmr_engine* e, const char* what) {
 
 }  // namespace
 
+namespace simmr {
+
+bool fit_share(simmr_engine* e, FitShare* out) {
+  FitState* s = state_of(e, false);
+  if (!s || !s->ready) return false;
+  *out = FitShare{s->dev(), s->sam_counts(), {s->ev[0], s->ev[1]}};
+  return true;
+}
+
+void fit_share_added(simmr_engine* e) {
+  FitState* s = state_of(e, false);
+  if (!s) return;
+  s->planned = false;
+  s->unplanned_add = true;
+  s->timed = true;
+}
+
+}  // namespace simmr
+
 extern "C" {
 
 int simmr_fit_reset(simmr_engine* e, uint32_t k, uint32_t max_alt_kmers, uint64_t pair_capacity) {
@@ -129,7 +149,7 @@ int simmr_fit_reset(simmr_engine* e, uint32_t k, uint32_t max_alt_kmers, uint64_
     FIT_TRY(e, hipMemsetAsync(s->tables.p, 0, s->words() * 8, st));
   } else {
     FIT_TRY(e, hipMemsetAsync(s->tables.p, 0, (s->n_dense + 2 * s->n_slots + s->dirty_pos * SIMMR_FIT_QUALS) * 8, st));
-    FIT_TRY(e, hipMemsetAsync(s->lhist(), 0, (FitState::L_WORDS + FitState::I_WORDS + 2) * 8, st));
+    FIT_TRY(e, hipMemsetAsync(s->lhist(), 0, (FitState::L_WORDS + FitState::I_WORDS + 2 + FIT_SAM_COUNTS) * 8, st));
   }
   s->dirty_pos = 0;
   s->unplanned_add = false;
@@ -191,6 +211,10 @@ int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info) {
                                      "leaves its contig or seq[], or it is longer than %u bases", SIMMR_FIT_MAX_L);
   if (errw & FIT_ERR_QUAL)
     return eng_fail(e, SIMMR_EINVAL, "a read added since the last simmr_fit_reset has a quality above %u", SIMMR_FIT_MAX_Q);
+  if (errw & FIT_ERR_SAM)
+    return eng_fail(e, SIMMR_EINVAL, "a SAM record added since the last simmr_fit_reset is malformed (fewer than 11 fields, a FLAG, MAPQ or TLEN that "
+                                     "is no number, a CIGAR that is neither * nor runs of <digits><op>, a QUAL that is neither * nor as long as SEQ "
+                                     "or holds a byte outside '!' .. '~')");
   if (errw & FIT_ERR_FULL)
     return eng_fail(e, SIMMR_ERANGE, "the pair table of simmr_fit_reset (%llu slots) is full", (unsigned long long)s->n_slots);
   // ---- lengths and inserts: scalars and bins on the host, mid-points to the device

@@ -147,14 +147,16 @@ class Engine:
         if rc != 0:
             raise SimmrError(rc, (self.lib.simmr_last_error(None) or b"").decode())
         self._h = h
+        self._fit_sam_texts = []  # SAM texts of fit_add_sam whose adds may still be enqueued
         self.device_index = int(device)
         self._keep = []
 
     # -- lifetime ---------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
-            self.lib.simmr_engine_destroy(self._h)
+            self.lib.simmr_engine_destroy(self._h)  # synchronises the device before it frees: enqueued adds have read their texts
             self._h = None
+            self._fit_sam_texts = []
 
     def __del__(self):
         try:
@@ -722,6 +724,27 @@ class Engine:
         pod = reads.pod()
         self._check(self.lib.simmr_fit_add(self._h, C.byref(pod), reads.n_reads, int(n_sets)))
 
+    def fit_add_sam(self, text, n_sets: int):
+        """Adds the records of SAM `text` to the tables (simmr_fit_add_sam): whole lines, as a CUDA uint8 tensor or as bytes
+        (copied up).  Enqueues only: every text is kept until a call that synchronises (fit_model, fit_sam_counts) or until
+        close(), whose simmr_engine_destroy synchronises the device before anything is dropped."""
+        torch = _torch()
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            host = np.frombuffer(bytes(text), dtype=np.uint8)
+            text = torch.from_numpy(host.copy()).to(self.device) if host.size else torch.empty(0, dtype=torch.uint8, device=self.device)
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise ValueError("fit_add_sam takes bytes or a contiguous CUDA uint8 tensor")
+        self._fit_sam_texts.append(text)
+        n = int(text.numel())
+        self._check(self.lib.simmr_fit_add_sam(self._h, C.c_void_p(text.data_ptr() if n else None), n, int(n_sets)))
+
+    def fit_sam_counts(self) -> dict:
+        """What the SAM adds since the last fit_reset took and skipped (simmr_fit_sam_counts_read), by the names of the struct."""
+        c = _abi.FitSamCounts()
+        self._check(self.lib.simmr_fit_sam_counts_read(self._h, C.byref(c)))
+        self._fit_sam_texts = []
+        return {n: int(getattr(c, n)) for n in _abi.FIT_SAM_COUNTS}
+
     def fit_model(self) -> dict:
         """Finishes the model from what was added (simmr_fit_plan / simmr_fit_emit): the columns of struct simmr_fit_out as
         numpy arrays, the scalars of struct simmr_fit_info, and `model_bytes`, the bincode image of the ErrorModelParams
@@ -729,7 +752,10 @@ class Engine:
         from . import model_io
         torch = _torch()
         info = _abi.FitInfo()
-        self._check(self.lib.simmr_fit_plan(self._h, C.byref(info)))
+        try:
+            self._check(self.lib.simmr_fit_plan(self._h, C.byref(info)))
+        finally:
+            self._fit_sam_texts = []  # the plan has synchronised
         nr, npair, npos, nl, ni = (int(info.n_ref_kmers), int(info.n_pairs), int(info.n_positions), int(info.n_length_bins),
                                    int(info.n_insert_bins))
         shapes = {"kmer_ref": (nr, torch.int32, np.uint32), "kmer_first": (nr + 1, torch.int64, np.uint64),

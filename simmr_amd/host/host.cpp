@@ -766,6 +766,11 @@ std::string usage() {
          "                            not with --devices\n"
          "            --fit-k <K>  k-mer size of --fit-model, 3 .. 10 [default: 7]\n"
          "            --fit-max-alt <N>  alternates kept per reference k-mer [default: 20]\n"
+         "            --fit-from-sam <FILE>  no simulation: fit the model of --fit-model from the alignments of a SAM file (plain text with\n"
+         "                            CIGAR and MD:Z; no BAM, no gzip), parsed, filtered and counted on the device; what was taken and\n"
+         "                            skipped goes to stderr; takes only --fit-model, --fit-k, --fit-max-alt, --single-reads and --device\n"
+         "                            (no genomes, no --output, not --devices)\n"
+         "            --single-reads  with --fit-from-sam: the reads are unpaired (no insert sizes are taken)\n"
          "            --depth <FILE>  coverage the run put on every sequence, as a TSV: genome_id sequence_id length covered depth_sum depth_max\n"
          "                            (read depth, mates counted separately; counted on the device from every range of the run;\n"
          "                             combines with --truth and --stats; not with --devices)\n"
@@ -798,6 +803,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
+  std::string first_other;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -822,6 +828,11 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
       return err->empty();
     };
     if (arg == "--help" || arg == "-h") { *help = true; return true; }
+    if (first_other.empty() && arg != "--fit-from-sam" && arg != "--fit-model" && arg != "--fit-k" && arg != "--fit-max-alt" &&
+        arg != "--single-reads" && arg != "--device")
+      first_other = arg;  // what --fit-from-sam does not take
+    if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
+    else if (arg == "--single-reads") a->single_reads = true;
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
     else if (arg == "--genome-file") { if (!need(&v)) return false; a->genome_file = v; }
     else if (arg == "--output") { if (!need(&v)) return false; a->output = v; }
@@ -909,6 +920,16 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--uniform-start") a->uniform_start = true;
     else { *err = "Found argument '" + arg + "' which wasn't expected"; return false; }
   }
+  if (!a->fit_from_sam.empty()) {  // no simulation: nothing of a run is asked for, and none of its flags is taken
+    if (!a->devices.empty()) { *err = "--fit-from-sam does not combine with --devices: use --device"; return false; }
+    if (!first_other.empty()) {
+      *err = "--fit-from-sam runs no simulation: it takes only --fit-model, --fit-k, --fit-max-alt, --single-reads and --device ('" + first_other + "' given)";
+      return false;
+    }
+    if (a->fit_model.empty()) { *err = "--fit-from-sam needs --fit-model"; return false; }
+    return true;
+  }
+  if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }
   if (a->sam_sorted && a->sam.empty()) { *err = "--sam-sorted needs --sam"; return false; }
   if (a->sam_sorted && !a->devices.empty()) { *err = "--sam-sorted does not combine with --devices: use --device"; return false; }
   if (!a->strain_sites.empty() && !a->with_ani) { *err = "--strain-sites needs --with-ani"; return false; }

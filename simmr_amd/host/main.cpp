@@ -850,12 +850,81 @@ struct Engines {  // released on every way out of run_main
   ~Engines() { for (simmr_engine* en : v) simmr_engine_destroy(en); }
 };
 
+// `--fit-from-sam FILE --fit-model OUT`: no simulation.  The file goes up in pieces cut at the last newline (a line longer than a
+// piece makes the piece grow), every piece is one simmr_fit_add_sam; then the plan and the model file of --fit-model.  What was
+// taken and skipped is printed in the manner of the reference's "Skipped N alignments ..." lines (simmrd/src/main.rs:259-290).
+static constexpr size_t SAM_PIECE = 64u << 20;
+static int run_fit_from_sam(const CliArgs& args) {
+  FILE* f = fopen(args.fit_from_sam.c_str(), "rb");
+  if (!f) return die("--fit-from-sam: cannot open " + args.fit_from_sam);
+  struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  SideOutputs side(args);
+  if (is_regular_file(args.fit_model)) remove(args.fit_model.c_str());
+  if (simmr_fit_reset(eng, args.fit_k, args.fit_max_alt, SideOutputs::FIT_PAIR_CAPACITY) != SIMMR_OK) return die(std::string("--fit-model: ") + simmr_last_error(eng));
+  info("Parsing " + args.fit_from_sam);
+  const uint32_t n_sets = args.single_reads ? 1u : 2u;
+  GrowBuf dev;
+  std::vector<uint8_t> piece;
+  size_t have = 0;  // bytes of `piece` read and not yet added: the open last line of the piece before
+  float device_ms = 0;
+  for (bool eof = false; !eof;) {
+    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
+    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
+    if (got < SAM_PIECE) {
+      if (ferror(f)) return die("--fit-from-sam: cannot read " + args.fit_from_sam);
+      eof = true;
+    }
+    have += got;
+    size_t cut = have;  // at the end of the file the last line may lack its newline
+    if (!eof) {
+      while (cut > 0 && piece[cut - 1] != '\n') cut--;
+      if (cut == 0) continue;  // one line longer than the piece: read on
+    }
+    if (cut > SIMMR_FIT_SAM_MAX_BYTES) return die("--fit-from-sam: a line of " + args.fit_from_sam + " is longer than one add takes");
+    if (cut > 0) {
+      uint8_t* d = dev.room(cut);
+      if (!d) return die("--fit-from-sam: device allocation failed");
+      if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die("--fit-from-sam: copy to the device failed");
+      if (simmr_fit_add_sam(eng, d, cut, n_sets) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
+      float ms = 0;  // (synchronises: the buffer is free for the next piece)
+      if (simmr_last_fit_ms(eng, &ms) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
+      device_ms += ms;
+    }
+    memmove(piece.data(), piece.data() + cut, have - cut);
+    have -= cut;
+  }
+  simmr_fit_sam_counts c{};
+  if (simmr_fit_sam_counts_read(eng, &c) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Read " + n(c.lines) + " lines: " + n(c.header_lines) + " header lines, " + n(c.records) + " alignments");
+  info("Using " + n(c.taken_alignment) + " alignments (" + n(c.taken_quality) + " for read lengths and qualities)");
+  info("Skipped " + n(c.skip_no_sequence) + " alignments that were missing sequences");
+  info("Skipped " + n(c.skip_secondary) + " alignments that were secondary or supplementary");
+  info("Skipped " + n(c.skip_too_long) + " alignments with reads longer than " + n(SIMMR_FIT_MAX_L) + " bases");
+  info("Skipped " + n(c.skip_unmapped) + " alignments where the read was unmapped");
+  info("Skipped " + n(c.skip_mapq0) + " alignments with MAPQ == 0");
+  info("Skipped " + n(c.skip_mate_unmapped) + " alignments where the mate was unmapped");
+  info("Skipped " + n(c.skip_no_md) + " alignments without an MD tag");
+  info("Skipped " + n(c.skip_insert) + " alignments with an insert size above " + n(SIMMR_FIT_MAX_INSERT));
+  info("Skipped " + n(c.skip_cigar_op) + " alignments with a CIGAR of * or an operation other than M = X I D S H");
+  info("Skipped " + n(c.skip_inconsistent) + " alignments whose CIGAR, MD and sequence disagree");
+  if (!side.finish_fit(eng)) return die(side.err);
+  info("Wrote sequence error model to " + args.fit_model);
+  return 0;
+}
+
+
 static int run_main(int argc, char** argv) {
   CliArgs args;
   std::string err;
   bool help = false;
   if (!parse_cli_args(argc, argv, &args, &err, &help)) { fprintf(stderr, "error: %s\n\n%s", err.c_str(), usage().c_str()); return 2; }
   if (help) { fputs(usage().c_str(), stdout); return 0; }
+  if (!args.fit_from_sam.empty()) return run_fit_from_sam(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

@@ -348,6 +348,8 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string fit_model;      // --fit-model FILE: an error model fitted from the run (simmr_fit_add over every range, one plan) as simmrd writes it
   uint32_t fit_k = 7;         // --fit-k K: its k-mer size, 3 .. 10
   uint32_t fit_max_alt = 20;  // --fit-max-alt N: alternates kept per reference k-mer
+  std::string fit_from_sam;   // --fit-from-sam FILE: no simulation; the model of --fit-model from the records of a SAM file (simmr_fit_add_sam)
+  bool single_reads = false;  // --single-reads: with --fit-from-sam, the file holds unpaired reads (n_sets 1: no insert sizes)
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions

@@ -2,8 +2,9 @@
 """Registers, scratch, LDS and occupancy of every kernel of libsimmr_hip.so, as the compiler reports them
 (`-Rpass-analysis=kernel-resource-usage`, gfx950 cross-compile: runs without a GPU).
 
-    python3 tools/resource_usage.py                 # table on stdout
+    python3 tools/resource_usage.py                 # table on stdout: engine.hip and the SAM fit's unit, fit_sam.hip
     python3 tools/resource_usage.py --json out.json # the same as JSON
+    python3 tools/resource_usage.py --source fit_sam.hip   # another translation unit (fit.hip, fit_sam.hip, depth.hip, ...)
 
 tests/test_resource_guard.py asserts the documented figures of the kernels the bench lines run against this."""
 import json
@@ -45,7 +46,8 @@ def collect(extra_flags=(), source="engine.hip"):
 
 
 def main():
-    ks = collect()
+    units = [sys.argv[sys.argv.index("--source") + 1]] if "--source" in sys.argv else ["engine.hip", "fit_sam.hip"]
+    ks = [k for u in units for k in collect(source=u)]
     if "--json" in sys.argv:
         Path(sys.argv[sys.argv.index("--json") + 1]).write_text(json.dumps(ks, indent=1))
     print(f"{len(ks)} kernels")
