@@ -873,6 +873,87 @@ int simmr_sam_sort_emit(simmr_engine* e, const simmr_reads_out* reads, const sim
  * simmr_sam_sort_emit after it, if any.  Synchronises the stream. */
 int simmr_last_sam_sort_ms(simmr_engine* e, float* ms);
 
+/* ---- the true alignments as BAM records, and BGZF framing of any device buffer ------------------------------------------------
+ * The binary form of the SAM line above, in read order: every field but QNAME and MD is a fixed-width integer, the bases are
+ * packed two to a byte and the qualities are raw Phred bytes, so a record is about half the bytes of its line and a consumer
+ * parses no decimal.  Two orthogonal pieces: simmr_bam_* writes the records of SAM spec 4.2 back to back, unframed;
+ * simmr_bgzf_frame wraps any device buffer into BGZF blocks.  The blocks hold STORED deflate blocks (compression level 0, what
+ * `samtools view -u` writes): every htslib tool reads them, samtools sort / index and bgzip recompress them.  Deflate is
+ * deliberately out of scope.  A BAM file is BGZF(header of the host + records) followed by the 28 bytes SIMMR_BGZF_EOF.
+ *
+ * Record of read r, little-endian, no alignment assumed.  lo, hi, L, rev, FLAG, the mate fields and the MD string are those of
+ * the SAM record above; nd = the number of decimal digits of read_id[r]; n = edit_off[r + 1] - edit_off[r].
+ *   offset  bytes  field
+ *        0      4  block_size   the bytes of the record that follow this field
+ *        4      4  refID        the index of (genome[r], contig[r]) among the contigs of `names`, flattened entry by entry: the
+ *                               `row` of simmr_sam_sort_*, the order of the @SQ lines
+ *        8      4  pos          lo (0-based)
+ *       12      1  l_read_name  nd + 1
+ *       13      1  mapq         255
+ *       14      2  bin          reg2bin(lo, L ? hi : lo + 1) of SAM spec 5.3, the 16 bits the field holds
+ *       16      2  n_cigar_op   L ? 1 : 0
+ *       18      2  flag         FLAG
+ *       20      4  l_seq        L
+ *       24      4  next_refID   paired: refID; else -1
+ *       28      4  next_pos     paired: lo of read r^1; else -1
+ *       32      4  tlen         paired: the signed span of the SAM rule; else 0
+ *       36  nd + 1 read_name    read_id[r] in decimal, NUL
+ *        .   0 | 4 cigar        L << 4 | 0 (the M operation); no word for L == 0
+ *        . (L+1)/2 seq          the bytes SAM shows (forward strand, every byte outside ACGTN as N), 4 bits each: A 1, C 2, G 4, T 8,
+ *                               N 15; the earlier base in the high nibble; the low nibble of a last odd byte is 0
+ *        .      L  qual         max(byte, 33) - 33 per base, back to front for a rev read
+ *        .  4 | 5  NM           'N' 'M' 'C' and n in one byte for n <= 255, else 'N' 'M' 'S' and n in two bytes (n <= L <= 65 535)
+ *        .      .  MD           'M' 'D' 'Z', the MD string, NUL
+ * Both layouts are read; reads->qual_offset must be 33.
+ *
+ * The records are a function of the inputs alone: sizes are counted and scanned, records written at their offsets; no atomic
+ * hands out space and launch geometry changes no byte.  The size pass and the write pass are one routine.  No store of record r
+ * leaves its own bytes of dst even when the columns were changed between the plan and the emit, and no load leaves a read's own
+ * bytes of seq[] / qual[] in either layout.
+ * Limits: read order only (samtools sort takes the stream), no @RG, no index. */
+
+/* simmr_sam_plan's arguments, checks and status codes; *record_bytes is the sum of the records' lengths.  On top of them: a read
+ * with max(start, end) >= 2^31 is refused on the device through the error word (SIMMR_EINVAL; pos and the read's end are int32),
+ * with nothing loaded or stored for it, and more than 2^31 - 1 name rows are SIMMR_ERANGE, decided on the host.  The state is
+ * the engine's own for BAM: a BAM plan and a SAM plan on one engine do not disturb each other. */
+int simmr_bam_plan(simmr_engine* e, const simmr_sam_names* names, const simmr_reads_out* reads,
+                   const simmr_truth_out* truth, uint64_t n_reads, int paired, uint64_t* record_bytes);
+/* simmr_sam_emit's arguments, checks and status codes (the plan meant is the last simmr_bam_plan): the n_reads records back to
+ * back in dst (DEVICE memory of at least record_bytes bytes), unframed.  Synchronises. */
+int simmr_bam_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_truth_out* truth,
+                   uint8_t* dst, uint64_t dst_capacity);
+/* HIP-event time (ms) of the last simmr_bam_plan's device work (size pass + scan) plus that of the simmr_bam_emit after it, if
+ * any.  Synchronises the stream. */
+int simmr_last_bam_ms(simmr_engine* e, float* ms);
+
+/* BGZF (SAM spec 4.1).  src is cut into blocks of 65 280 bytes (0xff00, htslib's figure), the last one shorter; block b of n
+ * source bytes starts at byte 65 311 b of dst and is n + 31 bytes:
+ *   offset  bytes
+ *        0      4  1f 8b 08 04       gzip: magic, deflate, FEXTRA
+ *        4      4  00 00 00 00       MTIME
+ *        8      2  00 ff             XFL, OS unknown
+ *       10      2  06 00             XLEN 6
+ *       12      4  'B' 'C' 02 00     the BGZF subfield, 2 bytes long
+ *       16      2  BSIZE             n + 30: the block's length - 1
+ *       18      1  01                one stored deflate block, the last (BFINAL 1, BTYPE 00)
+ *       19      2  LEN               n
+ *       21      2  ~LEN
+ *       23      n  the bytes
+ *   23 + n      4  CRC-32 of the bytes (zlib's: polynomial 0xEDB88320, start value and final xor 0xffffffff)
+ *   27 + n      4  ISIZE             n
+ * The end-of-file marker is a constant the caller appends, SIMMR_BGZF_EOF:
+ *   1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00 */
+#define SIMMR_BGZF_EOF_BYTES 28
+#define SIMMR_BGZF_EOF "\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00\x42\x43\x02\x00\x1b\x00\x03\x00\x00\x00\x00\x00\x00\x00\x00\x00"
+/* n_bytes + 31 * ceil(n_bytes / 65 280): what simmr_bgzf_frame writes for n_bytes.  Needs no engine. */
+uint64_t simmr_bgzf_bound(uint64_t n_bytes);
+/* Frames the n_bytes at src (DEVICE) into dst (DEVICE); *written = simmr_bgzf_bound(n_bytes).  A workgroup takes a block:
+ * every lane copies a segment of it and runs a table-driven CRC over it, and the lanes' CRCs are folded with multiplications
+ * by x^(8k) mod P.  Synchronises.  n_bytes == 0 writes nothing (*written = 0).  SIMMR_ERANGE, nothing written: dst_capacity is
+ * below the bound.  SIMMR_EINVAL: a NULL buffer, or src and dst overlap. */
+int simmr_bgzf_frame(simmr_engine* e, const uint8_t* src_device, uint64_t n_bytes, uint8_t* dst_device,
+                     uint64_t dst_capacity, uint64_t* written);
+
 /* ---- the true read-to-read overlaps as PAF: which reads of a run share reference bases, found and formatted on the device ------
  * Replaces nothing in the reference.  What overlappers (minimap2 -x ava-ont) and the overlap stage of long-read assemblers are
  * scored against: every pair of reads whose reference intervals share at least min_overlap bases, known here without aligning

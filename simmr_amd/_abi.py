@@ -336,6 +336,11 @@ SYMBOLS = {
     "simmr_sam_sort_plan": (C.c_int, [C.c_void_p, _P(SamNames), _P(ReadsOut), _P(TruthOut), C.c_uint64, C.c_int, _P(C.c_uint64)]),
     "simmr_sam_sort_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "simmr_last_sam_sort_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_bam_plan": (C.c_int, [C.c_void_p, _P(SamNames), _P(ReadsOut), _P(TruthOut), C.c_uint64, C.c_int, _P(C.c_uint64)]),
+    "simmr_bam_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut), C.c_void_p, C.c_uint64]),
+    "simmr_last_bam_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_bgzf_bound": (C.c_uint64, [C.c_uint64]),
+    "simmr_bgzf_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
     "simmr_overlap_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "simmr_overlap_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64]),
     "simmr_overlap_plan": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),

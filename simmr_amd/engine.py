@@ -456,6 +456,42 @@ class Engine:
         self._check(self.lib.simmr_last_sam_sort_ms(self._h, C.byref(ms)))
         return ms.value
 
+    # -- the true alignments as BAM records, and BGZF framing ------------------------------
+    def bam(self, reads: Reads, rnames, paired: bool, truth: Optional[Truth] = None, framed: bool = True):
+        """The BAM records of `reads` in read order (simmr_bam_plan + simmr_bam_emit) as a CUDA uint8 tensor: back to back,
+        or with `framed` their BGZF blocks (Engine.bgzf).  Arguments as Engine.sam().  A file is Engine.bgzf of
+        simmr_amd.sam.bam_header(...), these blocks, and simmr_amd.sam.BGZF_EOF."""
+        torch = _torch()
+        t = truth if truth is not None else self.truth(reads)
+        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
+                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        sn = self._sam_names(rnames)
+        pod = reads.pod()
+        total = C.c_uint64(0)
+        self._check(self.lib.simmr_bam_plan(self._h, C.byref(sn), C.byref(pod), C.byref(out), reads.n_reads,
+                                            1 if paired else 0, C.byref(total)))
+        rec = torch.empty(max(total.value, 1), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.simmr_bam_emit(self._h, C.byref(pod), C.byref(out), C.c_void_p(rec.data_ptr()), total.value))
+        return self.bgzf(rec[: total.value]) if framed else rec[: total.value]
+
+    def last_bam_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_bam_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def bgzf(self, data):
+        """The bytes of a contiguous CUDA uint8 tensor as BGZF blocks with stored deflate blocks (simmr_bgzf_frame), without the
+        end-of-file block (simmr_amd.sam.BGZF_EOF)."""
+        torch = _torch()
+        if data.dtype != torch.uint8 or not data.is_cuda or not data.is_contiguous():
+            raise ValueError("Engine.bgzf takes a contiguous CUDA uint8 tensor")
+        n = data.numel()
+        bound = self.lib.simmr_bgzf_bound(n)
+        dst = torch.empty(max(bound, 1), dtype=torch.uint8, device=self.device)
+        written = C.c_uint64(0)
+        self._check(self.lib.simmr_bgzf_frame(self._h, C.c_void_p(data.data_ptr()), n, C.c_void_p(dst.data_ptr()), bound, C.byref(written)))
+        return dst[: written.value]
+
     # -- the true read-to-read overlaps as PAF ------------------------------------------
     OVERLAP_COLUMNS = (("a", np.uint32), ("b", np.uint32), ("ref_start", np.uint64), ("ref_end", np.uint64), ("row", np.uint32))
 

@@ -751,6 +751,10 @@ std::string usage() {
          "            --sam-sorted    the file of --sam in coordinate order, under @HD SO:coordinate: the lines ascend by (@SQ index, POS),\n"
          "                            ties in read order, across every range of the run (each range is sorted on the device; several\n"
          "                            ranges are merged through a temporary file beside FILE); needs --sam; not with --devices\n"
+         "            --bam <FILE>    the same alignments as BAM, in read order: the header of --sam (unsorted) and one record per read, written\n"
+         "                            and framed into BGZF blocks on the device; the blocks are stored, not compressed (what samtools view -u\n"
+         "                            writes: samtools sort, samtools index after it, and bgzip recompress them); no index, no @RG; the\n"
+         "                            RNAME rules of --sam; combines with --sam and --truth; not with --devices\n"
          "            --overlaps <FILE>  the true read-to-read overlaps of the run as PAF: one record per pair of reads that share at least\n"
          "                            --min-overlap reference bases of one sequence, across every range of the run, found and formatted on\n"
          "                            the device; names as --sam's QNAME (the read id, /1 or /2 for pairs); columns 10 and 11 carry the\n"
@@ -874,6 +878,7 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--truth") { if (!file(&a->truth)) return false; }
     else if (arg == "--sam") { if (!file(&a->sam)) return false; }
     else if (arg == "--sam-sorted") a->sam_sorted = true;
+    else if (arg == "--bam") { if (!file(&a->bam)) return false; }
     else if (arg == "--overlaps") { if (!file(&a->overlaps)) return false; }
     else if (arg == "--min-overlap") { if (!uint(1, UINT64_MAX, " (at least 1)")) return false; a->min_overlap = u; }
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }

@@ -95,10 +95,11 @@ static bool device_truth(simmr_engine* eng, const simmr_reads_out* reads, uint64
   return true;
 }
 
-// `--sam`, before any device work: every sequence of the run's FASTA files gets its RNAME (the first word of its id; under
+// `--sam` / `--bam`, before any device work: every sequence of the run's FASTA files gets its RNAME (the first word of its id; under
 // --contiguous a genome is the one sequence "whole genome"), which has to be a SAM reference name that no other sequence of the
 // run has.  false with the one message that names the sequence.  A file that cannot be read is left to the loading code.
 static bool sam_check_names(const CliArgs& args, std::string* err) {
+  const std::string flag = args.sam.empty() ? "--bam: " : "--sam: ";
   std::vector<std::string> paths = args.genome;
   if (args.genome_file) {
     std::vector<GenomeRecord> records;
@@ -114,9 +115,9 @@ static bool sam_check_names(const CliArgs& args, std::string* err) {
     std::vector<std::string> ids = args.contiguous ? std::vector<std::string>{"whole genome"} : recs.ids;
     for (const std::string& id : ids) {
       const std::string rname = sam_rname(id), who = "sequence '" + id + "' of " + path;
-      if (!sam_rname_legal(rname)) { *err = "--sam: " + who + " gets the RNAME '" + rname + "', which is not a SAM reference name"; return false; }
+      if (!sam_rname_legal(rname)) { *err = flag + who + " gets the RNAME '" + rname + "', which is not a SAM reference name"; return false; }
       for (const auto& s : seen)
-        if (s.first == rname) { *err = "--sam: " + who + " gets the RNAME '" + rname + "', which " + s.second + " has already"; return false; }
+        if (s.first == rname) { *err = flag + who + " gets the RNAME '" + rname + "', which " + s.second + " has already"; return false; }
       seen.emplace_back(rname, who);
     }
   }
@@ -257,7 +258,7 @@ struct GrowBuf {
 // the text buffer of the drains: what one copy to the host moves, and what a window of --overlaps holds
 static constexpr size_t TEXT_CHUNK = 256u << 20;
 
-// The side outputs of a run: --truth, --sam, --overlaps, --stats, --fit-model, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
+// The side outputs of a run: --truth, --sam, --bam, --overlaps, --stats, --fit-model, --depth, --depth-track, --gold-assembly, --gold-regions and --strain-vcf.  They read the columns, so a run that wants one
 // takes the column route (the same bytes, include/simmr_hip.h).  A call that answers false leaves its message in `err`.
 struct SideOutputs {
   explicit SideOutputs(const CliArgs& args) : a(args) {}
@@ -282,27 +283,28 @@ struct SideOutputs {
   bool overlaps() const { return !a.overlaps.empty(); }
   bool vcf() const { return !a.strain_vcf.empty(); }
   bool sam() const { return !a.sam.empty(); }
+  bool bam() const { return !a.bam.empty(); }
   bool depth_files() const { return !a.depth.empty() || !a.depth_track.empty(); }
   bool gold() const { return !a.gold_assembly.empty() || !a.gold_regions.empty(); }
   bool depth() const { return depth_files() || gold(); }  // (the gold-standard assembly is read off the run's depth[])
   bool fit() const { return !a.fit_model.empty(); }
-  bool wanted() const { return !a.truth.empty() || sam() || overlaps() || !a.stats.empty() || fit() || depth() || vcf(); }
+  bool wanted() const { return !a.truth.empty() || sam() || bam() || overlaps() || !a.stats.empty() || fit() || depth() || vcf(); }
   bool fail(const char* flag, const std::string& what) { err = std::string(flag) + ": " + what; return false; }
   // true, with the message, if one of them is asked for together with --devices
   bool refuse_devices() {
-    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : fit() ? "--fit-model" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : sam() ? "--sam" : overlaps() ? "--overlaps" : nullptr;
+    const char* flag = !a.truth.empty() ? "--truth" : !a.stats.empty() ? "--stats" : fit() ? "--fit-model" : depth_files() ? "--depth" : !a.gold_assembly.empty() ? "--gold-assembly" : gold() ? "--gold-regions" : vcf() ? "--strain-vcf" : sam() ? "--sam" : bam() ? "--bam" : overlaps() ? "--overlaps" : nullptr;
     if (flag && !a.devices.empty()) err = std::string(flag) + " does not combine with --devices: use --device";
     return flag && !a.devices.empty();
   }
   // the old files go, the truth file gets its header line (every range appends its reads), the tables start at zero
   // (the genomes are staged: depth[] covers all of them)
   bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
-    for (const std::string* f : {&a.truth, &a.sam, &a.overlaps, &a.stats, &a.fit_model, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
+    for (const std::string* f : {&a.truth, &a.sam, &a.bam, &a.overlaps, &a.stats, &a.fit_model, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
       if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
     std::string e;
     if (overlaps() && simmr_overlap_reset(eng, run_paired ? 1 : 0) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
     if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
-    if (sam() && !begin_sam(genomes)) return false;
+    if ((sam() || bam()) && !begin_sam(eng, genomes)) return false;
     if (!a.stats.empty() && simmr_stats_reset(eng) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
     if (fit() && simmr_fit_reset(eng, a.fit_k, a.fit_max_alt, FIT_PAIR_CAPACITY) != SIMMR_OK) return fail("--fit-model", simmr_last_error(eng));
     // (--strain-vcf takes the sequences' lengths from the layout the depth reset records)
@@ -310,7 +312,7 @@ struct SideOutputs {
     return !vcf() || begin_pileup(eng);
   }
   // the names of the run's sequences as the device wants them, and the header: once, before the first range
-  bool begin_sam(const std::vector<Genome>& genomes) {
+  bool begin_sam(simmr_engine* eng, const std::vector<Genome>& genomes) {
     std::vector<uint64_t> lengths;
     for (size_t g = 0; g < genomes.size(); g++) {
       sam_genome.push_back((uint32_t)g);
@@ -318,10 +320,67 @@ struct SideOutputs {
       for (const Seq& q : genomes[g].sequence) { sam_names.push_back(sam_rname(q.id)); lengths.push_back(q.size); }
     }
     std::string text, e;
+    if (bam() && !begin_bam(eng, lengths)) return false;
+    if (!sam()) return true;
     if (!sam_header_text(sam_names, lengths, &text, &e, a.sam_sorted)) return fail("--sam", e);
     OutFile f(a.sam, false);
     f.append(text);
     return f.close(&e) || fail("--sam", e);
+  }
+  // --bam: the file's head — magic, the header text of --sam (read order), the references — built here, framed on the device
+  bool begin_bam(simmr_engine* eng, const std::vector<uint64_t>& lengths) {
+    std::string text, e, head;
+    if (!sam_header_text(sam_names, lengths, &text, &e, false)) return fail("--bam", e);
+    auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) head.push_back((char)(v >> (8 * k))); };
+    head += "BAM\1";
+    put32((uint32_t)text.size());
+    head += text;
+    put32((uint32_t)sam_names.size());
+    for (size_t k = 0; k < sam_names.size(); k++) {
+      if (lengths[k] >= (1ull << 31)) return fail("--bam", "sequence '" + sam_names[k] + "' has 2^31 bases or more: BAM's l_ref is an int32");
+      put32((uint32_t)sam_names[k].size() + 1u);
+      head.append(sam_names[k].c_str(), sam_names[k].size() + 1);
+      put32((uint32_t)lengths[k]);
+    }
+    DeviceMem mem;
+    uint8_t* src = nullptr;
+    if (!mem.alloc(&src, head.size()) || hipMemcpy(src, head.data(), head.size(), hipMemcpyHostToDevice) != hipSuccess) return fail("--bam", "copy to the device failed");
+    OutFile f(a.bam, false);
+    return bam_append_framed(eng, &mem, src, head.size(), &f) && (f.close(&e) || fail("--bam", e));
+  }
+  // n bytes of device memory as BGZF blocks (simmr_bgzf_frame), fetched and appended to the file
+  bool bam_append_framed(simmr_engine* eng, DeviceMem* mem, const uint8_t* src, uint64_t n, OutFile* f) {
+    const uint64_t bound = simmr_bgzf_bound(n);
+    uint8_t* blocks = nullptr;
+    uint64_t written = 0;
+    std::vector<uint8_t> h;
+    if (!mem->alloc(&blocks, bound)) return fail("--bam", "device allocation failed");
+    if (simmr_bgzf_frame(eng, src, n, blocks, bound, &written) != SIMMR_OK) return fail("--bam", simmr_last_error(eng));
+    if (!mem->fetch(&h, (const uint8_t*)blocks, written)) return fail("--bam", "copy back failed");
+    f->append(h.data(), h.size());
+    return true;
+  }
+  // the records of one range: plan, emit, frame, fetch, append
+  bool bam_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
+    std::vector<const char*> names;
+    for (const std::string& n : sam_names) names.push_back(n.c_str());
+    simmr_sam_names sn{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), names.data()};
+    uint64_t total = 0;
+    if (simmr_bam_plan(eng, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--bam", simmr_last_error(eng));
+    DeviceMem mem;
+    uint8_t* rec = nullptr;
+    if (!mem.alloc(&rec, total)) return fail("--bam", "device allocation failed");
+    if (simmr_bam_emit(eng, &reads, &t, rec, total) != SIMMR_OK) return fail("--bam", simmr_last_error(eng));
+    std::string e;
+    OutFile f(a.bam, true);
+    return bam_append_framed(eng, &mem, rec, total, &f) && (f.close(&e) || fail("--bam", e));
+  }
+  // the end-of-file block behind the last range's blocks
+  bool finish_bam() {
+    std::string e;
+    OutFile f(a.bam, true);
+    f.append(SIMMR_BGZF_EOF, SIMMR_BGZF_EOF_BYTES);
+    return f.close(&e) || fail("--bam", e);
   }
   // the alignment lines of one range, formatted on the device from its columns and truth columns, appended to the file
   bool sam_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
@@ -421,10 +480,11 @@ struct SideOutputs {
     if (overlaps() && simmr_overlap_add(eng, &reads, n_reads) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
     std::string e;
     qual_offset = reads.qual_offset;
-    if (a.truth.empty() && !sam()) return true;
-    DeviceMem mem;  // the truth columns on the device: --truth copies them out, --sam formats from them
+    if (a.truth.empty() && !sam() && !bam()) return true;
+    DeviceMem mem;  // the truth columns on the device: --truth copies them out, --sam and --bam format from them
     simmr_truth_out t{};
-    if (!device_truth(eng, &reads, n_reads, &mem, &t, a.truth.empty() ? nullptr : &truth, &e)) return fail(a.truth.empty() ? "--sam" : "--truth", e);
+    if (!device_truth(eng, &reads, n_reads, &mem, &t, a.truth.empty() ? nullptr : &truth, &e)) return fail(!a.truth.empty() ? "--truth" : sam() ? "--sam" : "--bam", e);
+    if (bam() && !bam_range(eng, reads, t, n_reads, paired)) return false;
     return !sam() || sam_range(eng, reads, t, n_reads, paired);
   }
   bool write_range(const std::vector<Genome>& genomes, const HostReads& h) {
@@ -493,6 +553,7 @@ struct SideOutputs {
     if (fit() && !finish_fit(eng)) return false;
     if (overlaps() && !finish_overlaps(eng)) return false;
     if (sam() && a.sam_sorted && !finish_sam_sorted()) return false;
+    if (bam() && !finish_bam()) return false;
     if (!a.stats.empty()) {
       auto st = std::make_unique<simmr_run_stats>();
       if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
@@ -928,7 +989,7 @@ static int run_main(int argc, char** argv) {
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);
-  if (side.sam() && !sam_check_names(args, &err)) return die(err);
+  if ((side.sam() || side.bam()) && !sam_check_names(args, &err)) return die(err);
   std::unique_ptr<ErrorProfile> eprofile = determine_error_profile(args, &err);  // main.rs:27
   if (!eprofile) return die(err);
   // main.rs:30-33

@@ -343,6 +343,7 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string truth;  // --truth FILE: per-read mismatch counts and edit lists (simmr_truth_plan / simmr_truth_emit) as a TSV
   bool sam_sorted = false;  // --sam-sorted: the file of --sam in coordinate order (simmr_sam_sort_plan / simmr_sam_sort_emit, a merge of the ranges)
   std::string sam;    // --sam FILE: the true alignments as SAM (simmr_sam_plan / simmr_sam_emit on every range's columns, the header from the host)
+  std::string bam;    // --bam FILE: the same alignments as BAM in read order (simmr_bam_plan / simmr_bam_emit on every range's columns, framed by simmr_bgzf_frame: stored blocks; the header from the host)
   std::string overlaps;       // --overlaps FILE: the true read-to-read overlaps of the run as PAF (simmr_overlap_add over every range, one plan, drained by windows)
   uint64_t min_overlap = 1;   // --min-overlap N: shared reference bases from which two reads overlap
   std::string fit_model;      // --fit-model FILE: an error model fitted from the run (simmr_fit_add over every range, one plan) as simmrd writes it
