@@ -910,7 +910,7 @@ int simmr_last_sam_sort_ms(simmr_engine* e, float* ms);
  * hands out space and launch geometry changes no byte.  The size pass and the write pass are one routine.  No store of record r
  * leaves its own bytes of dst even when the columns were changed between the plan and the emit, and no load leaves a read's own
  * bytes of seq[] / qual[] in either layout.
- * Limits: read order only (samtools sort takes the stream), no @RG, no index. */
+ * Limits: read order and no index here (simmr_bam_sort_* and simmr_bai_* below give coordinate order and a .bai), no @RG. */
 
 /* simmr_sam_plan's arguments, checks and status codes; *record_bytes is the sum of the records' lengths.  On top of them: a read
  * with max(start, end) >= 2^31 is refused on the device through the error word (SIMMR_EINVAL; pos and the read's end are int32),
@@ -953,6 +953,67 @@ uint64_t simmr_bgzf_bound(uint64_t n_bytes);
  * below the bound.  SIMMR_EINVAL: a NULL buffer, or src and dst overlap. */
 int simmr_bgzf_frame(simmr_engine* e, const uint8_t* src_device, uint64_t n_bytes, uint8_t* dst_device,
                      uint64_t dst_capacity, uint64_t* written);
+
+/* ---- the BAM records in coordinate order, and the BAI index of a coordinate-sorted record stream ------------------------------
+ * What a genome browser, a region query and a caller open directly.  The records are those of simmr_bam_emit, byte for byte; only
+ * their places differ: the key and the order are those of simmr_sam_sort_* (key = row << 40 | lo, ties in read order, the stable
+ * radix sort of that unit), with its limits and its refusal of a read that ends behind the staged length of its contig.
+ *
+ * The state of these calls is an object of its own, created on an engine and destroyed BEFORE the engine; its calls run on the
+ * engine's stream and leave their messages with the engine (simmr_last_error).  One object holds one sorted plan and one index
+ * plan; they do not disturb the engine's own BAM and SAM plans. */
+typedef struct simmr_bam_sort simmr_bam_sort;
+int simmr_bam_sort_create(simmr_engine* e, simmr_bam_sort** out);
+void simmr_bam_sort_destroy(simmr_bam_sort* h);
+/* simmr_bam_plan's arguments, checks and status codes, with the limits of simmr_sam_sort_plan on top; *record_bytes is what
+ * simmr_bam_plan returns for the same input.  Sizes the records, sorts the reads, scans the sizes in sorted order. */
+int simmr_bam_sort_plan(simmr_bam_sort* h, const simmr_sam_names* names, const simmr_reads_out* reads,
+                        const simmr_truth_out* truth, uint64_t n_reads, int paired, uint64_t* record_bytes);
+/* simmr_bam_emit's arguments, checks and status codes (the plan meant is the handle's last simmr_bam_sort_plan): the n_reads
+ * records in coordinate order, back to back in dst, unframed.  Every store of the i-th record is bounded by its planned length.
+ * Three optional outputs (DEVICE, may be NULL), all in the order written — what a merge of several sorted ranges and
+ * simmr_bai_plan take:
+ *   key_out      n_reads entries: the key (row << 40 | lo) of the i-th record, as simmr_sam_sort_emit gives it;
+ *   rec_off_out  n_reads + 1 entries: the offset of the i-th record in dst, and record_bytes behind the last;
+ *   end_out      n_reads entries: the exclusive end of the reference interval from which the record's own `bin` field was
+ *                computed (lo + L, or lo + 1 for a read without bases), so an index built from it cannot disagree with the record. */
+int simmr_bam_sort_emit(simmr_bam_sort* h, const simmr_reads_out* reads, const simmr_truth_out* truth,
+                        uint8_t* dst, uint64_t dst_capacity, uint64_t* key_out, uint64_t* rec_off_out, uint32_t* end_out);
+/* HIP-event time (ms) of the handle's last simmr_bam_sort_plan's device work plus that of the simmr_bam_sort_emit after it, if
+ * any.  Synchronises the stream. */
+int simmr_last_bam_sort_ms(simmr_bam_sort* h, float* ms);
+/* The staged length of every row of the handle's last simmr_bam_sort_plan (HOST, capacity entries; *n_rows = the rows), in the
+ * order of the @SQ lines: what the BAM header needs.  SIMMR_ERANGE (with *n_rows set): capacity < the rows. */
+int simmr_bam_sort_ref_lengths(simmr_bam_sort* h, uint64_t* lengths, uint64_t capacity, uint64_t* n_rows);
+
+/* The BAI index (SAM spec 5.2) of a coordinate-sorted record stream, built from columns: the file is never read back.
+ * Input (DEVICE): key[n] = row << 40 | lo ascending, end[n] (exclusive, lo < end <= 2^29), rec_off[n + 1] non-decreasing — the
+ * outputs of simmr_bam_sort_emit, or a merge of several — and on the host n_ref, ref_len[n_ref] (may be NULL: lengths unknown) and
+ * `base`, the uncompressed bytes in front of record 0 (the BAM header).
+ * Contract on the caller: header and records are framed as ONE stream by simmr_bgzf_frame, so every block but the last holds
+ * 65 280 source bytes and the virtual offset of uncompressed position p is ((p / 65280) * 65311) << 16 | (p % 65280), also for p =
+ * the stream's length (the EOF block).
+ * The file is a pure function of the input:
+ *   magic "BAI\1", n_ref; a reference without records has n_bin = 0 and n_intv = 0;
+ *   bins      ascending by bin number; a record's bin is reg2bin(lo, end);
+ *   chunks    of a bin: the maximal runs of records consecutive in file order that fall into the bin, in file order, each from
+ *             the virtual offset of its first record's start to that of its last record's end.  Chunks are not merged across
+ *             a gap (htslib merges chunks that share a block; the specification does not ask for it);
+ *   bin 37450 behind the real bins of a reference with records (n_bin counts it): two chunks, (virtual offset of the
+ *             reference's first record, that behind its last) and (n_mapped, n_unmapped = 0);
+ *   linear    n_intv = 1 + ((largest end - 1) >> 14); ioffset[w] = the smallest virtual offset of the start of a record that
+ *             overlaps window w of 16 384 bases; a window no record overlaps takes the value of the window before it, 0 at the front;
+ *   n_no_coor 0.
+ * ref_len == NULL: no length is checked — a contig of 2^29 bases or more is then NOT refused as such, only a record that ends
+ * beyond 2^29 is; a caller that knows the lengths passes them.
+ * simmr_bai_plan: *bai_bytes = the file's size.  SIMMR_ERANGE: a ref_len of 2^29 or more (CSI is not written), a record that
+ * ends beyond 2^29, a stream whose compressed size leaves the 48 bits of a virtual offset, 2^31 records or more, more than 2^24
+ * references.  SIMMR_EINVAL: keys that descend, rec_off that decreases, a row >= n_ref, an empty interval — found on the device.
+ * simmr_bai_emit writes the file to dst (DEVICE) from the columns of the plan, which must still be there and unchanged; every
+ * store is bounded by the plan's layout.  SIMMR_ESTATE without a plan, SIMMR_ERANGE for dst_capacity < bai_bytes.  Both synchronise. */
+int simmr_bai_plan(simmr_bam_sort* h, const uint64_t* key, const uint32_t* end, const uint64_t* rec_off, uint64_t n,
+                   uint64_t n_ref, const uint64_t* ref_len, uint64_t base, uint64_t* bai_bytes);
+int simmr_bai_emit(simmr_bam_sort* h, uint8_t* dst, uint64_t dst_capacity);
 
 /* ---- the true read-to-read overlaps as PAF: which reads of a run share reference bases, found and formatted on the device ------
  * Replaces nothing in the reference.  What overlappers (minimap2 -x ava-ont) and the overlap stage of long-read assemblers are

@@ -341,6 +341,14 @@ SYMBOLS = {
     "simmr_last_bam_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
     "simmr_bgzf_bound": (C.c_uint64, [C.c_uint64]),
     "simmr_bgzf_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "simmr_bam_sort_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_bam_sort_destroy": (None, [C.c_void_p]),
+    "simmr_bam_sort_plan": (C.c_int, [C.c_void_p, _P(SamNames), _P(ReadsOut), _P(TruthOut), C.c_uint64, C.c_int, _P(C.c_uint64)]),
+    "simmr_bam_sort_emit": (C.c_int, [C.c_void_p, _P(ReadsOut), _P(TruthOut), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "simmr_last_bam_sort_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_bam_sort_ref_lengths": (C.c_int, [C.c_void_p, _P(C.c_uint64), C.c_uint64, _P(C.c_uint64)]),
+    "simmr_bai_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, _P(C.c_uint64), C.c_uint64, _P(C.c_uint64)]),
+    "simmr_bai_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_overlap_reset": (C.c_int, [C.c_void_p, C.c_int]),
     "simmr_overlap_add": (C.c_int, [C.c_void_p, _P(ReadsOut), C.c_uint64]),
     "simmr_overlap_plan": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),

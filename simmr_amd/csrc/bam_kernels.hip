@@ -1,5 +1,6 @@
 // bam_kernels.hip — the true alignments as BAM records, and BGZF framing of any device buffer (include/simmr_hip.h:
-// simmr_bam_*, simmr_bgzf_*) on gfx950.  Included by bam.hip alone, a translation unit of libsimmr_hip.so of its own.  What a
+// simmr_bam_*, simmr_bgzf_*) on gfx950.  Included by bam.hip, a translation unit of libsimmr_hip.so of its own (and, without
+// its kernels, by bam_index_kernels.hip: the same records in coordinate order).  What a
 // read is, which reads are refused, the row scan, the bounded stores and the scans' bodies are those of sam_kernels.hip
 // (included without its kernels): a BAM record shows the fields of the SAM line of the same read, as integers.
 //
@@ -117,10 +118,12 @@ SIMMR_DEV SamRead bam_open(const SamReads& rd, const SamEdits& ed, const SamName
 
 // ---- a record: its length (WRITE == false) or its bytes (WRITE == true) ------------------------------------------------
 // Called by all 16 lanes of a row for read r; returns the record's bytes (0 for a refused read) in every lane.  The record is
-// bytes off[r] .. off[r + 1] of dst.
+// bytes off[place] .. off[place + 1] of dst: place == r in read order; the ordered writer of bam_index_kernels.hip gives the
+// read's place in coordinate order.
 template <bool WRITE>
-SIMMR_DEV uint32_t bam_record(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t n_reads, uint32_t paired,
-                              uint32_t sub, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst, uint32_t* __restrict__ err) {
+SIMMR_DEV uint32_t bam_record(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t place, uint64_t n_reads,
+                              uint32_t paired, uint32_t sub, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst,
+                              uint32_t* __restrict__ err) {
   const SamRead R = bam_open(rd, ed, nm, r, n_reads, paired, err, sub == 0u);
   if (!R.good) return 0u;
   const uint32_t L = R.L, rev = R.rev, n = R.n;
@@ -132,7 +135,7 @@ SIMMR_DEV uint32_t bam_record(const SamReads& rd, const SamEdits& ed, const SamN
   uint32_t room = 0;
   uint8_t* rec = nullptr;
   if (WRITE) {
-    const uint64_t o0 = off[r], o1 = off[r + 1];
+    const uint64_t o0 = off[place], o1 = off[place + 1];
     room = (o1 >= o0 && o1 - o0 <= 0xffffffffull) ? (uint32_t)(o1 - o0) : 0u;
     rec = dst + o0;
     // ---- the fixed fields, read_name, cigar and the tags' fixed bytes: a piece per lane
@@ -246,6 +249,8 @@ SIMMR_DEV uint32_t bam_record(const SamReads& rd, const SamEdits& ed, const SamN
   return md0 + cursor;
 }
 
+// BAM_ROUTINES_ONLY: the routines without the five kernels, for bam_index_kernels.hip (the sorted writer and the index)
+#ifndef BAM_ROUTINES_ONLY
 // ---- sizes ----------------------------------------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(256)
 k_bam_size(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, uint32_t* __restrict__ len,
@@ -257,7 +262,7 @@ k_bam_size(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_r
     uint32_t acc = 0;  // (a record is below 2^20 bytes: 64 of them fit)
     for (uint32_t it = 0; it < SAM_CHUNK / SAM_WG_READS; it++) {
       const uint64_t r = chunk * SAM_CHUNK + it * SAM_WG_READS + row;
-      const uint32_t bytes = bam_record<false>(rd, ed, nm, r, n_reads, paired, sub, nullptr, nullptr, err);
+      const uint32_t bytes = bam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, err);
       if (sub == 0u && r < n_reads) len[r] = bytes;
       acc += bytes;
     }
@@ -291,8 +296,9 @@ k_bam_write(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_
   const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
   const uint64_t n_batches = (n_reads + SAM_WG_READS - 1u) / SAM_WG_READS;
   for (uint64_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x)
-    (void)bam_record<true>(rd, ed, nm, batch * SAM_WG_READS + row, n_reads, paired, sub, off, dst, err);
+    (void)bam_record<true>(rd, ed, nm, batch * SAM_WG_READS + row, batch * SAM_WG_READS + row, n_reads, paired, sub, off, dst, err);
 }
+#endif  // BAM_ROUTINES_ONLY
 
 // ---- BGZF -------------------------------------------------------------------------------------------------------------
 struct BgzfTables {            // device memory, made on the host (bgzf_tables.hpp)
@@ -316,6 +322,7 @@ SIMMR_DEV uint32_t bgzf_crc_word(const uint32_t* t, uint32_t c, uint32_t w) {
   return t[768u + (c & 0xffu)] ^ t[512u + ((c >> 8) & 0xffu)] ^ t[256u + ((c >> 16) & 0xffu)] ^ t[c >> 24];
 }
 
+#ifndef BAM_ROUTINES_ONLY
 extern "C" __global__ void __launch_bounds__(BGZF_LANES)
 k_bgzf_frame(const uint8_t* __restrict__ src, uint64_t n_bytes, uint8_t* __restrict__ dst, const BgzfTables tb) {
   __shared__ uint32_t table[4u * 256u];
@@ -381,5 +388,6 @@ k_bgzf_frame(const uint8_t* __restrict__ src, uint64_t n_bytes, uint8_t* __restr
     __syncthreads();  // fold[] and last_crc are the next block's
   }
 }
+#endif  // BAM_ROUTINES_ONLY
 
 }  // namespace simmr

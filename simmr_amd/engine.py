@@ -154,6 +154,9 @@ class Engine:
     # -- lifetime ---------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
+            if getattr(self, "_bam_sort", None):  # (the sorted-BAM state lives on the engine: it goes first)
+                self.lib.simmr_bam_sort_destroy(self._bam_sort)
+                self._bam_sort = None
             self.lib.simmr_engine_destroy(self._h)  # synchronises the device before it frees: enqueued adds have read their texts
             self._h = None
             self._fit_sam_texts = []
@@ -491,6 +494,80 @@ class Engine:
         written = C.c_uint64(0)
         self._check(self.lib.simmr_bgzf_frame(self._h, C.c_void_p(data.data_ptr()), n, C.c_void_p(dst.data_ptr()), bound, C.byref(written)))
         return dst[: written.value]
+
+    # -- the BAM records in coordinate order, and the BAI index ---------------------------
+    def _bam_sort_handle(self):
+        """the state object of simmr_bam_sort_* / simmr_bai_*, made on first use and destroyed by close() before the engine"""
+        if getattr(self, "_bam_sort", None) is None:
+            h = C.c_void_p()
+            self._check(self.lib.simmr_bam_sort_create(self._h, C.byref(h)))
+            self._bam_sort = h
+        return self._bam_sort
+
+    def bam_sorted(self, reads: Reads, rnames, paired: bool, truth: Optional[Truth] = None, index: bool = True):
+        """A coordinate-sorted BAM and its BAI index (simmr_bam_sort_plan / _emit, simmr_bgzf_frame, simmr_bai_plan / _emit) as
+        two CUDA uint8 tensors (blocks, bai).  `blocks` holds simmr_amd.sam.bam_header(..., "coordinate") and the records of
+        Engine.bam() in the order of Engine.sam_sorted(), framed as ONE stream: blocks + simmr_amd.sam.BGZF_EOF is the file,
+        `bai` its index (None with index=False).  Arguments as Engine.sam()."""
+        from . import sam as _sam_py
+        torch = _torch()
+        t = truth if truth is not None else self.truth(reads)
+        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
+                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        h = self._bam_sort_handle()
+        sn = self._sam_names(rnames)
+        pod = reads.pod()
+        n = reads.n_reads
+        total = C.c_uint64(0)
+        self._check(self.lib.simmr_bam_sort_plan(h, C.byref(sn), C.byref(pod), C.byref(out), n, 1 if paired else 0, C.byref(total)))
+        flat = [str(name) for x in rnames for name in x[1]]
+        lens = (C.c_uint64 * max(len(flat), 1))()
+        n_rows = C.c_uint64(0)
+        self._check(self.lib.simmr_bam_sort_ref_lengths(h, lens, len(flat), C.byref(n_rows)))
+        lengths = [int(lens[i]) for i in range(n_rows.value)]
+        header = _sam_py.bam_header(flat, lengths, "coordinate")
+        base = len(header)
+        stream = torch.empty(base + total.value, dtype=torch.uint8, device=self.device)
+        stream[:base] = torch.frombuffer(bytearray(header), dtype=torch.uint8).to(self.device)
+        key = torch.empty(max(n, 1), dtype=torch.int64, device=self.device)
+        end = torch.empty(max(n, 1), dtype=torch.int32, device=self.device)
+        rec_off = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        self._check(self.lib.simmr_bam_sort_emit(h, C.byref(pod), C.byref(out), C.c_void_p(stream.data_ptr() + base), total.value,
+                                                 C.c_void_p(key.data_ptr()), C.c_void_p(rec_off.data_ptr()), C.c_void_p(end.data_ptr())))
+        blocks = self.bgzf(stream)
+        if not index:
+            return blocks, None
+        return blocks, self.bai(key[:n], end[:n], rec_off, len(flat), base, ref_len=lengths)
+
+    def last_bam_sort_ms(self) -> float:
+        ms = C.c_float()
+        if getattr(self, "_bam_sort", None) is None:
+            raise SimmrError(_abi.ESTATE, "no simmr_bam_sort_plan yet")
+        self._check(self.lib.simmr_last_bam_sort_ms(self._bam_sort, C.byref(ms)))
+        return ms.value
+
+    def bai(self, key, end, rec_off, n_ref: int, base: int, ref_len=None):
+        """The BAI index (simmr_bai_plan + simmr_bai_emit) of a coordinate-sorted record stream held as CUDA columns: key (int64,
+        row << 40 | lo, ascending), end (int32, exclusive), rec_off (int64, one entry more: the records' offsets behind the
+        `base` uncompressed bytes of the header).  The stream must have been framed as one (Engine.bgzf of header + records).
+        `ref_len`: the references' lengths if known (one of 2^29 bases or more is refused).  Returns a CUDA uint8 tensor."""
+        torch = _torch()
+        n = int(key.numel())
+        for col, dt, m in ((key, torch.int64, n), (end, torch.int32, n), (rec_off, torch.int64, n + 1)):
+            if col.dtype != dt or not col.is_cuda or not col.is_contiguous() or col.numel() != m:
+                raise ValueError("Engine.bai takes contiguous CUDA columns: key int64[n], end int32[n], rec_off int64[n + 1]")
+        lens = None
+        if ref_len is not None:
+            if len(ref_len) != n_ref:
+                raise ValueError("ref_len has one entry per reference")
+            lens = (C.c_uint64 * max(n_ref, 1))(*[int(x) for x in ref_len])
+        h = self._bam_sort_handle()
+        total = C.c_uint64(0)
+        self._check(self.lib.simmr_bai_plan(h, C.c_void_p(key.data_ptr()) if n else None, C.c_void_p(end.data_ptr()) if n else None,
+                                            C.c_void_p(rec_off.data_ptr()), n, int(n_ref), lens, int(base), C.byref(total)))
+        dst = torch.empty(total.value, dtype=torch.uint8, device=self.device)
+        self._check(self.lib.simmr_bai_emit(h, C.c_void_p(dst.data_ptr()), total.value))
+        return dst
 
     # -- the true read-to-read overlaps as PAF ------------------------------------------
     OVERLAP_COLUMNS = (("a", np.uint32), ("b", np.uint32), ("ref_start", np.uint64), ("ref_end", np.uint64), ("row", np.uint32))

@@ -755,6 +755,11 @@ std::string usage() {
          "                            and framed into BGZF blocks on the device; the blocks are stored, not compressed (what samtools view -u\n"
          "                            writes: samtools sort, samtools index after it, and bgzip recompress them); no index, no @RG; the\n"
          "                            RNAME rules of --sam; combines with --sam and --truth; not with --devices\n"
+         "            --bam-sorted    the file of --bam in coordinate order, under @HD SO:coordinate, and its BAI index written beside it as\n"
+         "                            FILE.bai (--bam-index <FILE> names another place): sorted and indexed on the device, across every\n"
+         "                            range of the run (several ranges are merged through a temporary file beside FILE); a genome browser\n"
+         "                            or a region query opens the pair directly; the blocks are stored, not compressed; every sequence\n"
+         "                            stays below 2^29 bases (the reach of a BAI index; no CSI); needs --bam; not with --devices\n"
          "            --overlaps <FILE>  the true read-to-read overlaps of the run as PAF: one record per pair of reads that share at least\n"
          "                            --min-overlap reference bases of one sequence, across every range of the run, found and formatted on\n"
          "                            the device; names as --sam's QNAME (the read id, /1 or /2 for pairs); columns 10 and 11 carry the\n"
@@ -879,6 +884,8 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--sam") { if (!file(&a->sam)) return false; }
     else if (arg == "--sam-sorted") a->sam_sorted = true;
     else if (arg == "--bam") { if (!file(&a->bam)) return false; }
+    else if (arg == "--bam-sorted") a->bam_sorted = true;
+    else if (arg == "--bam-index") { if (!file(&a->bam_index)) return false; }
     else if (arg == "--overlaps") { if (!file(&a->overlaps)) return false; }
     else if (arg == "--min-overlap") { if (!uint(1, UINT64_MAX, " (at least 1)")) return false; a->min_overlap = u; }
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }
@@ -937,6 +944,8 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }
   if (a->sam_sorted && a->sam.empty()) { *err = "--sam-sorted needs --sam"; return false; }
   if (a->sam_sorted && !a->devices.empty()) { *err = "--sam-sorted does not combine with --devices: use --device"; return false; }
+  if (a->bam_sorted && a->bam.empty()) { *err = "--bam-sorted needs --bam"; return false; }
+  if (!a->bam_index.empty() && !a->bam_sorted) { *err = "--bam-index needs --bam-sorted"; return false; }
   if (!a->strain_sites.empty() && !a->with_ani) { *err = "--strain-sites needs --with-ani"; return false; }
   if (!a->strain_vcf.empty() && !a->with_ani) { *err = "--strain-vcf needs --with-ani"; return false; }
   // cli.rs:88-92: ArgGroup "genomes" is required, and --output has no default

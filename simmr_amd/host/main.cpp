@@ -120,6 +120,20 @@ static bool sam_check_names(const CliArgs& args, std::string* err) {
         if (s.first == rname) { *err = flag + who + " gets the RNAME '" + rname + "', which " + s.second + " has already"; return false; }
       seen.emplace_back(rname, who);
     }
+    if (args.bam_sorted) {  // a BAI index reaches 2^29 bases: no sequence body may hold that many (line ends aside)
+      uint64_t whole = 0;
+      for (size_t k = 0; k < recs.body.size(); k++) {
+        uint64_t bases = 0;
+        for (size_t i = recs.body[k].first; i < recs.body[k].first + recs.body[k].second && i < recs.data.size(); i++)
+          bases += recs.data[i] != '\n' && recs.data[i] != '\r';
+        whole += bases;
+        if ((args.contiguous ? whole : bases) >= (1ull << 29)) {
+          *err = "--bam-sorted: " + (args.contiguous ? std::string("the genome") : "sequence '" + recs.ids[k] + "'") + " of " + path +
+                 " has 2^29 bases or more: a BAI index does not reach there (CSI is not written)";
+          return false;
+        }
+      }
+    }
   }
   return true;
 }
@@ -278,8 +292,23 @@ struct SideOutputs {
   std::vector<uint8_t> sam_first_text;
   std::string sam_tmp;
   uint64_t sam_tmp_bytes = 0;
+  // --bam-sorted: the same shape for the records of every range, with the ends of the records beside the keys; the header waits
+  // for finish(), which frames header and records as one stream.  The state object of simmr_bam_sort_* belongs to the owner of
+  // the engines (it has to go before its engine).
+  std::vector<SamSortedRun> bam_runs;
+  std::vector<std::vector<uint32_t>> bam_ends;
+  std::vector<uint8_t> bam_first_rec;
+  std::vector<uint64_t> bam_lengths;
+  std::string bam_head, bam_tmp;
+  uint64_t bam_tmp_bytes = 0;
+  simmr_bam_sort** bam_sort = nullptr;
+  static constexpr size_t BAM_PIECE_BLOCKS = 1024;  // blocks of 65 280 source bytes a framing call takes
   bool run_paired = false;  // --overlaps: the run's reads are interleaved mates (set before begin)
-  ~SideOutputs() { if (!sam_tmp.empty()) remove(sam_tmp.c_str()); }
+  ~SideOutputs() {
+    if (!sam_tmp.empty()) remove(sam_tmp.c_str());
+    if (!bam_tmp.empty()) remove(bam_tmp.c_str());
+  }
+  std::string bam_index_path() const { return a.bam_index.empty() ? a.bam + ".bai" : a.bam_index; }
   bool overlaps() const { return !a.overlaps.empty(); }
   bool vcf() const { return !a.strain_vcf.empty(); }
   bool sam() const { return !a.sam.empty(); }
@@ -301,6 +330,7 @@ struct SideOutputs {
   bool begin(simmr_engine* eng, const std::vector<Genome>& genomes) {
     for (const std::string* f : {&a.truth, &a.sam, &a.bam, &a.overlaps, &a.stats, &a.fit_model, &a.depth, &a.depth_track, &a.gold_assembly, &a.gold_regions, &a.strain_vcf})
       if (!f->empty() && is_regular_file(*f)) remove(f->c_str());
+    if (a.bam_sorted && is_regular_file(bam_index_path())) remove(bam_index_path().c_str());
     std::string e;
     if (overlaps() && simmr_overlap_reset(eng, run_paired ? 1 : 0) != SIMMR_OK) return fail("--overlaps", simmr_last_error(eng));
     if (!a.truth.empty() && !write_truth_tsv(genomes, HostReads{}, HostTruth{}, 33, a.truth, true, &e)) return fail("--truth", e);
@@ -330,7 +360,7 @@ struct SideOutputs {
   // --bam: the file's head — magic, the header text of --sam (read order), the references — built here, framed on the device
   bool begin_bam(simmr_engine* eng, const std::vector<uint64_t>& lengths) {
     std::string text, e, head;
-    if (!sam_header_text(sam_names, lengths, &text, &e, false)) return fail("--bam", e);
+    if (!sam_header_text(sam_names, lengths, &text, &e, a.bam_sorted)) return fail("--bam", e);
     auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; k++) head.push_back((char)(v >> (8 * k))); };
     head += "BAM\1";
     put32((uint32_t)text.size());
@@ -341,6 +371,13 @@ struct SideOutputs {
       put32((uint32_t)sam_names[k].size() + 1u);
       head.append(sam_names[k].c_str(), sam_names[k].size() + 1);
       put32((uint32_t)lengths[k]);
+    }
+    if (a.bam_sorted) {  // the header is framed with the records, as one stream, by finish_bam_sorted
+      for (size_t k = 0; k < lengths.size(); k++)
+        if (lengths[k] >= (1ull << 29)) return fail("--bam-sorted", "sequence '" + sam_names[k] + "' has 2^29 bases or more: a BAI index does not reach there");
+      bam_head = head;
+      bam_lengths = lengths;
+      return true;
     }
     DeviceMem mem;
     uint8_t* src = nullptr;
@@ -374,6 +411,139 @@ struct SideOutputs {
     std::string e;
     OutFile f(a.bam, true);
     return bam_append_framed(eng, &mem, rec, total, &f) && (f.close(&e) || fail("--bam", e));
+  }
+  // --bam-sorted: the records of one range in coordinate order, with the key, the length and the end of each: a sorted run
+  bool bam_sorted_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
+    std::vector<const char*> names;
+    for (const std::string& n : sam_names) names.push_back(n.c_str());
+    simmr_sam_names sn{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), names.data()};
+    if (!*bam_sort && simmr_bam_sort_create(eng, bam_sort) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
+    uint64_t total = 0;
+    if (simmr_bam_sort_plan(*bam_sort, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
+    DeviceMem mem;
+    uint8_t* rec = nullptr;
+    uint64_t *key = nullptr, *rec_off = nullptr;
+    uint32_t* end = nullptr;
+    std::vector<uint8_t> h;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> ends;
+    SamSortedRun run;
+    if (!(mem.alloc(&rec, total) && mem.alloc(&key, n_reads) && mem.alloc(&rec_off, n_reads + 1) && mem.alloc(&end, n_reads)))
+      return fail("--bam-sorted", "device allocation failed");
+    if (simmr_bam_sort_emit(*bam_sort, &reads, &t, rec, total, key, rec_off, end) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
+    if (!(mem.fetch(&h, (const uint8_t*)rec, total) && mem.fetch(&run.key, (const uint64_t*)key, n_reads) && mem.fetch(&off, (const uint64_t*)rec_off, n_reads + 1) &&
+          mem.fetch(&ends, (const uint32_t*)end, n_reads)))
+      return fail("--bam-sorted", "copy back failed");
+    run.len.resize(n_reads);
+    for (uint64_t i = 0; i < n_reads; i++) run.len[i] = off[i + 1] - off[i];
+    bam_ends.push_back(std::move(ends));
+    if (bam_runs.empty()) {  // a run of one range needs no file
+      bam_first_rec = std::move(h);
+      bam_runs.push_back(std::move(run));
+      return true;
+    }
+    std::string e;
+    if (bam_tmp.empty()) {
+      bam_tmp = a.bam + ".sorting.tmp";
+      OutFile f(bam_tmp, false);
+      f.append(bam_first_rec.data(), bam_first_rec.size());
+      if (!f.close(&e)) return fail("--bam-sorted", e);
+      bam_tmp_bytes = bam_first_rec.size();
+      std::vector<uint8_t>().swap(bam_first_rec);
+    }
+    run.offset = bam_tmp_bytes;
+    OutFile f(bam_tmp, true);
+    f.append(h.data(), h.size());
+    if (!f.close(&e)) return fail("--bam-sorted", e);
+    bam_tmp_bytes += h.size();
+    bam_runs.push_back(std::move(run));
+    return true;
+  }
+  // The file and its index.  Header and records are one stream: one range's records as they are, several merged by (key, range,
+  // place in the range); the stream goes to the device in pieces of whole blocks (BgzfPieces carries the rest), so only the last
+  // block is short.  The columns of the index take the same merge, as 16-byte tuples; they go up once, and simmr_bai_* writes
+  // the index from them.
+  bool finish_bam_sorted(simmr_engine* eng) {
+    std::string e;
+    if (!*bam_sort && simmr_bam_sort_create(eng, bam_sort) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
+    uint64_t n = 0;
+    for (const SamSortedRun& r : bam_runs) n += r.key.size();
+    std::vector<uint64_t> key, rec_off(1, 0);
+    std::vector<uint32_t> end;
+    key.reserve(n); end.reserve(n); rec_off.reserve(n + 1);
+    OutFile out(a.bam, false);
+    BgzfPieces pieces(BAM_PIECE_BLOCKS, [&](const uint8_t* p, size_t bytes) {
+      DeviceMem mem;
+      uint8_t* src = nullptr;
+      if (!mem.alloc(&src, bytes) || hipMemcpy(src, p, bytes, hipMemcpyHostToDevice) != hipSuccess) return fail("--bam-sorted", "copy to the device failed");
+      return bam_append_framed(eng, &mem, src, bytes, &out) && out.ok();
+    });
+    if (!pieces.append(bam_head.data(), bam_head.size())) return false;
+    if (bam_tmp.empty()) {
+      if (!pieces.append(bam_first_rec.data(), bam_first_rec.size())) return false;
+      if (!bam_runs.empty()) {
+        key = bam_runs[0].key;
+        end = bam_ends[0];
+        for (uint64_t len : bam_runs[0].len) rec_off.push_back(rec_off.back() + len);
+      }
+    } else {
+      FILE* src = fopen(bam_tmp.c_str(), "rb");
+      if (!src) return fail("--bam-sorted", "cannot open " + bam_tmp);
+      bool merged = sam_merge_sorted_runs(
+          bam_runs, [&](uint64_t at, size_t len, char* p) { return fseeko(src, (off_t)at, SEEK_SET) == 0 && fread(p, 1, len, src) == len; },
+          [&](const char* p, size_t len) { return pieces.append(p, len); });
+      fclose(src);
+      remove(bam_tmp.c_str());
+      bam_tmp.clear();
+      if (!merged) return err.empty() ? fail("--bam-sorted", "the merge of the sorted ranges failed") : false;
+      // the columns: (key, end, length) of every record, 16 bytes, through the same merge
+      std::vector<char> tuples(16 * n), order;
+      std::vector<SamSortedRun> col_runs(bam_runs.size());
+      uint64_t at = 0;
+      for (size_t r = 0; r < bam_runs.size(); r++) {
+        col_runs[r].key = bam_runs[r].key;
+        col_runs[r].len.assign(bam_runs[r].key.size(), 16);
+        col_runs[r].offset = 16 * at;
+        for (size_t i = 0; i < bam_runs[r].key.size(); i++, at++) {
+          const uint32_t len32 = (uint32_t)bam_runs[r].len[i];  // (a record is below 2^20 bytes)
+          memcpy(&tuples[16 * at], &bam_runs[r].key[i], 8);
+          memcpy(&tuples[16 * at + 8], &bam_ends[r][i], 4);
+          memcpy(&tuples[16 * at + 12], &len32, 4);
+        }
+      }
+      order.reserve(16 * n);
+      merged = sam_merge_sorted_runs(
+          col_runs, [&](uint64_t from, size_t len, char* p) { if (from + len > tuples.size()) return false; memcpy(p, &tuples[from], len); return true; },
+          [&](const char* p, size_t len) { order.insert(order.end(), p, p + len); return true; });
+      if (!merged || order.size() != 16 * n) return fail("--bam-sorted", "the merge of the sorted ranges failed");
+      for (uint64_t i = 0; i < n; i++) {
+        uint64_t k; uint32_t en, len32;
+        memcpy(&k, &order[16 * i], 8); memcpy(&en, &order[16 * i + 8], 4); memcpy(&len32, &order[16 * i + 12], 4);
+        key.push_back(k); end.push_back(en); rec_off.push_back(rec_off.back() + len32);
+      }
+    }
+    if (!pieces.finish()) return false;
+    out.append(SIMMR_BGZF_EOF, SIMMR_BGZF_EOF_BYTES);
+    if (!out.close(&e)) return fail("--bam-sorted", e);
+    if (pieces.bytes() != bam_head.size() + rec_off.back()) return fail("--bam-sorted", "the merged stream and its columns disagree");
+    // the index, from the columns
+    DeviceMem mem;
+    uint64_t *dkey = nullptr, *doff = nullptr, bai_bytes = 0;
+    uint32_t* dend = nullptr;
+    uint8_t* bai = nullptr;
+    if (!(mem.alloc(&dkey, n) && mem.alloc(&dend, n) && mem.alloc(&doff, n + 1))) return fail("--bam-sorted", "device allocation failed");
+    if ((n > 0 && (hipMemcpy(dkey, key.data(), n * 8, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(dend, end.data(), n * 4, hipMemcpyHostToDevice) != hipSuccess)) ||
+        hipMemcpy(doff, rec_off.data(), (n + 1) * 8, hipMemcpyHostToDevice) != hipSuccess)
+      return fail("--bam-sorted", "copy to the device failed");
+    if (simmr_bai_plan(*bam_sort, dkey, dend, doff, n, bam_lengths.size(), bam_lengths.data(), bam_head.size(), &bai_bytes) != SIMMR_OK)
+      return fail("--bam-sorted", simmr_last_error(eng));
+    std::vector<uint8_t> h;
+    if (!mem.alloc(&bai, bai_bytes)) return fail("--bam-sorted", "device allocation failed");
+    if (simmr_bai_emit(*bam_sort, bai, bai_bytes) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
+    if (!mem.fetch(&h, (const uint8_t*)bai, bai_bytes)) return fail("--bam-sorted", "copy back failed");
+    OutFile index(bam_index_path(), false);
+    index.append(h.data(), h.size());
+    return index.close(&e) || fail("--bam-index", e);
   }
   // the end-of-file block behind the last range's blocks
   bool finish_bam() {
@@ -484,7 +654,7 @@ struct SideOutputs {
     DeviceMem mem;  // the truth columns on the device: --truth copies them out, --sam and --bam format from them
     simmr_truth_out t{};
     if (!device_truth(eng, &reads, n_reads, &mem, &t, a.truth.empty() ? nullptr : &truth, &e)) return fail(!a.truth.empty() ? "--truth" : sam() ? "--sam" : "--bam", e);
-    if (bam() && !bam_range(eng, reads, t, n_reads, paired)) return false;
+    if (bam() && !(a.bam_sorted ? bam_sorted_range(eng, reads, t, n_reads, paired) : bam_range(eng, reads, t, n_reads, paired))) return false;
     return !sam() || sam_range(eng, reads, t, n_reads, paired);
   }
   bool write_range(const std::vector<Genome>& genomes, const HostReads& h) {
@@ -553,7 +723,7 @@ struct SideOutputs {
     if (fit() && !finish_fit(eng)) return false;
     if (overlaps() && !finish_overlaps(eng)) return false;
     if (sam() && a.sam_sorted && !finish_sam_sorted()) return false;
-    if (bam() && !finish_bam()) return false;
+    if (bam() && !(a.bam_sorted ? finish_bam_sorted(eng) : finish_bam())) return false;
     if (!a.stats.empty()) {
       auto st = std::make_unique<simmr_run_stats>();
       if (simmr_stats_read(eng, st.get()) != SIMMR_OK) return fail("--stats", simmr_last_error(eng));
@@ -908,7 +1078,11 @@ static int load_genome_device(simmr_engine* eng, uint32_t slot, const std::strin
 
 struct Engines {  // released on every way out of run_main
   std::vector<simmr_engine*> v;
-  ~Engines() { for (simmr_engine* en : v) simmr_engine_destroy(en); }
+  simmr_bam_sort* bam_sort = nullptr;  // --bam-sorted: its state lives on an engine and goes before it
+  ~Engines() {
+    simmr_bam_sort_destroy(bam_sort);
+    for (simmr_engine* en : v) simmr_engine_destroy(en);
+  }
 };
 
 // `--fit-from-sam FILE --fit-model OUT`: no simulation.  The file goes up in pieces cut at the last newline (a line longer than a
@@ -1002,6 +1176,7 @@ static int run_main(int argc, char** argv) {
   const std::vector<int> ordinals = args.devices.empty() ? std::vector<int>{args.device} : args.devices;
   if (ordinals.size() > 1 && args.host_fastq) return die("--devices writes the text on the devices: it does not combine with --host-fastq");
   Engines engines;
+  side.bam_sort = &engines.bam_sort;
   const std::vector<simmr_engine*>& engs = engines.v;
   for (int ord : ordinals) {
     simmr_engine* en = nullptr;

@@ -166,6 +166,42 @@ struct SamSortedRun {
 bool sam_merge_sorted_runs(const std::vector<SamSortedRun>& runs, const std::function<bool(uint64_t, size_t, char*)>& read,
                            const std::function<bool(const char*, size_t)>& write);
 
+// `simmr-hip --bam FILE --bam-sorted`: the merged stream (header and records) goes to the framing in pieces of a whole number
+// of BGZF blocks (65 280 source bytes each); what does not fill a piece is carried into the next, so only the file's last block
+// is short and the virtual offset of an uncompressed position is arithmetic (simmr_bai_plan's contract).  frame(p, n) takes a
+// piece: n is piece_blocks * 65280 for every call but the last one, which finish() makes with what is left (none if nothing is).
+class BgzfPieces {
+ public:
+  static constexpr size_t BLOCK = 65280;
+  BgzfPieces(size_t piece_blocks, std::function<bool(const uint8_t*, size_t)> frame)
+      : piece_((piece_blocks ? piece_blocks : 1) * BLOCK), frame_(std::move(frame)) { buf_.reserve(piece_); }
+  bool append(const void* src, size_t n) {
+    const uint8_t* p = (const uint8_t*)src;
+    while (n > 0) {
+      const size_t take = n < piece_ - buf_.size() ? n : piece_ - buf_.size();
+      buf_.insert(buf_.end(), p, p + take);
+      p += take; n -= take; bytes_ += take;
+      if (buf_.size() == piece_) {
+        if (!frame_(buf_.data(), buf_.size())) return false;
+        buf_.clear();
+      }
+    }
+    return true;
+  }
+  bool finish() {
+    const bool ok = buf_.empty() || frame_(buf_.data(), buf_.size());
+    buf_.clear();
+    return ok;
+  }
+  uint64_t bytes() const { return bytes_; }  // appended so far
+
+ private:
+  size_t piece_;
+  std::function<bool(const uint8_t*, size_t)> frame_;
+  std::vector<uint8_t> buf_;
+  uint64_t bytes_ = 0;
+};
+
 // ---------------------------------------------------------------- strain sites (no reference counterpart)
 // Host copy of simmr_strain_out for one genome.
 struct HostStrainSites {
@@ -344,6 +380,8 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   bool sam_sorted = false;  // --sam-sorted: the file of --sam in coordinate order (simmr_sam_sort_plan / simmr_sam_sort_emit, a merge of the ranges)
   std::string sam;    // --sam FILE: the true alignments as SAM (simmr_sam_plan / simmr_sam_emit on every range's columns, the header from the host)
   std::string bam;    // --bam FILE: the same alignments as BAM in read order (simmr_bam_plan / simmr_bam_emit on every range's columns, framed by simmr_bgzf_frame: stored blocks; the header from the host)
+  bool bam_sorted = false;  // --bam-sorted: the file of --bam in coordinate order with its BAI index (simmr_bam_sort_*, a merge of the ranges, simmr_bai_*)
+  std::string bam_index;    // --bam-index FILE: where the index goes [default: the file of --bam with ".bai" appended]
   std::string overlaps;       // --overlaps FILE: the true read-to-read overlaps of the run as PAF (simmr_overlap_add over every range, one plan, drained by windows)
   uint64_t min_overlap = 1;   // --min-overlap N: shared reference bases from which two reads overlap
   std::string fit_model;      // --fit-model FILE: an error model fitted from the run (simmr_fit_add over every range, one plan) as simmrd writes it
