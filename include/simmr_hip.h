@@ -1266,6 +1266,90 @@ int simmr_fit_add_sam(simmr_engine* e, const uint8_t* text, uint64_t n_bytes, ui
 /* The counts of the SAM adds since the last simmr_fit_reset.  Synchronises.  SIMMR_ESTATE: no simmr_fit_reset yet. */
 int simmr_fit_sam_counts_read(simmr_engine* e, simmr_fit_sam_counts* out);
 
+/* ---- an aligner's SAM scored against the true alignments: two texts in HBM, joined and classified on the device ---------------
+ * Replaces nothing in the reference.  What a simulator with ground truth is bought for, and what wgsim_eval and paftools mapeval
+ * do on the host: how many reads an aligner placed correctly, at which mapping quality.  Two SAM texts go in — the truth (the
+ * text of simmr_sam_emit, either order, or any SAM that follows the rules below) and the aligner's output for the same reads —
+ * and integer tables come out.  No simulation, no genome: like simmr_fit_add_sam.
+ *
+ * Text.  The rules of simmr_fit_add_sam: whole lines of plain SAM, every line ends in '\n' except that the last line of a call
+ * may lack it; the caller cuts a file at line ends, at most SIMMR_FIT_SAM_MAX_BYTES a call; an empty line is skipped and not
+ * counted; a line that starts with '@' is a header line, counted and skipped.  Every other line is a record.
+ *
+ * Malformed (sticky; simmr_mapeval_read answers SIMMR_EINVAL, simmr_mapeval_truth_plan too for the truth), checked on every
+ * record before any filter: fewer than 11 fields; a FLAG, POS or MAPQ that is not a decimal number of 1 to 18 digits; a MAPQ
+ * above 255; a POS above 2^31 - 1; a CIGAR that is neither "*" nor (<digits><op>)+ with 1 to 9 digits a run, an op being any
+ * byte that is no digit; an interval (below) that ends above 2^40.  SEQ, QUAL and the optional fields are not read.
+ *
+ * Key.  QNAME is the read id: 1 to 18 decimal digits (so below 2^62).  mate = (FLAG & 0x80) != 0.  key = id << 1 | mate.
+ * Names.  The caller hands in the reference names once (simmr_mapeval_config).  The library keeps them sorted in a device blob;
+ * a record's RNAME is resolved by exact byte comparison (a binary search, no hash).  The row of a name is its place in that
+ * order; only the equality of rows matters.
+ * Interval.  [POS - 1, POS - 1 + M + D), M counting the runs of M, = and X; S, H and I take no reference; a CIGAR of "*" gives
+ * the empty interval.  A record with any other op (N, P, ...) is left out: the limit of the fit's SAM route.
+ *
+ * Truth record, in this order:
+ *   1. FLAG has 0x100, 0x800 or 0x4, or the CIGAR holds another op: counted truth_skipped.
+ *   2. Malformed on this side: a QNAME that is not a read id, an RNAME outside the names, a POS of 0.
+ *   3. An entry: key, name row, interval, strand (FLAG & 0x10).  Counted truth_entries.
+ * Aligned record, in this order:
+ *   1. FLAG has 0x100 or 0x800: secondary.                  2. The CIGAR holds another op: cigar_op.
+ *   3. QNAME is not a read id, or no truth entry has the key: unknown_read.
+ *   4. FLAG 0x4, or RNAME "*": class 1, unmapped.
+ *   5. Otherwise the record is mapped (a POS of 0 here is malformed).  An RNAME outside the names: unknown_ref, and class 2,
+ *      wrong.  Else class 3, correct, iff the name row equals the entry's, the strand (FLAG & 0x10) equals the entry's, and with
+ *      ov = the length of the intersection of the two intervals and un = max(ends) - min(starts): ov >= 1 and
+ *      100 * ov >= min_overlap_pct * un, in 64-bit integers (min_overlap_pct 10 is the criterion of paftools mapeval).
+ *      Every other mapped record is class 2, wrong.  by_mapq[MAPQ][class 3 ? 0 : 1] counts it.
+ *   6. Steps 4 and 5 give the entry a hit: hits[entry] += 1, best[entry] = max(best[entry], class << 8 | MAPQ).
+ * Every output is an integer sum or maximum: the same for any launch geometry and any cut of either text into adds. */
+typedef struct simmr_mapeval simmr_mapeval;
+
+typedef struct simmr_mapeval_config {   /* HOST memory */
+  uint32_t n_names;
+  uint32_t min_overlap_pct;             /* 1 .. 100; 0: the default, 10 */
+  const char* const* rname;             /* n_names reference names, NUL-terminated, in any order */
+} simmr_mapeval_config;
+
+typedef struct simmr_mapeval_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_lines, truth_header, truth_entries, truth_skipped;   /* lines = header + records; cumulative since the reset */
+  uint64_t lines, header, records;                                    /* the aligned side, since the last truth plan */
+  uint64_t secondary, cigar_op, unknown_read, unknown_ref, unmapped, correct, wrong;   /* unknown_ref records are among wrong */
+  uint64_t missing, multiple;           /* truth entries with no hit, with more than one */
+  uint64_t reads_correct, reads_wrong, reads_unmapped;   /* truth entries by the class of their best record */
+} simmr_mapeval_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_bam_sort_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error). */
+int simmr_mapeval_create(simmr_engine* e, simmr_mapeval** out);
+void simmr_mapeval_destroy(simmr_mapeval* h);
+/* Takes the names and min_overlap_pct, and empties both sides.  SIMMR_EINVAL: a NULL argument, min_overlap_pct above 100, a name
+ * given twice.  SIMMR_ENOTSUP: a name that is empty, longer than 254 bytes or no SAM reference name (the rule of
+ * simmr_sam_plan).  SIMMR_ERANGE: more than 2^24 names. */
+int simmr_mapeval_reset(simmr_mapeval* h, const simmr_mapeval_config* cfg);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for an entry per 21 bytes of text (no record is shorter) grows with the
+ * object.  SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL text with n_bytes > 0.  SIMMR_ENOTSUP: n_bytes above
+ * SIMMR_FIT_SAM_MAX_BYTES. */
+int simmr_mapeval_truth_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes);
+/* Sorts the entries by key (the radix sort of simmr_sam_sort_plan, over the bits of the largest key), checks that no key
+ * stands twice, empties the aligned side and synchronises.  *n_entries (may be NULL) = the entries.  SIMMR_EINVAL: a malformed
+ * truth record, or two entries with one key.  SIMMR_ERANGE: 2^31 entries or more. */
+int simmr_mapeval_truth_plan(simmr_mapeval* h, uint64_t* n_entries);
+/* Scores the records of text[0 .. n_bytes) (DEVICE, as above) against the plan.  Only enqueues.  SIMMR_ESTATE: no truth plan
+ * in force.  SIMMR_EINVAL, SIMMR_ENOTSUP: as simmr_mapeval_truth_add. */
+int simmr_mapeval_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts and by_mapq_host[256][2] (HOST, either may be NULL): the mapped records by MAPQ, [0] correct and [1] wrong.
+ * Synchronises.  The last five counts are made here, by a reduction over best[] and hits[].  SIMMR_EINVAL: a malformed record
+ * on either side since the reset (nothing is written).  SIMMR_ESTATE: no reset yet. */
+int simmr_mapeval_read(simmr_mapeval* h, simmr_mapeval_counts* counts, uint64_t* by_mapq_host);
+/* The truth entries in ascending key order (unique keys: the order is a function of the input), three columns (DEVICE, capacity
+ * entries each, any may be NULL): key, best = the maximum over the entry's hits of class << 8 | MAPQ (0: no hit), hits.
+ * Synchronises.  SIMMR_ESTATE: no truth plan.  SIMMR_ERANGE, nothing written: capacity < n_entries. */
+int simmr_mapeval_emit(simmr_mapeval* h, uint64_t* key_dev, uint32_t* best_dev, uint32_t* hits_dev, uint64_t capacity);
+/* HIP-event time (ms) of the device work of every add and plan since the last reset.  Synchronises the stream. */
+int simmr_last_mapeval_ms(simmr_mapeval* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

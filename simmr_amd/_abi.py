@@ -238,6 +238,21 @@ class FitSamCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in FIT_SAM_COUNTS]
 
 
+MAPEVAL_COUNTS = ("truth_lines", "truth_header", "truth_entries", "truth_skipped", "lines", "header", "records", "secondary", "cigar_op",
+                  "unknown_read", "unknown_ref", "unmapped", "correct", "wrong", "missing", "multiple", "reads_correct", "reads_wrong",
+                  "reads_unmapped")
+
+
+class MapevalCounts(C.Structure):
+    """struct simmr_mapeval_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in MAPEVAL_COUNTS]
+
+
+class MapevalConfig(C.Structure):
+    """struct simmr_mapeval_config (host memory)"""
+    _fields_ = [("n_names", C.c_uint32), ("min_overlap_pct", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
+
+
 class SamNames(C.Structure):
     """struct simmr_sam_names (host memory)"""
     _fields_ = [
@@ -362,6 +377,15 @@ SYMBOLS = {
     "simmr_last_fit_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
     "simmr_fit_add_sam": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
     "simmr_fit_sam_counts_read": (C.c_int, [C.c_void_p, _P(FitSamCounts)]),
+    "simmr_mapeval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_mapeval_destroy": (None, [C.c_void_p]),
+    "simmr_mapeval_reset": (C.c_int, [C.c_void_p, _P(MapevalConfig)]),
+    "simmr_mapeval_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_mapeval_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "simmr_mapeval_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_mapeval_read": (C.c_int, [C.c_void_p, _P(MapevalCounts), _P(C.c_uint64)]),
+    "simmr_mapeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_last_mapeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip, fit_sam.hip, bam.hip, bam_index.hip) may ask of an engine.  simmr_engine is
+// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip, fit_sam.hip, bam.hip, bam_index.hip, mapeval.hip) may ask of an engine.  simmr_engine is
 // defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>

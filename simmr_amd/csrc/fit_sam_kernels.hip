@@ -1,6 +1,7 @@
 // fit_sam_kernels.hip — the front of the model fit for a user's SAM file (gfx950): SAM text in HBM to the tables of
 // fit_device.hpp (include/simmr_hip.h states every rule: the filters, the rows, the orientation, what is malformed).
-// Included by fit_sam.hip alone, a translation unit of its own beside fit.hip, whose kernels and budgets stay what they were.
+// Included by fit_sam.hip, a translation unit of its own beside fit.hip, whose kernels and budgets stay what they were; and, with
+// FSAM_ROUTINES_ONLY defined, by mapeval_kernels.hip, which takes the reader's routines without the six kernels.
 //
 // Six kernels; a work item past the line index is a LINE or a TAKEN record, shared by FSAM_LANES = 16 lanes (one DPP row).
 //   k_fsam_index    the line index.  A tile is FSAM_TILE = 4096 bytes, 16 per thread.  A byte starts a line when it is not
@@ -157,10 +158,10 @@ SIMMR_DEV uint32_t fsam_md_lane(const uint8_t* __restrict__ t, uint32_t a, uint3
 }
 
 // ---- the line index -----------------------------------------------------------------------------------------------------------
-extern "C" __global__ void __launch_bounds__(FSAM_WG)
-k_fsam_index(const uint8_t* __restrict__ text, uint64_t n_bytes, uint64_t n_tiles, uint64_t* __restrict__ tile_sum,
-             const uint64_t* __restrict__ tile_prefix, uint32_t* __restrict__ starts, uint64_t start_capacity) {
-  __shared__ uint32_t lds[FSAM_WG];
+// The bodies of the index's two kernels as device routines: mapeval_kernels.hip (a translation unit of its own) includes this
+// file with FSAM_ROUTINES_ONLY defined and wraps them in kernels of its own, as sam_sort_kernels.hip does with sam_kernels.hip.
+SIMMR_DEV void fsam_index_tiles(const uint8_t* __restrict__ text, uint64_t n_bytes, uint64_t n_tiles, uint64_t* __restrict__ tile_sum,
+                                const uint64_t* __restrict__ tile_prefix, uint32_t* __restrict__ starts, uint64_t start_capacity, uint32_t* lds) {
   for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {  // (uniform over the workgroup)
     const uint64_t p0 = tile * FSAM_TILE + 16u * threadIdx.x;
     uint32_t mask = 0;
@@ -182,6 +183,14 @@ k_fsam_index(const uint8_t* __restrict__ text, uint64_t n_bytes, uint64_t n_tile
     for (; mask; mask &= mask - 1u, at++)
       if (at < start_capacity) starts[at] = (uint32_t)(p0 + (uint32_t)__builtin_ctz(mask));
   }
+}
+
+#ifndef FSAM_ROUTINES_ONLY
+extern "C" __global__ void __launch_bounds__(FSAM_WG)
+k_fsam_index(const uint8_t* __restrict__ text, uint64_t n_bytes, uint64_t n_tiles, uint64_t* __restrict__ tile_sum,
+             const uint64_t* __restrict__ tile_prefix, uint32_t* __restrict__ starts, uint64_t start_capacity) {
+  __shared__ uint32_t lds[FSAM_WG];
+  fsam_index_tiles(text, n_bytes, n_tiles, tile_sum, tile_prefix, starts, start_capacity, lds);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -531,5 +540,6 @@ k_fsam_windows(FsamWork W, FitTables T) {
     }
   }
 }
+#endif  // FSAM_ROUTINES_ONLY
 
 }  // namespace simmr

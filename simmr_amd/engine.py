@@ -137,6 +137,100 @@ class Truth:
         }
 
 
+class Mapeval:
+    """An aligner's SAM scored against the true alignments on the device (simmr_mapeval_*, include/simmr_hip.h states the rules).
+    truth_add() the truth text, truth_plan(), add() the aligner's text, then read() and entries().  A text is bytes (copied up) or a
+    contiguous CUDA uint8 tensor; the adds only enqueue, so every text is kept until a call that synchronises."""
+
+    def __init__(self, engine: "Engine", names, min_overlap_pct: int = 10):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_mapeval_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(names, min_overlap_pct)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, names, min_overlap_pct: int = 10):
+        raw = [n if isinstance(n, bytes) else str(n).encode() for n in names]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        cfg = _abi.MapevalConfig(len(raw), int(min_overlap_pct), arr)
+        try:
+            self._check(self.lib.simmr_mapeval_reset(self._h, C.byref(cfg)))
+        finally:
+            self._texts = []  # the reset has synchronised
+
+    def _text(self, text):
+        torch = _torch()
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            host = np.frombuffer(bytes(text), dtype=np.uint8)
+            dev = self.engine.device
+            text = torch.from_numpy(host.copy()).to(dev) if host.size else torch.empty(0, dtype=torch.uint8, device=dev)
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise ValueError("a SAM text is bytes or a contiguous CUDA uint8 tensor")
+        self._texts.append(text)
+        n = int(text.numel())
+        return C.c_void_p(text.data_ptr() if n else None), n
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_mapeval_truth_add(self._h, p, n))
+
+    def truth_plan(self) -> int:
+        n = C.c_uint64(0)
+        try:
+            self._check(self.lib.simmr_mapeval_truth_plan(self._h, C.byref(n)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_entries = int(n.value)
+        return self.n_entries
+
+    def add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_mapeval_add(self._h, p, n))
+
+    def read(self):
+        """(counts by the names of struct simmr_mapeval_counts, by_mapq as a (256, 2) uint64 array: correct, wrong)"""
+        c = _abi.MapevalCounts()
+        by = np.zeros((256, 2), dtype=np.uint64)
+        try:
+            self._check(self.lib.simmr_mapeval_read(self._h, C.byref(c), by.ctypes.data_as(C.POINTER(C.c_uint64))))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.MAPEVAL_COUNTS}, by
+
+    def entries(self):
+        """(key uint64, best uint32, hits uint32) of every truth entry, ascending by key, as numpy arrays"""
+        torch = _torch()
+        n = getattr(self, "n_entries", 0)
+        dev = self.engine.device
+        key = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        best = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        hits = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        self._check(self.lib.simmr_mapeval_emit(self._h, C.c_void_p(key.data_ptr()), C.c_void_p(best.data_ptr()), C.c_void_p(hits.data_ptr()), n))
+        self._texts = []
+        return key[:n].cpu().numpy().view(np.uint64), best[:n].cpu().numpy().view(np.uint32), hits[:n].cpu().numpy().view(np.uint32)
+
+    def last_ms(self) -> float:
+        ms = C.c_float()
+        self._check(self.lib.simmr_last_mapeval_ms(self._h, C.byref(ms)))
+        return ms.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_mapeval_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
 class Engine:
     """One engine == one GPU == one host thread (include/simmr_hip.h)."""
 
@@ -154,6 +248,8 @@ class Engine:
     # -- lifetime ---------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None):
+            for m in list(getattr(self, "_mapevals", [])):  # (their state lives on the engine: they go first)
+                m.close()
             if getattr(self, "_bam_sort", None):  # (the sorted-BAM state lives on the engine: it goes first)
                 self.lib.simmr_bam_sort_destroy(self._bam_sort)
                 self._bam_sort = None
@@ -894,6 +990,16 @@ class Engine:
         ms = C.c_float()
         self._check(self.lib.simmr_last_fit_ms(self._h, C.byref(ms)))
         return ms.value
+
+    # -- an aligner's SAM against the true alignments ---------------------------------------
+    def mapeval(self, names, min_overlap_pct: int = 10) -> "Mapeval":
+        """An evaluation object (simmr_mapeval_*): `names` are the reference names of both texts, in any order.  Closed by
+        its close(), or by the engine's before the engine goes."""
+        m = Mapeval(self, names, min_overlap_pct)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
 
     # -- counters / timing --------------------------------------------------------
     def counters(self) -> np.ndarray:

@@ -798,7 +798,64 @@ std::string usage() {
          "            --strain-vcf <FILE>  the same sites as VCF 4.2 with what the reads of this run show at each: DP, AD, ADF, ADR (reference and\n"
          "                            alternate base, all / forward / reverse reads) and OTH (a third base or N), mates counted separately;\n"
          "                            counted on the device from every range of the run; CHROM is genome_id|sequence_id, POS 1-based;\n"
-         "                            needs --with-ani; combines with --strain-sites; not with --devices\n";
+         "                            needs --with-ani; combines with --strain-sites; not with --devices\n"
+         "            --eval-sam <FILE>  no simulation: score an aligner's SAM (plain text) against the true alignments of --eval-truth, joined by\n"
+         "                            QNAME (the read id) and mate and classified on the device: a mapped record is correct when it lies on the\n"
+         "                            truth's sequence and strand and the two reference intervals overlap by at least --eval-min-overlap percent\n"
+         "                            of their union (paftools mapeval's rule); takes only --eval-truth, --eval-report, --eval-reads,\n"
+         "                            --eval-min-overlap and --device (no genomes, no --output, not --devices)\n"
+         "            --eval-truth <FILE>  the file of --sam for the reads that were aligned (either order); its @SQ lines name the sequences\n"
+         "            --eval-report <FILE>  the result as a TSV: the counts as #name value lines, then from MAPQ 255 downwards a row per MAPQ\n"
+         "                            with records: Q, MAPQ, mapped, wrong, cumulative wrong / cumulative mapped, cumulative mapped\n"
+         "            --eval-reads <FILE>  every true read whose best record is not correct: id, mate bit, class (0 no record, 1 unmapped,\n"
+         "                            2 wrong), MAPQ, records\n"
+         "            --eval-min-overlap <PCT>  1 .. 100 [default: 10]\n";
+}
+
+void mapeval_sq_names(const char* text, size_t n, std::vector<std::string>* names) {
+  for (size_t a = 0; a < n;) {
+    const char* nl = (const char*)memchr(text + a, '\n', n - a);
+    const size_t b = nl ? (size_t)(nl - text) : n;  // the line is text[a, b)
+    if (b - a >= 4 && memcmp(text + a, "@SQ\t", 4) == 0) {
+      for (size_t f = a + 4; f < b;) {  // its fields
+        const char* tab = (const char*)memchr(text + f, '\t', b - f);
+        const size_t g = tab ? (size_t)(tab - text) : b;
+        if (g - f >= 3 && memcmp(text + f, "SN:", 3) == 0) { names->emplace_back(text + f + 3, g - f - 3); break; }
+        f = g + 1;
+      }
+    }
+    a = b + 1;
+  }
+}
+
+std::string mapeval_report(const uint64_t* counts, const uint64_t* by_mapq) {
+  static const char* const NAMES[MAPEVAL_N_COUNTS] = {"truth_lines", "truth_header", "truth_entries", "truth_skipped", "lines", "header", "records",
+                                                      "secondary", "cigar_op", "unknown_read", "unknown_ref", "unmapped", "correct", "wrong", "missing",
+                                                      "multiple", "reads_correct", "reads_wrong", "reads_unmapped"};
+  std::string out;
+  for (size_t i = 0; i < MAPEVAL_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + std::to_string((unsigned long long)counts[i]) + "\n";
+  uint64_t cum_mapped = 0, cum_wrong = 0;
+  for (int q = 255; q >= 0; q--) {
+    const uint64_t ok = by_mapq[2 * q], wrong = by_mapq[2 * q + 1];
+    if (ok + wrong == 0) continue;
+    cum_mapped += ok + wrong;
+    cum_wrong += wrong;
+    char ratio[64];
+    snprintf(ratio, sizeof ratio, "%.6g", (double)cum_wrong / (double)cum_mapped);
+    out += "Q\t" + std::to_string(q) + "\t" + std::to_string((unsigned long long)(ok + wrong)) + "\t" + std::to_string((unsigned long long)wrong) + "\t" +
+           ratio + "\t" + std::to_string((unsigned long long)cum_mapped) + "\n";
+  }
+  return out;
+}
+
+std::string mapeval_read_rows(const uint64_t* key, const uint32_t* best, const uint32_t* hits, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++) {
+    if ((best[i] >> 8) == 3u) continue;
+    out += std::to_string((unsigned long long)(key[i] >> 1)) + "\t" + std::to_string((unsigned)(key[i] & 1u)) + "\t" + std::to_string(best[i] >> 8) + "\t" +
+           std::to_string(best[i] & 255u) + "\t" + std::to_string(hits[i]) + "\n";
+  }
+  return out;
 }
 
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
@@ -812,7 +869,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other;
+  std::string first_other, first_not_eval, first_eval;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -840,6 +897,9 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     if (first_other.empty() && arg != "--fit-from-sam" && arg != "--fit-model" && arg != "--fit-k" && arg != "--fit-max-alt" &&
         arg != "--single-reads" && arg != "--device")
       first_other = arg;  // what --fit-from-sam does not take
+    const bool eval_flag = arg == "--eval-sam" || arg == "--eval-truth" || arg == "--eval-report" || arg == "--eval-reads" || arg == "--eval-min-overlap";
+    if (eval_flag && first_eval.empty()) first_eval = arg;
+    if (!eval_flag && arg != "--device" && first_not_eval.empty()) first_not_eval = arg;  // what --eval-sam does not take
     if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
     else if (arg == "--single-reads") a->single_reads = true;
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
@@ -891,6 +951,11 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--stats") { if (!file(&a->stats)) return false; }
     else if (arg == "--fit-model") { if (!file(&a->fit_model)) return false; }
     else if (arg == "--fit-k") { if (!uint(3, 10, " (3 .. 10)")) return false; a->fit_k = (uint32_t)u; }
+    else if (arg == "--eval-sam") { if (!file(&a->eval_sam)) return false; }
+    else if (arg == "--eval-truth") { if (!file(&a->eval_truth)) return false; }
+    else if (arg == "--eval-report") { if (!file(&a->eval_report)) return false; }
+    else if (arg == "--eval-reads") { if (!file(&a->eval_reads)) return false; }
+    else if (arg == "--eval-min-overlap") { if (!uint(1, 100, " (1 .. 100)")) return false; a->eval_min_overlap = (uint32_t)u; }
     else if (arg == "--fit-max-alt") { if (!uint(1, UINT32_MAX, " (at least 1)")) return false; a->fit_max_alt = (uint32_t)u; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
@@ -939,6 +1004,17 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
       return false;
     }
     if (a->fit_model.empty()) { *err = "--fit-from-sam needs --fit-model"; return false; }
+    return true;
+  }
+  if (!first_eval.empty()) {  // no simulation either: a mode of its own beside --fit-from-sam
+    if (a->eval_sam.empty()) { *err = first_eval + " needs --eval-sam"; return false; }
+    if (!first_not_eval.empty()) {
+      *err = "--eval-sam runs no simulation: it takes only --eval-truth, --eval-report, --eval-reads, --eval-min-overlap and --device ('" + first_not_eval +
+             "' given)";
+      return false;
+    }
+    if (a->eval_truth.empty()) { *err = "--eval-sam needs --eval-truth"; return false; }
+    if (a->eval_report.empty()) { *err = "--eval-sam needs --eval-report"; return false; }
     return true;
   }
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }

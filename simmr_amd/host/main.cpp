@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <condition_variable>
+#include <fstream>
 #include <mutex>
 #include <thread>
 #include <string>
@@ -1085,14 +1086,53 @@ struct Engines {  // released on every way out of run_main
   }
 };
 
-// `--fit-from-sam FILE --fit-model OUT`: no simulation.  The file goes up in pieces cut at the last newline (a line longer than a
-// piece makes the piece grow), every piece is one simmr_fit_add_sam; then the plan and the model file of --fit-model.  What was
-// taken and skipped is printed in the manner of the reference's "Skipped N alignments ..." lines (simmrd/src/main.rs:259-290).
+// A SAM file to the device in pieces cut at the last newline (a line longer than a piece makes the piece grow; at the end of the
+// file the last line may lack its newline): add(d, n) gets every piece as n bytes of device memory, and answers only when the
+// device has read them (the buffer is then free for the next piece); an answer other than 0 ends the walk with that answer.
+// `flag` names the file's option in the messages.
 static constexpr size_t SAM_PIECE = 64u << 20;
-static int run_fit_from_sam(const CliArgs& args) {
-  FILE* f = fopen(args.fit_from_sam.c_str(), "rb");
-  if (!f) return die("--fit-from-sam: cannot open " + args.fit_from_sam);
+static int sam_file_pieces(const std::string& flag, const std::string& path, const std::function<int(const uint8_t*, size_t)>& add) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return die(flag + ": cannot open " + path);
   struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+  GrowBuf dev;
+  std::vector<uint8_t> piece;
+  size_t have = 0;  // bytes of `piece` read and not yet added: the open last line of the piece before
+  for (bool eof = false; !eof;) {
+    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
+    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
+    if (got < SAM_PIECE) {
+      if (ferror(f)) return die(flag + ": cannot read " + path);
+      eof = true;
+    }
+    have += got;
+    size_t cut = have;  // at the end of the file the last line may lack its newline
+    if (!eof) {
+      while (cut > 0 && piece[cut - 1] != '\n') cut--;
+      if (cut == 0) continue;  // one line longer than the piece: read on
+    }
+    if (cut > SIMMR_FIT_SAM_MAX_BYTES) return die(flag + ": a line of " + path + " is longer than one add takes");
+    if (cut > 0) {
+      uint8_t* d = dev.room(cut);
+      if (!d) return die(flag + ": device allocation failed");
+      if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die(flag + ": copy to the device failed");
+      if (int rc = add(d, cut)) return rc;
+    }
+    memmove(piece.data(), piece.data() + cut, have - cut);
+    have -= cut;
+  }
+  return 0;
+}
+
+// `--fit-from-sam FILE --fit-model OUT`: no simulation.  Every piece of the file is one simmr_fit_add_sam; then the plan and the
+// model file of --fit-model.  What was taken and skipped is printed in the manner of the reference's "Skipped N alignments ..."
+// lines (simmrd/src/main.rs:259-290).
+static int run_fit_from_sam(const CliArgs& args) {
+  {  // (the file is looked at before an engine is made)
+    FILE* f = fopen(args.fit_from_sam.c_str(), "rb");
+    if (!f) return die("--fit-from-sam: cannot open " + args.fit_from_sam);
+    fclose(f);
+  }
   Engines engines;
   simmr_engine* eng = nullptr;
   if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
@@ -1102,36 +1142,15 @@ static int run_fit_from_sam(const CliArgs& args) {
   if (simmr_fit_reset(eng, args.fit_k, args.fit_max_alt, SideOutputs::FIT_PAIR_CAPACITY) != SIMMR_OK) return die(std::string("--fit-model: ") + simmr_last_error(eng));
   info("Parsing " + args.fit_from_sam);
   const uint32_t n_sets = args.single_reads ? 1u : 2u;
-  GrowBuf dev;
-  std::vector<uint8_t> piece;
-  size_t have = 0;  // bytes of `piece` read and not yet added: the open last line of the piece before
   float device_ms = 0;
-  for (bool eof = false; !eof;) {
-    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
-    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
-    if (got < SAM_PIECE) {
-      if (ferror(f)) return die("--fit-from-sam: cannot read " + args.fit_from_sam);
-      eof = true;
-    }
-    have += got;
-    size_t cut = have;  // at the end of the file the last line may lack its newline
-    if (!eof) {
-      while (cut > 0 && piece[cut - 1] != '\n') cut--;
-      if (cut == 0) continue;  // one line longer than the piece: read on
-    }
-    if (cut > SIMMR_FIT_SAM_MAX_BYTES) return die("--fit-from-sam: a line of " + args.fit_from_sam + " is longer than one add takes");
-    if (cut > 0) {
-      uint8_t* d = dev.room(cut);
-      if (!d) return die("--fit-from-sam: device allocation failed");
-      if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die("--fit-from-sam: copy to the device failed");
-      if (simmr_fit_add_sam(eng, d, cut, n_sets) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
-      float ms = 0;  // (synchronises: the buffer is free for the next piece)
-      if (simmr_last_fit_ms(eng, &ms) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
-      device_ms += ms;
-    }
-    memmove(piece.data(), piece.data() + cut, have - cut);
-    have -= cut;
-  }
+  if (int rc = sam_file_pieces("--fit-from-sam", args.fit_from_sam, [&](const uint8_t* d, size_t n) {
+        if (simmr_fit_add_sam(eng, d, n, n_sets) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
+        float ms = 0;  // (synchronises: the buffer is free for the next piece)
+        if (simmr_last_fit_ms(eng, &ms) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
+        device_ms += ms;
+        return 0;
+      }))
+    return rc;
   simmr_fit_sam_counts c{};
   if (simmr_fit_sam_counts_read(eng, &c) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
   auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
@@ -1152,6 +1171,93 @@ static int run_fit_from_sam(const CliArgs& args) {
   return 0;
 }
 
+// `--eval-sam ALIGNED --eval-truth TRUTH --eval-report OUT`: no simulation.  The names come from the @SQ lines in front of the
+// truth file's records; both files go up in pieces, the truth through simmr_mapeval_truth_add and, behind the plan, the aligner's
+// through simmr_mapeval_add; the report is written from the counts and by_mapq on the host.  Nothing is written unless all of it
+// succeeded.
+struct MapevalHandle {
+  simmr_mapeval* h = nullptr;
+  ~MapevalHandle() { simmr_mapeval_destroy(h); }
+};
+static int run_eval_sam(const CliArgs& args) {
+  std::vector<std::string> names;
+  {
+    std::ifstream in(args.eval_truth, std::ios::binary);
+    if (!in) return die("--eval-truth: cannot open " + args.eval_truth);
+    std::string head, ln;
+    while (std::getline(in, ln) && (ln.empty() || ln[0] == '@')) head += ln + "\n";
+    mapeval_sq_names(head.data(), head.size(), &names);
+  }
+  if (names.empty()) return die("--eval-truth: " + args.eval_truth + " has no @SQ lines in front of its records: the sequences' names come from them");
+  {
+    FILE* f = fopen(args.eval_sam.c_str(), "rb");
+    if (!f) return die("--eval-sam: cannot open " + args.eval_sam);
+    fclose(f);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  MapevalHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_mapeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-sam: ") + simmr_last_error(eng));
+  std::vector<const char*> rname;
+  for (const std::string& s : names) rname.push_back(s.c_str());
+  const simmr_mapeval_config cfg{(uint32_t)rname.size(), args.eval_min_overlap, rname.data()};
+  if (simmr_mapeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-truth: ") + simmr_last_error(eng));
+  float ms = 0;
+  info("Parsing " + args.eval_truth);
+  if (int rc = sam_file_pieces("--eval-truth", args.eval_truth, [&](const uint8_t* d, size_t n) {
+        if (simmr_mapeval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_mapeval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
+          return die(std::string("--eval-truth: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  uint64_t n_entries = 0;
+  if (simmr_mapeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-truth: ") + simmr_last_error(eng));
+  info("Parsing " + args.eval_sam);
+  if (int rc = sam_file_pieces("--eval-sam", args.eval_sam, [&](const uint8_t* d, size_t n) {
+        if (simmr_mapeval_add(ev.h, d, n) != SIMMR_OK || simmr_last_mapeval_ms(ev.h, &ms) != SIMMR_OK)
+          return die(std::string("--eval-sam: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  simmr_mapeval_counts c{};
+  static_assert(sizeof(c) == MAPEVAL_N_COUNTS * sizeof(uint64_t), "the report names every count");
+  std::vector<uint64_t> by_mapq(512);
+  if (simmr_mapeval_read(ev.h, &c, by_mapq.data()) != SIMMR_OK) return die(std::string("--eval-sam: ") + simmr_last_error(eng));
+  std::string rows;
+  if (!args.eval_reads.empty()) {
+    GrowBuf d_key, d_best, d_hits;
+    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
+    uint8_t *k = d_key.room(n1 * 8), *b = d_best.room(n1 * 4), *h = d_hits.room(n1 * 4);
+    if (!k || !b || !h) return die("--eval-reads: device allocation failed");
+    if (simmr_mapeval_emit(ev.h, (uint64_t*)k, (uint32_t*)b, (uint32_t*)h, n_entries) != SIMMR_OK) return die(std::string("--eval-reads: ") + simmr_last_error(eng));
+    std::vector<uint64_t> key(n1);
+    std::vector<uint32_t> best(n1), hits(n1);
+    if (n_entries > 0 && (hipMemcpy(key.data(), k, n_entries * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+                          hipMemcpy(best.data(), b, n_entries * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                          hipMemcpy(hits.data(), h, n_entries * 4, hipMemcpyDeviceToHost) != hipSuccess))
+      return die("--eval-reads: copy from the device failed");
+    rows = mapeval_read_rows(key.data(), best.data(), hits.data(), n_entries);
+  }
+  std::string err;
+  OutFile report(args.eval_report, false);
+  report.append(mapeval_report((const uint64_t*)&c, by_mapq.data()));
+  if (!report.close(&err)) return die("--eval-report: " + err);
+  if (!args.eval_reads.empty()) {
+    OutFile reads(args.eval_reads, false);
+    reads.append(rows);
+    if (!reads.close(&err)) return die("--eval-reads: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_entries) + " reads (" + n(c.truth_skipped) + " records skipped)");
+  info("Aligned: " + n(c.records) + " records: " + n(c.correct) + " correct, " + n(c.wrong) + " wrong, " + n(c.unmapped) + " unmapped; " + n(c.secondary) +
+       " secondary or supplementary, " + n(c.cigar_op) + " with an operation other than M = X I D S H, " + n(c.unknown_read) + " of unknown reads");
+  info("Reads: " + n(c.reads_correct) + " correct, " + n(c.reads_wrong) + " wrong, " + n(c.reads_unmapped) + " unmapped, " + n(c.missing) + " without a record");
+  info("Wrote " + args.eval_report);
+  return 0;
+}
+
 
 static int run_main(int argc, char** argv) {
   CliArgs args;
@@ -1160,6 +1266,7 @@ static int run_main(int argc, char** argv) {
   if (!parse_cli_args(argc, argv, &args, &err, &help)) { fprintf(stderr, "error: %s\n\n%s", err.c_str(), usage().c_str()); return 2; }
   if (help) { fputs(usage().c_str(), stdout); return 0; }
   if (!args.fit_from_sam.empty()) return run_fit_from_sam(args);
+  if (!args.eval_sam.empty()) return run_eval_sam(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

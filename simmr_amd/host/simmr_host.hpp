@@ -152,6 +152,18 @@ bool sam_rname_legal(const std::string& rname);
 // `coordinate`: SO:coordinate, for the file of --sam-sorted.
 bool sam_header_text(const std::vector<std::string>& rnames, const std::vector<uint64_t>& lengths, std::string* out, std::string* err,
                      bool coordinate = false);
+// `simmr-hip --eval-sam`: the SN: values of the @SQ lines of `text` (whole lines; the last may lack its newline), appended to
+// *names in file order.  An @SQ line without an SN: field gives nothing.
+void mapeval_sq_names(const char* text, size_t n, std::vector<std::string>* names);
+// The file of --eval-report, in the shape of paftools mapeval: the counts of struct simmr_mapeval_counts as "#name\tvalue" lines in
+// the struct's order (counts[MAPEVAL_N_COUNTS]), then from MAPQ 255 downwards one row per MAPQ that has mapped records:
+// Q, the MAPQ, mapped at it, wrong at it, cumulative wrong / cumulative mapped (%.6g), cumulative mapped.  by_mapq[q * 2] counts
+// the correct and by_mapq[q * 2 + 1] the wrong records of MAPQ q.
+constexpr size_t MAPEVAL_N_COUNTS = 19;
+std::string mapeval_report(const uint64_t* counts, const uint64_t* by_mapq);
+// The rows of --eval-reads for n truth entries in key order: id, mate bit, class (0 no record, 1 unmapped, 2 wrong), MAPQ and
+// records of every entry whose best class is not 3, tab-separated.
+std::string mapeval_read_rows(const uint64_t* key, const uint32_t* best, const uint32_t* hits, size_t n);
 // `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
 // (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
 // ascend, and its text lies at `offset` of the byte source.
@@ -389,6 +401,11 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   uint32_t fit_max_alt = 20;  // --fit-max-alt N: alternates kept per reference k-mer
   std::string fit_from_sam;   // --fit-from-sam FILE: no simulation; the model of --fit-model from the records of a SAM file (simmr_fit_add_sam)
   bool single_reads = false;  // --single-reads: with --fit-from-sam, the file holds unpaired reads (n_sets 1: no insert sizes)
+  std::string eval_sam;       // --eval-sam FILE: no simulation; an aligner's SAM scored against the truth of --eval-truth (simmr_mapeval_*)
+  std::string eval_truth;     // --eval-truth FILE: the true alignments (the file of --sam); its @SQ lines give the reference names
+  std::string eval_report;    // --eval-report FILE: the counts and the rows by MAPQ as a TSV
+  std::string eval_reads;     // --eval-reads FILE: every truth read whose best record is not correct
+  uint32_t eval_min_overlap = 0;  // --eval-min-overlap PCT: 1 .. 100 (0: not given, the library's default of 10)
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions
