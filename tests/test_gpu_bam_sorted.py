@@ -4,7 +4,6 @@ tests/_bai.py byte for byte, and region queries through the device's own index a
 hand-built (the passes read the columns, never the genome)."""
 import gzip
 import re
-import struct
 from pathlib import Path
 
 import pytest
@@ -13,7 +12,7 @@ from simmr_amd import _abi
 from simmr_amd.engine import Engine
 from simmr_amd.sam import BGZF_EOF
 from tests import _bai, _bai_cases, _bam
-from tests._bai_cases import CONTIGS, REFS, RNAMES, SLOTS, columns
+from tests._bai_cases import CONTIGS, MANY, MANY_CONTIGS, MANY_REFS, MANY_RNAMES, MANY_SLOT, REFS, RNAMES, SLOTS, WINDOW, columns
 from tests.test_gpu_sam_seams import device_columns
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +26,8 @@ def _define(name, macro):
 
 TILE = _define("sam_sort_kernels.hip", "SAMSORT_TILE")
 CHUNK = _define("sam_kernels.hip", "SAM_CHUNK")
-MANY_SLOT = 5
-MANY = [200 + c for c in range(300)]
-MANY_RNAMES = [(MANY_SLOT, [f"m{c}" for c in range(300)])]
-MANY_REFS = [(f"m{c}", MANY[c]) for c in range(300)]
-MANY_CONTIGS = [(MANY_SLOT, c) for c in range(300)]
+WG_READS = _define("sam_kernels.hip", "SAM_WG_READS")
+WGS_PER_CU = _define("sam_kernels.hip", "SAM_WGS_PER_CU")
 
 
 @pytest.fixture(scope="module")
@@ -86,8 +82,63 @@ def count_specs(n):
 
 @pytest.mark.parametrize("n", [0, 1, 2, 255, 256, 257, TILE + CHUNK + 3], ids=lambda n: f"{n}-reads")
 def test_read_counts_where_the_passes_change_shape(eng, n):
-    assert TILE + CHUNK + 3 > max(TILE, 2 * CHUNK)  # past a sort tile and past a scan chunk, in both the records and the runs
+    """the largest count is past a sort tile and past a scan chunk in the RECORDS.  The runs and the bins stay at five: every read
+    lies below position 251, in the first window of its contig; test_reads_whose_runs_pass_a_chunk takes the runs past a chunk"""
+    assert TILE + CHUNK + 3 > max(TILE, 2 * CHUNK)
     check(eng, count_specs(n), n % 2 == 0, f"{n} reads")
+
+
+def spread_specs(n):
+    """the reads of count_specs on contig 0 alone, two bases in front of the 67 window edges of its 1.1 Mbases, far from read order:
+    on one position a read of three bases reaches over the edge (a bin one level up or more), the shorter ones stay in the leaf,
+    and the stable order leaves them in read order — the bin changes with every second sorted read"""
+    edges = (SLOTS[0][0] - 1) // WINDOW
+    return [(0, (1 + (r * 7919) % edges) * WINDOW - 2, (r * 7 + r // CHUNK) % 4, (r >> 1 ^ r) & 1, r, [0] if (r * 7 + r // CHUNK) % 4 and r % 3 == 0 else [])
+            for r in range(n)]
+
+
+def test_reads_whose_runs_pass_a_chunk(eng):
+    """Engine.bam_sorted past a sort tile and a scan chunk in the records AND past a scan chunk in the runs: the second round of
+    k_bai_count / k_bai_scan / k_bai_compact takes more than one chunk of run keys"""
+    n = TILE + CHUNK + 3
+    assert n > max(TILE, 2 * CHUNK)
+    _, _, bai, order = check(eng, spread_specs(n), False, f"{n} reads around the window edges")
+    refs, _ = _bai.parse_bai(bai)
+    chunks = [len(refs[0]["bins"][b]) for b in refs[0]["order"] if b != _bai.META_BIN]
+    assert sum(chunks) > CHUNK and len(chunks) > (SLOTS[0][0] - 1) // WINDOW and len(refs[0]["ioffset"]) == 1 + (SLOTS[0][0] - 1) // WINDOW
+    assert order != sorted(order) and all(not r["order"] for r in refs[1:])
+
+
+def test_more_batches_of_reads_than_the_write_grid_has_workgroups(eng):
+    """k_bamsort_write's batch loop: 16 reads a workgroup and trip, SAM_WGS_PER_CU workgroups per CU — a second trip for 17 reads"""
+    import torch
+    cus = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    n = WG_READS * WGS_PER_CU * cus + 17
+    assert -(-n // WG_READS) > WGS_PER_CU * cus
+    specs = [((r // 2) % len(CONTIGS), (r * 7919) % 251, r % 3, (r >> 1 ^ r) & 1, r, []) for r in range(n)]
+    check(eng, specs, False, f"{n} reads of 0 to 2 bases")
+
+
+def test_a_names_set_whose_key_has_no_bits():
+    """one contig without a base: pos_bits = row_bits = 0, nothing is sorted and place i holds read i (perm == nullptr in
+    k_bamsort_gather and k_bamsort_write); every read is one without bases on position 0.  That the plan is on that path is
+    asserted on what it decides from: the staged length of the one row it reports is 0, and the routine it asks for the key's
+    widths (simmr_sam_sort_key_bits) answers no bit for one row of that length"""
+    import ctypes as C
+    e = Engine(0)
+    try:
+        e.stage_synthetic(0, [0], 5)
+        specs = [(0, 0, 0, r & 1, 10 * r, []) for r in range(CHUNK + 37)]
+        for paired in (False, True):
+            _, _, bai, order = check(e, specs[:len(specs) - paired], paired, f"no key bits, paired={paired}", rnames=[(0, ["z"])], refs=[("z", 0)], contigs=[(0, 0)])
+            assert order == list(range(len(specs) - paired))
+            lens, n_rows, p, r = (C.c_uint64 * 4)(7, 7, 7, 7), C.c_uint64(7), C.c_uint32(7), C.c_uint32(7)
+            assert e.lib.simmr_bam_sort_ref_lengths(e._bam_sort_handle(), lens, 4, C.byref(n_rows)) == 0 and (n_rows.value, lens[0]) == (1, 0)
+            assert e.lib.simmr_sam_sort_key_bits(n_rows.value, lens[0], C.byref(p), C.byref(r)) == 0 and (p.value, r.value) == (0, 0)
+            (ref0,), _ = _bai.parse_bai(bai)
+            assert ref0["order"] == [4681, _bai.META_BIN] and len(ref0["bins"][4681]) == 1 and len(ref0["ioffset"]) == 1
+    finally:
+        e.close()
 
 
 def test_every_read_on_one_position(eng):
@@ -102,7 +153,7 @@ def test_every_read_on_one_position(eng):
 def test_three_hundred_references_with_gaps(eng):
     """one read per reference, none on every third and none on the first and the last: empty references at both ends and between"""
     used = [c for c in range(1, 299) if c % 3]
-    specs = [(c, (c * 13) % 150, 20, c & 1, k, []) for k, c in enumerate(reversed(used))]
+    specs = _bai_cases.many_specs()
     _, _, bai, _ = check(eng, specs, False, "300 references", rnames=MANY_RNAMES, refs=MANY_REFS, contigs=MANY_CONTIGS)
     refs, _ = _bai.parse_bai(bai)
     assert [bool(r["order"]) for r in refs] == [c in used for c in range(300)]
@@ -146,17 +197,10 @@ def test_streams_that_end_at_a_block_edge(eng, target):
     assert last == _bai.voff(target) and _bai.Stream(file_bytes).upos(last) == target  # (at a block edge: the EOF block's start)
 
 
-def _plain(ref_id, pos, L):
-    """a record without cigar and tags whose interval is [pos, pos + L)"""
-    body = struct.pack("<iiBBHHHiiii", ref_id, pos, 2, 255, _bam.reg2bin(pos, pos + L), 0, 0, L, -1, -1, 0) + b"a\0"
-    body += bytes([0x11] * (L // 2)) + (bytes([0x10]) if L & 1 else b"") + bytes([30] * L)
-    return struct.pack("<i", len(body)) + body
-
-
 def test_an_index_of_columns_the_caller_holds(eng):
     import torch
     dev = eng.device
-    r0, r1 = _plain(1, 3, 7), _plain(1, 5, 5)
+    r0, r1 = _bai_cases.plain(1, 3, 7), _bai_cases.plain(1, 5, 5)
     up, down = [(1 << 40) | 3, (1 << 40) | 5], [(1 << 40) | 5, (1 << 40) | 3]
     i64 = lambda v: torch.tensor(v, dtype=torch.int64, device=dev)
     end = torch.tensor([10, 10], dtype=torch.int32, device=dev)

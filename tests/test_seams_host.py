@@ -1,10 +1,11 @@
 """The fast restatements of tests/_seams.py against the plain model of tests/_overlap.py on a few hundred reads: the pairs by
 index equal _overlap.pairs entry for entry, and every vectorised record length equals the length of the line _overlap.record
-formats.  Runs without a GPU."""
+formats; and the index from columns (bai_from_columns) against the plain index of tests/_bai.py, byte for byte, on the records of
+the sorted-BAM tests and on every shape of tests/test_gpu_bai_seams.py at a small size.  Runs without a GPU."""
 import numpy as np
 import pytest
 
-from tests import _overlap, _seams
+from tests import _bai, _bai_cases, _overlap, _seams
 
 DIGITS = [9, 10, 99, 100, 999_999_999, 1_000_000_000, 4_294_967_295]
 
@@ -62,3 +63,88 @@ def test_digit_counts_at_every_power_of_ten():
         ps = _overlap.pairs(rs, 1)
         assert len(ps) == 6
         assert lengths_of(rs, ps, paired).tolist() == [len(_overlap.record(rs, p)) for p in ps]
+
+
+# ---- the BAI index from columns (tests/_seams.py:bai_from_columns) against tests/_bai.py:bai_bytes --------------------------------
+def same_index(n_ref, ref, lo, end, rec_off, records, base):
+    """bai_from_columns equals bai_bytes byte for byte, and the counts it reports are those of the parsed index"""
+    counts = {}
+    got = _seams.bai_from_columns(n_ref, ref, lo, end, rec_off, base, counts)
+    want = _bai.bai_bytes(n_ref, records, base)
+    i = next((k for k in range(min(len(got), len(want))) if got[k] != want[k]), min(len(got), len(want)))
+    assert got == want, f"{len(got)} bytes against {len(want)}; first difference at byte {i}: {got[i:i + 16].hex()} / {want[i:i + 16].hex()}"
+    refs, n_no_coor = _bai.parse_bai(want)
+    real = [(b, len(r["bins"][b])) for r in refs for b in r["order"] if b != _bai.META_BIN]
+    assert n_no_coor == 0 and counts["bins"].tolist() == [b for b, _ in real] and counts["n_bins"] == len(real)
+    assert counts["n_runs"] == sum(c for _, c in real) and counts["max_chunks"] == max([c for _, c in real], default=0)
+    assert counts["n_intv"].tolist() == [len(r["ioffset"]) for r in refs]
+    return counts, refs
+
+
+def from_records(n_ref, records, base):
+    cols, total = _bai.record_columns(records)
+    ref, lo, end, off = (np.array([c[k] for c in cols], dtype=np.int64) for k in range(4))
+    return same_index(n_ref, ref, lo, end, np.concatenate([off, [total]]), records, base)
+
+
+@pytest.mark.parametrize("paired", [False, True], ids=["unpaired", "paired"])
+def test_index_from_columns_on_the_mixed_and_level_records(paired):
+    o, t = _bai_cases.columns(_bai_cases.mixed_specs() + _bai_cases.level_specs(), seed=31)
+    records, _ = _bai_cases.sorted_records(o, t, paired)
+    counts, _ = from_records(len(_bai_cases.REFS), records, len(_bai_cases.header()))
+    assert {9, 73, 585} <= set(counts["bins"].tolist()) and set(_seams.bin_level(counts["bins"]).tolist()) >= {2, 3, 4, 5}
+
+
+def test_index_from_columns_on_three_hundred_references_with_gaps():
+    o, t = _bai_cases.columns(_bai_cases.many_specs(), seed=3, contigs=_bai_cases.MANY_CONTIGS)
+    records, _ = _bai_cases.sorted_records(o, t, False, _bai_cases.MANY_RNAMES)
+    counts, refs = from_records(300, records, len(_bai_cases.header(_bai_cases.MANY_REFS)))
+    assert [bool(r["order"]) for r in refs] == [c % 3 != 0 and 0 < c < 299 for c in range(300)]
+
+
+SMALL_SHAPES = {
+    "bin_changes": dict(m=300, big=200, n_ref=1),
+    "bin_changes-3": dict(m=300, big=200, n_ref=3),
+    "ties": dict(k=9),
+    "ties-2": dict(k=2),
+    "linear": dict(n_intvs=(255, 256, 257, 512, 513, 32768), long=40),
+    "strides": dict(n_ref=21, n=3000),
+    "sparse_refs": dict(n_ref=600),
+}
+
+
+@pytest.mark.parametrize("name", SMALL_SHAPES)
+def test_index_from_columns_on_every_shape_at_a_small_size(name):
+    """the shape builder of tests/test_gpu_bai_seams.py with small sizes, as plain records; the stream starts a few records in
+    front of a block edge, so virtual offsets on both sides of one occur"""
+    s = _bai_cases.index_shape(name.split("-")[0], **SMALL_SHAPES[name])
+    ref, lo, end = s["ref"], s["lo"], s["end"]
+    records = b"".join(_bai_cases.plain(r, p, e - p) for r, p, e in zip(ref.tolist(), lo.tolist(), end.tolist()))
+    rec_off = _bai_cases.plain_offsets(lo, end)
+    assert int(rec_off[-1]) == len(records) and ref.size <= 5000
+    counts, refs = same_index(s["n_ref"], ref, lo, end, rec_off, records, 3 * 65280 - 100)
+    if name.startswith("bin_changes"):
+        assert counts["n_runs"] == ref.size and set(_seams.bin_level(counts["bins"]).tolist()) == {0, 1, 2, 3, 4, 5} and counts["max_chunks"] == 200 + 3  # (bin 0: edge 4096 and edge 8192)
+    if name.startswith("ties"):
+        assert counts["n_runs"] == ref.size and counts["n_bins"] == 2
+    if name == "linear":
+        assert counts["n_intv"].tolist() == [255, 256, 257, 512, 513, 32768, 0, 40]
+        assert len(set(refs[7]["ioffset"])) == 1 and refs[5]["ioffset"][:511] == [0] * 511 and refs[5]["ioffset"][511] != 0
+    if name == "strides":
+        assert counts["n_runs"] == ref.size and [bool(r["order"]) for r in refs] == [c % 3 != 0 and 0 < c < 20 for c in range(21)]
+    if name == "sparse_refs":
+        assert [c for c, r in enumerate(refs) if r["order"]] == [0, 300, 599]
+
+
+def test_virtual_offsets_of_columns_up_to_the_last_one_of_48_bits():
+    """the vectorised virtual offset against _bai.voff around block edges, where the block's file offset passes 2^32, and at the
+    largest position whose block starts below 2^48"""
+    edge = -(-2**32 // _bai.FRAMED)  # the first block whose file offset is 2^32 or more
+    top = (2**48 - 1) // _bai.FRAMED * _bai.BLOCK + _bai.BLOCK - 1
+    ps = [0, 1, 65279, 65280, 65281, edge * 65280 - 1, edge * 65280, edge * 65280 + 1, top - 65280, top]
+    assert (edge - 1) * _bai.FRAMED < 2**32 <= edge * _bai.FRAMED and _bai.voff(top) < 2**64 <= _bai.voff(top + 1)
+    assert _seams.virtual_offsets(np.array(ps, dtype=np.uint64)).tolist() == [_bai.voff(p) for p in ps]
+    r0, r1 = _bai_cases.plain(1, 3, 7), _bai_cases.plain(1, 5, 5)
+    for base in (100, edge * 65280 - 20, top - len(r0) - len(r1)):
+        got = _seams.bai_from_columns(2, [1, 1], [3, 5], [10, 10], [0, len(r0), len(r0) + len(r1)], base)
+        assert got == _bai.bai_bytes(2, r0 + r1, base), base
