@@ -13,6 +13,12 @@ And a fast restatement of tests/_bai.py for the sizes at which the index kernels
   bai_from_columns                _bai.bai_bytes from the columns (reference, lo, end, offset) instead of record bytes, with numpy
                                   over all records, runs, bins, references and windows at once: the rules of include/simmr_hip.h
                                   (simmr_bai_plan), no loop over references times records.
+And a fast restatement of tests/_mapeval.py for the sizes at which the mapeval kernels take their second grid trips
+(tests/test_gpu_mapeval_seams.py), held to _mapeval.evaluate table for table by tests/test_seams_host.py:
+
+  mapeval_from_columns            both SAM texts and every table of _mapeval.evaluate from columns (read id, mate, strand, name
+                                  row, pos, span; on the aligned side also MAPQ and flag bits) instead of lines: the texts as
+                                  byte matrices, the tables with searchsorted, bincount and maximum.at.  No loop over lines.
 Nothing here comes from the code under test."""
 import numpy as np
 
@@ -184,3 +190,121 @@ def bai_from_columns(n_ref, ref, lo, end, rec_off, base, counts=None):
     if counts is not None:
         counts.update(n_runs=n_runs, n_bins=n_bins, max_chunks=int(bin_chunks.max()) if n_bins else 0, bins=bin_key & 0xffff, n_intv=n_intv)
     return words.astype("<u4").tobytes()
+
+
+# ---- mapeval from columns ---------------------------------------------------------------------------------------------------
+MEV_STAR = -1  # a name row: RNAME "*", POS 0 and CIGAR "*" (unmapped without the flag)
+MEV_COUNTS = ("truth_lines", "truth_header", "truth_entries", "truth_skipped", "lines", "header", "records", "secondary", "cigar_op",
+              "unknown_read", "unknown_ref", "unmapped", "correct", "wrong", "missing", "multiple", "reads_correct", "reads_wrong",
+              "reads_unmapped")
+MEV_TAIL = b"\t*\t0\t0\t*\t*\n"
+
+
+def _column(cols, name, n, default=None):
+    v = cols.get(name, default)
+    assert v is not None, name
+    return np.broadcast_to(np.asarray(v, dtype=np.int64), (n,))
+
+
+def _put_number(mat, at, width, v, pad):
+    """v in decimal, right-aligned in mat[:, at : at + width]: the places in front hold '0' (pad) or NUL"""
+    v = v.astype(np.uint64)
+    shown = dec_digits(v)
+    assert (shown <= width).all()
+    for j in range(width):  # (over the places of a number, not over the lines)
+        place = ((v // np.uint64(10 ** j)) % np.uint64(10) + np.uint64(48)).astype(np.uint8)
+        if not pad:
+            place[shown <= j] = 0
+        mat[:, at + width - 1 - j] = place
+
+
+def mapeval_text(names, qid, flag, row, pos, mapq, span, pad, header=b""):
+    """The SAM text of n records `<id> <flag> <name> <pos> <mapq> <span>M * 0 0 * *` as a byte matrix: every field right-aligned
+    in a slot as wide as the column's widest value.  pad: the numbers are filled up with zeros in front (they stay the same
+    numbers under the rules) and a text whose names have one length is the matrix itself, all lines of one width; otherwise, and
+    for the names and the "*" of a row MEV_STAR always, the slot's front is NUL and the NULs are taken out of the text."""
+    n = qid.size
+    table = [bytes(x) for x in names] + [b"*"]  # (row -1, MEV_STAR, is the last)
+    w_name = max(len(x) for x in table)
+    name_mat = np.zeros((len(table), w_name), dtype=np.uint8)
+    for r, x in enumerate(table):  # (over the names, not over the lines)
+        name_mat[r, w_name - len(x):] = np.frombuffer(x, dtype=np.uint8)
+    star = row == MEV_STAR
+    assert ((row >= -1) & (row < len(names))).all() and (pos[star] == 0).all() and (pos[~star] >= 1).all() and (span <= 999_999_999).all()
+    width = lambda v: int(dec_digits(np.array([int(v.max()) if n else 0], dtype=np.uint64))[0])
+    w_id, w_flag, w_pos, w_mapq, w_span = width(qid), width(flag), width(pos), width(mapq), width(span)
+    p_flag = w_id + 1  # every slot is followed by a tab, the span's by its op
+    p_name = p_flag + w_flag + 1
+    p_pos = p_name + w_name + 1
+    p_mapq = p_pos + w_pos + 1
+    p_span = p_mapq + w_mapq + 1
+    p_tail = p_span + w_span + 1
+    mat = np.full((n, p_tail + len(MEV_TAIL)), 9, dtype=np.uint8)  # (9: a tab)
+    for p, w, v in ((0, w_id, qid), (p_flag, w_flag, flag), (p_pos, w_pos, pos), (p_mapq, w_mapq, mapq), (p_span, w_span, span)):
+        _put_number(mat, p, w, v, pad)
+    mat[:, p_name:p_name + w_name] = name_mat[row]
+    mat[:, p_tail - 1] = ord("M")
+    mat[star, p_span:p_tail - 1] = 0  # CIGAR "*"
+    mat[star, p_tail - 1] = ord("*")
+    mat[:, p_tail:] = np.frombuffer(MEV_TAIL, dtype=np.uint8)
+    return header + (mat.tobytes() if mat.all() else mat[mat != 0].tobytes())
+
+
+def mapeval_from_columns(names, truth, aligned, pct=10, pad=True, header=b"", n_present=None):
+    """_mapeval.evaluate(names[:n_present], [truth text], [aligned text], pct) from columns: a dict with both texts ("truth",
+    "aligned": `header`, then a record per entry of the columns), "counts", "by_mapq", "key", "best" and "hits".
+      truth    id, mate (1 or 2: FLAG 0x40 or 0x80, and bit 0 of the key), strand, row, pos, span [, mapq: 255];
+      aligned  the same and mapq and bits (0x4, 0x100, 0x800: or-ed into FLAG).
+    A row is an index into `names`; the names from n_present on are not in the table (an unknown reference; aligned side only);
+    MEV_STAR on the aligned side is RNAME "*".  A read is unknown when its (id, mate) is not in the truth.  A value given as a
+    scalar holds for every record.  The truth's keys are unique, every truth record is an entry, CIGAR is `<span>M`."""
+    n_present = len(names) if n_present is None else n_present
+    assert len(set(names)) == len(names) and b"*" not in names
+    nt, na = np.asarray(truth["id"]).size, np.asarray(aligned["id"]).size
+    t = {k: _column(truth, k, nt, d) for k, d in (("id", None), ("mate", None), ("strand", None), ("row", None), ("pos", None), ("span", None), ("mapq", 255))}
+    a = {k: _column(aligned, k, na, d) for k, d in (("id", None), ("mate", None), ("strand", None), ("row", None), ("pos", None), ("span", None), ("mapq", None), ("bits", 0))}
+    for c in (t, a):
+        assert ((c["mate"] == 1) | (c["mate"] == 2)).all() and ((c["strand"] | 1) == 1).all() and (c["id"] >= 0).all() and (c["mapq"] >> 8 == 0).all()
+    assert ((t["row"] >= 0) & (t["row"] < n_present)).all() and (a["bits"] & ~0x904 == 0).all()
+    flag_of = lambda c: np.where(c["mate"] == 2, 0x80, 0x40) | c["strand"] << 4
+    head_lines = sum(1 for ln in header.split(b"\n") if ln)
+    assert all(ln[:1] == b"@" for ln in header.split(b"\n") if ln) and (not header or header.endswith(b"\n"))
+    out = dict(truth=mapeval_text(names, t["id"], flag_of(t), t["row"], t["pos"], t["mapq"], t["span"], pad, header),
+               aligned=mapeval_text(names, a["id"], flag_of(a) | a["bits"], a["row"], a["pos"], a["mapq"], a["span"], pad, header))
+
+    key_of = lambda c: (c["id"].astype(np.uint64) << np.uint64(1)) | (c["mate"] == 2).astype(np.uint64)
+    t_key = key_of(t)
+    order = np.argsort(t_key, kind="stable")
+    key = t_key[order]
+    assert (key[1:] != key[:-1]).all(), "two truth records with one key"
+    t_row, t_strand, t_lo, t_hi = t["row"][order], t["strand"][order], (t["pos"] - 1)[order], (t["pos"] - 1 + t["span"])[order]
+
+    secondary = a["bits"] & 0x900 != 0
+    at = np.searchsorted(key, key_of(a))
+    at_in = np.minimum(at, max(nt - 1, 0))
+    found = ~secondary & (at < nt) & (key[at_in] == key_of(a) if nt else False)
+    unmapped = found & ((a["bits"] & 4 != 0) | (a["row"] == MEV_STAR))
+    mapped = found & ~unmapped
+    unknown_ref = mapped & (a["row"] >= n_present)
+    lo, hi = a["pos"] - 1, a["pos"] - 1 + a["span"]
+    if nt:
+        tl, th = t_lo[at_in], t_hi[at_in]
+        ov = np.maximum(0, np.minimum(hi, th) - np.maximum(lo, tl))
+        un = np.maximum(hi, th) - np.minimum(lo, tl)
+        correct = mapped & ~unknown_ref & (a["row"] == t_row[at_in]) & (a["strand"] == t_strand[at_in]) & (ov >= 1) & (100 * ov >= pct * un)
+    else:
+        correct = np.zeros(na, dtype=bool)
+    wrong = mapped & ~correct
+    cls = np.where(unmapped, 1, np.where(correct, 3, 2))
+    best = np.zeros(nt, dtype=np.uint32)
+    np.maximum.at(best, at[found], (cls[found] << 8 | a["mapq"][found]).astype(np.uint32))
+    hits = np.bincount(at[found], minlength=nt).astype(np.uint32)
+    by_mapq = np.bincount(2 * a["mapq"][mapped] + wrong[mapped], minlength=512).astype(np.uint64).reshape(256, 2)
+    counts = dict.fromkeys(MEV_COUNTS, 0)
+    counts.update(truth_lines=head_lines + nt, truth_header=head_lines, truth_entries=nt, lines=head_lines + na, header=head_lines, records=na,
+                  secondary=int(secondary.sum()), unknown_read=int((~secondary & ~found).sum()), unknown_ref=int(unknown_ref.sum()),
+                  unmapped=int(unmapped.sum()), correct=int(correct.sum()), wrong=int(wrong.sum()), missing=int((hits == 0).sum()),
+                  multiple=int((hits > 1).sum()), reads_correct=int((best >> 8 == 3).sum()), reads_wrong=int((best >> 8 == 2).sum()),
+                  reads_unmapped=int((best >> 8 == 1).sum()))
+    out.update(counts=counts, by_mapq=by_mapq, key=key, best=best, hits=hits)
+    return out

@@ -72,3 +72,35 @@ def test_refusals(workdir):
     assert r.returncode == 1 and "cannot open" in r.stderr and not report.exists()
     r = subprocess.run(base + ["--eval-truth", str(d / "ev_ok.sam")], capture_output=True, text=True)
     assert r.returncode == 0 and report.read_bytes().endswith(b"Q\t255\t1\t0\t0\t1\n") and reads.read_bytes() == b""
+
+
+def test_a_file_of_more_than_one_piece(workdir):
+    """sam_file_pieces' carry (main.cpp): a file just over SAM_PIECE whose cut falls inside a line, against itself, so the truth's
+    and the aligner's walk both carry an open line over; then the same file without its last newline"""
+    import re
+
+    import numpy as np
+
+    from tests import _seams
+    from tests.test_gpu_cli import ROOT
+    d, _ = workdir
+    piece = re.search(r"SAM_PIECE = (\d+)u? << (\d+)", (ROOT / "simmr_amd" / "host" / "main.cpp").read_text())
+    piece = int(piece.group(1)) << int(piece.group(2))
+    header = b"@HD\tVN:1.6\n@SQ\tSN:a\tLN:100000\n@SQ\tSN:b\tLN:100000\n@SQ\tSN:c\tLN:100000\n"
+    width = 38  # 7 + 3 + 1 + 4 + 3 + 4 bytes of fields, 16 of tabs, the fixed fields and the newline
+    n = (piece - len(header)) // width + 3000
+    i = np.arange(n, dtype=np.int64)
+    cols = dict(id=(i * 1_000_003) % n, mate=1 + (i & 1), strand=(i >> 1) & 1, row=i % 3, pos=1 + i % 9000, span=100 + i % 100, mapq=i % 256)
+    res = _seams.mapeval_from_columns([b"a", b"b", b"c"], cols, dict(cols, bits=0), header=header)
+    text = res["truth"]
+    assert text == res["aligned"] and len(text) == len(header) + n * width > piece and (piece - len(header)) % width != 0
+    assert text[len(header) + width - 1:len(header) + width] == b"\n" and text[piece - 1:piece] != b"\n"  # lines of one width; the cut is inside one
+    want = _mapeval.report(res["counts"], res["by_mapq"])
+    assert res["counts"]["correct"] == res["counts"]["reads_correct"] == n and want.count(b"\nQ\t") == 256
+    for name, body in (("ev_two_pieces.sam", text), ("ev_two_pieces_open.sam", text[:-1])):
+        path, report = d / name, d / (name + ".tsv")
+        path.write_bytes(body)
+        r = subprocess.run([str(EXE), "--eval-sam", str(path), "--eval-truth", str(path), "--eval-report", str(report)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        assert report.read_bytes() == want, name
+        path.unlink()

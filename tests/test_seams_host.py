@@ -1,11 +1,13 @@
 """The fast restatements of tests/_seams.py against the plain model of tests/_overlap.py on a few hundred reads: the pairs by
 index equal _overlap.pairs entry for entry, and every vectorised record length equals the length of the line _overlap.record
 formats; and the index from columns (bai_from_columns) against the plain index of tests/_bai.py, byte for byte, on the records of
-the sorted-BAM tests and on every shape of tests/test_gpu_bai_seams.py at a small size.  Runs without a GPU."""
+the sorted-BAM tests and on every shape of tests/test_gpu_bai_seams.py at a small size; and the mapeval tables from columns (mapeval_from_columns) against the
+plain model of tests/_mapeval.py, table for table, on random columns that hold every class and on every case of
+tests/test_gpu_mapeval_seams.py at a small size.  Runs without a GPU."""
 import numpy as np
 import pytest
 
-from tests import _bai, _bai_cases, _overlap, _seams
+from tests import _bai, _bai_cases, _mapeval, _mapeval_cases, _overlap, _seams
 
 DIGITS = [9, 10, 99, 100, 999_999_999, 1_000_000_000, 4_294_967_295]
 
@@ -148,3 +150,120 @@ def test_virtual_offsets_of_columns_up_to_the_last_one_of_48_bits():
     for base in (100, edge * 65280 - 20, top - len(r0) - len(r1)):
         got = _seams.bai_from_columns(2, [1, 1], [3, 5], [10, 10], [0, len(r0), len(r0) + len(r1)], base)
         assert got == _bai.bai_bytes(2, r0 + r1, base), base
+
+
+# ---- mapeval from columns (tests/_seams.py:mapeval_from_columns) against tests/_mapeval.py:evaluate ------------------------------------
+def same_tables(case, pct, pad, header=b""):
+    """both texts of the builder through the plain model: every count, by_mapq, and key / best / hits with their dtypes"""
+    res = _seams.mapeval_from_columns(case["names"], case["truth"], case["aligned"], pct, pad, header, case["n_present"])
+    m = _mapeval.evaluate(case["names"][:case["n_present"]], [res["truth"]], [res["aligned"]], pct)
+    counts, by = m.read()
+    assert tuple(res["counts"]) == _mapeval.COUNTS == _seams.MEV_COUNTS
+    assert res["counts"] == counts, {n: (res["counts"][n], counts[n]) for n in counts if counts[n] != res["counts"][n]}
+    assert res["by_mapq"].dtype == by.dtype and np.array_equal(res["by_mapq"], by)
+    for name, want in zip(("key", "best", "hits"), m.entries()):
+        assert res[name].dtype == want.dtype and np.array_equal(res[name], want), name
+    return res
+
+
+@pytest.mark.parametrize("pad", [False, True], ids=["unpadded", "padded"])
+@pytest.mark.parametrize("pct", [10, 50])
+def test_mapeval_from_random_columns(pct, pad):
+    """every class: correct, wrong by position, strand and contig, unmapped by flag and by "*", unknown read and reference,
+    secondary and supplementary, doubles and drops; overlaps on both sides of the threshold"""
+    rng = np.random.default_rng(pct + pad)
+    n = 400
+    ids = rng.permutation(np.unique(rng.integers(0, 10 ** rng.integers(1, 11, 3 * n))))[:n]  # 1 to 10 digits, distinct
+    assert ids.size == n
+    truth = dict(id=ids, mate=rng.integers(1, 3, n), strand=rng.integers(0, 2, n), row=rng.integers(0, 3, n), pos=rng.integers(1, 5000, n),
+                 span=rng.integers(1, 300, n), mapq=rng.integers(0, 256, n))
+    pick = np.concatenate([rng.permutation(n)[:300], rng.integers(0, n, 500)])  # a hundred dropped, many doubled
+    m = pick.size
+    kind = rng.integers(0, len(_mapeval_cases.KINDS), m)
+    is_ = lambda name: kind == _mapeval_cases.KINDS.index(name)
+    span = truth["span"][pick]
+    shift = np.where(is_("wrong_pos"), span + rng.integers(0, 50, m), np.where(is_("correct"), rng.integers(0, 2, m) * rng.integers(0, 300, m), 0))
+    aligned = dict(id=np.where(is_("unknown_read"), 10 ** 11 + np.arange(m), truth["id"][pick]), mate=truth["mate"][pick],
+                   strand=truth["strand"][pick] ^ is_("wrong_strand"),
+                   row=np.where(is_("wrong_contig"), (truth["row"][pick] + 1) % 3, np.where(is_("unknown_ref"), 3, np.where(is_("unmapped_star"), _seams.MEV_STAR, truth["row"][pick]))),
+                   pos=np.where(is_("unmapped_star"), 0, truth["pos"][pick] + shift), span=np.maximum(span + rng.integers(-3, 4, m), 1),
+                   mapq=rng.integers(0, 256, m), bits=np.where(is_("unmapped_flag"), 4, np.where(is_("secondary"), 0x100, np.where(is_("supplementary"), 0x800, 0))))
+    # the other mate of a known id is an unknown read too
+    aligned["mate"] = np.where(rng.integers(0, 20, m) == 0, 3 - aligned["mate"], aligned["mate"])
+    case = dict(names=[b"chr1", b"chr10", b"c", b"chrUn"], n_present=3, truth=truth, aligned=aligned)
+    res = same_tables(case, pct, pad, b"@HD\tVN:1.6\n@SQ\tSN:chr1\tLN:9\n")
+    c = res["counts"]
+    for name in ("secondary", "unknown_read", "unknown_ref", "unmapped", "correct", "wrong", "missing", "multiple", "reads_correct", "reads_wrong", "reads_unmapped"):
+        assert c[name] >= 5, name
+    assert c["truth_header"] == c["header"] == 2 and c["truth_entries"] == n and c["records"] == m
+    width = {len(ln) for ln in res["truth"].split(b"\n")[2:-1]}
+    assert len(width) > 1  # (names of three lengths)
+    # the threshold is on both sides among the records the builder calls wrong and correct
+    assert 0 < (res["by_mapq"][:, 0] > 0).sum() and 0 < (res["by_mapq"][:, 1] > 0).sum()
+
+
+def test_mapeval_text_is_a_byte_matrix_when_padded():
+    case = _mapeval_cases.search(33)
+    padded = _seams.mapeval_from_columns(case["names"], case["truth"], case["aligned"], n_present=3)
+    plain = _seams.mapeval_from_columns(case["names"], case["truth"], case["aligned"], pad=False, n_present=3)
+    assert len({len(ln) for ln in padded["truth"].split(b"\n")[:-1]}) == 1 and len({len(ln) for ln in plain["truth"].split(b"\n")[:-1]}) > 1
+    assert padded["truth"].startswith(b"01\t64\ta\t001\t255\t50M\t*\t0\t0\t*\t*\n") and plain["truth"].startswith(b"1\t64\ta\t1\t255\t50M\t*\t0\t0\t*\t*\n")
+    for name in ("key", "best", "hits", "by_mapq"):
+        assert np.array_equal(padded[name], plain[name])
+    assert padded["counts"] == plain["counts"]
+
+
+SMALL_CASES = {
+    "search-1": lambda: _mapeval_cases.search(1),
+    "search-17": lambda: _mapeval_cases.search(17),
+    "search-257": lambda: _mapeval_cases.search(257),
+    "trips": lambda: _mapeval_cases.trips(n=5000, edge=2560, grid_lines=2560, extra=300),
+    "trips-tiny": lambda: _mapeval_cases.trips(n=7, edge=4, grid_lines=16, extra=5),
+    "every_mapq": _mapeval_cases.every_mapq,
+    "many-all": lambda: _mapeval_cases.many_records("all", 700),
+    "many-no_correct": lambda: _mapeval_cases.many_records("no_correct", 700),
+    "many-unmapped": lambda: _mapeval_cases.many_records("unmapped", 700),
+    "names-1": lambda: _mapeval_cases.names(1),
+    "names-3": lambda: _mapeval_cases.names(3),
+    "names-65": lambda: _mapeval_cases.names(65),
+}
+
+
+@pytest.mark.parametrize("pad", [False, True], ids=["unpadded", "padded"])
+@pytest.mark.parametrize("pct", [10, 50])
+@pytest.mark.parametrize("name", SMALL_CASES)
+def test_mapeval_from_columns_on_every_case_at_a_small_size(name, pct, pad):
+    case = SMALL_CASES[name]()
+    res = same_tables(case, pct, pad)
+    c, best, hits = res["counts"], res["best"], res["hits"]
+    if name.startswith("search"):
+        assert (hits == 1).all() and np.array_equal(best, 3 << 8 | case["mapq"]) and c["unknown_read"] == case["absent"]
+    if name == "trips":
+        assert set(case["kind"].tolist()) == set(range(len(_mapeval_cases.KINDS))) and (hits[case["special"]] >= 1).all()
+        assert {0, 1, 2, 3} <= set(hits.tolist()) and (res["by_mapq"] > 0).all()
+        assert c["reads_correct"] + c["reads_wrong"] + c["reads_unmapped"] + c["missing"] == c["truth_entries"]
+        assert (best[-300:] >> 8 == 3).sum() > 50 and (hits[-300:] > 1).sum() > 50
+    if name == "every_mapq":
+        assert np.array_equal(res["by_mapq"][:, 0], case["right"]) and np.array_equal(res["by_mapq"][:, 1], case["wrong"])
+    if name.startswith("many"):
+        assert best[37] == case["best"] and hits[37] == case["hits"] == 700
+    if name.startswith("names"):
+        assert c["unknown_ref"] == case["absent"] and c["wrong"] == case["absent"] + case["moved"] and c["correct"] == c["truth_entries"]
+
+
+def test_the_lane_round_lines_fall_where_they_are_meant_to():
+    """the text case of tests/test_gpu_mapeval_seams.py:test_fields_at_the_lane_rounds holds its edges, and the plain model reads it"""
+    lines = _mapeval_cases.lane_lines()
+    facts = _mapeval_cases.lane_facts(lines)
+    assert facts["first_tab"] >= set(range(1, 19)) and facts["tabs"] == set(range(16)) and facts["newline"] == set(range(16))
+    assert facts["cigar_start"] == set(range(16)) and facts["op"] == set(range(16)) and facts["digits"] == set(range(1, 10))
+    assert sum(1 for f in lines if len(f) == 11) > 100 and sum(1 for f in lines if len(f) == 12) > 100 and sum(1 for f in lines if len(f) == 41) > 100
+    assert lines[-1][10] == b"" and b"\t".join(lines[-1]).count(b"\t") == 10
+    truth = b"".join(b"\t".join(f) + b"\n" for f in lines)
+    aligned = b"".join(b"\t".join(_mapeval_cases.lane_aligned(f, i)) + b"\n" for i, f in enumerate(lines))
+    c, by = _mapeval.evaluate(_mapeval_cases.LANE_NAMES, [truth], [aligned]).read()
+    assert c["truth_entries"] == c["records"] == len(lines) == c["correct"] + c["wrong"] and c["correct"] > 100 and c["wrong"] > 80 and (by.sum(axis=1) > 0).sum() == 256
+    for o in range(16):
+        assert len(_mapeval_cases.pad_line(o)) % 16 == o
+    for total in (1, 999_999_999, 10 ** 9, 2 ** 40, 2 ** 40 + 1):
+        assert _mapeval.cigar_span(_mapeval_cases.runs_summing_to(total)) == (total, False)
