@@ -2,7 +2,9 @@
 // simmr_bam_sort_*, simmr_bai_*): the entry points over bam_index_kernels.hip.  A translation unit of libsimmr_hip.so of its
 // own; it sees an engine through engine_internal.hpp only.  The engine's slot enum is full, so the state lives in an object of
 // its own that the caller creates on an engine and destroys before the engine (simmr_bam_sort_create / _destroy).  The names
-// table and the argument checks are sam.hip's (sam_names.hpp), the sort is sam_sort.hip's (samsort_sort_pairs).
+// table and the argument checks are sam.hip's (sam_names.hpp), the sort is sam_sort.hip's (samsort_sort_pairs); the plan, the emit
+// and the timer of the sorted records are the shared ones of record_stream_host.hpp, given this unit's traits (BamSortFormat, whose
+// state is the handle's).  simmr_bai_* is this unit's alone.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,7 +13,7 @@
 #include <vector>
 
 #include "bam_index_kernels.hip"
-#include "sam_names.hpp"
+#include "record_stream_host.hpp"
 
 using namespace simmr;
 
@@ -20,32 +22,6 @@ static_assert(BAI_KEY_POS_BITS == 40u, "the canonical key of simmr_sam_sort_emit
 namespace {
 
 uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
-
-struct SortState {
-  SamNameTable nt;
-  DevBuf len, end;         // per read
-  DevBuf key[2], idx[2];   // the pairs, ping and pong; behind the sort the free key buffer holds the canonical keys and the
-                           // free index buffer the sorted lengths
-  DevBuf send;             // the ends in sorted order
-  DevBuf hist, digit_total, rec_off, chunk_sum, chunk_prefix;
-  DevBuf word;             // the error word
-  const uint32_t* perm = nullptr;  // place -> read (nullptr: the identity, a key without bits)
-  const uint64_t* ckey = nullptr;  // the canonical key of every place
-  SamReads reads{};
-  SamEdits edits{};
-  uint32_t paired = 0;
-  uint64_t n_reads = 0, total = 0, epoch = 0;
-  bool ready = false, planned_once = false, emitted = false;
-  hipEvent_t ev[4] = {};
-  uint32_t* err_p() const { return word.as<uint32_t>(); }
-  void release() {
-    nt.release();
-    for (DevBuf* b : {&len, &end, &key[0], &key[1], &idx[0], &idx[1], &send, &hist, &digit_total, &rec_off, &chunk_sum, &chunk_prefix, &word})
-      b->release();
-    for (hipEvent_t& e : ev)
-      if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  }
-};
 
 struct BaiState {
   DevBuf rb, chunk_sum, chunk_prefix;
@@ -75,9 +51,42 @@ uint32_t item_grid(simmr_engine* e, uint64_t n) {
 
 struct simmr_bam_sort {
   simmr_engine* e = nullptr;
-  SortState s;
+  RecordStreamState s;
   BaiState b;
 };
+
+namespace {
+
+struct BamSortFormat : RecordFormat {
+  static constexpr bool SORTED = true, WITH_END = true;
+  static constexpr const char *PLAN = "simmr_bam_sort_plan", *EMIT = "simmr_bam_sort_emit", *NOUN = "sorted BAM", *TIMER = "sorted bam";
+  static constexpr const char *SYNC_PLAN = "sorted BAM plan", *SYNC_SIZE = "sorted BAM size and sort passes", *SYNC_WRITE = "sorted BAM write pass";
+  static constexpr const char* PLAN_REFUSAL =
+      "a read's bytes leave seq[], it is longer than %u bases, it ends at 2^31 or beyond, its edit_off decreases or leaves edits_capacity, or its "
+      "edit_pos do not ascend inside the read";
+  static simmr_engine* engine(simmr_bam_sort* h) { return h->e; }
+  static RecordStreamState* state(simmr_bam_sort* h, bool) { return &h->s; }
+  static void size(hipStream_t st, uint32_t grid, RecordStreamState& s, const SamReads& rd, const SamEdits& ed, uint64_t n, uint32_t paired, uint32_t pos_bits) {
+    hipLaunchKernelGGL(k_bamsort_size, dim3(grid), dim3(256), 0, st, rd, ed, s.nt.names(), s.nt.c_bases.as<const uint64_t>(), n, paired, pos_bits,
+                       s.len.as<uint32_t>(), s.key[0].as<uint64_t>(), s.end.as<uint32_t>(), s.err_p());
+  }
+  static void gather(hipStream_t st, uint32_t grid, RecordStreamState& s, uint64_t n, uint32_t pos_bits, int cur) {
+    hipLaunchKernelGGL(k_bamsort_gather, dim3(grid), dim3(256), 0, st, s.len.as<const uint32_t>(), s.end.as<const uint32_t>(), s.key[cur].as<const uint64_t>(),
+                       s.perm, n, pos_bits, s.idx[cur ^ 1].as<uint32_t>(), s.send.as<uint32_t>(), s.key[cur ^ 1].as<uint64_t>(), s.chunk_sum.as<uint64_t>());
+  }
+  static void scan(hipStream_t st, RecordStreamState& s, uint64_t n_chunks) {
+    hipLaunchKernelGGL(k_bamsort_scan, dim3(1), dim3(256), 0, st, s.chunk_sum.as<const uint64_t>(), s.chunk_prefix.as<uint64_t>(), n_chunks);
+  }
+  static void offsets(hipStream_t st, uint32_t grid, RecordStreamState& s, const uint32_t* slen, uint64_t n) {
+    hipLaunchKernelGGL(k_bamsort_offsets, dim3(grid), dim3(256), 0, st, slen, s.chunk_prefix.as<const uint64_t>(), n, s.off.as<uint64_t>());
+  }
+  static void write(hipStream_t st, uint32_t grid, RecordStreamState& s, uint8_t* dst) {
+    hipLaunchKernelGGL(k_bamsort_write, dim3(grid), dim3(256), 0, st, s.reads, s.edits, s.nt.names(), s.n_reads, s.paired, s.perm,
+                       s.off.as<const uint64_t>(), dst, s.err_p());
+  }
+};
+
+}  // namespace
 
 extern "C" {
 
@@ -103,133 +112,15 @@ void simmr_bam_sort_destroy(simmr_bam_sort* h) {
 
 int simmr_bam_sort_plan(simmr_bam_sort* h, const simmr_sam_names* names, const simmr_reads_out* reads, const simmr_truth_out* truth,
                         uint64_t n_reads, int paired, uint64_t* record_bytes) {
-  if (!h) return SIMMR_EINVAL;
-  simmr_engine* e = h->e;
-  SortState* s = &h->s;
-  s->ready = s->emitted = false;
-  if (int rc = check_plan_args(e, names, reads, truth, n_reads, paired, record_bytes, "simmr_bam_sort_plan")) return rc;
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = sam_sync_check(e, "sorted BAM plan")) return rc;  // (an upload of an earlier plan that failed may still read the host copies)
-  if (int rc = s->nt.build(e, names)) return rc;
-  uint32_t pos_bits = 0, row_bits = 0;
-  if (simmr_sam_sort_key_bits(s->nt.n_rows, s->nt.longest, &pos_bits, &row_bits) != SIMMR_OK)
-    return eng_fail(e, SIMMR_ERANGE, "simmr_bam_sort_plan: %llu named contigs, the longest of %llu bases: the key takes at most 2^24 contigs of "
-                                     "fewer than 2^40 bases", (unsigned long long)s->nt.n_rows, (unsigned long long)s->nt.longest);
-  const uint32_t key_bits = pos_bits + row_bits;
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) SAM_TRY(e, hipEventCreate(&ev));
-  const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1) / SAM_CHUNK, n_tiles = (n_reads + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
-  const uint64_t n1 = std::max<uint64_t>(n_reads, 1);
-  if (!s->nt.ensure(true) || !s->len.ensure(n1 * 4) || !s->end.ensure(n1 * 4) || !s->send.ensure(n1 * 4) || !s->key[0].ensure(n1 * 8) ||
-      !s->key[1].ensure(n1 * 8) || !s->idx[0].ensure(n1 * 4) || !s->idx[1].ensure(n1 * 4) ||
-      !s->hist.ensure(std::max<uint64_t>(n_tiles, 1) * SAMSORT_PAIRS_DIGITS * 4) || !s->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4) ||
-      !s->rec_off.ensure((n_reads + 1) * 8) || !s->chunk_sum.ensure(std::max<uint64_t>(n_chunks, 1) * 8) ||
-      !s->chunk_prefix.ensure((n_chunks + 1) * 8) || !s->word.ensure(16))
-    return eng_fail(e, SIMMR_ENOMEM, "sorted BAM plan allocation failed (%llu reads)", (unsigned long long)n_reads);
-  hipStream_t st = eng_stream(e);
-  SAM_TRY(e, s->nt.upload(st, true));
-  SAM_TRY(e, hipMemsetAsync(s->word.p, 0, 16, st));
-  SAM_TRY(e, hipEventRecord(s->ev[0], st));
-  const uint32_t grid = (uint32_t)std::max<uint64_t>(1, n_chunks);  // a workgroup per chunk (fewer than 2^21 of them)
-  if (n_reads > 0) {
-    hipLaunchKernelGGL(k_bamsort_size, dim3(grid), dim3(256), 0, st, sam_reads(reads), sam_edits(truth), s->nt.names(),
-                       s->nt.c_bases.as<const uint64_t>(), n_reads, paired ? 1u : 0u, pos_bits, s->len.as<uint32_t>(), s->key[0].as<uint64_t>(),
-                       s->end.as<uint32_t>(), s->err_p());
-    uint64_t* const keys[2] = {s->key[0].as<uint64_t>(), s->key[1].as<uint64_t>()};
-    uint32_t* const idxs[2] = {s->idx[0].as<uint32_t>(), s->idx[1].as<uint32_t>()};
-    const int cur = samsort_sort_pairs(st, keys, idxs, s->hist.as<uint32_t>(), s->digit_total.as<uint32_t>(), n_reads, key_bits);
-    s->perm = key_bits > 0u ? s->idx[cur].as<const uint32_t>() : nullptr;
-    s->ckey = s->key[cur ^ 1].as<const uint64_t>();
-    uint32_t* slen = s->idx[cur ^ 1].as<uint32_t>();
-    hipLaunchKernelGGL(k_bamsort_gather, dim3(grid), dim3(256), 0, st, s->len.as<const uint32_t>(), s->end.as<const uint32_t>(),
-                       s->key[cur].as<const uint64_t>(), s->perm, n_reads, pos_bits, slen, s->send.as<uint32_t>(), s->key[cur ^ 1].as<uint64_t>(),
-                       s->chunk_sum.as<uint64_t>());
-    hipLaunchKernelGGL(k_bamsort_scan, dim3(1), dim3(256), 0, st, s->chunk_sum.as<const uint64_t>(), s->chunk_prefix.as<uint64_t>(), n_chunks);
-    hipLaunchKernelGGL(k_bamsort_offsets, dim3(grid), dim3(256), 0, st, (const uint32_t*)slen, s->chunk_prefix.as<const uint64_t>(), n_reads,
-                       s->rec_off.as<uint64_t>());
-  } else {
-    SAM_TRY(e, hipMemsetAsync(s->rec_off.p, 0, 8, st));
-  }
-  SAM_TRY(e, hipEventRecord(s->ev[1], st));
-  uint64_t total = 0;
-  uint32_t errw = 0;
-  SAM_TRY(e, hipMemcpyAsync(&total, s->rec_off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, st));
-  SAM_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, "sorted BAM size and sort passes")) return rc;
-  s->planned_once = true;
-  if (errw & 2u)
-    return eng_fail(e, SIMMR_EINVAL, "a read's genome / contig has no name, or the read ends behind its contig's staged length");
-  if (errw)
-    return eng_fail(e, SIMMR_EINVAL, "a read's bytes leave seq[], it is longer than %u bases, it ends at 2^31 or beyond, its edit_off decreases or "
-                                     "leaves edits_capacity, or its edit_pos do not ascend inside the read", SAM_MAX_L);
-  s->reads = sam_reads(reads);
-  s->edits = sam_edits(truth);
-  s->paired = paired ? 1u : 0u;
-  s->n_reads = n_reads;
-  s->total = total;
-  s->epoch = eng_staging_epoch(e);
-  s->ready = true;
-  *record_bytes = total;
-  return SIMMR_OK;
+  return record_plan<BamSortFormat>(h, names, reads, truth, n_reads, paired, record_bytes);
 }
 
 int simmr_bam_sort_emit(simmr_bam_sort* h, const simmr_reads_out* reads, const simmr_truth_out* truth, uint8_t* dst, uint64_t dst_capacity,
                         uint64_t* key_out, uint64_t* rec_off_out, uint32_t* end_out) {
-  if (!h) return SIMMR_EINVAL;
-  simmr_engine* e = h->e;
-  SortState* s = &h->s;
-  if (!reads || !truth) return eng_fail(e, SIMMR_EINVAL, "simmr_bam_sort_emit: NULL argument");
-  s->emitted = false;
-  SamReads now_r{};  // (zeroed first: the structs are compared as bytes, padding included)
-  SamEdits now_e{};
-  std::memset(&now_r, 0, sizeof now_r);
-  std::memset(&now_e, 0, sizeof now_e);
-  assign_reads(&now_r, reads);
-  assign_edits(&now_e, truth);
-  if (!s->ready || std::memcmp(&now_r, &s->reads, sizeof now_r) != 0 || std::memcmp(&now_e, &s->edits, sizeof now_e) != 0)
-    return eng_fail(e, SIMMR_ESTATE, "simmr_bam_sort_emit called without a simmr_bam_sort_plan for these columns");
-  if (s->epoch != eng_staging_epoch(e)) return eng_fail(e, SIMMR_ESTATE, "a genome was staged since simmr_bam_sort_plan: plan again");
-  if (int rc = check_columns(e, reads, truth, "simmr_bam_sort_emit")) return rc;
-  if (dst_capacity < s->total)
-    return eng_fail(e, SIMMR_ERANGE, "dst_capacity %llu < %llu bytes planned", (unsigned long long)dst_capacity, (unsigned long long)s->total);
-  if (s->total > 0 && !dst) return eng_fail(e, SIMMR_EINVAL, "simmr_bam_sort_emit: NULL dst");
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
-  hipStream_t st = eng_stream(e);
-  SAM_TRY(e, hipEventRecord(s->ev[2], st));
-  if (s->n_reads > 0) {
-    const uint64_t n_batches = (s->n_reads + SAM_WG_READS - 1) / SAM_WG_READS;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(n_batches, (uint64_t)eng_cu_count(e) * SAM_WGS_PER_CU);
-    hipLaunchKernelGGL(k_bamsort_write, dim3(grid), dim3(256), 0, st, s->reads, s->edits, s->nt.names(), s->n_reads, s->paired, s->perm,
-                       s->rec_off.as<const uint64_t>(), dst, s->err_p());
-    if (key_out) SAM_TRY(e, hipMemcpyAsync(key_out, s->ckey, s->n_reads * 8, hipMemcpyDeviceToDevice, st));
-    if (end_out) SAM_TRY(e, hipMemcpyAsync(end_out, s->send.p, s->n_reads * 4, hipMemcpyDeviceToDevice, st));
-  }
-  if (rec_off_out) SAM_TRY(e, hipMemcpyAsync(rec_off_out, s->rec_off.p, (s->n_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
-  SAM_TRY(e, hipEventRecord(s->ev[3], st));
-  uint32_t errw = 0;
-  SAM_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, "sorted BAM write pass")) return rc;
-  s->emitted = true;
-  if (errw) {
-    s->ready = false;
-    return eng_fail(e, SIMMR_EINVAL, "the columns changed since simmr_bam_sort_plan: a read failed the bounds check of the write pass (no store "
-                                     "left its record)");
-  }
-  return SIMMR_OK;
+  return record_emit<BamSortFormat>(h, reads, truth, dst, dst_capacity, key_out, rec_off_out, end_out);
 }
 
-int simmr_last_bam_sort_ms(simmr_bam_sort* h, float* ms) {
-  if (!h || !ms) return SIMMR_EINVAL;
-  simmr_engine* e = h->e;
-  SortState* s = &h->s;
-  if (!s->planned_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_bam_sort_plan yet");
-  if (int rc = sam_sync_check(e, "sorted bam")) return rc;
-  float a = 0.f, b = 0.f;
-  SAM_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->emitted) SAM_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
-  *ms = a + b;
-  return SIMMR_OK;
-}
+int simmr_last_bam_sort_ms(simmr_bam_sort* h, float* ms) { return record_ms<BamSortFormat>(h, ms); }
 
 int simmr_bam_sort_ref_lengths(simmr_bam_sort* h, uint64_t* lengths, uint64_t capacity, uint64_t* n_rows) {
   if (!h) return SIMMR_EINVAL;

@@ -1,6 +1,6 @@
 // bam_index_kernels.hip — the BAM records in coordinate order and the BAI index of a coordinate-sorted record stream
 // (include/simmr_hip.h: simmr_bam_sort_*, simmr_bai_*) on gfx950.  Included by bam_index.hip alone, a translation unit of
-// libsimmr_hip.so of its own.  The record routine is bam_kernels.hip's (included without its kernels), the scans' bodies are
+// libsimmr_hip.so of its own.  The record policy (BamRec) is bam_kernels.hip's (included without its kernels), the scans' bodies are
 // sam_kernels.hip's, the sort is sam_sort.hip's (samsort_sort_pairs, engine_internal.hpp): a record's bytes cannot differ from
 // simmr_bam_emit's, only its place does.
 //
@@ -8,12 +8,14 @@
 // (atomicMax) and the smallest virtual offset of a window (atomicMin): values, which do not depend on the order.
 //
 // The sorted records, five kernels:
-//   k_bamsort_size     every record's length (bam_record<false>), its sort key row << P | lo after the bound check of the
+//   k_bamsort_size     every record's length (BamRec::size), its sort key row << P | lo after the bound check of the
 //                      sorted SAM (max(start, end) <= the staged length of the read's contig), and end[r]: the exclusive end
-//                      of the interval bam_record gives bam_reg2bin (lo + L, or lo + 1 for a read without bases);
+//                      of the interval the record gives bam_reg2bin (lo + L, or lo + 1 for a read without bases);
 //   k_bamsort_gather   lengths and ends in sorted order, the sum of every chunk of SAM_CHUNK lengths, the canonical keys;
 //   k_bamsort_scan, k_bamsort_offsets   the chunked scan of sam_kernels.hip: rec_off[0 .. n];
-//   k_bamsort_write    bam_record<true> for place i with r = perm[i]: every store bounded by rec_off[i + 1] - rec_off[i].
+//   k_bamsort_write    BamRec::write for place i with r = perm[i]: every store bounded by rec_off[i + 1] - rec_off[i].
+// The bodies of the size, gather and write kernels are rec_size_keyed, rec_gather and rec_write_places of record_stream.hpp,
+// shared with the sorted SAM; the record policy is bam_kernels.hip's BamRec, so this file holds no record routine.
 //
 // The index, nine kernels.  Input: key[i] = row << 40 | lo, end[i], rec_off[0 .. n] of n records in file order, and `base`,
 // the uncompressed bytes in front of record 0.  The virtual offset of uncompressed position p is
@@ -44,7 +46,7 @@
 
 namespace simmr {
 
-#define BAI_KEY_POS_BITS 40u      /* the canonical key: row << 40 | lo (SAMSORT_KEY_POS_BITS) */
+#define BAI_KEY_POS_BITS 40u      /* the canonical key: row << 40 | lo (REC_KEY_POS_BITS, record_stream.hpp) */
 #define BAI_BIN_BITS 16u          /* a run's key: row << 16 | bin */
 #define BAI_MAX_END 0x20000000u   /* 2^29: what the six bin levels cover */
 #define BAI_WINDOW_BITS 14u       /* the linear index: windows of 16384 bases */
@@ -53,40 +55,15 @@ namespace simmr {
 #define BAI_ERR_ORDER 1u          /* keys descend, rec_off decreases, a row outside n_ref, an empty interval */
 #define BAI_ERR_RANGE 2u          /* a record ends beyond 2^29 */
 
+static_assert(BAI_KEY_POS_BITS == REC_KEY_POS_BITS, "one canonical key for the sorted SAM, the sorted BAM and the index");
+
 // ---- the sorted records -------------------------------------------------------------------------------------------------
 // A workgroup takes chunks of SAM_CHUNK consecutive reads, 16 at a time, a row of 16 lanes per read.  A read outside its
 // contig (or without a named contig) sets the error word and has nothing else loaded or stored for it but zeros.
 extern "C" __global__ void __launch_bounds__(256)
 k_bamsort_size(const SamReads rd, const SamEdits ed, const SamNames nm, const uint64_t* __restrict__ c_bases, uint64_t n_reads, uint32_t paired,
                uint32_t pos_bits, uint32_t* __restrict__ len, uint64_t* __restrict__ key, uint32_t* __restrict__ end, uint32_t* __restrict__ err) {
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1u) / SAM_CHUNK;
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-    for (uint32_t it = 0; it < SAM_CHUNK / SAM_WG_READS; it++) {
-      const uint64_t r = chunk * SAM_CHUNK + it * SAM_WG_READS + row;
-      if (r >= n_reads) continue;  // (uniform over the row)
-      const uint64_t a = rd.start[r], b = rd.end[r];
-      const uint64_t lo = a < b ? a : b, hi = a < b ? b : a;
-      const uint32_t g = rd.genome[r], c = rd.contig[r];
-      bool ok = g < nm.n_slots;
-      if (ok) ok = c < nm.g_ncontig[g];
-      uint64_t crow = 0;
-      if (ok) {
-        crow = (uint64_t)nm.g_cbase[g] + c;
-        ok = hi <= c_bases[crow];
-      }
-      uint32_t bytes = 0, e = 0;
-      uint64_t k = 0;
-      if (ok) {
-        bytes = bam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, err);
-        k = (crow << pos_bits) | lo;  // (lo <= hi <= the contig's length < 2^pos_bits)
-        e = bytes ? (uint32_t)(hi > lo ? hi : lo + 1u) : 0u;  // (a record was sized: hi < 2^31)
-      } else if (sub == 0u) {
-        atomicOr(err, 2u);
-      }
-      if (sub == 0u) { len[r] = bytes; key[r] = k; end[r] = e; }
-    }
-  }
+  rec_size_keyed<BamRec, true>(rd, ed, nm, c_bases, n_reads, paired, pos_bits, len, key, end, err);
 }
 
 // a workgroup per chunk, four consecutive places per thread; perm == nullptr: place i holds read i (a key without bits)
@@ -95,27 +72,7 @@ k_bamsort_gather(const uint32_t* __restrict__ len, const uint32_t* __restrict__ 
                  const uint32_t* __restrict__ perm, uint64_t n, uint32_t pos_bits, uint32_t* __restrict__ slen, uint32_t* __restrict__ send,
                  uint64_t* __restrict__ ckey, uint64_t* __restrict__ chunk_sum) {
   __shared__ uint32_t lds[256];
-  const uint64_t n_chunks = (n + SAM_CHUNK - 1u) / SAM_CHUNK;
-  const uint64_t lo_mask = (1ull << pos_bits) - 1ull;  // (pos_bits <= 40)
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {  // (uniform over the workgroup)
-    const uint64_t i0 = chunk * SAM_CHUNK + 4u * threadIdx.x;
-    uint32_t sum = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < 4u; q++) {
-      const uint64_t i = i0 + q;
-      if (i >= n) continue;
-      const uint64_t r = perm ? perm[i] : i;
-      const uint32_t v = r < n ? len[r] : 0u;
-      const uint64_t k = key[i];
-      slen[i] = v;
-      send[i] = r < n ? end[r] : 0u;
-      ckey[i] = ((k >> pos_bits) << BAI_KEY_POS_BITS) | (k & lo_mask);
-      sum += v;
-    }
-    uint32_t total;  // (a chunk is below 2^30 bytes)
-    (void)sam_wg_scan<uint32_t>(sum, lds, &total);
-    if (threadIdx.x == 0) chunk_sum[chunk] = total;
-  }
+  rec_gather<true>(len, end, key, perm, n, pos_bits, slen, send, ckey, chunk_sum, lds);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -133,13 +90,7 @@ k_bamsort_offsets(const uint32_t* __restrict__ slen, const uint64_t* __restrict_
 extern "C" __global__ void __launch_bounds__(256)
 k_bamsort_write(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, const uint32_t* __restrict__ perm,
                 const uint64_t* __restrict__ rec_off, uint8_t* __restrict__ dst, uint32_t* __restrict__ err) {
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_batches = (n_reads + SAM_WG_READS - 1u) / SAM_WG_READS;
-  for (uint64_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
-    const uint64_t i = batch * SAM_WG_READS + row;
-    const uint64_t r = i < n_reads ? (perm ? (uint64_t)perm[i] : i) : n_reads;  // (a place past the end, like a read past it, has no record)
-    (void)bam_record<true>(rd, ed, nm, r, i, n_reads, paired, sub, rec_off, dst, err);
-  }
+  rec_write_places<BamRec, true>(rd, ed, nm, n_reads, paired, perm, rec_off, dst, err, nullptr);
 }
 
 // ---- the index ------------------------------------------------------------------------------------------------------------

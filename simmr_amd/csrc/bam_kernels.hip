@@ -12,6 +12,8 @@
 //   k_bam_write    the records, at off[r];
 //   k_bgzf_frame   a workgroup per block of BGZF_BLOCK source bytes: header, stored deflate block, CRC-32, ISIZE.
 // k_bam_size and k_bam_write are one routine, bam_record<WRITE>, so that a record's length and its bytes cannot disagree.
+// The loops around it are rec_size_chunks and rec_write_places of record_stream.hpp, the SAM writer's; BamRec below is what they
+// know of a BAM record.
 //
 // The record (SAM spec 4.2).  Work item: a read, shared by the SAM_LANES = 16 lanes of a DPP row.  No LDS: the few words that
 // need formatting are made in registers by every lane of the row (the same instructions whether one lane or sixteen run them)
@@ -249,6 +251,20 @@ SIMMR_DEV uint32_t bam_record(const SamReads& rd, const SamEdits& ed, const SamN
   return md0 + cursor;
 }
 
+// the record policy of record_stream.hpp; no LDS: a record's pieces are made in registers
+struct BamRec {
+  static constexpr uint32_t SLOT_BYTES = 0u;
+  SIMMR_DEV static uint32_t size(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t n_reads, uint32_t paired,
+                                 uint32_t sub, uint32_t* __restrict__ err) {
+    return bam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, err);
+  }
+  SIMMR_DEV static void write(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t place, uint64_t n_reads,
+                              uint32_t paired, uint32_t sub, uint8_t*, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst,
+                              uint32_t* __restrict__ err) {
+    (void)bam_record<true>(rd, ed, nm, r, place, n_reads, paired, sub, off, dst, err);
+  }
+};
+
 // BAM_ROUTINES_ONLY: the routines without the five kernels, for bam_index_kernels.hip (the sorted writer and the index)
 #ifndef BAM_ROUTINES_ONLY
 // ---- sizes ----------------------------------------------------------------------------------------------------------
@@ -256,25 +272,7 @@ extern "C" __global__ void __launch_bounds__(256)
 k_bam_size(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, uint32_t* __restrict__ len,
            uint64_t* __restrict__ chunk_sum, uint32_t* __restrict__ err) {
   __shared__ uint32_t part[SAM_WG_READS];
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1u) / SAM_CHUNK;
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-    uint32_t acc = 0;  // (a record is below 2^20 bytes: 64 of them fit)
-    for (uint32_t it = 0; it < SAM_CHUNK / SAM_WG_READS; it++) {
-      const uint64_t r = chunk * SAM_CHUNK + it * SAM_WG_READS + row;
-      const uint32_t bytes = bam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, err);
-      if (sub == 0u && r < n_reads) len[r] = bytes;
-      acc += bytes;
-    }
-    if (sub == 0u) part[row] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t s = 0;
-      for (uint32_t i = 0; i < SAM_WG_READS; i++) s += part[i];
-      chunk_sum[chunk] = s;
-    }
-    __syncthreads();
-  }
+  rec_size_chunks<BamRec>(rd, ed, nm, n_reads, paired, len, chunk_sum, err, part);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -293,10 +291,7 @@ k_bam_offsets(const uint32_t* __restrict__ len, const uint64_t* __restrict__ pre
 extern "C" __global__ void __launch_bounds__(256)
 k_bam_write(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, const uint64_t* __restrict__ off,
             uint8_t* __restrict__ dst, uint32_t* __restrict__ err) {
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_batches = (n_reads + SAM_WG_READS - 1u) / SAM_WG_READS;
-  for (uint64_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x)
-    (void)bam_record<true>(rd, ed, nm, batch * SAM_WG_READS + row, batch * SAM_WG_READS + row, n_reads, paired, sub, off, dst, err);
+  rec_write_places<BamRec, false>(rd, ed, nm, n_reads, paired, nullptr, off, dst, err, nullptr);
 }
 #endif  // BAM_ROUTINES_ONLY
 

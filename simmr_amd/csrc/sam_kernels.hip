@@ -10,6 +10,8 @@
 //   k_sam_offsets  a workgroup per chunk: off[r] = its chunk's prefix + the scan of the chunk's lengths;
 //   k_sam_write    the records, at off[r].
 // k_sam_size and k_sam_write are one routine, sam_record<WRITE>, so that a record's length and its bytes cannot disagree.
+// The loops around it — over chunks for the sizes, over row batches for the writer — are rec_size_chunks and rec_write_places
+// of record_stream.hpp, shared with the BAM writer and the sorted forms; SamRec below is what they know of a SAM record.
 //
 // Work item: a read.  SAM_LANES = 16 lanes (one DPP row) share it, as in the truth pass.  The record is five runs:
 //   head   QNAME .. TLEN and their tabs (and "*\t*" for a read without bases): lane 0 of the row formats it into an LDS
@@ -31,9 +33,9 @@
 // as k_truth<true> bounds its stores by `limit`: columns changed between the plan and the emit cannot carry a store out
 // of the record.
 // sam_sort_kernels.hip (the coordinate-sorted form, a unit of its own) includes this file with SAM_ROUTINES_ONLY defined: the
-// constants, the record routine and the scans' bodies without the four kernels, which stay in sam.hip's budget alone.  For
-// that form the place of a record is a parameter of sam_record (`at`: the entry of off[] the record starts at) beside the
-// read it shows: here the two are the same number.
+// constants, the record routine, its policy SamRec, the bodies of record_stream.hpp and the scans' bodies without the four
+// kernels, which stay in sam.hip's budget alone.  For that form the place of a record is a parameter of sam_record (`at`: the
+// entry of off[] the record starts at) beside the read it shows: here the two are the same number.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -411,13 +413,25 @@ SIMMR_DEV void sam_chunk_offsets(const uint32_t* __restrict__ len, const uint64_
   }
 }
 
-// ---- the writer's body: one row of 16 lanes writes the record of read r at entry `at` of off[] --------------------------
-// k_sam_write calls it with at == r (read order); the ordered writer of sam_sort_kernels.hip with r = perm[at].
-SIMMR_DEV void sam_write_row(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t at, uint64_t n_reads,
-                             uint32_t paired, uint32_t sub, uint8_t* slot, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst,
-                             uint32_t* __restrict__ err) {
-  (void)sam_record<true>(rd, ed, nm, r, at, n_reads, paired, sub, slot, off, dst, err);
-}
+// ---- the record policy of record_stream.hpp: what a record is, for the bodies the writers share ---------------------------
+// write: the record of read r at entry `at` of off[] (k_sam_write: at == r; the ordered writer of sam_sort_kernels.hip:
+// r = perm[at]); slot: the row's SLOT_BYTES of LDS.
+struct SamRec {
+  static constexpr uint32_t SLOT_BYTES = SAM_HEAD_PITCH + SAM_TAIL_PITCH;
+  SIMMR_DEV static uint32_t size(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t n_reads, uint32_t paired,
+                                 uint32_t sub, uint32_t* __restrict__ err) {
+    return sam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, nullptr, err);
+  }
+  SIMMR_DEV static void write(const SamReads& rd, const SamEdits& ed, const SamNames& nm, uint64_t r, uint64_t at, uint64_t n_reads,
+                              uint32_t paired, uint32_t sub, uint8_t* slot, const uint64_t* __restrict__ off, uint8_t* __restrict__ dst,
+                              uint32_t* __restrict__ err) {
+    (void)sam_record<true>(rd, ed, nm, r, at, n_reads, paired, sub, slot, off, dst, err);
+  }
+};
+
+}  // namespace simmr
+#include "record_stream.hpp"  // rec_size_chunks, rec_size_keyed, rec_gather, rec_write_places
+namespace simmr {
 
 #ifndef SAM_ROUTINES_ONLY
 // ---- sizes ----------------------------------------------------------------------------------------------------------
@@ -426,25 +440,7 @@ extern "C" __global__ void __launch_bounds__(256)
 k_sam_size(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, uint32_t* __restrict__ len,
            uint64_t* __restrict__ chunk_sum, uint32_t* __restrict__ err) {
   __shared__ uint32_t part[SAM_WG_READS];
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1u) / SAM_CHUNK;
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-    uint32_t acc = 0;  // (a record is below 2^20 bytes: 64 of them fit)
-    for (uint32_t it = 0; it < SAM_CHUNK / SAM_WG_READS; it++) {
-      const uint64_t r = chunk * SAM_CHUNK + it * SAM_WG_READS + row;
-      const uint32_t bytes = sam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, nullptr, err);
-      if (sub == 0u && r < n_reads) len[r] = bytes;
-      acc += bytes;
-    }
-    if (sub == 0u) part[row] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint64_t s = 0;
-      for (uint32_t i = 0; i < SAM_WG_READS; i++) s += part[i];
-      chunk_sum[chunk] = s;
-    }
-    __syncthreads();
-  }
+  rec_size_chunks<SamRec>(rd, ed, nm, n_reads, paired, len, chunk_sum, err, part);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -463,11 +459,8 @@ k_sam_offsets(const uint32_t* __restrict__ len, const uint64_t* __restrict__ pre
 extern "C" __global__ void __launch_bounds__(256)
 k_sam_write(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, const uint64_t* __restrict__ off,
             uint8_t* __restrict__ dst, uint32_t* __restrict__ err) {
-  __shared__ __attribute__((aligned(16))) uint8_t slots[SAM_WG_READS][SAM_HEAD_PITCH + SAM_TAIL_PITCH];
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_batches = (n_reads + SAM_WG_READS - 1u) / SAM_WG_READS;
-  for (uint64_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x)
-    sam_write_row(rd, ed, nm, batch * SAM_WG_READS + row, batch * SAM_WG_READS + row, n_reads, paired, sub, slots[row], off, dst, err);
+  __shared__ __attribute__((aligned(16))) uint8_t slots[SAM_WG_READS][SamRec::SLOT_BYTES];
+  rec_write_places<SamRec, false>(rd, ed, nm, n_reads, paired, nullptr, off, dst, err, &slots[0][0]);
 }
 #endif  // SAM_ROUTINES_ONLY
 

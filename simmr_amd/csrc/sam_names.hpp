@@ -1,6 +1,7 @@
-// sam_names.hpp — what sam.hip and sam_sort.hip share on the host: a growing device buffer, and the names of a plan — per
-// engine genome slot its rows, per row its RNAME in a blob (SamNames, sam_kernels.hip) and, for the sorted form's bound
-// check, the row's staged length.  Internal to the library; each unit that includes it gets its own copy of the routines.
+// sam_names.hpp — what the units over the read columns share on the host: a growing device buffer, and the names of a plan —
+// per engine genome slot its rows, per row its RNAME in a blob (SamNames, sam_kernels.hip) and, for the sorted form's bound
+// check, the row's staged length.  record_stream_host.hpp builds the record writers' plan and emit on it.  Internal to the
+// library; each unit that includes it gets its own copy of the routines.
 #pragma once
 #include <hip/hip_runtime.h>
 

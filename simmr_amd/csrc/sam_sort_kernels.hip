@@ -17,7 +17,9 @@
 //   k_samsort_gather      the lengths in sorted order (len[perm[i]]), the sum of every chunk of SAM_CHUNK of them, and the
 //                         canonical key row << 40 | lo of every place;
 //   k_samsort_scan, k_samsort_offsets   the chunked scan of sam_kernels.hip over the sorted lengths: line_off[0 .. n];
-//   k_samsort_write       sam_write_row for place i with r = perm[i]: every store bounded by line_off[i + 1] - line_off[i].
+//   k_samsort_write       SamRec::write for place i with r = perm[i]: every store bounded by line_off[i + 1] - line_off[i].
+// The bodies of the size, gather and write kernels are rec_size_keyed, rec_gather and rec_write_places of record_stream.hpp,
+// shared with the sorted BAM (bam_index_kernels.hip); the radix passes are this file's own.
 //
 // A tile is a fixed 2048 pairs whatever the grid, so the histogram's layout is a function of n alone.  Wave w of the four
 // owns pairs 512 w .. 512 w + 511 of the tile, 64 at a time (eight rounds): a pair's rank inside the tile is
@@ -41,10 +43,11 @@ namespace simmr {
 #define SAMSORT_TILE 2048u      /* pairs per workgroup and pass: four waves x eight rounds x 64 lanes */
 #define SAMSORT_ROUNDS 8u
 #define SAMSORT_DIGITS (1u << SAMSORT_DIGIT_BITS)
-#define SAMSORT_KEY_POS_BITS 40u /* the canonical key: row << 40 | lo */
+#define SAMSORT_KEY_POS_BITS 40u /* the canonical key: row << 40 | lo (REC_KEY_POS_BITS, record_stream.hpp) */
 
 static_assert(SAMSORT_TILE == 4u * SAMSORT_ROUNDS * 64u, "a tile is four waves of eight rounds");
 static_assert(SAMSORT_DIGITS == 256u, "one digit per thread of the workgroup");
+static_assert(SAMSORT_KEY_POS_BITS == REC_KEY_POS_BITS, "one canonical key for the sorted SAM, the sorted BAM and the index");
 
 // ---- sizes and keys ---------------------------------------------------------------------------------------------------
 // A workgroup takes chunks of SAM_CHUNK consecutive reads, 16 at a time, a row of 16 lanes per read.  A read outside its
@@ -52,33 +55,7 @@ static_assert(SAMSORT_DIGITS == 256u, "one digit per thread of the workgroup");
 extern "C" __global__ void __launch_bounds__(256)
 k_samsort_size(const SamReads rd, const SamEdits ed, const SamNames nm, const uint64_t* __restrict__ c_bases, uint64_t n_reads, uint32_t paired,
                uint32_t pos_bits, uint32_t* __restrict__ len, uint64_t* __restrict__ key, uint32_t* __restrict__ err) {
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1u) / SAM_CHUNK;
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
-    for (uint32_t it = 0; it < SAM_CHUNK / SAM_WG_READS; it++) {
-      const uint64_t r = chunk * SAM_CHUNK + it * SAM_WG_READS + row;
-      if (r >= n_reads) continue;  // (uniform over the row)
-      const uint64_t a = rd.start[r], b = rd.end[r];
-      const uint64_t lo = a < b ? a : b, hi = a < b ? b : a;
-      const uint32_t g = rd.genome[r], c = rd.contig[r];
-      bool ok = g < nm.n_slots;
-      if (ok) ok = c < nm.g_ncontig[g];
-      uint64_t crow = 0;
-      if (ok) {
-        crow = (uint64_t)nm.g_cbase[g] + c;
-        ok = hi <= c_bases[crow];
-      }
-      uint32_t bytes = 0;
-      uint64_t k = 0;
-      if (ok) {
-        bytes = sam_record<false>(rd, ed, nm, r, r, n_reads, paired, sub, nullptr, nullptr, nullptr, err);
-        k = (crow << pos_bits) | lo;  // (lo <= hi <= the contig's length < 2^pos_bits)
-      } else if (sub == 0u) {
-        atomicOr(err, 2u);
-      }
-      if (sub == 0u) { len[r] = bytes; key[r] = k; }
-    }
-  }
+  rec_size_keyed<SamRec, false>(rd, ed, nm, c_bases, n_reads, paired, pos_bits, len, key, nullptr, err);
 }
 
 // ---- a pass of the sort -------------------------------------------------------------------------------------------------
@@ -185,26 +162,7 @@ extern "C" __global__ void __launch_bounds__(256)
 k_samsort_gather(const uint32_t* __restrict__ len, const uint64_t* __restrict__ key, const uint32_t* __restrict__ perm, uint64_t n,
                  uint32_t pos_bits, uint32_t* __restrict__ slen, uint64_t* __restrict__ ckey, uint64_t* __restrict__ chunk_sum) {
   __shared__ uint32_t lds[256];
-  const uint64_t n_chunks = (n + SAM_CHUNK - 1u) / SAM_CHUNK;
-  const uint64_t lo_mask = (1ull << pos_bits) - 1ull;  // (pos_bits <= 40)
-  for (uint64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {  // (uniform over the workgroup)
-    const uint64_t i0 = chunk * SAM_CHUNK + 4u * threadIdx.x;
-    uint32_t sum = 0;
-#pragma unroll
-    for (uint32_t q = 0; q < 4u; q++) {
-      const uint64_t i = i0 + q;
-      if (i >= n) continue;
-      const uint64_t r = perm ? perm[i] : i;
-      const uint32_t v = r < n ? len[r] : 0u;
-      const uint64_t k = key[i];
-      slen[i] = v;
-      ckey[i] = ((k >> pos_bits) << SAMSORT_KEY_POS_BITS) | (k & lo_mask);
-      sum += v;
-    }
-    uint32_t total;  // (a chunk is below 2^30 bytes)
-    (void)sam_wg_scan<uint32_t>(sum, lds, &total);
-    if (threadIdx.x == 0) chunk_sum[chunk] = total;
-  }
+  rec_gather<false>(len, nullptr, key, perm, n, pos_bits, slen, nullptr, ckey, chunk_sum, lds);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -223,14 +181,8 @@ k_samsort_offsets(const uint32_t* __restrict__ slen, const uint64_t* __restrict_
 extern "C" __global__ void __launch_bounds__(256)
 k_samsort_write(const SamReads rd, const SamEdits ed, const SamNames nm, uint64_t n_reads, uint32_t paired, const uint32_t* __restrict__ perm,
                 const uint64_t* __restrict__ line_off, uint8_t* __restrict__ dst, uint32_t* __restrict__ err) {
-  __shared__ __attribute__((aligned(16))) uint8_t slots[SAM_WG_READS][SAM_HEAD_PITCH + SAM_TAIL_PITCH];
-  const uint32_t sub = threadIdx.x & (SAM_LANES - 1u), row = threadIdx.x / SAM_LANES;
-  const uint64_t n_batches = (n_reads + SAM_WG_READS - 1u) / SAM_WG_READS;
-  for (uint64_t batch = blockIdx.x; batch < n_batches; batch += gridDim.x) {
-    const uint64_t i = batch * SAM_WG_READS + row;
-    const uint64_t r = i < n_reads ? (perm ? (uint64_t)perm[i] : i) : n_reads;  // (a place past the end, like a read past it, has no record)
-    sam_write_row(rd, ed, nm, r, i, n_reads, paired, sub, slots[row], line_off, dst, err);
-  }
+  __shared__ __attribute__((aligned(16))) uint8_t slots[SAM_WG_READS][SamRec::SLOT_BYTES];
+  rec_write_places<SamRec, true>(rd, ed, nm, n_reads, paired, perm, line_off, dst, err, &slots[0][0]);
 }
 
 }  // namespace simmr

@@ -286,29 +286,21 @@ struct SideOutputs {
   std::vector<uint32_t> site_genome;
   std::vector<std::string> sam_names;  // --sam: RNAME per sequence, genome by genome (simmr_sam_names), and where each genome's begin
   std::vector<uint32_t> sam_genome, sam_contigs;
-  // --sam-sorted: every range's lines come sorted from the device.  The first range's text waits in memory; from the second
-  // range on the texts lie back to back in a temporary file beside the SAM file, and finish() merges them by the keys and line
-  // lengths kept here (16 bytes a read).  The temporary file goes on every way out.
-  std::vector<SamSortedRun> sam_runs;
-  std::vector<uint8_t> sam_first_text;
-  std::string sam_tmp;
-  uint64_t sam_tmp_bytes = 0;
+  std::vector<const char*> sam_name_ptrs;  // what `sn` points into: built once, by begin_sam
+  simmr_sam_names sn{};
+  // --sam-sorted: every range's lines come sorted from the device, a run with the key and the length of each line (16 bytes a
+  // read); finish() merges the runs (SortedRunSpill, simmr_host.hpp: one run in memory, several in a temporary file beside the SAM file).
+  SortedRunSpill sam_spill{a.sam};
   // --bam-sorted: the same shape for the records of every range, with the ends of the records beside the keys; the header waits
   // for finish(), which frames header and records as one stream.  The state object of simmr_bam_sort_* belongs to the owner of
   // the engines (it has to go before its engine).
-  std::vector<SamSortedRun> bam_runs;
+  SortedRunSpill bam_spill{a.bam};
   std::vector<std::vector<uint32_t>> bam_ends;
-  std::vector<uint8_t> bam_first_rec;
   std::vector<uint64_t> bam_lengths;
-  std::string bam_head, bam_tmp;
-  uint64_t bam_tmp_bytes = 0;
+  std::string bam_head;
   simmr_bam_sort** bam_sort = nullptr;
   static constexpr size_t BAM_PIECE_BLOCKS = 1024;  // blocks of 65 280 source bytes a framing call takes
   bool run_paired = false;  // --overlaps: the run's reads are interleaved mates (set before begin)
-  ~SideOutputs() {
-    if (!sam_tmp.empty()) remove(sam_tmp.c_str());
-    if (!bam_tmp.empty()) remove(bam_tmp.c_str());
-  }
   std::string bam_index_path() const { return a.bam_index.empty() ? a.bam + ".bai" : a.bam_index; }
   bool overlaps() const { return !a.overlaps.empty(); }
   bool vcf() const { return !a.strain_vcf.empty(); }
@@ -350,6 +342,8 @@ struct SideOutputs {
       sam_contigs.push_back((uint32_t)genomes[g].sequence.size());
       for (const Seq& q : genomes[g].sequence) { sam_names.push_back(sam_rname(q.id)); lengths.push_back(q.size); }
     }
+    for (const std::string& n : sam_names) sam_name_ptrs.push_back(n.c_str());
+    sn = simmr_sam_names{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), sam_name_ptrs.data()};
     std::string text, e;
     if (bam() && !begin_bam(eng, lengths)) return false;
     if (!sam()) return true;
@@ -400,9 +394,6 @@ struct SideOutputs {
   }
   // the records of one range: plan, emit, frame, fetch, append
   bool bam_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
-    std::vector<const char*> names;
-    for (const std::string& n : sam_names) names.push_back(n.c_str());
-    simmr_sam_names sn{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), names.data()};
     uint64_t total = 0;
     if (simmr_bam_plan(eng, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--bam", simmr_last_error(eng));
     DeviceMem mem;
@@ -415,9 +406,6 @@ struct SideOutputs {
   }
   // --bam-sorted: the records of one range in coordinate order, with the key, the length and the end of each: a sorted run
   bool bam_sorted_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
-    std::vector<const char*> names;
-    for (const std::string& n : sam_names) names.push_back(n.c_str());
-    simmr_sam_names sn{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), names.data()};
     if (!*bam_sort && simmr_bam_sort_create(eng, bam_sort) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
     uint64_t total = 0;
     if (simmr_bam_sort_plan(*bam_sort, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
@@ -438,27 +426,8 @@ struct SideOutputs {
     run.len.resize(n_reads);
     for (uint64_t i = 0; i < n_reads; i++) run.len[i] = off[i + 1] - off[i];
     bam_ends.push_back(std::move(ends));
-    if (bam_runs.empty()) {  // a run of one range needs no file
-      bam_first_rec = std::move(h);
-      bam_runs.push_back(std::move(run));
-      return true;
-    }
     std::string e;
-    if (bam_tmp.empty()) {
-      bam_tmp = a.bam + ".sorting.tmp";
-      OutFile f(bam_tmp, false);
-      f.append(bam_first_rec.data(), bam_first_rec.size());
-      if (!f.close(&e)) return fail("--bam-sorted", e);
-      bam_tmp_bytes = bam_first_rec.size();
-      std::vector<uint8_t>().swap(bam_first_rec);
-    }
-    run.offset = bam_tmp_bytes;
-    OutFile f(bam_tmp, true);
-    f.append(h.data(), h.size());
-    if (!f.close(&e)) return fail("--bam-sorted", e);
-    bam_tmp_bytes += h.size();
-    bam_runs.push_back(std::move(run));
-    return true;
+    return bam_spill.add(std::move(run), std::move(h), &e) || fail("--bam-sorted", e);
   }
   // The file and its index.  Header and records are one stream: one range's records as they are, several merged by (key, range,
   // place in the range); the stream goes to the device in pieces of whole blocks (BgzfPieces carries the rest), so only the last
@@ -467,6 +436,7 @@ struct SideOutputs {
   bool finish_bam_sorted(simmr_engine* eng) {
     std::string e;
     if (!*bam_sort && simmr_bam_sort_create(eng, bam_sort) != SIMMR_OK) return fail("--bam-sorted", simmr_last_error(eng));
+    const std::vector<SamSortedRun>& bam_runs = bam_spill.runs();
     uint64_t n = 0;
     for (const SamSortedRun& r : bam_runs) n += r.key.size();
     std::vector<uint64_t> key, rec_off(1, 0);
@@ -480,23 +450,14 @@ struct SideOutputs {
       return bam_append_framed(eng, &mem, src, bytes, &out) && out.ok();
     });
     if (!pieces.append(bam_head.data(), bam_head.size())) return false;
-    if (bam_tmp.empty()) {
-      if (!pieces.append(bam_first_rec.data(), bam_first_rec.size())) return false;
+    if (!bam_spill.merge([&](const char* p, size_t len) { return pieces.append(p, len); }, &e)) return err.empty() && !e.empty() ? fail("--bam-sorted", e) : false;
+    if (!bam_spill.spilled()) {
       if (!bam_runs.empty()) {
         key = bam_runs[0].key;
         end = bam_ends[0];
         for (uint64_t len : bam_runs[0].len) rec_off.push_back(rec_off.back() + len);
       }
     } else {
-      FILE* src = fopen(bam_tmp.c_str(), "rb");
-      if (!src) return fail("--bam-sorted", "cannot open " + bam_tmp);
-      bool merged = sam_merge_sorted_runs(
-          bam_runs, [&](uint64_t at, size_t len, char* p) { return fseeko(src, (off_t)at, SEEK_SET) == 0 && fread(p, 1, len, src) == len; },
-          [&](const char* p, size_t len) { return pieces.append(p, len); });
-      fclose(src);
-      remove(bam_tmp.c_str());
-      bam_tmp.clear();
-      if (!merged) return err.empty() ? fail("--bam-sorted", "the merge of the sorted ranges failed") : false;
       // the columns: (key, end, length) of every record, 16 bytes, through the same merge
       std::vector<char> tuples(16 * n), order;
       std::vector<SamSortedRun> col_runs(bam_runs.size());
@@ -513,7 +474,7 @@ struct SideOutputs {
         }
       }
       order.reserve(16 * n);
-      merged = sam_merge_sorted_runs(
+      const bool merged = sam_merge_sorted_runs(
           col_runs, [&](uint64_t from, size_t len, char* p) { if (from + len > tuples.size()) return false; memcpy(p, &tuples[from], len); return true; },
           [&](const char* p, size_t len) { order.insert(order.end(), p, p + len); return true; });
       if (!merged || order.size() != 16 * n) return fail("--bam-sorted", "the merge of the sorted ranges failed");
@@ -555,11 +516,8 @@ struct SideOutputs {
   }
   // the alignment lines of one range, formatted on the device from its columns and truth columns, appended to the file
   bool sam_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
-    std::vector<const char*> names;
-    for (const std::string& n : sam_names) names.push_back(n.c_str());
-    simmr_sam_names sn{(uint32_t)sam_genome.size(), sam_genome.data(), sam_contigs.data(), names.data()};
     uint64_t total = 0;
-    if (a.sam_sorted) return sam_sorted_range(eng, sn, reads, t, n_reads, paired);
+    if (a.sam_sorted) return sam_sorted_range(eng, reads, t, n_reads, paired);
     if (simmr_sam_plan(eng, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--sam", simmr_last_error(eng));
     DeviceMem mem;
     uint8_t* text = nullptr;
@@ -573,8 +531,7 @@ struct SideOutputs {
     return f.close(&e) || fail("--sam", e);
   }
   // the same lines in coordinate order, with the key and the length of each: a sorted run for finish() to merge
-  bool sam_sorted_range(simmr_engine* eng, const simmr_sam_names& sn, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads,
-                        bool paired) {
+  bool sam_sorted_range(simmr_engine* eng, const simmr_reads_out& reads, const simmr_truth_out& t, uint64_t n_reads, bool paired) {
     uint64_t total = 0;
     if (simmr_sam_sort_plan(eng, &sn, &reads, &t, n_reads, paired ? 1 : 0, &total) != SIMMR_OK) return fail("--sam-sorted", simmr_last_error(eng));
     DeviceMem mem;
@@ -588,46 +545,16 @@ struct SideOutputs {
     if (!(mem.fetch(&h, text, total) && mem.fetch(&run.key, key, n_reads) && mem.fetch(&off, line_off, n_reads + 1))) return fail("--sam-sorted", "copy back failed");
     run.len.resize(n_reads);
     for (uint64_t i = 0; i < n_reads; i++) run.len[i] = off[i + 1] - off[i];
-    if (sam_runs.empty()) {  // a run of one range needs no file
-      sam_first_text = std::move(h);
-      sam_runs.push_back(std::move(run));
-      return true;
-    }
     std::string e;
-    if (sam_tmp.empty()) {
-      sam_tmp = a.sam + ".sorting.tmp";
-      OutFile f(sam_tmp, false);
-      f.append(sam_first_text.data(), sam_first_text.size());
-      if (!f.close(&e)) return fail("--sam-sorted", e);
-      sam_tmp_bytes = sam_first_text.size();
-      std::vector<uint8_t>().swap(sam_first_text);
-    }
-    run.offset = sam_tmp_bytes;
-    OutFile f(sam_tmp, true);
-    f.append(h.data(), h.size());
-    if (!f.close(&e)) return fail("--sam-sorted", e);
-    sam_tmp_bytes += h.size();
-    sam_runs.push_back(std::move(run));
-    return true;
+    return sam_spill.add(std::move(run), std::move(h), &e) || fail("--sam-sorted", e);
   }
   // the run's lines behind the header: one range's text as it is, several merged by (key, range, place in the range)
   bool finish_sam_sorted() {
-    std::string e;
+    std::string e, merge_err;
     OutFile out(a.sam, true);
-    if (sam_tmp.empty()) {
-      out.append(sam_first_text.data(), sam_first_text.size());
-      return out.close(&e) || fail("--sam-sorted", e);
-    }
-    FILE* src = fopen(sam_tmp.c_str(), "rb");
-    if (!src) return fail("--sam-sorted", "cannot open " + sam_tmp);
-    const bool merged = sam_merge_sorted_runs(
-        sam_runs, [&](uint64_t at, size_t n, char* p) { return fseeko(src, (off_t)at, SEEK_SET) == 0 && fread(p, 1, n, src) == n; },
-        [&](const char* p, size_t n) { out.append(p, n); return out.ok(); });
-    fclose(src);
-    remove(sam_tmp.c_str());
-    sam_tmp.clear();
+    const bool merged = sam_spill.merge([&](const char* p, size_t n) { out.append(p, n); return out.ok(); }, &merge_err);
     if (!out.close(&e)) return fail("--sam-sorted", e);
-    return merged || fail("--sam-sorted", "the merge of the sorted ranges failed");
+    return merged || fail("--sam-sorted", merge_err);
   }
   // the kept sites go up as one list — genome index, contig, pos: ascending, genome by genome — and the table starts at zero
   bool begin_pileup(simmr_engine* eng) {

@@ -177,6 +177,62 @@ struct SamSortedRun {
 // merged bytes in order; either may answer false, and the merge then ends with false.
 bool sam_merge_sorted_runs(const std::vector<SamSortedRun>& runs, const std::function<bool(uint64_t, size_t, char*)>& read,
                            const std::function<bool(const char*, size_t)>& write);
+// Where the sorted runs of --sam-sorted and --bam-sorted wait for the merge.  The first run's bytes stay in memory: a run of one
+// range needs no file.  From the second run on the runs lie back to back in the temporary file `<out>.sorting.tmp` (each run's
+// `offset` is its place there).  merge() hands the one run as it is, or the runs merged by (key, run, place in the run), to the
+// sink; the file goes there and on every other way out.
+class SortedRunSpill {
+ public:
+  explicit SortedRunSpill(const std::string& out) : tmp_(out + ".sorting.tmp") {}
+  SortedRunSpill(const SortedRunSpill&) = delete;
+  ~SortedRunSpill() { drop(); }
+  const std::vector<SamSortedRun>& runs() const { return runs_; }
+  bool spilled() const { return on_disk_; }
+  // run: the keys and lengths of `bytes`, which are the run's lines or records back to back
+  bool add(SamSortedRun run, std::vector<uint8_t> bytes, std::string* err) {
+    if (runs_.empty()) {
+      first_ = std::move(bytes);
+      runs_.push_back(std::move(run));
+      return true;
+    }
+    if (!on_disk_) {
+      on_disk_ = true;
+      if (!write(first_, false, err)) return false;
+      std::vector<uint8_t>().swap(first_);
+    }
+    run.offset = tmp_bytes_;
+    if (!write(bytes, true, err)) return false;
+    runs_.push_back(std::move(run));
+    return true;
+  }
+  // false with *err untouched: the sink refused the one run; false with *err set: the file or the merge failed
+  bool merge(const std::function<bool(const char*, size_t)>& sink, std::string* err) {
+    if (!on_disk_) return first_.empty() || sink((const char*)first_.data(), first_.size());
+    FILE* src = fopen(tmp_.c_str(), "rb");
+    if (!src) { *err = "cannot open " + tmp_; drop(); return false; }
+    const bool merged = sam_merge_sorted_runs(
+        runs_, [&](uint64_t at, size_t n, char* p) { return fseeko(src, (off_t)at, SEEK_SET) == 0 && fread(p, 1, n, src) == n; }, sink);
+    fclose(src);
+    drop();
+    if (!merged) *err = "the merge of the sorted ranges failed";
+    return merged;
+  }
+
+ private:
+  bool write(const std::vector<uint8_t>& bytes, bool append, std::string* err) {
+    OutFile f(tmp_, append);
+    f.append(bytes.data(), bytes.size());
+    if (!f.close(err)) return false;
+    tmp_bytes_ += bytes.size();
+    return true;
+  }
+  void drop() { if (on_disk_) remove(tmp_.c_str()); }
+  std::string tmp_;
+  std::vector<SamSortedRun> runs_;
+  std::vector<uint8_t> first_;
+  uint64_t tmp_bytes_ = 0;
+  bool on_disk_ = false;
+};
 
 // `simmr-hip --bam FILE --bam-sorted`: the merged stream (header and records) goes to the framing in pieces of a whole number
 // of BGZF blocks (65 280 source bytes each); what does not fill a piece is carried into the next, so only the file's last block

@@ -139,8 +139,16 @@ def test_the_unit_is_built_without_a_slot_of_the_engine():
     unit = (CSRC / "bam_index.hip").read_text()
     assert "eng_ext_slot" not in unit and '#include "engine.hip"' not in unit and '#include "kernels.hip"' not in unit
     k = (CSRC / "bam_index_kernels.hip").read_text()
-    assert "#define BAM_ROUTINES_ONLY" in k and "bam_record<false>" in k and "bam_record<true>" in k and "samsort_sort_pairs" in unit
-    assert "#ifndef BAM_ROUTINES_ONLY" in (CSRC / "bam_kernels.hip").read_text()
+    assert "#define BAM_ROUTINES_ONLY" in k and "samsort_sort_pairs" in unit
+    # the sorted unit sizes and writes through the record policy of the unsorted unit and carries no record routine of its own:
+    # BamRec is bam_record<false> and bam_record<true>, and bam_record is defined once in the library
+    code = re.sub(r"//.*", "", k)
+    assert "rec_size_keyed<BamRec, true>" in code and "rec_write_places<BamRec, true>" in code and "bam_record" not in code
+    bk = (CSRC / "bam_kernels.hip").read_text()
+    policy = bk.split("struct BamRec {")[1].split("};")[0]
+    assert bk.count("struct BamRec {") == 1 and "bam_record<false>" in policy and "bam_record<true>" in policy
+    assert sum(len(re.findall(r"^SIMMR_DEV uint32_t bam_record\(", f.read_text(), re.M)) for f in CSRC.iterdir() if f.suffix in (".hip", ".hpp")) == 1
+    assert "#ifndef BAM_ROUTINES_ONLY" in bk
 
 
 @pytest.fixture(scope="module")

@@ -131,6 +131,8 @@ def test_the_unit_is_built_and_has_its_slot():
     defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(BGZF_\w+)\s+(\d+)u?\b", k, re.M)}
     assert defines["BGZF_BLOCK"] == 0xff00 and defines["BGZF_SEG"] * (defines["BGZF_LANES"] - 1) == defines["BGZF_BLOCK"]
     assert "#define SAM_ROUTINES_ONLY" in k and "bam_record<false>" in k and "bam_record<true>" in k
+    # one routine behind the sizes and the bytes: both kernels go through the policy that names it
+    assert "rec_size_chunks<BamRec>" in k and "rec_write_places<BamRec, false>" in k
 
 
 def test_bam_calls_need_an_engine():

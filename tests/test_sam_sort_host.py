@@ -139,6 +139,41 @@ def test_merge_in_a_stand_alone_program_under_the_sanitizers(tmp_path):
         assert r.returncode == 0 and r.stderr == b"" and r.stdout == expected(runs), (case, r.stderr[-2000:])
 
 
+# one run (no file), two and three runs with equal keys inside and across them: the order is (key, run, place)
+SPILL_RUNS = {
+    "one run": [[(1, "a"), (1, "b"), (7, "c")]],
+    "no run": [],
+    "two runs, equal keys": [[(5, "r0.0"), (5, "r0.1"), (9, "r0.2")], [(5, "r1.0"), (9, "r1.1"), (9, "r1.2")]],
+    "three runs, equal keys": RUNS["equal keys inside a run and across runs"],
+    "three runs, the first one empty": [[], [(2, "r1.0"), (4, "r1.1")], [(2, "r2.0"), (3, "r2.1")]],
+    # more than the merge's window of 2^20 bytes: the sink is called more than once
+    "three runs past a window": [[(i // 2, f"r{k}.{i}." + "x" * 2000) for i in range(200)] for k in range(3)],
+}
+
+
+def test_sorted_run_spill_in_a_stand_alone_program_under_the_sanitizers(tmp_path):
+    """SortedRunSpill of simmr_host.hpp, what --sam-sorted and --bam-sorted keep their ranges in: the merged bytes, a temporary
+    file only from the second run on, and none left behind, also when the sink refuses its second call"""
+    exe = tmp_path / "sam_merge_main"
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", str(exe),
+                           str(ROOT / "tests" / "sam_merge_main.cpp"), str(HOST / "host.cpp")])
+    out = tmp_path / "spill" / "x.sam"
+    out.parent.mkdir()
+    for case, runs in SPILL_RUNS.items():
+        text = f"{len(runs)}\n" + "".join(f"{len(run)}\n" + "".join(f"{k} {t}\n" for k, t in run) for run in runs)
+        r = subprocess.run([str(exe), "spill", str(out)], input=text.encode(), capture_output=True)
+        assert r.returncode == 0 and r.stderr == b"" and r.stdout == expected(runs), (case, r.returncode, r.stderr[-2000:])
+        assert list(out.parent.iterdir()) == [], case
+        want = expected(runs)
+        r = subprocess.run([str(exe), "spill", str(out), "2"], input=text.encode(), capture_output=True)
+        if len(want) > 1 << 20:  # the second call is refused: the first window's bytes, status 1, and still no file
+            assert r.returncode == 1 and r.stderr == b"" and 0 < len(r.stdout) < len(want) and want.startswith(r.stdout), case
+        else:
+            assert r.returncode == 0 and r.stdout == want, case
+        assert list(out.parent.iterdir()) == [], case
+    assert len(expected(SPILL_RUNS["three runs past a window"])) > 1 << 20
+
+
 USAGE_ROWS = [
     (["--genome", "a.fna", "--output", "x.fq", "--sam-sorted"], 2, "error: --sam-sorted needs --sam"),
     (["--genome", "a.fna", "--output", "x.fq", "--sam", "x.sam", "--sam-sorted", "--devices", "0"], 2,
