@@ -35,18 +35,7 @@ struct BamState {
   }
 };
 
-void bam_destroy(void* q) {
-  BamState* s = (BamState*)q;
-  s->rec.release();
-  s->tables.release();
-  delete s;
-}
-
-BamState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_BAM, bam_destroy);
-  if (!*slot && create) *slot = new BamState();
-  return (BamState*)*slot;
-}
+constexpr auto bam_state = unit_state<BamState, ENG_EXT_BAM>;
 
 struct BamFormat : RecordFormat {
   static constexpr const char *PLAN = "simmr_bam_plan", *EMIT = "simmr_bam_emit", *NOUN = "BAM", *TIMER = "bam";
@@ -59,7 +48,7 @@ struct BamFormat : RecordFormat {
     return SIMMR_OK;
   }
   static RecordStreamState* state(simmr_engine* e, bool create) {
-    BamState* s = state_of(e, create);
+    BamState* s = bam_state(e, create);
     return s ? &s->rec : nullptr;
   }
   static void size(hipStream_t st, uint32_t grid, RecordStreamState& s, const SamReads& rd, const SamEdits& ed, uint64_t n, uint32_t paired, uint32_t) {
@@ -107,8 +96,8 @@ int simmr_bgzf_frame(simmr_engine* e, const uint8_t* src, uint64_t n_bytes, uint
   if (!src || !dst) return eng_fail(e, SIMMR_EINVAL, "simmr_bgzf_frame: NULL buffer");
   const uintptr_t s0 = (uintptr_t)src, d0 = (uintptr_t)dst;
   if (s0 < d0 + bound && d0 < s0 + n_bytes) return eng_fail(e, SIMMR_EINVAL, "simmr_bgzf_frame: src and dst overlap");
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
-  BamState* s = state_of(e, true);
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  BamState* s = bam_state(e, true);
   hipStream_t st = eng_stream(e);
   if (!s->tables_ready) {
     if (!s->h_tables) {
@@ -116,14 +105,14 @@ int simmr_bgzf_frame(simmr_engine* e, const uint8_t* src, uint64_t n_bytes, uint
       bgzf::make_tables(s->h_tables.get());
     }
     if (!s->tables.ensure(sizeof(bgzf::Tables))) return eng_fail(e, SIMMR_ENOMEM, "BGZF table allocation failed");
-    SAM_TRY(e, hipMemcpyAsync(s->tables.p, s->h_tables.get(), sizeof(bgzf::Tables), hipMemcpyHostToDevice, st));
-    if (int rc = sam_sync_check(e, "BGZF tables")) return rc;
+    HIP_TRY(e, hipMemcpyAsync(s->tables.p, s->h_tables.get(), sizeof(bgzf::Tables), hipMemcpyHostToDevice, st));
+    if (int rc = sync_check(e, "BGZF tables")) return rc;
     s->tables_ready = true;
   }
   const uint64_t n_blocks = (n_bytes + BGZF_BLOCK - 1) / BGZF_BLOCK;
   const uint32_t grid = (uint32_t)std::min<uint64_t>(n_blocks, (uint64_t)eng_cu_count(e) * 8u);
   hipLaunchKernelGGL(k_bgzf_frame, dim3(grid), dim3(BGZF_LANES), 0, st, src, n_bytes, dst, s->bgzf_tables());
-  if (int rc = sam_sync_check(e, "BGZF framing")) return rc;
+  if (int rc = sync_check(e, "BGZF framing")) return rc;
   *written = bound;
   return SIMMR_OK;
 }

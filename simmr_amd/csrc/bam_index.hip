@@ -36,11 +36,6 @@ struct BaiState {
   const uint32_t* run_perm = nullptr;
   uint64_t n = 0, n_ref = 0, base = 0, n_runs = 0, n_bins = 0, n_windows = 0, total = 0;
   bool ready = false;
-  void release() {
-    for (DevBuf* b : {&rb, &chunk_sum, &chunk_prefix, &run_key[0], &run_key[1], &run_idx[0], &run_idx[1], &run_first, &hist, &digit_total, &bin_key,
-                      &bin_first, &ref_bin0, &ref_rec0, &ref_max_end, &ref_intv, &ref_off, &win_off, &win, &word})
-      b->release();
-  }
 };
 
 uint32_t item_grid(simmr_engine* e, uint64_t n) {
@@ -104,10 +99,8 @@ int simmr_bam_sort_create(simmr_engine* e, simmr_bam_sort** out) {
 void simmr_bam_sort_destroy(simmr_bam_sort* h) {
   if (!h) return;
   if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  h->s.release();
-  h->b.release();
+  delete h;  // (its buffers and events go with it)
   (void)hipGetLastError();
-  delete h;
 }
 
 int simmr_bam_sort_plan(simmr_bam_sort* h, const simmr_sam_names* names, const simmr_reads_out* reads, const simmr_truth_out* truth,
@@ -150,7 +143,7 @@ int simmr_bai_plan(simmr_bam_sort* h, const uint64_t* key, const uint32_t* end, 
       if (ref_len[i] >= (uint64_t)BAI_MAX_END)
         return eng_fail(e, SIMMR_ERANGE, "reference %llu has %llu bases: a BAI index covers contigs of fewer than 2^29 bases (CSI is not written)",
                         (unsigned long long)i, (unsigned long long)ref_len[i]);
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   const uint64_t n_chunks = (n + SAM_CHUNK - 1) / SAM_CHUNK;
   if (!b->rb.ensure(std::max<uint64_t>(n, 1) * 8) || !b->chunk_sum.ensure(std::max<uint64_t>(n_chunks, 1) * 8) || !b->chunk_prefix.ensure((n_chunks + 1) * 8) ||
@@ -158,8 +151,8 @@ int simmr_bai_plan(simmr_bam_sort* h, const uint64_t* key, const uint32_t* end, 
       !b->ref_intv.ensure(std::max<uint64_t>(n_ref, 1) * 4) || !b->ref_off.ensure((n_ref + 1) * 8) || !b->win_off.ensure((n_ref + 1) * 8) ||
       !b->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4) || !b->bin_first.ensure(4) || !b->word.ensure(16))
     return eng_fail(e, SIMMR_ENOMEM, "BAI plan allocation failed (%llu records, %llu references)", (unsigned long long)n, (unsigned long long)n_ref);
-  SAM_TRY(e, hipMemsetAsync(b->word.p, 0, 16, st));
-  SAM_TRY(e, hipMemsetAsync(b->ref_max_end.p, 0, std::max<uint64_t>(n_ref, 1) * 4, st));
+  HIP_TRY(e, hipMemsetAsync(b->word.p, 0, 16, st));
+  HIP_TRY(e, hipMemsetAsync(b->ref_max_end.p, 0, std::max<uint64_t>(n_ref, 1) * 4, st));
   uint64_t n_runs = 0, n_bins = 0;
   b->run_perm = nullptr;
   if (n > 0) {
@@ -170,10 +163,10 @@ int simmr_bai_plan(simmr_bam_sort* h, const uint64_t* key, const uint32_t* end, 
     hipLaunchKernelGGL(k_bai_scan, dim3(1), dim3(256), 0, st, b->chunk_sum.as<const uint64_t>(), b->chunk_prefix.as<uint64_t>(), n_chunks);
     uint32_t errw = 0;
     uint64_t stream_end = 0;
-    SAM_TRY(e, hipMemcpyAsync(&n_runs, b->chunk_prefix.as<uint64_t>() + n_chunks, 8, hipMemcpyDeviceToHost, st));
-    SAM_TRY(e, hipMemcpyAsync(&errw, b->word.p, 4, hipMemcpyDeviceToHost, st));
-    SAM_TRY(e, hipMemcpyAsync(&stream_end, rec_off + n, 8, hipMemcpyDeviceToHost, st));
-    if (int rc = sam_sync_check(e, "BAI check pass")) return rc;
+    HIP_TRY(e, hipMemcpyAsync(&n_runs, b->chunk_prefix.as<uint64_t>() + n_chunks, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipMemcpyAsync(&errw, b->word.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipMemcpyAsync(&stream_end, rec_off + n, 8, hipMemcpyDeviceToHost, st));
+    if (int rc = sync_check(e, "BAI check pass")) return rc;
     if (errw & BAI_ERR_ORDER)
       return eng_fail(e, SIMMR_EINVAL, "simmr_bai_plan: the keys do not ascend, rec_off decreases, a record's reference is not below n_ref, or its "
                                        "interval is empty");
@@ -198,8 +191,8 @@ int simmr_bai_plan(simmr_bam_sort* h, const uint64_t* key, const uint32_t* end, 
     const uint64_t run_chunks = (n_runs + SAM_CHUNK - 1) / SAM_CHUNK;  // (<= n_chunks: the scan's buffers fit)
     hipLaunchKernelGGL(k_bai_count, dim3((uint32_t)run_chunks), dim3(256), 0, st, skey, n_runs, b->chunk_sum.as<uint64_t>());
     hipLaunchKernelGGL(k_bai_scan, dim3(1), dim3(256), 0, st, b->chunk_sum.as<const uint64_t>(), b->chunk_prefix.as<uint64_t>(), run_chunks);
-    SAM_TRY(e, hipMemcpyAsync(&n_bins, b->chunk_prefix.as<uint64_t>() + run_chunks, 8, hipMemcpyDeviceToHost, st));
-    if (int rc = sam_sync_check(e, "BAI run sort")) return rc;
+    HIP_TRY(e, hipMemcpyAsync(&n_bins, b->chunk_prefix.as<uint64_t>() + run_chunks, 8, hipMemcpyDeviceToHost, st));
+    if (int rc = sync_check(e, "BAI run sort")) return rc;
     if (!b->bin_key.ensure(n_bins * 8) || !b->bin_first.ensure((n_bins + 1) * 4))
       return eng_fail(e, SIMMR_ENOMEM, "BAI plan allocation failed (%llu bins)", (unsigned long long)n_bins);
     hipLaunchKernelGGL(k_bai_compact, dim3((uint32_t)run_chunks), dim3(256), 0, st, skey, n_runs, b->chunk_prefix.as<const uint64_t>(), n_bins,
@@ -207,16 +200,16 @@ int simmr_bai_plan(simmr_bam_sort* h, const uint64_t* key, const uint32_t* end, 
     hipLaunchKernelGGL(k_bai_refs, dim3(item_grid(e, n_ref + 1)), dim3(256), 0, st, b->bin_key.as<const uint64_t>(), n_bins, key, n, n_ref,
                        b->ref_bin0.as<uint32_t>(), b->ref_rec0.as<uint32_t>());
   } else {
-    SAM_TRY(e, hipMemsetAsync(b->ref_bin0.p, 0, (n_ref + 1) * 4, st));
-    SAM_TRY(e, hipMemsetAsync(b->ref_rec0.p, 0, (n_ref + 1) * 4, st));
-    SAM_TRY(e, hipMemsetAsync(b->bin_first.p, 0, 4, st));
+    HIP_TRY(e, hipMemsetAsync(b->ref_bin0.p, 0, (n_ref + 1) * 4, st));
+    HIP_TRY(e, hipMemsetAsync(b->ref_rec0.p, 0, (n_ref + 1) * 4, st));
+    HIP_TRY(e, hipMemsetAsync(b->bin_first.p, 0, 4, st));
   }
   hipLaunchKernelGGL(k_bai_layout, dim3(1), dim3(256), 0, st, b->ref_bin0.as<const uint32_t>(), b->bin_first.as<const uint32_t>(),
                      b->ref_max_end.as<const uint32_t>(), n_ref, b->ref_intv.as<uint32_t>(), b->ref_off.as<uint64_t>(), b->win_off.as<uint64_t>());
   uint64_t body = 0, n_windows = 0;
-  SAM_TRY(e, hipMemcpyAsync(&body, b->ref_off.as<uint64_t>() + n_ref, 8, hipMemcpyDeviceToHost, st));
-  SAM_TRY(e, hipMemcpyAsync(&n_windows, b->win_off.as<uint64_t>() + n_ref, 8, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, "BAI layout")) return rc;
+  HIP_TRY(e, hipMemcpyAsync(&body, b->ref_off.as<uint64_t>() + n_ref, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&n_windows, b->win_off.as<uint64_t>() + n_ref, 8, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_check(e, "BAI layout")) return rc;
   if (!b->win.ensure(std::max<uint64_t>(n_windows, 1) * 8)) return eng_fail(e, SIMMR_ENOMEM, "BAI plan allocation failed (%llu windows)", (unsigned long long)n_windows);
   b->key = key; b->end = end; b->rec_off = rec_off;
   b->n = n; b->n_ref = n_ref; b->base = base; b->n_runs = n_runs; b->n_bins = n_bins; b->n_windows = n_windows;
@@ -234,9 +227,9 @@ int simmr_bai_emit(simmr_bam_sort* h, uint8_t* dst, uint64_t dst_capacity) {
   if (dst_capacity < b->total)
     return eng_fail(e, SIMMR_ERANGE, "dst_capacity %llu < %llu bytes planned", (unsigned long long)dst_capacity, (unsigned long long)b->total);
   if (!dst) return eng_fail(e, SIMMR_EINVAL, "simmr_bai_emit: NULL dst");
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  SAM_TRY(e, hipMemsetAsync(b->win.p, 0xff, std::max<uint64_t>(b->n_windows, 1) * 8, st));
+  HIP_TRY(e, hipMemsetAsync(b->win.p, 0xff, std::max<uint64_t>(b->n_windows, 1) * 8, st));
   if (b->n > 0) {
     hipLaunchKernelGGL(k_bai_windows, dim3(item_grid(e, b->n)), dim3(256), 0, st, b->key, b->end, b->rec_off, b->n, b->n_ref, b->base,
                        b->ref_intv.as<const uint32_t>(), b->win_off.as<const uint64_t>(), b->win.as<unsigned long long>());
@@ -248,7 +241,7 @@ int simmr_bai_emit(simmr_bam_sort* h, uint8_t* dst, uint64_t dst_capacity) {
   hipLaunchKernelGGL(k_bai_write_refs, dim3(grid), dim3(256), 0, st, b->ref_bin0.as<const uint32_t>(), b->ref_rec0.as<const uint32_t>(),
                      b->bin_first.as<const uint32_t>(), b->ref_intv.as<const uint32_t>(), b->ref_off.as<const uint64_t>(), b->win_off.as<const uint64_t>(),
                      b->win.as<const uint64_t>(), b->rec_off, b->n, b->n_ref, b->base, dst, b->total);
-  if (int rc = sam_sync_check(e, "BAI write pass")) return rc;
+  if (int rc = sync_check(e, "BAI write pass")) return rc;
   return SIMMR_OK;
 }
 

@@ -1,14 +1,15 @@
 // depth.hip — coverage depth (include/simmr_hip.h: simmr_depth_*): the entry points over depth_kernels.hip.  The second
 // translation unit of libsimmr_hip.so; it sees an engine through engine_internal.hpp only and keeps its state in the
-// engine's opaque slot (freed by simmr_engine_destroy through the hook given there).
+// engine's opaque slot (host_support.hpp: unit_state; simmr_engine_destroy deletes it, and its members free what they own).
 #include <hip/hip_runtime.h>
 #include <string.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "depth_kernels.hip"
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 using namespace simmr;
 
@@ -22,60 +23,24 @@ struct DepthState {
   std::vector<uint64_t> fwin;             // n_contigs + 1, of the last summarize
   uint64_t n_positions = 0, n_tiles = 0, epoch = 0, added = 0, resets = 0;
   bool ready = false, timed = false, emitted = false, summarized = false;
-  void *diff = nullptr, *tile_sum = nullptr, *d_slots = nullptr, *d_cfirst = nullptr, *d_fwin = nullptr, *d_out = nullptr;
-  size_t diff_cap = 0, tile_cap = 0, slots_cap = 0, cfirst_cap = 0, fwin_cap = 0, out_cap = 0;  // bytes
-  hipEvent_t ev[6] = {};                  // add, emit, summarize: begin / end
+  DevBuf diff, tile_sum, d_slots, d_cfirst, d_fwin, d_out;
+  Events<6> ev;                           // add, emit, summarize: begin / end
 
   size_t diff_bytes() const { return (size_t)n_tiles * DEPTH_TILE * 4u; }  // n_positions + 1 entries, padded to whole tiles
-  int32_t* diff_p() const { return (int32_t*)diff; }
-  uint32_t* err_p() const { return (uint32_t*)((char*)diff + diff_bytes()); }  // the sticky error word, behind the array
+  int32_t* diff_p() const { return diff.as<int32_t>(); }
+  uint32_t* err_p() const { return (uint32_t*)(diff.as<char>() + diff_bytes()); }  // the sticky error word, behind the array
 };
 
-bool ensure(void** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-  *cap = bytes;
-  return true;
-}
-
-void depth_destroy(void* q) {
-  DepthState* s = (DepthState*)q;
-  for (void* p : {s->diff, s->tile_sum, s->d_slots, s->d_cfirst, s->d_fwin, s->d_out})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t ev : s->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete s;
-}
-
-DepthState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_DEPTH, depth_destroy);
-  if (!*slot && create) *slot = new DepthState();
-  return (DepthState*)*slot;
-}
-
-#define DEPTH_TRY(e, call)                                                                  \
-  do {                                                                                      \
-    hipError_t _s = (call);                                                                 \
-    if (_s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); \
-  } while (0)
-
-int sync_check(simmr_engine* e, const char* what) {
-  hipError_t s = hipStreamSynchronize(eng_stream(e));
-  if (s == hipSuccess) s = hipGetLastError();
-  if (s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  return SIMMR_OK;
-}
+constexpr auto depth_state = unit_state<DepthState, ENG_EXT_DEPTH>;
 
 }  // namespace
 
 // engine_internal.hpp: what regions.hip reads of the layout
 namespace simmr {
 bool depth_layout(simmr_engine* e, DepthLayout* out) {
-  DepthState* s = state_of(e, false);
+  DepthState* s = depth_state(e, false);
   if (!s || !s->ready) return false;
-  *out = DepthLayout{s->cfirst.data(), (const uint64_t*)s->d_cfirst, s->c_genome.data(), s->c_contig.data(), s->c_genome.size(),
+  *out = DepthLayout{s->cfirst.data(), (const uint64_t*)s->d_cfirst.p, s->c_genome.data(), s->c_contig.data(), s->c_genome.size(),
                      s->n_positions, s->epoch, s->resets};
   return true;
 }
@@ -85,38 +50,30 @@ extern "C" {
 
 int simmr_depth_reset(simmr_engine* e, uint64_t* n_positions, uint64_t* n_contigs) {
   if (!e) return SIMMR_EINVAL;
-  DEPTH_TRY(e, hipSetDevice(eng_device(e)));
-  DepthState* s = state_of(e, true);
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  DepthState* s = depth_state(e, true);
   s->ready = false;
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) DEPTH_TRY(e, hipEventCreate(&ev));
-  const uint32_t n_slots = eng_genome_slots(e);
+  if (int rc = s->ev.create_missing(e)) return rc;
+  StagedRows rows = staged_rows(e, true);
+  const uint32_t n_slots = rows.n_slots();
   s->slots.assign(n_slots, DepthSlot{0u, 0u});
-  s->cfirst.assign(1, 0ull);
-  s->c_genome.clear();
-  s->c_contig.clear();
-  for (uint32_t g = 0; g < n_slots; g++) {
-    const uint32_t nc = eng_contig_count(e, g);
-    s->slots[g] = DepthSlot{(uint32_t)s->c_genome.size(), nc};
-    for (uint32_t c = 0; c < nc; c++) {
-      s->cfirst.push_back(s->cfirst.back() + eng_contig_len(e, g, c));
-      s->c_genome.push_back(g);
-      s->c_contig.push_back(c);
-    }
-  }
+  for (uint32_t g = 0; g < n_slots; g++) s->slots[g] = DepthSlot{rows.cbase[g], rows.ncontig[g]};
+  s->cfirst = std::move(rows.first);
+  s->c_genome = std::move(rows.genome);
+  s->c_contig = std::move(rows.contig);
   s->n_positions = s->cfirst.back();
   s->n_tiles = (s->n_positions + 1 + DEPTH_TILE - 1) / DEPTH_TILE;
   const uint64_t tops = (s->n_tiles + DEPTH_TOPS_WIDTH - 1) / DEPTH_TOPS_WIDTH * DEPTH_TOPS_WIDTH;
-  if (!ensure(&s->diff, &s->diff_cap, s->diff_bytes() + 16) || !ensure(&s->tile_sum, &s->tile_cap, tops * 4) ||
-      !ensure(&s->d_slots, &s->slots_cap, std::max<size_t>(n_slots, 1) * sizeof(DepthSlot)) ||
-      !ensure(&s->d_cfirst, &s->cfirst_cap, s->cfirst.size() * 8) || !ensure(&s->d_fwin, &s->fwin_cap, s->cfirst.size() * 8) ||
-      !ensure(&s->d_out, &s->out_cap, (3 * s->c_genome.size() + SIMMR_DEPTH_HIST_BINS) * 8))
+  if (!s->diff.ensure(s->diff_bytes() + 16) || !s->tile_sum.ensure(tops * 4) ||
+      !s->d_slots.ensure(std::max<size_t>(n_slots, 1) * sizeof(DepthSlot)) ||
+      !s->d_cfirst.ensure(s->cfirst.size() * 8) || !s->d_fwin.ensure(s->cfirst.size() * 8) ||
+      !s->d_out.ensure((3 * s->c_genome.size() + SIMMR_DEPTH_HIST_BINS) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "depth array allocation failed (%llu positions)", (unsigned long long)s->n_positions);
   hipStream_t st = eng_stream(e);
-  DEPTH_TRY(e, hipMemsetAsync(s->diff, 0, s->diff_bytes() + 16, st));
-  DEPTH_TRY(e, hipMemsetAsync(s->tile_sum, 0, tops * 4, st));
-  if (n_slots) DEPTH_TRY(e, hipMemcpyAsync(s->d_slots, s->slots.data(), n_slots * sizeof(DepthSlot), hipMemcpyHostToDevice, st));
-  DEPTH_TRY(e, hipMemcpyAsync(s->d_cfirst, s->cfirst.data(), s->cfirst.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemsetAsync(s->diff.p, 0, s->diff_bytes() + 16, st));
+  HIP_TRY(e, hipMemsetAsync(s->tile_sum.p, 0, tops * 4, st));
+  if (n_slots) HIP_TRY(e, hipMemcpyAsync(s->d_slots.p, s->slots.data(), n_slots * sizeof(DepthSlot), hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemcpyAsync(s->d_cfirst.p, s->cfirst.data(), s->cfirst.size() * 8, hipMemcpyHostToDevice, st));
   s->epoch = eng_staging_epoch(e);
   s->added = 0;
   s->timed = s->emitted = s->summarized = false;
@@ -133,20 +90,20 @@ int simmr_depth_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_re
   if (!reads) return eng_fail(e, SIMMR_EINVAL, "simmr_depth_add: NULL argument");
   if (!reads->start || !reads->end || !reads->contig || !reads->genome)
     return eng_fail(e, SIMMR_EINVAL, "simmr_depth_add needs start, end, contig and genome");
-  DepthState* s = state_of(e, false);
+  DepthState* s = depth_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_depth_add called before simmr_depth_reset");
   if (s->epoch != eng_staging_epoch(e))
     return eng_fail(e, SIMMR_ESTATE, "a genome was staged since simmr_depth_reset: the layout of depth[] is the reset's");
   if (n_reads >= (1ull << 31) || s->added + n_reads >= (1ull << 31))
     return eng_fail(e, SIMMR_ERANGE, "the reads added since simmr_depth_reset would reach 2^31");
-  DEPTH_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  DEPTH_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, hipEventRecord(s->ev[0], st));
   if (n_reads > 0)
     hipLaunchKernelGGL(k_depth_mark, dim3((uint32_t)((n_reads + DEPTH_WG - 1) / DEPTH_WG)), dim3(DEPTH_WG), 0, st, reads->start, reads->end,
-                       reads->contig, reads->genome, n_reads, (const DepthSlot*)s->d_slots, (uint32_t)s->slots.size(),
-                       (const uint64_t*)s->d_cfirst, s->diff_p(), s->err_p());
-  DEPTH_TRY(e, hipEventRecord(s->ev[1], st));
+                       reads->contig, reads->genome, n_reads, (const DepthSlot*)s->d_slots.p, (uint32_t)s->slots.size(),
+                       (const uint64_t*)s->d_cfirst.p, s->diff_p(), s->err_p());
+  HIP_TRY(e, hipEventRecord(s->ev[1], st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "depth launch failed: %s", hipGetErrorString(rc));
   s->added += n_reads;
@@ -157,26 +114,26 @@ int simmr_depth_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_re
 
 int simmr_depth_emit(simmr_engine* e, uint32_t* depth_device, uint64_t capacity) {
   if (!e) return SIMMR_EINVAL;
-  DepthState* s = state_of(e, false);
+  DepthState* s = depth_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_depth_emit called before simmr_depth_reset");
   if (capacity < s->n_positions)
     return eng_fail(e, SIMMR_ERANGE, "capacity %llu < %llu positions", (unsigned long long)capacity, (unsigned long long)s->n_positions);
   if (s->n_positions > 0 && (!depth_device || ((uintptr_t)depth_device & 15u)))
     return eng_fail(e, SIMMR_EINVAL, "simmr_depth_emit: depth_device must be a 16-byte aligned device pointer");
-  DEPTH_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  DEPTH_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, hipEventRecord(s->ev[2], st));
   if (s->n_positions > 0) {
     const uint32_t grid = (uint32_t)s->n_tiles;
-    hipLaunchKernelGGL(k_depth_tile_sums, dim3(grid), dim3(DEPTH_WG), 0, st, (const depth_v4i*)s->diff, (int32_t*)s->tile_sum);
-    hipLaunchKernelGGL(k_depth_scan_tiles, dim3(1), dim3(DEPTH_WG), 0, st, (int32_t*)s->tile_sum, s->n_tiles);
+    hipLaunchKernelGGL(k_depth_tile_sums, dim3(grid), dim3(DEPTH_WG), 0, st, (const depth_v4i*)s->diff.p, (int32_t*)s->tile_sum.p);
+    hipLaunchKernelGGL(k_depth_scan_tiles, dim3(1), dim3(DEPTH_WG), 0, st, (int32_t*)s->tile_sum.p, s->n_tiles);
     // (the tile that holds only the extra last slot has nothing to write)
     hipLaunchKernelGGL(k_depth_apply, dim3((uint32_t)((s->n_positions + DEPTH_TILE - 1) / DEPTH_TILE)), dim3(DEPTH_WG), 0, st,
-                       (const depth_v4i*)s->diff, (const int32_t*)s->tile_sum, depth_device, s->n_positions);
+                       (const depth_v4i*)s->diff.p, (const int32_t*)s->tile_sum.p, depth_device, s->n_positions);
   }
-  DEPTH_TRY(e, hipEventRecord(s->ev[3], st));
+  HIP_TRY(e, hipEventRecord(s->ev[3], st));
   uint32_t errw = 0;
-  DEPTH_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "depth scan")) return rc;
   if (s->timed) s->emitted = true;
   if (errw)
@@ -188,7 +145,7 @@ int simmr_depth_emit(simmr_engine* e, uint32_t* depth_device, uint64_t capacity)
 int simmr_depth_contig_first(simmr_engine* e, uint32_t genome_idx, uint32_t contig, uint64_t* first) {
   if (!e) return SIMMR_EINVAL;
   if (!first) return eng_fail(e, SIMMR_EINVAL, "simmr_depth_contig_first: NULL argument");
-  DepthState* s = state_of(e, false);
+  DepthState* s = depth_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_depth_contig_first called before simmr_depth_reset");
   if (genome_idx >= s->slots.size() || contig >= s->slots[genome_idx].n_contigs)
     return eng_fail(e, SIMMR_EINVAL, "genome %u contig %u is not tracked", genome_idx, contig);
@@ -199,7 +156,7 @@ int simmr_depth_contig_first(simmr_engine* e, uint32_t genome_idx, uint32_t cont
 int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_t window, simmr_depth_contig* rows_host,
                           uint64_t rows_capacity, uint64_t* hist_host, simmr_depth_windows* win) {
   if (!e) return SIMMR_EINVAL;
-  DepthState* s = state_of(e, false);
+  DepthState* s = depth_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_depth_summarize called before simmr_depth_reset");
   if (window >= (1u << 30)) return eng_fail(e, SIMMR_EINVAL, "simmr_depth_summarize: window must be below 2^30");
   const uint64_t n_contigs = s->c_genome.size();
@@ -217,14 +174,14 @@ int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_
   if (rows_host && rows_capacity < n_contigs)
     return eng_fail(e, SIMMR_ERANGE, "rows_capacity %llu < %llu contigs", (unsigned long long)rows_capacity, (unsigned long long)n_contigs);
   if (s->n_positions > 0 && !depth_device) return eng_fail(e, SIMMR_EINVAL, "simmr_depth_summarize: NULL depth array");
-  DEPTH_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   // d_out: three words per contig (sum, covered, max), the histogram behind them
   std::vector<unsigned long long> host(3 * n_contigs + SIMMR_DEPTH_HIST_BINS, 0ull);
-  void* const d_out = s->d_out;
-  DEPTH_TRY(e, hipMemsetAsync(d_out, 0, host.size() * 8, st));
-  DEPTH_TRY(e, hipMemcpyAsync(s->d_fwin, s->fwin.data(), s->fwin.size() * 8, hipMemcpyHostToDevice, st));
-  DEPTH_TRY(e, hipEventRecord(s->ev[4], st));
+  void* const d_out = s->d_out.p;
+  HIP_TRY(e, hipMemsetAsync(d_out, 0, host.size() * 8, st));
+  HIP_TRY(e, hipMemcpyAsync(s->d_fwin.p, s->fwin.data(), s->fwin.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipEventRecord(s->ev[4], st));
   if (n_units > 0) {
     // consecutive units per wave: enough waves to fill the device, and fewer than 2^30 positions per wave (unit < 2^30): an
     // LDS bin of the workgroup's four waves stays below 2^32
@@ -235,13 +192,13 @@ int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_
     const uint64_t grid = (n_waves + DEPTH_WG / 64 - 1) / (DEPTH_WG / 64);
     if (grid >= (1ull << 31)) return eng_fail(e, SIMMR_ERANGE, "simmr_depth_summarize: too many windows for one launch");
     unsigned long long* rows = (unsigned long long*)d_out;
-    hipLaunchKernelGGL(k_depth_summarize, dim3((uint32_t)grid), dim3(DEPTH_WG), 0, st, depth_device, (const uint64_t*)s->d_cfirst,
-                       (const uint64_t*)s->d_fwin, (uint32_t)n_contigs, unit, n_units, per_wave,
+    hipLaunchKernelGGL(k_depth_summarize, dim3((uint32_t)grid), dim3(DEPTH_WG), 0, st, depth_device, (const uint64_t*)s->d_cfirst.p,
+                       (const uint64_t*)s->d_fwin.p, (uint32_t)n_contigs, unit, n_units, per_wave,
                        windows ? (unsigned long long*)win->sum : nullptr, windows ? win->covered : nullptr, windows ? win->max : nullptr,
                        rows, rows + 3 * n_contigs);
   }
-  DEPTH_TRY(e, hipEventRecord(s->ev[5], st));
-  DEPTH_TRY(e, hipMemcpyAsync(host.data(), d_out, host.size() * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipEventRecord(s->ev[5], st));
+  HIP_TRY(e, hipMemcpyAsync(host.data(), d_out, host.size() * 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "depth summary")) return rc;
   if (s->timed) s->summarized = true;
   for (uint64_t k = 0; rows_host && k < n_contigs; k++) {
@@ -262,13 +219,13 @@ int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_
 
 int simmr_last_depth_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
-  DepthState* s = state_of(e, false);
+  DepthState* s = depth_state(e, false);
   if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_depth_add yet");
   if (int rc = sync_check(e, "depth")) return rc;
   float a = 0.f, b = 0.f, c = 0.f;
-  DEPTH_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->emitted) DEPTH_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
-  if (s->summarized) DEPTH_TRY(e, hipEventElapsedTime(&c, s->ev[4], s->ev[5]));
+  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+  if (s->emitted) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
+  if (s->summarized) HIP_TRY(e, hipEventElapsedTime(&c, s->ev[4], s->ev[5]));
   *ms = a + b + c;
   return SIMMR_OK;
 }

@@ -27,29 +27,13 @@
 #include "truth_kernels.hip"
 #include "stats_kernels.hip"
 #include "custom_model.hpp"
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 using namespace simmr;
 
 namespace {
 
 thread_local std::string g_create_error;
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    size_t want = bytes + bytes / 8 + 256;
-    if (hipMalloc(&p, want) != hipSuccess) { p = nullptr; return false; }
-    cap = want;
-    return true;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 struct GenomeHost {
   bool staged = false;
@@ -112,11 +96,14 @@ struct simmr_engine {
   std::vector<GenomeHost> genomes;
   DevBuf d_genomes;  // GenomeDev[genomes.size()]
   DevBuf d_tables, d_counters, d_err, d_scalars;
-  hipEvent_t ev_a = nullptr, ev_b = nullptr, ev_c = nullptr, ev_d = nullptr;
-  // The event pairs of the last emits (ev_c / ev_d = the pair of the emit in progress): simmr_emit_kernel_ms_mean averages them
-  // with ONE synchronisation, where asking after every emit (simmr_last_emit_kernel_ms) would wait for each.
+  Events<3> ev_own;  // the three below
+  hipEvent_t &ev_a = ev_own[0], &ev_b = ev_own[1];
+  // The event pairs of the last emits: simmr_emit_kernel_ms_mean averages them with ONE synchronisation, where asking after
+  // every emit (simmr_last_emit_kernel_ms) would wait for each.  The ring owns them; entry 0 is made with the engine.
+  // ev_c / ev_d name the pair of the emit in progress (entry 0 before the first emit) and own nothing.
   static constexpr int EMIT_RING = 64;
-  hipEvent_t ring_c[EMIT_RING] = {}, ring_d[EMIT_RING] = {};
+  Events<EMIT_RING> ring_c, ring_d;
+  hipEvent_t ev_c = nullptr, ev_d = nullptr;
   uint64_t n_emits = 0;
   float last_emit_ms = 0.f, last_plan_ms = 0.f, last_fastq_plan_ms = 0.f;
 
@@ -132,7 +119,8 @@ struct simmr_engine {
   // exchanges the two sets; mark[s] = the work on the caller's stream that read set s when set s was last given up.
   bool overlap = false;
   hipStream_t plan_stream = nullptr;
-  hipEvent_t ev_plan_done = nullptr, ev_mark[2] = {nullptr, nullptr};
+  hipEvent_t& ev_plan_done = ev_own[2];
+  Events<2> ev_mark;
   bool mark_valid[2] = {false, false};
   int cur_set = 0;
   DevBuf s_w_bytes, s_u_off64, s_m_genomes, s_u_contig, s_u_genome, s_u_seed, s_u_len, s_u_a, s_u_b, s_u_qs2, s_u_ms2, s_u_flags,
@@ -170,7 +158,7 @@ struct simmr_engine {
   // ground truth per read (simmr_truth_plan / simmr_truth_emit): counts, their scan, an error word of its own (a plan
   // of the next shard may own d_err), and the columns the plan was made for
   DevBuf tr_nm, tr_off, tr_err;
-  hipEvent_t tr_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // plan begin / end, emit begin / end
+  Events<4> tr_ev;  // plan begin / end, emit begin / end
   bool tr_ready = false, tr_emitted = false;
   uint64_t tr_reads = 0, tr_edits = 0;
   const void *tr_seq = nullptr, *tr_seq_off = nullptr;
@@ -179,11 +167,11 @@ struct simmr_engine {
   // run statistics (simmr_stats_reset / simmr_stats_add / simmr_stats_read): the simmr_run_stats the kernel adds to,
   // followed by its sticky error word
   DevBuf st_tab;
-  hipEvent_t st_ev[2] = {nullptr, nullptr};  // the last add's begin / end
+  Events<2> st_ev;  // the last add's begin / end
   bool st_ready = false, st_timed = false;
 
   // engine_internal.hpp: the simmr_stage_* calls so far, and the states of the library's other translation units
-  // (depth.hip: coverage depth, strain.hip: strain divergence) with the functions that free them
+  // (depth.hip: coverage depth, strain.hip: strain divergence, ...) with the hooks that delete them (host_support.hpp: unit_state)
   uint64_t staging_epoch = 0;
   void* ext_slot[ENG_EXT_COUNT] = {};
   void (*ext_destroy[ENG_EXT_COUNT])(void*) = {};
@@ -198,13 +186,6 @@ struct simmr_engine {
     return code;
   }
 };
-
-#define HIP_TRY(e, call)                                                                  \
-  do {                                                                                    \
-    hipError_t _s = (call);                                                               \
-    if (_s != hipSuccess)                                                                 \
-      return (e)->fail(SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s));      \
-  } while (0)
 
 namespace {
 
@@ -269,14 +250,6 @@ inline uint32_t grid_for(uint64_t n, uint32_t per_block) {
   return (uint32_t)g;
 }
 
-int sync_check(simmr_engine* e, const char* what) {
-  hipError_t s = hipStreamSynchronize(e->stream);
-  if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  s = hipGetLastError();
-  if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  return SIMMR_OK;
-}
-
 int refresh_genome_table(simmr_engine* e) {
   std::vector<GenomeDev> tab(e->genomes.size());
   for (size_t i = 0; i < e->genomes.size(); i++) {
@@ -291,7 +264,7 @@ int refresh_genome_table(simmr_engine* e) {
     }
     tab[i] = d;
   }
-  if (!e->d_genomes.ensure(sizeof(GenomeDev) * std::max<size_t>(tab.size(), 1)))
+  if (!e->d_genomes.ensure_slack(sizeof(GenomeDev) * std::max<size_t>(tab.size(), 1)))
     return e->fail(SIMMR_ENOMEM, "genome table allocation failed");
   HIP_TRY(e, hipMemcpyAsync(e->d_genomes.p, tab.data(), sizeof(GenomeDev) * tab.size(),
                             hipMemcpyHostToDevice, e->stream));
@@ -315,8 +288,8 @@ int layout_genome(simmr_engine* e, GenomeHost& g, uint32_t n_contigs, const uint
   g.plane_bases = base;
   const size_t pwords = FRONT_PAD_WORDS + base / 16 + BACK_PAD_WORDS;
   const size_t mwords = FRONT_PAD_WORDS + base / 32 + BACK_PAD_WORDS;
-  if (!g.packed.ensure(pwords * 4) || !g.mask.ensure(mwords * 4) ||
-      !g.d_contigs.ensure(sizeof(ContigDev) * std::max<uint32_t>(n_contigs, 1)))
+  if (!g.packed.ensure_slack(pwords * 4) || !g.mask.ensure_slack(mwords * 4) ||
+      !g.d_contigs.ensure_slack(sizeof(ContigDev) * std::max<uint32_t>(n_contigs, 1)))
     return e->fail(SIMMR_ENOMEM, "genome allocation failed (%zu bytes)", pwords * 4 + mwords * 4);
   HIP_TRY(e, hipMemsetAsync(g.packed.p, 0, pwords * 4, e->stream));
   HIP_TRY(e, hipMemsetAsync(g.mask.p, 0, mwords * 4, e->stream));
@@ -333,7 +306,7 @@ int check_genome(simmr_engine* e, uint32_t idx) {
 
 // ---- custom (empirical) profile: parse the model, build + upload the PDF tables --------
 template <class T> int upload_vec(simmr_engine* e, DevBuf& b, const std::vector<T>& v) {
-  if (!b.ensure(std::max<size_t>(v.size(), 1) * sizeof(T))) return e->fail(SIMMR_ENOMEM, "custom table allocation failed");
+  if (!b.ensure_slack(std::max<size_t>(v.size(), 1) * sizeof(T))) return e->fail(SIMMR_ENOMEM, "custom table allocation failed");
   if (!v.empty()) HIP_TRY(e, hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, e->stream));
   return SIMMR_OK;
 }
@@ -380,7 +353,7 @@ struct PlanScope {
     e->mark_valid[e->cur_set] = true;
     plan_sets_swap(e);
     if (e->mark_valid[e->cur_set]) (void)hipStreamWaitEvent(e->plan_stream, e->ev_mark[e->cur_set], 0);
-    if (!e->d_err.p && (!e->d_err.ensure(64) || hipMemset(e->d_err.p, 0, 64) != hipSuccess)) { /* the plan's own checks report it */ }
+    if (!e->d_err.p && (!e->d_err.ensure_slack(64) || hipMemset(e->d_err.p, 0, 64) != hipSuccess)) { /* the plan's own checks report it */ }
     e->stream = e->plan_stream;
     on = true;
   }
@@ -688,8 +661,8 @@ int run_outer(simmr_engine* e, uint64_t seed, uint64_t range, uint64_t start_slo
     if (attempt > 8) return e->fail(SIMMR_ESTATE, "outer stream did not yield %llu units", (unsigned long long)n_total);
     const uint64_t n_wg = (n_blocks + 255) / 256;
     if (n_wg > 0x7fffffffULL) return e->fail(SIMMR_ERANGE, "outer stream too long for one launch");
-    if (!e->o_last_idx.ensure(n_blocks * 4) || !e->o_wg_sums.ensure(n_wg * 4) ||
-        !e->o_wg_prefix.ensure(n_wg * sizeof(OuterPrefix)) || !e->o_result.ensure(sizeof(OuterScanResult)))
+    if (!e->o_last_idx.ensure_slack(n_blocks * 4) || !e->o_wg_sums.ensure_slack(n_wg * 4) ||
+        !e->o_wg_prefix.ensure_slack(n_wg * sizeof(OuterPrefix)) || !e->o_result.ensure_slack(sizeof(OuterScanResult)))
       return e->fail(SIMMR_ENOMEM, "outer stream scratch allocation failed");
     HIP_TRY(e, hipMemsetAsync(e->o_result.p, 0, sizeof(OuterScanResult), e->stream));
     hipLaunchKernelGGL(k_outer_classify, dim3((uint32_t)n_wg), dim3(256), 0, e->stream, P, first_block,
@@ -724,7 +697,7 @@ int run_outer(simmr_engine* e, uint64_t seed, uint64_t range, uint64_t start_slo
     HIP_TRY(e, hipMemcpyAsync(&r2, e->o_result.p, sizeof r2, hipMemcpyDeviceToHost, e->stream));
     int rc = sync_check(e, "outer stream end lookup");
     if (rc) return rc;
-    if (!e->scan_tmp.ensure(64)) return e->fail(SIMMR_ENOMEM, "scratch allocation failed");
+    if (!e->scan_tmp.ensure_slack(64)) return e->fail(SIMMR_ENOMEM, "scratch allocation failed");
     hipLaunchKernelGGL(k_outer_emit, dim3(1), dim3(256), 0, e->stream, P, first_block, n_blocks, first_skip,
                        r2.wg_lo, e->o_last_idx.as<uint32_t>(), e->o_wg_prefix.as<OuterPrefix>(),
                        n_total - 1, (uint64_t)1, e->scan_tmp.as<uint32_t>(),
@@ -743,7 +716,7 @@ int sort_by_length(simmr_engine* e, uint64_t count, uint32_t shift, bool* sorted
   *sorted = false;
   if (count == 0) return SIMMR_OK;
   if (count > 0xffffffffULL) return e->fail(SIMMR_ERANGE, "more than 2^32 units in one shard");
-  if (!e->u_order.ensure(count * 4) || !e->len_hist.ensure(LBINS * 4))
+  if (!e->u_order.ensure_slack(count * 4) || !e->len_hist.ensure_slack(LBINS * 4))
     return e->fail(SIMMR_ENOMEM, "order allocation failed");
   HIP_TRY(e, hipMemsetAsync(e->len_hist.p, 0, LBINS * 4, e->stream));
   const uint32_t g1 = (uint32_t)std::min<uint64_t>(grid_for(count, 256), (uint64_t)e->n_cu * 8);
@@ -760,7 +733,7 @@ int sort_by_length(simmr_engine* e, uint64_t count, uint32_t shift, bool* sorted
 // exclusive scan of scale * in[i] (n entries of type T) -> `out` (n + 1 u64 entries); returns the total
 template <typename T>
 int scan_scaled(simmr_engine* e, DevBuf& in, uint64_t n, uint32_t scale, DevBuf& out, uint64_t* total, uint32_t round = 0) {
-  if (!out.ensure((n + 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
+  if (!out.ensure_slack((n + 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
   if (n == 0) {
     HIP_TRY(e, hipMemsetAsync(out.p, 0, 8, e->stream));
     *total = 0;
@@ -768,7 +741,7 @@ int scan_scaled(simmr_engine* e, DevBuf& in, uint64_t n, uint32_t scale, DevBuf&
   }
   const uint32_t per_wg = SCAN_THREADS * SCAN_ITEMS;
   const uint64_t n_wg = (n + per_wg - 1) / per_wg;
-  if (!e->scan_tmp.ensure((n_wg + 2) * 8)) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
+  if (!e->scan_tmp.ensure_slack((n_wg + 2) * 8)) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
   uint64_t* wg_tot = e->scan_tmp.as<uint64_t>();
   uint64_t* grand = wg_tot + n_wg;
   hipLaunchKernelGGL(k_scan_reduce<T>, dim3((uint32_t)n_wg), dim3(SCAN_THREADS), 0, e->stream,
@@ -786,13 +759,13 @@ int scan_u64(simmr_engine* e, DevBuf& in, uint64_t n, DevBuf& out, uint64_t* tot
 unsigned long long* tile_sums_begin(simmr_engine* e, uint64_t n) {
   const uint32_t per_wg = SCAN_THREADS * SCAN_ITEMS;
   const uint64_t n_wg = (std::max<uint64_t>(n, 1) + per_wg - 1) / per_wg;
-  if (!e->scan_tmp.ensure((n_wg + 2) * 8)) return nullptr;
+  if (!e->scan_tmp.ensure_slack((n_wg + 2) * 8)) return nullptr;
   if (hipMemsetAsync(e->scan_tmp.p, 0, (n_wg + 2) * 8, e->stream) != hipSuccess) return nullptr;
   return e->scan_tmp.as<unsigned long long>();
 }
 template <typename T>
 int scan_presummed(simmr_engine* e, DevBuf& in, uint64_t n, uint32_t scale, DevBuf& out, uint64_t* total, uint32_t round = 0) {
-  if (!out.ensure((n + 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
+  if (!out.ensure_slack((n + 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
   if (n == 0) {
     HIP_TRY(e, hipMemsetAsync(out.p, 0, 8, e->stream));
     *total = 0;
@@ -815,11 +788,11 @@ int scan_offsets(simmr_engine* e, uint64_t n, uint32_t reads_per_unit, uint64_t*
 
 int ensure_plan_arrays(simmr_engine* e, uint64_t n, bool need_seeds2, bool need_genome) {
   const uint64_t m = std::max<uint64_t>(n, 1);
-  bool ok = e->u_contig.ensure(m * 4) && e->u_seed.ensure(m * 8) && e->u_len.ensure(m * 4) &&
-            e->u_a.ensure(m * 8) && e->u_b.ensure(m * 8) &&
-            e->u_flags.ensure(m);
-  if (need_seeds2) ok = ok && e->u_qs2.ensure(m * 8) && e->u_ms2.ensure(m * 8);
-  if (need_genome) ok = ok && e->u_genome.ensure(m * 4);
+  bool ok = e->u_contig.ensure_slack(m * 4) && e->u_seed.ensure_slack(m * 8) && e->u_len.ensure_slack(m * 4) &&
+            e->u_a.ensure_slack(m * 8) && e->u_b.ensure_slack(m * 8) &&
+            e->u_flags.ensure_slack(m);
+  if (need_seeds2) ok = ok && e->u_qs2.ensure_slack(m * 8) && e->u_ms2.ensure_slack(m * 8);
+  if (need_genome) ok = ok && e->u_genome.ensure_slack(m * 4);
   if (!ok) return e->fail(SIMMR_ENOMEM, "plan allocation failed for %llu units", (unsigned long long)n);
   return SIMMR_OK;
 }
@@ -876,15 +849,12 @@ bool plan_is_coarse(simmr_engine* e, const ProfileDev& prof) {
 hipError_t next_emit_events(simmr_engine* e) {
   const int i = (int)(e->n_emits % simmr_engine::EMIT_RING);
   if (!e->ring_c[i]) {
-    if (e->n_emits == 0) { e->ring_c[0] = e->ev_c; e->ring_d[0] = e->ev_d; }
-    else {
-      // both events exist before either is published: a slot never holds a start event without its end event
-      hipEvent_t c = nullptr, d = nullptr;
-      hipError_t s = hipEventCreate(&c);
-      if (s != hipSuccess) return s;
-      if ((s = hipEventCreate(&d)) != hipSuccess) { (void)hipEventDestroy(c); return s; }
-      e->ring_c[i] = c; e->ring_d[i] = d;
-    }
+    // both events exist before either is published: a slot never holds a start event without its end event
+    hipEvent_t c = nullptr, d = nullptr;
+    hipError_t s = hipEventCreate(&c);
+    if (s != hipSuccess) return s;
+    if ((s = hipEventCreate(&d)) != hipSuccess) { (void)hipEventDestroy(c); return s; }
+    e->ring_c[i] = c; e->ring_d[i] = d;
   }
   e->ev_c = e->ring_c[i]; e->ev_d = e->ring_d[i];
   e->n_emits++;
@@ -1139,10 +1109,12 @@ int simmr_engine_create(int device_ordinal, simmr_engine** out) {
   if (const char* v = getenv("SIMMR_TEXT_FORM")) e->text_form = atoi(v);
   if (const char* v = getenv("SIMMR_FAULT_INJECT")) e->inject_null_ctr_tables = strcmp(v, "null_ctr_tables") == 0;
   if (const char* v = getenv("SIMMR_SPLICE_VARIANT")) e->splice_variant = atoi(v);
-  bool ok = e->d_tables.ensure(sizeof(Tables)) && e->d_counters.ensure(8 * SIMMR_N_COUNTERS * (1 + SIMMR_CNT_SHARDS)) &&
-            e->d_err.ensure(64) && e->d_scalars.ensure(256);
+  bool ok = e->d_tables.ensure_slack(sizeof(Tables)) && e->d_counters.ensure_slack(8 * SIMMR_N_COUNTERS * (1 + SIMMR_CNT_SHARDS)) &&
+            e->d_err.ensure_slack(64) && e->d_scalars.ensure_slack(256);
   ok = ok && hipEventCreate(&e->ev_a) == hipSuccess && hipEventCreate(&e->ev_b) == hipSuccess &&
-       hipEventCreate(&e->ev_c) == hipSuccess && hipEventCreate(&e->ev_d) == hipSuccess;
+       hipEventCreate(&e->ring_c[0]) == hipSuccess && hipEventCreate(&e->ring_d[0]) == hipSuccess;
+  e->ev_c = e->ring_c[0];
+  e->ev_d = e->ring_d[0];
   if (ok) {
     Tables* T = new Tables();
     build_tables(T);
@@ -1264,32 +1236,7 @@ void simmr_engine_destroy(simmr_engine* e) {
   for (int i = 0; i < ENG_EXT_COUNT; i++)
     if (e->ext_slot[i] && e->ext_destroy[i]) e->ext_destroy[i](e->ext_slot[i]);
   if (e->plan_stream) (void)hipStreamDestroy(e->plan_stream);
-  if (e->ev_plan_done) (void)hipEventDestroy(e->ev_plan_done);
-  for (int i = 0; i < 2; i++) if (e->ev_mark[i]) (void)hipEventDestroy(e->ev_mark[i]);
-  for (DevBuf* b : {&e->s_w_bytes, &e->s_u_off64, &e->s_m_genomes, &e->s_u_contig, &e->s_u_genome, &e->s_u_seed, &e->s_u_len, &e->s_u_a,
-                    &e->s_u_b, &e->s_u_qs2, &e->s_u_ms2, &e->s_u_flags, &e->s_u_off, &e->s_u_order, &e->s_d_err, &e->s_d_runs,
-                    &e->s_d_usable, &e->s_ph_table})
-    b->release();
-  for (auto& g : e->genomes) { g.packed.release(); g.mask.release(); g.d_contigs.release(); }
-  DevBuf* bufs[] = {&e->d_genomes, &e->d_tables, &e->d_counters, &e->d_err, &e->d_scalars, &e->u_contig,
-                    &e->u_genome, &e->u_seed, &e->u_len, &e->u_a, &e->u_b, &e->u_qs2,
-                    &e->u_ms2, &e->u_flags, &e->u_off, &e->scan_tmp, &e->o_last_idx, &e->o_wg_sums,
-                    &e->o_wg_prefix, &e->o_result, &e->d_runs, &e->d_usable, &e->u_order, &e->len_hist, &e->c_pdfs, &e->c_odds, &e->c_alias, &e->c_low, &e->c_range, &e->c_zone, &e->c_colrec, &e->c_binrec, &e->c_kslots, &e->c_krecs, &e->c_kdirect, &e->c_kcnt8, &e->c_kcols, &e->c_krecs_ctr, &e->c_kcols_ctr, &e->c_ktab32, &e->ph_table,
-                    &e->fq_blob, &e->fq_gid_off, &e->fq_gid_len, &e->fq_cbase, &e->fq_ncontig, &e->fq_coff, &e->fq_clen,
-                    &e->fq_len, &e->fq_off, &e->m_genomes, &e->m_contig, &e->m_seed, &e->w_bytes, &e->u_off64, &e->fq_off64};
-  for (DevBuf* b : bufs) b->release();
-  for (DevBuf* b : {&e->tr_nm, &e->tr_off, &e->tr_err}) b->release();
-  for (hipEvent_t ev : e->tr_ev) if (ev) (void)hipEventDestroy(ev);
-  e->st_tab.release();
-  for (hipEvent_t ev : e->st_ev) if (ev) (void)hipEventDestroy(ev);
-  if (e->ev_a) (void)hipEventDestroy(e->ev_a);
-  if (e->ev_b) (void)hipEventDestroy(e->ev_b);
-  if (e->n_emits == 0) { e->ring_c[0] = e->ev_c; e->ring_d[0] = e->ev_d; }
-  for (int i = 0; i < simmr_engine::EMIT_RING; i++) {
-    if (e->ring_c[i]) (void)hipEventDestroy(e->ring_c[i]);
-    if (e->ring_d[i]) (void)hipEventDestroy(e->ring_d[i]);
-  }
-  delete e;
+  delete e;  // (the buffers and the events go with their members, the staged genomes' with theirs)
 }
 
 int simmr_engine_set_read_slots(simmr_engine* e, uint32_t slot_bytes) {
@@ -1337,7 +1284,7 @@ int simmr_stage_genome(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
   DevBuf stage;
   uint64_t maxlen = 0;
   for (uint32_t c = 0; c < n_contigs; c++) maxlen = std::max(maxlen, contig_len[c]);
-  if (!stage.ensure(std::min(maxlen, CHUNK) + 64)) return e->fail(SIMMR_ENOMEM, "staging buffer allocation failed");
+  if (!stage.ensure_slack(std::min(maxlen, CHUNK) + 64)) return e->fail(SIMMR_ENOMEM, "staging buffer allocation failed");
   HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
   uint32_t* d_any = e->d_err.as<uint32_t>() + 1;
   for (uint32_t c = 0; c < n_contigs; c++) {
@@ -1349,7 +1296,7 @@ int simmr_stage_genome(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
                          g.packed.as<uint32_t>() + FRONT_PAD_WORDS, g.mask.as<uint32_t>() + FRONT_PAD_WORDS,
                          d_any);
       rc = sync_check(e, "k_pack_ascii");  // the staging buffer is reused
-      if (rc) { stage.release(); return rc; }
+      if (rc) return rc;
     }
   }
   stage.release();
@@ -1378,30 +1325,26 @@ int simmr_stage_fasta(simmr_engine* e, uint32_t genome_idx, uint32_t n_records, 
   std::vector<uint64_t> tile0(n_records + 1, 0);
   for (uint32_t c = 0; c < n_records; c++) tile0[c + 1] = tile0[c] + (body_len[c] + FASTA_TILE - 1) / FASTA_TILE;
   const uint64_t n_tiles = tile0[n_records];
-  DevBuf raw, kept, prefix, d_tile0, d_gather, d_recs, d_sep;
-  auto release = [&]() { raw.release(); kept.release(); prefix.release(); d_tile0.release(); d_gather.release(); d_recs.release(); d_sep.release(); };
+  DevBuf raw, kept, prefix, d_tile0, d_gather, d_recs, d_sep;  // (of this call: a return frees them)
   int rc = SIMMR_OK;
-  if (!raw.ensure(std::max<uint64_t>(n_tiles, 1) * FASTA_TILE) || !kept.ensure(std::max<uint64_t>(n_tiles, 1) * 8) ||
-      !d_tile0.ensure((n_records + 1) * 8) || !d_gather.ensure((n_records + 1) * 8) ||
-      !d_recs.ensure(n_records * sizeof(FastaRecord)) || !d_sep.ensure(n_records * 8)) {
-    release();
+  if (!raw.ensure_slack(std::max<uint64_t>(n_tiles, 1) * FASTA_TILE) || !kept.ensure_slack(std::max<uint64_t>(n_tiles, 1) * 8) ||
+      !d_tile0.ensure_slack((n_records + 1) * 8) || !d_gather.ensure_slack((n_records + 1) * 8) ||
+      !d_recs.ensure_slack(n_records * sizeof(FastaRecord)) || !d_sep.ensure_slack(n_records * 8))
     return e->fail(SIMMR_ENOMEM, "FASTA staging allocation failed (%llu bytes)", (unsigned long long)(n_tiles * FASTA_TILE));
-  }
-#define FASTA_TRY(call) do { hipError_t _s = (call); if (_s != hipSuccess) { release(); return e->fail(SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); } } while (0)
-  FASTA_TRY(hipMemsetAsync(raw.p, '\n', std::max<uint64_t>(n_tiles, 1) * FASTA_TILE, e->stream));
+  HIP_TRY(e, hipMemsetAsync(raw.p, '\n', std::max<uint64_t>(n_tiles, 1) * FASTA_TILE, e->stream));
   for (uint32_t c = 0; c < n_records; c++)
     if (body_len[c])
-      FASTA_TRY(hipMemcpyAsync(raw.as<uint8_t>() + tile0[c] * FASTA_TILE, body[c], body_len[c], hipMemcpyHostToDevice, e->stream));
-  FASTA_TRY(hipMemcpyAsync(d_tile0.p, tile0.data(), (n_records + 1) * 8, hipMemcpyHostToDevice, e->stream));
+      HIP_TRY(e, hipMemcpyAsync(raw.as<uint8_t>() + tile0[c] * FASTA_TILE, body[c], body_len[c], hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(d_tile0.p, tile0.data(), (n_records + 1) * 8, hipMemcpyHostToDevice, e->stream));
   const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_tiles, 1), (uint64_t)e->n_cu * 16);
   if (n_tiles) hipLaunchKernelGGL(k_fasta_count, dim3(grid), dim3(256), 0, e->stream, raw.as<uint8_t>(), n_tiles, kept.as<uint64_t>());
   uint64_t total = 0;
-  if ((rc = scan_u64(e, kept, n_tiles, prefix, &total))) { release(); return rc; }  // prefix has n_tiles + 1 entries
+  if ((rc = scan_u64(e, kept, n_tiles, prefix, &total))) return rc;  // prefix has n_tiles + 1 entries
   std::vector<uint64_t> pre(n_records + 1, 0);
   hipLaunchKernelGGL(k_fasta_gather, dim3(grid_for(n_records + 1, 256)), dim3(256), 0, e->stream, prefix.as<uint64_t>(),
                      d_tile0.as<uint64_t>(), n_records + 1, d_gather.as<uint64_t>());
-  FASTA_TRY(hipMemcpyAsync(pre.data(), d_gather.p, (n_records + 1) * 8, hipMemcpyDeviceToHost, e->stream));
-  if ((rc = sync_check(e, "FASTA base counts"))) { release(); return rc; }
+  HIP_TRY(e, hipMemcpyAsync(pre.data(), d_gather.p, (n_records + 1) * 8, hipMemcpyDeviceToHost, e->stream));
+  if ((rc = sync_check(e, "FASTA base counts"))) return rc;
   for (uint32_t c = 0; c < n_records; c++) base_count[c] = pre[c + 1] - pre[c];
   // layout: the staged sequences and where every record's bases go
   std::vector<FastaRecord> recs(n_records);
@@ -1415,29 +1358,28 @@ int simmr_stage_fasta(simmr_engine* e, uint32_t genome_idx, uint32_t n_records, 
     for (uint32_t c = 0; c < n_records; c++)
       if (base_count[c] > min_size) { lens.push_back(base_count[c]); sizes.push_back(base_count[c]); }
   }
-  if (lens.empty()) { release(); return SIMMR_OK; }
-  if ((rc = layout_genome(e, g, (uint32_t)lens.size(), lens.data(), sizes.data()))) { release(); return rc; }
+  if (lens.empty()) return SIMMR_OK;
+  if ((rc = layout_genome(e, g, (uint32_t)lens.size(), lens.data(), sizes.data()))) return rc;
   if (!contiguous) {
     uint32_t k = 0;
     for (uint32_t c = 0; c < n_records; c++) recs[c] = FastaRecord{tile0[c], base_count[c] > min_size ? g.contigs[k++].base : ~0ull};
   }
-  FASTA_TRY(hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
+  HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
   uint32_t* d_any = e->d_err.as<uint32_t>() + 1;
-  FASTA_TRY(hipMemcpyAsync(d_recs.p, recs.data(), n_records * sizeof(FastaRecord), hipMemcpyHostToDevice, e->stream));
+  HIP_TRY(e, hipMemcpyAsync(d_recs.p, recs.data(), n_records * sizeof(FastaRecord), hipMemcpyHostToDevice, e->stream));
   if (n_tiles)
     hipLaunchKernelGGL(k_fasta_pack, dim3(grid), dim3(256), 0, e->stream, raw.as<uint8_t>(), n_tiles, prefix.as<uint64_t>(),
                        d_recs.as<FastaRecord>(), n_records, g.packed.as<uint32_t>() + FRONT_PAD_WORDS,
                        g.mask.as<uint32_t>() + FRONT_PAD_WORDS, d_any);
   if (!seps.empty()) {
-    FASTA_TRY(hipMemcpyAsync(d_sep.p, seps.data(), seps.size() * 8, hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(e, hipMemcpyAsync(d_sep.p, seps.data(), seps.size() * 8, hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(k_fasta_separators, dim3(grid_for(seps.size(), 256)), dim3(256), 0, e->stream, d_sep.as<uint64_t>(),
                        (uint32_t)seps.size(), g.mask.as<uint32_t>() + FRONT_PAD_WORDS, d_any);
   }
   uint32_t any = 0;
-  FASTA_TRY(hipMemcpyAsync(&any, d_any, 4, hipMemcpyDeviceToHost, e->stream));
-#undef FASTA_TRY
+  HIP_TRY(e, hipMemcpyAsync(&any, d_any, 4, hipMemcpyDeviceToHost, e->stream));
   rc = sync_check(e, "FASTA staging");  // the host vectors and the raw copy may go now
-  release();
+  for (DevBuf* b : {&raw, &kept, &prefix, &d_tile0, &d_gather, &d_recs, &d_sep}) b->release();  // (before the genome table is made anew)
   if (rc) return rc;
   g.has_exc = any != 0;
   g.staged = true;
@@ -1479,14 +1421,13 @@ int simmr_unstage_contig(simmr_engine* e, uint32_t genome_idx, uint32_t contig, 
     return e->fail(SIMMR_ERANGE, "unstage range outside the contig");
   if (count == 0) return SIMMR_OK;
   DevBuf tmp;
-  if (!tmp.ensure(count)) return e->fail(SIMMR_ENOMEM, "unstage buffer allocation failed");
+  if (!tmp.ensure_slack(count)) return e->fail(SIMMR_ENOMEM, "unstage buffer allocation failed");
   hipLaunchKernelGGL(k_unpack, dim3(grid_for(count, 256)), dim3(256), 0, e->stream,
                      g.packed.as<uint32_t>() + FRONT_PAD_WORDS,
                      g.has_exc ? g.mask.as<uint32_t>() + FRONT_PAD_WORDS : (const uint32_t*)nullptr,
                      g.contigs[contig].base + first, count, tmp.as<uint8_t>());
   hipError_t s = hipMemcpyAsync(dst_host, tmp.p, count, hipMemcpyDeviceToHost, e->stream);
   rc = (s == hipSuccess) ? sync_check(e, "k_unpack") : e->fail(SIMMR_ENODEV, "unstage copy: %s", hipGetErrorString(s));
-  tmp.release();
   return rc;
 }
 
@@ -1516,8 +1457,8 @@ int simmr_outer_summarize(simmr_engine* e, uint32_t genome_idx, uint64_t seed, u
   P.zone = (P.range << __builtin_clzll(P.range)) - 1;
   const uint64_t n_blocks = slot_count >> 3, n_wg = (n_blocks + 255) / 256;
   if (n_wg > 0x7fffffffULL) return e->fail(SIMMR_ERANGE, "slot range too long for one launch");
-  if (!e->o_last_idx.ensure(n_blocks * 4) || !e->o_wg_sums.ensure(n_wg * 4) ||
-      !e->o_wg_prefix.ensure(n_wg * sizeof(OuterPrefix)) || !e->o_result.ensure(sizeof(OuterScanResult)))
+  if (!e->o_last_idx.ensure_slack(n_blocks * 4) || !e->o_wg_sums.ensure_slack(n_wg * 4) ||
+      !e->o_wg_prefix.ensure_slack(n_wg * sizeof(OuterPrefix)) || !e->o_result.ensure_slack(sizeof(OuterScanResult)))
     return e->fail(SIMMR_ENOMEM, "outer stream scratch allocation failed");
   HIP_TRY(e, hipMemsetAsync(e->o_result.p, 0, sizeof(OuterScanResult), e->stream));
   hipLaunchKernelGGL(k_outer_classify, dim3((uint32_t)n_wg), dim3(256), 0, e->stream, P, slot_first >> 3, n_blocks, 0u,
@@ -1595,7 +1536,7 @@ static int plan_pe_pairs(simmr_engine* e, PlanState* p, uint32_t slot_round, uin
                 !(prof.kind == SIMMR_K_MINIMAL_SHORT && prof.rng_mode == SIMMR_RNG_REFERENCE);
     unsigned long long* tiles = presummed ? tile_sums_begin(e, count) : nullptr;
     if (presummed && !tiles) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
-    if (coarse && !e->w_bytes.ensure(((count + 63) / 64) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
+    if (coarse && !e->w_bytes.ensure_slack(((count + 63) / 64) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
     if ((rc = launch_plan_pe(e, prof, genome, count, u_genome, pw, tiles, slot_round,
                              coarse ? e->w_bytes.as<unsigned long long>() : (unsigned long long*)nullptr, oc)))
       return rc;
@@ -1736,7 +1677,7 @@ int simmr_pe_plan_multi(simmr_engine* e, uint32_t n_genomes, const uint32_t* gen
   for (Cls& c : classes) { c.off = list_total; list_total += c.need; }
   for (uint32_t g = 0; g < n_genomes; g++) mg[g].cls_off = classes.empty() ? 0 : classes[mg[g].pad].off;
   if ((rc = ensure_plan_arrays(e, count, prof.kind != SIMMR_K_PERFECT_SHORT, true))) return rc;
-  if (!e->m_contig.ensure(std::max<uint64_t>(list_total, 1) * 4) || !e->m_seed.ensure(std::max<uint64_t>(list_total, 1) * 8))
+  if (!e->m_contig.ensure_slack(std::max<uint64_t>(list_total, 1) * 4) || !e->m_seed.ensure_slack(std::max<uint64_t>(list_total, 1) * 8))
     return e->fail(SIMMR_ENOMEM, "outer list allocation failed");
   if ((rc = upload_vec(e, e->m_genomes, mg))) return rc;
   HIP_TRY(e, hipEventRecord(e->ev_a, e->stream));
@@ -1990,7 +1931,7 @@ int simmr_long_plan(simmr_engine* e, uint32_t n_genomes, const uint32_t* genome_
                        "genome %u has no sequence longer than the read length %u (the reference loops forever, simulate.rs:370)",
                        runs[r].genome, L0);
     }
-    if (!e->d_usable.ensure(std::max<size_t>(usable.size(), 1) * 4)) return e->fail(SIMMR_ENOMEM, "usable table allocation failed");
+    if (!e->d_usable.ensure_slack(std::max<size_t>(usable.size(), 1) * 4)) return e->fail(SIMMR_ENOMEM, "usable table allocation failed");
     HIP_TRY(e, hipMemcpyAsync(e->d_usable.p, usable.data(), usable.size() * 4, hipMemcpyHostToDevice, e->stream));
     for (size_t r = 0; r < runs.size(); r++) runs[r].usable = e->d_usable.as<uint32_t>() + uoff[r];
     // ONE StdRng across all genomes (simulate.rs:348): walk it segment by
@@ -2016,7 +1957,7 @@ int simmr_long_plan(simmr_engine* e, uint32_t n_genomes, const uint32_t* genome_
     }
     end_slot = slot;
   }
-  if (!e->d_runs.ensure(std::max<size_t>(runs.size(), 1) * sizeof(LongGenomeRun))) return e->fail(SIMMR_ENOMEM, "run table allocation failed");
+  if (!e->d_runs.ensure_slack(std::max<size_t>(runs.size(), 1) * sizeof(LongGenomeRun))) return e->fail(SIMMR_ENOMEM, "run table allocation failed");
   HIP_TRY(e, hipMemcpyAsync(e->d_runs.p, runs.data(), runs.size() * sizeof(LongGenomeRun), hipMemcpyHostToDevice, e->stream));
   if (count > 0) {
     if (!per_read) {
@@ -2163,7 +2104,7 @@ static int fq_prepare(simmr_engine* e, const char* header_format, const simmr_fa
       (rc = upload_vec(e, e->fq_ncontig, ncontig)) || (rc = upload_vec(e, e->fq_coff, coff)) ||
       (rc = upload_vec(e, e->fq_clen, clen)))
     return rc;
-  if (!e->fq_tpl_dev.ensure(sizeof(FqTemplate))) return e->fail(SIMMR_ENOMEM, "template allocation failed");
+  if (!e->fq_tpl_dev.ensure_slack(sizeof(FqTemplate))) return e->fail(SIMMR_ENOMEM, "template allocation failed");
   HIP_TRY(e, hipMemcpyAsync(e->fq_tpl_dev.p, &f->tpl, sizeof(FqTemplate), hipMemcpyHostToDevice, e->stream));
   if ((rc = sync_check(e, "fastq table upload"))) return rc;  // the host vectors go out of scope
   f->lit_bytes = lit_bytes;
@@ -2239,7 +2180,7 @@ int simmr_fastq_plan(simmr_engine* e, const char* header_format, const simmr_fas
   f.paired = paired != 0;
   int rc;
   if ((rc = fq_prepare(e, header_format, names, &f))) return rc;
-  if (!e->fq_len.ensure(std::max<uint64_t>(n_reads, 1) * 8)) return e->fail(SIMMR_ENOMEM, "record length allocation failed");
+  if (!e->fq_len.ensure_slack(std::max<uint64_t>(n_reads, 1) * 8)) return e->fail(SIMMR_ENOMEM, "record length allocation failed");
   HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
   if (n_reads > 0)
     hipLaunchKernelGGL(k_fastq_size, dim3(grid_for(n_reads, 256)), dim3(256), 0, e->stream, fq_len_coef(f.tpl), fq_tables(e, f.slots),
@@ -2307,7 +2248,7 @@ int simmr_fastq_plan_direct(simmr_engine* e, const char* header_format, const si
   int rc;
   if ((rc = fq_prepare(e, header_format, names, &f))) return rc;
   const uint64_t n_reads = c.n_reads;
-  if (!e->fq_len.ensure(std::max<uint64_t>(n_reads, 1) * 8) || !e->fq_hlen.ensure(std::max<uint64_t>(n_reads, 1)))
+  if (!e->fq_len.ensure_slack(std::max<uint64_t>(n_reads, 1) * 8) || !e->fq_hlen.ensure_slack(std::max<uint64_t>(n_reads, 1)))
     return e->fail(SIMMR_ENOMEM, "record length allocation failed");
   HIP_TRY(e, hipEventRecord(e->ev_a, e->stream));
   HIP_TRY(e, hipMemsetAsync(e->d_err.p, 0, 64, e->stream));
@@ -2317,7 +2258,7 @@ int simmr_fastq_plan_direct(simmr_engine* e, const char* header_format, const si
   const uint64_t n_w = (n_reads + 63) / 64;
   unsigned long long* tiles = coarse ? nullptr : tile_sums_begin(e, n_reads);
   if (!coarse && !tiles) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
-  if (coarse && !e->w_bytes.ensure(std::max<uint64_t>(n_w, 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
+  if (coarse && !e->w_bytes.ensure_slack(std::max<uint64_t>(n_w, 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
   if (n_reads > 0)
     hipLaunchKernelGGL(k_fastq_size_plan, dim3(grid_for(n_reads, 256)), dim3(256), 0, e->stream, fq_len_coef(f.tpl), fq_tables(e, f.slots),
                        fq_plan_view(e, c, read_id_base), n_reads, coarse ? (uint64_t*)nullptr : e->fq_len.as<uint64_t>(), e->fq_hlen.as<uint8_t>(),
@@ -2346,9 +2287,9 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
     // in buffers of the engine and framed from there (the same kernels as simmr_*_emit + simmr_fastq_emit; qualities
     // with the FASTQ offset, util.rs:46-57).
     const uint64_t tb_bytes = std::max<uint64_t>(e->plan.total_bases, 1), nr = std::max<uint64_t>(f.reads, 1);
-    if (!e->fd_seq.ensure(tb_bytes) || !e->fd_qual.ensure(tb_bytes) || !e->fd_seq_off.ensure((nr + 1) * 8) || !e->fd_start.ensure(nr * 8) ||
-        !e->fd_end.ensure(nr * 8) || !e->fd_contig.ensure(nr * 4) || !e->fd_genome.ensure(nr * 4) || !e->fd_read_id.ensure(nr * 4) ||
-        !e->fd_flags.ensure(nr))
+    if (!e->fd_seq.ensure_slack(tb_bytes) || !e->fd_qual.ensure_slack(tb_bytes) || !e->fd_seq_off.ensure_slack((nr + 1) * 8) || !e->fd_start.ensure_slack(nr * 8) ||
+        !e->fd_end.ensure_slack(nr * 8) || !e->fd_contig.ensure_slack(nr * 4) || !e->fd_genome.ensure_slack(nr * 4) || !e->fd_read_id.ensure_slack(nr * 4) ||
+        !e->fd_flags.ensure_slack(nr))
       return e->fail(SIMMR_ENOMEM, "column allocation failed (%llu bases, %llu reads)", (unsigned long long)tb_bytes, (unsigned long long)nr);
     simmr_reads_out cols{};
     cols.seq = e->fd_seq.as<uint8_t>(); cols.qual = e->fd_qual.as<uint8_t>(); cols.seq_off = e->fd_seq_off.as<uint64_t>();
@@ -2420,9 +2361,8 @@ int simmr_truth_plan(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
   int rc;
   if ((rc = check_read_columns(e, reads, n_reads, "simmr_truth_plan"))) return rc;
   HIP_TRY(e, hipSetDevice(e->device));
-  for (hipEvent_t& ev : e->tr_ev)
-    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
-  if (!e->tr_nm.ensure(std::max<uint64_t>(n_reads, 1) * 4) || !e->tr_err.ensure(64))
+  if (int rc = e->tr_ev.create_missing(e)) return rc;
+  if (!e->tr_nm.ensure_slack(std::max<uint64_t>(n_reads, 1) * 4) || !e->tr_err.ensure_slack(64))
     return e->fail(SIMMR_ENOMEM, "truth count allocation failed");
   HIP_TRY(e, hipMemsetAsync(e->tr_err.p, 0, 64, e->stream));
   HIP_TRY(e, hipEventRecord(e->tr_ev[0], e->stream));
@@ -2501,9 +2441,8 @@ static const size_t STATS_BYTES = sizeof(simmr_run_stats) + 8;  // the tables an
 int simmr_stats_reset(simmr_engine* e) {
   if (!e) return SIMMR_EINVAL;
   HIP_TRY(e, hipSetDevice(e->device));
-  for (hipEvent_t& ev : e->st_ev)
-    if (!ev) HIP_TRY(e, hipEventCreate(&ev));
-  if (!e->st_tab.ensure(STATS_BYTES)) return e->fail(SIMMR_ENOMEM, "statistics allocation failed");
+  if (int rc = e->st_ev.create_missing(e)) return rc;
+  if (!e->st_tab.ensure_slack(STATS_BYTES)) return e->fail(SIMMR_ENOMEM, "statistics allocation failed");
   HIP_TRY(e, hipMemsetAsync(e->st_tab.p, 0, STATS_BYTES, e->stream));
   e->st_ready = true;
   e->st_timed = false;

@@ -1,5 +1,7 @@
 // engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip, fit_sam.hip, bam.hip, bam_index.hip, mapeval.hip) may ask of an engine.  simmr_engine is
 // defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the C ABI.
+// The host plumbing over these accessors that every unit uses, engine.hip too (the owning DevBuf and Events, HIP_TRY, sync_check,
+// unit_state, staged_rows), is host_support.hpp, which includes this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -41,7 +43,8 @@ constexpr uint64_t SAMSORT_PAIRS_TILE = 2048, SAMSORT_PAIRS_DIGITS = 256;
 SIMMR_HIDDEN int samsort_sort_pairs(hipStream_t st, uint64_t* const key[2], uint32_t* const idx[2], uint32_t* hist, uint32_t* digit_total,
                                     uint64_t n, uint32_t key_bits);
 // One opaque slot per engine and translation unit for that unit's state; simmr_engine_destroy calls `destroy` on a non-null
-// slot (on the engine's device, after the device has been synchronised).
+// slot (on the engine's device, after the device has been synchronised).  Units reach their slot through unit_state of
+// host_support.hpp, whose hook deletes the state.
 enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_OVERLAP = 6, ENG_EXT_FIT = 7, ENG_EXT_FIT_SAM = 8, ENG_EXT_BAM = 9, ENG_EXT_COUNT = 10 };
 SIMMR_HIDDEN void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*));
 // The layout of depth[] that the last simmr_depth_reset recorded (defined in depth.hip): tracked contig k is entries

@@ -1,6 +1,6 @@
 // fit.hip — fitting a simmrd-format error model from the reads of a run (include/simmr_hip.h: simmr_fit_*): the entry
 // points over fit_kernels.hip.  A translation unit of its own; it sees an engine through engine_internal.hpp only and keeps
-// its state in the engine's opaque slot (freed by simmr_engine_destroy through the hook given there).
+// its state in the engine's opaque slot (host_support.hpp: unit_state; simmr_engine_destroy deletes it, and its members free what they own).
 //
 // reset: the tables (dense identity counts, the pair table, the three histograms) zeroed on the stream.
 // add:   k_fit_add, enqueue-only.
@@ -19,25 +19,11 @@
 
 #include "fit_kernels.hip"
 #include "fit_host.hpp"
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 using namespace simmr;
 
 namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;  // bytes
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    cap = bytes;
-    return true;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
 
 struct FitState {
   uint32_t k = 0, max_alt = 0;
@@ -51,7 +37,7 @@ struct FitState {
   DevBuf tables, out_key, out_cnt, pts, qdens, ldens, idens;
   // the finish: sort buffers, the per-reference tables (start | n_alt | total | first | sizes[2]), the model's pair columns
   DevBuf skey[2], sidx[2], perm[2], hist, digit_total, refs, kmer_ref, kmer_first, pair_alt, pair_count, pair_prob;
-  hipEvent_t ev[2] = {};
+  Events<2> ev;
   // the planned model (host side)
   simmr_fit_info info{};
   FitBins len, ins;
@@ -71,48 +57,21 @@ struct FitState {
   FitTables dev() const { return FitTables{dense(), hkey(), hcnt(), qhist(), lhist(), ihist(), err(), (uint32_t)(n_slots - 1), k}; }
 };
 
-void fit_destroy(void* q) {
-  FitState* s = (FitState*)q;
-  for (DevBuf* b : {&s->tables, &s->out_key, &s->out_cnt, &s->pts, &s->qdens, &s->ldens, &s->idens, &s->skey[0], &s->skey[1], &s->sidx[0], &s->sidx[1],
-                    &s->perm[0], &s->perm[1], &s->hist, &s->digit_total, &s->refs, &s->kmer_ref, &s->kmer_first, &s->pair_alt, &s->pair_count, &s->pair_prob})
-    if (b->p) (void)hipFree(b->p);
-  for (hipEvent_t ev : s->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete s;
-}
-
-FitState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_FIT, fit_destroy);
-  if (!*slot && create) *slot = new FitState();
-  return (FitState*)*slot;
-}
-
-#define FIT_TRY(e, call)                                                                    \
-  do {                                                                                      \
-    hipError_t _s = (call);                                                                 \
-    if (_s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); \
-  } while (0)
-
-int sync_check(simmr_engine* e, const char* what) {
-  hipError_t s = hipStreamSynchronize(eng_stream(e));
-  if (s == hipSuccess) s = hipGetLastError();
-  if (s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  return SIMMR_OK;
-}
+constexpr auto fit_state = unit_state<FitState, ENG_EXT_FIT>;
 
 }  // namespace
 
 namespace simmr {
 
 bool fit_share(simmr_engine* e, FitShare* out) {
-  FitState* s = state_of(e, false);
+  FitState* s = fit_state(e, false);
   if (!s || !s->ready) return false;
   *out = FitShare{s->dev(), s->sam_counts(), {s->ev[0], s->ev[1]}};
   return true;
 }
 
 void fit_share_added(simmr_engine* e) {
-  FitState* s = state_of(e, false);
+  FitState* s = fit_state(e, false);
   if (!s) return;
   s->planned = false;
   s->unplanned_add = true;
@@ -128,11 +87,10 @@ int simmr_fit_reset(simmr_engine* e, uint32_t k, uint32_t max_alt_kmers, uint64_
   if (k < 3u || k > 10u) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_reset: k is 3 .. 10");
   if (max_alt_kmers == 0u) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_reset: max_alt_kmers is at least 1");
   if (pair_capacity == 0 || pair_capacity > (1ull << 26)) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_reset: pair_capacity is 1 .. 2^26");
-  FIT_TRY(e, hipSetDevice(eng_device(e)));
-  FitState* s = state_of(e, true);
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  FitState* s = fit_state(e, true);
   s->ready = s->planned = s->timed = false;
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) FIT_TRY(e, hipEventCreate(&ev));
+  if (int rc = s->ev.create_missing(e)) return rc;
   s->k = k;
   s->max_alt = max_alt_kmers;
   s->n_dense = 1ull << (2u * k);
@@ -146,16 +104,16 @@ int simmr_fit_reset(simmr_engine* e, uint32_t k, uint32_t max_alt_kmers, uint64_
   // an add no plan has looked at), otherwise up to the longest read the plans since have seen
   const bool whole = s->tables.cap != cap_before || s->clean_dense != s->n_dense || s->clean_slots != s->n_slots || s->unplanned_add;
   if (whole) {
-    FIT_TRY(e, hipMemsetAsync(s->tables.p, 0, s->words() * 8, st));
+    HIP_TRY(e, hipMemsetAsync(s->tables.p, 0, s->words() * 8, st));
   } else {
-    FIT_TRY(e, hipMemsetAsync(s->tables.p, 0, (s->n_dense + 2 * s->n_slots + s->dirty_pos * SIMMR_FIT_QUALS) * 8, st));
-    FIT_TRY(e, hipMemsetAsync(s->lhist(), 0, (FitState::L_WORDS + FitState::I_WORDS + 2 + FIT_SAM_COUNTS) * 8, st));
+    HIP_TRY(e, hipMemsetAsync(s->tables.p, 0, (s->n_dense + 2 * s->n_slots + s->dirty_pos * SIMMR_FIT_QUALS) * 8, st));
+    HIP_TRY(e, hipMemsetAsync(s->lhist(), 0, (FitState::L_WORDS + FitState::I_WORDS + 2 + FIT_SAM_COUNTS) * 8, st));
   }
   s->dirty_pos = 0;
   s->unplanned_add = false;
   s->clean_dense = s->n_dense;
   s->clean_slots = s->n_slots;
-  FIT_TRY(e, hipMemsetAsync(s->hkey(), 0xff, s->n_slots * 8, st));
+  HIP_TRY(e, hipMemsetAsync(s->hkey(), 0xff, s->n_slots * 8, st));
   s->ready = true;
   return SIMMR_OK;
 }
@@ -167,11 +125,11 @@ int simmr_fit_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_read
   if (n_sets == 2u && (n_reads & 1u)) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_add: a paired shard has an even number of reads");
   if (!reads->seq || !reads->qual || !reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags)
     return eng_fail(e, SIMMR_EINVAL, "simmr_fit_add needs seq, qual, seq_off, start, end, contig, genome and flags");
-  FitState* s = state_of(e, false);
+  FitState* s = fit_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_fit_add called before simmr_fit_reset");
-  FIT_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  FIT_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, hipEventRecord(s->ev[0], st));
   if (n_reads > 0) {
     // persistent: one workgroup per CU (the LDS image takes most of a CU's 160 KB), each looping over its share of the batches
     const uint64_t batches = (n_reads + FIT_WG_READS - 1) / FIT_WG_READS;
@@ -182,7 +140,7 @@ int simmr_fit_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_read
                         reads->flags, reads->seq_capacity, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
     hipLaunchKernelGGL(k_fit_add, dim3(grid), dim3(FIT_WG), 0, st, genomes, n_genomes, rd, n_reads, n_sets, reads->qual_offset, s->dev());
   }
-  FIT_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, hipEventRecord(s->ev[1], st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "fit launch failed: %s", hipGetErrorString(rc));
   s->planned = false;
@@ -194,17 +152,17 @@ int simmr_fit_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_read
 int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info) {
   if (!e) return SIMMR_EINVAL;
   if (!info) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_plan: NULL argument");
-  FitState* s = state_of(e, false);
+  FitState* s = fit_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_fit_plan called before simmr_fit_reset");
-  FIT_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   s->planned = false;
   // ---- the error word and the two small histograms
   uint32_t errw = 0;
   std::vector<uint64_t> lhist(FitState::L_WORDS), ihist(FitState::I_WORDS);
-  FIT_TRY(e, hipMemcpyAsync(&errw, s->err(), 4, hipMemcpyDeviceToHost, st));
-  FIT_TRY(e, hipMemcpyAsync(lhist.data(), s->lhist(), FitState::L_WORDS * 8, hipMemcpyDeviceToHost, st));
-  FIT_TRY(e, hipMemcpyAsync(ihist.data(), s->ihist(), FitState::I_WORDS * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&errw, s->err(), 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(lhist.data(), s->lhist(), FitState::L_WORDS * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(ihist.data(), s->ihist(), FitState::I_WORDS * 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "fit add")) return rc;
   if (errw & FIT_ERR_READ)
     return eng_fail(e, SIMMR_EINVAL, "a read added since the last simmr_fit_reset names a genome slot or a contig that is not staged, its window "
@@ -234,7 +192,7 @@ int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info) {
   if (!s->pts.ensure(pts.size() * 8) || !s->qdens.ensure(std::max<uint64_t>(n_pos, 1) * SIMMR_FIT_DENSITIES * 8) ||
       !s->ldens.ensure(std::max<size_t>(s->len.lo.size(), 1) * 8) || !s->idens.ensure(std::max<size_t>(s->ins.lo.size(), 1) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "fit density allocation failed (%llu positions)", (unsigned long long)n_pos);
-  FIT_TRY(e, hipMemcpyAsync(s->pts.p, pts.data(), pts.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemcpyAsync(s->pts.p, pts.data(), pts.size() * 8, hipMemcpyHostToDevice, st));
   // ---- the device work: the densities
   if (n_pos > 0)
     hipLaunchKernelGGL(k_fit_density, dim3((uint32_t)n_pos, 1), dim3(FIT_DENSITY_WG), 0, st, s->qhist(), (uint64_t)SIMMR_FIT_QUALS, SIMMR_FIT_QUALS,
@@ -246,16 +204,16 @@ int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info) {
   if (!ipts.empty())
     hipLaunchKernelGGL(k_fit_density, dim3(1, (uint32_t)((ipts.size() + per_wg - 1) / per_wg)), dim3(FIT_DENSITY_WG), 0, st, s->ihist(), 0ull,
                        (uint32_t)FitState::I_WORDS, s->pts.as<const double>() + ip0, (uint32_t)ipts.size(), per_wg, 1e300, s->idens.as<double>());
-  if (s->len.point_mass) FIT_TRY(e, hipMemcpyAsync(s->ldens.p, s->len.density.data(), 8, hipMemcpyHostToDevice, st));
-  if (s->ins.point_mass) FIT_TRY(e, hipMemcpyAsync(s->idens.p, s->ins.density.data(), 8, hipMemcpyHostToDevice, st));
+  if (s->len.point_mass) HIP_TRY(e, hipMemcpyAsync(s->ldens.p, s->len.density.data(), 8, hipMemcpyHostToDevice, st));
+  if (s->ins.point_mass) HIP_TRY(e, hipMemcpyAsync(s->idens.p, s->ins.density.data(), 8, hipMemcpyHostToDevice, st));
   // ---- the pairs: counted, listed, sorted by (ref, count descending, alt ascending), totalled, cut, divided
   const uint64_t n_scan = s->n_dense + s->n_slots;
   const uint32_t scan_grid = (uint32_t)((n_scan + 255) / 256);
   unsigned long long n_live = 0;
-  FIT_TRY(e, hipMemsetAsync(s->n_out(), 0, 8, st));
+  HIP_TRY(e, hipMemsetAsync(s->n_out(), 0, 8, st));
   hipLaunchKernelGGL(k_fit_compact, dim3(scan_grid), dim3(256), 0, st, s->dev(), s->n_dense, s->n_slots, (unsigned long long*)nullptr,
                      (unsigned long long*)nullptr, 0ull, s->n_out());
-  FIT_TRY(e, hipMemcpyAsync(&n_live, s->n_out(), 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&n_live, s->n_out(), 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "fit plan (count)")) return rc;
   if (n_live > n_scan) return eng_fail(e, SIMMR_ENODEV, "fit plan: %llu live pairs in %llu entries", n_live, (unsigned long long)n_scan);
   const uint64_t n = n_live, n1 = std::max<uint64_t>(n, 1), n_tiles = (n + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
@@ -270,11 +228,11 @@ int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info) {
   unsigned long long* const total = s->refs.as<unsigned long long>();
   const FitRefs R{(uint32_t*)(total + 2 * s->n_dense), (uint32_t*)(total + 2 * s->n_dense) + s->n_dense, total, total + s->n_dense};
   unsigned long long* const sizes = total + 3 * s->n_dense;
-  FIT_TRY(e, hipMemsetAsync(s->refs.p, 0, refs_bytes, st));
-  FIT_TRY(e, hipMemsetAsync(R.start, 0xff, s->n_dense * 4, st));
-  FIT_TRY(e, hipMemsetAsync(s->kmer_first.p, 0, 8, st));
+  HIP_TRY(e, hipMemsetAsync(s->refs.p, 0, refs_bytes, st));
+  HIP_TRY(e, hipMemsetAsync(R.start, 0xff, s->n_dense * 4, st));
+  HIP_TRY(e, hipMemsetAsync(s->kmer_first.p, 0, 8, st));
   if (n > 0) {
-    FIT_TRY(e, hipMemsetAsync(s->n_out(), 0, 8, st));
+    HIP_TRY(e, hipMemsetAsync(s->n_out(), 0, 8, st));
     const unsigned long long* in_key = s->out_key.as<const unsigned long long>();
     const unsigned long long* in_cnt = s->out_cnt.as<const unsigned long long>();
     hipLaunchKernelGGL(k_fit_compact, dim3(scan_grid), dim3(256), 0, st, s->dev(), s->n_dense, s->n_slots, s->out_key.as<unsigned long long>(),
@@ -298,7 +256,7 @@ int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info) {
                        s->pair_count.as<unsigned long long>(), s->pair_prob.as<float>());
   }
   unsigned long long got[2] = {0, 0};
-  FIT_TRY(e, hipMemcpyAsync(got, sizes, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(got, sizes, 16, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "fit plan")) return rc;
   if (got[0] > max_refs || got[1] > n) return eng_fail(e, SIMMR_ENODEV, "fit plan: %llu reference k-mers and %llu pairs from %llu entries", got[0], got[1], n_live);
   simmr_fit_info f{};
@@ -329,7 +287,7 @@ int simmr_fit_plan(simmr_engine* e, simmr_fit_info* info) {
 int simmr_fit_emit(simmr_engine* e, const simmr_fit_out* out) {
   if (!e) return SIMMR_EINVAL;
   if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_emit: NULL argument");
-  FitState* s = state_of(e, false);
+  FitState* s = fit_state(e, false);
   if (!s || !s->ready || !s->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_fit_emit called without a simmr_fit_plan for the reads added");
   const simmr_fit_info& f = s->info;
   if (((out->kmer_ref || out->kmer_first) && out->ref_capacity < f.n_ref_kmers) ||
@@ -341,12 +299,12 @@ int simmr_fit_emit(simmr_engine* e, const simmr_fit_out* out) {
                                      "%llu length bins, %llu insert bins)",
                     (unsigned long long)f.n_ref_kmers, (unsigned long long)f.n_pairs, (unsigned long long)f.n_positions,
                     (unsigned long long)f.n_length_bins, (unsigned long long)f.n_insert_bins);
-  FIT_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
 #define FIT_H2D(dst, vec) \
-  if ((dst) && !(vec).empty()) FIT_TRY(e, hipMemcpyAsync((dst), (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, st))
+  if ((dst) && !(vec).empty()) HIP_TRY(e, hipMemcpyAsync((dst), (vec).data(), (vec).size() * sizeof((vec)[0]), hipMemcpyHostToDevice, st))
 #define FIT_D2D(dst, src, bytes) \
-  if ((dst) && (bytes)) FIT_TRY(e, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, st))
+  if ((dst) && (bytes)) HIP_TRY(e, hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, st))
   FIT_H2D(out->length_lo, s->len.lo);
   FIT_H2D(out->length_hi, s->len.hi);
   FIT_H2D(out->insert_lo, s->ins.lo);
@@ -369,10 +327,10 @@ int simmr_fit_emit(simmr_engine* e, const simmr_fit_out* out) {
 
 int simmr_last_fit_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
-  FitState* s = state_of(e, false);
+  FitState* s = fit_state(e, false);
   if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_fit_add yet");
   if (int rc = sync_check(e, "fit")) return rc;
-  FIT_TRY(e, hipEventElapsedTime(ms, s->ev[0], s->ev[1]));
+  HIP_TRY(e, hipEventElapsedTime(ms, s->ev[0], s->ev[1]));
   return SIMMR_OK;
 }
 

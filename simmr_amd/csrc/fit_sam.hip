@@ -1,7 +1,7 @@
 // fit_sam.hip — the model fit's SAM route (include/simmr_hip.h: simmr_fit_add_sam, simmr_fit_sam_counts_read): the entry
 // points over fit_sam_kernels.hip.  A translation unit of its own beside fit.hip: it adds into fit.hip's tables, which it gets
 // through fit_share (fit_device.hpp), and keeps only its side buffers in an engine slot of its own (ENG_EXT_FIT_SAM), grown on
-// demand and freed by simmr_engine_destroy.
+// demand and freed with the state (host_support.hpp).
 //
 // add:  enqueue-only, so nothing is sized from what the text holds.  The buffers are sized from n_bytes alone: a line start per
 //       two bytes (empty lines never enter the index), a descriptor per FSAM_MIN_TAKEN bytes (no shorter line is a taken
@@ -12,43 +12,18 @@
 #include <algorithm>
 
 #include "fit_sam_kernels.hip"
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 using namespace simmr;
 
 namespace {
 
-struct SideBuf {
-  void* p = nullptr;
-  size_t cap = 0;  // bytes
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);  // (waits for the work enqueued on it)
-    p = nullptr; cap = 0;
-    const size_t want = bytes + bytes / 4;
-    if (hipMalloc(&p, want) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    cap = want;
-    return true;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
-
 struct FitSamState {
-  SideBuf tile_sum, tile_prefix, starts, recs, rows, side, cursor;
+  DevBuf tile_sum, tile_prefix, starts, recs, rows, side, cursor;
 };
 
-void fit_sam_destroy(void* q) {
-  FitSamState* s = (FitSamState*)q;
-  for (SideBuf* b : {&s->tile_sum, &s->tile_prefix, &s->starts, &s->recs, &s->rows, &s->side, &s->cursor})
-    if (b->p) (void)hipFree(b->p);
-  delete s;
-}
-
-#define FSAM_TRY(e, call)                                                                   \
-  do {                                                                                      \
-    hipError_t _s = (call);                                                                 \
-    if (_s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); \
-  } while (0)
+// a side buffer that has to grow takes a quarter more than it is asked for (the free waits for the work enqueued on it)
+bool side_room(DevBuf& b, size_t bytes) { return b.ensure(bytes, bytes + bytes / 4); }
 
 }  // namespace
 
@@ -63,23 +38,21 @@ int simmr_fit_add_sam(simmr_engine* e, const uint8_t* text, uint64_t n_bytes, ui
                     (unsigned long long)n_bytes, (unsigned long long)SIMMR_FIT_SAM_MAX_BYTES);
   FitShare sh;
   if (!fit_share(e, &sh)) return eng_fail(e, SIMMR_ESTATE, "simmr_fit_add_sam called before simmr_fit_reset");
-  FSAM_TRY(e, hipSetDevice(eng_device(e)));
-  void** slot = eng_ext_slot(e, ENG_EXT_FIT_SAM, fit_sam_destroy);
-  if (!*slot) *slot = new FitSamState();
-  FitSamState* s = (FitSamState*)*slot;
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  FitSamState* s = unit_state<FitSamState, ENG_EXT_FIT_SAM>(e, true);
   hipStream_t st = eng_stream(e);
   const uint64_t n_tiles = (n_bytes + FSAM_TILE - 1) / FSAM_TILE, start_cap = n_bytes / 2 + 1, rec_cap = n_bytes / FSAM_MIN_TAKEN + 1;
   if (n_bytes > 0 &&
-      (!s->tile_sum.ensure(n_tiles * 8) || !s->tile_prefix.ensure((n_tiles + 1) * 8) || !s->starts.ensure(start_cap * 4) ||
-       !s->recs.ensure(rec_cap * sizeof(FsamRec)) || !s->rows.ensure(n_bytes + 16) || !s->side.ensure(n_bytes) || !s->cursor.ensure(16)))
+      (!side_room(s->tile_sum, n_tiles * 8) || !side_room(s->tile_prefix, (n_tiles + 1) * 8) || !side_room(s->starts, start_cap * 4) ||
+       !side_room(s->recs, rec_cap * sizeof(FsamRec)) || !side_room(s->rows, n_bytes + 16) || !side_room(s->side, n_bytes) || !side_room(s->cursor, 16)))
     return eng_fail(e, SIMMR_ENOMEM, "fit SAM side buffers: allocation failed for %llu bytes of text", (unsigned long long)n_bytes);
-  FSAM_TRY(e, hipEventRecord(sh.ev[0], st));
+  HIP_TRY(e, hipEventRecord(sh.ev[0], st));
   if (n_bytes > 0) {
     const uint32_t cus = (uint32_t)std::max(eng_cu_count(e), 1);
     const uint32_t tile_grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)cus * 16u);
     const uint32_t rec_grid = (uint32_t)std::min<uint64_t>(n_bytes / (FSAM_WG_RECS * FSAM_MIN_TAKEN) + 1, (uint64_t)cus * 8u);
-    FSAM_TRY(e, hipMemsetAsync(s->cursor.p, 0, 16, st));
-    FSAM_TRY(e, hipMemsetAsync(s->side.p, 0, n_bytes, st));
+    HIP_TRY(e, hipMemsetAsync(s->cursor.p, 0, 16, st));
+    HIP_TRY(e, hipMemsetAsync(s->side.p, 0, n_bytes, st));
     hipLaunchKernelGGL(k_fsam_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, s->tile_sum.as<uint64_t>(),
                        (const uint64_t*)nullptr, (uint32_t*)nullptr, 0ull);
     hipLaunchKernelGGL(k_fsam_scan, dim3(1), dim3(256), 0, st, s->tile_sum.as<const uint64_t>(), s->tile_prefix.as<uint64_t>(), n_tiles);
@@ -93,7 +66,7 @@ int simmr_fit_add_sam(simmr_engine* e, const uint8_t* text, uint64_t n_bytes, ui
     // the windows kernel keeps 64 KB of LDS: two workgroups a CU
     hipLaunchKernelGGL(k_fsam_windows, dim3(std::min(rec_grid, cus * 2u)), dim3(FSAM_WG), 0, st, W, sh.T);
   }
-  FSAM_TRY(e, hipEventRecord(sh.ev[1], st));
+  HIP_TRY(e, hipEventRecord(sh.ev[1], st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "fit SAM launch failed: %s", hipGetErrorString(rc));
   fit_share_added(e);
@@ -105,13 +78,10 @@ int simmr_fit_sam_counts_read(simmr_engine* e, simmr_fit_sam_counts* out) {
   if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_sam_counts_read: NULL argument");
   FitShare sh;
   if (!fit_share(e, &sh)) return eng_fail(e, SIMMR_ESTATE, "simmr_fit_sam_counts_read called before simmr_fit_reset");
-  FSAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  FSAM_TRY(e, hipMemcpyAsync(out, sh.counts, sizeof(*out), hipMemcpyDeviceToHost, st));
-  hipError_t rc = hipStreamSynchronize(st);
-  if (rc == hipSuccess) rc = hipGetLastError();
-  if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "fit SAM counts: %s", hipGetErrorString(rc));
-  return SIMMR_OK;
+  HIP_TRY(e, hipMemcpyAsync(out, sh.counts, sizeof(*out), hipMemcpyDeviceToHost, st));
+  return sync_check(e, "fit SAM counts");
 }
 
 }  // extern "C"

@@ -30,17 +30,13 @@ uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0
 // at least `bytes`, the first `keep` bytes of what it held copied over on `st`
 bool grow_keep(DevBuf* b, size_t bytes, size_t keep, hipStream_t st) {
   if (bytes <= b->cap) return true;
-  void* p = nullptr;
-  const size_t want = bytes + bytes / 2;
-  if (hipMalloc(&p, want) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (b->p && keep > 0 && hipMemcpyAsync(p, b->p, std::min(keep, b->cap), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+  DevBuf nb;
+  if (!nb.ensure(bytes, bytes + bytes / 2)) return false;
+  if (b->p && keep > 0 && hipMemcpyAsync(nb.p, b->p, std::min(keep, b->cap), hipMemcpyDeviceToDevice, st) != hipSuccess) {
     (void)hipGetLastError();
-    (void)hipFree(p);
     return false;
   }
-  if (b->p) (void)hipFree(b->p);  // (waits for the work enqueued on it, the copy included)
-  b->p = p;
-  b->cap = want;
+  *b = std::move(nb);  // (the free of what it held waits for the work enqueued on it, the copy included)
   return true;
 }
 
@@ -77,12 +73,7 @@ struct simmr_mapeval {
     }
     spans.clear();
   }
-  void release() {
-    for (DevBuf* b : {&blob, &name_off, &tile_sum, &tile_prefix, &starts, &u_key, &u_meta, &u_lo, &u_hi, &s_meta, &s_lo, &s_hi, &key[0], &key[1], &idx[0],
-                      &idx[1], &hist, &digit_total, &cursor, &counts, &word, &best, &hits})
-      b->release();
-    drop_spans();
-  }
+  ~simmr_mapeval() { drop_spans(); }  // (the list grows and is let go span by span: its events are not an Events set)
 };
 
 namespace {
@@ -107,10 +98,10 @@ int begin_span(simmr_mapeval* h, hipStream_t st) {
     h->spans.resize(kept);
   }
   Span s;
-  SAM_TRY(e, hipEventCreate(&s.a));
+  HIP_TRY(e, hipEventCreate(&s.a));
   h->spans.push_back(s);
-  SAM_TRY(e, hipEventCreate(&h->spans.back().b));
-  SAM_TRY(e, hipEventRecord(h->spans.back().a, st));
+  HIP_TRY(e, hipEventCreate(&h->spans.back().b));
+  HIP_TRY(e, hipEventRecord(h->spans.back().a, st));
   return SIMMR_OK;
 }
 
@@ -144,7 +135,7 @@ int enqueue_index(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes, hipSt
 
 int end_span(simmr_mapeval* h, hipStream_t st, const char* what) {
   simmr_engine* e = h->e;
-  SAM_TRY(e, hipEventRecord(h->spans.back().b, st));
+  HIP_TRY(e, hipEventRecord(h->spans.back().b, st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s launch failed: %s", what, hipGetErrorString(rc));
   return SIMMR_OK;
@@ -168,9 +159,8 @@ int simmr_mapeval_create(simmr_engine* e, simmr_mapeval** out) {
 void simmr_mapeval_destroy(simmr_mapeval* h) {
   if (!h) return;
   if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  h->release();
+  delete h;  // (its buffers and spans go with it)
   (void)hipGetLastError();
-  delete h;
 }
 
 int simmr_mapeval_reset(simmr_mapeval* h, const simmr_mapeval_config* cfg) {
@@ -198,8 +188,8 @@ int simmr_mapeval_reset(simmr_mapeval* h, const simmr_mapeval_config* cfg) {
     off.push_back((uint32_t)blob.size());
   }
   blob.resize(blob.size() + 8, 0);
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = sam_sync_check(e, "mapeval reset")) return rc;
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  if (int rc = sync_check(e, "mapeval reset")) return rc;
   h->planned = false;
   h->reset_once = false;
   h->drop_spans();
@@ -208,12 +198,12 @@ int simmr_mapeval_reset(simmr_mapeval* h, const simmr_mapeval_config* cfg) {
       !h->word.ensure(16))
     return eng_fail(e, SIMMR_ENOMEM, "mapeval reset: allocation failed");
   hipStream_t st = eng_stream(e);
-  SAM_TRY(e, hipMemcpyAsync(h->blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  SAM_TRY(e, hipMemcpyAsync(h->name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
-  SAM_TRY(e, hipMemsetAsync(h->cursor.p, 0, 16, st));
-  SAM_TRY(e, hipMemsetAsync(h->counts.p, 0, COUNT_WORDS * 8, st));
-  SAM_TRY(e, hipMemsetAsync(h->word.p, 0, 16, st));
-  if (int rc = sam_sync_check(e, "mapeval reset")) return rc;  // (the uploads read host vectors that end here)
+  HIP_TRY(e, hipMemcpyAsync(h->blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemcpyAsync(h->name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemsetAsync(h->cursor.p, 0, 16, st));
+  HIP_TRY(e, hipMemsetAsync(h->counts.p, 0, COUNT_WORDS * 8, st));
+  HIP_TRY(e, hipMemsetAsync(h->word.p, 0, 16, st));
+  if (int rc = sync_check(e, "mapeval reset")) return rc;  // (the uploads read host vectors that end here)
   h->n_names = (uint32_t)names.size();
   h->min_pct = cfg->min_overlap_pct ? cfg->min_overlap_pct : 10u;
   h->entry_cap = 0;
@@ -228,7 +218,7 @@ int simmr_mapeval_truth_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_by
   if (int rc = check_text(h, text, n_bytes, "simmr_mapeval_truth_add")) return rc;
   h->planned = false;
   if (n_bytes == 0) return SIMMR_OK;
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   const uint64_t cap = h->entry_cap + n_bytes / MEV_MIN_LINE + 1, held = h->entry_cap;
   if (!grow_keep(&h->u_key, cap * 8, held * 8, st) || !grow_keep(&h->u_meta, cap * 4, held * 4, st) || !grow_keep(&h->u_lo, cap * 8, held * 8, st) ||
@@ -250,13 +240,13 @@ int simmr_mapeval_truth_plan(simmr_mapeval* h, uint64_t* n_entries) {
   simmr_engine* e = h->e;
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "simmr_mapeval_truth_plan called before simmr_mapeval_reset");
   h->planned = false;
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   uint64_t cur2[2] = {0, 0};
   uint32_t errw = 0;
-  SAM_TRY(e, hipMemcpyAsync(cur2, h->cursor.p, 16, hipMemcpyDeviceToHost, st));
-  SAM_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, "mapeval truth adds")) return rc;
+  HIP_TRY(e, hipMemcpyAsync(cur2, h->cursor.p, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_check(e, "mapeval truth adds")) return rc;
   if (errw & MEV_ERR_TRUTH)
     return eng_fail(e, SIMMR_EINVAL, "a malformed truth record: fewer than 11 fields, a bad FLAG / POS / MAPQ / CIGAR, a QNAME that is no read id, an RNAME "
                                      "outside the names, or a POS of 0");
@@ -271,12 +261,12 @@ int simmr_mapeval_truth_plan(simmr_mapeval* h, uint64_t* n_entries) {
     return eng_fail(e, SIMMR_ENOMEM, "mapeval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
   if (int rc = begin_span(h, st)) return rc;
   // the aligned side starts over: its counts (the words behind the truth's four), by_mapq, best and hits
-  SAM_TRY(e, hipMemsetAsync(h->counts_p() + MC_LINES, 0, (COUNT_WORDS - MC_LINES) * 8, st));
-  SAM_TRY(e, hipMemsetAsync(h->best.p, 0, n1 * 4, st));
-  SAM_TRY(e, hipMemsetAsync(h->hits.p, 0, n1 * 4, st));
+  HIP_TRY(e, hipMemsetAsync(h->counts_p() + MC_LINES, 0, (COUNT_WORDS - MC_LINES) * 8, st));
+  HIP_TRY(e, hipMemsetAsync(h->best.p, 0, n1 * 4, st));
+  HIP_TRY(e, hipMemsetAsync(h->hits.p, 0, n1 * 4, st));
   h->skey = h->key[0].as<const uint64_t>();
   if (n > 0) {
-    SAM_TRY(e, hipMemcpyAsync(h->key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(e, hipMemcpyAsync(h->key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
     uint64_t* const keys[2] = {h->key[0].as<uint64_t>(), h->key[1].as<uint64_t>()};
     uint32_t* const idxs[2] = {h->idx[0].as<uint32_t>(), h->idx[1].as<uint32_t>()};
     const uint32_t key_bits = bits_of(cur2[1]);
@@ -289,11 +279,11 @@ int simmr_mapeval_truth_plan(simmr_mapeval* h, uint64_t* n_entries) {
                        n, h->word.as<uint32_t>());
   }
   if (int rc = end_span(h, st, "mapeval truth plan")) return rc;
-  SAM_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, "mapeval truth plan")) return rc;
+  HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_check(e, "mapeval truth plan")) return rc;
   if (errw & MEV_ERR_DUP) {
     uint32_t cleared = errw & ~MEV_ERR_DUP;  // (the entries stay; the flag is the plan's alone)
-    SAM_TRY(e, hipMemcpy(h->word.p, &cleared, 4, hipMemcpyHostToDevice));
+    HIP_TRY(e, hipMemcpy(h->word.p, &cleared, 4, hipMemcpyHostToDevice));
     return eng_fail(e, SIMMR_EINVAL, "two truth records have one read id and mate: the key of an entry is unique");
   }
   h->n_entries = n;
@@ -308,7 +298,7 @@ int simmr_mapeval_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes) {
   if (int rc = check_text(h, text, n_bytes, "simmr_mapeval_add")) return rc;
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_mapeval_add called without a simmr_mapeval_truth_plan in force");
   if (n_bytes == 0) return SIMMR_OK;
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   if (int rc = begin_span(h, st)) return rc;
   MevText W;
@@ -324,18 +314,18 @@ int simmr_mapeval_read(simmr_mapeval* h, simmr_mapeval_counts* counts, uint64_t*
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "simmr_mapeval_read called before simmr_mapeval_reset");
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  SAM_TRY(e, hipMemsetAsync(h->counts_p() + MC_MISSING, 0, 5 * 8, st));
+  HIP_TRY(e, hipMemsetAsync(h->counts_p() + MC_MISSING, 0, 5 * 8, st));
   if (h->planned && h->n_entries > 0) {
     const uint32_t grid = (uint32_t)std::min<uint64_t>((h->n_entries + 255) / 256, (uint64_t)std::max(eng_cu_count(e), 1) * 16u);
     hipLaunchKernelGGL(k_mev_reduce, dim3(grid), dim3(256), 0, st, h->best.as<const uint32_t>(), h->hits.as<const uint32_t>(), h->n_entries, h->counts_p());
   }
   std::vector<uint64_t> host(COUNT_WORDS);
   uint32_t errw = 0;
-  SAM_TRY(e, hipMemcpyAsync(host.data(), h->counts.p, COUNT_WORDS * 8, hipMemcpyDeviceToHost, st));
-  SAM_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, "mapeval read")) return rc;
+  HIP_TRY(e, hipMemcpyAsync(host.data(), h->counts.p, COUNT_WORDS * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_check(e, "mapeval read")) return rc;
   if (errw & (MEV_ERR_TRUTH | MEV_ERR_ALIGNED))
     return eng_fail(e, SIMMR_EINVAL, "a malformed %s record: fewer than 11 fields, a bad FLAG / POS / MAPQ / CIGAR, or a POS of 0 where the record is mapped",
                     errw & MEV_ERR_TRUTH ? "truth" : "aligned");
@@ -350,14 +340,14 @@ int simmr_mapeval_emit(simmr_mapeval* h, uint64_t* key_dev, uint32_t* best_dev, 
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_mapeval_emit called without a simmr_mapeval_truth_plan in force");
   if (capacity < h->n_entries)
     return eng_fail(e, SIMMR_ERANGE, "capacity %llu < %llu truth entries", (unsigned long long)capacity, (unsigned long long)h->n_entries);
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   if (h->n_entries > 0) {
-    if (key_dev) SAM_TRY(e, hipMemcpyAsync(key_dev, h->skey, h->n_entries * 8, hipMemcpyDeviceToDevice, st));
-    if (best_dev) SAM_TRY(e, hipMemcpyAsync(best_dev, h->best.p, h->n_entries * 4, hipMemcpyDeviceToDevice, st));
-    if (hits_dev) SAM_TRY(e, hipMemcpyAsync(hits_dev, h->hits.p, h->n_entries * 4, hipMemcpyDeviceToDevice, st));
+    if (key_dev) HIP_TRY(e, hipMemcpyAsync(key_dev, h->skey, h->n_entries * 8, hipMemcpyDeviceToDevice, st));
+    if (best_dev) HIP_TRY(e, hipMemcpyAsync(best_dev, h->best.p, h->n_entries * 4, hipMemcpyDeviceToDevice, st));
+    if (hits_dev) HIP_TRY(e, hipMemcpyAsync(hits_dev, h->hits.p, h->n_entries * 4, hipMemcpyDeviceToDevice, st));
   }
-  return sam_sync_check(e, "mapeval emit");
+  return sync_check(e, "mapeval emit");
 }
 
 int simmr_last_mapeval_ms(simmr_mapeval* h, float* ms) {
@@ -365,8 +355,8 @@ int simmr_last_mapeval_ms(simmr_mapeval* h, float* ms) {
   simmr_engine* e = h->e;
   if (!ms) return eng_fail(e, SIMMR_EINVAL, "simmr_last_mapeval_ms: NULL ms");
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_mapeval_reset yet");
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = sam_sync_check(e, "mapeval")) return rc;
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  if (int rc = sync_check(e, "mapeval")) return rc;
   for (const Span& s : h->spans) {
     float one = 0.f;
     if (s.a && s.b && hipEventElapsedTime(&one, s.a, s.b) == hipSuccess) h->done_ms += one;

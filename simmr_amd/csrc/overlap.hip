@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "overlap_kernels.hip"
@@ -30,27 +31,13 @@ struct OverlapState {
   uint64_t min_overlap = 0, total = 0;
   bool ready = false, planned = false, planned_once = false;
   float emit_ms = 0.f;
-  hipEvent_t ev[4] = {};
+  Events<4> ev;
   uint32_t* err_p() const { return word.as<uint32_t>(); }
   uint64_t* win_p() const { return word.as<uint64_t>() + 2; }
   OvlRows rows() const { return OvlRows{g_cbase.as<const uint32_t>(), g_ncontig.as<const uint32_t>(), c_bases.as<const uint64_t>(), n_slots}; }
 };
 
-void overlap_destroy(void* q) {
-  OverlapState* s = (OverlapState*)q;
-  for (DevBuf* b : {&s->g_cbase, &s->g_ncontig, &s->c_bases, &s->key, &s->meta, &s->rid, &s->skey[0], &s->skey[1], &s->sidx[0], &s->sidx[1], &s->hist,
-                    &s->digit_total, &s->smeta, &s->srid, &s->cnt, &s->rec_off, &s->chunk_sum, &s->chunk_prefix, &s->rsum, &s->rprefix, &s->word})
-    b->release();
-  for (hipEvent_t ev : s->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete s;
-}
-
-OverlapState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_OVERLAP, overlap_destroy);
-  if (!*slot && create) *slot = new OverlapState();
-  return (OverlapState*)*slot;
-}
+constexpr auto overlap_state = unit_state<OverlapState, ENG_EXT_OVERLAP>;
 
 // room for `want` entries of `width` bytes with the first `keep` entries kept: a column that grows by half of itself
 bool grow(DevBuf* b, uint64_t keep, uint64_t want, size_t width, hipStream_t st) {
@@ -59,11 +46,9 @@ bool grow(DevBuf* b, uint64_t keep, uint64_t want, size_t width, hipStream_t st)
   if (!nb.ensure((size_t)std::max<uint64_t>(want + want / 2, 1024) * width)) return false;
   if (keep > 0 && (hipMemcpyAsync(nb.p, b->p, keep * width, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)) {
     (void)hipGetLastError();
-    nb.release();
     return false;
   }
-  b->release();
-  *b = nb;
+  *b = std::move(nb);  // (frees what it held)
   return true;
 }
 
@@ -75,8 +60,8 @@ int window_of(simmr_engine* e, OverlapState* s, uint64_t first, uint64_t max_byt
   }
   hipStream_t st = eng_stream(e);
   hipLaunchKernelGGL(k_ovl_window, dim3(1), dim3(256), 0, st, s->sorted, s->rprefix.as<const uint64_t>(), first, max_bytes, fixed_places, s->win_p());
-  SAM_TRY(e, hipMemcpyAsync(out, s->win_p(), 48, hipMemcpyDeviceToHost, st));
-  return sam_sync_check(e, what);
+  HIP_TRY(e, hipMemcpyAsync(out, s->win_p(), 48, hipMemcpyDeviceToHost, st));
+  return sync_check(e, what);
 }
 
 int need_plan(simmr_engine* e, OverlapState* s, const char* who) {
@@ -92,26 +77,20 @@ extern "C" {
 
 int simmr_overlap_reset(simmr_engine* e, int paired) {
   if (!e) return SIMMR_EINVAL;
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
-  OverlapState* s = state_of(e, true);
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  OverlapState* s = overlap_state(e, true);
   s->ready = s->planned = false;
   s->n = 0;
-  if (int rc = sam_sync_check(e, "overlap reset")) return rc;
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) SAM_TRY(e, hipEventCreate(&ev));
-  const uint32_t n_slots = eng_genome_slots(e);
-  std::vector<uint32_t> cbase(std::max(n_slots, 1u), 0u), ncontig(std::max(n_slots, 1u), 0u);
-  std::vector<uint64_t> bases;
-  uint64_t longest = 0;
-  for (uint32_t g = 0; g < n_slots; g++) {
-    const uint32_t nc = eng_contig_count(e, g);
-    cbase[g] = (uint32_t)bases.size();
-    ncontig[g] = nc;
-    for (uint32_t c = 0; c < nc; c++) {
-      bases.push_back(eng_contig_len(e, g, c));
-      longest = std::max(longest, bases.back());
-    }
-  }
+  if (int rc = sync_check(e, "overlap reset")) return rc;
+  if (int rc = s->ev.create_missing(e)) return rc;
+  StagedRows rows = staged_rows(e);
+  const uint32_t n_slots = rows.n_slots();
+  std::vector<uint32_t>& cbase = rows.cbase;
+  std::vector<uint32_t>& ncontig = rows.ncontig;
+  std::vector<uint64_t>& bases = rows.bases;
+  const uint64_t longest = rows.longest;
+  cbase.resize(std::max(n_slots, 1u), 0u);
+  ncontig.resize(std::max(n_slots, 1u), 0u);
   s->n_rows = bases.size();
   if (bases.empty()) bases.push_back(0);
   // the sort key has one row more than the engine: where reads shorter than min_overlap go
@@ -122,11 +101,11 @@ int simmr_overlap_reset(simmr_engine* e, int paired) {
   if (!s->g_cbase.ensure(cbase.size() * 4) || !s->g_ncontig.ensure(ncontig.size() * 4) || !s->c_bases.ensure(bases.size() * 8) || !s->word.ensure(64))
     return eng_fail(e, SIMMR_ENOMEM, "overlap reset allocation failed");
   hipStream_t st = eng_stream(e);
-  SAM_TRY(e, hipMemcpyAsync(s->g_cbase.p, cbase.data(), cbase.size() * 4, hipMemcpyHostToDevice, st));
-  SAM_TRY(e, hipMemcpyAsync(s->g_ncontig.p, ncontig.data(), ncontig.size() * 4, hipMemcpyHostToDevice, st));
-  SAM_TRY(e, hipMemcpyAsync(s->c_bases.p, bases.data(), bases.size() * 8, hipMemcpyHostToDevice, st));
-  SAM_TRY(e, hipMemsetAsync(s->word.p, 0, 64, st));
-  if (int rc = sam_sync_check(e, "overlap reset")) return rc;  // (the tables were copied from vectors of this call)
+  HIP_TRY(e, hipMemcpyAsync(s->g_cbase.p, cbase.data(), cbase.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemcpyAsync(s->g_ncontig.p, ncontig.data(), ncontig.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemcpyAsync(s->c_bases.p, bases.data(), bases.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemsetAsync(s->word.p, 0, 64, st));
+  if (int rc = sync_check(e, "overlap reset")) return rc;  // (the tables were copied from vectors of this call)
   s->n_slots = n_slots;
   s->pos_bits = pos_bits;
   s->key_bits = pos_bits + row_bits;
@@ -141,7 +120,7 @@ int simmr_overlap_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_
   if (!reads) return eng_fail(e, SIMMR_EINVAL, "simmr_overlap_add: NULL argument");
   if (!reads->start || !reads->end || !reads->contig || !reads->genome || !reads->read_id || !reads->flags)
     return eng_fail(e, SIMMR_EINVAL, "simmr_overlap_add needs start, end, contig, genome, read_id and flags");
-  OverlapState* s = state_of(e, false);
+  OverlapState* s = overlap_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_overlap_add called before simmr_overlap_reset");
   if (s->epoch != eng_staging_epoch(e)) return eng_fail(e, SIMMR_ESTATE, "a genome was staged since simmr_overlap_reset: the rows are the reset's");
   if (s->paired && (n_reads & 1u)) return eng_fail(e, SIMMR_EINVAL, "simmr_overlap_add: paired with an odd number of reads");
@@ -149,18 +128,18 @@ int simmr_overlap_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_
     return eng_fail(e, SIMMR_ERANGE, "the reads added since simmr_overlap_reset would reach 2^31");
   s->planned = false;
   if (n_reads == 0) return SIMMR_OK;
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   const uint64_t want = s->n + n_reads;
   if (!grow(&s->key, s->n, want, 8, st) || !grow(&s->meta, s->n, want, 8, st) || !grow(&s->rid, s->n, want, 4, st))
     return eng_fail(e, SIMMR_ENOMEM, "overlap columns allocation failed (%llu reads)", (unsigned long long)want);
-  SAM_TRY(e, hipMemsetAsync(s->word.p, 0, 4, st));
+  HIP_TRY(e, hipMemsetAsync(s->word.p, 0, 4, st));
   hipLaunchKernelGGL(k_ovl_add, dim3((uint32_t)((n_reads + 255) / 256)), dim3(256), 0, st, reads->start, reads->end, reads->contig, reads->genome,
                      reads->read_id, reads->flags, n_reads, s->rows(), s->paired, s->key.as<uint64_t>() + s->n, s->meta.as<uint64_t>() + s->n,
                      s->rid.as<uint32_t>() + s->n, s->err_p());
   uint32_t errw = 0;
-  SAM_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, "overlap add")) return rc;
+  HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_check(e, "overlap add")) return rc;
   if (errw)
     return eng_fail(e, SIMMR_EINVAL, "a read's genome slot or contig is not staged, or the read ends behind its contig's staged length: nothing "
                                      "of this call was added");
@@ -170,12 +149,12 @@ int simmr_overlap_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_
 
 int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads, uint64_t* n_pairs, uint64_t* total_bytes) {
   if (!e) return SIMMR_EINVAL;
-  OverlapState* s = state_of(e, false);
+  OverlapState* s = overlap_state(e, false);
   if (s) s->planned = false;
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_overlap_plan called before simmr_overlap_reset");
   if (s->epoch != eng_staging_epoch(e)) return eng_fail(e, SIMMR_ESTATE, "a genome was staged since simmr_overlap_reset: the rows are the reset's");
   if (min_overlap < 1) return eng_fail(e, SIMMR_EINVAL, "simmr_overlap_plan: min_overlap is at least 1");
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   const uint64_t n = s->n, n1 = std::max<uint64_t>(n, 1);
   const uint64_t n_chunks = (n + SAM_CHUNK - 1) / SAM_CHUNK, n_tiles = (n + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
   if (!s->skey[0].ensure(n1 * 8) || !s->skey[1].ensure(n1 * 8) || !s->sidx[0].ensure(n1 * 4) || !s->sidx[1].ensure(n1 * 4) ||
@@ -185,7 +164,7 @@ int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads,
     return eng_fail(e, SIMMR_ENOMEM, "overlap plan allocation failed (%llu reads)", (unsigned long long)n);
   hipStream_t st = eng_stream(e);
   const uint32_t cap = (uint32_t)eng_cu_count(e) * OVL_WGS_PER_CU;
-  SAM_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, hipEventRecord(s->ev[0], st));
   uint64_t pairs = 0, total = 0;
   s->sorted = OvlSorted{};
   if (n > 0) {
@@ -202,8 +181,8 @@ int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads,
     hipLaunchKernelGGL(k_ovl_scan, dim3(1), dim3(256), 0, st, s->chunk_sum.as<const uint64_t>(), s->chunk_prefix.as<uint64_t>(), n_chunks);
     hipLaunchKernelGGL(k_ovl_offsets, dim3(grid), dim3(256), 0, st, s->cnt.as<const uint32_t>(), s->chunk_prefix.as<const uint64_t>(), n,
                        s->rec_off.as<uint64_t>());
-    SAM_TRY(e, hipMemcpyAsync(&pairs, s->rec_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
-    if (int rc = sam_sync_check(e, "overlap sort and partner count")) return rc;  // (the number of records sizes the second scan)
+    HIP_TRY(e, hipMemcpyAsync(&pairs, s->rec_off.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
+    if (int rc = sync_check(e, "overlap sort and partner count")) return rc;  // (the number of records sizes the second scan)
     const uint64_t r_chunks = (pairs + OVL_CHUNK - 1) / OVL_CHUNK;
     if (!s->rsum.ensure(std::max<uint64_t>(r_chunks, 1) * 8) || !s->rprefix.ensure((r_chunks + 1) * 8))
       return eng_fail(e, SIMMR_ENOMEM, "overlap plan allocation failed (%llu records)", (unsigned long long)pairs);
@@ -212,10 +191,10 @@ int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads,
     hipLaunchKernelGGL(k_ovl_size, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(r_chunks, cap))), dim3(256), 0, st, s->sorted,
                        s->rsum.as<uint64_t>());
     hipLaunchKernelGGL(k_ovl_scan, dim3(1), dim3(256), 0, st, s->rsum.as<const uint64_t>(), s->rprefix.as<uint64_t>(), r_chunks);
-    SAM_TRY(e, hipMemcpyAsync(&total, s->rprefix.as<uint64_t>() + r_chunks, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(e, hipMemcpyAsync(&total, s->rprefix.as<uint64_t>() + r_chunks, 8, hipMemcpyDeviceToHost, st));
   }
-  SAM_TRY(e, hipEventRecord(s->ev[1], st));
-  if (int rc = sam_sync_check(e, "overlap size pass and scan")) return rc;
+  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  if (int rc = sync_check(e, "overlap size pass and scan")) return rc;
   s->min_overlap = min_overlap;
   s->total = total;
   s->emit_ms = 0.f;
@@ -228,10 +207,10 @@ int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads,
 
 int simmr_overlap_window(simmr_engine* e, uint64_t first_place, uint64_t max_bytes, uint64_t* n_places, uint64_t* n_pairs, uint64_t* bytes) {
   if (!e) return SIMMR_EINVAL;
-  OverlapState* s = state_of(e, false);
+  OverlapState* s = overlap_state(e, false);
   if (int rc = need_plan(e, s, "simmr_overlap_window")) return rc;
   if (first_place > s->n) return eng_fail(e, SIMMR_EINVAL, "simmr_overlap_window: place %llu of %llu", (unsigned long long)first_place, (unsigned long long)s->n);
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   uint64_t w[6];
   if (int rc = window_of(e, s, first_place, max_bytes, ~0ull, w, "overlap window")) return rc;
   if (w[0] == 0 && first_place < s->n) {  // the first place alone does not fit
@@ -250,12 +229,12 @@ int simmr_overlap_window(simmr_engine* e, uint64_t first_place, uint64_t max_byt
 int simmr_overlap_emit(simmr_engine* e, uint64_t first_place, uint64_t n_places, const simmr_overlap_cols* cols, uint8_t* dst,
                        uint64_t dst_capacity) {
   if (!e) return SIMMR_EINVAL;
-  OverlapState* s = state_of(e, false);
+  OverlapState* s = overlap_state(e, false);
   if (int rc = need_plan(e, s, "simmr_overlap_emit")) return rc;
   if (first_place > s->n || n_places > s->n - first_place)
     return eng_fail(e, SIMMR_EINVAL, "simmr_overlap_emit: places %llu + %llu of %llu", (unsigned long long)first_place, (unsigned long long)n_places,
                     (unsigned long long)s->n);
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   uint64_t w[6];
   if (int rc = window_of(e, s, first_place, 0, n_places, w, "overlap emit")) return rc;
   const uint64_t j0 = w[1], j1 = w[2], b0 = w[3], bytes = w[4] - w[3];
@@ -267,27 +246,27 @@ int simmr_overlap_emit(simmr_engine* e, uint64_t first_place, uint64_t n_places,
   if (any && cols->capacity < j1 - j0)
     return eng_fail(e, SIMMR_ERANGE, "cols->capacity %llu < %llu records of these places", (unsigned long long)cols->capacity, (unsigned long long)(j1 - j0));
   hipStream_t st = eng_stream(e);
-  SAM_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, hipEventRecord(s->ev[2], st));
   if (j1 > j0 && (dst || any)) {
     const uint64_t chunks = (j1 + OVL_CHUNK - 1) / OVL_CHUNK - j0 / OVL_CHUNK;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(chunks, (uint64_t)eng_cu_count(e) * OVL_WGS_PER_CU);
     hipLaunchKernelGGL(k_ovl_write, dim3(grid), dim3(256), 0, st, s->sorted, s->rprefix.as<const uint64_t>(), j0, j1, b0, bytes, dst, c);
   }
-  SAM_TRY(e, hipEventRecord(s->ev[3], st));
-  if (int rc = sam_sync_check(e, "overlap write pass")) return rc;
+  HIP_TRY(e, hipEventRecord(s->ev[3], st));
+  if (int rc = sync_check(e, "overlap write pass")) return rc;
   float ms = 0.f;
-  SAM_TRY(e, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+  HIP_TRY(e, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
   s->emit_ms += ms;
   return SIMMR_OK;
 }
 
 int simmr_last_overlap_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
-  OverlapState* s = state_of(e, false);
+  OverlapState* s = overlap_state(e, false);
   if (!s || !s->planned_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_overlap_plan yet");
-  if (int rc = sam_sync_check(e, "overlap")) return rc;
+  if (int rc = sync_check(e, "overlap")) return rc;
   float a = 0.f;
-  SAM_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
   *ms = a + s->emit_ms;
   return SIMMR_OK;
 }

@@ -1,32 +1,19 @@
 // pileup.hip — allele counts at listed sites (include/simmr_hip.h: simmr_pileup_*): the entry points over
 // pileup_kernels.hip.  The fifth translation unit of libsimmr_hip.so; it sees an engine through engine_internal.hpp only,
 // records the dense layout of the staged genomes itself (as depth.hip does: it needs no simmr_depth_reset) and keeps its
-// state in the engine's opaque slot (freed by simmr_engine_destroy through the hook given there).
+// state in the engine's opaque slot (host_support.hpp: unit_state; simmr_engine_destroy deletes it, and its members free what they own).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "pileup_kernels.hip"
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 using namespace simmr;
 
 namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;  // bytes
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    cap = bytes;
-    return true;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
 
 struct PileupState {
   // the layout recorded by the last reset: genome slots -> contigs -> first position
@@ -36,7 +23,7 @@ struct PileupState {
   bool ready = false, timed = false;
   DevBuf d_slots, d_cfirst, keys;
   DevBuf table;  // counts[n][2][5], then the first bad site of the reset (64 bits), then the adds' sticky error word
-  hipEvent_t ev[2] = {};
+  Events<2> ev;
 
   size_t table_bytes() const { return (size_t)n * PILEUP_CELLS * 4u; }
   uint32_t* counts_p() const { return table.as<uint32_t>(); }
@@ -44,33 +31,7 @@ struct PileupState {
   uint32_t* err_p() const { return (uint32_t*)(table.as<char>() + table_bytes() + 8); }
 };
 
-void pileup_destroy(void* q) {
-  PileupState* s = (PileupState*)q;
-  for (DevBuf* b : {&s->d_slots, &s->d_cfirst, &s->keys, &s->table})
-    if (b->p) (void)hipFree(b->p);
-  for (hipEvent_t ev : s->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete s;
-}
-
-PileupState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_PILEUP, pileup_destroy);
-  if (!*slot && create) *slot = new PileupState();
-  return (PileupState*)*slot;
-}
-
-#define PILEUP_TRY(e, call)                                                                 \
-  do {                                                                                      \
-    hipError_t _s = (call);                                                                 \
-    if (_s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); \
-  } while (0)
-
-int sync_check(simmr_engine* e, const char* what) {
-  hipError_t s = hipStreamSynchronize(eng_stream(e));
-  if (s == hipSuccess) s = hipGetLastError();
-  if (s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  return SIMMR_OK;
-}
+constexpr auto pileup_state = unit_state<PileupState, ENG_EXT_PILEUP>;
 
 }  // namespace
 
@@ -82,35 +43,31 @@ int simmr_pileup_reset(simmr_engine* e, const simmr_pileup_sites* sites) {
   const uint64_t n = sites->n;
   if (n > 0 && (!sites->genome || !sites->contig || !sites->pos)) return eng_fail(e, SIMMR_EINVAL, "simmr_pileup_reset: NULL site column");
   if ((n + PILEUP_WG - 1) / PILEUP_WG >= (1ull << 31)) return eng_fail(e, SIMMR_ENOTSUP, "simmr_pileup_reset: too many sites for one launch");
-  PILEUP_TRY(e, hipSetDevice(eng_device(e)));
-  PileupState* s = state_of(e, true);
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  PileupState* s = pileup_state(e, true);
   s->ready = s->timed = false;
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) PILEUP_TRY(e, hipEventCreate(&ev));
+  if (int rc = s->ev.create_missing(e)) return rc;
   // the dense layout of the genomes staged now: contig firsts, no padding (depth[]'s order)
-  const uint32_t n_slots = eng_genome_slots(e);
+  StagedRows rows = staged_rows(e);
+  const uint32_t n_slots = rows.n_slots();
   s->slots.assign(n_slots, PileupSlot{0u, 0u});
-  s->cfirst.assign(1, 0ull);
-  for (uint32_t g = 0; g < n_slots; g++) {
-    const uint32_t nc = eng_contig_count(e, g);
-    s->slots[g] = PileupSlot{(uint32_t)(s->cfirst.size() - 1), nc};
-    for (uint32_t c = 0; c < nc; c++) s->cfirst.push_back(s->cfirst.back() + eng_contig_len(e, g, c));
-  }
+  for (uint32_t g = 0; g < n_slots; g++) s->slots[g] = PileupSlot{rows.cbase[g], rows.ncontig[g]};
+  s->cfirst = std::move(rows.first);
   s->n = n;
   if (!s->d_slots.ensure(std::max<size_t>(n_slots, 1) * sizeof(PileupSlot)) || !s->d_cfirst.ensure(s->cfirst.size() * 8) ||
       !s->keys.ensure(std::max<uint64_t>(n, 1) * 8) || !s->table.ensure(s->table_bytes() + 16))
     return eng_fail(e, SIMMR_ENOMEM, "pileup table allocation failed (%llu sites)", (unsigned long long)n);
   hipStream_t st = eng_stream(e);
-  PILEUP_TRY(e, hipMemsetAsync(s->table.p, 0, s->table_bytes() + 16, st));
-  PILEUP_TRY(e, hipMemsetAsync(s->bad_p(), 0xff, 8, st));
-  if (n_slots) PILEUP_TRY(e, hipMemcpyAsync(s->d_slots.p, s->slots.data(), n_slots * sizeof(PileupSlot), hipMemcpyHostToDevice, st));
-  PILEUP_TRY(e, hipMemcpyAsync(s->d_cfirst.p, s->cfirst.data(), s->cfirst.size() * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemsetAsync(s->table.p, 0, s->table_bytes() + 16, st));
+  HIP_TRY(e, hipMemsetAsync(s->bad_p(), 0xff, 8, st));
+  if (n_slots) HIP_TRY(e, hipMemcpyAsync(s->d_slots.p, s->slots.data(), n_slots * sizeof(PileupSlot), hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemcpyAsync(s->d_cfirst.p, s->cfirst.data(), s->cfirst.size() * 8, hipMemcpyHostToDevice, st));
   if (n > 0)
     hipLaunchKernelGGL(k_pileup_keys, dim3((uint32_t)((n + PILEUP_WG - 1) / PILEUP_WG)), dim3(PILEUP_WG), 0, st, sites->genome, sites->contig,
                        sites->pos, n, s->d_slots.as<const PileupSlot>(), n_slots, s->d_cfirst.as<const uint64_t>(), s->keys.as<uint64_t>(),
                        s->bad_p());
   unsigned long long bad = ~0ull;
-  PILEUP_TRY(e, hipMemcpyAsync(&bad, s->bad_p(), 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&bad, s->bad_p(), 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "pileup reset")) return rc;  // (the tables were copied from vectors the next reset rewrites)
   if (bad != ~0ull)
     return eng_fail(e, SIMMR_EINVAL, "site %llu: its genome slot is not staged, its contig does not exist, its position is not inside the "
@@ -127,15 +84,15 @@ int simmr_pileup_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
   if (!reads) return eng_fail(e, SIMMR_EINVAL, "simmr_pileup_add: NULL argument");
   if (!reads->seq || !reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags)
     return eng_fail(e, SIMMR_EINVAL, "simmr_pileup_add needs seq, seq_off, start, end, contig, genome and flags");
-  PileupState* s = state_of(e, false);
+  PileupState* s = pileup_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_pileup_add called before simmr_pileup_reset");
   if (s->epoch != eng_staging_epoch(e))
     return eng_fail(e, SIMMR_ESTATE, "a genome was staged since simmr_pileup_reset: the sites' keys are the reset's");
   if (n_reads >= (1ull << 31) || s->added + n_reads >= (1ull << 31))
     return eng_fail(e, SIMMR_ERANGE, "the reads added since simmr_pileup_reset would reach 2^31");
-  PILEUP_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  PILEUP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, hipEventRecord(s->ev[0], st));
   if (n_reads > 0 && s->n > 0) {
     // persistent: eight waves per SIMD's worth of waves, each looping over its share of the 64-read batches
     const uint64_t batches = (n_reads + 63) / 64, wgs = (batches + PILEUP_WG / 64 - 1) / (PILEUP_WG / 64);
@@ -144,7 +101,7 @@ int simmr_pileup_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
     hipLaunchKernelGGL(k_pileup_add, dim3(grid), dim3(PILEUP_WG), 0, st, rd, n_reads, s->d_slots.as<const PileupSlot>(),
                        (uint32_t)s->slots.size(), s->d_cfirst.as<const uint64_t>(), s->keys.as<const uint64_t>(), s->n, s->counts_p(), s->err_p());
   }
-  PILEUP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, hipEventRecord(s->ev[1], st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "pileup launch failed: %s", hipGetErrorString(rc));
   s->added += n_reads;
@@ -154,29 +111,29 @@ int simmr_pileup_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
 
 int simmr_pileup_read(simmr_engine* e, uint32_t* counts_device, uint64_t capacity_sites) {
   if (!e) return SIMMR_EINVAL;
-  PileupState* s = state_of(e, false);
+  PileupState* s = pileup_state(e, false);
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_pileup_read called before simmr_pileup_reset");
   if (capacity_sites < s->n)
     return eng_fail(e, SIMMR_ERANGE, "capacity %llu < %llu sites", (unsigned long long)capacity_sites, (unsigned long long)s->n);
   if (s->n > 0 && !counts_device) return eng_fail(e, SIMMR_EINVAL, "simmr_pileup_read: NULL argument");
-  PILEUP_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   uint32_t errw = 0;
-  PILEUP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "pileup add")) return rc;
   if (errw)
     return eng_fail(e, SIMMR_EINVAL, "a read added since the last simmr_pileup_reset names a genome slot that is not tracked or a contig "
                                      "that does not exist, or its window leaves its contig or its bytes leave seq[]");
-  if (s->n > 0) PILEUP_TRY(e, hipMemcpyAsync(counts_device, s->counts_p(), s->table_bytes(), hipMemcpyDeviceToDevice, st));
+  if (s->n > 0) HIP_TRY(e, hipMemcpyAsync(counts_device, s->counts_p(), s->table_bytes(), hipMemcpyDeviceToDevice, st));
   return sync_check(e, "pileup read");
 }
 
 int simmr_last_pileup_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
-  PileupState* s = state_of(e, false);
+  PileupState* s = pileup_state(e, false);
   if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_pileup_add yet");
   if (int rc = sync_check(e, "pileup")) return rc;
-  PILEUP_TRY(e, hipEventElapsedTime(ms, s->ev[0], s->ev[1]));
+  HIP_TRY(e, hipEventElapsedTime(ms, s->ev[0], s->ev[1]));
   return SIMMR_OK;
 }
 

@@ -33,24 +33,10 @@ struct RecordStreamState {
   uint32_t paired = 0;
   uint64_t n_reads = 0, total = 0, epoch = 0;
   bool ready = false, planned_once = false, emitted = false;
-  hipEvent_t ev[4] = {};
+  Events<4> ev;
 
   uint32_t* err_p() const { return word.as<uint32_t>(); }
-  void release() {
-    nt.release();
-    for (DevBuf* b : {&len, &off, &chunk_sum, &chunk_prefix, &word, &key[0], &key[1], &idx[0], &idx[1], &hist, &digit_total, &end, &send})
-      b->release();
-    for (hipEvent_t& e : ev)
-      if (e) { (void)hipEventDestroy(e); e = nullptr; }
-  }
 };
-
-// the destroy hook of a state kept in an engine's slot
-inline void record_state_destroy(void* q) {
-  RecordStreamState* s = (RecordStreamState*)q;
-  s->release();
-  delete s;
-}
 
 struct RecordFormat {  // a format in read order, without limits of its own, on an engine
   static constexpr bool SORTED = false, WITH_END = false;
@@ -65,9 +51,9 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
   simmr_engine* e = F::engine(c);
   if (RecordStreamState* old = F::state(c, false)) old->ready = old->emitted = false;
   if (int rc = check_plan_args(e, names, reads, truth, n_reads, paired, total_bytes, F::PLAN)) return rc;
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   RecordStreamState* s = F::state(c, true);
-  if (int rc = sam_sync_check(e, F::SYNC_PLAN)) return rc;  // (an upload of an earlier plan that failed may still read the host copies)
+  if (int rc = sync_check(e, F::SYNC_PLAN)) return rc;  // (an upload of an earlier plan that failed may still read the host copies)
   // ---- the names: a row per contig of every entry, the RNAMEs back to back
   if (int rc = s->nt.build(e, names)) return rc;
   if (int rc = F::check_names(e, s->nt)) return rc;
@@ -77,8 +63,7 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
       return eng_fail(e, SIMMR_ERANGE, "%s: %llu named contigs, the longest of %llu bases: the key takes at most 2^24 contigs of fewer than 2^40 bases",
                       F::PLAN, (unsigned long long)s->nt.n_rows, (unsigned long long)s->nt.longest);
   [[maybe_unused]] const uint32_t key_bits = pos_bits + row_bits;
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) SAM_TRY(e, hipEventCreate(&ev));
+  if (int rc = s->ev.create_missing(e)) return rc;
   const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1) / SAM_CHUNK;
   [[maybe_unused]] const uint64_t n_tiles = (n_reads + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
   const uint64_t n1 = std::max<uint64_t>(n_reads, 1);
@@ -90,9 +75,9 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
            (!F::WITH_END || (s->end.ensure(n1 * 4) && s->send.ensure(n1 * 4)));
   if (!fits) return eng_fail(e, SIMMR_ENOMEM, "%s plan allocation failed (%llu reads)", F::NOUN, (unsigned long long)n_reads);
   hipStream_t st = eng_stream(e);
-  SAM_TRY(e, s->nt.upload(st, F::SORTED));
-  SAM_TRY(e, hipMemsetAsync(s->word.p, 0, 16, st));
-  SAM_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->nt.upload(st, F::SORTED));
+  HIP_TRY(e, hipMemsetAsync(s->word.p, 0, 16, st));
+  HIP_TRY(e, hipEventRecord(s->ev[0], st));
   const SamReads rd = sam_reads(reads);
   const SamEdits ed = sam_edits(truth);
   const uint32_t pr = paired ? 1u : 0u;
@@ -110,7 +95,7 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
       F::scan(st, *s, n_chunks);
       F::offsets(st, grid, *s, s->idx[cur ^ 1].as<const uint32_t>(), n_reads);
     } else {
-      SAM_TRY(e, hipMemsetAsync(s->off.p, 0, 8, st));
+      HIP_TRY(e, hipMemsetAsync(s->off.p, 0, 8, st));
     }
   } else {
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_chunks, (uint64_t)eng_cu_count(e) * SAM_WGS_PER_CU));
@@ -118,12 +103,12 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
     F::scan(st, *s, n_chunks);
     F::offsets(st, grid, *s, s->len.as<const uint32_t>(), n_reads);
   }
-  SAM_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, hipEventRecord(s->ev[1], st));
   uint64_t total = 0;
   uint32_t errw = 0;
-  SAM_TRY(e, hipMemcpyAsync(&total, s->off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, st));
-  SAM_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, F::SYNC_SIZE)) return rc;
+  HIP_TRY(e, hipMemcpyAsync(&total, s->off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_check(e, F::SYNC_SIZE)) return rc;
   s->planned_once = true;
   if (F::SORTED && (errw & 2u))
     return eng_fail(e, SIMMR_EINVAL, "a read's genome / contig has no name, or the read ends behind its contig's staged length");
@@ -161,23 +146,23 @@ int record_emit(Ctx* c, const simmr_reads_out* reads, const simmr_truth_out* tru
   if (dst_capacity < s->total)
     return eng_fail(e, SIMMR_ERANGE, "dst_capacity %llu < %llu bytes planned", (unsigned long long)dst_capacity, (unsigned long long)s->total);
   if (s->total > 0 && !dst) return eng_fail(e, SIMMR_EINVAL, "%s: NULL dst", F::EMIT);
-  SAM_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  SAM_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, hipEventRecord(s->ev[2], st));
   if (s->n_reads > 0) {
     const uint64_t n_batches = (s->n_reads + SAM_WG_READS - 1) / SAM_WG_READS;
     F::write(st, (uint32_t)std::min<uint64_t>(n_batches, (uint64_t)eng_cu_count(e) * SAM_WGS_PER_CU), *s, dst);
     if constexpr (F::SORTED) {
-      if (key_out) SAM_TRY(e, hipMemcpyAsync(key_out, s->ckey, s->n_reads * 8, hipMemcpyDeviceToDevice, st));
-      if (F::WITH_END && end_out) SAM_TRY(e, hipMemcpyAsync(end_out, s->send.p, s->n_reads * 4, hipMemcpyDeviceToDevice, st));
+      if (key_out) HIP_TRY(e, hipMemcpyAsync(key_out, s->ckey, s->n_reads * 8, hipMemcpyDeviceToDevice, st));
+      if (F::WITH_END && end_out) HIP_TRY(e, hipMemcpyAsync(end_out, s->send.p, s->n_reads * 4, hipMemcpyDeviceToDevice, st));
     }
   }
   if constexpr (F::SORTED)
-    if (off_out) SAM_TRY(e, hipMemcpyAsync(off_out, s->off.p, (s->n_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
-  SAM_TRY(e, hipEventRecord(s->ev[3], st));
+    if (off_out) HIP_TRY(e, hipMemcpyAsync(off_out, s->off.p, (s->n_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(e, hipEventRecord(s->ev[3], st));
   uint32_t errw = 0;
-  SAM_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
-  if (int rc = sam_sync_check(e, F::SYNC_WRITE)) return rc;
+  HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
+  if (int rc = sync_check(e, F::SYNC_WRITE)) return rc;
   s->emitted = true;
   if (errw) {
     s->ready = false;
@@ -193,10 +178,10 @@ int record_ms(Ctx* c, float* ms) {
   simmr_engine* e = F::engine(c);
   RecordStreamState* s = F::state(c, false);
   if (!s || !s->planned_once) return eng_fail(e, SIMMR_ESTATE, "no %s yet", F::PLAN);
-  if (int rc = sam_sync_check(e, F::TIMER)) return rc;
+  if (int rc = sync_check(e, F::TIMER)) return rc;
   float a = 0.f, b = 0.f;
-  SAM_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->emitted) SAM_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
+  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+  if (s->emitted) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
   *ms = a + b;
   return SIMMR_OK;
 }

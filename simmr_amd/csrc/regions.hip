@@ -1,32 +1,18 @@
 // regions.hip — the gold-standard assembly (include/simmr_hip.h: simmr_regions_*): the entry points over
 // regions_kernels.hip.  The fourth translation unit of libsimmr_hip.so; it sees an engine through engine_internal.hpp only,
-// the layout of depth[] through depth.hip's accessor, and keeps its state in the engine's opaque slot (freed by
-// simmr_engine_destroy through the hook given there).
+// the layout of depth[] through depth.hip's accessor, and keeps its state in the engine's opaque slot (host_support.hpp:
+// unit_state; simmr_engine_destroy deletes it, and its members free what they own).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "regions_kernels.hip"
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 using namespace simmr;
 
 namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;  // bytes
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    cap = bytes;
-    return true;
-  }
-  template <class T> T* as() const { return (T*)p; }
-};
 
 struct RegionsState {
   // the plan in force: made for which layout of depth[] (staging epoch and reset), with which thresholds
@@ -39,36 +25,10 @@ struct RegionsState {
   DevBuf run_start, run_end;  // sized from the counted runs
   DevBuf r_x, r_c, r_off;     // the region table, sized from the counted regions
   DevBuf table;               // RegionContig per tracked contig
-  hipEvent_t ev[4] = {};      // plan, emit: begin / end
+  Events<4> ev;               // plan, emit: begin / end
 };
 
-void regions_destroy(void* q) {
-  RegionsState* s = (RegionsState*)q;
-  for (DevBuf* b : {&s->tile_count, &s->tile_prefix, &s->run_count, &s->run_prefix, &s->run_start, &s->run_end, &s->r_x, &s->r_c, &s->r_off, &s->table})
-    if (b->p) (void)hipFree(b->p);
-  for (hipEvent_t ev : s->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete s;
-}
-
-RegionsState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_REGIONS, regions_destroy);
-  if (!*slot && create) *slot = new RegionsState();
-  return (RegionsState*)*slot;
-}
-
-#define REGIONS_TRY(e, call)                                                                \
-  do {                                                                                      \
-    hipError_t _s = (call);                                                                 \
-    if (_s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); \
-  } while (0)
-
-int sync_check(simmr_engine* e, const char* what) {
-  hipError_t s = hipStreamSynchronize(eng_stream(e));
-  if (s == hipSuccess) s = hipGetLastError();
-  if (s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  return SIMMR_OK;
-}
+constexpr auto regions_state = unit_state<RegionsState, ENG_EXT_REGIONS>;
 
 uint64_t pad_tops(uint64_t n) { return std::max<uint64_t>((n + REGIONS_TOPS_WIDTH - 1) / REGIONS_TOPS_WIDTH, 1) * REGIONS_TOPS_WIDTH; }
 
@@ -88,16 +48,15 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
                        uint64_t* n_bases) {
   if (!e) return SIMMR_EINVAL;
   if (!n_regions || !n_bases) return eng_fail(e, SIMMR_EINVAL, "simmr_regions_plan: NULL argument");
-  RegionsState* s = state_of(e, true);
+  RegionsState* s = regions_state(e, true);
   s->planned = false;
   DepthLayout L{};
   if (int rc = layout_of(e, "simmr_regions_plan", &L)) return rc;
   if (min_depth == 0 || min_len == 0) return eng_fail(e, SIMMR_EINVAL, "simmr_regions_plan: min_depth and min_len are at least 1");
   if (L.n_positions > 0 && (!depth_device || ((uintptr_t)depth_device & 15u)))
     return eng_fail(e, SIMMR_EINVAL, "simmr_regions_plan: depth_device must be a 16-byte aligned device pointer");
-  REGIONS_TRY(e, hipSetDevice(eng_device(e)));
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) REGIONS_TRY(e, hipEventCreate(&ev));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  if (int rc = s->ev.create_missing(e)) return rc;
   hipStream_t st = eng_stream(e);
   const uint64_t n = L.n_positions, n_contigs = L.n_contigs;
   // the tracked contigs as the kernels see them (the slots are staged: the reset tracked them and nothing was staged since)
@@ -115,17 +74,17 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
   const uint64_t tops = pad_tops(n_tiles);
   if (!s->table.ensure(table.size() * sizeof(RegionContig)) || !s->tile_count.ensure(2 * tops * 8) || !s->tile_prefix.ensure(2 * (tops + 1) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "region tile allocation failed (%llu tiles)", (unsigned long long)n_tiles);
-  REGIONS_TRY(e, hipMemcpyAsync(s->table.p, table.data(), table.size() * sizeof(RegionContig), hipMemcpyHostToDevice, st));
-  REGIONS_TRY(e, hipMemsetAsync(s->tile_count.p, 0, 2 * tops * 8, st));
-  REGIONS_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, hipMemcpyAsync(s->table.p, table.data(), table.size() * sizeof(RegionContig), hipMemcpyHostToDevice, st));
+  HIP_TRY(e, hipMemsetAsync(s->tile_count.p, 0, 2 * tops * 8, st));
+  HIP_TRY(e, hipEventRecord(s->ev[0], st));
   if (n > 0)
     hipLaunchKernelGGL(k_regions_count, dim3((uint32_t)n_tiles), dim3(REGIONS_WG), 0, st, depth_device, n, min_depth, L.cfirst_device,
                        (uint32_t)n_contigs, s->tile_count.as<uint64_t>(), tops);
   hipLaunchKernelGGL(k_regions_scan, dim3(2), dim3(REGIONS_WG), 0, st, s->tile_count.as<const uint64_t>(), s->tile_prefix.as<uint64_t>(),
                      n_tiles, tops);
   uint64_t totals[2] = {0, 0};  // starts, ends: equal
-  REGIONS_TRY(e, hipMemcpyAsync(&totals[0], s->tile_prefix.as<uint64_t>() + tops, 8, hipMemcpyDeviceToHost, st));
-  REGIONS_TRY(e, hipMemcpyAsync(&totals[1], s->tile_prefix.as<uint64_t>() + 2 * tops + 1, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&totals[0], s->tile_prefix.as<uint64_t>() + tops, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&totals[1], s->tile_prefix.as<uint64_t>() + 2 * tops + 1, 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "region count")) return rc;  // (the table was copied from a vector that goes with this call)
   if (totals[0] != totals[1]) return eng_fail(e, SIMMR_ENODEV, "simmr_regions_plan: run starts and ends differ in number");
   const uint64_t n_runs = totals[0];
@@ -135,7 +94,7 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
   if (!s->run_start.ensure(std::max<uint64_t>(n_runs, 1) * 8) || !s->run_end.ensure(std::max<uint64_t>(n_runs, 1) * 8) ||
       !s->run_count.ensure(2 * rtops * 8) || !s->run_prefix.ensure(2 * (rtops + 1) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "run buffer allocation failed (%llu runs)", (unsigned long long)n_runs);
-  REGIONS_TRY(e, hipMemsetAsync(s->run_count.p, 0, 2 * rtops * 8, st));
+  HIP_TRY(e, hipMemsetAsync(s->run_count.p, 0, 2 * rtops * 8, st));
   if (n_runs > 0) {
     hipLaunchKernelGGL(k_regions_runs, dim3((uint32_t)n_tiles), dim3(REGIONS_WG), 0, st, depth_device, n, min_depth, L.cfirst_device,
                        (uint32_t)n_contigs, s->tile_prefix.as<const uint64_t>(), tops, n_runs, s->run_start.as<uint64_t>(),
@@ -145,8 +104,8 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
   }
   hipLaunchKernelGGL(k_regions_scan, dim3(2), dim3(REGIONS_WG), 0, st, s->run_count.as<const uint64_t>(), s->run_prefix.as<uint64_t>(),
                      run_tiles, rtops);
-  REGIONS_TRY(e, hipMemcpyAsync(&totals[0], s->run_prefix.as<uint64_t>() + rtops, 8, hipMemcpyDeviceToHost, st));
-  REGIONS_TRY(e, hipMemcpyAsync(&totals[1], s->run_prefix.as<uint64_t>() + 2 * rtops + 1, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&totals[0], s->run_prefix.as<uint64_t>() + rtops, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&totals[1], s->run_prefix.as<uint64_t>() + 2 * rtops + 1, 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "region scan")) return rc;
   const uint64_t nr = totals[0], nb = totals[1];
   // the region table, from the counted regions
@@ -157,8 +116,8 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
                        s->run_end.as<const uint64_t>(), n_runs, min_len, s->run_prefix.as<const uint64_t>(), rtops, L.cfirst_device,
                        (uint32_t)n_contigs, nr, nb, s->r_x.as<uint64_t>(), s->r_c.as<uint32_t>(), s->r_off.as<uint64_t>());
   else
-    REGIONS_TRY(e, hipMemsetAsync(s->r_off.p, 0, 8, st));
-  REGIONS_TRY(e, hipEventRecord(s->ev[1], st));
+    HIP_TRY(e, hipMemsetAsync(s->r_off.p, 0, 8, st));
+  HIP_TRY(e, hipEventRecord(s->ev[1], st));
   if (int rc = sync_check(e, "region table")) return rc;
   s->epoch = L.epoch;
   s->resets = L.resets;
@@ -177,7 +136,7 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
 int simmr_regions_emit(simmr_engine* e, const uint32_t* depth_device, const simmr_regions_out* out) {
   if (!e) return SIMMR_EINVAL;
   if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_regions_emit: NULL argument");
-  RegionsState* s = state_of(e, false);
+  RegionsState* s = regions_state(e, false);
   DepthLayout L{};
   if (!s || !s->planned || !depth_layout(e, &L) || L.epoch != eng_staging_epoch(e) || s->epoch != L.epoch || s->resets != L.resets) {
     if (s) s->planned = false;
@@ -194,10 +153,10 @@ int simmr_regions_emit(simmr_engine* e, const uint32_t* depth_device, const simm
   const uint64_t chunks = (s->n_bases + REGIONS_CHUNK - 1) / REGIONS_CHUNK, grid = (chunks + REGIONS_WG - 1) / REGIONS_WG;
   if (grid >= (1ull << 31) || s->n_regions / REGIONS_WG + 1 >= (1ull << 31))
     return eng_fail(e, SIMMR_ENOTSUP, "simmr_regions_emit: too many bases for one launch");
-  REGIONS_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  if (out->depth_sum && s->n_regions > 0) REGIONS_TRY(e, hipMemsetAsync(out->depth_sum, 0, s->n_regions * 8, st));
-  REGIONS_TRY(e, hipEventRecord(s->ev[2], st));
+  if (out->depth_sum && s->n_regions > 0) HIP_TRY(e, hipMemsetAsync(out->depth_sum, 0, s->n_regions * 8, st));
+  HIP_TRY(e, hipEventRecord(s->ev[2], st));
   if (out->genome || out->contig || out->start || out->len || out->seq_off)
     hipLaunchKernelGGL(k_regions_columns, dim3((uint32_t)(s->n_regions / REGIONS_WG + 1)), dim3(REGIONS_WG), 0, st, s->r_x.as<const uint64_t>(),
                        s->r_c.as<const uint32_t>(), s->r_off.as<const uint64_t>(), s->table.as<const RegionContig>(), s->n_regions,
@@ -206,19 +165,19 @@ int simmr_regions_emit(simmr_engine* e, const uint32_t* depth_device, const simm
     hipLaunchKernelGGL(k_regions_bases, dim3((uint32_t)grid), dim3(REGIONS_WG), 0, st, depth_device, s->r_x.as<const uint64_t>(),
                        s->r_c.as<const uint32_t>(), s->r_off.as<const uint64_t>(), s->table.as<const RegionContig>(), s->n_regions, s->n_bases,
                        out->seq, (unsigned long long*)out->depth_sum);
-  REGIONS_TRY(e, hipEventRecord(s->ev[3], st));
+  HIP_TRY(e, hipEventRecord(s->ev[3], st));
   s->emitted = true;
   return sync_check(e, "region emit");
 }
 
 int simmr_last_regions_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
-  RegionsState* s = state_of(e, false);
+  RegionsState* s = regions_state(e, false);
   if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_regions_plan yet");
   if (int rc = sync_check(e, "regions")) return rc;
   float a = 0.f, b = 0.f;
-  REGIONS_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->emitted) REGIONS_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
+  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+  if (s->emitted) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
   *ms = a + b;
   return SIMMR_OK;
 }

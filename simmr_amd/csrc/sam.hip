@@ -1,7 +1,7 @@
 // sam.hip — the true alignments as SAM text (include/simmr_hip.h: simmr_sam_*): the entry points over sam_kernels.hip.
 // The sixth translation unit of libsimmr_hip.so; it sees an engine through engine_internal.hpp only — the device, the
 // stream, which slots are staged and the staging epoch: the pass reads the caller's columns, never the genome planes —
-// and keeps its state in the engine's opaque slot (freed by simmr_engine_destroy through the hook given there).  The plan, the
+// and keeps its state in the engine's opaque slot (host_support.hpp: unit_state).  The plan, the
 // emit and the timer are record_plan / record_emit / record_ms of record_stream_host.hpp, shared with sam_sort.hip, bam.hip and
 // bam_index.hip: this unit gives them its state, its words and the launches of its four kernels.
 #include <hip/hip_runtime.h>
@@ -17,19 +17,13 @@ using namespace simmr;
 
 namespace {
 
-RecordStreamState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_SAM, record_state_destroy);
-  if (!*slot && create) *slot = new RecordStreamState();
-  return (RecordStreamState*)*slot;
-}
-
 struct SamFormat : RecordFormat {
   static constexpr const char *PLAN = "simmr_sam_plan", *EMIT = "simmr_sam_emit", *NOUN = "SAM", *TIMER = "sam";
   static constexpr const char *SYNC_PLAN = "SAM plan", *SYNC_SIZE = "SAM size pass", *SYNC_WRITE = "SAM write pass";
   static constexpr const char* PLAN_REFUSAL =
       "a read's genome / contig has no name, its bytes leave seq[], it is longer than %u bases, its edit_off decreases or leaves edits_capacity, or its "
       "edit_pos do not ascend inside the read";
-  static RecordStreamState* state(simmr_engine* e, bool create) { return state_of(e, create); }
+  static RecordStreamState* state(simmr_engine* e, bool create) { return unit_state<RecordStreamState, ENG_EXT_SAM>(e, create); }
   static void size(hipStream_t st, uint32_t grid, RecordStreamState& s, const SamReads& rd, const SamEdits& ed, uint64_t n, uint32_t paired, uint32_t) {
     hipLaunchKernelGGL(k_sam_size, dim3(grid), dim3(256), 0, st, rd, ed, s.nt.names(), n, paired, s.len.as<uint32_t>(), s.chunk_sum.as<uint64_t>(), s.err_p());
   }

@@ -1,4 +1,4 @@
-// sam_names.hpp — what the units over the read columns share on the host: a growing device buffer, and the names of a plan —
+// sam_names.hpp — what the units over the read columns share on the host beyond host_support.hpp: the names of a plan —
 // per engine genome slot its rows, per row its RNAME in a blob (SamNames, sam_kernels.hip) and, for the sorted form's bound
 // check, the row's staged length.  record_stream_host.hpp builds the record writers' plan and emit on it.  Internal to the
 // library; each unit that includes it gets its own copy of the routines.
@@ -9,25 +9,10 @@
 #include <cstring>
 #include <vector>
 
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 namespace simmr {
 namespace {
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;  // bytes
-  bool ensure(size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
-    cap = bytes;
-    return true;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-  template <class T> T* as() const { return (T*)p; }
-};
 
 // SAM's RNAME: [0-9A-Za-z!#$%&+./:;?@^_|~-][0-9A-Za-z!#$%&*+./:;=?@^_|~-]*
 inline bool rname_legal(const char* s, size_t n) {
@@ -54,12 +39,10 @@ struct SamNameTable {
     return SamNames{blob.as<const uint8_t>(), g_cbase.as<const uint32_t>(), g_ncontig.as<const uint32_t>(), c_off.as<const uint32_t>(),
                     c_len.as<const uint32_t>(), n_slots};
   }
-  void release() {
-    for (DevBuf* b : {&blob, &g_cbase, &g_ncontig, &c_off, &c_len, &c_bases}) b->release();
-  }
   // A row per contig of every entry, the RNAMEs back to back, into the host copies.  The caller has synchronised the stream.
   int build(simmr_engine* e, const simmr_sam_names* names) {
-    n_slots = eng_genome_slots(e);
+    const StagedRows staged = staged_rows(e);
+    n_slots = staged.n_slots();
     h_cbase.assign(std::max(n_slots, 1u), 0u);
     h_ncontig.assign(std::max(n_slots, 1u), 0u);
     h_off.clear(); h_len.clear(); h_blob.clear(); h_bases.clear();
@@ -67,7 +50,7 @@ struct SamNameTable {
     size_t flat = 0;
     for (uint32_t i = 0; i < names->n_genomes; i++) {
       const uint32_t g = names->genome_idx[i], nc = names->n_contigs[i];
-      if (g >= n_slots || eng_contig_count(e, g) == 0 || eng_contig_count(e, g) != nc)
+      if (g >= n_slots || staged.ncontig[g] == 0 || staged.ncontig[g] != nc)
         return eng_fail(e, SIMMR_EINVAL, "names entry %u: genome slot %u is not staged, or it does not have %u contigs", i, g, nc);
       h_cbase[g] = (uint32_t)h_off.size();
       h_ncontig[g] = nc;
@@ -79,7 +62,7 @@ struct SamNameTable {
         if (!rname_legal(s, n)) return eng_fail(e, SIMMR_ENOTSUP, "RNAME '%s' (contig %u of names entry %u) is not a SAM reference name", s, c, i);
         h_off.push_back((uint32_t)h_blob.size());
         h_len.push_back((uint32_t)n);
-        h_bases.push_back(eng_contig_len(e, g, c));
+        h_bases.push_back(staged.bases[staged.cbase[g] + c]);
         longest = std::max(longest, h_bases.back());
         h_blob.insert(h_blob.end(), s, s + n);
       }
@@ -103,19 +86,6 @@ struct SamNameTable {
     return s;
   }
 };
-
-#define SAM_TRY(e, call)                                                                    \
-  do {                                                                                      \
-    hipError_t _s = (call);                                                                 \
-    if (_s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); \
-  } while (0)
-
-inline int sam_sync_check(simmr_engine* e, const char* what) {
-  hipError_t s = hipStreamSynchronize(eng_stream(e));
-  if (s == hipSuccess) s = hipGetLastError();
-  if (s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  return SIMMR_OK;
-}
 
 // field by field into zeroed memory: the emit calls compare these structs with the plan's as bytes
 inline void assign_reads(SamReads* o, const simmr_reads_out* r) {

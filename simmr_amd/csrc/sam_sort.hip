@@ -17,12 +17,6 @@ using namespace simmr;
 
 namespace {
 
-RecordStreamState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_SAM_SORT, record_state_destroy);
-  if (!*slot && create) *slot = new RecordStreamState();
-  return (RecordStreamState*)*slot;
-}
-
 struct SamSortFormat : RecordFormat {
   static constexpr bool SORTED = true;
   static constexpr const char *PLAN = "simmr_sam_sort_plan", *EMIT = "simmr_sam_sort_emit", *NOUN = "sorted SAM", *TIMER = "sorted sam";
@@ -30,7 +24,7 @@ struct SamSortFormat : RecordFormat {
   static constexpr const char* PLAN_REFUSAL =
       "a read's bytes leave seq[], it is longer than %u bases, its edit_off decreases or leaves edits_capacity, or its edit_pos do not ascend inside "
       "the read";
-  static RecordStreamState* state(simmr_engine* e, bool create) { return state_of(e, create); }
+  static RecordStreamState* state(simmr_engine* e, bool create) { return unit_state<RecordStreamState, ENG_EXT_SAM_SORT>(e, create); }
   static void size(hipStream_t st, uint32_t grid, RecordStreamState& s, const SamReads& rd, const SamEdits& ed, uint64_t n, uint32_t paired, uint32_t pos_bits) {
     hipLaunchKernelGGL(k_samsort_size, dim3(grid), dim3(256), 0, st, rd, ed, s.nt.names(), s.nt.c_bases.as<const uint64_t>(), n, paired, pos_bits,
                        s.len.as<uint32_t>(), s.key[0].as<uint64_t>(), s.err_p());

@@ -1,12 +1,12 @@
 // strain.hip — strain divergence (include/simmr_hip.h: simmr_strain_*): the entry points over strain_kernels.hip.  The third
 // translation unit of libsimmr_hip.so; it sees an engine through engine_internal.hpp only and keeps its state in the
-// engine's opaque slot (freed by simmr_engine_destroy through the hook given there).
+// engine's opaque slot (host_support.hpp: unit_state; simmr_engine_destroy deletes it, and its members free what they own).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "strain_kernels.hip"
-#include "engine_internal.hpp"
+#include "host_support.hpp"
 
 using namespace simmr;
 
@@ -18,47 +18,11 @@ struct StrainState {
   uint32_t genome = 0;
   uint64_t epoch = 0, n_sites = 0, n_tiles = 0;
   StrainDraw draw{};
-  void *tile_count = nullptr, *tile_prefix = nullptr;  // u32 per tile; u64 per tile and the total, both padded to whole scan iterations
-  size_t count_cap = 0, prefix_cap = 0;                // bytes
-  hipEvent_t ev[4] = {};                               // plan, apply: begin / end
+  DevBuf tile_count, tile_prefix;  // u32 per tile; u64 per tile and the total, both padded to whole scan iterations
+  Events<4> ev;                    // plan, apply: begin / end
 };
 
-bool ensure(void** p, size_t* cap, size_t bytes) {
-  if (bytes <= *cap) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr; *cap = 0;
-  if (hipMalloc(p, bytes) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-  *cap = bytes;
-  return true;
-}
-
-void strain_destroy(void* q) {
-  StrainState* s = (StrainState*)q;
-  for (void* p : {s->tile_count, s->tile_prefix})
-    if (p) (void)hipFree(p);
-  for (hipEvent_t ev : s->ev)
-    if (ev) (void)hipEventDestroy(ev);
-  delete s;
-}
-
-StrainState* state_of(simmr_engine* e, bool create) {
-  void** slot = eng_ext_slot(e, ENG_EXT_STRAIN, strain_destroy);
-  if (!*slot && create) *slot = new StrainState();
-  return (StrainState*)*slot;
-}
-
-#define STRAIN_TRY(e, call)                                                                 \
-  do {                                                                                      \
-    hipError_t _s = (call);                                                                 \
-    if (_s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s failed: %s", #call, hipGetErrorString(_s)); \
-  } while (0)
-
-int sync_check(simmr_engine* e, const char* what) {
-  hipError_t s = hipStreamSynchronize(eng_stream(e));
-  if (s == hipSuccess) s = hipGetLastError();
-  if (s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
-  return SIMMR_OK;
-}
+constexpr auto strain_state = unit_state<StrainState, ENG_EXT_STRAIN>;
 
 // what the kernels take of a staged slot
 struct Planes {
@@ -90,11 +54,10 @@ int simmr_strain_plan(simmr_engine* e, uint32_t genome_idx, double identity, uin
   for (uint32_t c = 0; c < n_contigs; c++)
     if (eng_contig_len(e, genome_idx, c) >= (1ull << 34))
       return eng_fail(e, SIMMR_ENOTSUP, "contig %u has 2^34 bases or more: its positions do not fit the draws' counter", c);
-  STRAIN_TRY(e, hipSetDevice(eng_device(e)));
-  StrainState* s = state_of(e, true);
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
+  StrainState* s = strain_state(e, true);
   s->planned = false;
-  for (hipEvent_t& ev : s->ev)
-    if (!ev) STRAIN_TRY(e, hipEventCreate(&ev));
+  if (int rc = s->ev.create_missing(e)) return rc;
   // strain sites, version 1: the thresholds in integer arithmetic
   const uint64_t t32 = (uint64_t)((1.0 - identity) * 4294967296.0 + 0.5);  // at most 3 * 2^30
   s->draw = StrainDraw{(uint32_t)t32, (uint32_t)((t32 + 2) / 3), (uint32_t)((2 * t32 + 2) / 3), (uint32_t)seed, (uint32_t)(seed >> 32)};
@@ -102,19 +65,19 @@ int simmr_strain_plan(simmr_engine* e, uint32_t genome_idx, double identity, uin
   s->n_tiles = (p.plane_words + STRAIN_WG - 1) / STRAIN_WG;
   if (s->n_tiles >= (1ull << 31)) return eng_fail(e, SIMMR_ENOTSUP, "simmr_strain_plan: too many tiles for one launch");
   const uint64_t tops = (s->n_tiles + STRAIN_TOPS_WIDTH - 1) / STRAIN_TOPS_WIDTH * STRAIN_TOPS_WIDTH;
-  if (!ensure(&s->tile_count, &s->count_cap, std::max<uint64_t>(tops, 1) * 4) || !ensure(&s->tile_prefix, &s->prefix_cap, (tops + 1) * 8))
+  if (!s->tile_count.ensure(std::max<uint64_t>(tops, 1) * 4) || !s->tile_prefix.ensure((tops + 1) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "strain tile allocation failed (%llu tiles)", (unsigned long long)s->n_tiles);
   hipStream_t st = eng_stream(e);
-  STRAIN_TRY(e, hipMemsetAsync(s->tile_count, 0, std::max<uint64_t>(tops, 1) * 4, st));
-  STRAIN_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, hipMemsetAsync(s->tile_count.p, 0, std::max<uint64_t>(tops, 1) * 4, st));
+  HIP_TRY(e, hipEventRecord(s->ev[0], st));
   if (s->n_tiles > 0)
     hipLaunchKernelGGL(k_strain_count, dim3((uint32_t)s->n_tiles), dim3(STRAIN_WG), 0, st, p.mask, p.contigs, p.n_contigs, p.plane_words,
-                       s->draw, (uint32_t*)s->tile_count);
-  hipLaunchKernelGGL(k_strain_scan_tiles, dim3(1), dim3(STRAIN_WG), 0, st, (const uint32_t*)s->tile_count, (uint64_t*)s->tile_prefix,
+                       s->draw, s->tile_count.as<uint32_t>());
+  hipLaunchKernelGGL(k_strain_scan_tiles, dim3(1), dim3(STRAIN_WG), 0, st, s->tile_count.as<const uint32_t>(), s->tile_prefix.as<uint64_t>(),
                      s->n_tiles);
-  STRAIN_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, hipEventRecord(s->ev[1], st));
   uint64_t total = 0;
-  STRAIN_TRY(e, hipMemcpyAsync(&total, (const uint64_t*)s->tile_prefix + tops, 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(&total, (const uint64_t*)s->tile_prefix.p + tops, 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "strain count")) return rc;
   s->genome = genome_idx;
   s->epoch = eng_staging_epoch(e);
@@ -127,7 +90,7 @@ int simmr_strain_plan(simmr_engine* e, uint32_t genome_idx, double identity, uin
 int simmr_strain_apply(simmr_engine* e, uint32_t genome_idx, const simmr_strain_out* out) {
   if (!e) return SIMMR_EINVAL;
   if (eng_contig_count(e, genome_idx) == 0) return eng_fail(e, SIMMR_EINVAL, "genome %u is not staged", genome_idx);
-  StrainState* s = state_of(e, false);
+  StrainState* s = strain_state(e, false);
   if (!s || !s->planned || s->genome != genome_idx)
     return eng_fail(e, SIMMR_ESTATE, "simmr_strain_apply called without a simmr_strain_plan for genome %u", genome_idx);
   if (s->epoch != eng_staging_epoch(e)) {
@@ -137,16 +100,16 @@ int simmr_strain_apply(simmr_engine* e, uint32_t genome_idx, const simmr_strain_
   const bool columns = out && (out->contig || out->pos || out->ref || out->alt);
   if (columns && out->capacity < s->n_sites)
     return eng_fail(e, SIMMR_ERANGE, "capacity %llu < %llu sites", (unsigned long long)out->capacity, (unsigned long long)s->n_sites);
-  STRAIN_TRY(e, hipSetDevice(eng_device(e)));
+  HIP_TRY(e, hipSetDevice(eng_device(e)));
   const Planes p = planes_of(e, genome_idx);
   hipStream_t st = eng_stream(e);
   s->planned = false;  // consumed: the planes are about to change
-  STRAIN_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, hipEventRecord(s->ev[2], st));
   if (s->n_sites > 0)
     hipLaunchKernelGGL(k_strain_apply, dim3((uint32_t)s->n_tiles), dim3(STRAIN_WG), 0, st, p.packed, p.mask, p.contigs, p.n_contigs,
-                       p.plane_words, s->draw, (const uint64_t*)s->tile_prefix, columns ? out->contig : nullptr,
+                       p.plane_words, s->draw, s->tile_prefix.as<const uint64_t>(), columns ? out->contig : nullptr,
                        columns ? out->pos : nullptr, columns ? out->ref : nullptr, columns ? out->alt : nullptr);
-  STRAIN_TRY(e, hipEventRecord(s->ev[3], st));
+  HIP_TRY(e, hipEventRecord(s->ev[3], st));
   eng_planes_rewritten(e);
   s->applied = true;
   return sync_check(e, "strain apply");
@@ -154,12 +117,12 @@ int simmr_strain_apply(simmr_engine* e, uint32_t genome_idx, const simmr_strain_
 
 int simmr_last_strain_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
-  StrainState* s = state_of(e, false);
+  StrainState* s = strain_state(e, false);
   if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_strain_plan yet");
   if (int rc = sync_check(e, "strain")) return rc;
   float a = 0.f, b = 0.f;
-  STRAIN_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->applied) STRAIN_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
+  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
+  if (s->applied) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
   *ms = a + b;
   return SIMMR_OK;
 }

@@ -1,0 +1,263 @@
+// host_support_main.cpp — simmr_amd/csrc/host_support.hpp on a machine without a GPU: the HIP entry points and the engine
+// accessors the header uses are counting stubs over malloc and free, with a switch that makes the next allocation (or event)
+// fail.  Links no HIP library.  The exit status is the number of device allocations and events still alive at the end (0: every
+// owner freed what it owned), or 101 when a check failed (the failed checks go to stderr).
+//   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I<rocm>/include -fsanitize=address,undefined tests/host_support_main.cpp
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../simmr_amd/csrc/host_support.hpp"
+
+// ---- the stubs -------------------------------------------------------------------------------------------------------
+static long g_live_bufs = 0, g_live_events = 0, g_mallocs = 0, g_frees = 0, g_event_creates = 0, g_syncs = 0;
+static bool g_fail_next_malloc = false, g_fail_next_event = false;
+static hipError_t g_pending = hipSuccess;  // the sticky error hipGetLastError reads and clears
+static size_t g_last_malloc_bytes = 0;
+
+extern "C" {
+hipError_t hipMalloc(void** ptr, size_t size) {
+  if (g_fail_next_malloc) {
+    g_fail_next_malloc = false;
+    *ptr = (void*)0x1;  // (a failed call may leave anything behind)
+    return g_pending = hipErrorOutOfMemory;
+  }
+  *ptr = malloc(size ? size : 1);
+  g_last_malloc_bytes = size;
+  g_mallocs++;
+  g_live_bufs++;
+  return hipSuccess;
+}
+hipError_t hipFree(void* ptr) {
+  if (ptr) { free(ptr); g_frees++; g_live_bufs--; }
+  return hipSuccess;
+}
+hipError_t hipGetLastError(void) {
+  const hipError_t s = g_pending;
+  g_pending = hipSuccess;
+  return s;
+}
+hipError_t hipEventCreate(hipEvent_t* event) {
+  if (g_fail_next_event) { g_fail_next_event = false; return g_pending = hipErrorOutOfMemory; }
+  *event = (hipEvent_t)malloc(1);
+  g_event_creates++;
+  g_live_events++;
+  return hipSuccess;
+}
+hipError_t hipEventDestroy(hipEvent_t event) {
+  free((void*)event);
+  g_live_events--;
+  return hipSuccess;
+}
+hipError_t hipStreamSynchronize(hipStream_t) { g_syncs++; return hipSuccess; }
+const char* hipGetErrorString(hipError_t s) { return s == hipSuccess ? "no error" : "stub error"; }
+}
+
+struct simmr_engine {
+  void* slot[simmr::ENG_EXT_COUNT] = {};
+  void (*destroy[simmr::ENG_EXT_COUNT])(void*) = {};
+  std::vector<std::vector<uint64_t>> genomes;  // per slot the lengths of its contigs (none: not staged)
+  std::string err;
+};
+
+namespace simmr {
+hipStream_t eng_stream(const simmr_engine*) { return nullptr; }
+uint32_t eng_genome_slots(const simmr_engine* e) { return (uint32_t)e->genomes.size(); }
+uint32_t eng_contig_count(const simmr_engine* e, uint32_t slot) { return slot < e->genomes.size() ? (uint32_t)e->genomes[slot].size() : 0u; }
+uint64_t eng_contig_len(const simmr_engine* e, uint32_t slot, uint32_t contig) { return e->genomes[slot][contig]; }
+int eng_fail(simmr_engine* e, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  e->err = buf;
+  return code;
+}
+void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*)) {
+  e->destroy[which] = destroy;
+  return &e->slot[which];
+}
+}  // namespace simmr
+
+using namespace simmr;
+
+static int g_failed = 0;
+#define CHECK(cond)                                                             \
+  do {                                                                          \
+    if (!(cond)) { fprintf(stderr, "line %d: %s\n", __LINE__, #cond); g_failed++; } \
+  } while (0)
+
+static long live() { return g_live_bufs + g_live_events; }
+
+// ---- the checks ------------------------------------------------------------------------------------------------------
+static void ensure_keeps_grows_and_fails() {
+  DevBuf b;
+  CHECK(b.p == nullptr && b.cap == 0);
+  CHECK(b.ensure(100) && b.p && b.cap == 100 && g_mallocs == 1);
+  void* const first = b.p;
+  CHECK(b.ensure(50) && b.ensure(100) && b.p == first && b.cap == 100 && g_mallocs == 1 && g_frees == 0);  // large enough: kept
+  CHECK(b.ensure(101) && b.cap == 101 && g_mallocs == 2 && g_frees == 1 && g_live_bufs == 1);              // grows: freed, allocated anew
+  CHECK(b.as<char>() == (char*)b.p);
+  g_fail_next_malloc = true;
+  CHECK(!b.ensure(400));
+  CHECK(b.p == nullptr && b.cap == 0 && g_live_bufs == 0);
+  CHECK(g_pending == hipSuccess);  // no error left for the next sync_check to report
+  CHECK(b.ensure(8) && b.cap == 8);
+  b.release();
+  CHECK(b.p == nullptr && b.cap == 0 && g_live_bufs == 0);
+  b.release();  // (twice is once)
+  CHECK(g_live_bufs == 0);
+}
+
+static void growth_rules() {
+  DevBuf b;
+  CHECK(b.ensure_slack(0) && b.ensure(0) && b.p == nullptr && b.cap == 0);  // nothing asked, nothing allocated
+  for (size_t bytes : {(size_t)1, (size_t)7, (size_t)1000, (size_t)65537}) {
+    b.release();
+    CHECK(b.ensure_slack(bytes) && b.cap == bytes + bytes / 8 + 256 && g_last_malloc_bytes == b.cap);
+  }
+  const long mallocs = g_mallocs;
+  CHECK(b.ensure_slack(65537 + 65537 / 8 + 256) && g_mallocs == mallocs);  // the slack is room: kept
+  CHECK(b.ensure_slack(65537 + 65537 / 8 + 257) && g_mallocs == mallocs + 1);
+  DevBuf c;
+  CHECK(c.ensure(100, 125) && c.cap == 125 && g_last_malloc_bytes == 125);  // a caller's own rule
+  CHECK(c.ensure(125, 999) && c.cap == 125);
+  DevBuf d;
+  CHECK(d.ensure(64) && d.cap == 64 && g_last_malloc_bytes == 64);  // exactly what is asked
+}
+
+static void one_owner() {
+  DevBuf a;
+  CHECK(a.ensure(32));
+  void* const pa = a.p;
+  DevBuf b(std::move(a));
+  CHECK(a.p == nullptr && a.cap == 0 && b.p == pa && b.cap == 32 && g_live_bufs == 1);
+  DevBuf c;
+  CHECK(c.ensure(16));
+  void* const pc = c.p;
+  CHECK(g_live_bufs == 2);
+  c = std::move(b);  // what c held is freed
+  CHECK(b.p == nullptr && b.cap == 0 && c.p == pa && c.cap == 32 && g_live_bufs == 1);
+  (void)pc;
+  DevBuf& self = c;
+  c = std::move(self);
+  CHECK(c.p == pa && c.cap == 32 && g_live_bufs == 1);
+  DevBuf d;
+  CHECK(d.ensure(48));
+  void* const pd = d.p;
+  std::swap(c, d);
+  CHECK(c.p == pd && c.cap == 48 && d.p == pa && d.cap == 32 && g_live_bufs == 2);
+  static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "a DevBuf does not copy");
+  static_assert(std::is_nothrow_move_constructible<DevBuf>::value && std::is_nothrow_move_assignable<DevBuf>::value, "and moves without throwing");
+}
+
+struct Holder {  // as the engine's GenomeHost: buffers inside a vector's element
+  int tag = 0;
+  DevBuf x, y;
+};
+
+static void vector_of_holders() {
+  const long before = g_live_bufs;
+  {
+    std::vector<Holder> v(2);
+    for (int i = 0; i < 2; i++) { v[i].tag = i; CHECK(v[i].x.ensure(10 + i) && v[i].y.ensure(20 + i)); }
+    void* const x1 = v[1].x.p;
+    v.resize(40);  // reallocates: the elements move
+    CHECK(g_live_bufs == before + 4 && v[1].x.p == x1 && v[1].tag == 1 && v[1].y.cap == 21 && v[39].x.p == nullptr);
+    CHECK(v[39].x.ensure(5));
+    v.erase(v.begin());  // every later element moves down by one; the first one's buffers are freed
+    CHECK(g_live_bufs == before + 3 && v[0].tag == 1 && v[0].x.p == x1 && v[38].x.cap == 5);
+    v.resize(1);
+    CHECK(g_live_bufs == before + 2);
+  }
+  CHECK(g_live_bufs == before);
+}
+
+static void events_set(simmr_engine* e) {
+  const long before = g_live_events;
+  {
+    Events<4> ev;
+    CHECK(ev[0] == nullptr && ev[3] == nullptr);
+    CHECK(hipEventCreate(&ev[1]) == hipSuccess);
+    hipEvent_t const had = ev[1];
+    const long creates = g_event_creates;
+    CHECK(ev.create_missing(e) == SIMMR_OK && g_event_creates == creates + 3 && ev[1] == had && ev[0] && ev[2] && ev[3]);
+    CHECK(ev.create_missing(e) == SIMMR_OK && g_event_creates == creates + 3);  // none is missing
+    CHECK(g_live_events == before + 4);
+    Events<2> two;
+    g_fail_next_event = true;
+    CHECK(two.create_missing(e) == SIMMR_ENODEV && e->err == "hipEventCreate(&ev) failed: stub error");
+    (void)hipGetLastError();
+    CHECK(two.create_missing(e) == SIMMR_OK && g_live_events == before + 6);
+  }
+  CHECK(g_live_events == before);
+}
+
+struct UnitState {  // as a unit's state: buffers, an array of buffers, events, host members
+  DevBuf a, b[2];
+  Events<4> ev;
+  std::vector<uint64_t> host = {1, 2, 3};
+};
+
+static void state_in_a_slot(simmr_engine* e) {
+  const long before = live();
+  CHECK((unit_state<UnitState, ENG_EXT_STRAIN>(e, false)) == nullptr && e->slot[ENG_EXT_STRAIN] == nullptr);
+  UnitState* s = unit_state<UnitState, ENG_EXT_STRAIN>(e, true);
+  CHECK(s && e->slot[ENG_EXT_STRAIN] == s && e->destroy[ENG_EXT_STRAIN]);
+  CHECK((unit_state<UnitState, ENG_EXT_STRAIN>(e, true)) == s && (unit_state<UnitState, ENG_EXT_STRAIN>(e, false)) == s);
+  CHECK((unit_state<UnitState, ENG_EXT_DEPTH>(e, false)) == nullptr);  // another unit's slot
+  CHECK(s->a.ensure(100) && s->b[0].ensure(200) && s->b[1].ensure_slack(300) && s->ev.create_missing(e) == SIMMR_OK);
+  CHECK(live() == before + 3 + 4);
+  // what simmr_engine_destroy does with a slot
+  e->destroy[ENG_EXT_STRAIN](e->slot[ENG_EXT_STRAIN]);
+  e->slot[ENG_EXT_STRAIN] = nullptr;
+  CHECK(live() == before);
+}
+
+static void sync_and_macro(simmr_engine* e) {
+  const long syncs = g_syncs;
+  CHECK(sync_check(e, "a pass") == SIMMR_OK && g_syncs == syncs + 1);
+  g_pending = hipErrorOutOfMemory;  // an error some earlier call left behind
+  CHECK(sync_check(e, "a pass") == SIMMR_ENODEV && e->err == "a pass: stub error" && g_pending == hipSuccess);
+  auto through_macro = [](simmr_engine* e, hipError_t s) -> int {
+    HIP_TRY(e, hipGetErrorString(s) ? s : s);
+    return SIMMR_OK;
+  };
+  CHECK(through_macro(e, hipSuccess) == SIMMR_OK);
+  CHECK(through_macro(e, hipErrorOutOfMemory) == SIMMR_ENODEV && e->err == "hipGetErrorString(s) ? s : s failed: stub error");
+}
+
+static void rows(simmr_engine* e) {
+  using V32 = std::vector<uint32_t>;
+  using V64 = std::vector<uint64_t>;
+  StagedRows none = staged_rows(e, true);
+  CHECK(none.n_slots() == 0 && none.n_rows() == 0 && none.first == V64{0} && none.longest == 0 && none.cbase.empty());
+  e->genomes = {{5, 7}, {}, {3}, {}};  // slots 1 and 3 are not staged
+  StagedRows r = staged_rows(e, true);
+  CHECK(r.n_slots() == 4 && r.n_rows() == 3 && r.longest == 7);
+  CHECK((r.cbase == V32{0, 2, 2, 3}) && (r.ncontig == V32{2, 0, 1, 0}));
+  CHECK((r.bases == V64{5, 7, 3}) && (r.first == V64{0, 5, 12, 15}));
+  CHECK((r.genome == V32{0, 0, 2}) && (r.contig == V32{0, 1, 0}));
+  StagedRows plain = staged_rows(e);
+  CHECK(plain.genome.empty() && plain.contig.empty() && plain.bases == r.bases && plain.first == r.first && plain.cbase == r.cbase);
+}
+
+int main() {
+  simmr_engine e;
+  ensure_keeps_grows_and_fails();
+  growth_rules();
+  one_owner();
+  vector_of_holders();
+  events_set(&e);
+  state_in_a_slot(&e);
+  sync_and_macro(&e);
+  rows(&e);
+  if (g_failed) return 101;
+  printf("ok: %ld allocations, %ld events, %ld alive\n", g_mallocs, g_event_creates, live());
+  return live() > 100 ? 100 : (int)live();
+}

@@ -126,7 +126,7 @@ def test_the_unit_is_built_and_has_its_slot():
     internal = (CSRC / "engine_internal.hpp").read_text()
     assert "ENG_EXT_BAM = 9, ENG_EXT_COUNT = 10" in internal
     unit = (CSRC / "bam.hip").read_text()
-    assert "eng_ext_slot(e, ENG_EXT_BAM, bam_destroy)" in unit and '#include "engine.hip"' not in unit and '#include "kernels.hip"' not in unit
+    assert "unit_state<BamState, ENG_EXT_BAM>" in unit and '#include "engine.hip"' not in unit and '#include "kernels.hip"' not in unit
     k = (CSRC / "bam_kernels.hip").read_text()
     defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(BGZF_\w+)\s+(\d+)u?\b", k, re.M)}
     assert defines["BGZF_BLOCK"] == 0xff00 and defines["BGZF_SEG"] * (defines["BGZF_LANES"] - 1) == defines["BGZF_BLOCK"]
