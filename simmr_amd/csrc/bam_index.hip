@@ -119,7 +119,7 @@ int simmr_bam_sort_ref_lengths(simmr_bam_sort* h, uint64_t* lengths, uint64_t ca
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
   if (!n_rows) return eng_fail(e, SIMMR_EINVAL, "simmr_bam_sort_ref_lengths: NULL n_rows");
-  if (!h->s.planned_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_bam_sort_plan yet");
+  if (!h->s.sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no simmr_bam_sort_plan yet");
   *n_rows = h->s.nt.n_rows;
   if (capacity < h->s.nt.n_rows) return eng_fail(e, SIMMR_ERANGE, "capacity %llu < %llu rows", (unsigned long long)capacity, (unsigned long long)h->s.nt.n_rows);
   if (h->s.nt.n_rows > 0 && !lengths) return eng_fail(e, SIMMR_EINVAL, "simmr_bam_sort_ref_lengths: NULL lengths");

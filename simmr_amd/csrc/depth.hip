@@ -22,9 +22,9 @@ struct DepthState {
   std::vector<uint32_t> c_genome, c_contig;
   std::vector<uint64_t> fwin;             // n_contigs + 1, of the last summarize
   uint64_t n_positions = 0, n_tiles = 0, epoch = 0, added = 0, resets = 0;
-  bool ready = false, timed = false, emitted = false, summarized = false;
+  bool ready = false;
   DevBuf diff, tile_sum, d_slots, d_cfirst, d_fwin, d_out;
-  Events<6> ev;                           // add, emit, summarize: begin / end
+  Spans<3> sp;                            // add, emit, summarize
 
   size_t diff_bytes() const { return (size_t)n_tiles * DEPTH_TILE * 4u; }  // n_positions + 1 entries, padded to whole tiles
   int32_t* diff_p() const { return diff.as<int32_t>(); }
@@ -53,7 +53,7 @@ int simmr_depth_reset(simmr_engine* e, uint64_t* n_positions, uint64_t* n_contig
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   DepthState* s = depth_state(e, true);
   s->ready = false;
-  if (int rc = s->ev.create_missing(e)) return rc;
+  if (int rc = s->sp.create_missing(e)) return rc;
   StagedRows rows = staged_rows(e, true);
   const uint32_t n_slots = rows.n_slots();
   s->slots.assign(n_slots, DepthSlot{0u, 0u});
@@ -76,7 +76,7 @@ int simmr_depth_reset(simmr_engine* e, uint64_t* n_positions, uint64_t* n_contig
   HIP_TRY(e, hipMemcpyAsync(s->d_cfirst.p, s->cfirst.data(), s->cfirst.size() * 8, hipMemcpyHostToDevice, st));
   s->epoch = eng_staging_epoch(e);
   s->added = 0;
-  s->timed = s->emitted = s->summarized = false;
+  s->sp.invalidate_from(0);
   if (int rc = sync_check(e, "depth reset")) return rc;  // (the tables were copied from vectors the next reset rewrites)
   s->ready = true;
   s->resets++;
@@ -98,17 +98,17 @@ int simmr_depth_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_re
     return eng_fail(e, SIMMR_ERANGE, "the reads added since simmr_depth_reset would reach 2^31");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->sp.begin(0, st));
   if (n_reads > 0)
     hipLaunchKernelGGL(k_depth_mark, dim3((uint32_t)((n_reads + DEPTH_WG - 1) / DEPTH_WG)), dim3(DEPTH_WG), 0, st, reads->start, reads->end,
                        reads->contig, reads->genome, n_reads, (const DepthSlot*)s->d_slots.p, (uint32_t)s->slots.size(),
                        (const uint64_t*)s->d_cfirst.p, s->diff_p(), s->err_p());
-  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, s->sp.end(0, st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "depth launch failed: %s", hipGetErrorString(rc));
   s->added += n_reads;
-  s->timed = true;
-  s->emitted = s->summarized = false;
+  s->sp.mark(0);
+  s->sp.invalidate_from(1);
   return SIMMR_OK;
 }
 
@@ -122,7 +122,7 @@ int simmr_depth_emit(simmr_engine* e, uint32_t* depth_device, uint64_t capacity)
     return eng_fail(e, SIMMR_EINVAL, "simmr_depth_emit: depth_device must be a 16-byte aligned device pointer");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, s->sp.begin(1, st));
   if (s->n_positions > 0) {
     const uint32_t grid = (uint32_t)s->n_tiles;
     hipLaunchKernelGGL(k_depth_tile_sums, dim3(grid), dim3(DEPTH_WG), 0, st, (const depth_v4i*)s->diff.p, (int32_t*)s->tile_sum.p);
@@ -131,11 +131,11 @@ int simmr_depth_emit(simmr_engine* e, uint32_t* depth_device, uint64_t capacity)
     hipLaunchKernelGGL(k_depth_apply, dim3((uint32_t)((s->n_positions + DEPTH_TILE - 1) / DEPTH_TILE)), dim3(DEPTH_WG), 0, st,
                        (const depth_v4i*)s->diff.p, (const int32_t*)s->tile_sum.p, depth_device, s->n_positions);
   }
-  HIP_TRY(e, hipEventRecord(s->ev[3], st));
+  HIP_TRY(e, s->sp.end(1, st));
   uint32_t errw = 0;
   HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "depth scan")) return rc;
-  if (s->timed) s->emitted = true;
+  if (s->sp.valid[0]) s->sp.mark(1);
   if (errw)
     return eng_fail(e, SIMMR_EINVAL, "a read added since the last simmr_depth_reset names a genome slot that is not tracked or a "
                                      "contig that does not exist, or its window leaves its contig");
@@ -181,7 +181,7 @@ int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_
   void* const d_out = s->d_out.p;
   HIP_TRY(e, hipMemsetAsync(d_out, 0, host.size() * 8, st));
   HIP_TRY(e, hipMemcpyAsync(s->d_fwin.p, s->fwin.data(), s->fwin.size() * 8, hipMemcpyHostToDevice, st));
-  HIP_TRY(e, hipEventRecord(s->ev[4], st));
+  HIP_TRY(e, s->sp.begin(2, st));
   if (n_units > 0) {
     // consecutive units per wave: enough waves to fill the device, and fewer than 2^30 positions per wave (unit < 2^30): an
     // LDS bin of the workgroup's four waves stays below 2^32
@@ -197,10 +197,10 @@ int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_
                        windows ? (unsigned long long*)win->sum : nullptr, windows ? win->covered : nullptr, windows ? win->max : nullptr,
                        rows, rows + 3 * n_contigs);
   }
-  HIP_TRY(e, hipEventRecord(s->ev[5], st));
+  HIP_TRY(e, s->sp.end(2, st));
   HIP_TRY(e, hipMemcpyAsync(host.data(), d_out, host.size() * 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "depth summary")) return rc;
-  if (s->timed) s->summarized = true;
+  if (s->sp.valid[0]) s->sp.mark(2);
   for (uint64_t k = 0; rows_host && k < n_contigs; k++) {
     simmr_depth_contig& r = rows_host[k];
     memset(&r, 0, sizeof r);
@@ -220,14 +220,8 @@ int simmr_depth_summarize(simmr_engine* e, const uint32_t* depth_device, uint32_
 int simmr_last_depth_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
   DepthState* s = depth_state(e, false);
-  if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_depth_add yet");
-  if (int rc = sync_check(e, "depth")) return rc;
-  float a = 0.f, b = 0.f, c = 0.f;
-  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->emitted) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
-  if (s->summarized) HIP_TRY(e, hipEventElapsedTime(&c, s->ev[4], s->ev[5]));
-  *ms = a + b + c;
-  return SIMMR_OK;
+  if (!s || !s->sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no simmr_depth_add yet");
+  return s->sp.total_ms(e, "depth", ms);
 }
 
 }  // extern "C"

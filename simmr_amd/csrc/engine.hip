@@ -24,8 +24,6 @@
 #include "kernels.hip"
 #include "text_lines.hip"
 #include "fastq_kernels.hip"
-#include "truth_kernels.hip"
-#include "stats_kernels.hip"
 #include "custom_model.hpp"
 #include "host_support.hpp"
 
@@ -154,21 +152,6 @@ struct simmr_engine {
   DevBuf fq_hlen;                  // header bytes per read (direct form)
   DevBuf fq_tpl_dev;               // the compiled header template, read by the kernels through a pointer
   DevBuf fd_seq, fd_qual, fd_seq_off, fd_start, fd_end, fd_contig, fd_genome, fd_read_id, fd_flags;  // columns of the unfused fallback
-
-  // ground truth per read (simmr_truth_plan / simmr_truth_emit): counts, their scan, an error word of its own (a plan
-  // of the next shard may own d_err), and the columns the plan was made for
-  DevBuf tr_nm, tr_off, tr_err;
-  Events<4> tr_ev;  // plan begin / end, emit begin / end
-  bool tr_ready = false, tr_emitted = false;
-  uint64_t tr_reads = 0, tr_edits = 0;
-  const void *tr_seq = nullptr, *tr_seq_off = nullptr;
-  uint32_t tr_slot = 0;
-
-  // run statistics (simmr_stats_reset / simmr_stats_add / simmr_stats_read): the simmr_run_stats the kernel adds to,
-  // followed by its sticky error word
-  DevBuf st_tab;
-  Events<2> st_ev;  // the last add's begin / end
-  bool st_ready = false, st_timed = false;
 
   // engine_internal.hpp: the simmr_stage_* calls so far, and the states of the library's other translation units
   // (depth.hip: coverage depth, strain.hip: strain divergence, ...) with the hooks that delete them (host_support.hpp: unit_state)
@@ -731,11 +714,11 @@ int sort_by_length(simmr_engine* e, uint64_t count, uint32_t shift, bool* sorted
 }
 
 // exclusive scan of scale * in[i] (n entries of type T) -> `out` (n + 1 u64 entries); returns the total
+// (the body, over raw pointers: `out` has room for its n + 1 entries)
 template <typename T>
-int scan_scaled(simmr_engine* e, DevBuf& in, uint64_t n, uint32_t scale, DevBuf& out, uint64_t* total, uint32_t round = 0) {
-  if (!out.ensure_slack((n + 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
+int scan_scaled_into(simmr_engine* e, const T* in, uint64_t n, uint32_t scale, uint64_t* out, uint64_t* total, uint32_t round) {
   if (n == 0) {
-    HIP_TRY(e, hipMemsetAsync(out.p, 0, 8, e->stream));
+    HIP_TRY(e, hipMemsetAsync(out, 0, 8, e->stream));
     *total = 0;
     return SIMMR_OK;
   }
@@ -744,13 +727,17 @@ int scan_scaled(simmr_engine* e, DevBuf& in, uint64_t n, uint32_t scale, DevBuf&
   if (!e->scan_tmp.ensure_slack((n_wg + 2) * 8)) return e->fail(SIMMR_ENOMEM, "scan scratch allocation failed");
   uint64_t* wg_tot = e->scan_tmp.as<uint64_t>();
   uint64_t* grand = wg_tot + n_wg;
-  hipLaunchKernelGGL(k_scan_reduce<T>, dim3((uint32_t)n_wg), dim3(SCAN_THREADS), 0, e->stream,
-                     (const T*)in.as<T>(), n, scale, round, wg_tot);
+  hipLaunchKernelGGL(k_scan_reduce<T>, dim3((uint32_t)n_wg), dim3(SCAN_THREADS), 0, e->stream, in, n, scale, round, wg_tot);
   hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(SCAN_THREADS), 0, e->stream, wg_tot, n_wg, grand);
-  hipLaunchKernelGGL(k_scan_apply<T>, dim3((uint32_t)n_wg), dim3(SCAN_THREADS), 0, e->stream,
-                     (const T*)in.as<T>(), n, scale, round, (const uint64_t*)wg_tot, out.as<uint64_t>());
+  hipLaunchKernelGGL(k_scan_apply<T>, dim3((uint32_t)n_wg), dim3(SCAN_THREADS), 0, e->stream, in, n, scale, round,
+                     (const uint64_t*)wg_tot, out);
   HIP_TRY(e, hipMemcpyAsync(total, grand, 8, hipMemcpyDeviceToHost, e->stream));
   return sync_check(e, "offset scan");
+}
+template <typename T>
+int scan_scaled(simmr_engine* e, DevBuf& in, uint64_t n, uint32_t scale, DevBuf& out, uint64_t* total, uint32_t round = 0) {
+  if (!out.ensure_slack((n + 1) * 8)) return e->fail(SIMMR_ENOMEM, "offset allocation failed");
+  return scan_scaled_into<T>(e, in.as<T>(), n, scale, out.as<uint64_t>(), total, round);
 }
 int scan_u64(simmr_engine* e, DevBuf& in, uint64_t n, DevBuf& out, uint64_t* total) { return scan_scaled<uint64_t>(e, in, n, 1u, out, total); }
 
@@ -1053,10 +1040,12 @@ void eng_genome_planes(const simmr_engine* e, uint32_t slot, uint32_t** packed, 
   *plane_bases = g.plane_bases;
 }
 void eng_planes_rewritten(simmr_engine* e) {
-  e->tr_ready = false;
   e->staging_epoch++;
   e->plan = PlanState{};
   if (e->fq.kind == FQPLAN_DIRECT) e->fq = FqState{};
+}
+int eng_scan_u32(simmr_engine* e, const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* total) {
+  return scan_scaled_into<uint32_t>(e, in, n, 1u, out, total, 0u);
 }
 void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*)) {
   e->ext_destroy[which] = destroy;
@@ -1271,7 +1260,6 @@ int simmr_stage_genome(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
                        const uint8_t* const* contig_ascii, const uint64_t* contig_len,
                        const uint64_t* contig_size) {
   if (!e) return SIMMR_EINVAL;
-  e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
   e->staging_epoch++;
   if (!contig_ascii || !contig_len || n_contigs == 0) return e->fail(SIMMR_EINVAL, "empty genome");
   HIP_TRY(e, hipSetDevice(e->device));
@@ -1313,7 +1301,6 @@ int simmr_stage_fasta(simmr_engine* e, uint32_t genome_idx, uint32_t n_records, 
                       const uint64_t* body_len, int contiguous, uint64_t min_size, uint64_t* base_count,
                       uint32_t* n_staged) {
   if (!e) return SIMMR_EINVAL;
-  e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
   e->staging_epoch++;
   if (!body || !body_len || !base_count || n_records == 0) return e->fail(SIMMR_EINVAL, "empty FASTA");
   HIP_TRY(e, hipSetDevice(e->device));
@@ -1390,7 +1377,6 @@ int simmr_stage_fasta(simmr_engine* e, uint32_t genome_idx, uint32_t n_records, 
 int simmr_stage_synthetic(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
                           const uint64_t* contig_len, uint64_t splitmix_seed) {
   if (!e) return SIMMR_EINVAL;
-  e->tr_ready = false;  // a truth plan counted against the staging that is being replaced
   e->staging_epoch++;
   if (!contig_len || n_contigs == 0) return e->fail(SIMMR_EINVAL, "empty genome");
   HIP_TRY(e, hipSetDevice(e->device));
@@ -2329,169 +2315,6 @@ int simmr_emit_fastq(simmr_engine* e, uint8_t* dst, uint64_t dst_capacity) {
   HIP_TRY(e, hipEventRecord(e->ev_d, e->stream));
   hipError_t s = hipGetLastError();
   if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "fastq launch failed: %s", hipGetErrorString(s));
-  return SIMMR_OK;
-}
-
-// ---- ground truth per read (include/simmr_hip.h) ------------------------------------------------------------------
-static TruthReads truth_reads(const simmr_reads_out* reads) {
-  return TruthReads{reads->seq, reads->qual, reads->seq_off, reads->start, reads->end, reads->contig, reads->genome,
-                    reads->flags, reads->seq_capacity, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
-}
-// the grid of the kernels that walk the reads, a row of 16 lanes per read and 16 reads per workgroup and batch
-static_assert(TRUTH_WG_READS == STATS_WG_READS, "k_truth and k_read_stats batch their reads alike");
-static uint32_t row_grid(const simmr_engine* e, uint64_t n_reads, uint32_t wgs_per_cu) {
-  const uint64_t n_batches = (n_reads + TRUTH_WG_READS - 1) / TRUTH_WG_READS;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_batches, (uint64_t)e->n_cu * wgs_per_cu));
-}
-// the columns those kernels read: all of them, seq and qual once there is a read (n_reads > 0), and, where the call
-// takes the layout from `reads` (check_slot), a slot_bytes it knows
-static int check_read_columns(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, const char* who, bool check_slot = true) {
-  if (!reads->seq_off || !reads->start || !reads->end || !reads->contig || !reads->genome || !reads->flags ||
-      (n_reads > 0 && (!reads->seq || !reads->qual)))
-    return e->fail(SIMMR_EINVAL, "%s needs seq, qual, seq_off, start, end, contig, genome and flags", who);
-  if (check_slot && reads->slot_bytes > 1u && reads->slot_bytes != SIMMR_SLOT16) return e->fail(SIMMR_EINVAL, "reads->slot_bytes is 0 (compact) or 16");
-  return SIMMR_OK;
-}
-
-int simmr_truth_plan(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint64_t* n_edits) {
-  if (!e) return SIMMR_EINVAL;
-  e->tr_ready = false;
-  e->tr_emitted = false;
-  if (!reads || !n_edits) return e->fail(SIMMR_EINVAL, "simmr_truth_plan: NULL argument");
-  int rc;
-  if ((rc = check_read_columns(e, reads, n_reads, "simmr_truth_plan"))) return rc;
-  HIP_TRY(e, hipSetDevice(e->device));
-  if (int rc = e->tr_ev.create_missing(e)) return rc;
-  if (!e->tr_nm.ensure_slack(std::max<uint64_t>(n_reads, 1) * 4) || !e->tr_err.ensure_slack(64))
-    return e->fail(SIMMR_ENOMEM, "truth count allocation failed");
-  HIP_TRY(e, hipMemsetAsync(e->tr_err.p, 0, 64, e->stream));
-  HIP_TRY(e, hipEventRecord(e->tr_ev[0], e->stream));
-  if (n_reads > 0)
-    hipLaunchKernelGGL(k_truth<false>, dim3(row_grid(e, n_reads, TRUTH_WGS_PER_CU)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
-                       (uint32_t)e->genomes.size(), truth_reads(reads), n_reads, e->tr_nm.as<uint32_t>(),
-                       (const uint64_t*)nullptr, TruthCols{nullptr, nullptr, nullptr, nullptr}, e->tr_err.as<uint32_t>());
-  uint64_t total = 0;
-  if ((rc = scan_scaled<uint32_t>(e, e->tr_nm, n_reads, 1u, e->tr_off, &total))) return rc;
-  HIP_TRY(e, hipEventRecord(e->tr_ev[1], e->stream));
-  uint32_t errw = 0;
-  HIP_TRY(e, hipMemcpyAsync(&errw, e->tr_err.p, 4, hipMemcpyDeviceToHost, e->stream));
-  if ((rc = sync_check(e, "truth count readback"))) return rc;
-  if (errw & SIMMR_ERRBIT_TRUTH)
-    return e->fail(SIMMR_EINVAL, "a read names a genome or contig that is not staged, or its coordinates leave the contig or seq[]");
-  e->tr_reads = n_reads;
-  e->tr_edits = total;
-  e->tr_seq = reads->seq;
-  e->tr_seq_off = reads->seq_off;
-  e->tr_slot = reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u;
-  e->tr_ready = true;
-  *n_edits = total;
-  return SIMMR_OK;
-}
-
-int simmr_truth_emit(simmr_engine* e, const simmr_reads_out* reads, const simmr_truth_out* out) {
-  if (!e) return SIMMR_EINVAL;
-  e->tr_emitted = false;  // (simmr_last_truth_ms: an emit that fails adds nothing to the plan's time)
-  if (!reads || !out) return e->fail(SIMMR_EINVAL, "simmr_truth_emit: NULL argument");
-  if (!e->tr_ready || reads->seq != e->tr_seq || reads->seq_off != e->tr_seq_off ||
-      (reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u) != e->tr_slot)
-    return e->fail(SIMMR_ESTATE, "simmr_truth_emit called without a simmr_truth_plan for these columns");
-  // (seq and seq_off are the plan's, which checked them; so is the layout)
-  if (int rc = check_read_columns(e, reads, e->tr_reads, "simmr_truth_emit", false)) return rc;
-  const bool any_edit = out->edit_pos || out->edit_ref || out->edit_alt || out->edit_qual;
-  if (any_edit && !out->edit_off) return e->fail(SIMMR_EINVAL, "edit columns without edit_off");
-  if ((out->nm || out->edit_off) && out->reads_capacity < e->tr_reads)
-    return e->fail(SIMMR_ERANGE, "reads_capacity %llu < %llu reads planned", (unsigned long long)out->reads_capacity,
-                   (unsigned long long)e->tr_reads);
-  if (any_edit && out->edits_capacity < e->tr_edits)
-    return e->fail(SIMMR_ERANGE, "edits_capacity %llu < %llu edits planned", (unsigned long long)out->edits_capacity,
-                   (unsigned long long)e->tr_edits);
-  HIP_TRY(e, hipSetDevice(e->device));
-  HIP_TRY(e, hipEventRecord(e->tr_ev[2], e->stream));
-  if (out->nm && e->tr_reads > 0)
-    HIP_TRY(e, hipMemcpyAsync(out->nm, e->tr_nm.p, e->tr_reads * 4, hipMemcpyDeviceToDevice, e->stream));
-  if (out->edit_off)
-    HIP_TRY(e, hipMemcpyAsync(out->edit_off, e->tr_off.p, (e->tr_reads + 1) * 8, hipMemcpyDeviceToDevice, e->stream));
-  if (any_edit && e->tr_edits > 0)
-    hipLaunchKernelGGL(k_truth<true>, dim3(row_grid(e, e->tr_reads, TRUTH_WGS_PER_CU)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(),
-                       (uint32_t)e->genomes.size(), truth_reads(reads), e->tr_reads, (uint32_t*)nullptr,
-                       (const uint64_t*)e->tr_off.as<uint64_t>(), TruthCols{out->edit_pos, out->edit_ref, out->edit_alt, out->edit_qual},
-                       e->tr_err.as<uint32_t>());
-  HIP_TRY(e, hipEventRecord(e->tr_ev[3], e->stream));
-  hipError_t s = hipGetLastError();
-  if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "truth launch failed: %s", hipGetErrorString(s));
-  e->tr_emitted = true;
-  return SIMMR_OK;
-}
-
-int simmr_last_truth_ms(simmr_engine* e, float* ms) {
-  if (!e || !ms) return SIMMR_EINVAL;
-  if (!e->tr_ready) return e->fail(SIMMR_ESTATE, "no truth plan yet");
-  int rc = sync_check(e, "truth");
-  if (rc) return rc;
-  float a = 0.f, b = 0.f;
-  HIP_TRY(e, hipEventElapsedTime(&a, e->tr_ev[0], e->tr_ev[1]));
-  if (e->tr_emitted) HIP_TRY(e, hipEventElapsedTime(&b, e->tr_ev[2], e->tr_ev[3]));
-  *ms = a + b;
-  return SIMMR_OK;
-}
-
-// ---- run statistics (include/simmr_hip.h) -----------------------------------------------------------------------
-static const size_t STATS_BYTES = sizeof(simmr_run_stats) + 8;  // the tables and the error word behind them
-
-int simmr_stats_reset(simmr_engine* e) {
-  if (!e) return SIMMR_EINVAL;
-  HIP_TRY(e, hipSetDevice(e->device));
-  if (int rc = e->st_ev.create_missing(e)) return rc;
-  if (!e->st_tab.ensure_slack(STATS_BYTES)) return e->fail(SIMMR_ENOMEM, "statistics allocation failed");
-  HIP_TRY(e, hipMemsetAsync(e->st_tab.p, 0, STATS_BYTES, e->stream));
-  e->st_ready = true;
-  e->st_timed = false;
-  return SIMMR_OK;
-}
-
-int simmr_stats_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_reads, uint32_t n_sets) {
-  if (!e) return SIMMR_EINVAL;
-  if (!reads) return e->fail(SIMMR_EINVAL, "simmr_stats_add: NULL argument");
-  if (n_sets != 1u && n_sets != 2u) return e->fail(SIMMR_EINVAL, "simmr_stats_add: n_sets is 1 or 2");
-  // (seq and qual are asked for even of no reads)
-  if (int rc = check_read_columns(e, reads, std::max<uint64_t>(n_reads, 1), "simmr_stats_add")) return rc;
-  if (!e->st_ready) return e->fail(SIMMR_ESTATE, "simmr_stats_add called before simmr_stats_reset");
-  HIP_TRY(e, hipSetDevice(e->device));
-  HIP_TRY(e, hipEventRecord(e->st_ev[0], e->stream));
-  if (n_reads > 0) {
-    unsigned long long* tab = e->st_tab.as<unsigned long long>();
-    hipLaunchKernelGGL(k_read_stats, dim3(row_grid(e, n_reads, STATS_WGS_PER_CU)), dim3(256), 0, e->stream, e->d_genomes.as<GenomeDev>(), (uint32_t)e->genomes.size(),
-                       truth_reads(reads), n_reads, n_sets, reads->qual_offset, tab, (uint32_t*)(tab + STATS_TABLE_WORDS));
-  }
-  HIP_TRY(e, hipEventRecord(e->st_ev[1], e->stream));
-  hipError_t s = hipGetLastError();
-  if (s != hipSuccess) return e->fail(SIMMR_ENODEV, "statistics launch failed: %s", hipGetErrorString(s));
-  e->st_timed = true;
-  return SIMMR_OK;
-}
-
-int simmr_stats_read(simmr_engine* e, simmr_run_stats* dst_host) {
-  if (!e) return SIMMR_EINVAL;
-  if (!dst_host) return e->fail(SIMMR_EINVAL, "simmr_stats_read: NULL argument");
-  if (!e->st_ready) return e->fail(SIMMR_ESTATE, "simmr_stats_read called before simmr_stats_reset");
-  HIP_TRY(e, hipSetDevice(e->device));
-  std::vector<uint64_t> host(STATS_BYTES / 8);
-  HIP_TRY(e, hipMemcpyAsync(host.data(), e->st_tab.p, STATS_BYTES, hipMemcpyDeviceToHost, e->stream));
-  int rc = sync_check(e, "statistics readback");
-  if (rc) return rc;
-  if (host[STATS_TABLE_WORDS] != 0)
-    return e->fail(SIMMR_EINVAL, "a read added since the last simmr_stats_reset names a genome or contig that is not staged, "
-                                 "its coordinates leave the contig or seq[], or it is longer than 65535 bases");
-  memcpy(dst_host, host.data(), sizeof(simmr_run_stats));
-  return SIMMR_OK;
-}
-
-int simmr_last_stats_ms(simmr_engine* e, float* ms) {
-  if (!e || !ms) return SIMMR_EINVAL;
-  if (!e->st_timed) return e->fail(SIMMR_ESTATE, "no simmr_stats_add yet");
-  int rc = sync_check(e, "statistics");
-  if (rc) return rc;
-  HIP_TRY(e, hipEventElapsedTime(ms, e->st_ev[0], e->st_ev[1]));
   return SIMMR_OK;
 }
 

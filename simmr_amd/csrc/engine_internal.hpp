@@ -1,7 +1,8 @@
-// engine_internal.hpp — what another translation unit of libsimmr_hip.so (depth.hip, strain.hip, regions.hip, pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip, fit_sam.hip, bam.hip, bam_index.hip, mapeval.hip) may ask of an engine.  simmr_engine is
-// defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the C ABI.
-// The host plumbing over these accessors that every unit uses, engine.hip too (the owning DevBuf and Events, HIP_TRY, sync_check,
-// unit_state, staged_rows), is host_support.hpp, which includes this file.
+// engine_internal.hpp — what another translation unit of libsimmr_hip.so (truth.hip, stats.hip, depth.hip, strain.hip, regions.hip,
+// pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip, fit_sam.hip, bam.hip, bam_index.hip, mapeval.hip) may ask of an engine.
+// simmr_engine is defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the
+// C ABI.  The host plumbing over these accessors that every unit uses, engine.hip too (the owning DevBuf and Events, the Spans that
+// time a unit's calls, HIP_TRY, sync_check, unit_state, staged_rows), is host_support.hpp, which includes this file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,8 +32,9 @@ SIMMR_HIDDEN void eng_genome_planes(const simmr_engine* e, uint32_t slot, uint32
 // The device table of the genome slots (GenomeDev[*n_slots], what the read walker of read_walk.hpp takes); rewritten by every
 // simmr_stage_* call on the engine's stream, so a kernel enqueued there sees the table of its own moment.
 SIMMR_HIDDEN const GenomeDev* eng_genome_table(const simmr_engine* e, uint32_t* n_slots);
-// What a call that rewrites staged bases owes the engine: what every simmr_stage_* call does (the truth plan is dropped,
-// the staging epoch counts on), and the plan in force is dropped with the direct FASTQ plan made from it.
+// What a call that rewrites staged bases owes the engine: what every simmr_stage_* call does (the staging epoch counts on:
+// a truth plan, like every state that kept the epoch it saw, is no longer in force), and the plan in force is dropped with the
+// direct FASTQ plan made from it.
 SIMMR_HIDDEN void eng_planes_rewritten(simmr_engine* e);
 // The stable radix sort of sam_sort_kernels.hip (defined in sam_sort.hip, whose kernels cannot be included into a second unit):
 // sorts the n pairs (key[0][i], i) over the low key_bits bits of the keys on `st`, in 8-bit digits, least significant first.
@@ -42,10 +44,14 @@ SIMMR_HIDDEN void eng_planes_rewritten(simmr_engine* e);
 constexpr uint64_t SAMSORT_PAIRS_TILE = 2048, SAMSORT_PAIRS_DIGITS = 256;
 SIMMR_HIDDEN int samsort_sort_pairs(hipStream_t st, uint64_t* const key[2], uint32_t* const idx[2], uint32_t* hist, uint32_t* digit_total,
                                     uint64_t n, uint32_t key_bits);
+// The engine's scan (defined in engine.hip, whose k_scan_* kernels cannot be included into a second unit): the exclusive prefix
+// sums of in[0 .. n) into out[0 .. n] (device pointers; the caller made room for the n + 1 entries) on the engine's stream, over the
+// engine's scan scratch; *total = out[n].  Synchronises the stream.  n == 0: out[0] = 0, total 0, nothing launched.
+SIMMR_HIDDEN int eng_scan_u32(simmr_engine* e, const uint32_t* in, uint64_t n, uint64_t* out, uint64_t* total);
 // One opaque slot per engine and translation unit for that unit's state; simmr_engine_destroy calls `destroy` on a non-null
 // slot (on the engine's device, after the device has been synchronised).  Units reach their slot through unit_state of
 // host_support.hpp, whose hook deletes the state.
-enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_OVERLAP = 6, ENG_EXT_FIT = 7, ENG_EXT_FIT_SAM = 8, ENG_EXT_BAM = 9, ENG_EXT_COUNT = 10 };
+enum EngExt { ENG_EXT_DEPTH = 0, ENG_EXT_STRAIN = 1, ENG_EXT_REGIONS = 2, ENG_EXT_PILEUP = 3, ENG_EXT_SAM = 4, ENG_EXT_SAM_SORT = 5, ENG_EXT_OVERLAP = 6, ENG_EXT_FIT = 7, ENG_EXT_FIT_SAM = 8, ENG_EXT_BAM = 9, ENG_EXT_TRUTH = 10, ENG_EXT_STATS = 11, ENG_EXT_COUNT = 12 };
 SIMMR_HIDDEN void** eng_ext_slot(simmr_engine* e, EngExt which, void (*destroy)(void*));
 // The layout of depth[] that the last simmr_depth_reset recorded (defined in depth.hip): tracked contig k is entries
 // cfirst[k] .. cfirst[k + 1] - 1 (n_contigs + 1 entries, on the host and on the device) and contig c_contig[k] of genome slot

@@ -28,7 +28,7 @@ namespace {
 struct FitState {
   uint32_t k = 0, max_alt = 0;
   uint64_t n_dense = 0, n_slots = 0;
-  bool ready = false, planned = false, timed = false;
+  bool ready = false, planned = false;
   // what of qhist a reset has to clear: every add is followed by a plan that says how far its reads reached (dirty_pos, the
   // largest since the tables were last cleared whole); an add without a plan behind it leaves the whole table suspect
   uint64_t dirty_pos = 0, clean_dense = 0, clean_slots = 0;
@@ -37,7 +37,7 @@ struct FitState {
   DevBuf tables, out_key, out_cnt, pts, qdens, ldens, idens;
   // the finish: sort buffers, the per-reference tables (start | n_alt | total | first | sizes[2]), the model's pair columns
   DevBuf skey[2], sidx[2], perm[2], hist, digit_total, refs, kmer_ref, kmer_first, pair_alt, pair_count, pair_prob;
-  Events<2> ev;
+  Spans<1> sp;  // the last add (the SAM route's adds record it through fit_share)
   // the planned model (host side)
   simmr_fit_info info{};
   FitBins len, ins;
@@ -66,7 +66,7 @@ namespace simmr {
 bool fit_share(simmr_engine* e, FitShare* out) {
   FitState* s = fit_state(e, false);
   if (!s || !s->ready) return false;
-  *out = FitShare{s->dev(), s->sam_counts(), {s->ev[0], s->ev[1]}};
+  *out = FitShare{s->dev(), s->sam_counts(), {s->sp.ev[0], s->sp.ev[1]}};
   return true;
 }
 
@@ -75,7 +75,7 @@ void fit_share_added(simmr_engine* e) {
   if (!s) return;
   s->planned = false;
   s->unplanned_add = true;
-  s->timed = true;
+  s->sp.mark(0);
 }
 
 }  // namespace simmr
@@ -89,8 +89,9 @@ int simmr_fit_reset(simmr_engine* e, uint32_t k, uint32_t max_alt_kmers, uint64_
   if (pair_capacity == 0 || pair_capacity > (1ull << 26)) return eng_fail(e, SIMMR_EINVAL, "simmr_fit_reset: pair_capacity is 1 .. 2^26");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   FitState* s = fit_state(e, true);
-  s->ready = s->planned = s->timed = false;
-  if (int rc = s->ev.create_missing(e)) return rc;
+  s->ready = s->planned = false;
+  s->sp.invalidate_from(0);
+  if (int rc = s->sp.create_missing(e)) return rc;
   s->k = k;
   s->max_alt = max_alt_kmers;
   s->n_dense = 1ull << (2u * k);
@@ -129,7 +130,7 @@ int simmr_fit_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_read
   if (!s || !s->ready) return eng_fail(e, SIMMR_ESTATE, "simmr_fit_add called before simmr_fit_reset");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->sp.begin(0, st));
   if (n_reads > 0) {
     // persistent: one workgroup per CU (the LDS image takes most of a CU's 160 KB), each looping over its share of the batches
     const uint64_t batches = (n_reads + FIT_WG_READS - 1) / FIT_WG_READS;
@@ -140,12 +141,12 @@ int simmr_fit_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_read
                         reads->flags, reads->seq_capacity, reads->slot_bytes == SIMMR_SLOT16 ? 1u : 0u};
     hipLaunchKernelGGL(k_fit_add, dim3(grid), dim3(FIT_WG), 0, st, genomes, n_genomes, rd, n_reads, n_sets, reads->qual_offset, s->dev());
   }
-  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, s->sp.end(0, st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "fit launch failed: %s", hipGetErrorString(rc));
   s->planned = false;
   s->unplanned_add = true;
-  s->timed = true;
+  s->sp.mark(0);
   return SIMMR_OK;
 }
 
@@ -328,10 +329,8 @@ int simmr_fit_emit(simmr_engine* e, const simmr_fit_out* out) {
 int simmr_last_fit_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
   FitState* s = fit_state(e, false);
-  if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_fit_add yet");
-  if (int rc = sync_check(e, "fit")) return rc;
-  HIP_TRY(e, hipEventElapsedTime(ms, s->ev[0], s->ev[1]));
-  return SIMMR_OK;
+  if (!s || !s->sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no simmr_fit_add yet");
+  return s->sp.total_ms(e, "fit", ms);
 }
 
 }  // extern "C"

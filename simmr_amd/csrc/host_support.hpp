@@ -1,6 +1,6 @@
 // host_support.hpp — the host plumbing every translation unit of libsimmr_hip.so shares (engine.hip included): the owning
-// device buffer, the check of a HIP call, the synchronisation check, an owning set of events, the accessor of a unit's state in
-// its engine slot, and the dense table of the staged rows.  Host code only; internal to the library, and each unit that includes
+// device buffer, the check of a HIP call, the synchronisation check, an owning set of events, the spans that time a unit's calls, the
+// accessor of a unit's state in its engine slot, and the dense table of the staged rows.  Host code only; internal to the library, and each unit that includes
 // it gets its own copy of the routines.  Whatever owns device memory or events here frees them in its destructor: a state is a
 // struct of such members and needs no destroy code of its own.
 #pragma once
@@ -61,6 +61,9 @@ template <int N> struct Events {
   Events() = default;
   Events(const Events&) = delete;
   Events& operator=(const Events&) = delete;
+  Events(Events&& o) noexcept {
+    for (int i = 0; i < N; i++) { v[i] = o.v[i]; o.v[i] = nullptr; }
+  }
   ~Events() {
     for (hipEvent_t ev : v)
       if (ev) (void)hipEventDestroy(ev);
@@ -80,6 +83,32 @@ inline int sync_check(simmr_engine* e, const char* what) {
   if (s != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s: %s", what, hipGetErrorString(s));
   return SIMMR_OK;
 }
+
+// The device time of a unit's calls: N spans (pair i: events 2i and 2i + 1 around what call i enqueues) and which of them
+// count.  Recording an event marks nothing: a unit marks a span where its call has succeeded and unmarks the spans a new
+// call makes stale; total_ms adds up the marked ones.
+template <int N> struct Spans {
+  Events<2 * N> ev;
+  bool valid[N] = {};
+  int create_missing(simmr_engine* e) { return ev.create_missing(e); }
+  hipError_t begin(int i, hipStream_t st) { return hipEventRecord(ev[2 * i], st); }
+  hipError_t end(int i, hipStream_t st) { return hipEventRecord(ev[2 * i + 1], st); }
+  void mark(int i, bool on = true) { valid[i] = on; }
+  void invalidate_from(int i) {
+    for (; i < N; i++) valid[i] = false;
+  }
+  int total_ms(simmr_engine* e, const char* what, float* ms) const {
+    if (int rc = sync_check(e, what)) return rc;
+    float sum = 0.f;
+    for (int i = 0; i < N; i++) {
+      float one = 0.f;
+      if (valid[i]) HIP_TRY(e, hipEventElapsedTime(&one, ev[2 * i], ev[2 * i + 1]));
+      sum += one;
+    }
+    *ms = sum;
+    return SIMMR_OK;
+  }
+};
 
 // The state of type T that a unit keeps in its slot W of the engine (nullptr: none yet and `create` is false).
 // simmr_engine_destroy deletes it through the hook given here; T's members free what they own.

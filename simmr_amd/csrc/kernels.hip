@@ -85,15 +85,7 @@ SIMMR_DEV uint32_t wg_exclusive_scan_u32(uint32_t v, uint32_t* lds4, uint32_t* t
 SIMMR_DEV uint32_t wg_exclusive_scan_u32(uint32_t v, uint32_t* lds4, uint32_t* total) {
   return wg_exclusive_scan_u32(v, lds4, total, threadIdx.x);
 }
-// inclusive scan of one u32 over each row of 16 lanes (every lane of the row active): four DPP row shifts, one v_add
-// with a DPP source each.  The row's last lane holds the row's sum.
-SIMMR_DEV uint32_t row_inclusive_scan_u32(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);   // row_shr:1
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);   // row_shr:2
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);   // row_shr:4
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);   // row_shr:8
-  return v;
-}
+// (read_walk.hpp: row_inclusive_scan_u32, the scan over each row of 16 lanes)
 // ... and over a whole wave: the row scan and the two GFX9 row broadcasts — where __shfl_up costs a ds_bpermute, its
 // address and a select per step
 SIMMR_DEV uint32_t wave_inclusive_scan_u32(uint32_t v) {

@@ -29,9 +29,9 @@ struct OverlapState {
   DevBuf word;  // the error word, and six words of k_ovl_window's answer behind it
   OvlSorted sorted{};
   uint64_t min_overlap = 0, total = 0;
-  bool ready = false, planned = false, planned_once = false;
+  bool ready = false, planned = false;
+  Spans<2> sp;  // plan; an emit call (measured call by call into emit_ms, never marked)
   float emit_ms = 0.f;
-  Events<4> ev;
   uint32_t* err_p() const { return word.as<uint32_t>(); }
   uint64_t* win_p() const { return word.as<uint64_t>() + 2; }
   OvlRows rows() const { return OvlRows{g_cbase.as<const uint32_t>(), g_ncontig.as<const uint32_t>(), c_bases.as<const uint64_t>(), n_slots}; }
@@ -82,7 +82,7 @@ int simmr_overlap_reset(simmr_engine* e, int paired) {
   s->ready = s->planned = false;
   s->n = 0;
   if (int rc = sync_check(e, "overlap reset")) return rc;
-  if (int rc = s->ev.create_missing(e)) return rc;
+  if (int rc = s->sp.create_missing(e)) return rc;
   StagedRows rows = staged_rows(e);
   const uint32_t n_slots = rows.n_slots();
   std::vector<uint32_t>& cbase = rows.cbase;
@@ -164,7 +164,7 @@ int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads,
     return eng_fail(e, SIMMR_ENOMEM, "overlap plan allocation failed (%llu reads)", (unsigned long long)n);
   hipStream_t st = eng_stream(e);
   const uint32_t cap = (uint32_t)eng_cu_count(e) * OVL_WGS_PER_CU;
-  HIP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->sp.begin(0, st));
   uint64_t pairs = 0, total = 0;
   s->sorted = OvlSorted{};
   if (n > 0) {
@@ -193,12 +193,13 @@ int simmr_overlap_plan(simmr_engine* e, uint64_t min_overlap, uint64_t* n_reads,
     hipLaunchKernelGGL(k_ovl_scan, dim3(1), dim3(256), 0, st, s->rsum.as<const uint64_t>(), s->rprefix.as<uint64_t>(), r_chunks);
     HIP_TRY(e, hipMemcpyAsync(&total, s->rprefix.as<uint64_t>() + r_chunks, 8, hipMemcpyDeviceToHost, st));
   }
-  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, s->sp.end(0, st));
   if (int rc = sync_check(e, "overlap size pass and scan")) return rc;
   s->min_overlap = min_overlap;
   s->total = total;
   s->emit_ms = 0.f;
-  s->planned = s->planned_once = true;
+  s->planned = true;
+  s->sp.mark(0);
   if (n_reads) *n_reads = n;
   if (n_pairs) *n_pairs = pairs;
   if (total_bytes) *total_bytes = total;
@@ -246,16 +247,16 @@ int simmr_overlap_emit(simmr_engine* e, uint64_t first_place, uint64_t n_places,
   if (any && cols->capacity < j1 - j0)
     return eng_fail(e, SIMMR_ERANGE, "cols->capacity %llu < %llu records of these places", (unsigned long long)cols->capacity, (unsigned long long)(j1 - j0));
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, s->sp.begin(1, st));
   if (j1 > j0 && (dst || any)) {
     const uint64_t chunks = (j1 + OVL_CHUNK - 1) / OVL_CHUNK - j0 / OVL_CHUNK;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(chunks, (uint64_t)eng_cu_count(e) * OVL_WGS_PER_CU);
     hipLaunchKernelGGL(k_ovl_write, dim3(grid), dim3(256), 0, st, s->sorted, s->rprefix.as<const uint64_t>(), j0, j1, b0, bytes, dst, c);
   }
-  HIP_TRY(e, hipEventRecord(s->ev[3], st));
+  HIP_TRY(e, s->sp.end(1, st));
   if (int rc = sync_check(e, "overlap write pass")) return rc;
   float ms = 0.f;
-  HIP_TRY(e, hipEventElapsedTime(&ms, s->ev[2], s->ev[3]));
+  HIP_TRY(e, hipEventElapsedTime(&ms, s->sp.ev[2], s->sp.ev[3]));
   s->emit_ms += ms;
   return SIMMR_OK;
 }
@@ -263,11 +264,10 @@ int simmr_overlap_emit(simmr_engine* e, uint64_t first_place, uint64_t n_places,
 int simmr_last_overlap_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
   OverlapState* s = overlap_state(e, false);
-  if (!s || !s->planned_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_overlap_plan yet");
-  if (int rc = sync_check(e, "overlap")) return rc;
-  float a = 0.f;
-  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  *ms = a + s->emit_ms;
+  if (!s || !s->sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no simmr_overlap_plan yet");
+  float plan = 0.f;
+  if (int rc = s->sp.total_ms(e, "overlap", &plan)) return rc;
+  *ms = plan + s->emit_ms;
   return SIMMR_OK;
 }
 

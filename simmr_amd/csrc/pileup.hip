@@ -20,10 +20,10 @@ struct PileupState {
   std::vector<PileupSlot> slots;
   std::vector<uint64_t> cfirst;  // n_contigs + 1
   uint64_t n = 0, epoch = 0, added = 0;
-  bool ready = false, timed = false;
+  bool ready = false;
   DevBuf d_slots, d_cfirst, keys;
   DevBuf table;  // counts[n][2][5], then the first bad site of the reset (64 bits), then the adds' sticky error word
-  Events<2> ev;
+  Spans<1> sp;  // the last add
 
   size_t table_bytes() const { return (size_t)n * PILEUP_CELLS * 4u; }
   uint32_t* counts_p() const { return table.as<uint32_t>(); }
@@ -45,8 +45,9 @@ int simmr_pileup_reset(simmr_engine* e, const simmr_pileup_sites* sites) {
   if ((n + PILEUP_WG - 1) / PILEUP_WG >= (1ull << 31)) return eng_fail(e, SIMMR_ENOTSUP, "simmr_pileup_reset: too many sites for one launch");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   PileupState* s = pileup_state(e, true);
-  s->ready = s->timed = false;
-  if (int rc = s->ev.create_missing(e)) return rc;
+  s->ready = false;
+  s->sp.invalidate_from(0);
+  if (int rc = s->sp.create_missing(e)) return rc;
   // the dense layout of the genomes staged now: contig firsts, no padding (depth[]'s order)
   StagedRows rows = staged_rows(e);
   const uint32_t n_slots = rows.n_slots();
@@ -92,7 +93,7 @@ int simmr_pileup_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
     return eng_fail(e, SIMMR_ERANGE, "the reads added since simmr_pileup_reset would reach 2^31");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->sp.begin(0, st));
   if (n_reads > 0 && s->n > 0) {
     // persistent: eight waves per SIMD's worth of waves, each looping over its share of the 64-read batches
     const uint64_t batches = (n_reads + 63) / 64, wgs = (batches + PILEUP_WG / 64 - 1) / (PILEUP_WG / 64);
@@ -101,11 +102,11 @@ int simmr_pileup_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
     hipLaunchKernelGGL(k_pileup_add, dim3(grid), dim3(PILEUP_WG), 0, st, rd, n_reads, s->d_slots.as<const PileupSlot>(),
                        (uint32_t)s->slots.size(), s->d_cfirst.as<const uint64_t>(), s->keys.as<const uint64_t>(), s->n, s->counts_p(), s->err_p());
   }
-  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, s->sp.end(0, st));
   hipError_t rc = hipGetLastError();
   if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "pileup launch failed: %s", hipGetErrorString(rc));
   s->added += n_reads;
-  s->timed = true;
+  s->sp.mark(0);
   return SIMMR_OK;
 }
 
@@ -131,10 +132,8 @@ int simmr_pileup_read(simmr_engine* e, uint32_t* counts_device, uint64_t capacit
 int simmr_last_pileup_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
   PileupState* s = pileup_state(e, false);
-  if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_pileup_add yet");
-  if (int rc = sync_check(e, "pileup")) return rc;
-  HIP_TRY(e, hipEventElapsedTime(ms, s->ev[0], s->ev[1]));
-  return SIMMR_OK;
+  if (!s || !s->sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no simmr_pileup_add yet");
+  return s->sp.total_ms(e, "pileup", ms);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // read_walk.hpp — what a kernel needs to walk reads against the staged planes: the plane routines (fetch_codes16 ..
 // expand4, gather_piece: the emit kernels' funnel-shift addressing and code-domain reverse complement) and the read walker
-// (walk_open / walk_window) that k_truth, k_read_stats and k_fit_add share.  Plain device routines, no kernel: a translation
-// unit that includes this file keeps its own kernel budget (kernels.hip and truth_kernels.hip include it; so does
-// fit_kernels.hip, which must not see their kernels).
+// (walk_open / walk_window) that k_truth, k_read_stats and k_fit_add share, and the scan over a row of 16 lanes that the kernels
+// with a row per read use.  Plain device routines, no kernel: a translation unit that includes this file keeps its own kernel
+// budget (kernels.hip, truth_kernels.hip and fit_kernels.hip include it, and none of them sees another's kernels).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -207,6 +207,18 @@ SIMMR_DEV ReadWindow walk_window(const ReadWalk& w, uint32_t grp, const uint8_t*
   o.diff = (truth_nonzero_bytes(o.have.x ^ o.want.x) | truth_nonzero_bytes(o.have.y ^ o.want.y) << 4 |
             truth_nonzero_bytes(o.have.z ^ o.want.z) << 8 | truth_nonzero_bytes(o.have.w ^ o.want.w) << 12) & o.keep;
   return o;
+}
+
+// ---- a row of 16 lanes -------------------------------------------------------------------------------------------
+
+// inclusive scan of one u32 over each row of 16 lanes (every lane of the row active): four DPP row shifts, one v_add
+// with a DPP source each.  The row's last lane holds the row's sum.
+SIMMR_DEV uint32_t row_inclusive_scan_u32(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);   // row_shr:1
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);   // row_shr:2
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);   // row_shr:4
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);   // row_shr:8
+  return v;
 }
 
 }  // namespace simmr

@@ -32,8 +32,8 @@ struct RecordStreamState {
   SamEdits edits{};
   uint32_t paired = 0;
   uint64_t n_reads = 0, total = 0, epoch = 0;
-  bool ready = false, planned_once = false, emitted = false;
-  Events<4> ev;
+  bool ready = false;
+  Spans<2> sp;  // plan, emit
 
   uint32_t* err_p() const { return word.as<uint32_t>(); }
 };
@@ -49,7 +49,7 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
                 uint64_t* total_bytes) {
   if (!c) return SIMMR_EINVAL;
   simmr_engine* e = F::engine(c);
-  if (RecordStreamState* old = F::state(c, false)) old->ready = old->emitted = false;
+  if (RecordStreamState* old = F::state(c, false)) { old->ready = false; old->sp.invalidate_from(1); }
   if (int rc = check_plan_args(e, names, reads, truth, n_reads, paired, total_bytes, F::PLAN)) return rc;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   RecordStreamState* s = F::state(c, true);
@@ -63,7 +63,7 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
       return eng_fail(e, SIMMR_ERANGE, "%s: %llu named contigs, the longest of %llu bases: the key takes at most 2^24 contigs of fewer than 2^40 bases",
                       F::PLAN, (unsigned long long)s->nt.n_rows, (unsigned long long)s->nt.longest);
   [[maybe_unused]] const uint32_t key_bits = pos_bits + row_bits;
-  if (int rc = s->ev.create_missing(e)) return rc;
+  if (int rc = s->sp.create_missing(e)) return rc;
   const uint64_t n_chunks = (n_reads + SAM_CHUNK - 1) / SAM_CHUNK;
   [[maybe_unused]] const uint64_t n_tiles = (n_reads + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
   const uint64_t n1 = std::max<uint64_t>(n_reads, 1);
@@ -77,7 +77,7 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
   hipStream_t st = eng_stream(e);
   HIP_TRY(e, s->nt.upload(st, F::SORTED));
   HIP_TRY(e, hipMemsetAsync(s->word.p, 0, 16, st));
-  HIP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->sp.begin(0, st));
   const SamReads rd = sam_reads(reads);
   const SamEdits ed = sam_edits(truth);
   const uint32_t pr = paired ? 1u : 0u;
@@ -103,13 +103,13 @@ int record_plan(Ctx* c, const simmr_sam_names* names, const simmr_reads_out* rea
     F::scan(st, *s, n_chunks);
     F::offsets(st, grid, *s, s->len.as<const uint32_t>(), n_reads);
   }
-  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, s->sp.end(0, st));
   uint64_t total = 0;
   uint32_t errw = 0;
   HIP_TRY(e, hipMemcpyAsync(&total, s->off.as<uint64_t>() + n_reads, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, F::SYNC_SIZE)) return rc;
-  s->planned_once = true;
+  s->sp.mark(0);
   if (F::SORTED && (errw & 2u))
     return eng_fail(e, SIMMR_EINVAL, "a read's genome / contig has no name, or the read ends behind its contig's staged length");
   if (errw) return eng_fail(e, SIMMR_EINVAL, F::PLAN_REFUSAL, SAM_MAX_L);
@@ -132,7 +132,7 @@ int record_emit(Ctx* c, const simmr_reads_out* reads, const simmr_truth_out* tru
   simmr_engine* e = F::engine(c);
   if (!reads || !truth) return eng_fail(e, SIMMR_EINVAL, "%s: NULL argument", F::EMIT);
   RecordStreamState* s = F::state(c, false);
-  if (s) s->emitted = false;
+  if (s) s->sp.invalidate_from(1);
   SamReads now_r;  // (zeroed first, then field by field: the structs are compared as bytes, padding included)
   SamEdits now_e;
   std::memset(&now_r, 0, sizeof now_r);
@@ -148,7 +148,7 @@ int record_emit(Ctx* c, const simmr_reads_out* reads, const simmr_truth_out* tru
   if (s->total > 0 && !dst) return eng_fail(e, SIMMR_EINVAL, "%s: NULL dst", F::EMIT);
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, s->sp.begin(1, st));
   if (s->n_reads > 0) {
     const uint64_t n_batches = (s->n_reads + SAM_WG_READS - 1) / SAM_WG_READS;
     F::write(st, (uint32_t)std::min<uint64_t>(n_batches, (uint64_t)eng_cu_count(e) * SAM_WGS_PER_CU), *s, dst);
@@ -159,11 +159,11 @@ int record_emit(Ctx* c, const simmr_reads_out* reads, const simmr_truth_out* tru
   }
   if constexpr (F::SORTED)
     if (off_out) HIP_TRY(e, hipMemcpyAsync(off_out, s->off.p, (s->n_reads + 1) * 8, hipMemcpyDeviceToDevice, st));
-  HIP_TRY(e, hipEventRecord(s->ev[3], st));
+  HIP_TRY(e, s->sp.end(1, st));
   uint32_t errw = 0;
   HIP_TRY(e, hipMemcpyAsync(&errw, s->err_p(), 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, F::SYNC_WRITE)) return rc;
-  s->emitted = true;
+  s->sp.mark(1);
   if (errw) {
     s->ready = false;
     return eng_fail(e, SIMMR_EINVAL, "the columns changed since %s: a read failed the bounds check of the write pass (no store left its record)", F::PLAN);
@@ -177,13 +177,8 @@ int record_ms(Ctx* c, float* ms) {
   if (!c || !ms) return SIMMR_EINVAL;
   simmr_engine* e = F::engine(c);
   RecordStreamState* s = F::state(c, false);
-  if (!s || !s->planned_once) return eng_fail(e, SIMMR_ESTATE, "no %s yet", F::PLAN);
-  if (int rc = sync_check(e, F::TIMER)) return rc;
-  float a = 0.f, b = 0.f;
-  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->emitted) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
-  *ms = a + b;
-  return SIMMR_OK;
+  if (!s || !s->sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no %s yet", F::PLAN);
+  return s->sp.total_ms(e, F::TIMER, ms);
 }
 
 }  // namespace

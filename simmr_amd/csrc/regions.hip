@@ -16,7 +16,7 @@ namespace {
 
 struct RegionsState {
   // the plan in force: made for which layout of depth[] (staging epoch and reset), with which thresholds
-  bool planned = false, timed = false, emitted = false;
+  bool planned = false;
   uint64_t epoch = 0, resets = 0, min_len = 0;
   uint32_t min_depth = 0, n_contigs = 0;
   uint64_t n_positions = 0, n_runs = 0, n_regions = 0, n_bases = 0;
@@ -25,7 +25,7 @@ struct RegionsState {
   DevBuf run_start, run_end;  // sized from the counted runs
   DevBuf r_x, r_c, r_off;     // the region table, sized from the counted regions
   DevBuf table;               // RegionContig per tracked contig
-  Events<4> ev;               // plan, emit: begin / end
+  Spans<2> sp;                // plan, emit
 };
 
 constexpr auto regions_state = unit_state<RegionsState, ENG_EXT_REGIONS>;
@@ -56,7 +56,7 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
   if (L.n_positions > 0 && (!depth_device || ((uintptr_t)depth_device & 15u)))
     return eng_fail(e, SIMMR_EINVAL, "simmr_regions_plan: depth_device must be a 16-byte aligned device pointer");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = s->ev.create_missing(e)) return rc;
+  if (int rc = s->sp.create_missing(e)) return rc;
   hipStream_t st = eng_stream(e);
   const uint64_t n = L.n_positions, n_contigs = L.n_contigs;
   // the tracked contigs as the kernels see them (the slots are staged: the reset tracked them and nothing was staged since)
@@ -76,7 +76,7 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
     return eng_fail(e, SIMMR_ENOMEM, "region tile allocation failed (%llu tiles)", (unsigned long long)n_tiles);
   HIP_TRY(e, hipMemcpyAsync(s->table.p, table.data(), table.size() * sizeof(RegionContig), hipMemcpyHostToDevice, st));
   HIP_TRY(e, hipMemsetAsync(s->tile_count.p, 0, 2 * tops * 8, st));
-  HIP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->sp.begin(0, st));
   if (n > 0)
     hipLaunchKernelGGL(k_regions_count, dim3((uint32_t)n_tiles), dim3(REGIONS_WG), 0, st, depth_device, n, min_depth, L.cfirst_device,
                        (uint32_t)n_contigs, s->tile_count.as<uint64_t>(), tops);
@@ -117,7 +117,7 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
                        (uint32_t)n_contigs, nr, nb, s->r_x.as<uint64_t>(), s->r_c.as<uint32_t>(), s->r_off.as<uint64_t>());
   else
     HIP_TRY(e, hipMemsetAsync(s->r_off.p, 0, 8, st));
-  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, s->sp.end(0, st));
   if (int rc = sync_check(e, "region table")) return rc;
   s->epoch = L.epoch;
   s->resets = L.resets;
@@ -128,8 +128,9 @@ int simmr_regions_plan(simmr_engine* e, const uint32_t* depth_device, uint32_t m
   s->n_runs = n_runs;
   s->n_regions = *n_regions = nr;
   s->n_bases = *n_bases = nb;
-  s->planned = s->timed = true;
-  s->emitted = false;
+  s->planned = true;
+  s->sp.mark(0);
+  s->sp.invalidate_from(1);
   return SIMMR_OK;
 }
 
@@ -156,7 +157,7 @@ int simmr_regions_emit(simmr_engine* e, const uint32_t* depth_device, const simm
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   if (out->depth_sum && s->n_regions > 0) HIP_TRY(e, hipMemsetAsync(out->depth_sum, 0, s->n_regions * 8, st));
-  HIP_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, s->sp.begin(1, st));
   if (out->genome || out->contig || out->start || out->len || out->seq_off)
     hipLaunchKernelGGL(k_regions_columns, dim3((uint32_t)(s->n_regions / REGIONS_WG + 1)), dim3(REGIONS_WG), 0, st, s->r_x.as<const uint64_t>(),
                        s->r_c.as<const uint32_t>(), s->r_off.as<const uint64_t>(), s->table.as<const RegionContig>(), s->n_regions,
@@ -165,21 +166,16 @@ int simmr_regions_emit(simmr_engine* e, const uint32_t* depth_device, const simm
     hipLaunchKernelGGL(k_regions_bases, dim3((uint32_t)grid), dim3(REGIONS_WG), 0, st, depth_device, s->r_x.as<const uint64_t>(),
                        s->r_c.as<const uint32_t>(), s->r_off.as<const uint64_t>(), s->table.as<const RegionContig>(), s->n_regions, s->n_bases,
                        out->seq, (unsigned long long*)out->depth_sum);
-  HIP_TRY(e, hipEventRecord(s->ev[3], st));
-  s->emitted = true;
+  HIP_TRY(e, s->sp.end(1, st));
+  s->sp.mark(1);
   return sync_check(e, "region emit");
 }
 
 int simmr_last_regions_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
   RegionsState* s = regions_state(e, false);
-  if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_regions_plan yet");
-  if (int rc = sync_check(e, "regions")) return rc;
-  float a = 0.f, b = 0.f;
-  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->emitted) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
-  *ms = a + b;
-  return SIMMR_OK;
+  if (!s || !s->sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no simmr_regions_plan yet");
+  return s->sp.total_ms(e, "regions", ms);
 }
 
 }  // extern "C"

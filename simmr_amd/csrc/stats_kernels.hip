@@ -1,6 +1,6 @@
 // stats_kernels.hip — run statistics on the device (gfx950): quality, base and mismatch tables of the emitted reads,
-// as integer sums in a simmr_run_stats (include/simmr_hip.h states every table).  Included by engine.hip after
-// truth_kernels.hip; entry points simmr_stats_reset / simmr_stats_add / simmr_stats_read.
+// as integer sums in a simmr_run_stats (include/simmr_hip.h states every table).  Included by stats.hip behind
+// truth_host.hpp; entry points simmr_stats_reset / simmr_stats_add / simmr_stats_read.
 //
 // One kernel, k_read_stats, one pass over the columns.  It walks the reads with the walker of truth_kernels.hip
 // (walk_open / walk_window, shared with k_truth) — STATS_LANES = 16 lanes (one DPP row) share a read, a lane takes 16

@@ -14,12 +14,12 @@ namespace {
 
 struct StrainState {
   // the plan in force: which genome, at which staging epoch, with which draw
-  bool planned = false, timed = false, applied = false;
+  bool planned = false;
   uint32_t genome = 0;
   uint64_t epoch = 0, n_sites = 0, n_tiles = 0;
   StrainDraw draw{};
   DevBuf tile_count, tile_prefix;  // u32 per tile; u64 per tile and the total, both padded to whole scan iterations
-  Events<4> ev;                    // plan, apply: begin / end
+  Spans<2> sp;                     // plan, apply
 };
 
 constexpr auto strain_state = unit_state<StrainState, ENG_EXT_STRAIN>;
@@ -57,7 +57,7 @@ int simmr_strain_plan(simmr_engine* e, uint32_t genome_idx, double identity, uin
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   StrainState* s = strain_state(e, true);
   s->planned = false;
-  if (int rc = s->ev.create_missing(e)) return rc;
+  if (int rc = s->sp.create_missing(e)) return rc;
   // strain sites, version 1: the thresholds in integer arithmetic
   const uint64_t t32 = (uint64_t)((1.0 - identity) * 4294967296.0 + 0.5);  // at most 3 * 2^30
   s->draw = StrainDraw{(uint32_t)t32, (uint32_t)((t32 + 2) / 3), (uint32_t)((2 * t32 + 2) / 3), (uint32_t)seed, (uint32_t)(seed >> 32)};
@@ -69,21 +69,22 @@ int simmr_strain_plan(simmr_engine* e, uint32_t genome_idx, double identity, uin
     return eng_fail(e, SIMMR_ENOMEM, "strain tile allocation failed (%llu tiles)", (unsigned long long)s->n_tiles);
   hipStream_t st = eng_stream(e);
   HIP_TRY(e, hipMemsetAsync(s->tile_count.p, 0, std::max<uint64_t>(tops, 1) * 4, st));
-  HIP_TRY(e, hipEventRecord(s->ev[0], st));
+  HIP_TRY(e, s->sp.begin(0, st));
   if (s->n_tiles > 0)
     hipLaunchKernelGGL(k_strain_count, dim3((uint32_t)s->n_tiles), dim3(STRAIN_WG), 0, st, p.mask, p.contigs, p.n_contigs, p.plane_words,
                        s->draw, s->tile_count.as<uint32_t>());
   hipLaunchKernelGGL(k_strain_scan_tiles, dim3(1), dim3(STRAIN_WG), 0, st, s->tile_count.as<const uint32_t>(), s->tile_prefix.as<uint64_t>(),
                      s->n_tiles);
-  HIP_TRY(e, hipEventRecord(s->ev[1], st));
+  HIP_TRY(e, s->sp.end(0, st));
   uint64_t total = 0;
   HIP_TRY(e, hipMemcpyAsync(&total, (const uint64_t*)s->tile_prefix.p + tops, 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "strain count")) return rc;
   s->genome = genome_idx;
   s->epoch = eng_staging_epoch(e);
   s->n_sites = *n_sites = total;
-  s->planned = s->timed = true;
-  s->applied = false;
+  s->planned = true;
+  s->sp.mark(0);
+  s->sp.invalidate_from(1);
   return SIMMR_OK;
 }
 
@@ -104,27 +105,22 @@ int simmr_strain_apply(simmr_engine* e, uint32_t genome_idx, const simmr_strain_
   const Planes p = planes_of(e, genome_idx);
   hipStream_t st = eng_stream(e);
   s->planned = false;  // consumed: the planes are about to change
-  HIP_TRY(e, hipEventRecord(s->ev[2], st));
+  HIP_TRY(e, s->sp.begin(1, st));
   if (s->n_sites > 0)
     hipLaunchKernelGGL(k_strain_apply, dim3((uint32_t)s->n_tiles), dim3(STRAIN_WG), 0, st, p.packed, p.mask, p.contigs, p.n_contigs,
                        p.plane_words, s->draw, s->tile_prefix.as<const uint64_t>(), columns ? out->contig : nullptr,
                        columns ? out->pos : nullptr, columns ? out->ref : nullptr, columns ? out->alt : nullptr);
-  HIP_TRY(e, hipEventRecord(s->ev[3], st));
+  HIP_TRY(e, s->sp.end(1, st));
   eng_planes_rewritten(e);
-  s->applied = true;
+  s->sp.mark(1);
   return sync_check(e, "strain apply");
 }
 
 int simmr_last_strain_ms(simmr_engine* e, float* ms) {
   if (!e || !ms) return SIMMR_EINVAL;
   StrainState* s = strain_state(e, false);
-  if (!s || !s->timed) return eng_fail(e, SIMMR_ESTATE, "no simmr_strain_plan yet");
-  if (int rc = sync_check(e, "strain")) return rc;
-  float a = 0.f, b = 0.f;
-  HIP_TRY(e, hipEventElapsedTime(&a, s->ev[0], s->ev[1]));
-  if (s->applied) HIP_TRY(e, hipEventElapsedTime(&b, s->ev[2], s->ev[3]));
-  *ms = a + b;
-  return SIMMR_OK;
+  if (!s || !s->sp.valid[0]) return eng_fail(e, SIMMR_ESTATE, "no simmr_strain_plan yet");
+  return s->sp.total_ms(e, "strain", ms);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // truth_kernels.hip — ground truth per read (gfx950): which bases of an emitted read differ from the staged
-// reference, as counts (nm) and as CSR edit lists.  Included by engine.hip; entry points simmr_truth_plan /
+// reference, as counts (nm) and as CSR edit lists.  Included by truth.hip; entry points simmr_truth_plan /
 // simmr_truth_emit (include/simmr_hip.h states what an edit is).
 //
 // The pass is a DIFF of seq[] against the 2-bit planes, not a replay of the draws: it serves every profile, rng mode
@@ -19,7 +19,7 @@
 // The expected bytes come from gather_piece (the emit kernels' funnel-shift addressing and code-domain reverse
 // complement) and expand4; the comparison is bytewise, so 'N' and '-' need no special case.
 // The bounds check and the window loads are the read walker of read_walk.hpp (walk_open / walk_window), which k_read_stats
-// (stats_kernels.hip, included after this file) and k_fit_add (fit_kernels.hip, a unit of its own) use too.
+// (stats_kernels.hip, a unit of its own) and k_fit_add (fit_kernels.hip, a unit of its own) use too.
 #pragma once
 
 #include "read_walk.hpp"  // TruthReads and the read walker (walk_open / walk_window), shared with fit_kernels.hip

@@ -125,6 +125,10 @@ class Truth:
     n_reads: int
     n_edits: int
 
+    def pod(self) -> "_abi.TruthOut":
+        return _abi.TruthOut(self.nm.data_ptr(), self.edit_off.data_ptr(), self.edit_pos.data_ptr(), self.edit_ref.data_ptr(),
+                             self.edit_alt.data_ptr(), self.edit_qual.data_ptr(), self.n_reads, self.n_edits)
+
     def to_host(self) -> dict:
         n, m = self.n_reads, self.n_edits
         return {
@@ -218,9 +222,7 @@ class Mapeval:
         return key[:n].cpu().numpy().view(np.uint64), best[:n].cpu().numpy().view(np.uint32), hits[:n].cpu().numpy().view(np.uint32)
 
     def last_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_mapeval_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self.engine._ms(self.lib.simmr_last_mapeval_ms, self._h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -266,6 +268,12 @@ class Engine:
     def _check(self, rc: int):
         if rc != 0:
             raise SimmrError(rc, (self.lib.simmr_last_error(self._h) or b"").decode())
+
+    def _ms(self, fn, handle=None) -> float:
+        """what a simmr_last_*_ms call answers (`handle`: the object it is asked of, the engine by default)"""
+        ms = C.c_float()
+        self._check(fn(self._h if handle is None else handle, C.byref(ms)))
+        return ms.value
 
     @property
     def device(self):
@@ -458,9 +466,7 @@ class Engine:
         return out[:total]
 
     def last_fastq_plan_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_fastq_plan_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_fastq_plan_ms)
 
     # -- ground truth per read ------------------------------------------------------
     def truth_plan(self, reads: Reads) -> int:
@@ -482,16 +488,13 @@ class Engine:
                   edit_alt=torch.empty(max(m, 1), dtype=torch.uint8, device=self.device),
                   edit_qual=torch.empty(max(m, 1), dtype=torch.uint8, device=self.device),
                   n_reads=n, n_edits=m)
-        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
-                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), n, m)
+        out = t.pod()
         pod = reads.pod()
         self._check(self.lib.simmr_truth_emit(self._h, C.byref(pod), C.byref(out)))
         return t
 
     def last_truth_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_truth_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_truth_ms)
 
     # -- the true alignments as SAM text ---------------------------------------------
     def _sam_names(self, rnames):
@@ -510,8 +513,7 @@ class Engine:
         must have been emitted with qual_offset=33.  `truth`: what Engine.truth(reads) returned; made here if None."""
         torch = _torch()
         t = truth if truth is not None else self.truth(reads)
-        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
-                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        out = t.pod()
         sn = self._sam_names(rnames)
         pod = reads.pod()
         total = C.c_uint64(0)
@@ -522,9 +524,7 @@ class Engine:
         return text[: total.value]
 
     def last_sam_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_sam_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_sam_ms)
 
     def sam_sorted(self, reads: Reads, rnames, paired: bool, truth: Optional[Truth] = None, with_keys: bool = False):
         """The alignment lines of Engine.sam() in coordinate order (simmr_sam_sort_plan + simmr_sam_sort_emit): ascending by
@@ -533,8 +533,7 @@ class Engine:
         offsets (n_reads + 1)."""
         torch = _torch()
         t = truth if truth is not None else self.truth(reads)
-        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
-                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        out = t.pod()
         sn = self._sam_names(rnames)
         pod = reads.pod()
         total = C.c_uint64(0)
@@ -551,9 +550,7 @@ class Engine:
         return text[: total.value]
 
     def last_sam_sort_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_sam_sort_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_sam_sort_ms)
 
     # -- the true alignments as BAM records, and BGZF framing ------------------------------
     def bam(self, reads: Reads, rnames, paired: bool, truth: Optional[Truth] = None, framed: bool = True):
@@ -562,8 +559,7 @@ class Engine:
         simmr_amd.sam.bam_header(...), these blocks, and simmr_amd.sam.BGZF_EOF."""
         torch = _torch()
         t = truth if truth is not None else self.truth(reads)
-        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
-                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        out = t.pod()
         sn = self._sam_names(rnames)
         pod = reads.pod()
         total = C.c_uint64(0)
@@ -574,9 +570,7 @@ class Engine:
         return self.bgzf(rec[: total.value]) if framed else rec[: total.value]
 
     def last_bam_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_bam_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_bam_ms)
 
     def bgzf(self, data):
         """The bytes of a contiguous CUDA uint8 tensor as BGZF blocks with stored deflate blocks (simmr_bgzf_frame), without the
@@ -608,8 +602,7 @@ class Engine:
         from . import sam as _sam_py
         torch = _torch()
         t = truth if truth is not None else self.truth(reads)
-        out = _abi.TruthOut(t.nm.data_ptr(), t.edit_off.data_ptr(), t.edit_pos.data_ptr(), t.edit_ref.data_ptr(),
-                            t.edit_alt.data_ptr(), t.edit_qual.data_ptr(), t.n_reads, t.n_edits)
+        out = t.pod()
         h = self._bam_sort_handle()
         sn = self._sam_names(rnames)
         pod = reads.pod()
@@ -636,11 +629,9 @@ class Engine:
         return blocks, self.bai(key[:n], end[:n], rec_off, len(flat), base, ref_len=lengths)
 
     def last_bam_sort_ms(self) -> float:
-        ms = C.c_float()
         if getattr(self, "_bam_sort", None) is None:
             raise SimmrError(_abi.ESTATE, "no simmr_bam_sort_plan yet")
-        self._check(self.lib.simmr_last_bam_sort_ms(self._bam_sort, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_bam_sort_ms, self._bam_sort)
 
     def bai(self, key, end, rec_off, n_ref: int, base: int, ref_len=None):
         """The BAI index (simmr_bai_plan + simmr_bai_emit) of a coordinate-sorted record stream held as CUDA columns: key (int64,
@@ -723,9 +714,7 @@ class Engine:
         return out[:total] if text else cols
 
     def last_overlap_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_overlap_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_overlap_ms)
 
     # -- strain divergence ------------------------------------------------------------
     def strain_plan(self, genome_idx: int, identity: float, seed: int) -> int:
@@ -753,9 +742,7 @@ class Engine:
         return {"contig": host["contig"].view(np.uint32), "pos": host["pos"].view(np.uint64), "ref": host["ref"], "alt": host["alt"]}
 
     def last_strain_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_strain_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_strain_ms)
 
     # -- run statistics -------------------------------------------------------------
     def stats_reset(self):
@@ -774,9 +761,7 @@ class Engine:
         return {name: np.ctypeslib.as_array(getattr(st, name)).astype(np.uint64) for name, _ in _abi.RunStats._fields_}
 
     def last_stats_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_stats_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_stats_ms)
 
     # -- coverage depth ---------------------------------------------------------------
     def depth_reset(self) -> int:
@@ -839,9 +824,7 @@ class Engine:
         return out
 
     def last_depth_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_depth_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_depth_ms)
 
     # -- gold-standard assembly ---------------------------------------------------------
     REGION_COLUMNS = (("genome", np.uint32), ("contig", np.uint32), ("start", np.uint64), ("len", np.uint64),
@@ -878,9 +861,7 @@ class Engine:
         return res
 
     def last_regions_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_regions_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_regions_ms)
 
     # -- allele counts at listed sites ----------------------------------------------------
     def pileup_reset(self, genome, contig, pos) -> int:
@@ -918,9 +899,7 @@ class Engine:
         return out[: n * 10].cpu().numpy().view(np.uint32).reshape(n, 2, 5)
 
     def last_pileup_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_pileup_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_pileup_ms)
 
     # -- fitting an error model from a run ------------------------------------------------
     def fit_reset(self, k: int = 7, max_alt_kmers: int = 20, pair_capacity: int = 1 << 20):
@@ -987,9 +966,7 @@ class Engine:
         return m
 
     def last_fit_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_fit_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_fit_ms)
 
     # -- an aligner's SAM against the true alignments ---------------------------------------
     def mapeval(self, names, min_overlap_pct: int = 10) -> "Mapeval":
@@ -1032,9 +1009,7 @@ class Engine:
         self._check(self.lib.simmr_allreduce_counts(self._h, C.c_void_p(tensor.data_ptr()), int(tensor.numel())))
 
     def last_emit_kernel_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_emit_kernel_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_emit_kernel_ms)
 
     def emit_kernel_ms_mean(self, last_n: int) -> float:
         """Mean HIP-event time of the last `last_n` emits (one synchronisation; simmr_emit_kernel_ms_mean)."""
@@ -1043,6 +1018,4 @@ class Engine:
         return ms.value
 
     def last_plan_ms(self) -> float:
-        ms = C.c_float()
-        self._check(self.lib.simmr_last_plan_ms(self._h, C.byref(ms)))
-        return ms.value
+        return self._ms(self.lib.simmr_last_plan_ms)

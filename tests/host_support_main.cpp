@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <map>
 #include <string>
 #include <utility>
 #include <vector>
@@ -18,6 +19,10 @@ static long g_live_bufs = 0, g_live_events = 0, g_mallocs = 0, g_frees = 0, g_ev
 static bool g_fail_next_malloc = false, g_fail_next_event = false;
 static hipError_t g_pending = hipSuccess;  // the sticky error hipGetLastError reads and clears
 static size_t g_last_malloc_bytes = 0;
+static std::map<hipEvent_t, float> g_span_ms;  // what hipEventElapsedTime answers for a pair, by its begin event
+static std::vector<hipEvent_t> g_recorded;     // the events recorded, in order
+static long g_elapsed_calls = 0;
+static bool g_fail_next_elapsed = false;
 
 extern "C" {
 hipError_t hipMalloc(void** ptr, size_t size) {
@@ -54,6 +59,14 @@ hipError_t hipEventDestroy(hipEvent_t event) {
   return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t) { g_syncs++; return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t event, hipStream_t) { g_recorded.push_back(event); return hipSuccess; }
+hipError_t hipEventElapsedTime(float* ms, hipEvent_t start, hipEvent_t stop) {
+  g_elapsed_calls++;
+  if (g_fail_next_elapsed) { g_fail_next_elapsed = false; return hipErrorNotReady; }
+  if (!start || !stop || !g_span_ms.count(start)) return hipErrorInvalidHandle;
+  *ms = g_span_ms[start];
+  return hipSuccess;
+}
 const char* hipGetErrorString(hipError_t s) { return s == hipSuccess ? "no error" : "stub error"; }
 }
 
@@ -198,9 +211,75 @@ static void events_set(simmr_engine* e) {
   CHECK(g_live_events == before);
 }
 
+// Spans: only the marked pairs are read and summed; recording marks nothing; a failure is reported with the call's text
+static void spans(simmr_engine* e) {
+  const long before = g_live_events;
+  {
+    Spans<3> sp;
+    CHECK(hipEventCreate(&sp.ev[3]) == hipSuccess);
+    hipEvent_t const had = sp.ev[3];
+    long creates = g_event_creates;
+    g_fail_next_event = true;  // the first missing one cannot be made: reported, nothing made, the one that was there kept
+    CHECK(sp.create_missing(e) == SIMMR_ENODEV && e->err == "hipEventCreate(&ev) failed: stub error" && g_event_creates == creates);
+    CHECK(sp.ev[0] == nullptr && sp.ev[3] == had && g_live_events == before + 1);
+    (void)hipGetLastError();
+    CHECK(sp.create_missing(e) == SIMMR_OK && g_event_creates == creates + 5 && sp.ev[3] == had && g_live_events == before + 6);
+    CHECK(sp.create_missing(e) == SIMMR_OK && g_event_creates == creates + 5);  // none is missing
+    for (int i = 0; i < 3; i++) CHECK(!sp.valid[i]);
+    hipStream_t st = nullptr;
+    g_recorded.clear();
+    for (int i = 0; i < 3; i++) CHECK(sp.begin(i, st) == hipSuccess && sp.end(i, st) == hipSuccess);
+    CHECK(g_recorded.size() == 6);
+    for (int i = 0; i < 6; i++) CHECK(g_recorded[i] == sp.ev[i]);  // pair i is events 2i and 2i + 1
+    for (int i = 0; i < 3; i++) CHECK(!sp.valid[i]);               // recording marks nothing
+    g_span_ms[sp.ev[0]] = 1.5f;
+    g_span_ms[sp.ev[2]] = 0.25f;
+    g_span_ms[sp.ev[4]] = 8.f;
+    float ms = -1.f;
+    long calls = g_elapsed_calls, syncs = g_syncs;
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 0.f && g_elapsed_calls == calls && g_syncs == syncs + 1);  // none marked, none read
+    sp.mark(0);
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 1.5f && g_elapsed_calls == calls + 1);
+    sp.mark(2);
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 9.5f && g_elapsed_calls == calls + 3);  // 0 and 2, not 1
+    sp.mark(1);
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 9.75f);
+    sp.mark(2, false);
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 1.75f);
+    sp.mark(2);
+    sp.invalidate_from(1);
+    CHECK(sp.valid[0] && !sp.valid[1] && !sp.valid[2]);
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 1.5f);
+    sp.invalidate_from(3);  // from behind the last: nothing
+    CHECK(sp.valid[0]);
+    // the synchronisation is checked first, under the caller's name
+    g_pending = hipErrorOutOfMemory;
+    calls = g_elapsed_calls;
+    ms = -1.f;
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_ENODEV && e->err == "spans: stub error" && ms == -1.f && g_elapsed_calls == calls);
+    g_fail_next_elapsed = true;
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_ENODEV && ms == -1.f);
+    CHECK(e->err == "hipEventElapsedTime(&one, ev[2 * i], ev[2 * i + 1]) failed: stub error");
+    sp.invalidate_from(0);
+    CHECK(sp.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 0.f);
+    // a state moves with its events: what it is moved from destroys nothing
+    sp.mark(0);
+    Spans<3> to(std::move(sp));
+    for (int i = 0; i < 6; i++) CHECK(sp.ev[i] == nullptr && to.ev[i] != nullptr);
+    CHECK(to.ev[3] == had && to.valid[0] && !to.valid[1] && g_live_events == before + 6);
+    CHECK(to.total_ms(e, "spans", &ms) == SIMMR_OK && ms == 1.5f);
+    static_assert(!std::is_copy_constructible<Spans<3>>::value && !std::is_copy_assignable<Spans<3>>::value, "a set of spans does not copy");
+    Spans<1> one;  // never used: owns nothing
+  }
+  CHECK(g_live_events == before);
+  g_span_ms.clear();
+  g_recorded.clear();
+}
+
 struct UnitState {  // as a unit's state: buffers, an array of buffers, events, host members
   DevBuf a, b[2];
   Events<4> ev;
+  Spans<2> sp;
   std::vector<uint64_t> host = {1, 2, 3};
 };
 
@@ -211,8 +290,8 @@ static void state_in_a_slot(simmr_engine* e) {
   CHECK(s && e->slot[ENG_EXT_STRAIN] == s && e->destroy[ENG_EXT_STRAIN]);
   CHECK((unit_state<UnitState, ENG_EXT_STRAIN>(e, true)) == s && (unit_state<UnitState, ENG_EXT_STRAIN>(e, false)) == s);
   CHECK((unit_state<UnitState, ENG_EXT_DEPTH>(e, false)) == nullptr);  // another unit's slot
-  CHECK(s->a.ensure(100) && s->b[0].ensure(200) && s->b[1].ensure_slack(300) && s->ev.create_missing(e) == SIMMR_OK);
-  CHECK(live() == before + 3 + 4);
+  CHECK(s->a.ensure(100) && s->b[0].ensure(200) && s->b[1].ensure_slack(300) && s->ev.create_missing(e) == SIMMR_OK && s->sp.create_missing(e) == SIMMR_OK);
+  CHECK(live() == before + 3 + 4 + 4);
   // what simmr_engine_destroy does with a slot
   e->destroy[ENG_EXT_STRAIN](e->slot[ENG_EXT_STRAIN]);
   e->slot[ENG_EXT_STRAIN] = nullptr;
@@ -254,6 +333,7 @@ int main() {
   one_owner();
   vector_of_holders();
   events_set(&e);
+  spans(&e);
   state_in_a_slot(&e);
   sync_and_macro(&e);
   rows(&e);

@@ -135,7 +135,8 @@ def test_the_unit_is_built_without_a_slot_of_the_engine():
     assert make.count(" bam_index.hip bam.hip fit_sam.hip fit.hip overlap.hip sam_sort.hip sam.hip pileup.hip engine.hip depth.hip strain.hip regions.hip\n") == 2
     srcs = re.search(r"^SRCS = (.*)$", make, re.M).group(1).split()
     assert {"bam_index.hip", "bam_index_kernels.hip"} <= set(srcs)
-    assert "ENG_EXT_BAM = 9, ENG_EXT_COUNT = 10" in (CSRC / "engine_internal.hpp").read_text()
+    internal = (CSRC / "engine_internal.hpp").read_text()
+    assert "ENG_EXT_BAM = 9," in internal and "ENG_EXT_COUNT = 12" in internal
     unit = (CSRC / "bam_index.hip").read_text()
     assert "eng_ext_slot" not in unit and '#include "engine.hip"' not in unit and '#include "kernels.hip"' not in unit
     k = (CSRC / "bam_index_kernels.hip").read_text()

@@ -1,5 +1,5 @@
 """Build-time guard for the coverage-depth kernels (depth_kernels.hip), the second translation unit of libsimmr_hip.so, in
-the manner of tests/test_stats_resource_guard.py: a budget of six kernels of its own (engine.hip's 88 are asserted there),
+the manner of tests/test_stats_resource_guard.py: a budget of six kernels of its own (engine.hip's 85 are asserted there),
 no scratch, no AGPRs, and a mark kernel light enough for eight waves per SIMD."""
 import sys
 from pathlib import Path

@@ -36,4 +36,4 @@ def test_the_add_kernel_is_one_workgroup_per_cu(kernels):
 
 def test_engine_unit_keeps_its_kernels():
     import resource_usage
-    assert len(resource_usage.collect()) == 88
+    assert len(resource_usage.collect()) == 85

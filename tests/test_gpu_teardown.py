@@ -1,6 +1,8 @@
 """Closing an engine gives back everything it allocated.  The route taken is the one whose buffers no list named: a paired plan
 in the reference RNG mode, whose emit kernel does not write text, so simmr_emit_fastq builds the columns in buffers of the
-engine first (fd_seq and fd_qual of plan.total_bases bytes each, seven smaller ones, fq_hlen and fq_tpl_dev) and frames them."""
+engine first (fd_seq and fd_qual of plan.total_bases bytes each, seven smaller ones, fq_hlen and fq_tpl_dev) and frames them.
+Each cycle also takes the ground truth and the run statistics of a small shard, so the states of those two units, which live in
+slots of the engine, are part of what a close has to give back."""
 import pytest
 
 from simmr_amd import MinimalShortErrorProfile, _abi
@@ -32,6 +34,13 @@ def test_closed_engines_leave_no_device_memory_behind():
             text = eng.fastq_direct(FMT, names)
             assert text.numel() > 2 * info.total_bases
             del text
+            # the states the units keep in the engine's slots: truth.hip's and stats.hip's buffers and events go with the engine too
+            reads = eng.simulate_pe_reads_from_genome(0, prof, 2000, 42, qual_offset=33)
+            assert eng.truth(reads).n_edits > 0 and eng.last_truth_ms() > 0
+            eng.stats_reset()
+            eng.stats_add(reads, 2)
+            assert eng.stats()["reads"].sum() == reads.n_reads and eng.last_stats_ms() > 0
+            del reads
         finally:
             eng.close()
         torch.cuda.synchronize()

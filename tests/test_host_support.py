@@ -7,14 +7,14 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "simmr_amd" / "csrc"
-UNITS = ("engine.hip", "depth.hip", "strain.hip", "regions.hip", "pileup.hip", "sam.hip", "sam_sort.hip", "overlap.hip", "fit.hip", "fit_sam.hip",
+UNITS = ("engine.hip", "truth.hip", "stats.hip", "depth.hip", "strain.hip", "regions.hip", "pileup.hip", "sam.hip", "sam_sort.hip", "overlap.hip", "fit.hip", "fit_sam.hip",
          "bam.hip", "bam_index.hip", "mapeval.hip")
 
 
 def test_the_support_header_in_a_stand_alone_program_under_the_sanitizers(tmp_path):
     """tests/host_support_main.cpp: ensure keeps, grows and fails clean; the engine's slack; one owner through moves and swaps and
-    inside a vector; Events creates only what is missing; a state deleted through unit_state's hook leaves nothing alive.  The
-    exit status is the number of allocations and events still alive."""
+    inside a vector; Events creates only what is missing; Spans adds up exactly the spans that are marked; a state deleted
+    through unit_state's hook leaves nothing alive.  The exit status is the number of allocations and events still alive."""
     exe = tmp_path / "host_support_main"
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-D__HIP_PLATFORM_AMD__", f"-I{rocm}/include", "-fsanitize=address,undefined",
@@ -25,21 +25,31 @@ def test_the_support_header_in_a_stand_alone_program_under_the_sanitizers(tmp_pa
 
 
 def test_one_copy_of_the_plumbing():
-    """one DevBuf, one check macro, one sync_check, no unit-private state accessor or destroy hook; frees and event destroys
-    outside the header only where the thing freed is neither a DevBuf nor an Events set"""
+    """one DevBuf, one check macro, one sync_check, one Spans, no unit-private state accessor or destroy hook; frees and event
+    destroys outside the header only where the thing freed is neither a DevBuf nor an Events set; elapsed times read outside the
+    header only where the pair is not a unit's span; truth and statistics keep nothing in the engine"""
     files = {f.name: f.read_text() for f in CSRC.iterdir() if f.suffix in (".hip", ".hpp")}
     everything = "\n".join(files.values())
     assert len(re.findall(r"^\s*struct DevBuf\b", everything, re.M)) == 1 and "struct DevBuf {" in files["host_support.hpp"]
+    assert len(re.findall(r"^\s*(?:template\s*<[^>]*>\s*)?struct Spans\b", everything, re.M)) == 1 and "struct Spans {" in files["host_support.hpp"]
     assert re.findall(r"^\s*#\s*define\s+(\w*_TRY)\b", everything, re.M) == ["HIP_TRY"]
     assert len(re.findall(r"^\s*(?:inline\s+)?int \w*sync_check\(", everything, re.M)) == 1
     assert "state_of" not in everything and not re.search(r"\w+_destroy\(void\*", everything)
     for name in UNITS:
         assert '#include "host_support.hpp"' in files[name] or '#include "sam_names.hpp"' in files[name] or \
-            '#include "record_stream_host.hpp"' in files[name], name
+            '#include "record_stream_host.hpp"' in files[name] or '#include "truth_host.hpp"' in files[name], name
+    assert '#include "host_support.hpp"' in files["truth_host.hpp"]
     assert '#include "host_support.hpp"' in files["sam_names.hpp"] and '#include "sam_names.hpp"' in files["record_stream_host.hpp"]
     outside = {name: len(re.findall(r"\bhipFree\(|\bhipEventDestroy\(", text)) for name, text in files.items() if name != "host_support.hpp"}
     # engine.hip: the first event of a ring pair whose second could not be made; mapeval.hip: its growing list of spans
     assert {k: v for k, v in outside.items() if v} == {"engine.hip": 1, "mapeval.hip": 4}
+    elapsed = {name: len(re.findall(r"\bhipEventElapsedTime\(", text)) for name, text in files.items() if name != "host_support.hpp"}
+    # engine.hip: the plan's, the FASTQ plan's and the emit's pairs and the ring of emits, none of them a unit's span;
+    # overlap.hip: an emit call, measured call by call into a sum; mapeval.hip: its growing list of spans
+    assert {k: v for k, v in elapsed.items() if v} == {"engine.hip": 4, "overlap.hip": 1, "mapeval.hip": 2}
+    assert len(re.findall(r"\bhipEventElapsedTime\(", files["host_support.hpp"])) == 1
+    assert not re.search(r"\b(?:tr|st)_(?:nm|off|err|ev|ready|emitted|reads|edits|seq|seq_off|slot|tab|timed)\b", files["engine.hip"])
+    assert "truth_kernels.hip" not in files["engine.hip"] and "stats_kernels.hip" not in files["engine.hip"]
     for name in ("depth.hip", "pileup.hip", "overlap.hip", "sam_names.hpp"):
         assert "staged_rows(e" in files[name] and "eng_contig_len(" not in files[name], name
     make = (CSRC / "Makefile").read_text()

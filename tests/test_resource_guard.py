@@ -76,5 +76,5 @@ def test_other_bench_kernels(kernels):
 
 def test_library_size(kernels):
     """The forms that were measured and lost are not in the tree any more (git history keeps them)."""
-    assert len(kernels) <= 88, len(kernels)
+    assert len(kernels) <= 85, len(kernels)  # (88 before k_truth<> and k_read_stats left for units of their own)
     assert not _named(kernels, r"k_emit_philox_tile|k_emit_stream|k_fastq_headers")

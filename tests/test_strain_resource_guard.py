@@ -1,5 +1,5 @@
 """Build-time guard for the strain-divergence kernels (strain_kernels.hip), the third translation unit of libsimmr_hip.so, in
-the manner of tests/test_depth_resource_guard.py: a budget of four kernels of its own (engine.hip's 88 and depth.hip's six are
+the manner of tests/test_depth_resource_guard.py: a budget of four kernels of its own (engine.hip's 85 and depth.hip's six are
 asserted there), no scratch, no AGPRs, no spills, and draw kernels light enough for eight waves per SIMD."""
 import sys
 from pathlib import Path

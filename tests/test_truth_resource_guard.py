@@ -1,6 +1,6 @@
 """Build-time guard for the ground-truth kernels (truth_kernels.hip), in the manner of tests/test_resource_guard.py: one
-template, two instantiations (count, write), neither with scratch or AGPRs, both at four waves per SIMD or more, and
-the library within its budget of 88 kernels."""
+template, two instantiations (count, write), neither with scratch or AGPRs, both at four waves per SIMD or more; they are
+the two kernels of their unit, truth.hip, and engine.hip, which they left, stays within its budget of 85 kernels."""
 import re
 import sys
 from pathlib import Path
@@ -14,7 +14,7 @@ sys.path.insert(0, str(ROOT / "tools"))
 @pytest.fixture(scope="module")
 def kernels():
     import resource_usage
-    return resource_usage.collect()
+    return resource_usage.collect(source="truth.hip")
 
 
 def test_truth_kernels(kernels):
@@ -26,4 +26,7 @@ def test_truth_kernels(kernels):
 
 
 def test_library_size_with_the_truth_kernels(kernels):
-    assert len(kernels) <= 88, len(kernels)
+    import resource_usage
+    assert len(kernels) == 2, [k["name"] for k in kernels]
+    engine = resource_usage.collect()
+    assert len(engine) <= 85 and not [k for k in engine if "truth" in k["name"]], len(engine)
