@@ -1350,6 +1350,93 @@ int simmr_mapeval_emit(simmr_mapeval* h, uint64_t* key_dev, uint32_t* best_dev, 
 /* HIP-event time (ms) of the device work of every add and plan since the last reset.  Synchronises the stream. */
 int simmr_last_mapeval_ms(simmr_mapeval* h, float* ms);
 
+/* ---- an overlapper's PAF scored against the true overlaps: two texts in HBM, joined and classified on the device --------------
+ * Replaces nothing in the reference.  The other half of simmr_overlap_*: the truth (the text of simmr_overlap_emit, or any PAF
+ * that follows the rules below) and an all-vs-all overlapper's output for the same reads go in, and integer tables come out:
+ * the records that are correct and wrong and why, the true pairs found, missed and reported more than once, and found / not
+ * found by the true overlap's length.  No simulation, no genome: like simmr_mapeval_*.
+ *
+ * Text.  Whole lines of plain PAF (no gzip): every line ends in '\n', except that the last line of a call may lack it; the
+ * caller cuts a file at line ends, at most SIMMR_FIT_SAM_MAX_BYTES a call.  An empty line is skipped and not counted.  There are
+ * no header lines: every other line is a record.
+ *
+ * Record.  At least 12 tab-separated fields; further fields (tags) are not read:
+ *   1 query name, 2 query length, 3 query start, 4 query end, 5 strand, 6 target name, 7 target length, 8 target start,
+ *   9 target end, 10 matches, 11 block length, 12 mapping quality.
+ * Fields 2, 3, 4 and 7 to 12 are decimal numbers of 1 to 18 digits; field 5 is "+" or "-"; on both sides
+ * start <= end <= length < 2^40.
+ * Malformed (sticky; simmr_ovleval_read answers SIMMR_EINVAL, simmr_ovleval_truth_plan too for the truth), checked on every
+ * record before any filter: anything else in those fields.  A malformed line is counted in truth_lines / lines and not in
+ * truth_entries / records.
+ *
+ * Name and key.  A read name is a read id of 1 to 18 decimal digits, optionally followed by "/1" or "/2": exactly what
+ * simmr_overlap_emit writes.  mate = 1 iff the suffix is "/2".  key = id << 1 | mate.
+ *
+ * Truth record.  Both names must be read names and the two keys must differ; otherwise the record is malformed.  The entry is
+ * the unordered pair (lo_key, hi_key), lo_key < hi_key.  It holds the relative strand (field 5), the interval [start, end) of
+ * the lower-keyed read and that of the higher-keyed read, each in its own read's coordinates as PAF gives them, and
+ * ov = query end - query start.  Two entries with one pair: simmr_ovleval_truth_plan answers SIMMR_EINVAL.  The reads of the
+ * truth are the distinct keys of its entries.
+ *
+ * Candidate record, in this order (records counts every well-formed one):
+ *   1. Either name is not a read name, or its key is that of no read of the truth: unknown_read, and the record is wrong.
+ *   2. Both keys are equal: self, and the record is left out (neither correct nor wrong).
+ *   3. The pair is not an entry: no_pair, wrong.
+ *   4. The strand differs from the entry's: wrong_strand, wrong.
+ *   5. For each of the two reads the record's interval on that read is compared with the entry's: with ov = the length of the
+ *      intersection and un = max(ends) - min(starts), the comparison holds iff ov >= 1 and 100 * ov >= min_pct * un, in 64-bit
+ *      integers.  A candidate may name the pair in either order; its query interval goes with whichever read it names as
+ *      query.  If either read's comparison fails: wrong_interval, wrong.  Otherwise: correct.
+ *   6. Steps 4 and 5 give the entry a hit: hits[entry] += 1, best[entry] = max(best[entry], class), class 2 for wrong and 3 for
+ *      correct.
+ * wrong = unknown_read + no_pair + wrong_strand + wrong_interval; records = wrong + correct + self.
+ * Every output is an integer sum or maximum: the same for any launch geometry and any cut of either text into adds. */
+#define SIMMR_OVLEVAL_LEN_ROWS 41u   /* by_len: row b holds the entries whose ov has bit length b (0 for ov == 0; ov < 2^40) */
+
+typedef struct simmr_ovleval simmr_ovleval;
+
+typedef struct simmr_ovleval_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_lines, truth_entries, truth_reads;   /* cumulative since the reset; truth_reads: the distinct keys, made by the plan */
+  uint64_t lines, records;                            /* the candidate side, since the last truth plan */
+  uint64_t unknown_read, self, no_pair, wrong_strand, wrong_interval, correct, wrong;
+  uint64_t pairs_found, pairs_wrong, pairs_missed, pairs_multiple;   /* truth entries: best 3, best 2, no hit, more than one hit */
+} simmr_ovleval_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_mapeval_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error). */
+int simmr_ovleval_create(simmr_engine* e, simmr_ovleval** out);
+void simmr_ovleval_destroy(simmr_ovleval* h);
+/* Takes min_pct (1 .. 100; 0: the default, 10) and empties both sides.  Synchronises.  SIMMR_EINVAL: min_pct above 100. */
+int simmr_ovleval_reset(simmr_ovleval* h, uint32_t min_pct);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for an entry per 23 bytes of text (no record is shorter) grows with the
+ * object.  SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL text with n_bytes > 0.  SIMMR_ENOTSUP: n_bytes above
+ * SIMMR_FIT_SAM_MAX_BYTES. */
+int simmr_ovleval_truth_add(simmr_ovleval* h, const uint8_t* text, uint64_t n_bytes);
+/* Ranks the reads (the 2 n keys sorted by the radix sort of simmr_sam_sort_plan, their heads flagged and scanned: a dense rank
+ * below 2^31 per distinct key), sorts the entries by rank_lo << 31 | rank_hi, checks that no pair stands twice, empties the
+ * candidate side and synchronises.  *n_entries, *n_reads (either may be NULL) = the entries and the distinct keys.
+ * SIMMR_EINVAL: a malformed truth record, or two entries with one pair.  SIMMR_ERANGE: 2^30 entries or more. */
+int simmr_ovleval_truth_plan(simmr_ovleval* h, uint64_t* n_entries, uint64_t* n_reads);
+/* Scores the records of text[0 .. n_bytes) (DEVICE, as above) against the plan.  Only enqueues.  SIMMR_ESTATE: no truth plan
+ * in force.  SIMMR_EINVAL, SIMMR_ENOTSUP: as simmr_ovleval_truth_add. */
+int simmr_ovleval_add(simmr_ovleval* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts and by_len_host[SIMMR_OVLEVAL_LEN_ROWS][2] (HOST, either may be NULL): the truth entries by the bit length of
+ * their ov, [0] found (best 3) and [1] not found.  Synchronises.  The pairs_* counts and by_len are made here, by a reduction over
+ * best[], hits[] and ov[].  SIMMR_EINVAL: a malformed record on either side since the reset (nothing is written).
+ * SIMMR_ESTATE: no reset yet. */
+int simmr_ovleval_read(simmr_ovleval* h, simmr_ovleval_counts* counts, uint64_t* by_len_host);
+/* The truth entries, five columns (DEVICE, capacity entries each, any may be NULL): key_a < key_b the pair's keys, ov, best (0:
+ * no hit, 2: wrong, 3: correct), hits.  Entries ascend by (key_a, key_b): ranks are monotone in keys, so this is the sorted
+ * order, a function of the input.  Synchronises.  SIMMR_ESTATE: no truth plan.  SIMMR_ERANGE, nothing written:
+ * capacity < n_entries. */
+int simmr_ovleval_emit(simmr_ovleval* h, uint64_t* key_a_dev, uint64_t* key_b_dev, uint64_t* ov_dev, uint32_t* best_dev, uint32_t* hits_dev,
+                       uint64_t capacity);
+/* HIP-event time (ms) of the device work since the last reset: the truth adds, the plans and the adds.  Synchronises the stream.
+ * A run of adds with no synchronising call of this object between them (the plan or this call) is timed as one span,
+ * from the first add's start to the last one's end on the stream. */
+int simmr_last_ovleval_ms(simmr_ovleval* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

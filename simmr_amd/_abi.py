@@ -248,6 +248,16 @@ class MapevalCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in MAPEVAL_COUNTS]
 
 
+OVLEVAL_COUNTS = ("truth_lines", "truth_entries", "truth_reads", "lines", "records", "unknown_read", "self", "no_pair", "wrong_strand",
+                  "wrong_interval", "correct", "wrong", "pairs_found", "pairs_wrong", "pairs_missed", "pairs_multiple")
+OVLEVAL_LEN_ROWS = 41  # SIMMR_OVLEVAL_LEN_ROWS
+
+
+class OvlevalCounts(C.Structure):
+    """struct simmr_ovleval_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in OVLEVAL_COUNTS]
+
+
 class MapevalConfig(C.Structure):
     """struct simmr_mapeval_config (host memory)"""
     _fields_ = [("n_names", C.c_uint32), ("min_overlap_pct", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
@@ -386,6 +396,15 @@ SYMBOLS = {
     "simmr_mapeval_read": (C.c_int, [C.c_void_p, _P(MapevalCounts), _P(C.c_uint64)]),
     "simmr_mapeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_last_mapeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_ovleval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_ovleval_destroy": (None, [C.c_void_p]),
+    "simmr_ovleval_reset": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "simmr_ovleval_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_ovleval_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_ovleval_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_ovleval_read": (C.c_int, [C.c_void_p, _P(OvlevalCounts), _P(C.c_uint64)]),
+    "simmr_ovleval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_last_ovleval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

@@ -8,6 +8,7 @@
 #include <stddef.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "engine_internal.hpp"
@@ -51,6 +52,19 @@ struct DevBuf {
   bool ensure(size_t bytes) { return ensure(bytes, bytes); }
   // the engine's buffers, which are asked for a little more shard after shard: an eighth and 256 bytes of slack
   bool ensure_slack(size_t bytes) { return ensure(bytes, bytes + bytes / 8 + 256); }
+  // Room for `bytes` in a column that is appended to: a buffer that has to grow gets half as much again, and the first `keep`
+  // bytes of what it held are copied over on `st` (the free of the old one waits for the work enqueued on it, the copy included).
+  bool grow_keep(size_t bytes, size_t keep, hipStream_t st) {
+    if (bytes <= cap) return true;
+    DevBuf nb;
+    if (!nb.ensure(bytes, bytes + bytes / 2)) return false;
+    if (p && keep > 0 && hipMemcpyAsync(nb.p, p, std::min(keep, cap), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      (void)hipGetLastError();
+      return false;
+    }
+    *this = std::move(nb);
+    return true;
+  }
   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
   template <class T> T* as() const { return (T*)p; }
 };

@@ -27,19 +27,6 @@ namespace {
 
 uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
-// at least `bytes`, the first `keep` bytes of what it held copied over on `st`
-bool grow_keep(DevBuf* b, size_t bytes, size_t keep, hipStream_t st) {
-  if (bytes <= b->cap) return true;
-  DevBuf nb;
-  if (!nb.ensure(bytes, bytes + bytes / 2)) return false;
-  if (b->p && keep > 0 && hipMemcpyAsync(nb.p, b->p, std::min(keep, b->cap), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  *b = std::move(nb);  // (the free of what it held waits for the work enqueued on it, the copy included)
-  return true;
-}
-
 struct Span { hipEvent_t a = nullptr, b = nullptr; };
 
 }  // namespace
@@ -221,8 +208,8 @@ int simmr_mapeval_truth_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_by
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
   const uint64_t cap = h->entry_cap + n_bytes / MEV_MIN_LINE + 1, held = h->entry_cap;
-  if (!grow_keep(&h->u_key, cap * 8, held * 8, st) || !grow_keep(&h->u_meta, cap * 4, held * 4, st) || !grow_keep(&h->u_lo, cap * 8, held * 8, st) ||
-      !grow_keep(&h->u_hi, cap * 8, held * 8, st))
+  if (!h->u_key.grow_keep(cap * 8, held * 8, st) || !h->u_meta.grow_keep(cap * 4, held * 4, st) || !h->u_lo.grow_keep(cap * 8, held * 8, st) ||
+      !h->u_hi.grow_keep(cap * 8, held * 8, st))
     return eng_fail(e, SIMMR_ENOMEM, "mapeval truth: allocation failed for %llu entries", (unsigned long long)cap);
   h->entry_cap = cap;
   if (int rc = begin_span(h, st)) return rc;

@@ -1,6 +1,7 @@
 // mapeval_kernels.hip — an aligner's SAM scored against the true alignments (gfx950): two SAM texts in HBM to integer tables
 // (include/simmr_hip.h states every rule: the key, the interval, the verdict, what is malformed, the order of the filters).
-// Included by mapeval.hip alone, a translation unit of its own.  The SAM reader is fit_sam_kernels.hip's, taken as routines
+// Included by mapeval.hip, a translation unit of its own; and, with MEV_ROUTINES_ONLY defined, by ovleval_kernels.hip, which takes the
+// group search and the text's structs without the six kernels.  The SAM reader is fit_sam_kernels.hip's, taken as routines
 // (FSAM_ROUTINES_ONLY): the line index by tile counts and a chunked scan, a line per group of 16 lanes, the tabs from a ballot,
 // the CIGAR summed bytewise with fsam_cigar_lane.
 //
@@ -171,6 +172,9 @@ SIMMR_DEV MevLine mev_read_line(const uint8_t* __restrict__ t, uint64_t n, uint3
   return L;
 }
 
+// The kernels.  ovleval_kernels.hip (a translation unit of its own) includes this file with MEV_ROUTINES_ONLY defined and takes the
+// routines above without them, as this file takes fit_sam_kernels.hip's.
+#ifndef MEV_ROUTINES_ONLY
 // ---- the line index -----------------------------------------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(FSAM_WG)
 k_mev_index(const uint8_t* __restrict__ text, uint64_t n_bytes, uint64_t n_tiles, uint64_t* __restrict__ tile_sum,
@@ -328,5 +332,6 @@ k_mev_reduce(const uint32_t* __restrict__ best, const uint32_t* __restrict__ hit
 }
 
 #undef MEV_COUNT
+#endif  // MEV_ROUTINES_ONLY
 
 }  // namespace simmr

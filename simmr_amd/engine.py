@@ -233,6 +233,100 @@ class Mapeval:
                 self.engine._mapevals.remove(self)
 
 
+class OverlapEval:
+    """An overlapper's PAF scored against the true overlaps on the device (simmr_ovleval_*, include/simmr_hip.h states the rules).
+    truth_add() the truth text (what Engine.overlaps() gives), truth_plan(), add() the overlapper's text, then read() and pairs().
+    A text is bytes (copied up) or a contiguous CUDA uint8 tensor; the adds only enqueue, so every text is kept until a call that
+    synchronises."""
+
+    def __init__(self, engine: "Engine", min_pct: int = 10):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        self.n_entries = self.n_reads = 0
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_ovleval_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(min_pct)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, min_pct: int = 10):
+        if not 0 <= int(min_pct) < 2 ** 32:
+            raise ValueError("min_pct is 1 .. 100")
+        try:
+            self._check(self.lib.simmr_ovleval_reset(self._h, int(min_pct)))
+        finally:
+            self._texts = []  # the reset has synchronised
+        self.n_entries = self.n_reads = 0
+
+    def _text(self, text):
+        torch = _torch()
+        if isinstance(text, (bytes, bytearray, memoryview)):
+            host = np.frombuffer(bytes(text), dtype=np.uint8)
+            dev = self.engine.device
+            text = torch.from_numpy(host.copy()).to(dev) if host.size else torch.empty(0, dtype=torch.uint8, device=dev)
+        if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous():
+            raise ValueError("a PAF text is bytes or a contiguous CUDA uint8 tensor")
+        self._texts.append(text)
+        n = int(text.numel())
+        return C.c_void_p(text.data_ptr() if n else None), n
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_ovleval_truth_add(self._h, p, n))
+
+    def truth_plan(self):
+        """(true pairs, distinct reads among them)"""
+        n, r = C.c_uint64(0), C.c_uint64(0)
+        self.n_entries = self.n_reads = 0
+        try:
+            self._check(self.lib.simmr_ovleval_truth_plan(self._h, C.byref(n), C.byref(r)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_entries, self.n_reads = int(n.value), int(r.value)
+        return self.n_entries, self.n_reads
+
+    def add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_ovleval_add(self._h, p, n))
+
+    def read(self):
+        """(counts by the names of struct simmr_ovleval_counts, by_len as a (41, 2) uint64 array: found, not found)"""
+        c = _abi.OvlevalCounts()
+        by = np.zeros((_abi.OVLEVAL_LEN_ROWS, 2), dtype=np.uint64)
+        try:
+            self._check(self.lib.simmr_ovleval_read(self._h, C.byref(c), by.ctypes.data_as(C.POINTER(C.c_uint64))))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.OVLEVAL_COUNTS}, by
+
+    def pairs(self):
+        """The true pairs ascending by (key_a, key_b), as numpy arrays: key_a, key_b, ov (uint64), best, hits (uint32)"""
+        torch = _torch()
+        n, dev = self.n_entries, self.engine.device
+        wide = [torch.zeros(max(n, 1), dtype=torch.int64, device=dev) for _ in range(3)]
+        narrow = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(2)]
+        self._check(self.lib.simmr_ovleval_emit(self._h, *[C.c_void_p(t.data_ptr()) for t in wide + narrow], n))
+        self._texts = []
+        return tuple(t[:n].cpu().numpy().view(np.uint64) for t in wide) + tuple(t[:n].cpu().numpy().view(np.uint32) for t in narrow)
+
+    def last_ms(self) -> float:
+        return self.engine._ms(self.lib.simmr_last_ovleval_ms, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_ovleval_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
 class Engine:
     """One engine == one GPU == one host thread (include/simmr_hip.h)."""
 
@@ -973,6 +1067,16 @@ class Engine:
         """An evaluation object (simmr_mapeval_*): `names` are the reference names of both texts, in any order.  Closed by
         its close(), or by the engine's before the engine goes."""
         m = Mapeval(self, names, min_overlap_pct)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
+
+    # -- an overlapper's PAF against the true overlaps --------------------------------------
+    def overlap_eval(self, min_pct: int = 10) -> "OverlapEval":
+        """An evaluation object (simmr_ovleval_*).  Closed by its close(), or by the engine's before the engine goes (it is kept
+        in the list of the mapeval objects, which the engine closes first)."""
+        m = OverlapEval(self, min_pct)
         if not hasattr(self, "_mapevals"):
             self._mapevals = []
         self._mapevals.append(m)

@@ -765,6 +765,19 @@ std::string usage() {
          "                            the device; names as --sam's QNAME (the read id, /1 or /2 for pairs); columns 10 and 11 carry the\n"
          "                            length of the shared reference interval; not with --devices\n"
          "            --min-overlap <N>  shared reference bases from which two reads overlap [default: 1]\n"
+         "            --eval-overlaps <FILE>  no simulation: score an overlapper's PAF (plain text, as minimap2 -x ava-ont writes it) against the\n"
+         "                            true overlaps of --eval-overlaps-truth, joined by the two read names and classified on the device: a record\n"
+         "                            is correct when it names a true pair on the true relative strand and, on both reads, its interval and\n"
+         "                            the true one overlap by at least --eval-overlaps-min-pct percent of their union; takes only\n"
+         "                            --eval-overlaps-truth, --eval-overlaps-report, --eval-overlaps-pairs, --eval-overlaps-min-pct and --device\n"
+         "                            (no genomes, no --output, not --devices)\n"
+         "            --eval-overlaps-truth <FILE>  the file of --overlaps for the reads that were overlapped\n"
+         "            --eval-overlaps-report <FILE>  the result as a TSV: the counts as #name value lines, #sensitivity (true pairs found) and\n"
+         "                            #precision (records correct), then a row per bit length of the true overlap with pairs: L, bits, found,\n"
+         "                            not found\n"
+         "            --eval-overlaps-pairs <FILE>  every true pair: the two read names, the true overlap's length on the query, the class of its\n"
+         "                            best record (0 no record, 2 wrong, 3 correct), records\n"
+         "            --eval-overlaps-min-pct <PCT>  1 .. 100 [default: 10]\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -858,6 +871,37 @@ std::string mapeval_read_rows(const uint64_t* key, const uint32_t* best, const u
   return out;
 }
 
+std::string ovleval_report(const uint64_t* counts, const uint64_t* by_len) {
+  static const char* const NAMES[OVLEVAL_N_COUNTS] = {"truth_lines", "truth_entries", "truth_reads", "lines", "records", "unknown_read", "self", "no_pair",
+                                                      "wrong_strand", "wrong_interval", "correct", "wrong", "pairs_found", "pairs_wrong", "pairs_missed",
+                                                      "pairs_multiple"};
+  std::string out;
+  for (size_t i = 0; i < OVLEVAL_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + std::to_string((unsigned long long)counts[i]) + "\n";
+  auto ratio = [](uint64_t num, uint64_t den) -> std::string {
+    if (den == 0) return "0";
+    char text[64];
+    snprintf(text, sizeof text, "%.6f", (double)num / (double)den);
+    return text;
+  };
+  const uint64_t entries = counts[1], correct = counts[10], wrong = counts[11], found = counts[12];
+  out += "#sensitivity\t" + ratio(found, entries) + "\n";
+  out += "#precision\t" + ratio(correct, correct + wrong) + "\n";
+  for (size_t b = 0; b < OVLEVAL_LEN_ROWS; b++) {
+    if (by_len[2 * b] == 0 && by_len[2 * b + 1] == 0) continue;
+    out += "L\t" + std::to_string(b) + "\t" + std::to_string((unsigned long long)by_len[2 * b]) + "\t" + std::to_string((unsigned long long)by_len[2 * b + 1]) + "\n";
+  }
+  return out;
+}
+
+std::string ovleval_pair_rows(const uint64_t* key_a, const uint64_t* key_b, const uint64_t* ov, const uint32_t* best, const uint32_t* hits, size_t n) {
+  auto name = [](uint64_t key) { return std::to_string((unsigned long long)(key >> 1)) + (key & 1u ? "/2" : ""); };
+  std::string out;
+  for (size_t i = 0; i < n; i++)
+    out += name(key_a[i]) + "\t" + name(key_b[i]) + "\t" + std::to_string((unsigned long long)ov[i]) + "\t" + std::to_string(best[i]) + "\t" +
+           std::to_string(hits[i]) + "\n";
+  return out;
+}
+
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
   if (s.empty()) return false;
   char* end = nullptr;
@@ -869,7 +913,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other, first_not_eval, first_eval;
+  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -900,6 +944,10 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     const bool eval_flag = arg == "--eval-sam" || arg == "--eval-truth" || arg == "--eval-report" || arg == "--eval-reads" || arg == "--eval-min-overlap";
     if (eval_flag && first_eval.empty()) first_eval = arg;
     if (!eval_flag && arg != "--device" && first_not_eval.empty()) first_not_eval = arg;  // what --eval-sam does not take
+    const bool ovl_flag = arg == "--eval-overlaps" || arg == "--eval-overlaps-truth" || arg == "--eval-overlaps-report" || arg == "--eval-overlaps-pairs" ||
+                          arg == "--eval-overlaps-min-pct";
+    if (ovl_flag && first_ovl.empty()) first_ovl = arg;
+    if (!ovl_flag && arg != "--device" && first_not_ovl.empty()) first_not_ovl = arg;  // what --eval-overlaps does not take
     if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
     else if (arg == "--single-reads") a->single_reads = true;
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
@@ -956,6 +1004,11 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--eval-report") { if (!file(&a->eval_report)) return false; }
     else if (arg == "--eval-reads") { if (!file(&a->eval_reads)) return false; }
     else if (arg == "--eval-min-overlap") { if (!uint(1, 100, " (1 .. 100)")) return false; a->eval_min_overlap = (uint32_t)u; }
+    else if (arg == "--eval-overlaps") { if (!file(&a->eval_overlaps)) return false; }
+    else if (arg == "--eval-overlaps-truth") { if (!file(&a->eval_overlaps_truth)) return false; }
+    else if (arg == "--eval-overlaps-report") { if (!file(&a->eval_overlaps_report)) return false; }
+    else if (arg == "--eval-overlaps-pairs") { if (!file(&a->eval_overlaps_pairs)) return false; }
+    else if (arg == "--eval-overlaps-min-pct") { if (!uint(1, 100, " (1 .. 100)")) return false; a->eval_overlaps_min_pct = (uint32_t)u; }
     else if (arg == "--fit-max-alt") { if (!uint(1, UINT32_MAX, " (at least 1)")) return false; a->fit_max_alt = (uint32_t)u; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
@@ -1015,6 +1068,17 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     }
     if (a->eval_truth.empty()) { *err = "--eval-sam needs --eval-truth"; return false; }
     if (a->eval_report.empty()) { *err = "--eval-sam needs --eval-report"; return false; }
+    return true;
+  }
+  if (!first_ovl.empty()) {  // the third mode without a simulation
+    if (a->eval_overlaps.empty()) { *err = first_ovl + " needs --eval-overlaps"; return false; }
+    if (!first_not_ovl.empty()) {
+      *err = "--eval-overlaps runs no simulation: it takes only --eval-overlaps-truth, --eval-overlaps-report, --eval-overlaps-pairs, "
+             "--eval-overlaps-min-pct and --device ('" + first_not_ovl + "' given)";
+      return false;
+    }
+    if (a->eval_overlaps_truth.empty()) { *err = "--eval-overlaps needs --eval-overlaps-truth"; return false; }
+    if (a->eval_overlaps_report.empty()) { *err = "--eval-overlaps needs --eval-overlaps-report"; return false; }
     return true;
   }
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }

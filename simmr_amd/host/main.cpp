@@ -1185,6 +1185,82 @@ static int run_eval_sam(const CliArgs& args) {
   return 0;
 }
 
+// `--eval-overlaps CANDIDATE --eval-overlaps-truth TRUTH --eval-overlaps-report OUT`: no simulation.  Both files go up in pieces, the
+// truth through simmr_ovleval_truth_add and, behind the plan, the overlapper's through simmr_ovleval_add; the report is written from
+// the counts and by_len on the host.  Nothing is written unless all of it succeeded.
+struct OvlevalHandle {
+  simmr_ovleval* h = nullptr;
+  ~OvlevalHandle() { simmr_ovleval_destroy(h); }
+};
+static int run_eval_overlaps(const CliArgs& args) {
+  for (const auto& [flag, path] : {std::make_pair("--eval-overlaps-truth", &args.eval_overlaps_truth), std::make_pair("--eval-overlaps", &args.eval_overlaps)}) {
+    FILE* f = fopen(path->c_str(), "rb");  // (the files are looked at before an engine is made)
+    if (!f) return die(std::string(flag) + ": cannot open " + *path);
+    fclose(f);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  OvlevalHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_ovleval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
+  if (simmr_ovleval_reset(ev.h, args.eval_overlaps_min_pct) != SIMMR_OK) return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
+  float ms = 0;
+  info("Parsing " + args.eval_overlaps_truth);
+  if (int rc = sam_file_pieces("--eval-overlaps-truth", args.eval_overlaps_truth, [&](const uint8_t* d, size_t n) {
+        if (simmr_ovleval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_ovleval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
+          return die(std::string("--eval-overlaps-truth: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  uint64_t n_entries = 0, n_reads = 0;
+  if (simmr_ovleval_truth_plan(ev.h, &n_entries, &n_reads) != SIMMR_OK) return die(std::string("--eval-overlaps-truth: ") + simmr_last_error(eng));
+  info("Parsing " + args.eval_overlaps);
+  if (int rc = sam_file_pieces("--eval-overlaps", args.eval_overlaps, [&](const uint8_t* d, size_t n) {
+        if (simmr_ovleval_add(ev.h, d, n) != SIMMR_OK || simmr_last_ovleval_ms(ev.h, &ms) != SIMMR_OK)
+          return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  simmr_ovleval_counts c{};
+  static_assert(sizeof(c) == OVLEVAL_N_COUNTS * sizeof(uint64_t) && OVLEVAL_LEN_ROWS == SIMMR_OVLEVAL_LEN_ROWS, "the report names every count and row");
+  std::vector<uint64_t> by_len(2 * OVLEVAL_LEN_ROWS);
+  if (simmr_ovleval_read(ev.h, &c, by_len.data()) != SIMMR_OK) return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
+  std::string rows;
+  if (!args.eval_overlaps_pairs.empty()) {
+    GrowBuf d_wide, d_narrow;
+    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
+    uint8_t *w = d_wide.room(3 * n1 * 8), *nw = d_narrow.room(2 * n1 * 4);
+    if (!w || !nw) return die("--eval-overlaps-pairs: device allocation failed");
+    uint64_t* const wide = (uint64_t*)w;
+    uint32_t* const narrow = (uint32_t*)nw;
+    if (simmr_ovleval_emit(ev.h, wide, wide + n1, wide + 2 * n1, narrow, narrow + n1, n_entries) != SIMMR_OK)
+      return die(std::string("--eval-overlaps-pairs: ") + simmr_last_error(eng));
+    std::vector<uint64_t> hw(3 * n1);
+    std::vector<uint32_t> hn(2 * n1);
+    if (hipMemcpy(hw.data(), w, 3 * n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), nw, 2 * n1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
+      return die("--eval-overlaps-pairs: copy from the device failed");
+    rows = ovleval_pair_rows(hw.data(), hw.data() + n1, hw.data() + 2 * n1, hn.data(), hn.data() + n1, n_entries);
+  }
+  std::string err;
+  OutFile report(args.eval_overlaps_report, false);
+  report.append(ovleval_report((const uint64_t*)&c, by_len.data()));
+  if (!report.close(&err)) return die("--eval-overlaps-report: " + err);
+  if (!args.eval_overlaps_pairs.empty()) {
+    OutFile pairs(args.eval_overlaps_pairs, false);
+    pairs.append(rows);
+    if (!pairs.close(&err)) return die("--eval-overlaps-pairs: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_entries) + " pairs of " + n(c.truth_reads) + " reads");
+  info("Candidate: " + n(c.records) + " records: " + n(c.correct) + " correct, " + n(c.wrong) + " wrong (" + n(c.unknown_read) + " of unknown reads, " +
+       n(c.no_pair) + " of pairs that do not overlap, " + n(c.wrong_strand) + " on the other strand, " + n(c.wrong_interval) + " off the interval), " +
+       n(c.self) + " of a read with itself");
+  info("Pairs: " + n(c.pairs_found) + " found, " + n(c.pairs_wrong) + " reported wrong only, " + n(c.pairs_missed) + " missed, " + n(c.pairs_multiple) +
+       " reported more than once");
+  info("Wrote " + args.eval_overlaps_report);
+  return 0;
+}
 
 static int run_main(int argc, char** argv) {
   CliArgs args;
@@ -1194,6 +1270,7 @@ static int run_main(int argc, char** argv) {
   if (help) { fputs(usage().c_str(), stdout); return 0; }
   if (!args.fit_from_sam.empty()) return run_fit_from_sam(args);
   if (!args.eval_sam.empty()) return run_eval_sam(args);
+  if (!args.eval_overlaps.empty()) return run_eval_overlaps(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

@@ -164,6 +164,16 @@ std::string mapeval_report(const uint64_t* counts, const uint64_t* by_mapq);
 // The rows of --eval-reads for n truth entries in key order: id, mate bit, class (0 no record, 1 unmapped, 2 wrong), MAPQ and
 // records of every entry whose best class is not 3, tab-separated.
 std::string mapeval_read_rows(const uint64_t* key, const uint32_t* best, const uint32_t* hits, size_t n);
+// The file of --eval-overlaps-report: the counts of struct simmr_ovleval_counts as "#name\tvalue" lines in the struct's order
+// (counts[OVLEVAL_N_COUNTS]); "#sensitivity" = pairs_found / truth_entries and "#precision" = correct / (correct + wrong), with six
+// decimals, "0" where the denominator is 0; then a row per bit length with an entry in by_len[OVLEVAL_LEN_ROWS][2]: L, the bit
+// length of the true overlap, the pairs found, the pairs not found.
+constexpr size_t OVLEVAL_N_COUNTS = 16, OVLEVAL_LEN_ROWS = 41;
+std::string ovleval_report(const uint64_t* counts, const uint64_t* by_len);
+// The rows of --eval-overlaps-pairs for n truth entries in pair order: the two read names rebuilt from the keys (the id, and
+// "/2" where the mate bit is set: a key does not keep whether a name of mate 0 carried "/1"), ov, best (0 no record, 2 wrong,
+// 3 correct) and records, tab-separated.
+std::string ovleval_pair_rows(const uint64_t* key_a, const uint64_t* key_b, const uint64_t* ov, const uint32_t* best, const uint32_t* hits, size_t n);
 // `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
 // (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
 // ascend, and its text lies at `offset` of the byte source.
@@ -462,6 +472,11 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string eval_report;    // --eval-report FILE: the counts and the rows by MAPQ as a TSV
   std::string eval_reads;     // --eval-reads FILE: every truth read whose best record is not correct
   uint32_t eval_min_overlap = 0;  // --eval-min-overlap PCT: 1 .. 100 (0: not given, the library's default of 10)
+  std::string eval_overlaps;         // --eval-overlaps FILE: no simulation; an overlapper's PAF scored against the truth of --eval-overlaps-truth (simmr_ovleval_*)
+  std::string eval_overlaps_truth;   // --eval-overlaps-truth FILE: the true overlaps (the file of --overlaps)
+  std::string eval_overlaps_report;  // --eval-overlaps-report FILE: the counts, sensitivity, precision and the rows by overlap length as a TSV
+  std::string eval_overlaps_pairs;   // --eval-overlaps-pairs FILE: a row per true pair
+  uint32_t eval_overlaps_min_pct = 0;  // --eval-overlaps-min-pct PCT: 1 .. 100 (0: not given, the library's default of 10)
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions
