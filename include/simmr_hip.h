@@ -1437,6 +1437,120 @@ int simmr_ovleval_emit(simmr_ovleval* h, uint64_t* key_a_dev, uint64_t* key_b_de
  * from the first add's start to the last one's end on the stream. */
 int simmr_last_ovleval_ms(simmr_ovleval* h, float* ms);
 
+/* ---- a variant caller's VCF scored against the strain's sites: two texts in HBM, joined and classified on the device ----------
+ * Replaces nothing in the reference.  The third truth a run writes is the strain's sites (simmr_pileup_*, `--strain-vcf`): every
+ * substituted position with the allele counts the run's reads show there.  The truth (that VCF, or any VCF that follows the
+ * rules below) and a variant caller's VCF for the same reads go in, and integer tables come out: the calls correct and wrong and
+ * why, by QUAL; the sites found, missed and called more than once; and found / not found by the number of reads that showed the
+ * alternate base, which only the simulator knows.  No simulation, no genome: like simmr_mapeval_*.
+ *
+ * Text.  Whole lines of plain VCF (no gzip, no BCF): every line ends in '\n', except that the last line of a call may lack it;
+ * the caller cuts a file at line ends, at most SIMMR_FIT_SAM_MAX_BYTES a call.  An empty line is skipped and not counted.  A line
+ * that starts with '#' is a header line, counted and skipped.  Every other line is a record.
+ *
+ * Record.  At least 8 tab-separated fields: 1 CHROM, 2 POS, 3 ID, 4 REF, 5 ALT, 6 QUAL, 7 FILTER, 8 INFO.  Field 9 (FORMAT) and
+ * field 10 (the first sample) are read if present; further samples are not read.
+ * Malformed (sticky; simmr_vcfeval_read answers SIMMR_EINVAL, simmr_vcfeval_truth_plan too for the truth), checked on every
+ * record of either side before any filter: fewer than 8 fields; a POS that is not a decimal number of 1 to 18 digits, is 0 or is
+ * above 2^40; an empty REF or a REF with a byte outside ACGTNacgtn; an empty ALT; a QUAL that is neither "." nor
+ * [0-9]+(\.[0-9]*)?([eE][+-]?[0-9]{1,3})? with at most 18 digits before the point.
+ *
+ * Names and key.  The caller hands in the contig names once (simmr_vcfeval_config), under the rule and the limits of
+ * simmr_mapeval_reset; the library keeps them sorted in a device blob and resolves a CHROM by exact byte comparison.  The row of a
+ * name is its place in that order.  key = row << 40 | (POS - 1): rows are below 2^24, positions below 2^40.
+ *
+ * Truth record.  REF and ALT are one base each of ACGT (either case, folded to upper) and differ; CHROM is among the names;
+ * anything else is malformed on this side.  The entry holds the key, the ref class and the alt class (A C G T = 0 1 2 3) and
+ * ad_alt: the second number of the first ';'-separated item of INFO whose text starts with "AD=", which must be
+ * "AD=<r>,<a>" with r and a of 1 to 10 digits and a below 2^32 (anything else in that item is malformed); 0 where INFO has no
+ * such item.  Two entries with one key: simmr_vcfeval_truth_plan answers SIMMR_EINVAL.  FILTER and the sample columns are not
+ * read on this side.
+ *
+ * Candidate record, in this order (records counts every well-formed one):
+ *   1. Filtered.  FILTER is neither "." nor "PASS" and use_filtered is 0: counted filtered, and the record is left out.
+ *   2. The QUAL row.  qrow = min(255, floor(QUAL)), from the digits in integers: with n digits before the point and the exponent
+ *      e, the floor is the number that the first n + e digits spell — the digits before the point, then those behind it, then
+ *      zeros (none where n + e <= 0: row 0).  So a negative exponent shifts the point left and a positive one right through the
+ *      fraction digits; a value whose integer part passes three digits is row 255.  "." is row 0, and the record is also counted
+ *      qual_missing.
+ *   3. The called alleles.  ALT is a comma-separated list of n_alt alleles.  If the record has a FORMAT that is "GT" or starts
+ *      with "GT:" and a sample column, GT is the sample's text up to its first ':': items separated by '/' or '|', each "." or
+ *      a decimal number of 1 to 18 digits (any other item is malformed, and so is a number above n_alt).  The called alleles are
+ *      the ALT alleles whose 1-based index is among the numbers; a GT without a number of 1 or more is counted ref_call and the
+ *      record is left out.  Without such a FORMAT or without a sample column every ALT allele is called.
+ *   4. Each called allele, in ALT order, is one of:
+ *        "*", or an allele that starts with '<' or contains '[' or ']': counted symbolic, no call;
+ *        else a length other than REF's, or a byte outside ACGTNacgtn: counted indel, no call (the strain has substitutions
+ *          only: these are counted and never scored as right or wrong);
+ *        else a length L above 64: counted long_allele, no call;
+ *        else one CALL at every offset j < L where the upper-cased ALT byte differs from the upper-cased REF byte and both are
+ *          of ACGT: position POS + j, ref base REF[j], alt base ALT[j] (an SNV is L = 1, an MNP gives a call per changed base).
+ *          An allele whose upper-cased bytes all equal REF's is counted ref_call_allele.
+ *   5. A call's verdict (calls counts every call):
+ *        CHROM is not among the names: unknown_contig, wrong.
+ *        Else no entry has the key row << 40 | (POS + j - 1) (none can where POS + j - 1 reaches 2^40): no_site, wrong.
+ *        Else the call's ref class differs from the entry's: ref_mismatch, wrong, class 2.
+ *        Else the alt class differs: wrong_allele, wrong, class 2.                Else: correct, class 3.
+ *      by_qual[qrow][class 3 ? 0 : 1] counts every call, the first two kinds under wrong.  The last three verdicts give the
+ *      entry a hit: hits[entry] += 1, best[entry] = max(best[entry], class << 8 | qrow).
+ *   6. wrong = unknown_contig + no_site + ref_mismatch + wrong_allele, and calls = wrong + correct.
+ * Per truth entry, made by a reduction in simmr_vcfeval_read: sites_found (best's class is 3), sites_wrong (class 2),
+ * sites_missed (no hit), sites_multiple (hits > 1), and by_ad[SIMMR_VCFEVAL_AD_ROWS][2]: the entries by the bit length of ad_alt
+ * (0 for 0), [0] found and [1] not found — recall against the number of reads that showed the allele.
+ * The truth is haploid: a called allele is a call whatever its zygosity.
+ * Every output is an integer sum or maximum: the same for any launch geometry and any cut of either text into adds. */
+#define SIMMR_VCFEVAL_AD_ROWS 33u   /* by_ad: row b holds the entries whose ad_alt has bit length b (ad_alt < 2^32) */
+
+typedef struct simmr_vcfeval simmr_vcfeval;
+
+typedef struct simmr_vcfeval_config {   /* HOST memory */
+  uint32_t n_names;
+  uint32_t use_filtered;                /* 0: a record whose FILTER is neither "." nor "PASS" is left out; else: it is scored */
+  const char* const* rname;             /* n_names contig names, NUL-terminated, in any order */
+} simmr_vcfeval_config;
+
+typedef struct simmr_vcfeval_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_lines, truth_header, truth_entries;   /* lines = header + records; cumulative since the reset */
+  uint64_t lines, header, records;                     /* the candidate side, since the last truth plan */
+  uint64_t filtered, qual_missing, ref_call;           /* records */
+  uint64_t symbolic, indel, long_allele, ref_call_allele;   /* called alleles that give no call */
+  uint64_t calls, unknown_contig, no_site, ref_mismatch, wrong_allele, correct, wrong;
+  uint64_t sites_found, sites_wrong, sites_missed, sites_multiple;   /* truth entries: best class 3, class 2, no hit, more than one hit */
+} simmr_vcfeval_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_mapeval_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error). */
+int simmr_vcfeval_create(simmr_engine* e, simmr_vcfeval** out);
+void simmr_vcfeval_destroy(simmr_vcfeval* h);
+/* Takes the names and use_filtered, and empties both sides.  Synchronises.  SIMMR_EINVAL: a NULL argument, a name given twice.
+ * SIMMR_ENOTSUP: a name that is empty, longer than 254 bytes or no SAM reference name.  SIMMR_ERANGE: more than 2^24 names. */
+int simmr_vcfeval_reset(simmr_vcfeval* h, const simmr_vcfeval_config* cfg);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for an entry per 15 bytes of text (no record is shorter: 8 one-byte fields
+ * and 7 tabs) grows with the object.  SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL text with n_bytes > 0.  SIMMR_ENOTSUP:
+ * n_bytes above SIMMR_FIT_SAM_MAX_BYTES. */
+int simmr_vcfeval_truth_add(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes);
+/* Sorts the entries by key (the radix sort of simmr_sam_sort_plan, over the bits of the largest key), checks that no key stands
+ * twice, empties the candidate side and synchronises.  *n_entries (may be NULL) = the entries.  SIMMR_EINVAL: a malformed truth
+ * record, or two entries with one key.  SIMMR_ERANGE: 2^31 entries or more. */
+int simmr_vcfeval_truth_plan(simmr_vcfeval* h, uint64_t* n_entries);
+/* Scores the records of text[0 .. n_bytes) (DEVICE, as above) against the plan.  Only enqueues.  SIMMR_ESTATE: no truth plan
+ * in force.  SIMMR_EINVAL, SIMMR_ENOTSUP: as simmr_vcfeval_truth_add. */
+int simmr_vcfeval_add(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts, by_qual_host[256][2] (the calls by QUAL row, [0] correct and [1] wrong) and by_ad_host[SIMMR_VCFEVAL_AD_ROWS][2]
+ * (HOST, any may be NULL).  Synchronises.  The sites_* counts and by_ad are made here, by a reduction over best[], hits[] and
+ * ad[].  SIMMR_EINVAL: a malformed record on either side since the reset (nothing is written).  SIMMR_ESTATE: no reset yet. */
+int simmr_vcfeval_read(simmr_vcfeval* h, simmr_vcfeval_counts* counts, uint64_t* by_qual_host, uint64_t* by_ad_host);
+/* The truth entries in ascending key order (unique keys: the order is a function of the input), five columns (DEVICE, capacity
+ * entries each, any may be NULL): key, alleles = ref class << 2 | alt class, ad = ad_alt, best = the maximum over the entry's
+ * hits of class << 8 | qrow (0: no hit), hits.  Synchronises.  SIMMR_ESTATE: no truth plan.  SIMMR_ERANGE, nothing written:
+ * capacity < n_entries. */
+int simmr_vcfeval_emit(simmr_vcfeval* h, uint64_t* key_dev, uint32_t* alleles_dev, uint32_t* ad_dev, uint32_t* best_dev, uint32_t* hits_dev,
+                       uint64_t capacity);
+/* HIP-event time (ms) of the device work since the last reset: the truth adds, the plans and the adds.  Synchronises the stream.
+ * A run of adds with no synchronising call of this object between them (the plan or this call) is timed as one span. */
+int simmr_last_vcfeval_ms(simmr_vcfeval* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,22 @@ class OvlevalCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in OVLEVAL_COUNTS]
 
 
+VCFEVAL_COUNTS = ("truth_lines", "truth_header", "truth_entries", "lines", "header", "records", "filtered", "qual_missing", "ref_call", "symbolic",
+                  "indel", "long_allele", "ref_call_allele", "calls", "unknown_contig", "no_site", "ref_mismatch", "wrong_allele", "correct", "wrong",
+                  "sites_found", "sites_wrong", "sites_missed", "sites_multiple")
+VCFEVAL_AD_ROWS = 33  # SIMMR_VCFEVAL_AD_ROWS
+
+
+class VcfevalCounts(C.Structure):
+    """struct simmr_vcfeval_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in VCFEVAL_COUNTS]
+
+
+class VcfevalConfig(C.Structure):
+    """struct simmr_vcfeval_config (host memory)"""
+    _fields_ = [("n_names", C.c_uint32), ("use_filtered", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
+
+
 class MapevalConfig(C.Structure):
     """struct simmr_mapeval_config (host memory)"""
     _fields_ = [("n_names", C.c_uint32), ("min_overlap_pct", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
@@ -405,6 +421,15 @@ SYMBOLS = {
     "simmr_ovleval_read": (C.c_int, [C.c_void_p, _P(OvlevalCounts), _P(C.c_uint64)]),
     "simmr_ovleval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_last_ovleval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_vcfeval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_vcfeval_destroy": (None, [C.c_void_p]),
+    "simmr_vcfeval_reset": (C.c_int, [C.c_void_p, _P(VcfevalConfig)]),
+    "simmr_vcfeval_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_vcfeval_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "simmr_vcfeval_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_vcfeval_read": (C.c_int, [C.c_void_p, _P(VcfevalCounts), _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_vcfeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_last_vcfeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 // engine_internal.hpp — what another translation unit of libsimmr_hip.so (truth.hip, stats.hip, depth.hip, strain.hip, regions.hip,
-// pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip, fit_sam.hip, bam.hip, bam_index.hip, mapeval.hip, ovleval.hip) may ask of an engine.
+// pileup.hip, sam.hip, sam_sort.hip, overlap.hip, fit.hip, fit_sam.hip, bam.hip, bam_index.hip, mapeval.hip, ovleval.hip, vcfeval.hip) may
+// ask of an engine.
 // simmr_engine is defined in engine.hip alone; these accessors are defined there and hidden, so the library exports nothing but the
 // C ABI.  The host plumbing over these accessors that every unit uses, engine.hip too (the owning DevBuf and Events, the Spans that
 // time a unit's calls, HIP_TRY, sync_check, unit_state, staged_rows), is host_support.hpp, which includes this file.

@@ -327,6 +327,105 @@ class OverlapEval:
                 self.engine._mapevals.remove(self)
 
 
+class VcfEval:
+    """A variant caller's VCF scored against the strain's sites on the device (simmr_vcfeval_*, include/simmr_hip.h states the
+    rules).  truth_add() the truth text (the file of --strain-vcf), truth_plan(), add() the caller's text, then read() and sites().
+    A text is bytes (copied up) or a contiguous CUDA uint8 tensor; the adds only enqueue, so every text is kept until a call that
+    synchronises."""
+
+    def __init__(self, engine: "Engine", names, use_filtered: bool = False):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        self.n_entries = 0
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_vcfeval_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(names, use_filtered)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, names, use_filtered: bool = False):
+        raw = [n if isinstance(n, bytes) else str(n).encode() for n in names]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        cfg = _abi.VcfevalConfig(len(raw), 1 if use_filtered else 0, arr)
+        try:
+            self._check(self.lib.simmr_vcfeval_reset(self._h, C.byref(cfg)))
+        finally:
+            self._texts = []  # the reset has synchronised
+        self.n_entries = 0
+
+    _text = Mapeval._text
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_vcfeval_truth_add(self._h, p, n))
+
+    def truth_plan(self) -> int:
+        n = C.c_uint64(0)
+        self.n_entries = 0
+        try:
+            self._check(self.lib.simmr_vcfeval_truth_plan(self._h, C.byref(n)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_entries = int(n.value)
+        return self.n_entries
+
+    def add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_vcfeval_add(self._h, p, n))
+
+    def read(self):
+        """(counts by the names of struct simmr_vcfeval_counts, by_qual as a (256, 2) uint64 array: correct, wrong, by_ad as a
+        (33, 2) uint64 array: found, not found)"""
+        c = _abi.VcfevalCounts()
+        by_qual = np.zeros((256, 2), dtype=np.uint64)
+        by_ad = np.zeros((_abi.VCFEVAL_AD_ROWS, 2), dtype=np.uint64)
+        try:
+            self._check(self.lib.simmr_vcfeval_read(self._h, C.byref(c), by_qual.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                    by_ad.ctypes.data_as(C.POINTER(C.c_uint64))))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.VCFEVAL_COUNTS}, by_qual, by_ad
+
+    def sites(self):
+        """The truth entries ascending by key, as numpy arrays: key (uint64), alleles, ad, best, hits (uint32)"""
+        torch = _torch()
+        n, dev = self.n_entries, self.engine.device
+        key = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        narrow = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(4)]
+        self._check(self.lib.simmr_vcfeval_emit(self._h, *[C.c_void_p(t.data_ptr()) for t in [key] + narrow], n))
+        self._texts = []
+        return (key[:n].cpu().numpy().view(np.uint64),) + tuple(t[:n].cpu().numpy().view(np.uint32) for t in narrow)
+
+    def last_ms(self) -> float:
+        return self.engine._ms(self.lib.simmr_last_vcfeval_ms, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_vcfeval_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
+def cut_at_line_ends(text: bytes, pieces: int):
+    """`text` in at most `pieces` parts of about one size, each cut behind a newline"""
+    out, a = [], 0
+    for i in range(1, pieces):
+        b = text.find(b"\n", max(a, len(text) * i // pieces - 1)) + 1
+        if b <= a:
+            break
+        out.append(text[a:b])
+        a = b
+    return out + [text[a:]]
+
+
 class Engine:
     """One engine == one GPU == one host thread (include/simmr_hip.h)."""
 
@@ -1081,6 +1180,37 @@ class Engine:
             self._mapevals = []
         self._mapevals.append(m)
         return m
+
+    # -- a variant caller's VCF against the strain's sites ----------------------------------
+    def vcf_eval_open(self, names, use_filtered: bool = False) -> "VcfEval":
+        """An evaluation object (simmr_vcfeval_*) over the contig names.  Closed by its close(), or by the engine's before the
+        engine goes (it is kept in the list of the mapeval objects, which the engine closes first)."""
+        m = VcfEval(self, names, use_filtered)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
+
+    def vcf_eval(self, truth, calls, names, use_filtered: bool = False, pieces=None):
+        """Scores the VCF text `calls` against the truth VCF `truth` (each bytes, a CUDA uint8 tensor, or a list of those: an add
+        each; with `pieces`, a bytes text goes up in that many adds cut at line ends).  Returns (counts as a dict, by_qual
+        (256, 2), by_ad (33, 2), (key, alleles, ad, best, hits) of the truth entries in key order)."""
+        def adds(text):
+            texts = list(text) if isinstance(text, (list, tuple)) else [text]
+            if pieces:
+                texts = [part for t in texts for part in (cut_at_line_ends(bytes(t), int(pieces)) if isinstance(t, (bytes, bytearray, memoryview)) else [t])]
+            return texts
+        ev = self.vcf_eval_open(names, use_filtered)
+        try:
+            for t in adds(truth):
+                ev.truth_add(t)
+            ev.truth_plan()
+            for t in adds(calls):
+                ev.add(t)
+            counts, by_qual, by_ad = ev.read()
+            return counts, by_qual, by_ad, ev.sites()
+        finally:
+            ev.close()
 
     # -- counters / timing --------------------------------------------------------
     def counters(self) -> np.ndarray:

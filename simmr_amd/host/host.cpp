@@ -778,6 +778,20 @@ std::string usage() {
          "            --eval-overlaps-pairs <FILE>  every true pair: the two read names, the true overlap's length on the query, the class of its\n"
          "                            best record (0 no record, 2 wrong, 3 correct), records\n"
          "            --eval-overlaps-min-pct <PCT>  1 .. 100 [default: 10]\n"
+         "            --eval-vcf <FILE>  no simulation: score a variant caller's VCF (plain text, as bcftools call -mv writes it) against the strain's\n"
+         "                            sites of --eval-vcf-truth, joined by contig and position and classified on the device: a call is an\n"
+         "                            ALT base that differs from REF (an MNP gives one per changed base; of the first sample's GT only the\n"
+         "                            called alleles count), correct when the site exists with that reference and alternate base; indels and\n"
+         "                            symbolic alleles are counted and not scored; takes only --eval-vcf-truth, --eval-vcf-report,\n"
+         "                            --eval-vcf-sites, --eval-vcf-filtered and --device (no genomes, no --output, not --devices)\n"
+         "            --eval-vcf-truth <FILE>  the file of --strain-vcf for the reads that were called; its ##contig lines name the contigs\n"
+         "            --eval-vcf-report <FILE>  the result as a TSV: the counts as #name value lines, #precision (calls correct) and #recall\n"
+         "                            (sites found) as fractions and percentages, a Q row per QUAL row with calls from 255 downward with\n"
+         "                            the cumulative precision and correct calls per site, an AD row per bit length of the reads that\n"
+         "                            showed the alternate base: found, not found\n"
+         "            --eval-vcf-sites <FILE>  every true site: contig, position, ref, alt, reads that showed alt, the class of its best call\n"
+         "                            (0 no call, 2 wrong, 3 correct), that call's QUAL row, calls\n"
+         "            --eval-vcf-filtered  score the records whose FILTER is neither . nor PASS too\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -902,6 +916,64 @@ std::string ovleval_pair_rows(const uint64_t* key_a, const uint64_t* key_b, cons
   return out;
 }
 
+void vcfeval_contig_names(const char* text, size_t n, std::vector<std::string>* names) {
+  static const char KEY[] = "##contig=<ID=";
+  const size_t k = sizeof KEY - 1;
+  for (size_t a = 0; a < n;) {
+    size_t b = a;
+    while (b < n && text[b] != '\n') b++;
+    if (b - a > k && memcmp(text + a, KEY, k) == 0) {
+      size_t e = a + k;
+      while (e < b && text[e] != ',' && text[e] != '>') e++;
+      if (e > a + k) names->emplace_back(text + a + k, e - (a + k));
+    }
+    a = b + 1;
+  }
+}
+
+std::string vcfeval_report(const uint64_t* counts, const uint64_t* by_qual, const uint64_t* by_ad) {
+  static const char* const NAMES[VCFEVAL_N_COUNTS] = {"truth_lines", "truth_header", "truth_entries", "lines", "header", "records", "filtered", "qual_missing",
+                                                      "ref_call", "symbolic", "indel", "long_allele", "ref_call_allele", "calls", "unknown_contig", "no_site",
+                                                      "ref_mismatch", "wrong_allele", "correct", "wrong", "sites_found", "sites_wrong", "sites_missed",
+                                                      "sites_multiple"};
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  std::string out;
+  for (size_t i = 0; i < VCFEVAL_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + n(counts[i]) + "\n";
+  auto frac = [&](uint64_t num, uint64_t den) -> std::string {
+    char text[64] = "0";
+    if (den != 0) snprintf(text, sizeof text, "%.4f", 100.0 * (double)num / (double)den);
+    return n(num) + "/" + n(den) + "\t" + text;
+  };
+  const uint64_t entries = counts[2], calls = counts[13], correct = counts[18], found = counts[20];
+  out += "#precision\t" + frac(correct, calls) + "\n";
+  out += "#recall\t" + frac(found, entries) + "\n";
+  uint64_t cum_correct = 0, cum_calls = 0;
+  for (size_t q = 256; q-- > 0;) {
+    if (by_qual[2 * q] == 0 && by_qual[2 * q + 1] == 0) continue;
+    cum_correct += by_qual[2 * q];
+    cum_calls += by_qual[2 * q] + by_qual[2 * q + 1];
+    out += "Q\t" + std::to_string(q) + "\t" + n(by_qual[2 * q]) + "\t" + n(by_qual[2 * q + 1]) + "\t" + frac(cum_correct, cum_calls) + "\t" +
+           frac(cum_correct, entries) + "\n";
+  }
+  for (size_t b = 0; b < VCFEVAL_AD_ROWS; b++) {
+    if (by_ad[2 * b] == 0 && by_ad[2 * b + 1] == 0) continue;
+    out += "AD\t" + std::to_string(b) + "\t" + n(by_ad[2 * b]) + "\t" + n(by_ad[2 * b + 1]) + "\n";
+  }
+  return out;
+}
+
+std::string vcfeval_site_rows(const std::vector<std::string>& names, const uint64_t* key, const uint32_t* alleles, const uint32_t* ad, const uint32_t* best,
+                              const uint32_t* hits, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++) {
+    const uint64_t row = key[i] >> 40, pos = (key[i] & ((1ull << 40) - 1)) + 1;
+    out += row < names.size() ? names[row] : std::string("?");
+    out += "\t" + std::to_string((unsigned long long)pos) + "\t" + "ACGT"[(alleles[i] >> 2) & 3u] + "\t" + "ACGT"[alleles[i] & 3u] + "\t" + std::to_string(ad[i]) +
+           "\t" + std::to_string(best[i] >> 8) + "\t" + std::to_string(best[i] & 255u) + "\t" + std::to_string(hits[i]) + "\n";
+  }
+  return out;
+}
+
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
   if (s.empty()) return false;
   char* end = nullptr;
@@ -913,7 +985,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl;
+  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -948,6 +1020,9 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
                           arg == "--eval-overlaps-min-pct";
     if (ovl_flag && first_ovl.empty()) first_ovl = arg;
     if (!ovl_flag && arg != "--device" && first_not_ovl.empty()) first_not_ovl = arg;  // what --eval-overlaps does not take
+    const bool vcf_flag = arg == "--eval-vcf" || arg == "--eval-vcf-truth" || arg == "--eval-vcf-report" || arg == "--eval-vcf-sites" || arg == "--eval-vcf-filtered";
+    if (vcf_flag && first_vcf.empty()) first_vcf = arg;
+    if (!vcf_flag && arg != "--device" && first_not_vcf.empty()) first_not_vcf = arg;  // what --eval-vcf does not take
     if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
     else if (arg == "--single-reads") a->single_reads = true;
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
@@ -1009,6 +1084,11 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--eval-overlaps-report") { if (!file(&a->eval_overlaps_report)) return false; }
     else if (arg == "--eval-overlaps-pairs") { if (!file(&a->eval_overlaps_pairs)) return false; }
     else if (arg == "--eval-overlaps-min-pct") { if (!uint(1, 100, " (1 .. 100)")) return false; a->eval_overlaps_min_pct = (uint32_t)u; }
+    else if (arg == "--eval-vcf") { if (!file(&a->eval_vcf)) return false; }
+    else if (arg == "--eval-vcf-truth") { if (!file(&a->eval_vcf_truth)) return false; }
+    else if (arg == "--eval-vcf-report") { if (!file(&a->eval_vcf_report)) return false; }
+    else if (arg == "--eval-vcf-sites") { if (!file(&a->eval_vcf_sites)) return false; }
+    else if (arg == "--eval-vcf-filtered") a->eval_vcf_filtered = true;
     else if (arg == "--fit-max-alt") { if (!uint(1, UINT32_MAX, " (at least 1)")) return false; a->fit_max_alt = (uint32_t)u; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
@@ -1079,6 +1159,17 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     }
     if (a->eval_overlaps_truth.empty()) { *err = "--eval-overlaps needs --eval-overlaps-truth"; return false; }
     if (a->eval_overlaps_report.empty()) { *err = "--eval-overlaps needs --eval-overlaps-report"; return false; }
+    return true;
+  }
+  if (!first_vcf.empty()) {  // the fourth mode without a simulation
+    if (a->eval_vcf.empty()) { *err = first_vcf + " needs --eval-vcf"; return false; }
+    if (!first_not_vcf.empty()) {
+      *err = "--eval-vcf runs no simulation: it takes only --eval-vcf-truth, --eval-vcf-report, --eval-vcf-sites, --eval-vcf-filtered and --device ('" +
+             first_not_vcf + "' given)";
+      return false;
+    }
+    if (a->eval_vcf_truth.empty()) { *err = "--eval-vcf needs --eval-vcf-truth"; return false; }
+    if (a->eval_vcf_report.empty()) { *err = "--eval-vcf needs --eval-vcf-report"; return false; }
     return true;
   }
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }

@@ -1261,6 +1261,96 @@ static int run_eval_overlaps(const CliArgs& args) {
   info("Wrote " + args.eval_overlaps_report);
   return 0;
 }
+// `--eval-vcf CALLS --eval-vcf-truth TRUTH --eval-vcf-report OUT`: no simulation.  The names come from the ##contig lines in front
+// of the truth file's records; both files go up in pieces, the truth through simmr_vcfeval_truth_add and, behind the plan, the
+// caller's through simmr_vcfeval_add; the report is written from the counts, by_qual and by_ad on the host.  Nothing is written
+// unless all of it succeeded.
+struct VcfevalHandle {
+  simmr_vcfeval* h = nullptr;
+  ~VcfevalHandle() { simmr_vcfeval_destroy(h); }
+};
+static int run_eval_vcf(const CliArgs& args) {
+  std::vector<std::string> names;
+  {
+    std::ifstream in(args.eval_vcf_truth, std::ios::binary);
+    if (!in) return die("--eval-vcf-truth: cannot open " + args.eval_vcf_truth);
+    std::string head, ln;
+    while (std::getline(in, ln) && (ln.empty() || ln[0] == '#')) head += ln + "\n";
+    vcfeval_contig_names(head.data(), head.size(), &names);
+  }
+  if (names.empty()) return die("--eval-vcf-truth: " + args.eval_vcf_truth + " has no ##contig=<ID=...> lines in front of its records: the contigs' names come from them");
+  {
+    FILE* f = fopen(args.eval_vcf.c_str(), "rb");
+    if (!f) return die("--eval-vcf: cannot open " + args.eval_vcf);
+    fclose(f);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  VcfevalHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_vcfeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-vcf: ") + simmr_last_error(eng));
+  std::vector<const char*> rname;
+  for (const std::string& s : names) rname.push_back(s.c_str());
+  const simmr_vcfeval_config cfg{(uint32_t)rname.size(), args.eval_vcf_filtered ? 1u : 0u, rname.data()};
+  if (simmr_vcfeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-vcf-truth: ") + simmr_last_error(eng));
+  float ms = 0;
+  info("Parsing " + args.eval_vcf_truth);
+  if (int rc = sam_file_pieces("--eval-vcf-truth", args.eval_vcf_truth, [&](const uint8_t* d, size_t n) {
+        if (simmr_vcfeval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_vcfeval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
+          return die(std::string("--eval-vcf-truth: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  uint64_t n_entries = 0;
+  if (simmr_vcfeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-vcf-truth: ") + simmr_last_error(eng));
+  info("Parsing " + args.eval_vcf);
+  if (int rc = sam_file_pieces("--eval-vcf", args.eval_vcf, [&](const uint8_t* d, size_t n) {
+        if (simmr_vcfeval_add(ev.h, d, n) != SIMMR_OK || simmr_last_vcfeval_ms(ev.h, &ms) != SIMMR_OK)
+          return die(std::string("--eval-vcf: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  simmr_vcfeval_counts c{};
+  static_assert(sizeof(c) == VCFEVAL_N_COUNTS * sizeof(uint64_t) && VCFEVAL_AD_ROWS == SIMMR_VCFEVAL_AD_ROWS, "the report names every count and row");
+  std::vector<uint64_t> by_qual(512), by_ad(2 * VCFEVAL_AD_ROWS);
+  if (simmr_vcfeval_read(ev.h, &c, by_qual.data(), by_ad.data()) != SIMMR_OK) return die(std::string("--eval-vcf: ") + simmr_last_error(eng));
+  std::string rows;
+  if (!args.eval_vcf_sites.empty()) {
+    GrowBuf d_key, d_narrow;
+    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
+    uint8_t *k = d_key.room(n1 * 8), *nw = d_narrow.room(4 * n1 * 4);
+    if (!k || !nw) return die("--eval-vcf-sites: device allocation failed");
+    uint32_t* const narrow = (uint32_t*)nw;
+    if (simmr_vcfeval_emit(ev.h, (uint64_t*)k, narrow, narrow + n1, narrow + 2 * n1, narrow + 3 * n1, n_entries) != SIMMR_OK)
+      return die(std::string("--eval-vcf-sites: ") + simmr_last_error(eng));
+    std::vector<uint64_t> hk(n1);
+    std::vector<uint32_t> hn(4 * n1);
+    if (hipMemcpy(hk.data(), k, n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), nw, 4 * n1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
+      return die("--eval-vcf-sites: copy from the device failed");
+    std::sort(names.begin(), names.end());  // (the rows of the key are places in the sorted names)
+    rows = vcfeval_site_rows(names, hk.data(), hn.data(), hn.data() + n1, hn.data() + 2 * n1, hn.data() + 3 * n1, n_entries);
+  }
+  std::string err;
+  OutFile report(args.eval_vcf_report, false);
+  report.append(vcfeval_report((const uint64_t*)&c, by_qual.data(), by_ad.data()));
+  if (!report.close(&err)) return die("--eval-vcf-report: " + err);
+  if (!args.eval_vcf_sites.empty()) {
+    OutFile sites(args.eval_vcf_sites, false);
+    sites.append(rows);
+    if (!sites.close(&err)) return die("--eval-vcf-sites: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_entries) + " sites");
+  info("Calls: " + n(c.records) + " records (" + n(c.filtered) + " filtered, " + n(c.ref_call) + " reference calls): " + n(c.calls) + " calls, " + n(c.correct) +
+       " correct, " + n(c.wrong) + " wrong (" + n(c.unknown_contig) + " on unknown contigs, " + n(c.no_site) + " where no site is, " + n(c.ref_mismatch) +
+       " with another reference base, " + n(c.wrong_allele) + " with another allele); " + n(c.indel) + " indel, " + n(c.symbolic) + " symbolic and " +
+       n(c.long_allele) + " long alleles not scored");
+  info("Sites: " + n(c.sites_found) + " found, " + n(c.sites_wrong) + " called wrong only, " + n(c.sites_missed) + " missed, " + n(c.sites_multiple) +
+       " called more than once");
+  info("Wrote " + args.eval_vcf_report);
+  return 0;
+}
 
 static int run_main(int argc, char** argv) {
   CliArgs args;
@@ -1271,6 +1361,7 @@ static int run_main(int argc, char** argv) {
   if (!args.fit_from_sam.empty()) return run_fit_from_sam(args);
   if (!args.eval_sam.empty()) return run_eval_sam(args);
   if (!args.eval_overlaps.empty()) return run_eval_overlaps(args);
+  if (!args.eval_vcf.empty()) return run_eval_vcf(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

@@ -174,6 +174,22 @@ std::string ovleval_report(const uint64_t* counts, const uint64_t* by_len);
 // "/2" where the mate bit is set: a key does not keep whether a name of mate 0 carried "/1"), ov, best (0 no record, 2 wrong,
 // 3 correct) and records, tab-separated.
 std::string ovleval_pair_rows(const uint64_t* key_a, const uint64_t* key_b, const uint64_t* ov, const uint32_t* best, const uint32_t* hits, size_t n);
+// The contig names of a VCF header: the ID of every "##contig=<ID=NAME[,...]>" line of text[0, n), in file order.
+void vcfeval_contig_names(const char* text, size_t n, std::vector<std::string>* names);
+// The file of --eval-vcf-report: the counts of struct simmr_vcfeval_counts as "#name\tvalue" lines in the struct's order
+// (counts[VCFEVAL_N_COUNTS]); "#precision" = correct / calls and "#recall" = sites_found / truth_entries, each as the exact
+// fraction "num/den" and, behind a tab, as a percentage with four decimals ("0" where the denominator is 0); then from QUAL row 255
+// downward a row per row of by_qual[256][2] with a call: Q, the row, correct, wrong, and cumulatively over the rows so far the
+// precision (correct / calls) and the correct calls per truth entry, each as fraction and percentage — the latter is the recall at
+// that threshold where no site is called more than once (sites_multiple is 0), and an upper bound of it otherwise; then a row per
+// row of by_ad[VCFEVAL_AD_ROWS][2] with an entry: AD, the bit length of ad_alt, the sites found, the sites not found.
+constexpr size_t VCFEVAL_N_COUNTS = 24, VCFEVAL_AD_ROWS = 33;
+std::string vcfeval_report(const uint64_t* counts, const uint64_t* by_qual, const uint64_t* by_ad);
+// The rows of --eval-vcf-sites for n truth entries in key order: the contig name (names: the sorted names, the row is key >> 40),
+// the 1-based position, ref, alt, ad_alt, the class of the best call (0 none, 2 wrong, 3 correct), its QUAL row and the calls,
+// tab-separated.  A row whose name index is outside `names` gets "?".
+std::string vcfeval_site_rows(const std::vector<std::string>& names, const uint64_t* key, const uint32_t* alleles, const uint32_t* ad, const uint32_t* best,
+                              const uint32_t* hits, size_t n);
 // `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
 // (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
 // ascend, and its text lies at `offset` of the byte source.
@@ -477,6 +493,11 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string eval_overlaps_report;  // --eval-overlaps-report FILE: the counts, sensitivity, precision and the rows by overlap length as a TSV
   std::string eval_overlaps_pairs;   // --eval-overlaps-pairs FILE: a row per true pair
   uint32_t eval_overlaps_min_pct = 0;  // --eval-overlaps-min-pct PCT: 1 .. 100 (0: not given, the library's default of 10)
+  std::string eval_vcf;         // --eval-vcf FILE: no simulation; a variant caller's VCF scored against the truth of --eval-vcf-truth (simmr_vcfeval_*)
+  std::string eval_vcf_truth;   // --eval-vcf-truth FILE: the strain's sites (the file of --strain-vcf)
+  std::string eval_vcf_report;  // --eval-vcf-report FILE: the counts, precision, recall, the rows by QUAL and by the alternate allele's reads as a TSV
+  std::string eval_vcf_sites;   // --eval-vcf-sites FILE: a row per true site
+  bool eval_vcf_filtered = false;  // --eval-vcf-filtered: score the records whose FILTER is neither "." nor PASS too
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
   std::string depth_track;  // --depth-track FILE: the same per window of --depth-window positions
