@@ -139,8 +139,16 @@ class Tables:
             if line:
                 self.add_line(line)
 
-    def add_line(self, line: bytes):
-        c = self.c
+    def add_line(self, line: bytes, times=1):
+        """the line `times` times over: every table is an integer sum (tests/test_fit_sam_host.py holds this to the repetition)"""
+        c = dict.fromkeys(COUNTS, 0)
+        try:
+            self._add_line(line, times, c)
+        finally:
+            for name, v in c.items():
+                self.c[name] += v * times
+
+    def _add_line(self, line, times, c):
         c["lines"] += 1
         if line[:1] == b"@":
             c["header_lines"] += 1
@@ -167,10 +175,10 @@ class Tables:
             return
         rev = bool(flag & 0x10)
         c["taken_quality"] += 1
-        self.lengths.append(L)
+        self.lengths += [L] * times
         if qual != b"*":
             for i in range(L):
-                self.scores.setdefault(i, []).append(qual[L - 1 - i if rev else i] - 33)
+                self.scores.setdefault(i, []).extend([qual[L - 1 - i if rev else i] - 33] * times)
         if flag & 4:
             c["skip_unmapped"] += 1
             return
@@ -188,7 +196,7 @@ class Tables:
             c["skip_insert"] += 1
             return
         if self.n_sets == 2:
-            self.inserts.append(tlen)
+            self.inserts += [tlen] * times
         got = "cigar_op" if cigar == b"*" else rows(cigar, md, seq)
         if isinstance(got, str):
             c["skip_" + got] += 1
@@ -196,7 +204,8 @@ class Tables:
         c["taken_alignment"] += 1
         ref, qry = (reverse_complement(r) for r in got) if rev else got
         # a query byte outside ACGTN- skips its window: kmerize_alignment's encoder answers None for it
-        _fit.kmerize_alignment(self.k, ref, qry, self.counts)
+        for pair, n in _fit.kmerize_alignment(self.k, ref, qry).items():
+            self.counts[pair] = self.counts.get(pair, 0) + n * times
 
     def model(self, max_alt):
         """the dict tests/_fit.model answers, from these tables"""

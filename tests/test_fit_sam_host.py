@@ -100,3 +100,122 @@ def test_every_filter():
 def test_malformed(line):
     with pytest.raises(_fit_sam.Malformed):
         _fit_sam.Tables(3, 2).add_text(line)
+
+
+# ---- the cases of the seam tests (tests/_fit_sam_cases.py): where each lands, by the restatement alone ---------------------------
+from collections import Counter  # noqa: E402
+
+from tests import _fit_sam_cases as cases  # noqa: E402
+
+
+def lands(item, n_sets=1, k=3):
+    """the counters one line moves, beside those every record moves"""
+    t = _fit_sam.Tables(k, n_sets)
+    t.add_text(item.line)
+    assert t.c["lines"] == t.c["records"] == 1, item.what
+    return {n for n, v in t.c.items() if v} - {"lines", "records", "taken_quality"}
+
+
+def fit_repeated(text, n_sets, k):
+    """the tables of a text whose lines repeat, each distinct line added once with its multiplicity"""
+    t = _fit_sam.Tables(k, n_sets)
+    for ln, n in Counter(x for x in text.split(b"\n") if x).items():
+        t.add_line(ln, times=n)
+    return t
+
+
+def test_seam_cases_land_where_they_say():
+    items = cases.rounds_items() + [i for k in cases.KS for i in cases.window_rows(k)] + cases.quality_offsets()[0]
+    assert len({i.line for i in items}) > 900
+    for item in items:
+        assert lands(item) == {item.lands}, item.what
+    named = {i.what: i.lands for i in items}
+    for flag in cases.STRANDS:
+        assert named[f"a number of 10 digits over the seam, flag {flag}"] == "skip_inconsistent"
+        assert named[f"a number of 9 digits, the last on lane 0, flag {flag}"] == "taken_alignment"
+        assert named[f"MD:Z:9 as RNEXT and no MD behind QUAL, flag {flag}"] == "skip_no_md"
+        assert named[f"the text ends inside the tag, flag {flag}"] == "skip_no_md"
+        assert named[f"the text ends in an empty MD, the CIGAR has no M, flag {flag}"] == "taken_alignment"
+        assert named[f"two MD fields: the first is taken, flag {flag}"] == "taken_alignment"
+        assert named[f"0D twice in a row, flag {flag}"] == named[f"runs of 9 digits with leading zeros, flag {flag}"] == "taken_alignment"
+        for op in "NP":
+            assert named[f"{op} on lane 15, flag {flag}"] == named[f"{op} on lane 0, flag {flag}"] == "skip_cigar_op"
+        for bad in ("a", "*", " "):
+            assert named[f"the byte {bad!r} on lane 0, flag {flag}"] == named[f"the byte {bad!r} on lane 15, flag {flag}"] == "skip_inconsistent"
+    # the texts the GPU tests add hold every item once, and the sum of the lines is the sum of the texts
+    texts = cases.texts_of(cases.rounds_items())
+    _, c = _fit_sam.fit(texts, 1, 7, 20)
+    want = Counter(i.lands for i in cases.rounds_items())
+    n_last = len(texts) - 1
+    assert c["taken_alignment"] == want["taken_alignment"] + n_last and c["records"] == len(cases.rounds_items()) + n_last
+    assert all(c[n] == want[n] for n in want if n != "taken_alignment")
+
+
+def test_seam_rows_mean_what_they_say():
+    """the deleted letters of a long '^' run and the adjacent mismatch letters reach the rows as the header says"""
+    by = {i.what: i.line for i in cases.md_rounds(0)}
+    f = by["^ run of 48 letters, shift 1, flag 0"].split(b"\t")
+    ref, qry = _fit_sam.rows(f[5], f[-1][5:].rstrip(b"\n"), f[9])
+    assert qry.count(b"-") == 48 and b"-" * 48 in qry and ref[qry.index(b"-"):][:48] == b"ACGGTCATTGCAAGTCCGTAGGCTTAACGTCAGTCAGGTTACGCATGC"
+    f = by["40 adjacent mismatch letters, shift 0, flag 0"].split(b"\t")
+    ref, qry = _fit_sam.rows(f[5], f[-1][5:].rstrip(b"\n"), f[9])
+    assert b"-" not in qry and b"-" not in ref and sum(r != q for r, q in zip(ref, qry)) == 40 + 7 and f[5] == b"%dM" % len(ref)
+    f = by["^AC0T, the 0 on lane 15, flag 0"].split(b"\t")
+    ref, qry = _fit_sam.rows(f[5], f[-1][5:].rstrip(b"\n"), f[9])
+    at = qry.index(b"--")
+    assert ref[at:at + 3] == b"ACT" and qry[at + 2:at + 3] == b"A"  # two deleted bases, then the mismatch T
+    # a run of zero gives no column and moves no other (the reference's expand_cigar pushes its op zero times)
+    assert _fit_sam.rows(b"0I3M0D0M2I0S1M0H", b"4", b"ACGTAC") == _fit_sam.rows(b"3M2I1M", b"4", b"ACGTAC") == (b"ACG--C", b"ACGTAC")
+
+
+def test_quality_offsets_around_the_lds_limit():
+    items, want = cases.quality_offsets()
+    m, c = _fit_sam.fit([b"".join(i.line for i in items)], 1, 3, 20)
+    assert c["taken_alignment"] == len(items) == 16 and m["qual_hist"].shape[0] == 320
+    for off in (158, 159, 160, 161, 319):
+        assert {q: int(n) for q, n in enumerate(m["qual_hist"][off]) if n} == want[off], off
+    assert len(want[cases.LDS_POS]) == 4 and 60 not in want[cases.LDS_POS]
+
+
+@pytest.mark.parametrize("what", list(cases.MALFORMED))
+def test_seam_malformed_kinds(what):
+    with pytest.raises(_fit_sam.Malformed):
+        _fit_sam.fit([cases.GOOD + cases.MALFORMED[what] + cases.GOOD], 2, 7, 20)
+    with pytest.raises(_fit_sam.Malformed):
+        _fit_sam.fit([cases.record_trips_text(4, last=cases.MALFORMED[what])["text"]], 2, 7, 20)
+    assert lands(cases.Item("good", cases.GOOD, "taken_alignment", False)) == {"taken_alignment"}
+
+
+def test_geometry_cases():
+    texts, items = cases.line_shift()
+    _, c = _fit_sam.fit(texts, 1, 7, 20)
+    want = Counter(i.lands for i in items)
+    assert all(c[n] == cases.LANES * want[n] for n in want) and c["records"] == cases.LANES * len(items)
+    for case in cases.scan_chunk_texts() + [cases.index_trips_text(3)]:
+        _, c = _fit_sam.fit([case["text"]], 1, 7, 20)
+        assert c["taken_alignment"] == c["records"] == case["taken"] and c["header_lines"] > case["n_tiles"]
+    for cus in (4, 304):
+        case = cases.record_trips_text(cus)
+        _, c = _fit_sam.fit([case["text"]], 1, 7, 20)
+        want = Counter(i.lands for i in case["items"])
+        assert c["lines"] == case["n_lines"] and c["records"] == len(case["items"]) and all(c[n] == want[n] for n in want)
+        assert case["grid"] == (32 if cus == 4 else case["grid"]) and want["taken_alignment"] > 20 and want["skip_inconsistent"] > 2
+        assert b"".join(cases.cut(case["text"])) == case["text"].rstrip(b"\n")
+
+
+def test_times_is_repetition():
+    """Tables.add_line(line, times=n) against n repetitions, table for table: the expected side of the taken-trips test"""
+    case = cases.taken_trips_text(2)
+    plain = _fit_sam.Tables(8, 2)
+    plain.add_text(case["text"])
+    fast = fit_repeated(case["text"], 2, 8)
+    assert plain.c == fast.c and plain.counts == fast.counts and sorted(plain.lengths) == sorted(fast.lengths)
+    assert sorted(plain.inserts) == sorted(fast.inserts) and plain.scores.keys() == fast.scores.keys()
+    assert all(sorted(plain.scores[i]) == sorted(fast.scores[i]) for i in plain.scores)
+    assert plain.c["taken_alignment"] == case["taken"] and all(plain.c[n] == v for n, v in case["skips"].items())
+    assert case["distinct"] <= 64 + 6 and plain.c["lines"] == case["n_lines"] > case["taken"]
+    _fit.assert_model(fast.model(20), plain.model(20), "times against repetition")
+    bad = _fit_sam.Tables(3, 1)
+    with pytest.raises(_fit_sam.Malformed):
+        bad.add_line(cases.MALFORMED["CIGAR M10"], times=5)
+    assert bad.c["records"] == 5
