@@ -1551,6 +1551,128 @@ int simmr_vcfeval_emit(simmr_vcfeval* h, uint64_t* key_dev, uint32_t* alleles_de
  * A run of adds with no synchronising call of this object between them (the plan or this call) is timed as one span. */
 int simmr_last_vcfeval_ms(simmr_vcfeval* h, float* ms);
 
+/* ---- a read classifier's calls scored against each read's true genome: a taxonomy and two texts in HBM ------------------------
+ * Replaces nothing in the reference.  A run over many genomes is a metagenome, and the fourth truth it writes is the one a
+ * taxonomic read classifier is held against: `--truth` names the genome of every read.  That TSV, the per-read output of a
+ * classifier (the format of Kraken 2, which Centrifuge and others can write), a taxonomy and the taxid of every genome go in, and
+ * integer tables come out: per rank the records and the reads correct, right but less specific, wrong and unclassified, and per
+ * taxon the reads that belong to it, that were called into it, and both.  No simulation, no genome: like simmr_mapeval_*.
+ *
+ * Taxonomy (simmr_taxeval_config, HOST arrays, taken by simmr_taxeval_reset).  n_nodes nodes: taxid[], parent[] (the parent's
+ * taxid) and rank[].  Taxid 0 is reserved for "unclassified" and is no node.  A root is a node whose parent is itself or 0; there
+ * may be several.  Rank codes: 1 domain (also "superkingdom"), 2 phylum, 3 class, 4 order, 5 family, 6 genus, 7 species, 8 strain;
+ * 0 any other rank or none.  The reset sorts the nodes by taxid on the device; the ROW of a node is its place in that order.  It
+ * resolves every parent to a row and builds, per node, its depth (the steps to its root; a root has depth 0) and the row of its
+ * ancestor-or-self at each of the 8 ranks: the nearest node of that rank walking up from the node, itself included; none where
+ * the lineage has no node of that rank.  SIMMR_EINVAL: a taxid of 0, a taxid given twice, a parent that is no node, a walk that
+ * reaches no root within SIMMR_TAXEVAL_MAX_DEPTH steps (a cycle, or a tree deeper than that), a rank code above 8, a lineage that
+ * holds one rank twice, a genome whose taxid is 0 or no node.  SIMMR_ERANGE: more than 2^26 nodes.
+ * Genomes.  n_genomes pairs of genome_id[] (NUL-terminated, 1 to 254 bytes, no tab and no newline: SIMMR_ENOTSUP otherwise) and
+ * genome_taxid[].  An id given twice is SIMMR_EINVAL, more than 2^24 of them SIMMR_ERANGE.  The library keeps the ids sorted
+ * bytewise in a device blob and resolves a genome_id field by exact byte comparison; the genome ROW is the place in that order.
+ *
+ * Text, both sides.  Whole lines of plain text (no gzip): every line ends in '\n', except that the last line of a call may lack
+ * it; the caller cuts a file at line ends, at most SIMMR_FIT_SAM_MAX_BYTES a call.  An empty line is skipped and not counted.  A
+ * line whose first byte is '#', or that starts with "read_id<tab>", is a header line, counted and skipped.  Every other line is a
+ * record.  Only the first three tab-separated fields of a record are read.
+ *
+ * Truth record: read_id, pair, genome_id.  Malformed (sticky; simmr_taxeval_truth_plan and simmr_taxeval_read answer SIMMR_EINVAL):
+ * fewer than 3 fields; a read_id that is not 1 to 18 digits; a pair that is not exactly "0", "1" or "2"; a genome_id that is not
+ * among the genomes.  The plan sorts the lines by read id and collapses equal ids into one ENTRY (id, genome row, mates = the
+ * lines behind it: both mates of a pair come from one genome).  One id with two different genomes, or with more than two lines:
+ * the plan answers SIMMR_EINVAL.
+ *
+ * Candidate record: "C" or "U", the read name, the taxon.  Malformed (sticky; simmr_taxeval_read answers SIMMR_EINVAL), checked
+ * on every record before any step: fewer than 3 fields; a field 1 that is not exactly "C" or "U"; a field 3 that is neither 1 to
+ * 10 digits with a value below 2^32 nor any text that ends in "(taxid <1 to 10 digits, below 2^32>)" (the --use-names form).
+ * The read name is a read id of 1 to 18 digits with an optional "/1" or "/2" (the name rule of simmr_ovleval_*); the suffix is
+ * dropped.  A record is handled in this order (records counts every well-formed one):
+ *   1. A name that is no read id, or an id with no entry: unknown_read; not scored, no table changes.
+ *   2. "U", or taxid 0: unclassified.  Class 1 at every rank the truth has, class 0 at the others.
+ *   3. A taxid that is no node: unknown_taxon.  Class 2 at every rank the truth has, class 0 at the others.
+ *   4. Otherwise scored.  With t = the node of the entry's genome and c = the called node, rank r = 1 .. 8 gets the class
+ *        0 absent:   t has no ancestor-or-self at r;
+ *        4 correct:  c has one, and it is the same row as t's;
+ *        2 wrong:    c has one, and it is another row;
+ *        3 above:    c has none, and c is an ancestor-or-self of t (the lowest common ancestor of t and c is c): right, but
+ *                    less specific than r;
+ *        2 wrong:    c has none, and c is not on t's path.
+ * Every record of steps 2 to 4 updates: by_rank[r - 1][class] += 1 for each rank (class 0 included); hits[entry] += 1;
+ * seen[entry] |= one bit per rank, bit 4 (r - 1) + class - 1 (class 0 sets none), so the best class of a read at rank r is the
+ * highest set bit of nibble r - 1, plus one; and the direct per-node counts: n_true[t] += 1, and for step 4 also n_called[c] += 1
+ * and n_both[lca(t, c)] += 1 (nothing where t and c stand under different roots).
+ * Per entry, made by a reduction in simmr_taxeval_read: truth_paired (mates == 2), missing (no hit), multiple (more hits than
+ * mates), and reads_by_rank[r - 1][class]: the entries by the best class of their records at r; an entry with no record counts as
+ * class 1 at the ranks its genome has and 0 at the others.
+ * Every output is an integer sum or an OR: the same for any launch geometry and any cut of either text into adds. */
+#define SIMMR_TAXEVAL_RANKS 8u
+#define SIMMR_TAXEVAL_CLASSES 5u        /* 0 absent, 1 unclassified, 2 wrong, 3 above, 4 correct */
+#define SIMMR_TAXEVAL_MAX_DEPTH 255u    /* the longest walk from a node to its root, in steps */
+
+typedef struct simmr_taxeval simmr_taxeval;
+
+typedef struct simmr_taxeval_config {   /* HOST memory; every array in any order */
+  uint64_t n_nodes;
+  const uint32_t* taxid;                /* [n_nodes] */
+  const uint32_t* parent;               /* [n_nodes] the parent's taxid; itself or 0: a root */
+  const uint8_t* rank;                  /* [n_nodes] the rank code, 0 .. 8 */
+  uint64_t n_genomes;
+  const char* const* genome_id;         /* [n_genomes] NUL-terminated */
+  const uint32_t* genome_taxid;         /* [n_genomes] */
+} simmr_taxeval_config;
+
+typedef struct simmr_taxeval_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_lines, truth_header;                  /* lines = header + records; cumulative since the reset */
+  uint64_t truth_entries, truth_paired;                /* of the plan in force: the entries, and those with two lines */
+  uint64_t lines, header, records;                     /* the candidate side, since the last truth plan */
+  uint64_t unknown_read, unclassified, unknown_taxon, scored;   /* records = the sum of these four */
+  uint64_t missing, multiple;                          /* truth entries: no hit, more hits than lines */
+} simmr_taxeval_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_mapeval_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error). */
+int simmr_taxeval_create(simmr_engine* e, simmr_taxeval** out);
+void simmr_taxeval_destroy(simmr_taxeval* h);
+/* Takes the taxonomy and the genomes, builds the tree on the device and empties both sides.  Synchronises.  The errors are those
+ * of the two paragraphs above, and SIMMR_EINVAL for a NULL argument.  A reset that fails leaves the object without a tree: every
+ * other call answers SIMMR_ESTATE until a reset succeeds. */
+int simmr_taxeval_reset(simmr_taxeval* h, const simmr_taxeval_config* cfg);
+/* The lineage of the node `taxid`: out_taxid[r - 1] (HOST, 8 words, may be NULL) = the taxid of its ancestor-or-self at rank r, 0
+ * where it has none; *depth (may be NULL) = its steps to the root.  Synchronises.  SIMMR_EINVAL: no such node.  SIMMR_ESTATE. */
+int simmr_taxeval_lineage(simmr_taxeval* h, uint32_t taxid, uint32_t* out_taxid, uint32_t* depth);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for a line per 5 bytes of text (no record is shorter: 3 one-byte fields and
+ * 2 tabs) grows with the object.  SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL text with n_bytes > 0.  SIMMR_ENOTSUP:
+ * n_bytes above SIMMR_FIT_SAM_MAX_BYTES. */
+int simmr_taxeval_truth_add(simmr_taxeval* h, const uint8_t* text, uint64_t n_bytes);
+/* Sorts the lines by read id (the radix sort of simmr_sam_sort_plan, over the bits of the largest id), collapses equal ids into
+ * entries with a head flag, a scan and a compaction, empties the candidate side and synchronises.  *n_entries (may be NULL) = the
+ * entries.  SIMMR_EINVAL: a malformed truth record, one id with two genomes or with more than two lines.  SIMMR_ERANGE: 2^31
+ * lines or more. */
+int simmr_taxeval_truth_plan(simmr_taxeval* h, uint64_t* n_entries);
+/* Scores the records of text[0 .. n_bytes) (DEVICE, as above) against the plan.  Only enqueues.  SIMMR_ESTATE: no truth plan
+ * in force.  SIMMR_EINVAL, SIMMR_ENOTSUP: as simmr_taxeval_truth_add. */
+int simmr_taxeval_add(simmr_taxeval* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts, by_rank_host[8][5] (the records by rank and class) and reads_by_rank_host[8][5] (the entries by rank and best
+ * class) (HOST, any may be NULL).  Synchronises.  truth_paired, missing, multiple and reads_by_rank are made here, by a reduction
+ * over seen[], hits[] and mates[].  SIMMR_EINVAL: a malformed record on either side since the reset (nothing is written).
+ * SIMMR_ESTATE: no reset yet. */
+int simmr_taxeval_read(simmr_taxeval* h, simmr_taxeval_counts* counts, uint64_t* by_rank_host, uint64_t* reads_by_rank_host);
+/* The truth entries in ascending id order, five columns (DEVICE, capacity entries each, any may be NULL): the read id, the genome
+ * row, mates (the lines behind the entry, 1 or 2), seen and hits.  Synchronises.  SIMMR_ESTATE: no truth plan.  SIMMR_ERANGE,
+ * nothing written: capacity < n_entries. */
+int simmr_taxeval_emit(simmr_taxeval* h, uint64_t* id_dev, uint32_t* genome_row_dev, uint32_t* mates_dev, uint32_t* seen_dev, uint32_t* hits_dev,
+                       uint64_t capacity);
+/* One row per node in taxid order, four columns (DEVICE, capacity_nodes each, any may be NULL): the taxid and the three CLADE sums
+ * — a node's sum over itself and all its descendants of n_true, n_called and n_both.  So for a node X of rank r, called[X] counts
+ * the records called into X at r or below, true[X] those that truly belong to it, and both[X] the true positives.  The direct
+ * counts are only read: the sums are made anew by every call, and a second call gives the same answer.  Synchronises.
+ * SIMMR_ESTATE: no reset yet.  SIMMR_ERANGE, nothing written: capacity_nodes < n_nodes. */
+int simmr_taxeval_taxa(simmr_taxeval* h, uint32_t* taxid_dev, uint64_t* true_dev, uint64_t* called_dev, uint64_t* both_dev, uint64_t capacity_nodes);
+/* HIP-event time (ms) of the device work since the last reset: the truth adds, the plans and the adds (not the reset's tree).
+ * Synchronises the stream.  A run of adds with no synchronising call of this object between them is timed as one span. */
+int simmr_last_taxeval_ms(simmr_taxeval* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,6 +274,24 @@ class VcfevalConfig(C.Structure):
     _fields_ = [("n_names", C.c_uint32), ("use_filtered", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
 
 
+TAXEVAL_COUNTS = ("truth_lines", "truth_header", "truth_entries", "truth_paired", "lines", "header", "records", "unknown_read", "unclassified",
+                  "unknown_taxon", "scored", "missing", "multiple")
+TAXEVAL_RANKS = 8        # SIMMR_TAXEVAL_RANKS
+TAXEVAL_CLASSES = 5      # SIMMR_TAXEVAL_CLASSES
+TAXEVAL_MAX_DEPTH = 255  # SIMMR_TAXEVAL_MAX_DEPTH
+
+
+class TaxevalCounts(C.Structure):
+    """struct simmr_taxeval_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in TAXEVAL_COUNTS]
+
+
+class TaxevalConfig(C.Structure):
+    """struct simmr_taxeval_config (host memory)"""
+    _fields_ = [("n_nodes", C.c_uint64), ("taxid", C.POINTER(C.c_uint32)), ("parent", C.POINTER(C.c_uint32)), ("rank", C.POINTER(C.c_uint8)),
+                ("n_genomes", C.c_uint64), ("genome_id", C.POINTER(C.c_char_p)), ("genome_taxid", C.POINTER(C.c_uint32))]
+
+
 class MapevalConfig(C.Structure):
     """struct simmr_mapeval_config (host memory)"""
     _fields_ = [("n_names", C.c_uint32), ("min_overlap_pct", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
@@ -430,6 +448,17 @@ SYMBOLS = {
     "simmr_vcfeval_read": (C.c_int, [C.c_void_p, _P(VcfevalCounts), _P(C.c_uint64), _P(C.c_uint64)]),
     "simmr_vcfeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_last_vcfeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_taxeval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_taxeval_destroy": (None, [C.c_void_p]),
+    "simmr_taxeval_reset": (C.c_int, [C.c_void_p, _P(TaxevalConfig)]),
+    "simmr_taxeval_lineage": (C.c_int, [C.c_void_p, C.c_uint32, _P(C.c_uint32), _P(C.c_uint32)]),
+    "simmr_taxeval_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_taxeval_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "simmr_taxeval_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_taxeval_read": (C.c_int, [C.c_void_p, _P(TaxevalCounts), _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_taxeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_taxeval_taxa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_last_taxeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
 }
 
 _lib = None

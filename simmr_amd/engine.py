@@ -414,6 +414,120 @@ class VcfEval:
                 self.engine._mapevals.remove(self)
 
 
+class TaxEval:
+    """A read classifier's calls scored against each read's true genome on the device (simmr_taxeval_*, include/simmr_hip.h
+    states the rules).  truth_add() the truth text (the file of --truth), truth_plan(), add() the classifier's per-read text, then
+    read(), reads() and taxa().  A text is bytes (copied up) or a contiguous CUDA uint8 tensor; the adds only enqueue, so every
+    text is kept until a call that synchronises."""
+
+    def __init__(self, engine: "Engine", taxonomy, genomes):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        self.n_entries = self.n_nodes = 0
+        self.genome_ids = []
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_taxeval_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(taxonomy, genomes)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, taxonomy, genomes):
+        """`taxonomy`: (taxid, parent, rank) arrays of one length; `genomes`: a list of (genome_id, taxid)"""
+        taxid, parent = (np.ascontiguousarray(a, dtype=np.uint32) for a in taxonomy[:2])
+        rank = np.ascontiguousarray(taxonomy[2], dtype=np.uint8)
+        if not (taxid.ndim == parent.ndim == rank.ndim == 1 and len(taxid) == len(parent) == len(rank)):
+            raise ValueError("a taxonomy is three arrays of one length: taxid, parent, rank")
+        raw = [g if isinstance(g, bytes) else str(g).encode() for g, _ in genomes]
+        ids = (C.c_char_p * max(len(raw), 1))(*raw)
+        gtax = np.array([int(t) for _, t in genomes], dtype=np.uint32)
+        u32, u8 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        cfg = _abi.TaxevalConfig(len(taxid), taxid.ctypes.data_as(u32), parent.ctypes.data_as(u32), rank.ctypes.data_as(u8), len(raw), ids,
+                                 gtax.ctypes.data_as(u32))
+        self.n_entries = self.n_nodes = 0
+        try:
+            self._check(self.lib.simmr_taxeval_reset(self._h, C.byref(cfg)))
+        finally:
+            self._texts = []  # the reset has synchronised
+        self.n_nodes = len(taxid)
+        self.genome_ids = sorted(raw)  # the genome row is the place in this order
+
+    _text = Mapeval._text
+
+    def lineage(self, taxid: int):
+        """(the taxids of the node's ancestor-or-self at the 8 ranks, 0 where it has none; its depth)"""
+        out, depth = (C.c_uint32 * _abi.TAXEVAL_RANKS)(), C.c_uint32(0)
+        self._check(self.lib.simmr_taxeval_lineage(self._h, int(taxid), out, C.byref(depth)))
+        return [int(v) for v in out], int(depth.value)
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_taxeval_truth_add(self._h, p, n))
+
+    def truth_plan(self) -> int:
+        n = C.c_uint64(0)
+        self.n_entries = 0
+        try:
+            self._check(self.lib.simmr_taxeval_truth_plan(self._h, C.byref(n)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_entries = int(n.value)
+        return self.n_entries
+
+    def add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_taxeval_add(self._h, p, n))
+
+    def read(self):
+        """(counts by the names of struct simmr_taxeval_counts, by_rank as an (8, 5) uint64 array: the records by rank and class,
+        reads_by_rank as an (8, 5) uint64 array: the truth entries by rank and best class)"""
+        c = _abi.TaxevalCounts()
+        by_rank = np.zeros((_abi.TAXEVAL_RANKS, _abi.TAXEVAL_CLASSES), dtype=np.uint64)
+        reads_by_rank = np.zeros_like(by_rank)
+        try:
+            self._check(self.lib.simmr_taxeval_read(self._h, C.byref(c), by_rank.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                    reads_by_rank.ctypes.data_as(C.POINTER(C.c_uint64))))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.TAXEVAL_COUNTS}, by_rank, reads_by_rank
+
+    def reads(self):
+        """The truth entries ascending by id, as numpy arrays: id (uint64), genome_row, mates, seen, hits (uint32)"""
+        torch = _torch()
+        n, dev = self.n_entries, self.engine.device
+        key = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        narrow = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(4)]
+        self._check(self.lib.simmr_taxeval_emit(self._h, *[C.c_void_p(t.data_ptr()) for t in [key] + narrow], n))
+        self._texts = []
+        return (key[:n].cpu().numpy().view(np.uint64),) + tuple(t[:n].cpu().numpy().view(np.uint32) for t in narrow)
+
+    def taxa(self):
+        """One row per node in taxid order, as numpy arrays: taxid (uint32) and the clade sums true, called, both (uint64)"""
+        torch = _torch()
+        n, dev = self.n_nodes, self.engine.device
+        taxid = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        wide = [torch.zeros(max(n, 1), dtype=torch.int64, device=dev) for _ in range(3)]
+        self._check(self.lib.simmr_taxeval_taxa(self._h, *[C.c_void_p(t.data_ptr()) for t in [taxid] + wide], n))
+        self._texts = []
+        return (taxid[:n].cpu().numpy().view(np.uint32),) + tuple(t[:n].cpu().numpy().view(np.uint64) for t in wide)
+
+    def last_ms(self) -> float:
+        return self.engine._ms(self.lib.simmr_last_taxeval_ms, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_taxeval_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
 def cut_at_line_ends(text: bytes, pieces: int):
     """`text` in at most `pieces` parts of about one size, each cut behind a newline"""
     out, a = [], 0
@@ -1209,6 +1323,37 @@ class Engine:
                 ev.add(t)
             counts, by_qual, by_ad = ev.read()
             return counts, by_qual, by_ad, ev.sites()
+        finally:
+            ev.close()
+
+    # -- a read classifier's calls against each read's true genome ---------------------------
+    def classify_eval_open(self, taxonomy, genomes) -> "TaxEval":
+        """An evaluation object (simmr_taxeval_*) over a taxonomy, a triple of arrays (taxid, parent, rank), and the genomes, a list
+        of (genome_id, taxid).  Closed by its close(), or by the engine's before the engine goes (it is kept in the list of the
+        mapeval objects, which the engine closes first)."""
+        m = TaxEval(self, taxonomy, genomes)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
+
+    def classify_eval(self, truth, calls, taxonomy, genomes, pieces=1):
+        """Scores the classifier's per-read text `calls` against the truth TSV `truth` (each bytes, a CUDA uint8 tensor, or a list
+        of those: an add each; a bytes text goes up in `pieces` adds cut at line ends).  Returns (counts as a dict, by_rank (8, 5),
+        reads_by_rank (8, 5), (id, genome_row, mates, seen, hits) of the truth entries in id order, (taxid, true, called, both)
+        of the nodes in taxid order)."""
+        def adds(text):
+            texts = list(text) if isinstance(text, (list, tuple)) else [text]
+            return [part for t in texts for part in (cut_at_line_ends(bytes(t), max(int(pieces), 1)) if isinstance(t, (bytes, bytearray, memoryview)) else [t])]
+        ev = self.classify_eval_open(taxonomy, genomes)
+        try:
+            for t in adds(truth):
+                ev.truth_add(t)
+            ev.truth_plan()
+            for t in adds(calls):
+                ev.add(t)
+            counts, by_rank, reads_by_rank = ev.read()
+            return counts, by_rank, reads_by_rank, ev.reads(), ev.taxa()
         finally:
             ev.close()
 

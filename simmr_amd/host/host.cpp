@@ -792,6 +792,20 @@ std::string usage() {
          "            --eval-vcf-sites <FILE>  every true site: contig, position, ref, alt, reads that showed alt, the class of its best call\n"
          "                            (0 no call, 2 wrong, 3 correct), that call's QUAL row, calls\n"
          "            --eval-vcf-filtered  score the records whose FILTER is neither . nor PASS too\n"
+         "            --eval-classified <FILE>  no simulation: score a read classifier's per-read output (plain text, the columns of Kraken 2: C or U,\n"
+         "                            the read name, the taxid, also as 'name (taxid N)') against the genome of every read in the file of\n"
+         "                            --eval-classified-truth, joined by read id and classified per rank on the device: correct, above\n"
+         "                            (right but less specific), wrong, unclassified; takes only --eval-classified-truth, --eval-taxonomy,\n"
+         "                            --eval-genome-taxa, --eval-classified-report, --eval-classified-reads, --eval-classified-taxa and\n"
+         "                            --device (no genomes, no --output, not --devices)\n"
+         "            --eval-classified-truth <FILE>  the file of --truth for the reads that were classified\n"
+         "            --eval-taxonomy <FILE>  the tree: NCBI's nodes.dmp, or taxid, parent and rank as a TSV (merged.dmp is not read)\n"
+         "            --eval-genome-taxa <FILE>  genome_id and taxid as a TSV, a line per genome of the truth\n"
+         "            --eval-classified-report <FILE>  the result as a TSV: the counts as #name value lines, an R row per rank with the records and\n"
+         "                            the reads by class, a P row per rank with precision, sensitivity and F1 on both, an A row per rank with\n"
+         "                            the L1 distance between the true and the called abundance profile (by reads)\n"
+         "            --eval-classified-reads <FILE>  every true read: id, genome, lines, records, the best class at each of the 8 ranks\n"
+         "            --eval-classified-taxa <FILE>  every taxon with reads: taxid, rank, true, called, both (clade sums), precision, recall\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -974,6 +988,188 @@ std::string vcfeval_site_rows(const std::vector<std::string>& names, const uint6
   return out;
 }
 
+// ---- --eval-classified ---------------------------------------------------------------------------------------------------------------
+static const char* const TAXEVAL_RANK_NAMES[TAXEVAL_RANKS + 1] = {"no_rank", "domain", "phylum", "class", "order", "family", "genus", "species", "strain"};
+
+uint8_t taxeval_rank_code(const std::string& name) {
+  if (name == "superkingdom") return 1;
+  for (size_t r = 1; r <= TAXEVAL_RANKS; r++)
+    if (name == TAXEVAL_RANK_NAMES[r]) return (uint8_t)r;
+  return 0;
+}
+
+const char* taxeval_rank_name(uint32_t code) { return TAXEVAL_RANK_NAMES[code <= TAXEVAL_RANKS ? code : 0]; }
+
+// the fields of text[a, b): cut at "\t|\t" where the line holds one (a trailing "\t|" dropped), at tabs otherwise
+static std::vector<std::string> taxeval_fields(const char* text, size_t a, size_t b) {
+  std::string line(text + a, b - a);
+  if (!line.empty() && line.back() == '\r') line.pop_back();
+  std::vector<std::string> out;
+  const bool dmp = line.find("\t|\t") != std::string::npos;
+  if (dmp && line.size() >= 2 && line.compare(line.size() - 2, 2, "\t|") == 0) line.resize(line.size() - 2);
+  const std::string sep = dmp ? "\t|\t" : "\t";
+  for (size_t at = 0;;) {
+    const size_t e = line.find(sep, at);
+    out.push_back(line.substr(at, e == std::string::npos ? std::string::npos : e - at));
+    if (e == std::string::npos) break;
+    at = e + sep.size();
+  }
+  return out;
+}
+
+static bool taxeval_taxid(const std::string& s, uint32_t* out) {
+  if (s.empty() || s.size() > 10) return false;
+  uint64_t v = 0;
+  for (char c : s) {
+    if (c < '0' || c > '9') return false;
+    v = v * 10 + (uint64_t)(c - '0');
+  }
+  if (v > 0xffffffffull) return false;
+  *out = (uint32_t)v;
+  return true;
+}
+
+bool taxeval_parse_nodes(const char* text, size_t n, std::vector<uint32_t>* taxid, std::vector<uint32_t>* parent, std::vector<uint8_t>* rank, std::string* err) {
+  size_t line_no = 0;
+  for (size_t a = 0; a < n;) {
+    size_t b = a;
+    while (b < n && text[b] != '\n') b++;
+    line_no++;
+    if (b > a && !(b - a == 1 && text[a] == '\r')) {
+      const std::vector<std::string> f = taxeval_fields(text, a, b);
+      uint32_t t = 0, p = 0;
+      if (f.size() < 3 || !taxeval_taxid(f[0], &t) || !taxeval_taxid(f[1], &p)) {
+        *err = "line " + std::to_string(line_no) + " is not 'taxid | parent | rank'";
+        return false;
+      }
+      taxid->push_back(t);
+      parent->push_back(p);
+      rank->push_back(taxeval_rank_code(f[2]));
+    }
+    a = b + 1;
+  }
+  return true;
+}
+
+bool taxeval_parse_map(const char* text, size_t n, std::vector<std::string>* genome_id, std::vector<uint32_t>* taxid, std::string* err) {
+  size_t line_no = 0;
+  bool first = true;  // the first line that is not empty may be a header
+  for (size_t a = 0; a < n;) {
+    size_t b = a;
+    while (b < n && text[b] != '\n') b++;
+    line_no++;
+    if (b > a && !(b - a == 1 && text[a] == '\r')) {
+      std::string line(text + a, b - a);
+      if (line.back() == '\r') line.pop_back();
+      const size_t tab = line.find('\t');
+      const size_t e = tab == std::string::npos ? tab : line.find('\t', tab + 1);
+      uint32_t t = 0;
+      const bool ok = tab != std::string::npos && tab > 0 && taxeval_taxid(line.substr(tab + 1, e == std::string::npos ? e : e - tab - 1), &t);
+      if (!ok && !(first && tab != std::string::npos)) {
+        *err = "line " + std::to_string(line_no) + " is not 'genome_id <tab> taxid'";
+        return false;
+      }
+      if (ok) {
+        genome_id->push_back(line.substr(0, tab));
+        taxid->push_back(t);
+      }
+      first = false;
+    }
+    a = b + 1;
+  }
+  return true;
+}
+
+static std::string taxeval_ratio(uint64_t num, uint64_t den) {
+  if (den == 0) return "NA";
+  char text[64];
+  snprintf(text, sizeof text, "%.6f", (double)num / (double)den);
+  return text;
+}
+
+// precision, sensitivity and F1 of one row of five class counts
+static std::string taxeval_prf(const uint64_t* k) {
+  const uint64_t scored = k[1] + k[2] + k[3] + k[4], cw = k[4] + k[2];
+  std::string f1 = "NA";
+  if (cw != 0 && scored != 0) {
+    const double p = (double)k[4] / (double)cw, s = (double)k[4] / (double)scored;
+    if (p + s != 0.0) {
+      char text[64];
+      snprintf(text, sizeof text, "%.6f", 2.0 * p * s / (p + s));
+      f1 = text;
+    }
+  }
+  return taxeval_ratio(k[4], cw) + "\t" + taxeval_ratio(k[4], scored) + "\t" + f1;
+}
+
+std::string taxeval_report(const uint64_t* counts, const uint64_t* by_rank, const uint64_t* reads_by_rank, const uint8_t* rank_code, const uint64_t* true_sum,
+                           const uint64_t* called_sum, size_t n_nodes) {
+  static const char* const NAMES[TAXEVAL_N_COUNTS] = {"truth_lines", "truth_header", "truth_entries", "truth_paired", "lines", "header", "records", "unknown_read",
+                                                      "unclassified", "unknown_taxon", "scored", "missing", "multiple"};
+  static const char* const CLASS[TAXEVAL_CLASSES] = {"absent", "unclassified", "wrong", "above", "correct"};
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  std::string out;
+  for (size_t i = 0; i < TAXEVAL_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + n(counts[i]) + "\n";
+  out += "#R\trank\tname";
+  for (const char* w : {"records", "reads"})
+    for (size_t k = 0; k < TAXEVAL_CLASSES; k++) out += std::string("\t") + w + "_" + CLASS[k];
+  out += "\n";
+  for (size_t r = 0; r < TAXEVAL_RANKS; r++) {
+    out += "R\t" + std::to_string(r + 1) + "\t" + TAXEVAL_RANK_NAMES[r + 1];
+    for (size_t k = 0; k < TAXEVAL_CLASSES; k++) out += "\t" + n(by_rank[r * TAXEVAL_CLASSES + k]);
+    for (size_t k = 0; k < TAXEVAL_CLASSES; k++) out += "\t" + n(reads_by_rank[r * TAXEVAL_CLASSES + k]);
+    out += "\n";
+  }
+  out += "#P\trank\tname\trecords_precision\trecords_sensitivity\trecords_f1\treads_precision\treads_sensitivity\treads_f1\n";
+  for (size_t r = 0; r < TAXEVAL_RANKS; r++)
+    out += "P\t" + std::to_string(r + 1) + "\t" + TAXEVAL_RANK_NAMES[r + 1] + "\t" + taxeval_prf(by_rank + r * TAXEVAL_CLASSES) + "\t" +
+           taxeval_prf(reads_by_rank + r * TAXEVAL_CLASSES) + "\n";
+  out += "#A\trank\tname\tnodes\tl1_distance\n";
+  for (size_t r = 1; r <= TAXEVAL_RANKS; r++) {
+    uint64_t st = 0, sc = 0, nodes = 0;
+    for (size_t i = 0; i < n_nodes; i++)
+      if (rank_code[i] == r) { st += true_sum[i]; sc += called_sum[i]; nodes++; }
+    double l1 = 0.0;
+    if (st != 0 && sc != 0)
+      for (size_t i = 0; i < n_nodes; i++)
+        if (rank_code[i] == r) l1 += fabs((double)true_sum[i] / (double)st - (double)called_sum[i] / (double)sc);
+    char text[64] = "NA";
+    if (st != 0 && sc != 0) snprintf(text, sizeof text, "%.6f", l1);
+    out += "A\t" + std::to_string(r) + "\t" + TAXEVAL_RANK_NAMES[r] + "\t" + n(nodes) + "\t" + text + "\n";
+  }
+  return out;
+}
+
+std::string taxeval_read_rows(const std::vector<std::string>& genome_ids, const std::vector<uint32_t>& genome_has, const uint64_t* id, const uint32_t* genome,
+                              const uint32_t* mates, const uint32_t* seen, const uint32_t* hits, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t g = genome[i];
+    out += std::to_string((unsigned long long)id[i]) + "\t" + (g < genome_ids.size() ? genome_ids[g] : std::string("?")) + "\t" + std::to_string(mates[i]) + "\t" +
+           std::to_string(hits[i]);
+    const uint32_t has = g < genome_has.size() ? genome_has[g] : 0u;
+    for (size_t r = 0; r < TAXEVAL_RANKS; r++) {
+      const uint32_t nib = (seen[i] >> (4 * r)) & 15u;
+      const uint32_t best = hits[i] == 0 ? (has >> r) & 1u : nib ? 32u - (uint32_t)__builtin_clz(nib) : 0u;
+      out += "\t" + std::to_string(best);
+    }
+    out += "\n";
+  }
+  return out;
+}
+
+std::string taxeval_taxa_rows(const uint32_t* taxid, const uint8_t* rank_code, const uint64_t* true_sum, const uint64_t* called_sum, const uint64_t* both_sum,
+                              size_t n_nodes) {
+  std::string out;
+  for (size_t i = 0; i < n_nodes; i++) {
+    if (true_sum[i] == 0 && called_sum[i] == 0 && both_sum[i] == 0) continue;
+    out += std::to_string(taxid[i]) + "\t" + taxeval_rank_name(rank_code[i]) + "\t" + std::to_string((unsigned long long)true_sum[i]) + "\t" +
+           std::to_string((unsigned long long)called_sum[i]) + "\t" + std::to_string((unsigned long long)both_sum[i]) + "\t" +
+           taxeval_ratio(both_sum[i], called_sum[i]) + "\t" + taxeval_ratio(both_sum[i], true_sum[i]) + "\n";
+  }
+  return out;
+}
+
 static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
   if (s.empty()) return false;
   char* end = nullptr;
@@ -985,7 +1181,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf;
+  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -1023,6 +1219,10 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     const bool vcf_flag = arg == "--eval-vcf" || arg == "--eval-vcf-truth" || arg == "--eval-vcf-report" || arg == "--eval-vcf-sites" || arg == "--eval-vcf-filtered";
     if (vcf_flag && first_vcf.empty()) first_vcf = arg;
     if (!vcf_flag && arg != "--device" && first_not_vcf.empty()) first_not_vcf = arg;  // what --eval-vcf does not take
+    const bool tax_flag = arg == "--eval-classified" || arg == "--eval-classified-truth" || arg == "--eval-taxonomy" || arg == "--eval-genome-taxa" ||
+                          arg == "--eval-classified-report" || arg == "--eval-classified-reads" || arg == "--eval-classified-taxa";
+    if (tax_flag && first_tax.empty()) first_tax = arg;
+    if (!tax_flag && arg != "--device" && first_not_tax.empty()) first_not_tax = arg;  // what --eval-classified does not take
     if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
     else if (arg == "--single-reads") a->single_reads = true;
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
@@ -1089,6 +1289,13 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     else if (arg == "--eval-vcf-report") { if (!file(&a->eval_vcf_report)) return false; }
     else if (arg == "--eval-vcf-sites") { if (!file(&a->eval_vcf_sites)) return false; }
     else if (arg == "--eval-vcf-filtered") a->eval_vcf_filtered = true;
+    else if (arg == "--eval-classified") { if (!file(&a->eval_classified)) return false; }
+    else if (arg == "--eval-classified-truth") { if (!file(&a->eval_classified_truth)) return false; }
+    else if (arg == "--eval-taxonomy") { if (!file(&a->eval_taxonomy)) return false; }
+    else if (arg == "--eval-genome-taxa") { if (!file(&a->eval_genome_taxa)) return false; }
+    else if (arg == "--eval-classified-report") { if (!file(&a->eval_classified_report)) return false; }
+    else if (arg == "--eval-classified-reads") { if (!file(&a->eval_classified_reads)) return false; }
+    else if (arg == "--eval-classified-taxa") { if (!file(&a->eval_classified_taxa)) return false; }
     else if (arg == "--fit-max-alt") { if (!uint(1, UINT32_MAX, " (at least 1)")) return false; a->fit_max_alt = (uint32_t)u; }
     else if (arg == "--depth") { if (!file(&a->depth)) return false; }
     else if (arg == "--depth-track") { if (!file(&a->depth_track)) return false; }
@@ -1170,6 +1377,19 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     }
     if (a->eval_vcf_truth.empty()) { *err = "--eval-vcf needs --eval-vcf-truth"; return false; }
     if (a->eval_vcf_report.empty()) { *err = "--eval-vcf needs --eval-vcf-report"; return false; }
+    return true;
+  }
+  if (!first_tax.empty()) {  // the fifth mode without a simulation
+    if (a->eval_classified.empty()) { *err = first_tax + " needs --eval-classified"; return false; }
+    if (!first_not_tax.empty()) {
+      *err = "--eval-classified runs no simulation: it takes only --eval-classified-truth, --eval-taxonomy, --eval-genome-taxa, --eval-classified-report, "
+             "--eval-classified-reads, --eval-classified-taxa and --device ('" + first_not_tax + "' given)";
+      return false;
+    }
+    if (a->eval_classified_truth.empty()) { *err = "--eval-classified needs --eval-classified-truth"; return false; }
+    if (a->eval_taxonomy.empty()) { *err = "--eval-classified needs --eval-taxonomy"; return false; }
+    if (a->eval_genome_taxa.empty()) { *err = "--eval-classified needs --eval-genome-taxa"; return false; }
+    if (a->eval_classified_report.empty()) { *err = "--eval-classified needs --eval-classified-report"; return false; }
     return true;
   }
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }

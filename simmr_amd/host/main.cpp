@@ -1352,6 +1352,136 @@ static int run_eval_vcf(const CliArgs& args) {
   return 0;
 }
 
+// `--eval-classified CALLS --eval-classified-truth TRUTH --eval-taxonomy NODES --eval-genome-taxa MAP --eval-classified-report OUT`:
+// no simulation.  The two small files are parsed here and handed to simmr_taxeval_reset; both big files go up in pieces, the truth
+// through simmr_taxeval_truth_add and, behind the plan, the classifier's through simmr_taxeval_add; the three texts are written
+// from the integer tables on the host.  Nothing is written unless all of it succeeded.
+struct TaxevalHandle {
+  simmr_taxeval* h = nullptr;
+  ~TaxevalHandle() { simmr_taxeval_destroy(h); }
+};
+static bool slurp(const std::string& path, std::string* out) {
+  std::ifstream in(path, std::ios::binary);
+  if (!in) return false;
+  out->assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
+  return true;
+}
+static int run_eval_classified(const CliArgs& args) {
+  std::string text, perr;
+  std::vector<uint32_t> taxid, parent, gtax;
+  std::vector<uint8_t> rank;
+  std::vector<std::string> gid;
+  if (!slurp(args.eval_taxonomy, &text)) return die("--eval-taxonomy: cannot open " + args.eval_taxonomy);
+  if (!taxeval_parse_nodes(text.data(), text.size(), &taxid, &parent, &rank, &perr)) return die("--eval-taxonomy: " + args.eval_taxonomy + ": " + perr);
+  if (!slurp(args.eval_genome_taxa, &text)) return die("--eval-genome-taxa: cannot open " + args.eval_genome_taxa);
+  if (!taxeval_parse_map(text.data(), text.size(), &gid, &gtax, &perr)) return die("--eval-genome-taxa: " + args.eval_genome_taxa + ": " + perr);
+  text.clear();
+  for (const std::string* f : {&args.eval_classified_truth, &args.eval_classified}) {
+    FILE* fp = fopen(f->c_str(), "rb");
+    if (!fp) return die(std::string(f == &args.eval_classified ? "--eval-classified" : "--eval-classified-truth") + ": cannot open " + *f);
+    fclose(fp);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  TaxevalHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_taxeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-classified: ") + simmr_last_error(eng));
+  std::vector<const char*> ids;
+  for (const std::string& s : gid) ids.push_back(s.c_str());
+  const simmr_taxeval_config cfg{taxid.size(), taxid.data(), parent.data(), rank.data(), gid.size(), ids.data(), gtax.data()};
+  if (simmr_taxeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-taxonomy: ") + simmr_last_error(eng));
+  float ms = 0;
+  info("Parsing " + args.eval_classified_truth);
+  if (int rc = sam_file_pieces("--eval-classified-truth", args.eval_classified_truth, [&](const uint8_t* d, size_t n) {
+        if (simmr_taxeval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_taxeval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
+          return die(std::string("--eval-classified-truth: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  uint64_t n_entries = 0;
+  if (simmr_taxeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-classified-truth: ") + simmr_last_error(eng));
+  info("Parsing " + args.eval_classified);
+  if (int rc = sam_file_pieces("--eval-classified", args.eval_classified, [&](const uint8_t* d, size_t n) {
+        if (simmr_taxeval_add(ev.h, d, n) != SIMMR_OK || simmr_last_taxeval_ms(ev.h, &ms) != SIMMR_OK)
+          return die(std::string("--eval-classified: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  simmr_taxeval_counts c{};
+  static_assert(sizeof(c) == TAXEVAL_N_COUNTS * sizeof(uint64_t) && TAXEVAL_RANKS == SIMMR_TAXEVAL_RANKS && TAXEVAL_CLASSES == SIMMR_TAXEVAL_CLASSES,
+                "the report names every count, rank and class");
+  std::vector<uint64_t> by_rank(TAXEVAL_RANKS * TAXEVAL_CLASSES), reads_by_rank(TAXEVAL_RANKS * TAXEVAL_CLASSES);
+  if (simmr_taxeval_read(ev.h, &c, by_rank.data(), reads_by_rank.data()) != SIMMR_OK) return die(std::string("--eval-classified: ") + simmr_last_error(eng));
+  // the per-taxon rows: the clade sums in taxid order, and the ranks put into that order here
+  const uint64_t nn = taxid.size(), nn1 = std::max<uint64_t>(nn, 1);
+  std::vector<uint32_t> h_taxid(nn1);
+  std::vector<uint64_t> h_sums(3 * nn1);
+  {
+    GrowBuf d_taxid, d_sums;
+    uint8_t *t = d_taxid.room(nn1 * 4), *s = d_sums.room(3 * nn1 * 8);
+    if (!t || !s) return die("--eval-classified: device allocation failed");
+    uint64_t* const sums = (uint64_t*)s;
+    if (simmr_taxeval_taxa(ev.h, (uint32_t*)t, sums, sums + nn1, sums + 2 * nn1, nn) != SIMMR_OK) return die(std::string("--eval-classified: ") + simmr_last_error(eng));
+    if (hipMemcpy(h_taxid.data(), t, nn1 * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(h_sums.data(), s, 3 * nn1 * 8, hipMemcpyDeviceToHost) != hipSuccess)
+      return die("--eval-classified: copy from the device failed");
+  }
+  std::vector<uint32_t> order(nn);
+  for (uint32_t i = 0; i < nn; i++) order[i] = i;
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return taxid[a] < taxid[b]; });
+  std::vector<uint8_t> s_rank(nn1, 0);
+  for (uint64_t i = 0; i < nn; i++) s_rank[i] = rank[order[i]];
+  std::string rows;
+  if (!args.eval_classified_reads.empty()) {
+    // a genome's row is its place among the sorted ids; the ranks its lineage has come from simmr_taxeval_lineage
+    std::vector<uint32_t> g_order(gid.size());
+    for (uint32_t i = 0; i < gid.size(); i++) g_order[i] = i;
+    std::sort(g_order.begin(), g_order.end(), [&](uint32_t a, uint32_t b) { return gid[a] < gid[b]; });
+    std::vector<std::string> s_gid;
+    std::vector<uint32_t> has;
+    for (uint32_t g : g_order) {
+      uint32_t lin[TAXEVAL_RANKS] = {}, mask = 0;
+      if (simmr_taxeval_lineage(ev.h, gtax[g], lin, nullptr) != SIMMR_OK) return die(std::string("--eval-classified-reads: ") + simmr_last_error(eng));
+      for (size_t r = 0; r < TAXEVAL_RANKS; r++) mask |= lin[r] ? 1u << r : 0u;
+      s_gid.push_back(gid[g]);
+      has.push_back(mask);
+    }
+    GrowBuf d_id, d_narrow;
+    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
+    uint8_t *k = d_id.room(n1 * 8), *nw = d_narrow.room(4 * n1 * 4);
+    if (!k || !nw) return die("--eval-classified-reads: device allocation failed");
+    uint32_t* const narrow = (uint32_t*)nw;
+    if (simmr_taxeval_emit(ev.h, (uint64_t*)k, narrow, narrow + n1, narrow + 2 * n1, narrow + 3 * n1, n_entries) != SIMMR_OK)
+      return die(std::string("--eval-classified-reads: ") + simmr_last_error(eng));
+    std::vector<uint64_t> hk(n1);
+    std::vector<uint32_t> hn(4 * n1);
+    if (hipMemcpy(hk.data(), k, n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), nw, 4 * n1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
+      return die("--eval-classified-reads: copy from the device failed");
+    rows = taxeval_read_rows(s_gid, has, hk.data(), hn.data(), hn.data() + n1, hn.data() + 2 * n1, hn.data() + 3 * n1, n_entries);
+  }
+  std::string err;
+  OutFile report(args.eval_classified_report, false);
+  report.append(taxeval_report((const uint64_t*)&c, by_rank.data(), reads_by_rank.data(), s_rank.data(), h_sums.data(), h_sums.data() + nn1, nn));
+  if (!report.close(&err)) return die("--eval-classified-report: " + err);
+  if (!args.eval_classified_reads.empty()) {
+    OutFile reads(args.eval_classified_reads, false);
+    reads.append(rows);
+    if (!reads.close(&err)) return die("--eval-classified-reads: " + err);
+  }
+  if (!args.eval_classified_taxa.empty()) {
+    OutFile taxa(args.eval_classified_taxa, false);
+    taxa.append(taxeval_taxa_rows(h_taxid.data(), s_rank.data(), h_sums.data(), h_sums.data() + nn1, h_sums.data() + 2 * nn1, nn));
+    if (!taxa.close(&err)) return die("--eval-classified-taxa: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_entries) + " reads (" + n(c.truth_paired) + " paired) of " + n(gid.size()) + " genomes; " + n(nn) + " taxa");
+  info("Calls: " + n(c.records) + " records: " + n(c.scored) + " scored, " + n(c.unclassified) + " unclassified, " + n(c.unknown_taxon) +
+       " with a taxid that is no node, " + n(c.unknown_read) + " of unknown reads");
+  info("Reads: " + n(c.missing) + " without a record, " + n(c.multiple) + " with more records than lines");
+  info("Wrote " + args.eval_classified_report);
+  return 0;
+}
+
 static int run_main(int argc, char** argv) {
   CliArgs args;
   std::string err;
@@ -1362,6 +1492,7 @@ static int run_main(int argc, char** argv) {
   if (!args.eval_sam.empty()) return run_eval_sam(args);
   if (!args.eval_overlaps.empty()) return run_eval_overlaps(args);
   if (!args.eval_vcf.empty()) return run_eval_vcf(args);
+  if (!args.eval_classified.empty()) return run_eval_classified(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

@@ -190,6 +190,39 @@ std::string vcfeval_report(const uint64_t* counts, const uint64_t* by_qual, cons
 // tab-separated.  A row whose name index is outside `names` gets "?".
 std::string vcfeval_site_rows(const std::vector<std::string>& names, const uint64_t* key, const uint32_t* alleles, const uint32_t* ad, const uint32_t* best,
                               const uint32_t* hits, size_t n);
+// ---- --eval-classified: the host's share (the files that are small, and the three texts) ----
+constexpr size_t TAXEVAL_N_COUNTS = 13, TAXEVAL_RANKS = 8, TAXEVAL_CLASSES = 5;
+// The rank code of a rank's name as NCBI's nodes.dmp spells it: 1 domain or superkingdom, 2 phylum, 3 class, 4 order, 5 family,
+// 6 genus, 7 species, 8 strain; 0 any other text.  ... and the name a code is written with ("no_rank" for 0).
+uint8_t taxeval_rank_code(const std::string& name);
+const char* taxeval_rank_name(uint32_t code);
+// The nodes of --eval-taxonomy from text[0, n): a line is "taxid | parent | rank | ..." with the separator "<tab>|<tab>" (NCBI's
+// nodes.dmp; a "<tab>|" that ends the line is dropped) or "taxid <tab> parent <tab> rank"; the first three fields are read, empty
+// lines are skipped.  false, and the line's number in *err: a line without three fields, or a taxid or parent that is no number
+// of 1 to 10 digits below 2^32.
+bool taxeval_parse_nodes(const char* text, size_t n, std::vector<uint32_t>* taxid, std::vector<uint32_t>* parent, std::vector<uint8_t>* rank, std::string* err);
+// The map of --eval-genome-taxa from text[0, n): "genome_id <tab> taxid" a line; a first line whose second field is no number is a
+// header; empty lines are skipped.  false, and the line's number in *err: a line without two fields, or a taxid that is no such number.
+bool taxeval_parse_map(const char* text, size_t n, std::vector<std::string>* genome_id, std::vector<uint32_t>* taxid, std::string* err);
+// The file of --eval-classified-report: the counts of struct simmr_taxeval_counts as "#name\tvalue" lines in the struct's order
+// (counts[TAXEVAL_N_COUNTS]); an R row per rank with by_rank[8][5] and reads_by_rank[8][5] (absent, unclassified, wrong, above,
+// correct); a P row per rank with precision = correct / (correct + wrong), sensitivity = correct / (unclassified + wrong + above +
+// correct) and F1 = 2 P S / (P + S), on the records and then on the reads, "%.6f", "NA" where a denominator is 0; an A row per rank
+// with the nodes of that rank and the L1 distance between the true and the called relative abundances over them, from the clade
+// sums (rank_code, true_sum, called_sum: n_nodes entries in taxid order), each side normalised by its own sum at that rank, "NA"
+// where either sum is 0.  Each block has a header line that starts with '#'.
+std::string taxeval_report(const uint64_t* counts, const uint64_t* by_rank, const uint64_t* reads_by_rank, const uint8_t* rank_code, const uint64_t* true_sum,
+                           const uint64_t* called_sum, size_t n_nodes);
+// The rows of --eval-classified-reads for n truth entries in id order: the read id, the genome id (genome_ids: sorted, the row is
+// its index; "?" outside), the lines behind the entry, its records, and the best class at each of the 8 ranks: the highest set bit
+// of the rank's nibble of seen, plus one; for an entry without a record 1 where the genome's lineage has the rank (genome_has[row]
+// bit r - 1) and 0 where not.
+std::string taxeval_read_rows(const std::vector<std::string>& genome_ids, const std::vector<uint32_t>& genome_has, const uint64_t* id, const uint32_t* genome,
+                              const uint32_t* mates, const uint32_t* seen, const uint32_t* hits, size_t n);
+// The rows of --eval-classified-taxa: for every node (taxid order) with a clade sum that is not zero its taxid, the name of its rank,
+// true, called, both, precision = both / called and recall = both / true ("%.6f", or "NA").
+std::string taxeval_taxa_rows(const uint32_t* taxid, const uint8_t* rank_code, const uint64_t* true_sum, const uint64_t* called_sum, const uint64_t* both_sum,
+                              size_t n_nodes);
 // `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
 // (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
 // ascend, and its text lies at `offset` of the byte source.
@@ -497,6 +530,13 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string eval_vcf_truth;   // --eval-vcf-truth FILE: the strain's sites (the file of --strain-vcf)
   std::string eval_vcf_report;  // --eval-vcf-report FILE: the counts, precision, recall, the rows by QUAL and by the alternate allele's reads as a TSV
   std::string eval_vcf_sites;   // --eval-vcf-sites FILE: a row per true site
+  std::string eval_classified;         // --eval-classified FILE: no simulation; a read classifier's per-read output scored against --truth (simmr_taxeval_*)
+  std::string eval_classified_truth;   // --eval-classified-truth FILE: the file of --truth
+  std::string eval_taxonomy;           // --eval-taxonomy FILE: nodes.dmp, or taxid parent rank as a TSV
+  std::string eval_genome_taxa;        // --eval-genome-taxa FILE: genome_id taxid as a TSV
+  std::string eval_classified_report;  // --eval-classified-report FILE: the counts, a row per rank, precision / sensitivity / F1, the profile's L1 distance
+  std::string eval_classified_reads;   // --eval-classified-reads FILE: a row per true read
+  std::string eval_classified_taxa;    // --eval-classified-taxa FILE: a row per taxon with reads
   bool eval_vcf_filtered = false;  // --eval-vcf-filtered: score the records whose FILTER is neither "." nor PASS too
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
