@@ -1673,6 +1673,110 @@ int simmr_taxeval_taxa(simmr_taxeval* h, uint32_t* taxid_dev, uint64_t* true_dev
  * Synchronises the stream.  A run of adds with no synchronising call of this object between them is timed as one span. */
 int simmr_last_taxeval_ms(simmr_taxeval* h, float* ms);
 
+/* ---- an assembler's contigs scored against the gold-standard assembly: two FASTA texts in HBM, compared by canonical k-mers -----
+ * Replaces nothing in the reference.  The fifth truth a run writes is the gold-standard assembly (simmr_regions_*,
+ * `--gold-assembly`): the stretches of every genome that the reads covered.  That FASTA and an assembler's contigs go in, and
+ * integer tables come out, alignment-free: how many of each genome's distinct k-mers the contigs hold (completeness), how many of
+ * the contigs' k-mers are in no genome (the consensus quality), and for every contig the genome most of its k-mers vote for.  No
+ * simulation, no genome: like simmr_mapeval_*.
+ *
+ * Text.  Plain FASTA (no gzip).  One add holds whole records: its first non-empty line starts with '>', and the caller cuts a
+ * file in front of a '>' that begins a line, at most SIMMR_ASMEVAL_MAX_BYTES a call.  A line that starts with '>' is a header;
+ * every other non-empty line is a sequence line of the record above it.  Empty lines are skipped.  A '\r' directly before '\n'
+ * is not a base (a line that holds nothing else is empty); the last line may lack its '\n', and then a '\r' that ends it is a
+ * byte like any other.  A '>' that does not begin a line is an ordinary byte of the line it stands in.
+ * Malformed (sticky; simmr_asmeval_read answers SIMMR_EINVAL, simmr_asmeval_truth_plan too for the truth): a sequence line with a
+ * base in front of the add's first header.
+ *
+ * Bases and k-mers.  Every byte of a sequence line is one base position, apart from the line end.  ACGTacgt are the classes
+ * 0 1 2 3 with case folded; any other byte is an invalid base.  k is odd and lies between 15 and 31, so no k-mer is its own
+ * reverse complement.  A k-mer is k consecutive valid bases of one record; line ends are transparent to it, and a record shorter
+ * than k has none.  Its first base is the most significant digit of its 2k-bit value, and its key is the smaller of that value
+ * and the value of its reverse complement.
+ *
+ * Truth side.  The genome of a truth record is the header's text between '>' and the first '|' of its first word (the word ends
+ * at a blank, a tab or the line's end): `--gold-assembly` writes ">GENOME|SEQ:start-end depth_sum=N".  The caller hands in the
+ * genome names once (simmr_asmeval_config), under the rule and the limits of simmr_mapeval_reset, fewer than 2^24 of them; the
+ * library keeps them sorted in a device blob and compares bytes exactly.  The row of a genome is its place in that order.  A
+ * header with no '|' in its first word, or with a prefix that is not among the names, is malformed.  simmr_asmeval_truth_add
+ * appends every k-mer occurrence as (key, genome row).  simmr_asmeval_truth_plan (1) sorts the occurrences by key over 2k bits,
+ * (2) marks the run heads and scans them, (3) compacts the runs into the distinct entries in ascending key order, builds the
+ * lookup table (min(24, bit length of the entries) of the key's top bits) and (4) empties the candidate side and synchronises.
+ * An entry has key, mult (its occurrences) and genome: the one row all its occurrences share, or the row n_genomes ("shared")
+ * where they come from two genomes or more.
+ *
+ * Candidate side.  A contig is a record; its row is its ordinal among the candidate records since the truth plan, in add order
+ * and then text order.  Candidate headers are not read beyond their extent.  Every k-mer of a contig is looked up among the
+ * entries: a miss is novel; a hit is found and hits[entry] += 1 (hits is below 2^32); a hit on a shared entry is also shared; a
+ * hit on an entry of one genome is a vote of the contig for that genome.  top_genome is the genome with the most votes (ties go
+ * to the lowest row) and top_kmers its votes; without a vote they are 0xffffffff and 0.  Six columns per contig: length in
+ * bases (u64, invalid ones included), kmers, found, shared, top_genome, top_kmers (u32).
+ *
+ * Tables (simmr_asmeval_read).  The counts below; the contig classes are exclusive and their sum is records: contigs_short (no
+ * k-mer), contigs_novel (k-mers, none found), contigs_pure (votes, all for one genome), contigs_mixed (votes for two genomes or
+ * more), contigs_shared_only (found k-mers, no vote).  by_genome[n_genomes + 1][SIMMR_ASMEVAL_GENOME_COLS], the last row
+ * "shared": distinct (the entries of that row), distinct_found (those with a hit), over (those whose hits exceed mult: the
+ * assembly holds the k-mer more often than the truth), contigs (whose top_genome is the row) and contig_bases (their lengths);
+ * the shared row has 0 in the last two.
+ * Every output is an integer sum or maximum: the same for any launch geometry, for any cut of either text into adds, and when
+ * any candidate record is replaced by its reverse complement. */
+#define SIMMR_ASMEVAL_MAX_BYTES 0x7fffffffull   /* most bytes of text in one add of either side */
+#define SIMMR_ASMEVAL_GENOME_COLS 5u            /* by_genome: distinct, distinct_found, over, contigs, contig_bases */
+
+typedef struct simmr_asmeval simmr_asmeval;
+
+typedef struct simmr_asmeval_config {   /* HOST memory */
+  uint32_t n_genomes;
+  uint32_t k;                           /* odd, 15 .. 31 */
+  uint32_t plain_search;                /* 0: a lookup goes through the table of the key's top bits; else: a binary search over all entries (the same answers) */
+  const char* const* genome;            /* n_genomes genome names, NUL-terminated, in any order */
+} simmr_asmeval_config;
+
+typedef struct simmr_asmeval_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_records, truth_bases, truth_invalid, truth_kmers;   /* cumulative since the reset; kmers = occurrences */
+  uint64_t truth_distinct, truth_shared_distinct;                    /* the entries of the plan in force, and those of two genomes or more */
+  uint64_t records, bases, invalid, kmers, found, shared, novel;     /* the candidate side, since the last truth plan; novel = kmers - found */
+  uint64_t contigs_short, contigs_novel, contigs_pure, contigs_mixed, contigs_shared_only;
+} simmr_asmeval_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_vcfeval_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error). */
+int simmr_asmeval_create(simmr_engine* e, simmr_asmeval** out);
+void simmr_asmeval_destroy(simmr_asmeval* h);
+/* Takes the names, k and the lookup, and empties both sides.  Synchronises.  SIMMR_EINVAL: a NULL argument, a name given twice, a
+ * k that is even, below 15 or above 31.  SIMMR_ENOTSUP: a name that is empty, longer than 254 bytes or no SAM reference name.
+ * SIMMR_ERANGE: 2^24 names or more. */
+int simmr_asmeval_reset(simmr_asmeval* h, const simmr_asmeval_config* cfg);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for a k-mer occurrence per byte of text grows with the object.
+ * SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL text with n_bytes > 0.  SIMMR_ENOTSUP: n_bytes above SIMMR_ASMEVAL_MAX_BYTES. */
+int simmr_asmeval_truth_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes);
+/* The plan, in the order stated above.  Synchronises.  *n_entries (may be NULL) = the distinct entries.  SIMMR_EINVAL: a malformed
+ * truth text.  SIMMR_ERANGE: 2^31 k-mer occurrences or more since the reset. */
+int simmr_asmeval_truth_plan(simmr_asmeval* h, uint64_t* n_entries);
+/* Scores the records of text[0 .. n_bytes) (DEVICE, as above) against the plan.  SYNCHRONISES, three times: it needs the add's
+ * records and bases on the host for the contig columns, and the number of its votes for their sort and scan.  SIMMR_ESTATE: no
+ * truth plan in force.  SIMMR_ERANGE: 2^31 contigs or more since the plan.  SIMMR_EINVAL, SIMMR_ENOTSUP: as
+ * simmr_asmeval_truth_add. */
+int simmr_asmeval_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts and by_genome_host[n_genomes + 1][SIMMR_ASMEVAL_GENOME_COLS] (HOST, either may be NULL).  Synchronises.  The
+ * candidate counts, the contig classes and by_genome are made here, by reductions over the entry and contig columns that combine
+ * the first 1024 rows in LDS.  SIMMR_EINVAL: a malformed text on either side since the reset (nothing is written).
+ * SIMMR_ESTATE: no reset yet. */
+int simmr_asmeval_read(simmr_asmeval* h, simmr_asmeval_counts* counts, uint64_t* by_genome_host);
+/* The entries in ascending key order, four columns (DEVICE, capacity entries each, any may be NULL): key, genome, mult, hits.
+ * Synchronises.  SIMMR_ESTATE: no truth plan.  SIMMR_ERANGE, nothing written: capacity < n_entries. */
+int simmr_asmeval_emit(simmr_asmeval* h, uint64_t* key_dev, uint32_t* genome_dev, uint32_t* mult_dev, uint32_t* hits_dev, uint64_t capacity);
+/* The contigs in row order, six columns (DEVICE, capacity entries each, any may be NULL).  *n_contigs (may be NULL) = the contigs
+ * since the plan, written whenever a plan is in force: a call with capacity 0 asks for it.  Synchronises.  SIMMR_ESTATE: no truth
+ * plan.  SIMMR_ERANGE, no column written: capacity < the contigs. */
+int simmr_asmeval_contigs(simmr_asmeval* h, uint64_t* length_dev, uint32_t* kmers_dev, uint32_t* found_dev, uint32_t* shared_dev, uint32_t* top_genome_dev,
+                          uint32_t* top_kmers_dev, uint64_t capacity, uint64_t* n_contigs);
+/* HIP-event time (ms) of the device work since the last reset: the truth adds, the plans and the adds.  Synchronises the stream.
+ * A run of adds with no synchronising call of this object between them (the plan or this call) is timed as one span; the host's
+ * waits inside simmr_asmeval_add lie inside that span.  *plan_sort_ms (may be NULL) = the sort's share of the last plan. */
+int simmr_last_asmeval_ms(simmr_asmeval* h, float* ms, float* plan_sort_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,6 +292,23 @@ class TaxevalConfig(C.Structure):
                 ("n_genomes", C.c_uint64), ("genome_id", C.POINTER(C.c_char_p)), ("genome_taxid", C.POINTER(C.c_uint32))]
 
 
+ASMEVAL_COUNTS = ("truth_records", "truth_bases", "truth_invalid", "truth_kmers", "truth_distinct", "truth_shared_distinct", "records", "bases",
+                  "invalid", "kmers", "found", "shared", "novel", "contigs_short", "contigs_novel", "contigs_pure", "contigs_mixed",
+                  "contigs_shared_only")
+ASMEVAL_GENOME_COLS = ("distinct", "distinct_found", "over", "contigs", "contig_bases")  # SIMMR_ASMEVAL_GENOME_COLS
+ASMEVAL_MAX_BYTES = 0x7fffffff  # SIMMR_ASMEVAL_MAX_BYTES
+
+
+class AsmevalCounts(C.Structure):
+    """struct simmr_asmeval_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in ASMEVAL_COUNTS]
+
+
+class AsmevalConfig(C.Structure):
+    """struct simmr_asmeval_config (host memory)"""
+    _fields_ = [("n_genomes", C.c_uint32), ("k", C.c_uint32), ("plain_search", C.c_uint32), ("genome", C.POINTER(C.c_char_p))]
+
+
 class MapevalConfig(C.Structure):
     """struct simmr_mapeval_config (host memory)"""
     _fields_ = [("n_names", C.c_uint32), ("min_overlap_pct", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
@@ -448,6 +465,16 @@ SYMBOLS = {
     "simmr_vcfeval_read": (C.c_int, [C.c_void_p, _P(VcfevalCounts), _P(C.c_uint64), _P(C.c_uint64)]),
     "simmr_vcfeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_last_vcfeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
+    "simmr_asmeval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_asmeval_destroy": (None, [C.c_void_p]),
+    "simmr_asmeval_reset": (C.c_int, [C.c_void_p, _P(AsmevalConfig)]),
+    "simmr_asmeval_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_asmeval_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "simmr_asmeval_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_asmeval_read": (C.c_int, [C.c_void_p, _P(AsmevalCounts), _P(C.c_uint64)]),
+    "simmr_asmeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_asmeval_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "simmr_last_asmeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float), _P(C.c_float)]),
     "simmr_taxeval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "simmr_taxeval_destroy": (None, [C.c_void_p]),
     "simmr_taxeval_reset": (C.c_int, [C.c_void_p, _P(TaxevalConfig)]),

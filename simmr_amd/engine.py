@@ -414,6 +414,115 @@ class VcfEval:
                 self.engine._mapevals.remove(self)
 
 
+class AsmEval:
+    """An assembler's contigs scored against the gold-standard assembly on the device (simmr_asmeval_*, include/simmr_hip.h states
+    the rules).  truth_add() the truth FASTA (the file of --gold-assembly), truth_plan(), add() the contigs, then read(), entries()
+    and contigs().  A text is bytes (copied up) or a contiguous CUDA uint8 tensor and holds whole records; truth_add only enqueues,
+    so every text is kept until a call that synchronises."""
+
+    def __init__(self, engine: "Engine", genomes, k: int = 31, plain_search: bool = False):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        self.n_entries = self.n_genomes = 0
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_asmeval_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(genomes, k, plain_search)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, genomes, k: int = 31, plain_search: bool = False):
+        raw = [n if isinstance(n, bytes) else str(n).encode() for n in genomes]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        cfg = _abi.AsmevalConfig(len(raw), int(k), 1 if plain_search else 0, arr)
+        try:
+            self._check(self.lib.simmr_asmeval_reset(self._h, C.byref(cfg)))
+        finally:
+            self._texts = []  # the reset has synchronised
+        self.n_entries, self.n_genomes, self.k = 0, len(raw), int(k)
+
+    _text = Mapeval._text
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_asmeval_truth_add(self._h, p, n))
+
+    def truth_plan(self) -> int:
+        n = C.c_uint64(0)
+        self.n_entries = 0
+        try:
+            self._check(self.lib.simmr_asmeval_truth_plan(self._h, C.byref(n)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_entries = int(n.value)
+        return self.n_entries
+
+    def add(self, text):
+        p, n = self._text(text)
+        try:
+            self._check(self.lib.simmr_asmeval_add(self._h, p, n))
+        finally:
+            self._texts = []  # the add has synchronised
+
+    def read(self):
+        """(counts by the names of struct simmr_asmeval_counts, by_genome as an (n_genomes + 1, 5) uint64 array: distinct,
+        distinct_found, over, contigs, contig_bases; the last row is "shared")"""
+        c = _abi.AsmevalCounts()
+        by = np.zeros((self.n_genomes + 1, len(_abi.ASMEVAL_GENOME_COLS)), dtype=np.uint64)
+        try:
+            self._check(self.lib.simmr_asmeval_read(self._h, C.byref(c), by.ctypes.data_as(C.POINTER(C.c_uint64))))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.ASMEVAL_COUNTS}, by
+
+    def entries(self):
+        """The distinct k-mers of the truth ascending by key, as numpy arrays: key (uint64), genome, mult, hits (uint32)"""
+        torch = _torch()
+        n, dev = self.n_entries, self.engine.device
+        key = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        narrow = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(3)]
+        self._check(self.lib.simmr_asmeval_emit(self._h, *[C.c_void_p(t.data_ptr()) for t in [key] + narrow], n))
+        self._texts = []
+        return (key[:n].cpu().numpy().view(np.uint64),) + tuple(t[:n].cpu().numpy().view(np.uint32) for t in narrow)
+
+    def n_contigs(self) -> int:
+        n = C.c_uint64(0)
+        rc = self.lib.simmr_asmeval_contigs(self._h, None, None, None, None, None, None, 0, C.byref(n))
+        if rc not in (0, -34):  # (SIMMR_ERANGE: capacity 0 asks for the number alone)
+            self._check(rc)
+        return int(n.value)
+
+    def contigs(self):
+        """The contigs in row order, as numpy arrays: length (uint64), kmers, found, shared, top_genome, top_kmers (uint32)"""
+        torch = _torch()
+        n, dev = self.n_contigs(), self.engine.device
+        length = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        narrow = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(5)]
+        self._check(self.lib.simmr_asmeval_contigs(self._h, *[C.c_void_p(t.data_ptr()) for t in [length] + narrow], n, None))
+        self._texts = []
+        return (length[:n].cpu().numpy().view(np.uint64),) + tuple(t[:n].cpu().numpy().view(np.uint32) for t in narrow)
+
+    def ms(self):
+        """(the device time of the unit's calls since the reset, the sort's share of the last plan), in ms"""
+        a, b = C.c_float(), C.c_float()
+        self._check(self.lib.simmr_last_asmeval_ms(self._h, C.byref(a), C.byref(b)))
+        self._texts = []
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_asmeval_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
 class TaxEval:
     """A read classifier's calls scored against each read's true genome on the device (simmr_taxeval_*, include/simmr_hip.h
     states the rules).  truth_add() the truth text (the file of --truth), truth_plan(), add() the classifier's per-read text, then
@@ -1354,6 +1463,34 @@ class Engine:
                 ev.add(t)
             counts, by_rank, reads_by_rank = ev.read()
             return counts, by_rank, reads_by_rank, ev.reads(), ev.taxa()
+        finally:
+            ev.close()
+
+    # -- an assembler's contigs against the gold-standard assembly ---------------------------
+    def assembly_eval_open(self, genomes, k: int = 31, plain_search: bool = False) -> "AsmEval":
+        """An evaluation object (simmr_asmeval_*) over the genome names.  Closed by its close(), or by the engine's before the
+        engine goes (it is kept in the list of the mapeval objects, which the engine closes first)."""
+        m = AsmEval(self, genomes, k, plain_search)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
+
+    def assembly_eval(self, truth_bytes, contigs_bytes, genomes, k: int = 31):
+        """Scores the FASTA `contigs_bytes` against the gold-standard FASTA `truth_bytes` (each bytes, a CUDA uint8 tensor, or a
+        list of those: an add each, of whole records).  Returns (counts as a dict, by_genome (n_genomes + 1, 5), (key, genome,
+        mult, hits) of the entries in key order, (length, kmers, found, shared, top_genome, top_kmers) of the contigs)."""
+        def adds(text):
+            return list(text) if isinstance(text, (list, tuple)) else [text]
+        ev = self.assembly_eval_open(genomes, k)
+        try:
+            for t in adds(truth_bytes):
+                ev.truth_add(t)
+            ev.truth_plan()
+            for t in adds(contigs_bytes):
+                ev.add(t)
+            counts, by_genome = ev.read()
+            return counts, by_genome, ev.entries(), ev.contigs()
         finally:
             ev.close()
 

@@ -806,6 +806,16 @@ std::string usage() {
          "                            the L1 distance between the true and the called abundance profile (by reads)\n"
          "            --eval-classified-reads <FILE>  every true read: id, genome, lines, records, the best class at each of the 8 ranks\n"
          "            --eval-classified-taxa <FILE>  every taxon with reads: taxid, rank, true, called, both (clade sums), precision, recall\n"
+         "            --eval-assembly <FILE>  no simulation: score an assembler's contigs (plain FASTA) against the gold-standard assembly of\n"
+         "                            --eval-assembly-truth by canonical k-mers, looked up on the device: completeness per genome, the\n"
+         "                            k-mers in no genome and the consensus quality they give, the genome of every contig; takes only\n"
+         "                            --eval-assembly-truth, --eval-assembly-report, --eval-assembly-contigs, --eval-assembly-k and --device\n"
+         "                            (no genomes, no --output, not --devices)\n"
+         "            --eval-assembly-truth <FILE>  the file of --gold-assembly; the genomes are the header prefixes in front of '|'\n"
+         "            --eval-assembly-report <FILE>  the result as a TSV: the counts as #name value lines, #completeness, #qv, the contiguity\n"
+         "                            of both sides (records, bases, longest, N50) and a G row per genome\n"
+         "            --eval-assembly-contigs <FILE>  every contig: name, length, kmers, found, shared, top genome row, its votes, its name\n"
+         "            --eval-assembly-k <K>  k-mer size, odd, 15 .. 31 [default: 31]\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -984,6 +994,91 @@ std::string vcfeval_site_rows(const std::vector<std::string>& names, const uint6
     out += row < names.size() ? names[row] : std::string("?");
     out += "\t" + std::to_string((unsigned long long)pos) + "\t" + "ACGT"[(alleles[i] >> 2) & 3u] + "\t" + "ACGT"[alleles[i] & 3u] + "\t" + std::to_string(ad[i]) +
            "\t" + std::to_string(best[i] >> 8) + "\t" + std::to_string(best[i] & 255u) + "\t" + std::to_string(hits[i]) + "\n";
+  }
+  return out;
+}
+
+// ---- --eval-assembly ------------------------------------------------------------------------------------------------------------------
+void asmeval_fasta_records(const char* text, size_t n, std::vector<std::string>* first_word, std::vector<uint64_t>* length) {
+  bool any = false;
+  for (size_t a = 0; a < n;) {
+    size_t b = a;
+    while (b < n && text[b] != '\n') b++;
+    size_t e = b;
+    if (b < n && e > a && text[e - 1] == '\r') e--;  // (only directly before a '\n')
+    if (e > a && text[a] == '>') {
+      size_t w = a + 1;
+      while (w < e && text[w] != ' ' && text[w] != '\t' && text[w] != '\r') w++;
+      first_word->emplace_back(text + a + 1, w - (a + 1));
+      length->push_back(0);
+      any = true;
+    } else if (any) {
+      length->back() += e - a;
+    }
+    a = b + 1;
+  }
+}
+
+void asmeval_contiguity(const uint64_t* length, size_t n, uint64_t out[4]) {
+  std::vector<uint64_t> ls(length, length + n);
+  std::sort(ls.begin(), ls.end(), std::greater<uint64_t>());
+  uint64_t total = 0, run = 0;
+  for (uint64_t x : ls) total += x;
+  out[0] = n; out[1] = total; out[2] = n ? ls[0] : 0; out[3] = 0;
+  for (uint64_t x : ls) {
+    run += x;
+    if (2 * run >= total) { out[3] = x; break; }
+  }
+}
+
+std::string asmeval_report(const uint64_t* counts, uint32_t k, const std::vector<std::string>& genomes, const uint64_t* by_genome, const uint64_t* truth_length,
+                           size_t n_truth, const uint64_t* contig_length, size_t n_contigs) {
+  static const char* const NAMES[ASMEVAL_N_COUNTS] = {"truth_records", "truth_bases", "truth_invalid", "truth_kmers", "truth_distinct", "truth_shared_distinct",
+                                                      "records", "bases", "invalid", "kmers", "found", "shared", "novel", "contigs_short", "contigs_novel",
+                                                      "contigs_pure", "contigs_mixed", "contigs_shared_only"};
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  auto frac = [&](uint64_t num, uint64_t den) -> std::string {
+    char text[64] = "NA";
+    if (den != 0) snprintf(text, sizeof text, "%.6f", (double)num / (double)den);
+    return text;
+  };
+  std::string out;
+  for (size_t i = 0; i < ASMEVAL_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + n(counts[i]) + "\n";
+  out += "#k\t" + std::to_string(k) + "\n";
+  uint64_t distinct = 0, distinct_found = 0;
+  for (size_t g = 0; g <= genomes.size(); g++) {
+    distinct += by_genome[g * ASMEVAL_GENOME_COLS];
+    distinct_found += by_genome[g * ASMEVAL_GENOME_COLS + 1];
+  }
+  out += "#completeness\t" + n(distinct_found) + "/" + n(distinct) + "\t" + frac(distinct_found, distinct) + "\n";
+  const uint64_t kmers = counts[9], novel = counts[12];
+  char qv[64] = "NA";
+  if (kmers != 0 && novel == 0) snprintf(qv, sizeof qv, "inf");
+  else if (kmers != 0) snprintf(qv, sizeof qv, "%.4f", -10.0 * log10(1.0 - pow(1.0 - (double)novel / (double)kmers, 1.0 / (double)k)));
+  out += std::string("#qv\t") + qv + "\n";
+  uint64_t c[4];
+  asmeval_contiguity(truth_length, n_truth, c);
+  out += "#truth_contiguity\t" + n(c[0]) + "\t" + n(c[1]) + "\t" + n(c[2]) + "\t" + n(c[3]) + "\n";
+  asmeval_contiguity(contig_length, n_contigs, c);
+  out += "#contigs_contiguity\t" + n(c[0]) + "\t" + n(c[1]) + "\t" + n(c[2]) + "\t" + n(c[3]) + "\n";
+  out += "#G\tgenome\tdistinct\tdistinct_found\tover\tcontigs\tcontig_bases\tcompleteness\n";
+  for (size_t g = 0; g <= genomes.size(); g++) {
+    const uint64_t* r = by_genome + g * ASMEVAL_GENOME_COLS;
+    out += "G\t" + (g < genomes.size() ? genomes[g] : std::string("shared"));
+    for (size_t j = 0; j < ASMEVAL_GENOME_COLS; j++) out += "\t" + n(r[j]);
+    out += "\t" + frac(r[1], r[0]) + "\n";
+  }
+  return out;
+}
+
+std::string asmeval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const uint64_t* length, const uint32_t* kmers,
+                                const uint32_t* found, const uint32_t* shared, const uint32_t* top_genome, const uint32_t* top_kmers, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++) {
+    out += i < names.size() ? names[i] : std::string("?");
+    out += "\t" + std::to_string((unsigned long long)length[i]) + "\t" + std::to_string(kmers[i]) + "\t" + std::to_string(found[i]) + "\t" +
+           std::to_string(shared[i]) + "\t" + std::to_string(top_genome[i]) + "\t" + std::to_string(top_kmers[i]) + "\t" +
+           (top_genome[i] < genomes.size() ? genomes[top_genome[i]] : std::string(".")) + "\n";
   }
   return out;
 }
@@ -1181,7 +1276,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax;
+  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax, first_not_asm, first_asm;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -1223,7 +1318,20 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
                           arg == "--eval-classified-report" || arg == "--eval-classified-reads" || arg == "--eval-classified-taxa";
     if (tax_flag && first_tax.empty()) first_tax = arg;
     if (!tax_flag && arg != "--device" && first_not_tax.empty()) first_not_tax = arg;  // what --eval-classified does not take
+    const bool asm_flag = arg == "--eval-assembly" || arg == "--eval-assembly-truth" || arg == "--eval-assembly-report" || arg == "--eval-assembly-contigs" ||
+                          arg == "--eval-assembly-k";
+    if (asm_flag && first_asm.empty()) first_asm = arg;
+    if (!asm_flag && arg != "--device" && first_not_asm.empty()) first_not_asm = arg;  // what --eval-assembly does not take
     if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
+    else if (arg == "--eval-assembly") { if (!file(&a->eval_assembly)) return false; }
+    else if (arg == "--eval-assembly-truth") { if (!file(&a->eval_assembly_truth)) return false; }
+    else if (arg == "--eval-assembly-report") { if (!file(&a->eval_assembly_report)) return false; }
+    else if (arg == "--eval-assembly-contigs") { if (!file(&a->eval_assembly_contigs)) return false; }
+    else if (arg == "--eval-assembly-k") {
+      if (!uint(15, 31)) return false;
+      if (u % 2 == 0) { *err = "invalid value '" + v + "' for '--eval-assembly-k': k is odd"; return false; }
+      a->eval_assembly_k = (uint32_t)u;
+    }
     else if (arg == "--single-reads") a->single_reads = true;
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
     else if (arg == "--genome-file") { if (!need(&v)) return false; a->genome_file = v; }
@@ -1390,6 +1498,17 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     if (a->eval_taxonomy.empty()) { *err = "--eval-classified needs --eval-taxonomy"; return false; }
     if (a->eval_genome_taxa.empty()) { *err = "--eval-classified needs --eval-genome-taxa"; return false; }
     if (a->eval_classified_report.empty()) { *err = "--eval-classified needs --eval-classified-report"; return false; }
+    return true;
+  }
+  if (!first_asm.empty()) {  // the sixth mode without a simulation
+    if (a->eval_assembly.empty()) { *err = first_asm + " needs --eval-assembly"; return false; }
+    if (!first_not_asm.empty()) {
+      *err = "--eval-assembly runs no simulation: it takes only --eval-assembly-truth, --eval-assembly-report, --eval-assembly-contigs, --eval-assembly-k "
+             "and --device ('" + first_not_asm + "' given)";
+      return false;
+    }
+    if (a->eval_assembly_truth.empty()) { *err = "--eval-assembly needs --eval-assembly-truth"; return false; }
+    if (a->eval_assembly_report.empty()) { *err = "--eval-assembly needs --eval-assembly-report"; return false; }
     return true;
   }
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }

@@ -1482,6 +1482,139 @@ static int run_eval_classified(const CliArgs& args) {
   return 0;
 }
 
+// `--eval-assembly CONTIGS.fa --eval-assembly-truth GOLD.fa --eval-assembly-report OUT`: no simulation.  A FASTA file goes to the
+// device in pieces of whole records: a piece is cut in front of the last '>' that begins a line, grows to hold a record that is
+// longer, and may not pass what one add takes.  The host reads every piece once for the records' first words and lengths: the
+// genomes are the distinct prefixes of the truth's first words, in a pass of their own in front of the reset, which needs them.
+static int fasta_file_pieces(const std::string& flag, const std::string& path, const std::function<int(const uint8_t*, const char*, size_t)>& add) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return die(flag + ": cannot open " + path);
+  struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+  GrowBuf dev;
+  std::vector<uint8_t> piece;
+  size_t have = 0;
+  for (bool eof = false; !eof;) {
+    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
+    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
+    if (got < SAM_PIECE) {
+      if (ferror(f)) return die(flag + ": cannot read " + path);
+      eof = true;
+    }
+    have += got;
+    size_t cut = have;
+    if (!eof) {
+      while (cut > 1 && !(piece[cut - 1] == '>' && piece[cut - 2] == '\n')) cut--;
+      cut = cut > 1 ? cut - 1 : 0;  // in front of the '>'
+      if (cut == 0) {
+        if (have > SIMMR_ASMEVAL_MAX_BYTES) { fprintf(stderr, "error: %s: a record of %s is longer than one add takes\n", flag.c_str(), path.c_str()); return 2; }
+        continue;  // one record longer than the piece: read on
+      }
+    }
+    if (cut > SIMMR_ASMEVAL_MAX_BYTES) { fprintf(stderr, "error: %s: a record of %s is longer than one add takes\n", flag.c_str(), path.c_str()); return 2; }
+    if (cut > 0) {
+      if (add) {
+        uint8_t* d = dev.room(cut);
+        if (!d) return die(flag + ": device allocation failed");
+        if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die(flag + ": copy to the device failed");
+        if (int rc = add(d, (const char*)piece.data(), cut)) return rc;
+      }
+    }
+    memmove(piece.data(), piece.data() + cut, have - cut);
+    have -= cut;
+  }
+  return 0;
+}
+
+struct AsmevalHandle {
+  simmr_asmeval* h = nullptr;
+  ~AsmevalHandle() { simmr_asmeval_destroy(h); }
+};
+static int run_eval_assembly(const CliArgs& args) {
+  {
+    FILE* f = fopen(args.eval_assembly.c_str(), "rb");
+    if (!f) return die("--eval-assembly: cannot open " + args.eval_assembly);
+    fclose(f);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  AsmevalHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_asmeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-assembly: ") + simmr_last_error(eng));
+  // the truth file is held on the device piece by piece while the host reads it: the names first, then the adds
+  std::vector<std::string> t_words, c_words;
+  std::vector<uint64_t> t_len, c_len_host;
+  struct Piece { GrowBuf dev; size_t n = 0; };
+  std::vector<std::unique_ptr<Piece>> pieces;
+  info("Parsing " + args.eval_assembly_truth);
+  if (int rc = fasta_file_pieces("--eval-assembly-truth", args.eval_assembly_truth, [&](const uint8_t* d, const char* host, size_t n) {
+        asmeval_fasta_records(host, n, &t_words, &t_len);
+        pieces.emplace_back(new Piece());
+        uint8_t* keep = pieces.back()->dev.room(n);
+        if (!keep || hipMemcpy(keep, d, n, hipMemcpyDeviceToDevice) != hipSuccess) return die("--eval-assembly-truth: device allocation failed");
+        pieces.back()->n = n;
+        return 0;
+      }))
+    return rc;
+  std::vector<std::string> genomes;
+  for (const std::string& w : t_words) {
+    const size_t bar = w.find('|');
+    if (bar == std::string::npos || bar == 0)
+      return die("--eval-assembly-truth: the header '>" + w + "' has no genome in front of a '|': " + args.eval_assembly_truth + " is not a file of --gold-assembly");
+    genomes.push_back(w.substr(0, bar));
+  }
+  std::sort(genomes.begin(), genomes.end());
+  genomes.erase(std::unique(genomes.begin(), genomes.end()), genomes.end());
+  std::vector<const char*> gname;
+  for (const std::string& s : genomes) gname.push_back(s.c_str());
+  const simmr_asmeval_config cfg{(uint32_t)gname.size(), args.eval_assembly_k, 0u, gname.data()};
+  if (simmr_asmeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-assembly-truth: ") + simmr_last_error(eng));
+  for (const auto& p : pieces)
+    if (simmr_asmeval_truth_add(ev.h, (const uint8_t*)p->dev.room(p->n), p->n) != SIMMR_OK) return die(std::string("--eval-assembly-truth: ") + simmr_last_error(eng));
+  uint64_t n_entries = 0;
+  if (simmr_asmeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-assembly-truth: ") + simmr_last_error(eng));
+  pieces.clear();
+  info("Parsing " + args.eval_assembly);
+  if (int rc = fasta_file_pieces("--eval-assembly", args.eval_assembly, [&](const uint8_t* d, const char* host, size_t n) {
+        asmeval_fasta_records(host, n, &c_words, &c_len_host);
+        if (simmr_asmeval_add(ev.h, d, n) != SIMMR_OK) return die(std::string("--eval-assembly: ") + simmr_last_error(eng));  // (synchronises)
+        return 0;
+      }))
+    return rc;
+  simmr_asmeval_counts c{};
+  static_assert(sizeof(c) == ASMEVAL_N_COUNTS * sizeof(uint64_t) && ASMEVAL_GENOME_COLS == SIMMR_ASMEVAL_GENOME_COLS, "the report names every count and column");
+  std::vector<uint64_t> by_genome((genomes.size() + 1) * ASMEVAL_GENOME_COLS);
+  if (simmr_asmeval_read(ev.h, &c, by_genome.data()) != SIMMR_OK) return die(std::string("--eval-assembly: ") + simmr_last_error(eng));
+  const uint64_t nc = c.records, nc1 = std::max<uint64_t>(nc, 1);
+  GrowBuf d_len, d_narrow;
+  uint8_t *dl = d_len.room(nc1 * 8), *dn = d_narrow.room(5 * nc1 * 4);
+  if (!dl || !dn) return die("--eval-assembly: device allocation failed");
+  uint32_t* const narrow = (uint32_t*)dn;
+  if (simmr_asmeval_contigs(ev.h, (uint64_t*)dl, narrow, narrow + nc1, narrow + 2 * nc1, narrow + 3 * nc1, narrow + 4 * nc1, nc, nullptr) != SIMMR_OK)
+    return die(std::string("--eval-assembly: ") + simmr_last_error(eng));
+  std::vector<uint64_t> hl(nc1);
+  std::vector<uint32_t> hn(5 * nc1);
+  if (hipMemcpy(hl.data(), dl, nc1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), dn, 5 * nc1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return die("--eval-assembly: copy from the device failed");
+  std::string err;
+  OutFile report(args.eval_assembly_report, false);
+  report.append(asmeval_report((const uint64_t*)&c, args.eval_assembly_k, genomes, by_genome.data(), t_len.data(), t_len.size(), hl.data(), nc));
+  if (!report.close(&err)) return die("--eval-assembly-report: " + err);
+  if (!args.eval_assembly_contigs.empty()) {
+    OutFile rows(args.eval_assembly_contigs, false);
+    rows.append(asmeval_contig_rows(c_words, genomes, hl.data(), hn.data(), hn.data() + nc1, hn.data() + 2 * nc1, hn.data() + 3 * nc1, hn.data() + 4 * nc1, nc));
+    if (!rows.close(&err)) return die("--eval-assembly-contigs: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_records) + " records, " + n(c.truth_bases) + " bases, " + n(n_entries) + " distinct " + std::to_string(args.eval_assembly_k) + "-mers of " +
+       n(genomes.size()) + " genomes (" + n(c.truth_shared_distinct) + " in more than one)");
+  info("Contigs: " + n(c.records) + " records, " + n(c.bases) + " bases, " + n(c.kmers) + " k-mers: " + n(c.found) + " found, " + n(c.novel) + " in no genome; " +
+       n(c.contigs_pure) + " pure, " + n(c.contigs_mixed) + " mixed, " + n(c.contigs_novel) + " novel, " + n(c.contigs_shared_only) + " shared only, " +
+       n(c.contigs_short) + " shorter than k");
+  info("Wrote " + args.eval_assembly_report);
+  return 0;
+}
+
 static int run_main(int argc, char** argv) {
   CliArgs args;
   std::string err;
@@ -1493,6 +1626,7 @@ static int run_main(int argc, char** argv) {
   if (!args.eval_overlaps.empty()) return run_eval_overlaps(args);
   if (!args.eval_vcf.empty()) return run_eval_vcf(args);
   if (!args.eval_classified.empty()) return run_eval_classified(args);
+  if (!args.eval_assembly.empty()) return run_eval_assembly(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

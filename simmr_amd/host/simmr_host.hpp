@@ -223,6 +223,25 @@ std::string taxeval_read_rows(const std::vector<std::string>& genome_ids, const 
 // true, called, both, precision = both / called and recall = both / true ("%.6f", or "NA").
 std::string taxeval_taxa_rows(const uint32_t* taxid, const uint8_t* rank_code, const uint64_t* true_sum, const uint64_t* called_sum, const uint64_t* both_sum,
                               size_t n_nodes);
+// ---- --eval-assembly: the host's share (the names of the records, the contiguity, the two files) ----
+constexpr size_t ASMEVAL_N_COUNTS = 18, ASMEVAL_GENOME_COLS = 5;
+// The records of the FASTA text[0, n), which begins at a line's start: per header line (a '>' that begins a line) its first word
+// (the text behind '>' up to a blank, a tab, a '\r' or the line's end) and the bytes of the record's sequence lines without their line
+// ends (a '\r' directly before '\n' is part of the line end).  Sequence lines in front of the first header are not counted.
+void asmeval_fasta_records(const char* text, size_t n, std::vector<std::string>* first_word, std::vector<uint64_t>* length);
+// (records, bases, the longest record, N50: the length of the record at which the lengths, longest first, reach half the bases)
+void asmeval_contiguity(const uint64_t* length, size_t n, uint64_t out[4]);
+// The file of --eval-assembly-report: the counts of struct simmr_asmeval_counts as "#name\tvalue" lines in the struct's order
+// (counts[ASMEVAL_N_COUNTS]); "#k"; "#completeness" = the entries with a hit / the entries, as the exact fraction and "%.6f" ("NA"
+// without entries); "#qv" = -10 log10(1 - (1 - novel / kmers)^(1/k)) as "%.4f", "inf" where novel is 0, "NA" without k-mers;
+// "#truth_contiguity" and "#contigs_contiguity" with records, bases, longest and N50; then a header line and a G row per genome
+// (genomes: the sorted names) and one for "shared" with the five columns of by_genome[n + 1][5] and distinct_found / distinct.
+std::string asmeval_report(const uint64_t* counts, uint32_t k, const std::vector<std::string>& genomes, const uint64_t* by_genome, const uint64_t* truth_length,
+                           size_t n_truth, const uint64_t* contig_length, size_t n_contigs);
+// The rows of --eval-assembly-contigs for n contigs in row order: the name (names[i]; "?" beyond them), length, kmers, found, shared,
+// top_genome, top_kmers, and the genome's name (genomes: sorted, the row is its index), "." where the contig has no vote.
+std::string asmeval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const uint64_t* length, const uint32_t* kmers,
+                                const uint32_t* found, const uint32_t* shared, const uint32_t* top_genome, const uint32_t* top_kmers, size_t n);
 // `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
 // (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
 // ascend, and its text lies at `offset` of the byte source.
@@ -537,6 +556,11 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string eval_classified_report;  // --eval-classified-report FILE: the counts, a row per rank, precision / sensitivity / F1, the profile's L1 distance
   std::string eval_classified_reads;   // --eval-classified-reads FILE: a row per true read
   std::string eval_classified_taxa;    // --eval-classified-taxa FILE: a row per taxon with reads
+  std::string eval_assembly;          // --eval-assembly FILE: no simulation; an assembler's contigs scored against --eval-assembly-truth (simmr_asmeval_*)
+  std::string eval_assembly_truth;    // --eval-assembly-truth FILE: the file of --gold-assembly
+  std::string eval_assembly_report;   // --eval-assembly-report FILE: the counts, completeness per genome and overall, the QV, the contiguity of both sides
+  std::string eval_assembly_contigs;  // --eval-assembly-contigs FILE: a row per contig
+  uint32_t eval_assembly_k = 31;      // --eval-assembly-k K: odd, 15 .. 31
   bool eval_vcf_filtered = false;  // --eval-vcf-filtered: score the records whose FILTER is neither "." nor PASS too
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
