@@ -97,7 +97,7 @@ int simmr_pileup_add(simmr_engine* e, const simmr_reads_out* reads, uint64_t n_r
   if (n_reads > 0 && s->n > 0) {
     // persistent: eight waves per SIMD's worth of waves, each looping over its share of the 64-read batches
     const uint64_t batches = (n_reads + 63) / 64, wgs = (batches + PILEUP_WG / 64 - 1) / (PILEUP_WG / 64);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)eng_cu_count(e) * 8u);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(wgs, (uint64_t)eng_cu_count(e) * PILEUP_WGS_PER_CU);
     const PileupReads rd{reads->seq, reads->seq_off, reads->start, reads->end, reads->contig, reads->genome, reads->flags, reads->seq_capacity};
     hipLaunchKernelGGL(k_pileup_add, dim3(grid), dim3(PILEUP_WG), 0, st, rd, n_reads, s->d_slots.as<const PileupSlot>(),
                        (uint32_t)s->slots.size(), s->d_cfirst.as<const uint64_t>(), s->keys.as<const uint64_t>(), s->n, s->counts_p(), s->err_p());

@@ -16,7 +16,8 @@
 //                  prefixes through ds_bpermute (no LDS array, no barrier: the waves are independent), fetches that read's
 //                  first site and byte address the same way, loads the site's key and ONE byte of seq[], classifies and
 //                  complements it, and adds 1 to counts[s][strand][class] with a no-return relaxed agent-scope atomic.
-//                  Persistent grid: a wave loops over its share of the 64-read batches.
+//                  Persistent grid of at most PILEUP_WGS_PER_CU workgroups per CU: a wave loops over its share of the 64-read
+//                  batches.
 // Tried: this form only.  One lane walking its own read's sites serialises a 20 kb read's 200 sites behind one lane; a
 // site-major pass needs the reads sorted by position; counts privatised in LDS per tile of sites only pay at depths where
 // same-address atomics dominate (DESIGN.md section 4 says what was weighed and has the measured times).
@@ -35,6 +36,7 @@ namespace simmr {
 constexpr uint32_t PILEUP_WG = 256;             // threads of every workgroup here: four independent waves
 constexpr uint32_t PILEUP_ROUND = 1u << 24;     // pairs a lane hands to one scan: 64 of them stay below 2^31
 constexpr uint32_t PILEUP_CELLS = 10;           // uint32_t counts per site: [strand][class]
+constexpr uint32_t PILEUP_WGS_PER_CU = 8;       // the add's grid is capped at this many workgroups per CU; beyond it waves loop
 
 #define PILEUP_DEV __device__ __forceinline__
 

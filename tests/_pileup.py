@@ -18,6 +18,17 @@ INFO_LINES = (
 COLUMNS = "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO"
 
 
+def constants():
+    """(PILEUP_WG, PILEUP_ROUND, PILEUP_WGS_PER_CU) as simmr_amd/csrc/pileup_kernels.hip states them: the seam tests size their
+    reads, rounds and grid trips from these (a value is a decimal number or `1u << k`)"""
+    import re
+    from pathlib import Path
+    src = (Path(__file__).resolve().parent.parent / "simmr_amd" / "csrc" / "pileup_kernels.hip").read_text()
+    c = {m.group(1): int(m.group(3)) << int(m.group(4)) if m.group(4) else int(m.group(2))
+         for m in re.finditer(r"^constexpr uint32_t (PILEUP_\w+) = (?:(\d+)|(\d+)u << (\d+));", src, re.M)}
+    return c["PILEUP_WG"], c["PILEUP_ROUND"], c["PILEUP_WGS_PER_CU"]
+
+
 def firsts(lens):
     """lens: {genome slot: [contig lengths]} -> {(slot, contig): first position}: slots ascending, contigs in order, no padding"""
     out, at = {}, 0

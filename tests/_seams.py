@@ -19,8 +19,19 @@ And a fast restatement of tests/_mapeval.py for the sizes at which the mapeval k
   mapeval_from_columns            both SAM texts and every table of _mapeval.evaluate from columns (read id, mate, strand, name
                                   row, pos, span; on the aligned side also MAPQ and flag bits) instead of lines: the texts as
                                   byte matrices, the tables with searchsorted, bincount and maximum.at.  No loop over lines.
+And a fast restatement of tests/_pileup.py for the sizes at which k_pileup_add takes its second grid trip and its second scan
+round (tests/test_gpu_pileup_seams.py), held to _pileup.site_keys and _pileup.pileup cell for cell by tests/test_seams_host.py:
+
+  pileup_keys                     _pileup.site_keys with a (slot, contig) -> first table and one gather, under the same assertions.
+                                  No loop over sites.
+  pileup_from_columns             _pileup.pileup from the same columns: two searchsorted calls over all reads, the (read, site)
+                                  pairs laid out with repeat, one bincount over site * 10 + strand * 5 + class per chunk of
+                                  pairs (a chunk may end inside a read; `unique` instead where a chunk's few pairs lie far
+                                  apart).  No loop over reads or sites.
 Nothing here comes from the code under test."""
 import numpy as np
+
+from tests import _pileup
 
 POW10 = np.array([10 ** k for k in range(1, 20)], dtype=np.uint64)
 BGZF_BLOCK, BGZF_FRAMED = 65280, 65311  # source bytes of a full block, and its bytes in the file
@@ -308,3 +319,80 @@ def mapeval_from_columns(names, truth, aligned, pct=10, pad=True, header=b"", n_
                   reads_unmapped=int((best >> 8 == 1).sum()))
     out.update(counts=counts, by_mapq=by_mapq, key=key, best=best, hits=hits)
     return out
+
+
+# ---- the pileup from columns ------------------------------------------------------------------------------------------------
+def pileup_layout(lens):
+    """lens: {genome slot: [contig lengths]} -> (first, length), int64 tables indexed [slot, contig]: slots ascending, contigs in
+    order, no padding; first is -1 where there is no contig"""
+    n_slots = max(lens) + 1 if lens else 0
+    width = max((len(v) for v in lens.values()), default=0)
+    first, length = np.full((n_slots, width), -1, dtype=np.int64), np.zeros((n_slots, width), dtype=np.int64)
+    at = 0
+    for g in sorted(lens):  # (over the contigs, not over sites or reads)
+        for c, n in enumerate(lens[g]):
+            first[g, c], length[g, c] = at, int(n)
+            at += int(n)
+    return first, length
+
+
+def _first_of(first, g, c):
+    """first[g, c] of every entry, after the assertion that the slot is staged and the contig exists"""
+    assert ((g >= 0) & (g < first.shape[0]) & (c >= 0) & (c < first.shape[1])).all(), "a slot or contig beyond the table"
+    f = first[g, c]
+    assert (f >= 0).all(), "a slot that is not staged or a contig that does not exist"
+    return f
+
+
+def pileup_keys(sites, lens):
+    """_pileup.site_keys(sites, lens): int64 keys first(slot, contig) + pos, under the same assertions"""
+    first, length = pileup_layout(lens)
+    g, c, p = (np.asarray(x).astype(np.int64) for x in sites)
+    assert g.shape == c.shape == p.shape
+    k = _first_of(first, g, c) + p
+    assert ((p >= 0) & (p < length[g, c])).all(), "a position outside its contig"
+    assert (np.diff(k) > 0).all(), "sites are strictly ascending by (slot, contig, pos)"
+    return k
+
+
+def pileup_from_columns(cols, sites, lens, chunk_pairs=1 << 24, seq_base=0, keys=None):
+    """_pileup.pileup(cols, sites, lens) as uint32[n, 2, 5].  cols["seq"] may be the tail of the device's buffer that starts at
+    byte `seq_base` of it: seq_off counts from the buffer's start.  The pairs are taken `chunk_pairs` at a time, so the host's
+    memory is bounded by the chunk whatever a read's length.  keys: pileup_keys(sites, lens) where the caller has them already."""
+    assert chunk_pairs >= 1
+    first, _ = pileup_layout(lens)
+    keys = pileup_keys(sites, lens) if keys is None else keys
+    n_reads = len(cols["start"])
+    col = lambda name: np.asarray(cols[name])[:n_reads].astype(np.int64)
+    a, b, rev = col("start"), col("end"), col("flags") & _pileup.REVCOMP
+    lo, L = np.minimum(a, b), np.abs(b - a)
+    klo = _first_of(first, col("genome"), col("contig")) + lo
+    s0 = np.searchsorted(keys, klo, side="left")
+    n_pairs = np.searchsorted(keys, klo + L, side="left") - s0
+    off = col("seq_off") - int(seq_base)
+    seq = np.asarray(cols["seq"])
+    has = n_pairs > 0
+    assert (off[has] >= 0).all() and (off[has] + L[has] <= seq.size).all(), "a read's bytes outside the part of seq[] given"
+    end = np.cumsum(n_pairs)  # pair q of all belongs to the read with begin <= q < end
+    begin = end - n_pairs
+    observed = np.stack([_pileup.CLASS, np.where(_pileup.CLASS < 4, 3 - _pileup.CLASS, 4)])  # [strand, byte]: a reverse read's class is complemented
+    cell_of = observed + np.array([[0], [5]])
+    flat = np.zeros(keys.size * 10, dtype=np.uint32)
+    for q0 in range(0, int(end[-1]) if n_reads else 0, chunk_pairs):  # (over chunks of pairs)
+        q1 = min(q0 + chunk_pairs, int(end[-1]))
+        some = np.arange(np.searchsorted(end, q0, side="right"), np.searchsorted(begin, q1, side="left"))
+        take = np.maximum(np.minimum(end[some], q1) - np.maximum(begin[some], q0), 0)
+        of_read = lambda v: np.repeat(v[some], take)  # a column of the reads, pair by pair
+        s = np.arange(q0, q1) + of_read(s0 - begin)
+        d = keys[s] - of_read(klo)  # pos - lo
+        strand = of_read(rev)
+        j = np.where(strand == 1, of_read(L - 1) - d, d)
+        cell = s * 10 + cell_of[strand, seq[of_read(off) + j]]
+        at = int(cell.min())
+        if int(cell.max()) - at < 16 * cell.size:  # one bincount over the cells the chunk spans
+            k = np.bincount(cell - at)
+            flat[at:at + k.size] += k.astype(np.uint32)
+        else:  # a few pairs spread over a long list: the span is not worth an array
+            at, k = np.unique(cell, return_counts=True)
+            flat[at] += k.astype(np.uint32)
+    return flat.reshape(keys.size, 2, 5)

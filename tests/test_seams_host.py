@@ -3,11 +3,13 @@ index equal _overlap.pairs entry for entry, and every vectorised record length e
 formats; and the index from columns (bai_from_columns) against the plain index of tests/_bai.py, byte for byte, on the records of
 the sorted-BAM tests and on every shape of tests/test_gpu_bai_seams.py at a small size; and the mapeval tables from columns (mapeval_from_columns) against the
 plain model of tests/_mapeval.py, table for table, on random columns that hold every class and on every case of
-tests/test_gpu_mapeval_seams.py at a small size.  Runs without a GPU."""
+tests/test_gpu_mapeval_seams.py at a small size; and the pileup from columns (pileup_keys, pileup_from_columns) against the
+plain model of tests/_pileup.py, cell for cell, on a few hundred reads over the three genomes of the GPU suite and on the small
+cases of tests/test_gpu_pileup_seams.py.  Runs without a GPU."""
 import numpy as np
 import pytest
 
-from tests import _bai, _bai_cases, _mapeval, _mapeval_cases, _overlap, _seams
+from tests import _bai, _bai_cases, _mapeval, _mapeval_cases, _overlap, _pileup, _pileup_cases, _seams
 
 DIGITS = [9, 10, 99, 100, 999_999_999, 1_000_000_000, 4_294_967_295]
 
@@ -267,3 +269,182 @@ def test_the_lane_round_lines_fall_where_they_are_meant_to():
         assert len(_mapeval_cases.pad_line(o)) % 16 == o
     for total in (1, 999_999_999, 10 ** 9, 2 ** 40, 2 ** 40 + 1):
         assert _mapeval.cigar_span(_mapeval_cases.runs_summing_to(total)) == (total, False)
+
+
+# ---- the pileup from columns (tests/_seams.py:pileup_from_columns) against tests/_pileup.py:pileup -----------------------------------
+def same_pileup(cols, sites, lens, chunk_pairs=1 << 24):
+    got = _seams.pileup_from_columns(cols, sites, lens, chunk_pairs)
+    want = _pileup.pileup(cols, sites, lens)
+    assert got.dtype == want.dtype == np.uint32 and got.shape == want.shape == (len(sites[2]), 2, 5)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:8]
+    assert np.array_equal(_seams.pileup_keys(sites, lens), _pileup.site_keys(sites, lens))
+    return got
+
+
+def mixed_reads(layout, seed):
+    """three hundred reads of L in [0, 300) over the three genomes, both strands, some of L = 0, and four that end at their
+    contig's last base; the sites: one position in fifty of every contig, and position 0 of the contigs behind those four"""
+    rng = np.random.default_rng(seed)
+    lens = _pileup_cases.LENS
+    g, c, lo, L, rev = _pileup_cases.spread_reads(300, lens, rng, lmax=300)
+    L[::17] = 0
+    at_end = [(1, 0, 150, 0), (1, 0, 1, 1), (1, 2, 40, 1), (1, 3, 150, 0)]  # (slot, contig, L, reverse)
+    g = np.concatenate([g, [a[0] for a in at_end]])
+    c = np.concatenate([c, [a[1] for a in at_end]])
+    lo = np.concatenate([lo, [lens[a[0]][a[1]] - a[2] for a in at_end]])
+    L = np.concatenate([L, [a[2] for a in at_end]])
+    rev = np.concatenate([rev, [a[3] for a in at_end]])
+    cols = _pileup_cases.read_columns(g, c, lo, L, rev, layout, rng)
+    triples = {(s, k, int(p)) for s in lens for k, n in enumerate(lens[s]) for p in np.flatnonzero(rng.random(n) < 0.02)}
+    triples |= {(1, 1, 0), (1, 3, 0), (1, 4, 0), (1, 0, lens[1][0] - 1), (1, 2, lens[1][2] - 1)}
+    t = sorted(triples)
+    return cols, _pileup_cases.site_columns(*([x[i] for x in t] for i in range(3))), lens
+
+
+@pytest.mark.parametrize("chunk_pairs", [1, 7, 1 << 24])
+@pytest.mark.parametrize("layout", [0, 16], ids=["compact", "slot16"])
+def test_pileup_from_columns_on_mixed_reads(layout, chunk_pairs):
+    cols, sites, lens = mixed_reads(layout, 40 + layout)
+    got = same_pileup(cols, sites, lens, chunk_pairs)
+    keys = _pileup.site_keys(sites, lens)
+    f = _pileup.firsts(lens)
+    lo = np.minimum(cols["start"], cols["end"]).astype(np.int64)
+    L = np.abs(cols["end"].astype(np.int64) - cols["start"].astype(np.int64))
+    klo = np.array([f[(int(a), int(b))] for a, b in zip(cols["genome"], cols["contig"])]) + lo
+    n_pairs = np.searchsorted(keys, klo + L) - np.searchsorted(keys, klo)
+    # what the reads hold: both strands, L = 0, reads without a site, reads of more pairs than a chunk of 7, all three genomes
+    assert set(cols["flags"].tolist()) == {0, 1} and (L == 0).sum() >= 15 and (n_pairs[L > 0] == 0).sum() >= 10 and (n_pairs > 7).sum() >= 10
+    assert set(cols["genome"].tolist()) == {0, 1, 3} and int(got.sum()) == int(n_pairs.sum()) > 500
+    assert got[:, 0].sum() > 0 and got[:, 1].sum() > 0 and got[:, :, 4].sum() > 0 and (got[:, :, :4].sum(axis=(0, 1)) > 0).all()
+    # a read that ends at its contig's last base covers that base and not position 0 of the next contig
+    key = {t: i for i, t in enumerate(zip(*(x.tolist() for x in sites)))}
+    assert got[key[(1, 0, lens[1][0] - 1)]].sum() >= 2 and got[key[(1, 2, lens[1][2] - 1)]].sum() >= 1
+    for first_of_next, behind in (((1, 1, 0), 300), ((1, 3, 0), 302), ((1, 4, 0), 303)):
+        assert n_pairs[behind] > 0 and got[key[first_of_next]].sum() == ((klo <= keys[key[first_of_next]]) & (keys[key[first_of_next]] < klo + L)).sum()
+    if layout == 16:
+        assert (cols["seq_off"][:-1] % 16 != 0).any() and (np.diff(cols["seq_off"].astype(np.int64)) != L).any()
+
+
+@pytest.mark.parametrize("n_sites", [0, 1])
+def test_pileup_from_columns_on_no_site_and_one_site(n_sites):
+    cols, sites, lens = mixed_reads(0, 3)
+    cover = _pileup_cases.read_columns([1, 1, 1], [1, 1, 1], [500, 520, 601], [150, 150, 9], [0, 1, 1], 0, np.random.default_rng(1))
+    one = tuple(x[:n_sites] for x in _pileup_cases.site_columns([1], [1], [600]))
+    assert same_pileup(cols, one, lens).shape == (n_sites, 2, 5)
+    assert int(same_pileup(cover, one, lens, 1).sum()) == 2 * n_sites
+
+
+def test_pileup_from_columns_takes_the_tail_of_seq():
+    """seq_base: the bytes in front of the first read's are not given, and seq_off counts from the buffer's start"""
+    cols, sites, lens = mixed_reads(0, 5)
+    want = _pileup.pileup(cols, sites, lens)
+    base = 2**32 - 1000
+    moved = dict(cols, seq_off=cols["seq_off"] + np.uint64(base))
+    assert np.array_equal(_seams.pileup_from_columns(moved, sites, lens, 7, seq_base=base), want) and int(moved["seq_off"].max()) >= 2**32
+    cut = int(cols["seq_off"][100])
+    tail = dict(cols, seq=cols["seq"][cut:])
+    for name in ("start", "end", "contig", "genome", "flags", "seq_off"):
+        tail[name] = cols[name][100:]
+    assert np.array_equal(_seams.pileup_from_columns(tail, sites, lens, seq_base=cut), want - _pileup.pileup({k: v[:100] if k != "seq" else v for k, v in cols.items() if k not in ("total_bases", "layout")}, sites, lens))
+    with pytest.raises(AssertionError):  # bytes that lie in front of the part given
+        _seams.pileup_from_columns(tail, sites, lens, seq_base=cut + 1)
+
+
+BAD_LISTS = {
+    "out of order": [(1, 0, 10), (1, 0, 30), (1, 0, 20), (1, 1, 0)],
+    "contigs out of order": [(1, 1, 10), (1, 0, 30)],
+    "slots out of order": [(0, 0, 5), (3, 0, 5), (1, 0, 5)],
+    "a repeat": [(0, 0, 5), (1, 2, 7), (1, 2, 7)],
+    "pos == len": [(1, 0, 5), (1, 1, 90_001)],
+    "pos == len of the last contig": [(3, 0, 30_000)],
+    "an unstaged slot": [(1, 0, 5), (2, 0, 0)],
+    "a slot beyond the table": [(77, 0, 0)],
+    "a contig that does not exist": [(0, 0, 1), (1, 5, 0)],
+}
+
+
+@pytest.mark.parametrize("name", BAD_LISTS)
+def test_pileup_keys_refuses_what_the_model_refuses(name):
+    bad = _pileup_cases.site_columns(*([t[i] for t in BAD_LISTS[name]] for i in range(3)))
+    for keys_of in (_pileup.site_keys, _seams.pileup_keys):
+        with pytest.raises(AssertionError):
+            keys_of(bad, _pileup_cases.LENS)
+    good = tuple(x[:1] for x in bad) if name not in ("pos == len of the last contig", "a slot beyond the table") else _pileup_cases.site_columns([3], [0], [29_999])
+    assert _seams.pileup_keys(good, _pileup_cases.LENS).tolist() == _pileup.site_keys(good, _pileup_cases.LENS).tolist()
+    none = _pileup_cases.site_columns([], [], [])
+    assert _seams.pileup_keys(none, _pileup_cases.LENS).shape == (0,) and _seams.pileup_keys(none, {}).shape == (0,)
+
+
+def test_pileup_constants_come_from_the_kernel_file():
+    wg, round_pairs, per_cu = _pileup.constants()
+    assert all(isinstance(v, int) and v > 0 for v in (wg, round_pairs, per_cu))
+    assert wg % 64 == 0 and 64 * round_pairs < 2**31
+
+
+# ---- the small cases of tests/test_gpu_pileup_seams.py through the plain model ------------------------------------------------------
+def pairs_per_read(cols, sites, lens):
+    """how many sites every read covers, from the model's keys and the model's two searchsorted calls"""
+    keys = _pileup.site_keys(sites, lens)
+    f = _pileup.firsts(lens)
+    lo = np.minimum(cols["start"], cols["end"]).astype(np.int64)
+    L = np.abs(cols["end"].astype(np.int64) - cols["start"].astype(np.int64))
+    klo = np.array([f[(int(a), int(b))] for a, b in zip(cols["genome"], cols["contig"])], dtype=np.int64) + lo
+    s0 = np.searchsorted(keys, klo, side="left")
+    return np.searchsorted(keys, klo + L, side="left") - s0, s0
+
+
+@pytest.mark.parametrize("which", _pileup_cases.STRANDS)
+@pytest.mark.parametrize("name", _pileup_cases.STEP_COUNTS)
+def test_step_cases_hold_their_counts(name, which):
+    reads, sites, counts = _pileup_cases.step_case(name, which)
+    cols = _pileup_cases.read_columns(*reads, 0, np.random.default_rng(2))
+    got = same_pileup(cols, sites, _pileup_cases.LENS, 64)
+    n_pairs, _ = pairs_per_read(cols, sites, _pileup_cases.LENS)
+    assert np.array_equal(n_pairs, counts) and np.array_equal(counts[:64], counts[128:]) and not counts[64:128].any()
+    assert int(got.sum()) == int(counts.sum()) and int((got.sum(axis=(1, 2)) == 0).sum()) == 96  # (the sites in front of every other read)
+    prefix = np.cumsum(_pileup_cases.STEP_COUNTS[name])
+    if name == "edges_64_128_256":
+        assert {64, 128, 256} <= set(prefix.tolist()) and prefix[-1] == 321 and prefix[8] == 321
+    if name == "edges_reversed":  # (the first pairs belong to lane 55, the last 64 to lane 63; one edge stays on a step's end)
+        assert not prefix[:55].any() and prefix[55:].tolist() == [65, 65, 65, 193, 256, 257, 257, 257, 321]
+    if name == "lanes_31_32":
+        assert prefix[-1] % 64 == 1 and prefix[30] == 0 and 0 < prefix[31] < prefix[32] == prefix[63]
+
+
+@pytest.mark.parametrize("before", [0, 3])
+@pytest.mark.parametrize("m", [149, 150, 151, 152])
+def test_list_end_cases_end_where_they_say(m, before):
+    reads, sites, = _pileup_cases.list_end_case(m, before)
+    cols = _pileup_cases.read_columns(*reads, 0, np.random.default_rng(3))
+    got = same_pileup(cols, sites, _pileup_cases.LENS, 100)
+    n_pairs, s0 = pairs_per_read(cols, sites, _pileup_cases.LENS)
+    n, L = len(sites[2]), _pileup_cases.END_L
+    assert n - s0[0] == n - s0[1] == m and n_pairs[0] == n_pairs[1] == min(m, L)
+    assert n_pairs.tolist() == [min(m, L)] * 2 + [0] * 4 + [n] * 2 + [min(m - 75, L)] * 2 + [before] * 2 + [1] * 2 + [0] * 2
+    assert got[:, 0].sum() == got[:, 1].sum() == n_pairs.sum() // 2
+
+
+@pytest.mark.parametrize("pos", [(40_000,), (40_000, 40_001), (40_000, 40_149), (40_000, 40_150)], ids=lambda p: f"{len(p)}-{p[-1] - p[0]}")
+def test_short_list_cases(pos):
+    reads, sites = _pileup_cases.short_list_case(np.array(pos))
+    cols = _pileup_cases.read_columns(*reads, 16, np.random.default_rng(4))
+    got = same_pileup(cols, sites, _pileup_cases.LENS, 3)
+    n_pairs, _ = pairs_per_read(cols, sites, _pileup_cases.LENS)
+    two = len(pos) - 1
+    second = lambda lo, L: int(two and lo <= pos[-1] < lo + L)
+    p = pos[0]
+    want = [1 + second(p, 150), 1 + second(p - 149, 150), 0, second(p + 1, 150), 0, 0, 1 + two, 1, 0]
+    assert n_pairs.tolist() == [x for x in want for _ in range(2)] and int(got.sum()) == 2 * sum(want)
+
+
+@pytest.mark.parametrize("identical", [False, True], ids=["every offset", "one read"])
+def test_deep_case_at_a_small_depth(identical):
+    rng = np.random.default_rng(6)
+    reads, sites = _pileup_cases.deep_case(700, identical, rng)
+    cols = _pileup_cases.read_columns(*reads, 0, rng, shared=identical)
+    got = same_pileup(cols, sites, _pileup_cases.LENS, 50)
+    assert got[2].sum() == 700 and got[0].sum() == got[4].sum() == 0
+    if identical:
+        assert got[2].max() == 700 and got[1].sum() == 0 and got[3].sum() == 0
+    else:
+        assert got[2, 0].sum() == got[2, 1].sum() == 350 and got[1].sum() > 0 and got[3].sum() > 0
