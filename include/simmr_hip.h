@@ -1777,6 +1777,127 @@ int simmr_asmeval_contigs(simmr_asmeval* h, uint64_t* length_dev, uint32_t* kmer
  * waits inside simmr_asmeval_add lie inside that span.  *plan_sort_ms (may be NULL) = the sort's share of the last plan. */
 int simmr_last_asmeval_ms(simmr_asmeval* h, float* ms, float* plan_sort_ms);
 
+/* ---- a binner's contig bins scored against each contig's true genome: two tab-separated texts in HBM, joined by name -----------
+ * Replaces nothing in the reference.  `--eval-assembly-contigs` writes, per contig, its name, its length and the genome most of
+ * its k-mers vote for; a binner (MetaBAT, CONCOCT, MaxBin, VAMB, DAS Tool) puts the same contigs into bins.  Both texts go in and
+ * integer tables come out: the (bin, genome) contingency table in contigs and in bases, every bin's purity and every genome's
+ * completeness, the pair sums of the adjusted Rand index and CAMI's bin classes.  No simulation, no genome: like simmr_asmeval_*.
+ *
+ * Truth text.  Plain text (no gzip), eight tab-separated fields a line: field 1 the contig's name, field 2 its length in bases,
+ * field 8 the genome's name, or "." for a contig without a top genome; fields 3 to 7 are only checked to be numbers.  A number is
+ * one to eighteen decimal digits.  Further fields are ignored.  Empty lines are skipped, and so are lines that begin with '#'.  A
+ * '\r' directly before '\n' is not part of the line (a line that holds nothing else is empty); the last line may lack its '\n',
+ * and then a '\r' that ends it is a byte like any other.  The caller cuts a file behind a '\n', at most SIMMR_BINEVAL_MAX_BYTES a
+ * call.
+ * Names.  A contig name or a bin name is 1 to 254 bytes, none of them a tab, a blank or a control byte (0x00 .. 0x20, 0x7f).  Two
+ * names are the same name exactly when their bytes are equal: nothing is trimmed, folded or parsed.  The genome names are handed in
+ * once (simmr_bineval_config), under the rule and the limits of simmr_mapeval_reset, fewer than 2^24 of them; the row of a genome
+ * is its place in the library's sorted order, and row n_genomes is "none" (".").
+ * Candidate text.  A binner's assignment, one record a line: contig name, tab, bin name; further tab-separated fields are ignored.
+ * Lines that begin with '#' or '@' are no records (the CAMI bioboxes head "@Version:", "@@SEQUENCEID BINID" passes unchanged);
+ * line ends as in the truth.  A record's ordinal counts the records since the truth plan, in add order and then text order.
+ * Malformed (sticky, the truth until the reset and the candidate until the next plan; simmr_bineval_truth_plan for the truth and
+ * simmr_bineval_read for the candidate answer SIMMR_EINVAL and write nothing): a truth line with
+ * fewer than eight fields, a field 2 to 7 that is no number, a genome name that is neither "." nor among the names, a contig name
+ * that occurs twice in the truth, on either side an empty name or one longer than 254 bytes or with a byte a name may not hold, a
+ * candidate record without a second field.
+ *
+ * The join.  The hash of a name is 64-bit FNV-1a over its bytes (SIMMR_BINEVAL_FNV_OFFSET, SIMMR_BINEVAL_FNV_PRIME).
+ * simmr_bineval_truth_plan sorts the truth contigs by the low hash_bits bits of their hash; a lookup finds the run of equal
+ * truncated hash by a binary search and walks it comparing bytes: the hash only narrows the search, byte equality decides.
+ * hash_bits may be 0 to 64 (64 is what a caller without a reason gives); with 0 every name shares one run.  The answers are the
+ * same for every value.  The object copies the names it needs (the truth's contig names, the records' bin names)
+ * into buffers of its own: the caller's text may change once the stream has run the add.
+ * Assignment.  A record whose contig is not in the truth is an unknown_contig: counted, not scored.  A truth contig named by
+ * several records belongs to the bin of the record with the lowest ordinal; the others are `repeated`.  A truth contig named by no
+ * record is unassigned.
+ * Bins.  A bin is a distinct bin name among the records of known contigs, repeated ones included.  A bin's row is its rank by
+ * first appearance, the lowest ordinal of a record of a known contig that carries the name (first_record).
+ * The table.  A cell is (bin, genome row) with contigs and bases: the count and the summed lengths of the assigned truth contigs
+ * of that bin whose true genome is that row, "none" included; cells are in (bin, genome) order.  Per bin: contigs, bases,
+ * none_bases, first_record, and top_genome with top_bases: the real genome (never "none") with the most bases in the bin, ties to
+ * the lowest row; without a real genome 0xffffffff and 0.  by_genome[n_genomes + 1][SIMMR_BINEVAL_GENOME_COLS]: truth_contigs,
+ * truth_bases (assigned or not), assigned_contigs, assigned_bases, bins (the bins that hold any of it), best_bin and best_bases:
+ * the bin with the most of the genome's bases, ties to the lowest bin row; without any 0xffffffff and 0.  The "none" row has 0 in
+ * the last three.  A maximum is taken over the 64-bit bases alone and the lowest row that reaches it by a second pass, so no bits
+ * go to a row: bins below 2^31 and any bases fit.  Base limit: the lengths of the truth sum to less than 2^57 (the classes
+ * multiply a sum by 100); it is the caller's to keep.
+ * Counts.  pairs_cells, pairs_bins and pairs_genomes are the sums of n (n - 1) / 2 over the cells', the bins' and the genome
+ * rows' contig counts, over assigned contigs with a real genome.  The six classes are cumulative, as CAMI prints them: with t the
+ * bin's top genome, a bin counts in bins_cC_xX where 100 * top_bases >= C * truth_bases[t] and 100 * (bases - top_bases) <= X *
+ * bases, in integers.  A bin without a top genome is in none.  A contig in no genome is contamination: a bin's purity is
+ * top_bases / bases, "none" bases included.
+ * Every output is an integer sum, minimum or maximum: the same for any launch geometry, any cut of either text into adds at line
+ * ends and any hash_bits; the same under any renaming of the bins that keeps them distinct, and under any reordering of the
+ * candidate's lines that keeps the order of the bins' first appearances and, for every contig, which of its records comes first.
+ * One engine. */
+#define SIMMR_BINEVAL_MAX_BYTES 0x7fffffffull         /* most bytes of text in one add of either side */
+#define SIMMR_BINEVAL_GENOME_COLS 7u                  /* by_genome: truth_contigs, truth_bases, assigned_contigs, assigned_bases, bins, best_bin, best_bases */
+#define SIMMR_BINEVAL_FNV_OFFSET 0xcbf29ce484222325ull /* 64-bit FNV-1a: h = offset; for every byte: h = (h ^ byte) * prime */
+#define SIMMR_BINEVAL_FNV_PRIME 0x100000001b3ull
+
+typedef struct simmr_bineval simmr_bineval;
+
+typedef struct simmr_bineval_config {   /* HOST memory */
+  uint32_t n_genomes;
+  uint32_t hash_bits;                   /* 0 .. 64: the low bits of the hash that order the truth and the records (64 unless a test wants long runs) */
+  const char* const* genome;            /* n_genomes genome names, NUL-terminated, in any order */
+} simmr_bineval_config;
+
+typedef struct simmr_bineval_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_records, truth_bases, truth_none;                        /* the truth of the plan in force; none: contigs whose genome is "." */
+  uint64_t records, unknown_contig, repeated, assigned, assigned_bases;   /* the candidate side, since the last truth plan */
+  uint64_t bins, cells;
+  uint64_t sum_top_bases, sum_best_bases;                                 /* over the bins; over the real genomes */
+  uint64_t pairs_cells, pairs_bins, pairs_genomes;
+  uint64_t bins_c90_x5, bins_c70_x5, bins_c50_x5, bins_c90_x10, bins_c70_x10, bins_c50_x10;
+} simmr_bineval_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_asmeval_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error). */
+int simmr_bineval_create(simmr_engine* e, simmr_bineval** out);
+void simmr_bineval_destroy(simmr_bineval* h);
+/* Takes the names and hash_bits, and empties both sides.  Synchronises.  SIMMR_EINVAL: a NULL argument, a name given twice, a
+ * hash_bits above 64.  SIMMR_ENOTSUP: a name that is empty, longer than 254 bytes or no
+ * SAM reference name.  SIMMR_ERANGE: 2^24 names or more. */
+int simmr_bineval_reset(simmr_bineval* h, const simmr_bineval_config* cfg);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for a contig per 16 bytes of text and for the names grows with the object.
+ * SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL text with n_bytes > 0.  SIMMR_ENOTSUP: n_bytes above SIMMR_BINEVAL_MAX_BYTES. */
+int simmr_bineval_truth_add(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes);
+/* The plan: sorts the truth's contigs by the low hash_bits bits of their hash, looks for a name that occurs twice, and empties the
+ * candidate side.  Synchronises.  *n_contigs (may be NULL) = the truth's contigs.  SIMMR_EINVAL: a malformed truth text.
+ * SIMMR_ERANGE: 2^31 truth contigs or more since the reset. */
+int simmr_bineval_truth_plan(simmr_bineval* h, uint64_t* n_contigs);
+/* Joins the records of text[0 .. n_bytes) (DEVICE, as above) to the truth.  SYNCHRONISES, once: it needs the add's records and the
+ * bytes of their bin names on the host, for the room of the record columns.  SIMMR_ESTATE: no truth plan in force.  SIMMR_ERANGE:
+ * 2^31 records or more since the plan.  SIMMR_EINVAL, SIMMR_ENOTSUP: as simmr_bineval_truth_add. */
+int simmr_bineval_add(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts and by_genome_host[n_genomes + 1][SIMMR_BINEVAL_GENOME_COLS] (HOST, either may be NULL).  The bin rows, the cells and
+ * the tables are made here, from the records and the assignment that the adds left: a second read gives the same answer, and an
+ * add after a read is scored by the next read.  Synchronises (the two scans and the end).  SIMMR_EINVAL: a malformed candidate
+ * text since the plan (nothing is written; a malformed truth has no plan).  SIMMR_ESTATE: no truth plan in force. */
+int simmr_bineval_read(simmr_bineval* h, simmr_bineval_counts* counts, uint64_t* by_genome_host);
+/* The bins of the last read in row order, six columns (DEVICE, capacity entries each, any may be NULL): contigs (u32), bases,
+ * none_bases (u64), first_record, top_genome (u32), top_bases (u64).  *n_bins (may be NULL) is written whenever a read holds: a
+ * call with capacity 0 asks for it.  Synchronises.  SIMMR_ESTATE: no simmr_bineval_read since the plan or since the last add.
+ * SIMMR_ERANGE, no column written: capacity < the bins. */
+int simmr_bineval_bins(simmr_bineval* h, uint32_t* contigs_dev, uint64_t* bases_dev, uint64_t* none_bases_dev, uint32_t* first_record_dev,
+                       uint32_t* top_genome_dev, uint64_t* top_bases_dev, uint64_t capacity, uint64_t* n_bins);
+/* The cells of the last read in (bin, genome) order, four columns (DEVICE, any may be NULL): bin, genome, contigs (u32), bases
+ * (u64).  *n_cells, the states and the errors as simmr_bineval_bins. */
+int simmr_bineval_cells(simmr_bineval* h, uint32_t* bin_dev, uint32_t* genome_dev, uint32_t* contigs_dev, uint64_t* bases_dev, uint64_t capacity,
+                        uint64_t* n_cells);
+/* The truth contigs in truth order (add order, then text order), four columns (DEVICE, any may be NULL): the genome row (u32), the
+ * length (u64), the bin row of the last read or 0xffffffff (u32), the records that named it (u32).  *n_contigs, the states and the
+ * errors as simmr_bineval_bins. */
+int simmr_bineval_contigs(simmr_bineval* h, uint32_t* genome_dev, uint64_t* length_dev, uint32_t* bin_dev, uint32_t* records_dev, uint64_t capacity,
+                          uint64_t* n_contigs);
+/* HIP-event time (ms) of the device work since the last reset: the truth adds, the plans, the adds and the reads.  Synchronises
+ * the stream.  A run of adds with no synchronising call of this object between them is timed as one span; the host's wait inside
+ * simmr_bineval_add lies inside that span.  *plan_sort_ms (may be NULL) = the sort's share of the last plan. */
+int simmr_last_bineval_ms(simmr_bineval* h, float* ms, float* plan_sort_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -309,6 +309,23 @@ class AsmevalConfig(C.Structure):
     _fields_ = [("n_genomes", C.c_uint32), ("k", C.c_uint32), ("plain_search", C.c_uint32), ("genome", C.POINTER(C.c_char_p))]
 
 
+BINEVAL_COUNTS = ("truth_records", "truth_bases", "truth_none", "records", "unknown_contig", "repeated", "assigned", "assigned_bases", "bins", "cells",
+                  "sum_top_bases", "sum_best_bases", "pairs_cells", "pairs_bins", "pairs_genomes", "bins_c90_x5", "bins_c70_x5", "bins_c50_x5",
+                  "bins_c90_x10", "bins_c70_x10", "bins_c50_x10")
+BINEVAL_GENOME_COLS = ("truth_contigs", "truth_bases", "assigned_contigs", "assigned_bases", "bins", "best_bin", "best_bases")  # SIMMR_BINEVAL_GENOME_COLS
+BINEVAL_MAX_BYTES = 0x7fffffff  # SIMMR_BINEVAL_MAX_BYTES
+
+
+class BinevalCounts(C.Structure):
+    """struct simmr_bineval_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in BINEVAL_COUNTS]
+
+
+class BinevalConfig(C.Structure):
+    """struct simmr_bineval_config (host memory)"""
+    _fields_ = [("n_genomes", C.c_uint32), ("hash_bits", C.c_uint32), ("genome", C.POINTER(C.c_char_p))]
+
+
 class MapevalConfig(C.Structure):
     """struct simmr_mapeval_config (host memory)"""
     _fields_ = [("n_names", C.c_uint32), ("min_overlap_pct", C.c_uint32), ("rname", C.POINTER(C.c_char_p))]
@@ -475,6 +492,17 @@ SYMBOLS = {
     "simmr_asmeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_asmeval_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
     "simmr_last_asmeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float), _P(C.c_float)]),
+    "simmr_bineval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_bineval_destroy": (None, [C.c_void_p]),
+    "simmr_bineval_reset": (C.c_int, [C.c_void_p, _P(BinevalConfig)]),
+    "simmr_bineval_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_bineval_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "simmr_bineval_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_bineval_read": (C.c_int, [C.c_void_p, _P(BinevalCounts), _P(C.c_uint64)]),
+    "simmr_bineval_bins": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "simmr_bineval_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "simmr_bineval_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "simmr_last_bineval_ms": (C.c_int, [C.c_void_p, _P(C.c_float), _P(C.c_float)]),
     "simmr_taxeval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "simmr_taxeval_destroy": (None, [C.c_void_p]),
     "simmr_taxeval_reset": (C.c_int, [C.c_void_p, _P(TaxevalConfig)]),

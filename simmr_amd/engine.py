@@ -523,6 +523,111 @@ class AsmEval:
                 self.engine._mapevals.remove(self)
 
 
+class BinEval:
+    """A binner's contig bins scored against each contig's true genome on the device (simmr_bineval_*, include/simmr_hip.h states
+    the rules).  truth_add() the truth text (the file of --eval-assembly-contigs), truth_plan(), add() the binner's assignment, then
+    read(), bins(), cells() and contigs().  A text is bytes (copied up) or a contiguous CUDA uint8 tensor cut behind a line end;
+    truth_add only enqueues, so every text is kept until a call that synchronises."""
+
+    def __init__(self, engine: "Engine", genomes, hash_bits: int = 64):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        self.n_contigs = self.n_genomes = 0
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_bineval_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(genomes, hash_bits)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, genomes, hash_bits: int = 64):
+        raw = [n if isinstance(n, bytes) else str(n).encode() for n in genomes]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        cfg = _abi.BinevalConfig(len(raw), int(hash_bits), arr)
+        try:
+            self._check(self.lib.simmr_bineval_reset(self._h, C.byref(cfg)))
+        finally:
+            self._texts = []  # the reset has synchronised
+        self.n_contigs, self.n_genomes, self.hash_bits = 0, len(raw), int(hash_bits)
+
+    _text = Mapeval._text
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_bineval_truth_add(self._h, p, n))
+
+    def truth_plan(self) -> int:
+        n = C.c_uint64(0)
+        self.n_contigs = 0
+        try:
+            self._check(self.lib.simmr_bineval_truth_plan(self._h, C.byref(n)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_contigs = int(n.value)
+        return self.n_contigs
+
+    def add(self, text):
+        p, n = self._text(text)  # (kept: the add waits in its middle, and its lookups read the text behind that wait)
+        self._check(self.lib.simmr_bineval_add(self._h, p, n))
+
+    def read(self):
+        """(counts by the names of struct simmr_bineval_counts, by_genome as an (n_genomes + 1, 7) uint64 array: truth_contigs,
+        truth_bases, assigned_contigs, assigned_bases, bins, best_bin, best_bases; the last row is "none")"""
+        c = _abi.BinevalCounts()
+        by = np.zeros((self.n_genomes + 1, len(_abi.BINEVAL_GENOME_COLS)), dtype=np.uint64)
+        try:
+            self._check(self.lib.simmr_bineval_read(self._h, C.byref(c), by.ctypes.data_as(C.POINTER(C.c_uint64))))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.BINEVAL_COUNTS}, by
+
+    def _columns(self, fn, wide):
+        """the columns of one of the three tables as numpy arrays; wide[i]: column i is 64-bit"""
+        torch = _torch()
+        n = C.c_uint64(0)
+        none = [None] * len(wide)
+        rc = fn(self._h, *none, 0, C.byref(n))
+        if rc not in (0, -34):  # (SIMMR_ERANGE: capacity 0 asks for the number alone)
+            self._check(rc)
+        n, dev = int(n.value), self.engine.device
+        cols = [torch.zeros(max(n, 1), dtype=torch.int64 if w else torch.int32, device=dev) for w in wide]
+        self._check(fn(self._h, *[C.c_void_p(t.data_ptr()) for t in cols], n, None))
+        return tuple(t[:n].cpu().numpy().view(np.uint64 if w else np.uint32) for t, w in zip(cols, wide))
+
+    def bins(self):
+        """The bins of the last read in row order: contigs (uint32), bases, none_bases (uint64), first_record, top_genome (uint32),
+        top_bases (uint64)"""
+        return self._columns(self.lib.simmr_bineval_bins, (False, True, True, False, False, True))
+
+    def cells(self):
+        """The cells of the last read in (bin, genome) order: bin, genome, contigs (uint32), bases (uint64)"""
+        return self._columns(self.lib.simmr_bineval_cells, (False, False, False, True))
+
+    def contigs(self):
+        """The truth contigs in truth order: genome (uint32), length (uint64), bin or 0xffffffff, records (uint32)"""
+        return self._columns(self.lib.simmr_bineval_contigs, (False, True, False, False))
+
+    def ms(self):
+        """(the device time of the unit's calls since the reset, the sort's share of the last plan), in ms"""
+        a, b = C.c_float(), C.c_float()
+        self._check(self.lib.simmr_last_bineval_ms(self._h, C.byref(a), C.byref(b)))
+        self._texts = []
+        return a.value, b.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_bineval_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
 class TaxEval:
     """A read classifier's calls scored against each read's true genome on the device (simmr_taxeval_*, include/simmr_hip.h
     states the rules).  truth_add() the truth text (the file of --truth), truth_plan(), add() the classifier's per-read text, then
@@ -1491,6 +1596,34 @@ class Engine:
                 ev.add(t)
             counts, by_genome = ev.read()
             return counts, by_genome, ev.entries(), ev.contigs()
+        finally:
+            ev.close()
+
+    # -- a binner's bins against each contig's true genome ------------------------------------
+    def binning_eval_open(self, genomes, hash_bits: int = 64) -> "BinEval":
+        """An evaluation object (simmr_bineval_*) over the genome names.  Closed by its close(), or by the engine's before the
+        engine goes (it is kept in the list of the mapeval objects, which the engine closes first)."""
+        m = BinEval(self, genomes, hash_bits)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
+
+    def binning_eval(self, truth_bytes, bins_bytes, genomes, hash_bits: int = 64):
+        """Scores the binner's assignment `bins_bytes` against the contig truth `truth_bytes` (each bytes, a CUDA uint8 tensor, or a
+        list of those: an add each, cut behind a line end).  Returns (counts as a dict, by_genome (n_genomes + 1, 7), the six bin
+        columns, the four cell columns, the four contig columns)."""
+        def adds(text):
+            return list(text) if isinstance(text, (list, tuple)) else [text]
+        ev = self.binning_eval_open(genomes, hash_bits)
+        try:
+            for t in adds(truth_bytes):
+                ev.truth_add(t)
+            ev.truth_plan()
+            for t in adds(bins_bytes):
+                ev.add(t)
+            counts, by_genome = ev.read()
+            return counts, by_genome, ev.bins(), ev.cells(), ev.contigs()
         finally:
             ev.close()
 

@@ -816,6 +816,14 @@ std::string usage() {
          "                            of both sides (records, bases, longest, N50) and a G row per genome\n"
          "            --eval-assembly-contigs <FILE>  every contig: name, length, kmers, found, shared, top genome row, its votes, its name\n"
          "            --eval-assembly-k <K>  k-mer size, odd, 15 .. 31 [default: 31]\n"
+         "            --eval-bins <FILE>  no simulation: score a binner's assignment (contig, tab, bin a line; '#' and '@' lines skipped) against\n"
+         "                            the contigs file of --eval-bins-truth, joined by name on the device: purity, completeness, F1, the\n"
+         "                            adjusted Rand index, CAMI's bin classes; takes only --eval-bins-truth, --eval-bins-report,\n"
+         "                            --eval-bins-bins, --eval-bins-contigs and --device\n"
+         "            --eval-bins-truth <FILE>  the file of --eval-assembly-contigs; the genomes are its distinct field-8 values other than '.'\n"
+         "            --eval-bins-report <FILE>  the result as a TSV: the counts as #name value lines, the fractions, a G row per genome, a B row per bin\n"
+         "            --eval-bins-bins <FILE>  every (bin, genome) cell: bin, genome, contigs, bases\n"
+         "            --eval-bins-contigs <FILE>  every truth contig: name, length, genome, bin or '.', records\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -1083,6 +1091,130 @@ std::string asmeval_contig_rows(const std::vector<std::string>& names, const std
   return out;
 }
 
+// ---- --eval-bins ---------------------------------------------------------------------------------------------------------------------
+// calls line(a, b) for every record line text[a, b) of text[0, n): not empty, without its line end, not begun by one of `skip`
+template <class F>
+static void bineval_lines(const char* text, size_t n, const char* skip, F&& line) {
+  for (size_t a = 0; a < n;) {
+    size_t nl = a;
+    while (nl < n && text[nl] != '\n') nl++;
+    size_t b = nl;
+    if (nl < n && b > a && text[b - 1] == '\r') b--;
+    if (b > a && !strchr(skip, text[a])) line(a, b);
+    a = nl + 1;
+  }
+}
+
+// field `want` (from 1) of text[a, b), "" where the line has fewer
+static std::string bineval_field(const char* text, size_t a, size_t b, unsigned want) {
+  for (unsigned f = 1;; f++) {
+    size_t e = a;
+    while (e < b && text[e] != '\t') e++;
+    if (f == want) return std::string(text + a, e - a);
+    if (e == b) return std::string();
+    a = e + 1;
+  }
+}
+
+void bineval_truth_names(const char* text, size_t n, std::vector<std::string>* contig, std::vector<std::string>* genome) {
+  bineval_lines(text, n, "#", [&](size_t a, size_t b) {
+    contig->push_back(bineval_field(text, a, b, 1));
+    genome->push_back(bineval_field(text, a, b, 8));
+  });
+}
+
+void bineval_record_bins(const char* text, size_t n, std::vector<std::string>* bin) {
+  bineval_lines(text, n, "#@", [&](size_t a, size_t b) { bin->push_back(bineval_field(text, a, b, 2)); });
+}
+
+static std::string bineval_frac(double num, double den) {
+  char text[64] = "NA";
+  if (den != 0.0) snprintf(text, sizeof text, "%.6f", num / den);
+  return text;
+}
+
+std::string bineval_ari(uint64_t pairs_cells, uint64_t pairs_bins, uint64_t pairs_genomes, uint64_t n) {
+  const double all = (double)n * (double)(n ? n - 1 : 0) / 2.0;
+  if (all == 0.0) return "NA";
+  const double expected = (double)pairs_bins * (double)pairs_genomes / all;
+  return bineval_frac((double)pairs_cells - expected, ((double)pairs_bins + (double)pairs_genomes) / 2.0 - expected);
+}
+
+std::string bineval_report(const uint64_t* counts, const std::vector<std::string>& genomes, const uint64_t* by_genome, const std::vector<std::string>& bin_names,
+                           const uint32_t* contigs, const uint64_t* bases, const uint64_t* none_bases, const uint32_t* top_genome, const uint64_t* top_bases,
+                           size_t n_bins) {
+  static const char* const NAMES[BINEVAL_N_COUNTS] = {"truth_records", "truth_bases", "truth_none", "records", "unknown_contig", "repeated", "assigned",
+                                                      "assigned_bases", "bins", "cells", "sum_top_bases", "sum_best_bases", "pairs_cells", "pairs_bins",
+                                                      "pairs_genomes", "bins_c90_x5", "bins_c70_x5", "bins_c50_x5", "bins_c90_x10", "bins_c70_x10", "bins_c50_x10"};
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  const size_t G = genomes.size();
+  std::string out;
+  for (size_t i = 0; i < BINEVAL_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + n(counts[i]) + "\n";
+  const uint64_t truth_bases = counts[1], assigned_bases = counts[7], sum_top = counts[10], sum_best = counts[11];
+  uint64_t real_bases = 0, real_assigned = 0;
+  for (size_t g = 0; g < G; g++) {
+    real_bases += by_genome[g * BINEVAL_GENOME_COLS + 1];
+    real_assigned += by_genome[g * BINEVAL_GENOME_COLS + 2];
+  }
+  out += "#purity\t" + n(sum_top) + "/" + n(assigned_bases) + "\t" + bineval_frac((double)sum_top, (double)assigned_bases) + "\n";
+  out += "#completeness\t" + n(sum_best) + "/" + n(real_bases) + "\t" + bineval_frac((double)sum_best, (double)real_bases) + "\n";
+  std::string f1 = "NA";
+  if (assigned_bases != 0 && real_bases != 0) {
+    const double p = (double)sum_top / (double)assigned_bases, c = (double)sum_best / (double)real_bases;
+    f1 = bineval_frac(2.0 * p * c, p + c);
+  }
+  out += "#f1\t" + f1 + "\n";
+  out += "#assigned_fraction\t" + n(assigned_bases) + "/" + n(truth_bases) + "\t" + bineval_frac((double)assigned_bases, (double)truth_bases) + "\n";
+  out += "#ari_contigs\t" + bineval_ari(counts[12], counts[13], counts[14], real_assigned) + "\n";
+  double sum = 0.0;
+  uint64_t with = 0;
+  for (size_t b = 0; b < n_bins; b++)
+    if (bases[b] != 0) { sum += (double)top_bases[b] / (double)bases[b]; with++; }
+  out += "#average_purity\t" + bineval_frac(sum, (double)with) + "\n";
+  sum = 0.0;
+  with = 0;
+  for (size_t g = 0; g < G; g++) {
+    const uint64_t* r = by_genome + g * BINEVAL_GENOME_COLS;
+    if (r[1] != 0) { sum += (double)r[6] / (double)r[1]; with++; }
+  }
+  out += "#average_completeness\t" + bineval_frac(sum, (double)with) + "\n";
+  out += "#G\tgenome\ttruth_contigs\ttruth_bases\tassigned_contigs\tassigned_bases\tbins\tbest_bin\tbest_bases\tcompleteness\n";
+  for (size_t g = 0; g <= G; g++) {
+    const uint64_t* r = by_genome + g * BINEVAL_GENOME_COLS;
+    out += "G\t" + (g < G ? genomes[g] : std::string("."));
+    for (size_t j = 0; j < BINEVAL_GENOME_COLS; j++) out += "\t" + n(r[j]);
+    out += "\t" + bineval_frac((double)r[6], (double)r[1]) + "\n";
+  }
+  out += "#B\tbin\tcontigs\tbases\ttop_genome\ttop_bases\tnone_bases\tpurity\tcompleteness\n";
+  for (size_t b = 0; b < n_bins; b++) {
+    const bool top = top_genome[b] < G;
+    out += "B\t" + (b < bin_names.size() ? bin_names[b] : std::string("?")) + "\t" + std::to_string(contigs[b]) + "\t" + n(bases[b]) + "\t" +
+           (top ? genomes[top_genome[b]] : std::string(".")) + "\t" + n(top_bases[b]) + "\t" + n(none_bases[b]) + "\t" +
+           bineval_frac((double)top_bases[b], (double)bases[b]) + "\t" +
+           (top ? bineval_frac((double)top_bases[b], (double)by_genome[top_genome[b] * BINEVAL_GENOME_COLS + 1]) : std::string("NA")) + "\n";
+  }
+  return out;
+}
+
+std::string bineval_cell_rows(const std::vector<std::string>& bin_names, const std::vector<std::string>& genomes, const uint32_t* bin, const uint32_t* genome,
+                              const uint32_t* contigs, const uint64_t* bases, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++)
+    out += (bin[i] < bin_names.size() ? bin_names[bin[i]] : std::string("?")) + "\t" + (genome[i] < genomes.size() ? genomes[genome[i]] : std::string(".")) + "\t" +
+           std::to_string(contigs[i]) + "\t" + std::to_string((unsigned long long)bases[i]) + "\n";
+  return out;
+}
+
+std::string bineval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const std::vector<std::string>& bin_names,
+                                const uint32_t* genome, const uint64_t* length, const uint32_t* bin, const uint32_t* records, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++)
+    out += (i < names.size() ? names[i] : std::string("?")) + "\t" + std::to_string((unsigned long long)length[i]) + "\t" +
+           (genome[i] < genomes.size() ? genomes[genome[i]] : std::string(".")) + "\t" + (bin[i] < bin_names.size() ? bin_names[bin[i]] : std::string(".")) + "\t" +
+           std::to_string(records[i]) + "\n";
+  return out;
+}
+
 // ---- --eval-classified ---------------------------------------------------------------------------------------------------------------
 static const char* const TAXEVAL_RANK_NAMES[TAXEVAL_RANKS + 1] = {"no_rank", "domain", "phylum", "class", "order", "family", "genus", "species", "strain"};
 
@@ -1276,7 +1408,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax, first_not_asm, first_asm;
+  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax, first_not_asm, first_asm, first_not_bin, first_bin;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -1322,8 +1454,16 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
                           arg == "--eval-assembly-k";
     if (asm_flag && first_asm.empty()) first_asm = arg;
     if (!asm_flag && arg != "--device" && first_not_asm.empty()) first_not_asm = arg;  // what --eval-assembly does not take
+    const bool bin_flag = arg == "--eval-bins" || arg == "--eval-bins-truth" || arg == "--eval-bins-report" || arg == "--eval-bins-bins" || arg == "--eval-bins-contigs";
+    if (bin_flag && first_bin.empty()) first_bin = arg;
+    if (!bin_flag && arg != "--device" && first_not_bin.empty()) first_not_bin = arg;  // what --eval-bins does not take
     if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
     else if (arg == "--eval-assembly") { if (!file(&a->eval_assembly)) return false; }
+    else if (arg == "--eval-bins") { if (!file(&a->eval_bins)) return false; }
+    else if (arg == "--eval-bins-truth") { if (!file(&a->eval_bins_truth)) return false; }
+    else if (arg == "--eval-bins-report") { if (!file(&a->eval_bins_report)) return false; }
+    else if (arg == "--eval-bins-bins") { if (!file(&a->eval_bins_bins)) return false; }
+    else if (arg == "--eval-bins-contigs") { if (!file(&a->eval_bins_contigs)) return false; }
     else if (arg == "--eval-assembly-truth") { if (!file(&a->eval_assembly_truth)) return false; }
     else if (arg == "--eval-assembly-report") { if (!file(&a->eval_assembly_report)) return false; }
     else if (arg == "--eval-assembly-contigs") { if (!file(&a->eval_assembly_contigs)) return false; }
@@ -1509,6 +1649,17 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     }
     if (a->eval_assembly_truth.empty()) { *err = "--eval-assembly needs --eval-assembly-truth"; return false; }
     if (a->eval_assembly_report.empty()) { *err = "--eval-assembly needs --eval-assembly-report"; return false; }
+    return true;
+  }
+  if (!first_bin.empty()) {  // the seventh mode without a simulation
+    if (a->eval_bins.empty()) { *err = first_bin + " needs --eval-bins"; return false; }
+    if (!first_not_bin.empty()) {
+      *err = "--eval-bins runs no simulation: it takes only --eval-bins-truth, --eval-bins-report, --eval-bins-bins, --eval-bins-contigs and --device ('" +
+             first_not_bin + "' given)";
+      return false;
+    }
+    if (a->eval_bins_truth.empty()) { *err = "--eval-bins needs --eval-bins-truth"; return false; }
+    if (a->eval_bins_report.empty()) { *err = "--eval-bins needs --eval-bins-report"; return false; }
     return true;
   }
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }

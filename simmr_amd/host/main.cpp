@@ -1615,6 +1615,117 @@ static int run_eval_assembly(const CliArgs& args) {
   return 0;
 }
 
+// `--eval-bins BINS.tsv --eval-bins-truth CONTIGS.tsv --eval-bins-report OUT`: no simulation.  Both files go up in pieces cut at the
+// last newline (sam_file_pieces).  The host reads every piece once for the names: the truth's contig names and its genomes (the
+// distinct field-8 values other than "."), in a pass in front of the reset, which needs them; the records' bin names, of which a
+// bin's name is the one at its first_record.
+struct BinevalHandle {
+  simmr_bineval* h = nullptr;
+  ~BinevalHandle() { simmr_bineval_destroy(h); }
+};
+static int run_eval_bins(const CliArgs& args) {
+  {
+    FILE* f = fopen(args.eval_bins.c_str(), "rb");
+    if (!f) return die("--eval-bins: cannot open " + args.eval_bins);
+    fclose(f);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  BinevalHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_bineval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-bins: ") + simmr_last_error(eng));
+  std::vector<std::string> t_names, t_genomes, r_bins;
+  std::vector<uint8_t> host;
+  struct Piece { GrowBuf dev; size_t n = 0; };
+  std::vector<std::unique_ptr<Piece>> pieces;
+  info("Parsing " + args.eval_bins_truth);
+  if (int rc = sam_file_pieces("--eval-bins-truth", args.eval_bins_truth, [&](const uint8_t* d, size_t n) {
+        pieces.emplace_back(new Piece());
+        uint8_t* keep = pieces.back()->dev.room(n);
+        host.resize(n);
+        if (!keep || hipMemcpy(keep, d, n, hipMemcpyDeviceToDevice) != hipSuccess || hipMemcpy(host.data(), d, n, hipMemcpyDeviceToHost) != hipSuccess)
+          return die("--eval-bins-truth: device allocation failed");
+        pieces.back()->n = n;
+        bineval_truth_names((const char*)host.data(), n, &t_names, &t_genomes);
+        return 0;
+      }))
+    return rc;
+  std::vector<std::string> genomes;
+  for (const std::string& g : t_genomes)
+    if (g != "." && !g.empty()) genomes.push_back(g);
+  std::vector<std::string>().swap(t_genomes);
+  std::sort(genomes.begin(), genomes.end());
+  genomes.erase(std::unique(genomes.begin(), genomes.end()), genomes.end());
+  std::vector<const char*> gname;
+  for (const std::string& s : genomes) gname.push_back(s.c_str());
+  const simmr_bineval_config cfg{(uint32_t)gname.size(), 64u, gname.data()};
+  if (simmr_bineval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-bins-truth: ") + simmr_last_error(eng));
+  for (const auto& p : pieces)
+    if (simmr_bineval_truth_add(ev.h, (const uint8_t*)p->dev.p, p->n) != SIMMR_OK) return die(std::string("--eval-bins-truth: ") + simmr_last_error(eng));
+  uint64_t n_truth = 0;
+  if (simmr_bineval_truth_plan(ev.h, &n_truth) != SIMMR_OK) return die(std::string("--eval-bins-truth: ") + simmr_last_error(eng));
+  pieces.clear();
+  info("Parsing " + args.eval_bins);
+  if (int rc = sam_file_pieces("--eval-bins", args.eval_bins, [&](const uint8_t* d, size_t n) {
+        if (simmr_bineval_add(ev.h, d, n) != SIMMR_OK) return die(std::string("--eval-bins: ") + simmr_last_error(eng));
+        host.resize(n);
+        // (a copy on the null stream: it ends behind the add's lookups, so the walker may reuse the buffer)
+        if (hipMemcpy(host.data(), d, n, hipMemcpyDeviceToHost) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return die("--eval-bins: copy from the device failed");
+        bineval_record_bins((const char*)host.data(), n, &r_bins);
+        return 0;
+      }))
+    return rc;
+  simmr_bineval_counts c{};
+  static_assert(sizeof(c) == BINEVAL_N_COUNTS * sizeof(uint64_t) && BINEVAL_GENOME_COLS == SIMMR_BINEVAL_GENOME_COLS, "the report names every count and column");
+  std::vector<uint64_t> by_genome((genomes.size() + 1) * BINEVAL_GENOME_COLS);
+  if (simmr_bineval_read(ev.h, &c, by_genome.data()) != SIMMR_OK) return die(std::string("--eval-bins: ") + simmr_last_error(eng));
+  const uint64_t nb = c.bins, nb1 = std::max<uint64_t>(nb, 1), nc = c.cells, nc1 = std::max<uint64_t>(nc, 1), nt = c.truth_records, nt1 = std::max<uint64_t>(nt, 1);
+  // the columns: 64-bit ones in one buffer, 32-bit ones in another, bins then cells then contigs
+  GrowBuf d_wide, d_narrow;
+  const uint64_t n_wide = 3 * nb1 + nc1 + nt1, n_narrow = 3 * nb1 + 3 * nc1 + 3 * nt1;
+  uint64_t* const w = (uint64_t*)d_wide.room(n_wide * 8);
+  uint32_t* const u = (uint32_t*)d_narrow.room(n_narrow * 4);
+  if (!w || !u) return die("--eval-bins: device allocation failed");
+  uint64_t *wb = w, *wc = w + 3 * nb1, *wt = wc + nc1;
+  uint32_t *ub = u, *uc = u + 3 * nb1, *ut = uc + 3 * nc1;
+  if (simmr_bineval_bins(ev.h, ub, wb, wb + nb1, ub + nb1, ub + 2 * nb1, wb + 2 * nb1, nb, nullptr) != SIMMR_OK ||
+      simmr_bineval_cells(ev.h, uc, uc + nc1, uc + 2 * nc1, wc, nc, nullptr) != SIMMR_OK ||
+      simmr_bineval_contigs(ev.h, ut, wt, ut + nt1, ut + 2 * nt1, nt, nullptr) != SIMMR_OK)
+    return die(std::string("--eval-bins: ") + simmr_last_error(eng));
+  std::vector<uint64_t> hw(n_wide);
+  std::vector<uint32_t> hu(n_narrow);
+  if (hipMemcpy(hw.data(), w, n_wide * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hu.data(), u, n_narrow * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return die("--eval-bins: copy from the device failed");
+  wb = hw.data(); wc = wb + 3 * nb1; wt = wc + nc1;
+  ub = hu.data(); uc = ub + 3 * nb1; ut = uc + 3 * nc1;
+  std::vector<std::string> bin_names;
+  for (uint64_t b = 0; b < nb; b++) {
+    const uint32_t first = ub[nb1 + b];
+    bin_names.push_back(first < r_bins.size() ? r_bins[first] : std::string("?"));
+  }
+  std::string err;
+  OutFile report(args.eval_bins_report, false);
+  report.append(bineval_report((const uint64_t*)&c, genomes, by_genome.data(), bin_names, ub, wb, wb + nb1, ub + 2 * nb1, wb + 2 * nb1, nb));
+  if (!report.close(&err)) return die("--eval-bins-report: " + err);
+  if (!args.eval_bins_bins.empty()) {
+    OutFile rows(args.eval_bins_bins, false);
+    rows.append(bineval_cell_rows(bin_names, genomes, uc, uc + nc1, uc + 2 * nc1, wc, nc));
+    if (!rows.close(&err)) return die("--eval-bins-bins: " + err);
+  }
+  if (!args.eval_bins_contigs.empty()) {
+    OutFile rows(args.eval_bins_contigs, false);
+    rows.append(bineval_contig_rows(t_names, genomes, bin_names, ut, wt, ut + nt1, ut + 2 * nt1, nt));
+    if (!rows.close(&err)) return die("--eval-bins-contigs: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_records) + " contigs, " + n(c.truth_bases) + " bases of " + n(genomes.size()) + " genomes (" + n(c.truth_none) + " contigs of none)");
+  info("Bins: " + n(c.records) + " records: " + n(c.unknown_contig) + " of unknown contigs, " + n(c.repeated) + " repeated; " + n(c.assigned) + " contigs in " +
+       n(c.bins) + " bins, " + n(c.cells) + " cells");
+  info("Wrote " + args.eval_bins_report);
+  return 0;
+}
+
 static int run_main(int argc, char** argv) {
   CliArgs args;
   std::string err;
@@ -1627,6 +1738,7 @@ static int run_main(int argc, char** argv) {
   if (!args.eval_vcf.empty()) return run_eval_vcf(args);
   if (!args.eval_classified.empty()) return run_eval_classified(args);
   if (!args.eval_assembly.empty()) return run_eval_assembly(args);
+  if (!args.eval_bins.empty()) return run_eval_bins(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

@@ -242,6 +242,34 @@ std::string asmeval_report(const uint64_t* counts, uint32_t k, const std::vector
 // top_genome, top_kmers, and the genome's name (genomes: sorted, the row is its index), "." where the contig has no vote.
 std::string asmeval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const uint64_t* length, const uint32_t* kmers,
                                 const uint32_t* found, const uint32_t* shared, const uint32_t* top_genome, const uint32_t* top_kmers, size_t n);
+// ---- --eval-bins: the host's share (the names of both texts, the report with its fractions, the two files) ----
+constexpr size_t BINEVAL_N_COUNTS = 21, BINEVAL_GENOME_COLS = 7;
+// The record lines of the truth text[0, n), which begins at a line's start (empty lines and lines that begin with '#' are none; a
+// '\r' directly before '\n' is not part of the line): per line its field 1 and its field 8 ("" where the line has fewer fields).
+void bineval_truth_names(const char* text, size_t n, std::vector<std::string>* contig, std::vector<std::string>* genome);
+// The record lines of the candidate text[0, n) (lines that begin with '#' or '@' are none): per line its field 2 ("" without one).
+void bineval_record_bins(const char* text, size_t n, std::vector<std::string>* bin);
+// The adjusted Rand index of the assigned contigs of real genomes from the three pair sums and their number n, as "%.6f":
+// (cells - E) / ((bins + genomes) / 2 - E) with E = bins * genomes / C(n, 2); "NA" where C(n, 2) or the denominator is 0.
+std::string bineval_ari(uint64_t pairs_cells, uint64_t pairs_bins, uint64_t pairs_genomes, uint64_t n);
+// The file of --eval-bins-report: the counts of struct simmr_bineval_counts as "#name\tvalue" lines in the struct's order
+// (counts[BINEVAL_N_COUNTS]); "#purity" = sum_top_bases / assigned_bases and "#completeness" = sum_best_bases / the truth bases of the
+// real genomes, each as the exact fraction and "%.6f" ("NA" where the denominator is 0); "#f1" of the two; "#assigned_fraction" =
+// assigned_bases / truth_bases; "#ari_contigs" (bineval_ari with n = the assigned contigs of the real genomes); "#average_purity" =
+// the mean over the bins with bases of top_bases / bases and "#average_completeness" = the mean over the real genomes with truth
+// bases of best_bases / truth_bases, summed in row order in double; then a header line and a G row per genome (genomes: the sorted
+// names; "." for the last row) with the seven columns of by_genome[n + 1][7] and best_bases / truth_bases, and a header line and a B
+// row per bin: its name (bin_names[b]; "?" beyond them), contigs, bases, the top genome's name or ".", top_bases, none_bases,
+// purity = top_bases / bases and completeness = top_bases / the truth bases of the top genome.
+std::string bineval_report(const uint64_t* counts, const std::vector<std::string>& genomes, const uint64_t* by_genome, const std::vector<std::string>& bin_names,
+                           const uint32_t* contigs, const uint64_t* bases, const uint64_t* none_bases, const uint32_t* top_genome, const uint64_t* top_bases,
+                           size_t n_bins);
+// The rows of --eval-bins-bins for n cells: the bin's name, the genome's name or ".", contigs, bases.
+std::string bineval_cell_rows(const std::vector<std::string>& bin_names, const std::vector<std::string>& genomes, const uint32_t* bin, const uint32_t* genome,
+                              const uint32_t* contigs, const uint64_t* bases, size_t n);
+// The rows of --eval-bins-contigs for n truth contigs in truth order: name, length, the genome's name or ".", the bin's name or ".", records.
+std::string bineval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const std::vector<std::string>& bin_names,
+                                const uint32_t* genome, const uint64_t* length, const uint32_t* bin, const uint32_t* records, size_t n);
 // `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
 // (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
 // ascend, and its text lies at `offset` of the byte source.
@@ -561,6 +589,11 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string eval_assembly_report;   // --eval-assembly-report FILE: the counts, completeness per genome and overall, the QV, the contiguity of both sides
   std::string eval_assembly_contigs;  // --eval-assembly-contigs FILE: a row per contig
   uint32_t eval_assembly_k = 31;      // --eval-assembly-k K: odd, 15 .. 31
+  std::string eval_bins;              // --eval-bins FILE: no simulation; a binner's contig<TAB>bin text scored against --eval-bins-truth (simmr_bineval_*)
+  std::string eval_bins_truth;        // --eval-bins-truth FILE: the file of --eval-assembly-contigs
+  std::string eval_bins_report;       // --eval-bins-report FILE: the counts, purity, completeness, F1, ARI, a row per genome and per bin
+  std::string eval_bins_bins;         // --eval-bins-bins FILE: the cells with names
+  std::string eval_bins_contigs;      // --eval-bins-contigs FILE: a row per truth contig
   bool eval_vcf_filtered = false;  // --eval-vcf-filtered: score the records whose FILTER is neither "." nor PASS too
   std::string stats;  // --stats FILE: the run's quality, base and mismatch tables (simmr_stats_add over every range) as a TSV
   std::string depth;        // --depth FILE: covered positions, depth sum and maximum per contig (simmr_depth_add over every range) as a TSV
