@@ -1898,6 +1898,113 @@ int simmr_bineval_contigs(simmr_bineval* h, uint32_t* genome_dev, uint64_t* leng
  * simmr_bineval_add lies inside that span.  *plan_sort_ms (may be NULL) = the sort's share of the last plan. */
 int simmr_last_bineval_ms(simmr_bineval* h, float* ms, float* plan_sort_ms);
 
+/* ---- a read error corrector's output scored against the true reads: a SAM text and a FASTQ text in HBM, compared base by base ----
+ * Replaces nothing in the reference.  The truth is the text of simmr_sam_emit (either order), or any SAM that follows the rules
+ * below: a line carries the read as emitted (SEQ, QUAL), its strand, and in MD:Z the reference base at every mismatch, so the true
+ * read is SEQ with MD's letters put in.  The other text is what a corrector (BFC, Lighter, Musket, Karect, ...) made of the run's
+ * FASTQ.  No profile changes a read's length and the truth stops at substitutions, so the comparison is position by position and no
+ * alignment is made.  No simulation, no genome, no name table: like simmr_mapeval_* without its names.
+ *
+ * Truth text.  The line rules of simmr_mapeval_truth_add: whole lines of plain SAM, every line ends in '\n' except that the last
+ * line of a call may lack it; the caller cuts a file at line ends, at most SIMMR_FIT_SAM_MAX_BYTES a call; an empty line is skipped
+ * and not counted; a line that starts with '@' is a header line, counted and skipped.  Every other line is a record, L = the
+ * length of SEQ, and goes through these steps in this order:
+ *   0. Malformed (sticky): what simmr_mapeval_* calls malformed (fewer than 11 fields; a FLAG, POS or MAPQ that is no number of 1 to
+ *      18 digits; a MAPQ above 255; a POS above 2^31 - 1; a CIGAR that is neither "*" nor (<digits><op>)+; an interval that ends
+ *      above 2^40).  Nothing of a record can be read before this, so it stands first.
+ *   1. Counted truth_skipped: FLAG has 0x100, 0x800 or 0x4; SEQ is "*"; the CIGAR is not exactly one run "<L>M" (1 to 18 digits,
+ *      the op 'M' itself).
+ *   2. Malformed (sticky): a QNAME that is no read id (1 to 18 decimal digits) or a POS of 0; a QUAL that is neither "*" nor as long
+ *      as SEQ, or a QUAL byte outside '!' .. '~'; no "MD:Z:" field among the optional fields (the first one counts); an MD with
+ *      '^' or any byte outside the digits and 'A' .. 'Z', or a number of more than 9 digits; MD's matches plus mismatches differ
+ *      from L.  (An empty SEQ never gets here: "0M" is no run.)
+ *   3. An entry: key = id << 1 | (FLAG & 0x80 ? 1 : 0), L, and per base i of the read IN THE READ'S OWN ORIENTATION (FLAG 0x10:
+ *      reversed and complemented, the qualities back to front: the orientation rule of simmr_fit_add_sam) the original class o[i]
+ *      (from SEQ), the true class t[i] (MD's letter at a mismatch, o[i] elsewhere) and the quality q[i] = QUAL byte - 33, or 94
+ *      where QUAL is "*".  Classes: A C G T in either letter case are 0 .. 3, every other byte is 4; the complement of a class
+ *      below 4 is 3 - class, 4 stays.  before = the positions with o != t and t != 4.  RNAME is not resolved.
+ *
+ * Corrected text.  Records of lines_per_record lines: 4 (FASTQ: '@'name, bases, '+', qualities) or 2 (FASTA: '>'name, bases).
+ * Unlike the SAM side EVERY '\n' ends a line, an empty one too, because an empty sequence line is a legal record (a read trimmed
+ * to nothing).  The last line of a call may lack its '\n' (a last line that is EMPTY needs it: behind the last '\n' of a call
+ * there is no line).  The caller cuts at record ends, at most SIMMR_FIT_SAM_MAX_BYTES a call.  No CRLF (a '\r' is a byte of its
+ * line: a base of class 4, a byte of the name) and no records whose bases or qualities run over several lines.  Malformed (sticky):
+ * a call whose lines are no multiple of lines_per_record; a first line that does not start with '@' ('>' for two lines); with four
+ * lines a third line that does not start with '+', or a fourth line whose length differs from the second's.  The quality line is
+ * checked for its length only.
+ * Name.  The bytes behind the first character up to the first ' ', '\t' or the line's end, read by the rule of
+ * simmr_ovleval_*: 1 to 18 decimal digits, then nothing, "/1" or "/2"; key = id << 1 | ("/2" ? 1 : 0).  A name that is no read
+ * name, or a key without an entry, counts unknown_read; every other record is scored (counted `scored`).
+ *
+ * Verdict.  Lc = the length of the record's bases, c[i] the class of byte i.  For i < min(L, Lc) (the COMPARED positions):
+ *   t == 4: ambiguous.   o == t: kept if c == t, else damaged.   o != t: fixed if c == t, left if c == o, else miscorrected.
+ * For Lc <= i < L: ambiguous if t == 4, else trimmed_error if o != t, else trimmed_clean.  Only trimming at the 3' end is
+ * understood: a read trimmed at its 5' end is compared from its first base like any other, and so is a read whose corrector put
+ * in or took out bases in the middle.  Lc > L: extra += Lc - L (longer_records counts the record, trimmed_records one with Lc < L).
+ * The nine sums of a record add up to L + extra.  residual = the positions i < L with t != 4 that do not show t (c != t, or
+ * i >= Lc), plus extra = damaged + left + miscorrected + trimmed_error + trimmed_clean + extra: 0 means the record is the true read.
+ * Tables, over the compared positions: cube[t][o][c] (125 sums, every position); by_qual[q][v] and
+ * by_pos[min(i, SIMMR_CORREVAL_POS - 1)][v] with v = 0 kept, 1 damaged, 2 fixed, 3 left, 4 miscorrected (ambiguous positions are
+ * in the cube only).
+ * Per entry: hits += 1 per scored record, residual = the minimum over its records (0xffffffff: no hit).
+ * Every output is an integer sum or minimum: the same for any launch geometry, any cut of either text into adds at line or record
+ * ends, and any order of the records. */
+#define SIMMR_CORREVAL_POS 512u      /* rows of by_pos: the last one takes every position from 511 on */
+#define SIMMR_CORREVAL_QUALS 95u     /* rows of by_qual: 0 .. 93, and 94 for a truth QUAL of "*" */
+#define SIMMR_CORREVAL_CLASSES 5u    /* kept, damaged, fixed, left, miscorrected */
+#define SIMMR_CORREVAL_NO_HIT 0xffffffffu
+
+typedef struct simmr_correval simmr_correval;
+
+typedef struct simmr_correval_config {   /* HOST memory */
+  uint32_t lines_per_record;            /* 4 (FASTQ) or 2 (two-line FASTA); 0: 4 */
+  uint32_t reserved;                    /* 0 */
+} simmr_correval_config;
+
+typedef struct simmr_correval_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_lines, truth_header, truth_records, truth_entries, truth_skipped;   /* lines = header + records; cumulative since the reset */
+  uint64_t lines, records;                                 /* the corrected side, since the last truth plan */
+  uint64_t unknown_read, scored, trimmed_records, longer_records;   /* records = unknown_read + scored */
+  uint64_t compared;                                       /* positions: the sum of min(L, Lc), and the sum of the cube */
+  uint64_t kept, damaged, fixed, left, miscorrected, ambiguous, trimmed_error, trimmed_clean, extra;   /* bases */
+  uint64_t missing, multiple;                              /* truth entries with no hit, with more than one */
+  uint64_t clean_kept, clean_damaged;                      /* entries with a hit and before == 0: residual == 0, residual > 0 */
+  uint64_t fixed_all, improved, unchanged, worse;          /* before > 0: residual == 0, 0 < residual < before, == before, > before */
+} simmr_correval_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_mapeval_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error). */
+int simmr_correval_create(simmr_engine* e, simmr_correval** out);
+void simmr_correval_destroy(simmr_correval* h);
+/* Takes lines_per_record and empties both sides.  Synchronises.  SIMMR_EINVAL: a NULL argument, a lines_per_record other than 0, 2
+ * or 4, a reserved word that is not 0. */
+int simmr_correval_reset(simmr_correval* h, const simmr_correval_config* cfg);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for an entry per 21 bytes of text (no record is shorter) and for a base per
+ * byte of text, in two byte planes (o | t << 3, and q), grows with the object.  SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL
+ * text with n_bytes > 0.  SIMMR_ENOTSUP: n_bytes above SIMMR_FIT_SAM_MAX_BYTES. */
+int simmr_correval_truth_add(simmr_correval* h, const uint8_t* text, uint64_t n_bytes);
+/* Sorts the entries by key (the radix sort of simmr_sam_sort_plan, over the bits of the largest key), checks that no key stands
+ * twice, empties the corrected side and synchronises.  *n_entries (may be NULL) = the entries.  SIMMR_EINVAL: a malformed truth
+ * record, or two entries with one key.  SIMMR_ERANGE: 2^31 entries or more. */
+int simmr_correval_truth_plan(simmr_correval* h, uint64_t* n_entries);
+/* Scores the records of text[0 .. n_bytes) (DEVICE, as above; whole records) against the plan.  Only enqueues.  A line index of
+ * four bytes per byte of text grows with the object.  SIMMR_ESTATE: no truth plan in force.  SIMMR_EINVAL, SIMMR_ENOTSUP: as
+ * simmr_correval_truth_add. */
+int simmr_correval_add(simmr_correval* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts, cube_host[5][5][5] ([t][o][c]), by_qual_host[SIMMR_CORREVAL_QUALS][5] and by_pos_host[SIMMR_CORREVAL_POS][5] (HOST,
+ * any may be NULL).  Synchronises.  The last eight counts are made here, by a reduction over the entries.  SIMMR_EINVAL: a
+ * malformed record on either side since the reset (nothing is written).  SIMMR_ESTATE: no reset yet. */
+int simmr_correval_read(simmr_correval* h, simmr_correval_counts* counts, uint64_t* cube_host, uint64_t* by_qual_host, uint64_t* by_pos_host);
+/* The truth entries in ascending key order (unique keys: the order is a function of the input), five columns (DEVICE, capacity
+ * entries each, any may be NULL): key (u64), length, before, residual (SIMMR_CORREVAL_NO_HIT: no hit), hits (u32).  Synchronises.
+ * SIMMR_ESTATE: no truth plan.  SIMMR_ERANGE, nothing written: capacity < n_entries. */
+int simmr_correval_emit(simmr_correval* h, uint64_t* key_dev, uint32_t* length_dev, uint32_t* before_dev, uint32_t* residual_dev, uint32_t* hits_dev,
+                        uint64_t capacity);
+/* HIP-event time (ms) of the device work since the last reset: the adds of either side, the plans and the reads.  Synchronises the
+ * stream.  A run of adds with no synchronising call of this object between them is timed as one span. */
+int simmr_last_correval_ms(simmr_correval* h, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

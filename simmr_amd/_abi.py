@@ -321,6 +321,25 @@ class BinevalCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in BINEVAL_COUNTS]
 
 
+CORREVAL_COUNTS = ("truth_lines", "truth_header", "truth_records", "truth_entries", "truth_skipped", "lines", "records", "unknown_read", "scored",
+                   "trimmed_records", "longer_records", "compared", "kept", "damaged", "fixed", "left", "miscorrected", "ambiguous", "trimmed_error",
+                   "trimmed_clean", "extra", "missing", "multiple", "clean_kept", "clean_damaged", "fixed_all", "improved", "unchanged", "worse")
+CORREVAL_CLASSES = ("kept", "damaged", "fixed", "left", "miscorrected")  # SIMMR_CORREVAL_CLASSES
+CORREVAL_POS = 512   # SIMMR_CORREVAL_POS
+CORREVAL_QUALS = 95  # SIMMR_CORREVAL_QUALS
+CORREVAL_NO_HIT = 0xffffffff  # SIMMR_CORREVAL_NO_HIT
+
+
+class CorrevalCounts(C.Structure):
+    """struct simmr_correval_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in CORREVAL_COUNTS]
+
+
+class CorrevalConfig(C.Structure):
+    """struct simmr_correval_config (host memory)"""
+    _fields_ = [("lines_per_record", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class BinevalConfig(C.Structure):
     """struct simmr_bineval_config (host memory)"""
     _fields_ = [("n_genomes", C.c_uint32), ("hash_bits", C.c_uint32), ("genome", C.POINTER(C.c_char_p))]
@@ -492,6 +511,15 @@ SYMBOLS = {
     "simmr_asmeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_asmeval_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
     "simmr_last_asmeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float), _P(C.c_float)]),
+    "simmr_correval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_correval_destroy": (None, [C.c_void_p]),
+    "simmr_correval_reset": (C.c_int, [C.c_void_p, _P(CorrevalConfig)]),
+    "simmr_correval_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_correval_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "simmr_correval_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_correval_read": (C.c_int, [C.c_void_p, _P(CorrevalCounts), _P(C.c_uint64), _P(C.c_uint64), _P(C.c_uint64)]),
+    "simmr_correval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_last_correval_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
     "simmr_bineval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "simmr_bineval_destroy": (None, [C.c_void_p]),
     "simmr_bineval_reset": (C.c_int, [C.c_void_p, _P(BinevalConfig)]),

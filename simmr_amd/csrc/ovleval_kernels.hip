@@ -127,6 +127,9 @@ SIMMR_DEV bool ove_name_key(const uint8_t* __restrict__ t, uint32_t a, uint32_t 
   return true;
 }
 
+// The kernels.  correval_kernels.hip (a translation unit of its own) includes this file with OVE_ROUTINES_ONLY defined and takes the
+// routines above without them, as this file takes mapeval_kernels.hip's.
+#ifndef OVE_ROUTINES_ONLY
 // ---- the line index and the scan ------------------------------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(FSAM_WG)
 k_ove_index(const uint8_t* __restrict__ text, uint64_t n_bytes, uint64_t n_tiles, uint64_t* __restrict__ tile_sum,
@@ -331,5 +334,6 @@ k_ove_reduce(const uint32_t* __restrict__ best, const uint32_t* __restrict__ hit
     if (v) atomicAdd(k < 4u ? counts + OC_PAIRS_FOUND + k : by_len + (k - 4u), (unsigned long long)v);
   }
 }
+#endif  // OVE_ROUTINES_ONLY
 
 }  // namespace simmr

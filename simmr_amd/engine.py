@@ -742,6 +742,90 @@ class TaxEval:
                 self.engine._mapevals.remove(self)
 
 
+class CorrEval:
+    """A read error corrector's output scored against the true reads on the device (simmr_correval_*, include/simmr_hip.h states the
+    rules).  truth_add() the truth SAM text, truth_plan(), add() the corrected FASTQ (or two-line FASTA) in whole records, then read()
+    and entries().  A text is bytes (copied up) or a contiguous CUDA uint8 tensor; the adds only enqueue, so every text is kept until
+    a call that synchronises."""
+
+    def __init__(self, engine: "Engine", lines_per_record: int = 4):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_correval_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(lines_per_record)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, lines_per_record: int = 4):
+        cfg = _abi.CorrevalConfig(int(lines_per_record), 0)
+        try:
+            self._check(self.lib.simmr_correval_reset(self._h, C.byref(cfg)))
+        finally:
+            self._texts = []  # the reset has synchronised
+
+    _text = Mapeval._text
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_correval_truth_add(self._h, p, n))
+
+    def truth_plan(self) -> int:
+        n = C.c_uint64(0)
+        try:
+            self._check(self.lib.simmr_correval_truth_plan(self._h, C.byref(n)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_entries = int(n.value)
+        return self.n_entries
+
+    def add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_correval_add(self._h, p, n))
+
+    def read(self):
+        """(counts by the names of struct simmr_correval_counts, cube (5, 5, 5) [t][o][c], by_qual (95, 5), by_pos (512, 5)), uint64 arrays;
+        the five columns are kept, damaged, fixed, left, miscorrected"""
+        c = _abi.CorrevalCounts()
+        cube = np.zeros((5, 5, 5), dtype=np.uint64)
+        by_qual = np.zeros((_abi.CORREVAL_QUALS, 5), dtype=np.uint64)
+        by_pos = np.zeros((_abi.CORREVAL_POS, 5), dtype=np.uint64)
+        u64 = C.POINTER(C.c_uint64)
+        try:
+            self._check(self.lib.simmr_correval_read(self._h, C.byref(c), cube.ctypes.data_as(u64), by_qual.ctypes.data_as(u64), by_pos.ctypes.data_as(u64)))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.CORREVAL_COUNTS}, cube, by_qual, by_pos
+
+    def entries(self):
+        """(key uint64, length, before, residual, hits uint32) of every truth entry, ascending by key, as numpy arrays"""
+        torch = _torch()
+        n = getattr(self, "n_entries", 0)
+        dev = self.engine.device
+        key = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        cols = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(4)]
+        self._check(self.lib.simmr_correval_emit(self._h, C.c_void_p(key.data_ptr()), *[C.c_void_p(c.data_ptr()) for c in cols], n))
+        self._texts = []
+        return (key[:n].cpu().numpy().view(np.uint64),) + tuple(c[:n].cpu().numpy().view(np.uint32) for c in cols)
+
+    def last_ms(self) -> float:
+        return self.engine._ms(self.lib.simmr_last_correval_ms, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_correval_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
 def cut_at_line_ends(text: bytes, pieces: int):
     """`text` in at most `pieces` parts of about one size, each cut behind a newline"""
     out, a = [], 0
@@ -1624,6 +1708,35 @@ class Engine:
                 ev.add(t)
             counts, by_genome = ev.read()
             return counts, by_genome, ev.bins(), ev.cells(), ev.contigs()
+        finally:
+            ev.close()
+
+    # -- a read error corrector's output against the true reads -------------------------------
+    def correction_eval_open(self, lines_per_record: int = 4) -> "CorrEval":
+        """An evaluation object (simmr_correval_*).  Closed by its close(), or by the engine's before the engine goes (it is kept in
+        the list of the mapeval objects, which the engine closes first)."""
+        m = CorrEval(self, lines_per_record)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
+
+    def correction_eval(self, truth_sam_bytes, corrected_bytes, lines_per_record: int = 4):
+        """Scores the corrected reads `corrected_bytes` (FASTQ, or two-line FASTA with lines_per_record=2) against the truth SAM
+        `truth_sam_bytes` (each bytes, a CUDA uint8 tensor, or a list of those: an add each, cut at a line's end for the truth and at
+        a record's end for the reads).  Returns (counts as a dict, cube (5, 5, 5), by_qual (95, 5), by_pos (512, 5), (key, length,
+        before, residual, hits) of the truth entries in key order)."""
+        def adds(text):
+            return list(text) if isinstance(text, (list, tuple)) else [text]
+        ev = self.correction_eval_open(lines_per_record)
+        try:
+            for t in adds(truth_sam_bytes):
+                ev.truth_add(t)
+            ev.truth_plan()
+            for t in adds(corrected_bytes):
+                ev.add(t)
+            counts, cube, by_qual, by_pos = ev.read()
+            return counts, cube, by_qual, by_pos, ev.entries()
         finally:
             ev.close()
 

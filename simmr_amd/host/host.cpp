@@ -824,6 +824,14 @@ std::string usage() {
          "            --eval-bins-report <FILE>  the result as a TSV: the counts as #name value lines, the fractions, a G row per genome, a B row per bin\n"
          "            --eval-bins-bins <FILE>  every (bin, genome) cell: bin, genome, contigs, bases\n"
          "            --eval-bins-contigs <FILE>  every truth contig: name, length, genome, bin or '.', records\n"
+         "            --eval-corrected <FILE>  no simulation: score a read error corrector's FASTQ against the true reads of --eval-corrected-truth,\n"
+         "                            base by base on the device: kept, damaged, fixed, left, miscorrected, trimmed; gain, sensitivity,\n"
+         "                            specificity; takes only --eval-corrected-truth, --eval-corrected-report, --eval-corrected-reads,\n"
+         "                            --eval-corrected-fasta and --device\n"
+         "            --eval-corrected-truth <FILE>  the file of --sam for the same run: SEQ, QUAL, the strand and MD:Z give every read's true bases\n"
+         "            --eval-corrected-report <FILE>  the result as a TSV: the counts as #name value lines, the three ratios, rows by quality and by position, the cube\n"
+         "            --eval-corrected-reads <FILE>  every read that is not its true self: id, mate, length, errors before, errors left or '.', records\n"
+         "            --eval-corrected-fasta  the corrected reads are two-line FASTA ('>'name, bases), not FASTQ\n"
          "            --stats <FILE>  the run's statistics as a long-form TSV (table set i j count, non-zero entries): reads and bases per mate,\n"
          "                            bases and edits by Phred, expected x written base, edits per read, GC per read, and per cycle the\n"
          "                            reads, quality sum, edits and base composition; counted on the device; combines with --truth;\n"
@@ -1087,6 +1095,65 @@ std::string asmeval_contig_rows(const std::vector<std::string>& names, const std
     out += "\t" + std::to_string((unsigned long long)length[i]) + "\t" + std::to_string(kmers[i]) + "\t" + std::to_string(found[i]) + "\t" +
            std::to_string(shared[i]) + "\t" + std::to_string(top_genome[i]) + "\t" + std::to_string(top_kmers[i]) + "\t" +
            (top_genome[i] < genomes.size() ? genomes[top_genome[i]] : std::string(".")) + "\n";
+  }
+  return out;
+}
+
+// ---- --eval-corrected ----------------------------------------------------------------------------------------------------------------
+std::string correval_ratio(bool negative, uint64_t num, uint64_t den) {
+  if (den == 0) return "NA";
+  const unsigned __int128 q = ((unsigned __int128)num * 2000000u + den) / ((unsigned __int128)den * 2u);  // millionths, half up
+  char buf[64];
+  snprintf(buf, sizeof buf, "%s%llu.%06llu", negative && q != 0 ? "-" : "", (unsigned long long)(q / 1000000u), (unsigned long long)(q % 1000000u));
+  return buf;
+}
+
+std::string correval_report(const uint64_t* counts, const uint64_t* cube, const uint64_t* by_qual, const uint64_t* by_pos) {
+  static const char* const NAMES[CORREVAL_N_COUNTS] = {
+      "truth_lines", "truth_header", "truth_records", "truth_entries", "truth_skipped", "lines", "records", "unknown_read", "scored", "trimmed_records",
+      "longer_records", "compared", "kept", "damaged", "fixed", "left", "miscorrected", "ambiguous", "trimmed_error", "trimmed_clean", "extra", "missing",
+      "multiple", "clean_kept", "clean_damaged", "fixed_all", "improved", "unchanged", "worse"};
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  std::string out;
+  for (size_t i = 0; i < CORREVAL_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + n(counts[i]) + "\n";
+  const uint64_t kept = counts[12], damaged = counts[13], fixed = counts[14], left = counts[15], mis = counts[16], trimmed_error = counts[18];
+  const unsigned __int128 errors128 = (unsigned __int128)fixed + left + mis + trimmed_error;
+  const uint64_t errors = errors128 > UINT64_MAX ? UINT64_MAX : (uint64_t)errors128;   // (sums of positions: far below 2^64)
+  const bool neg = damaged > fixed;
+  const uint64_t net = neg ? damaged - fixed : fixed - damaged;
+  out += "#gain\t" + std::string(neg ? "-" : "") + n(net) + "/" + n(errors) + "\t" + correval_ratio(neg, net, errors) + "\n";
+  out += "#sensitivity\t" + n(fixed) + "/" + n(errors) + "\t" + correval_ratio(false, fixed, errors) + "\n";
+  const unsigned __int128 clean128 = (unsigned __int128)kept + damaged;
+  const uint64_t clean = clean128 > UINT64_MAX ? UINT64_MAX : (uint64_t)clean128;
+  out += "#specificity\t" + n(kept) + "/" + n(clean) + "\t" + correval_ratio(false, kept, clean) + "\n";
+  auto rows = [&](const char* tag, const char* what, const uint64_t* table, size_t n_rows) {
+    out += std::string("#") + tag + "\t" + what + "\tkept\tdamaged\tfixed\tleft\tmiscorrected\n";
+    for (size_t r = 0; r < n_rows; r++) {
+      const uint64_t* v = table + r * 5;
+      if (!(v[0] | v[1] | v[2] | v[3] | v[4])) continue;
+      out += std::string(tag) + "\t" + n(r);
+      for (int j = 0; j < 5; j++) out += "\t" + n(v[j]);
+      out += "\n";
+    }
+  };
+  rows("Q", "quality", by_qual, CORREVAL_N_QUALS);
+  rows("P", "position", by_pos, CORREVAL_N_POS);
+  out += "#C\ttrue\toriginal\tA\tC\tG\tT\tN\n";
+  for (int t = 0; t < 5; t++)
+    for (int o = 0; o < 5; o++) {
+      out += std::string("C\t") + "ACGTN"[t] + "\t" + "ACGTN"[o];
+      for (int c = 0; c < 5; c++) out += "\t" + n(cube[(t * 5 + o) * 5 + c]);
+      out += "\n";
+    }
+  return out;
+}
+
+std::string correval_read_rows(const uint64_t* key, const uint32_t* length, const uint32_t* before, const uint32_t* residual, const uint32_t* hits, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++) {
+    if (hits[i] != 0u && residual[i] == 0u) continue;
+    out += std::to_string((unsigned long long)(key[i] >> 1)) + "\t" + std::to_string((unsigned)(key[i] & 1u)) + "\t" + std::to_string(length[i]) + "\t" +
+           std::to_string(before[i]) + "\t" + (hits[i] ? std::to_string(residual[i]) : std::string(".")) + "\t" + std::to_string(hits[i]) + "\n";
   }
   return out;
 }
@@ -1408,7 +1475,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax, first_not_asm, first_asm, first_not_bin, first_bin;
+  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax, first_not_asm, first_asm, first_not_bin, first_bin, first_not_corr, first_corr;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -1457,7 +1524,16 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     const bool bin_flag = arg == "--eval-bins" || arg == "--eval-bins-truth" || arg == "--eval-bins-report" || arg == "--eval-bins-bins" || arg == "--eval-bins-contigs";
     if (bin_flag && first_bin.empty()) first_bin = arg;
     if (!bin_flag && arg != "--device" && first_not_bin.empty()) first_not_bin = arg;  // what --eval-bins does not take
+    const bool corr_flag = arg == "--eval-corrected" || arg == "--eval-corrected-truth" || arg == "--eval-corrected-report" || arg == "--eval-corrected-reads" ||
+                           arg == "--eval-corrected-fasta";
+    if (corr_flag && first_corr.empty()) first_corr = arg;
+    if (!corr_flag && arg != "--device" && first_not_corr.empty()) first_not_corr = arg;  // what --eval-corrected does not take
     if (arg == "--fit-from-sam") { if (!file(&a->fit_from_sam)) return false; }
+    else if (arg == "--eval-corrected") { if (!file(&a->eval_corrected)) return false; }
+    else if (arg == "--eval-corrected-truth") { if (!file(&a->eval_corrected_truth)) return false; }
+    else if (arg == "--eval-corrected-report") { if (!file(&a->eval_corrected_report)) return false; }
+    else if (arg == "--eval-corrected-reads") { if (!file(&a->eval_corrected_reads)) return false; }
+    else if (arg == "--eval-corrected-fasta") a->eval_corrected_fasta = true;
     else if (arg == "--eval-assembly") { if (!file(&a->eval_assembly)) return false; }
     else if (arg == "--eval-bins") { if (!file(&a->eval_bins)) return false; }
     else if (arg == "--eval-bins-truth") { if (!file(&a->eval_bins_truth)) return false; }
@@ -1660,6 +1736,17 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     }
     if (a->eval_bins_truth.empty()) { *err = "--eval-bins needs --eval-bins-truth"; return false; }
     if (a->eval_bins_report.empty()) { *err = "--eval-bins needs --eval-bins-report"; return false; }
+    return true;
+  }
+  if (!first_corr.empty()) {  // the eighth mode without a simulation
+    if (a->eval_corrected.empty()) { *err = first_corr + " needs --eval-corrected"; return false; }
+    if (!first_not_corr.empty()) {
+      *err = "--eval-corrected runs no simulation: it takes only --eval-corrected-truth, --eval-corrected-report, --eval-corrected-reads, "
+             "--eval-corrected-fasta and --device ('" + first_not_corr + "' given)";
+      return false;
+    }
+    if (a->eval_corrected_truth.empty()) { *err = "--eval-corrected needs --eval-corrected-truth"; return false; }
+    if (a->eval_corrected_report.empty()) { *err = "--eval-corrected needs --eval-corrected-report"; return false; }
     return true;
   }
   if (a->single_reads) { *err = "--single-reads needs --fit-from-sam"; return false; }

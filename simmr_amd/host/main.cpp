@@ -1726,6 +1726,121 @@ static int run_eval_bins(const CliArgs& args) {
   return 0;
 }
 
+// `--eval-corrected READS.fastq --eval-corrected-truth TRUTH.sam --eval-corrected-report OUT`: no simulation, no genomes, one engine.
+// The truth goes up in pieces cut at the last newline (sam_file_pieces) through simmr_correval_truth_add; behind the plan the reads go up
+// in pieces cut at a record's end: the host counts the piece's newlines and cuts behind the last one whose number is a multiple of the
+// record's lines.  Nothing is written unless all of it succeeded.
+struct CorrevalHandle {
+  simmr_correval* h = nullptr;
+  ~CorrevalHandle() { simmr_correval_destroy(h); }
+};
+static int record_file_pieces(const std::string& flag, const std::string& path, uint32_t lines_per_record, const std::function<int(const uint8_t*, size_t)>& add) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return die(flag + ": cannot open " + path);
+  struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
+  GrowBuf dev;
+  std::vector<uint8_t> piece;
+  size_t have = 0;  // bytes of `piece` read and not yet added: the open last record of the piece before
+  for (bool eof = false; !eof;) {
+    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
+    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
+    if (got < SAM_PIECE) {
+      if (ferror(f)) return die(flag + ": cannot read " + path);
+      eof = true;
+    }
+    have += got;
+    size_t cut = have;  // at the end of the file the last line may lack its newline
+    if (!eof) {
+      size_t lines = 0;
+      cut = 0;
+      for (size_t i = 0; i < have; i++)
+        if (piece[i] == '\n' && ++lines % lines_per_record == 0) cut = i + 1;
+      if (cut == 0) continue;  // one record longer than the piece: read on
+    }
+    if (cut > SIMMR_FIT_SAM_MAX_BYTES) return die(flag + ": a record of " + path + " is longer than one add takes");
+    if (cut > 0) {
+      uint8_t* d = dev.room(cut);
+      if (!d) return die(flag + ": device allocation failed");
+      if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die(flag + ": copy to the device failed");
+      if (int rc = add(d, cut)) return rc;
+    }
+    memmove(piece.data(), piece.data() + cut, have - cut);
+    have -= cut;
+  }
+  return 0;
+}
+static int run_eval_corrected(const CliArgs& args) {
+  for (const std::string* path : {&args.eval_corrected_truth, &args.eval_corrected}) {  // (the files are looked at before an engine is made)
+    FILE* f = fopen(path->c_str(), "rb");
+    if (!f) return die(std::string(path == &args.eval_corrected ? "--eval-corrected" : "--eval-corrected-truth") + ": cannot open " + *path);
+    fclose(f);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  CorrevalHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_correval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
+  const uint32_t lpr = args.eval_corrected_fasta ? 2u : 4u;
+  const simmr_correval_config cfg{lpr, 0u};
+  if (simmr_correval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
+  float ms = 0;
+  info("Parsing " + args.eval_corrected_truth);
+  if (int rc = sam_file_pieces("--eval-corrected-truth", args.eval_corrected_truth, [&](const uint8_t* d, size_t n) {
+        if (simmr_correval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_correval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
+          return die(std::string("--eval-corrected-truth: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  uint64_t n_entries = 0;
+  if (simmr_correval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-corrected-truth: ") + simmr_last_error(eng));
+  info("Parsing " + args.eval_corrected);
+  if (int rc = record_file_pieces("--eval-corrected", args.eval_corrected, lpr, [&](const uint8_t* d, size_t n) {
+        if (simmr_correval_add(ev.h, d, n) != SIMMR_OK || simmr_last_correval_ms(ev.h, &ms) != SIMMR_OK)
+          return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
+        return 0;
+      }))
+    return rc;
+  simmr_correval_counts c{};
+  static_assert(sizeof(c) == CORREVAL_N_COUNTS * sizeof(uint64_t), "the report names every count");
+  static_assert(CORREVAL_N_QUALS == SIMMR_CORREVAL_QUALS && CORREVAL_N_POS == SIMMR_CORREVAL_POS, "the report's rows are the tables'");
+  std::vector<uint64_t> cube(125), by_qual(CORREVAL_N_QUALS * 5), by_pos(CORREVAL_N_POS * 5);
+  if (simmr_correval_read(ev.h, &c, cube.data(), by_qual.data(), by_pos.data()) != SIMMR_OK) return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
+  std::string rows;
+  if (!args.eval_corrected_reads.empty()) {
+    GrowBuf d_key, d_cols;
+    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
+    uint8_t* k = d_key.room(n1 * 8);
+    uint32_t* u = (uint32_t*)d_cols.room(n1 * 16);
+    if (!k || !u) return die("--eval-corrected-reads: device allocation failed");
+    if (simmr_correval_emit(ev.h, (uint64_t*)k, u, u + n1, u + 2 * n1, u + 3 * n1, n_entries) != SIMMR_OK)
+      return die(std::string("--eval-corrected-reads: ") + simmr_last_error(eng));
+    std::vector<uint64_t> key(n1);
+    std::vector<uint32_t> cols(4 * n1);
+    if (hipMemcpy(key.data(), k, n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cols.data(), u, n1 * 16, hipMemcpyDeviceToHost) != hipSuccess)
+      return die("--eval-corrected-reads: copy from the device failed");
+    rows = correval_read_rows(key.data(), cols.data(), cols.data() + n1, cols.data() + 2 * n1, cols.data() + 3 * n1, n_entries);
+  }
+  std::string err;
+  OutFile report(args.eval_corrected_report, false);
+  report.append(correval_report((const uint64_t*)&c, cube.data(), by_qual.data(), by_pos.data()));
+  if (!report.close(&err)) return die("--eval-corrected-report: " + err);
+  if (!args.eval_corrected_reads.empty()) {
+    OutFile reads(args.eval_corrected_reads, false);
+    reads.append(rows);
+    if (!reads.close(&err)) return die("--eval-corrected-reads: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_entries) + " reads (" + n(c.truth_skipped) + " records skipped)");
+  info("Corrected: " + n(c.records) + " records, " + n(c.unknown_read) + " of unknown reads, " + n(c.trimmed_records) + " trimmed, " + n(c.longer_records) + " longer");
+  info("Bases: " + n(c.kept) + " kept, " + n(c.damaged) + " damaged, " + n(c.fixed) + " fixed, " + n(c.left) + " left, " + n(c.miscorrected) + " miscorrected, " +
+       n(c.trimmed_error) + " errors trimmed away");
+  info("Reads: " + n(c.fixed_all) + " fixed, " + n(c.improved) + " improved, " + n(c.unchanged) + " unchanged, " + n(c.worse) + " worse, " + n(c.clean_damaged) +
+       " clean ones damaged, " + n(c.missing) + " without a record");
+  info("Wrote " + args.eval_corrected_report);
+  return 0;
+}
+
 static int run_main(int argc, char** argv) {
   CliArgs args;
   std::string err;
@@ -1739,6 +1854,7 @@ static int run_main(int argc, char** argv) {
   if (!args.eval_classified.empty()) return run_eval_classified(args);
   if (!args.eval_assembly.empty()) return run_eval_assembly(args);
   if (!args.eval_bins.empty()) return run_eval_bins(args);
+  if (!args.eval_corrected.empty()) return run_eval_corrected(args);
 
   SideOutputs side(args);
   if (side.refuse_devices()) return die(side.err);

@@ -242,6 +242,21 @@ std::string asmeval_report(const uint64_t* counts, uint32_t k, const std::vector
 // top_genome, top_kmers, and the genome's name (genomes: sorted, the row is its index), "." where the contig has no vote.
 std::string asmeval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const uint64_t* length, const uint32_t* kmers,
                                 const uint32_t* found, const uint32_t* shared, const uint32_t* top_genome, const uint32_t* top_kmers, size_t n);
+// ---- --eval-corrected: the report and the reads file ----
+// num / den to six decimals from the integers alone (millionths, rounded half up; '-' in front where `negative` and the result is
+// not zero); "NA" where den is 0.
+std::string correval_ratio(bool negative, uint64_t num, uint64_t den);
+// The file of --eval-corrected-report: the counts of struct simmr_correval_counts as "#name\tvalue" lines in the struct's order
+// (counts[CORREVAL_N_COUNTS]); "#gain" = (fixed - damaged) / (fixed + left + miscorrected + trimmed_error), "#sensitivity" = fixed / the
+// same denominator and "#specificity" = kept / (kept + damaged), each as the exact fraction and correval_ratio; a header line and a Q
+// row per quality that has a compared base (quality, kept, damaged, fixed, left, miscorrected: by_qual[q * 5 ..]); the same as P rows
+// per position (by_pos); a header line and the cube's 25 C rows: the true base, the original base, and the corrected bases A C G T N
+// (cube[(t * 5 + o) * 5 + c]).
+constexpr size_t CORREVAL_N_COUNTS = 29, CORREVAL_N_QUALS = 95, CORREVAL_N_POS = 512;
+std::string correval_report(const uint64_t* counts, const uint64_t* cube, const uint64_t* by_qual, const uint64_t* by_pos);
+// The rows of --eval-corrected-reads for n truth entries in key order: id, mate bit, length, before, residual ('.' without a record)
+// and records of every entry that has no record with residual 0, tab-separated.
+std::string correval_read_rows(const uint64_t* key, const uint32_t* length, const uint32_t* before, const uint32_t* residual, const uint32_t* hits, size_t n);
 // ---- --eval-bins: the host's share (the names of both texts, the report with its fractions, the two files) ----
 constexpr size_t BINEVAL_N_COUNTS = 21, BINEVAL_GENOME_COLS = 7;
 // The record lines of the truth text[0, n), which begins at a line's start (empty lines and lines that begin with '#' are none; a
@@ -589,6 +604,11 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string eval_assembly_report;   // --eval-assembly-report FILE: the counts, completeness per genome and overall, the QV, the contiguity of both sides
   std::string eval_assembly_contigs;  // --eval-assembly-contigs FILE: a row per contig
   uint32_t eval_assembly_k = 31;      // --eval-assembly-k K: odd, 15 .. 31
+  std::string eval_corrected;         // --eval-corrected FILE: no simulation; a corrector's FASTQ scored against --eval-corrected-truth (simmr_correval_*)
+  std::string eval_corrected_truth;   // --eval-corrected-truth FILE: the file of --sam
+  std::string eval_corrected_report;  // --eval-corrected-report FILE: the counts, gain, sensitivity, specificity, the rows by quality and position, the cube
+  std::string eval_corrected_reads;   // --eval-corrected-reads FILE: a row per read that is not its true self
+  bool eval_corrected_fasta = false;  // --eval-corrected-fasta: two-line FASTA records
   std::string eval_bins;              // --eval-bins FILE: no simulation; a binner's contig<TAB>bin text scored against --eval-bins-truth (simmr_bineval_*)
   std::string eval_bins_truth;        // --eval-bins-truth FILE: the file of --eval-assembly-contigs
   std::string eval_bins_report;       // --eval-bins-report FILE: the counts, purity, completeness, F1, ARI, a row per genome and per bin
