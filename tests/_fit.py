@@ -7,6 +7,8 @@ bin builders — and the one documented departure, the point mass where the band
 oracle's reads and the host genome bytes (tests/_stats.flat_reads: the expected-byte model of tests/_truth.py).  Nothing
 here comes from the code under test."""
 import math
+import re
+from pathlib import Path
 
 import numpy as np
 
@@ -14,6 +16,14 @@ from tests import _stats
 
 QUALS, DENSITIES, MAX_L, MAX_INSERT = 94, 71, 65535, 5000
 ACGT = b"ACGT"
+CONSTANTS = ("FIT_LANES", "FIT_WG_READS", "FIT_FLUSH_BATCHES", "FIT_LDS_POS", "FIT_LDS_LEN", "FIT_LDS_K", "FIT_MAX_PROBE", "FIT_MAX_L")
+
+
+def constants():
+    """{name: value} of CONSTANTS as fit_device.hpp states them: what tests/_fit_cases.py and tests/test_gpu_fit_seams.py size
+    their cases from"""
+    src = (Path(__file__).resolve().parent.parent / "simmr_amd" / "csrc" / "fit_device.hpp").read_text()
+    return {n: int(re.search(rf"#define {n} (\d+)u\b", src).group(1)) for n in CONSTANTS}
 
 
 def encode3(kmer: bytes):

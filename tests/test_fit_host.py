@@ -223,3 +223,85 @@ def test_cli_serialiser_writes_model_io_s_bytes(tmp_path):
         answer = C.string_at(ptr).decode()
         lib.simmr_host_free(ptr)
         assert answer == "OK" and path.read_bytes() == model_io.serialize_fitted(variant)
+
+
+# ---- the cases of tests/test_gpu_fit_seams.py land where their builders say -----------------------------------------------------
+def changed_and_all(k, host, r, oracle, genomes):
+    """(windows, changed windows, distinct changed pairs) of read r by the plain rule on its two rows"""
+    from tests import _fit_cases, _stats
+    one = _fit_cases.rows(host, r, r + 1)
+    _, _, _, _, have, want, _ = _stats.flat_reads(oracle, one, genomes)
+    counts = _fit.kmerize_alignment(k, bytes(want.tolist()), bytes(have.tolist()))
+    changed = {key: c for key, c in counts.items() if key[0] != key[1]}
+    return sum(counts.values()) // 2, sum(changed.values()), len(changed)
+
+
+def test_constants_parse():
+    c = _fit.constants()
+    assert list(c) == list(_fit.CONSTANTS) and all(isinstance(v, int) and v > 0 for v in c.values())
+    assert c["FIT_LANES"] == 16 and c["FIT_MAX_L"] == _fit.MAX_L and c["FIT_WG_READS"] * c["FIT_LANES"] == 512
+    assert c["FIT_LDS_K"] in range(3, 10) and c["FIT_MAX_PROBE"] & (c["FIT_MAX_PROBE"] - 1) == 0
+
+
+def test_uniform_batches_scale_the_model_of_one_batch(oracle):
+    """the scaled model of the flush case is tests/_fit.model of the same reads laid out in full, table for table"""
+    from tests import _fit_cases as cases
+    genomes = cases.host_genomes()
+    for n_batches in (1, 3):
+        u = cases.uniform_batches(oracle, genomes, n_batches)
+        assert u.n_reads == cases.WG_READS * n_batches == len(u.host["start"])
+        assert np.array_equal(u.host["seq"][:cases.WG_READS * cases.UNIFORM_L], u.host["seq"][-cases.WG_READS * cases.UNIFORM_L:])
+        want = _fit.model(oracle, [u.host], genomes, 2, cases.QUAL_OFFSET, cases.UNIFORM_K, 20)
+        assert set(want) == set(u.model)
+        for name in want:
+            assert np.array_equal(np.asarray(u.model[name]), np.asarray(want[name])), (name, n_batches)
+            assert np.asarray(u.model[name]).dtype == np.asarray(want[name]).dtype, name
+        _fit.assert_model(u.model, want, "uniform batches")
+        assert want["length_hist"][cases.UNIFORM_L] == u.n_reads == want["insert_hist"][cases.UNIFORM_SPAN]
+        assert (want["pair_alt"] != np.repeat(want["kmer_ref"], np.diff(want["kmer_first"].astype(np.int64)))).sum() > 8  # changed pairs
+        assert (want["pair_alt"] >> np.uint32(3 * (cases.UNIFORM_K - 1))).max() == 4                                      # the written N
+
+
+@pytest.mark.parametrize("k", [3, 7, 8, 10])
+def test_seam_rows_land_on_both_sides_of_every_seam(oracle, k):
+    from tests import _fit_cases as cases
+    genomes = cases.host_genomes()
+    case = cases.seam_rows(k)
+    host = cases.reads_of(oracle, genomes, case.specs, np.random.default_rng(k))
+    assert len(case.notes) == len(case.specs) == 3 * 2 * (2 * k + 1 + k + 3)
+    for r, (spec, note) in enumerate(zip(case.specs, case.notes)):
+        windows, changed, _ = changed_and_all(k, host, r, oracle, genomes)
+        assert (windows, changed) == (note.windows, note.changed), (r, spec[:5])
+    for E in cases.EDGES:
+        at = sorted(p for n in case.notes if n.E == E and len(n.at) == 1 for p in n.at)
+        assert at == sorted(2 * list(range(E - k, E + k)))
+        sides = {cases.place(p)[:2] for p in at}
+        assert sides == {cases.place(E - 1)[:2], cases.place(E)[:2]} and len(sides) == 2
+        lengths = sorted(s[3] for s, n in zip(case.specs, case.notes) if n.E == E and not n.at)
+        assert lengths == sorted(2 * list(range(E - 1, E + k + 2)))
+    m = _fit.model(oracle, [host], genomes, 1, cases.QUAL_OFFSET, k, 20)
+    assert len(m["pair_alt"]) > len(m["kmer_ref"]) and len(m["qual_hist"]) == case.n_positions
+    assert [int(m["length_hist"][v]) for v in (255, 256, 257, 258)] == [2, 2, 2, 2]
+
+
+def test_insert_pairs_and_full_table_land(oracle):
+    from tests import _fit_cases as cases
+    genomes = cases.host_genomes()
+    case = cases.insert_pairs()
+    host = cases.reads_of(oracle, genomes, case.specs, np.random.default_rng(1))
+    assert sorted(_fit.insert_sizes(host, 2)) == case.kept and len(case.kept) == 2 * sum(s <= 5000 for s in case.spans)
+    assert {1, 1023, 1024, 1025, 4999, 5000, 5001} <= set(case.spans) and max(case.spans) > 100_000
+    assert any(a[4] != b[4] for a, b in zip(case.specs[0::2], case.specs[1::2])) and any(b[2] < a[2] for a, b in zip(case.specs[0::2], case.specs[1::2]))
+    for D in (1, 2, 3, 8, 9, 257):
+        t = cases.full_table(D)
+        host = cases.reads_of(oracle, genomes, t.specs, np.random.default_rng(2))
+        _, _, _, j, have, want, _ = _stats_flat(oracle, host, genomes)
+        counts = _fit.kmerize_flat(t.k, have, want, j, np.full(j.size, t.k + 1))
+        changed = {key: c for key, c in counts.items() if key[0] != key[1]}
+        assert len(changed) == D == t.distinct and sorted(changed.values()) == sorted(t.times) and len({key[0] for key in counts}) == 1
+        assert all(a >> (3 * (t.k - 1)) < 4 for _, a in changed)  # ACGT k-mers
+
+
+def _stats_flat(oracle, host, genomes):
+    from tests import _stats
+    return _stats.flat_reads(oracle, host, genomes)

@@ -9,7 +9,7 @@ import pytest
 
 from simmr_amd import (CustomShortErrorProfile, MinimalLongErrorProfile, MinimalShortErrorProfile, PerfectShortErrorProfile,
                        SimmrError, _abi)
-from tests import _fit, _model, _oracle, _synth, _truth
+from tests import _fit, _fit_cases, _model, _oracle
 from tests._hand_built import hand_built
 from tests.test_gpu_parity import assert_same
 
@@ -22,17 +22,8 @@ COLS = ("seq_off", "start", "end", "contig", "flags", "qual", "seq")
 @pytest.fixture(scope="module")
 def genomes(engine):
     # (the genomes of tests/test_gpu_truth.py)
-    rng = np.random.default_rng(21)
-    seq = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, 30000)].copy()
-    seq[rng.integers(0, 30000, 3000)] = ord("N")
-    seq[rng.integers(0, 30000, 500)] = ord("-")
-    seq[12_000:12_400] = ord("N")
-    g = {0: _oracle.HostGenome(_synth.synthetic_contigs([1_000_000], 1)),
-         1: _oracle.HostGenome(_synth.synthetic_contigs([300_000, 90_001, 30_017, 70_000, 123_457], 7)),
-         3: _oracle.HostGenome([seq])}
-    engine.stage_synthetic(0, [1_000_000], 1)
-    engine.stage_genome(1, g[1].contigs)
-    engine.stage_genome(3, g[3].contigs)
+    g = _fit_cases.host_genomes()
+    _fit_cases.stage(engine, g)
     return g
 
 
@@ -64,10 +55,7 @@ def window_reads(oracle, genomes, device, layout, k, max_alt):
     """Reads copied from genome 1 contig 0 with chosen bytes altered: lengths k - 1, k, k + 1 and 2 k (0, 0, 1 and k windows),
     a written N (one, and k of them), alternates with equal counts, and more than max_alt alternates of one reference k-mer
     with a tie across the cut; and reads over the N / '-' runs of genome 3 (an expected N inside and at the edge of a window)."""
-    import torch
-    from simmr_amd.engine import Reads
-    comp = _truth.complement_lut(oracle)
-    specs = []  # genome, contig, lo, L, rev, {offset: byte}
+    specs = []  # genome, contig, lo, L, rev, {offset: byte}: tests/_fit_cases.py builds the columns
     for i, L in enumerate((k - 1, k, k + 1, 2 * k)):
         for rev in (0, 1):
             specs.append((1, 0, 500 + 40 * i, L, rev, {}))
@@ -89,46 +77,8 @@ def window_reads(oracle, genomes, device, layout, k, max_alt):
     for lo in (11_990, 11_995, 12_000 - k, 12_395, 12_400 - 1, 100, 731):      # the N run of genome 3: its edges inside windows
         for rev in (0, 1):
             specs.append((3, 0, lo, 4 * k, rev, {}))
-    seqs, quals = [], []
-    rng = np.random.default_rng(k)
-    for g, c, lo, L, rev, alter in specs:
-        want = genomes[g].contigs[c][lo:lo + L].copy()
-        assert want.size == L
-        if rev:
-            want = comp[want[::-1]]
-        for j, ch in alter.items():
-            want[j] = ord(ch)
-        seqs.append(want)
-        quals.append((33 + rng.integers(0, 61, L)).astype(np.uint8))
-    n = len(specs)
-    L = np.array([s[3] for s in specs], dtype=np.int64)
-    lo = np.array([s[2] for s in specs], dtype=np.int64)
-    rev = np.array([s[4] for s in specs], dtype=np.uint8)
-    cols = {"start": np.where(rev == 1, lo + L, lo).astype(np.uint64), "end": np.where(rev == 1, lo, lo + L).astype(np.uint64),
-            "contig": np.array([s[1] for s in specs], dtype=np.uint32), "genome": np.array([s[0] for s in specs], dtype=np.uint32),
-            "flags": rev.copy(), "read_id": np.arange(n, dtype=np.uint32)}
-    off = np.zeros(n + 1, dtype=np.uint64)
-    np.cumsum(L, out=off[1:])
-    host = dict(cols, seq=np.concatenate(seqs), qual=np.concatenate(quals), seq_off=off)
-    if layout == 16:
-        slot = (L + 15) // 16 * 16
-        first = np.zeros(n + 1, dtype=np.int64)
-        np.cumsum(slot, out=first[1:])
-        total = int(first[n])
-        seq, qual = np.zeros(total, dtype=np.uint8), np.zeros(total, dtype=np.uint8)
-        seq_off = first.copy()
-        seq_off[:n] += np.where(rev == 1, slot - L, 0)
-        for r in range(n):
-            seq[seq_off[r]:seq_off[r] + L[r]] = seqs[r]
-            qual[first[r]:first[r] + L[r]] = quals[r]
-    else:
-        seq, qual, seq_off, total = host["seq"], host["qual"], off.astype(np.int64), int(off[n])
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(device)
-    dev = Reads(seq=t(seq, np.uint8), qual=t(qual, np.uint8), seq_off=t(seq_off, np.int64), start=t(cols["start"], np.int64),
-                end=t(cols["end"], np.int64), contig=t(cols["contig"], np.int32), genome=t(cols["genome"], np.int32),
-                read_id=t(cols["read_id"], np.int32), flags=t(cols["flags"], np.uint8), n_reads=n, total_bases=total,
-                qual_offset=33, slot_bytes=layout)
-    return dev, host
+    host = _fit_cases.reads_of(oracle, genomes, specs, np.random.default_rng(k))
+    return _fit_cases.device_reads(host, layout, device), host
 
 
 @pytest.mark.parametrize("k", [3, 7, 10])
