@@ -3,17 +3,29 @@
 Same expected-byte model as tests/_truth.py: the expected byte at offset j of read r is the genome's byte at lo + j, or the
 complement of the byte at lo + L - 1 - j for a reverse-complemented read; an edit is an offset whose byte differs.  Every
 table is a count over the flat list of (read, offset) pairs.  Nothing here comes from the code under test."""
+import re
+from pathlib import Path
+
 import numpy as np
 
 from simmr_amd import _abi
 from tests import _truth
 
 CYCLES, NM_BINS = 512, 64
+CONSTANTS = ("STATS_LANES", "STATS_WG_READS", "STATS_WGS_PER_CU", "STATS_FLUSH_BATCHES", "STATS_MAX_L", "STATS_CYC_STRIDE")
 SHAPES = {"reads": (2,), "bases": (2,), "qual_n": (256,), "qual_mismatch": (256,), "pair": (5, 5), "nm_hist": (NM_BINS,),
           "gc_hist": (101,), "cycle_n": (2, CYCLES), "cycle_qsum": (2, CYCLES), "cycle_mismatch": (2, CYCLES),
           "cycle_base": (2, CYCLES, 5)}
 CLASS = np.full(256, 4, dtype=np.int64)
 CLASS[list(b"ACGT")] = [0, 1, 2, 3]
+
+
+def constants():
+    """{name: value} of CONSTANTS as stats_kernels.hip states them: what tests/_stats_cases.py and tests/test_gpu_stats_seams.py size
+    their cases from"""
+    src = (Path(__file__).resolve().parent.parent / "simmr_amd" / "csrc" / "stats_kernels.hip").read_text()
+    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(STATS_\w+)\s+(\d+)u?\b", src, re.M)}
+    return {n: defines[n] for n in CONSTANTS}
 
 
 def zeros():

@@ -3,8 +3,6 @@ numpy restatement of the header's tables (tests/_stats.py), applied to the ORACL
 device reads are first shown to be the oracle's, so nothing expected here comes from the pass under test.  Every comparison
 is exact."""
 import ctypes as C
-import re
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -16,7 +14,6 @@ from tests._hand_built import hand_built
 from tests.test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 RNG_MODES = [_abi.RNG_REFERENCE, _abi.RNG_PHILOX, _abi.RNG_PHILOX_FULL]
 RNG_IDS = ["reference", "philox", "philox-full"]
 COLS = ("seq_off", "start", "end", "contig", "flags", "qual", "seq")
@@ -170,8 +167,7 @@ def test_hand_built_columns(engine, oracle, genomes, layout, n_sets):
 # ---- 7 ----------------------------------------------------------------------------------------------------------------
 def test_workgroups_loop(engine, oracle, genomes):
     import torch
-    k = (ROOT / "simmr_amd" / "csrc" / "stats_kernels.hip").read_text()
-    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^#define\s+(STATS_\w+)\s+(\d+)u?\b", k, re.M)}
+    defines = _stats.constants()
     wg_reads, per_cu = defines["STATS_WG_READS"], defines["STATS_WGS_PER_CU"]
     assert defines["STATS_LANES"] * wg_reads == 256
     grid_cap = per_cu * int(torch.cuda.get_device_properties(0).multi_processor_count)
