@@ -1777,6 +1777,129 @@ int simmr_asmeval_contigs(simmr_asmeval* h, uint64_t* length_dev, uint32_t* kmer
  * waits inside simmr_asmeval_add lie inside that span.  *plan_sort_ms (may be NULL) = the sort's share of the last plan. */
 int simmr_last_asmeval_ms(simmr_asmeval* h, float* ms, float* plan_sort_ms);
 
+/* ---- an assembler's contigs PLACED on the gold-standard assembly: anchors, collinear blocks and the breakpoints between them -----
+ * Replaces nothing in the reference.  simmr_asmeval_* is alignment-free and cannot tell a correct contig from a chimera of two
+ * genomes; this object gives every k-mer of the truth its POSITION, so that a contig falls into collinear blocks on the truth
+ * records and the places where the blocks change are the misassemblies (metaQUAST's classes, and the blocks NA50 / NGA50 are
+ * computed from).  All of it is integer arithmetic.  No simulation, no genome: like simmr_asmeval_*.
+ *
+ * Text, bases, k-mers, keys, genome names, malformed texts: the rules of simmr_asmeval_* above, word for word, with
+ * SIMMR_ASMEVAL_MAX_BYTES a call.
+ *
+ * Truth side.  A truth record's row t is its ordinal among the truth records since the reset, in add order and then text order;
+ * its genome row is as in asmeval.  Every k-mer occurrence carries its key, t, p (the position of its first base in the record,
+ * counting every base position, invalid ones included) and o (1 where the key is the reverse complement's value, else 0).
+ * simmr_asmmap_truth_plan sorts the occurrences by key over 2k bits and keeps as ANCHORS the keys that occur exactly once in the
+ * whole truth; a key with two occurrences or more, in one genome or several, anchors nothing: it is a REPEAT.  The anchor index is
+ * (key, t, p, o) in ascending key order behind asmeval's prefix table (min(24, bit length of the entries) of the key's top
+ * bits); the distinct repeat keys stand in a second index of the same kind, searched only where the first misses, so that a
+ * repeat is told from a k-mer the truth does not hold.  The plan empties the candidate side and synchronises.
+ *
+ * Candidate side.  A contig's row c is defined as in asmeval.  A k-mer of a contig has its first base at q (in the record, as p)
+ * and its orientation bit oc.  A hit on an anchor key is an ANCHOR HIT with relative strand s = oc ^ o and the diagonal d, a signed
+ * 64-bit number: d = p - q where s = 0, d = p + q where s = 1.  The hits of an add are compacted in (contig, q) order by a count
+ * pass, a scan and a write pass, never appended by atomics: their order is the data.
+ * Runs.  In that order a hit starts a new run where it is the first hit of its contig, where its t or its s differs from the
+ * previous hit's, or where |d - d_prev| > band.  A run with fewer than min_anchors hits is STRAY: it is dropped and its hits count
+ * in stray_hits.
+ * Blocks.  Over the kept runs of a contig, in order, a run starts a new block where it is the contig's first kept run, where its
+ * t or s differs from the previous kept run's, or where |d_first - d_last of the previous kept run| > band.  That is ONE merge
+ * round: a dropped run between two runs on one diagonal does not break them.  Nine columns a block: contig, truth_record, strand,
+ * q_start (the first hit's q), q_end (the last hit's q + k), p_start (the smallest p), p_end (the largest p + k), hits, join.
+ * Blocks stand in (contig, q) order.
+ * Breakpoints.  join of a contig's first block is 0; of every further block it is the class of the step from the block before it,
+ * the first that applies: SIMMR_ASMMAP_INTER_GENOME (the two truth records belong to different genomes), _INTER_RECORD (one genome,
+ * another truth record; the gold assembly's records are covered regions, so this also marks a contig that bridges a coverage
+ * gap), _INVERSION (one record, the other strand), _RELOCATION (one record and strand, |dd| > relocation), _LOCAL (one record and
+ * strand, band < |dd| <= relocation); dd is taken between the last hit of the earlier block and the first hit of the later one.
+ *
+ * Tables (simmr_asmmap_read; every entry an integer sum or maximum).  The counts below.  truth_repeats are the distinct repeat
+ * keys; repeat_hits the candidate k-mers that found one; block_bases the sum of q_end - q_start.  The contig classes are exclusive
+ * and sum to records: contigs_unplaced (no block), contigs_clean (one block), contigs_local_only (two blocks or more, every join
+ * local), contigs_misassembled (any other join); misassembled_bases are the lengths of the last.
+ * by_genome[n_genomes][SIMMR_ASMMAP_GENOME_COLS]: truth_bases, truth_anchors, and by the genome of the block's truth record
+ * blocks, block_bases, longest_block (a maximum).
+ * Contig columns (simmr_asmmap_contigs): length (u64), hits, blocks, first_block (the row of its first block, 0xffffffff: none),
+ * block_bases (u64), worst_join (the smallest non-zero join class among its blocks, 0: none).
+ * Invariances.  Every count, by_genome, the contig columns other than first_block and the multiset of (contig, truth_record, hits,
+ * q_end - q_start, p_start, p_end) of the blocks are the same for any launch geometry, for any cut of either text into adds at
+ * record boundaries, and when any contig is replaced by its reverse complement: the run rule and the block rule are symmetric in
+ * their two neighbours, and d only shifts by the constant L - k under the reversal of a contig of L bases.
+ * Limits: a record shorter than 2^32 bases, fewer than 2^31 k-mer occurrences and fewer than 2^31 truth records (SIMMR_ERANGE). */
+#define SIMMR_ASMMAP_GENOME_COLS 5u   /* by_genome: truth_bases, truth_anchors, blocks, block_bases, longest_block */
+#define SIMMR_ASMMAP_BLOCK_COLS 9u    /* contig, truth_record, strand, q_start, q_end, p_start, p_end, hits, join */
+#define SIMMR_ASMMAP_INTER_GENOME 1u
+#define SIMMR_ASMMAP_INTER_RECORD 2u
+#define SIMMR_ASMMAP_INVERSION 3u
+#define SIMMR_ASMMAP_RELOCATION 4u
+#define SIMMR_ASMMAP_LOCAL 5u
+
+typedef struct simmr_asmmap simmr_asmmap;
+
+typedef struct simmr_asmmap_config {   /* HOST memory */
+  uint32_t n_genomes;
+  uint32_t k;                          /* odd, 15 .. 31 */
+  uint32_t band;                       /* two neighbours lie on one diagonal where their d differ by at most this (64 through Python and the CLI) */
+  uint32_t relocation;                 /* a step of more than this is a relocation (1000: QUAST's extensive misassembly); below 2^31 */
+  uint32_t min_anchors;                /* a run of fewer hits is stray (16); at least 1 */
+  const char* const* genome;           /* n_genomes genome names, NUL-terminated, in any order */
+} simmr_asmmap_config;
+
+typedef struct simmr_asmmap_counts {   /* HOST; every entry an integer sum, in this order */
+  uint64_t truth_records, truth_bases, truth_invalid, truth_kmers;   /* cumulative since the reset; kmers = occurrences */
+  uint64_t truth_anchors, truth_repeats;                             /* of the plan in force */
+  uint64_t records, bases, invalid, kmers, hits, stray_hits, repeat_hits;   /* the candidate side, since the last truth plan */
+  uint64_t runs, runs_dropped, blocks, block_bases;
+  uint64_t breaks_inter_genome, breaks_inter_record, breaks_inversion, breaks_relocation, breaks_local;
+  uint64_t contigs_unplaced, contigs_clean, contigs_local_only, contigs_misassembled;
+  uint64_t misassembled_bases;
+} simmr_asmmap_counts;
+
+/* The state is an object of its own, created on an engine and destroyed BEFORE the engine (as simmr_asmeval_create); its calls
+ * run on the engine's stream and leave their messages with the engine (simmr_last_error).  simmr_asmmap_create reads the
+ * environment variable SIMMR_ASMMAP_MAX_WGS once: a positive number caps the workgroups of every launch of the k_amap_* kernels of
+ * this object (not of the text-to-planes stage it shares with asmeval).  It is there for tests and measurements of the launch
+ * geometry; no answer depends on it. */
+int simmr_asmmap_create(simmr_engine* e, simmr_asmmap** out);
+void simmr_asmmap_destroy(simmr_asmmap* h);
+/* Takes the names, k and the three thresholds, and empties both sides.  Synchronises.  SIMMR_EINVAL: a NULL argument, a name
+ * given twice, a k that is even, below 15 or above 31, band above relocation, min_anchors of 0, relocation of 2^31 or more.
+ * SIMMR_ENOTSUP, SIMMR_ERANGE for the names: as simmr_asmeval_reset. */
+int simmr_asmmap_reset(simmr_asmmap* h, const simmr_asmmap_config* cfg);
+/* Adds the records of text[0 .. n_bytes) (DEVICE memory, which must stay as it is until the stream has run the add) to the
+ * truth.  Only enqueues.  Drops a truth plan.  Room for a k-mer occurrence per byte of text grows with the object.
+ * SIMMR_ESTATE: no reset yet.  SIMMR_EINVAL: a NULL text with n_bytes > 0.  SIMMR_ENOTSUP: n_bytes above SIMMR_ASMEVAL_MAX_BYTES. */
+int simmr_asmmap_truth_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes);
+/* The plan, as stated above.  Synchronises.  *n_anchors (may be NULL) = the anchors.  SIMMR_EINVAL: a malformed truth text.
+ * SIMMR_ERANGE: 2^31 k-mer occurrences or truth records or more since the reset. */
+int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors);
+/* Places the records of text[0 .. n_bytes) (DEVICE, as above) on the plan.  SYNCHRONISES, five times: it needs the add's records
+ * and bases on the host for the contig columns, and then the totals of four scans, each of which sizes what the next stage
+ * writes: the anchor hits, the runs, the kept runs and the blocks.  SIMMR_ESTATE: no truth plan in force.  SIMMR_ERANGE: 2^31
+ * contigs, or 2^32 - 1 blocks, or more since the plan.  SIMMR_EINVAL, SIMMR_ENOTSUP: as simmr_asmmap_truth_add. */
+int simmr_asmmap_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes);
+/* The counts and by_genome_host[n_genomes][SIMMR_ASMMAP_GENOME_COLS] (HOST, either may be NULL).  Synchronises.  The block and
+ * contig sums are made here, by reductions over the block and contig columns.  Without a plan in force (none yet, or dropped by a
+ * truth add) truth_anchors, truth_repeats, every candidate count and every column of by_genome are 0.  SIMMR_EINVAL: a malformed text on either side
+ * since the reset (nothing is written).  SIMMR_ESTATE: no reset yet. */
+int simmr_asmmap_read(simmr_asmmap* h, simmr_asmmap_counts* counts, uint64_t* by_genome_host);
+/* The anchor index in ascending key order, four columns (DEVICE, capacity entries each, any may be NULL): key, t, p, o.
+ * Synchronises.  SIMMR_ESTATE: no truth plan.  SIMMR_ERANGE, nothing written: capacity < the anchors. */
+int simmr_asmmap_anchors(simmr_asmmap* h, uint64_t* key_dev, uint32_t* t_dev, uint32_t* p_dev, uint32_t* o_dev, uint64_t capacity);
+/* The blocks in row order, SIMMR_ASMMAP_BLOCK_COLS columns in the order stated above (DEVICE; cols_dev is a HOST array of nine
+ * device pointers of capacity entries each, any of which may be NULL, or NULL itself).  *n_blocks (may be NULL) = the blocks since
+ * the plan, written whenever a plan is in force: a call with capacity 0 asks for it.  Synchronises.  SIMMR_ESTATE: no truth plan.
+ * SIMMR_ERANGE, no column written: capacity < the blocks. */
+int simmr_asmmap_blocks(simmr_asmmap* h, uint32_t* const* cols_dev, uint64_t capacity, uint64_t* n_blocks);
+/* The contigs in row order, six columns (DEVICE, capacity entries each, any may be NULL); *n_contigs and the errors as
+ * simmr_asmmap_blocks. */
+int simmr_asmmap_contigs(simmr_asmmap* h, uint64_t* length_dev, uint32_t* hits_dev, uint32_t* blocks_dev, uint32_t* first_block_dev, uint64_t* block_bases_dev,
+                         uint32_t* worst_join_dev, uint64_t capacity, uint64_t* n_contigs);
+/* HIP-event time (ms) of the device work since the last reset: the truth adds, the plans and the adds.  Synchronises the stream.
+ * A run of adds with no synchronising call of this object between them (the plan or this call) is timed as one span; the host's
+ * waits inside simmr_asmmap_add lie inside that span. */
+int simmr_last_asmmap_ms(simmr_asmmap* h, float* ms);
+
 /* ---- a binner's contig bins scored against each contig's true genome: two tab-separated texts in HBM, joined by name -----------
  * Replaces nothing in the reference.  `--eval-assembly-contigs` writes, per contig, its name, its length and the genome most of
  * its k-mers vote for; a binner (MetaBAT, CONCOCT, MaxBin, VAMB, DAS Tool) puts the same contigs into bins.  Both texts go in and

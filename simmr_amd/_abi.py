@@ -309,6 +309,26 @@ class AsmevalConfig(C.Structure):
     _fields_ = [("n_genomes", C.c_uint32), ("k", C.c_uint32), ("plain_search", C.c_uint32), ("genome", C.POINTER(C.c_char_p))]
 
 
+ASMMAP_COUNTS = ("truth_records", "truth_bases", "truth_invalid", "truth_kmers", "truth_anchors", "truth_repeats", "records", "bases", "invalid", "kmers",
+                 "hits", "stray_hits", "repeat_hits", "runs", "runs_dropped", "blocks", "block_bases", "breaks_inter_genome", "breaks_inter_record",
+                 "breaks_inversion", "breaks_relocation", "breaks_local", "contigs_unplaced", "contigs_clean", "contigs_local_only", "contigs_misassembled",
+                 "misassembled_bases")
+ASMMAP_GENOME_COLS = ("truth_bases", "truth_anchors", "blocks", "block_bases", "longest_block")  # SIMMR_ASMMAP_GENOME_COLS
+ASMMAP_BLOCK_COLS = ("contig", "truth_record", "strand", "q_start", "q_end", "p_start", "p_end", "hits", "join")  # SIMMR_ASMMAP_BLOCK_COLS
+ASMMAP_JOINS = ("none", "inter_genome", "inter_record", "inversion", "relocation", "local")  # SIMMR_ASMMAP_INTER_GENOME .. _LOCAL are 1 .. 5
+
+
+class AsmmapCounts(C.Structure):
+    """struct simmr_asmmap_counts (host memory)"""
+    _fields_ = [(n, C.c_uint64) for n in ASMMAP_COUNTS]
+
+
+class AsmmapConfig(C.Structure):
+    """struct simmr_asmmap_config (host memory)"""
+    _fields_ = [("n_genomes", C.c_uint32), ("k", C.c_uint32), ("band", C.c_uint32), ("relocation", C.c_uint32), ("min_anchors", C.c_uint32),
+                ("genome", C.POINTER(C.c_char_p))]
+
+
 BINEVAL_COUNTS = ("truth_records", "truth_bases", "truth_none", "records", "unknown_contig", "repeated", "assigned", "assigned_bases", "bins", "cells",
                   "sum_top_bases", "sum_best_bases", "pairs_cells", "pairs_bins", "pairs_genomes", "bins_c90_x5", "bins_c70_x5", "bins_c50_x5",
                   "bins_c90_x10", "bins_c70_x10", "bins_c50_x10")
@@ -511,6 +531,17 @@ SYMBOLS = {
     "simmr_asmeval_emit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "simmr_asmeval_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
     "simmr_last_asmeval_ms": (C.c_int, [C.c_void_p, _P(C.c_float), _P(C.c_float)]),
+    "simmr_asmmap_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
+    "simmr_asmmap_destroy": (None, [C.c_void_p]),
+    "simmr_asmmap_reset": (C.c_int, [C.c_void_p, _P(AsmmapConfig)]),
+    "simmr_asmmap_truth_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_asmmap_truth_plan": (C.c_int, [C.c_void_p, _P(C.c_uint64)]),
+    "simmr_asmmap_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_asmmap_read": (C.c_int, [C.c_void_p, _P(AsmmapCounts), _P(C.c_uint64)]),
+    "simmr_asmmap_anchors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "simmr_asmmap_blocks": (C.c_int, [C.c_void_p, _P(C.c_void_p), C.c_uint64, _P(C.c_uint64)]),
+    "simmr_asmmap_contigs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, _P(C.c_uint64)]),
+    "simmr_last_asmmap_ms": (C.c_int, [C.c_void_p, _P(C.c_float)]),
     "simmr_correval_create": (C.c_int, [C.c_void_p, _P(C.c_void_p)]),
     "simmr_correval_destroy": (None, [C.c_void_p]),
     "simmr_correval_reset": (C.c_int, [C.c_void_p, _P(CorrevalConfig)]),

@@ -26,6 +26,7 @@
 
 #include "host_support.hpp"
 #include "asmeval_kernels.hip"
+#include "asmeval_front.hpp"
 #include "sam_names.hpp"
 
 using namespace simmr;
@@ -48,8 +49,9 @@ struct simmr_asmeval {
   // the names
   DevBuf blob, name_off;
   uint32_t n_genomes = 0, k = 0, plain_search = 0;
-  // the front of one add: the line index, the lines, the planes
-  DevBuf tile_sum, tile_prefix, starts, chunk_sum, chunk_prefix, line_base, rec_start, rec_hdr, tot, code, valid, rec_row;
+  // the front of one add: the line index, the lines, the planes (asmeval_front.hpp)
+  AsmFront front;
+  DevBuf rec_row;
   // the truth: the occurrences as appended, the sort's buffers, the entries
   DevBuf u_key, u_row, key[2], idx[2], hist, digit_total, head, before;
   DevBuf e_key, e_start, e_genome, e_mult, hits, table;
@@ -68,8 +70,8 @@ struct simmr_asmeval {
   float done_ms = 0.f;
 
   MevNames names() const { return MevNames{blob.as<const uint8_t>(), name_off.as<const uint32_t>(), n_genomes}; }
-  AsmLines lines() const { return AsmLines{line_base.as<uint32_t>(), rec_start.as<uint32_t>(), rec_hdr.as<uint32_t>(), tot.as<uint32_t>()}; }
-  AsmPlane plane() const { return AsmPlane{code.as<const uint64_t>(), valid.as<const uint32_t>(), rec_start.as<const uint32_t>(), tot.as<const uint32_t>()}; }
+  AsmLines lines() const { return front.lines(); }
+  AsmPlane plane() const { return front.plane(); }
   AsmContigs contigs() const {
     return AsmContigs{c_len.as<uint64_t>(), c_kmers.as<uint32_t>(), c_found.as<uint32_t>(), c_shared.as<uint32_t>(), c_top.as<unsigned long long>(),
                       c_voted.as<uint32_t>()};
@@ -128,29 +130,10 @@ uint32_t grid_for(simmr_engine* e, uint64_t items, uint32_t per_wg, uint32_t wgs
 // text[0, n_bytes) (n_bytes > 0) to the object's line entries and planes; `truth`: the side whose counts and error bit it feeds
 int enqueue_front(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes, hipStream_t st, bool truth, MevText* W) {
   simmr_engine* e = h->e;
-  const uint64_t n_tiles = (n_bytes + FSAM_TILE - 1) / FSAM_TILE, line_cap = n_bytes / 2 + 1, chunk_cap = line_cap / ASM_CHUNK + 1;
-  const uint64_t word_cap = n_bytes / ASM_WORD + 1;
-  bool room = h->tile_sum.ensure(n_tiles * 8) && h->tile_prefix.ensure((n_tiles + 1) * 8) && h->starts.ensure(line_cap * 4) &&
-              h->chunk_sum.ensure(chunk_cap * 8) && h->chunk_prefix.ensure((chunk_cap + 1) * 8) && h->line_base.ensure((line_cap + 1) * 4) &&
-              h->rec_start.ensure((line_cap + 1) * 4) && h->rec_hdr.ensure(line_cap * 4) && h->tot.ensure(16) && h->code.ensure(word_cap * 8) &&
-              h->valid.ensure(word_cap * 4);
-  if (!room) return eng_fail(e, SIMMR_ENOMEM, "asmeval: allocation failed for %llu bytes of text", (unsigned long long)n_bytes);
-  const uint32_t tile_grid = grid_for(e, n_tiles, 1, 16), line_grid = grid_for(e, chunk_cap, 1, 8), word_grid = grid_for(e, word_cap, ASM_WG, 16);
-  hipLaunchKernelGGL(k_asm_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(), (const uint64_t*)nullptr,
-                     (uint32_t*)nullptr, 0ull);
-  hipLaunchKernelGGL(k_asm_scan, dim3(1), dim3(256), 0, st, h->tile_sum.as<const uint64_t>(), h->tile_prefix.as<uint64_t>(), n_tiles);
-  hipLaunchKernelGGL(k_asm_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(),
-                     h->tile_prefix.as<const uint64_t>(), h->starts.as<uint32_t>(), line_cap);
-  *W = MevText{text, n_bytes, h->tile_prefix.as<const uint64_t>() + n_tiles, h->starts.as<const uint32_t>()};
-  const uint32_t err_bit = truth ? ASM_ERR_TRUTH : ASM_ERR_CAND;
-  hipLaunchKernelGGL(k_asm_lines, dim3(line_grid), dim3(ASM_WG), 0, st, *W, line_cap, h->chunk_sum.as<uint64_t>(), (const uint64_t*)nullptr, h->lines(),
-                     h->word.as<uint32_t>(), err_bit);
-  hipLaunchKernelGGL(k_asm_chunks, dim3(1), dim3(256), 0, st, W->n_lines, line_cap, h->chunk_sum.as<const uint64_t>(), h->chunk_prefix.as<uint64_t>(),
-                     h->lines(), h->counts_p(), (uint32_t)(truth ? AC_T_RECORDS : AC_RECORDS), (uint32_t)(truth ? AC_T_BASES : AC_BASES));
-  hipLaunchKernelGGL(k_asm_lines, dim3(line_grid), dim3(ASM_WG), 0, st, *W, line_cap, h->chunk_sum.as<uint64_t>(), h->chunk_prefix.as<const uint64_t>(),
-                     h->lines(), h->word.as<uint32_t>(), err_bit);
-  hipLaunchKernelGGL(k_asm_pack, dim3(word_grid), dim3(ASM_WG), 0, st, *W, h->lines(), h->code.as<uint64_t>(), h->valid.as<uint32_t>(), h->counts_p(),
-                     (uint32_t)(truth ? AC_T_INVALID : AC_INVALID));
+  if (!h->front.ensure(n_bytes)) return eng_fail(e, SIMMR_ENOMEM, "asmeval: allocation failed for %llu bytes of text", (unsigned long long)n_bytes);
+  const AsmFrontSums sums{h->counts_p(), (uint32_t)(truth ? AC_T_RECORDS : AC_RECORDS), (uint32_t)(truth ? AC_T_BASES : AC_BASES),
+                          (uint32_t)(truth ? AC_T_INVALID : AC_INVALID), h->word.as<uint32_t>(), truth ? ASM_ERR_TRUTH : ASM_ERR_CAND};
+  asm_front_launch(e, st, text, n_bytes, h->front.bufs(), sums, W);
   return SIMMR_OK;
 }
 
@@ -168,6 +151,29 @@ bool grow_zero(DevBuf* b, uint64_t want, uint64_t held, uint32_t width, hipStrea
 }
 
 }  // namespace
+
+namespace simmr {
+
+void asm_front_launch(simmr_engine* e, hipStream_t st, const uint8_t* text, uint64_t n_bytes, const AsmFrontBufs& B, const AsmFrontSums& S, MevText* W) {
+  const uint64_t n_tiles = (n_bytes + FSAM_TILE - 1) / FSAM_TILE, line_cap = n_bytes / 2 + 1, chunk_cap = line_cap / ASM_CHUNK + 1;
+  const uint64_t word_cap = n_bytes / ASM_WORD + 1;
+  const uint32_t tile_grid = grid_for(e, n_tiles, 1, 16), line_grid = grid_for(e, chunk_cap, 1, 8), word_grid = grid_for(e, word_cap, ASM_WG, 16);
+  hipLaunchKernelGGL(k_asm_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, B.tile_sum, (const uint64_t*)nullptr, (uint32_t*)nullptr, 0ull);
+  hipLaunchKernelGGL(k_asm_scan, dim3(1), dim3(256), 0, st, (const uint64_t*)B.tile_sum, B.tile_prefix, n_tiles);
+  hipLaunchKernelGGL(k_asm_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, B.tile_sum, (const uint64_t*)B.tile_prefix, B.starts, line_cap);
+  *W = MevText{text, n_bytes, (const uint64_t*)B.tile_prefix + n_tiles, (const uint32_t*)B.starts};
+  hipLaunchKernelGGL(k_asm_lines, dim3(line_grid), dim3(ASM_WG), 0, st, *W, line_cap, B.chunk_sum, (const uint64_t*)nullptr, B.lines, S.err, S.err_bit);
+  hipLaunchKernelGGL(k_asm_chunks, dim3(1), dim3(256), 0, st, W->n_lines, line_cap, (const uint64_t*)B.chunk_sum, B.chunk_prefix, B.lines, S.counts, S.records_at,
+                     S.bases_at);
+  hipLaunchKernelGGL(k_asm_lines, dim3(line_grid), dim3(ASM_WG), 0, st, *W, line_cap, B.chunk_sum, (const uint64_t*)B.chunk_prefix, B.lines, S.err, S.err_bit);
+  hipLaunchKernelGGL(k_asm_pack, dim3(word_grid), dim3(ASM_WG), 0, st, *W, B.lines, B.code, B.valid, S.counts, S.invalid_at);
+}
+
+void asm_front_genomes(simmr_engine* e, hipStream_t st, const MevText& W, const AsmLines& L, const MevNames& N, uint32_t* rec_row, uint32_t* err) {
+  hipLaunchKernelGGL(k_asm_genomes, dim3(grid_for(e, W.n_bytes / 2 + 1, ASM_WG_RECS, 8)), dim3(ASM_WG), 0, st, W, L, N, rec_row, err);
+}
+
+}  // namespace simmr
 
 extern "C" {
 
@@ -259,8 +265,7 @@ int simmr_asmeval_truth_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_by
   if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
   MevText W;
   if (int rc = enqueue_front(h, text, n_bytes, st, true, &W)) return rc;
-  hipLaunchKernelGGL(k_asm_genomes, dim3(grid_for(e, n_bytes / 2 + 1, ASM_WG_RECS, 8)), dim3(ASM_WG), 0, st, W, h->lines(), h->names(), h->rec_row.as<uint32_t>(),
-                     h->word.as<uint32_t>());
+  asm_front_genomes(e, st, W, h->lines(), h->names(), h->rec_row.as<uint32_t>(), h->word.as<uint32_t>());
   hipLaunchKernelGGL(k_asm_roll_truth, dim3(grid_for(e, n_bytes / ASM_WORD + 1, ASM_WG, 32)), dim3(ASM_WG), 0, st, h->plane(), h->k,
                      h->rec_row.as<const uint32_t>(), h->u_key.as<uint64_t>(), h->u_row.as<uint32_t>(), cap, h->cursor_p());
   return end_span(h, SPAN_ADDS, st, "asmeval truth add");
@@ -345,7 +350,7 @@ int simmr_asmeval_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes) {
   MevText W;
   if (int rc = enqueue_front(h, text, n_bytes, st, false, &W)) return rc;
   uint32_t tot[3] = {0, 0, 0};
-  HIP_TRY(e, hipMemcpyAsync(tot, h->tot.p, 12, hipMemcpyDeviceToHost, st));
+  HIP_TRY(e, hipMemcpyAsync(tot, h->front.tot.p, 12, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "asmeval add")) return rc;
   const uint64_t n_bases = tot[1], n_rec = tot[2], c0 = h->n_contigs, want = c0 + n_rec;
   if (want >= (1ull << 31)) return eng_fail(e, SIMMR_ERANGE, "simmr_asmeval_add takes fewer than 2^31 contigs since the plan (%llu given)", (unsigned long long)want);
@@ -362,7 +367,7 @@ int simmr_asmeval_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes) {
   h->n_contigs = want;
   HIP_TRY(e, hipMemsetAsync(h->cursor_p() + 1, 0, 8, st));
   if (n_rec > 0)
-    hipLaunchKernelGGL(k_asm_contig_len, dim3(grid_for(e, n_rec, 256, 32)), dim3(256), 0, st, h->rec_start.as<const uint32_t>(), (uint32_t)n_rec, c0,
+    hipLaunchKernelGGL(k_asm_contig_len, dim3(grid_for(e, n_rec, 256, 32)), dim3(256), 0, st, h->front.rec_start.as<const uint32_t>(), (uint32_t)n_rec, c0,
                        h->c_len.as<uint64_t>());
   if (n_bases > 0)
     hipLaunchKernelGGL(k_asm_roll_cand, dim3(grid_for(e, n_bases / ASM_WORD + 1, ASM_WG, 32)), dim3(ASM_WG), 0, st, h->plane(), h->k, h->entries(), h->n_genomes,

@@ -143,8 +143,10 @@ SIMMR_DEV uint32_t asm_find(const AsmEntries& E, uint64_t key) {
 
 // THE ROLL.  emit(rec, key) for every k-mer that ends on a base of word w, in position order; rec is the record's ordinal in
 // the add.  n_bases > 32 w.  A base before the add's first record (a malformed text) has no k-mer.
+// asm_roll_at is the walk itself and hands out two things more: the add's position of the k-mer's LAST base, and whether the key
+// is the reverse complement's value (asmmap_kernels.hip places k-mers with them); asm_roll is the same walk without them.
 template <class F>
-SIMMR_DEV void asm_roll(const AsmPlane& P, uint32_t w, uint32_t n_bases, uint32_t n_rec, uint32_t k, F&& emit) {
+SIMMR_DEV void asm_roll_at(const AsmPlane& P, uint32_t w, uint32_t n_bases, uint32_t n_rec, uint32_t k, F&& emit) {
   const uint32_t pos0 = w * ASM_WORD, end = pos0 + ASM_WORD < n_bases ? pos0 + ASM_WORD : n_bases;
   const uint32_t back = pos0 < k - 1u ? pos0 : k - 1u, ps = pos0 - back;
   uint64_t chi = P.code[w], clo = w ? P.code[w - 1u] : 0ull;
@@ -174,10 +176,18 @@ SIMMR_DEV void asm_roll(const AsmPlane& P, uint32_t w, uint32_t n_bases, uint32_
     fwd = ((fwd << 2) | c) & mask;
     rc = (rc >> 2) | ((3ull - c) << top);
     run = ok ? run + 1u : 0u;
-    if (p >= pos0 && run >= k && rec != ASM_NONE) emit(rec, fwd < rc ? fwd : rc);
+    if (p >= pos0 && run >= k && rec != ASM_NONE) emit(rec, fwd < rc ? fwd : rc, p, fwd < rc ? 0u : 1u);
   }
 }
 
+template <class F>
+SIMMR_DEV void asm_roll(const AsmPlane& P, uint32_t w, uint32_t n_bases, uint32_t n_rec, uint32_t k, F&& emit) {
+  asm_roll_at(P, w, n_bases, n_rec, k, [&](uint32_t rec, uint64_t key, uint32_t, uint32_t) { emit(rec, key); });
+}
+
+// The kernels.  asmmap_kernels.hip (a translation unit of its own) includes this file with ASM_ROUTINES_ONLY defined and takes the
+// routines and the structs above without them; the text-to-planes stage reaches it through asmeval_front.hpp.
+#ifndef ASM_ROUTINES_ONLY
 // ---- the line index -----------------------------------------------------------------------------------------------------------
 extern "C" __global__ void __launch_bounds__(FSAM_WG)
 k_asm_index(const uint8_t* __restrict__ text, uint64_t n_bytes, uint64_t n_tiles, uint64_t* __restrict__ tile_sum,
@@ -563,5 +573,7 @@ k_asm_reduce_contigs(AsmContigs C, uint64_t n_contigs, uint32_t n_genomes, unsig
     atomicAdd(counts + at, l_c[threadIdx.x]);
   }
 }
+
+#endif  // ASM_ROUTINES_ONLY
 
 }  // namespace simmr

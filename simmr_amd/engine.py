@@ -523,6 +523,130 @@ class AsmEval:
                 self.engine._mapevals.remove(self)
 
 
+class AsmMap:
+    """An assembler's contigs placed on the gold-standard assembly on the device (simmr_asmmap_*, include/simmr_hip.h states the
+    rules): anchors, collinear blocks and the breakpoints between them.  truth_add() the truth FASTA (the file of --gold-assembly),
+    truth_plan(), add() the contigs, then read(), anchors(), blocks() and contigs().  A text is bytes (copied up) or a contiguous
+    CUDA uint8 tensor and holds whole records; truth_add only enqueues, so every text is kept until a call that synchronises."""
+
+    def __init__(self, engine: "Engine", genomes, k: int = 31, band: int = 64, relocation: int = 1000, min_anchors: int = 16):
+        self.engine, self.lib = engine, engine.lib
+        self._texts = []
+        self.n_anchors = self.n_genomes = 0
+        h = C.c_void_p()
+        engine._check(self.lib.simmr_asmmap_create(engine._h, C.byref(h)))
+        self._h = h
+        try:
+            self.reset(genomes, k, band, relocation, min_anchors)
+        except Exception:
+            self.close()
+            raise
+
+    def _check(self, rc: int):
+        self.engine._check(rc)
+
+    def reset(self, genomes, k: int = 31, band: int = 64, relocation: int = 1000, min_anchors: int = 16):
+        raw = [n if isinstance(n, bytes) else str(n).encode() for n in genomes]
+        arr = (C.c_char_p * max(len(raw), 1))(*raw)
+        cfg = _abi.AsmmapConfig(len(raw), int(k), int(band), int(relocation), int(min_anchors), arr)
+        try:
+            self._check(self.lib.simmr_asmmap_reset(self._h, C.byref(cfg)))
+        finally:
+            self._texts = []  # the reset has synchronised
+        self.n_anchors, self.n_genomes, self.k = 0, len(raw), int(k)
+
+    _text = Mapeval._text
+
+    def truth_add(self, text):
+        p, n = self._text(text)
+        self._check(self.lib.simmr_asmmap_truth_add(self._h, p, n))
+
+    def truth_plan(self) -> int:
+        n = C.c_uint64(0)
+        self.n_anchors = 0
+        try:
+            self._check(self.lib.simmr_asmmap_truth_plan(self._h, C.byref(n)))
+        finally:
+            self._texts = []  # the plan has synchronised
+        self.n_anchors = int(n.value)
+        return self.n_anchors
+
+    def add(self, text):
+        p, n = self._text(text)
+        try:
+            self._check(self.lib.simmr_asmmap_add(self._h, p, n))
+        finally:
+            self._texts = []  # the add has synchronised
+
+    def read(self):
+        """(counts by the names of struct simmr_asmmap_counts, by_genome as an (n_genomes, 5) uint64 array: truth_bases,
+        truth_anchors, blocks, block_bases, longest_block)"""
+        c = _abi.AsmmapCounts()
+        by = np.zeros((self.n_genomes, len(_abi.ASMMAP_GENOME_COLS)), dtype=np.uint64)
+        try:
+            self._check(self.lib.simmr_asmmap_read(self._h, C.byref(c), by.ctypes.data_as(C.POINTER(C.c_uint64))))
+        finally:
+            self._texts = []
+        return {n: int(getattr(c, n)) for n in _abi.ASMMAP_COUNTS}, by
+
+    def anchors(self):
+        """The anchor index ascending by key, as numpy arrays: key (uint64), t, p, o (uint32)"""
+        torch = _torch()
+        n, dev = self.n_anchors, self.engine.device
+        key = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        narrow = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(3)]
+        self._check(self.lib.simmr_asmmap_anchors(self._h, *[C.c_void_p(t.data_ptr()) for t in [key] + narrow], n))
+        self._texts = []
+        return (key[:n].cpu().numpy().view(np.uint64),) + tuple(t[:n].cpu().numpy().view(np.uint32) for t in narrow)
+
+    def n_blocks(self) -> int:
+        n = C.c_uint64(0)
+        self._check(self.lib.simmr_asmmap_blocks(self._h, None, 2 ** 64 - 1, C.byref(n)))  # (no column: the number alone, and no capacity to miss)
+        return int(n.value)
+
+    def blocks(self):
+        """The blocks in row order, nine uint32 numpy arrays: contig, truth_record, strand, q_start, q_end, p_start, p_end, hits, join"""
+        torch = _torch()
+        n, dev = self.n_blocks(), self.engine.device
+        cols = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in _abi.ASMMAP_BLOCK_COLS]
+        ptrs = (C.c_void_p * len(cols))(*[t.data_ptr() for t in cols])
+        self._check(self.lib.simmr_asmmap_blocks(self._h, ptrs, n, None))
+        self._texts = []
+        return tuple(t[:n].cpu().numpy().view(np.uint32) for t in cols)
+
+    def n_contigs(self) -> int:
+        n = C.c_uint64(0)
+        self._check(self.lib.simmr_asmmap_contigs(self._h, None, None, None, None, None, None, 2 ** 64 - 1, C.byref(n)))  # (no column: the number alone)
+        return int(n.value)
+
+    def contigs(self):
+        """The contigs in row order, as numpy arrays: length (uint64), hits, blocks, first_block (uint32), block_bases (uint64),
+        worst_join (uint32)"""
+        torch = _torch()
+        n, dev = self.n_contigs(), self.engine.device
+        wide = [torch.zeros(max(n, 1), dtype=torch.int64, device=dev) for _ in range(2)]
+        narrow = [torch.zeros(max(n, 1), dtype=torch.int32, device=dev) for _ in range(4)]
+        order = [wide[0], narrow[0], narrow[1], narrow[2], wide[1], narrow[3]]
+        self._check(self.lib.simmr_asmmap_contigs(self._h, *[C.c_void_p(t.data_ptr()) for t in order], n, None))
+        self._texts = []
+        return tuple(t[:n].cpu().numpy().view(np.uint64 if t.dtype == torch.int64 else np.uint32) for t in order)
+
+    def ms(self) -> float:
+        """the device time of the unit's calls since the reset, in ms"""
+        a = C.c_float()
+        self._check(self.lib.simmr_last_asmmap_ms(self._h, C.byref(a)))
+        self._texts = []
+        return a.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.simmr_asmmap_destroy(self._h)  # synchronises the stream before it frees: enqueued adds have read their texts
+            self._h = None
+            self._texts = []
+            if self in getattr(self.engine, "_mapevals", []):
+                self.engine._mapevals.remove(self)
+
+
 class BinEval:
     """A binner's contig bins scored against each contig's true genome on the device (simmr_bineval_*, include/simmr_hip.h states
     the rules).  truth_add() the truth text (the file of --eval-assembly-contigs), truth_plan(), add() the binner's assignment, then
@@ -1680,6 +1804,34 @@ class Engine:
                 ev.add(t)
             counts, by_genome = ev.read()
             return counts, by_genome, ev.entries(), ev.contigs()
+        finally:
+            ev.close()
+
+    # -- an assembler's contigs placed on the gold-standard assembly -------------------------
+    def assembly_map_open(self, genomes, k: int = 31, band: int = 64, relocation: int = 1000, min_anchors: int = 16) -> "AsmMap":
+        """A placement object (simmr_asmmap_*) over the genome names.  Closed by its close(), or by the engine's before the
+        engine goes (it is kept in the list of the mapeval objects, which the engine closes first)."""
+        m = AsmMap(self, genomes, k, band, relocation, min_anchors)
+        if not hasattr(self, "_mapevals"):
+            self._mapevals = []
+        self._mapevals.append(m)
+        return m
+
+    def assembly_map(self, truth_bytes, contigs_bytes, genomes, k: int = 31, band: int = 64, relocation: int = 1000, min_anchors: int = 16):
+        """Places the FASTA `contigs_bytes` on the gold-standard FASTA `truth_bytes` (each bytes, a CUDA uint8 tensor, or a list
+        of those: an add each, of whole records).  Returns (counts as a dict, by_genome (n_genomes, 5), (length, hits, blocks,
+        first_block, block_bases, worst_join) of the contigs, the nine block columns)."""
+        def adds(text):
+            return list(text) if isinstance(text, (list, tuple)) else [text]
+        ev = self.assembly_map_open(genomes, k, band, relocation, min_anchors)
+        try:
+            for t in adds(truth_bytes):
+                ev.truth_add(t)
+            ev.truth_plan()
+            for t in adds(contigs_bytes):
+                ev.add(t)
+            counts, by_genome = ev.read()
+            return counts, by_genome, ev.contigs(), ev.blocks()
         finally:
             ev.close()
 

@@ -816,6 +816,20 @@ std::string usage() {
          "                            of both sides (records, bases, longest, N50) and a G row per genome\n"
          "            --eval-assembly-contigs <FILE>  every contig: name, length, kmers, found, shared, top genome row, its votes, its name\n"
          "            --eval-assembly-k <K>  k-mer size, odd, 15 .. 31 [default: 31]\n"
+         "            --eval-placement <FILE>  no simulation: place an assembler's contigs (plain FASTA) on the gold-standard assembly of\n"
+         "                            --eval-placement-truth by unique k-mers, on the device: collinear blocks, the breakpoints between them by\n"
+         "                            class, the misassembled contigs.  Takes only --eval-placement-truth, --eval-placement-report, --eval-placement-blocks,\n"
+         "                            --eval-placement-contigs, --eval-placement-k, --eval-placement-band, --eval-placement-relocation,\n"
+         "                            --eval-placement-min-anchors and --device\n"
+         "            --eval-placement-truth <FILE>  the file of --gold-assembly; the genomes are the header prefixes in front of '|'\n"
+         "            --eval-placement-report <FILE>  the result as a TSV: the counts as #name value lines, #misassemblies, #NA50, #NGA50 and a G\n"
+         "                            row per genome with its own NGA50 and its anchored fraction\n"
+         "            --eval-placement-blocks <FILE>  every block: contig, q_start, q_end, truth record, p_start, p_end, strand, hits, join class\n"
+         "            --eval-placement-contigs <FILE>  every contig: name, length, hits, blocks, first block, block bases, worst join class\n"
+         "            --eval-placement-k <K>  k-mer size, odd, 15 .. 31 [default: 31]\n"
+         "            --eval-placement-band <N>  two neighbouring hits lie on one diagonal where their diagonals differ by at most N [default: 64]\n"
+         "            --eval-placement-relocation <N>  a step of more than N bases on one record and strand is a relocation [default: 1000]\n"
+         "            --eval-placement-min-anchors <N>  a run of fewer hits is dropped [default: 16]\n"
          "            --eval-bins <FILE>  no simulation: score a binner's assignment (contig, tab, bin a line; '#' and '@' lines skipped) against\n"
          "                            the contigs file of --eval-bins-truth, joined by name on the device: purity, completeness, F1, the\n"
          "                            adjusted Rand index, CAMI's bin classes; takes only --eval-bins-truth, --eval-bins-report,\n"
@@ -1095,6 +1109,74 @@ std::string asmeval_contig_rows(const std::vector<std::string>& names, const std
     out += "\t" + std::to_string((unsigned long long)length[i]) + "\t" + std::to_string(kmers[i]) + "\t" + std::to_string(found[i]) + "\t" +
            std::to_string(shared[i]) + "\t" + std::to_string(top_genome[i]) + "\t" + std::to_string(top_kmers[i]) + "\t" +
            (top_genome[i] < genomes.size() ? genomes[top_genome[i]] : std::string(".")) + "\n";
+  }
+  return out;
+}
+
+// ---- --eval-placement ----------------------------------------------------------------------------------------------------------------
+static const char* const ASMMAP_JOIN_NAMES[6] = {"none", "inter_genome", "inter_record", "inversion", "relocation", "local"};
+
+std::string asmmap_nga50(const uint64_t* block_length, size_t n, uint64_t target) {
+  std::vector<uint64_t> ls(block_length, block_length + n);
+  std::sort(ls.begin(), ls.end(), std::greater<uint64_t>());
+  unsigned __int128 run = 0;
+  for (uint64_t x : ls) {
+    run += x;
+    if (2 * run >= target) return std::to_string((unsigned long long)x);
+  }
+  return "NA";
+}
+
+std::string asmmap_report(const uint64_t* counts, uint32_t k, uint32_t band, uint32_t relocation, uint32_t min_anchors, const std::vector<std::string>& genomes,
+                          const uint64_t* by_genome, const uint64_t* block_length, const uint32_t* block_genome, size_t n_blocks) {
+  static const char* const NAMES[ASMMAP_N_COUNTS] = {
+      "truth_records", "truth_bases", "truth_invalid", "truth_kmers", "truth_anchors", "truth_repeats", "records", "bases", "invalid", "kmers", "hits", "stray_hits",
+      "repeat_hits", "runs", "runs_dropped", "blocks", "block_bases", "breaks_inter_genome", "breaks_inter_record", "breaks_inversion", "breaks_relocation",
+      "breaks_local", "contigs_unplaced", "contigs_clean", "contigs_local_only", "contigs_misassembled", "misassembled_bases"};
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  std::string out;
+  for (size_t i = 0; i < ASMMAP_N_COUNTS; i++) out += std::string("#") + NAMES[i] + "\t" + n(counts[i]) + "\n";
+  out += "#k\t" + std::to_string(k) + "\n#band\t" + std::to_string(band) + "\n#relocation\t" + std::to_string(relocation) + "\n#min_anchors\t" +
+         std::to_string(min_anchors) + "\n";
+  out += "#misassemblies\t" + n(counts[17] + counts[18] + counts[19] + counts[20]) + "\n";
+  const uint64_t truth_bases = counts[1], bases = counts[7];
+  out += "#NA50\t" + (bases ? asmmap_nga50(block_length, n_blocks, bases) : std::string("NA")) + "\n";
+  out += "#NGA50\t" + (truth_bases ? asmmap_nga50(block_length, n_blocks, truth_bases) : std::string("NA")) + "\n";
+  out += "#G\tgenome\ttruth_bases\ttruth_anchors\tblocks\tblock_bases\tlongest_block\tNGA50\tanchored\n";
+  for (size_t g = 0; g < genomes.size(); g++) {
+    const uint64_t* r = by_genome + g * ASMMAP_GENOME_COLS;
+    out += "G\t" + genomes[g];
+    for (size_t j = 0; j < ASMMAP_GENOME_COLS; j++) out += "\t" + n(r[j]);
+    std::vector<uint64_t> own;
+    for (size_t i = 0; i < n_blocks; i++)
+      if (block_genome[i] == g) own.push_back(block_length[i]);
+    char frac[64] = "NA";
+    if (r[0] != 0) snprintf(frac, sizeof frac, "%.6f", (double)r[3] / (double)r[0]);
+    out += "\t" + (r[0] ? asmmap_nga50(own.data(), own.size(), r[0]) : std::string("NA")) + "\t" + frac + "\n";
+  }
+  return out;
+}
+
+std::string asmmap_block_rows(const std::vector<std::string>& contig_names, const std::vector<std::string>& truth_names, const uint32_t* const cols[9], size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t c = cols[0][i], t = cols[1][i], join = cols[8][i];
+    out += c < contig_names.size() ? contig_names[c] : std::string("?");
+    out += "\t" + std::to_string(cols[3][i]) + "\t" + std::to_string(cols[4][i]) + "\t" + (t < truth_names.size() ? truth_names[t] : std::string("?")) + "\t" +
+           std::to_string(cols[5][i]) + "\t" + std::to_string(cols[6][i]) + "\t" + (cols[2][i] ? "-" : "+") + "\t" + std::to_string(cols[7][i]) + "\t" +
+           (join < 6 ? ASMMAP_JOIN_NAMES[join] : "?") + "\n";
+  }
+  return out;
+}
+
+std::string asmmap_contig_rows(const std::vector<std::string>& names, const uint64_t* length, const uint32_t* hits, const uint32_t* blocks,
+                               const uint32_t* first_block, const uint64_t* block_bases, const uint32_t* worst_join, size_t n) {
+  std::string out;
+  for (size_t i = 0; i < n; i++) {
+    out += i < names.size() ? names[i] : std::string("?");
+    out += "\t" + std::to_string((unsigned long long)length[i]) + "\t" + std::to_string(hits[i]) + "\t" + std::to_string(blocks[i]) + "\t" +
+           std::to_string(first_block[i]) + "\t" + std::to_string((unsigned long long)block_bases[i]) + "\t" +
+           (worst_join[i] < 6 ? ASMMAP_JOIN_NAMES[worst_join[i]] : "?") + "\n";
   }
   return out;
 }
@@ -1475,7 +1557,7 @@ static bool parse_u64(const std::string& s, uint64_t max, uint64_t* out) {
 
 bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* err, bool* help) {
   *help = false;
-  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax, first_not_asm, first_asm, first_not_bin, first_bin, first_not_corr, first_corr;
+  std::string first_other, first_not_eval, first_eval, first_not_ovl, first_ovl, first_not_vcf, first_vcf, first_not_tax, first_tax, first_not_asm, first_asm, first_not_bin, first_bin, first_not_corr, first_corr, first_not_place, first_place;
   for (int i = 1; i < argc; i++) {
     std::string arg = argv[i], val;
     bool has_val = false;
@@ -1521,6 +1603,9 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
                           arg == "--eval-assembly-k";
     if (asm_flag && first_asm.empty()) first_asm = arg;
     if (!asm_flag && arg != "--device" && first_not_asm.empty()) first_not_asm = arg;  // what --eval-assembly does not take
+    const bool place_flag = arg.compare(0, 16, "--eval-placement") == 0;
+    if (place_flag && first_place.empty()) first_place = arg;
+    if (!place_flag && arg != "--device" && first_not_place.empty()) first_not_place = arg;  // what --eval-placement does not take
     const bool bin_flag = arg == "--eval-bins" || arg == "--eval-bins-truth" || arg == "--eval-bins-report" || arg == "--eval-bins-bins" || arg == "--eval-bins-contigs";
     if (bin_flag && first_bin.empty()) first_bin = arg;
     if (!bin_flag && arg != "--device" && first_not_bin.empty()) first_not_bin = arg;  // what --eval-bins does not take
@@ -1548,6 +1633,19 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
       if (u % 2 == 0) { *err = "invalid value '" + v + "' for '--eval-assembly-k': k is odd"; return false; }
       a->eval_assembly_k = (uint32_t)u;
     }
+    else if (arg == "--eval-placement") { if (!file(&a->eval_placement)) return false; }
+    else if (arg == "--eval-placement-truth") { if (!file(&a->eval_placement_truth)) return false; }
+    else if (arg == "--eval-placement-report") { if (!file(&a->eval_placement_report)) return false; }
+    else if (arg == "--eval-placement-blocks") { if (!file(&a->eval_placement_blocks)) return false; }
+    else if (arg == "--eval-placement-contigs") { if (!file(&a->eval_placement_contigs)) return false; }
+    else if (arg == "--eval-placement-k") {
+      if (!uint(15, 31)) return false;
+      if (u % 2 == 0) { *err = "invalid value '" + v + "' for '--eval-placement-k': k is odd"; return false; }
+      a->eval_placement_k = (uint32_t)u;
+    }
+    else if (arg == "--eval-placement-band") { if (!uint(0, 0x7fffffffull)) return false; a->eval_placement_band = (uint32_t)u; }
+    else if (arg == "--eval-placement-relocation") { if (!uint(0, 0x7fffffffull)) return false; a->eval_placement_relocation = (uint32_t)u; }
+    else if (arg == "--eval-placement-min-anchors") { if (!uint(1, 0xffffffffull)) return false; a->eval_placement_min_anchors = (uint32_t)u; }
     else if (arg == "--single-reads") a->single_reads = true;
     else if (arg == "--genome") { if (!need(&v)) return false; a->genome.push_back(v); }
     else if (arg == "--genome-file") { if (!need(&v)) return false; a->genome_file = v; }
@@ -1725,6 +1823,22 @@ bool parse_cli_args(int argc, const char* const* argv, CliArgs* a, std::string* 
     }
     if (a->eval_assembly_truth.empty()) { *err = "--eval-assembly needs --eval-assembly-truth"; return false; }
     if (a->eval_assembly_report.empty()) { *err = "--eval-assembly needs --eval-assembly-report"; return false; }
+    return true;
+  }
+  if (!first_place.empty()) {  // a mode without a simulation beside --eval-assembly: the same two files, placed instead of counted
+    if (a->eval_placement.empty()) { *err = first_place + " needs --eval-placement"; return false; }
+    if (!first_not_place.empty()) {
+      *err = "--eval-placement runs no simulation: it takes only --eval-placement-truth, --eval-placement-report, --eval-placement-blocks, "
+             "--eval-placement-contigs, --eval-placement-k, --eval-placement-band, --eval-placement-relocation, --eval-placement-min-anchors and --device ('" +
+             first_not_place + "' given)";
+      return false;
+    }
+    if (a->eval_placement_truth.empty()) { *err = "--eval-placement needs --eval-placement-truth"; return false; }
+    if (a->eval_placement_report.empty()) { *err = "--eval-placement needs --eval-placement-report"; return false; }
+    if (a->eval_placement_band > a->eval_placement_relocation) {
+      *err = "--eval-placement-band " + std::to_string(a->eval_placement_band) + " is above --eval-placement-relocation " + std::to_string(a->eval_placement_relocation);
+      return false;
+    }
     return true;
   }
   if (!first_bin.empty()) {  // the seventh mode without a simulation

@@ -1615,6 +1615,122 @@ static int run_eval_assembly(const CliArgs& args) {
   return 0;
 }
 
+// `--eval-placement CONTIGS.fa --eval-placement-truth GOLD.fa --eval-placement-report OUT`: no simulation.  The files and the genome
+// names are read exactly as --eval-assembly reads them (fasta_file_pieces, asmeval_fasta_records); the host keeps the first words
+// of both sides for the block rows and computes NA50 / NGA50 from the block columns, as it computes N50 there.
+struct AsmmapHandle {
+  simmr_asmmap* h = nullptr;
+  ~AsmmapHandle() { simmr_asmmap_destroy(h); }
+};
+static int run_eval_placement(const CliArgs& args) {
+  {
+    FILE* f = fopen(args.eval_placement.c_str(), "rb");
+    if (!f) return die("--eval-placement: cannot open " + args.eval_placement);
+    fclose(f);
+  }
+  Engines engines;
+  simmr_engine* eng = nullptr;
+  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
+  engines.v.push_back(eng);
+  AsmmapHandle ev;  // (declared behind the engines: it goes first)
+  if (simmr_asmmap_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));
+  std::vector<std::string> t_words, c_words;
+  std::vector<uint64_t> t_len, c_len_host;
+  struct Piece { GrowBuf dev; size_t n = 0; };
+  std::vector<std::unique_ptr<Piece>> pieces;
+  info("Parsing " + args.eval_placement_truth);
+  if (int rc = fasta_file_pieces("--eval-placement-truth", args.eval_placement_truth, [&](const uint8_t* d, const char* host, size_t n) {
+        asmeval_fasta_records(host, n, &t_words, &t_len);
+        pieces.emplace_back(new Piece());
+        uint8_t* keep = pieces.back()->dev.room(n);
+        if (!keep || hipMemcpy(keep, d, n, hipMemcpyDeviceToDevice) != hipSuccess) return die("--eval-placement-truth: device allocation failed");
+        pieces.back()->n = n;
+        return 0;
+      }))
+    return rc;
+  std::vector<std::string> genomes;
+  for (const std::string& w : t_words) {
+    const size_t bar = w.find('|');
+    if (bar == std::string::npos || bar == 0)
+      return die("--eval-placement-truth: the header '>" + w + "' has no genome in front of a '|': " + args.eval_placement_truth + " is not a file of --gold-assembly");
+    genomes.push_back(w.substr(0, bar));
+  }
+  std::vector<std::string> t_genome_name = genomes;  // per truth record
+  std::sort(genomes.begin(), genomes.end());
+  genomes.erase(std::unique(genomes.begin(), genomes.end()), genomes.end());
+  std::vector<const char*> gname;
+  for (const std::string& s : genomes) gname.push_back(s.c_str());
+  const simmr_asmmap_config cfg{(uint32_t)gname.size(), args.eval_placement_k, args.eval_placement_band, args.eval_placement_relocation,
+                                args.eval_placement_min_anchors, gname.data()};
+  if (simmr_asmmap_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-placement-truth: ") + simmr_last_error(eng));
+  for (const auto& p : pieces)
+    if (simmr_asmmap_truth_add(ev.h, (const uint8_t*)p->dev.room(p->n), p->n) != SIMMR_OK) return die(std::string("--eval-placement-truth: ") + simmr_last_error(eng));
+  uint64_t n_anchors = 0;
+  if (simmr_asmmap_truth_plan(ev.h, &n_anchors) != SIMMR_OK) return die(std::string("--eval-placement-truth: ") + simmr_last_error(eng));
+  pieces.clear();
+  info("Parsing " + args.eval_placement);
+  if (int rc = fasta_file_pieces("--eval-placement", args.eval_placement, [&](const uint8_t* d, const char* host, size_t n) {
+        asmeval_fasta_records(host, n, &c_words, &c_len_host);
+        if (simmr_asmmap_add(ev.h, d, n) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));  // (synchronises)
+        return 0;
+      }))
+    return rc;
+  simmr_asmmap_counts c{};
+  static_assert(sizeof(c) == ASMMAP_N_COUNTS * sizeof(uint64_t) && ASMMAP_GENOME_COLS == SIMMR_ASMMAP_GENOME_COLS && ASMMAP_BLOCK_COLS == SIMMR_ASMMAP_BLOCK_COLS,
+                "the report names every count and column");
+  std::vector<uint64_t> by_genome(std::max<size_t>(genomes.size(), 1) * ASMMAP_GENOME_COLS);
+  if (simmr_asmmap_read(ev.h, &c, by_genome.data()) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));
+  // the block columns and the contig columns
+  const uint64_t nb = c.blocks, nb1 = std::max<uint64_t>(nb, 1), nc = c.records, nc1 = std::max<uint64_t>(nc, 1);
+  GrowBuf d_blocks, d_wide, d_narrow;
+  uint8_t *db = d_blocks.room(ASMMAP_BLOCK_COLS * nb1 * 4), *dw = d_wide.room(2 * nc1 * 8), *dn = d_narrow.room(4 * nc1 * 4);
+  if (!db || !dw || !dn) return die("--eval-placement: device allocation failed");
+  uint32_t* bcols[ASMMAP_BLOCK_COLS];
+  for (size_t j = 0; j < ASMMAP_BLOCK_COLS; j++) bcols[j] = (uint32_t*)db + j * nb1;
+  if (simmr_asmmap_blocks(ev.h, bcols, nb, nullptr) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));
+  uint64_t* const wide = (uint64_t*)dw;
+  uint32_t* const narrow = (uint32_t*)dn;
+  if (simmr_asmmap_contigs(ev.h, wide, narrow, narrow + nc1, narrow + 2 * nc1, wide + nc1, narrow + 3 * nc1, nc, nullptr) != SIMMR_OK)
+    return die(std::string("--eval-placement: ") + simmr_last_error(eng));
+  std::vector<uint32_t> hb(ASMMAP_BLOCK_COLS * nb1), hn(4 * nc1);
+  std::vector<uint64_t> hw(2 * nc1);
+  if (hipMemcpy(hb.data(), db, hb.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hw.data(), dw, hw.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(hn.data(), dn, hn.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
+    return die("--eval-placement: copy from the device failed");
+  const uint32_t* hcols[ASMMAP_BLOCK_COLS];
+  for (size_t j = 0; j < ASMMAP_BLOCK_COLS; j++) hcols[j] = hb.data() + j * nb1;
+  std::vector<uint64_t> block_length(nb);
+  std::vector<uint32_t> block_genome(nb);
+  for (uint64_t i = 0; i < nb; i++) {
+    block_length[i] = hcols[4][i] - hcols[3][i];
+    const uint32_t t = hcols[1][i];
+    block_genome[i] = t < t_genome_name.size() ? (uint32_t)(std::lower_bound(genomes.begin(), genomes.end(), t_genome_name[t]) - genomes.begin()) : 0xffffffffu;
+  }
+  std::string err;
+  OutFile report(args.eval_placement_report, false);
+  report.append(asmmap_report((const uint64_t*)&c, args.eval_placement_k, args.eval_placement_band, args.eval_placement_relocation, args.eval_placement_min_anchors,
+                              genomes, by_genome.data(), block_length.data(), block_genome.data(), nb));
+  if (!report.close(&err)) return die("--eval-placement-report: " + err);
+  if (!args.eval_placement_blocks.empty()) {
+    OutFile rows(args.eval_placement_blocks, false);
+    rows.append(asmmap_block_rows(c_words, t_words, hcols, nb));
+    if (!rows.close(&err)) return die("--eval-placement-blocks: " + err);
+  }
+  if (!args.eval_placement_contigs.empty()) {
+    OutFile rows(args.eval_placement_contigs, false);
+    rows.append(asmmap_contig_rows(c_words, hw.data(), hn.data(), hn.data() + nc1, hn.data() + 2 * nc1, hw.data() + nc1, hn.data() + 3 * nc1, nc));
+    if (!rows.close(&err)) return die("--eval-placement-contigs: " + err);
+  }
+  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
+  info("Truth: " + n(c.truth_records) + " records, " + n(c.truth_bases) + " bases, " + n(n_anchors) + " unique " + std::to_string(args.eval_placement_k) + "-mers of " +
+       n(genomes.size()) + " genomes as anchors (" + n(c.truth_repeats) + " repeated)");
+  info("Contigs: " + n(c.records) + " records, " + n(c.bases) + " bases, " + n(c.hits) + " anchor hits in " + n(c.blocks) + " blocks; " +
+       n(c.breaks_inter_genome + c.breaks_inter_record + c.breaks_inversion + c.breaks_relocation) + " misassemblies in " + n(c.contigs_misassembled) + " contigs, " +
+       n(c.breaks_local) + " local breaks, " + n(c.contigs_unplaced) + " contigs unplaced");
+  info("Wrote " + args.eval_placement_report);
+  return 0;
+}
+
 // `--eval-bins BINS.tsv --eval-bins-truth CONTIGS.tsv --eval-bins-report OUT`: no simulation.  Both files go up in pieces cut at the
 // last newline (sam_file_pieces).  The host reads every piece once for the names: the truth's contig names and its genomes (the
 // distinct field-8 values other than "."), in a pass in front of the reset, which needs them; the records' bin names, of which a
@@ -1853,6 +1969,7 @@ static int run_main(int argc, char** argv) {
   if (!args.eval_vcf.empty()) return run_eval_vcf(args);
   if (!args.eval_classified.empty()) return run_eval_classified(args);
   if (!args.eval_assembly.empty()) return run_eval_assembly(args);
+  if (!args.eval_placement.empty()) return run_eval_placement(args);
   if (!args.eval_bins.empty()) return run_eval_bins(args);
   if (!args.eval_corrected.empty()) return run_eval_corrected(args);
 

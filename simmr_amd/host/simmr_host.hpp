@@ -242,6 +242,26 @@ std::string asmeval_report(const uint64_t* counts, uint32_t k, const std::vector
 // top_genome, top_kmers, and the genome's name (genomes: sorted, the row is its index), "." where the contig has no vote.
 std::string asmeval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const uint64_t* length, const uint32_t* kmers,
                                 const uint32_t* found, const uint32_t* shared, const uint32_t* top_genome, const uint32_t* top_kmers, size_t n);
+// ---- --eval-placement: the host's share (the names come from asmeval_fasta_records; NA50 / NGA50 and the three files) ----
+constexpr size_t ASMMAP_N_COUNTS = 27, ASMMAP_GENOME_COLS = 5, ASMMAP_BLOCK_COLS = 9;
+// The length of the block at which the lengths, longest first, reach half of `target`, as a decimal number; "NA" where they never
+// do (NA50: the target is the contigs' bases; NGA50: the truth's).
+std::string asmmap_nga50(const uint64_t* block_length, size_t n, uint64_t target);
+// The file of --eval-placement-report: the counts of struct simmr_asmmap_counts as "#name\tvalue" lines in the struct's order
+// (counts[ASMMAP_N_COUNTS]); "#k", "#band", "#relocation", "#min_anchors"; "#misassemblies" = the four non-local classes; "#NA50" and
+// "#NGA50" over the block lengths (block_length[n_blocks] = q_end - q_start; "NA" too where the target is 0); then a header line and
+// a G row per genome (genomes: the sorted names) with the five columns of by_genome[n][5], the genome's own NGA50 (the blocks whose
+// block_genome is the row, against half of its truth_bases) and block_bases / truth_bases as "%.6f" ("NA" without truth bases).
+std::string asmmap_report(const uint64_t* counts, uint32_t k, uint32_t band, uint32_t relocation, uint32_t min_anchors, const std::vector<std::string>& genomes,
+                          const uint64_t* by_genome, const uint64_t* block_length, const uint32_t* block_genome, size_t n_blocks);
+// The rows of --eval-placement-blocks for n blocks in row order (cols: the nine columns of simmr_asmmap_blocks): the contig's name
+// (contig_names[contig]; "?" beyond them), q_start, q_end, the truth record's first word (truth_names[truth_record]; "?" beyond
+// them), p_start, p_end, '+' or '-', hits, and the join class by name (none, inter_genome, inter_record, inversion, relocation, local).
+std::string asmmap_block_rows(const std::vector<std::string>& contig_names, const std::vector<std::string>& truth_names, const uint32_t* const cols[9], size_t n);
+// The rows of --eval-placement-contigs for n contigs in row order: the name ("?" beyond the names), length, hits, blocks, first_block,
+// block_bases and the worst join by name.
+std::string asmmap_contig_rows(const std::vector<std::string>& names, const uint64_t* length, const uint32_t* hits, const uint32_t* blocks,
+                               const uint32_t* first_block, const uint64_t* block_bases, const uint32_t* worst_join, size_t n);
 // ---- --eval-corrected: the report and the reads file ----
 // num / den to six decimals from the integers alone (millionths, rounded half up; '-' in front where `negative` and the result is
 // not zero); "NA" where den is 0.
@@ -604,6 +624,15 @@ struct CliArgs {  // cli.rs:93-220, same flags and defaults
   std::string eval_assembly_report;   // --eval-assembly-report FILE: the counts, completeness per genome and overall, the QV, the contiguity of both sides
   std::string eval_assembly_contigs;  // --eval-assembly-contigs FILE: a row per contig
   uint32_t eval_assembly_k = 31;      // --eval-assembly-k K: odd, 15 .. 31
+  std::string eval_placement;          // --eval-placement FILE: no simulation; an assembler's contigs placed on --eval-placement-truth (simmr_asmmap_*)
+  std::string eval_placement_truth;    // --eval-placement-truth FILE: the file of --gold-assembly
+  std::string eval_placement_report;   // --eval-placement-report FILE: the counts, the misassemblies, NA50 / NGA50, a row per genome
+  std::string eval_placement_blocks;   // --eval-placement-blocks FILE: a row per block
+  std::string eval_placement_contigs;  // --eval-placement-contigs FILE: a row per contig
+  uint32_t eval_placement_k = 31;      // --eval-placement-k K: odd, 15 .. 31
+  uint32_t eval_placement_band = 64;          // --eval-placement-band N
+  uint32_t eval_placement_relocation = 1000;  // --eval-placement-relocation N: below 2^31
+  uint32_t eval_placement_min_anchors = 16;   // --eval-placement-min-anchors N: at least 1
   std::string eval_corrected;         // --eval-corrected FILE: no simulation; a corrector's FASTQ scored against --eval-corrected-truth (simmr_correval_*)
   std::string eval_corrected_truth;   // --eval-corrected-truth FILE: the file of --sam
   std::string eval_corrected_report;  // --eval-corrected-report FILE: the counts, gain, sensitivity, specificity, the rows by quality and position, the cube
