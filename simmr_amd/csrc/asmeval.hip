@@ -1,8 +1,6 @@
 // asmeval.hip — an assembler's contigs scored against the gold-standard assembly (include/simmr_hip.h: simmr_asmeval_*): the
-// entry points over asmeval_kernels.hip.  A translation unit of libsimmr_hip.so of its own; it sees an engine through
-// engine_internal.hpp only.  The engine's slot enum is full, so the state lives in an object of its own that the caller creates on
-// an engine and destroys before the engine, as vcfeval.hip's does.  The names are mapeval.hip's (sorted, in a device blob; the rule
-// of sam_names.hpp), the sort is sam_sort.hip's (samsort_sort_pairs), the scan of the run heads is the engine's (eng_scan_u32).
+// entry points over asmeval_kernels.hip, on the scaffold of scorer_host.hpp.  The front (asmeval_front.hpp) is this unit's and
+// asmmap.hip's; the scan of the run heads is the engine's (eng_scan_u32).
 //
 // The front of an add of either side (enqueue_front) only enqueues and sizes everything from n_bytes: a line per two bytes, a
 // record per line, a base per byte.  index (count) -> scan -> index (write) -> lines (count) -> chunks -> lines (write) -> pack.
@@ -13,27 +11,23 @@
 //             (bits = min(24, bit length of the entries)) and empties the candidate side.
 // add:        the front, then SYNCHRONISES for the add's bases and records (room for the contig columns), the roll with the lookups,
 //             synchronises for the number of vote pairs, sorts them, scans their heads (synchronises) and takes every contig's top.
-// Time: two spans, as ovleval.hip keeps them: the adds of either side are one span from the first add's begin to the last one's
-// end, folded into a sum by a call that synchronises anyway (the plan, simmr_last_asmeval_ms); the plan has a span of its own, and
-// the sort inside the plan a `Spans` of one beside them (it counts once, inside the plan).
+// Time: the adds' span and the plan's, and the sort inside the plan in a `Spans` of one beside them (it counts once, inside the
+// plan).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "host_support.hpp"
 #include "asmeval_kernels.hip"
 #include "asmeval_front.hpp"
 #include "sam_names.hpp"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
 namespace {
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 enum { SPAN_ADDS = 0, SPAN_PLAN = 1, SPAN_COUNT = 2 };
 constexpr uint32_t TABLE_MAX_BITS = 24;  // the prefix table: min(24, bit length of the entries) bits of the key's top
@@ -46,30 +40,28 @@ const char* const MALFORMED_CAND = "a sequence line in front of the add's first 
 
 struct simmr_asmeval {
   simmr_engine* e = nullptr;
-  // the names
-  DevBuf blob, name_off;
+  DeviceNames genomes;
   uint32_t n_genomes = 0, k = 0, plain_search = 0;
   // the front of one add: the line index, the lines, the planes (asmeval_front.hpp)
   AsmFront front;
   DevBuf rec_row;
   // the truth: the occurrences as appended, the sort's buffers, the entries
-  DevBuf u_key, u_row, key[2], idx[2], hist, digit_total, head, before;
+  DevBuf u_key, u_row, head, before;
+  PairSort occ_sort, pair_sort;  // the plan's over the occurrences, an add's over its vote pairs (their keys go into pair_sort.key[0])
   DevBuf e_key, e_start, e_genome, e_mult, hits, table;
   DevBuf cursor;   // [0] occurrences, [1] the vote pairs of the add
   DevBuf counts;   // AC_COUNT words
   DevBuf word;     // the error word
   // the candidates: the contig columns, the pairs and votes of one add, the per-genome table of a read
-  DevBuf c_len, c_kmers, c_found, c_shared, c_top, c_voted, p_key[2], p_idx[2], p_count, v_key, v_count, g_table;
+  DevBuf c_len, c_kmers, c_found, c_shared, c_top, c_voted, p_count, v_key, v_count, g_table;
   uint64_t occ_cap = 0;     // occurrences the truth adds since the reset may have appended
   uint64_t n_entries = 0, n_contigs = 0, contig_cap = 0;
   uint32_t table_bits = 0;
   bool reset_once = false, planned = false;
-  Spans<SPAN_COUNT> sp;
+  FoldedSpans<SPAN_COUNT> sp;
   Spans<1> sort_sp;  // the sort inside the last plan: beside the spans above, so that it counts once, inside the plan
-  bool open = false;  // the span of the adds has begun and is not folded yet
-  float done_ms = 0.f;
 
-  MevNames names() const { return MevNames{blob.as<const uint8_t>(), name_off.as<const uint32_t>(), n_genomes}; }
+  MevNames names() const { return genomes.names(n_genomes); }
   AsmLines lines() const { return front.lines(); }
   AsmPlane plane() const { return front.plane(); }
   AsmContigs contigs() const {
@@ -86,45 +78,8 @@ struct simmr_asmeval {
 
 namespace {
 
-int check_text(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
-  simmr_engine* e = h->e;
-  if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "%s called before simmr_asmeval_reset", who);
-  if (!text && n_bytes > 0) return eng_fail(e, SIMMR_EINVAL, "%s: NULL text", who);
-  if (n_bytes > SIMMR_ASMEVAL_MAX_BYTES)
-    return eng_fail(e, SIMMR_ENOTSUP, "%s: %llu bytes in one add (at most %llu: cut the text in front of a header)", who, (unsigned long long)n_bytes,
-                    (unsigned long long)SIMMR_ASMEVAL_MAX_BYTES);
-  return SIMMR_OK;
-}
-
-int begin_span(simmr_asmeval* h, int which, hipStream_t st) {
-  if (which == SPAN_ADDS && h->open) return SIMMR_OK;
-  HIP_TRY(h->e, h->sp.begin(which, st));
-  return SIMMR_OK;
-}
-
-// the spans that count into the sum, and closed.  Synchronises.
-int fold_spans(simmr_asmeval* h) {
-  float now = 0.f;
-  if (int rc = h->sp.total_ms(h->e, "asmeval", &now)) return rc;
-  h->done_ms += now;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  return SIMMR_OK;
-}
-
-int end_span(simmr_asmeval* h, int which, hipStream_t st, const char* what) {
-  simmr_engine* e = h->e;
-  hipError_t rc = hipGetLastError();
-  if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s launch failed: %s", what, hipGetErrorString(rc));
-  HIP_TRY(e, h->sp.end(which, st));
-  if (which == SPAN_ADDS) h->open = true;
-  h->sp.mark(which);
-  return SIMMR_OK;
-}
-
-uint32_t grid_for(simmr_engine* e, uint64_t items, uint32_t per_wg, uint32_t wgs_per_cu) {
-  const uint64_t cus = (uint64_t)std::max(eng_cu_count(e), 1);
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + per_wg - 1) / per_wg, cus * wgs_per_cu));
+int check_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
+  return check_add_text(h->e, h->reset_once, text, n_bytes, SIMMR_ASMEVAL_MAX_BYTES, who, "simmr_asmeval_reset", "cut the text in front of a header");
 }
 
 // text[0, n_bytes) (n_bytes > 0) to the object's line entries and planes; `truth`: the side whose counts and error bit it feeds
@@ -135,19 +90,6 @@ int enqueue_front(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes, hipSt
                           (uint32_t)(truth ? AC_T_INVALID : AC_INVALID), h->word.as<uint32_t>(), truth ? ASM_ERR_TRUTH : ASM_ERR_CAND};
   asm_front_launch(e, st, text, n_bytes, h->front.bufs(), sums, W);
   return SIMMR_OK;
-}
-
-// room for n pairs in the sort's pong, index and histogram buffers, and in the heads and their scan
-bool sort_room(simmr_asmeval* h, DevBuf* pong, DevBuf* idx2, uint64_t n) {
-  const uint64_t n_tiles = std::max<uint64_t>((n + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE, 1);
-  return pong->ensure(n * 8) && idx2[0].ensure(n * 4) && idx2[1].ensure(n * 4) && h->hist.ensure(n_tiles * SAMSORT_PAIRS_DIGITS * 4) &&
-         h->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4) && h->head.ensure(n * 4) && h->before.ensure((n + 1) * 8);
-}
-
-// a contig column with room for `want` entries of `width` bytes; what it held stays and the new part is zero
-bool grow_zero(DevBuf* b, uint64_t want, uint64_t held, uint32_t width, hipStream_t st) {
-  if (!b->grow_keep(want * width, held * width, st)) return false;
-  return hipMemsetAsync((uint8_t*)b->p + held * width, 0, (want - held) * width, st) == hipSuccess;
 }
 
 }  // namespace
@@ -177,23 +119,9 @@ void asm_front_genomes(simmr_engine* e, hipStream_t st, const MevText& W, const 
 
 extern "C" {
 
-int simmr_asmeval_create(simmr_engine* e, simmr_asmeval** out) {
-  if (!e) return SIMMR_EINVAL;
-  if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_asmeval_create: NULL out");
-  *out = nullptr;
-  simmr_asmeval* h = new (std::nothrow) simmr_asmeval();
-  if (!h) return eng_fail(e, SIMMR_ENOMEM, "simmr_asmeval_create: out of memory");
-  h->e = e;
-  *out = h;
-  return SIMMR_OK;
-}
+int simmr_asmeval_create(simmr_engine* e, simmr_asmeval** out) { return scorer_create(e, out, "simmr_asmeval_create"); }
 
-void simmr_asmeval_destroy(simmr_asmeval* h) {
-  if (!h) return;
-  if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  delete h;  // (its buffers and events go with it)
-  (void)hipGetLastError();
-}
+void simmr_asmeval_destroy(simmr_asmeval* h) { scorer_destroy(h); }
 
 int simmr_asmeval_reset(simmr_asmeval* h, const simmr_asmeval_config* cfg) {
   if (!h) return SIMMR_EINVAL;
@@ -201,45 +129,24 @@ int simmr_asmeval_reset(simmr_asmeval* h, const simmr_asmeval_config* cfg) {
   if (!cfg || (cfg->n_genomes > 0 && !cfg->genome)) return eng_fail(e, SIMMR_EINVAL, "simmr_asmeval_reset: NULL argument");
   if (cfg->k < 15u || cfg->k > 31u || cfg->k % 2u == 0u) return eng_fail(e, SIMMR_EINVAL, "simmr_asmeval_reset: k = %u (an odd number of 15 to 31)", cfg->k);
   if (cfg->n_genomes > (1u << 24) - 1u) return eng_fail(e, SIMMR_ERANGE, "simmr_asmeval_reset: %u genome names (fewer than 2^24)", cfg->n_genomes);
-  std::vector<std::string> names;
-  names.reserve(cfg->n_genomes);
-  for (uint32_t i = 0; i < cfg->n_genomes; i++) {
-    const char* s = cfg->genome[i];
-    const size_t n = s ? std::strlen(s) : 0;
-    if (n == 0 || n > SAM_RNAME_MAX) return eng_fail(e, SIMMR_ENOTSUP, "genome name %u is empty or longer than %u bytes", i, SAM_RNAME_MAX);
-    if (!rname_legal(s, n)) return eng_fail(e, SIMMR_ENOTSUP, "'%s' (genome name %u) is not a SAM reference name", s, i);
-    names.emplace_back(s, n);
-  }
-  std::sort(names.begin(), names.end());  // (bytewise, a prefix first: the bytes are below 128)
-  for (size_t i = 1; i < names.size(); i++)
-    if (names[i] == names[i - 1]) return eng_fail(e, SIMMR_EINVAL, "genome name '%s' is given twice", names[i].c_str());
-  std::vector<uint8_t> blob;
-  std::vector<uint32_t> off{0u};
-  for (const std::string& s : names) {
-    blob.insert(blob.end(), s.begin(), s.end());
-    off.push_back((uint32_t)blob.size());
-  }
-  blob.resize(blob.size() + 8, 0);
+  SortedNames sorted;
+  if (int rc = sorted_names(e, cfg->genome, cfg->n_genomes, SAM_RNAME_MAX, rname_legal, "genome name", nullptr, &sorted)) return rc;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   if (int rc = sync_check(e, "asmeval reset")) return rc;
   h->planned = false;
   h->reset_once = false;
-  h->sp.invalidate_from(0);
-  h->open = false;
   h->sort_sp.invalidate_from(0);
-  h->done_ms = 0.f;
-  if (int rc = h->sp.create_missing(e)) return rc;
+  if (int rc = h->sp.reset(e)) return rc;
   if (int rc = h->sort_sp.create_missing(e)) return rc;
-  if (!h->blob.ensure(blob.size()) || !h->name_off.ensure(off.size() * 4) || !h->cursor.ensure(16) || !h->counts.ensure(AC_COUNT * 8) || !h->word.ensure(16))
+  if (!h->genomes.room(sorted) || !h->cursor.ensure(16) || !h->counts.ensure(AC_COUNT * 8) || !h->word.ensure(16))
     return eng_fail(e, SIMMR_ENOMEM, "asmeval reset: allocation failed");
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipMemcpyAsync(h->blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  HIP_TRY(e, hipMemcpyAsync(h->name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+  if (int rc = h->genomes.upload(e, sorted, st)) return rc;
   HIP_TRY(e, hipMemsetAsync(h->cursor.p, 0, 16, st));
   HIP_TRY(e, hipMemsetAsync(h->counts.p, 0, AC_COUNT * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->word.p, 0, 16, st));
   if (int rc = sync_check(e, "asmeval reset")) return rc;  // (the uploads read host vectors that end here)
-  h->n_genomes = (uint32_t)names.size();
+  h->n_genomes = cfg->n_genomes;
   h->k = cfg->k;
   h->plain_search = cfg->plain_search ? 1u : 0u;
   h->occ_cap = 0;
@@ -253,7 +160,7 @@ int simmr_asmeval_reset(simmr_asmeval* h, const simmr_asmeval_config* cfg) {
 int simmr_asmeval_truth_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_asmeval_truth_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_asmeval_truth_add")) return rc;
   h->planned = false;
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
@@ -262,13 +169,13 @@ int simmr_asmeval_truth_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_by
   if (!h->u_key.grow_keep(cap * 8, held * 8, st) || !h->u_row.grow_keep(cap * 4, held * 4, st) || !h->rec_row.ensure((n_bytes / 2 + 1) * 4))
     return eng_fail(e, SIMMR_ENOMEM, "asmeval truth: allocation failed for %llu k-mer occurrences", (unsigned long long)cap);
   h->occ_cap = cap;
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   if (int rc = enqueue_front(h, text, n_bytes, st, true, &W)) return rc;
   asm_front_genomes(e, st, W, h->lines(), h->names(), h->rec_row.as<uint32_t>(), h->word.as<uint32_t>());
   hipLaunchKernelGGL(k_asm_roll_truth, dim3(grid_for(e, n_bytes / ASM_WORD + 1, ASM_WG, 32)), dim3(ASM_WG), 0, st, h->plane(), h->k,
                      h->rec_row.as<const uint32_t>(), h->u_key.as<uint64_t>(), h->u_row.as<uint32_t>(), cap, h->cursor_p());
-  return end_span(h, SPAN_ADDS, st, "asmeval truth add");
+  return h->sp.end(e, SPAN_ADDS, st, "asmeval truth add");
 }
 
 int simmr_asmeval_truth_plan(simmr_asmeval* h, uint64_t* n_entries) {
@@ -283,34 +190,32 @@ int simmr_asmeval_truth_plan(simmr_asmeval* h, uint64_t* n_entries) {
   HIP_TRY(e, hipMemcpyAsync(&cur, h->cursor.p, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "asmeval truth adds")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "asmeval")) return rc;
   if (errw & ASM_ERR_TRUTH) return eng_fail(e, SIMMR_EINVAL, "a malformed truth text: %s", MALFORMED_TRUTH);
   const uint64_t n = std::min(cur, h->occ_cap);
   if (n >= (1ull << 31))
     return eng_fail(e, SIMMR_ERANGE, "simmr_asmeval_truth_plan takes fewer than 2^31 k-mer occurrences (%llu given)", (unsigned long long)n);
   const uint64_t n1 = std::max<uint64_t>(n, 1);
-  if (!h->key[0].ensure(n1 * 8) || !sort_room(h, &h->key[1], h->idx, n1))
+  if (!h->occ_sort.room(n1) || !h->head.ensure(n1 * 4) || !h->before.ensure((n1 + 1) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "asmeval truth plan: allocation failed (%llu k-mer occurrences)", (unsigned long long)n);
-  if (int rc = begin_span(h, SPAN_PLAN, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_PLAN, st)) return rc;
   // the candidate side starts over
   HIP_TRY(e, hipMemsetAsync(h->counts_p() + AC_RECORDS, 0, (AC_COUNT - AC_RECORDS) * 8, st));
   h->n_contigs = 0;
   h->contig_cap = 0;
   h->sort_sp.invalidate_from(0);
   uint64_t nd = 0;
-  const uint64_t* skey = h->key[0].as<const uint64_t>();
+  const uint64_t* skey = h->occ_sort.key[0].as<const uint64_t>();
   const uint32_t* sidx = nullptr;
   const uint32_t grid = grid_for(e, n1, 256, 32);
   if (n > 0) {
-    HIP_TRY(e, hipMemcpyAsync(h->key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
-    uint64_t* const keys[2] = {h->key[0].as<uint64_t>(), h->key[1].as<uint64_t>()};
-    uint32_t* const idxs[2] = {h->idx[0].as<uint32_t>(), h->idx[1].as<uint32_t>()};
+    HIP_TRY(e, hipMemcpyAsync(h->occ_sort.key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
     HIP_TRY(e, h->sort_sp.begin(0, st));
-    const int side = samsort_sort_pairs(st, keys, idxs, h->hist.as<uint32_t>(), h->digit_total.as<uint32_t>(), n, 2u * h->k);
+    const PairSort::Sorted by_key = h->occ_sort.sort(st, n, 2u * h->k);
     HIP_TRY(e, h->sort_sp.end(0, st));
     h->sort_sp.mark(0);
-    skey = h->key[side].as<const uint64_t>();
-    sidx = h->idx[side].as<const uint32_t>();
+    skey = by_key.keys;
+    sidx = by_key.perm;
     hipLaunchKernelGGL(k_asm_heads, dim3(grid), dim3(256), 0, st, skey, n, h->head.as<uint32_t>());
     if (int rc = eng_scan_u32(e, h->head.as<const uint32_t>(), n, h->before.as<uint64_t>(), &nd)) return rc;  // (synchronises)
   }
@@ -328,12 +233,12 @@ int simmr_asmeval_truth_plan(simmr_asmeval* h, uint64_t* n_entries) {
     hipLaunchKernelGGL(k_asm_table, dim3(grid_for(e, (1ull << bits) + 1, 256, 32)), dim3(256), 0, st, h->e_key.as<const uint64_t>(), (uint32_t)nd, bits,
                        2u * h->k - bits, h->table.as<uint32_t>());
   }
-  if (int rc = end_span(h, SPAN_PLAN, st, "asmeval truth plan")) return rc;
+  if (int rc = h->sp.end(e, SPAN_PLAN, st, "asmeval truth plan")) return rc;
   if (int rc = sync_check(e, "asmeval truth plan")) return rc;
   h->n_entries = nd;
   h->table_bits = nd > 0 ? bits : 0u;
   h->planned = true;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "asmeval")) return rc;
   if (n_entries) *n_entries = nd;
   return SIMMR_OK;
 }
@@ -341,12 +246,12 @@ int simmr_asmeval_truth_plan(simmr_asmeval* h, uint64_t* n_entries) {
 int simmr_asmeval_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_asmeval_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_asmeval_add")) return rc;
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_asmeval_add called without a simmr_asmeval_truth_plan in force");
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   if (int rc = enqueue_front(h, text, n_bytes, st, false, &W)) return rc;
   uint32_t tot[3] = {0, 0, 0};
@@ -362,7 +267,7 @@ int simmr_asmeval_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes) {
            grow_zero(&h->c_found, cap, held, 4, st) && grow_zero(&h->c_shared, cap, held, 4, st) && grow_zero(&h->c_voted, cap, held, 4, st);
     if (room) h->contig_cap = cap;
   }
-  room = room && h->p_key[0].ensure(pair_cap * 8) && h->p_count.ensure(pair_cap * 4);
+  room = room && h->pair_sort.key[0].ensure(pair_cap * 8) && h->p_count.ensure(pair_cap * 4);
   if (!room) return eng_fail(e, SIMMR_ENOMEM, "asmeval add: allocation failed (%llu contigs, %llu bases)", (unsigned long long)want, (unsigned long long)n_bases);
   h->n_contigs = want;
   HIP_TRY(e, hipMemsetAsync(h->cursor_p() + 1, 0, 8, st));
@@ -371,29 +276,27 @@ int simmr_asmeval_add(simmr_asmeval* h, const uint8_t* text, uint64_t n_bytes) {
                        h->c_len.as<uint64_t>());
   if (n_bases > 0)
     hipLaunchKernelGGL(k_asm_roll_cand, dim3(grid_for(e, n_bases / ASM_WORD + 1, ASM_WG, 32)), dim3(ASM_WG), 0, st, h->plane(), h->k, h->entries(), h->n_genomes,
-                       h->hits.as<uint32_t>(), c0, h->contigs(), h->p_key[0].as<uint64_t>(), h->p_count.as<uint32_t>(), pair_cap, h->cursor_p() + 1);
+                       h->hits.as<uint32_t>(), c0, h->contigs(), h->pair_sort.key[0].as<uint64_t>(), h->p_count.as<uint32_t>(), pair_cap, h->cursor_p() + 1);
   uint64_t np = 0;
   HIP_TRY(e, hipMemcpyAsync(&np, h->cursor_p() + 1, 8, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "asmeval add")) return rc;
   np = std::min(np, pair_cap);
   if (np > 0) {
-    if (!sort_room(h, &h->p_key[1], h->p_idx, np)) return eng_fail(e, SIMMR_ENOMEM, "asmeval add: allocation failed (%llu vote pairs)", (unsigned long long)np);
-    uint64_t* const keys[2] = {h->p_key[0].as<uint64_t>(), h->p_key[1].as<uint64_t>()};
-    uint32_t* const idxs[2] = {h->p_idx[0].as<uint32_t>(), h->p_idx[1].as<uint32_t>()};
-    const uint32_t key_bits = bits_of((want - 1) << ASM_GENOME_BITS | 0xffffffull);
-    const int side = samsort_sort_pairs(st, keys, idxs, h->hist.as<uint32_t>(), h->digit_total.as<uint32_t>(), np, key_bits);
+    if (!h->pair_sort.room(np) || !h->head.ensure(np * 4) || !h->before.ensure((np + 1) * 8))
+      return eng_fail(e, SIMMR_ENOMEM, "asmeval add: allocation failed (%llu vote pairs)", (unsigned long long)np);
+    const PairSort::Sorted by_pair = h->pair_sort.sort(st, np, bits_of((want - 1) << ASM_GENOME_BITS | 0xffffffull));  // (24 bits at least: a permutation)
     const uint32_t grid = grid_for(e, np, 256, 32);
-    hipLaunchKernelGGL(k_asm_heads, dim3(grid), dim3(256), 0, st, (const uint64_t*)keys[side], np, h->head.as<uint32_t>());
+    hipLaunchKernelGGL(k_asm_heads, dim3(grid), dim3(256), 0, st, by_pair.keys, np, h->head.as<uint32_t>());
     uint64_t nv = 0;
     if (int rc = eng_scan_u32(e, h->head.as<const uint32_t>(), np, h->before.as<uint64_t>(), &nv)) return rc;  // (synchronises)
     if (!h->v_key.ensure(nv * 8) || !h->v_count.ensure(nv * 4)) return eng_fail(e, SIMMR_ENOMEM, "asmeval add: allocation failed (%llu votes)", (unsigned long long)nv);
     HIP_TRY(e, hipMemsetAsync(h->v_count.p, 0, nv * 4, st));
-    hipLaunchKernelGGL(k_asm_vote_sum, dim3(grid), dim3(256), 0, st, (const uint64_t*)keys[side], (const uint32_t*)idxs[side], h->p_count.as<const uint32_t>(),
+    hipLaunchKernelGGL(k_asm_vote_sum, dim3(grid), dim3(256), 0, st, by_pair.keys, by_pair.perm, h->p_count.as<const uint32_t>(),
                        h->before.as<const uint64_t>(), np, nv, h->v_key.as<uint64_t>(), h->v_count.as<uint32_t>());
     hipLaunchKernelGGL(k_asm_vote_top, dim3(grid_for(e, nv, 256, 32)), dim3(256), 0, st, h->v_key.as<const uint64_t>(), h->v_count.as<const uint32_t>(), nv, want,
                        h->contigs());
   }
-  return end_span(h, SPAN_ADDS, st, "asmeval add");
+  return h->sp.end(e, SPAN_ADDS, st, "asmeval add");
 }
 
 int simmr_asmeval_read(simmr_asmeval* h, simmr_asmeval_counts* counts, uint64_t* by_genome_host) {
@@ -478,8 +381,7 @@ int simmr_last_asmeval_ms(simmr_asmeval* h, float* ms, float* plan_sort_ms) {
   if (!ms) return eng_fail(e, SIMMR_EINVAL, "simmr_last_asmeval_ms: NULL ms");
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_asmeval_reset yet");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = fold_spans(h)) return rc;  // (the next add of either side begins a new span)
-  *ms = h->done_ms;
+  if (int rc = h->sp.last_ms(e, "asmeval", ms)) return rc;
   if (plan_sort_ms)
     if (int rc = h->sort_sp.total_ms(e, "asmeval", plan_sort_ms)) return rc;
   return SIMMR_OK;

@@ -1,8 +1,6 @@
 // asmmap.hip — an assembler's contigs placed on the gold-standard assembly (include/simmr_hip.h: simmr_asmmap_*): the entry points
-// over asmmap_kernels.hip.  A translation unit of libsimmr_hip.so of its own; it sees an engine through engine_internal.hpp only,
-// and its state is an object the caller creates on an engine and destroys before the engine, as asmeval.hip's.  The names are
-// mapeval.hip's (sorted, in a device blob; the rule of sam_names.hpp), the text-to-planes stage is asmeval's (asmeval_front.hpp),
-// the sort is sam_sort.hip's (samsort_sort_pairs), every scan is the engine's (eng_scan_u32).
+// over asmmap_kernels.hip, on the scaffold of scorer_host.hpp.  The text-to-planes stage is asmeval's (asmeval_front.hpp), every
+// scan is the engine's (eng_scan_u32).
 //
 // truth_add:  the front, the genome of every record, the truth rows (genome, length), the roll; the occurrences (key, t << 1 | o, p)
 //             are appended through a cursor, their columns sized from the bytes of every truth add since the reset and the truth
@@ -13,26 +11,23 @@
 // add:        the front, then SYNCHRONISES for the add's bases and records; count pass, scan (hits), write pass, run heads, scan
 //             (runs), run columns, kept marks, scan (kept runs), their compaction, block heads, scan (blocks), block columns,
 //             spans, joins.  Five waits: each total sizes what the next stage writes.
-// Time: two spans, as asmeval.hip keeps them.
+// Time: the adds' span and the plan's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "host_support.hpp"
 #include "asmmap_kernels.hip"
 #include "asmeval_front.hpp"
 #include "sam_names.hpp"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
 namespace {
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 enum { SPAN_ADDS = 0, SPAN_PLAN = 1, SPAN_COUNT = 2 };
 constexpr uint32_t TABLE_MAX_BITS = 24;  // the prefix table: min(24, bit length of the entries) bits of the key's top
@@ -45,12 +40,13 @@ const char* const MALFORMED_CAND = "a sequence line in front of the add's first 
 
 struct simmr_asmmap {
   simmr_engine* e = nullptr;
-  DevBuf blob, name_off;
+  DeviceNames genomes;
   uint32_t n_genomes = 0, k = 0, band = 0, relocation = 0, min_anchors = 0;
   AsmFront front;
   DevBuf rec_row;
   // the truth: the rows, the occurrences as appended, the sort's buffers, the two indexes
-  DevBuf t_genome, t_len, u_key, u_to, u_p, key[2], idx[2], hist, digit_total, mark_a, mark_r, before_a, before_r;
+  DevBuf t_genome, t_len, u_key, u_to, u_p, mark_a, mark_r, before_a, before_r;
+  PairSort order;
   DevBuf a_key, a_t, a_p, a_o, a_table, r_key, r_table, g_truth;
   DevBuf cursor, counts, word;
   // one add: the hits, the runs, the kept runs and their scans
@@ -62,11 +58,9 @@ struct simmr_asmmap {
   uint32_t a_bits = 0, r_bits = 0;
   uint32_t max_wgs = 0;  // SIMMR_ASMMAP_MAX_WGS; 0: no cap
   bool reset_once = false, planned = false;
-  Spans<SPAN_COUNT> sp;
-  bool open = false;
-  float done_ms = 0.f;
+  FoldedSpans<SPAN_COUNT> sp;
 
-  MevNames names() const { return MevNames{blob.as<const uint8_t>(), name_off.as<const uint32_t>(), n_genomes}; }
+  MevNames names() const { return genomes.names(n_genomes); }
   AmapAnchors anchors() const {
     return AmapAnchors{AsmEntries{a_key.as<const uint64_t>(), nullptr, a_table.as<const uint32_t>(), (uint32_t)n_anchors, a_bits, 2u * k - a_bits},
                        AsmEntries{r_key.as<const uint64_t>(), nullptr, r_table.as<const uint32_t>(), (uint32_t)n_repeats, r_bits, 2u * k - r_bits},
@@ -88,40 +82,8 @@ struct simmr_asmmap {
 
 namespace {
 
-int check_text(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
-  simmr_engine* e = h->e;
-  if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "%s called before simmr_asmmap_reset", who);
-  if (!text && n_bytes > 0) return eng_fail(e, SIMMR_EINVAL, "%s: NULL text", who);
-  if (n_bytes > SIMMR_ASMEVAL_MAX_BYTES)
-    return eng_fail(e, SIMMR_ENOTSUP, "%s: %llu bytes in one add (at most %llu: cut the text in front of a header)", who, (unsigned long long)n_bytes,
-                    (unsigned long long)SIMMR_ASMEVAL_MAX_BYTES);
-  return SIMMR_OK;
-}
-
-int begin_span(simmr_asmmap* h, int which, hipStream_t st) {
-  if (which == SPAN_ADDS && h->open) return SIMMR_OK;
-  HIP_TRY(h->e, h->sp.begin(which, st));
-  return SIMMR_OK;
-}
-
-// the spans that count into the sum, and closed.  Synchronises.
-int fold_spans(simmr_asmmap* h) {
-  float now = 0.f;
-  if (int rc = h->sp.total_ms(h->e, "asmmap", &now)) return rc;
-  h->done_ms += now;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  return SIMMR_OK;
-}
-
-int end_span(simmr_asmmap* h, int which, hipStream_t st, const char* what) {
-  simmr_engine* e = h->e;
-  hipError_t rc = hipGetLastError();
-  if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s launch failed: %s", what, hipGetErrorString(rc));
-  HIP_TRY(e, h->sp.end(which, st));
-  if (which == SPAN_ADDS) h->open = true;
-  h->sp.mark(which);
-  return SIMMR_OK;
+int check_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
+  return check_add_text(h->e, h->reset_once, text, n_bytes, SIMMR_ASMEVAL_MAX_BYTES, who, "simmr_asmmap_reset", "cut the text in front of a header");
 }
 
 // the workgroups of a launch of one of this unit's kernels over `items`; SIMMR_ASMMAP_MAX_WGS (read at create, include/simmr_hip.h)
@@ -129,8 +91,7 @@ int end_span(simmr_asmmap* h, int which, hipStream_t st, const char* what) {
 // launches are asmeval's (asm_front_launch) and are not capped.
 uint32_t grid_for(const simmr_asmmap* h, uint64_t items, uint32_t per_wg, uint32_t wgs_per_cu) {
   const uint64_t cus = (uint64_t)std::max(eng_cu_count(h->e), 1);
-  const uint64_t most = h->max_wgs ? std::min<uint64_t>(cus * wgs_per_cu, h->max_wgs) : cus * wgs_per_cu;
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + per_wg - 1) / per_wg, most));
+  return grid_capped(items, per_wg, h->max_wgs ? std::min<uint64_t>(cus * wgs_per_cu, h->max_wgs) : cus * wgs_per_cu);
 }
 
 int enqueue_front(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes, hipStream_t st, bool truth, MevText* W) {
@@ -139,12 +100,6 @@ int enqueue_front(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes, hipStr
                           (uint32_t)(truth ? AM_T_INVALID : AM_INVALID), h->word.as<uint32_t>(), truth ? ASM_ERR_TRUTH : ASM_ERR_CAND};
   asm_front_launch(h->e, st, text, n_bytes, h->front.bufs(), sums, W);
   return SIMMR_OK;
-}
-
-// a column with room for `want` entries of `width` bytes; what it held stays and the new part is zero
-bool grow_zero(DevBuf* b, uint64_t want, uint64_t held, uint32_t width, hipStream_t st) {
-  if (!b->grow_keep(want * width, held * width, st)) return false;
-  return hipMemsetAsync((uint8_t*)b->p + held * width, 0, (want - held) * width, st) == hipSuccess;
 }
 
 // the prefix table over n sorted keys: its bits, and the launch
@@ -163,23 +118,12 @@ int build_table(simmr_asmmap* h, hipStream_t st, const DevBuf& keys, uint64_t n,
 extern "C" {
 
 int simmr_asmmap_create(simmr_engine* e, simmr_asmmap** out) {
-  if (!e) return SIMMR_EINVAL;
-  if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_asmmap_create: NULL out");
-  *out = nullptr;
-  simmr_asmmap* h = new (std::nothrow) simmr_asmmap();
-  if (!h) return eng_fail(e, SIMMR_ENOMEM, "simmr_asmmap_create: out of memory");
-  h->e = e;
-  if (const char* v = std::getenv("SIMMR_ASMMAP_MAX_WGS")) h->max_wgs = (uint32_t)std::max(std::atoi(v), 0);
-  *out = h;
+  if (int rc = scorer_create(e, out, "simmr_asmmap_create")) return rc;
+  if (const char* v = std::getenv("SIMMR_ASMMAP_MAX_WGS")) (*out)->max_wgs = (uint32_t)std::max(std::atoi(v), 0);
   return SIMMR_OK;
 }
 
-void simmr_asmmap_destroy(simmr_asmmap* h) {
-  if (!h) return;
-  if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  delete h;  // (its buffers and events go with it)
-  (void)hipGetLastError();
-}
+void simmr_asmmap_destroy(simmr_asmmap* h) { scorer_destroy(h); }
 
 int simmr_asmmap_reset(simmr_asmmap* h, const simmr_asmmap_config* cfg) {
   if (!h) return SIMMR_EINVAL;
@@ -190,43 +134,22 @@ int simmr_asmmap_reset(simmr_asmmap* h, const simmr_asmmap_config* cfg) {
   if (cfg->band > cfg->relocation) return eng_fail(e, SIMMR_EINVAL, "simmr_asmmap_reset: band = %u above relocation = %u", cfg->band, cfg->relocation);
   if (cfg->min_anchors == 0u) return eng_fail(e, SIMMR_EINVAL, "simmr_asmmap_reset: min_anchors = 0 (at least 1)");
   if (cfg->n_genomes > (1u << 24) - 1u) return eng_fail(e, SIMMR_ERANGE, "simmr_asmmap_reset: %u genome names (fewer than 2^24)", cfg->n_genomes);
-  std::vector<std::string> names;
-  names.reserve(cfg->n_genomes);
-  for (uint32_t i = 0; i < cfg->n_genomes; i++) {
-    const char* s = cfg->genome[i];
-    const size_t n = s ? std::strlen(s) : 0;
-    if (n == 0 || n > SAM_RNAME_MAX) return eng_fail(e, SIMMR_ENOTSUP, "genome name %u is empty or longer than %u bytes", i, SAM_RNAME_MAX);
-    if (!rname_legal(s, n)) return eng_fail(e, SIMMR_ENOTSUP, "'%s' (genome name %u) is not a SAM reference name", s, i);
-    names.emplace_back(s, n);
-  }
-  std::sort(names.begin(), names.end());  // (bytewise, a prefix first: the bytes are below 128)
-  for (size_t i = 1; i < names.size(); i++)
-    if (names[i] == names[i - 1]) return eng_fail(e, SIMMR_EINVAL, "genome name '%s' is given twice", names[i].c_str());
-  std::vector<uint8_t> blob;
-  std::vector<uint32_t> off{0u};
-  for (const std::string& s : names) {
-    blob.insert(blob.end(), s.begin(), s.end());
-    off.push_back((uint32_t)blob.size());
-  }
-  blob.resize(blob.size() + 8, 0);
+  SortedNames sorted;
+  if (int rc = sorted_names(e, cfg->genome, cfg->n_genomes, SAM_RNAME_MAX, rname_legal, "genome name", nullptr, &sorted)) return rc;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   if (int rc = sync_check(e, "asmmap reset")) return rc;
   h->planned = false;
   h->reset_once = false;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  h->done_ms = 0.f;
-  if (int rc = h->sp.create_missing(e)) return rc;
-  if (!h->blob.ensure(blob.size()) || !h->name_off.ensure(off.size() * 4) || !h->cursor.ensure(16) || !h->counts.ensure(AM_COUNT * 8) || !h->word.ensure(16))
+  if (int rc = h->sp.reset(e)) return rc;
+  if (!h->genomes.room(sorted) || !h->cursor.ensure(16) || !h->counts.ensure(AM_COUNT * 8) || !h->word.ensure(16))
     return eng_fail(e, SIMMR_ENOMEM, "asmmap reset: allocation failed");
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipMemcpyAsync(h->blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  HIP_TRY(e, hipMemcpyAsync(h->name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+  if (int rc = h->genomes.upload(e, sorted, st)) return rc;
   HIP_TRY(e, hipMemsetAsync(h->cursor.p, 0, 16, st));
   HIP_TRY(e, hipMemsetAsync(h->counts.p, 0, AM_COUNT * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->word.p, 0, 16, st));
   if (int rc = sync_check(e, "asmmap reset")) return rc;  // (the uploads read host vectors that end here)
-  h->n_genomes = (uint32_t)names.size();
+  h->n_genomes = cfg->n_genomes;
   h->k = cfg->k;
   h->band = cfg->band;
   h->relocation = cfg->relocation;
@@ -241,7 +164,7 @@ int simmr_asmmap_reset(simmr_asmmap* h, const simmr_asmmap_config* cfg) {
 int simmr_asmmap_truth_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_asmmap_truth_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_asmmap_truth_add")) return rc;
   h->planned = false;
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
@@ -252,7 +175,7 @@ int simmr_asmmap_truth_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_byte
     return eng_fail(e, SIMMR_ENOMEM, "asmmap truth: allocation failed for %llu k-mer occurrences", (unsigned long long)cap);
   h->occ_cap = cap;
   h->truth_cap = rows;
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   if (int rc = enqueue_front(h, text, n_bytes, st, true, &W)) return rc;
   asm_front_genomes(e, st, W, h->front.lines(), h->names(), h->rec_row.as<uint32_t>(), h->word.as<uint32_t>());
@@ -261,7 +184,7 @@ int simmr_asmmap_truth_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_byte
                      h->t_len.as<uint32_t>());
   hipLaunchKernelGGL(k_amap_roll_truth, dim3(grid_for(h, n_bytes / ASM_WORD + 1, AMAP_WG, 32)), dim3(AMAP_WG), 0, st, h->front.plane(), h->k,
                      (const unsigned long long*)h->counts_p(), h->u_key.as<uint64_t>(), h->u_to.as<uint32_t>(), h->u_p.as<uint32_t>(), cap, h->cursor_p());
-  return end_span(h, SPAN_ADDS, st, "asmmap truth add");
+  return h->sp.end(e, SPAN_ADDS, st, "asmmap truth add");
 }
 
 int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors) {
@@ -277,7 +200,7 @@ int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors) {
   HIP_TRY(e, hipMemcpyAsync(&n_truth, h->counts_p() + AM_T_RECORDS, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "asmmap truth adds")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "asmmap")) return rc;
   if (errw & ASM_ERR_TRUTH) return eng_fail(e, SIMMR_EINVAL, "a malformed truth text: %s", MALFORMED_TRUTH);
   const uint64_t n = std::min(cur, h->occ_cap);
   n_truth = std::min(n_truth, h->truth_cap);
@@ -285,26 +208,23 @@ int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors) {
     return eng_fail(e, SIMMR_ERANGE, "simmr_asmmap_truth_plan takes fewer than 2^31 k-mer occurrences (%llu given)", (unsigned long long)n);
   if (n_truth >= (1ull << 31))
     return eng_fail(e, SIMMR_ERANGE, "simmr_asmmap_truth_plan takes fewer than 2^31 truth records (%llu given)", (unsigned long long)n_truth);
-  const uint64_t n1 = std::max<uint64_t>(n, 1), n_tiles = std::max<uint64_t>((n1 + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE, 1);
+  const uint64_t n1 = std::max<uint64_t>(n, 1);
   const uint64_t g2 = (uint64_t)std::max(h->n_genomes, 1u) * 2;
-  if (!h->key[0].ensure(n1 * 8) || !h->key[1].ensure(n1 * 8) || !h->idx[0].ensure(n1 * 4) || !h->idx[1].ensure(n1 * 4) ||
-      !h->hist.ensure(n_tiles * SAMSORT_PAIRS_DIGITS * 4) || !h->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4) || !h->mark_a.ensure(n1 * 4) ||
-      !h->mark_r.ensure(n1 * 4) || !h->before_a.ensure((n1 + 1) * 8) || !h->before_r.ensure((n1 + 1) * 8) || !h->g_truth.ensure(g2 * 8))
+  if (!h->order.room(n1) || !h->mark_a.ensure(n1 * 4) || !h->mark_r.ensure(n1 * 4) || !h->before_a.ensure((n1 + 1) * 8) ||
+      !h->before_r.ensure((n1 + 1) * 8) || !h->g_truth.ensure(g2 * 8))
     return eng_fail(e, SIMMR_ENOMEM, "asmmap truth plan: allocation failed (%llu k-mer occurrences)", (unsigned long long)n);
-  if (int rc = begin_span(h, SPAN_PLAN, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_PLAN, st)) return rc;
   // the candidate side starts over
   HIP_TRY(e, hipMemsetAsync(h->counts_p() + AM_RECORDS, 0, (AM_COUNT - AM_RECORDS) * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->g_truth.p, 0, g2 * 8, st));
   h->n_contigs = h->contig_cap = h->n_blocks = h->block_cap = h->n_runs = 0;
   uint64_t na = 0, nr = 0;
   const uint32_t grid = grid_for(h, n1, AMAP_WG, 32);
-  int side = 0;
+  PairSort::Sorted by_key{};
   if (n > 0) {
-    HIP_TRY(e, hipMemcpyAsync(h->key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
-    uint64_t* const keys[2] = {h->key[0].as<uint64_t>(), h->key[1].as<uint64_t>()};
-    uint32_t* const idxs[2] = {h->idx[0].as<uint32_t>(), h->idx[1].as<uint32_t>()};
-    side = samsort_sort_pairs(st, keys, idxs, h->hist.as<uint32_t>(), h->digit_total.as<uint32_t>(), n, 2u * h->k);
-    hipLaunchKernelGGL(k_amap_marks, dim3(grid), dim3(AMAP_WG), 0, st, (const uint64_t*)keys[side], n, h->mark_a.as<uint32_t>(), h->mark_r.as<uint32_t>());
+    HIP_TRY(e, hipMemcpyAsync(h->order.key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
+    by_key = h->order.sort(st, n, 2u * h->k);
+    hipLaunchKernelGGL(k_amap_marks, dim3(grid), dim3(AMAP_WG), 0, st, by_key.keys, n, h->mark_a.as<uint32_t>(), h->mark_r.as<uint32_t>());
     if (int rc = eng_scan_u32(e, h->mark_a.as<const uint32_t>(), n, h->before_a.as<uint64_t>(), &na)) return rc;  // (synchronises)
     if (int rc = eng_scan_u32(e, h->mark_r.as<const uint32_t>(), n, h->before_r.as<uint64_t>(), &nr)) return rc;  // (synchronises)
   }
@@ -312,7 +232,7 @@ int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors) {
   if (!h->a_key.ensure(na1 * 8) || !h->a_t.ensure(na1 * 4) || !h->a_p.ensure(na1 * 4) || !h->a_o.ensure(na1 * 4) || !h->r_key.ensure(nr1 * 8))
     return eng_fail(e, SIMMR_ENOMEM, "asmmap truth plan: allocation failed (%llu anchors, %llu repeats)", (unsigned long long)na, (unsigned long long)nr);
   if (n > 0)
-    hipLaunchKernelGGL(k_amap_index, dim3(grid), dim3(AMAP_WG), 0, st, h->key[side].as<const uint64_t>(), h->idx[side].as<const uint32_t>(),
+    hipLaunchKernelGGL(k_amap_index, dim3(grid), dim3(AMAP_WG), 0, st, by_key.keys, by_key.perm,
                        h->mark_a.as<const uint32_t>(), h->mark_r.as<const uint32_t>(), h->before_a.as<const uint64_t>(), h->before_r.as<const uint64_t>(),
                        h->u_to.as<const uint32_t>(), h->u_p.as<const uint32_t>(), n, na, nr, h->a_key.as<uint64_t>(), h->a_t.as<uint32_t>(), h->a_p.as<uint32_t>(),
                        h->a_o.as<uint32_t>(), h->r_key.as<uint64_t>());
@@ -322,7 +242,7 @@ int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors) {
   if (n_truth > 0)
     hipLaunchKernelGGL(k_amap_reduce_truth, dim3(grid_for(h, std::max(n_truth, na), AMAP_WG, 8)), dim3(AMAP_WG), 0, st, h->t_genome.as<const uint32_t>(),
                        h->t_len.as<const uint32_t>(), n_truth, h->a_t.as<const uint32_t>(), na, h->n_genomes, h->g_truth.as<unsigned long long>());
-  if (int rc = end_span(h, SPAN_PLAN, st, "asmmap truth plan")) return rc;
+  if (int rc = h->sp.end(e, SPAN_PLAN, st, "asmmap truth plan")) return rc;
   if (int rc = sync_check(e, "asmmap truth plan")) return rc;
   h->n_truth = n_truth;
   h->n_anchors = na;
@@ -330,7 +250,7 @@ int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors) {
   h->a_bits = a_bits;
   h->r_bits = r_bits;
   h->planned = true;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "asmmap")) return rc;
   if (n_anchors) *n_anchors = na;
   return SIMMR_OK;
 }
@@ -338,12 +258,12 @@ int simmr_asmmap_truth_plan(simmr_asmmap* h, uint64_t* n_anchors) {
 int simmr_asmmap_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_asmmap_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_asmmap_add")) return rc;
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_asmmap_add called without a simmr_asmmap_truth_plan in force");
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   if (int rc = enqueue_front(h, text, n_bytes, st, false, &W)) return rc;
   uint32_t tot[3] = {0, 0, 0};
@@ -365,13 +285,13 @@ int simmr_asmmap_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes) {
   if (n_rec > 0)
     hipLaunchKernelGGL(k_amap_contig_len, dim3(grid_for(h, n_rec, AMAP_WG, 32)), dim3(AMAP_WG), 0, st, h->front.rec_start.as<const uint32_t>(), (uint32_t)n_rec, c0,
                        h->c_len.as<uint64_t>());
-  if (n_words == 0) return end_span(h, SPAN_ADDS, st, "asmmap add");
+  if (n_words == 0) return h->sp.end(e, SPAN_ADDS, st, "asmmap add");
   // the hits: count, scan, write (without an anchor the k-mers and the repeat hits still count)
   hipLaunchKernelGGL(k_amap_roll_count, dim3(grid_for(h, n_words, AMAP_WG, 32)), dim3(AMAP_WG), 0, st, h->front.plane(), h->k, h->anchors(), c0,
                      h->c_hits.as<uint32_t>(), h->lane_hits.as<uint32_t>(), h->counts_p());
   uint64_t nh = 0;
   if (int rc = eng_scan_u32(e, h->lane_hits.as<const uint32_t>(), n_words, h->lane_off.as<uint64_t>(), &nh)) return rc;  // (synchronises)
-  if (nh == 0) return end_span(h, SPAN_ADDS, st, "asmmap add");
+  if (nh == 0) return h->sp.end(e, SPAN_ADDS, st, "asmmap add");
   if (!h->h_c.ensure(nh * 4) || !h->h_q.ensure(nh * 4) || !h->h_ts.ensure(nh * 4) || !h->h_d.ensure(nh * 8) || !h->run_head.ensure(nh * 4) ||
       !h->run_before.ensure((nh + 1) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "asmmap add: allocation failed (%llu anchor hits)", (unsigned long long)nh);
@@ -392,7 +312,7 @@ int simmr_asmmap_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes) {
                      h->kept.as<uint32_t>(), h->counts_p());
   uint64_t nk = 0;
   if (int rc = eng_scan_u32(e, h->kept.as<const uint32_t>(), nr, h->kept_before.as<uint64_t>(), &nk)) return rc;  // (synchronises)
-  if (nk == 0) return end_span(h, SPAN_ADDS, st, "asmmap add");
+  if (nk == 0) return h->sp.end(e, SPAN_ADDS, st, "asmmap add");
   if (!h->k_first.ensure(nk * 4) || !h->k_last.ensure(nk * 4) || !h->blk_head.ensure(nk * 4) || !h->blk_before.ensure((nk + 1) * 8))
     return eng_fail(e, SIMMR_ENOMEM, "asmmap add: allocation failed (%llu kept runs)", (unsigned long long)nk);
   const uint32_t kept_grid = grid_for(h, nk, AMAP_WG, 32);
@@ -422,7 +342,7 @@ int simmr_asmmap_add(simmr_asmmap* h, const uint8_t* text, uint64_t n_bytes) {
                      b0, h->k, B);
   hipLaunchKernelGGL(k_amap_joins, dim3(grid_for(h, nb, AMAP_WG, 32)), dim3(AMAP_WG), 0, st, B, b0, nb, h->t_genome.as<const uint32_t>(), (uint64_t)h->band,
                      (uint64_t)h->relocation, h->contigs());
-  return end_span(h, SPAN_ADDS, st, "asmmap add");
+  return h->sp.end(e, SPAN_ADDS, st, "asmmap add");
 }
 
 int simmr_asmmap_read(simmr_asmmap* h, simmr_asmmap_counts* counts, uint64_t* by_genome_host) {
@@ -531,9 +451,7 @@ int simmr_last_asmmap_ms(simmr_asmmap* h, float* ms) {
   if (!ms) return eng_fail(e, SIMMR_EINVAL, "simmr_last_asmmap_ms: NULL ms");
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_asmmap_reset yet");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = fold_spans(h)) return rc;  // (the next add of either side begins a new span)
-  *ms = h->done_ms;
-  return SIMMR_OK;
+  return h->sp.last_ms(e, "asmmap", ms);
 }
 
 }  // extern "C"

@@ -9,19 +9,17 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "bam_index_kernels.hip"
 #include "record_stream_host.hpp"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
 static_assert(BAI_KEY_POS_BITS == 40u, "the canonical key of simmr_sam_sort_emit");
 
 namespace {
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 struct BaiState {
   DevBuf rb, chunk_sum, chunk_prefix;
@@ -85,23 +83,9 @@ struct BamSortFormat : RecordFormat {
 
 extern "C" {
 
-int simmr_bam_sort_create(simmr_engine* e, simmr_bam_sort** out) {
-  if (!e) return SIMMR_EINVAL;
-  if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_bam_sort_create: NULL out");
-  *out = nullptr;
-  simmr_bam_sort* h = new (std::nothrow) simmr_bam_sort();
-  if (!h) return eng_fail(e, SIMMR_ENOMEM, "simmr_bam_sort_create: out of memory");
-  h->e = e;
-  *out = h;
-  return SIMMR_OK;
-}
+int simmr_bam_sort_create(simmr_engine* e, simmr_bam_sort** out) { return scorer_create(e, out, "simmr_bam_sort_create"); }
 
-void simmr_bam_sort_destroy(simmr_bam_sort* h) {
-  if (!h) return;
-  if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  delete h;  // (its buffers and events go with it)
-  (void)hipGetLastError();
-}
+void simmr_bam_sort_destroy(simmr_bam_sort* h) { scorer_destroy(h); }
 
 int simmr_bam_sort_plan(simmr_bam_sort* h, const simmr_sam_names* names, const simmr_reads_out* reads, const simmr_truth_out* truth,
                         uint64_t n_reads, int paired, uint64_t* record_bytes) {

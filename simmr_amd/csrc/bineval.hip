@@ -1,8 +1,5 @@
 // bineval.hip — a binner's contig bins scored against each contig's true genome (include/simmr_hip.h: simmr_bineval_*): the entry
-// points over bineval_kernels.hip.  A translation unit of libsimmr_hip.so of its own; it sees an engine through engine_internal.hpp
-// only.  The engine's slot enum is full, so the state lives in an object of its own that the caller creates on an engine and
-// destroys before the engine, as asmeval.hip's does.  The genome names are mapeval.hip's (sorted, in a device blob; the rule of
-// sam_names.hpp), the sorts are sam_sort.hip's (samsort_sort_pairs), the scans of the flags are the engine's (eng_scan_u32).
+// points over bineval_kernels.hip, on the scaffold of scorer_host.hpp.  The scans of the flags are the engine's (eng_scan_u32).
 //
 // The front of an add of either side (enqueue_front) only enqueues and sizes everything from n_bytes: a line per two bytes.
 // index (count) -> scan -> index (write) -> lines -> chunks -> write.
@@ -14,26 +11,22 @@
 //             columns), then the write pass with the lookups, the first record and the records of every truth contig.
 // read:       sorts the records by the bin name's hash, finds the representatives, scans their flags (synchronises: the bins),
 //             assigns, sorts the cell keys, scans the cell heads (synchronises: the cells), sums, and makes the tables.
-// Time: three spans, as asmeval.hip keeps its two: the adds of either side are one span from the first add's begin to the last
-// one's end, folded into a sum by a call that synchronises anyway; the plan and the read have spans of their own, and the sort
-// inside the plan a `Spans` of one beside them (it counts once, inside the plan).
+// Time: the adds' span, the plan's and the read's, and the sort inside the plan in a `Spans` of one beside them (it counts once,
+// inside the plan).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "host_support.hpp"
 #include "bineval_kernels.hip"
 #include "sam_names.hpp"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
 namespace {
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 // Workgroups a CU of every grid: beyond them the workgroups loop.  Small, so that a text of a few MB takes every kernel past one trip.
 constexpr uint32_t WGS_PER_CU = 2;
@@ -50,14 +43,15 @@ const char* const MALFORMED_CAND = "a record without a second field, or a name t
 
 struct simmr_bineval {
   simmr_engine* e = nullptr;
-  // the names
-  DevBuf blob, name_off;
+  DeviceNames genomes;
   uint32_t n_genomes = 0, hash_bits = 64;
   // the front of one add: the line index, the chunks, the totals
-  DevBuf tile_sum, tile_prefix, starts, info, chunk_sum, chunk_prefix, tot, rec_field;
+  LineIndex line_index;
+  DevBuf info, chunk_sum, chunk_prefix, tot, rec_field;
   // the truth: the rows as appended, the order of the plan, the assignment
   DevBuf t_pool, t_off, t_len, t_hash, t_length, t_genome, t_first, t_records, t_bin;
-  DevBuf key[2], idx[2], hist, digit_total, head, before;
+  PairSort truth_sort, rec_sort, cell_sort;  // the plan's over the truth's hashes, a read's over the records' hashes and over the cell keys
+  DevBuf head, before;
   DevBuf cursor;   // [0] the truth's rows, [1] the bytes of their names
   DevBuf unknown;  // the records of contigs that are not in the truth
   DevBuf counts;   // BC_COUNT words
@@ -65,27 +59,25 @@ struct simmr_bineval {
   // the candidate records since the plan
   DevBuf b_pool, b_off, b_len, b_hash, r_contig;
   // a read: the records' order, the bin rows, the cells, the tables
-  DevBuf r_key[2], r_idx[2], rep, flag, rec_bin;
+  DevBuf rep, flag, rec_bin;
   DevBuf q_contigs, q_real, q_bases, q_none, q_first, q_top_genome, q_top_bases;
-  DevBuf c_key[2], c_idx[2], c_bin, c_genome, c_contigs, c_bases;
+  DevBuf c_bin, c_genome, c_contigs, c_bases;
   DevBuf g_table, best_bin;
   uint64_t row_cap = 0, pool_cap = 0;   // what the truth adds since the reset may have appended
   uint64_t n_truth = 0, n_records = 0, n_bpool = 0, n_bins = 0, n_cells = 0;
-  int side = 0;
+  PairSort::Sorted truth_order{};  // the truth's rows in the plan's order
   bool reset_once = false, planned = false, read_holds = false;
-  Spans<SPAN_COUNT> sp;
+  FoldedSpans<SPAN_COUNT> sp;
   Spans<1> sort_sp;
-  bool open = false;  // the span of the adds has begun and is not folded yet
-  float done_ms = 0.f;
 
   uint64_t mask() const { return hash_bits >= 64u ? ~0ull : (1ull << hash_bits) - 1ull; }
-  MevNames names() const { return MevNames{blob.as<const uint8_t>(), name_off.as<const uint32_t>(), n_genomes}; }
+  MevNames names() const { return genomes.names(n_genomes); }
   BinNames truth_names() const { return BinNames{t_pool.as<uint8_t>(), t_off.as<uint64_t>(), t_len.as<uint32_t>(), t_hash.as<uint64_t>(), row_cap, pool_cap}; }
   BinNames bin_names(uint64_t rows, uint64_t bytes) const {
     return BinNames{b_pool.as<uint8_t>(), b_off.as<uint64_t>(), b_len.as<uint32_t>(), b_hash.as<uint64_t>(), rows, bytes};
   }
   BinIndex index() const {
-    return BinIndex{key[side].as<const uint64_t>(), idx[side].as<const uint32_t>(), t_pool.as<const uint8_t>(), t_off.as<const uint64_t>(),
+    return BinIndex{truth_order.keys, truth_order.perm, t_pool.as<const uint8_t>(), t_off.as<const uint64_t>(),
                     t_len.as<const uint32_t>(), t_hash.as<const uint64_t>(), (uint32_t)n_truth, mask()};
   }
   BinBins bins() const {
@@ -98,82 +90,27 @@ struct simmr_bineval {
 
 namespace {
 
-int check_text(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
-  simmr_engine* e = h->e;
-  if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "%s called before simmr_bineval_reset", who);
-  if (!text && n_bytes > 0) return eng_fail(e, SIMMR_EINVAL, "%s: NULL text", who);
-  if (n_bytes > SIMMR_BINEVAL_MAX_BYTES)
-    return eng_fail(e, SIMMR_ENOTSUP, "%s: %llu bytes in one add (at most %llu: cut the text behind a line end)", who, (unsigned long long)n_bytes,
-                    (unsigned long long)SIMMR_BINEVAL_MAX_BYTES);
-  return SIMMR_OK;
-}
-
-int begin_span(simmr_bineval* h, int which, hipStream_t st) {
-  if (which == SPAN_ADDS && h->open) return SIMMR_OK;
-  HIP_TRY(h->e, h->sp.begin(which, st));
-  return SIMMR_OK;
-}
-
-// the spans that count into the sum, and closed.  Synchronises.
-int fold_spans(simmr_bineval* h) {
-  float now = 0.f;
-  if (int rc = h->sp.total_ms(h->e, "bineval", &now)) return rc;
-  h->done_ms += now;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  return SIMMR_OK;
-}
-
-int end_span(simmr_bineval* h, int which, hipStream_t st, const char* what) {
-  simmr_engine* e = h->e;
-  hipError_t rc = hipGetLastError();
-  if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s launch failed: %s", what, hipGetErrorString(rc));
-  HIP_TRY(e, h->sp.end(which, st));
-  if (which == SPAN_ADDS) h->open = true;
-  h->sp.mark(which);
-  return SIMMR_OK;
-}
-
-uint32_t grid_for(simmr_engine* e, uint64_t items, uint32_t per_wg, uint32_t wgs_per_cu) {
-  const uint64_t cus = (uint64_t)std::max(eng_cu_count(e), 1);
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + per_wg - 1) / per_wg, cus * wgs_per_cu));
+int check_add(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
+  return check_add_text(h->e, h->reset_once, text, n_bytes, SIMMR_BINEVAL_MAX_BYTES, who, "simmr_bineval_reset", "cut the text behind a line end");
 }
 
 // text[0, n_bytes) (n_bytes > 0) to the object's line index
 int enqueue_front(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes, hipStream_t st, MevText* W, uint64_t* line_cap_out) {
   simmr_engine* e = h->e;
   const uint64_t n_tiles = (n_bytes + FSAM_TILE - 1) / FSAM_TILE, line_cap = n_bytes / 2 + 1, chunk_cap = line_cap / BIN_CHUNK + 1;
-  bool room = h->tile_sum.ensure(n_tiles * 8) && h->tile_prefix.ensure((n_tiles + 1) * 8) && h->starts.ensure(line_cap * 4) &&
-              h->chunk_sum.ensure(chunk_cap * 8) && h->chunk_prefix.ensure((chunk_cap + 1) * 8) && h->tot.ensure(sizeof(BinTot)) &&
-              h->rec_field.ensure(line_cap * 8) && h->info.ensure(line_cap * 16);
+  bool room = h->line_index.room(n_tiles, line_cap) && h->chunk_sum.ensure(chunk_cap * 8) && h->chunk_prefix.ensure((chunk_cap + 1) * 8) &&
+              h->tot.ensure(sizeof(BinTot)) && h->rec_field.ensure(line_cap * 8) && h->info.ensure(line_cap * 16);
   if (!room) return eng_fail(e, SIMMR_ENOMEM, "bineval: allocation failed for %llu bytes of text", (unsigned long long)n_bytes);
-  const uint32_t tile_grid = grid_for(e, n_tiles, 1, WGS_PER_CU);
-  hipLaunchKernelGGL(k_bin_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(), (const uint64_t*)nullptr,
-                     (uint32_t*)nullptr, 0ull);
-  hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(256), 0, st, h->tile_sum.as<const uint64_t>(), h->tile_prefix.as<uint64_t>(), n_tiles);
-  hipLaunchKernelGGL(k_bin_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(),
-                     h->tile_prefix.as<const uint64_t>(), h->starts.as<uint32_t>(), line_cap);
-  *W = MevText{text, n_bytes, h->tile_prefix.as<const uint64_t>() + n_tiles, h->starts.as<const uint32_t>()};
+  h->line_index.enqueue(st, k_bin_index, k_bin_scan, text, n_bytes, FSAM_TILE, grid_for(e, n_tiles, 1, WGS_PER_CU), line_cap, W);
   *line_cap_out = line_cap;
   return SIMMR_OK;
 }
 
-// room for n pairs in a sort's pong and index buffers, in the histograms, and in the heads and their scan
-bool sort_room(simmr_bineval* h, DevBuf* pong, DevBuf* idx2, uint64_t n) {
-  const uint64_t n_tiles = std::max<uint64_t>((n + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE, 1);
-  return pong->ensure(n * 8) && idx2[0].ensure(n * 4) && idx2[1].ensure(n * 4) && h->hist.ensure(n_tiles * SAMSORT_PAIRS_DIGITS * 4) &&
-         h->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4) && h->head.ensure(n * 4) && h->before.ensure((n + 1) * 8);
-}
-
-// the n pairs (key[0][i], i) in the order of the low `bits` bits of the keys; the side that holds them.  No bits: the identity.
-int sort_by(simmr_bineval* h, hipStream_t st, DevBuf* key2, DevBuf* idx2, uint64_t n, uint32_t bits) {
-  if (bits == 0u) {
-    hipLaunchKernelGGL(k_bin_iota, dim3(grid_for(h->e, n, 256, WGS_PER_CU)), dim3(256), 0, st, idx2[0].as<uint32_t>(), n);
-    return 0;
-  }
-  uint64_t* const keys[2] = {key2[0].as<uint64_t>(), key2[1].as<uint64_t>()};
-  uint32_t* const idxs[2] = {idx2[0].as<uint32_t>(), idx2[1].as<uint32_t>()};
-  return samsort_sort_pairs(st, keys, idxs, h->hist.as<uint32_t>(), h->digit_total.as<uint32_t>(), n, bits);
+// the n pairs (S->key[0][i], i) in the order of the low `bits` bits of the keys.  No bits: the identity, written out.
+PairSort::Sorted sort_by(simmr_bineval* h, hipStream_t st, PairSort* S, uint64_t n, uint32_t bits) {
+  if (bits > 0u) return S->sort(st, n, bits);
+  hipLaunchKernelGGL(k_bin_iota, dim3(grid_for(h->e, n, 256, WGS_PER_CU)), dim3(256), 0, st, S->idx[0].as<uint32_t>(), n);
+  return PairSort::Sorted{S->key[0].as<const uint64_t>(), S->idx[0].as<const uint32_t>()};
 }
 
 int malformed(simmr_bineval* h, uint32_t errw) {
@@ -197,23 +134,9 @@ int emit_check(simmr_bineval* h, const char* who, const char* what, uint64_t n, 
 
 extern "C" {
 
-int simmr_bineval_create(simmr_engine* e, simmr_bineval** out) {
-  if (!e) return SIMMR_EINVAL;
-  if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_bineval_create: NULL out");
-  *out = nullptr;
-  simmr_bineval* h = new (std::nothrow) simmr_bineval();
-  if (!h) return eng_fail(e, SIMMR_ENOMEM, "simmr_bineval_create: out of memory");
-  h->e = e;
-  *out = h;
-  return SIMMR_OK;
-}
+int simmr_bineval_create(simmr_engine* e, simmr_bineval** out) { return scorer_create(e, out, "simmr_bineval_create"); }
 
-void simmr_bineval_destroy(simmr_bineval* h) {
-  if (!h) return;
-  if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  delete h;  // (its buffers and events go with it)
-  (void)hipGetLastError();
-}
+void simmr_bineval_destroy(simmr_bineval* h) { scorer_destroy(h); }
 
 int simmr_bineval_reset(simmr_bineval* h, const simmr_bineval_config* cfg) {
   if (!h) return SIMMR_EINVAL;
@@ -221,48 +144,27 @@ int simmr_bineval_reset(simmr_bineval* h, const simmr_bineval_config* cfg) {
   if (!cfg || (cfg->n_genomes > 0 && !cfg->genome)) return eng_fail(e, SIMMR_EINVAL, "simmr_bineval_reset: NULL argument");
   if (cfg->hash_bits > 64u) return eng_fail(e, SIMMR_EINVAL, "simmr_bineval_reset: hash_bits = %u (0 to 64)", cfg->hash_bits);
   if (cfg->n_genomes > (1u << 24) - 1u) return eng_fail(e, SIMMR_ERANGE, "simmr_bineval_reset: %u genome names (fewer than 2^24)", cfg->n_genomes);
-  std::vector<std::string> names;
-  names.reserve(cfg->n_genomes);
-  for (uint32_t i = 0; i < cfg->n_genomes; i++) {
-    const char* s = cfg->genome[i];
-    const size_t n = s ? std::strlen(s) : 0;
-    if (n == 0 || n > SAM_RNAME_MAX) return eng_fail(e, SIMMR_ENOTSUP, "genome name %u is empty or longer than %u bytes", i, SAM_RNAME_MAX);
-    if (!rname_legal(s, n)) return eng_fail(e, SIMMR_ENOTSUP, "'%s' (genome name %u) is not a SAM reference name", s, i);
-    names.emplace_back(s, n);
-  }
-  std::sort(names.begin(), names.end());  // (bytewise, a prefix first: the bytes are below 128)
-  for (size_t i = 1; i < names.size(); i++)
-    if (names[i] == names[i - 1]) return eng_fail(e, SIMMR_EINVAL, "genome name '%s' is given twice", names[i].c_str());
-  std::vector<uint8_t> blob;
-  std::vector<uint32_t> off{0u};
-  for (const std::string& s : names) {
-    blob.insert(blob.end(), s.begin(), s.end());
-    off.push_back((uint32_t)blob.size());
-  }
-  blob.resize(blob.size() + 8, 0);
+  SortedNames sorted;
+  if (int rc = sorted_names(e, cfg->genome, cfg->n_genomes, SAM_RNAME_MAX, rname_legal, "genome name", nullptr, &sorted)) return rc;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   if (int rc = sync_check(e, "bineval reset")) return rc;
   h->planned = false;
   h->read_holds = false;
   h->reset_once = false;
-  h->sp.invalidate_from(0);
-  h->open = false;
   h->sort_sp.invalidate_from(0);
-  h->done_ms = 0.f;
-  if (int rc = h->sp.create_missing(e)) return rc;
+  if (int rc = h->sp.reset(e)) return rc;
   if (int rc = h->sort_sp.create_missing(e)) return rc;
-  if (!h->blob.ensure(blob.size()) || !h->name_off.ensure(off.size() * 4) || !h->cursor.ensure(16) || !h->unknown.ensure(8) ||
+  if (!h->genomes.room(sorted) || !h->cursor.ensure(16) || !h->unknown.ensure(8) ||
       !h->counts.ensure(BC_COUNT * 8) || !h->word.ensure(16))
     return eng_fail(e, SIMMR_ENOMEM, "bineval reset: allocation failed");
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipMemcpyAsync(h->blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  HIP_TRY(e, hipMemcpyAsync(h->name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+  if (int rc = h->genomes.upload(e, sorted, st)) return rc;
   HIP_TRY(e, hipMemsetAsync(h->cursor.p, 0, 16, st));
   HIP_TRY(e, hipMemsetAsync(h->unknown.p, 0, 8, st));
   HIP_TRY(e, hipMemsetAsync(h->counts.p, 0, BC_COUNT * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->word.p, 0, 16, st));
   if (int rc = sync_check(e, "bineval reset")) return rc;  // (the uploads read host vectors that end here)
-  h->n_genomes = (uint32_t)names.size();
+  h->n_genomes = cfg->n_genomes;
   h->hash_bits = cfg->hash_bits;
   h->row_cap = h->pool_cap = 0;
   h->n_truth = h->n_records = h->n_bpool = h->n_bins = h->n_cells = 0;
@@ -273,7 +175,7 @@ int simmr_bineval_reset(simmr_bineval* h, const simmr_bineval_config* cfg) {
 int simmr_bineval_truth_add(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_bineval_truth_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_bineval_truth_add")) return rc;
   h->planned = false;
   h->read_holds = false;
   if (n_bytes == 0) return SIMMR_OK;
@@ -286,7 +188,7 @@ int simmr_bineval_truth_add(simmr_bineval* h, const uint8_t* text, uint64_t n_by
     return eng_fail(e, SIMMR_ENOMEM, "bineval truth: allocation failed for %llu contigs", (unsigned long long)rows);
   h->row_cap = rows;
   h->pool_cap = bytes;
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   uint64_t line_cap = 0;
   if (int rc = enqueue_front(h, text, n_bytes, st, &W, &line_cap)) return rc;
@@ -300,7 +202,7 @@ int simmr_bineval_truth_add(simmr_bineval* h, const uint8_t* text, uint64_t n_by
                      (const BinTot*)tot, h->truth_names(), h->t_length.as<uint64_t>(), h->rec_field.as<uint32_t>());
   hipLaunchKernelGGL(k_bin_genomes, dim3(grid_for(e, line_cap, BIN_WG_RECS, WGS_PER_CU)), dim3(BIN_WG), 0, st, W, (const BinTot*)tot, h->rec_field.as<const uint32_t>(),
                      h->names(), h->t_genome.as<uint32_t>(), h->row_cap, h->word.as<uint32_t>());
-  return end_span(h, SPAN_ADDS, st, "bineval truth add");
+  return h->sp.end(e, SPAN_ADDS, st, "bineval truth add");
 }
 
 int simmr_bineval_truth_plan(simmr_bineval* h, uint64_t* n_contigs) {
@@ -316,14 +218,14 @@ int simmr_bineval_truth_plan(simmr_bineval* h, uint64_t* n_contigs) {
   HIP_TRY(e, hipMemcpyAsync(&cur, h->cursor.p, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "bineval truth adds")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "bineval")) return rc;
   if (errw & BIN_ERR_TRUTH) return malformed(h, BIN_ERR_TRUTH);
   const uint64_t n = std::min(cur, h->row_cap);
   if (n >= (1ull << 31)) return eng_fail(e, SIMMR_ERANGE, "simmr_bineval_truth_plan takes fewer than 2^31 truth contigs (%llu given)", (unsigned long long)n);
   const uint64_t n1 = std::max<uint64_t>(n, 1);
-  if (!h->key[0].ensure(n1 * 8) || !sort_room(h, &h->key[1], h->idx, n1) || !h->t_first.ensure(n1 * 4) || !h->t_records.ensure(n1 * 4) || !h->t_bin.ensure(n1 * 4))
+  if (!h->truth_sort.room(n1) || !h->head.ensure(n1 * 4) || !h->before.ensure((n1 + 1) * 8) || !h->t_first.ensure(n1 * 4) || !h->t_records.ensure(n1 * 4) || !h->t_bin.ensure(n1 * 4))
     return eng_fail(e, SIMMR_ENOMEM, "bineval truth plan: allocation failed (%llu contigs)", (unsigned long long)n);
-  if (int rc = begin_span(h, SPAN_PLAN, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_PLAN, st)) return rc;
   // the candidate side starts over
   HIP_TRY(e, hipMemsetAsync(h->unknown.p, 0, 8, st));
   HIP_TRY(e, hipMemsetAsync(h->t_first.p, 0xff, n1 * 4, st));
@@ -331,20 +233,20 @@ int simmr_bineval_truth_plan(simmr_bineval* h, uint64_t* n_contigs) {
   HIP_TRY(e, hipMemsetAsync(h->word.p, 0, 4, st));  // (the truth is well-formed here; a duplicate is looked for below)
   h->n_records = h->n_bpool = h->n_bins = h->n_cells = 0;
   h->n_truth = n;
-  h->side = 0;
+  h->truth_order = PairSort::Sorted{h->truth_sort.key[0].as<const uint64_t>(), h->truth_sort.idx[0].as<const uint32_t>()};
   h->sort_sp.invalidate_from(0);
   if (n > 0) {
-    hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, h->t_hash.as<const uint64_t>(), h->mask(), n, h->key[0].as<uint64_t>());
+    hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, h->t_hash.as<const uint64_t>(), h->mask(), n, h->truth_sort.key[0].as<uint64_t>());
     HIP_TRY(e, h->sort_sp.begin(0, st));
-    h->side = sort_by(h, st, h->key, h->idx, n, h->hash_bits);
+    h->truth_order = sort_by(h, st, &h->truth_sort, n, h->hash_bits);
     HIP_TRY(e, h->sort_sp.end(0, st));
     h->sort_sp.mark(0);
     hipLaunchKernelGGL(k_bin_truth_dups, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, h->index(), h->word.as<uint32_t>());
   }
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
-  if (int rc = end_span(h, SPAN_PLAN, st, "bineval truth plan")) return rc;
+  if (int rc = h->sp.end(e, SPAN_PLAN, st, "bineval truth plan")) return rc;
   if (int rc = sync_check(e, "bineval truth plan")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "bineval")) return rc;
   if (errw & BIN_ERR_DUP) return malformed(h, BIN_ERR_DUP);
   h->planned = true;
   if (n_contigs) *n_contigs = n;
@@ -354,12 +256,12 @@ int simmr_bineval_truth_plan(simmr_bineval* h, uint64_t* n_contigs) {
 int simmr_bineval_add(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_bineval_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_bineval_add")) return rc;
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_bineval_add called without a simmr_bineval_truth_plan in force");
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   uint64_t line_cap = 0;
   if (int rc = enqueue_front(h, text, n_bytes, st, &W, &line_cap)) return rc;
@@ -374,13 +276,13 @@ int simmr_bineval_add(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes) {
   if (int rc = sync_check(e, "bineval add")) return rc;
   const uint64_t held = h->n_records, want = held + got.records, bytes = h->n_bpool + got.bytes;
   if (want >= (1ull << 31)) {
-    (void)end_span(h, SPAN_ADDS, st, "bineval add");  // (the front of the refused add has run: the span closes behind it)
+    (void)h->sp.end(e, SPAN_ADDS, st, "bineval add");  // (the front of the refused add has run: the span closes behind it)
     return eng_fail(e, SIMMR_ERANGE, "simmr_bineval_add takes fewer than 2^31 records since the plan (%llu given)", (unsigned long long)want);
   }
   if (!h->b_pool.grow_keep(std::max<uint64_t>(bytes, 1), h->n_bpool, st) || !h->b_off.grow_keep(want * 8 + 8, held * 8, st) ||
       !h->b_len.grow_keep(want * 4 + 4, held * 4, st) || !h->b_hash.grow_keep(want * 8 + 8, held * 8, st) || !h->r_contig.grow_keep(want * 4 + 4, held * 4, st))
   {
-    (void)end_span(h, SPAN_ADDS, st, "bineval add");
+    (void)h->sp.end(e, SPAN_ADDS, st, "bineval add");
     return eng_fail(e, SIMMR_ENOMEM, "bineval add: allocation failed (%llu records)", (unsigned long long)want);
   }
   h->read_holds = false;
@@ -390,7 +292,7 @@ int simmr_bineval_add(simmr_bineval* h, const uint8_t* text, uint64_t n_bytes) {
                        h->t_records.as<uint32_t>(), h->unknown.as<unsigned long long>());
   h->n_records = want;
   h->n_bpool = bytes;
-  return end_span(h, SPAN_ADDS, st, "bineval add");
+  return h->sp.end(e, SPAN_ADDS, st, "bineval add");
 }
 
 int simmr_bineval_read(simmr_bineval* h, simmr_bineval_counts* counts, uint64_t* by_genome_host) {
@@ -403,20 +305,20 @@ int simmr_bineval_read(simmr_bineval* h, simmr_bineval_counts* counts, uint64_t*
   h->read_holds = false;
   const uint64_t n = h->n_records, nt = h->n_truth, rows = (uint64_t)h->n_genomes + 1, table_words = rows * BIN_GENOME_COLS;
   if (!h->g_table.ensure(table_words * 8) || !h->best_bin.ensure(rows * 4)) return eng_fail(e, SIMMR_ENOMEM, "bineval read: allocation failed");
-  if (int rc = fold_spans(h)) return rc;  // (the adds' span ends here)
-  if (int rc = begin_span(h, SPAN_READ, st)) return rc;
+  if (int rc = h->sp.fold(e, "bineval")) return rc;  // (the adds' span ends here)
+  if (int rc = h->sp.begin(e, SPAN_READ, st)) return rc;
   HIP_TRY(e, hipMemsetAsync(h->counts.p, 0, BC_COUNT * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->g_table.p, 0, table_words * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->best_bin.p, 0xff, rows * 4, st));
   // the bin rows
   uint64_t n_bins = 0;
   if (n > 0) {
-    if (!h->r_key[0].ensure(n * 8) || !sort_room(h, &h->r_key[1], h->r_idx, n) || !h->rep.ensure(n * 4) || !h->flag.ensure(n * 4) || !h->rec_bin.ensure(n * 4))
+    if (!h->rec_sort.room(n) || !h->head.ensure(n * 4) || !h->before.ensure((n + 1) * 8) || !h->rep.ensure(n * 4) || !h->flag.ensure(n * 4) || !h->rec_bin.ensure(n * 4))
       return eng_fail(e, SIMMR_ENOMEM, "bineval read: allocation failed (%llu records)", (unsigned long long)n);
-    hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, h->b_hash.as<const uint64_t>(), h->mask(), n, h->r_key[0].as<uint64_t>());
+    hipLaunchKernelGGL(k_bin_keys, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, h->b_hash.as<const uint64_t>(), h->mask(), n, h->rec_sort.key[0].as<uint64_t>());
     HIP_TRY(e, hipMemsetAsync(h->flag.p, 0, n * 4, st));
-    const int side = sort_by(h, st, h->r_key, h->r_idx, n, h->hash_bits);
-    hipLaunchKernelGGL(k_bin_reps, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, h->r_key[side].as<const uint64_t>(), h->r_idx[side].as<const uint32_t>(),
+    const PairSort::Sorted by_hash = sort_by(h, st, &h->rec_sort, n, h->hash_bits);
+    hipLaunchKernelGGL(k_bin_reps, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, by_hash.keys, by_hash.perm,
                        h->r_contig.as<const uint32_t>(), h->bin_names(n, h->n_bpool), n, h->rep.as<uint32_t>(), h->flag.as<uint32_t>());
     if (int rc = eng_scan_u32(e, h->flag.as<const uint32_t>(), n, h->before.as<uint64_t>(), &n_bins)) return rc;  // (synchronises)
   }
@@ -435,15 +337,15 @@ int simmr_bineval_read(simmr_bineval* h, simmr_bineval_counts* counts, uint64_t*
                        h->rec_bin.as<uint32_t>(), h->q_first.as<uint32_t>());
   // the cells
   uint64_t n_cells = 0;
-  int cside = 0;
+  PairSort::Sorted by_cell{};
   if (nt > 0) {
-    if (!h->c_key[0].ensure(nt * 8) || !sort_room(h, &h->c_key[1], h->c_idx, nt))
+    if (!h->cell_sort.room(nt) || !h->head.ensure(nt * 4) || !h->before.ensure((nt + 1) * 8))
       return eng_fail(e, SIMMR_ENOMEM, "bineval read: allocation failed (%llu contigs)", (unsigned long long)nt);
     const uint32_t grid = grid_for(e, nt, 256, WGS_PER_CU);
     hipLaunchKernelGGL(k_bin_assign, dim3(grid), dim3(256), 0, st, h->t_first.as<const uint32_t>(), h->t_genome.as<const uint32_t>(),
-                       h->rec_bin.as<const uint32_t>(), nt, n, (uint32_t)n_bins, h->c_key[0].as<uint64_t>(), h->t_bin.as<uint32_t>());
-    cside = sort_by(h, st, h->c_key, h->c_idx, nt, BIN_GENOME_BITS + bits_of(n_bins));
-    hipLaunchKernelGGL(k_bin_cell_heads, dim3(grid), dim3(256), 0, st, h->c_key[cside].as<const uint64_t>(), nt, (uint32_t)n_bins, h->head.as<uint32_t>());
+                       h->rec_bin.as<const uint32_t>(), nt, n, (uint32_t)n_bins, h->cell_sort.key[0].as<uint64_t>(), h->t_bin.as<uint32_t>());
+    by_cell = sort_by(h, st, &h->cell_sort, nt, BIN_GENOME_BITS + bits_of(n_bins));
+    hipLaunchKernelGGL(k_bin_cell_heads, dim3(grid), dim3(256), 0, st, by_cell.keys, nt, (uint32_t)n_bins, h->head.as<uint32_t>());
     if (int rc = eng_scan_u32(e, h->head.as<const uint32_t>(), nt, h->before.as<uint64_t>(), &n_cells)) return rc;  // (synchronises)
   }
   const uint64_t nc1 = std::max<uint64_t>(n_cells, 1);
@@ -454,7 +356,7 @@ int simmr_bineval_read(simmr_bineval* h, simmr_bineval_counts* counts, uint64_t*
   if (nt > 0) {
     const uint32_t grid = grid_for(e, nt, 256, WGS_PER_CU);
     if (n_cells > 0)
-      hipLaunchKernelGGL(k_bin_cell_sum, dim3(grid), dim3(256), 0, st, h->c_key[cside].as<const uint64_t>(), h->c_idx[cside].as<const uint32_t>(),
+      hipLaunchKernelGGL(k_bin_cell_sum, dim3(grid), dim3(256), 0, st, by_cell.keys, by_cell.perm,
                          h->t_length.as<const uint64_t>(), h->before.as<const uint64_t>(), nt, (uint32_t)n_bins, n_cells, h->cells());
     hipLaunchKernelGGL(k_bin_truth_rows, dim3(grid), dim3(256), 0, st, h->t_genome.as<const uint32_t>(), h->t_length.as<const uint64_t>(),
                        h->t_first.as<const uint32_t>(), h->t_records.as<const uint32_t>(), nt, h->n_genomes, h->g_table.as<unsigned long long>(), h->counts_p());
@@ -473,9 +375,9 @@ int simmr_bineval_read(simmr_bineval* h, simmr_bineval_counts* counts, uint64_t*
   HIP_TRY(e, hipMemcpyAsync(table.data(), h->g_table.p, table_words * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&unknown, h->unknown.p, 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
-  if (int rc = end_span(h, SPAN_READ, st, "bineval read")) return rc;
+  if (int rc = h->sp.end(e, SPAN_READ, st, "bineval read")) return rc;
   if (int rc = sync_check(e, "bineval read")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "bineval")) return rc;
   if (errw) return malformed(h, errw);
   h->n_bins = n_bins;
   h->n_cells = n_cells;
@@ -549,8 +451,7 @@ int simmr_last_bineval_ms(simmr_bineval* h, float* ms, float* plan_sort_ms) {
   if (!ms) return eng_fail(e, SIMMR_EINVAL, "simmr_last_bineval_ms: NULL ms");
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_bineval_reset yet");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = fold_spans(h)) return rc;  // (the next add of either side begins a new span)
-  *ms = h->done_ms;
+  if (int rc = h->sp.last_ms(e, "bineval", ms)) return rc;
   if (plan_sort_ms)
     if (int rc = h->sort_sp.total_ms(e, "bineval", plan_sort_ms)) return rc;
   return SIMMR_OK;

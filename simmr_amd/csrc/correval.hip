@@ -1,7 +1,5 @@
 // correval.hip — a read error corrector's output scored against the true reads (include/simmr_hip.h: simmr_correval_*): the entry
-// points over correval_kernels.hip.  A translation unit of libsimmr_hip.so of its own; it sees an engine through engine_internal.hpp
-// only.  The engine's slot enum is full, so the state lives in an object of its own that the caller creates on an engine and
-// destroys before the engine, as mapeval.hip's does.  The sort is sam_sort.hip's (samsort_sort_pairs).
+// points over correval_kernels.hip, on the scaffold of scorer_host.hpp.
 //
 // truth_add:  enqueue-only, so nothing is sized from what the text holds.  The index buffers are sized from n_bytes (a line start
 //             per two bytes), the entry columns and the two planes from the bytes of every truth add since the reset (an entry per
@@ -11,23 +9,20 @@
 //             gathers the columns into key order and checks the neighbours; empties the corrected side.
 // add:        lines (count) -> scan -> lines (write) -> score.  A line start per byte: every '\n' ends a line.
 // read:       the reduce over the entries, the table to the host, by_pos's kept column from the histogram of the compared lengths.
-// Time: three spans, as bineval.hip keeps them: the adds of either side are one span from the first add's begin to the last one's
-// end, folded into a sum by a call that synchronises anyway; the plan and the read have spans of their own.
+// Time: the adds' span, the plan's and the read's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "host_support.hpp"
 #include "correval_kernels.hip"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
 namespace {
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 // Workgroups a CU of every grid: beyond them the workgroups loop.  Small, so that a text of a few hundred KB takes every kernel past one trip.
 constexpr uint32_t WGS_PER_CU = 2;
@@ -47,10 +42,10 @@ const char* const MALFORMED_READS =
 struct simmr_correval {
   simmr_engine* e = nullptr;
   uint32_t lpr = 4;
-  // the line index of one add
-  DevBuf tile_sum, tile_prefix, starts;
-  // the truth: the entries as appended (u_*), and in key order (s_*, with the sorted keys in key[cur]); the planes
-  DevBuf u_key, u_len, u_off, u_before, s_len, s_off, s_before, key[2], idx[2], hist, digit_total;
+  LineIndex index;  // of one add
+  // the truth: the entries as appended (u_*), and in key order (s_*, with the sorted keys in skey); the planes
+  DevBuf u_key, u_len, u_off, u_before, s_len, s_off, s_before;
+  PairSort order;
   DevBuf plane_ot, plane_q;
   DevBuf cursor;   // [0] entries, [1] the largest key, [2] plane bytes
   DevBuf table;    // CT_WORDS words
@@ -60,9 +55,7 @@ struct simmr_correval {
   uint64_t entry_cap = 0, plane_cap = 0;   // what the truth adds since the reset may have appended
   uint64_t n_entries = 0;
   bool reset_once = false, planned = false;
-  Spans<SPAN_COUNT> sp;
-  bool open = false;  // the span of the adds has begun and is not folded yet
-  float done_ms = 0.f;
+  FoldedSpans<SPAN_COUNT> sp;
 
   unsigned long long* table_p() const { return table.as<unsigned long long>(); }
   CevEntries appended() const { return CevEntries{u_key.as<uint64_t>(), u_len.as<uint32_t>(), u_off.as<uint64_t>(), u_before.as<uint32_t>()}; }
@@ -72,66 +65,17 @@ struct simmr_correval {
 
 namespace {
 
-int check_text(simmr_correval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
-  simmr_engine* e = h->e;
-  if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "%s called before simmr_correval_reset", who);
-  if (!text && n_bytes > 0) return eng_fail(e, SIMMR_EINVAL, "%s: NULL text", who);
-  if (n_bytes > SIMMR_FIT_SAM_MAX_BYTES)
-    return eng_fail(e, SIMMR_ENOTSUP, "%s: %llu bytes in one add (at most %llu: cut the text at a line's or a record's end)", who,
-                    (unsigned long long)n_bytes, (unsigned long long)SIMMR_FIT_SAM_MAX_BYTES);
-  return SIMMR_OK;
-}
-
-int begin_span(simmr_correval* h, int which, hipStream_t st) {
-  if (which == SPAN_ADDS && h->open) return SIMMR_OK;
-  HIP_TRY(h->e, h->sp.begin(which, st));
-  return SIMMR_OK;
-}
-
-// the spans that count into the sum, and closed.  Synchronises.
-int fold_spans(simmr_correval* h) {
-  float now = 0.f;
-  if (int rc = h->sp.total_ms(h->e, "correval", &now)) return rc;
-  h->done_ms += now;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  return SIMMR_OK;
-}
-
-int end_span(simmr_correval* h, int which, hipStream_t st, const char* what) {
-  simmr_engine* e = h->e;
-  hipError_t rc = hipGetLastError();
-  if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s launch failed: %s", what, hipGetErrorString(rc));
-  HIP_TRY(e, h->sp.end(which, st));
-  if (which == SPAN_ADDS) h->open = true;
-  h->sp.mark(which);
-  return SIMMR_OK;
-}
-
-uint32_t grid_for(simmr_engine* e, uint64_t items, uint32_t per_wg) {
-  const uint64_t cus = (uint64_t)std::max(eng_cu_count(e), 1);
-  return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((items + per_wg - 1) / per_wg, cus * WGS_PER_CU));
+int check_add(simmr_correval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
+  return check_add_text(h->e, h->reset_once, text, n_bytes, SIMMR_FIT_SAM_MAX_BYTES, who, "simmr_correval_reset", "cut the text at a line's or a record's end");
 }
 
 // the line index of text[0, n_bytes) into the object's buffers (n_bytes > 0): the SAM rule (empty lines never enter it), or every line
 int enqueue_index(simmr_correval* h, const uint8_t* text, uint64_t n_bytes, bool every_line, hipStream_t st, MevText* W) {
   simmr_engine* e = h->e;
   const uint64_t n_tiles = (n_bytes + CEV_TILE - 1) / CEV_TILE, start_cap = every_line ? n_bytes : n_bytes / 2 + 1;
-  if (!h->tile_sum.ensure(n_tiles * 8) || !h->tile_prefix.ensure((n_tiles + 1) * 8) || !h->starts.ensure(start_cap * 4))
+  if (!h->index.room(n_tiles, start_cap))
     return eng_fail(e, SIMMR_ENOMEM, "correval line index: allocation failed for %llu bytes of text", (unsigned long long)n_bytes);
-  const uint32_t tile_grid = grid_for(e, n_tiles, 1);
-  uint64_t* const sum = h->tile_sum.as<uint64_t>();
-  uint64_t* const prefix = h->tile_prefix.as<uint64_t>();
-  if (every_line) {
-    hipLaunchKernelGGL(k_cev_lines, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, sum, (const uint64_t*)nullptr, (uint32_t*)nullptr, 0ull);
-    hipLaunchKernelGGL(k_cev_scan, dim3(1), dim3(256), 0, st, (const uint64_t*)sum, prefix, n_tiles);
-    hipLaunchKernelGGL(k_cev_lines, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, sum, (const uint64_t*)prefix, h->starts.as<uint32_t>(), start_cap);
-  } else {
-    hipLaunchKernelGGL(k_cev_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, sum, (const uint64_t*)nullptr, (uint32_t*)nullptr, 0ull);
-    hipLaunchKernelGGL(k_cev_scan, dim3(1), dim3(256), 0, st, (const uint64_t*)sum, prefix, n_tiles);
-    hipLaunchKernelGGL(k_cev_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, sum, (const uint64_t*)prefix, h->starts.as<uint32_t>(), start_cap);
-  }
-  *W = MevText{text, n_bytes, h->tile_prefix.as<const uint64_t>() + n_tiles, h->starts.as<const uint32_t>()};
+  h->index.enqueue(st, every_line ? k_cev_lines : k_cev_index, k_cev_scan, text, n_bytes, CEV_TILE, grid_for(e, n_tiles, 1, WGS_PER_CU), start_cap, W);
   return SIMMR_OK;
 }
 
@@ -147,23 +91,9 @@ int malformed(simmr_correval* h, uint32_t errw) {
 
 extern "C" {
 
-int simmr_correval_create(simmr_engine* e, simmr_correval** out) {
-  if (!e) return SIMMR_EINVAL;
-  if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_correval_create: NULL out");
-  *out = nullptr;
-  simmr_correval* h = new (std::nothrow) simmr_correval();
-  if (!h) return eng_fail(e, SIMMR_ENOMEM, "simmr_correval_create: out of memory");
-  h->e = e;
-  *out = h;
-  return SIMMR_OK;
-}
+int simmr_correval_create(simmr_engine* e, simmr_correval** out) { return scorer_create(e, out, "simmr_correval_create"); }
 
-void simmr_correval_destroy(simmr_correval* h) {
-  if (!h) return;
-  if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  delete h;  // (its buffers and events go with it)
-  (void)hipGetLastError();
-}
+void simmr_correval_destroy(simmr_correval* h) { scorer_destroy(h); }
 
 int simmr_correval_reset(simmr_correval* h, const simmr_correval_config* cfg) {
   if (!h) return SIMMR_EINVAL;
@@ -175,10 +105,7 @@ int simmr_correval_reset(simmr_correval* h, const simmr_correval_config* cfg) {
   if (int rc = sync_check(e, "correval reset")) return rc;
   h->planned = false;
   h->reset_once = false;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  h->done_ms = 0.f;
-  if (int rc = h->sp.create_missing(e)) return rc;
+  if (int rc = h->sp.reset(e)) return rc;
   if (!h->cursor.ensure(32) || !h->table.ensure(CT_WORDS * 8) || !h->word.ensure(16)) return eng_fail(e, SIMMR_ENOMEM, "correval reset: allocation failed");
   hipStream_t st = eng_stream(e);
   HIP_TRY(e, hipMemsetAsync(h->cursor.p, 0, 32, st));
@@ -195,7 +122,7 @@ int simmr_correval_reset(simmr_correval* h, const simmr_correval_config* cfg) {
 int simmr_correval_truth_add(simmr_correval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_correval_truth_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_correval_truth_add")) return rc;
   h->planned = false;
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
@@ -206,13 +133,13 @@ int simmr_correval_truth_add(simmr_correval* h, const uint8_t* text, uint64_t n_
     return eng_fail(e, SIMMR_ENOMEM, "correval truth: allocation failed for %llu entries and %llu bases", (unsigned long long)cap, (unsigned long long)bytes);
   h->entry_cap = cap;
   h->plane_cap = bytes;
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   if (int rc = enqueue_index(h, text, n_bytes, false, st, &W)) return rc;
-  const uint32_t grid = grid_for(e, n_bytes / CEV_MIN_LINE + 1, CEV_WG_RECS);
+  const uint32_t grid = grid_for(e, n_bytes / CEV_MIN_LINE + 1, CEV_WG_RECS, WGS_PER_CU);
   hipLaunchKernelGGL(k_cev_truth, dim3(grid), dim3(CEV_WG), 0, st, W, h->appended(), cap, h->planes(), h->cursor.as<unsigned long long>(), h->table_p(),
                      h->word.as<uint32_t>());
-  return end_span(h, SPAN_ADDS, st, "correval truth add");
+  return h->sp.end(e, SPAN_ADDS, st, "correval truth add");
 }
 
 int simmr_correval_truth_plan(simmr_correval* h, uint64_t* n_entries) {
@@ -227,37 +154,30 @@ int simmr_correval_truth_plan(simmr_correval* h, uint64_t* n_entries) {
   HIP_TRY(e, hipMemcpyAsync(cur3, h->cursor.p, 24, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "correval truth adds")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "correval")) return rc;
   if (errw & CEV_ERR_TRUTH) return malformed(h, CEV_ERR_TRUTH);
   const uint64_t n = std::min(cur3[0], h->entry_cap);
   if (n >= (1ull << 31)) return eng_fail(e, SIMMR_ERANGE, "simmr_correval_truth_plan takes fewer than 2^31 truth entries (%llu given)", (unsigned long long)n);
-  const uint64_t n1 = std::max<uint64_t>(n, 1), n_tiles = (n + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
-  for (DevBuf* b : {&h->key[0], &h->key[1], &h->s_off})
-    if (!b->ensure(n1 * 8)) return eng_fail(e, SIMMR_ENOMEM, "correval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
-  for (DevBuf* b : {&h->idx[0], &h->idx[1], &h->s_len, &h->s_before, &h->residual, &h->hits})
-    if (!b->ensure(n1 * 4)) return eng_fail(e, SIMMR_ENOMEM, "correval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
-  if (!h->hist.ensure(std::max<uint64_t>(n_tiles, 1) * SAMSORT_PAIRS_DIGITS * 4) || !h->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4))
-    return eng_fail(e, SIMMR_ENOMEM, "correval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
-  if (int rc = begin_span(h, SPAN_PLAN, st)) return rc;
+  const uint64_t n1 = std::max<uint64_t>(n, 1);
+  bool room = h->order.room(n1) && h->s_off.ensure(n1 * 8);
+  for (DevBuf* b : {&h->s_len, &h->s_before, &h->residual, &h->hits}) room = room && b->ensure(n1 * 4);
+  if (!room) return eng_fail(e, SIMMR_ENOMEM, "correval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
+  if (int rc = h->sp.begin(e, SPAN_PLAN, st)) return rc;
   // the corrected side starts over: its counts (the words behind the truth's five), the tables, residual and hits
   HIP_TRY(e, hipMemsetAsync(h->table_p() + CC_LINES, 0, (CT_WORDS - CC_LINES) * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->residual.p, 0xff, n1 * 4, st));
   HIP_TRY(e, hipMemsetAsync(h->hits.p, 0, n1 * 4, st));
-  h->skey = h->key[0].as<const uint64_t>();
+  h->skey = h->order.key[0].as<const uint64_t>();
   if (n > 0) {
-    HIP_TRY(e, hipMemcpyAsync(h->key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
-    uint64_t* const keys[2] = {h->key[0].as<uint64_t>(), h->key[1].as<uint64_t>()};
-    uint32_t* const idxs[2] = {h->idx[0].as<uint32_t>(), h->idx[1].as<uint32_t>()};
-    const uint32_t key_bits = bits_of(cur3[1]);
-    const int cur = samsort_sort_pairs(st, keys, idxs, h->hist.as<uint32_t>(), h->digit_total.as<uint32_t>(), n, key_bits);
-    h->skey = h->key[cur].as<const uint64_t>();
-    hipLaunchKernelGGL(k_cev_gather, dim3(grid_for(e, n, 256)), dim3(256), 0, st, h->skey,
-                       key_bits > 0u ? h->idx[cur].as<const uint32_t>() : (const uint32_t*)nullptr, h->appended(), h->sorted(), n, h->word.as<uint32_t>());
+    HIP_TRY(e, hipMemcpyAsync(h->order.key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
+    const PairSort::Sorted by_key = h->order.sort(st, n, bits_of(cur3[1]));
+    h->skey = by_key.keys;
+    hipLaunchKernelGGL(k_cev_gather, dim3(grid_for(e, n, 256, WGS_PER_CU)), dim3(256), 0, st, h->skey, by_key.perm, h->appended(), h->sorted(), n, h->word.as<uint32_t>());
   }
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
-  if (int rc = end_span(h, SPAN_PLAN, st, "correval truth plan")) return rc;
+  if (int rc = h->sp.end(e, SPAN_PLAN, st, "correval truth plan")) return rc;
   if (int rc = sync_check(e, "correval truth plan")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "correval")) return rc;
   if (errw & CEV_ERR_DUP) {
     uint32_t cleared = errw & ~CEV_ERR_DUP;  // (the entries stay; the flag is the plan's alone)
     HIP_TRY(e, hipMemcpy(h->word.p, &cleared, 4, hipMemcpyHostToDevice));
@@ -272,19 +192,19 @@ int simmr_correval_truth_plan(simmr_correval* h, uint64_t* n_entries) {
 int simmr_correval_add(simmr_correval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_correval_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_correval_add")) return rc;
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_correval_add called without a simmr_correval_truth_plan in force");
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   if (int rc = enqueue_index(h, text, n_bytes, true, st, &W)) return rc;
   // a record is at least its lines' ends: lines_per_record bytes
-  const uint32_t grid = grid_for(e, n_bytes / h->lpr + 1, CEV_WG_RECS);
+  const uint32_t grid = grid_for(e, n_bytes / h->lpr + 1, CEV_WG_RECS, WGS_PER_CU);
   hipLaunchKernelGGL(k_cev_score, dim3(grid), dim3(CEV_WG), 0, st, W, h->lpr, h->skey, h->sorted(), h->n_entries, h->planes(), h->table_p(),
                      h->residual.as<uint32_t>(), h->hits.as<uint32_t>(), h->word.as<uint32_t>());
-  return end_span(h, SPAN_ADDS, st, "correval add");
+  return h->sp.end(e, SPAN_ADDS, st, "correval add");
 }
 
 int simmr_correval_read(simmr_correval* h, simmr_correval_counts* counts, uint64_t* cube_host, uint64_t* by_qual_host, uint64_t* by_pos_host) {
@@ -293,19 +213,19 @@ int simmr_correval_read(simmr_correval* h, simmr_correval_counts* counts, uint64
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "simmr_correval_read called before simmr_correval_reset");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  if (int rc = fold_spans(h)) return rc;  // (the adds' span ends here)
-  if (int rc = begin_span(h, SPAN_READ, st)) return rc;
+  if (int rc = h->sp.fold(e, "correval")) return rc;  // (the adds' span ends here)
+  if (int rc = h->sp.begin(e, SPAN_READ, st)) return rc;
   HIP_TRY(e, hipMemsetAsync(h->table_p() + CC_MISSING, 0, 8 * 8, st));
   if (h->planned && h->n_entries > 0)
-    hipLaunchKernelGGL(k_cev_reduce, dim3(grid_for(e, h->n_entries, 256)), dim3(256), 0, st, h->hits.as<const uint32_t>(), h->residual.as<const uint32_t>(),
+    hipLaunchKernelGGL(k_cev_reduce, dim3(grid_for(e, h->n_entries, 256, WGS_PER_CU)), dim3(256), 0, st, h->hits.as<const uint32_t>(), h->residual.as<const uint32_t>(),
                        h->s_before.as<const uint32_t>(), h->n_entries, h->table_p());
   std::vector<uint64_t> host(CT_WORDS);
   uint32_t errw = 0;
   HIP_TRY(e, hipMemcpyAsync(host.data(), h->table.p, CT_WORDS * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
-  if (int rc = end_span(h, SPAN_READ, st, "correval read")) return rc;
+  if (int rc = h->sp.end(e, SPAN_READ, st, "correval read")) return rc;
   if (int rc = sync_check(e, "correval read")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "correval")) return rc;
   if (errw & (CEV_ERR_TRUTH | CEV_ERR_READS)) return malformed(h, errw & (CEV_ERR_TRUTH | CEV_ERR_READS));
   if (counts) std::memcpy(counts, host.data(), sizeof(*counts));
   if (cube_host) std::memcpy(cube_host, host.data() + CT_CUBE, 125 * 8);
@@ -350,9 +270,7 @@ int simmr_last_correval_ms(simmr_correval* h, float* ms) {
   if (!ms) return eng_fail(e, SIMMR_EINVAL, "simmr_last_correval_ms: NULL ms");
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_correval_reset yet");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = fold_spans(h)) return rc;  // (the next add of either side begins a new span)
-  *ms = h->done_ms;
-  return SIMMR_OK;
+  return h->sp.last_ms(e, "correval", ms);
 }
 
 }  // extern "C"

@@ -1,7 +1,6 @@
 // mapeval.hip — an aligner's SAM scored against the true alignments (include/simmr_hip.h: simmr_mapeval_*): the entry points over
-// mapeval_kernels.hip.  A translation unit of libsimmr_hip.so of its own; it sees an engine through engine_internal.hpp only.  The
-// engine's slot enum is full, so the state lives in an object of its own that the caller creates on an engine and destroys before
-// the engine, as bam_index.hip's does.  The sort is sam_sort.hip's (samsort_sort_pairs).
+// mapeval_kernels.hip, on the scaffold of scorer_host.hpp (the object, the text check, the line index, the names, the pair sort).
+// Its time is its own: a growing list of spans, one per call, so that the sum is the calls' alone.
 //
 // truth_add:  enqueue-only, so nothing is sized from what the text holds.  The index buffers are sized from n_bytes (a line start
 //             per two bytes), the entry columns from the bytes of every truth add since the reset (an entry per MEV_MIN_LINE
@@ -13,19 +12,16 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
-#include <string>
 #include <utility>
 #include <vector>
 
 #include "mapeval_kernels.hip"
 #include "sam_names.hpp"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
 namespace {
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 struct Span { hipEvent_t a = nullptr, b = nullptr; };
 
@@ -33,13 +29,12 @@ struct Span { hipEvent_t a = nullptr, b = nullptr; };
 
 struct simmr_mapeval {
   simmr_engine* e = nullptr;
-  // the names
-  DevBuf blob, name_off;
+  DeviceNames rnames;
   uint32_t n_names = 0, min_pct = 10;
-  // the line index of one add
-  DevBuf tile_sum, tile_prefix, starts;
-  // the truth: the entries as appended (u_*), and in key order (s_*, with the sorted keys in key[cur])
-  DevBuf u_key, u_meta, u_lo, u_hi, s_meta, s_lo, s_hi, key[2], idx[2], hist, digit_total;
+  LineIndex index;  // of one add
+  // the truth: the entries as appended (u_*), and in key order (s_*, with the sorted keys in skey)
+  DevBuf u_key, u_meta, u_lo, u_hi, s_meta, s_lo, s_hi;
+  PairSort order;
   DevBuf cursor;   // [0] entries, [1] the largest key
   DevBuf counts;   // MC_COUNT words, then by_mapq's 512
   DevBuf word;     // the error word
@@ -51,7 +46,7 @@ struct simmr_mapeval {
   std::vector<Span> spans;
   float done_ms = 0.f;
 
-  MevNames names() const { return MevNames{blob.as<const uint8_t>(), name_off.as<const uint32_t>(), n_names}; }
+  MevNames names() const { return rnames.names(n_names); }
   unsigned long long* counts_p() const { return counts.as<unsigned long long>(); }
   void drop_spans() {
     for (Span& s : spans) {
@@ -92,31 +87,19 @@ int begin_span(simmr_mapeval* h, hipStream_t st) {
   return SIMMR_OK;
 }
 
-int check_text(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
-  simmr_engine* e = h->e;
-  if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "%s called before simmr_mapeval_reset", who);
-  if (!text && n_bytes > 0) return eng_fail(e, SIMMR_EINVAL, "%s: NULL text", who);
-  if (n_bytes > SIMMR_FIT_SAM_MAX_BYTES)
-    return eng_fail(e, SIMMR_ENOTSUP, "%s: %llu bytes in one add (at most %llu: cut the text at a line's end)", who, (unsigned long long)n_bytes,
-                    (unsigned long long)SIMMR_FIT_SAM_MAX_BYTES);
-  return SIMMR_OK;
+int check_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
+  return check_add_text(h->e, h->reset_once, text, n_bytes, SIMMR_FIT_SAM_MAX_BYTES, who, "simmr_mapeval_reset", "cut the text at a line's end");
 }
 
 // the line index of text[0, n_bytes) into the object's buffers (n_bytes > 0)
 int enqueue_index(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes, hipStream_t st, MevText* W, uint32_t* rec_grid) {
   simmr_engine* e = h->e;
   const uint64_t n_tiles = (n_bytes + FSAM_TILE - 1) / FSAM_TILE, start_cap = n_bytes / 2 + 1;
-  if (!h->tile_sum.ensure(n_tiles * 8) || !h->tile_prefix.ensure((n_tiles + 1) * 8) || !h->starts.ensure(start_cap * 4))
+  if (!h->index.room(n_tiles, start_cap))
     return eng_fail(e, SIMMR_ENOMEM, "mapeval line index: allocation failed for %llu bytes of text", (unsigned long long)n_bytes);
   const uint32_t cus = (uint32_t)std::max(eng_cu_count(e), 1);
-  const uint32_t tile_grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)cus * 16u);
   *rec_grid = (uint32_t)std::min<uint64_t>(n_bytes / (MEV_WG_RECS * MEV_MIN_LINE) + 1, (uint64_t)cus * 8u);
-  hipLaunchKernelGGL(k_mev_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(), (const uint64_t*)nullptr,
-                     (uint32_t*)nullptr, 0ull);
-  hipLaunchKernelGGL(k_mev_scan, dim3(1), dim3(256), 0, st, h->tile_sum.as<const uint64_t>(), h->tile_prefix.as<uint64_t>(), n_tiles);
-  hipLaunchKernelGGL(k_mev_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(),
-                     h->tile_prefix.as<const uint64_t>(), h->starts.as<uint32_t>(), start_cap);
-  *W = MevText{text, n_bytes, h->tile_prefix.as<const uint64_t>() + n_tiles, h->starts.as<const uint32_t>()};
+  h->index.enqueue(st, k_mev_index, k_mev_scan, text, n_bytes, FSAM_TILE, (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)cus * 16u), start_cap, W);
   return SIMMR_OK;
 }
 
@@ -132,23 +115,9 @@ int end_span(simmr_mapeval* h, hipStream_t st, const char* what) {
 
 extern "C" {
 
-int simmr_mapeval_create(simmr_engine* e, simmr_mapeval** out) {
-  if (!e) return SIMMR_EINVAL;
-  if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_mapeval_create: NULL out");
-  *out = nullptr;
-  simmr_mapeval* h = new (std::nothrow) simmr_mapeval();
-  if (!h) return eng_fail(e, SIMMR_ENOMEM, "simmr_mapeval_create: out of memory");
-  h->e = e;
-  *out = h;
-  return SIMMR_OK;
-}
+int simmr_mapeval_create(simmr_engine* e, simmr_mapeval** out) { return scorer_create(e, out, "simmr_mapeval_create"); }
 
-void simmr_mapeval_destroy(simmr_mapeval* h) {
-  if (!h) return;
-  if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  delete h;  // (its buffers and spans go with it)
-  (void)hipGetLastError();
-}
+void simmr_mapeval_destroy(simmr_mapeval* h) { scorer_destroy(h); }
 
 int simmr_mapeval_reset(simmr_mapeval* h, const simmr_mapeval_config* cfg) {
   if (!h) return SIMMR_EINVAL;
@@ -156,42 +125,24 @@ int simmr_mapeval_reset(simmr_mapeval* h, const simmr_mapeval_config* cfg) {
   if (!cfg || (cfg->n_names > 0 && !cfg->rname)) return eng_fail(e, SIMMR_EINVAL, "simmr_mapeval_reset: NULL argument");
   if (cfg->min_overlap_pct > 100u) return eng_fail(e, SIMMR_EINVAL, "simmr_mapeval_reset: min_overlap_pct is 1 .. 100 (0: the default, 10)");
   if (cfg->n_names > (1u << 24)) return eng_fail(e, SIMMR_ERANGE, "simmr_mapeval_reset: %u names (at most 2^24)", cfg->n_names);
-  std::vector<std::string> names;
-  names.reserve(cfg->n_names);
-  for (uint32_t i = 0; i < cfg->n_names; i++) {
-    const char* s = cfg->rname[i];
-    const size_t n = s ? std::strlen(s) : 0;
-    if (n == 0 || n > SAM_RNAME_MAX) return eng_fail(e, SIMMR_ENOTSUP, "reference name %u is empty or longer than %u bytes", i, SAM_RNAME_MAX);
-    if (!rname_legal(s, n)) return eng_fail(e, SIMMR_ENOTSUP, "'%s' (reference name %u) is not a SAM reference name", s, i);
-    names.emplace_back(s, n);
-  }
-  std::sort(names.begin(), names.end());  // (bytewise, a prefix first: the bytes are below 128)
-  for (size_t i = 1; i < names.size(); i++)
-    if (names[i] == names[i - 1]) return eng_fail(e, SIMMR_EINVAL, "reference name '%s' is given twice", names[i].c_str());
-  std::vector<uint8_t> blob;
-  std::vector<uint32_t> off{0u};
-  for (const std::string& s : names) {
-    blob.insert(blob.end(), s.begin(), s.end());
-    off.push_back((uint32_t)blob.size());
-  }
-  blob.resize(blob.size() + 8, 0);
+  SortedNames sorted;
+  if (int rc = sorted_names(e, cfg->rname, cfg->n_names, SAM_RNAME_MAX, rname_legal, "reference name", nullptr, &sorted)) return rc;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   if (int rc = sync_check(e, "mapeval reset")) return rc;
   h->planned = false;
   h->reset_once = false;
   h->drop_spans();
   h->done_ms = 0.f;
-  if (!h->blob.ensure(blob.size()) || !h->name_off.ensure(off.size() * 4) || !h->cursor.ensure(16) || !h->counts.ensure(COUNT_WORDS * 8) ||
+  if (!h->rnames.room(sorted) || !h->cursor.ensure(16) || !h->counts.ensure(COUNT_WORDS * 8) ||
       !h->word.ensure(16))
     return eng_fail(e, SIMMR_ENOMEM, "mapeval reset: allocation failed");
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipMemcpyAsync(h->blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  HIP_TRY(e, hipMemcpyAsync(h->name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+  if (int rc = h->rnames.upload(e, sorted, st)) return rc;
   HIP_TRY(e, hipMemsetAsync(h->cursor.p, 0, 16, st));
   HIP_TRY(e, hipMemsetAsync(h->counts.p, 0, COUNT_WORDS * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->word.p, 0, 16, st));
   if (int rc = sync_check(e, "mapeval reset")) return rc;  // (the uploads read host vectors that end here)
-  h->n_names = (uint32_t)names.size();
+  h->n_names = cfg->n_names;
   h->min_pct = cfg->min_overlap_pct ? cfg->min_overlap_pct : 10u;
   h->entry_cap = 0;
   h->n_entries = 0;
@@ -202,7 +153,7 @@ int simmr_mapeval_reset(simmr_mapeval* h, const simmr_mapeval_config* cfg) {
 int simmr_mapeval_truth_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_mapeval_truth_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_mapeval_truth_add")) return rc;
   h->planned = false;
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
@@ -239,31 +190,24 @@ int simmr_mapeval_truth_plan(simmr_mapeval* h, uint64_t* n_entries) {
                                      "outside the names, or a POS of 0");
   const uint64_t n = std::min(cur2[0], h->entry_cap);
   if (n >= (1ull << 31)) return eng_fail(e, SIMMR_ERANGE, "simmr_mapeval_truth_plan takes fewer than 2^31 truth entries (%llu given)", (unsigned long long)n);
-  const uint64_t n1 = std::max<uint64_t>(n, 1), n_tiles = (n + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
-  for (DevBuf* b : {&h->key[0], &h->key[1], &h->s_lo, &h->s_hi})
-    if (!b->ensure(n1 * 8)) return eng_fail(e, SIMMR_ENOMEM, "mapeval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
-  for (DevBuf* b : {&h->idx[0], &h->idx[1], &h->s_meta, &h->best, &h->hits})
-    if (!b->ensure(n1 * 4)) return eng_fail(e, SIMMR_ENOMEM, "mapeval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
-  if (!h->hist.ensure(std::max<uint64_t>(n_tiles, 1) * SAMSORT_PAIRS_DIGITS * 4) || !h->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4))
-    return eng_fail(e, SIMMR_ENOMEM, "mapeval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
+  const uint64_t n1 = std::max<uint64_t>(n, 1);
+  bool room = h->order.room(n1) && h->s_lo.ensure(n1 * 8) && h->s_hi.ensure(n1 * 8);
+  for (DevBuf* b : {&h->s_meta, &h->best, &h->hits}) room = room && b->ensure(n1 * 4);
+  if (!room) return eng_fail(e, SIMMR_ENOMEM, "mapeval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
   if (int rc = begin_span(h, st)) return rc;
   // the aligned side starts over: its counts (the words behind the truth's four), by_mapq, best and hits
   HIP_TRY(e, hipMemsetAsync(h->counts_p() + MC_LINES, 0, (COUNT_WORDS - MC_LINES) * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->best.p, 0, n1 * 4, st));
   HIP_TRY(e, hipMemsetAsync(h->hits.p, 0, n1 * 4, st));
-  h->skey = h->key[0].as<const uint64_t>();
+  h->skey = h->order.key[0].as<const uint64_t>();
   if (n > 0) {
-    HIP_TRY(e, hipMemcpyAsync(h->key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
-    uint64_t* const keys[2] = {h->key[0].as<uint64_t>(), h->key[1].as<uint64_t>()};
-    uint32_t* const idxs[2] = {h->idx[0].as<uint32_t>(), h->idx[1].as<uint32_t>()};
-    const uint32_t key_bits = bits_of(cur2[1]);
-    const int cur = samsort_sort_pairs(st, keys, idxs, h->hist.as<uint32_t>(), h->digit_total.as<uint32_t>(), n, key_bits);
-    h->skey = h->key[cur].as<const uint64_t>();
+    HIP_TRY(e, hipMemcpyAsync(h->order.key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
+    const PairSort::Sorted by_key = h->order.sort(st, n, bits_of(cur2[1]));
+    h->skey = by_key.keys;
     const MevEntries U{h->u_key.as<uint64_t>(), h->u_meta.as<uint32_t>(), h->u_lo.as<uint64_t>(), h->u_hi.as<uint64_t>()};
     const MevEntries S{nullptr, h->s_meta.as<uint32_t>(), h->s_lo.as<uint64_t>(), h->s_hi.as<uint64_t>()};
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(eng_cu_count(e), 1) * 32u);
-    hipLaunchKernelGGL(k_mev_gather, dim3(grid), dim3(256), 0, st, h->skey, key_bits > 0u ? h->idx[cur].as<const uint32_t>() : (const uint32_t*)nullptr, U, S,
-                       n, h->word.as<uint32_t>());
+    hipLaunchKernelGGL(k_mev_gather, dim3(grid), dim3(256), 0, st, h->skey, by_key.perm, U, S, n, h->word.as<uint32_t>());
   }
   if (int rc = end_span(h, st, "mapeval truth plan")) return rc;
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
@@ -282,7 +226,7 @@ int simmr_mapeval_truth_plan(simmr_mapeval* h, uint64_t* n_entries) {
 int simmr_mapeval_add(simmr_mapeval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_mapeval_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_mapeval_add")) return rc;
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_mapeval_add called without a simmr_mapeval_truth_plan in force");
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));

@@ -12,6 +12,7 @@
 
 #include "sam_sort_kernels.hip"
 #include "record_stream_host.hpp"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
@@ -44,8 +45,6 @@ struct SamSortFormat : RecordFormat {
                        s.off.as<const uint64_t>(), dst, s.err_p());
   }
 };
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 }  // namespace
 

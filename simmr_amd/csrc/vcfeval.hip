@@ -1,8 +1,5 @@
 // vcfeval.hip — a variant caller's VCF scored against the strain's sites (include/simmr_hip.h: simmr_vcfeval_*): the entry points
-// over vcfeval_kernels.hip.  A translation unit of libsimmr_hip.so of its own; it sees an engine through engine_internal.hpp only.
-// The engine's slot enum is full, so the state lives in an object of its own that the caller creates on an engine and destroys
-// before the engine, as mapeval.hip's and ovleval.hip's do.  The names are mapeval.hip's (sorted, in a device blob; the rule of
-// sam_names.hpp), the sort is sam_sort.hip's (samsort_sort_pairs), run once by the plan.
+// over vcfeval_kernels.hip, on the scaffold of scorer_host.hpp.  The contig names are held as mapeval.hip holds its names.
 //
 // truth_add:  enqueue-only, so nothing is sized from what the text holds.  The index buffers are sized from n_bytes (a line start
 //             per two bytes), the entry columns from the bytes of every truth add since the reset (an entry per VCE_MIN_LINE
@@ -10,26 +7,21 @@
 // truth_plan: reads the cursor and the largest key, copies the keys to the sort's ping, sorts over the bits of the largest key,
 //             gathers the columns into key order and checks the neighbours; zeroes the candidate side.
 // add:        index (count) -> scan -> index (write) -> record.
-// Time: two spans, as ovleval.hip keeps them.  The adds of either side only enqueue: the first begins the span of the adds and
-// every one ends it anew, so a run of adds is one span.  A call that synchronises anyway (the plan, simmr_last_vcfeval_ms) moves
-// the spans that count into a sum and closes them; the plan has a span of its own.
+// Time: the adds' span and the plan's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
-#include <new>
-#include <string>
 #include <vector>
 
 #include "host_support.hpp"
 #include "vcfeval_kernels.hip"
 #include "sam_names.hpp"
+#include "scorer_host.hpp"
 
 using namespace simmr;
 
 namespace {
-
-uint32_t bits_of(uint64_t v) { return v ? 64u - (uint32_t)__builtin_clzll(v) : 0u; }
 
 enum { SPAN_ADDS = 0, SPAN_PLAN = 1, SPAN_COUNT = 2 };
 constexpr size_t QUAL_WORDS = 2u * VCE_QUAL_ROWS, AD_WORDS = 2u * VCE_AD_ROWS;
@@ -43,13 +35,12 @@ const char* const MALFORMED =
 
 struct simmr_vcfeval {
   simmr_engine* e = nullptr;
-  // the names
-  DevBuf blob, name_off;
+  DeviceNames rnames;
   uint32_t n_names = 0, use_filtered = 0;
-  // the line index of one add
-  DevBuf tile_sum, tile_prefix, starts;
-  // the truth: the entries as appended (u_*), and in key order (s_*, with the sorted keys in key[cur])
-  DevBuf u_key, u_alleles, u_ad, s_alleles, s_ad, key[2], idx[2], hist, digit_total;
+  LineIndex index;  // of one add
+  // the truth: the entries as appended (u_*), and in key order (s_*, with the sorted keys in skey)
+  DevBuf u_key, u_alleles, u_ad, s_alleles, s_ad;
+  PairSort order;
   DevBuf cursor;   // [0] entries, [1] the largest key
   DevBuf counts;   // VC_COUNT words, then by_qual's 512 and by_ad's 66
   DevBuf word;     // the error word
@@ -58,11 +49,9 @@ struct simmr_vcfeval {
   uint64_t entry_cap = 0;   // entries the truth adds since the reset may have appended
   uint64_t n_entries = 0;
   bool reset_once = false, planned = false;
-  Spans<SPAN_COUNT> sp;
-  bool open = false;  // the span of the adds has begun and is not folded yet
-  float done_ms = 0.f;
+  FoldedSpans<SPAN_COUNT> sp;
 
-  MevNames names() const { return MevNames{blob.as<const uint8_t>(), name_off.as<const uint32_t>(), n_names}; }
+  MevNames names() const { return rnames.names(n_names); }
   VceEntries appended() const { return VceEntries{u_key.as<uint64_t>(), u_alleles.as<uint32_t>(), u_ad.as<uint32_t>()}; }
   VceEntries sorted() const { return VceEntries{nullptr, s_alleles.as<uint32_t>(), s_ad.as<uint32_t>()}; }
   unsigned long long* counts_p() const { return counts.as<unsigned long long>(); }
@@ -70,59 +59,19 @@ struct simmr_vcfeval {
 
 namespace {
 
-int check_text(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
-  simmr_engine* e = h->e;
-  if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "%s called before simmr_vcfeval_reset", who);
-  if (!text && n_bytes > 0) return eng_fail(e, SIMMR_EINVAL, "%s: NULL text", who);
-  if (n_bytes > SIMMR_FIT_SAM_MAX_BYTES)
-    return eng_fail(e, SIMMR_ENOTSUP, "%s: %llu bytes in one add (at most %llu: cut the text at a line's end)", who, (unsigned long long)n_bytes,
-                    (unsigned long long)SIMMR_FIT_SAM_MAX_BYTES);
-  return SIMMR_OK;
-}
-
-// the span `which` runs from here, unless it is the adds' and open already
-int begin_span(simmr_vcfeval* h, int which, hipStream_t st) {
-  if (which == SPAN_ADDS && h->open) return SIMMR_OK;
-  HIP_TRY(h->e, h->sp.begin(which, st));
-  return SIMMR_OK;
-}
-
-// the spans that count into the sum, and closed.  Synchronises.
-int fold_spans(simmr_vcfeval* h) {
-  float now = 0.f;
-  if (int rc = h->sp.total_ms(h->e, "vcfeval", &now)) return rc;
-  h->done_ms += now;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  return SIMMR_OK;
-}
-
-// ... and ends behind what was enqueued; a launch that failed leaves the span as it was
-int end_span(simmr_vcfeval* h, int which, hipStream_t st, const char* what) {
-  simmr_engine* e = h->e;
-  hipError_t rc = hipGetLastError();
-  if (rc != hipSuccess) return eng_fail(e, SIMMR_ENODEV, "%s launch failed: %s", what, hipGetErrorString(rc));
-  HIP_TRY(e, h->sp.end(which, st));
-  if (which == SPAN_ADDS) h->open = true;
-  h->sp.mark(which);
-  return SIMMR_OK;
+int check_add(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes, const char* who) {
+  return check_add_text(h->e, h->reset_once, text, n_bytes, SIMMR_FIT_SAM_MAX_BYTES, who, "simmr_vcfeval_reset", "cut the text at a line's end");
 }
 
 // the line index of text[0, n_bytes) into the object's buffers (n_bytes > 0)
 int enqueue_index(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes, hipStream_t st, MevText* W, uint32_t* rec_grid) {
   simmr_engine* e = h->e;
   const uint64_t n_tiles = (n_bytes + FSAM_TILE - 1) / FSAM_TILE, start_cap = n_bytes / 2 + 1;
-  if (!h->tile_sum.ensure(n_tiles * 8) || !h->tile_prefix.ensure((n_tiles + 1) * 8) || !h->starts.ensure(start_cap * 4))
+  if (!h->index.room(n_tiles, start_cap))
     return eng_fail(e, SIMMR_ENOMEM, "vcfeval line index: allocation failed for %llu bytes of text", (unsigned long long)n_bytes);
   const uint32_t cus = (uint32_t)std::max(eng_cu_count(e), 1);
-  const uint32_t tile_grid = (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)cus * 16u);
   *rec_grid = (uint32_t)std::min<uint64_t>(n_bytes / (VCE_WG_RECS * VCE_MIN_LINE) + 1, (uint64_t)cus * 8u);
-  hipLaunchKernelGGL(k_vce_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(), (const uint64_t*)nullptr,
-                     (uint32_t*)nullptr, 0ull);
-  hipLaunchKernelGGL(k_vce_scan, dim3(1), dim3(256), 0, st, h->tile_sum.as<const uint64_t>(), h->tile_prefix.as<uint64_t>(), n_tiles);
-  hipLaunchKernelGGL(k_vce_index, dim3(tile_grid), dim3(FSAM_WG), 0, st, text, n_bytes, n_tiles, h->tile_sum.as<uint64_t>(),
-                     h->tile_prefix.as<const uint64_t>(), h->starts.as<uint32_t>(), start_cap);
-  *W = MevText{text, n_bytes, h->tile_prefix.as<const uint64_t>() + n_tiles, h->starts.as<const uint32_t>()};
+  h->index.enqueue(st, k_vce_index, k_vce_scan, text, n_bytes, FSAM_TILE, (uint32_t)std::min<uint64_t>(n_tiles, (uint64_t)cus * 16u), start_cap, W);
   return SIMMR_OK;
 }
 
@@ -130,67 +79,32 @@ int enqueue_index(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes, hipSt
 
 extern "C" {
 
-int simmr_vcfeval_create(simmr_engine* e, simmr_vcfeval** out) {
-  if (!e) return SIMMR_EINVAL;
-  if (!out) return eng_fail(e, SIMMR_EINVAL, "simmr_vcfeval_create: NULL out");
-  *out = nullptr;
-  simmr_vcfeval* h = new (std::nothrow) simmr_vcfeval();
-  if (!h) return eng_fail(e, SIMMR_ENOMEM, "simmr_vcfeval_create: out of memory");
-  h->e = e;
-  *out = h;
-  return SIMMR_OK;
-}
+int simmr_vcfeval_create(simmr_engine* e, simmr_vcfeval** out) { return scorer_create(e, out, "simmr_vcfeval_create"); }
 
-void simmr_vcfeval_destroy(simmr_vcfeval* h) {
-  if (!h) return;
-  if (hipSetDevice(eng_device(h->e)) == hipSuccess) (void)hipStreamSynchronize(eng_stream(h->e));
-  delete h;  // (its buffers and events go with it)
-  (void)hipGetLastError();
-}
+void simmr_vcfeval_destroy(simmr_vcfeval* h) { scorer_destroy(h); }
 
 int simmr_vcfeval_reset(simmr_vcfeval* h, const simmr_vcfeval_config* cfg) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
   if (!cfg || (cfg->n_names > 0 && !cfg->rname)) return eng_fail(e, SIMMR_EINVAL, "simmr_vcfeval_reset: NULL argument");
   if (cfg->n_names > (1u << 24)) return eng_fail(e, SIMMR_ERANGE, "simmr_vcfeval_reset: %u names (at most 2^24)", cfg->n_names);
-  std::vector<std::string> names;
-  names.reserve(cfg->n_names);
-  for (uint32_t i = 0; i < cfg->n_names; i++) {
-    const char* s = cfg->rname[i];
-    const size_t n = s ? std::strlen(s) : 0;
-    if (n == 0 || n > SAM_RNAME_MAX) return eng_fail(e, SIMMR_ENOTSUP, "contig name %u is empty or longer than %u bytes", i, SAM_RNAME_MAX);
-    if (!rname_legal(s, n)) return eng_fail(e, SIMMR_ENOTSUP, "'%s' (contig name %u) is not a SAM reference name", s, i);
-    names.emplace_back(s, n);
-  }
-  std::sort(names.begin(), names.end());  // (bytewise, a prefix first: the bytes are below 128)
-  for (size_t i = 1; i < names.size(); i++)
-    if (names[i] == names[i - 1]) return eng_fail(e, SIMMR_EINVAL, "contig name '%s' is given twice", names[i].c_str());
-  std::vector<uint8_t> blob;
-  std::vector<uint32_t> off{0u};
-  for (const std::string& s : names) {
-    blob.insert(blob.end(), s.begin(), s.end());
-    off.push_back((uint32_t)blob.size());
-  }
-  blob.resize(blob.size() + 8, 0);
+  SortedNames sorted;
+  if (int rc = sorted_names(e, cfg->rname, cfg->n_names, SAM_RNAME_MAX, rname_legal, "contig name", nullptr, &sorted)) return rc;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   if (int rc = sync_check(e, "vcfeval reset")) return rc;
   h->planned = false;
   h->reset_once = false;
-  h->sp.invalidate_from(0);
-  h->open = false;
-  h->done_ms = 0.f;
-  if (int rc = h->sp.create_missing(e)) return rc;
-  if (!h->blob.ensure(blob.size()) || !h->name_off.ensure(off.size() * 4) || !h->cursor.ensure(16) || !h->counts.ensure(COUNT_WORDS * 8) ||
+  if (int rc = h->sp.reset(e)) return rc;
+  if (!h->rnames.room(sorted) || !h->cursor.ensure(16) || !h->counts.ensure(COUNT_WORDS * 8) ||
       !h->word.ensure(16))
     return eng_fail(e, SIMMR_ENOMEM, "vcfeval reset: allocation failed");
   hipStream_t st = eng_stream(e);
-  HIP_TRY(e, hipMemcpyAsync(h->blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-  HIP_TRY(e, hipMemcpyAsync(h->name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+  if (int rc = h->rnames.upload(e, sorted, st)) return rc;
   HIP_TRY(e, hipMemsetAsync(h->cursor.p, 0, 16, st));
   HIP_TRY(e, hipMemsetAsync(h->counts.p, 0, COUNT_WORDS * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->word.p, 0, 16, st));
   if (int rc = sync_check(e, "vcfeval reset")) return rc;  // (the uploads read host vectors that end here)
-  h->n_names = (uint32_t)names.size();
+  h->n_names = cfg->n_names;
   h->use_filtered = cfg->use_filtered ? 1u : 0u;
   h->entry_cap = 0;
   h->n_entries = 0;
@@ -201,7 +115,7 @@ int simmr_vcfeval_reset(simmr_vcfeval* h, const simmr_vcfeval_config* cfg) {
 int simmr_vcfeval_truth_add(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_vcfeval_truth_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_vcfeval_truth_add")) return rc;
   h->planned = false;
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
@@ -210,13 +124,13 @@ int simmr_vcfeval_truth_add(simmr_vcfeval* h, const uint8_t* text, uint64_t n_by
   if (!h->u_key.grow_keep(cap * 8, held * 8, st) || !h->u_alleles.grow_keep(cap * 4, held * 4, st) || !h->u_ad.grow_keep(cap * 4, held * 4, st))
     return eng_fail(e, SIMMR_ENOMEM, "vcfeval truth: allocation failed for %llu entries", (unsigned long long)cap);
   h->entry_cap = cap;
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   uint32_t rec_grid = 1;
   if (int rc = enqueue_index(h, text, n_bytes, st, &W, &rec_grid)) return rc;
   hipLaunchKernelGGL(k_vce_truth, dim3(rec_grid), dim3(VCE_WG), 0, st, W, h->names(), h->appended(), cap, h->cursor.as<unsigned long long>(),
                      h->counts_p(), h->word.as<uint32_t>());
-  return end_span(h, SPAN_ADDS, st, "vcfeval truth add");
+  return h->sp.end(e, SPAN_ADDS, st, "vcfeval truth add");
 }
 
 int simmr_vcfeval_truth_plan(simmr_vcfeval* h, uint64_t* n_entries) {
@@ -231,35 +145,30 @@ int simmr_vcfeval_truth_plan(simmr_vcfeval* h, uint64_t* n_entries) {
   HIP_TRY(e, hipMemcpyAsync(cur2, h->cursor.p, 16, hipMemcpyDeviceToHost, st));
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "vcfeval truth adds")) return rc;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "vcfeval")) return rc;
   if (errw & VCE_ERR_TRUTH)
     return eng_fail(e, SIMMR_EINVAL, "a malformed truth record: %s, a REF or ALT that is not one base of ACGT, REF equal to ALT, a CHROM outside the names, or "
                                      "an AD= item that is not two numbers", MALFORMED);
   const uint64_t n = std::min(cur2[0], h->entry_cap);
   if (n >= (1ull << 31)) return eng_fail(e, SIMMR_ERANGE, "simmr_vcfeval_truth_plan takes fewer than 2^31 truth entries (%llu given)", (unsigned long long)n);
-  const uint64_t n1 = std::max<uint64_t>(n, 1), n_tiles = (n + SAMSORT_PAIRS_TILE - 1) / SAMSORT_PAIRS_TILE;
-  bool room = h->hist.ensure(std::max<uint64_t>(n_tiles, 1) * SAMSORT_PAIRS_DIGITS * 4) && h->digit_total.ensure(SAMSORT_PAIRS_DIGITS * 4);
-  for (DevBuf* b : {&h->key[0], &h->key[1]}) room = room && b->ensure(n1 * 8);
-  for (DevBuf* b : {&h->idx[0], &h->idx[1], &h->s_alleles, &h->s_ad, &h->best, &h->hits}) room = room && b->ensure(n1 * 4);
+  const uint64_t n1 = std::max<uint64_t>(n, 1);
+  bool room = h->order.room(n1);
+  for (DevBuf* b : {&h->s_alleles, &h->s_ad, &h->best, &h->hits}) room = room && b->ensure(n1 * 4);
   if (!room) return eng_fail(e, SIMMR_ENOMEM, "vcfeval truth plan: allocation failed (%llu entries)", (unsigned long long)n);
-  if (int rc = begin_span(h, SPAN_PLAN, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_PLAN, st)) return rc;
   // the candidate side starts over: its counts (the words behind the truth's three), by_qual, by_ad, best and hits
   HIP_TRY(e, hipMemsetAsync(h->counts_p() + VC_LINES, 0, (COUNT_WORDS - VC_LINES) * 8, st));
   HIP_TRY(e, hipMemsetAsync(h->best.p, 0, n1 * 4, st));
   HIP_TRY(e, hipMemsetAsync(h->hits.p, 0, n1 * 4, st));
-  h->skey = h->key[0].as<const uint64_t>();
+  h->skey = h->order.key[0].as<const uint64_t>();
   if (n > 0) {
-    HIP_TRY(e, hipMemcpyAsync(h->key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
-    uint64_t* const keys[2] = {h->key[0].as<uint64_t>(), h->key[1].as<uint64_t>()};
-    uint32_t* const idxs[2] = {h->idx[0].as<uint32_t>(), h->idx[1].as<uint32_t>()};
-    const uint32_t key_bits = bits_of(cur2[1]);
-    const int cur = samsort_sort_pairs(st, keys, idxs, h->hist.as<uint32_t>(), h->digit_total.as<uint32_t>(), n, key_bits);
-    h->skey = h->key[cur].as<const uint64_t>();
+    HIP_TRY(e, hipMemcpyAsync(h->order.key[0].p, h->u_key.p, n * 8, hipMemcpyDeviceToDevice, st));
+    const PairSort::Sorted by_key = h->order.sort(st, n, bits_of(cur2[1]));
+    h->skey = by_key.keys;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)std::max(eng_cu_count(e), 1) * 32u);
-    hipLaunchKernelGGL(k_vce_gather, dim3(grid), dim3(256), 0, st, h->skey, key_bits > 0u ? h->idx[cur].as<const uint32_t>() : (const uint32_t*)nullptr,
-                       h->appended(), h->sorted(), n, h->word.as<uint32_t>());
+    hipLaunchKernelGGL(k_vce_gather, dim3(grid), dim3(256), 0, st, h->skey, by_key.perm, h->appended(), h->sorted(), n, h->word.as<uint32_t>());
   }
-  if (int rc = end_span(h, SPAN_PLAN, st, "vcfeval truth plan")) return rc;
+  if (int rc = h->sp.end(e, SPAN_PLAN, st, "vcfeval truth plan")) return rc;
   HIP_TRY(e, hipMemcpyAsync(&errw, h->word.p, 4, hipMemcpyDeviceToHost, st));
   if (int rc = sync_check(e, "vcfeval truth plan")) return rc;
   if (errw & VCE_ERR_DUP) {
@@ -269,7 +178,7 @@ int simmr_vcfeval_truth_plan(simmr_vcfeval* h, uint64_t* n_entries) {
   }
   h->n_entries = n;
   h->planned = true;
-  if (int rc = fold_spans(h)) return rc;
+  if (int rc = h->sp.fold(e, "vcfeval")) return rc;
   if (n_entries) *n_entries = n;
   return SIMMR_OK;
 }
@@ -277,18 +186,18 @@ int simmr_vcfeval_truth_plan(simmr_vcfeval* h, uint64_t* n_entries) {
 int simmr_vcfeval_add(simmr_vcfeval* h, const uint8_t* text, uint64_t n_bytes) {
   if (!h) return SIMMR_EINVAL;
   simmr_engine* e = h->e;
-  if (int rc = check_text(h, text, n_bytes, "simmr_vcfeval_add")) return rc;
+  if (int rc = check_add(h, text, n_bytes, "simmr_vcfeval_add")) return rc;
   if (!h->planned) return eng_fail(e, SIMMR_ESTATE, "simmr_vcfeval_add called without a simmr_vcfeval_truth_plan in force");
   if (n_bytes == 0) return SIMMR_OK;
   HIP_TRY(e, hipSetDevice(eng_device(e)));
   hipStream_t st = eng_stream(e);
-  if (int rc = begin_span(h, SPAN_ADDS, st)) return rc;
+  if (int rc = h->sp.begin(e, SPAN_ADDS, st)) return rc;
   MevText W;
   uint32_t rec_grid = 1;
   if (int rc = enqueue_index(h, text, n_bytes, st, &W, &rec_grid)) return rc;
   hipLaunchKernelGGL(k_vce_record, dim3(rec_grid), dim3(VCE_WG), 0, st, W, h->names(), h->skey, h->s_alleles.as<const uint32_t>(), h->n_entries,
                      h->use_filtered, h->counts_p(), h->best.as<uint32_t>(), h->hits.as<uint32_t>(), h->word.as<uint32_t>());
-  return end_span(h, SPAN_ADDS, st, "vcfeval add");
+  return h->sp.end(e, SPAN_ADDS, st, "vcfeval add");
 }
 
 int simmr_vcfeval_read(simmr_vcfeval* h, simmr_vcfeval_counts* counts, uint64_t* by_qual_host, uint64_t* by_ad_host) {
@@ -343,9 +252,7 @@ int simmr_last_vcfeval_ms(simmr_vcfeval* h, float* ms) {
   if (!ms) return eng_fail(e, SIMMR_EINVAL, "simmr_last_vcfeval_ms: NULL ms");
   if (!h->reset_once) return eng_fail(e, SIMMR_ESTATE, "no simmr_vcfeval_reset yet");
   HIP_TRY(e, hipSetDevice(eng_device(e)));
-  if (int rc = fold_spans(h)) return rc;  // (the next add of either side begins a new span)
-  *ms = h->done_ms;
-  return SIMMR_OK;
+  return h->sp.last_ms(e, "vcfeval", ms);
 }
 
 }  // extern "C"

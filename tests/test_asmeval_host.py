@@ -13,6 +13,7 @@ import pytest
 from simmr_amd import _abi
 from tests import _asmeval
 from tests._asmeval import NONE, fasta, revcomp_bytes
+from tests._scaffold import sorts_through_the_pair_sort
 from tests._synth import synthetic_contigs
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -166,7 +167,7 @@ def test_the_unit_is_built_without_a_slot_of_the_engine():
     assert "ENG_EXT_COUNT = 12" in (CSRC / "engine_internal.hpp").read_text()
     unit = (CSRC / "asmeval.hip").read_text()
     assert "eng_ext_slot" not in unit and "unit_state" not in unit and '#include "engine.hip"' not in unit and '#include "kernels.hip"' not in unit
-    assert '#include "host_support.hpp"' in unit and "Spans<" in unit and "samsort_sort_pairs(" in unit and "eng_scan_u32(" in unit
+    assert '#include "host_support.hpp"' in unit and "Spans<" in unit and sorts_through_the_pair_sort("asmeval.hip") and "eng_scan_u32(" in unit
 
 
 # ---- the command line --------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,8 @@ from pathlib import Path
 
 import pytest
 
+from tests._scaffold import sorts_through_the_pair_sort
+
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 
@@ -53,5 +55,5 @@ def test_the_shared_routines_are_taken_not_restated():
     assert not re.search(r"SIMMR_DEV \w+ (?:mev_|fsam_|sam_)\w+\(", text)
     assert "mev_name_row(" in text and "fsam_index_tiles(" in text and "sam_scan_chunks(" in text and "sam_wg_scan<" in text
     unit = (ROOT / "simmr_amd" / "csrc" / "asmeval.hip").read_text()
-    assert "samsort_sort_pairs(" in unit and "eng_scan_u32(" in unit
+    assert sorts_through_the_pair_sort("asmeval.hip") and "eng_scan_u32(" in unit
     assert "min(24, bit length" in text   # the table's rule is fixed in a comment

@@ -8,6 +8,8 @@ from pathlib import Path
 
 import pytest
 
+from tests._scaffold import sorts_through_the_pair_sort
+
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "simmr_amd" / "csrc"
 sys.path.insert(0, str(ROOT / "tools"))
@@ -57,7 +59,7 @@ def test_the_shared_routines_are_taken_not_restated():
     for t in (text, unit):
         assert not re.search(r"SIMMR_DEV [\w ]+ (?:asm_roll\w*|mev_\w+|fsam_\w+|sam_\w+)\(", t)
     assert "asm_roll_at(" in text and "asm_find(" in text
-    assert "samsort_sort_pairs(" in unit and "eng_scan_u32(" in unit and "asm_front_launch(" in unit and "DevBuf" in unit and "Spans<" in unit
+    assert sorts_through_the_pair_sort("asmmap.hip") and "eng_scan_u32(" in unit and "asm_front_launch(" in unit and "DevBuf" in unit and "Spans<" in unit
     assert "min(24, bit length" in text   # the table's rule is fixed in a comment
     guarded = (CSRC / "asmeval_kernels.hip").read_text()
     assert guarded.index("#ifndef ASM_ROUTINES_ONLY") < guarded.index("k_asm_index(") and guarded.index("SIMMR_DEV void asm_roll(") < guarded.index("#ifndef ASM_ROUTINES_ONLY")

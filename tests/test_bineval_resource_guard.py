@@ -8,6 +8,8 @@ from pathlib import Path
 
 import pytest
 
+from tests._scaffold import sorts_through_the_pair_sort
+
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 
@@ -55,7 +57,7 @@ def test_the_shared_routines_are_taken_not_restated():
     assert not re.search(r"SIMMR_DEV \w+ (?:mev_|fsam_|sam_)\w+\(", text)
     assert "mev_name_row(" in text and "fsam_index_tiles(" in text and "sam_scan_chunks(" in text and "sam_wg_scan<" in text
     unit = (ROOT / "simmr_amd" / "csrc" / "bineval.hip").read_text()
-    assert "samsort_sort_pairs(" in unit and "eng_scan_u32(" in unit and '#include "host_support.hpp"' in unit
+    assert sorts_through_the_pair_sort("bineval.hip") and "eng_scan_u32(" in unit and '#include "host_support.hpp"' in unit
     assert not re.search(r"struct (DevBuf|Spans)\b", unit)
     make = (ROOT / "simmr_amd" / "csrc" / "Makefile").read_text()
     assert len(re.findall(r"-shared -o \S+ .*\bbineval\.hip\b", make)) == 2, "both link lines"

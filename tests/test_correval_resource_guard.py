@@ -8,6 +8,8 @@ from pathlib import Path
 
 import pytest
 
+from tests._scaffold import sorts_through_the_pair_sort
+
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 
@@ -60,7 +62,7 @@ def test_the_shared_routines_are_taken_not_restated():
     ove = (ROOT / "simmr_amd" / "csrc" / "ovleval_kernels.hip").read_text()
     assert "#ifndef OVE_ROUTINES_ONLY" in ove and ove.index("ove_name_key(const") < ove.index("#ifndef OVE_ROUTINES_ONLY") < ove.index("k_ove_index(")
     unit = (ROOT / "simmr_amd" / "csrc" / "correval.hip").read_text()
-    assert "samsort_sort_pairs(" in unit and '#include "host_support.hpp"' in unit and "Spans<" in unit and "DevBuf " in unit
+    assert sorts_through_the_pair_sort("correval.hip") and '#include "host_support.hpp"' in unit and "Spans<" in unit and "DevBuf " in unit
     assert not re.search(r"struct (DevBuf|Spans)\b", unit)
     make = (ROOT / "simmr_amd" / "csrc" / "Makefile").read_text()
     assert len(re.findall(r"-shared -o \S+ .*\bcorreval\.hip\b", make)) == 2, "both link lines"

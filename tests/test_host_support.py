@@ -1,5 +1,6 @@
-"""simmr_amd/csrc/host_support.hpp — the plumbing every host unit of libsimmr_hip.so shares — without a GPU: a stand-alone
-program over counting stubs of the HIP calls, built and run under the sanitizers, and the shape the sources keep."""
+"""simmr_amd/csrc/host_support.hpp — the plumbing every host unit of libsimmr_hip.so shares — and scorer_host.hpp — the scaffold
+of the scorer units over it — without a GPU: a stand-alone program over counting stubs of the HIP calls, built and run under the
+sanitizers, and the shape the sources keep."""
 import os
 import re
 import subprocess
@@ -8,13 +9,19 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "simmr_amd" / "csrc"
 UNITS = ("engine.hip", "truth.hip", "stats.hip", "depth.hip", "strain.hip", "regions.hip", "pileup.hip", "sam.hip", "sam_sort.hip", "overlap.hip", "fit.hip", "fit_sam.hip",
-         "bam.hip", "bam_index.hip", "mapeval.hip")
+         "bam.hip", "bam_index.hip", "mapeval.hip", "ovleval.hip", "vcfeval.hip", "taxeval.hip", "asmeval.hip", "bineval.hip", "correval.hip", "asmmap.hip")
+SCORERS = UNITS[-8:]
 
 
 def test_the_support_header_in_a_stand_alone_program_under_the_sanitizers(tmp_path):
     """tests/host_support_main.cpp: ensure keeps, grows and fails clean; the engine's slack; one owner through moves and swaps and
     inside a vector; Events creates only what is missing; Spans adds up exactly the spans that are marked; a state deleted
-    through unit_state's hook leaves nothing alive.  The exit status is the number of allocations and events still alive."""
+    through unit_state's hook leaves nothing alive.  Of scorer_host.hpp, what stands without a unit's kernels: bits_of and the grids at
+    their edges; grow_zero; check_add_text's three refusals in their order, to the byte; FoldedSpans (two adds are one span, a fold adds
+    the marked spans once and closes them, a begin after it opens a new one, a failed launch leaves the span as it was, reset zeroes
+    the sum); sorted_names (the refusals' texts, a name given twice, a prefix first, bytes from 128 on as unsigned, the order that
+    std::sort gave the units before, the order array, the blob's eight zero bytes) and DeviceNames; the rooms of LineIndex and
+    PairSort; scorer_create and scorer_destroy.  The exit status is the number of allocations and events still alive."""
     exe = tmp_path / "host_support_main"
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-D__HIP_PLATFORM_AMD__", f"-I{rocm}/include", "-fsanitize=address,undefined",
@@ -52,5 +59,26 @@ def test_one_copy_of_the_plumbing():
     assert "truth_kernels.hip" not in files["engine.hip"] and "stats_kernels.hip" not in files["engine.hip"]
     for name in ("depth.hip", "pileup.hip", "overlap.hip", "sam_names.hpp"):
         assert "staged_rows(e" in files[name] and "eng_contig_len(" not in files[name], name
+    # the scorers' scaffold: one copy of what they share, in scorer_host.hpp, and none left in a unit
+    scaffold = files["scorer_host.hpp"]
+    assert '#include "host_support.hpp"' in scaffold and "__global__" not in scaffold and "__device__" not in scaffold
+    for name in SCORERS + ("bam_index.hip", "sam_sort.hip"):
+        assert '#include "scorer_host.hpp"' in files[name], name
+
+    def defined(fn):
+        return [name for name, text in files.items() if re.search(r"^(?:template\s*<[^>]*>\s*)?(?:inline\s+)?[\w:]+[\s*&]+%s\(" % fn, text, re.M)]
+    for fn in ("bits_of", "grow_zero", "check_add_text", "sorted_names", "scorer_create", "scorer_destroy"):
+        assert defined(fn) == ["scorer_host.hpp"], fn
+    assert sorted(defined("grid_for")) == ["asmmap.hip", "engine.hip", "scorer_host.hpp"]  # asmmap's: under SIMMR_ASMMAP_MAX_WGS; the engine's: blocks of a count
+    for fn in ("check_text", "fold_spans", "sort_room"):
+        assert defined(fn) == [], fn
+    assert defined("begin_span") == defined("end_span") == ["mapeval.hip"]  # its growing list of per-add spans
+    for struct in ("FoldedSpans", "LineIndex", "PairSort", "DeviceNames"):
+        assert len(re.findall(r"^\s*(?:template\s*<[^>]*>\s*)?struct %s\b" % struct, everything, re.M)) == 1 and "struct %s {" % struct in scaffold
+    for once in ("new (std::nothrow)", "blob.resize(blob.size() + 8"):
+        assert [name for name, text in files.items() if once in text] == ["scorer_host.hpp"], once
+    for name in SCORERS:
+        assert re.search(r"^int simmr_\w+_create\(simmr_engine\* e, simmr_\w+\*\* out\) \{", files[name], re.M), name  # the entry points stay in their units
     make = (CSRC / "Makefile").read_text()
+    assert "scorer_host.hpp" in re.search(r"^SRCS = (.*)$", make, re.M).group(1).split()
     assert "host_support.hpp" in re.search(r"^SRCS = (.*)$", make, re.M).group(1).split()

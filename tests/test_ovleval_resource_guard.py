@@ -7,6 +7,8 @@ from pathlib import Path
 
 import pytest
 
+from tests._scaffold import sorts_through_the_pair_sort
+
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 
@@ -49,4 +51,4 @@ def test_mapeval_keeps_its_kernels_behind_the_shared_routines():
     text = (ROOT / "simmr_amd" / "csrc" / "ovleval_kernels.hip").read_text()
     assert "#define MEV_ROUTINES_ONLY" in text and '#include "mapeval_kernels.hip"' in text
     assert "mev_lower_bound(" in text and not re.search(r"SIMMR_DEV \w+ (?:mev_|fsam_|sam_)\w+\(", text)
-    assert "fsam_index_tiles(" in text and "sam_scan_chunks(" in text and "samsort_sort_pairs(" in (ROOT / "simmr_amd" / "csrc" / "ovleval.hip").read_text()
+    assert "fsam_index_tiles(" in text and "sam_scan_chunks(" in text and sorts_through_the_pair_sort("ovleval.hip")

@@ -13,6 +13,7 @@ import pytest
 from simmr_amd import _abi
 from tests import _vcfeval
 from tests._vcfeval import rec, site
+from tests._scaffold import sorts_through_the_pair_sort
 
 ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "simmr_amd" / "csrc"
@@ -226,7 +227,7 @@ def test_the_unit_is_built_without_a_slot_of_the_engine():
     assert "ENG_EXT_COUNT = 12" in (CSRC / "engine_internal.hpp").read_text()
     unit = (CSRC / "vcfeval.hip").read_text()
     assert "eng_ext_slot" not in unit and "unit_state" not in unit and '#include "engine.hip"' not in unit and '#include "kernels.hip"' not in unit
-    assert '#include "host_support.hpp"' in unit and "Spans<" in unit and "samsort_sort_pairs(" in unit
+    assert '#include "host_support.hpp"' in unit and "Spans<" in unit and sorts_through_the_pair_sort("vcfeval.hip")
     for text in (unit, (CSRC / "vcfeval_kernels.hip").read_text()):
         assert not re.search(r"\bhipFree\(|\bhipEventDestroy\(|\bhipEventElapsedTime\(|#\s*define\s+\w*_TRY\b", text)
 

@@ -7,6 +7,8 @@ from pathlib import Path
 
 import pytest
 
+from tests._scaffold import sorts_through_the_pair_sort
+
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT / "tools"))
 
@@ -52,4 +54,4 @@ def test_the_shared_routines_are_taken_not_restated():
     assert "#define MEV_ROUTINES_ONLY" in text and '#include "mapeval_kernels.hip"' in text
     assert not re.search(r"SIMMR_DEV \w+ (?:mev_|fsam_|sam_)\w+\(", text)
     assert "mev_lower_bound(" in text and "mev_name_row(" in text and "fsam_index_tiles(" in text and "sam_scan_chunks(" in text
-    assert "samsort_sort_pairs(" in (ROOT / "simmr_amd" / "csrc" / "vcfeval.hip").read_text()
+    assert sorts_through_the_pair_sort("vcfeval.hip")
