@@ -1364,6 +1364,53 @@ std::string bineval_contig_rows(const std::vector<std::string>& names, const std
   return out;
 }
 
+// ---- a file in pieces ------------------------------------------------------------------------------------------------------------------
+size_t piece_cut(const uint8_t* p, size_t have, PieceCut rule) {
+  size_t cut = 0;
+  switch (rule.kind) {
+    case PieceCut::Newline:
+      for (cut = have; cut > 0 && p[cut - 1] != '\n';) cut--;
+      break;
+    case PieceCut::Fasta:
+      for (cut = have; cut > 1 && !(p[cut - 1] == '>' && p[cut - 2] == '\n');) cut--;
+      cut = cut > 1 ? cut - 1 : 0;  // in front of the '>'
+      break;
+    case PieceCut::Record:
+      for (size_t i = 0, lines = 0; i < have; i++)
+        if (p[i] == '\n' && ++lines % rule.lines == 0) cut = i + 1;
+      break;
+  }
+  return cut;
+}
+
+PieceReader::End PieceReader::next(const uint8_t** p, size_t* n) {
+  if (cut_ > 0) {  // the open last line or record of the piece before moves to the front
+    memmove(buf_.data(), buf_.data() + cut_, have_ - cut_);
+    have_ -= cut_;
+    cut_ = 0;
+  }
+  while (!eof_) {
+    if (buf_.size() < have_ + piece_) buf_.resize(have_ + piece_);
+    const size_t got = fread(buf_.data() + have_, 1, piece_, f_);
+    if (got < piece_) {
+      if (ferror(f_)) return CannotRead;
+      eof_ = true;
+    }
+    have_ += got;
+    const size_t cut = eof_ ? have_ : piece_cut(buf_.data(), have_, rule_);
+    if (cut == 0) {  // longer than the buffer: read on (or the file's end with nothing left)
+      if (!eof_ && rule_.kind == PieceCut::Fasta && have_ > max_) return TooLong;
+      continue;
+    }
+    if (cut > max_) return TooLong;
+    cut_ = cut;
+    *p = buf_.data();
+    *n = cut;
+    return Piece;
+  }
+  return Done;
+}
+
 // ---- --eval-classified ---------------------------------------------------------------------------------------------------------------
 static const char* const TAXEVAL_RANK_NAMES[TAXEVAL_RANKS + 1] = {"no_rank", "domain", "phylum", "class", "order", "family", "genus", "species", "strain"};
 

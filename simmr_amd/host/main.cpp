@@ -15,13 +15,12 @@
 #include <string>
 #include <vector>
 
+#include "cli_common.hpp"
+#include "eval_cli.hpp"
 #include "simmr_host.hpp"
 
 using namespace simmr_host;
 
-static void info(const std::string& msg) { fprintf(stderr, " INFO simmr-hip: %s\n", msg.c_str()); }
-static void warn(const std::string& msg) { fprintf(stderr, " WARN simmr-hip: %s\n", msg.c_str()); }
-static int die(const std::string& msg) { fprintf(stderr, "ERROR simmr-hip: %s\n", msg.c_str()); return 1; }
 static void reads_not_written(const std::string& err) { fprintf(stderr, "ERROR simmr-hip: Failed to write reads to the output file: %s\n", err.c_str()); }
 static bool exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0; }
 static bool is_regular_file(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
@@ -249,26 +248,6 @@ static bool write_vcf_file(simmr_engine* eng, const CliArgs& args, const std::ve
   if (!mem.fetch(&counts, table, n * 10)) { *err = "copy back failed"; return false; }
   return write_strain_vcf(genomes, lens, sites, site_genome, counts, args.strain_vcf, err);
 }
-
-// A buffer that grows to the largest size asked of it, with a sixteenth to spare so that sizes creeping up do not allocate
-// every time: device memory, or pinned host memory.
-struct GrowBuf {
-  bool pinned = false;
-  void* p = nullptr;
-  uint64_t cap = 0;
-  ~GrowBuf() { release(); }
-  void release() { if (p) (void)(pinned ? hipHostFree(p) : hipFree(p)); p = nullptr; cap = 0; }
-  // room for `bytes`, or nullptr if there is none; what the buffer held is gone when it grows
-  uint8_t* room(uint64_t bytes) {
-    if (cap < bytes) {
-      release();
-      const uint64_t want = bytes + bytes / 16 + 256;
-      if ((pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return nullptr; }
-      cap = want;
-    }
-    return (uint8_t*)p;
-  }
-};
 
 // the text buffer of the drains: what one copy to the host moves, and what a window of --overlaps holds
 static constexpr size_t TEXT_CHUNK = 256u << 20;
@@ -1004,62 +983,11 @@ static int load_genome_device(simmr_engine* eng, uint32_t slot, const std::strin
   return 0;
 }
 
-struct Engines {  // released on every way out of run_main
-  std::vector<simmr_engine*> v;
-  simmr_bam_sort* bam_sort = nullptr;  // --bam-sorted: its state lives on an engine and goes before it
-  ~Engines() {
-    simmr_bam_sort_destroy(bam_sort);
-    for (simmr_engine* en : v) simmr_engine_destroy(en);
-  }
-};
-
-// A SAM file to the device in pieces cut at the last newline (a line longer than a piece makes the piece grow; at the end of the
-// file the last line may lack its newline): add(d, n) gets every piece as n bytes of device memory, and answers only when the
-// device has read them (the buffer is then free for the next piece); an answer other than 0 ends the walk with that answer.
-// `flag` names the file's option in the messages.
-static constexpr size_t SAM_PIECE = 64u << 20;
-static int sam_file_pieces(const std::string& flag, const std::string& path, const std::function<int(const uint8_t*, size_t)>& add) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return die(flag + ": cannot open " + path);
-  struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
-  GrowBuf dev;
-  std::vector<uint8_t> piece;
-  size_t have = 0;  // bytes of `piece` read and not yet added: the open last line of the piece before
-  for (bool eof = false; !eof;) {
-    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
-    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
-    if (got < SAM_PIECE) {
-      if (ferror(f)) return die(flag + ": cannot read " + path);
-      eof = true;
-    }
-    have += got;
-    size_t cut = have;  // at the end of the file the last line may lack its newline
-    if (!eof) {
-      while (cut > 0 && piece[cut - 1] != '\n') cut--;
-      if (cut == 0) continue;  // one line longer than the piece: read on
-    }
-    if (cut > SIMMR_FIT_SAM_MAX_BYTES) return die(flag + ": a line of " + path + " is longer than one add takes");
-    if (cut > 0) {
-      uint8_t* d = dev.room(cut);
-      if (!d) return die(flag + ": device allocation failed");
-      if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die(flag + ": copy to the device failed");
-      if (int rc = add(d, cut)) return rc;
-    }
-    memmove(piece.data(), piece.data() + cut, have - cut);
-    have -= cut;
-  }
-  return 0;
-}
-
 // `--fit-from-sam FILE --fit-model OUT`: no simulation.  Every piece of the file is one simmr_fit_add_sam; then the plan and the
 // model file of --fit-model.  What was taken and skipped is printed in the manner of the reference's "Skipped N alignments ..."
 // lines (simmrd/src/main.rs:259-290).
 static int run_fit_from_sam(const CliArgs& args) {
-  {  // (the file is looked at before an engine is made)
-    FILE* f = fopen(args.fit_from_sam.c_str(), "rb");
-    if (!f) return die("--fit-from-sam: cannot open " + args.fit_from_sam);
-    fclose(f);
-  }
+  if (int rc = probe_file("--fit-from-sam", args.fit_from_sam)) return rc;
   Engines engines;
   simmr_engine* eng = nullptr;
   if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
@@ -1070,8 +998,8 @@ static int run_fit_from_sam(const CliArgs& args) {
   info("Parsing " + args.fit_from_sam);
   const uint32_t n_sets = args.single_reads ? 1u : 2u;
   float device_ms = 0;
-  if (int rc = sam_file_pieces("--fit-from-sam", args.fit_from_sam, [&](const uint8_t* d, size_t n) {
-        if (simmr_fit_add_sam(eng, d, n, n_sets) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
+  if (int rc = file_pieces("--fit-from-sam", args.fit_from_sam, PieceCut{PieceCut::Newline, 1}, [&](const uint8_t* d, const char*, size_t bytes) {
+        if (simmr_fit_add_sam(eng, d, bytes, n_sets) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
         float ms = 0;  // (synchronises: the buffer is free for the next piece)
         if (simmr_last_fit_ms(eng, &ms) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
         device_ms += ms;
@@ -1080,7 +1008,6 @@ static int run_fit_from_sam(const CliArgs& args) {
     return rc;
   simmr_fit_sam_counts c{};
   if (simmr_fit_sam_counts_read(eng, &c) != SIMMR_OK) return die(std::string("--fit-from-sam: ") + simmr_last_error(eng));
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
   info("Read " + n(c.lines) + " lines: " + n(c.header_lines) + " header lines, " + n(c.records) + " alignments");
   info("Using " + n(c.taken_alignment) + " alignments (" + n(c.taken_quality) + " for read lengths and qualities)");
   info("Skipped " + n(c.skip_no_sequence) + " alignments that were missing sequences");
@@ -1095,865 +1022,6 @@ static int run_fit_from_sam(const CliArgs& args) {
   info("Skipped " + n(c.skip_inconsistent) + " alignments whose CIGAR, MD and sequence disagree");
   if (!side.finish_fit(eng)) return die(side.err);
   info("Wrote sequence error model to " + args.fit_model);
-  return 0;
-}
-
-// `--eval-sam ALIGNED --eval-truth TRUTH --eval-report OUT`: no simulation.  The names come from the @SQ lines in front of the
-// truth file's records; both files go up in pieces, the truth through simmr_mapeval_truth_add and, behind the plan, the aligner's
-// through simmr_mapeval_add; the report is written from the counts and by_mapq on the host.  Nothing is written unless all of it
-// succeeded.
-struct MapevalHandle {
-  simmr_mapeval* h = nullptr;
-  ~MapevalHandle() { simmr_mapeval_destroy(h); }
-};
-static int run_eval_sam(const CliArgs& args) {
-  std::vector<std::string> names;
-  {
-    std::ifstream in(args.eval_truth, std::ios::binary);
-    if (!in) return die("--eval-truth: cannot open " + args.eval_truth);
-    std::string head, ln;
-    while (std::getline(in, ln) && (ln.empty() || ln[0] == '@')) head += ln + "\n";
-    mapeval_sq_names(head.data(), head.size(), &names);
-  }
-  if (names.empty()) return die("--eval-truth: " + args.eval_truth + " has no @SQ lines in front of its records: the sequences' names come from them");
-  {
-    FILE* f = fopen(args.eval_sam.c_str(), "rb");
-    if (!f) return die("--eval-sam: cannot open " + args.eval_sam);
-    fclose(f);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  MapevalHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_mapeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-sam: ") + simmr_last_error(eng));
-  std::vector<const char*> rname;
-  for (const std::string& s : names) rname.push_back(s.c_str());
-  const simmr_mapeval_config cfg{(uint32_t)rname.size(), args.eval_min_overlap, rname.data()};
-  if (simmr_mapeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-truth: ") + simmr_last_error(eng));
-  float ms = 0;
-  info("Parsing " + args.eval_truth);
-  if (int rc = sam_file_pieces("--eval-truth", args.eval_truth, [&](const uint8_t* d, size_t n) {
-        if (simmr_mapeval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_mapeval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
-          return die(std::string("--eval-truth: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  uint64_t n_entries = 0;
-  if (simmr_mapeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-truth: ") + simmr_last_error(eng));
-  info("Parsing " + args.eval_sam);
-  if (int rc = sam_file_pieces("--eval-sam", args.eval_sam, [&](const uint8_t* d, size_t n) {
-        if (simmr_mapeval_add(ev.h, d, n) != SIMMR_OK || simmr_last_mapeval_ms(ev.h, &ms) != SIMMR_OK)
-          return die(std::string("--eval-sam: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  simmr_mapeval_counts c{};
-  static_assert(sizeof(c) == MAPEVAL_N_COUNTS * sizeof(uint64_t), "the report names every count");
-  std::vector<uint64_t> by_mapq(512);
-  if (simmr_mapeval_read(ev.h, &c, by_mapq.data()) != SIMMR_OK) return die(std::string("--eval-sam: ") + simmr_last_error(eng));
-  std::string rows;
-  if (!args.eval_reads.empty()) {
-    GrowBuf d_key, d_best, d_hits;
-    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
-    uint8_t *k = d_key.room(n1 * 8), *b = d_best.room(n1 * 4), *h = d_hits.room(n1 * 4);
-    if (!k || !b || !h) return die("--eval-reads: device allocation failed");
-    if (simmr_mapeval_emit(ev.h, (uint64_t*)k, (uint32_t*)b, (uint32_t*)h, n_entries) != SIMMR_OK) return die(std::string("--eval-reads: ") + simmr_last_error(eng));
-    std::vector<uint64_t> key(n1);
-    std::vector<uint32_t> best(n1), hits(n1);
-    if (n_entries > 0 && (hipMemcpy(key.data(), k, n_entries * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-                          hipMemcpy(best.data(), b, n_entries * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                          hipMemcpy(hits.data(), h, n_entries * 4, hipMemcpyDeviceToHost) != hipSuccess))
-      return die("--eval-reads: copy from the device failed");
-    rows = mapeval_read_rows(key.data(), best.data(), hits.data(), n_entries);
-  }
-  std::string err;
-  OutFile report(args.eval_report, false);
-  report.append(mapeval_report((const uint64_t*)&c, by_mapq.data()));
-  if (!report.close(&err)) return die("--eval-report: " + err);
-  if (!args.eval_reads.empty()) {
-    OutFile reads(args.eval_reads, false);
-    reads.append(rows);
-    if (!reads.close(&err)) return die("--eval-reads: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_entries) + " reads (" + n(c.truth_skipped) + " records skipped)");
-  info("Aligned: " + n(c.records) + " records: " + n(c.correct) + " correct, " + n(c.wrong) + " wrong, " + n(c.unmapped) + " unmapped; " + n(c.secondary) +
-       " secondary or supplementary, " + n(c.cigar_op) + " with an operation other than M = X I D S H, " + n(c.unknown_read) + " of unknown reads");
-  info("Reads: " + n(c.reads_correct) + " correct, " + n(c.reads_wrong) + " wrong, " + n(c.reads_unmapped) + " unmapped, " + n(c.missing) + " without a record");
-  info("Wrote " + args.eval_report);
-  return 0;
-}
-
-// `--eval-overlaps CANDIDATE --eval-overlaps-truth TRUTH --eval-overlaps-report OUT`: no simulation.  Both files go up in pieces, the
-// truth through simmr_ovleval_truth_add and, behind the plan, the overlapper's through simmr_ovleval_add; the report is written from
-// the counts and by_len on the host.  Nothing is written unless all of it succeeded.
-struct OvlevalHandle {
-  simmr_ovleval* h = nullptr;
-  ~OvlevalHandle() { simmr_ovleval_destroy(h); }
-};
-static int run_eval_overlaps(const CliArgs& args) {
-  for (const auto& [flag, path] : {std::make_pair("--eval-overlaps-truth", &args.eval_overlaps_truth), std::make_pair("--eval-overlaps", &args.eval_overlaps)}) {
-    FILE* f = fopen(path->c_str(), "rb");  // (the files are looked at before an engine is made)
-    if (!f) return die(std::string(flag) + ": cannot open " + *path);
-    fclose(f);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  OvlevalHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_ovleval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
-  if (simmr_ovleval_reset(ev.h, args.eval_overlaps_min_pct) != SIMMR_OK) return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
-  float ms = 0;
-  info("Parsing " + args.eval_overlaps_truth);
-  if (int rc = sam_file_pieces("--eval-overlaps-truth", args.eval_overlaps_truth, [&](const uint8_t* d, size_t n) {
-        if (simmr_ovleval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_ovleval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
-          return die(std::string("--eval-overlaps-truth: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  uint64_t n_entries = 0, n_reads = 0;
-  if (simmr_ovleval_truth_plan(ev.h, &n_entries, &n_reads) != SIMMR_OK) return die(std::string("--eval-overlaps-truth: ") + simmr_last_error(eng));
-  info("Parsing " + args.eval_overlaps);
-  if (int rc = sam_file_pieces("--eval-overlaps", args.eval_overlaps, [&](const uint8_t* d, size_t n) {
-        if (simmr_ovleval_add(ev.h, d, n) != SIMMR_OK || simmr_last_ovleval_ms(ev.h, &ms) != SIMMR_OK)
-          return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  simmr_ovleval_counts c{};
-  static_assert(sizeof(c) == OVLEVAL_N_COUNTS * sizeof(uint64_t) && OVLEVAL_LEN_ROWS == SIMMR_OVLEVAL_LEN_ROWS, "the report names every count and row");
-  std::vector<uint64_t> by_len(2 * OVLEVAL_LEN_ROWS);
-  if (simmr_ovleval_read(ev.h, &c, by_len.data()) != SIMMR_OK) return die(std::string("--eval-overlaps: ") + simmr_last_error(eng));
-  std::string rows;
-  if (!args.eval_overlaps_pairs.empty()) {
-    GrowBuf d_wide, d_narrow;
-    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
-    uint8_t *w = d_wide.room(3 * n1 * 8), *nw = d_narrow.room(2 * n1 * 4);
-    if (!w || !nw) return die("--eval-overlaps-pairs: device allocation failed");
-    uint64_t* const wide = (uint64_t*)w;
-    uint32_t* const narrow = (uint32_t*)nw;
-    if (simmr_ovleval_emit(ev.h, wide, wide + n1, wide + 2 * n1, narrow, narrow + n1, n_entries) != SIMMR_OK)
-      return die(std::string("--eval-overlaps-pairs: ") + simmr_last_error(eng));
-    std::vector<uint64_t> hw(3 * n1);
-    std::vector<uint32_t> hn(2 * n1);
-    if (hipMemcpy(hw.data(), w, 3 * n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), nw, 2 * n1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
-      return die("--eval-overlaps-pairs: copy from the device failed");
-    rows = ovleval_pair_rows(hw.data(), hw.data() + n1, hw.data() + 2 * n1, hn.data(), hn.data() + n1, n_entries);
-  }
-  std::string err;
-  OutFile report(args.eval_overlaps_report, false);
-  report.append(ovleval_report((const uint64_t*)&c, by_len.data()));
-  if (!report.close(&err)) return die("--eval-overlaps-report: " + err);
-  if (!args.eval_overlaps_pairs.empty()) {
-    OutFile pairs(args.eval_overlaps_pairs, false);
-    pairs.append(rows);
-    if (!pairs.close(&err)) return die("--eval-overlaps-pairs: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_entries) + " pairs of " + n(c.truth_reads) + " reads");
-  info("Candidate: " + n(c.records) + " records: " + n(c.correct) + " correct, " + n(c.wrong) + " wrong (" + n(c.unknown_read) + " of unknown reads, " +
-       n(c.no_pair) + " of pairs that do not overlap, " + n(c.wrong_strand) + " on the other strand, " + n(c.wrong_interval) + " off the interval), " +
-       n(c.self) + " of a read with itself");
-  info("Pairs: " + n(c.pairs_found) + " found, " + n(c.pairs_wrong) + " reported wrong only, " + n(c.pairs_missed) + " missed, " + n(c.pairs_multiple) +
-       " reported more than once");
-  info("Wrote " + args.eval_overlaps_report);
-  return 0;
-}
-// `--eval-vcf CALLS --eval-vcf-truth TRUTH --eval-vcf-report OUT`: no simulation.  The names come from the ##contig lines in front
-// of the truth file's records; both files go up in pieces, the truth through simmr_vcfeval_truth_add and, behind the plan, the
-// caller's through simmr_vcfeval_add; the report is written from the counts, by_qual and by_ad on the host.  Nothing is written
-// unless all of it succeeded.
-struct VcfevalHandle {
-  simmr_vcfeval* h = nullptr;
-  ~VcfevalHandle() { simmr_vcfeval_destroy(h); }
-};
-static int run_eval_vcf(const CliArgs& args) {
-  std::vector<std::string> names;
-  {
-    std::ifstream in(args.eval_vcf_truth, std::ios::binary);
-    if (!in) return die("--eval-vcf-truth: cannot open " + args.eval_vcf_truth);
-    std::string head, ln;
-    while (std::getline(in, ln) && (ln.empty() || ln[0] == '#')) head += ln + "\n";
-    vcfeval_contig_names(head.data(), head.size(), &names);
-  }
-  if (names.empty()) return die("--eval-vcf-truth: " + args.eval_vcf_truth + " has no ##contig=<ID=...> lines in front of its records: the contigs' names come from them");
-  {
-    FILE* f = fopen(args.eval_vcf.c_str(), "rb");
-    if (!f) return die("--eval-vcf: cannot open " + args.eval_vcf);
-    fclose(f);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  VcfevalHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_vcfeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-vcf: ") + simmr_last_error(eng));
-  std::vector<const char*> rname;
-  for (const std::string& s : names) rname.push_back(s.c_str());
-  const simmr_vcfeval_config cfg{(uint32_t)rname.size(), args.eval_vcf_filtered ? 1u : 0u, rname.data()};
-  if (simmr_vcfeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-vcf-truth: ") + simmr_last_error(eng));
-  float ms = 0;
-  info("Parsing " + args.eval_vcf_truth);
-  if (int rc = sam_file_pieces("--eval-vcf-truth", args.eval_vcf_truth, [&](const uint8_t* d, size_t n) {
-        if (simmr_vcfeval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_vcfeval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
-          return die(std::string("--eval-vcf-truth: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  uint64_t n_entries = 0;
-  if (simmr_vcfeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-vcf-truth: ") + simmr_last_error(eng));
-  info("Parsing " + args.eval_vcf);
-  if (int rc = sam_file_pieces("--eval-vcf", args.eval_vcf, [&](const uint8_t* d, size_t n) {
-        if (simmr_vcfeval_add(ev.h, d, n) != SIMMR_OK || simmr_last_vcfeval_ms(ev.h, &ms) != SIMMR_OK)
-          return die(std::string("--eval-vcf: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  simmr_vcfeval_counts c{};
-  static_assert(sizeof(c) == VCFEVAL_N_COUNTS * sizeof(uint64_t) && VCFEVAL_AD_ROWS == SIMMR_VCFEVAL_AD_ROWS, "the report names every count and row");
-  std::vector<uint64_t> by_qual(512), by_ad(2 * VCFEVAL_AD_ROWS);
-  if (simmr_vcfeval_read(ev.h, &c, by_qual.data(), by_ad.data()) != SIMMR_OK) return die(std::string("--eval-vcf: ") + simmr_last_error(eng));
-  std::string rows;
-  if (!args.eval_vcf_sites.empty()) {
-    GrowBuf d_key, d_narrow;
-    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
-    uint8_t *k = d_key.room(n1 * 8), *nw = d_narrow.room(4 * n1 * 4);
-    if (!k || !nw) return die("--eval-vcf-sites: device allocation failed");
-    uint32_t* const narrow = (uint32_t*)nw;
-    if (simmr_vcfeval_emit(ev.h, (uint64_t*)k, narrow, narrow + n1, narrow + 2 * n1, narrow + 3 * n1, n_entries) != SIMMR_OK)
-      return die(std::string("--eval-vcf-sites: ") + simmr_last_error(eng));
-    std::vector<uint64_t> hk(n1);
-    std::vector<uint32_t> hn(4 * n1);
-    if (hipMemcpy(hk.data(), k, n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), nw, 4 * n1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
-      return die("--eval-vcf-sites: copy from the device failed");
-    std::sort(names.begin(), names.end());  // (the rows of the key are places in the sorted names)
-    rows = vcfeval_site_rows(names, hk.data(), hn.data(), hn.data() + n1, hn.data() + 2 * n1, hn.data() + 3 * n1, n_entries);
-  }
-  std::string err;
-  OutFile report(args.eval_vcf_report, false);
-  report.append(vcfeval_report((const uint64_t*)&c, by_qual.data(), by_ad.data()));
-  if (!report.close(&err)) return die("--eval-vcf-report: " + err);
-  if (!args.eval_vcf_sites.empty()) {
-    OutFile sites(args.eval_vcf_sites, false);
-    sites.append(rows);
-    if (!sites.close(&err)) return die("--eval-vcf-sites: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_entries) + " sites");
-  info("Calls: " + n(c.records) + " records (" + n(c.filtered) + " filtered, " + n(c.ref_call) + " reference calls): " + n(c.calls) + " calls, " + n(c.correct) +
-       " correct, " + n(c.wrong) + " wrong (" + n(c.unknown_contig) + " on unknown contigs, " + n(c.no_site) + " where no site is, " + n(c.ref_mismatch) +
-       " with another reference base, " + n(c.wrong_allele) + " with another allele); " + n(c.indel) + " indel, " + n(c.symbolic) + " symbolic and " +
-       n(c.long_allele) + " long alleles not scored");
-  info("Sites: " + n(c.sites_found) + " found, " + n(c.sites_wrong) + " called wrong only, " + n(c.sites_missed) + " missed, " + n(c.sites_multiple) +
-       " called more than once");
-  info("Wrote " + args.eval_vcf_report);
-  return 0;
-}
-
-// `--eval-classified CALLS --eval-classified-truth TRUTH --eval-taxonomy NODES --eval-genome-taxa MAP --eval-classified-report OUT`:
-// no simulation.  The two small files are parsed here and handed to simmr_taxeval_reset; both big files go up in pieces, the truth
-// through simmr_taxeval_truth_add and, behind the plan, the classifier's through simmr_taxeval_add; the three texts are written
-// from the integer tables on the host.  Nothing is written unless all of it succeeded.
-struct TaxevalHandle {
-  simmr_taxeval* h = nullptr;
-  ~TaxevalHandle() { simmr_taxeval_destroy(h); }
-};
-static bool slurp(const std::string& path, std::string* out) {
-  std::ifstream in(path, std::ios::binary);
-  if (!in) return false;
-  out->assign(std::istreambuf_iterator<char>(in), std::istreambuf_iterator<char>());
-  return true;
-}
-static int run_eval_classified(const CliArgs& args) {
-  std::string text, perr;
-  std::vector<uint32_t> taxid, parent, gtax;
-  std::vector<uint8_t> rank;
-  std::vector<std::string> gid;
-  if (!slurp(args.eval_taxonomy, &text)) return die("--eval-taxonomy: cannot open " + args.eval_taxonomy);
-  if (!taxeval_parse_nodes(text.data(), text.size(), &taxid, &parent, &rank, &perr)) return die("--eval-taxonomy: " + args.eval_taxonomy + ": " + perr);
-  if (!slurp(args.eval_genome_taxa, &text)) return die("--eval-genome-taxa: cannot open " + args.eval_genome_taxa);
-  if (!taxeval_parse_map(text.data(), text.size(), &gid, &gtax, &perr)) return die("--eval-genome-taxa: " + args.eval_genome_taxa + ": " + perr);
-  text.clear();
-  for (const std::string* f : {&args.eval_classified_truth, &args.eval_classified}) {
-    FILE* fp = fopen(f->c_str(), "rb");
-    if (!fp) return die(std::string(f == &args.eval_classified ? "--eval-classified" : "--eval-classified-truth") + ": cannot open " + *f);
-    fclose(fp);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  TaxevalHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_taxeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-classified: ") + simmr_last_error(eng));
-  std::vector<const char*> ids;
-  for (const std::string& s : gid) ids.push_back(s.c_str());
-  const simmr_taxeval_config cfg{taxid.size(), taxid.data(), parent.data(), rank.data(), gid.size(), ids.data(), gtax.data()};
-  if (simmr_taxeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-taxonomy: ") + simmr_last_error(eng));
-  float ms = 0;
-  info("Parsing " + args.eval_classified_truth);
-  if (int rc = sam_file_pieces("--eval-classified-truth", args.eval_classified_truth, [&](const uint8_t* d, size_t n) {
-        if (simmr_taxeval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_taxeval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
-          return die(std::string("--eval-classified-truth: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  uint64_t n_entries = 0;
-  if (simmr_taxeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-classified-truth: ") + simmr_last_error(eng));
-  info("Parsing " + args.eval_classified);
-  if (int rc = sam_file_pieces("--eval-classified", args.eval_classified, [&](const uint8_t* d, size_t n) {
-        if (simmr_taxeval_add(ev.h, d, n) != SIMMR_OK || simmr_last_taxeval_ms(ev.h, &ms) != SIMMR_OK)
-          return die(std::string("--eval-classified: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  simmr_taxeval_counts c{};
-  static_assert(sizeof(c) == TAXEVAL_N_COUNTS * sizeof(uint64_t) && TAXEVAL_RANKS == SIMMR_TAXEVAL_RANKS && TAXEVAL_CLASSES == SIMMR_TAXEVAL_CLASSES,
-                "the report names every count, rank and class");
-  std::vector<uint64_t> by_rank(TAXEVAL_RANKS * TAXEVAL_CLASSES), reads_by_rank(TAXEVAL_RANKS * TAXEVAL_CLASSES);
-  if (simmr_taxeval_read(ev.h, &c, by_rank.data(), reads_by_rank.data()) != SIMMR_OK) return die(std::string("--eval-classified: ") + simmr_last_error(eng));
-  // the per-taxon rows: the clade sums in taxid order, and the ranks put into that order here
-  const uint64_t nn = taxid.size(), nn1 = std::max<uint64_t>(nn, 1);
-  std::vector<uint32_t> h_taxid(nn1);
-  std::vector<uint64_t> h_sums(3 * nn1);
-  {
-    GrowBuf d_taxid, d_sums;
-    uint8_t *t = d_taxid.room(nn1 * 4), *s = d_sums.room(3 * nn1 * 8);
-    if (!t || !s) return die("--eval-classified: device allocation failed");
-    uint64_t* const sums = (uint64_t*)s;
-    if (simmr_taxeval_taxa(ev.h, (uint32_t*)t, sums, sums + nn1, sums + 2 * nn1, nn) != SIMMR_OK) return die(std::string("--eval-classified: ") + simmr_last_error(eng));
-    if (hipMemcpy(h_taxid.data(), t, nn1 * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(h_sums.data(), s, 3 * nn1 * 8, hipMemcpyDeviceToHost) != hipSuccess)
-      return die("--eval-classified: copy from the device failed");
-  }
-  std::vector<uint32_t> order(nn);
-  for (uint32_t i = 0; i < nn; i++) order[i] = i;
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return taxid[a] < taxid[b]; });
-  std::vector<uint8_t> s_rank(nn1, 0);
-  for (uint64_t i = 0; i < nn; i++) s_rank[i] = rank[order[i]];
-  std::string rows;
-  if (!args.eval_classified_reads.empty()) {
-    // a genome's row is its place among the sorted ids; the ranks its lineage has come from simmr_taxeval_lineage
-    std::vector<uint32_t> g_order(gid.size());
-    for (uint32_t i = 0; i < gid.size(); i++) g_order[i] = i;
-    std::sort(g_order.begin(), g_order.end(), [&](uint32_t a, uint32_t b) { return gid[a] < gid[b]; });
-    std::vector<std::string> s_gid;
-    std::vector<uint32_t> has;
-    for (uint32_t g : g_order) {
-      uint32_t lin[TAXEVAL_RANKS] = {}, mask = 0;
-      if (simmr_taxeval_lineage(ev.h, gtax[g], lin, nullptr) != SIMMR_OK) return die(std::string("--eval-classified-reads: ") + simmr_last_error(eng));
-      for (size_t r = 0; r < TAXEVAL_RANKS; r++) mask |= lin[r] ? 1u << r : 0u;
-      s_gid.push_back(gid[g]);
-      has.push_back(mask);
-    }
-    GrowBuf d_id, d_narrow;
-    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
-    uint8_t *k = d_id.room(n1 * 8), *nw = d_narrow.room(4 * n1 * 4);
-    if (!k || !nw) return die("--eval-classified-reads: device allocation failed");
-    uint32_t* const narrow = (uint32_t*)nw;
-    if (simmr_taxeval_emit(ev.h, (uint64_t*)k, narrow, narrow + n1, narrow + 2 * n1, narrow + 3 * n1, n_entries) != SIMMR_OK)
-      return die(std::string("--eval-classified-reads: ") + simmr_last_error(eng));
-    std::vector<uint64_t> hk(n1);
-    std::vector<uint32_t> hn(4 * n1);
-    if (hipMemcpy(hk.data(), k, n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), nw, 4 * n1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
-      return die("--eval-classified-reads: copy from the device failed");
-    rows = taxeval_read_rows(s_gid, has, hk.data(), hn.data(), hn.data() + n1, hn.data() + 2 * n1, hn.data() + 3 * n1, n_entries);
-  }
-  std::string err;
-  OutFile report(args.eval_classified_report, false);
-  report.append(taxeval_report((const uint64_t*)&c, by_rank.data(), reads_by_rank.data(), s_rank.data(), h_sums.data(), h_sums.data() + nn1, nn));
-  if (!report.close(&err)) return die("--eval-classified-report: " + err);
-  if (!args.eval_classified_reads.empty()) {
-    OutFile reads(args.eval_classified_reads, false);
-    reads.append(rows);
-    if (!reads.close(&err)) return die("--eval-classified-reads: " + err);
-  }
-  if (!args.eval_classified_taxa.empty()) {
-    OutFile taxa(args.eval_classified_taxa, false);
-    taxa.append(taxeval_taxa_rows(h_taxid.data(), s_rank.data(), h_sums.data(), h_sums.data() + nn1, h_sums.data() + 2 * nn1, nn));
-    if (!taxa.close(&err)) return die("--eval-classified-taxa: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_entries) + " reads (" + n(c.truth_paired) + " paired) of " + n(gid.size()) + " genomes; " + n(nn) + " taxa");
-  info("Calls: " + n(c.records) + " records: " + n(c.scored) + " scored, " + n(c.unclassified) + " unclassified, " + n(c.unknown_taxon) +
-       " with a taxid that is no node, " + n(c.unknown_read) + " of unknown reads");
-  info("Reads: " + n(c.missing) + " without a record, " + n(c.multiple) + " with more records than lines");
-  info("Wrote " + args.eval_classified_report);
-  return 0;
-}
-
-// `--eval-assembly CONTIGS.fa --eval-assembly-truth GOLD.fa --eval-assembly-report OUT`: no simulation.  A FASTA file goes to the
-// device in pieces of whole records: a piece is cut in front of the last '>' that begins a line, grows to hold a record that is
-// longer, and may not pass what one add takes.  The host reads every piece once for the records' first words and lengths: the
-// genomes are the distinct prefixes of the truth's first words, in a pass of their own in front of the reset, which needs them.
-static int fasta_file_pieces(const std::string& flag, const std::string& path, const std::function<int(const uint8_t*, const char*, size_t)>& add) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return die(flag + ": cannot open " + path);
-  struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
-  GrowBuf dev;
-  std::vector<uint8_t> piece;
-  size_t have = 0;
-  for (bool eof = false; !eof;) {
-    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
-    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
-    if (got < SAM_PIECE) {
-      if (ferror(f)) return die(flag + ": cannot read " + path);
-      eof = true;
-    }
-    have += got;
-    size_t cut = have;
-    if (!eof) {
-      while (cut > 1 && !(piece[cut - 1] == '>' && piece[cut - 2] == '\n')) cut--;
-      cut = cut > 1 ? cut - 1 : 0;  // in front of the '>'
-      if (cut == 0) {
-        if (have > SIMMR_ASMEVAL_MAX_BYTES) { fprintf(stderr, "error: %s: a record of %s is longer than one add takes\n", flag.c_str(), path.c_str()); return 2; }
-        continue;  // one record longer than the piece: read on
-      }
-    }
-    if (cut > SIMMR_ASMEVAL_MAX_BYTES) { fprintf(stderr, "error: %s: a record of %s is longer than one add takes\n", flag.c_str(), path.c_str()); return 2; }
-    if (cut > 0) {
-      if (add) {
-        uint8_t* d = dev.room(cut);
-        if (!d) return die(flag + ": device allocation failed");
-        if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die(flag + ": copy to the device failed");
-        if (int rc = add(d, (const char*)piece.data(), cut)) return rc;
-      }
-    }
-    memmove(piece.data(), piece.data() + cut, have - cut);
-    have -= cut;
-  }
-  return 0;
-}
-
-struct AsmevalHandle {
-  simmr_asmeval* h = nullptr;
-  ~AsmevalHandle() { simmr_asmeval_destroy(h); }
-};
-static int run_eval_assembly(const CliArgs& args) {
-  {
-    FILE* f = fopen(args.eval_assembly.c_str(), "rb");
-    if (!f) return die("--eval-assembly: cannot open " + args.eval_assembly);
-    fclose(f);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  AsmevalHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_asmeval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-assembly: ") + simmr_last_error(eng));
-  // the truth file is held on the device piece by piece while the host reads it: the names first, then the adds
-  std::vector<std::string> t_words, c_words;
-  std::vector<uint64_t> t_len, c_len_host;
-  struct Piece { GrowBuf dev; size_t n = 0; };
-  std::vector<std::unique_ptr<Piece>> pieces;
-  info("Parsing " + args.eval_assembly_truth);
-  if (int rc = fasta_file_pieces("--eval-assembly-truth", args.eval_assembly_truth, [&](const uint8_t* d, const char* host, size_t n) {
-        asmeval_fasta_records(host, n, &t_words, &t_len);
-        pieces.emplace_back(new Piece());
-        uint8_t* keep = pieces.back()->dev.room(n);
-        if (!keep || hipMemcpy(keep, d, n, hipMemcpyDeviceToDevice) != hipSuccess) return die("--eval-assembly-truth: device allocation failed");
-        pieces.back()->n = n;
-        return 0;
-      }))
-    return rc;
-  std::vector<std::string> genomes;
-  for (const std::string& w : t_words) {
-    const size_t bar = w.find('|');
-    if (bar == std::string::npos || bar == 0)
-      return die("--eval-assembly-truth: the header '>" + w + "' has no genome in front of a '|': " + args.eval_assembly_truth + " is not a file of --gold-assembly");
-    genomes.push_back(w.substr(0, bar));
-  }
-  std::sort(genomes.begin(), genomes.end());
-  genomes.erase(std::unique(genomes.begin(), genomes.end()), genomes.end());
-  std::vector<const char*> gname;
-  for (const std::string& s : genomes) gname.push_back(s.c_str());
-  const simmr_asmeval_config cfg{(uint32_t)gname.size(), args.eval_assembly_k, 0u, gname.data()};
-  if (simmr_asmeval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-assembly-truth: ") + simmr_last_error(eng));
-  for (const auto& p : pieces)
-    if (simmr_asmeval_truth_add(ev.h, (const uint8_t*)p->dev.room(p->n), p->n) != SIMMR_OK) return die(std::string("--eval-assembly-truth: ") + simmr_last_error(eng));
-  uint64_t n_entries = 0;
-  if (simmr_asmeval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-assembly-truth: ") + simmr_last_error(eng));
-  pieces.clear();
-  info("Parsing " + args.eval_assembly);
-  if (int rc = fasta_file_pieces("--eval-assembly", args.eval_assembly, [&](const uint8_t* d, const char* host, size_t n) {
-        asmeval_fasta_records(host, n, &c_words, &c_len_host);
-        if (simmr_asmeval_add(ev.h, d, n) != SIMMR_OK) return die(std::string("--eval-assembly: ") + simmr_last_error(eng));  // (synchronises)
-        return 0;
-      }))
-    return rc;
-  simmr_asmeval_counts c{};
-  static_assert(sizeof(c) == ASMEVAL_N_COUNTS * sizeof(uint64_t) && ASMEVAL_GENOME_COLS == SIMMR_ASMEVAL_GENOME_COLS, "the report names every count and column");
-  std::vector<uint64_t> by_genome((genomes.size() + 1) * ASMEVAL_GENOME_COLS);
-  if (simmr_asmeval_read(ev.h, &c, by_genome.data()) != SIMMR_OK) return die(std::string("--eval-assembly: ") + simmr_last_error(eng));
-  const uint64_t nc = c.records, nc1 = std::max<uint64_t>(nc, 1);
-  GrowBuf d_len, d_narrow;
-  uint8_t *dl = d_len.room(nc1 * 8), *dn = d_narrow.room(5 * nc1 * 4);
-  if (!dl || !dn) return die("--eval-assembly: device allocation failed");
-  uint32_t* const narrow = (uint32_t*)dn;
-  if (simmr_asmeval_contigs(ev.h, (uint64_t*)dl, narrow, narrow + nc1, narrow + 2 * nc1, narrow + 3 * nc1, narrow + 4 * nc1, nc, nullptr) != SIMMR_OK)
-    return die(std::string("--eval-assembly: ") + simmr_last_error(eng));
-  std::vector<uint64_t> hl(nc1);
-  std::vector<uint32_t> hn(5 * nc1);
-  if (hipMemcpy(hl.data(), dl, nc1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hn.data(), dn, 5 * nc1 * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return die("--eval-assembly: copy from the device failed");
-  std::string err;
-  OutFile report(args.eval_assembly_report, false);
-  report.append(asmeval_report((const uint64_t*)&c, args.eval_assembly_k, genomes, by_genome.data(), t_len.data(), t_len.size(), hl.data(), nc));
-  if (!report.close(&err)) return die("--eval-assembly-report: " + err);
-  if (!args.eval_assembly_contigs.empty()) {
-    OutFile rows(args.eval_assembly_contigs, false);
-    rows.append(asmeval_contig_rows(c_words, genomes, hl.data(), hn.data(), hn.data() + nc1, hn.data() + 2 * nc1, hn.data() + 3 * nc1, hn.data() + 4 * nc1, nc));
-    if (!rows.close(&err)) return die("--eval-assembly-contigs: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_records) + " records, " + n(c.truth_bases) + " bases, " + n(n_entries) + " distinct " + std::to_string(args.eval_assembly_k) + "-mers of " +
-       n(genomes.size()) + " genomes (" + n(c.truth_shared_distinct) + " in more than one)");
-  info("Contigs: " + n(c.records) + " records, " + n(c.bases) + " bases, " + n(c.kmers) + " k-mers: " + n(c.found) + " found, " + n(c.novel) + " in no genome; " +
-       n(c.contigs_pure) + " pure, " + n(c.contigs_mixed) + " mixed, " + n(c.contigs_novel) + " novel, " + n(c.contigs_shared_only) + " shared only, " +
-       n(c.contigs_short) + " shorter than k");
-  info("Wrote " + args.eval_assembly_report);
-  return 0;
-}
-
-// `--eval-placement CONTIGS.fa --eval-placement-truth GOLD.fa --eval-placement-report OUT`: no simulation.  The files and the genome
-// names are read exactly as --eval-assembly reads them (fasta_file_pieces, asmeval_fasta_records); the host keeps the first words
-// of both sides for the block rows and computes NA50 / NGA50 from the block columns, as it computes N50 there.
-struct AsmmapHandle {
-  simmr_asmmap* h = nullptr;
-  ~AsmmapHandle() { simmr_asmmap_destroy(h); }
-};
-static int run_eval_placement(const CliArgs& args) {
-  {
-    FILE* f = fopen(args.eval_placement.c_str(), "rb");
-    if (!f) return die("--eval-placement: cannot open " + args.eval_placement);
-    fclose(f);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  AsmmapHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_asmmap_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));
-  std::vector<std::string> t_words, c_words;
-  std::vector<uint64_t> t_len, c_len_host;
-  struct Piece { GrowBuf dev; size_t n = 0; };
-  std::vector<std::unique_ptr<Piece>> pieces;
-  info("Parsing " + args.eval_placement_truth);
-  if (int rc = fasta_file_pieces("--eval-placement-truth", args.eval_placement_truth, [&](const uint8_t* d, const char* host, size_t n) {
-        asmeval_fasta_records(host, n, &t_words, &t_len);
-        pieces.emplace_back(new Piece());
-        uint8_t* keep = pieces.back()->dev.room(n);
-        if (!keep || hipMemcpy(keep, d, n, hipMemcpyDeviceToDevice) != hipSuccess) return die("--eval-placement-truth: device allocation failed");
-        pieces.back()->n = n;
-        return 0;
-      }))
-    return rc;
-  std::vector<std::string> genomes;
-  for (const std::string& w : t_words) {
-    const size_t bar = w.find('|');
-    if (bar == std::string::npos || bar == 0)
-      return die("--eval-placement-truth: the header '>" + w + "' has no genome in front of a '|': " + args.eval_placement_truth + " is not a file of --gold-assembly");
-    genomes.push_back(w.substr(0, bar));
-  }
-  std::vector<std::string> t_genome_name = genomes;  // per truth record
-  std::sort(genomes.begin(), genomes.end());
-  genomes.erase(std::unique(genomes.begin(), genomes.end()), genomes.end());
-  std::vector<const char*> gname;
-  for (const std::string& s : genomes) gname.push_back(s.c_str());
-  const simmr_asmmap_config cfg{(uint32_t)gname.size(), args.eval_placement_k, args.eval_placement_band, args.eval_placement_relocation,
-                                args.eval_placement_min_anchors, gname.data()};
-  if (simmr_asmmap_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-placement-truth: ") + simmr_last_error(eng));
-  for (const auto& p : pieces)
-    if (simmr_asmmap_truth_add(ev.h, (const uint8_t*)p->dev.room(p->n), p->n) != SIMMR_OK) return die(std::string("--eval-placement-truth: ") + simmr_last_error(eng));
-  uint64_t n_anchors = 0;
-  if (simmr_asmmap_truth_plan(ev.h, &n_anchors) != SIMMR_OK) return die(std::string("--eval-placement-truth: ") + simmr_last_error(eng));
-  pieces.clear();
-  info("Parsing " + args.eval_placement);
-  if (int rc = fasta_file_pieces("--eval-placement", args.eval_placement, [&](const uint8_t* d, const char* host, size_t n) {
-        asmeval_fasta_records(host, n, &c_words, &c_len_host);
-        if (simmr_asmmap_add(ev.h, d, n) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));  // (synchronises)
-        return 0;
-      }))
-    return rc;
-  simmr_asmmap_counts c{};
-  static_assert(sizeof(c) == ASMMAP_N_COUNTS * sizeof(uint64_t) && ASMMAP_GENOME_COLS == SIMMR_ASMMAP_GENOME_COLS && ASMMAP_BLOCK_COLS == SIMMR_ASMMAP_BLOCK_COLS,
-                "the report names every count and column");
-  std::vector<uint64_t> by_genome(std::max<size_t>(genomes.size(), 1) * ASMMAP_GENOME_COLS);
-  if (simmr_asmmap_read(ev.h, &c, by_genome.data()) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));
-  // the block columns and the contig columns
-  const uint64_t nb = c.blocks, nb1 = std::max<uint64_t>(nb, 1), nc = c.records, nc1 = std::max<uint64_t>(nc, 1);
-  GrowBuf d_blocks, d_wide, d_narrow;
-  uint8_t *db = d_blocks.room(ASMMAP_BLOCK_COLS * nb1 * 4), *dw = d_wide.room(2 * nc1 * 8), *dn = d_narrow.room(4 * nc1 * 4);
-  if (!db || !dw || !dn) return die("--eval-placement: device allocation failed");
-  uint32_t* bcols[ASMMAP_BLOCK_COLS];
-  for (size_t j = 0; j < ASMMAP_BLOCK_COLS; j++) bcols[j] = (uint32_t*)db + j * nb1;
-  if (simmr_asmmap_blocks(ev.h, bcols, nb, nullptr) != SIMMR_OK) return die(std::string("--eval-placement: ") + simmr_last_error(eng));
-  uint64_t* const wide = (uint64_t*)dw;
-  uint32_t* const narrow = (uint32_t*)dn;
-  if (simmr_asmmap_contigs(ev.h, wide, narrow, narrow + nc1, narrow + 2 * nc1, wide + nc1, narrow + 3 * nc1, nc, nullptr) != SIMMR_OK)
-    return die(std::string("--eval-placement: ") + simmr_last_error(eng));
-  std::vector<uint32_t> hb(ASMMAP_BLOCK_COLS * nb1), hn(4 * nc1);
-  std::vector<uint64_t> hw(2 * nc1);
-  if (hipMemcpy(hb.data(), db, hb.size() * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hw.data(), dw, hw.size() * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-      hipMemcpy(hn.data(), dn, hn.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return die("--eval-placement: copy from the device failed");
-  const uint32_t* hcols[ASMMAP_BLOCK_COLS];
-  for (size_t j = 0; j < ASMMAP_BLOCK_COLS; j++) hcols[j] = hb.data() + j * nb1;
-  std::vector<uint64_t> block_length(nb);
-  std::vector<uint32_t> block_genome(nb);
-  for (uint64_t i = 0; i < nb; i++) {
-    block_length[i] = hcols[4][i] - hcols[3][i];
-    const uint32_t t = hcols[1][i];
-    block_genome[i] = t < t_genome_name.size() ? (uint32_t)(std::lower_bound(genomes.begin(), genomes.end(), t_genome_name[t]) - genomes.begin()) : 0xffffffffu;
-  }
-  std::string err;
-  OutFile report(args.eval_placement_report, false);
-  report.append(asmmap_report((const uint64_t*)&c, args.eval_placement_k, args.eval_placement_band, args.eval_placement_relocation, args.eval_placement_min_anchors,
-                              genomes, by_genome.data(), block_length.data(), block_genome.data(), nb));
-  if (!report.close(&err)) return die("--eval-placement-report: " + err);
-  if (!args.eval_placement_blocks.empty()) {
-    OutFile rows(args.eval_placement_blocks, false);
-    rows.append(asmmap_block_rows(c_words, t_words, hcols, nb));
-    if (!rows.close(&err)) return die("--eval-placement-blocks: " + err);
-  }
-  if (!args.eval_placement_contigs.empty()) {
-    OutFile rows(args.eval_placement_contigs, false);
-    rows.append(asmmap_contig_rows(c_words, hw.data(), hn.data(), hn.data() + nc1, hn.data() + 2 * nc1, hw.data() + nc1, hn.data() + 3 * nc1, nc));
-    if (!rows.close(&err)) return die("--eval-placement-contigs: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_records) + " records, " + n(c.truth_bases) + " bases, " + n(n_anchors) + " unique " + std::to_string(args.eval_placement_k) + "-mers of " +
-       n(genomes.size()) + " genomes as anchors (" + n(c.truth_repeats) + " repeated)");
-  info("Contigs: " + n(c.records) + " records, " + n(c.bases) + " bases, " + n(c.hits) + " anchor hits in " + n(c.blocks) + " blocks; " +
-       n(c.breaks_inter_genome + c.breaks_inter_record + c.breaks_inversion + c.breaks_relocation) + " misassemblies in " + n(c.contigs_misassembled) + " contigs, " +
-       n(c.breaks_local) + " local breaks, " + n(c.contigs_unplaced) + " contigs unplaced");
-  info("Wrote " + args.eval_placement_report);
-  return 0;
-}
-
-// `--eval-bins BINS.tsv --eval-bins-truth CONTIGS.tsv --eval-bins-report OUT`: no simulation.  Both files go up in pieces cut at the
-// last newline (sam_file_pieces).  The host reads every piece once for the names: the truth's contig names and its genomes (the
-// distinct field-8 values other than "."), in a pass in front of the reset, which needs them; the records' bin names, of which a
-// bin's name is the one at its first_record.
-struct BinevalHandle {
-  simmr_bineval* h = nullptr;
-  ~BinevalHandle() { simmr_bineval_destroy(h); }
-};
-static int run_eval_bins(const CliArgs& args) {
-  {
-    FILE* f = fopen(args.eval_bins.c_str(), "rb");
-    if (!f) return die("--eval-bins: cannot open " + args.eval_bins);
-    fclose(f);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  BinevalHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_bineval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-bins: ") + simmr_last_error(eng));
-  std::vector<std::string> t_names, t_genomes, r_bins;
-  std::vector<uint8_t> host;
-  struct Piece { GrowBuf dev; size_t n = 0; };
-  std::vector<std::unique_ptr<Piece>> pieces;
-  info("Parsing " + args.eval_bins_truth);
-  if (int rc = sam_file_pieces("--eval-bins-truth", args.eval_bins_truth, [&](const uint8_t* d, size_t n) {
-        pieces.emplace_back(new Piece());
-        uint8_t* keep = pieces.back()->dev.room(n);
-        host.resize(n);
-        if (!keep || hipMemcpy(keep, d, n, hipMemcpyDeviceToDevice) != hipSuccess || hipMemcpy(host.data(), d, n, hipMemcpyDeviceToHost) != hipSuccess)
-          return die("--eval-bins-truth: device allocation failed");
-        pieces.back()->n = n;
-        bineval_truth_names((const char*)host.data(), n, &t_names, &t_genomes);
-        return 0;
-      }))
-    return rc;
-  std::vector<std::string> genomes;
-  for (const std::string& g : t_genomes)
-    if (g != "." && !g.empty()) genomes.push_back(g);
-  std::vector<std::string>().swap(t_genomes);
-  std::sort(genomes.begin(), genomes.end());
-  genomes.erase(std::unique(genomes.begin(), genomes.end()), genomes.end());
-  std::vector<const char*> gname;
-  for (const std::string& s : genomes) gname.push_back(s.c_str());
-  const simmr_bineval_config cfg{(uint32_t)gname.size(), 64u, gname.data()};
-  if (simmr_bineval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-bins-truth: ") + simmr_last_error(eng));
-  for (const auto& p : pieces)
-    if (simmr_bineval_truth_add(ev.h, (const uint8_t*)p->dev.p, p->n) != SIMMR_OK) return die(std::string("--eval-bins-truth: ") + simmr_last_error(eng));
-  uint64_t n_truth = 0;
-  if (simmr_bineval_truth_plan(ev.h, &n_truth) != SIMMR_OK) return die(std::string("--eval-bins-truth: ") + simmr_last_error(eng));
-  pieces.clear();
-  info("Parsing " + args.eval_bins);
-  if (int rc = sam_file_pieces("--eval-bins", args.eval_bins, [&](const uint8_t* d, size_t n) {
-        if (simmr_bineval_add(ev.h, d, n) != SIMMR_OK) return die(std::string("--eval-bins: ") + simmr_last_error(eng));
-        host.resize(n);
-        // (a copy on the null stream: it ends behind the add's lookups, so the walker may reuse the buffer)
-        if (hipMemcpy(host.data(), d, n, hipMemcpyDeviceToHost) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return die("--eval-bins: copy from the device failed");
-        bineval_record_bins((const char*)host.data(), n, &r_bins);
-        return 0;
-      }))
-    return rc;
-  simmr_bineval_counts c{};
-  static_assert(sizeof(c) == BINEVAL_N_COUNTS * sizeof(uint64_t) && BINEVAL_GENOME_COLS == SIMMR_BINEVAL_GENOME_COLS, "the report names every count and column");
-  std::vector<uint64_t> by_genome((genomes.size() + 1) * BINEVAL_GENOME_COLS);
-  if (simmr_bineval_read(ev.h, &c, by_genome.data()) != SIMMR_OK) return die(std::string("--eval-bins: ") + simmr_last_error(eng));
-  const uint64_t nb = c.bins, nb1 = std::max<uint64_t>(nb, 1), nc = c.cells, nc1 = std::max<uint64_t>(nc, 1), nt = c.truth_records, nt1 = std::max<uint64_t>(nt, 1);
-  // the columns: 64-bit ones in one buffer, 32-bit ones in another, bins then cells then contigs
-  GrowBuf d_wide, d_narrow;
-  const uint64_t n_wide = 3 * nb1 + nc1 + nt1, n_narrow = 3 * nb1 + 3 * nc1 + 3 * nt1;
-  uint64_t* const w = (uint64_t*)d_wide.room(n_wide * 8);
-  uint32_t* const u = (uint32_t*)d_narrow.room(n_narrow * 4);
-  if (!w || !u) return die("--eval-bins: device allocation failed");
-  uint64_t *wb = w, *wc = w + 3 * nb1, *wt = wc + nc1;
-  uint32_t *ub = u, *uc = u + 3 * nb1, *ut = uc + 3 * nc1;
-  if (simmr_bineval_bins(ev.h, ub, wb, wb + nb1, ub + nb1, ub + 2 * nb1, wb + 2 * nb1, nb, nullptr) != SIMMR_OK ||
-      simmr_bineval_cells(ev.h, uc, uc + nc1, uc + 2 * nc1, wc, nc, nullptr) != SIMMR_OK ||
-      simmr_bineval_contigs(ev.h, ut, wt, ut + nt1, ut + 2 * nt1, nt, nullptr) != SIMMR_OK)
-    return die(std::string("--eval-bins: ") + simmr_last_error(eng));
-  std::vector<uint64_t> hw(n_wide);
-  std::vector<uint32_t> hu(n_narrow);
-  if (hipMemcpy(hw.data(), w, n_wide * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hu.data(), u, n_narrow * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    return die("--eval-bins: copy from the device failed");
-  wb = hw.data(); wc = wb + 3 * nb1; wt = wc + nc1;
-  ub = hu.data(); uc = ub + 3 * nb1; ut = uc + 3 * nc1;
-  std::vector<std::string> bin_names;
-  for (uint64_t b = 0; b < nb; b++) {
-    const uint32_t first = ub[nb1 + b];
-    bin_names.push_back(first < r_bins.size() ? r_bins[first] : std::string("?"));
-  }
-  std::string err;
-  OutFile report(args.eval_bins_report, false);
-  report.append(bineval_report((const uint64_t*)&c, genomes, by_genome.data(), bin_names, ub, wb, wb + nb1, ub + 2 * nb1, wb + 2 * nb1, nb));
-  if (!report.close(&err)) return die("--eval-bins-report: " + err);
-  if (!args.eval_bins_bins.empty()) {
-    OutFile rows(args.eval_bins_bins, false);
-    rows.append(bineval_cell_rows(bin_names, genomes, uc, uc + nc1, uc + 2 * nc1, wc, nc));
-    if (!rows.close(&err)) return die("--eval-bins-bins: " + err);
-  }
-  if (!args.eval_bins_contigs.empty()) {
-    OutFile rows(args.eval_bins_contigs, false);
-    rows.append(bineval_contig_rows(t_names, genomes, bin_names, ut, wt, ut + nt1, ut + 2 * nt1, nt));
-    if (!rows.close(&err)) return die("--eval-bins-contigs: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_records) + " contigs, " + n(c.truth_bases) + " bases of " + n(genomes.size()) + " genomes (" + n(c.truth_none) + " contigs of none)");
-  info("Bins: " + n(c.records) + " records: " + n(c.unknown_contig) + " of unknown contigs, " + n(c.repeated) + " repeated; " + n(c.assigned) + " contigs in " +
-       n(c.bins) + " bins, " + n(c.cells) + " cells");
-  info("Wrote " + args.eval_bins_report);
-  return 0;
-}
-
-// `--eval-corrected READS.fastq --eval-corrected-truth TRUTH.sam --eval-corrected-report OUT`: no simulation, no genomes, one engine.
-// The truth goes up in pieces cut at the last newline (sam_file_pieces) through simmr_correval_truth_add; behind the plan the reads go up
-// in pieces cut at a record's end: the host counts the piece's newlines and cuts behind the last one whose number is a multiple of the
-// record's lines.  Nothing is written unless all of it succeeded.
-struct CorrevalHandle {
-  simmr_correval* h = nullptr;
-  ~CorrevalHandle() { simmr_correval_destroy(h); }
-};
-static int record_file_pieces(const std::string& flag, const std::string& path, uint32_t lines_per_record, const std::function<int(const uint8_t*, size_t)>& add) {
-  FILE* f = fopen(path.c_str(), "rb");
-  if (!f) return die(flag + ": cannot open " + path);
-  struct Closer { FILE* f; ~Closer() { fclose(f); } } closer{f};
-  GrowBuf dev;
-  std::vector<uint8_t> piece;
-  size_t have = 0;  // bytes of `piece` read and not yet added: the open last record of the piece before
-  for (bool eof = false; !eof;) {
-    if (piece.size() < have + SAM_PIECE) piece.resize(have + SAM_PIECE);
-    const size_t got = fread(piece.data() + have, 1, SAM_PIECE, f);
-    if (got < SAM_PIECE) {
-      if (ferror(f)) return die(flag + ": cannot read " + path);
-      eof = true;
-    }
-    have += got;
-    size_t cut = have;  // at the end of the file the last line may lack its newline
-    if (!eof) {
-      size_t lines = 0;
-      cut = 0;
-      for (size_t i = 0; i < have; i++)
-        if (piece[i] == '\n' && ++lines % lines_per_record == 0) cut = i + 1;
-      if (cut == 0) continue;  // one record longer than the piece: read on
-    }
-    if (cut > SIMMR_FIT_SAM_MAX_BYTES) return die(flag + ": a record of " + path + " is longer than one add takes");
-    if (cut > 0) {
-      uint8_t* d = dev.room(cut);
-      if (!d) return die(flag + ": device allocation failed");
-      if (hipMemcpy(d, piece.data(), cut, hipMemcpyHostToDevice) != hipSuccess) return die(flag + ": copy to the device failed");
-      if (int rc = add(d, cut)) return rc;
-    }
-    memmove(piece.data(), piece.data() + cut, have - cut);
-    have -= cut;
-  }
-  return 0;
-}
-static int run_eval_corrected(const CliArgs& args) {
-  for (const std::string* path : {&args.eval_corrected_truth, &args.eval_corrected}) {  // (the files are looked at before an engine is made)
-    FILE* f = fopen(path->c_str(), "rb");
-    if (!f) return die(std::string(path == &args.eval_corrected ? "--eval-corrected" : "--eval-corrected-truth") + ": cannot open " + *path);
-    fclose(f);
-  }
-  Engines engines;
-  simmr_engine* eng = nullptr;
-  if (simmr_engine_create(args.device, &eng) != SIMMR_OK) return die(std::string("cannot create engine: ") + simmr_last_error(nullptr));
-  engines.v.push_back(eng);
-  CorrevalHandle ev;  // (declared behind the engines: it goes first)
-  if (simmr_correval_create(eng, &ev.h) != SIMMR_OK) return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
-  const uint32_t lpr = args.eval_corrected_fasta ? 2u : 4u;
-  const simmr_correval_config cfg{lpr, 0u};
-  if (simmr_correval_reset(ev.h, &cfg) != SIMMR_OK) return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
-  float ms = 0;
-  info("Parsing " + args.eval_corrected_truth);
-  if (int rc = sam_file_pieces("--eval-corrected-truth", args.eval_corrected_truth, [&](const uint8_t* d, size_t n) {
-        if (simmr_correval_truth_add(ev.h, d, n) != SIMMR_OK || simmr_last_correval_ms(ev.h, &ms) != SIMMR_OK)  // (the second synchronises)
-          return die(std::string("--eval-corrected-truth: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  uint64_t n_entries = 0;
-  if (simmr_correval_truth_plan(ev.h, &n_entries) != SIMMR_OK) return die(std::string("--eval-corrected-truth: ") + simmr_last_error(eng));
-  info("Parsing " + args.eval_corrected);
-  if (int rc = record_file_pieces("--eval-corrected", args.eval_corrected, lpr, [&](const uint8_t* d, size_t n) {
-        if (simmr_correval_add(ev.h, d, n) != SIMMR_OK || simmr_last_correval_ms(ev.h, &ms) != SIMMR_OK)
-          return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
-        return 0;
-      }))
-    return rc;
-  simmr_correval_counts c{};
-  static_assert(sizeof(c) == CORREVAL_N_COUNTS * sizeof(uint64_t), "the report names every count");
-  static_assert(CORREVAL_N_QUALS == SIMMR_CORREVAL_QUALS && CORREVAL_N_POS == SIMMR_CORREVAL_POS, "the report's rows are the tables'");
-  std::vector<uint64_t> cube(125), by_qual(CORREVAL_N_QUALS * 5), by_pos(CORREVAL_N_POS * 5);
-  if (simmr_correval_read(ev.h, &c, cube.data(), by_qual.data(), by_pos.data()) != SIMMR_OK) return die(std::string("--eval-corrected: ") + simmr_last_error(eng));
-  std::string rows;
-  if (!args.eval_corrected_reads.empty()) {
-    GrowBuf d_key, d_cols;
-    const uint64_t n1 = std::max<uint64_t>(n_entries, 1);
-    uint8_t* k = d_key.room(n1 * 8);
-    uint32_t* u = (uint32_t*)d_cols.room(n1 * 16);
-    if (!k || !u) return die("--eval-corrected-reads: device allocation failed");
-    if (simmr_correval_emit(ev.h, (uint64_t*)k, u, u + n1, u + 2 * n1, u + 3 * n1, n_entries) != SIMMR_OK)
-      return die(std::string("--eval-corrected-reads: ") + simmr_last_error(eng));
-    std::vector<uint64_t> key(n1);
-    std::vector<uint32_t> cols(4 * n1);
-    if (hipMemcpy(key.data(), k, n1 * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(cols.data(), u, n1 * 16, hipMemcpyDeviceToHost) != hipSuccess)
-      return die("--eval-corrected-reads: copy from the device failed");
-    rows = correval_read_rows(key.data(), cols.data(), cols.data() + n1, cols.data() + 2 * n1, cols.data() + 3 * n1, n_entries);
-  }
-  std::string err;
-  OutFile report(args.eval_corrected_report, false);
-  report.append(correval_report((const uint64_t*)&c, cube.data(), by_qual.data(), by_pos.data()));
-  if (!report.close(&err)) return die("--eval-corrected-report: " + err);
-  if (!args.eval_corrected_reads.empty()) {
-    OutFile reads(args.eval_corrected_reads, false);
-    reads.append(rows);
-    if (!reads.close(&err)) return die("--eval-corrected-reads: " + err);
-  }
-  auto n = [](uint64_t v) { return std::to_string((unsigned long long)v); };
-  info("Truth: " + n(c.truth_entries) + " reads (" + n(c.truth_skipped) + " records skipped)");
-  info("Corrected: " + n(c.records) + " records, " + n(c.unknown_read) + " of unknown reads, " + n(c.trimmed_records) + " trimmed, " + n(c.longer_records) + " longer");
-  info("Bases: " + n(c.kept) + " kept, " + n(c.damaged) + " damaged, " + n(c.fixed) + " fixed, " + n(c.left) + " left, " + n(c.miscorrected) + " miscorrected, " +
-       n(c.trimmed_error) + " errors trimmed away");
-  info("Reads: " + n(c.fixed_all) + " fixed, " + n(c.improved) + " improved, " + n(c.unchanged) + " unchanged, " + n(c.worse) + " worse, " + n(c.clean_damaged) +
-       " clean ones damaged, " + n(c.missing) + " without a record");
-  info("Wrote " + args.eval_corrected_report);
   return 0;
 }
 

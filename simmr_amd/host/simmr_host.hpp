@@ -305,6 +305,36 @@ std::string bineval_cell_rows(const std::vector<std::string>& bin_names, const s
 // The rows of --eval-bins-contigs for n truth contigs in truth order: name, length, the genome's name or ".", the bin's name or ".", records.
 std::string bineval_contig_rows(const std::vector<std::string>& names, const std::vector<std::string>& genomes, const std::vector<std::string>& bin_names,
                                 const uint32_t* genome, const uint64_t* length, const uint32_t* bin, const uint32_t* records, size_t n);
+// ---- a file in pieces: what the nine commands that run no simulation read their files with ----
+// Where a piece of a file that has not ended is cut: behind the last '\n' (Newline); in front of the last '>' that begins a line
+// and is not the buffer's first byte (Fasta); behind the last '\n' whose number, counted from the buffer's start, is a multiple of
+// `lines` (Record).
+struct PieceCut {
+  enum Kind { Newline, Fasta, Record } kind = Newline;
+  uint32_t lines = 1;  // of a record (Record only)
+};
+// The cut of the buffer p[0, have) under `rule`; 0: the buffer holds no boundary, read on.
+size_t piece_cut(const uint8_t* p, size_t have, PieceCut rule);
+constexpr size_t FILE_PIECE = 64u << 20;  // bytes of one fread
+// The pieces of a file: next() reads `piece_bytes` at a time until the buffer holds a cut, hands out the bytes in front of it and
+// carries the rest over into the next piece; a line or record longer than a read makes the buffer grow.  At the end of the file the
+// remainder is one piece, whether or not it ends in a newline.  No piece is longer than `max_bytes` (what one add takes): TooLong
+// where a cut passes it, and under Fasta already where the buffer passes it with no cut in sight.
+class PieceReader {
+ public:
+  enum End { Piece, Done, CannotRead, TooLong };
+  PieceReader(FILE* f, PieceCut rule, size_t max_bytes, size_t piece_bytes = FILE_PIECE) : f_(f), rule_(rule), max_(max_bytes), piece_(piece_bytes) {}
+  // Piece: p[0, n) is the next piece, good until the next call; any other answer is the walk's end
+  End next(const uint8_t** p, size_t* n);
+
+ private:
+  FILE* f_;
+  PieceCut rule_;
+  size_t max_, piece_;
+  std::vector<uint8_t> buf_;
+  size_t have_ = 0, cut_ = 0;  // bytes of buf_ read; of those, handed out by the last call
+  bool eof_ = false;
+};
 // `simmr-hip --sam FILE --sam-sorted` over several ranges: every range's lines come sorted from the device
 // (simmr_sam_sort_plan / simmr_sam_sort_emit) with the key and the length of each.  A run is one range's lines: its keys
 // ascend, and its text lies at `offset` of the byte source.

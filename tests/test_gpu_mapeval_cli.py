@@ -75,7 +75,7 @@ def test_refusals(workdir):
 
 
 def test_a_file_of_more_than_one_piece(workdir):
-    """sam_file_pieces' carry (main.cpp): a file just over SAM_PIECE whose cut falls inside a line, against itself, so the truth's
+    """The file walker's carry (PieceReader): a file just over FILE_PIECE whose cut falls inside a line, against itself, so the truth's
     and the aligner's walk both carry an open line over; then the same file without its last newline"""
     import re
 
@@ -84,7 +84,7 @@ def test_a_file_of_more_than_one_piece(workdir):
     from tests import _seams
     from tests.test_gpu_cli import ROOT
     d, _ = workdir
-    piece = re.search(r"SAM_PIECE = (\d+)u? << (\d+)", (ROOT / "simmr_amd" / "host" / "main.cpp").read_text())
+    piece = re.search(r"FILE_PIECE = (\d+)u? << (\d+)", (ROOT / "simmr_amd" / "host" / "simmr_host.hpp").read_text())
     piece = int(piece.group(1)) << int(piece.group(2))
     header = b"@HD\tVN:1.6\n@SQ\tSN:a\tLN:100000\n@SQ\tSN:b\tLN:100000\n@SQ\tSN:c\tLN:100000\n"
     width = 38  # 7 + 3 + 1 + 4 + 3 + 4 bytes of fields, 16 of tabs, the fixed fields and the newline

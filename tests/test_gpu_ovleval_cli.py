@@ -93,11 +93,11 @@ def test_refusals(run):
 
 
 def test_a_file_of_more_than_one_piece(run):
-    """sam_file_pieces' carry (main.cpp): a file just over SAM_PIECE whose cut falls inside a line, against itself, so the truth's
+    """The file walker's carry (PieceReader): a file just over FILE_PIECE whose cut falls inside a line, against itself, so the truth's
     and the candidate's walk both carry an open line over; then the same file without its last newline.  The tables are those of
     the Python path, which takes the text in one add."""
     d = run
-    piece = re.search(r"SAM_PIECE = (\d+)u? << (\d+)", (ROOT / "simmr_amd" / "host" / "main.cpp").read_text())
+    piece = re.search(r"FILE_PIECE = (\d+)u? << (\d+)", (ROOT / "simmr_amd" / "host" / "simmr_host.hpp").read_text())
     piece = int(piece.group(1)) << int(piece.group(2))
     width = len(rec(1_000_000, 5000, 1000, 3000, "+", 1_000_001, 5000, 1000, 3000, tail=(2000, 2000, 255)))
     n = piece // width + 3000
