@@ -272,7 +272,12 @@ int simmr_engine_set_plan_overlap(simmr_engine* e, int on);
  * shared/src/encoding.rs:146-152) plus a 1-bit exception plane for 'N' / '-'.
  * contig_len[i] = bytes in contig_ascii[i] (Seq.seq.len()),
  * contig_size[i] = Seq.size (differs only under --contiguous, genome.rs:127);
- * NULL means size == len. */
+ * NULL means size == len.
+ * A contig may have no bases (contig_len[i] == 0): it is staged and keeps its index, and it shares its
+ * first base in the plane and its first position in depth[] with the contig behind it, which owns both.
+ * simmr_depth_summarize gives it a row of zeros and no windows, no region (simmr_regions_*) and no site
+ * (simmr_strain_*) is ever on it, and of the reads simmr_depth_add is given only one of length 0 at its
+ * offset 0 stays inside it (tests/test_gpu_layout_seams.py). */
 int simmr_stage_genome(simmr_engine* e, uint32_t genome_idx, uint32_t n_contigs,
                        const uint8_t* const* contig_ascii, const uint64_t* contig_len,
                        const uint64_t* contig_size);

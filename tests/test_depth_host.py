@@ -99,6 +99,54 @@ def test_model_equals_a_read_by_read_loop():
                 assert int(s["win_sum"][a:b].sum()) == int(s["depth_sum"][k]) and int(s["win_max"][a:b].max(initial=0)) == int(s["depth_max"][k])
 
 
+def summary_loop(d, lens, window):
+    """_depth.summary window by window and position by position, in plain Python"""
+    out = {k: [] for k in ("first", "len", "covered", "depth_sum", "depth_max", "first_window", "win_sum", "win_covered", "win_max")}
+    hist, x = [0] * _depth.HIST_BINS, 0
+    for g in sorted(lens):
+        for n in lens[g]:
+            vals = [int(v) for v in d[x:x + n]]
+            out["first"].append(x)
+            out["len"].append(n)
+            out["covered"].append(sum(1 for v in vals if v))
+            out["depth_sum"].append(sum(vals))
+            out["depth_max"].append(max(vals, default=0))
+            out["first_window"].append(len(out["win_sum"]) if window else 0)
+            for v in vals:
+                hist[min(v, _depth.HIST_BINS - 1)] += 1
+            for a in range(0, n, window) if window else ():
+                w = vals[a:a + window]
+                out["win_sum"].append(sum(w))
+                out["win_covered"].append(sum(1 for v in w if v))
+                out["win_max"].append(max(w))
+            x += n
+    out["hist"] = hist
+    return out
+
+
+@pytest.mark.parametrize("name", ["fragmented", "seam-1", "seam+0", "seam+3", "empty-1", "empty+0", "empty+2"])
+def test_models_on_the_seam_layouts(name):
+    """the layouts of tests/test_gpu_layout_seams.py (the fragmented one with fewer contigs: the loops are slow): depth[] against
+    the read-by-read loop and the summary against a plain loop per window, empty contigs included"""
+    from tests import test_gpu_layout_seams as seams
+    lens = seams.layout_lens(name, tiles_before=2, cycles_after=20) if name == "fragmented" else seams.layout_lens(name)
+    flat = [x for g in sorted(lens) for x in lens[g]]
+    cols = seams.layout_reads(lens, np.random.default_rng(4), 1500)
+    d = _depth.depth(cols, lens)
+    assert np.array_equal(d, _depth.depth_loop(cols, lens)) and d.size == sum(flat) and d.min() >= 2
+    L = np.abs(cols["end"].astype(np.int64) - cols["start"].astype(np.int64))
+    assert (L == 0).sum() == flat.count(0) and int(L.sum()) == int(d.sum())
+    for w in (0, 1, 3, 64, seams.TILE, max(flat) + 1):
+        s, want = _depth.summary(d, lens, w), summary_loop(d, lens, w)
+        for k, v in want.items():
+            if w or not k.startswith("win_"):
+                assert s[k].tolist() == v, (name, w, k)
+        assert int(s["hist"].sum()) == d.size and ("win_sum" in s) == bool(w)
+        for k in np.flatnonzero(np.array(flat) == 0):  # an empty contig: a row of zeros and no windows
+            assert s["len"][k] == s["covered"][k] == s["depth_sum"][k] == s["depth_max"][k] == 0
+            assert k + 1 == len(flat) or s["first_window"][k] == s["first_window"][k + 1]
+
+
 def test_tsv_writers_equal_the_python_formatter(host_lib, tmp_path):
     rng = np.random.default_rng(7)
     lens = {0: [1000, 37], 1: [5, 0, 300]}

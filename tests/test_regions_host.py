@@ -101,6 +101,40 @@ def test_model_equals_a_position_by_position_loop():
     assert full["len"].tolist() == [700, 1, 37, 5, 300, 1, 64] and full["contig"].tolist() == [0, 1, 2, 0, 2, 3, 0]  # (the empty contig has no region)
 
 
+def test_the_seam_layouts_are_what_their_cases_need():
+    from tests import test_gpu_layout_seams as seams
+    seams.test_the_layouts_are_what_the_cases_need()  # (plain arithmetic on the kernels' constants: checked without a GPU too)
+
+
+@pytest.mark.parametrize("name", ["fragmented", "seam-1", "seam+0", "seam+3", "empty-1", "empty+0", "empty+2"])
+def test_model_equals_the_loop_on_the_seam_layouts(name):
+    """the layouts and the depth arrays of tests/test_gpu_layout_seams.py (the fragmented one with fewer contigs: the loop is
+    slow), empty contigs included"""
+    from tests import test_gpu_layout_seams as seams
+    lens = seams.layout_lens(name, tiles_before=2, cycles_after=20) if name == "fragmented" else seams.layout_lens(name)
+    flat = [x for g in sorted(lens) for x in lens[g]]
+    g, c, first = _regions.layout(lens)
+    n = int(first[-1])
+    rows = {x: k for k, x in enumerate(zip(g.tolist(), c.tolist()))}
+    rng = np.random.default_rng(6)
+    cases = [("all covered", np.full(n, 2, dtype=np.uint32), 2, 1)]
+    for p in (0.5, 0.95):
+        d = (rng.random(n) < p).astype(np.uint32) * rng.integers(1, 9, n).astype(np.uint32)
+        cases += [((p, ml), d, 1, ml) for ml in (1, 2)]
+    for what, d in seams.boundary_depths(first, n).items():
+        cases += [((what, ml), d, 1, ml) for ml in (1, 2)]
+    big, k = seams.large_depths(lens, first, n, rng)
+    cases += [(("large", hex(md)), big, md, 1) for md in (1, 0x80000000, 0xFFFFFFFF)]
+    for what, d, md, ml in cases:
+        a, b = _regions.regions(d, lens, md, ml), _regions.regions_loop(d, lens, md, ml)
+        _regions.assert_regions(a, b, (name, what))
+        assert int(a["seq_off"][-1]) == int(a["len"].sum()) and (a["len"] >= ml).all()
+        row = np.array([rows[x] for x in zip(a["genome"].tolist(), a["contig"].tolist())], dtype=np.int64)
+        assert (a["start"] + a["len"] <= np.array(flat, dtype=np.uint64)[row]).all()  # inside its contig: never an empty contig's
+    full = _regions.regions(cases[0][1], lens, 2, 1)
+    assert full["len"].tolist() == [x for x in flat if x] and int(_regions.regions(big, lens, 0xFFFFFFFF)["depth_sum"][0]) == 0xFFFFFFFF * flat[k] > 1 << 32
+
+
 def gold_files(host_lib, r, seq, names, fasta_path, tsv_path):
     n = len(r["genome"])
     cols = [np.ascontiguousarray(r[k]) for k, _ in _regions.COLUMNS]
