@@ -125,3 +125,124 @@ def test_gpu_truth_test_is_sized_from_the_kernels_constants():
     assert defines["TRUTH_WG_READS"] == test_gpu_truth.TRUTH_WG_READS
     assert defines["TRUTH_WGS_PER_CU"] == test_gpu_truth.TRUTH_WGS_PER_CU
     assert defines["TRUTH_LANES"] * defines["TRUTH_WG_READS"] == 256  # one workgroup: a row of lanes per read
+
+
+# ---- the builders of tests/_truth_cases.py, which tests/test_gpu_truth_seams.py runs through the pass -------------------------------
+def test_seam_cases_are_sized_from_the_sources():
+    """tests/_truth_cases.py reads its constants out of truth_kernels.hip and kernels.hip; the geometry it derives from them is the
+    geometry the sources use them for."""
+    from tests import _truth_cases as tc
+    csrc = ROOT / "simmr_amd" / "csrc"
+    kern, scan, eng, host = ((csrc / f).read_text() for f in ("truth_kernels.hip", "kernels.hip", "engine.hip", "truth_host.hpp"))
+    K = tc.constants()
+    assert tuple(K) == tc.CONSTANTS and (tc.LANES, tc.WG_READS, tc.WGS_PER_CU, tc.SCAN_THREADS, tc.SCAN_ITEMS) == tuple(K.values())
+    assert K["TRUTH_LANES"] * K["TRUTH_WG_READS"] == 256 and "__launch_bounds__(256)\nk_truth(" in kern
+    # a lane's window is 16 bases, a round TRUTH_LANES of them; workgroups step by the grid, which row_grid caps
+    assert "g0 += TRUTH_LANES" in kern and "(L + 15u) >> 4" in kern and tc.GROUP == 16 and tc.ROUND == 16 * K["TRUTH_LANES"] == 256
+    assert "batch += gridDim.x" in kern and "batch * TRUTH_WG_READS + row" in kern
+    assert "(n_reads + TRUTH_WG_READS - 1) / TRUTH_WG_READS" in host and "(uint64_t)eng_cu_count(e) * wgs_per_cu" in host
+    assert "row_grid(e, n_reads, TRUTH_WGS_PER_CU)" in (csrc / "truth.hip").read_text()
+    # the scan: SCAN_THREADS * SCAN_ITEMS counts a workgroup, SCAN_THREADS of their sums per trip of k_scan_tops
+    assert "per_wg = SCAN_THREADS * SCAN_ITEMS" in eng and "base < n_wg; base += SCAN_THREADS" in scan
+    assert tc.SCAN_TILE == K["SCAN_THREADS"] * K["SCAN_ITEMS"]
+    for cus in (1, 64, 256, 304):
+        n = tc.tiny_n(cus)
+        for m, last in ((n, 5), (n - 5, tc.WG_READS)):
+            s = tc.tiny_shape(m, cus)
+            assert s.trips >= 3 and (s.trips == 3) == (cus >= 256) and s.last == last and s.batches - 1 >= 2 * s.grid and s.scan_tiles > K["SCAN_THREADS"] + 1
+
+
+def test_dense_reads_are_all_edits(oracle):
+    from tests import _truth_cases as tc
+    genomes = tc.host_genomes()
+    case = tc.dense_reads(oracle)
+    m = _truth.model(oracle, case.host, genomes)
+    off = m["edit_off"].astype(np.int64)
+    seen = []
+    for r, kind in enumerate(case.kinds):
+        pos = m["edit_pos"][off[r]:off[r + 1]]
+        if kind == "dense":
+            assert m["nm"][r] == case.L[r] and np.array_equal(pos, np.arange(case.L[r]))
+            assert np.array_equal(m["edit_qual"][off[r]:off[r + 1]], tc.qual_of(case.L[r], r))
+            if case.L[r] >= 33:
+                assert np.unique(m["edit_alt"][off[r]:off[r + 1]]).size >= 5   # three steps, N and lower case
+            seen.append((int(case.L[r]), int(case.host["flags"][r])))
+        else:
+            assert pos.tolist() == ([] if kind == "clean" else [0])
+    assert sorted(set(seen)) == sorted((L, rev) for L in tc.DENSE_LENGTHS for rev in (0, 1))
+    assert case.kinds[::3] == len(case.kinds) // 3 * ["dense"] and int(m["nm"].max()) == 65535
+    assert {int(g) for g, k in zip(case.host["genome"], case.kinds) if k == "dense"} == {tc.BIG, tc.RANDOM, tc.HOMOPOLYMER}
+    # stepped_each is tests/_stats_cases.stepped over arrays
+    want = np.frombuffer(b"ACGTTGCA", dtype=np.uint8)
+    steps = np.array([1, 2, 3, 1, 2, 3, 1, 2])
+    assert tc.stepped_each(want, steps).tolist() == [tc.sc.stepped(b, s) for b, s in zip(want, steps)]
+
+
+def test_overlap_reads_edit_exactly_the_overlapped_bytes(oracle):
+    from tests import _truth_cases as tc
+    case = tc.overlap_reads(oracle)
+    m = _truth.model(oracle, case.host, tc.host_genomes())
+    off = m["edit_off"].astype(np.int64)
+    L = np.diff(case.host["seq_off"].astype(np.int64))
+    assert sorted(set(L.tolist())) == list(tc.OVERLAP_LENGTHS) == [17, 18, 31, 33, 47, 255, 257, 513]
+    for r, at in enumerate(case.at):
+        assert np.array_equal(m["edit_pos"][off[r]:off[r + 1]], at), r
+        owned = 16 * (L[r] // 16)
+        pattern = "abc"[r % 3]
+        lo, hi = {"a": (L[r] - 16, owned), "b": (owned, L[r]), "c": (L[r] - 16, L[r])}[pattern]
+        assert at.tolist() == list(range(lo, hi)) and at.size == {"a": 16 - L[r] % 16, "b": L[r] % 16, "c": 16}[pattern]
+    assert set(zip(L.tolist(), case.host["flags"].tolist())) == {(n, rev) for n in tc.OVERLAP_LENGTHS for rev in (0, 1)}
+
+
+def test_long_reads_pass_65535_with_a_dense_stretch(oracle):
+    from tests import _truth_cases as tc
+    case = tc.long_reads(oracle)
+    m = _truth.model(oracle, case.host, tc.host_genomes())
+    off = m["edit_off"].astype(np.int64)
+    L = np.diff(case.host["seq_off"].astype(np.int64))
+    assert L.tolist() == [65536, 65536, 65537, 65537, 70000, 70000] and case.host["flags"].tolist() == [0, 1, 0, 1, 0, 1]
+    assert (case.host["contig"] == tc.LONG_CONTIG).all() and (np.maximum(case.host["start"], case.host["end"]) <= 70000).all()
+    for r, at in enumerate(case.at):
+        pos = m["edit_pos"][off[r]:off[r + 1]].astype(np.int64)
+        assert np.array_equal(pos, at) and 65535 in pos and np.isin(np.arange(0, L[r], 251), pos).all()
+        b = min(L[r], 65700)
+        run = pos[(pos >= b - 300) & (pos < b)]
+        assert np.array_equal(run, np.arange(b - 300, b)) and run[0] < 65535 <= run[-1]  # 300 edits in a row over 65 535
+        assert any(run[0] < e <= run[-1] for e in range(256, L[r], 256))       # ... with the start of a round inside
+        assert (pos > 65535).any() == (L[r] > 65536)
+    assert int(m["edit_pos"].max()) == 69999
+
+
+def test_the_assembler_of_the_tiny_reads_is_the_model(oracle):
+    """tests/_truth_cases.assembled puts the expectation of the grid case together from the models of four 16-read units; here it is
+    held to tests/_truth.model run over every read of the tiled host columns, with a partial and with a whole last batch."""
+    from tests import _truth_cases as tc
+    genomes = tc.host_genomes()
+    units = tc.tiny_units(oracle)
+    models = [_truth.model(oracle, u, genomes) for u in units]
+    assert len({int(m["nm"].sum()) for m in models}) == len(units) == 4 and not models[0]["nm"].any()
+    k = 301
+    order = tc.unit_order(k, len(units))
+    assert set(order.tolist()) == {0, 1, 2, 3}
+    for cus in (64, 256, 304):  # a batch, or a trip of the grid, later is another unit more often than not
+        long_order = tc.unit_order(3 * cus * tc.WGS_PER_CU, len(units))
+        for shift in (1, cus * tc.WGS_PER_CU, 2 * cus * tc.WGS_PER_CU):
+            assert (long_order[shift:] != long_order[:-shift]).mean() > 0.5
+    for n in (k * 16 - 11, k * 16 - 16 + 1, k * 16):
+        host = tc.host_sequenced(units, order, n)
+        assert len(host["start"]) == n and host["seq"].size == int(host["seq_off"][n])
+        want = _truth.model(oracle, host, genomes)
+        _truth.assert_truth(tc.assembled(models, order, n), want, f"{n} tiny reads")
+        assert want["nm"].sum() > 0
+
+
+def test_small_reads_hold_what_they_say(oracle):
+    from tests import _truth_cases as tc
+    genomes = tc.host_genomes()
+    case = tc.small_reads(oracle)
+    m = _truth.model(oracle, case.host, genomes)
+    assert m["nm"].tolist() == case.planned
+    h = case.host
+    assert int(h["end"][3]) == int(h["start"][6]) == case.clen and h["flags"][3] == 0 and h["flags"][6] == 1
+    assert int(h["start"][4]) == int(h["end"][4]) == case.clen and h["seq_off"][4] == h["seq_off"][5]
+    assert tc.UNSTAGED not in genomes and case.clen == genomes[tc.RANDOM].contigs[tc.EDGE_CONTIG].size
